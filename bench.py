@@ -2,6 +2,7 @@
 """bench.py -- particle-steps/sec of the bootstrap-filter hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5|dt|smc2|c5dt] [--scaling weak|strong]
+                    [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input = one
 log_likelihood(N, y, model) call (src/particles.jl:132-147) for every filter on the rank.
@@ -21,9 +22,15 @@ Whole-sampler workloads (every EXECUTED inner particle-step counted, SURVEY 8d; 
   c5dt   density_tempered over UCSV with the example's prior = BASELINE configs[4]
 --scaling weak (default): N_theta = 512 per GPU.  --scaling strong: N_theta fixed (--n-theta, default 4096:
 north_star "SMC^2 N_theta = 4096"), split evenly over the ranks.
-With the default filter workload the JSON line also carries "aux": the two strong-scaling sampler runs
-(smc2 and c5dt at N_theta = 4096) measured after the timed region, so that the driver's N = 1,2,4,8 sweep
-yields the north_star scaling curve too (--no-aux skips them).
+
+A plain run sets up, warms up, times --steps steps and prints the line; "roofline" and "cpu_baseline" are null.
+--full adds the secondary measurements after the timed region: the roofline of the dominant kernel (its own
+event-bracketed launches), the CPU baseline (the oracle on a bounded sample, --no-cpu-baseline skips it) and, with a
+filter workload, "aux": the two strong-scaling sampler runs (smc2 and c5dt at N_theta = 4096), so that the driver's
+N = 1,2,4,8 sweep yields the north_star scaling curve too (--no-aux skips them).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy
+(float64): a filter workload's logZ and final particles x and weights w, a sampler's theta, logZ and omega.
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Launching.  Under torch.distributed.run (RANK/WORLD_SIZE set) this file is one rank.  A bare
 `python bench.py --gpus N` (N > 1, no WORLD_SIZE) makes THIS process a launcher: before anything touches
@@ -93,8 +100,13 @@ def parse_args(argv=None):
     ap.add_argument("--n-theta", type=int, default=4096, help="total parameter particles of a strong-scaling sampler run")
     ap.add_argument("--window", type=int, default=16, help="smc2: propagation steps per device call (smc2_run); 1 = one smc2! per call")
     ap.add_argument("--seg", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-aux", action="store_true", help="skip the strong-scaling sampler runs appended to a filter workload's line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the roofline, the CPU baseline and (filter workloads) the "
+                         "strong-scaling sampler runs; a plain run measures only the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-aux", action="store_true", help="--full: skip the strong-scaling sampler runs appended to a filter workload's line")
     ap.add_argument("--resampler", default="multinomial", choices=["multinomial", "systematic"],
                     help="multinomial = the reference's resample (default, the judged configuration); systematic = opt-in "
                          "variant (SMC_FLAG_SYSTEMATIC), reported in config.resampler")
@@ -192,7 +204,7 @@ def main(argv=None):
             ctx.dist.destroy_process_group()
         return
     if args.workload in SAMPLERS:
-        out = bench_sampler(args, ctx, args.workload, args.scaling, args.steps, args.warmup)
+        out = bench_sampler(args, ctx, args.workload, args.scaling, args.steps, args.warmup, dump=args.dump_outputs)
     else:
         out = bench_filter(args, ctx)
     if ctx.rank == 0:
@@ -257,12 +269,16 @@ def bench_filter(args, ctx):
 
     psteps = float(nth) * nx * T * args.steps * world
     value = psteps / elapsed
+    if args.dump_outputs and rank == 0:
+        # before the roofline: its event-bracketed launches advance the same filters
+        x, w, _ = h.state(want_anc=False)
+        dump_outputs(args.dump_outputs, logZ=logZ, x=x, w=w)
 
     # ---- roofline of the dominant kernel -----------------------------------------------------
     d = {1: 1, 2: 1, 3: 3}[model]
     bytes_per_pstep = 32 + 16 * d                      # 48 B (d=1), 80 B (d=3)
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         if h.resident:
             # one k_resident launch does the whole series: HIP-event time of the call
             ms = dev_ms / args.steps
@@ -310,7 +326,7 @@ def bench_filter(args, ctx):
 
     # ---- CPU baseline: the oracle (scalar port of particles.jl), bounded sample -----------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, h, model, raw, raws, nth, nx, T, y)
 
     h.close()
@@ -328,11 +344,20 @@ def bench_filter(args, ctx):
             "device_ms_per_step": dev_ms / args.steps,
             "roofline": roof, "cpu_baseline": cpu,
         }
-    if not args.no_aux:
+    if args.full and not args.no_aux:
         aux = run_aux(args, ctx)
         if out is not None:
             out["aux"] = aux
     return out
+
+
+def dump_outputs(d, **arrays):
+    """DIR/<name>.npy in float64 for every array (at most 64 MB in all: every workload's outputs fit whole)"""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def cpu_baseline(args, h, model, raw, raws, nth, nx, T, y):
@@ -438,7 +463,7 @@ def sampler_setup(algo):
     return y, prior, mod, tmap
 
 
-def bench_sampler(args, ctx, algo, scaling, steps, warmup):
+def bench_sampler(args, ctx, algo, scaling, steps, warmup, dump=None):
     """Whole sampler, N_theta x Nx = 1024, T = 200, chain = 3, ess_threshold = 0.5 (README.md:98).
     "dt": density_tempered (src/smc_samplers.jl:222-281) on the README LG model; "c5dt": the same over UCSV with the
     example's prior (BASELINE configs[4]); "smc2": the online SMC^2 run of BASELINE configs[3] (smc2 then smc2! for
@@ -484,6 +509,8 @@ def bench_sampler(args, ctx, algo, scaling, steps, warmup):
         skipped += s.psteps_skipped
     ctx.barrier()
     elapsed = ctx.max_over_ranks(time.perf_counter() - t0)
+    if dump and ctx.rank == 0:
+        dump_outputs(dump, theta=s.theta, logZ=s.logZ, omega=s.omega)
     out = None
     if ctx.rank == 0:
         names = {"dt": "density_tempered LG (README.md:81-98)", "smc2": "online SMC^2 LG (BASELINE configs[3])",

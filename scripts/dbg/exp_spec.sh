@@ -4,7 +4,7 @@
 for lib in "" _r7 _f _r7f; do
   if [ -z "$lib" ]; then unset SMC_LIB; else export SMC_LIB=$PWD/sequential_monte_carlo_amd/csrc/build_exp/libsmchip_exp$lib.so; fi
   for wl in c2 c4; do
-    python bench.py --workload $wl --no-aux --no-cpu-baseline 2>/dev/null | python -c "
+    python bench.py --full --workload $wl --no-aux --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

@@ -1,9 +1,10 @@
-import sys, io, time
-sys.path.insert(0, "/root/repo")
+import os, sys, io, time
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
 import importlib.util
 import numpy as np
 import sequential_monte_carlo_amd as smc
-spec = importlib.util.spec_from_file_location("bench", "/root/repo/bench.py"); b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py")); b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
 y, prior, mod, tmap = b.sampler_setup("dt")
 backend = smc.smc_samplers.HipBackend()
 for M in (100, 256, 512, 768, 1024, 2048):

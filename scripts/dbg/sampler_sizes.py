@@ -1,11 +1,12 @@
 """The samplers at state-particle counts other than 1024 (examples/inflation_example.jl:256 runs SMC(8192, 512, ...) on UCSV):
 density_tempered and the online loop over multi-segment inner filters - do they run, how long."""
-import sys, io, time
-sys.path.insert(0, "/root/repo")
+import os, sys, io, time
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
 import importlib.util
 import numpy as np
 import sequential_monte_carlo_amd as smc
-spec = importlib.util.spec_from_file_location("bench", "/root/repo/bench.py"); b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py")); b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
 for algo, N, M, T in (("c5dt", 8192, 128, 100), ("c5dt", 1024, 128, 100), ("dt", 8192, 128, 100), ("dt", 16384, 64, 100), ("smc2", 4096, 64, 60), ("c5smc2", 8192, 32, 40)):
     y, prior, mod, tmap = b.sampler_setup("c5dt" if algo.startswith("c5") else "dt")
     y = y[:T]

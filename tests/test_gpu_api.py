@@ -840,12 +840,12 @@ def test_online_smc2_posterior_matches_density_tempered_and_exact():
 
 
 def test_bench_line_contract():
-    """`python bench.py` prints ONE JSON line with the driver's keys, `roofline` (live event brackets) and `cpu_baseline`
+    """`python bench.py --full` prints ONE JSON line with the driver's keys, `roofline` (live event brackets) and `cpu_baseline`
     (the oracle on a bounded sample): run as the driver runs it, in a fresh process."""
     import json
     import subprocess
     import sys
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-aux"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--no-aux"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -862,3 +862,35 @@ def test_bench_line_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 1e6 and "sample" in c
 
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `python bench.py` (no --full) times exactly --steps steps and prints the headline line alone (roofline and
+    cpu_baseline null, no aux); --dump-outputs writes what the last timed step computed in float64 - the logZ the line quotes
+    and the final cloud of the filter, a sampler's theta, logZ and omega - identically from two runs with the same arguments."""
+    import json
+    import subprocess
+    import sys
+    shapes = {"c2": {"logZ": (1,), "x": (1, 1, 1 << 20), "w": (1, 1 << 20)}, "dt": {"logZ": (512,), "theta": (512, 3), "omega": (512,)}}
+    for wl, shape in shapes.items():
+        runs = []
+        for k in range(2):
+            dump = tmp_path / ("%s%d" % (wl, k))
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--steps", "2", "--warmup", "1",
+                                  "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600)
+            assert out.returncode == 0, out.stderr[-2000:]
+            lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+            assert len(lines) == 1
+            d = json.loads(lines[0])
+            assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f64"
+            assert d["roofline"] is None and d["cpu_baseline"] is None and "aux" not in d
+            got = {n: np.load(str(dump / (n + ".npy"))) for n in shape}
+            assert sorted(os.listdir(dump)) == sorted(n + ".npy" for n in shape)
+            for n, a in got.items():
+                assert a.dtype == np.float64 and a.shape == shape[n] and np.all(np.isfinite(a)), n
+            if wl == "c2":
+                assert got["logZ"][0] == d["config"]["logZ_rank0_theta0"] and abs(got["w"].sum() - 1) < 1e-9
+            else:
+                assert abs(got["omega"].sum() - 1) < 1e-9
+            runs.append(got)
+        for n in shape:
+            assert np.array_equal(bits(runs[0][n]), bits(runs[1][n])), (wl, n)
