@@ -107,8 +107,13 @@ int smc_permute(smc_handle h, const int32_t* a /*[n_theta]*/);
 int smc_copy_from(smc_handle dst, smc_handle src, const uint8_t* mask /*[n_theta]*/);
 
 /* Proposals outside the prior's support: the reference never filters them (src/smc_samplers.jl:116).  Filters m with
- * skip[m] != 0 are left out by the following smc_log_likelihood calls (their logZ reads -inf, their state is not
- * touched); NULL runs every filter again. */
+ * skip[m] != 0 are left out by the following smc_log_likelihood calls; NULL runs every filter again.  What such a call
+ * leaves for a skipped filter m, on every launch path:
+ *   logZ[m] (returned and smc_get_logZ)         -inf;
+ *   logmu_trace / ess_trace column m            NaN at every step;
+ *   smc_get_summaries rows of m (q, mean, var)  NaN at every step;
+ *   x, w, ancestors and raw weights of slot m   what they were before the call, bit for bit.
+ * The mask applies to smc_log_likelihood only: the step API and smc_step_window run every filter. */
 int smc_set_skip(smc_handle h, const uint8_t* skip /*[n_theta] or NULL*/);
 
 /* ---- rejuvenate!(smc, y, xi) on the device: src/smc_samplers.jl:103-146 -------------------------

@@ -483,7 +483,8 @@ class Handle:
         check(lib().smc_copy_from(self._h, src._h, m.ctypes.data_as(C.POINTER(C.c_uint8))))
 
     def set_skip(self, skip):
-        """filters the following log_likelihood calls leave out (logZ = -inf); None: run all again"""
+        """filters the following log_likelihood calls leave out; None: run all again.  A skipped filter reads logZ = -inf,
+        NaN in its trace columns and summary rows, and keeps its x, w, ancestors and raw weights (include/smc_hip.h)"""
         if skip is None:
             check(lib().smc_set_skip(self._h, None))
             return

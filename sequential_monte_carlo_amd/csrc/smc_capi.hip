@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <algorithm>
 #include <map>
@@ -62,6 +63,8 @@ struct smc_filter_s {
     unsigned char* d_skip = nullptr;           // smc_set_skip: filters log_likelihood leaves out
     int32_t* d_order = nullptr;                //   and the order the one-workgroup-per-filter kernel takes them in: [ntheta] | n_active
     bool skip_on = false;
+    std::vector<uint8_t> h_skip;               //   host copy of the mask: the skipped filters' trace columns and summary rows are set to NaN on the host
+    std::vector<uint8_t> sum_skip;             //   the mask of the call whose summaries smc_get_summaries hands over (empty: none)
     // per-step summaries inside the multi-step calls (smc_set_summaries / smc_get_summaries)
     int sum_np = 0, sum_comp = 0, sum_mom = 0;
     uint64_t sum_p64[QMAX] = {};
@@ -830,6 +833,19 @@ extern "C" int smc_get_summaries(smc_handle h, int64_t T, double* q, double* mea
     if (q) HIPCHK(hipMemcpy(q, h->d_sum_q, (size_t)T * nth * h->sum_np * 8, hipMemcpyDeviceToHost));
     if (mean) HIPCHK(hipMemcpy2D(mean, nout * 8, h->d_sum_m, 2 * nout * 8, nout * 8, (size_t)T, hipMemcpyDeviceToHost));
     if (var) HIPCHK(hipMemcpy2D(var, nout * 8, h->d_sum_m + nout, 2 * nout * 8, nout * 8, (size_t)T, hipMemcpyDeviceToHost));
+    if (!h->sum_skip.empty()) {   // filters the call left out have no summaries: NaN (the device rows hold whatever was there)
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (size_t m = 0; m < nth; ++m) {
+            if (!h->sum_skip[m]) continue;
+            for (int64_t t = 0; t < T; ++t) {
+                if (q) for (int j = 0; j < h->sum_np; ++j) q[((size_t)t * nth + m) * h->sum_np + j] = nan;
+                for (int c = 0; c < h->d; ++c) {
+                    if (mean) mean[(size_t)t * nout + (size_t)c * nth + m] = nan;
+                    if (var) var[(size_t)t * nout + (size_t)c * nth + m] = nan;
+                }
+            }
+        }
+    }
     return SMC_OK;
 }
 
@@ -925,13 +941,24 @@ extern "C" int smc_log_likelihood(smc_handle h, const double* y, int64_t T, doub
     const bool summ = summaries_on(h);
     if (summ && (rc = ensure_summaries(h, T))) return rc;
     h->sum_T = 0;
+    h->sum_skip.clear();
     HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
     if (h->skip_on) { h->v.skip = h->d_skip; h->v.order = h->d_order; h->v.n_active = h->d_order + h->v.ntheta; }
+    const int cur0 = h->cur;   // where the state of the filters the call leaves out stays
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     rc = enqueue_log_likelihood(h, y[0], T, want_trace, summ);
     h->v.skip = nullptr; h->v.order = nullptr; h->v.n_active = nullptr;
     if (rc) return rc;
-    if (summ) h->sum_T = T;
+    if (h->skip_on && h->cur != cur0) {   // the call ends in the other buffer: the skipped filters' untouched state goes with it
+        const FilterView& v = h->v;
+        hipLaunchKernelGGL(k_copy_slots, dim3((unsigned)((v.npad + 255) / 256), v.ntheta), dim3(256), 0, h->stream, v, h->cur, v, cur0,
+                           h->d, h->d_skip);
+        HIPCHK(hipGetLastError());
+    }
+    if (summ) {
+        h->sum_T = T;
+        if (h->skip_on) h->sum_skip = h->h_skip;
+    }
     rc = finish_timing(h, logZ);
     if (rc) return rc;
     if (h->h_perr && *h->h_perr) {
@@ -943,6 +970,17 @@ extern "C" int smc_log_likelihood(smc_handle h, const double* y, int64_t T, doub
     }
     if (logmu_trace) HIPCHK(hipMemcpy(logmu_trace, h->d_tr_logmu, (size_t)T * h->v.ntheta * 8, hipMemcpyDeviceToHost));
     if (ess_trace) HIPCHK(hipMemcpy(ess_trace, h->d_tr_ess, (size_t)T * h->v.ntheta * 8, hipMemcpyDeviceToHost));
+    if (h->skip_on && want_trace) {   // filters the call left out have no steps: NaN in their trace columns
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        const size_t nt = (size_t)h->v.ntheta;
+        for (size_t m = 0; m < nt; ++m) {
+            if (!h->h_skip[m]) continue;
+            for (int64_t t = 0; t < T; ++t) {
+                if (logmu_trace) logmu_trace[(size_t)t * nt + m] = nan;
+                if (ess_trace) ess_trace[(size_t)t * nt + m] = nan;
+            }
+        }
+    }
     return SMC_OK;
 }
 
@@ -972,6 +1010,7 @@ extern "C" int smc_step_window(smc_handle h, const double* y, int k, double* log
     if (summ && !summaries_fit_lds(h)) return fail(SMC_EINVAL, "smc_step_window: no LDS left for the summaries of filters this long; fewer levels, or smc_step");
     if (summ && (rc = ensure_summaries(h, WIN_MAX))) return rc;
     h->sum_T = 0;
+    h->sum_skip.clear();   // (the skip mask applies to smc_log_likelihood only)
     HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)k * 8, hipMemcpyHostToDevice, h->stream));
     h->v.y = h->d_y;
     if (summ) view_summaries(h);
@@ -1014,7 +1053,7 @@ extern "C" int smc_step_commit(smc_handle h, int j) {
 extern "C" int smc_set_skip(smc_handle h, const uint8_t* skip) {
     if (!h) return fail(SMC_EINVAL, "smc_set_skip: NULL handle");
     HIPCHK(hipSetDevice(h->device));
-    if (!skip) { h->skip_on = false; return SMC_OK; }
+    if (!skip) { h->skip_on = false; h->h_skip.clear(); return SMC_OK; }
     const int nt = h->v.ntheta;
     if (!h->d_skip) HIPCHK(dalloc(&h->d_skip, (size_t)nt));
     if (!h->d_order) HIPCHK(dalloc(&h->d_order, (size_t)nt + 1));
@@ -1028,6 +1067,7 @@ extern "C" int smc_set_skip(smc_handle h, const uint8_t* skip) {
     HIPCHK(hipMemcpyAsync(h->d_skip, skip, (size_t)nt, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_order, ord.data(), ord.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    h->h_skip.assign(skip, skip + nt);
     h->skip_on = true;
     return SMC_OK;
 }

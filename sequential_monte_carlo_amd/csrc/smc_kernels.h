@@ -1414,7 +1414,13 @@ __global__ __launch_bounds__(THREADS) void k_table(FilterView v, int cur, int em
     __shared__ int redk[NW];
     __shared__ uint64_t wt[NW], wr[NW];
     const int th = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    if (v.skip && v.skip[th]) return;
+    if (v.skip && v.skip[th]) {   // a filter that was not run: an emitting launch reports logZ = -inf (as k_finalize does)
+        if (emit != 0 && tid == 0) {
+            v.logZ[th] = -inf();
+            if (v.host_out) v.host_out[th] = -inf();
+        }
+        return;
+    }
     const size_t base = (size_t)th * v.nseg;
     const double* sk = v.segk[cur] + base;
     const uint64_t* sS = v.segS[cur] + base;

@@ -222,7 +222,7 @@ def test_skipped_filters_are_not_run(ob):
     from sequential_monte_carlo_amd import _lib as L
     raw = [0.5, 1.0, 0.9, 0.8, 0.0, 1.0]
     _, y = ob.simulate(1, raw, 12, 3)
-    for n, seg, fl in ((1024, 0, 0), (1024, 0, L.FLAG_NO_RESIDENT), (3000, 1024, 0)):
+    for n, seg, fl in ((1024, 0, 0), (1024, 0, L.FLAG_NO_RESIDENT), (3000, 1024, 0), (70000, 256, 0)):   # last: k_table emits
         h = L.Handle(1, 5, n, seg=seg, seed=8, flags=fl)
         h.set_params(np.tile(raw, (5, 1)))
         z0 = h.log_likelihood(y)
@@ -238,6 +238,18 @@ def test_skipped_filters_are_not_run(ob):
         assert np.all(z1[[1, 3, 4]] == -np.inf) and np.array_equal(bits(z1[[0, 2]]), bits(z2[[0, 2]])) and np.all(np.isfinite(z2))
         assert np.array_equal(bits(x1[:, [1, 3, 4]]), bits(x0[:, [1, 3, 4]]))          # skipped slots keep their old state
         assert np.array_equal(bits(x1[:, [0, 2]]), bits(x2[:, [0, 2]]))
+        h.close()
+    # a reused bundle: the destroyed handle's pinned mirror held finite values when its successor's first call is skipped
+    for n, seg in ((1024, 0), (70000, 256)):
+        h = L.Handle(1, 5, n, seg=seg, seed=8)
+        h.set_params(np.tile(raw, (5, 1)))
+        z0 = h.log_likelihood(y)
+        h.close()
+        h = L.Handle(1, 5, n, seg=seg, seed=8)
+        h.set_params(np.tile(raw, (5, 1)))
+        h.set_skip([0, 1, 0, 1, 1])
+        z1 = h.log_likelihood(y)
+        assert np.all(np.isfinite(z0)) and np.all(z1[[1, 3, 4]] == -np.inf) and np.array_equal(bits(z1[[0, 2]]), bits(z0[[0, 2]])), (n, z1)
         h.close()
 
 
