@@ -86,6 +86,7 @@ int smc_log_likelihood(smc_handle h, const double* y, int64_t T, double* logZ /*
  * observation (the README loop becomes ONE call).  component: state coordinate of the quantiles; p [np], np <= 8 (0: no
  * quantiles); moments != 0: mean and variance of every coordinate.  np = 0 and moments = 0 switch it off again.
  * Quantile definition: that of smc_get_quantiles (inverse of the weighted empirical CDF in the filter's integer weights).
+ * Moments: those of smc_get_moments (NaN at a step after which every weight is 0).
  * smc_get_summaries hands over the first T steps of the last such call: q [T][n_theta][np], mean / var [T][d][n_theta]
  * (NULL: not wanted).  Single-segment filters compute them inside the LDS-resident kernel; larger ones by trailing kernels
  * on the handle's stream after every step. */
@@ -258,7 +259,11 @@ int smc_resample(const double* w, int64_t n, int64_t ndraw, uint64_t seed, uint3
 int smc_kalman_log_likelihood(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first,
                               double* out /*[n_theta][3]*/, int device);
 /* filtered mean and variance of every state coordinate under the current weights, on the device
- * (README.md:41,51 summaries; src/plotting_utils.jl:116-124 estimated_trend). mean, var: [d][n_theta]. */
+ * (README.md:41,51 summaries; src/plotting_utils.jl:116-124 estimated_trend). mean, var: [d][n_theta].
+ * Definition: StatsBase's uncorrected weighted moments with the dense weights w of smc_get_state, mean = sum w x and
+ * var = sum w (x - mean)^2 (centred: no cancellation for a state with a level).  Accuracy: against the
+ * exactly rounded sums, |mean - m| <= 1e-11 |m| + 1e-12 sqrt(v) and |var - v| <= 1e-9 v + (1e-11 m)^2; var >= 0.
+ * NaN mean and var for a collapsed filter (every weight 0), as its quantiles. */
 int smc_get_moments(smc_handle h, double* mean, double* var);
 
 /* weighted quantiles of state coordinate `component` under the current weights, per filter, on the

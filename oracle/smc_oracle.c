@@ -970,10 +970,15 @@ void orc_filter_moments(const orc_filter* f, double* mean, double* var) {
     const int64_t n = f->n;
     double* w = (double*)malloc(8 * (size_t)n);
     weights_dense(&f->W, w);
+    /* StatsBase's uncorrected weighted moments: mean = sum w x, var = sum w (x - mean)^2 (centred: the error scales with var, not
+       with mean^2); a collapsed filter (every weight 0) has none: NaN */
     for (int c = 0; c < f->model.d; ++c) {
+        const double* xc = f->x + (size_t)c * n;
+        if (!f->W.Dtot) { mean[c] = var[c] = NAN; continue; }
         double m = 0.0, m2 = 0.0;
-        for (int64_t i = 0; i < n; ++i) { const double x = f->x[(size_t)c * n + i]; m += w[i] * x; m2 += w[i] * x * x; }
-        mean[c] = m; var[c] = m2 - m * m;
+        for (int64_t i = 0; i < n; ++i) m += w[i] ? w[i] * xc[i] : 0.0;   /* (a particle without weight does not enter) */
+        for (int64_t i = 0; i < n; ++i) { const double e = xc[i] - m; m2 += w[i] ? w[i] * (e * e) : 0.0; }
+        mean[c] = m; var[c] = m2;
     }
     free(w);
 }

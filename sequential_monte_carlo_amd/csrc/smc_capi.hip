@@ -790,7 +790,11 @@ static int enqueue_ms(smc_handle h, int component, int np, const uint64_t* p64, 
     const int g_read = groups(256), g_hist = groups(64);
     hipLaunchKernelGGL(k_ms_range, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, h->d, ms);
     if (np > 0) hipLaunchKernelGGL(k_ms_hist, dim3(g_hist, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, g_read, ms);
-    hipLaunchKernelGGL(k_ms_pick, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, h->d, g_read, ms, q_out, mean, var);
+    hipLaunchKernelGGL(k_ms_pick, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, h->d, g_read, ms, q_out, mean);
+    if (mom) {   // the variance centred on that mean: a second read of the cloud
+        hipLaunchKernelGGL(k_ms_center, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, h->d, ms, (const double*)mean);
+        hipLaunchKernelGGL(k_ms_var, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, h->d, g_read, ms, var);
+    }
     int64_t two_level = MS_TWO_LEVEL;
     if (const char* e = getenv("SMC_MS_TWO_LEVEL")) two_level = atoll(e);   // tuning / test knob: results do not depend on it
     if (np > 0 && h->v.n > two_level) {   // big filters: the chosen bins cut a second time before the candidates are collected

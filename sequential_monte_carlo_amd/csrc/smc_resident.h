@@ -35,7 +35,10 @@ __host__ __device__ inline size_t resident_lds_bytes(int seg, int threads, int n
 //              particles of that bin are collected and ranked inside the wave - four barriers.  Whenever that does not apply
 //              (a non-finite value carrying weight, an empty or overflowing range, more than 64 particles in a chosen bin) the
 //              step falls back to the 8-pass radix select on the order-preserving key, one wave per level picking the digit;
-//   moments:   sum w x and sum w x^2 with the dense weights w = q 2^-48 / (S 2^-48) (smc_get_state's w).
+//   moments:   StatsBase's uncorrected weighted mean and variance with the dense weights w = q 2^-48 / (S 2^-48) (smc_get_state's
+//              w), in two passes over the particles in LDS: mean = sum w x, then var = sum w (x - mean)^2 - centred, so that its
+//              error scales with var and not with mean^2 (a state with a level: sum w x^2 - mean^2 cancels catastrophically).
+//              Particles beyond n do not enter; a collapsed filter (S = 0) has NaN moments.
 // Called by every thread of the workgroup after the step's last barrier; ends with the histograms cleared for the next step.
 template <int THREADS, int NP, int D>
 __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, int64_t row, const uint64_t* Cs, const double* xs, int SEGP,
@@ -56,25 +59,24 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
         q[2 * k] = c0 - prev;
         q[2 * k + 1] = c1 - c0;
     }
+    // the dense weight of the particle of q[i] (0 beyond n: those never enter a sum, whatever their state holds)
+    const double Dd = (double)S * pow2i(-48), sc = pow2i(-48);
+    auto wdense = [&](int i) { return (S && 2 * (tid + (i >> 1) * THREADS) + (i & 1) < (int)v.n) ? ((double)q[i] * sc) / Dd : 0.0; };
     if (v.sum_mom) {
-        const double Dd = (double)S * pow2i(-48), sc = pow2i(-48);
 #pragma unroll
-        for (int c = 0; c < D; ++c) {
-            double m = 0.0, m2 = 0.0;
+        for (int c = 0; c < D; ++c) {   // first pass: the waves' partial sums of w x
+            double m = 0.0;
 #pragma unroll
             for (int k = 0; k < NP; ++k) {
                 const int pp = lds_pad(2 * (tid + k * THREADS));
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    const double x = xs[c * SEGP + pp + j];
-                    const double w = S ? ((double)q[2 * k + j] * sc) / Dd : 0.0;
-                    m += w * x;
-                    m2 += w * x * x;
+                    const double w = wdense(2 * k + j);
+                    m += w ? w * xs[c * SEGP + pp + j] : 0.0;
                 }
             }
             m = wave_sum_f64(m);
-            m2 = wave_sum_f64(m2);
-            if (lane == 0) { red[(0 * 3 + c) * 16 + wave] = m; red[(1 * 3 + c) * 16 + wave] = m2; }
+            if (lane == 0) red[(0 * 3 + c) * 16 + wave] = m;
         }
     }
     if (nq > 0 && S == 0) {   // collapsed filter: no quantile (workgroup-uniform)
@@ -220,11 +222,31 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
     }
     if (v.sum_mom) {
         __syncthreads();
+#pragma unroll
+        for (int c = 0; c < D; ++c) {   // second pass, after the quantiles' selection: every thread sums the waves' partials in wave
+                                        // order (the same mean everywhere), then w (x - mean)^2
+            double a = 0.0;
+            for (int w = 0; w < NW; ++w) a += red[(0 * 3 + c) * 16 + w];
+            double m2 = 0.0;
+#pragma unroll
+            for (int k = 0; k < NP; ++k) {
+                const int pp = lds_pad(2 * (tid + k * THREADS));
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const double w = wdense(2 * k + j), e = xs[c * SEGP + pp + j] - a;
+                    m2 += w ? w * (e * e) : 0.0;
+                }
+            }
+            m2 = wave_sum_f64(m2);
+            if (lane == 0) red[(1 * 3 + c) * 16 + wave] = m2;
+        }
+        __syncthreads();
         if (tid < D) {
             double a = 0.0, b2 = 0.0;
             for (int w = 0; w < NW; ++w) { a += red[(0 * 3 + tid) * 16 + w]; b2 += red[(1 * 3 + tid) * 16 + w]; }
-            v.sum_m[(((size_t)row * 2 + 0) * D + tid) * v.ntheta + th] = a;
-            v.sum_m[(((size_t)row * 2 + 1) * D + tid) * v.ntheta + th] = b2 - a * a;
+            const double nan = bits2d(0x7ff8000000000000ULL);   // collapsed filter: no moments
+            v.sum_m[(((size_t)row * 2 + 0) * D + tid) * v.ntheta + th] = S ? a : nan;
+            v.sum_m[(((size_t)row * 2 + 1) * D + tid) * v.ntheta + th] = S ? b2 : nan;
         }
     }
 }

@@ -9,16 +9,20 @@
 // sum{W_i : x_i <= v} > T, values ordered by the IEEE total order of their bits.  Any selection that narrows by a MONOTONE map
 // of x finds that same particle, so:
 //   k_ms_range    per segment: the range of the values that carry weight (and, for the moments, the segment's partial sums of
-//                 w x and w x^2 with the dense weights w = q 2^-48-dk / (Dtot 2^(SH-48)) in a fixed order)
+//                 w x with the dense weights w = q 2^-48-dk / (Dtot 2^(SH-48)) in a fixed order)
 //   k_ms_hist     histogram of the integer weights over MS_BINS equal-width VALUE bins (LDS per workgroup, then 64-bit atomics)
-//   k_ms_pick     one workgroup per filter: total weight, every level's target, bin and the weight below it; the moments' sums
+//   k_ms_pick     one workgroup per filter: total weight, every level's target, bin and the weight below it; the mean
+//   k_ms_center   (moments) per segment: the partial sums of w (x - mean)^2, in the same fixed order as k_ms_range's
+//   k_ms_var      (moments) one workgroup per filter: the variance from those partial sums
 //   k_ms_collect  the particles of the chosen bins into a candidate list per level
 //   k_ms_select   one workgroup per (level, filter): 8-pass radix select on the order-preserving key among the candidates in LDS -
 //                 or, when the range is unusable (a non-finite value carrying weight, all values alike, an overflowing width) or
 //                 a bin holds more than MS_CAP particles, the same radix select streaming over ALL particles of the filter
 //                 (slow, rare, always right).
 // Every cross-workgroup combination is an integer sum or a maximum: the quantiles are bit-identical to the oracle's sort.  The
-// moments are sums of doubles in a fixed order (segment by segment), equal to the oracle's to rounding.
+// moments are StatsBase's uncorrected weighted mean and variance: sums of doubles in a fixed order (segment by segment), the
+// variance centred on the mean (a second read of the cloud: its error scales with var, not with mean^2 as that of
+// sum w x^2 - mean^2 does); NaN for a collapsed filter.  DESIGN.md section 2 states the bound.
 #pragma once
 #include "smc_kernels.h"
 
@@ -33,7 +37,7 @@ constexpr int MS_STASH = 64;      // matches a workgroup of k_ms_collect keeps i
 struct MsScratch {
     double* rng;                 // [ntheta][parts][2]     largest value / largest negated value carrying weight (+inf: non-finite), per
                                  //                        workgroup of k_ms_range (parts <= nseg: room for nseg)
-    double* mpart;               // [ntheta][d][parts][2]  partial sums of w x, w x^2
+    double* mpart;               // [ntheta][d][parts][2]  partial sums of w x, w (x - mean)^2
     unsigned long long* hist;    // [ntheta][MS_BINS]
     uint64_t* hdr;               // [ntheta][4]            lo, scale (doubles) | usable (0 / 1) | total weight
     uint64_t* st;                // [ntheta][QMAX][6]      bin | weight below | target | state (0 fallback, 1 binned, 2 no weight) | sub-bin | -
@@ -103,14 +107,14 @@ __device__ __forceinline__ void ms_for_each(const FilterView& v, int cur, int th
     }
 }
 
-// grid (G, ntheta): per workgroup the range of the weighted values and the partial sums of the moments
+// grid (G, ntheta): per workgroup the range of the weighted values and the partial sums of the mean
 __global__ __launch_bounds__(MS_STREAM) void k_ms_range(FilterView v, int cur, int d, MsScratch ms) {
     constexpr int NW = MS_STREAM / WAVE;
-    __shared__ double red[8][NW];
+    __shared__ double red[5][NW];
     const int g = blockIdx.x, G = gridDim.x, th = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     const uint64_t Dtot = v.last_D[th];
     const double Dd = (double)Dtot * pow2i(v.SH - 48);
-    double vhi = -inf(), vlo = -inf(), mo[3] = {0.0, 0.0, 0.0}, mo2[3] = {0.0, 0.0, 0.0};
+    double vhi = -inf(), vlo = -inf(), mo[3] = {0.0, 0.0, 0.0};
     bool odd = false;
     const bool want_q = v.sum_np != 0, want_m = v.sum_mom != 0;
     ms_for_each(v, cur, th, v.sum_comp, [&](int64_t i, uint64_t q, double xq, const MsSeg& sg) {
@@ -124,11 +128,8 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_range(FilterView v, int cur, i
         }
         if (want_m) {
             const double w = Dtot ? ((double)q * sg.sc) / Dd : 0.0;
-            for (int c = 0; c < d; ++c) {
-                const double x = c == v.sum_comp ? xq : v.x[cur][((size_t)c * v.ntheta + th) * v.npad + i];
-                mo[c] += w * x;
-                mo2[c] += w * x * x;
-            }
+            if (w)
+                for (int c = 0; c < d; ++c) mo[c] += w * (c == v.sum_comp ? xq : v.x[cur][((size_t)c * v.ntheta + th) * v.npad + i]);
         }
     });
     if (want_q) {
@@ -139,8 +140,8 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_range(FilterView v, int cur, i
     }
     if (want_m)
         for (int c = 0; c < d; ++c) {
-            const double a = wave_sum_f64(mo[c]), a2 = wave_sum_f64(mo2[c]);
-            if (lane == 0) { red[2 + 2 * c][wave] = a; red[3 + 2 * c][wave] = a2; }
+            const double a = wave_sum_f64(mo[c]);
+            if (lane == 0) red[2 + c][wave] = a;
         }
     __syncthreads();
     if (tid == 0) {
@@ -152,11 +153,67 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_range(FilterView v, int cur, i
         }
         if (want_m)
             for (int c = 0; c < d; ++c) {
-                double a = 0.0, a2 = 0.0;
-                for (int w = 0; w < NW; ++w) { a += red[2 + 2 * c][w]; a2 += red[3 + 2 * c][w]; }
+                double a = 0.0;
+                for (int w = 0; w < NW; ++w) a += red[2 + c][w];
                 ms.mpart[(((size_t)th * d + c) * G + g) * 2] = a;
-                ms.mpart[(((size_t)th * d + c) * G + g) * 2 + 1] = a2;
             }
+    }
+}
+
+// grid (G, ntheta), moments only, behind k_ms_pick: per workgroup the partial sums of w (x - mean)^2 (the same particles, order and
+// dense weights as k_ms_range's partial sums of w x)
+__global__ __launch_bounds__(MS_STREAM) void k_ms_center(FilterView v, int cur, int d, MsScratch ms, const double* mean) {
+    constexpr int NW = MS_STREAM / WAVE;
+    __shared__ double red[3][NW];
+    const int g = blockIdx.x, G = gridDim.x, th = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const uint64_t Dtot = v.last_D[th];
+    const double Dd = (double)Dtot * pow2i(v.SH - 48);
+    double mu[3] = {0.0, 0.0, 0.0}, mo2[3] = {0.0, 0.0, 0.0};
+    for (int c = 0; c < d; ++c) mu[c] = mean[(size_t)c * v.ntheta + th];
+    ms_for_each(v, cur, th, 0, [&](int64_t i, uint64_t q, double x0, const MsSeg& sg) {
+        const double w = Dtot ? ((double)q * sg.sc) / Dd : 0.0;
+        if (w)
+            for (int c = 0; c < d; ++c) {
+                const double e = (c == 0 ? x0 : v.x[cur][((size_t)c * v.ntheta + th) * v.npad + i]) - mu[c];
+                mo2[c] += w * (e * e);
+            }
+    });
+    for (int c = 0; c < d; ++c) {
+        const double a2 = wave_sum_f64(mo2[c]);
+        if (lane == 0) red[c][wave] = a2;
+    }
+    __syncthreads();
+    if (tid == 0)
+        for (int c = 0; c < d; ++c) {
+            double a2 = 0.0;
+            for (int w = 0; w < NW; ++w) a2 += red[c][w];
+            ms.mpart[(((size_t)th * d + c) * G + g) * 2 + 1] = a2;
+        }
+}
+
+// the filter's total of slot `k` of the partial sums of coordinate c (k_ms_range / k_ms_center): thread t takes the partial sums
+// t, t + 256, ...; lanes, then waves, in order.  Every thread of the workgroup gets it; two barriers inside.
+__device__ __forceinline__ double ms_moment_total(const MsScratch& ms, int th, int d, int c, int k, int nparts, double* red) {
+    constexpr int NW = MS_THREADS / WAVE;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    double a = 0.0;
+    for (int g = tid; g < nparts; g += MS_THREADS) a += ms.mpart[(((size_t)th * d + c) * nparts + g) * 2 + k];
+    a = wave_sum_f64(a);
+    __syncthreads();
+    if (lane == 0) red[wave] = a;
+    __syncthreads();
+    double s = 0.0;
+    for (int w = 0; w < NW; ++w) s += red[w];
+    return s;
+}
+
+// grid (ntheta), moments only, behind k_ms_center: var [d][ntheta]
+__global__ __launch_bounds__(MS_THREADS) void k_ms_var(FilterView v, int d, int nparts, MsScratch ms, double* var) {
+    __shared__ double red[MS_THREADS / WAVE];
+    const int th = blockIdx.x;
+    for (int c = 0; c < d; ++c) {
+        const double s2 = ms_moment_total(ms, th, d, c, 1, nparts, red);
+        if (threadIdx.x == 0) var[(size_t)c * v.ntheta + th] = v.last_D[th] ? s2 : bits2d(0x7ff8000000000000ULL);   // collapsed: NaN
     }
 }
 
@@ -208,30 +265,16 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_hist(FilterView v, int cur, in
         if (lh[i]) atomicAdd(&ms.hist[(size_t)th * MS_BINS + i], lh[i]);
 }
 
-// grid (ntheta): the filter's histogram -> total, targets, bins; the moments' sums.  mean / var: [d][ntheta] rows of the output
-__global__ __launch_bounds__(MS_THREADS) void k_ms_pick(FilterView v, int d, int nparts, MsScratch ms, double* q_out, double* mean, double* var) {
+// grid (ntheta): the filter's histogram -> total, targets, bins; the mean.  mean: [d][ntheta] rows of the output
+__global__ __launch_bounds__(MS_THREADS) void k_ms_pick(FilterView v, int d, int nparts, MsScratch ms, double* q_out, double* mean) {
     constexpr int NW = MS_THREADS / WAVE, PER = MS_BINS / MS_THREADS;
     __shared__ uint64_t wt[NW];
-    __shared__ double red[2][NW];
+    __shared__ double red[NW];
     const int th = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     if (v.sum_mom)
-        for (int c = 0; c < d; ++c) {   // fixed order: thread t takes the partial sums t, t + 256, ...; lanes, then waves, in order
-            double a = 0.0, a2 = 0.0;
-            for (int g = tid; g < nparts; g += MS_THREADS) {
-                a += ms.mpart[(((size_t)th * d + c) * nparts + g) * 2];
-                a2 += ms.mpart[(((size_t)th * d + c) * nparts + g) * 2 + 1];
-            }
-            a = wave_sum_f64(a);
-            a2 = wave_sum_f64(a2);
-            __syncthreads();
-            if (lane == 0) { red[0][wave] = a; red[1][wave] = a2; }
-            __syncthreads();
-            if (tid == 0) {
-                double s = 0.0, s2 = 0.0;
-                for (int w = 0; w < NW; ++w) { s += red[0][w]; s2 += red[1][w]; }
-                mean[(size_t)c * v.ntheta + th] = s;
-                var[(size_t)c * v.ntheta + th] = s2 - s * s;
-            }
+        for (int c = 0; c < d; ++c) {
+            const double s = ms_moment_total(ms, th, d, c, 0, nparts, red);
+            if (tid == 0) mean[(size_t)c * v.ntheta + th] = v.last_D[th] ? s : bits2d(0x7ff8000000000000ULL);   // collapsed: NaN
         }
     const int nq = v.sum_np;
     if (nq == 0) return;

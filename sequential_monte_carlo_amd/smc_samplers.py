@@ -314,8 +314,9 @@ def estimated_trend(smc):
     else:
         obs = np.zeros(rows.shape[0])
     allobs = _per_theta(smc, obs[:, None])[:, 0]
-    w = smc.omega
-    return float(w @ allobs)
+    w = np.asarray(smc.omega, dtype=np.float64)
+    keep = w > 0                     # a filter of no weight may have a NaN mean (collapsed): it does not enter (0 * NaN is NaN)
+    return float(w[keep] @ allobs[keep])
 
 
 def resample_(smc):
@@ -495,8 +496,11 @@ def smc2_step(smc, y, t, verbose=True, out=sys.stdout):
 
 def _integrate(w, rows):
     """[M][np + 1] per-filter (quantiles | variance) rows of every rank -> their omega-weighted means (quantiles [np], variance);
-    the products summed over the parameter particles in index order (one definition for every caller: no BLAS in between)"""
-    tot = np.add.reduce(w[:, None] * np.ascontiguousarray(rows, dtype=np.float64), axis=0)
+    the products summed over the parameter particles in index order (one definition for every caller: no BLAS in between).
+    Only filters with omega > 0 enter: a filter of no weight may have NaN rows (a collapsed filter), and 0 * NaN is NaN"""
+    w = np.asarray(w, dtype=np.float64)
+    keep = w > 0
+    tot = np.add.reduce(w[keep, None] * np.ascontiguousarray(rows, dtype=np.float64)[keep], axis=0)
     return tot[:-1], float(tot[-1])
 
 

@@ -301,3 +301,47 @@ def test_ucsv_particle_filter_against_rao_blackwellised_filter(ob):
     # (power check with the Rao-Blackwellised filter itself: shifting gamma by 50 % moves logZ by far more than the se)
     zw = np.array([rbpf_ucsv.log_likelihood(y, 0.3, 0.3, *UC[2:], n=8000, rng=rng) for _ in range(8)])
     assert abs(zw.mean() - zr.mean()) > 5 * (zr.std(ddof=1) / np.sqrt(zr.size) + zw.std(ddof=1) / np.sqrt(zw.size))
+
+
+def test_summary_reference_is_exact():
+    """tests/summary_reference.py: the fsum moments equal the exact rational ones to rounding (small n, a cloud at 1e8)"""
+    from fractions import Fraction
+    from summary_reference import ref_moments
+    rng = np.random.default_rng(31)
+    for off in (0.0, 1e8, -1e6):
+        x = off + 0.3 * rng.standard_normal(37)
+        w = rng.uniform(0, 1, 37)
+        w[3] = 0.0
+        W = sum(Fraction(v) for v in w)
+        m = sum(Fraction(a) * Fraction(b) for a, b in zip(w, x)) / W
+        v = sum(Fraction(b) * (Fraction(a) - m) ** 2 for a, b in zip(x, w)) / W
+        rm, rv = ref_moments(x, w)
+        assert abs(Fraction(rm) - m) <= Fraction(4e-16) * abs(m) + Fraction(1e-300)
+        assert abs(Fraction(rv) - v) <= Fraction(1e-14) * v
+
+
+@pytest.mark.parametrize("x0,Q,R", [(0.0, 0.9, 0.8), (1e4, 1.0, 1.0), (1e6, 1e-6, 1.0), (1e8, 1.0, 1.0), (-1e6, 1e-6, 1.0), (1e6, 1.0, 1e-6)])
+def test_oracle_moments_exact_at_a_level(ob, x0, Q, R):
+    """orc_filter_moments (centred) against the fsum reference after every step of LG clouds with a level (A = 1): the error
+    scales with var, not with mean^2 - the tolerances of tests/summary_reference.py; NaN for a collapsed filter"""
+    from summary_reference import check_moments
+    raw = [1.0, 1.0, Q, R, x0, 1.0]
+    _, y = ob.simulate(ob.LG1D, raw, 8, 5)
+    y[5] = 1e200                                      # every weight 0 after step 5
+    for n, seg in ((1024, 0), (5000, 1024)):
+        f = ob.Filter(ob.LG1D, raw, n, seg=seg, seed=3)
+        for t in range(len(y)):
+            f.bootstrap_filter(y[0]) if t == 0 else f.step(y[t])
+            x, w, _, _ = f.state()
+            m, v = f.moments()
+            check_moments(m[0], v[0], x[0], w, (x0, Q, R, n, t))
+            assert np.isnan(m[0]) == (t == 5)
+    # UCSV: all three coordinates, the trend at 1e5
+    f = ob.Filter(ob.UCSV3D, [0.2, 0.2, 1e5, 0.0, 0.0], 2048, seed=4)
+    _, yu = ob.simulate(ob.UCSV3D, [0.2, 0.2, 1e5, 0.0, 0.0], 6, 9)
+    for t in range(6):
+        f.bootstrap_filter(yu[0]) if t == 0 else f.step(yu[t])
+        x, w, _, _ = f.state()
+        m, v = f.moments()
+        for c in range(3):
+            check_moments(m[c], v[c], x[c], w, ("ucsv", t, c))

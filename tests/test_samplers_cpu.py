@@ -337,6 +337,26 @@ def test_filtered_summaries_and_trend():
     assert smc.estimated_trend(s) == pytest.approx(float(om @ (1.0 * means)), rel=1e-9)      # B = 1 in lg_mod
 
 
+def test_integrate_leaves_out_filters_without_weight():
+    """_integrate / estimated_trend sum only the filters with omega > 0, in index order: the NaN rows of a collapsed filter
+    (omega = 0) do not poison the integrated summaries (0 * NaN is NaN)"""
+    from sequential_monte_carlo_amd.smc_samplers import _integrate
+    rng = np.random.default_rng(4)
+    rows = rng.normal(1e6, 1.0, (6, 4))
+    w = rng.uniform(0.1, 1.0, 6)
+    w[2] = 0.0
+    w /= w.sum()
+    bad = rows.copy()
+    bad[2] = np.nan
+    q, v = _integrate(w, bad)
+    keep = np.arange(6) != 2
+    q0, v0 = _integrate(w[keep], rows[keep])
+    assert np.all(np.isfinite(q)) and np.isfinite(v)
+    assert np.array_equal(q, q0) and v == v0
+    # filters with weight: unchanged, the products summed in index order
+    assert np.array_equal(_integrate(w + (w == 0) * 0.1, rows)[0], np.add.reduce((w + (w == 0) * 0.1)[:, None] * rows, axis=0)[:-1])
+
+
 def test_windowed_run_collects_per_period_summaries():
     """smc2_run(..., summaries=p): the per-period filtered summaries the example's loop collects (examples/inflation_example.jl:
     78-86: get_quantiles_uc(smc) after every smc²!) from summaries recorded per step inside the window launches - the same
