@@ -86,12 +86,37 @@ int smc_log_likelihood(smc_handle h, const double* y, int64_t T, double* logZ /*
  * observation (the README loop becomes ONE call).  component: state coordinate of the quantiles; p [np], np <= 8 (0: no
  * quantiles); moments != 0: mean and variance of every coordinate.  np = 0 and moments = 0 switch it off again.
  * Quantile definition: that of smc_get_quantiles (inverse of the weighted empirical CDF in the filter's integer weights).
- * Moments: those of smc_get_moments (NaN at a step after which every weight is 0).
+ * Moments: those of smc_get_moments (NaN at a step after which every weight is 0).  Both in the handle's summary mode
+ * (smc_set_summary_mode below): SMC_SUMM_UNWEIGHTED gives the README loop's own quantile(x, p) and var(x).
  * smc_get_summaries hands over the first T steps of the last such call: q [T][n_theta][np], mean / var [T][d][n_theta]
  * (NULL: not wanted).  Single-segment filters compute them inside the LDS-resident kernel; larger ones by trailing kernels
  * on the handle's stream after every step. */
 int smc_set_summaries(smc_handle h, int component, const double* p /*[np]*/, int np, int moments);
 int smc_get_summaries(smc_handle h, int64_t T, double* q /*[T][n_theta][np]*/, double* mean /*[T][d][n_theta]*/, double* var /*[T][d][n_theta]*/);
+/* Summary modes.  SMC_SUMM_WEIGHTED (the default of a fresh or recycled handle): the definitions stated at smc_get_quantiles and
+ * smc_get_moments.  SMC_SUMM_UNWEIGHTED: the statistics README.md:33-61 and examples/inflation_example.jl:165-171,241-252,341-348
+ * compute on the cloud as bootstrap_filter! leaves it, Statistics.quantile(x, p) (unweighted, Hyndman-Fan type 7, interpolating;
+ * numpy's default "linear" method) and Statistics.var(x) (unweighted, corrected):
+ *   cloud      the n particles of state coordinate `component` of the current state (the x of smc_get_state), ALL of them, whatever
+ *              their weights; padding slots beyond n never enter.  Order: the IEEE total order of the bits (-0.0 < +0.0).
+ *   quantile   at level p (clamped to [0, 1]), in doubles and in exactly this order of operations:
+ *                  h = n*p + (1 - p)
+ *                  j = clamp(trunc(h), 1, n-1)          1-based rank
+ *                  g = clamp(h - j, 0, 1)
+ *                  a = x_(j),  b = x_(j+1)              n == 1: a = b = x_(1)
+ *                  q = a + g*(b - a)                    a, b finite; otherwise (1-g)*a + g*b
+ *              without a fused multiply-add: a pure function of the cloud, bit for bit.  The interpolation runs on the device.
+ *   moments    mean = (1/n) sum x, var = sum (x - mean)^2 / (n - 1), centred second pass, sums in a fixed order; accuracy as stated
+ *              at smc_get_moments with weights 1/n.  n == 1: var is NaN (as Julia).
+ * A collapsed filter (every weight 0) has ordinary, finite unweighted summaries; a skipped filter keeps its NaN rows (smc_set_skip).
+ * smc_set_summary_mode applies to the following smc_get_quantiles, smc_get_moments, and to the per-step summaries of
+ * smc_log_likelihood / smc_step_window armed by smc_set_summaries; rows recorded before it are no longer handed out.  Unknown
+ * mode: SMC_EINVAL, handle unchanged.
+ * NOT offered: StatsBase's weighted INTERPOLATING quantile(x, weights(w), p) of get_quantiles_uc (examples/inflation_example.jl:45);
+ * StatsBase is not vendored by the reference, so that variant cannot be pinned.  The weighted mode does not interpolate. */
+#define SMC_SUMM_WEIGHTED 0
+#define SMC_SUMM_UNWEIGHTED 1
+int smc_set_summary_mode(smc_handle h, int mode);
 /* the (x, w) the reference returns / mutates; any pointer may be NULL. w is the normalised
  * weight vector of normalize() (particles.jl:11); anc needs SMC_FLAG_ANCESTORS. */
 int smc_get_state(smc_handle h, double* x /*[d][n_theta][n_x]*/, double* w /*[n_theta][n_x]*/,
@@ -263,16 +288,17 @@ int smc_kalman_log_likelihood(const double* raw, int64_t n_theta, const double* 
  * Definition: StatsBase's uncorrected weighted moments with the dense weights w of smc_get_state, mean = sum w x and
  * var = sum w (x - mean)^2 (centred: no cancellation for a state with a level).  Accuracy: against the
  * exactly rounded sums, |mean - m| <= 1e-11 |m| + 1e-12 sqrt(v) and |var - v| <= 1e-9 v + (1e-11 m)^2; var >= 0.
- * NaN mean and var for a collapsed filter (every weight 0), as its quantiles. */
+ * NaN mean and var for a collapsed filter (every weight 0), as its quantiles.
+ * In SMC_SUMM_UNWEIGHTED mode (smc_set_summary_mode): the sample mean and the corrected sample variance of the cloud. */
 int smc_get_moments(smc_handle h, double* mean, double* var);
 
 /* weighted quantiles of state coordinate `component` under the current weights, per filter, on the
  * device: what quantile(smc.x[i], weights(smc.w[i]), [0.25,0.5,0.75]) computes per theta-particle in
  * examples/inflation_example.jl:45-46 (and README.md:41,51 for an unweighted cloud).  Definition: the
  * inverse of the weighted empirical CDF in the filter's integer weights - the smallest particle value v
- * with sum{W_i : x_i <= v} > floor(p * sum W) - no interpolation between particles (StatsBase
- * interpolates; it is not vendored, so that variant is unpinned).  np <= 8; out [n_theta][np];
- * NaN for a collapsed filter. */
+ * with sum{W_i : x_i <= v} > floor(p * sum W) - no interpolation between particles.  np <= 8;
+ * out [n_theta][np]; NaN for a collapsed filter.  The README's unweighted, interpolating quantile(x, p) is
+ * the SMC_SUMM_UNWEIGHTED mode (smc_set_summary_mode, which also names the one variant not offered). */
 int smc_get_quantiles(smc_handle h, int component, const double* p, int np, double* out);
 
 /* ---- host-side helpers (no GPU needed) ---------------------------------------------------------*/
@@ -283,6 +309,10 @@ int smc_model_nraw(int model_id);
 /* the segment length smc_create picks for seg = 0: a function of the model family (its state dimension) and n_x alone */
 int smc_auto_seg(int model_id, int64_t n_x);
 int smc_device_count(void);
+/* the SMC_SUMM_UNWEIGHTED definitions (smc_set_summary_mode) on the host, by sorting: the type-7 quantiles of x [n] at the levels
+ * p [np] in [0, 1] (else SMC_EINVAL), and the sample mean and corrected variance (n == 1: var NaN) */
+int smc_host_quantile7(const double* x, int64_t n, const double* p, int np, double* out);
+int smc_host_sample_moments(const double* x, int64_t n, double* mean, double* var);
 /* the spec's elementary functions on the host (parity tests of the host build) */
 double smc_host_exp(double x);
 double smc_host_log(double x);

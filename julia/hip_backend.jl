@@ -199,6 +199,36 @@ function StatsBase.quantile(x::HipParticles, ::Union{HipWeights,StatsBase.Abstra
     return out[:, x.m]
 end
 
+# quantile(x, p) and var(x) of the cloud itself, as the README loop (README.md:41,51) and get_quantiles_ucsv
+# (examples/inflation_example.jl:241-252) compute them - unweighted, type 7, interpolating; corrected variance - through the
+# handle's unweighted summary mode (SMC_SUMM_UNWEIGHTED = 1), weighted (0) again afterwards; the cloud stays on the device.
+# (Not offered: StatsBase's weighted INTERPOLATING quantile - the weighted method above does not interpolate.)
+function with_unweighted(g, f::HipFilter)
+    smc_check(ccall((:smc_set_summary_mode, LIBSMC), Cint, (Ptr{Cvoid}, Cint), f.h, 1))
+    try
+        return g()
+    finally
+        smc_check(ccall((:smc_set_summary_mode, LIBSMC), Cint, (Ptr{Cvoid}, Cint), f.h, 0))
+    end
+end
+function Statistics.quantile(x::HipParticles, p::AbstractVector{<:Real}; component=0)
+    pp = Float64.(p); out = Matrix{Float64}(undef, length(pp), x.f.M)
+    with_unweighted(x.f) do
+        GC.@preserve pp out smc_check(ccall((:smc_get_quantiles, LIBSMC), Cint,
+            (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Ptr{Float64}), x.f.h, component, pp, length(pp), out))
+    end
+    return out[:, x.m]
+end
+# var(x): scalar state -> a number, else the d coordinates' variances (the rows of the handle are [M x d] column-major)
+function Statistics.var(x::HipParticles)
+    mean = Matrix{Float64}(undef, x.f.M, x.f.d); var = Matrix{Float64}(undef, x.f.M, x.f.d)
+    with_unweighted(x.f) do
+        GC.@preserve mean var smc_check(ccall((:smc_get_moments, LIBSMC), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), x.f.h, mean, var))
+    end
+    return x.f.d == 1 ? var[x.m, 1] : var[x.m, :]
+end
+
 # normalize / resample on whole clouds (particles.jl:5-19), on the device
 function normalize(logw::Vector{Float64}, ::Val{:hip})
     w = similar(logw); logμ = Ref{Float64}(); ess = Ref{Float64}()

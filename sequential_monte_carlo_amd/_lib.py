@@ -27,8 +27,10 @@ EXPORTS = [
     "smc_comm_exchange_slots", "smc_host_reweight", "smc_comm_plan_exchange",
     "smc_outer_seg", "smc_host_outer_records", "smc_host_outer_combine", "smc_host_outer_window", "smc_host_outer_walk",
     "smc_host_outer_advance", "smc_host_outer_temper", "smc_host_outer_resample", "smc_host_rw_factor",
-    "smc_set_summaries", "smc_get_summaries",
+    "smc_set_summaries", "smc_get_summaries", "smc_set_summary_mode", "smc_host_quantile7", "smc_host_sample_moments",
 ]
+SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
+_SUMM_MODES = {"weighted": SUMM_WEIGHTED, "unweighted": SUMM_UNWEIGHTED}
 COMM_ID_BYTES = 128
 PRIOR_UNIFORM, PRIOR_NORMAL, PRIOR_TRUNCNORMAL, PRIOR_LOGNORMAL, PRIOR_NPAR, MAX_DTHETA = 1, 2, 3, 4, 5, 8
 
@@ -104,6 +106,9 @@ def lib():
     L.smc_get_moments.argtypes = [h, _dp, _dp]
     L.smc_get_quantiles.argtypes = [h, C.c_int, _dp, C.c_int, _dp]
     L.smc_set_summaries.argtypes = [h, C.c_int, _dp, C.c_int, C.c_int]
+    L.smc_set_summary_mode.argtypes = [h, C.c_int]
+    L.smc_host_quantile7.argtypes = [_dp, C.c_int64, _dp, C.c_int, _dp]
+    L.smc_host_sample_moments.argtypes = [_dp, C.c_int64, _dp, _dp]
     L.smc_get_summaries.argtypes = [h, C.c_int64, _dp, _dp, _dp]
     L.smc_sys_targets.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.c_int]
     L.smc_simulate.argtypes = [C.c_int, _dp, C.c_int64, C.c_uint64, _dp, _dp]
@@ -227,6 +232,23 @@ def host_reweight(logw, want_w=True):
     lm, ess = C.c_double(), C.c_double()
     check(lib().smc_host_reweight(_d(logw), logw.size, _d(w), C.byref(lm), C.byref(ess)))
     return lm.value, w, ess.value
+
+
+def host_quantile7(x, p):
+    """the unweighted type-7 quantiles of x at the levels p (smc_host_quantile7: the unweighted summary mode's definition; no GPU)"""
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    p = np.ascontiguousarray(p, dtype=np.float64).ravel()
+    out = np.zeros(p.size)
+    check(lib().smc_host_quantile7(_d(x), x.size, _d(p), p.size, _d(out)))
+    return out
+
+
+def host_sample_moments(x):
+    """(mean, corrected variance) of x (smc_host_sample_moments; no GPU)"""
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    m, v = C.c_double(), C.c_double()
+    check(lib().smc_host_sample_moments(_d(x), x.size, C.byref(m), C.byref(v)))
+    return m.value, v.value
 
 
 def host_outer_records(logw_local):
@@ -355,6 +377,7 @@ class Handle:
 
     def __init__(self, model_id, n_theta, n_x, seg=0, seed=1, device=0, flags=0):
         self._h = C.c_void_p()
+        self.summary_mode = "weighted"
         self.model_id, self.n_theta, self.n_x = model_id, int(n_theta), int(n_x)
         check(lib().smc_create(model_id, self.n_theta, self.n_x, seg, seed, device, flags, C.byref(self._h)))
         seg_, nseg, d, res = C.c_int(), C.c_int(), C.c_int(), C.c_int()
@@ -447,23 +470,35 @@ class Handle:
         assert a.size == self.n_theta
         check(lib().smc_permute(self._h, a.ctypes.data_as(_i32p)))
 
+    def set_summary_mode(self, mode):
+        """"weighted" (the default) or "unweighted": which statistics quantiles(), moments() and the per-step summaries compute from
+        now on (smc_set_summary_mode).  "unweighted" is the README loop's quantile(x, p) (type 7, interpolating) and var(x)
+        (corrected) of the cloud whatever its weights."""
+        if mode not in _SUMM_MODES:
+            raise ValueError("summary mode must be 'weighted' or 'unweighted'")
+        check(lib().smc_set_summary_mode(self._h, _SUMM_MODES[mode]))
+        self.summary_mode = mode
+
     def moments(self):
-        """filtered (mean, variance) of every state coordinate, [d][n_theta] each, computed on the device."""
+        """filtered (mean, variance) of every state coordinate, [d][n_theta] each, computed on the device (in the handle's summary
+        mode: weighted mean and uncorrected variance, or the cloud's sample mean and corrected variance)."""
         m = np.zeros((self.d, self.n_theta))
         v = np.zeros((self.d, self.n_theta))
         check(lib().smc_get_moments(self._h, _d(m), _d(v)))
         return m, v
 
     def quantiles(self, p, component=0):
-        """weighted quantiles of one state coordinate under the current weights, [n_theta][len(p)], on the device."""
+        """quantiles of one state coordinate, [n_theta][len(p)], on the device (in the handle's summary mode: the inverse of the
+        weighted empirical CDF, or the cloud's unweighted type-7 quantiles)."""
         p = np.ascontiguousarray(p, dtype=np.float64).ravel()
         out = np.zeros((self.n_theta, p.size))
         check(lib().smc_get_quantiles(self._h, int(component), _d(p), p.size, _d(out)))
         return out
 
     def set_summaries(self, p=None, component=0, moments=False):
-        """per-step summaries inside the following log_likelihood / step_window calls (smc_set_summaries): weighted quantiles of
-        one state coordinate at the levels p (<= 8) and / or mean and variance of every coordinate; set_summaries() switches it off"""
+        """per-step summaries inside the following log_likelihood / step_window calls (smc_set_summaries): quantiles of one state
+        coordinate at the levels p (<= 8) and / or mean and variance of every coordinate, in the handle's summary mode
+        (set_summary_mode); set_summaries() switches it off"""
         p = np.ascontiguousarray([] if p is None else p, dtype=np.float64).ravel()
         check(lib().smc_set_summaries(self._h, int(component), _d(p) if p.size else None, p.size, int(bool(moments))))
         self._sum_np, self._sum_mom = int(p.size), bool(moments)

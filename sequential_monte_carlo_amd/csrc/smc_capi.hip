@@ -68,6 +68,8 @@ struct smc_filter_s {
     // per-step summaries inside the multi-step calls (smc_set_summaries / smc_get_summaries)
     int sum_np = 0, sum_comp = 0, sum_mom = 0;
     uint64_t sum_p64[QMAX] = {};
+    double sum_p[QMAX] = {};                   //   the same levels as doubles in [0, 1]: what the unweighted mode reads
+    int sum_mode = SMC_SUMM_WEIGHTED;          //   smc_set_summary_mode (v.sum_unw mirrors it)
     double *d_sum_q = nullptr, *d_sum_m = nullptr;   // [T][ntheta][np] | [T][2][d][ntheta]
     int64_t sum_cap = 0, sum_T = 0;            // steps the traces hold / steps the last call recorded
     unsigned* d_pflags = nullptr;              // opt-in persistent step kernel (SMC_PERSIST=1): completion flags [2][ntheta * nseg]
@@ -758,8 +760,12 @@ static int ensure_summaries(smc_handle h, int64_t T) {
 static void view_summaries(smc_handle h) {
     FilterView& v = h->v;
     v.sum_np = h->sum_np; v.sum_comp = h->sum_comp; v.sum_mom = h->sum_mom;
-    for (int j = 0; j < QMAX; ++j) v.sum_p64[j] = h->sum_p64[j];
+    for (int j = 0; j < QMAX; ++j) v.sum_p64[j] = h->sum_mode == SMC_SUMM_UNWEIGHTED ? d2bits(h->sum_p[j]) : h->sum_p64[j];
     v.sum_q = h->d_sum_q; v.sum_m = h->d_sum_m;
+}
+// the levels of a request in the form the kernels of the handle's mode read (FilterView::sum_p64)
+static void level_words(const smc_filter_s* h, const double* p, int np, uint64_t* out) {
+    for (int j = 0; j < QMAX; ++j) out[j] = j >= np ? 0 : h->sum_mode == SMC_SUMM_UNWEIGHTED ? d2bits(q7_level(p[j])) : prob_to_u64(p[j]);
 }
 // The summaries of the CURRENT weights of filters of any size, enqueued on the handle's stream behind the launch that produced
 // them (no host synchronisation): smc_summ_kernels.h.  q_out [ntheta][np], mean / var [d][ntheta] are device pointers.  The
@@ -772,7 +778,8 @@ static int ensure_ms(smc_handle h) {
     }
     return SMC_OK;
 }
-static int enqueue_ms(smc_handle h, int component, int np, const uint64_t* p64, bool mom, double* q_out, double* mean, double* var) {
+template <bool UNW>
+static int enqueue_ms_t(smc_handle h, int component, int np, const uint64_t* p64, bool mom, double* q_out, double* mean, double* var) {
     const size_t nth = (size_t)h->v.ntheta;
     int rc = ensure_ms(h);
     if (rc) return rc;
@@ -788,33 +795,43 @@ static int enqueue_ms(smc_handle h, int component, int np, const uint64_t* p64, 
         return g > h->v.nseg ? h->v.nseg : g;
     };
     const int g_read = groups(256), g_hist = groups(64);
-    hipLaunchKernelGGL(k_ms_range, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, h->d, ms);
-    if (np > 0) hipLaunchKernelGGL(k_ms_hist, dim3(g_hist, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, g_read, ms);
-    hipLaunchKernelGGL(k_ms_pick, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, h->d, g_read, ms, q_out, mean);
+    hipLaunchKernelGGL(k_ms_range<UNW>, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, h->d, ms);
+    if (np > 0) hipLaunchKernelGGL(k_ms_hist<UNW>, dim3(g_hist, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, g_read, ms);
+    hipLaunchKernelGGL(k_ms_pick<UNW>, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, h->d, g_read, ms, q_out, mean);
     if (mom) {   // the variance centred on that mean: a second read of the cloud
-        hipLaunchKernelGGL(k_ms_center, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, h->d, ms, (const double*)mean);
-        hipLaunchKernelGGL(k_ms_var, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, h->d, g_read, ms, var);
+        hipLaunchKernelGGL(k_ms_center<UNW>, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, h->d, ms, (const double*)mean);
+        hipLaunchKernelGGL(k_ms_var<UNW>, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, h->d, g_read, ms, var);
     }
     int64_t two_level = MS_TWO_LEVEL;
     if (const char* e = getenv("SMC_MS_TWO_LEVEL")) two_level = atoll(e);   // tuning / test knob: results do not depend on it
     if (np > 0 && h->v.n > two_level) {   // big filters: the chosen bins cut a second time before the candidates are collected
-        hipLaunchKernelGGL(k_ms_hist2, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, ms);
+        hipLaunchKernelGGL(k_ms_hist2<UNW>, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, ms);
         hipLaunchKernelGGL(k_ms_pick2, dim3(np, h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, ms);
-        hipLaunchKernelGGL(k_ms_collect<true>, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, ms);
+        hipLaunchKernelGGL((k_ms_collect<true, UNW>), dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, ms);
     } else if (np > 0) {
-        hipLaunchKernelGGL(k_ms_collect<false>, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, ms);
+        hipLaunchKernelGGL((k_ms_collect<false, UNW>), dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, ms);
     }
     if (np > 0) {
-        hipLaunchKernelGGL(k_ms_select, dim3(np, h->v.ntheta), dim3(MS_SEL_THREADS), 0, h->stream, v, h->cur, ms, q_out);
+        hipLaunchKernelGGL(k_ms_select<UNW>, dim3(np, h->v.ntheta), dim3(MS_SEL_THREADS), 0, h->stream, v, h->cur, ms, q_out);
+        if (UNW) {   // the neighbour x_(j+1) of every level, then the interpolation
+            hipLaunchKernelGGL(k_ms_succ, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, ms);
+            hipLaunchKernelGGL(k_ms_interp, dim3(h->v.ntheta), dim3(WAVE), 0, h->stream, v, ms, q_out);
+        }
     }
     HIPCHK(hipGetLastError());
     return SMC_OK;
+}
+static int enqueue_ms(smc_handle h, int component, int np, const uint64_t* p64, bool mom, double* q_out, double* mean, double* var) {
+    return h->sum_mode == SMC_SUMM_UNWEIGHTED ? enqueue_ms_t<true>(h, component, np, p64, mom, q_out, mean, var)
+                                              : enqueue_ms_t<false>(h, component, np, p64, mom, q_out, mean, var);
 }
 // ... into row `row` of the traces of a multi-step call
 static int enqueue_step_summaries(smc_handle h, int64_t row) {
     const size_t nth = (size_t)h->v.ntheta, nout = (size_t)h->d * nth;
     double* mbase = h->d_sum_m + (size_t)row * 2 * nout;
-    return enqueue_ms(h, h->sum_comp, h->sum_np, h->sum_p64, h->sum_mom != 0, h->d_sum_q + (size_t)row * nth * h->sum_np, mbase, mbase + nout);
+    uint64_t pw[QMAX];
+    level_words(h, h->sum_p, h->sum_np, pw);
+    return enqueue_ms(h, h->sum_comp, h->sum_np, pw, h->sum_mom != 0, h->d_sum_q + (size_t)row * nth * h->sum_np, mbase, mbase + nout);
 }
 
 extern "C" int smc_set_summaries(smc_handle h, int component, const double* p, int np, int moments) {
@@ -822,8 +839,17 @@ extern "C" int smc_set_summaries(smc_handle h, int component, const double* p, i
     if (np < 0 || np > QMAX || (np > 0 && !p)) return fail(SMC_EINVAL, "smc_set_summaries: 0 <= np <= 8");
     if (np > 0 && (component < 0 || component >= h->d)) return fail(SMC_EINVAL, "smc_set_summaries: component out of range");
     h->sum_np = np; h->sum_comp = np > 0 ? component : 0; h->sum_mom = moments ? 1 : 0;
-    for (int j = 0; j < QMAX; ++j) h->sum_p64[j] = j < np ? prob_to_u64(p[j]) : 0;
+    for (int j = 0; j < QMAX; ++j) { h->sum_p64[j] = j < np ? prob_to_u64(p[j]) : 0; h->sum_p[j] = j < np ? q7_level(p[j]) : 0.0; }
     h->sum_T = 0;
+    return SMC_OK;
+}
+
+extern "C" int smc_set_summary_mode(smc_handle h, int mode) {
+    if (!h) return fail(SMC_EINVAL, "smc_set_summary_mode: NULL handle");
+    if (mode != SMC_SUMM_WEIGHTED && mode != SMC_SUMM_UNWEIGHTED) return fail(SMC_EINVAL, "smc_set_summary_mode: unknown mode");
+    h->sum_mode = mode;
+    h->v.sum_unw = mode == SMC_SUMM_UNWEIGHTED ? 1 : 0;
+    h->sum_T = 0;   // (rows recorded in the other mode are not handed out as this one's)
     return SMC_OK;
 }
 
@@ -1626,7 +1652,7 @@ static int summaries_once(smc_handle h, int component, const double* p, int np, 
     if (!h->h_once) HIPCHK(hipHostMalloc((void**)&h->h_once, ((size_t)QMAX * nth + 2 * nout) * 8, hipHostMallocDefault));
     FilterView v = h->v;
     v.sum_np = np; v.sum_comp = component; v.sum_mom = mom ? 1 : 0;
-    for (int j = 0; j < QMAX; ++j) v.sum_p64[j] = j < np ? prob_to_u64(p[j]) : 0;
+    level_words(h, p, np, v.sum_p64);
     v.sum_q = h->h_once; v.sum_m = h->h_once + (size_t)QMAX * nth;
     hipError_t e = hipErrorInvalidValue;
     switch (h->model) {
@@ -1674,7 +1700,7 @@ extern "C" int smc_get_quantiles(smc_handle h, int component, const double* p, i
     if ((rc = summaries_once(h, component, p, np, false, out, nullptr, nullptr, done)) || done) return rc;
     const size_t nth = (size_t)h->v.ntheta, nst = nth * np;
     uint64_t hp[QMAX];
-    for (int j = 0; j < QMAX; ++j) hp[j] = j < np ? prob_to_u64(p[j]) : 0;
+    level_words(h, p, np, hp);
     if ((rc = ensure_ms(h))) return rc;
     double* d_out = (double*)(h->d_ms + ms_words(nth, (size_t)h->v.nseg, (size_t)h->d));
     if ((rc = enqueue_ms(h, component, np, hp, false, d_out, nullptr, nullptr))) return rc;
@@ -1684,6 +1710,33 @@ extern "C" int smc_get_quantiles(smc_handle h, int component, const double* p, i
 }
 
 // ---- host-side helpers ---------------------------------------------------------------------------
+// The unweighted summaries' definition on the host, by sorting (include/smc_hip.h "summary modes"): the spec's twin of the UNW kernels.
+extern "C" int smc_host_quantile7(const double* x, int64_t n, const double* p, int np, double* out) {
+    if (!x || !p || !out || n < 1 || np < 0) return fail(SMC_EINVAL, "smc_host_quantile7: bad argument");
+    for (int j = 0; j < np; ++j)
+        if (!(p[j] >= 0.0 && p[j] <= 1.0)) return fail(SMC_EINVAL, "smc_host_quantile7: levels must lie in [0, 1]");
+    std::vector<uint64_t> k((size_t)n);
+    for (int64_t i = 0; i < n; ++i) k[(size_t)i] = order_key(x[i]);
+    std::sort(k.begin(), k.end());
+    for (int j = 0; j < np; ++j) {
+        const Q7Rank r = q7_rank(n, p[j]);
+        const uint64_t ka = k[(size_t)(r.j > 1 ? r.j - 1 : 0)], kb = n == 1 ? ka : k[(size_t)r.j];
+        out[j] = q7_interp(key_value(ka), key_value(kb), r.g);
+    }
+    return SMC_OK;
+}
+extern "C" int smc_host_sample_moments(const double* x, int64_t n, double* mean, double* var) {
+    if (!x || !mean || !var || n < 1) return fail(SMC_EINVAL, "smc_host_sample_moments: bad argument");
+    double s = 0.0, s2 = 0.0;
+    for (int64_t i = 0; i < n; ++i) s += x[i];
+    double m = s / (double)n, r = 0.0;
+    for (int64_t i = 0; i < n; ++i) r += x[i] - m;   // (the rounding of the first sum, taken back)
+    m += r / (double)n;
+    for (int64_t i = 0; i < n; ++i) { const double e = x[i] - m; s2 += e * e; }
+    *mean = m;
+    *var = s2 / (double)(n - 1);   // (n == 1: 0 / 0, NaN as Statistics.var)
+    return SMC_OK;
+}
 template <int MODEL>
 static void simulate_t(const Params& p, int64_t T, uint64_t seed, double* x, double* y) {
     constexpr int D = model_dim<MODEL>::value;

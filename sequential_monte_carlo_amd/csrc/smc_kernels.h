@@ -114,7 +114,9 @@ struct FilterView {
     // per-step filtered summaries inside the multi-step calls (smc_set_summaries; README.md:33-61 computes quantile(x, ...) after
     // every bootstrap_filter!): weighted quantiles of state coordinate sum_comp at the levels sum_p64 (2^-64 fixed point) and
     // mean / variance of every coordinate, written per step by the kernel that owns the filter.  sum_np = sum_mom = 0: off.
-    int sum_np, sum_comp, sum_mom;
+    // sum_unw (smc_set_summary_mode, SMC_SUMM_UNWEIGHTED): the unweighted type-7 quantiles and the sample variance of the cloud
+    // instead; sum_p64 then holds the BITS of the levels as doubles, clamped to [0, 1] (q7_rank)
+    int sum_np, sum_comp, sum_mom, sum_unw;
     uint64_t sum_p64[8];
     double* sum_q;           // [T][ntheta][sum_np]
     double* sum_m;           // [T][2][d][ntheta]  (mean | variance)
@@ -159,6 +161,25 @@ __host__ __device__ inline uint64_t prob_to_u64(double p) {   // floor(p * 2^64)
     if (p >= 1.0) return ~(uint64_t)0;
     return (uint64_t)(p * TWO_P64);
 }
+// The unweighted quantile of n values at level p (include/smc_hip.h "summary modes": Statistics.quantile with its defaults,
+// Hyndman-Fan type 7), in exactly this order of operations: h = n p + (1 - p), j = clamp(trunc(h), 1, n - 1) the 1-based rank of
+// a = x_(j), b = x_(j+1), g = clamp(h - j, 0, 1); then a + g (b - a), or (1 - g) a + g b when a or b is not finite.  No fused
+// multiply-add (the build sets -ffp-contract=off on host and device).  n == 1: j = 0 and a = b = x_(1).
+struct Q7Rank { int64_t j; double g; };
+__host__ __device__ inline Q7Rank q7_rank(int64_t n, double p) {
+    const double h = (double)n * p + (1.0 - p);
+    int64_t j = (int64_t)h;
+    j = j > n - 1 ? n - 1 : (j < 1 ? 1 : j);
+    double g = h - (double)j;
+    g = g > 1.0 ? 1.0 : (g < 0.0 ? 0.0 : g);
+    Q7Rank r; r.j = j; r.g = g;
+    return r;
+}
+__host__ __device__ inline double q7_interp(double a, double b, double g) {
+    const bool fin = (a - a == 0.0) && (b - b == 0.0);
+    return fin ? a + g * (b - a) : (1.0 - g) * a + g * b;
+}
+__host__ __device__ inline double q7_level(double p) { return p > 0.0 ? (p < 1.0 ? p : 1.0) : 0.0; }   // clamped like prob_to_u64
 
 
 // Wave priority by phase of the step (0 = start .. 3 = normalisation): the EARLIER phase wins the issue slot.  Two

@@ -39,8 +39,14 @@ __host__ __device__ inline size_t resident_lds_bytes(int seg, int threads, int n
 //              w), in two passes over the particles in LDS: mean = sum w x, then var = sum w (x - mean)^2 - centred, so that its
 //              error scales with var and not with mean^2 (a state with a level: sum w x^2 - mean^2 cancels catastrophically).
 //              Particles beyond n do not enter; a collapsed filter (S = 0) has NaN moments.
+// UNW (smc_set_summary_mode, SMC_SUMM_UNWEIGHTED; a compile-time mode: the weighted kernels are the code they were): the
+// README loop's own statistics, quantile(x, p) and var(x) of the cloud whatever its weights.  Every particle below n counts 1
+// and the "total weight" is n, so the same selection finds a = x_(j), the order statistic of rank j = q7_rank(n, p).j, and it
+// knows count{x <= a}.  b = x_(j+1) is a when that count exceeds j, else the smallest key above key(a): one min reduction
+// over the keys the threads still hold.  The interpolation (q7_interp) happens here; moments: mean = sum x / n, then
+// sum (x - mean)^2 / (n - 1) in the same fixed order (n == 1: NaN).  A collapsed filter has ordinary summaries.
 // Called by every thread of the workgroup after the step's last barrier; ends with the histograms cleared for the next step.
-template <int THREADS, int NP, int D>
+template <int THREADS, int NP, int D, bool UNW = false>
 __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, int64_t row, const uint64_t* Cs, const double* xs, int SEGP,
                                                    uint64_t S, uint64_t* sm) {
     constexpr int NW = THREADS / WAVE, NQ = 2 * NP;
@@ -56,12 +62,22 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
     for (int k = 0; k < NP; ++k) {
         const int i0 = 2 * (tid + k * THREADS), pp = lds_pad(i0);
         const uint64_t c0 = Cs[pp], c1 = Cs[pp + 1], prev = i0 ? Cs[lds_pad(i0 - 1)] : 0;
-        q[2 * k] = c0 - prev;
-        q[2 * k + 1] = c1 - c0;
+        q[2 * k] = UNW ? (uint64_t)(i0 < (int)v.n) : c0 - prev;
+        q[2 * k + 1] = UNW ? (uint64_t)(i0 + 1 < (int)v.n) : c1 - c0;
     }
+    if (UNW) S = (uint64_t)v.n;   // the total of the counts
+    // the (0-based) target of level j: the weight below the quantile / the rank of a
+    auto target_of = [&](int j) -> uint64_t {
+        if (!UNW) return __umul64hi(v.sum_p64[j], S);
+        const int64_t r = q7_rank((int64_t)v.n, bits2d(v.sum_p64[j])).j;
+        return (uint64_t)(r > 1 ? r - 1 : 0);
+    };
     // the dense weight of the particle of q[i] (0 beyond n: those never enter a sum, whatever their state holds)
     const double Dd = (double)S * pow2i(-48), sc = pow2i(-48);
-    auto wdense = [&](int i) { return (S && 2 * (tid + (i >> 1) * THREADS) + (i & 1) < (int)v.n) ? ((double)q[i] * sc) / Dd : 0.0; };
+    auto wdense = [&](int i) {
+        if (UNW) return q[i] ? 1.0 : 0.0;
+        return (S && 2 * (tid + (i >> 1) * THREADS) + (i & 1) < (int)v.n) ? ((double)q[i] * sc) / Dd : 0.0;
+    };
     if (v.sum_mom) {
 #pragma unroll
         for (int c = 0; c < D; ++c) {   // first pass: the waves' partial sums of w x
@@ -138,7 +154,7 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
 #pragma unroll 4
                 for (int t = 0; t < PER; ++t) sum += hbin[t * WAVE + lane];
                 const uint64_t excl = wave_incl_scan(sum, lane) - sum;
-                const uint64_t target = __umul64hi(v.sum_p64[j], S);
+                const uint64_t target = target_of(j);
                 const unsigned long long own = __ballot(sum && excl <= target && target < excl + sum);   // exactly one lane
                 const int L = own ? __builtin_ctzll(own) : 0;
                 // ... and the 16 bins of that lane, one per lane of the first row
@@ -178,8 +194,12 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
                     // the candidates whose value the target falls on (all of them hold the same key): the quantile
                     const uint64_t tg = st_target[j];
                     const unsigned long long hit = __ballot(lane < c && less <= tg && tg < upto);
-                    const uint64_t best = readlane_u64(ck, hit ? __builtin_ctzll(hit) : 0);
-                    if (lane == 0) v.sum_q[((size_t)row * v.ntheta + th) * nq + j] = key_value(best);
+                    const int hl = hit ? __builtin_ctzll(hit) : 0;
+                    const uint64_t best = readlane_u64(ck, hl);
+                    if (UNW) {   // a, count{x <= a}, and the minimum of the successor search
+                        const uint64_t cle = readlane_u64(upto, hl);
+                        if (lane == 0) { st_prefix[j] = best; st_below[j] = cle; st_bin[j] = ~0ULL; }
+                    } else if (lane == 0) v.sum_q[((size_t)row * v.ntheta + th) * nq + j] = key_value(best);
                 }
             }
         }
@@ -201,7 +221,7 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
                 hb[0] = hb[1] = hb[2] = hb[3] = 0;   // ready for the next pass / step
                 const uint64_t sum = h0 + h1 + h2 + h3;
                 const uint64_t excl = wave_incl_scan(sum, lane) - sum;
-                const uint64_t target = pass ? st_target[j] : __umul64hi(v.sum_p64[j], S);
+                const uint64_t target = pass ? st_target[j] : target_of(j);
                 const uint64_t prefix = pass ? st_prefix[j] : 0;
                 uint64_t run = (pass ? st_below[j] : 0) + excl;
                 const uint64_t hh[4] = {h0, h1, h2, h3};
@@ -212,12 +232,37 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
                         st_prefix[j] = np_;
                         st_below[j] = run;
                         st_target[j] = target;
-                        if (pass == 7) v.sum_q[((size_t)row * v.ntheta + th) * nq + j] = key_value(np_);
+                        if (pass == 7) {
+                            if (UNW) { st_below[j] = run + hh[t]; st_bin[j] = ~0ULL; }
+                            else v.sum_q[((size_t)row * v.ntheta + th) * nq + j] = key_value(np_);
+                        }
                     }
                     run += hh[t];
                 }
             }
             __syncthreads();
+        }
+        if (UNW) {   // b = x_(j+1): a again when more than j values are <= a, else the smallest key above key(a); then the quantile
+            __syncthreads();
+            for (int j = 0; j < nq; ++j) {
+                const Q7Rank r = q7_rank((int64_t)v.n, bits2d(v.sum_p64[j]));
+                if (st_below[j] > (uint64_t)r.j) continue;   // (workgroup-uniform)
+                const uint64_t ka = st_prefix[j];
+                uint64_t m = ~0ULL;
+#pragma unroll
+                for (int i = 0; i < NQ; ++i) m = (q[i] && key[i] > ka && key[i] < m) ? key[i] : m;
+                for (int dd = WAVE / 2; dd >= 1; dd >>= 1) {
+                    const uint64_t o = __shfl_xor((unsigned long long)m, dd, WAVE);
+                    m = o < m ? o : m;
+                }
+                if (lane == 0 && m != ~0ULL) atomicMin((unsigned long long*)&st_bin[j], (unsigned long long)m);
+            }
+            __syncthreads();
+            if (tid < nq) {
+                const Q7Rank r = q7_rank((int64_t)v.n, bits2d(v.sum_p64[tid]));
+                const uint64_t ka = st_prefix[tid], kb = st_below[tid] > (uint64_t)r.j ? ka : st_bin[tid];
+                v.sum_q[((size_t)row * v.ntheta + th) * nq + tid] = q7_interp(key_value(ka), key_value(kb), r.g);
+            }
         }
     }
     if (v.sum_mom) {
@@ -227,6 +272,7 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
                                         // order (the same mean everywhere), then w (x - mean)^2
             double a = 0.0;
             for (int w = 0; w < NW; ++w) a += red[(0 * 3 + c) * 16 + w];
+            if (UNW) a = a / (double)v.n;
             double m2 = 0.0;
 #pragma unroll
             for (int k = 0; k < NP; ++k) {
@@ -245,6 +291,7 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
             double a = 0.0, b2 = 0.0;
             for (int w = 0; w < NW; ++w) { a += red[(0 * 3 + tid) * 16 + w]; b2 += red[(1 * 3 + tid) * 16 + w]; }
             const double nan = bits2d(0x7ff8000000000000ULL);   // collapsed filter: no moments
+            if (UNW) { a = a / (double)v.n; b2 = b2 / (double)(v.n - 1); }   // (n == 1: 0 / 0, NaN as Statistics.var)
             v.sum_m[(((size_t)row * 2 + 0) * D + tid) * v.ntheta + th] = S ? a : nan;
             v.sum_m[(((size_t)row * 2 + 1) * D + tid) * v.ntheta + th] = S ? b2 : nan;
         }
@@ -253,7 +300,7 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
 
 // The summaries of the CURRENT state of single-segment filters in one launch (smc_get_quantiles / smc_get_moments between two
 // steps of the README loop, README.md:41,51): state and weights of buffer `cur` into LDS, then the per-step routine above, row 0.
-template <int THREADS, int NP, int D>
+template <int THREADS, int NP, int D, bool UNW = false>
 __global__ __launch_bounds__(THREADS) void k_summ_once(FilterView v, int cur) {
     constexpr int SEG = 2 * NP * THREADS, SEGP = lds_padded_len(SEG);
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -271,7 +318,7 @@ __global__ __launch_bounds__(THREADS) void k_summ_once(FilterView v, int cur) {
     }
     for (int i = tid; i < (int)summary_lds_words(v.sum_np); i += THREADS) sm[i] = 0;
     __syncthreads();
-    resident_summaries<THREADS, NP, D>(v, th, 0, Cs, xs, SEGP, v.segS[cur][th], sm);
+    resident_summaries<THREADS, NP, D, UNW>(v, th, 0, Cs, xs, SEGP, v.segS[cur][th], sm);
 }
 template <int D>
 __host__ inline size_t summ_once_lds_bytes(int seg, int nq) { return (size_t)lds_padded_len(seg) * 8 * (1 + D) + summary_lds_words(nq) * 8; }
@@ -289,8 +336,8 @@ template <int MODEL, int THREADS, int NP>
 constexpr int resident_min_waves() {
     return (THREADS == 512 && NP == 1) ? 4 : 1;
 }
-// SUMM: per-step summaries (resident_summaries) after every step, for the levels / coordinate the view names
-template <int MODEL, int THREADS, int NP, bool SYS = false, bool WIN = false, bool SUMM = false>
+// SUMM: per-step summaries (resident_summaries) after every step, for the levels / coordinate the view names; UNW: its mode
+template <int MODEL, int THREADS, int NP, bool SYS = false, bool WIN = false, bool SUMM = false, bool UNW = false>
 __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())) void k_resident(FilterView v, int T, StepRec* recs /*[ntheta][T]*/, int t0, int bin, int bout,
                                                       double* win) {
     constexpr int D = model_dim<MODEL>::value;
@@ -505,7 +552,7 @@ __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())
             usys[w] = ((uint64_t)uw.v[1] << 32) | uw.v[0];
         }
         __syncthreads();  // Cs, xs complete; scr free
-        if (SUMM) resident_summaries<THREADS, NP, D>(v, th, (int64_t)(t - t0), Cs, xs, SEGP, S, sm);
+        if (SUMM) resident_summaries<THREADS, NP, D, UNW>(v, th, (int64_t)(t - t0), Cs, xs, SEGP, S, sm);
     }
 
     // state out: same layout as the k_step path leaves it (log_likelihood: buffer 0)

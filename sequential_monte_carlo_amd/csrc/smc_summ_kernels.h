@@ -23,6 +23,15 @@
 // moments are StatsBase's uncorrected weighted mean and variance: sums of doubles in a fixed order (segment by segment), the
 // variance centred on the mean (a second read of the cloud: its error scales with var, not with mean^2 as that of
 // sum w x^2 - mean^2 does); NaN for a collapsed filter.  DESIGN.md section 2 states the bound.
+//
+// UNW (smc_set_summary_mode, SMC_SUMM_UNWEIGHTED; a template parameter: the weighted kernels are the code they were): quantile(x, p)
+// and var(x) of the cloud whatever its weights (include/smc_hip.h "summary modes").  Every particle counts W = 1, the range is that
+// of all particles, the total is n and the target of a level the rank j of a = x_(j) (q7_rank): the same chain selects a and knows
+// count{x <= a}.  k_ms_select then leaves (key(a), that count) in the level's state instead of a result, and two more launches end
+// the chain:
+//   k_ms_succ     per level that needs it (count <= j): the smallest key above key(a) over ALL particles - a minimum of integers
+//   k_ms_interp   b = a or that successor; the quantile a + g (b - a) (q7_interp)
+// Moments: the partial sums of x and of (x - mean)^2 in the same fixed order; mean = sum / n, var = sum / (n - 1).
 #pragma once
 #include "smc_kernels.h"
 
@@ -41,6 +50,7 @@ struct MsScratch {
     unsigned long long* hist;    // [ntheta][MS_BINS]
     uint64_t* hdr;               // [ntheta][4]            lo, scale (doubles) | usable (0 / 1) | total weight
     uint64_t* st;                // [ntheta][QMAX][6]      bin | weight below | target | state (0 fallback, 1 binned, 2 no weight) | sub-bin | -
+                                 //                        UNW, behind k_ms_select: key(a) | count{x <= a} | . | . | . | smallest key above key(a)
     unsigned long long* hist2;   // [ntheta][QMAX][MS_BINS]  second level (filters beyond MS_TWO_LEVEL particles): the chosen bin cut again
     unsigned* cnt;               // [ntheta][QMAX]         candidates collected per level
     uint64_t* cand;              // [ntheta][QMAX][MS_CAP][2]   (key, W)
@@ -69,6 +79,16 @@ __device__ __forceinline__ MsSeg ms_segment(const FilterView& v, int cur, int th
     s.sh = seg_shift(K, kb, v.SH);
     s.sc = (dk >= 0.0 && dk < 900.0) ? pow2i(-48 - (int)dk) : 0.0;
     return s;
+}
+// the weight of a particle in the selection: table units of its integer weight, or (UNW) one
+template <bool UNW>
+__device__ __forceinline__ uint64_t ms_weight(uint64_t q, const MsSeg& sg) { return UNW ? 1 : (sg.sh < 64 ? q >> sg.sh : 0); }
+// the (0-based) target of level j among a total of `tot`: the weight below the quantile / (UNW, tot = n) the rank of a
+template <bool UNW>
+__device__ __forceinline__ uint64_t ms_target(const FilterView& v, int j, uint64_t tot) {
+    if (!UNW) return __umul64hi(v.sum_p64[j], tot);
+    const int64_t r = q7_rank((int64_t)tot, bits2d(v.sum_p64[j])).j;
+    return (uint64_t)(r > 1 ? r - 1 : 0);
 }
 __device__ __forceinline__ int ms_bin(double x, double lo, double scale) {
     const int b = (int)((x - lo) * scale);   // monotone in x: differences, products and truncation all are
@@ -108,6 +128,7 @@ __device__ __forceinline__ void ms_for_each(const FilterView& v, int cur, int th
 }
 
 // grid (G, ntheta): per workgroup the range of the weighted values and the partial sums of the mean
+template <bool UNW>
 __global__ __launch_bounds__(MS_STREAM) void k_ms_range(FilterView v, int cur, int d, MsScratch ms) {
     constexpr int NW = MS_STREAM / WAVE;
     __shared__ double red[5][NW];
@@ -119,7 +140,7 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_range(FilterView v, int cur, i
     const bool want_q = v.sum_np != 0, want_m = v.sum_mom != 0;
     ms_for_each(v, cur, th, v.sum_comp, [&](int64_t i, uint64_t q, double xq, const MsSeg& sg) {
         if (want_q) {
-            const uint64_t W = sg.sh < 64 ? q >> sg.sh : 0;
+            const uint64_t W = ms_weight<UNW>(q, sg);
             if (W) {
                 odd = odd || !(fabs(xq) < inf());
                 vhi = xq > vhi ? xq : vhi;
@@ -127,7 +148,7 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_range(FilterView v, int cur, i
             }
         }
         if (want_m) {
-            const double w = Dtot ? ((double)q * sg.sc) / Dd : 0.0;
+            const double w = UNW ? 1.0 : Dtot ? ((double)q * sg.sc) / Dd : 0.0;
             if (w)
                 for (int c = 0; c < d; ++c) mo[c] += w * (c == v.sum_comp ? xq : v.x[cur][((size_t)c * v.ntheta + th) * v.npad + i]);
         }
@@ -162,6 +183,7 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_range(FilterView v, int cur, i
 
 // grid (G, ntheta), moments only, behind k_ms_pick: per workgroup the partial sums of w (x - mean)^2 (the same particles, order and
 // dense weights as k_ms_range's partial sums of w x)
+template <bool UNW>
 __global__ __launch_bounds__(MS_STREAM) void k_ms_center(FilterView v, int cur, int d, MsScratch ms, const double* mean) {
     constexpr int NW = MS_STREAM / WAVE;
     __shared__ double red[3][NW];
@@ -171,7 +193,7 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_center(FilterView v, int cur, 
     double mu[3] = {0.0, 0.0, 0.0}, mo2[3] = {0.0, 0.0, 0.0};
     for (int c = 0; c < d; ++c) mu[c] = mean[(size_t)c * v.ntheta + th];
     ms_for_each(v, cur, th, 0, [&](int64_t i, uint64_t q, double x0, const MsSeg& sg) {
-        const double w = Dtot ? ((double)q * sg.sc) / Dd : 0.0;
+        const double w = UNW ? 1.0 : Dtot ? ((double)q * sg.sc) / Dd : 0.0;
         if (w)
             for (int c = 0; c < d; ++c) {
                 const double e = (c == 0 ? x0 : v.x[cur][((size_t)c * v.ntheta + th) * v.npad + i]) - mu[c];
@@ -208,11 +230,15 @@ __device__ __forceinline__ double ms_moment_total(const MsScratch& ms, int th, i
 }
 
 // grid (ntheta), moments only, behind k_ms_center: var [d][ntheta]
+template <bool UNW>
 __global__ __launch_bounds__(MS_THREADS) void k_ms_var(FilterView v, int d, int nparts, MsScratch ms, double* var) {
     __shared__ double red[MS_THREADS / WAVE];
     const int th = blockIdx.x;
     for (int c = 0; c < d; ++c) {
         const double s2 = ms_moment_total(ms, th, d, c, 1, nparts, red);
+        if (UNW) {
+            if (threadIdx.x == 0) var[(size_t)c * v.ntheta + th] = s2 / (double)(v.n - 1);   // (n == 1: 0 / 0, NaN as Statistics.var)
+        } else
         if (threadIdx.x == 0) var[(size_t)c * v.ntheta + th] = v.last_D[th] ? s2 : bits2d(0x7ff8000000000000ULL);   // collapsed: NaN
     }
 }
@@ -241,6 +267,7 @@ __device__ __forceinline__ void ms_range_of(const MsScratch& ms, int th, int npa
 }
 
 // grid (G, ntheta): few, large workgroups - each flushes its LDS histogram with one device-scope atomic per occupied bin
+template <bool UNW>
 __global__ __launch_bounds__(MS_STREAM) void k_ms_hist(FilterView v, int cur, int nparts, MsScratch ms) {
     __shared__ unsigned long long lh[MS_BINS];
     __shared__ double red[2 * (MS_STREAM / WAVE)];
@@ -257,7 +284,7 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_hist(FilterView v, int cur, in
     for (int i = tid; i < MS_BINS; i += MS_STREAM) lh[i] = 0;
     __syncthreads();
     ms_for_each(v, cur, th, v.sum_comp, [&](int64_t, uint64_t q, double x, const MsSeg& sg) {
-        const uint64_t W = sg.sh < 64 ? q >> sg.sh : 0;
+        const uint64_t W = ms_weight<UNW>(q, sg);
         if (W) atomicAdd(&lh[ms_bin(x, lo, scale)], (unsigned long long)W);
     });
     __syncthreads();
@@ -266,6 +293,7 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_hist(FilterView v, int cur, in
 }
 
 // grid (ntheta): the filter's histogram -> total, targets, bins; the mean.  mean: [d][ntheta] rows of the output
+template <bool UNW>
 __global__ __launch_bounds__(MS_THREADS) void k_ms_pick(FilterView v, int d, int nparts, MsScratch ms, double* q_out, double* mean) {
     constexpr int NW = MS_THREADS / WAVE, PER = MS_BINS / MS_THREADS;
     __shared__ uint64_t wt[NW];
@@ -274,6 +302,9 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_pick(FilterView v, int d, int
     if (v.sum_mom)
         for (int c = 0; c < d; ++c) {
             const double s = ms_moment_total(ms, th, d, c, 0, nparts, red);
+            if (UNW) {
+                if (tid == 0) mean[(size_t)c * v.ntheta + th] = s / (double)v.n;
+            } else
             if (tid == 0) mean[(size_t)c * v.ntheta + th] = v.last_D[th] ? s : bits2d(0x7ff8000000000000ULL);   // collapsed: NaN
         }
     const int nq = v.sum_np;
@@ -300,7 +331,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_pick(FilterView v, int d, int
             if (tid == 0) { st[j * 6 + 3] = 2; q_out[(size_t)th * nq + j] = bits2d(0x7ff8000000000000ULL); }
             continue;
         }
-        const uint64_t target = __umul64hi(v.sum_p64[j], tot);
+        const uint64_t target = ms_target<UNW>(v, j, tot);
         if (sum && excl <= target && target < excl + sum) {   // exactly one thread
             uint64_t run = excl;
 #pragma unroll
@@ -319,6 +350,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_pick(FilterView v, int d, int
 
 // second level (filters beyond MS_TWO_LEVEL particles): the particles of every level's chosen bin, a few thousand, cut into MS_BINS
 // sub-bins - few enough for device-scope atomics straight into the level's histogram.  grid (G, ntheta)
+template <bool UNW>
 __global__ __launch_bounds__(MS_STREAM) void k_ms_hist2(FilterView v, int cur, MsScratch ms) {
     const int th = blockIdx.y, nq = v.sum_np;
     if (!ms.hdr[(size_t)th * 4 + 2] || !ms.hdr[(size_t)th * 4 + 3]) return;
@@ -327,7 +359,7 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_hist2(FilterView v, int cur, M
 #pragma unroll
     for (int j = 0; j < QMAX; ++j) sb[j] = j < nq ? (int)ms.st[((size_t)th * QMAX + j) * 6] : -1;
     ms_for_each(v, cur, th, v.sum_comp, [&](int64_t, uint64_t q, double x, const MsSeg& sg) {
-        const uint64_t W = sg.sh < 64 ? q >> sg.sh : 0;
+        const uint64_t W = ms_weight<UNW>(q, sg);
         if (!W) return;
         int sub;
         const int bin = ms_bin2(x, lo, scale, sub);
@@ -367,7 +399,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_pick2(FilterView v, MsScratch
 
 // grid (G, ntheta): a workgroup keeps its matches in LDS (MS_STASH per level) and asks for room in the level's list ONCE - the
 // list's counter is one address all workgroups of a filter share; a match beyond the stash asks by itself
-template <bool TWO>
+template <bool TWO, bool UNW>
 __global__ __launch_bounds__(MS_STREAM) void k_ms_collect(FilterView v, int cur, MsScratch ms) {
     __shared__ uint64_t stash[QMAX][MS_STASH][2];
     __shared__ unsigned ln[QMAX], lbase[QMAX];
@@ -383,7 +415,7 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_collect(FilterView v, int cur,
     if (tid < QMAX) ln[tid] = 0;
     __syncthreads();
     ms_for_each(v, cur, th, v.sum_comp, [&](int64_t, uint64_t q, double x, const MsSeg& sg) {
-        const uint64_t W = sg.sh < 64 ? q >> sg.sh : 0;
+        const uint64_t W = ms_weight<UNW>(q, sg);
         if (!W) return;
         int sub = 0;
         const int bin = TWO ? ms_bin2(x, lo, scale, sub) : ms_bin(x, lo, scale);
@@ -420,7 +452,8 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_collect(FilterView v, int cur,
     }
 }
 
-// grid (nq, ntheta): the quantile of one level of one filter
+// grid (nq, ntheta): the quantile of one level of one filter (UNW: key(a) and count{x <= a} into the level's state)
+template <bool UNW>
 __global__ __launch_bounds__(MS_SEL_THREADS) void k_ms_select(FilterView v, int cur, MsScratch ms, double* q_out) {
     constexpr int NW = MS_SEL_THREADS / WAVE;
     __shared__ uint64_t ck[MS_CAP], cw[MS_CAP];
@@ -428,7 +461,7 @@ __global__ __launch_bounds__(MS_SEL_THREADS) void k_ms_select(FilterView v, int 
     __shared__ uint64_t wt[NW], ck_mx[NW];
     __shared__ uint64_t sel[2];   // prefix, below
     const int jq = blockIdx.x, th = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE, nq = v.sum_np;
-    const uint64_t* st = ms.st + ((size_t)th * QMAX + jq) * 6;
+    uint64_t* st = ms.st + ((size_t)th * QMAX + jq) * 6;
     const uint64_t state = st[3];
     const unsigned c = ms.cnt[(size_t)th * QMAX + jq];
     __syncthreads();
@@ -449,7 +482,7 @@ __global__ __launch_bounds__(MS_SEL_THREADS) void k_ms_select(FilterView v, int 
             const int b = (int)(i / v.seg), j = (int)(i % v.seg);
             const int sh = ms_segment(v, cur, th, b).sh;
             const uint64_t q = C[i] - (j ? C[i - 1] : 0);
-            s += sh < 64 ? q >> sh : 0;
+            s += UNW ? 1 : (sh < 64 ? q >> sh : 0);
         }
         s = wave_sum(s);
         if (lane == 0) wt[wave] = s;
@@ -461,7 +494,7 @@ __global__ __launch_bounds__(MS_SEL_THREADS) void k_ms_select(FilterView v, int 
             if (tid == 0) q_out[(size_t)th * nq + jq] = bits2d(0x7ff8000000000000ULL);
             return;
         }
-        target = __umul64hi(v.sum_p64[jq], tot);
+        target = ms_target<UNW>(v, jq, tot);
         below0 = 0;
     }
     // the candidates of one value bin share the leading bytes of their keys (sign, exponent, the first mantissa bits): those passes
@@ -482,6 +515,9 @@ __global__ __launch_bounds__(MS_SEL_THREADS) void k_ms_select(FilterView v, int 
         kmn = wt[0]; kmx = ck_mx[0];
         for (int w = 1; w < NW; ++w) { kmn = wt[w] < kmn ? wt[w] : kmn; kmx = ck_mx[w] > kmx ? ck_mx[w] : kmx; }
         if (kmn == kmx) {
+            if (UNW) {
+                if (tid == 0) { st[0] = kmn; st[1] = below0 + c; st[5] = ~0ULL; }
+            } else
             if (tid == 0) q_out[(size_t)th * nq + jq] = key_value(kmn);
             return;
         }
@@ -502,7 +538,7 @@ __global__ __launch_bounds__(MS_SEL_THREADS) void k_ms_select(FilterView v, int 
                 const int b = (int)(i / v.seg), j = (int)(i % v.seg);
                 const int sh = ms_segment(v, cur, th, b).sh;
                 const uint64_t q = C[i] - (j ? C[i - 1] : 0);
-                const uint64_t W = sh < 64 ? q >> sh : 0;
+                const uint64_t W = UNW ? 1 : (sh < 64 ? q >> sh : 0);
                 if (!W) continue;
                 const uint64_t key = order_key(x[i]);
                 if (pass == 0 || (key >> hs) == pref) atomicAdd(&lh[(int)((key >> (hs - 8)) & 255)], (unsigned long long)W);
@@ -521,13 +557,62 @@ __global__ __launch_bounds__(MS_SEL_THREADS) void k_ms_select(FilterView v, int 
                     const uint64_t np_ = (pref << 8) | (uint64_t)(4 * lane + t);
                     sel[0] = np_;
                     sel[1] = run;
-                    if (pass == 7) q_out[(size_t)th * nq + jq] = key_value(np_);
+                    if (pass == 7) {
+                        if (UNW) { st[0] = np_; st[1] = run + hh[t]; st[5] = ~0ULL; }
+                        else q_out[(size_t)th * nq + jq] = key_value(np_);
+                    }
                 }
                 run += hh[t];
             }
         }
         __syncthreads();
     }
+}
+
+// UNW, behind k_ms_select.  grid (G, ntheta): the smallest key above key(a) of every level whose a is not repeated past rank j
+// (count{x <= a} <= j; n >= 2 then, and such a key exists) - per thread, wave, workgroup, then one device-scope minimum per level
+__global__ __launch_bounds__(MS_STREAM) void k_ms_succ(FilterView v, int cur, MsScratch ms) {
+    __shared__ unsigned long long lmin[QMAX];
+    const int th = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1), nq = v.sum_np;
+    uint64_t* st = ms.st + (size_t)th * QMAX * 6;
+    uint64_t ka[QMAX], m[QMAX];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < QMAX; ++j) {
+        const bool need = j < nq && st[j * 6 + 1] <= (uint64_t)q7_rank((int64_t)v.n, bits2d(v.sum_p64[j])).j;
+        ka[j] = need ? st[j * 6] : ~0ULL;   // (no key lies above ~0)
+        m[j] = ~0ULL;
+        any = any || need;
+    }
+    if (!any) return;   // (workgroup-uniform)
+    if (tid < QMAX) lmin[tid] = ~0ULL;
+    __syncthreads();
+    ms_for_each(v, cur, th, v.sum_comp, [&](int64_t, uint64_t, double x, const MsSeg&) {
+        const uint64_t key = order_key(x);
+#pragma unroll
+        for (int j = 0; j < QMAX; ++j) m[j] = (key > ka[j] && key < m[j]) ? key : m[j];
+    });
+#pragma unroll
+    for (int j = 0; j < QMAX; ++j) {
+        if (ka[j] == ~0ULL) continue;   // (workgroup-uniform)
+        uint64_t mm = m[j];
+        for (int dd = WAVE / 2; dd >= 1; dd >>= 1) {
+            const uint64_t o = __shfl_xor((unsigned long long)mm, dd, WAVE);
+            mm = o < mm ? o : mm;
+        }
+        if (lane == 0 && mm != ~0ULL) atomicMin(&lmin[j], (unsigned long long)mm);
+    }
+    __syncthreads();
+    if (tid < nq && lmin[tid] != ~0ULL) atomicMin((unsigned long long*)&st[tid * 6 + 5], lmin[tid]);
+}
+// UNW, last.  grid (ntheta): the quantiles from (key(a), count{x <= a}, successor) of every level
+__global__ __launch_bounds__(WAVE) void k_ms_interp(FilterView v, MsScratch ms, double* q_out) {
+    const int th = blockIdx.x, j = threadIdx.x, nq = v.sum_np;
+    if (j >= nq) return;
+    const uint64_t* st = ms.st + ((size_t)th * QMAX + j) * 6;
+    const Q7Rank r = q7_rank((int64_t)v.n, bits2d(v.sum_p64[j]));
+    const uint64_t ka = st[0], kb = st[1] > (uint64_t)r.j ? ka : st[5];
+    q_out[(size_t)th * nq + j] = q7_interp(key_value(ka), key_value(kb), r.g);
 }
 
 }  // namespace smc

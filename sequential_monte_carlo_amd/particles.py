@@ -65,6 +65,22 @@ class _Filters:
         return float(a[0]) if self.single else a
 
 
+class _summary_mode:
+    """the handle in the summary mode of one call (weighted=False: the unweighted mode), restored afterwards"""
+
+    def __init__(self, h, weighted):
+        self.h, self.mode = h, "weighted" if weighted else "unweighted"
+
+    def __enter__(self):
+        self.old = self.h.summary_mode
+        if self.mode != self.old:
+            self.h.set_summary_mode(self.mode)
+
+    def __exit__(self, *exc):
+        if self.mode != self.old:
+            self.h.set_summary_mode(self.old)
+
+
 class Particles:
     """x: the particle states, resident on the GPU.  np.asarray(x) -> [N] (scalar state), [N, d], or with
     a leading batch axis for a list of models."""
@@ -82,19 +98,25 @@ class Particles:
     def __len__(self):
         return self._f.h.n_x
 
-    def moments(self):
-        """(mean, variance) of the filtered state under the current weights, computed on the device."""
-        m, v = self._f.h.moments()           # [d][n_theta]
+    def moments(self, weighted=True):
+        """(mean, variance) of the filtered state under the current weights, computed on the device.  weighted=False: the sample
+        mean and the corrected variance of the cloud itself, mean(x) and var(x) (README.md:33-61 of the reference)."""
+        with _summary_mode(self._f.h, weighted):
+            m, v = self._f.h.moments()       # [d][n_theta]
         m, v = m.T, v.T
         if m.shape[-1] == 1:
             m, v = m[..., 0], v[..., 0]
         return (m[0], v[0]) if self._f.single else (m, v)
 
-    def quantile(self, p, component=0):
-        """Weighted quantiles of the filtered state (`quantile(x, weights(w), p)`,
-        examples/inflation_example.jl:45), computed on the device: the inverse of the weighted
-        empirical CDF (no interpolation between particles).  [len(p)] or [n_theta][len(p)]."""
-        q = self._f.h.quantiles(p, component)
+    def quantile(self, p, component=0, weighted=True):
+        """Quantiles of the filtered state, computed on the device.  [len(p)] or [n_theta][len(p)].
+        weighted=True: the inverse of the weighted empirical CDF (no interpolation between particles).
+        weighted=False: `quantile(x, p)` of the cloud whatever its weights, as the reference's README loop and UCSV example
+        compute it (Statistics.quantile: Hyndman-Fan type 7, interpolating; numpy's default method), bit for bit.
+        Not offered: StatsBase's weighted *interpolating* `quantile(x, weights(w), p)` of get_quantiles_uc
+        (examples/inflation_example.jl:45) - StatsBase is not part of the reference tree, so it cannot be pinned."""
+        with _summary_mode(self._f.h, weighted):
+            q = self._f.h.quantiles(p, component)
         return q[0] if self._f.single else q
 
     def ancestors(self):
@@ -153,13 +175,15 @@ def _summaries_out(f, T):
 
 
 def log_likelihood(N, y, model, seed=None, seg=0, device=0, streams=None, ancestors=False, trace=False,
-                   resampler="multinomial", quantiles=None, component=0, moments=False):
+                   resampler="multinomial", quantiles=None, component=0, moments=False, weighted=True):
     """x, w, logZ = log_likelihood(N, y, model)   particles.jl:132-147
     trace=True additionally returns the per-step (logmu_t, ess_t).  resampler="systematic": opt-in systematic
     resampling (same expectation, lower variance, one launch per step for big filters; not the reference's law).
     quantiles=[...] / moments=True: the README loop (README.md:33-61: bootstrap_filter!, then quantile(x, ...) at every
-    observation) as ONE call - the per-step weighted quantiles of state coordinate `component` and / or mean and variance
-    are computed on the device inside the filter loop and returned as a dict behind the usual results."""
+    observation) as ONE call - the per-step quantiles of state coordinate `component` and / or mean and variance are computed
+    on the device inside the filter loop and returned as a dict behind the usual results.  weighted=False gives the README's own
+    numbers: the unweighted type-7 `quantile(x, p)` and the corrected `var(x)` of the cloud (see Particles.quantile);
+    weighted=True (the default) the weighted inverse CDF and the uncorrected weighted variance."""
     if seed is None:
         seed = next(_seed_counter)
     f = _Filters(int(N), model, seed, seg, device, streams, ancestors, resampler)
@@ -168,8 +192,9 @@ def log_likelihood(N, y, model, seed=None, seg=0, device=0, streams=None, ancest
     if summ:
         f.h.set_summaries(quantiles, component, moments)
         try:
-            res = f.h.log_likelihood(y, trace=trace)
-            extra = _summaries_out(f, y.size)
+            with _summary_mode(f.h, weighted):
+                res = f.h.log_likelihood(y, trace=trace)
+                extra = _summaries_out(f, y.size)
         finally:
             f.h.set_summaries()
         if trace:

@@ -281,20 +281,40 @@ def _per_theta(smc, local):
     return smc._gather(local.ravel()).reshape(smc.M, k)
 
 
-def filtered_summaries(smc, p=(0.25, 0.5, 0.75), component=0):
+class _literal_mode:
+    """the online filters' handle in the unweighted summary mode (literal=True) for one block, weighted again afterwards"""
+
+    def __init__(self, main, literal):
+        self.main, self.literal = main, bool(literal)
+        if self.literal and not hasattr(main, "set_summary_mode"):
+            raise NotImplementedError("literal=True needs the device's unweighted summary mode (smc_set_summary_mode)")
+
+    def __enter__(self):
+        if self.literal:
+            self.main.set_summary_mode("unweighted")
+
+    def __exit__(self, *exc):
+        if self.literal:
+            self.main.set_summary_mode("weighted")
+
+
+def filtered_summaries(smc, p=(0.25, 0.5, 0.75), component=0, literal=False):
     """(quantiles [len(p)], variance) of the filtered state of the online sampler, integrated over the parameter particles:
-    per theta-particle the weighted quantiles and variance of its x cloud, then their omega-weighted means - what
-    get_quantiles_uc computes every period in examples/inflation_example.jl:39-55.
-    The per-filter summaries are computed on the device (smc_get_quantiles / smc_get_moments): no cloud leaves the GPU.
-    DEVIATIONS from the example, on purpose (parity unpinned: no reference fixture covers these numbers): (1) the example's
-    UCSV variant (:244-248) takes UNWEIGHTED quantile(x_cloud) / var(x_cloud) of the clouds and multiplies by the raw smc.ω;
-    here both variants use the w-weighted summaries of the UC variant and the normalised omega (right after rejuvenate! the
-    reference's ω is all ones: its sum is then M times the mean).  (2) The quantile is the inverse of the weighted empirical
-    CDF in the filter's integer weights (smc_get_quantiles), not StatsBase's interpolating definition (not vendored)."""
+    per theta-particle the quantiles and variance of its x cloud, then their omega-weighted means.
+    literal=False: the w-weighted summaries per filter (the inverse of the weighted empirical CDF in the filter's integer
+    weights, smc_get_quantiles, and the uncorrected weighted variance) - the statistic of get_quantiles_uc
+    (examples/inflation_example.jl:39-55), except that StatsBase's weighted quantile there INTERPOLATES between particles;
+    that variant is not offered (StatsBase is not part of the reference tree, so it cannot be pinned).
+    literal=True: get_quantiles_ucsv (:241-252) - per filter the UNWEIGHTED type-7 quantile(x_cloud, p) and the corrected
+    var(x_cloud) of the cloud as the filter leaves it (the device's unweighted summary mode, smc_set_summary_mode).
+    Either way the per-filter summaries are computed on the device: no cloud leaves the GPU.  One deviation remains in both:
+    omega is the normalised one (the example multiplies by the raw smc.ω, all ones right after rejuvenate!: its sum is then M
+    times the mean)."""
     if smc._main is None:
         raise ValueError("filtered_summaries needs the online sampler's filters (call smc2 first)")
-    q = np.asarray(smc._main.quantiles(list(p), component))            # [M_local][len(p)]
-    _, var = smc._main.moments()                                       # [d][M_local]
+    with _literal_mode(smc._main, literal):
+        q = np.asarray(smc._main.quantiles(list(p), component))        # [M_local][len(p)]
+        _, var = smc._main.moments()                                   # [d][M_local]
     return _integrate(smc.omega, _per_theta(smc, np.column_stack([q, np.asarray(var)[component]])))
 
 
@@ -529,7 +549,7 @@ def _window_summaries(smc, t, lik_local, j, logw_local):
     return rows
 
 
-def smc2_run(smc, y, t_from, t_to, window=16, verbose=True, out=sys.stdout, summaries=None, component=0):
+def smc2_run(smc, y, t_from, t_to, window=16, verbose=True, out=sys.stdout, summaries=None, component=0, literal=False):
     """for t in t_from:t_to  smc²!(smc, y, t)  end   (the online loop of smc_samplers.jl:308-340 / README.md:93-101),
     with the same results bit for bit, but up to `window` propagation steps per device call: between two
     resample-move decisions the inner filters only need y[t], so a window of steps runs in ONE launch with the particle
@@ -540,17 +560,20 @@ def smc2_run(smc, y, t_from, t_to, window=16, verbose=True, out=sys.stdout, summ
     summaries=[p...] (optional): additionally collect, after every step, what the example's loop collects per period
     (examples/inflation_example.jl:78-86: get_quantiles_uc(smc) after each smc²!) - filtered_summaries(smc, p, component) -
     from per-step summaries recorded on the device inside the window launches; returned as smc.summary_trace =
-    [(t, quantiles [len(p)], variance)], bit-identical to calling filtered_summaries after every smc2_step."""
+    [(t, quantiles [len(p)], variance)], bit-identical to calling filtered_summaries after every smc2_step.
+    literal=True: the summaries are filtered_summaries(..., literal=True) (unweighted per-filter quantiles, corrected variance)."""
     y = np.asarray(y, dtype=np.float64)
     t = int(t_from)
-    smc._summ = None if summaries is None else {"p": [float(v) for v in summaries], "component": int(component)}
+    smc._summ = None if summaries is None else {"p": [float(v) for v in summaries], "component": int(component), "literal": bool(literal)}
+    if smc._summ and literal and smc._main is not None:
+        _literal_mode(smc._main, True)                                   # (fails here, not mid-run, where the mode does not exist)
     smc.summary_trace = []
     while t <= t_to:
         k = min(int(window), t_to - t + 1)
         if k <= 1 or not getattr(smc._main, "can_window", False):
             smc2_step(smc, y, t, verbose, out)
             if smc._summ:
-                qq, vv = filtered_summaries(smc, smc._summ["p"], smc._summ["component"])
+                qq, vv = filtered_summaries(smc, smc._summ["p"], smc._summ["component"], smc._summ["literal"])
                 smc.summary_trace.append((t, qq, vv))
             t += 1
             continue
@@ -564,7 +587,7 @@ def smc2_run(smc, y, t_from, t_to, window=16, verbose=True, out=sys.stdout, summ
                 _step_only(smc, y, t, verbose, out)
                 if smc._summ:
                     smc._sync_outer()
-                    qq, vv = filtered_summaries(smc, smc._summ["p"], smc._summ["component"])
+                    qq, vv = filtered_summaries(smc, smc._summ["p"], smc._summ["component"], smc._summ["literal"])
                     smc.summary_trace.append((t, qq, vv))
                 t += 1
                 continue
@@ -572,12 +595,13 @@ def smc2_run(smc, y, t_from, t_to, window=16, verbose=True, out=sys.stdout, summ
         if smc._summ:
             smc._main.set_summaries(smc._summ["p"], smc._summ["component"], moments=True)
         try:
-            lik, _ = smc._main.step_window(y[t - 1: t - 1 + k])          # [k][M_local]
-            lik = np.asarray(lik, dtype=np.float64)
-            logw_before = smc.logw[smc.lo:smc.hi].copy()
-            ess, j = smc.outer.window_walk(smc, lik, smc.ess_min)
-            if smc._summ:
-                smc.summary_trace.extend(_window_summaries(smc, t, lik, j, logw_before))
+            with _literal_mode(smc._main, smc._summ is not None and smc._summ["literal"]):
+                lik, _ = smc._main.step_window(y[t - 1: t - 1 + k])      # [k][M_local]
+                lik = np.asarray(lik, dtype=np.float64)
+                logw_before = smc.logw[smc.lo:smc.hi].copy()
+                ess, j = smc.outer.window_walk(smc, lik, smc.ess_min)
+                if smc._summ:
+                    smc.summary_trace.extend(_window_summaries(smc, t, lik, j, logw_before))
         finally:
             if smc._summ:
                 smc._main.set_summaries()                                # (the traces are read: recording off again)
