@@ -63,6 +63,45 @@ int smc_set_params(smc_handle h, const double* raw /*[n_theta][n_raw]*/);
 int smc_set_streams(smc_handle h, const uint32_t* stream /*[n_theta]*/);
 int smc_reseed(smc_handle h, uint64_t seed);
 
+/* ---- proposals: the guided particle filter ----------------------------------------------------
+ * particle_filter(N, y, model, proposal) / particle_filter!(x, w, y, model, proposal)          src/particles.jl:28-84
+ * A handle has a proposal.  SMC_PROP_NONE (the default of a fresh or recycled handle) is the bootstrap filter.  With a proposal
+ * every step after the first draws x from it instead of the transition and weights it as particles.jl:72-80 does,
+ *     logw = logpdf(observation(x), y) + logpdf(transition(xp), x) - logpdf(proposal(xp, y), x),
+ * with the normals of the bootstrap step (one per state coordinate, the same Philox slots).  Resampling, normalisation, logZ,
+ * ESS, summaries, skip masks, windows, slot moves and PMMH are as without a proposal.
+ *   SMC_PROP_AFFINE   LG1D only.  Row (c0, c1, c2, s2) per filter, s2 > 0 a variance:  m = c0 + c1 xp + c2 y,
+ *                     x = m + sqrt(s2) z,  logw = logobs(x, y) + [logN(x; A xp, Q) - logN(x; m, s2)].
+ *                     The row (0, A, 0, Q) IS the bootstrap filter, bit for bit (the bracket evaluates to +0.0).
+ *   SMC_PROP_OPTIMAL  LG1D: the AFFINE row derived from the model row, with D = B B Q + R: (0, A R / D, B Q / D, Q R / D)
+ *                     (smc_host_optimal_proposal; an AFFINE handle given exactly these doubles computes the same bits).
+ *                     UCSV3D: the log-volatilities move by the transition; with Q = exp(xp[1]), R = exp(x[2]), K = Q / (Q + R):
+ *                     x[0] = xp[0] + K (y - xp[0]) + sqrt(K R) z[0],  logw = logN(y; xp[0], Q + R)  (the closed form of the
+ *                     three terms; it does not depend on x[0]).
+ *   Every other pair (SV1D with a proposal, UCSV3D with AFFINE), an unknown kind, rows with AFFINE missing or given with another
+ *   kind, a row that is not finite or has s2 <= 0: SMC_EINVAL, and the handle is unchanged.
+ * Deviation from the reference, on purpose: the FIRST step is the bootstrap first step (draw from initial_dist, weight by the
+ * observation density).  particle_filter adds logpdf(initial_dist, x) there (:41-44), a slip: its own commented line :43 shows
+ * the intended correction, which is zero for a draw from initial_dist.
+ * The call may be made between steps; it applies from the next smc_step, smc_step_window or smc_log_likelihood (a pending window
+ * is dropped).  smc_set_params after SMC_PROP_OPTIMAL derives the proposal of the new rows; AFFINE rows stay as given.  Like
+ * parameters and stream ids a proposal stays with its slot under smc_permute, smc_copy_from, smc_pack_slots / smc_unpack_slots
+ * and smc_comm_exchange_slots: only the state travels.  smc_pmmh_rejuvenate on a handle with SMC_PROP_OPTIMAL derives the
+ * proposal of every theta' on the device; AFFINE rows stay as set.  The opt-in persistent step kernel is declined by a handle
+ * with a proposal (one launch per step instead). */
+#define SMC_PROP_NONE 0
+#define SMC_PROP_AFFINE 1
+#define SMC_PROP_OPTIMAL 2
+#define SMC_PROP_NPAR 4
+int smc_set_proposal(smc_handle h, int kind, const double* par /*[n_theta][SMC_PROP_NPAR], AFFINE only; else NULL*/);
+int smc_host_optimal_proposal(int model_id, const double* raw, double* par /*[SMC_PROP_NPAR]*/);   /* LG1D */
+/* one particle, one step, on the host: the specification's guided draw and log-weight (tests, Julia-side checks) */
+int smc_host_guided_step(int model_id, const double* raw, int kind, const double* par, const double* xp /*[d]*/,
+                         const double* z /*[d]*/, double y, double* x /*[d]*/, double* logw);
+/* the same for n particles on the device, xp z x [d][n] (parity tests; the twin of smc_device_math) */
+int smc_device_guided_step(int model_id, const double* raw, int kind, const double* par, const double* xp,
+                           const double* z, double y, int64_t n, double* x, double* logw, int device);
+
 /* ---- the hot path ----------------------------------------------------------------------------*/
 /* bootstrap_filter(N, y, model) -> (x, w, logmu)            src/particles.jl:87-105 */
 int smc_init(smc_handle h, double y1, double* logmu /*[n_theta]*/);

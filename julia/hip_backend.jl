@@ -138,6 +138,55 @@ function bootstrap_filter!(states::HipParticles, weights::HipWeights, y::Float64
     return logμ[], HipWeights(f, states.m), ess[]
 end
 
+# ---- the guided filter: particle_filter / particle_filter!          particles.jl:28-84 ---------------------------------
+# proposals are enumerated like the model families (include/smc_hip.h "proposals"): an affine Gaussian row for the linear
+# Gaussian model, the locally optimal proposal for the linear Gaussian and the UCSV model; `nothing` is the bootstrap filter
+struct AffineGaussianProposal; c0::Float64; c1::Float64; c2::Float64; s2::Float64; end   # x ~ N(c0 + c1 xp + c2 y, sqrt(s2))
+struct OptimalProposal end
+const HipProposals = Union{Nothing,AffineGaussianProposal,OptimalProposal}
+function set_proposal!(f::HipFilter, p::HipProposals)
+    if p === nothing
+        smc_check(ccall((:smc_set_proposal, LIBSMC), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), f.h, 0, C_NULL))
+    elseif p isa OptimalProposal
+        smc_check(ccall((:smc_set_proposal, LIBSMC), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), f.h, 2, C_NULL))
+    else
+        rows = repeat([p.c0, p.c1, p.c2, p.s2], f.M)
+        GC.@preserve rows smc_check(ccall((:smc_set_proposal, LIBSMC), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), f.h, 1, rows))
+    end
+    f
+end
+# the locally optimal proposal of a linear Gaussian model as an AffineGaussianProposal
+function optimal_proposal(model::HipModels)
+    id, raw = hip_model(model)
+    par = Vector{Float64}(undef, 4)
+    GC.@preserve raw par smc_check(ccall((:smc_host_optimal_proposal, LIBSMC), Cint, (Cint, Ptr{Float64}, Ptr{Float64}), id, raw, par))
+    return AffineGaussianProposal(par...)
+end
+# particle_filter(N, y, model, proposal) -> (x, w, logμ): the first step is bootstrap_filter's (the reference adds
+# logpdf(initial_dist, x) there, particles.jl:41-44, a slip - see include/smc_hip.h)
+function particle_filter(N::Int64, y::Float64, model::HipModels, proposal::HipProposals)
+    f = set_proposal!(set_models!(HipFilter(hip_model(model)[1], 1, N), [model]), proposal)
+    logμ = Ref{Float64}()
+    smc_check(ccall((:smc_init, LIBSMC), Cint, (Ptr{Cvoid}, Float64, Ptr{Float64}), f.h, y, logμ))
+    return HipParticles(f, 1), HipWeights(f, 1), logμ[]
+end
+# particle_filter!(x, w, y, model, proposal) -> (logμ, w, ess)
+function particle_filter!(states::HipParticles, weights::HipWeights, y::Float64, model::HipModels, proposal::HipProposals)
+    f = set_proposal!(invalidate!(states.f), proposal)
+    logμ = Ref{Float64}(); ess = Ref{Float64}()
+    smc_check(ccall((:smc_step, LIBSMC), Cint, (Ptr{Cvoid}, Float64, Ptr{Float64}, Ptr{Float64}), f.h, y, logμ, ess))
+    return logμ[], HipWeights(f, states.m), ess[]
+end
+# log_likelihood(N, y, model, proposal) -> (x, w, logZ)
+function log_likelihood(N::Int64, y::Vector{Float64}, model::HipModels, proposal::Union{AffineGaussianProposal,OptimalProposal})
+    f = set_proposal!(set_models!(HipFilter(hip_model(model)[1], 1, N), [model]), proposal)
+    logZ = Ref{Float64}()
+    GC.@preserve y smc_check(ccall((:smc_log_likelihood, LIBSMC), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        f.h, y, length(y), logZ, C_NULL, C_NULL))
+    return HipParticles(f, 1), HipWeights(f, 1), logZ[]
+end
+
 # log_likelihood(N, y, model) -> (x, w, logZ)                         particles.jl:132-147
 function log_likelihood(N::Int64, y::Vector{Float64}, model::HipModels)
     f = set_models!(HipFilter(hip_model(model)[1], 1, N), [model])

@@ -28,7 +28,9 @@ EXPORTS = [
     "smc_outer_seg", "smc_host_outer_records", "smc_host_outer_combine", "smc_host_outer_window", "smc_host_outer_walk",
     "smc_host_outer_advance", "smc_host_outer_temper", "smc_host_outer_resample", "smc_host_rw_factor",
     "smc_set_summaries", "smc_get_summaries", "smc_set_summary_mode", "smc_host_quantile7", "smc_host_sample_moments",
+    "smc_set_proposal", "smc_host_optimal_proposal", "smc_host_guided_step", "smc_device_guided_step",
 ]
+PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
 _SUMM_MODES = {"weighted": SUMM_WEIGHTED, "unweighted": SUMM_UNWEIGHTED}
 COMM_ID_BYTES = 128
@@ -109,6 +111,10 @@ def lib():
     L.smc_set_summary_mode.argtypes = [h, C.c_int]
     L.smc_host_quantile7.argtypes = [_dp, C.c_int64, _dp, C.c_int, _dp]
     L.smc_host_sample_moments.argtypes = [_dp, C.c_int64, _dp, _dp]
+    L.smc_set_proposal.argtypes = [h, C.c_int, _dp]
+    L.smc_host_optimal_proposal.argtypes = [C.c_int, _dp, _dp]
+    L.smc_host_guided_step.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, _dp, _dp]
+    L.smc_device_guided_step.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int64, _dp, _dp, C.c_int]
     L.smc_get_summaries.argtypes = [h, C.c_int64, _dp, _dp, _dp]
     L.smc_sys_targets.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.c_int]
     L.smc_simulate.argtypes = [C.c_int, _dp, C.c_int64, C.c_uint64, _dp, _dp]
@@ -220,6 +226,47 @@ def device_math(which, a, b=None, device=0):
     out = np.zeros_like(a)
     check(lib().smc_device_math(which, _d(a), _d(b), a.size, _d(out), device))
     return out
+
+
+def host_optimal_proposal(model_id, raw):
+    """the locally optimal proposal of an LG1D parameter row as an AFFINE row (c0, c1, c2, s2) (smc_host_optimal_proposal; no GPU)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    par = np.zeros(PROP_NPAR)
+    check(lib().smc_host_optimal_proposal(int(model_id), _d(raw), _d(par)))
+    return par
+
+
+def _row_or_none(par):
+    return None if par is None else np.ascontiguousarray(par, dtype=np.float64).ravel()
+
+
+def host_guided_step(model_id, raw, kind, par, xp, z, y):
+    """one particle, one guided step by the specification on the host: (x [d], logw) (smc_host_guided_step; no GPU)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    par = _row_or_none(par)
+    xp = np.ascontiguousarray(xp, dtype=np.float64).ravel()
+    z = np.ascontiguousarray(z, dtype=np.float64).ravel()
+    d = lib().smc_model_dim(int(model_id))
+    assert d > 0 and xp.size == d and z.size == d
+    x = np.zeros(d)
+    lw = C.c_double()
+    check(lib().smc_host_guided_step(int(model_id), _d(raw), int(kind), _d(par), _d(xp), _d(z), float(y), _d(x), C.byref(lw)))
+    return x, lw.value
+
+
+def device_guided_step(model_id, raw, kind, par, xp, z, y, device=0):
+    """the same for n particles on the device: xp, z [d][n] -> (x [d][n], logw [n]) (smc_device_guided_step)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    par = _row_or_none(par)
+    d = lib().smc_model_dim(int(model_id))
+    xp = np.ascontiguousarray(xp, dtype=np.float64).reshape(d, -1)
+    z = np.ascontiguousarray(z, dtype=np.float64).reshape(d, -1)
+    assert xp.shape == z.shape
+    n = xp.shape[1]
+    x = np.zeros((d, n))
+    lw = np.zeros(n)
+    check(lib().smc_device_guided_step(int(model_id), _d(raw), int(kind), _d(par), _d(xp), _d(z), float(y), n, _d(x), _d(lw), device))
+    return x, lw
 
 
 OUTER_SEG = 8     # SMC_OUTER_SEG: entries per segment of the outer level's integer normalisation
@@ -400,6 +447,20 @@ class Handle:
         raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(self.n_theta, -1)
         assert raw.shape[1] == lib().smc_model_nraw(self.model_id)
         check(lib().smc_set_params(self._h, _d(raw)))
+
+    def set_proposal(self, kind, par=None):
+        """the proposal of the handle's filters from the next step on (smc_set_proposal): PROP_NONE (bootstrap, the default),
+        PROP_AFFINE with rows par [n_theta][4] = (c0, c1, c2, s2) (LG1D), or PROP_OPTIMAL (LG1D, UCSV3D; derived from the
+        parameter rows, also after later set_params calls)"""
+        if par is not None:
+            par = np.ascontiguousarray(par, dtype=np.float64)
+            if par.size == PROP_NPAR and self.n_theta > 1:
+                par = np.tile(par.reshape(1, PROP_NPAR), (self.n_theta, 1))
+            if par.size != self.n_theta * PROP_NPAR:
+                raise ValueError("proposal rows must be [n_theta][4]")
+            par = np.ascontiguousarray(par)
+        check(lib().smc_set_proposal(self._h, int(kind), _d(par)))
+        self.proposal_kind = int(kind)
 
     def set_streams(self, streams):
         s = np.ascontiguousarray(streams, dtype=np.uint32)

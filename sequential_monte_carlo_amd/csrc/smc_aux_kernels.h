@@ -229,6 +229,11 @@ __global__ void k_pmmh_propose(FilterView v, PmmhSpec s, PmmhDev p, int model, u
     pmmh_raw_row(s, pr, P.raw);
     derive_params(model, P.raw, P.der);
     params[m] = P;
+    if (v.prop_kind != PROP_NONE) {   // a guided handle: OPTIMAL rows follow theta', AFFINE rows stay as set (their constants are renewed)
+        PropRow R = v.prop[m];
+        derive_proposal(model, v.prop_kind, P.raw, P.der, R.p);
+        v.prop[m] = R;
+    }
 }
 __global__ void k_pmmh_accept(FilterView v, PmmhDev p, int d, uint64_t move_seed, uint32_t c, double xi) {
     const int m = blockIdx.x * blockDim.x + threadIdx.x;

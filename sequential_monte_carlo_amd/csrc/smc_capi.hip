@@ -84,6 +84,8 @@ struct smc_filter_s {
     PmmhDev pm{};
     double* h_pm_out = nullptr;                // pinned mirror: theta [ntheta][d] | logZ [ntheta] | any [ntheta] | nrun
     int32_t* h_perm = nullptr;                 // pinned copy of smc_permute's index vector (the call does not wait for the device)
+    std::vector<double> prop_par;              // smc_set_proposal(AFFINE): the rows [ntheta][SMC_PROP_NPAR] as given (v.prop_kind: the kind)
+    PropRow *d_prop = nullptr, *h_prop = nullptr;   //   the proposal rows of a guided handle (v.prop) and their pinned twin; bootstrap: none
     Params* h_params = nullptr;                // pinned twin of d_params (smc_set_params does not wait either)
     double* pm_in = nullptr;                   // ONE device block: pm.theta | pm.logZ | pm.chol | pm.nrun | pm.counts | pm.any -
     double* h_pm_in = nullptr;                 //   a rejuvenation call fills its pinned twin and uploads it in one copy
@@ -181,6 +183,13 @@ static hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y) 
         if (e != hipSuccess) return e;
         emit_prev = 0;
     }
+    if (h->v.prop_kind) {   // a handle with a proposal: the guided kernels (the families smc_set_proposal accepts)
+        switch (h->model) {
+        case MODEL_LG1D: return launch_step_g<MODEL_LG1D>(h->v, h->geo, h->cur, t, emit_prev, y, h->stream);
+        case MODEL_UCSV3D: return launch_step_g<MODEL_UCSV3D>(h->v, h->geo, h->cur, t, emit_prev, y, h->stream);
+        }
+        return hipErrorInvalidValue;
+    }
     switch (h->model) {
     case MODEL_LG1D: return launch_step<MODEL_LG1D>(h->v, h->geo, h->cur, t, emit_prev, y, h->stream);
     case MODEL_SV1D: return launch_step<MODEL_SV1D>(h->v, h->geo, h->cur, t, emit_prev, y, h->stream);
@@ -233,6 +242,13 @@ static hipError_t do_persist(smc_filter_s* h, uint32_t t0, uint32_t t1, PersistC
     return hipErrorInvalidValue;
 }
 static hipError_t do_resident(smc_filter_s* h, int T) {
+    if (h->v.prop_kind) {
+        switch (h->model) {
+        case MODEL_LG1D: return launch_resident_g<MODEL_LG1D>(h->v, T, h->d_recs, h->stream);
+        case MODEL_UCSV3D: return launch_resident_g<MODEL_UCSV3D>(h->v, T, h->d_recs, h->stream);
+        }
+        return hipErrorInvalidValue;
+    }
     switch (h->model) {
     case MODEL_LG1D: return launch_resident<MODEL_LG1D>(h->v, T, h->d_recs, h->stream);
     case MODEL_SV1D: return launch_resident<MODEL_SV1D>(h->v, T, h->d_recs, h->stream);
@@ -242,6 +258,13 @@ static hipError_t do_resident(smc_filter_s* h, int T) {
 }
 
 static hipError_t do_window(smc_filter_s* h, int k, int bout) {
+    if (h->v.prop_kind) {
+        switch (h->model) {
+        case MODEL_LG1D: return launch_window_g<MODEL_LG1D>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->h_win, h->stream);
+        case MODEL_UCSV3D: return launch_window_g<MODEL_UCSV3D>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->h_win, h->stream);
+        }
+        return hipErrorInvalidValue;
+    }
     switch (h->model) {
     case MODEL_LG1D: return launch_window<MODEL_LG1D>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->h_win, h->stream);
     case MODEL_SV1D: return launch_window<MODEL_SV1D>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->h_win, h->stream);
@@ -539,6 +562,8 @@ extern "C" int smc_destroy(smc_handle h) {
     if (h->h_pm_in) (void)hipHostFree(h->h_pm_in);
     if (h->h_perm) (void)hipHostFree(h->h_perm);
     if (h->h_params && !kept) (void)hipHostFree(h->h_params);
+    if (h->d_prop) (void)hipFree(h->d_prop);
+    if (h->h_prop) (void)hipHostFree(h->h_prop);
     (void)hipFree(h->d_skip); (void)hipFree(h->d_order);
     if (h->h_win) (void)hipHostFree(h->h_win);
     if (h->h_once) (void)hipHostFree(h->h_once);
@@ -560,6 +585,16 @@ extern "C" int smc_destroy(smc_handle h) {
     return SMC_OK;
 }
 
+// the proposal row of filter m from its parameter row (and, AFFINE, from the stored row): smc_spec.h "proposals"
+static void fill_proposal(smc_handle h, int m) {
+    const Params& P = h->h_params[m];
+    double* q = h->h_prop[m].p;
+    for (int k = 0; k < NPARAM; ++k) q[k] = 0.0;
+    if (h->v.prop_kind == PROP_AFFINE)
+        for (int k = 0; k < PROP_NPAR; ++k) q[k] = h->prop_par[(size_t)m * PROP_NPAR + k];
+    derive_proposal(h->model, h->v.prop_kind, P.raw, P.der, q);
+}
+
 extern "C" int smc_set_params(smc_handle h, const double* raw) {
     if (!h || !raw) return fail(SMC_EINVAL, "smc_set_params: NULL argument");
     HIPCHK(hipSetDevice(h->device));
@@ -572,9 +607,80 @@ extern "C" int smc_set_params(smc_handle h, const double* raw) {
     for (int m = 0; m < h->v.ntheta; ++m) {
         for (int k = 0; k < NPARAM; ++k) P[m].raw[k] = k < nraw ? raw[(size_t)m * nraw + k] : 0.0;
         derive_params(h->model, P[m].raw, P[m].der);
+        if (h->v.prop_kind) fill_proposal(h, m);
     }
     HIPCHK(hipMemcpyAsync(h->d_params, P, (size_t)h->v.ntheta * sizeof(Params), hipMemcpyHostToDevice, h->stream));
+    if (h->v.prop_kind)   // a guided handle: the proposal rows follow the parameter rows
+        HIPCHK(hipMemcpyAsync(h->d_prop, h->h_prop, (size_t)h->v.ntheta * sizeof(PropRow), hipMemcpyHostToDevice, h->stream));
     h->have_params = true;
+    return SMC_OK;
+}
+
+static bool affine_row_ok(const double* par) {
+    for (int k = 0; k < PROP_NPAR; ++k)
+        if (!finite_d(par[k])) return false;
+    return par[3] > 0.0;
+}
+extern "C" int smc_set_proposal(smc_handle h, int kind, const double* par) {
+    if (!h) return fail(SMC_EINVAL, "smc_set_proposal: NULL handle");
+    if (kind != PROP_NONE && kind != PROP_AFFINE && kind != PROP_OPTIMAL) return fail(SMC_EINVAL, "smc_set_proposal: unknown kind");
+    if (!proposal_supported(h->model, kind)) return fail(SMC_EINVAL, "smc_set_proposal: this model family has no proposal of that kind");
+    if ((kind == PROP_AFFINE) != (par != nullptr)) return fail(SMC_EINVAL, "smc_set_proposal: rows are given with SMC_PROP_AFFINE and only then");
+    if (kind == PROP_AFFINE)
+        for (int m = 0; m < h->v.ntheta; ++m)
+            if (!affine_row_ok(par + (size_t)m * PROP_NPAR)) return fail(SMC_EINVAL, "smc_set_proposal: rows must be finite with s2 > 0");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t nt = (size_t)h->v.ntheta;
+    if (kind != PROP_NONE && !h->d_prop) {
+        HIPCHK(hipMalloc((void**)&h->d_prop, nt * sizeof(PropRow)));
+        HIPCHK(hipHostMalloc((void**)&h->h_prop, nt * sizeof(PropRow), hipHostMallocDefault));
+    }
+    if (kind == PROP_AFFINE) h->prop_par.assign(par, par + nt * PROP_NPAR);
+    else h->prop_par.clear();
+    h->v.prop_kind = kind;
+    h->v.prop = kind != PROP_NONE ? h->d_prop : nullptr;
+    h->win_k = 0;   // an uncommitted window belongs to the previous proposal
+    if (kind == PROP_NONE) return SMC_OK;
+    // the rows on the device.  The parameter rows they derive from are read back first: a proposal handle of the device PMMH had
+    // them written there (k_pmmh_propose), not through the pinned twin.  Without parameters yet: the rows as given, the
+    // constants follow with smc_set_params / the device PMMH
+    if (!h->h_params) {
+        HIPCHK(hipHostMalloc((void**)&h->h_params, nt * sizeof(Params), hipHostMallocDefault));
+        memset(h->h_params, 0, nt * sizeof(Params));
+    }
+    if (h->have_params) HIPCHK(hipMemcpy(h->h_params, h->d_params, nt * sizeof(Params), hipMemcpyDeviceToHost));
+    for (int m = 0; m < h->v.ntheta; ++m) fill_proposal(h, m);
+    HIPCHK(hipMemcpyAsync(h->d_prop, h->h_prop, nt * sizeof(PropRow), hipMemcpyHostToDevice, h->stream));
+    return SMC_OK;
+}
+extern "C" int smc_host_optimal_proposal(int model_id, const double* raw, double* par) {
+    if (!raw || !par) return fail(SMC_EINVAL, "smc_host_optimal_proposal: NULL argument");
+    if (model_id != MODEL_LG1D) return fail(SMC_EINVAL, "smc_host_optimal_proposal: LG1D only (the UCSV proposal has no parameters)");
+    optimal_proposal_lg(raw, par);
+    return SMC_OK;
+}
+// the parameter and proposal rows of one guided particle step from (raw, kind, par); false: refused
+static bool guided_params(int model_id, const double* raw, int kind, const double* par, Params& P, PropRow& R) {
+    const int nraw = model_nraw_rt(model_id);
+    if (nraw < 0 || !raw || kind == PROP_NONE || !proposal_supported(model_id, kind)) return false;
+    if ((kind == PROP_AFFINE) != (par != nullptr)) return false;
+    if (kind == PROP_AFFINE && !affine_row_ok(par)) return false;
+    for (int k = 0; k < NPARAM; ++k) { P.raw[k] = k < nraw ? raw[k] : 0.0; R.p[k] = 0.0; }
+    derive_params(model_id, P.raw, P.der);
+    if (kind == PROP_AFFINE)
+        for (int k = 0; k < PROP_NPAR; ++k) R.p[k] = par[k];
+    derive_proposal(model_id, kind, P.raw, P.der, R.p);
+    return true;
+}
+extern "C" int smc_host_guided_step(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z,
+                                    double y, double* x, double* logw) {
+    if (!xp || !z || !x || !logw) return fail(SMC_EINVAL, "smc_host_guided_step: NULL argument");
+    Params P;
+    PropRow R;
+    if (!guided_params(model_id, raw, kind, par, P, R)) return fail(SMC_EINVAL, "smc_host_guided_step: bad model, kind or row");
+    if (model_id == MODEL_LG1D) *logw = model_guided<MODEL_LG1D>(P, R, xp, z, y, x);
+    else *logw = model_guided<MODEL_UCSV3D>(P, R, xp, z, y, x);
     return SMC_OK;
 }
 
@@ -920,7 +1026,8 @@ static int enqueue_log_likelihood(smc_handle h, double y0, int64_t T, bool want_
         // OPT-IN (SMC_PERSIST=1; measured slower than one launch per step): the steps 1 .. T-2 in persistent
         // launches, one per window of prepared break points; the last step (which carries the sum of squares) by its own launch
         if (h->persist < 0) { const char* e = getenv("SMC_PERSIST"); h->persist = (e && atoi(e) == 1) ? 1 : 0; }
-        if (h->persist == 1 && !want_trace && h->v.nseg > 1 && !h->v.skip && !h->v.anc && T > 3) {
+        // (a handle with a proposal declines it: k_persist exists for the bootstrap step only - one launch per step instead)
+        if (h->persist == 1 && !h->v.prop_kind && !want_trace && h->v.nseg > 1 && !h->v.skip && !h->v.anc && T > 3) {
             const size_t nfl = (size_t)h->v.ntheta * h->v.nseg;
             if (!h->d_pflags) {
                 HIPCHK(dalloc(&h->d_pflags, 2 * nfl));
@@ -1199,7 +1306,7 @@ extern "C" int smc_pmmh_rejuvenate(smc_handle h, smc_handle main, const double* 
     const dim3 grid((unsigned)((nt + 127) / 128)), block(128);
     for (int c = 0; c < chain; ++c) {
         hipLaunchKernelGGL(k_pmmh_propose, grid, block, 0, h->stream, h->v, sp, h->pm, h->model, move_seed, (uint32_t)c,
-                           sqrt(scales[c]), h->d_params);
+                           sqrt(scales[c]), h->d_params);   // (derives the proposal rows of a guided handle too)
         HIPCHK(hipGetLastError());
         h->have_params = true;
         h->v.seed = filter_seeds[c];
@@ -1831,6 +1938,45 @@ extern "C" int smc_sys_targets(uint64_t Dtot, uint32_t n, uint64_t u, uint64_t j
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d.p, (size_t)nk * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+
+template <int MODEL>
+__global__ void k_guided_step(Params P, PropRow R, const double* xp, const double* z, double y, int64_t n, double* x, double* logw) {
+    constexpr int D = model_dim<MODEL>::value;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double a[D], zz[D], xn[D];
+    for (int c = 0; c < D; ++c) { a[c] = xp[(size_t)c * n + i]; zz[c] = z[(size_t)c * n + i]; }
+    logw[i] = model_guided<MODEL>(P, R, a, zz, y, xn);
+    for (int c = 0; c < D; ++c) x[(size_t)c * n + i] = xn[c];
+}
+extern "C" int smc_device_guided_step(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z,
+                                      double y, int64_t n, double* x, double* logw, int device) {
+    if (!xp || !z || !x || !logw || n <= 0) return fail(SMC_EINVAL, "smc_device_guided_step: bad argument");
+    Params P;
+    PropRow R;
+    if (!guided_params(model_id, raw, kind, par, P, R)) return fail(SMC_EINVAL, "smc_device_guided_step: bad model, kind or row");
+    const int d = model_dim_rt(model_id);
+    HIPCHK(hipSetDevice(device));
+    double *dxp = nullptr, *dz = nullptr, *dx = nullptr, *dlw = nullptr;
+    const size_t bytes = (size_t)d * n * 8;
+    hipError_t e = hipMalloc((void**)&dxp, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&dz, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&dx, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&dlw, (size_t)n * 8);
+    if (e == hipSuccess) e = hipMemcpy(dxp, xp, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dz, z, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        if (model_id == MODEL_LG1D) hipLaunchKernelGGL(k_guided_step<MODEL_LG1D>, grid, block, 0, 0, P, R, dxp, dz, y, n, dx, dlw);
+        else hipLaunchKernelGGL(k_guided_step<MODEL_UCSV3D>, grid, block, 0, 0, P, R, dxp, dz, y, n, dx, dlw);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(x, dx, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(logw, dlw, (size_t)n * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(dxp); (void)hipFree(dz); (void)hipFree(dx); (void)hipFree(dlw);
+    HIPCHK(e);
     return SMC_OK;
 }
 

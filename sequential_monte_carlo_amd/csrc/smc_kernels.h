@@ -121,7 +121,9 @@ struct FilterView {
     double* sum_q;           // [T][ntheta][sum_np]
     double* sum_m;           // [T][2][d][ntheta]  (mean | variance)
     int abl;                 // ablation mask: always 0 in the product (profiling builds only, -DSMC_ABLATE)
+    int prop_kind;           // smc_set_proposal: 0 bootstrap; else the host launches the GUIDED kernels
     unsigned long long* dbg; // phase stamps [workgroup][8] (profiling builds only), else nullptr
+    PropRow* prop;           // [ntheta] proposal rows of a guided handle (smc_spec.h "proposals"), else nullptr; read by the GUIDED kernels only
 };
 
 #ifdef SMC_ABLATE
@@ -882,7 +884,9 @@ __host__ __device__ inline size_t step_lds_bytes(int nseg_p2, int threads, int n
 // step): filters with more segments than the workgroup has threads.  No table in LDS, no emission here.
 // RPT = 2: filters with more segments than threads, but at most twice as many: the window prologue with TWO records per thread
 // (no k_table launch yet; the rare full table in LDS as ever).
-template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS, bool PERSIST, class VIEW, bool GTAB = false, int RPT = 1>
+// GUIDED: the state comes from the filter's proposal and the weight carries the correction (smc_spec.h "proposals"; the parameter
+// row's prop entries): the guided handles' instantiations - bootstrap handles run the GUIDED = false ones, which never read them.
+template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS, bool PERSIST, class VIEW, bool GTAB = false, int RPT = 1, bool GUIDED = false>
 __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, int emit_prev, double yval, char* smem) {
     static_assert(!GTAB || (MULTI && !PERSIST), "global table: multi-segment launches");
     static_assert(RPT == 1 || (RPT == 2 && MULTI && !GTAB && !PERSIST), "two records per thread: multi-segment launches");
@@ -899,6 +903,8 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
     if (!PERSIST && v.skip && v.skip[th]) return;   // workgroup-uniform
     const int nxt = cur ^ 1;
     const Params prm = v.params[th];
+    PropRow prw;
+    if constexpr (GUIDED) prw = v.prop[th];
     const uint32_t stream = v.stream[th];
     const double y = v.y ? v.y[t] : yval;
     // particle indices fit 32 bits (smc_create: n_x <= 2^31): index arithmetic in 32 bits, 64 bits only in the addresses
@@ -1288,8 +1294,12 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
             double zz[D];
 #pragma unroll
             for (int c = 0; c < D; ++c) zz[c] = z[k][c][j];
-            model_transition<MODEL>(prm, xp[2 * k + j], zz, xn[j]);
-            lw[k][j] = model_logobs<MODEL>(prm, xn[j], y);
+            if constexpr (GUIDED) {
+                lw[k][j] = model_guided<MODEL>(prm, prw, xp[2 * k + j], zz, y, xn[j]);
+            } else {
+                model_transition<MODEL>(prm, xp[2 * k + j], zz, xn[j]);
+                lw[k][j] = model_logobs<MODEL>(prm, xn[j], y);
+            }
         }
         if (ragged) {   // masked children: NaN weight, zero state
             asm volatile("; ragged");
@@ -1329,10 +1339,10 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
     SMC_STAMP(v, 7);
 }
 
-template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS = false, bool GTAB = false, int RPT = 1>
+template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS = false, bool GTAB = false, int RPT = 1, bool GUIDED = false>
 __global__ __launch_bounds__(THREADS) void k_step(FilterView v, int cur, uint32_t t, int emit_prev, double yval) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    step_body<MODEL, THREADS, NP, MULTI, SYS, false, FilterView, GTAB, RPT>(v, cur, t, emit_prev, yval, smem);
+    step_body<MODEL, THREADS, NP, MULTI, SYS, false, FilterView, GTAB, RPT, GUIDED>(v, cur, t, emit_prev, yval, smem);
 }
 
 // ---------------------------------------------------------------------------------------------

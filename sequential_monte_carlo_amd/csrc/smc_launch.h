@@ -25,5 +25,10 @@ template <int MODEL> hipError_t launch_persist(const FilterView& v, Geo g, int c
 template <int MODEL> hipError_t launch_summ_once(const FilterView& v, int cur, hipStream_t s);
 // window mode: steps [t0, t0 + T) from the state in buffer bin to buffer bout, (logmu, ess) of every step to win
 template <int MODEL> hipError_t launch_window(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
+// the same three for a handle with a proposal (smc_set_proposal): the GUIDED kernels, instantiated for the families that have
+// proposals (LG1D, UCSV3D) in translation units of their own (smc_model.hip with -DSMC_GUIDED=1)
+template <int MODEL> hipError_t launch_step_g(const FilterView& v, Geo g, int cur, uint32_t t, int emit_prev, double y, hipStream_t s);
+template <int MODEL> hipError_t launch_resident_g(const FilterView& v, int T, StepRec* recs, hipStream_t s);
+template <int MODEL> hipError_t launch_window_g(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
 
 }  // namespace smc

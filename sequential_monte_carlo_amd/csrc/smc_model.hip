@@ -6,6 +6,12 @@
 #ifndef SMC_MODEL
 #error "compile with -DSMC_MODEL=<model id>"
 #endif
+// -DSMC_GUIDED=1: the same launchers for the GUIDED kernels (handles with a proposal, smc_set_proposal), as translation units
+// of their own (build/guided<model>.o): launch_step_g, launch_resident_g, launch_window_g.  Without it: the bootstrap kernels.
+#ifndef SMC_GUIDED
+#define SMC_GUIDED 0
+#endif
+#define SMC_G (SMC_GUIDED != 0)
 
 namespace smc {
 
@@ -23,41 +29,43 @@ static hipError_t raise_lds_limit(K kernel, size_t lds, bool (&raised)[16]) {
 }
 
 
+#if !SMC_G
 template <int THREADS, int NP>
 static hipError_t init_t(const FilterView& v, int nxt, double y, hipStream_t s) {
     const size_t lds = scr_words(THREADS, NP) * 8;
     hipLaunchKernelGGL((k_init<SMC_MODEL, THREADS, NP>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, nxt, y);
     return hipGetLastError();
 }
+#endif
 template <int THREADS, int NP, bool SYS>
 static hipError_t step_sys_t(const FilterView& v, int cur, uint32_t t, int emit_prev, double y, hipStream_t s) {
     if (v.tabD) {   // the table comes from k_table (launched by the caller before this step): no table in LDS, nothing to emit
         const size_t lds = step_lds_bytes(0, THREADS, NP, true);
         static bool raised[16] = {};
-        hipError_t e = raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, true, SYS, true>, lds, raised);
+        hipError_t e = raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, true, SYS, true, 1, SMC_G>, lds, raised);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, true, SYS, true>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, cur, t, 0, y);
+        hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, true, SYS, true, 1, SMC_G>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, cur, t, 0, y);
         return hipGetLastError();
     }
     const size_t lds = step_lds_bytes(v.nseg_p2, THREADS, NP, v.nseg > 1);
     if (v.nseg_p2 > THREADS) {   // up to twice as many segments as threads: the window prologue with two records per thread
         static bool raised[16] = {};
-        hipError_t e = raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, true, SYS, false, 2>, lds, raised);
+        hipError_t e = raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, true, SYS, false, 2, SMC_G>, lds, raised);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, true, SYS, false, 2>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, cur, t, emit_prev, y);
+        hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, true, SYS, false, 2, SMC_G>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, cur, t, emit_prev, y);
         return hipGetLastError();
     }
     {
         static bool raised[2][16] = {};   // per instantiation, variant and device
-        hipError_t e = v.nseg > 1 ? raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, true, SYS>, lds, raised[1])
-                                  : raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, false, SYS>, lds, raised[0]);
+        hipError_t e = v.nseg > 1 ? raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, true, SYS, false, 1, SMC_G>, lds, raised[1])
+                                  : raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, false, SYS, false, 1, SMC_G>, lds, raised[0]);
         if (e != hipSuccess) return e;
     }
     if (v.nseg > 1)
-        hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, true, SYS>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, cur, t,
+        hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, true, SYS, false, 1, SMC_G>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, cur, t,
                            emit_prev, y);
     else
-        hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, false, SYS>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, cur, t,
+        hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, false, SYS, false, 1, SMC_G>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, cur, t,
                            emit_prev, y);
     return hipGetLastError();
 }
@@ -85,12 +93,21 @@ static hipError_t step_t(const FilterView& v, int cur, uint32_t t, int emit_prev
     }                                                                             \
     return hipErrorInvalidValue;
 
+#if !SMC_G
 template <>
 hipError_t launch_init<SMC_MODEL>(const FilterView& v, Geo g, int nxt, double y, hipStream_t s) {
     SMC_GEO_SWITCH(init_t, v, nxt, y, s)
 }
+#define SMC_LAUNCH_STEP launch_step
+#define SMC_LAUNCH_RESIDENT launch_resident
+#define SMC_LAUNCH_WINDOW launch_window
+#else
+#define SMC_LAUNCH_STEP launch_step_g
+#define SMC_LAUNCH_RESIDENT launch_resident_g
+#define SMC_LAUNCH_WINDOW launch_window_g
+#endif
 template <>
-hipError_t launch_step<SMC_MODEL>(const FilterView& v, Geo g, int cur, uint32_t t, int emit_prev, double y, hipStream_t s) {
+hipError_t SMC_LAUNCH_STEP<SMC_MODEL>(const FilterView& v, Geo g, int cur, uint32_t t, int emit_prev, double y, hipStream_t s) {
     SMC_GEO_SWITCH(step_t, v, cur, t, emit_prev, y, s)
 }
 
@@ -99,9 +116,9 @@ static hipError_t resident_sys_t(const FilterView& v, int T, StepRec* recs, int 
     const size_t lds = resident_lds_bytes<SMC_MODEL>(2 * NP * THREADS, THREADS, NP, SUMM ? v.sum_np : -1);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     static bool raised[16] = {};   // per instantiation and device
-    hipError_t e = raise_lds_limit(k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW>, lds, raised);
+    hipError_t e = raise_lds_limit(k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW, SMC_G>, lds, raised);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW>), dim3(v.ntheta), dim3(THREADS), lds, s, v, T, recs, t0, bin, bout, win);
+    hipLaunchKernelGGL((k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW, SMC_G>), dim3(v.ntheta), dim3(THREADS), lds, s, v, T, recs, t0, bin, bout, win);
     return hipGetLastError();
 }
 // per-step summaries (smc_set_summaries) select the SUMM kernels; they exist for the multinomial default only (the C ABI sends
@@ -132,7 +149,7 @@ static int resident_np(const FilterView& v) {
 }
 
 template <>
-hipError_t launch_resident<SMC_MODEL>(const FilterView& v, int T, StepRec* recs, hipStream_t s) {
+hipError_t SMC_LAUNCH_RESIDENT<SMC_MODEL>(const FilterView& v, int T, StepRec* recs, hipStream_t s) {
     const int np = resident_np(v);
     switch (v.seg) {
     case 256: return resident_t<128, 1>(v, T, recs, s);
@@ -147,6 +164,7 @@ hipError_t launch_resident<SMC_MODEL>(const FilterView& v, int T, StepRec* recs,
     return hipErrorInvalidValue;
 }
 
+#if !SMC_G
 template <int THREADS, int NP, bool UNW>
 static hipError_t summ_once_m(const FilterView& v, int cur, hipStream_t s) {
     constexpr int D = model_dim<SMC_MODEL>::value;
@@ -175,9 +193,10 @@ hipError_t launch_summ_once<SMC_MODEL>(const FilterView& v, int cur, hipStream_t
     }
     return hipErrorInvalidValue;
 }
+#endif
 
 template <>
-hipError_t launch_window<SMC_MODEL>(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s) {
+hipError_t SMC_LAUNCH_WINDOW<SMC_MODEL>(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s) {
     const int np = resident_np(v);
     switch (v.seg) {
     case 256: return window_t<128, 1>(v, T, recs, t0, bin, bout, win, s);

@@ -337,7 +337,9 @@ constexpr int resident_min_waves() {
     return (THREADS == 512 && NP == 1) ? 4 : 1;
 }
 // SUMM: per-step summaries (resident_summaries) after every step, for the levels / coordinate the view names; UNW: its mode
-template <int MODEL, int THREADS, int NP, bool SYS = false, bool WIN = false, bool SUMM = false, bool UNW = false>
+// GUIDED: as in step_body (smc_kernels.h) - the steps after the first draw from the proposal; the weight is complete when the
+// draw is, so the ancestors' states are used where they are gathered and nothing of them is kept for the observation loop
+template <int MODEL, int THREADS, int NP, bool SYS = false, bool WIN = false, bool SUMM = false, bool UNW = false, bool GUIDED = false>
 __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())) void k_resident(FilterView v, int T, StepRec* recs /*[ntheta][T]*/, int t0, int bin, int bout,
                                                       double* win) {
     constexpr int D = model_dim<MODEL>::value;
@@ -369,6 +371,8 @@ __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())
         return;
     }
     const Params prm = v.params[th];
+    PropRow prw;
+    if constexpr (GUIDED) prw = v.prop[th];
     const uint32_t stream = v.stream[th];
     StepRec* rec = recs + (size_t)th * T;
 #ifdef SMC_ABLATE
@@ -492,7 +496,8 @@ __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())
                     double zz[D];
 #pragma unroll
                     for (int c = 0; c < D; ++c) zz[c] = z[k][c][j];
-                    model_transition<MODEL>(prm, xp[2 * k + j], zz, xn[k][j]);
+                    if constexpr (GUIDED) lw[k][j] = model_guided<MODEL>(prm, prw, xp[2 * k + j], zz, y, xn[k][j]);
+                    else model_transition<MODEL>(prm, xp[2 * k + j], zz, xn[k][j]);
                 }
         } else {
             // a real (workgroup-uniform) branch: flattened into selects, every step of the series would also evaluate the
@@ -508,10 +513,12 @@ __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())
                     model_initial<MODEL>(prm, zz, xn[k][j]);
                 }
         }
+        if (!GUIDED || t == 0) {
 #pragma unroll
-        for (int k = 0; k < NP; ++k)
+            for (int k = 0; k < NP; ++k)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) lw[k][j] = model_logobs<MODEL>(prm, xn[k][j], y);
+                for (int j = 0; j < 2; ++j) lw[k][j] = model_logobs<MODEL>(prm, xn[k][j], y);
+        }
         if (ragged) {   // n < SEG: the particles beyond n carry NaN weights and zero states (a real branch: the samplers' filters are full)
             asm volatile("; ragged");
 #pragma unroll

@@ -475,6 +475,11 @@ struct Params {
     double raw[NPARAM];
     double der[NPARAM];
 };
+// the proposal of a guided filter ("proposals" below), a table of its own beside the parameter rows: bootstrap handles have none
+//            LG1D (c0,c1,c2,s2, ss,1/ss,1/sQ,log ss - log sQ)
+struct PropRow {
+    double p[NPARAM];
+};
 
 SMC_HD void derive_params(int model, const double* raw, double* der) {
     for (int k = 0; k < NPARAM; ++k) der[k] = 0.0;
@@ -546,6 +551,91 @@ SMC_HD void model_obs_moments(const Params& p, const double* x, double& mean, do
     } else {
         mean = x[0];
         sd = sp_exp(0.5 * x[2]);
+    }
+}
+
+// ---- proposals: the guided particle filter (particle_filter / particle_filter!, particles.jl:28-84) ------------------------
+// Every step after the first draws x from proposal(xp, y) instead of the transition and weights it by (particles.jl:72-80)
+//     logw = logpdf(observation(x), y) + logpdf(transition(xp), x) - logpdf(proposal(xp, y), x).
+// The proposals are enumerated like the model families.  A guided step consumes the normals of the bootstrap step: one per
+// state coordinate, the same Philox slots.
+//   PROP_AFFINE  (LG1D)  row (c0, c1, c2, s2), s2 a variance:  m = c0 + c1 xp + c2 y,  x = m + sqrt(s2) z
+//   PROP_OPTIMAL (LG1D)  the AFFINE row derived from the model row: D = B B Q + R, (0, A R / D, B Q / D, Q R / D)
+//   PROP_OPTIMAL (UCSV)  the log-volatilities move by the transition (same normals); with Q = exp(xp[1]), R = exp(x[2]),
+//                        K = Q / (Q + R):  x[0] = xp[0] + K (y - xp[0]) + sqrt(K R) z[0],  logw = logN(y; xp[0], Q + R)
+//                        (the three terms collapse to this closed form; it does not depend on x[0])
+// Order of operations of the LG1D step (model_guided): k = fma(c2, y, c0), replaced by -0.0 when it is zero, so that
+// m = fma(c1, xp, k) is then the rounded product c1 xp with its sign of zero; x = fma(ss, z, m);
+//     zt = (x - A xp) / sQ, zp = (x - m) / ss (as products with the stored reciprocals),
+//     logw = logobs(x, y) + (((0.5 zp) zp - (0.5 zt) zt) + (log ss - log sQ)).
+// With the row (0, A, 0, Q) every operand of the bracket coincides, it evaluates to +0.0, and the step is the bootstrap step
+// bit for bit.  The FIRST step of a guided filter is the bootstrap first step (initial_dist, observation weight): the reference
+// adds logpdf(initial_dist, x) there (particles.jl:41-44), a slip - its own commented line :43 shows the intended correction,
+// which is zero for a draw from initial_dist.
+constexpr int PROP_NONE = 0;
+constexpr int PROP_AFFINE = 1;
+constexpr int PROP_OPTIMAL = 2;
+constexpr int PROP_NPAR = 4;
+
+SMC_HD bool proposal_supported(int model, int kind) {
+    return kind == PROP_NONE || (model == MODEL_LG1D && (kind == PROP_AFFINE || kind == PROP_OPTIMAL)) ||
+           (model == MODEL_UCSV3D && kind == PROP_OPTIMAL);
+}
+// the locally optimal proposal of an LG1D row as an AFFINE row.  Each entry is a quotient of a product by D = B B Q + R; D and the
+// products are carried with their rounding errors (fma residuals, a two-sum) and the quotient gets one correction step, so
+// every entry is within one ulp of the formula whatever the row (a plain evaluation rounds five times).  Once per filter.
+SMC_HD double quotient_corrected(double a, double b, double D, double De) {   // (a b) / (D + De)
+    const double n = a * b, ne = fma(a, b, -n);
+    const double c = n / D;
+    const double r = fma(-c, D, n);
+    return c + ((r + ne) - c * De) / D;
+}
+SMC_HD void optimal_proposal_lg(const double* raw, double* par) {
+    const double A = raw[0], B = raw[1], Q = raw[2], R = raw[3];
+    const double p = B * B, pe = fma(B, B, -p);
+    const double q = p * Q, qe = fma(p, Q, -q) + pe * Q;
+    const double D = q + R, t = D - q;
+    const double De = ((q - (D - t)) + (R - t)) + qe;
+    par[0] = 0.0;
+    par[1] = quotient_corrected(A, R, D, De);
+    par[2] = quotient_corrected(B, Q, D, De);
+    par[3] = quotient_corrected(Q, R, D, De);
+}
+// the proposal row of a parameter row: OPTIMAL fills the four parameters from raw, AFFINE keeps the ones in prop[0..3]; then
+// the constants of the step.  der = derive_params(raw).  PROP_NONE and UCSV (nothing to store): zeros.
+SMC_HD void derive_proposal(int model, int kind, const double* raw, const double* der, double* prop) {
+    if (model != MODEL_LG1D || kind == PROP_NONE) {
+        for (int k = 0; k < NPARAM; ++k) prop[k] = 0.0;
+        return;
+    }
+    if (kind == PROP_OPTIMAL) optimal_proposal_lg(raw, prop);
+    const double ss = sqrt(prop[3]);
+    prop[4] = ss;
+    prop[5] = 1.0 / ss;
+    prop[6] = 1.0 / der[0];
+    prop[7] = sp_log(ss) - sp_log(der[0]);
+}
+
+// x = rand(proposal(model, xp, y)); returns the log-weight of the guided step (LG1D: AFFINE rows, UCSV: OPTIMAL)
+template <int MODEL>
+SMC_HD double model_guided(const Params& p, const PropRow& q, const double* xp, const double* z, double y, double* x) {
+    if constexpr (MODEL == MODEL_LG1D) {
+        const double k = fma(q.p[2], y, q.p[0]);
+        const double m = fma(q.p[1], xp[0], k == 0.0 ? -0.0 : k);
+        x[0] = fma(q.p[4], z[0], m);
+        const double zt = (x[0] - p.raw[0] * xp[0]) * q.p[6];
+        const double zp = (x[0] - m) * q.p[5];
+        return model_logobs<MODEL>(p, x, y) + (((0.5 * zp) * zp - (0.5 * zt) * zt) + q.p[7]);
+    } else if constexpr (MODEL == MODEL_UCSV3D) {
+        x[1] = fma(p.raw[0], z[1], xp[1]);
+        x[2] = fma(p.raw[1], z[2], xp[2]);
+        const double Q = sp_exp(xp[1]), R = sp_exp(x[2]);
+        const double D = Q + R, iD = 1.0 / D, K = Q * iD, e = y - xp[0];
+        x[0] = fma(sqrt(K * R), z[0], fma(K, e, xp[0]));
+        return fma(-0.5 * (e * iD), e, fma(-0.5, sp_log(D), -HALF_LOG2PI));
+    } else {
+        x[0] = xp[0] + z[0] * y;   // (no proposal for this family: never instantiated by the library)
+        return bits2d(0x7ff8000000000000ULL);
     }
 }
 

@@ -5,6 +5,11 @@
     bootstrap_filter(N, y1, model)       -> (x, w, logmu)       particles.jl:87-105
     bootstrap_filter_(x, w, y, model)    -> (logmu, w, ess)     particles.jl:107-129   ("bootstrap_filter!")
     log_likelihood(N, y, model)          -> (x, w, logZ)        particles.jl:132-147
+    particle_filter(N, y1, model, proposal)       -> (x, w, logmu)     particles.jl:28-52
+    particle_filter_(x, w, y, model, proposal)    -> (logmu, w, ess)   particles.jl:54-84    ("particle_filter!")
+
+A proposal is AffineGaussianProposal(c0, c1, c2, s2) (UnivariateLinearGaussian), OptimalProposal() (UnivariateLinearGaussian,
+UCSV) or None, "leave the proposal argument empty" of the reference's README: the bootstrap filter.
 
 `model` may be one StateSpaceModel or a list of them (the batched callers smc_samplers.jl:112-121,
 223-229,289-295,325-335): then logmu / logZ / ess are arrays over the list.
@@ -38,10 +43,45 @@ def resample(w, N=None, seed=None, stream=0, t=0, device=0):
     return _lib.resample(np.asarray(w, dtype=np.float64), N, seed, stream, t, device)
 
 
+class AffineGaussianProposal:
+    """x ~ Normal(c0 + c1*xp + c2*y, sqrt(s2)) for UnivariateLinearGaussian models (s2 a variance, like Q).  One proposal, or a
+    list of them beside a list of models.  AffineGaussianProposal(0, A, 0, Q) is the bootstrap filter bit for bit."""
+
+    def __init__(self, c0, c1, c2, s2):
+        self.row = (float(c0), float(c1), float(c2), float(s2))
+
+
+class OptimalProposal:
+    """the locally optimal proposal p(x | xp, y), derived from the model on the device: UnivariateLinearGaussian (all of the
+    state) and UCSV (the trend, given the volatilities, which move by the transition)."""
+
+
+def optimal_proposal(model):
+    """the locally optimal proposal of a UnivariateLinearGaussian model as an AffineGaussianProposal (the row OptimalProposal()
+    uses); OptimalProposal() itself for a UCSV model, whose proposal has no parameters"""
+    mid, raw = params_matrix(model)
+    if mid == _lib.MODEL_UCSV3D:
+        return OptimalProposal()
+    return AffineGaussianProposal(*_lib.host_optimal_proposal(mid, raw[0]))
+
+
+def proposal_rows(proposal, n_theta):
+    """(kind, rows or None) of a proposal argument for a handle of n_theta filters (Handle.set_proposal)"""
+    if proposal is None:
+        return _lib.PROP_NONE, None
+    if isinstance(proposal, OptimalProposal):
+        return _lib.PROP_OPTIMAL, None
+    if isinstance(proposal, AffineGaussianProposal):
+        return _lib.PROP_AFFINE, np.tile(np.asarray(proposal.row), (n_theta, 1))
+    if isinstance(proposal, (list, tuple)) and len(proposal) == n_theta and all(isinstance(p, AffineGaussianProposal) for p in proposal):
+        return _lib.PROP_AFFINE, np.asarray([p.row for p in proposal])
+    raise ValueError("proposal must be None, OptimalProposal(), an AffineGaussianProposal or a list of them, one per model")
+
+
 class _Filters:
     """Device state shared by the Particles / Weights views of one bootstrap_filter call."""
 
-    def __init__(self, N, models, seed, seg, device, streams, ancestors, resampler="multinomial"):
+    def __init__(self, N, models, seed, seg, device, streams, ancestors, resampler="multinomial", proposal=None):
         mid, raw = params_matrix(models)
         self.single = not isinstance(models, (list, tuple))
         if resampler not in ("multinomial", "systematic"):
@@ -52,6 +92,22 @@ class _Filters:
         if streams is not None:
             self.h.set_streams(streams)
         self.model_id, self.raw = mid, raw
+        self.proposal = None
+        self.set_proposal(proposal)
+
+    def set_proposal(self, proposal):
+        kind, rows = proposal_rows(proposal, self.h.n_theta)
+        if kind != _lib.PROP_NONE or self.proposal is not None:
+            self.h.set_proposal(kind, rows)
+        self.proposal = None if kind == _lib.PROP_NONE else (kind, rows)
+
+    def check_proposal(self, proposal):
+        kind, rows = proposal_rows(proposal, self.h.n_theta)
+        new = None if kind == _lib.PROP_NONE else (kind, rows)
+        same = (new is None and self.proposal is None) or (
+            new is not None and self.proposal is not None and new[0] == self.proposal[0] and np.array_equal(new[1], self.proposal[1]))
+        if not same:
+            self.set_proposal(proposal)
 
     def check_model(self, models):
         mid, raw = params_matrix(models)
@@ -159,6 +215,31 @@ def bootstrap_filter_(states, weights, y, model):
     return f.out(logmu), Weights(f), f.out(ess)
 
 
+def particle_filter(N, y, model, proposal=None, seed=None, seg=0, device=0, streams=None, ancestors=False, resampler="multinomial"):
+    """x, w, logmu = particle_filter(N, y[1], model, proposal)   particles.jl:28-52
+    The first step draws from initial_dist and weights by the observation density, exactly bootstrap_filter (the reference
+    adds logpdf(initial_dist, x) there, a slip: DESIGN.md "Guided filters"); the proposal applies to the particle_filter_ steps
+    that follow.  proposal=None is bootstrap_filter."""
+    if seed is None:
+        seed = next(_seed_counter)
+    f = _Filters(int(N), model, seed, seg, device, streams, ancestors, resampler, proposal)
+    logmu = f.h.init(float(y))
+    return Particles(f), Weights(f), f.out(logmu)
+
+
+def particle_filter_(states, weights, y, model, proposal=None):
+    """logmu, w, ess = particle_filter!(x, w, y[t], model, proposal)   particles.jl:54-84
+    x = rand(proposal(xp, y)), logw = logpdf(observation(x), y) + logpdf(transition(xp), x) - logpdf(proposal(xp, y), x);
+    proposal=None is bootstrap_filter_."""
+    f = states._f
+    if weights._f is not f:
+        raise ValueError("states and weights belong to different filters")
+    f.check_model(model)
+    f.check_proposal(proposal)
+    logmu, ess = f.h.step(float(y))
+    return f.out(logmu), Weights(f), f.out(ess)
+
+
 def _summaries_out(f, T):
     """per-step summaries of the call just made, in the shapes of the README loop: quantiles [T][len(p)], mean / var [T] (scalar
     state) or [T][d]; with a list of models a batch axis follows T"""
@@ -175,7 +256,7 @@ def _summaries_out(f, T):
 
 
 def log_likelihood(N, y, model, seed=None, seg=0, device=0, streams=None, ancestors=False, trace=False,
-                   resampler="multinomial", quantiles=None, component=0, moments=False, weighted=True):
+                   resampler="multinomial", quantiles=None, component=0, moments=False, weighted=True, proposal=None):
     """x, w, logZ = log_likelihood(N, y, model)   particles.jl:132-147
     trace=True additionally returns the per-step (logmu_t, ess_t).  resampler="systematic": opt-in systematic
     resampling (same expectation, lower variance, one launch per step for big filters; not the reference's law).
@@ -183,10 +264,11 @@ def log_likelihood(N, y, model, seed=None, seg=0, device=0, streams=None, ancest
     observation) as ONE call - the per-step quantiles of state coordinate `component` and / or mean and variance are computed
     on the device inside the filter loop and returned as a dict behind the usual results.  weighted=False gives the README's own
     numbers: the unweighted type-7 `quantile(x, p)` and the corrected `var(x)` of the cloud (see Particles.quantile);
-    weighted=True (the default) the weighted inverse CDF and the uncorrected weighted variance."""
+    weighted=True (the default) the weighted inverse CDF and the uncorrected weighted variance.
+    proposal: the guided filter (particle_filter_ at every step after the first) instead of the bootstrap filter."""
     if seed is None:
         seed = next(_seed_counter)
-    f = _Filters(int(N), model, seed, seg, device, streams, ancestors, resampler)
+    f = _Filters(int(N), model, seed, seg, device, streams, ancestors, resampler, proposal)
     y = np.ascontiguousarray(y, dtype=np.float64)
     summ = quantiles is not None or moments
     if summ:

@@ -106,12 +106,15 @@ class LibOuter:
 
 
 class HipBackend:
-    """Runs the batched inner filters on one GPU through the C ABI (no CPU fallback)."""
+    """Runs the batched inner filters on one GPU through the C ABI (no CPU fallback).
+    proposal: OptimalProposal() or an AffineGaussianProposal (particles.py) makes every inner filter - the main, proposal and
+    exchange handles alike, and the device PMMH - a guided particle filter; None (the default) the bootstrap filter."""
 
     outer = LibOuter()
 
-    def __init__(self, device=0, seg=0, resampler="multinomial"):
+    def __init__(self, device=0, seg=0, resampler="multinomial", proposal=None):
         self.device, self.seg = device, seg
+        self.proposal = proposal
         self.flags = _lib.FLAG_SYSTEMATIC if resampler == "systematic" else 0   # opt-in; default = the reference's law
         self._handles = {}
 
@@ -120,6 +123,9 @@ class HipBackend:
         h = self._handles.get(k)
         if h is None:
             h = _lib.Handle(model_id, n_theta, N, seg=self.seg, seed=seed, device=self.device, flags=self.flags)
+            if self.proposal is not None:
+                from .particles import proposal_rows
+                h.set_proposal(*proposal_rows(self.proposal, n_theta))
             self._handles[k] = h
         h.reseed(seed)
         return h
