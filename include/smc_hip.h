@@ -322,6 +322,49 @@ int smc_resample(const double* w, int64_t n, int64_t ndraw, uint64_t seed, uint3
  * reference loop; 0 starts at x_1 ~ N(x0, sigma0) like bootstrap_filter. */
 int smc_kalman_log_likelihood(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first,
                               double* out /*[n_theta][3]*/, int device);
+/* ---- the IBIS sampler: src/ibis.jl (SMC^2 with the exact Kalman filter inside) ------------------------------------
+ * A handle of its own (opaque; `void*` at this boundary) keeps M parameter particles on the device for its whole life:
+ * theta, the LinearModel row smc.model(theta) = (A,B,Q,R,x0,sigma0), the Kalman state (x, Sigma), logZ and the
+ * un-normalised outer log-weight logw (see "the OUTER level" above).  One lane per particle; the only random numbers are
+ * the PMMH proposal normals and accept uniforms of smc_pmmh_rejuvenate's contract, keyed by (move_seed, particle index,
+ * chain position): results do not depend on launch geometry, window length or device.
+ *   smc_ibis_create      IBIS(M, model, prior, chain, ess_threshold)      :26-58 (the device half: storage).  predict_first as
+ *                        in smc_kalman_log_likelihood: 0 starts at x_1 ~ N(x0, sigma0); != 0 is the reference's literal
+ *                        kalman_filter on y[1] (:136-140).  It applies to t = 1 online AND to every re-filter of
+ *                        smc_ibis_rejuvenate / smc_ibis_filter, so that an online logZ and a re-filter of the same
+ *                        observations are the same number.  `out` receives the handle (the address of a void*).
+ *   smc_ibis_configure   the prior and smc.model(theta), the arguments of smc_pmmh_configure (the family is LG1D: 6 row entries)
+ *   smc_ibis_set_theta   theta [n_theta][d_theta] (:35); rows, (x, Sigma) = (x0, sigma0) (:38-40), logZ = logw = 0, t = 0
+ *   smc_ibis_window      smc²! :166-187 for k <= 64 observations in ONE launch (smc², :134-147, is k = 1 on a fresh state):
+ *                        per step (x, Sigma) <- kalman_filter(row, x, Sigma, y_t), logw += lik, logZ += lik, and the
+ *                        segment records of reweight(logw) (:187) computed on the device - rec [k][nseg][4] 8-byte words,
+ *                        bit for bit what smc_host_outer_window gives for the same lik; lik [k][n_theta] or NULL.
+ *                        The host walks the records (smc_host_outer_walk).  Nothing is advanced until
+ *   smc_ibis_commit      keeps the first j <= k steps of the pending window (the same bits whatever k was)
+ *   smc_ibis_filter      log_likelihood(y, model(theta[m])) for every m from (x0, sigma0) (density_tempered's first pass):
+ *                        (x, Sigma, logZ) of the whole series, logw = logZ, t = T
+ *   smc_ibis_permute     resample! :73-84: particle m <- particle a[m] (theta, row, x, Sigma, logZ, logw), a value copy
+ *   smc_ibis_set_logw    the outer log-weights as given (the tempered weights of density_tempered)
+ *   smc_ibis_rejuvenate  rejuvenate! :86-125 in ONE launch: for every particle the whole `for c in 1:chain` loop - proposal
+ *                        theta + sqrt(scales[c]) L z (:97), insupport (:99), the Kalman filter over y[0:T) (:100), the accept
+ *                        test log(rand()) < xi (logZ' - logZ) + logprior(theta') - logprior(theta) with logZ' + logprior(theta')
+ *                        > -inf (:102-108), the overwrite of theta, logZ, x, Sigma (:109-112) - then logw = 0 (:118).
+ *                        *accepted = number of particles that moved at least once (sum(acc_array), :121); moved [n_theta] or NULL.
+ *   smc_ibis_get         any of theta [n_theta][d_theta], x, S, logZ, logw [n_theta]; NULL: not wanted */
+int smc_ibis_create(int64_t n_theta, uint64_t seed, int device, int predict_first, void* out);
+int smc_ibis_destroy(void* h);
+int smc_ibis_configure(void* h, int d_theta, const int32_t* prior_family /*[d_theta]*/, const double* prior_par /*[d_theta][SMC_PRIOR_NPAR]*/,
+                       const int32_t* raw_from /*[6]*/, const double* raw_const /*[6]*/);
+int smc_ibis_set_theta(void* h, const double* theta /*[n_theta][d_theta]*/);
+int smc_ibis_window(void* h, const double* y /*[k]*/, int k, double* lik /*[k][n_theta] or NULL*/, uint64_t* rec /*[k][nseg][4]*/);
+int smc_ibis_commit(void* h, int j);
+int smc_ibis_filter(void* h, const double* y, int64_t T);
+int smc_ibis_permute(void* h, const int32_t* a /*[n_theta]*/);
+int smc_ibis_set_logw(void* h, const double* logw /*[n_theta]*/);
+int smc_ibis_rejuvenate(void* h, const double* y, int64_t T, double xi, const double* chol /*[d_theta][d_theta]*/,
+                        const double* scales /*[chain]*/, int chain, uint64_t move_seed, int64_t* accepted /*or NULL*/,
+                        uint8_t* moved /*[n_theta] or NULL*/);
+int smc_ibis_get(void* h, double* theta, double* x, double* S, double* logZ, double* logw);
 /* filtered mean and variance of every state coordinate under the current weights, on the device
  * (README.md:41,51 summaries; src/plotting_utils.jl:116-124 estimated_trend). mean, var: [d][n_theta].
  * Definition: StatsBase's uncorrected weighted moments with the dense weights w of smc_get_state, mean = sum w x and

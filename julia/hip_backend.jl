@@ -686,3 +686,153 @@ function smc²_run!(smc::HipSMC, y::Vector{Float64}, t1::Int64, t2::Int64; windo
     end
     sync_omega!(smc)
 end
+
+# ---- IBIS (src/ibis.jl): SMC² with the exact scalar Kalman filter inside, on the device (smc_ibis_*).  Unexecuted here, like the
+# rest of this file; the tested twin is sequential_monte_carlo_amd/ibis.py.  A parameter particle's whole state - θ, its
+# LinearModel row, (x, Σ), logZ, logw - stays on the GPU; the host keeps the ESS decision, the index draw of resample! and the
+# random-walk factor.  Fields of the reference's struct (θ, ω, x, Σ, logZ) are read from the device on access.
+mutable struct HipIBIS <: Sampler
+    h::Ptr{Cvoid}
+    M::Int64
+    dθ::Int
+    chain::Int64
+    ess::Float64
+    ess_min::Float64
+    acc_threshold::Float64
+    acc_ratio::Float64
+    model
+    prior
+    seed::UInt64
+    calls::UInt64
+    t::Int64
+end
+next_seed!(s::HipIBIS) = (s.calls += 1; (s.seed << 20) + s.calls)
+
+# IBIS(M, model, prior, chain, ess_threshold, min_ar=-1.0)   ibis.jl:26-58
+function HipIBIS(M::Int64, model::SSM, prior::Sampleable, chain::Int64, ess_threshold::Float64, min_ar::Float64=-1.0;
+                 seed::UInt64=rand(UInt64), device::Int=0, predict_first::Bool=false) where SSM
+    θ = map(m -> rand(prior), 1:M)                                                # :35
+    comps = prior_components(prior)
+    specs = comps === nothing ? nothing : hip_prior.(comps)
+    (specs === nothing || any(isnothing, specs)) && error("IBIS on the GPU needs a prior of the enumerated families")
+    θ0 = Float64.(collect(θ[1])); dθ = length(θ0)
+    tm = infer_theta_map(model, θ0, eltype(θ) <: Number)
+    (tm === nothing || tm[1] != 1) && error("IBIS on the GPU needs model(θ) to be a univariate LinearModel row map")
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    smc_check(ccall((:smc_ibis_create, LIBSMC), Cint, (Int64, UInt64, Cint, Cint, Ptr{Cvoid}), M, seed, device, predict_first ? 1 : 0, h))
+    fam = Int32[s[1] for s in specs]; par = reduce(hcat, [s[2] for s in specs]); rf = Int32.(tm[2]); rc = Float64.(tm[3])
+    GC.@preserve fam par rf rc smc_check(ccall((:smc_ibis_configure, LIBSMC), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}), h[], dθ, fam, par, rf, rc))
+    θm = eltype(θ) <: Number ? reshape(Float64.(θ), 1, :) : reduce(hcat, θ)        # [dθ x M] column-major == [M][dθ] row-major
+    GC.@preserve θm smc_check(ccall((:smc_ibis_set_theta, LIBSMC), Cint, (Ptr{Cvoid}, Ptr{Float64}), h[], θm))
+    ib = HipIBIS(h[], M, dθ, chain, 1.0 * M, M * ess_threshold, min_ar, 0.0, model, prior, seed, UInt64(0), 0)
+    finalizer(x -> ccall((:smc_ibis_destroy, LIBSMC), Cint, (Ptr{Cvoid},), x.h), ib)
+    return ib
+end
+
+function ibis_get(ib::HipIBIS; θ=false, x=false, Σ=false, logZ=false, logw=false)
+    bufθ = θ ? Matrix{Float64}(undef, ib.dθ, ib.M) : nothing
+    v(want) = want ? Vector{Float64}(undef, ib.M) : nothing
+    bx, bS, bZ, bw = v(x), v(Σ), v(logZ), v(logw)
+    p(b) = b === nothing ? Ptr{Float64}(C_NULL) : pointer(b)
+    GC.@preserve bufθ bx bS bZ bw smc_check(ccall((:smc_ibis_get, LIBSMC), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ib.h, p(bufθ), p(bx), p(bS), p(bZ), p(bw)))
+    return (θ=bufθ, x=bx, Σ=bS, logZ=bZ, logw=bw)
+end
+function Base.getproperty(ib::HipIBIS, s::Symbol)
+    s === :θ && return (m = ibis_get(ib; θ=true).θ; ib.dθ == 1 ? vec(m) : [m[:, i] for i in 1:ib.M])
+    s === :x && return ibis_get(ib; x=true).x
+    s === :Σ && return ibis_get(ib; Σ=true).Σ
+    s === :logZ && return ibis_get(ib; logZ=true).logZ
+    s === :ω && return reweight(ibis_get(ib; logw=true).logw)[2]
+    return getfield(ib, s)
+end
+
+function expected_parameters(ib::HipIBIS)                                        # ibis.jl:60-64
+    g = ibis_get(ib; θ=true, logw=true)
+    return g.θ * reweight(g.logw)[2]
+end
+
+# k steps of smc²! in one launch; the device computes the reweight records, the host walks them (ibis.jl:166-187)
+function ibis_window!(ib::HipIBIS, yk::Vector{Float64}, ess_min::Float64)
+    k = length(yk); nseg = cld(ib.M, 8)
+    rec = Array{UInt64,3}(undef, 4, nseg, k)                                       # column-major == [k][nseg][4]
+    GC.@preserve yk rec smc_check(ccall((:smc_ibis_window, LIBSMC), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{UInt64}),
+        ib.h, yk, k, C_NULL, rec))
+    e, j = outer_walk(rec, ib.M, ess_min)
+    smc_check(ccall((:smc_ibis_commit, LIBSMC), Cint, (Ptr{Cvoid}, Cint), ib.h, j))
+    return e, j
+end
+
+function resample!(ib::HipIBIS, logw::Vector{Float64}=ibis_get(ib; logw=true).logw)   # ibis.jl:73-84
+    a = Int32.(outer_resample(logw, ib.M, next_seed!(ib)) .- 1)
+    GC.@preserve a smc_check(ccall((:smc_ibis_permute, LIBSMC), Cint, (Ptr{Cvoid}, Ptr{Int32}), ib.h, a))
+    return ib
+end
+
+function rejuvenate!(ib::HipIBIS, y::Vector{Float64}, ξ::Float64, verbose::Bool)     # ibis.jl:86-125
+    if verbose @printf("\t[rejuvenating]") end
+    L, uni = rw_factor(ibis_get(ib; θ=true).θ)
+    scales = 0.5 * reverse(1:ib.chain)                                             # :91
+    s = uni ? scales .^ 2 : collect(scales)
+    acc = Ref{Int64}(0)
+    GC.@preserve y L s smc_check(ccall((:smc_ibis_rejuvenate, LIBSMC), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Float64, Ptr{Float64}, Ptr{Float64}, Cint, UInt64, Ptr{Int64}, Ptr{UInt8}),
+        ib.h, y, length(y), ξ, L, s, ib.chain, next_seed!(ib), acc, C_NULL))
+    ib.acc_ratio = acc[] / ib.M                                                    # :121
+    if verbose @printf("\tacc_rate: %1.5f", ib.acc_ratio) end
+    return ib
+end
+rejuvenate!(ib::HipIBIS, y::Vector{Float64}, verbose::Bool) = rejuvenate!(ib, y, 1.0, verbose)      # :127
+
+function smc²(ib::HipIBIS, y::Vector{Float64})                                    # ibis.jl:134-147
+    e, _ = ibis_window!(ib, y[1:1], 0.0)
+    ib.ess = e[1]; ib.t = 1
+    return ib
+end
+
+function smc²!(ib::HipIBIS, y::Vector{Float64}, t::Int64, verbose::Bool=true)      # ibis.jl:154-189
+    if verbose @printf("t = %4d\tess = %4.3f", t - 1, ib.ess) end
+    if ib.ess < ib.ess_min
+        resample!(ib)
+        rejuvenate!(ib, y[1:(t-1)], verbose)
+    end
+    e, _ = ibis_window!(ib, y[t:t], 0.0)
+    ib.ess = e[1]; ib.t = t
+    if verbose print("\n") end
+end
+
+function smc²_run!(ib::HipIBIS, y::Vector{Float64}, t1::Int64, t2::Int64; window::Int=16, verbose::Bool=true)
+    t = t1
+    while t <= t2
+        if ib.ess < ib.ess_min
+            resample!(ib)
+            rejuvenate!(ib, y[1:(t-1)], verbose)
+        end
+        k = min(window, 64, t2 - t + 1)
+        e, j = ibis_window!(ib, y[t:(t+k-1)], ib.ess_min)
+        ib.ess = e[end]; ib.t = t + j - 1
+        t += j
+    end
+    return ib
+end
+
+# density_tempered(ibis, y): the loop of smc_samplers.jl:222-281 with the exact logZ (ibis.jl exports the name)
+function density_tempered(ib::HipIBIS, y::Vector{Float64}, verbose=true)
+    GC.@preserve y smc_check(ccall((:smc_ibis_filter, LIBSMC), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), ib.h, y, length(y)))
+    logZ = ibis_get(ib; logZ=true).logZ
+    ib.ess = reweight(logZ)[3]; ξ = 0.0
+    while ξ < 1.0
+        ξ, ib.ess, flag, logw = temper(logZ, ξ, ib.ess_min)
+        if verbose @printf("ξ = %1.5f\tess = %4.3f", ξ, ib.ess) end
+        if flag
+            resample!(ib, logw)
+            rejuvenate!(ib, y, ξ, verbose)
+            logZ = ibis_get(ib; logZ=true).logZ
+        else
+            GC.@preserve logw smc_check(ccall((:smc_ibis_set_logw, LIBSMC), Cint, (Ptr{Cvoid}, Ptr{Float64}), ib.h, logw))
+        end
+        if verbose print("\n") end
+    end
+    return ib
+end

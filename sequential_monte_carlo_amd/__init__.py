@@ -2,10 +2,11 @@
 charlesknipp/sequential_monte_carlo behind the reference's own API names.
 
 Hand-written HIP kernels for gfx950 (csrc/) behind a C ABI (include/smc_hip.h); this package is the
-host-side mirror of src/particles.jl, src/state_space_models.jl and src/smc_samplers.jl.
+host-side mirror of src/particles.jl, src/state_space_models.jl, src/smc_samplers.jl and src/ibis.jl.
 There is no CPU fallback: importing works anywhere, running a filter needs the GPU library.
 """
 from .distributions import LogNormal, Normal, TruncatedNormal, Uniform, product_distribution  # noqa: F401
+from .ibis import IBIS  # noqa: F401
 from .kalman_filter import log_likelihood_kalman  # noqa: F401
 from .models import (UCSV, LinearModel, StateSpaceModel, StochasticVolatility, UnivariateLinearGaussian,  # noqa: F401
                      simulate, unobserved_components, unobserved_components_stochastic_volatility)

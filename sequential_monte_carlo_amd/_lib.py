@@ -29,6 +29,8 @@ EXPORTS = [
     "smc_host_outer_advance", "smc_host_outer_temper", "smc_host_outer_resample", "smc_host_rw_factor",
     "smc_set_summaries", "smc_get_summaries", "smc_set_summary_mode", "smc_host_quantile7", "smc_host_sample_moments",
     "smc_set_proposal", "smc_host_optimal_proposal", "smc_host_guided_step", "smc_device_guided_step",
+    "smc_ibis_create", "smc_ibis_destroy", "smc_ibis_configure", "smc_ibis_set_theta", "smc_ibis_window", "smc_ibis_commit",
+    "smc_ibis_filter", "smc_ibis_permute", "smc_ibis_set_logw", "smc_ibis_rejuvenate", "smc_ibis_get",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -159,6 +161,18 @@ def lib():
     L.smc_comm_exchange_slots.argtypes = [h, h, _i32p, C.c_int64]
     L.smc_comm_plan_exchange.argtypes = [_i32p, C.c_int64, C.c_int, C.c_int, _i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _i32p,
                                          C.POINTER(C.c_int64)]
+    L.smc_ibis_create.argtypes = [C.c_int64, C.c_uint64, C.c_int, C.c_int, C.POINTER(h)]
+    L.smc_ibis_destroy.argtypes = [h]
+    L.smc_ibis_configure.argtypes = [h, C.c_int, _i32p, _dp, _i32p, _dp]
+    L.smc_ibis_set_theta.argtypes = [h, _dp]
+    L.smc_ibis_window.argtypes = [h, _dp, C.c_int, _dp, _u64p]
+    L.smc_ibis_commit.argtypes = [h, C.c_int]
+    L.smc_ibis_filter.argtypes = [h, _dp, C.c_int64]
+    L.smc_ibis_permute.argtypes = [h, _i32p]
+    L.smc_ibis_set_logw.argtypes = [h, _dp]
+    L.smc_ibis_rejuvenate.argtypes = [h, _dp, C.c_int64, C.c_double, _dp, _dp, C.c_int, C.c_uint64, C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_uint8)]
+    L.smc_ibis_get.argtypes = [h, _dp, _dp, _dp, _dp, _dp]
     L.smc_last_error.restype = C.c_char_p
     L.smc_version.restype = C.c_char_p
     _lib = L
@@ -660,3 +674,82 @@ class Handle:
 
     def synchronize(self):
         check(lib().smc_synchronize(self._h))
+
+
+class IbisHandle:
+    """The device half of the IBIS sampler (smc_ibis_*): M parameter particles with their exact Kalman state, resident on one
+    GPU.  d: parameter dimension; families / pars: the prior (distributions.py spec()); raw_from / raw_const: ThetaMap to LG1D rows."""
+
+    def __init__(self, M, d, families, pars, raw_from, raw_const, seed=1, device=0, predict_first=False):
+        self._h = C.c_void_p()
+        self.M, self.d = int(M), int(d)
+        self.nseg = (self.M + OUTER_SEG - 1) // OUTER_SEG
+        check(lib().smc_ibis_create(self.M, int(seed), int(device), int(bool(predict_first)), C.byref(self._h)))
+        fam = np.ascontiguousarray(families, dtype=np.int32)
+        par = np.ascontiguousarray(pars, dtype=np.float64).reshape(fam.size, PRIOR_NPAR)
+        rf = np.ascontiguousarray(raw_from, dtype=np.int32)
+        rc = np.ascontiguousarray(raw_const, dtype=np.float64)
+        assert fam.size == self.d and rf.size == rc.size == 6
+        check(lib().smc_ibis_configure(self._h, self.d, fam.ctypes.data_as(_i32p), _d(par), rf.ctypes.data_as(_i32p), _d(rc)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().smc_ibis_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_theta(self, theta):
+        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(self.M, self.d)
+        check(lib().smc_ibis_set_theta(self._h, _d(theta)))
+
+    def window(self, y, want_lik=False):
+        """len(y) online steps in one launch, not yet kept: (records [k][nseg][4] uint64, lik [k][M] or None); follow with commit(j)"""
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        rec = np.zeros((y.size, self.nseg, 4), dtype=np.uint64)
+        lik = np.zeros((y.size, self.M)) if want_lik else None
+        check(lib().smc_ibis_window(self._h, _d(y), y.size, _d(lik), rec.ctypes.data_as(_u64p)))
+        return rec, lik
+
+    def commit(self, j):
+        check(lib().smc_ibis_commit(self._h, int(j)))
+
+    def filter(self, y):
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        check(lib().smc_ibis_filter(self._h, _d(y), y.size))
+
+    def permute(self, a):
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        assert a.size == self.M
+        check(lib().smc_ibis_permute(self._h, a.ctypes.data_as(_i32p)))
+
+    def set_logw(self, logw):
+        logw = np.ascontiguousarray(logw, dtype=np.float64)
+        assert logw.size == self.M
+        check(lib().smc_ibis_set_logw(self._h, _d(logw)))
+
+    def rejuvenate(self, y, xi, chol, scales, move_seed):
+        """rejuvenate!(ibis, y, xi) in one launch -> (number of particles that moved, moved mask [M])"""
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        chol = np.ascontiguousarray(chol, dtype=np.float64).reshape(self.d, self.d)
+        scales = np.ascontiguousarray(scales, dtype=np.float64)
+        n = C.c_int64()
+        moved = np.zeros(self.M, dtype=np.uint8)
+        check(lib().smc_ibis_rejuvenate(self._h, _d(y), y.size, float(xi), _d(chol), _d(scales), scales.size, int(move_seed), C.byref(n),
+                                        moved.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return int(n.value), moved.astype(bool)
+
+    def get(self, theta=False, x=False, S=False, logZ=False, logw=False):
+        """the requested arrays from the device, as a dict"""
+        out = {}
+        if theta:
+            out["theta"] = np.zeros((self.M, self.d))
+        for name, want in (("x", x), ("S", S), ("logZ", logZ), ("logw", logw)):
+            if want:
+                out[name] = np.zeros(self.M)
+        check(lib().smc_ibis_get(self._h, _d(out.get("theta")), _d(out.get("x")), _d(out.get("S")), _d(out.get("logZ")), _d(out.get("logw"))))
+        return out

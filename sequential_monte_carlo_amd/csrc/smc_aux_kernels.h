@@ -53,12 +53,7 @@ __global__ void k_kalman(const double* raw, int64_t ntheta, const double* y, int
     const double A = raw[m * 6 + 0], B = raw[m * 6 + 1], Q = raw[m * 6 + 2], R = raw[m * 6 + 3];
     double x = raw[m * 6 + 4], S = raw[m * 6 + 5], logZ = 0.0;
     for (int64_t t = 0; t < T; ++t) {
-        if (predict_first || t > 0) { x = A * x; S = (A * A) * S + Q; }
-        const double s = (B * B) * S + R, dy = y[t] - B * x;
-        const double K = S * B, inv = 1.0 / s;
-        x = x + (K * inv) * dy;
-        S = S - (K * K) * inv;
-        logZ += -0.5 * (0x1.d67f1c864beb5p+0 + sp_log(s) + (dy / s) * dy);
+        logZ += kalman_step(A, B, Q, R, predict_first || t > 0, y[t], x, S);
     }
     out[m * 3 + 0] = x; out[m * 3 + 1] = S; out[m * 3 + 2] = logZ;
 }

@@ -1,0 +1,336 @@
+// smc_ibis.hip -- C ABI of the IBIS sampler (include/smc_hip.h "IBIS"; src/ibis.jl): the handle that keeps a cloud of
+// parameter particles with their exact Kalman state on the device, and the launches of smc_ibis_kernels.h.
+#include "../../include/smc_hip.h"
+#include "smc_ibis_kernels.h"
+
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+extern "C" int smc_set_error_(int code, const char* msg);   // smc_capi.hip
+
+using namespace smc;
+
+namespace {
+int fail(int code, const std::string& msg) { return smc_set_error_(code, msg.c_str()); }
+}  // namespace
+#define HIPCHK(expr)                                                                                          \
+    do {                                                                                                      \
+        hipError_t _e = (expr);                                                                               \
+        if (_e != hipSuccess)                                                                                 \
+            return fail(SMC_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" +      \
+                                      std::to_string(__LINE__) + ")");                                        \
+    } while (0)
+
+struct smc_ibis_s {
+    uint32_t magic = 0x53494249u;   // "IBIS": the boundary type is void*, so a foreign pointer is at least noticed
+    int device = 0;
+    int predict_first = 0;
+    hipStream_t stream = nullptr;
+    IbisView v{};
+    int cp = 0, cs = 0;             // current (theta, raw) set and current (x, S, logZ, logw) set
+    PmmhSpec spec{};
+    bool configured = false, have_theta = false;
+    int64_t t = 0;                  // observations committed so far
+    int win_k = 0;                  // steps of the pending window (its end state sits in set cs ^ 1); 0: none
+    std::vector<double> win_y;
+    double* d_y = nullptr;   size_t y_cap = 0;
+    double* d_lik = nullptr; size_t lik_cap = 0;
+    uint64_t* d_rec = nullptr; size_t rec_cap = 0;
+    int32_t* d_a = nullptr;
+    unsigned char* d_moved = nullptr;
+    unsigned long long* d_count = nullptr;
+    double* d_chol = nullptr;       // [MAX_DTHETA^2] | sq [IBIS_MAX_CHAIN]
+};
+typedef smc_ibis_s* ibis_t;
+
+namespace {
+constexpr int IBIS_MAX_CHAIN = 64;
+
+ibis_t as_ibis(void* p) {
+    ibis_t h = (ibis_t)p;
+    return (h && h->magic == 0x53494249u) ? h : nullptr;
+}
+unsigned grid_of(int64_t M) { return (unsigned)((M + IBIS_THREADS - 1) / IBIS_THREADS); }
+
+template <class T>
+hipError_t grow(T** p, size_t* cap, size_t count) {
+    if (*cap >= count) return hipSuccess;
+    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
+    if (e == hipSuccess) *cap = count;
+    return e;
+}
+
+void release(ibis_t h) {
+    for (int b = 0; b < 2; ++b) {
+        (void)hipFree(h->v.theta[b]); (void)hipFree(h->v.raw[b]); (void)hipFree(h->v.x[b]);
+        (void)hipFree(h->v.S[b]); (void)hipFree(h->v.logZ[b]); (void)hipFree(h->v.logw[b]);
+    }
+    (void)hipFree(h->d_y); (void)hipFree(h->d_lik); (void)hipFree(h->d_rec); (void)hipFree(h->d_a);
+    (void)hipFree(h->d_moved); (void)hipFree(h->d_count); (void)hipFree(h->d_chol);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+template <int D>
+void launch_init(ibis_t h) {
+    hipLaunchKernelGGL((k_ibis_init<D>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->spec);
+}
+template <int D>
+void launch_rejuvenate(ibis_t h, int64_t T, double xi, int chain, uint64_t move_seed) {
+    hipLaunchKernelGGL((k_ibis_rejuvenate<D>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->spec,
+                       h->d_y, T, h->predict_first, xi, h->d_chol, h->d_chol + MAX_DTHETA * MAX_DTHETA, chain, move_seed, h->d_moved,
+                       h->d_count);
+}
+#define IBIS_BY_D(d, CALL)                                                                                      \
+    switch (d) {                                                                                                \
+    case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;             \
+    case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; default: CALL(8); break;            \
+    }
+
+// run `steps` observations from the committed state in place (no records): the prefix of a window that is kept, or a whole series
+int steps_in_place(ibis_t h, const double* y, int64_t steps) {
+    HIPCHK(grow(&h->d_y, &h->y_cap, (size_t)steps));
+    HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)steps * 8, hipMemcpyHostToDevice, h->stream));
+    int64_t done = 0;
+    while (done < steps) {   // (the kernel's step count is an int)
+        const int k = (int)(steps - done > (1 << 20) ? (1 << 20) : steps - done);
+        hipLaunchKernelGGL((k_ibis_window<false>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->cs,
+                           h->d_y + done, k, (h->t + done > 0 || h->predict_first) ? 1 : 0, (double*)nullptr, (uint64_t*)nullptr);
+        HIPCHK(hipGetLastError());
+        done += k;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));   // (y is the caller's: the copy has to be over when the call returns)
+    h->t += steps;
+    return SMC_OK;
+}
+}  // namespace
+
+extern "C" int smc_ibis_create(int64_t n_theta, uint64_t seed, int device, int predict_first, void* out) {
+    (void)seed;   // every random number of the device side is keyed by the move_seed of its call
+    if (!out) return fail(SMC_EINVAL, "smc_ibis_create: NULL out");
+    *(void**)out = nullptr;
+    if (n_theta < 2 || n_theta > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_ibis_create: 2 <= n_theta <= 2^30");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(SMC_EHIP, "smc_ibis_create: no HIP device");
+    if (device < 0 || device >= ndev) return fail(SMC_EINVAL, "smc_ibis_create: bad device");
+    HIPCHK(hipSetDevice(device));
+    ibis_t h = new (std::nothrow) smc_ibis_s();
+    if (!h) return fail(SMC_ENOMEM, "smc_ibis_create: out of host memory");
+    h->device = device;
+    h->predict_first = predict_first ? 1 : 0;
+    h->v.M = n_theta;
+    const size_t M = (size_t)n_theta;
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    for (int b = 0; b < 2 && e == hipSuccess; ++b) {
+        if (e == hipSuccess) e = hipMalloc((void**)&h->v.theta[b], M * MAX_DTHETA * 8);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->v.raw[b], M * IBIS_NRAW * 8);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->v.x[b], M * 8);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->v.S[b], M * 8);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->v.logZ[b], M * 8);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->v.logw[b], M * 8);
+    }
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_a, M * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_moved, M);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_count, 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_chol, (MAX_DTHETA * MAX_DTHETA + IBIS_MAX_CHAIN) * 8);
+    if (e != hipSuccess) {
+        release(h);
+        return fail(e == hipErrorOutOfMemory ? SMC_ENOMEM : SMC_EHIP, std::string("smc_ibis_create: ") + hipGetErrorString(e));
+    }
+    *(void**)out = h;
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_destroy(void* hp) {
+    ibis_t h = as_ibis(hp);
+    if (!h) return fail(SMC_EINVAL, "smc_ibis_destroy: not an IBIS handle");
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    h->magic = 0;
+    release(h);
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_configure(void* hp, int d_theta, const int32_t* prior_family, const double* prior_par, const int32_t* raw_from,
+                                  const double* raw_const) {
+    ibis_t h = as_ibis(hp);
+    if (!h) return fail(SMC_EINVAL, "smc_ibis_configure: not an IBIS handle");
+    if (!prior_family || !prior_par || !raw_from || !raw_const) return fail(SMC_EINVAL, "smc_ibis_configure: NULL argument");
+    if (d_theta < 1 || d_theta > MAX_DTHETA) return fail(SMC_EINVAL, "smc_ibis_configure: 1 <= d_theta <= 8");
+    PmmhSpec sp{};
+    sp.d = d_theta;
+    for (int i = 0; i < d_theta; ++i) {
+        if (prior_family[i] < PRIOR_UNIFORM || prior_family[i] > PRIOR_LOGNORMAL)
+            return fail(SMC_EINVAL, "smc_ibis_configure: unknown prior family " + std::to_string(prior_family[i]));
+        sp.family[i] = prior_family[i];
+        for (int k = 0; k < PRIOR_NPAR; ++k) sp.par[i][k] = prior_par[(size_t)i * PRIOR_NPAR + k];
+    }
+    sp.nraw = IBIS_NRAW;
+    for (int k = 0; k < IBIS_NRAW; ++k) {
+        if (raw_from[k] >= d_theta) return fail(SMC_EINVAL, "smc_ibis_configure: raw_from index out of range");
+        sp.raw_from[k] = raw_from[k];
+        sp.raw_const[k] = raw_const[k];
+    }
+    h->spec = sp;
+    h->configured = true;
+    h->have_theta = false;
+    h->win_k = 0;
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_set_theta(void* hp, const double* theta) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !theta) return fail(SMC_EINVAL, "smc_ibis_set_theta: bad argument");
+    if (!h->configured) return fail(SMC_ESTATE, "smc_ibis_set_theta: smc_ibis_configure has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t M = (size_t)h->v.M;
+    const int d = h->spec.d;
+    std::vector<double> pad(M * MAX_DTHETA, 0.0);
+    for (size_t m = 0; m < M; ++m)
+        for (int i = 0; i < d; ++i) pad[m * MAX_DTHETA + i] = theta[m * d + i];
+    HIPCHK(hipMemcpyAsync(h->v.theta[h->cp], pad.data(), pad.size() * 8, hipMemcpyHostToDevice, h->stream));
+#define IBIS_CALL_INIT(D) launch_init<D>(h)
+    IBIS_BY_D(d, IBIS_CALL_INIT)
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->have_theta = true;
+    h->t = 0;
+    h->win_k = 0;
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_window(void* hp, const double* y, int k, double* lik, uint64_t* rec) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !y || !rec) return fail(SMC_EINVAL, "smc_ibis_window: bad argument");
+    if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_window: smc_ibis_set_theta has not been called");
+    if (k < 1 || k > IBIS_MAX_WINDOW) return fail(SMC_EINVAL, "smc_ibis_window: 1 <= k <= 64");
+    HIPCHK(hipSetDevice(h->device));
+    h->win_k = 0;
+    const size_t M = (size_t)h->v.M, nseg = (M + IBIS_OSEG - 1) / IBIS_OSEG;
+    HIPCHK(grow(&h->d_y, &h->y_cap, (size_t)k));
+    HIPCHK(grow(&h->d_rec, &h->rec_cap, (size_t)k * nseg * 4));
+    if (lik) HIPCHK(grow(&h->d_lik, &h->lik_cap, (size_t)k * M));
+    HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)k * 8, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL((k_ibis_window<true>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->cs ^ 1,
+                       h->d_y, k, (h->t > 0 || h->predict_first) ? 1 : 0, lik ? h->d_lik : (double*)nullptr, h->d_rec);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rec, h->d_rec, (size_t)k * nseg * 32, hipMemcpyDeviceToHost, h->stream));
+    if (lik) HIPCHK(hipMemcpyAsync(lik, h->d_lik, (size_t)k * M * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->win_y.assign(y, y + k);
+    h->win_k = k;
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_commit(void* hp, int j) {
+    ibis_t h = as_ibis(hp);
+    if (!h) return fail(SMC_EINVAL, "smc_ibis_commit: not an IBIS handle");
+    if (h->win_k < 1) return fail(SMC_ESTATE, "smc_ibis_commit: no pending window");
+    if (j < 0 || j > h->win_k) return fail(SMC_EINVAL, "smc_ibis_commit: j outside the window");
+    HIPCHK(hipSetDevice(h->device));
+    const int k = h->win_k;
+    h->win_k = 0;
+    if (j == k) {            // the window's end state is the new state
+        h->cs ^= 1;
+        h->t += k;
+        return SMC_OK;
+    }
+    if (j == 0) return SMC_OK;
+    return steps_in_place(h, h->win_y.data(), j);   // the same arithmetic on the same operands: the bits of the window's first j steps
+}
+
+extern "C" int smc_ibis_filter(void* hp, const double* y, int64_t T) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !y || T < 1) return fail(SMC_EINVAL, "smc_ibis_filter: bad argument");
+    if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_filter: smc_ibis_set_theta has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    h->win_k = 0;
+    hipLaunchKernelGGL(k_ibis_reset, dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs);
+    HIPCHK(hipGetLastError());
+    h->t = 0;
+    return steps_in_place(h, y, T);
+}
+
+extern "C" int smc_ibis_permute(void* hp, const int32_t* a) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !a) return fail(SMC_EINVAL, "smc_ibis_permute: bad argument");
+    if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_permute: smc_ibis_set_theta has not been called");
+    const int64_t M = h->v.M;
+    for (int64_t m = 0; m < M; ++m)
+        if (a[m] < 0 || a[m] >= M) return fail(SMC_EINVAL, "smc_ibis_permute: ancestor index out of range");
+    HIPCHK(hipSetDevice(h->device));
+    h->win_k = 0;
+    HIPCHK(hipMemcpyAsync(h->d_a, a, (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_ibis_permute, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->d_a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->cp ^= 1;
+    h->cs ^= 1;
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_set_logw(void* hp, const double* logw) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !logw) return fail(SMC_EINVAL, "smc_ibis_set_logw: bad argument");
+    if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_set_logw: smc_ibis_set_theta has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    h->win_k = 0;
+    HIPCHK(hipMemcpyAsync(h->v.logw[h->cs], logw, (size_t)h->v.M * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_rejuvenate(void* hp, const double* y, int64_t T, double xi, const double* chol, const double* scales, int chain,
+                                   uint64_t move_seed, int64_t* accepted, uint8_t* moved) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !y || !chol || !scales) return fail(SMC_EINVAL, "smc_ibis_rejuvenate: bad argument");
+    if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_rejuvenate: smc_ibis_set_theta has not been called");
+    if (T < 1 || chain < 0 || chain > IBIS_MAX_CHAIN) return fail(SMC_EINVAL, "smc_ibis_rejuvenate: T >= 1, 0 <= chain <= 64");
+    HIPCHK(hipSetDevice(h->device));
+    h->win_k = 0;
+    const int d = h->spec.d;
+    double par[MAX_DTHETA * MAX_DTHETA + IBIS_MAX_CHAIN] = {0.0};
+    for (int i = 0; i < d * d; ++i) par[i] = chol[i];
+    for (int c = 0; c < chain; ++c) par[MAX_DTHETA * MAX_DTHETA + c] = sqrt(scales[c]);
+    HIPCHK(grow(&h->d_y, &h->y_cap, (size_t)T));
+    HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_chol, par, sizeof(par), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_count, 0, 8, h->stream));
+#define IBIS_CALL_REJ(D) launch_rejuvenate<D>(h, T, xi, chain, move_seed)
+    IBIS_BY_D(d, IBIS_CALL_REJ)
+    HIPCHK(hipGetLastError());
+    unsigned long long n = 0;
+    HIPCHK(hipMemcpyAsync(&n, h->d_count, 8, hipMemcpyDeviceToHost, h->stream));
+    if (moved) HIPCHK(hipMemcpyAsync(moved, h->d_moved, (size_t)h->v.M, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (accepted) *accepted = (int64_t)n;
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_get(void* hp, double* theta, double* x, double* S, double* logZ, double* logw) {
+    ibis_t h = as_ibis(hp);
+    if (!h) return fail(SMC_EINVAL, "smc_ibis_get: not an IBIS handle");
+    if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_get: smc_ibis_set_theta has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t M = (size_t)h->v.M;
+    std::vector<double> pad;
+    if (theta) {
+        pad.resize(M * MAX_DTHETA);
+        HIPCHK(hipMemcpyAsync(pad.data(), h->v.theta[h->cp], pad.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (x) HIPCHK(hipMemcpyAsync(x, h->v.x[h->cs], M * 8, hipMemcpyDeviceToHost, h->stream));
+    if (S) HIPCHK(hipMemcpyAsync(S, h->v.S[h->cs], M * 8, hipMemcpyDeviceToHost, h->stream));
+    if (logZ) HIPCHK(hipMemcpyAsync(logZ, h->v.logZ[h->cs], M * 8, hipMemcpyDeviceToHost, h->stream));
+    if (logw) HIPCHK(hipMemcpyAsync(logw, h->v.logw[h->cs], M * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (theta) {
+        const int d = h->spec.d;
+        for (size_t m = 0; m < M; ++m)
+            for (int i = 0; i < d; ++i) theta[m * d + i] = pad[m * MAX_DTHETA + i];
+    }
+    return SMC_OK;
+}

@@ -1,0 +1,226 @@
+// smc_ibis_kernels.h -- the IBIS sampler (src/ibis.jl): SMC^2 whose inner "filter" is the exact scalar Kalman filter of the
+// univariate LinearModel.  One lane per parameter particle; the whole state of a particle is (theta, row, x, Sigma, logZ, logw),
+// resident on the device for the life of the handle.  Included by smc_ibis.hip only.
+//
+//   k_ibis_init        theta -> model rows, (x, Sigma) = (x0, sigma0), logZ = logw = 0          ibis.jl:35-43
+//   k_ibis_window      k online steps smc²! (:166-187; smc², :134-147, is k = 1 from the initial state) and the segment
+//                      records of the outer reweight after every step
+//   k_ibis_rejuvenate  rejuvenate! (:86-125): the whole chain of PMMH moves of a particle, Kalman re-filters included
+//   k_ibis_permute     resample! (:73-84): gather through the ancestor vector
+//
+// Random numbers: pmmh_propose / pmmh_log_uniform keyed by (move_seed, stream = index of the parameter particle, chain
+// position) and nothing else, so no result depends on the launch geometry.  Every store is a plain vector store.
+#pragma once
+#include "smc_kernels.h"
+
+namespace smc {
+
+constexpr int IBIS_OSEG = 8;              // SMC_OUTER_SEG: entries per segment record of the outer reweight
+constexpr int IBIS_NRAW = 6;              // LinearModel row (A, B, Q, R, x0, sigma0)
+constexpr int IBIS_THREADS = 64;          // one wave per workgroup: a cloud of a few hundred particles still spreads over the CUs
+constexpr int IBIS_MAX_WINDOW = 64;
+
+struct IbisView {
+    int64_t M;
+    double* theta[2];     // [M][MAX_DTHETA]   (theta, raw) and (x, S, logZ, logw) are double-buffered separately:
+    double* raw[2];       // [M][IBIS_NRAW]     a window leaves its end state in the other (x, S, logZ, logw) set,
+    double* x[2];         // [M]                a permutation gathers both
+    double* S[2];         // [M]
+    double* logZ[2];      // [M]
+    double* logw[2];      // [M]
+};
+
+// reductions over the 8 consecutive lanes of a segment (lane & ~7 .. lane | 7), result in every one of them: quad_perm
+// [1,0,3,2], quad_perm [2,3,0,1] and row_half_mirror (lane i <-> 7 - i of each half row) as DPP moves
+template <int CTRL>
+__device__ __forceinline__ uint32_t seg8_move(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
+}
+template <int CTRL>
+__device__ __forceinline__ uint64_t seg8_move64(uint64_t v) {
+    return ((uint64_t)seg8_move<CTRL>((uint32_t)(v >> 32)) << 32) | seg8_move<CTRL>((uint32_t)v);
+}
+__device__ __forceinline__ int seg8_max(int v) {
+    int o = (int)seg8_move<0xB1>((uint32_t)v); v = o > v ? o : v;
+    o = (int)seg8_move<0x4E>((uint32_t)v); v = o > v ? o : v;
+    o = (int)seg8_move<0x141>((uint32_t)v); v = o > v ? o : v;
+    return v;
+}
+__device__ __forceinline__ uint64_t seg8_sum(uint64_t v) {
+    v += seg8_move64<0xB1>(v);
+    v += seg8_move64<0x4E>(v);
+    v += seg8_move64<0x141>(v);
+    return v;
+}
+__device__ __forceinline__ U128 seg8_sum128(U128 v) {
+    v = add128(v, U128{seg8_move64<0xB1>(v.lo), seg8_move64<0xB1>(v.hi)});
+    v = add128(v, U128{seg8_move64<0x4E>(v.lo), seg8_move64<0x4E>(v.hi)});
+    v = add128(v, U128{seg8_move64<0x141>(v.lo), seg8_move64<0x141>(v.hi)});
+    return v;
+}
+
+// smc.model(theta) as a gather without a run-time index into registers: row[k] = theta[raw_from[k]] or raw_const[k]
+template <int D>
+__device__ __forceinline__ void ibis_row(const PmmhSpec& s, const double* th, double* row) {
+#pragma unroll
+    for (int k = 0; k < IBIS_NRAW; ++k) {
+        double v = s.raw_const[k];
+        const int from = s.raw_from[k];
+#pragma unroll
+        for (int i = 0; i < D; ++i) v = from == i ? th[i] : v;
+        row[k] = v;
+    }
+}
+
+// theta -> rows and the initial state of every particle   ibis.jl:38-43
+template <int D>
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_init(IbisView v, int cp, int cs, PmmhSpec s) {
+    const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
+    if (m >= v.M) return;
+    double th[D], row[IBIS_NRAW];
+#pragma unroll
+    for (int i = 0; i < D; ++i) th[i] = v.theta[cp][m * MAX_DTHETA + i];
+    ibis_row<D>(s, th, row);
+#pragma unroll
+    for (int k = 0; k < IBIS_NRAW; ++k) v.raw[cp][m * IBIS_NRAW + k] = row[k];
+    v.x[cs][m] = row[4];
+    v.S[cs][m] = row[5];
+    v.logZ[cs][m] = 0.0;
+    v.logw[cs][m] = 0.0;
+}
+
+// The same state from the rows alone: the beginning of a whole-series filter (density_tempered's first pass)
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_reset(IbisView v, int cp, int cs) {
+    const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
+    if (m >= v.M) return;
+    v.x[cs][m] = v.raw[cp][m * IBIS_NRAW + 4];
+    v.S[cs][m] = v.raw[cp][m * IBIS_NRAW + 5];
+    v.logZ[cs][m] = 0.0;
+    v.logw[cs][m] = 0.0;
+}
+
+// k steps of smc²! (ibis.jl:166-187) from the committed state (set cs), one lane per parameter particle:
+//   (x, S) <- kalman_filter(row, x, S, y[j]);  logw += lik;  logZ += lik          (:171-181)
+// RECORD: lik [k][M] (optional) and, after every step, the record (kb, S, S2hi, S2lo) of each segment of 8 consecutive
+// particles of reweight(logw) (:187) - the integers smc_host_outer_window computes from the same logw, so the host only
+// walks k x nseg records.  The end state goes to the set `dst` (== cs: the steps are committed in place).
+// predict0: whether the first of the k steps predicts (false only at t = 1 of a sampler with predict_first = 0).
+template <bool RECORD>
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_window(IbisView v, int cp, int cs, int dst, const double* y, int k, int predict0,
+                                                             double* lik /*[k][M] or null*/, uint64_t* rec /*[k][nseg][4]*/) {
+    const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
+    const bool valid = m < v.M;
+    const int64_t mm = valid ? m : v.M - 1;            // lanes beyond the cloud compute on the last particle and store nothing
+    const double* row = v.raw[cp] + mm * IBIS_NRAW;
+    const double A = row[0], B = row[1], Q = row[2], R = row[3];
+    double x = v.x[cs][mm], S = v.S[cs][mm], logZ = v.logZ[cs][mm], logw = v.logw[cs][mm];
+    const int64_t nseg = (v.M + IBIS_OSEG - 1) / IBIS_OSEG;
+    for (int j = 0; j < k; ++j) {
+        const double l = kalman_step(A, B, Q, R, j > 0 || predict0 != 0, y[j], x, S);
+        logw = logw + l;
+        logZ = logZ + l;
+        if (RECORD) {
+            if (lik && valid) lik[(size_t)j * (size_t)v.M + (size_t)m] = l;
+            const bool alive = valid && lw_alive(logw);
+            double kd = 0.0;
+            const double p = sp_exp_parts(alive ? logw : 0.0, kd);
+            const int ki = alive ? (int)kd : -(1 << 30);
+            const int kb = seg8_max(ki);
+            const uint64_t q = alive ? fix_weight_i(p, ki - kb, FIX_BITS) : 0;
+            const uint64_t Ssum = seg8_sum(q);
+            const U128 s2 = seg8_sum128(sq128(q));
+            if (valid && (threadIdx.x & (IBIS_OSEG - 1)) == 0) {
+                uint64_t* r = rec + ((size_t)j * (size_t)nseg + (size_t)(m / IBIS_OSEG)) * 4;
+                const bool live = kb != -(1 << 30);
+                r[0] = d2bits(live ? (double)kb : -inf());
+                r[1] = live ? Ssum : 0;
+                r[2] = live ? s2.hi : 0;
+                r[3] = live ? s2.lo : 0;
+            }
+        }
+    }
+    if (valid) {
+        v.x[dst][m] = x;
+        v.S[dst][m] = S;
+        v.logZ[dst][m] = logZ;
+        v.logw[dst][m] = logw;
+    }
+}
+
+// rejuvenate!(ibis, y, xi) (ibis.jl:86-125) in one launch, one lane per parameter particle m:
+//   for c in 1:chain                                                                  :96
+//       theta' = rand(kernel(theta[m], scales[c]))       pmmh_propose                 :97
+//       if insupport(prior, theta')                      (a lane outside is predicated off for this c)   :99
+//           x', S', logZ' = log_likelihood(y, model(theta'))   the Kalman filter over y[0:T) in registers  :100
+//           accept iff logZ' + logprior(theta') > -inf and log(rand()) < xi (logZ' - logZ) + logprior(theta') - logprior(theta)
+//           then theta, logZ, x, S <- theta', logZ', x', S'; acc_array[m] = 1          :102-115
+//   omega[m] = 1                                          logw[m] = 0                  :118
+// y[t] is the same address in every lane (the compiler reads it through the scalar cache); chol [D][D] and sq [chain] likewise.
+template <int D>
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rejuvenate(IbisView v, int cp, int cs, PmmhSpec s, const double* y, int64_t T,
+                                                                 int predict_first, double xi, const double* chol, const double* sq,
+                                                                 int chain, uint64_t move_seed, unsigned char* moved,
+                                                                 unsigned long long* n_moved) {
+    const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
+    const bool valid = m < v.M;
+    const int64_t mm = valid ? m : v.M - 1;
+    const uint32_t stream = (uint32_t)mm;
+    double th[D], row[IBIS_NRAW];
+#pragma unroll
+    for (int i = 0; i < D; ++i) th[i] = v.theta[cp][mm * MAX_DTHETA + i];
+#pragma unroll
+    for (int k = 0; k < IBIS_NRAW; ++k) row[k] = v.raw[cp][mm * IBIS_NRAW + k];
+    double x = v.x[cs][mm], S = v.S[cs][mm], logZ = v.logZ[cs][mm];
+    bool any = false;
+    for (int c = 0; c < chain; ++c) {
+        double pr[D], prow[IBIS_NRAW];
+        pmmh_propose<D>(s, move_seed, stream, (uint32_t)c, th, chol, sq[c], pr);
+        const bool ok = pmmh_insupport<D>(s, pr);
+        ibis_row<D>(s, pr, prow);
+        const double lpp = pmmh_logprior<D>(s, pr), lpc = pmmh_logprior<D>(s, th);
+        double xp = prow[4], Sp = prow[5], logZp = 0.0;
+        for (int64_t t = 0; t < T; ++t) logZp += kalman_step(prow[0], prow[1], prow[2], prow[3], predict_first != 0 || t > 0, y[t], xp, Sp);
+        const double likelihood_ratio = xi * (logZp - logZ), prior_ratio = lpp - lpc;
+        const double acc_ratio = likelihood_ratio + prior_ratio, log_post_prop = logZp + lpp;
+        const bool acc = ok && log_post_prop > -inf() && pmmh_log_uniform(move_seed, stream, (uint32_t)c) < acc_ratio;
+#pragma unroll
+        for (int i = 0; i < D; ++i) th[i] = acc ? pr[i] : th[i];
+#pragma unroll
+        for (int k = 0; k < IBIS_NRAW; ++k) row[k] = acc ? prow[k] : row[k];
+        logZ = acc ? logZp : logZ;
+        x = acc ? xp : x;
+        S = acc ? Sp : S;
+        any = any || acc;
+    }
+    any = any && valid;
+    if (valid) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) v.theta[cp][m * MAX_DTHETA + i] = th[i];
+#pragma unroll
+        for (int k = 0; k < IBIS_NRAW; ++k) v.raw[cp][m * IBIS_NRAW + k] = row[k];
+        v.x[cs][m] = x;
+        v.S[cs][m] = S;
+        v.logZ[cs][m] = logZ;
+        v.logw[cs][m] = 0.0;
+        moved[m] = any ? 1 : 0;
+    }
+    const unsigned long long cnt = (unsigned long long)__popcll(__ballot(any));   // one integer add per wave: order-free
+    if (threadIdx.x == 0 && cnt) atomicAdd(n_moved, cnt);
+}
+
+// resample!(ibis) (ibis.jl:73-84): particle m <- particle a[m], a value copy of everything it owns, into the other buffers
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_permute(IbisView v, int cp, int cs, const int32_t* a) {
+    const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
+    if (m >= v.M) return;
+    const int64_t src = a[m];
+#pragma unroll
+    for (int i = 0; i < MAX_DTHETA; ++i) v.theta[cp ^ 1][m * MAX_DTHETA + i] = v.theta[cp][src * MAX_DTHETA + i];
+#pragma unroll
+    for (int k = 0; k < IBIS_NRAW; ++k) v.raw[cp ^ 1][m * IBIS_NRAW + k] = v.raw[cp][src * IBIS_NRAW + k];
+    v.x[cs ^ 1][m] = v.x[cs][src];
+    v.S[cs ^ 1][m] = v.S[cs][src];
+    v.logZ[cs ^ 1][m] = v.logZ[cs][src];
+    v.logw[cs ^ 1][m] = v.logw[cs][src];
+}
+
+}  // namespace smc

@@ -686,27 +686,45 @@ SMC_HD double prior_logpdf(int fam, const double* par, double x) {
     return -inf();
 }
 // insupport / logpdf of the product prior: components in order, sum from 0.0 left to right
+// (D > 0: the dimension as a compile-time constant - s.d == D - so that theta stays in a kernel's registers; D = 0, the default:
+//  s.d.  The loops run to MAX_DTHETA under a guard and are unrolled: every array index is a constant either way, and the
+//  operations and their order are the same.)
+template <int D = 0>
 SMC_HD bool pmmh_insupport(const PmmhSpec& s, const double* th) {
+    const int d = D > 0 ? D : s.d;
     bool ok = true;
-    for (int i = 0; i < s.d; ++i) ok = ok && prior_insupport(s.family[i], s.par[i], th[i]);
+#pragma unroll
+    for (int i = 0; i < MAX_DTHETA; ++i)
+        if (i < d) ok = ok && prior_insupport(s.family[i], s.par[i], th[i]);
     return ok;
 }
+template <int D = 0>
 SMC_HD double pmmh_logprior(const PmmhSpec& s, const double* th) {
+    const int d = D > 0 ? D : s.d;
     double lp = 0.0;
-    for (int i = 0; i < s.d; ++i) lp = lp + prior_logpdf(s.family[i], s.par[i], th[i]);
+#pragma unroll
+    for (int i = 0; i < MAX_DTHETA; ++i)
+        if (i < d) lp = lp + prior_logpdf(s.family[i], s.par[i], th[i]);
     return lp;
 }
 // theta' = rand(MvNormal(theta, scale * Sigma)), Sigma = L L'  (smc_samplers.jl:99-100,114):
 // theta'_i = theta_i + sq * sum_{k<=i} L[i][k] z_k, sq = sqrt(scale), the sum taken left to right
+template <int D = 0>
 SMC_HD void pmmh_propose(const PmmhSpec& s, uint64_t seed, uint32_t stream, uint32_t c, const double* th, const double* L /*[d][d]*/,
                          double sq, double* prop) {
+    const int d = D > 0 ? D : s.d;
     double z[MAX_DTHETA + 1];
-    for (int k = 0; k < s.d; k += 2) box_muller(draw(seed, (uint32_t)(k >> 1), stream, c, SLOT_PMMH_Z), z[k], z[k + 1]);
-    for (int i = 0; i < s.d; ++i) {
-        double a = 0.0;
-        for (int k = 0; k <= i; ++k) a = a + L[i * s.d + k] * z[k];
-        prop[i] = th[i] + sq * a;
-    }
+#pragma unroll
+    for (int k = 0; k < MAX_DTHETA; k += 2)
+        if (k < d) box_muller(draw(seed, (uint32_t)(k >> 1), stream, c, SLOT_PMMH_Z), z[k], z[k + 1]);
+#pragma unroll
+    for (int i = 0; i < MAX_DTHETA; ++i)
+        if (i < d) {
+            double a = 0.0;
+#pragma unroll
+            for (int k = 0; k <= i; ++k) a = a + L[i * d + k] * z[k];
+            prop[i] = th[i] + sq * a;
+        }
 }
 // log(rand()) of the accept test (smc_samplers.jl:129): u in (0, 1]
 SMC_HD double pmmh_log_uniform(uint64_t seed, uint32_t stream, uint32_t c) {
@@ -715,6 +733,20 @@ SMC_HD double pmmh_log_uniform(uint64_t seed, uint32_t stream, uint32_t c) {
 // smc.model(theta): parameter row of the model family
 SMC_HD void pmmh_raw_row(const PmmhSpec& s, const double* th, double* raw /*[NPARAM]*/) {
     for (int k = 0; k < NPARAM; ++k) raw[k] = k < s.nraw ? (s.raw_from[k] >= 0 ? th[s.raw_from[k]] : s.raw_const[k]) : 0.0;
+}
+
+// ---- the exact scalar Kalman filter (src/kalman_filter.jl:29-53), one step ---------------------------------------
+// kalman_filter(model, x, Sigma, y) for the univariate LinearModel row (A, B, Q, R): the prediction (:39-40; `predict` false
+// leaves it out: the first step of a filter that starts at x_1 ~ N(x0, sigma0) like bootstrap_filter), the update (:43-49)
+// and the step's log-likelihood (:51).  (x, S) are advanced in place.  The one definition behind smc_kalman_log_likelihood
+// and the IBIS sampler (src/ibis.jl:136-140,172-177): logZ of a series is the sum of these values in step order.
+SMC_HD double kalman_step(double A, double B, double Q, double R, bool predict, double y, double& x, double& S) {
+    if (predict) { x = A * x; S = (A * A) * S + Q; }
+    const double s = (B * B) * S + R, dy = y - B * x;
+    const double K = S * B, inv = 1.0 / s;
+    x = x + (K * inv) * dy;
+    S = S - (K * K) * inv;
+    return -0.5 * (0x1.d67f1c864beb5p+0 + sp_log(s) + (dy / s) * dy);
 }
 
 // ---- segment combine (integers only) ----------------------------------------------------------

@@ -1,0 +1,220 @@
+"""Host mirror of src/ibis.jl: the IBIS sampler - Chopin's SMC² with the exact scalar Kalman filter as the inner "filter" - for
+the univariate LinearModel (UnivariateLinearGaussian, unobserved_components).
+
+    IBIS(M, model, prior, chain, ess_threshold, min_ar=-1.0)        ibis.jl:26-58
+    smc2 / smc2_step / smc2_run, resample_, rejuvenate_, expected_parameters, density_tempered   (smc_samplers.py dispatches here)
+
+A parameter particle owns O(1) state - theta, its model row, (x, Sigma), logZ, logw - and all of it lives on the device for the
+life of the sampler (smc_ibis_*, csrc/smc_ibis_kernels.h): an online step is one Kalman update per particle, a window of steps
+one launch that also computes the outer reweight's segment records, and rejuvenate! one launch for the whole chain of moves,
+re-filters included.  So the cloud can be very large (M = 2^20 is 16 MB of state).  The host keeps what the reference keeps
+outside the loop over m: the ESS decision, the index draw of resample! and the random-walk factor (one read of theta per
+rejuvenation), all by the library's outer-level routines, as for SMC.
+
+`model` is the reference's closure and is kept for the caller; the device evaluates `theta_map` (ThetaMap to LG1D rows) and a
+prior of the enumerated families instead - a GPU cannot call a closure, so both are required.
+
+predict_first: the reference's smc²(ibis, y) runs kalman_filter on y[1], which predicts before the first update
+(kalman_filter.jl:39-40).  As in log_likelihood_kalman the default (False) starts from x_1 ~ N(x0, sigma0), the limit of the
+particle filters; True is the literal loop.  The flag holds online and in every re-filter alike, so logZ[m] always equals
+log_likelihood_kalman(y[:t], model(theta[m])) with the same flag.
+"""
+import sys
+
+import numpy as np
+
+from . import _lib
+
+
+class IBIS:
+    """IBIS(M, model, prior, chain, ess_threshold, min_ar=-1.0)   ibis.jl:3-58.  M parameter particles; theta is drawn exactly
+    as SMC draws it (the same cloud for the same seed).  Arrays (theta, x, Sigma, logZ, logw, omega) are read from the device
+    on access; no device call is made before the first sampler call."""
+
+    def __init__(self, M, model, prior, chain, ess_threshold, min_ar=-1.0, seed=1, theta_map=None, device=0, predict_first=False):
+        self.M, self.model, self.prior, self.chain = int(M), model, prior, int(chain)
+        if theta_map is None or getattr(theta_map, "model_id", None) != _lib.MODEL_LG1D:
+            raise TypeError("IBIS needs theta_map=ThetaMap(LG1D rows): the Kalman filter inside runs on the GPU, which cannot call "
+                            "the `model` closure, and it is exact for the univariate LinearModel only")
+        spec = prior.spec() if hasattr(prior, "spec") else None
+        if spec is None:
+            raise TypeError("IBIS needs a prior of the enumerated families (Uniform, Normal, TruncatedNormal, LogNormal or their "
+                            "product_distribution): the GPU evaluates insupport / logpdf from prior.spec(), not from a closure")
+        self.theta_map = theta_map
+        self.prior_spec = (np.atleast_1d(np.asarray(spec[0], dtype=np.int32)), np.atleast_2d(np.asarray(spec[1], dtype=np.float64)))
+        self.rng = np.random.default_rng(seed)
+        self.seed = int(seed)
+        if hasattr(prior, "rand_many"):
+            self._theta0 = np.ascontiguousarray(prior.rand_many(self.rng, self.M), dtype=np.float64)
+        else:
+            self._theta0 = np.array([np.atleast_1d(prior.rand(self.rng)) for _ in range(self.M)], dtype=np.float64)
+        if self._theta0.shape[1] != len(self.prior_spec[0]) or self._theta0.shape[1] > _lib.MAX_DTHETA:
+            raise TypeError("the prior's spec() must describe every component of theta (at most %d)" % _lib.MAX_DTHETA)
+        if self.chain > 64:
+            raise ValueError("chain <= 64")
+        self.device, self.predict_first = int(device), bool(predict_first)
+        self.ess = float(self.M)
+        self.ess_min = self.M * float(ess_threshold)
+        self.acc_threshold, self.acc_ratio = float(min_ar), 0.0
+        self.accepted = np.zeros(self.M, dtype=bool)      # acc_array of the last rejuvenate! (ibis.jl:87)
+        self.n_rejuvenations = 0
+        self._calls = 0
+        self._h = None
+        self.t = 0
+
+    # -- the device half ------------------------------------------------------------------------------
+    def _handle(self):
+        if self._h is None:
+            fam, par = self.prior_spec
+            self._h = _lib.IbisHandle(self.M, self._theta0.shape[1], fam, par, self.theta_map.raw_from, self.theta_map.raw_const,
+                                      seed=self.seed, device=self.device, predict_first=self.predict_first)
+            self._h.set_theta(self._theta0)
+        return self._h
+
+    def close(self):
+        if self._h is not None:
+            self._h.close()
+            self._h = None
+
+    def _next_seed(self):
+        self._calls += 1
+        return (self.seed << 20) + self._calls
+
+    def _get(self, name):
+        if self._h is None:                # nothing has run: the initial cloud (ibis.jl:35-43)
+            if name == "theta":
+                return self._theta0.copy()
+            rows = self.theta_map.rows(self._theta0)
+            return {"x": rows[:, 4].copy(), "S": rows[:, 5].copy()}.get(name, np.zeros(self.M))
+        return self._h.get(**{name: True})[name]
+
+    theta = property(lambda self: self._get("theta"))
+    x = property(lambda self: self._get("x"))
+    Sigma = property(lambda self: self._get("S"))
+    logZ = property(lambda self: self._get("logZ"))
+    logw = property(lambda self: self._get("logw"))
+
+    @property
+    def omega(self):
+        """the normalised outer weights (ibis.ω after reweight)"""
+        return _lib.host_reweight(self.logw)[1]
+
+    def __repr__(self):
+        w = self.omega
+        return "ess     = %.3f\nmean(theta) = %s" % (self.ess, np.array2string((self.theta * w[:, None]).sum(axis=0)))
+
+
+def _window(ibis, y, ess_min):
+    """k = len(y) steps of smc²! in one launch; the host walks the k x nseg records the device computed and keeps the steps up to
+    the first whose ESS is below ess_min -> (ess [j], j)"""
+    h = ibis._handle()
+    rec, _ = h.window(y)
+    ess, j = _lib.host_outer_walk(rec, ibis.M, ess_min)
+    h.commit(j)
+    return ess, j
+
+
+def smc2(ibis, y):
+    """smc²(ibis, y)   ibis.jl:134-147"""
+    y = np.asarray(y, dtype=np.float64)
+    h = ibis._handle()
+    if ibis.t != 0:
+        h.set_theta(ibis.theta)           # again from (x0, sigma0), logZ = logw = 0
+    ess, _ = _window(ibis, y[:1], 0.0)
+    ibis.ess = float(ess[0])
+    ibis.t = 1
+    return ibis
+
+
+def resample_(ibis, logw=None):
+    """resample!(ibis)   ibis.jl:73-84 - value copies (the reference's aliasing of equal ancestors is not inherited)"""
+    lw = ibis.logw if logw is None else logw
+    a = np.asarray(_lib.host_outer_resample(lw, ibis.M, ibis._next_seed()), dtype=np.int32)
+    ibis._handle().permute(a)
+    return a
+
+
+def rejuvenate_(ibis, y, xi=1.0, verbose=False, out=sys.stdout):
+    """rejuvenate!(ibis, y, xi, verbose)   ibis.jl:86-125 in one launch"""
+    from .smc_samplers import random_walk_factor
+    y = np.asarray(y, dtype=np.float64)
+    if verbose:
+        out.write("\t[rejuvenating]")
+    L, s = random_walk_factor(ibis.theta, 0.5 * np.arange(ibis.chain, 0, -1))       # ibis.kernel(ibis.θ), 0.5*reverse(1:chain)
+    n, ibis.accepted = ibis._handle().rejuvenate(y, float(xi), L, s, ibis._next_seed())
+    ibis.acc_ratio = float(n) / ibis.M
+    ibis.n_rejuvenations += 1
+    if verbose:
+        out.write("\tacc_rate: %1.5f" % ibis.acc_ratio)
+    return ibis
+
+
+def smc2_step(ibis, y, t, verbose=True, out=sys.stdout):
+    """smc²!(ibis, y, t)   ibis.jl:154-189 (1-based t, t >= 2)"""
+    y = np.asarray(y, dtype=np.float64)
+    if verbose:
+        out.write("t = %4d\tess = %4.3f" % (t - 1, ibis.ess))
+    if ibis.ess < ibis.ess_min:
+        resample_(ibis)
+        rejuvenate_(ibis, y[: t - 1], 1.0, verbose, out)
+    ess, _ = _window(ibis, y[t - 1: t], 0.0)
+    ibis.ess = float(ess[0])
+    ibis.t = t
+    if verbose:
+        out.write("\n")
+    return ibis
+
+
+def smc2_run(ibis, y, t_from, t_to, window=16, verbose=True, out=sys.stdout):
+    """for t in t_from:t_to  smc²!(ibis, y, t)  end, the same results bit for bit, with up to `window` steps per launch: the
+    device computes the reweight records of every step, the host finds the first step whose ESS falls below the threshold,
+    the steps up to it are kept and the rest redone after the resample-move."""
+    y = np.asarray(y, dtype=np.float64)
+    t = int(t_from)
+    while t <= t_to:
+        if verbose:
+            out.write("t = %4d\tess = %4.3f" % (t - 1, ibis.ess))
+        if ibis.ess < ibis.ess_min:
+            resample_(ibis)
+            rejuvenate_(ibis, y[: t - 1], 1.0, verbose, out)
+        k = max(1, min(int(window), 64, t_to - t + 1))
+        ess, j = _window(ibis, y[t - 1: t - 1 + k], ibis.ess_min)
+        ibis.ess = float(ess[-1])
+        ibis.t = t + j - 1
+        if verbose:
+            out.write("\n" + "".join("t = %4d\tess = %4.3f\n" % (t + i, ess[i]) for i in range(j - 1)))
+        t += j
+    return ibis
+
+
+def expected_parameters(ibis):
+    """sum_m theta[m] * omega[m]   ibis.jl:60-64"""
+    w = ibis.omega
+    return (ibis.theta * w[:, None]).sum(axis=0)
+
+
+def density_tempered(ibis, y, verbose=True, out=sys.stdout):
+    """density_tempered(ibis, y): the loop of smc_samplers.jl:222-281 with logZ from one whole-series Kalman pass per particle
+    (ibis.jl exports the name and has rejuvenate!(ibis, y, ξ, verbose) for it)."""
+    y = np.asarray(y, dtype=np.float64)
+    h = ibis._handle()
+    h.filter(y)
+    ibis.t = len(y)
+    logZ = ibis.logZ
+    _, _, ibis.ess = _lib.host_reweight(logZ, want_w=False)                  # :232
+    xi = 0.0
+    stages = []
+    while xi < 1.0:
+        xi, ibis.ess, resample_flag, logw = _lib.host_outer_temper(logZ, xi, ibis.ess_min)     # :240-266
+        if verbose:
+            out.write("ξ = %1.5f\tess = %4.3f" % (xi, ibis.ess))
+        if resample_flag:
+            resample_(ibis, logw)
+            rejuvenate_(ibis, y, xi, verbose, out)
+            logZ = ibis.logZ
+        else:
+            h.set_logw(logw)
+        stages.append((xi, ibis.ess, ibis.acc_ratio if resample_flag else None))
+        if verbose:
+            out.write("\n")
+    return stages

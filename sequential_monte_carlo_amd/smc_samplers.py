@@ -33,6 +33,8 @@ import sys
 import numpy as np
 
 from . import _lib
+from . import ibis as _ibis
+from .ibis import IBIS
 from .models import params_matrix
 
 
@@ -274,6 +276,8 @@ class SMC:
 
 def expected_parameters(smc):
     """sum_m theta[m] * omega[m]   (smc_samplers.jl:61-65; omega normalised)"""
+    if isinstance(smc, IBIS):
+        return _ibis.expected_parameters(smc)
     w = smc.omega
     return (smc.theta * w[:, None]).sum(axis=0)
 
@@ -347,6 +351,8 @@ def estimated_trend(smc):
 
 def resample_(smc):
     """resample!(smc)   smc_samplers.jl:74-84 -- value-copy semantics."""
+    if isinstance(smc, IBIS):
+        return _ibis.resample_(smc)
     smc._sync_outer()
     # iid multinomial (sample(1:M, Weights(w), M)) through the integer CDF of the outer weights, pick numbers from Philox keyed
     # by the evaluation counter (the same on every rank).  The order of the resampled population carries no information (the
@@ -402,6 +408,8 @@ def rejuvenate_(smc, y, xi=1.0, verbose=False, out=sys.stdout):
     """rejuvenate!(smc, y, xi)   smc_samplers.jl:103-146 -- PMMH moves, `chain` per parameter particle.
     On the device in one call per rank when the sampler has a ThetaMap and an enumerated prior; otherwise the
     loop below with all M proposals of one chain position filtered in one batched call."""
+    if isinstance(smc, IBIS):
+        return _ibis.rejuvenate_(smc, y, xi, verbose, out)
     y = np.asarray(y, dtype=np.float64)
     if verbose:
         out.write("\t[rejuvenating]")
@@ -473,6 +481,8 @@ def _rejuvenate_host(smc, y, xi):
 
 def density_tempered(smc, y, verbose=True, out=sys.stdout):
     """density_tempered(smc, y)   smc_samplers.jl:222-281 (Duan & Fulop)."""
+    if isinstance(smc, IBIS):
+        return _ibis.density_tempered(smc, y, verbose, out)
     y = np.asarray(y, dtype=np.float64)
     smc.logZ, _ = smc._filter_all(smc.theta, y)
     smc._set_logw(smc.logZ)                               # :232
@@ -495,6 +505,8 @@ def density_tempered(smc, y, verbose=True, out=sys.stdout):
 
 def smc2(smc, y):
     """smc²(smc, y): initialisation at t = 1   smc_samplers.jl:288-301"""
+    if isinstance(smc, IBIS):
+        return _ibis.smc2(smc, y)
     y = np.asarray(y, dtype=np.float64)
     models = smc._models(smc.theta[smc.lo:smc.hi])
     logmu, smc._main = smc.backend.init(models, smc.N, float(y[0]), smc._next_seed(), smc._streams(), key="main")
@@ -508,6 +520,8 @@ def smc2(smc, y):
 def smc2_step(smc, y, t, verbose=True, out=sys.stdout):
     """smc²!(smc, y, t): online step for observation y[t] (1-based t as in the reference, t >= 2)
     smc_samplers.jl:308-340"""
+    if isinstance(smc, IBIS):
+        return _ibis.smc2_step(smc, y, t, verbose, out)
     y = np.asarray(y, dtype=np.float64)
     if verbose:
         out.write("t = %4d\tess = %4.3f" % (t - 1, smc.ess))
@@ -568,6 +582,10 @@ def smc2_run(smc, y, t_from, t_to, window=16, verbose=True, out=sys.stdout, summ
     from per-step summaries recorded on the device inside the window launches; returned as smc.summary_trace =
     [(t, quantiles [len(p)], variance)], bit-identical to calling filtered_summaries after every smc2_step.
     literal=True: the summaries are filtered_summaries(..., literal=True) (unweighted per-filter quantiles, corrected variance)."""
+    if isinstance(smc, IBIS):
+        if summaries is not None:
+            raise NotImplementedError("IBIS has no particle cloud to summarise: x and Sigma are the exact filtered moments")
+        return _ibis.smc2_run(smc, y, t_from, t_to, window, verbose, out)
     y = np.asarray(y, dtype=np.float64)
     t = int(t_from)
     smc._summ = None if summaries is None else {"p": [float(v) for v in summaries], "component": int(component), "literal": bool(literal)}
