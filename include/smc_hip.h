@@ -365,6 +365,29 @@ int smc_ibis_rejuvenate(void* h, const double* y, int64_t T, double xi, const do
                         const double* scales /*[chain]*/, int chain, uint64_t move_seed, int64_t* accepted /*or NULL*/,
                         uint8_t* moved /*[n_theta] or NULL*/);
 int smc_ibis_get(void* h, double* theta, double* x, double* S, double* logZ, double* logw);
+/* Summaries of an IBIS cloud, on the device (src/plotting_utils.jl:94-137: observation_dist, estimated_trend, quantile).  With
+ * omega the normalised weights of logw and, per particle, ym = B x, vm = B^2 Sigma + R (ahead = 0) or the same after one
+ * Kalman prediction x <- A x, Sigma <- A^2 Sigma + Q (ahead = 1, the one-step forecast the comment at :126-127 asks for):
+ *   out [8] = (y, Sigma, between, xbar, Sbar, between_x, K, D)
+ *   y = sum omega ym, Sigma = sum omega vm                     observation_dist literally at ahead = 0 (:107-108)
+ *   between = sum omega (ym - y)^2                             what the reference's Sigma leaves out: Sigma + between is the
+ *                                                              variance of the mixture sum omega N(ym, vm)
+ *   xbar = sum omega x, Sbar = sum omega Sigma_m, between_x    the filtered state, whatever `ahead`
+ *   K, D                                                       logsumexp(logw) = K ln 2 + log D
+ * The order of every operation is fixed by csrc/smc_spec.h ("summaries of an IBIS cloud": chunks of 64 particles, a tree
+ * within the chunk, chunks left to right; one pass with a shift per chunk), so the result is a function of the arrays alone: no
+ * atomics, the same bits from the stand-alone call, from a window's recording and from the host twin.  A particle whose logw
+ * is -inf or NaN contributes nothing, whatever its x.  NaN (K = -inf, D = 0) when no particle is alive.
+ *   smc_ibis_summary        the committed cloud, two small launches, 64 bytes read back
+ *   smc_ibis_set_summaries  on != 0: every later smc_ibis_window also records the row of summaries after each of its k steps
+ *                           (a template flag of the window kernel; off: the kernel of before)
+ *   smc_ibis_get_summaries  the first j <= k rows of the last recorded window, out [j][8]: bit for bit smc_ibis_summary after
+ *                           the same steps taken one at a time - also for the j steps kept of a window that smc_ibis_commit cuts
+ *   smc_host_ibis_summary   the same specification on the host (no GPU): rows [M][6] = (A,B,Q,R,x0,sigma0), x, S, logw [M] */
+int smc_ibis_summary(void* h, int ahead, double* out /*[8]*/);
+int smc_ibis_set_summaries(void* h, int on, int ahead);
+int smc_ibis_get_summaries(void* h, int j, double* out /*[j][8]*/);
+int smc_host_ibis_summary(const double* rows, const double* x, const double* S, const double* logw, int64_t M, int ahead, double* out /*[8]*/);
 /* filtered mean and variance of every state coordinate under the current weights, on the device
  * (README.md:41,51 summaries; src/plotting_utils.jl:116-124 estimated_trend). mean, var: [d][n_theta].
  * Definition: StatsBase's uncorrected weighted moments with the dense weights w of smc_get_state, mean = sum w x and

@@ -705,6 +705,7 @@ mutable struct HipIBIS <: Sampler
     seed::UInt64
     calls::UInt64
     t::Int64
+    summary_trace::Vector{NTuple{6,Float64}}      # (t, y, Σ, between, xbar, Sbar) per period kept by smc²_run!(...; summaries=true)
 end
 next_seed!(s::HipIBIS) = (s.calls += 1; (s.seed << 20) + s.calls)
 
@@ -725,7 +726,7 @@ function HipIBIS(M::Int64, model::SSM, prior::Sampleable, chain::Int64, ess_thre
         (Ptr{Cvoid}, Cint, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}), h[], dθ, fam, par, rf, rc))
     θm = eltype(θ) <: Number ? reshape(Float64.(θ), 1, :) : reduce(hcat, θ)        # [dθ x M] column-major == [M][dθ] row-major
     GC.@preserve θm smc_check(ccall((:smc_ibis_set_theta, LIBSMC), Cint, (Ptr{Cvoid}, Ptr{Float64}), h[], θm))
-    ib = HipIBIS(h[], M, dθ, chain, 1.0 * M, M * ess_threshold, min_ar, 0.0, model, prior, seed, UInt64(0), 0)
+    ib = HipIBIS(h[], M, dθ, chain, 1.0 * M, M * ess_threshold, min_ar, 0.0, model, prior, seed, UInt64(0), 0, NTuple{6,Float64}[])
     finalizer(x -> ccall((:smc_ibis_destroy, LIBSMC), Cint, (Ptr{Cvoid},), x.h), ib)
     return ib
 end
@@ -753,13 +754,40 @@ function expected_parameters(ib::HipIBIS)                                       
     return g.θ * reweight(g.logw)[2]
 end
 
+# observation_dist(ibis), estimated_trend(ibis), quantile(ibis, p)   plotting_utils.jl:94-137, reduced on the device:
+# smc_ibis_summary -> (y, Σ, between, xbar, Sbar, between_x, K, D) in the fixed order of csrc/smc_spec.h.  ahead=1: after one
+# Kalman prediction per particle (the one-step forecast, :126-127); between: Σ ω (ym - y)², what Σ leaves out of the mixture's variance
+function ibis_summary(ib::HipIBIS, ahead::Int=0)
+    out = Vector{Float64}(undef, 8)
+    GC.@preserve out smc_check(ccall((:smc_ibis_summary, LIBSMC), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), ib.h, ahead, out))
+    return out
+end
+function observation_dist(ib::HipIBIS; ahead::Int=0, between::Bool=false)
+    r = ibis_summary(ib, ahead)
+    return between ? (r[1], r[2], r[3]) : (r[1], r[2])
+end
+estimated_trend(ib::HipIBIS) = observation_dist(ib)[1]                           # :114
+function quantile(ib::HipIBIS, p::Union{PT,Vector{PT}}; ahead::Int=0, total::Bool=false) where PT <: Number
+    y, Σ, b = observation_dist(ib; ahead=ahead, between=true)                     # :134
+    return quantile(Normal(y, sqrt(total ? Σ + b : Σ)), sort(p))                  # :136 on a sorted COPY (the reference's sort!(p) is a slip)
+end
+
 # k steps of smc²! in one launch; the device computes the reweight records, the host walks them (ibis.jl:166-187)
-function ibis_window!(ib::HipIBIS, yk::Vector{Float64}, ess_min::Float64)
+# summaries: the same launch records the row of ibis_summary after every step; the rows of the j kept steps join summary_trace
+function ibis_window!(ib::HipIBIS, yk::Vector{Float64}, ess_min::Float64; summaries::Bool=false, ahead::Int=0, t::Int64=0)
     k = length(yk); nseg = cld(ib.M, 8)
+    smc_check(ccall((:smc_ibis_set_summaries, LIBSMC), Cint, (Ptr{Cvoid}, Cint, Cint), ib.h, summaries ? 1 : 0, ahead))
     rec = Array{UInt64,3}(undef, 4, nseg, k)                                       # column-major == [k][nseg][4]
     GC.@preserve yk rec smc_check(ccall((:smc_ibis_window, LIBSMC), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{UInt64}),
         ib.h, yk, k, C_NULL, rec))
     e, j = outer_walk(rec, ib.M, ess_min)
+    if summaries
+        rows = Matrix{Float64}(undef, 8, j)                                       # column-major == [j][8]
+        GC.@preserve rows smc_check(ccall((:smc_ibis_get_summaries, LIBSMC), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), ib.h, j, rows))
+        for i in 1:j
+            push!(ib.summary_trace, (Float64(t + i - 1), rows[1, i], rows[2, i], rows[3, i], rows[4, i], rows[5, i]))
+        end
+    end
     smc_check(ccall((:smc_ibis_commit, LIBSMC), Cint, (Ptr{Cvoid}, Cint), ib.h, j))
     return e, j
 end
@@ -802,15 +830,17 @@ function smc²!(ib::HipIBIS, y::Vector{Float64}, t::Int64, verbose::Bool=true)  
     if verbose print("\n") end
 end
 
-function smc²_run!(ib::HipIBIS, y::Vector{Float64}, t1::Int64, t2::Int64; window::Int=16, verbose::Bool=true)
+function smc²_run!(ib::HipIBIS, y::Vector{Float64}, t1::Int64, t2::Int64; window::Int=16, verbose::Bool=true,
+                   summaries::Bool=false, ahead::Int=0)
     t = t1
+    summaries && filter!(e -> e[1] < t1, ib.summary_trace)
     while t <= t2
         if ib.ess < ib.ess_min
             resample!(ib)
             rejuvenate!(ib, y[1:(t-1)], verbose)
         end
         k = min(window, 64, t2 - t + 1)
-        e, j = ibis_window!(ib, y[t:(t+k-1)], ib.ess_min)
+        e, j = ibis_window!(ib, y[t:(t+k-1)], ib.ess_min; summaries=summaries, ahead=ahead, t=t)
         ib.ess = e[end]; ib.t = t + j - 1
         t += j
     end

@@ -31,6 +31,7 @@ EXPORTS = [
     "smc_set_proposal", "smc_host_optimal_proposal", "smc_host_guided_step", "smc_device_guided_step",
     "smc_ibis_create", "smc_ibis_destroy", "smc_ibis_configure", "smc_ibis_set_theta", "smc_ibis_window", "smc_ibis_commit",
     "smc_ibis_filter", "smc_ibis_permute", "smc_ibis_set_logw", "smc_ibis_rejuvenate", "smc_ibis_get",
+    "smc_ibis_summary", "smc_ibis_set_summaries", "smc_ibis_get_summaries", "smc_host_ibis_summary",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -173,6 +174,10 @@ def lib():
     L.smc_ibis_rejuvenate.argtypes = [h, _dp, C.c_int64, C.c_double, _dp, _dp, C.c_int, C.c_uint64, C.POINTER(C.c_int64),
                                       C.POINTER(C.c_uint8)]
     L.smc_ibis_get.argtypes = [h, _dp, _dp, _dp, _dp, _dp]
+    L.smc_ibis_summary.argtypes = [h, C.c_int, _dp]
+    L.smc_ibis_set_summaries.argtypes = [h, C.c_int, C.c_int]
+    L.smc_ibis_get_summaries.argtypes = [h, C.c_int, _dp]
+    L.smc_host_ibis_summary.argtypes = [_dp, _dp, _dp, _dp, C.c_int64, C.c_int, _dp]
     L.smc_last_error.restype = C.c_char_p
     L.smc_version.restype = C.c_char_p
     _lib = L
@@ -676,6 +681,17 @@ class Handle:
         check(lib().smc_synchronize(self._h))
 
 
+def host_ibis_summary(rows, x, S, logw, ahead=0):
+    """(y, Sigma, between, xbar, Sbar, between_x, K, D) of a cloud of LG1D rows [M][6] with Kalman state (x, S) and outer
+    log-weights logw (smc_host_ibis_summary: the device's specification on the host; no GPU)"""
+    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 6)
+    x, S, logw = (np.ascontiguousarray(v, dtype=np.float64) for v in (x, S, logw))
+    assert x.size == S.size == logw.size == rows.shape[0]
+    out = np.zeros(8)
+    check(lib().smc_host_ibis_summary(_d(rows), _d(x), _d(S), _d(logw), x.size, int(ahead), _d(out)))
+    return out
+
+
 class IbisHandle:
     """The device half of the IBIS sampler (smc_ibis_*): M parameter particles with their exact Kalman state, resident on one
     GPU.  d: parameter dimension; families / pars: the prior (distributions.py spec()); raw_from / raw_const: ThetaMap to LG1D rows."""
@@ -752,4 +768,20 @@ class IbisHandle:
             if want:
                 out[name] = np.zeros(self.M)
         check(lib().smc_ibis_get(self._h, _d(out.get("theta")), _d(out.get("x")), _d(out.get("S")), _d(out.get("logZ")), _d(out.get("logw"))))
+        return out
+
+    def summary(self, ahead=0):
+        """(y, Sigma, between, xbar, Sbar, between_x, K, D) of the committed cloud, reduced on the device (smc_ibis_summary)"""
+        out = np.zeros(8)
+        check(lib().smc_ibis_summary(self._h, int(ahead), _d(out)))
+        return out
+
+    def set_summaries(self, on, ahead=0):
+        """record the row of summaries after every step of the windows that follow (smc_ibis_set_summaries)"""
+        check(lib().smc_ibis_set_summaries(self._h, int(bool(on)), int(ahead)))
+
+    def get_summaries(self, j):
+        """rows [j][8] of the first j steps of the last recorded window"""
+        out = np.zeros((int(j), 8))
+        check(lib().smc_ibis_get_summaries(self._h, int(j), _d(out)))
         return out

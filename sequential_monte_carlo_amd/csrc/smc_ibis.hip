@@ -43,6 +43,14 @@ struct smc_ibis_s {
     unsigned char* d_moved = nullptr;
     unsigned long long* d_count = nullptr;
     double* d_chol = nullptr;       // [MAX_DTHETA^2] | sq [IBIS_MAX_CHAIN]
+    // summaries (smc_ibis_set_summaries / smc_ibis_summary): chunk records and scratch, rows of the last window
+    bool summ_on = false;
+    int summ_ahead = 0;
+    double* d_part = nullptr; size_t part_cap = 0;   // [rows][IBIS_SUM_NCOL][nchunk]
+    double* d_srow = nullptr;                        // [IBIS_MAX_WINDOW][IBIS_SUM_NOUT]
+    double* d_one = nullptr; size_t one_cap = 0;     // [IBIS_SUM_NCOL][nchunk] | [IBIS_SUM_NOUT]: smc_ibis_summary
+    double srow[IBIS_MAX_WINDOW * IBIS_SUM_NOUT];
+    int srow_k = 0;                                  // rows of srow that are set
 };
 typedef smc_ibis_s* ibis_t;
 
@@ -71,6 +79,7 @@ void release(ibis_t h) {
     }
     (void)hipFree(h->d_y); (void)hipFree(h->d_lik); (void)hipFree(h->d_rec); (void)hipFree(h->d_a);
     (void)hipFree(h->d_moved); (void)hipFree(h->d_count); (void)hipFree(h->d_chol);
+    (void)hipFree(h->d_part); (void)hipFree(h->d_srow); (void)hipFree(h->d_one);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -99,7 +108,8 @@ int steps_in_place(ibis_t h, const double* y, int64_t steps) {
     while (done < steps) {   // (the kernel's step count is an int)
         const int k = (int)(steps - done > (1 << 20) ? (1 << 20) : steps - done);
         hipLaunchKernelGGL((k_ibis_window<false>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->cs,
-                           h->d_y + done, k, (h->t + done > 0 || h->predict_first) ? 1 : 0, (double*)nullptr, (uint64_t*)nullptr);
+                           h->d_y + done, k, (h->t + done > 0 || h->predict_first) ? 1 : 0, (double*)nullptr, (uint64_t*)nullptr,
+                           (double*)nullptr, 0);
         HIPCHK(hipGetLastError());
         done += k;
     }
@@ -113,7 +123,7 @@ extern "C" int smc_ibis_create(int64_t n_theta, uint64_t seed, int device, int p
     (void)seed;   // every random number of the device side is keyed by the move_seed of its call
     if (!out) return fail(SMC_EINVAL, "smc_ibis_create: NULL out");
     *(void**)out = nullptr;
-    if (n_theta < 2 || n_theta > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_ibis_create: 2 <= n_theta <= 2^30");
+    if (n_theta < 1 || n_theta > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_ibis_create: 1 <= n_theta <= 2^30");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(SMC_EHIP, "smc_ibis_create: no HIP device");
     if (device < 0 || device >= ndev) return fail(SMC_EINVAL, "smc_ibis_create: bad device");
@@ -137,6 +147,7 @@ extern "C" int smc_ibis_create(int64_t n_theta, uint64_t seed, int device, int p
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_moved, M);
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_count, 8);
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_chol, (MAX_DTHETA * MAX_DTHETA + IBIS_MAX_CHAIN) * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_srow, IBIS_MAX_WINDOW * IBIS_SUM_NOUT * 8);
     if (e != hipSuccess) {
         release(h);
         return fail(e == hipErrorOutOfMemory ? SMC_ENOMEM : SMC_EHIP, std::string("smc_ibis_create: ") + hipGetErrorString(e));
@@ -200,6 +211,7 @@ extern "C" int smc_ibis_set_theta(void* hp, const double* theta) {
     h->have_theta = true;
     h->t = 0;
     h->win_k = 0;
+    h->srow_k = 0;
     return SMC_OK;
 }
 
@@ -214,15 +226,136 @@ extern "C" int smc_ibis_window(void* hp, const double* y, int k, double* lik, ui
     HIPCHK(grow(&h->d_y, &h->y_cap, (size_t)k));
     HIPCHK(grow(&h->d_rec, &h->rec_cap, (size_t)k * nseg * 4));
     if (lik) HIPCHK(grow(&h->d_lik, &h->lik_cap, (size_t)k * M));
+    const size_t nchunk = grid_of(h->v.M);
+    h->srow_k = 0;
+    if (h->summ_on) HIPCHK(grow(&h->d_part, &h->part_cap, (size_t)k * IBIS_SUM_NCOL * nchunk));
     HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)k * 8, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL((k_ibis_window<true>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->cs ^ 1,
-                       h->d_y, k, (h->t > 0 || h->predict_first) ? 1 : 0, lik ? h->d_lik : (double*)nullptr, h->d_rec);
-    HIPCHK(hipGetLastError());
+    if (h->summ_on) {   // the same steps, and the chunk records of the summaries after each; then one workgroup per row combines them
+        hipLaunchKernelGGL((k_ibis_window<true, true>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs,
+                           h->cs ^ 1, h->d_y, k, (h->t > 0 || h->predict_first) ? 1 : 0, lik ? h->d_lik : (double*)nullptr, h->d_rec,
+                           h->d_part, h->summ_ahead);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_ibis_sum_combine, dim3((unsigned)k), dim3(IBIS_SUM_CTHREADS), 0, h->stream, h->d_part, (int64_t)nchunk,
+                           h->d_srow);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h->srow, h->d_srow, (size_t)k * IBIS_SUM_NOUT * 8, hipMemcpyDeviceToHost, h->stream));
+    } else {
+        hipLaunchKernelGGL((k_ibis_window<true>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->cs ^ 1,
+                           h->d_y, k, (h->t > 0 || h->predict_first) ? 1 : 0, lik ? h->d_lik : (double*)nullptr, h->d_rec,
+                           (double*)nullptr, 0);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipMemcpyAsync(rec, h->d_rec, (size_t)k * nseg * 32, hipMemcpyDeviceToHost, h->stream));
     if (lik) HIPCHK(hipMemcpyAsync(lik, h->d_lik, (size_t)k * M * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->win_y.assign(y, y + k);
     h->win_k = k;
+    if (h->summ_on) h->srow_k = k;
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_set_summaries(void* hp, int on, int ahead) {
+    ibis_t h = as_ibis(hp);
+    if (!h) return fail(SMC_EINVAL, "smc_ibis_set_summaries: not an IBIS handle");
+    if (ahead != 0 && ahead != 1) return fail(SMC_EINVAL, "smc_ibis_set_summaries: ahead is 0 or 1");
+    h->summ_on = on != 0;
+    h->summ_ahead = ahead;
+    h->srow_k = 0;
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_get_summaries(void* hp, int j, double* out) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !out) return fail(SMC_EINVAL, "smc_ibis_get_summaries: bad argument");
+    if (j < 0 || j > h->srow_k) return fail(SMC_ESTATE, "smc_ibis_get_summaries: the last window recorded fewer steps (is recording on?)");
+    memcpy(out, h->srow, (size_t)j * IBIS_SUM_NOUT * 8);
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_summary(void* hp, int ahead, double* out) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !out) return fail(SMC_EINVAL, "smc_ibis_summary: bad argument");
+    if (ahead != 0 && ahead != 1) return fail(SMC_EINVAL, "smc_ibis_summary: ahead is 0 or 1");
+    if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_summary: smc_ibis_set_theta has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nchunk = grid_of(h->v.M);
+    // (a buffer of its own: the rows of a pending window stay intact)
+    HIPCHK(grow(&h->d_one, &h->one_cap, IBIS_SUM_NCOL * nchunk + IBIS_SUM_NOUT));
+    double* d_one = h->d_one;
+    hipLaunchKernelGGL(k_ibis_sum_chunks, dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, ahead, d_one);
+    hipLaunchKernelGGL(k_ibis_sum_combine, dim3(1), dim3(IBIS_SUM_CTHREADS), 0, h->stream, d_one, (int64_t)nchunk,
+                       d_one + IBIS_SUM_NCOL * nchunk);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_one + IBIS_SUM_NCOL * nchunk, IBIS_SUM_NOUT * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return SMC_OK;
+}
+
+// The same specification on the host (no GPU): rows [M][6] = (A, B, Q, R, x0, sigma0), x, S, logw [M]
+extern "C" int smc_host_ibis_summary(const double* rows, const double* x, const double* S, const double* logw, int64_t M, int ahead,
+                                     double* out) {
+    if (!rows || !x || !S || !logw || !out || M < 1) return fail(SMC_EINVAL, "smc_host_ibis_summary: bad argument");
+    if (ahead != 0 && ahead != 1) return fail(SMC_EINVAL, "smc_host_ibis_summary: ahead is 0 or 1");
+    const int64_t nchunk = (M + IBIS_SUM_CHUNK - 1) / IBIS_SUM_CHUNK;
+    std::vector<double> rec((size_t)nchunk * IBIS_SUM_NF);
+    for (int64_t c = 0; c < nchunk; ++c) {
+        double p[IBIS_SUM_CHUNK], u[IBIS_SUM_CHUNK], ym[IBIS_SUM_CHUNK], vm[IBIS_SUM_CHUNK], xs[IBIS_SUM_CHUNK], Ss[IBIS_SUM_CHUNK];
+        double t[7][IBIS_SUM_CHUNK];
+        int k[IBIS_SUM_CHUNK], kc = IBIS_SUM_DEADK;
+        for (int l = 0; l < IBIS_SUM_CHUNK; ++l) {
+            const int64_t m = c * IBIS_SUM_CHUNK + l;
+            const bool valid = m < M;
+            const int64_t mm = valid ? m : M - 1;
+            const double* r = rows + mm * IBIS_NRAW;
+            xs[l] = x[mm];
+            Ss[l] = S[mm];
+            p[l] = ibis_sum_parts(logw[mm], valid, k[l]);
+            kc = k[l] > kc ? k[l] : kc;
+            ibis_obs_moments(r[0], r[1], r[2], r[3], xs[l], Ss[l], ahead != 0, ym[l], vm[l]);
+        }
+        int ls = -1;
+        for (int l = 0; l < IBIS_SUM_CHUNK; ++l) {
+            u[l] = ibis_sum_u(p[l], k[l], kc);
+            if (u[l] > 0.0 && (ls < 0 || u[l] > u[ls])) ls = l;
+        }
+        const double cy = ls >= 0 ? ym[ls] : 0.0, cx = ls >= 0 ? xs[ls] : 0.0;
+        for (int l = 0; l < IBIS_SUM_CHUNK; ++l) {
+            double tl[7];
+            ibis_sum_terms(u[l], ym[l], vm[l], xs[l], Ss[l], cy, cx, tl);
+            for (int i = 0; i < 7; ++i) t[i][l] = tl[i];
+        }
+        for (int i = 0; i < 7; ++i)      // lane 0 of the butterfly: the balanced tree over neighbours
+            for (int s = 1; s < IBIS_SUM_CHUNK; s <<= 1)
+                for (int l = 0; l < IBIS_SUM_CHUNK; l += 2 * s) t[i][l] = t[i][l] + t[i][l + s];
+        double* r = rec.data() + (size_t)c * IBIS_SUM_NF;
+        r[ISF_KC] = kc == IBIS_SUM_DEADK ? -inf() : (double)kc;
+        r[ISF_W] = t[0][0]; r[ISF_CY] = cy; r[ISF_DY] = t[1][0]; r[ISF_V] = t[2][0]; r[ISF_MY] = t[3][0];
+        r[ISF_CX] = cx; r[ISF_DX] = t[4][0]; r[ISF_SX] = t[5][0]; r[ISF_MX] = t[6][0];
+    }
+    double K = -inf(), D = 0.0;
+    for (int64_t c = 0; c < nchunk; ++c) K = rec[(size_t)c * IBIS_SUM_NF] > K ? rec[(size_t)c * IBIS_SUM_NF] : K;
+    for (int64_t c = 0; c < nchunk; ++c) {
+        const double* r = rec.data() + (size_t)c * IBIS_SUM_NF;
+        D = D + ibis_sum_factor(K, r[ISF_KC], r[ISF_W]) * r[ISF_W];
+    }
+    double a[4] = {0.0, 0.0, 0.0, 0.0}, b[2] = {0.0, 0.0};
+    for (int64_t c = 0; c < nchunk; ++c) {
+        const double* r = rec.data() + (size_t)c * IBIS_SUM_NF;
+        double ac[4];
+        ibis_sum_first(r, ibis_sum_factor(K, r[ISF_KC], r[ISF_W]), D, ac);
+        for (int i = 0; i < 4; ++i) a[i] = a[i] + ac[i];
+    }
+    for (int64_t c = 0; c < nchunk; ++c) {
+        const double* r = rec.data() + (size_t)c * IBIS_SUM_NF;
+        double bc[2];
+        ibis_sum_second(r, ibis_sum_factor(K, r[ISF_KC], r[ISF_W]), D, a[0], a[2], bc);
+        for (int i = 0; i < 2; ++i) b[i] = b[i] + bc[i];
+    }
+    const bool live = D > 0.0;
+    const double nan = bits2d(0x7ff8000000000000ULL);
+    out[0] = live ? a[0] : nan; out[1] = live ? a[1] : nan; out[2] = live ? b[0] : nan;
+    out[3] = live ? a[2] : nan; out[4] = live ? a[3] : nan; out[5] = live ? b[1] : nan;
+    out[6] = K; out[7] = D;
     return SMC_OK;
 }
 

@@ -99,15 +99,154 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_reset(IbisView v, int cp,
     v.logw[cs][m] = 0.0;
 }
 
+// ---- summaries of the cloud (smc_spec.h "summaries of an IBIS cloud"; plotting_utils.jl:94-137) ------------------------------
+// A workgroup is one wave and owns one chunk.  part: [IBIS_SUM_NCOL][nchunk] doubles per row of summaries (one row per step of
+// a window), column-major so that the combine's left-to-right sums read consecutive addresses: columns 0..9 the chunk record,
+// the rest scratch of k_ibis_sum_combine.
+static_assert(IBIS_THREADS == IBIS_SUM_CHUNK, "one wave per chunk of the summaries");
+constexpr int IBIS_SUM_NCOL = 16;
+constexpr int IBIS_SUM_CTHREADS = 256;
+
+__device__ __forceinline__ double wave_tree_sum(double v) {   // a[i] += a[i ^ s], s = 1, 2, .., 32: the same bits in every lane
+#pragma unroll
+    for (int s = 1; s < IBIS_SUM_CHUNK; s <<= 1) v = v + __shfl_xor(v, s, IBIS_SUM_CHUNK);
+    return v;
+}
+
+// the record of the chunk this wave holds, from the registers of its lanes; lane 0 stores it (vector stores)
+__device__ __forceinline__ void ibis_chunk_record(double A, double B, double Q, double R, double x, double S, double logw, bool valid,
+                                                  int ahead, double* part, int64_t nchunk, int64_t c) {
+    int k;
+    const double p = ibis_sum_parts(logw, valid, k);
+    int kc = k;
+#pragma unroll
+    for (int s = 1; s < IBIS_SUM_CHUNK; s <<= 1) { const int o = __shfl_xor(kc, s, IBIS_SUM_CHUNK); kc = o > kc ? o : kc; }
+    const double u = ibis_sum_u(p, k, kc);
+    double um = u;
+#pragma unroll
+    for (int s = 1; s < IBIS_SUM_CHUNK; s <<= 1) { const double o = __shfl_xor(um, s, IBIS_SUM_CHUNK); um = o > um ? o : um; }
+    const unsigned long long top = __ballot(u > 0.0 && u == um);
+    const int ls = top ? __ffsll(top) - 1 : 0;
+    double ym, vm;
+    ibis_obs_moments(A, B, Q, R, x, S, ahead != 0, ym, vm);
+    const double cy = top ? __shfl(ym, ls, IBIS_SUM_CHUNK) : 0.0, cx = top ? __shfl(x, ls, IBIS_SUM_CHUNK) : 0.0;
+    double t[7];
+    ibis_sum_terms(u, ym, vm, x, S, cy, cx, t);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) t[i] = wave_tree_sum(t[i]);
+    if (threadIdx.x == 0) {
+        part[ISF_KC * nchunk + c] = kc == IBIS_SUM_DEADK ? -inf() : (double)kc;
+        part[ISF_W * nchunk + c] = t[0];
+        part[ISF_CY * nchunk + c] = cy;
+        part[ISF_DY * nchunk + c] = t[1];
+        part[ISF_V * nchunk + c] = t[2];
+        part[ISF_MY * nchunk + c] = t[3];
+        part[ISF_CX * nchunk + c] = cx;
+        part[ISF_DX * nchunk + c] = t[4];
+        part[ISF_SX * nchunk + c] = t[5];
+        part[ISF_MX * nchunk + c] = t[6];
+    }
+}
+
+// the chunk records of the resident cloud (one row)
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_sum_chunks(IbisView v, int cp, int cs, int ahead, double* part) {
+    const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
+    const bool valid = m < v.M;
+    const int64_t mm = valid ? m : v.M - 1;
+    const double* row = v.raw[cp] + mm * IBIS_NRAW;
+    ibis_chunk_record(row[0], row[1], row[2], row[3], v.x[cs][mm], v.S[cs][mm], v.logw[cs][mm], valid, ahead, part, gridDim.x, blockIdx.x);
+}
+
+// sum of a [n] from 0.0, left to right, by the calling lane (loads of 8 addends ahead of their additions)
+__device__ __forceinline__ double left_to_right_sum(const double* a, int64_t n) {
+    double acc = 0.0;
+    int64_t c = 0;
+    for (; c + 8 <= n; c += 8) {
+        double w[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) w[i] = a[c + i];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc = acc + w[i];
+    }
+    for (; c < n; ++c) acc = acc + a[c];
+    return acc;
+}
+
+// chunk records -> the row of summaries; workgroup r combines row r.  The addends of every chunk are computed by all lanes, the
+// sums are taken by one lane each, in chunk order.
+__global__ __launch_bounds__(IBIS_SUM_CTHREADS) void k_ibis_sum_combine(double* part_all, int64_t nchunk, double* out /*[rows][IBIS_SUM_NOUT]*/) {
+    __shared__ double red[IBIS_SUM_CTHREADS];
+    __shared__ double bc[8];
+    double* part = part_all + (size_t)blockIdx.x * IBIS_SUM_NCOL * (size_t)nchunk;
+    const int tid = threadIdx.x;
+    double K = -inf();
+    for (int64_t c = tid; c < nchunk; c += IBIS_SUM_CTHREADS) { const double kc = part[ISF_KC * nchunk + c]; K = kc > K ? kc : K; }
+    red[tid] = K;
+    __syncthreads();
+    for (int s = IBIS_SUM_CTHREADS / 2; s > 0; s >>= 1) {      // a maximum: any order
+        if (tid < s) red[tid] = red[tid + s] > red[tid] ? red[tid + s] : red[tid];
+        __syncthreads();
+    }
+    K = red[0];
+    double* g = part + 10 * nchunk;
+    for (int64_t c = tid; c < nchunk; c += IBIS_SUM_CTHREADS) {
+        const double W = part[ISF_W * nchunk + c];
+        g[c] = ibis_sum_factor(K, part[ISF_KC * nchunk + c], W) * W;
+    }
+    __syncthreads();
+    if (tid == 0) bc[0] = left_to_right_sum(g, nchunk);
+    __syncthreads();
+    const double D = bc[0];
+    for (int64_t c = tid; c < nchunk; c += IBIS_SUM_CTHREADS) {
+        double r[IBIS_SUM_NF], a[4];
+#pragma unroll
+        for (int i = 0; i < IBIS_SUM_NF; ++i) r[i] = part[i * nchunk + c];
+        ibis_sum_first(r, ibis_sum_factor(K, r[ISF_KC], r[ISF_W]), D, a);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) part[(11 + i) * nchunk + c] = a[i];
+    }
+    __syncthreads();
+    if (tid < 4) bc[1 + tid] = left_to_right_sum(part + (11 + tid) * nchunk, nchunk);
+    __syncthreads();
+    const double y = bc[1], xbar = bc[3];
+    for (int64_t c = tid; c < nchunk; c += IBIS_SUM_CTHREADS) {
+        double r[IBIS_SUM_NF], b[2];
+#pragma unroll
+        for (int i = 0; i < IBIS_SUM_NF; ++i) r[i] = part[i * nchunk + c];
+        ibis_sum_second(r, ibis_sum_factor(K, r[ISF_KC], r[ISF_W]), D, y, xbar, b);
+        part[10 * nchunk + c] = b[0];
+        part[15 * nchunk + c] = b[1];
+    }
+    __syncthreads();
+    if (tid < 2) bc[5 + tid] = left_to_right_sum(part + (tid == 0 ? 10 : 15) * nchunk, nchunk);
+    __syncthreads();
+    if (tid == 0) {
+        double* o = out + (size_t)blockIdx.x * IBIS_SUM_NOUT;
+        const bool live = D > 0.0;
+        const double nan = bits2d(0x7ff8000000000000ULL);
+        o[0] = live ? bc[1] : nan;
+        o[1] = live ? bc[2] : nan;
+        o[2] = live ? bc[5] : nan;
+        o[3] = live ? bc[3] : nan;
+        o[4] = live ? bc[4] : nan;
+        o[5] = live ? bc[6] : nan;
+        o[6] = K;
+        o[7] = D;
+    }
+}
+
 // k steps of smc²! (ibis.jl:166-187) from the committed state (set cs), one lane per parameter particle:
 //   (x, S) <- kalman_filter(row, x, S, y[j]);  logw += lik;  logZ += lik          (:171-181)
 // RECORD: lik [k][M] (optional) and, after every step, the record (kb, S, S2hi, S2lo) of each segment of 8 consecutive
 // particles of reweight(logw) (:187) - the integers smc_host_outer_window computes from the same logw, so the host only
 // walks k x nseg records.  The end state goes to the set `dst` (== cs: the steps are committed in place).
 // predict0: whether the first of the k steps predicts (false only at t = 1 of a sampler with predict_first = 0).
-template <bool RECORD>
+// SUMM: also the chunk record of the summaries after every step (row j of part), from the registers the step left: the
+// operands the stand-alone k_ibis_sum_chunks reads back after the same steps, so the same bits.
+template <bool RECORD, bool SUMM = false>
 __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_window(IbisView v, int cp, int cs, int dst, const double* y, int k, int predict0,
-                                                             double* lik /*[k][M] or null*/, uint64_t* rec /*[k][nseg][4]*/) {
+                                                             double* lik /*[k][M] or null*/, uint64_t* rec /*[k][nseg][4]*/,
+                                                             double* part /*[k][IBIS_SUM_NCOL][nchunk]*/, int ahead) {
     const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
     const bool valid = m < v.M;
     const int64_t mm = valid ? m : v.M - 1;            // lanes beyond the cloud compute on the last particle and store nothing
@@ -138,6 +277,9 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_window(IbisView v, int cp
                 r[3] = live ? s2.lo : 0;
             }
         }
+        if (SUMM)
+            ibis_chunk_record(A, B, Q, R, x, S, logw, valid, ahead, part + (size_t)j * IBIS_SUM_NCOL * (size_t)gridDim.x, gridDim.x,
+                              blockIdx.x);
     }
     if (valid) {
         v.x[dst][m] = x;

@@ -749,6 +749,83 @@ SMC_HD double kalman_step(double A, double B, double Q, double R, bool predict, 
     return -0.5 * (0x1.d67f1c864beb5p+0 + sp_log(s) + (dy / s) * dy);
 }
 
+// ---- summaries of an IBIS cloud (src/plotting_utils.jl:94-137: observation_dist, estimated_trend, quantile) -----------------
+// Particle m: row (A, B, Q, R), filtered state (x, S), outer log-weight logw.  With omega_m the normalised weight of logw:
+//   ahead = 0:  ym = B x,        vm = (B B) S + R                         (:104-105)
+//   ahead = 1:  ym = B (A x),    vm = (B B) ((A A) S + Q) + R             one prediction of kalman_step first (kalman_filter.jl:39-40)
+//   y = sum omega ym, Sigma = sum omega vm (:107-108), by = sum omega (ym - y)^2   (Sigma + by: the variance of the mixture)
+//   xbar = sum omega x, Sbar = sum omega S, bx = sum omega (x - xbar)^2            (the filtered state, whatever `ahead`)
+// Order of operations - a function of the arrays alone.  The cloud is cut into CHUNKS of IBIS_SUM_CHUNK = 64 consecutive
+// particles (the last one padded with dead lanes).  Per chunk, with exp(logw) = p 2^k (sp_exp_parts; a lane takes part iff lw_alive):
+//   kc = max k;  u = p 2^(k - kc), 0 when k - kc <= -64 or the lane is dead;  a lane with u = 0 contributes +0.0 to every sum,
+//                whatever its x (NaN included)
+//   l* = the lowest lane with the largest u;  cy = ym[l*], cx = x[l*]        (the shifts of the chunk; 0 for a dead chunk)
+//   W = sum u, Dy = sum u (ym - cy), V = sum u vm, My = sum u ((ym - cy)(ym - cy)), Dx, Sx, Mx likewise in (x, S):
+//   each the TREE sum over the 64 lanes: a[i] += a[i ^ 1], then ^ 2, 4, 8, 16, 32 (a wave's butterfly; every lane ends equal)
+// The chunk record is (kc, W, cy, Dy, V, My, cx, Dx, Sx, Mx), IBIS_SUM_NF doubles.  Combine, chunks LEFT TO RIGHT from 0.0:
+//   K = max kc;  f_c = 2^-(K - kc), 0 when K - kc >= 64 or W_c = 0;  D = sum_c f_c W_c;  Om_c = (f_c W_c) / D
+//   y     = sum_c (Om_c cy_c + (f_c Dy_c) / D)         Sigma = sum_c (f_c V_c) / D          (xbar, Sbar likewise)
+//   by    = sum_c ((f_c My_c) / D + (2 e_c) ((f_c Dy_c) / D) + Om_c (e_c e_c)),  e_c = cy_c - y      (bx likewise)
+// - a single pass over the cloud with one shift per chunk: every term of by is a sum of squares about a member of its own chunk
+// plus the exact correction to y, so nothing cancels, and a cloud whose weight sits on one particle gives by = bx = 0 exactly.
+// A chunk with f_c W_c = 0 adds nothing.  A cloud without a live particle (D = 0) gives NaN everywhere.
+// out [IBIS_SUM_NOUT] = (y, Sigma, by, xbar, Sbar, bx, K, D):  logsumexp(logw) = K ln 2 + log D.
+constexpr int IBIS_SUM_CHUNK = 64;
+constexpr int IBIS_SUM_NF = 10;
+constexpr int IBIS_SUM_NOUT = 8;
+enum { ISF_KC = 0, ISF_W, ISF_CY, ISF_DY, ISF_V, ISF_MY, ISF_CX, ISF_DX, ISF_SX, ISF_MX };
+
+constexpr int IBIS_SUM_DEADK = -(1 << 30);
+// (ym, vm) of a particle
+SMC_HD void ibis_obs_moments(double A, double B, double Q, double R, double x, double S, bool ahead, double& ym, double& vm) {
+    if (ahead) { x = A * x; S = (A * A) * S + Q; }
+    ym = B * x;
+    vm = (B * B) * S + R;
+}
+// exp(logw) = p 2^k of a lane: k = IBIS_SUM_DEADK for a lane that takes no part
+SMC_HD double ibis_sum_parts(double logw, bool valid, int& k) {
+    const bool alive = valid && lw_alive(logw);
+    double kd = 0.0;
+    const double p = sp_exp_parts(alive ? logw : 0.0, kd);
+    k = alive ? (int)kd : IBIS_SUM_DEADK;
+    return alive ? p : 0.0;
+}
+SMC_HD double ibis_sum_u(double p, int k, int kc) { return (k != IBIS_SUM_DEADK && k - kc > -64) ? scale2(p, k - kc) : 0.0; }
+// the seven addends of a lane, t = (u, u dy, u vm, u dy dy, u dx, u S, u dx dx)
+SMC_HD void ibis_sum_terms(double u, double ym, double vm, double x, double S, double cy, double cx, double* t) {
+    const bool on = u > 0.0;
+    const double dy = ym - cy, dx = x - cx;
+    t[0] = u;
+    t[1] = on ? u * dy : 0.0;
+    t[2] = on ? u * vm : 0.0;
+    t[3] = on ? u * (dy * dy) : 0.0;
+    t[4] = on ? u * dx : 0.0;
+    t[5] = on ? u * S : 0.0;
+    t[6] = on ? u * (dx * dx) : 0.0;
+}
+// g_c = f_c W_c of a chunk against the cloud's K (both integral doubles or -inf)
+SMC_HD double ibis_sum_factor(double K, double kc, double W) {
+    const double dk = K - kc;
+    return (W > 0.0 && dk >= 0.0 && dk < 64.0) ? pow2i(-(int)dk) : 0.0;
+}
+// the first-moment addends of a chunk once D is known: (Om cy + f Dy / D, f V / D, Om cx + f Dx / D, f Sx / D)
+SMC_HD void ibis_sum_first(const double* r /*[IBIS_SUM_NF]*/, double f, double D, double* a /*[4]*/) {
+    const bool on = f * r[ISF_W] > 0.0;
+    const double Om = (f * r[ISF_W]) / D;
+    a[0] = on ? Om * r[ISF_CY] + (f * r[ISF_DY]) / D : 0.0;
+    a[1] = on ? (f * r[ISF_V]) / D : 0.0;
+    a[2] = on ? Om * r[ISF_CX] + (f * r[ISF_DX]) / D : 0.0;
+    a[3] = on ? (f * r[ISF_SX]) / D : 0.0;
+}
+// the second-moment addends of a chunk once y and xbar are known
+SMC_HD void ibis_sum_second(const double* r, double f, double D, double y, double xbar, double* b /*[2]*/) {
+    const bool on = f * r[ISF_W] > 0.0;
+    const double Om = (f * r[ISF_W]) / D;
+    const double ey = r[ISF_CY] - y, ex = r[ISF_CX] - xbar;
+    b[0] = on ? ((f * r[ISF_MY]) / D + (2.0 * ey) * ((f * r[ISF_DY]) / D)) + Om * (ey * ey) : 0.0;
+    b[1] = on ? ((f * r[ISF_MX]) / D + (2.0 * ex) * ((f * r[ISF_DX]) / D)) + Om * (ex * ex) : 0.0;
+}
+
 // ---- segment combine (integers only) ----------------------------------------------------------
 // A segment record is (kb, S, S2): kb = max k_i of the segment (integral double, -inf if the segment
 // has no live particle), S = sum q, S2 = sum q^2 (128 bit).  With K = max kb:

@@ -3,6 +3,7 @@ the univariate LinearModel (UnivariateLinearGaussian, unobserved_components).
 
     IBIS(M, model, prior, chain, ess_threshold, min_ar=-1.0)        ibis.jl:26-58
     smc2 / smc2_step / smc2_run, resample_, rejuvenate_, expected_parameters, density_tempered   (smc_samplers.py dispatches here)
+    observation_dist, estimated_trend, quantile (plotting_utils.jl:94-137), filtered_state: reductions over the cloud on the device
 
 A parameter particle owns O(1) state - theta, its model row, (x, Sigma), logZ, logw - and all of it lives on the device for the
 life of the sampler (smc_ibis_*, csrc/smc_ibis_kernels.h): an online step is one Kalman update per particle, a window of steps
@@ -19,6 +20,8 @@ predict_first: the reference's smc²(ibis, y) runs kalman_filter on y[1], which 
 particle filters; True is the literal loop.  The flag holds online and in every re-filter alike, so logZ[m] always equals
 log_likelihood_kalman(y[:t], model(theta[m])) with the same flag.
 """
+import math
+import statistics
 import sys
 
 import numpy as np
@@ -61,6 +64,8 @@ class IBIS:
         self._calls = 0
         self._h = None
         self.t = 0
+        self._summ = None              # {"p": levels or None, "ahead": 0 | 1} while every period's summaries are recorded
+        self.summary_trace = []        # [(t, y, Sigma, between, xbar, Sbar, quantiles or None)], one entry per period kept
 
     # -- the device half ------------------------------------------------------------------------------
     def _handle(self):
@@ -99,19 +104,97 @@ class IBIS:
         """the normalised outer weights (ibis.ω after reweight)"""
         return _lib.host_reweight(self.logw)[1]
 
+    def set_summaries(self, summaries=True, ahead=0):
+        """record observation_dist / filtered_state of every period from now on into summary_trace (smc2, smc2_step and
+        smc2_run append their periods; on the device, inside the step's launch).  summaries: True, a list of quantile levels,
+        or None / False to switch the recording off."""
+        if summaries is None or summaries is False:
+            self._summ = None
+        else:
+            if ahead not in (0, 1):
+                raise ValueError("ahead is 0 (the filtered observation) or 1 (the one-step forecast)")
+            self._summ = {"p": None if summaries is True else [float(v) for v in np.atleast_1d(summaries)], "ahead": int(ahead)}
+        return self
+
     def __repr__(self):
         w = self.omega
         return "ess     = %.3f\nmean(theta) = %s" % (self.ess, np.array2string((self.theta * w[:, None]).sum(axis=0)))
 
 
-def _window(ibis, y, ess_min):
+def _window(ibis, y, ess_min, t=None):
     """k = len(y) steps of smc²! in one launch; the host walks the k x nseg records the device computed and keeps the steps up to
-    the first whose ESS is below ess_min -> (ess [j], j)"""
+    the first whose ESS is below ess_min -> (ess [j], j).  With summaries switched on the same launch records every step's row
+    and the rows of the j kept steps (periods t .. t + j - 1) go to summary_trace: the dropped steps are redone by a later
+    window, which records them then."""
     h = ibis._handle()
+    summ = ibis._summ if t is not None else None
+    want = (summ is not None, summ["ahead"] if summ else 0)
+    if want != getattr(h, "_recording", (False, 0)):       # (a run without summaries makes the calls it made before)
+        h.set_summaries(*want)
+        h._recording = want
     rec, _ = h.window(y)
     ess, j = _lib.host_outer_walk(rec, ibis.M, ess_min)
+    if summ is not None:
+        for i, r in enumerate(h.get_summaries(j)):
+            q = None if summ["p"] is None else _normal_quantiles(r[0], r[1], summ["p"])
+            ibis.summary_trace.append((t + i, float(r[0]), float(r[1]), float(r[2]), float(r[3]), float(r[4]), q))
     h.commit(j)
     return ess, j
+
+
+def _summary(ibis, ahead=0):
+    """(y, Sigma, between, xbar, Sbar, between_x, K, D): smc_ibis_summary on the resident cloud; before the first sampler call
+    the same specification on the host (smc_host_ibis_summary) over the initial cloud - no device call"""
+    if ahead not in (0, 1):
+        raise ValueError("ahead is 0 (the filtered observation) or 1 (the one-step forecast)")
+    if ibis._h is None:
+        rows = ibis.theta_map.rows(ibis._theta0)
+        return _lib.host_ibis_summary(rows, rows[:, 4], rows[:, 5], np.zeros(ibis.M), ahead)
+    return ibis._h.summary(ahead)
+
+
+def observation_dist(ibis, ahead=0, between=False):
+    """observation_dist(ibis)   plotting_utils.jl:94-112 -> (y, Sigma) = (sum omega B x, sum omega (B Sigma_m B' + R)), reduced on
+    the device.  ahead=1: after one Kalman prediction per particle (the one-step forecast; :126-127).  between=True adds
+    sum omega (ym - y)^2, the spread of the component means that the reference's Sigma leaves out: Sigma + between is the variance
+    of the mixture."""
+    r = _summary(ibis, ahead)
+    return (float(r[0]), float(r[1]), float(r[2])) if between else (float(r[0]), float(r[1]))
+
+
+def estimated_trend(ibis):
+    """estimated_trend(ibis) = observation_dist(ibis)[1]   plotting_utils.jl:114 (1-based there: the mean)"""
+    return observation_dist(ibis)[0]
+
+
+def filtered_state(ibis):
+    """(xbar, Sbar, between) = (sum omega x, sum omega Sigma_m, sum omega (x - xbar)^2): the filtered state of the mixture"""
+    r = _summary(ibis, 0)
+    return float(r[3]), float(r[4]), float(r[5])
+
+
+def _normal_quantiles(mean, var, p):
+    """quantile(Normal(mean, sqrt(var)), p) for the levels p in ascending order (a copy is sorted), on the host"""
+    out = np.empty(len(p))
+    for i, v in enumerate(sorted(p)):
+        if not 0.0 <= v <= 1.0:
+            raise ValueError("quantile levels lie in [0, 1]")
+        if not (math.isfinite(mean) and var >= 0.0 and math.isfinite(var)):
+            out[i] = math.nan
+        elif v in (0.0, 1.0) or var == 0.0:
+            out[i] = mean if var == 0.0 else (-math.inf if v == 0.0 else math.inf)
+        else:
+            out[i] = statistics.NormalDist(mean, math.sqrt(var)).inv_cdf(v)
+    return out
+
+
+def quantile(ibis, p, ahead=0, total=False):
+    """quantile(ibis, p)   plotting_utils.jl:128-137: the quantiles of Normal(y, sqrt(Sigma)), (y, Sigma) = observation_dist(ibis,
+    ahead), at the levels p in ascending order.  The caller's p is left as it is (the reference sorts it in place, :132).
+    total=True: Normal(y, sqrt(Sigma + between)), the moment-matched normal of the mixture.  A scalar p gives a float."""
+    y, S, b = observation_dist(ibis, ahead, between=True)
+    q = _normal_quantiles(y, S + b if total else S, [float(v) for v in np.atleast_1d(p)])
+    return float(q[0]) if np.ndim(p) == 0 else q
 
 
 def smc2(ibis, y):
@@ -120,7 +203,8 @@ def smc2(ibis, y):
     h = ibis._handle()
     if ibis.t != 0:
         h.set_theta(ibis.theta)           # again from (x0, sigma0), logZ = logw = 0
-    ess, _ = _window(ibis, y[:1], 0.0)
+    ibis.summary_trace = []
+    ess, _ = _window(ibis, y[:1], 0.0, 1)
     ibis.ess = float(ess[0])
     ibis.t = 1
     return ibis
@@ -157,7 +241,7 @@ def smc2_step(ibis, y, t, verbose=True, out=sys.stdout):
     if ibis.ess < ibis.ess_min:
         resample_(ibis)
         rejuvenate_(ibis, y[: t - 1], 1.0, verbose, out)
-    ess, _ = _window(ibis, y[t - 1: t], 0.0)
+    ess, _ = _window(ibis, y[t - 1: t], 0.0, t)
     ibis.ess = float(ess[0])
     ibis.t = t
     if verbose:
@@ -165,12 +249,24 @@ def smc2_step(ibis, y, t, verbose=True, out=sys.stdout):
     return ibis
 
 
-def smc2_run(ibis, y, t_from, t_to, window=16, verbose=True, out=sys.stdout):
+def smc2_run(ibis, y, t_from, t_to, window=16, verbose=True, out=sys.stdout, summaries=None, ahead=0):
     """for t in t_from:t_to  smc²!(ibis, y, t)  end, the same results bit for bit, with up to `window` steps per launch: the
     device computes the reweight records of every step, the host finds the first step whose ESS falls below the threshold,
-    the steps up to it are kept and the rest redone after the resample-move."""
+    the steps up to it are kept and the rest redone after the resample-move.
+    summaries=True or a list of quantile levels: ibis.summary_trace gets one entry per period kept,
+    (t, y, Sigma, between, xbar, Sbar, quantiles or None) with (y, Sigma, between) = observation_dist(ibis, ahead, between=True)
+    and (xbar, Sbar) of filtered_state(ibis) after that period - recorded inside the window launches, bit for bit what those
+    calls give after every smc2_step, with no read of the cloud.  (Without the argument: as switched by ibis.set_summaries.)"""
     y = np.asarray(y, dtype=np.float64)
     t = int(t_from)
+    if summaries is not None:
+        keep = ibis._summ
+        ibis.set_summaries(summaries, ahead)
+        ibis.summary_trace = [e for e in ibis.summary_trace if e[0] < t]
+        try:
+            return smc2_run(ibis, y, t_from, t_to, window, verbose, out)
+        finally:
+            ibis._summ = keep
     while t <= t_to:
         if verbose:
             out.write("t = %4d\tess = %4.3f" % (t - 1, ibis.ess))
@@ -178,7 +274,7 @@ def smc2_run(ibis, y, t_from, t_to, window=16, verbose=True, out=sys.stdout):
             resample_(ibis)
             rejuvenate_(ibis, y[: t - 1], 1.0, verbose, out)
         k = max(1, min(int(window), 64, t_to - t + 1))
-        ess, j = _window(ibis, y[t - 1: t - 1 + k], ibis.ess_min)
+        ess, j = _window(ibis, y[t - 1: t - 1 + k], ibis.ess_min, t)
         ibis.ess = float(ess[-1])
         ibis.t = t + j - 1
         if verbose:

@@ -328,11 +328,34 @@ def filtered_summaries(smc, p=(0.25, 0.5, 0.75), component=0, literal=False):
     return _integrate(smc.omega, _per_theta(smc, np.column_stack([q, np.asarray(var)[component]])))
 
 
+def observation_dist(ibis, ahead=0, between=False):
+    """observation_dist(ibis)   src/plotting_utils.jl:94-112 (an IBIS sampler only: ibis.py)"""
+    if not isinstance(ibis, IBIS):
+        raise TypeError("observation_dist is defined for an IBIS sampler (plotting_utils.jl:94)")
+    return _ibis.observation_dist(ibis, ahead, between)
+
+
+def quantile(ibis, p, ahead=0, total=False):
+    """quantile(ibis, p)   src/plotting_utils.jl:128-137 (an IBIS sampler only: ibis.py; for SMC see filtered_summaries)"""
+    if not isinstance(ibis, IBIS):
+        raise TypeError("quantile is defined for an IBIS sampler (plotting_utils.jl:128); for SMC use filtered_summaries")
+    return _ibis.quantile(ibis, p, ahead, total)
+
+
+def filtered_state(ibis):
+    """(xbar, Sbar, between) of an IBIS sampler's filtered state (ibis.py)"""
+    if not isinstance(ibis, IBIS):
+        raise TypeError("filtered_state is defined for an IBIS sampler")
+    return _ibis.filtered_state(ibis)
+
+
 def estimated_trend(smc):
     """estimated_trend(smc)   src/plotting_utils.jl:116-124:  sum_m omega[m] * mean(observation(model(theta[m]), w[m]' x[m])),
     with the NORMALISED omega (the reference uses smc.ω as it stands - all ones right after rejuvenate!; stated deviation).
     The filtered means w[m]' x[m] come from the device; mean(observation(.)) is B x for the linear model (ssm.jl:96-103),
     x[1] for UCSV (:244-247) and 0 for the stochastic-volatility model."""
+    if isinstance(smc, IBIS):
+        return _ibis.estimated_trend(smc)                              # plotting_utils.jl:114
     if smc._main is None:
         raise ValueError("estimated_trend needs the online sampler's filters (call smc2 first)")
     mean, _ = smc._main.moments()                                      # [d][M_local]
@@ -569,7 +592,7 @@ def _window_summaries(smc, t, lik_local, j, logw_local):
     return rows
 
 
-def smc2_run(smc, y, t_from, t_to, window=16, verbose=True, out=sys.stdout, summaries=None, component=0, literal=False):
+def smc2_run(smc, y, t_from, t_to, window=16, verbose=True, out=sys.stdout, summaries=None, component=0, literal=False, ahead=0):
     """for t in t_from:t_to  smc²!(smc, y, t)  end   (the online loop of smc_samplers.jl:308-340 / README.md:93-101),
     with the same results bit for bit, but up to `window` propagation steps per device call: between two
     resample-move decisions the inner filters only need y[t], so a window of steps runs in ONE launch with the particle
@@ -583,9 +606,7 @@ def smc2_run(smc, y, t_from, t_to, window=16, verbose=True, out=sys.stdout, summ
     [(t, quantiles [len(p)], variance)], bit-identical to calling filtered_summaries after every smc2_step.
     literal=True: the summaries are filtered_summaries(..., literal=True) (unweighted per-filter quantiles, corrected variance)."""
     if isinstance(smc, IBIS):
-        if summaries is not None:
-            raise NotImplementedError("IBIS has no particle cloud to summarise: x and Sigma are the exact filtered moments")
-        return _ibis.smc2_run(smc, y, t_from, t_to, window, verbose, out)
+        return _ibis.smc2_run(smc, y, t_from, t_to, window, verbose, out, summaries, ahead)   # (summaries: observation_dist per period)
     y = np.asarray(y, dtype=np.float64)
     t = int(t_from)
     smc._summ = None if summaries is None else {"p": [float(v) for v in summaries], "component": int(component), "literal": bool(literal)}
