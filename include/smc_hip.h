@@ -27,6 +27,7 @@ extern "C" {
 #define SMC_MODEL_LG1D 1   /* UnivariateLinearGaussian :74-109  raw = (A,B,Q,R,x0,sigma0), Q R sigma0 variances */
 #define SMC_MODEL_SV1D 2   /* stochastic volatility (SURVEY A7') raw = (mu,rho,sigma)                            */
 #define SMC_MODEL_UCSV3D 3 /* UCSV :215-263                     raw = (gamma_eps,gamma_eta,x0,log_s_eps0,log_s_eta0) */
+#define SMC_MODEL_UCSV_RB 4 /* UCSV with the trend integrated out (Rao-Blackwellised); the same raw row: "marginal UCSV" below */
 
 #define SMC_OK 0
 #define SMC_EINVAL (-1)
@@ -101,6 +102,28 @@ int smc_host_guided_step(int model_id, const double* raw, int kind, const double
 /* the same for n particles on the device, xp z x [d][n] (parity tests; the twin of smc_device_math) */
 int smc_device_guided_step(int model_id, const double* raw, int kind, const double* par, const double* xp,
                            const double* z, double y, int64_t n, double* x, double* logw, int device);
+
+/* ---- marginal UCSV: the Rao-Blackwellised filter ----------------------------------------------------
+ * SMC_MODEL_UCSV_RB is a filter family for the UCSV model (src/state_space_models.jl:215-263): given the two log-volatility
+ * paths (x, y) is linear-Gaussian, so a particle samples only the volatilities and carries the exact scalar Kalman filter of
+ * the trend (src/kalman_filter.jl:29-53 with A = B = 1).  State rows (m, lse, lsn, P), smc_model_dim = 4: rows 1, 2 as UCSV3D,
+ * row 0 the filtered mean of the trend, row 3 its filtered variance - always the posterior after the step's observation.
+ * The parameter row is UCSV3D's (smc_model_nraw = 5), with the reference's conventions.  One step, the first included:
+ *     P- = P + exp(lse_prev)                    (t = 1: m = x0, P- = exp(lse0), and the volatilities start from lse0, lsn0)
+ *     lse = lse_prev + g_eps z0,  lsn = lsn_prev + g_eta z1
+ *     R = exp(lsn),  S = P- + R,  e = y - m,    logw = -(log 2pi + log S + e e / S) / 2
+ *     K = P- / S,  m' = m + K e,  P' = P- R / S (product form: 0 < P' <= min(P-, R))
+ * logZ estimates the same p(y) as a UCSV3D filter, without bias; the trend adds no Monte-Carlo variance.  Two normals per particle
+ * and step (Philox slots 1 and 2: lse, lsn).  Everything a handle offers applies (every launch path, ESS, summaries of all four
+ * rows, skip masks, windows, slot moves, PMMH, exchange) except proposals: smc_set_proposal with a kind other than SMC_PROP_NONE
+ * is SMC_EINVAL.  LDS-resident up to 2048 particles.  The observation moments are UCSV3D's with row 0 for the trend; the trend's
+ * filtered variance is var(row 0) + mean(row 3).  smc_simulate with this id simulates UCSV3D (x [3][T]). */
+/* one particle, one step, on the host: sp (m, lse, lsn, P) of the ancestor (not read when first != 0), z the two normals */
+int smc_host_rb_step(const double* raw /*[5]*/, const double* sp /*[4]*/, const double* z /*[2]*/, double y, int first,
+                     double* s /*[4]*/, double* logw);
+/* the same for n particles on the device, sp s [4][n], z [2][n] (parity tests) */
+int smc_device_rb_step(const double* raw, const double* sp, const double* z, double y, int first, int64_t n, double* s,
+                       double* logw, int device);
 
 /* ---- the hot path ----------------------------------------------------------------------------*/
 /* bootstrap_filter(N, y, model) -> (x, w, logmu)            src/particles.jl:87-105 */
@@ -408,7 +431,10 @@ int smc_get_quantiles(smc_handle h, int component, const double* p, int np, doub
 
 /* ---- host-side helpers (no GPU needed) ---------------------------------------------------------*/
 /* simulate(rng, model, T) -> (x, y)                         src/state_space_models.jl:11-26 */
-int smc_simulate(int model_id, const double* raw, int64_t T, uint64_t seed, double* x /*[d][T]*/, double* y /*[T]*/);
+int smc_simulate(int model_id, const double* raw, int64_t T, uint64_t seed, double* x /*[smc_simulate_dim][T] or NULL*/, double* y /*[T]*/);
+/* rows of smc_simulate's x: smc_model_dim(model_id), except for SMC_MODEL_UCSV_RB, whose data-generating model is UCSV3D (3 rows:
+ * x, log s_eps, log s_eta - not the 4 rows of the filter's state); -1 for an unknown id */
+int smc_simulate_dim(int model_id);
 int smc_model_dim(int model_id);
 int smc_model_nraw(int model_id);
 /* the segment length smc_create picks for seg = 0: a function of the model family (its state dimension) and n_x alone */

@@ -105,9 +105,15 @@ Base.collect(w::HipWeights) = fetch_state!(w.f).wcache[:, w.m]
 
 # model families the GPU implements (include/smc_hip.h: SMC_MODEL_*), and their parameter rows
 const HipLG = LinearModel{Float64,Float64,Float64,Float64,Float64,Float64}
-const HipModels = Union{HipLG,UCSV}
+# MarginalUCSV(ucsv): the same model run by the Rao-Blackwellised filter family (SMC_MODEL_UCSV_RB: the trend integrated out by a
+# Kalman filter inside every particle; state rows (m, log σε, log ση, P)).  Same parameter row; takes no proposal.
+struct MarginalUCSV <: StateSpaceModel
+    model::UCSV
+end
+const HipModels = Union{HipLG,UCSV,MarginalUCSV}
 hip_model(m::HipLG) = (Cint(1), Float64[m.A, m.B, m.Q, m.R, m.x0, m.σ0])                      # state_space_models.jl:46-58
 hip_model(m::UCSV) = (Cint(3), Float64[m.γ[1], m.γ[2], m.x0, m.log_σ0[1], m.log_σ0[2]])        # :215-222
+hip_model(m::MarginalUCSV) = (Cint(4), hip_model(m.model)[2])
 # [n_raw x M] column-major == the C ABI's [n_theta][n_raw] row-major
 hip_rows(models::Vector{<:HipModels}) = reduce(hcat, last.(hip_model.(models)))
 

@@ -8,10 +8,10 @@ There is no CPU fallback: importing works anywhere, running a filter needs the G
 from .distributions import LogNormal, Normal, TruncatedNormal, Uniform, product_distribution  # noqa: F401
 from .ibis import IBIS  # noqa: F401
 from .kalman_filter import log_likelihood_kalman  # noqa: F401
-from .models import (UCSV, LinearModel, StateSpaceModel, StochasticVolatility, UnivariateLinearGaussian,  # noqa: F401
+from .models import (UCSV, LinearModel, MarginalUCSV, StateSpaceModel, StochasticVolatility, UnivariateLinearGaussian,  # noqa: F401
                      simulate, unobserved_components, unobserved_components_stochastic_volatility)
 from .particles import (AffineGaussianProposal, OptimalProposal, bootstrap_filter, bootstrap_filter_, log_likelihood, normalize,  # noqa: F401
-                        optimal_proposal, particle_filter, particle_filter_, resample, reweight)
+                        optimal_proposal, particle_filter, particle_filter_, resample, reweight, trend_moments)
 from .smc_samplers import (SMC, ThetaMap, density_tempered, estimated_trend, expected_parameters, filtered_state,  # noqa: F401
                            filtered_summaries, observation_dist, quantile, rejuvenate_, resample_, smc2, smc2_run, smc2_step)
 

@@ -11,14 +11,14 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMC_LIB") or os.path.join(_HERE, "lib", "libsmchip.so")   # SMC_LIB: profiling builds
 
-MODEL_LG1D, MODEL_SV1D, MODEL_UCSV3D = 1, 2, 3
+MODEL_LG1D, MODEL_SV1D, MODEL_UCSV3D, MODEL_UCSV_RB = 1, 2, 3, 4
 FLAG_ANCESTORS, FLAG_NO_RESIDENT, FLAG_SYSTEMATIC = 1, 2, 4
 
 # every symbol include/smc_hip.h declares
 EXPORTS = [
     "smc_create", "smc_destroy", "smc_set_params", "smc_set_streams", "smc_reseed", "smc_init", "smc_step",
     "smc_log_likelihood", "smc_get_state", "smc_get_logZ", "smc_permute", "smc_copy_from", "smc_slot_bytes", "smc_pack_slots", "smc_unpack_slots", "smc_get_weights_raw", "smc_get_geometry",
-    "smc_last_elapsed_ms", "smc_synchronize", "smc_time_step_kernel", "smc_event_overhead_ms", "smc_normalize", "smc_resample", "smc_kalman_log_likelihood", "smc_get_moments", "smc_get_quantiles", "smc_simulate", "smc_model_dim",
+    "smc_last_elapsed_ms", "smc_synchronize", "smc_time_step_kernel", "smc_event_overhead_ms", "smc_normalize", "smc_resample", "smc_kalman_log_likelihood", "smc_get_moments", "smc_get_quantiles", "smc_simulate", "smc_simulate_dim", "smc_model_dim",
     "smc_model_nraw", "smc_auto_seg", "smc_device_count", "smc_host_exp", "smc_host_log", "smc_host_philox4x32_10",
     "smc_host_box_muller", "smc_sys_targets", "smc_device_math", "smc_last_error", "smc_version",
     "smc_set_skip", "smc_pmmh_configure", "smc_pmmh_rejuvenate", "smc_host_pmmh_propose", "smc_host_pmmh_log_uniform",
@@ -29,6 +29,7 @@ EXPORTS = [
     "smc_host_outer_advance", "smc_host_outer_temper", "smc_host_outer_resample", "smc_host_rw_factor",
     "smc_set_summaries", "smc_get_summaries", "smc_set_summary_mode", "smc_host_quantile7", "smc_host_sample_moments",
     "smc_set_proposal", "smc_host_optimal_proposal", "smc_host_guided_step", "smc_device_guided_step",
+    "smc_host_rb_step", "smc_device_rb_step",
     "smc_ibis_create", "smc_ibis_destroy", "smc_ibis_configure", "smc_ibis_set_theta", "smc_ibis_window", "smc_ibis_commit",
     "smc_ibis_filter", "smc_ibis_permute", "smc_ibis_set_logw", "smc_ibis_rejuvenate", "smc_ibis_get",
     "smc_ibis_summary", "smc_ibis_set_summaries", "smc_ibis_get_summaries", "smc_host_ibis_summary",
@@ -118,10 +119,13 @@ def lib():
     L.smc_host_optimal_proposal.argtypes = [C.c_int, _dp, _dp]
     L.smc_host_guided_step.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, _dp, _dp]
     L.smc_device_guided_step.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int64, _dp, _dp, C.c_int]
+    L.smc_host_rb_step.argtypes = [_dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp]
+    L.smc_device_rb_step.argtypes = [_dp, _dp, _dp, C.c_double, C.c_int, C.c_int64, _dp, _dp, C.c_int]
     L.smc_get_summaries.argtypes = [h, C.c_int64, _dp, _dp, _dp]
     L.smc_sys_targets.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.c_int]
     L.smc_simulate.argtypes = [C.c_int, _dp, C.c_int64, C.c_uint64, _dp, _dp]
     L.smc_model_dim.argtypes = [C.c_int]
+    L.smc_simulate_dim.argtypes = [C.c_int]
     L.smc_model_nraw.argtypes = [C.c_int]
     L.smc_auto_seg.argtypes = [C.c_int, C.c_int64]
     L.smc_host_exp.restype = C.c_double
@@ -207,7 +211,7 @@ def sys_targets(Dtot, n, u, j0, nk, device=-1):
 def simulate(model_id, raw, T, seed):
     """simulate(rng, model, T) -> (x [d][T], y [T])   src/state_space_models.jl:11-26 (host code)."""
     raw = np.ascontiguousarray(raw, dtype=np.float64)
-    d = lib().smc_model_dim(model_id)
+    d = lib().smc_simulate_dim(model_id)   # rows of the simulated state: smc_model_dim, except UCSV's 3 for the marginal family
     x = np.zeros((d, T))
     y = np.zeros(T)
     check(lib().smc_simulate(model_id, _d(raw), T, seed, _d(x), _d(y)))
@@ -286,6 +290,32 @@ def device_guided_step(model_id, raw, kind, par, xp, z, y, device=0):
     lw = np.zeros(n)
     check(lib().smc_device_guided_step(int(model_id), _d(raw), int(kind), _d(par), _d(xp), _d(z), float(y), n, _d(x), _d(lw), device))
     return x, lw
+
+
+def host_rb_step(raw, sp, z, y, first=False):
+    """one particle, one step of the marginal UCSV family by the specification on the host: state (m, lse, lsn, P) [4] and two
+    normals -> (state [4], logw) (smc_host_rb_step; no GPU).  first=True: the step at t = 1, which does not read sp"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    sp = np.ascontiguousarray(sp, dtype=np.float64).ravel()
+    z = np.ascontiguousarray(z, dtype=np.float64).ravel()
+    assert raw.size == 5 and sp.size == 4 and z.size == 2
+    s = np.zeros(4)
+    lw = C.c_double()
+    check(lib().smc_host_rb_step(_d(raw), _d(sp), _d(z), float(y), int(bool(first)), _d(s), C.byref(lw)))
+    return s, lw.value
+
+
+def device_rb_step(raw, sp, z, y, first=False, device=0):
+    """the same for n particles on the device: sp [4][n], z [2][n] -> (state [4][n], logw [n]) (smc_device_rb_step)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    sp = np.ascontiguousarray(sp, dtype=np.float64).reshape(4, -1)
+    z = np.ascontiguousarray(z, dtype=np.float64).reshape(2, -1)
+    assert raw.size == 5 and sp.shape[1] == z.shape[1]
+    n = sp.shape[1]
+    s = np.zeros((4, n))
+    lw = np.zeros(n)
+    check(lib().smc_device_rb_step(_d(raw), _d(sp), _d(z), float(y), int(bool(first)), n, _d(s), _d(lw), device))
+    return s, lw
 
 
 OUTER_SEG = 8     # SMC_OUTER_SEG: entries per segment of the outer level's integer normalisation

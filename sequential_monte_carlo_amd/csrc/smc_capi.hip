@@ -139,14 +139,16 @@ extern "C" int smc_auto_seg(int model_id, int64_t n) {
     // beyond 512 segments the table of the segments is built once per step by k_table instead of by every workgroup; longer
     // segments keep the count at MAX_NSEG for still larger filters.  The segment length is part of the numerical spec (the CPU
     // restatement used by the tests follows the same rule).
-    const bool d3 = model_dim_rt(model_id) == 3;
+    // (four state rows - the marginal UCSV family - follow the three-row rule with the resident limit their LDS allows: 2048)
+    const int dm = model_dim_rt(model_id);
+    const bool d3 = dm >= 3;
     if (n > (int64_t)MAX_NSEG * 4096) return 8192;
     if (n > (int64_t)MAX_NSEG * 2048) return 4096;
     if (n > (int64_t)MAX_NSEG * 1024) return 2048;
     if (n > ((int64_t)1 << 19)) return d3 ? 1024 : 2048;
     if (n > ((int64_t)1 << 17)) return 1024;
     if (n > ((int64_t)1 << 15)) return 512;
-    if (n > (d3 ? 4096 : MAX_SEG)) return 256;
+    if (n > (dm > 3 ? 2048 : d3 ? 4096 : MAX_SEG)) return 256;
     int s = 256;
     while (s < n) s <<= 1;
     return s;
@@ -167,6 +169,7 @@ static hipError_t do_init(smc_filter_s* h, double y) {
     case MODEL_LG1D: return launch_init<MODEL_LG1D>(h->v, h->geo, h->cur, y, h->stream);
     case MODEL_SV1D: return launch_init<MODEL_SV1D>(h->v, h->geo, h->cur, y, h->stream);
     case MODEL_UCSV3D: return launch_init<MODEL_UCSV3D>(h->v, h->geo, h->cur, y, h->stream);
+    case MODEL_UCSV_RB: return launch_init<MODEL_UCSV_RB>(h->v, h->geo, h->cur, y, h->stream);
     }
     return hipErrorInvalidValue;
 }
@@ -194,6 +197,7 @@ static hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y) 
     case MODEL_LG1D: return launch_step<MODEL_LG1D>(h->v, h->geo, h->cur, t, emit_prev, y, h->stream);
     case MODEL_SV1D: return launch_step<MODEL_SV1D>(h->v, h->geo, h->cur, t, emit_prev, y, h->stream);
     case MODEL_UCSV3D: return launch_step<MODEL_UCSV3D>(h->v, h->geo, h->cur, t, emit_prev, y, h->stream);
+    case MODEL_UCSV_RB: return launch_step<MODEL_UCSV_RB>(h->v, h->geo, h->cur, t, emit_prev, y, h->stream);
     }
     return hipErrorInvalidValue;
 }
@@ -238,6 +242,7 @@ static hipError_t do_persist(smc_filter_s* h, uint32_t t0, uint32_t t1, PersistC
     case MODEL_LG1D: return launch_persist<MODEL_LG1D>(h->v, h->geo, h->cur, t0, t1, pc, h->stream);
     case MODEL_SV1D: return launch_persist<MODEL_SV1D>(h->v, h->geo, h->cur, t0, t1, pc, h->stream);
     case MODEL_UCSV3D: return launch_persist<MODEL_UCSV3D>(h->v, h->geo, h->cur, t0, t1, pc, h->stream);
+    case MODEL_UCSV_RB: return hipErrorCooperativeLaunchTooLarge;   // (no persistent kernel for this family: one launch per step)
     }
     return hipErrorInvalidValue;
 }
@@ -253,6 +258,7 @@ static hipError_t do_resident(smc_filter_s* h, int T) {
     case MODEL_LG1D: return launch_resident<MODEL_LG1D>(h->v, T, h->d_recs, h->stream);
     case MODEL_SV1D: return launch_resident<MODEL_SV1D>(h->v, T, h->d_recs, h->stream);
     case MODEL_UCSV3D: return launch_resident<MODEL_UCSV3D>(h->v, T, h->d_recs, h->stream);
+    case MODEL_UCSV_RB: return launch_resident<MODEL_UCSV_RB>(h->v, T, h->d_recs, h->stream);
     }
     return hipErrorInvalidValue;
 }
@@ -269,6 +275,7 @@ static hipError_t do_window(smc_filter_s* h, int k, int bout) {
     case MODEL_LG1D: return launch_window<MODEL_LG1D>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->h_win, h->stream);
     case MODEL_SV1D: return launch_window<MODEL_SV1D>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->h_win, h->stream);
     case MODEL_UCSV3D: return launch_window<MODEL_UCSV3D>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->h_win, h->stream);
+    case MODEL_UCSV_RB: return launch_window<MODEL_UCSV_RB>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->h_win, h->stream);
     }
     return hipErrorInvalidValue;
 }
@@ -624,6 +631,8 @@ static bool affine_row_ok(const double* par) {
 extern "C" int smc_set_proposal(smc_handle h, int kind, const double* par) {
     if (!h) return fail(SMC_EINVAL, "smc_set_proposal: NULL handle");
     if (kind != PROP_NONE && kind != PROP_AFFINE && kind != PROP_OPTIMAL) return fail(SMC_EINVAL, "smc_set_proposal: unknown kind");
+    if (h->model == MODEL_UCSV_RB && kind != PROP_NONE)
+        return fail(SMC_EINVAL, "smc_set_proposal: SMC_MODEL_UCSV_RB takes no proposal (its step already conditions on y: the trend is integrated out)");
     if (!proposal_supported(h->model, kind)) return fail(SMC_EINVAL, "smc_set_proposal: this model family has no proposal of that kind");
     if ((kind == PROP_AFFINE) != (par != nullptr)) return fail(SMC_EINVAL, "smc_set_proposal: rows are given with SMC_PROP_AFFINE and only then");
     if (kind == PROP_AFFINE)
@@ -848,7 +857,7 @@ struct SeriesScope {
 static bool summaries_on(const smc_filter_s* h) { return h->sum_np > 0 || h->sum_mom != 0; }
 // whether the LDS-resident kernels have room for the summaries' histograms next to the filter's state (160 KiB per workgroup)
 static bool summaries_fit_lds(const smc_filter_s* h) {
-    return (size_t)lds_padded_len(h->v.seg) * 8 * (size_t)(1 + h->d) + scr_words(1024, 4) * 8 + summary_lds_words(h->sum_np) * 8 <= (size_t)160 * 1024;
+    return (size_t)lds_padded_len(h->v.seg) * 8 * (size_t)(1 + h->d) + scr_words(1024, 4) * 8 + summary_lds_words(h->sum_np, h->d) * 8 <= (size_t)160 * 1024;
 }
 static int ensure_summaries(smc_handle h, int64_t T) {
     if (T > h->sum_cap) {
@@ -1766,6 +1775,7 @@ static int summaries_once(smc_handle h, int component, const double* p, int np, 
     case MODEL_LG1D: e = launch_summ_once<MODEL_LG1D>(v, h->cur, h->stream); break;
     case MODEL_SV1D: e = launch_summ_once<MODEL_SV1D>(v, h->cur, h->stream); break;
     case MODEL_UCSV3D: e = launch_summ_once<MODEL_UCSV3D>(v, h->cur, h->stream); break;
+    case MODEL_UCSV_RB: e = launch_summ_once<MODEL_UCSV_RB>(v, h->cur, h->stream); break;
     }
     if (e == hipErrorInvalidValue) return SMC_OK;
     HIPCHK(e);
@@ -1859,6 +1869,7 @@ static void simulate_t(const Params& p, int64_t T, uint64_t seed, double* x, dou
     }
 }
 
+extern "C" int smc_simulate_dim(int model_id) { return model_id == MODEL_UCSV_RB ? model_dim_rt(MODEL_UCSV3D) : model_dim_rt(model_id); }
 extern "C" int smc_simulate(int model_id, const double* raw, int64_t T, uint64_t seed, double* x, double* y) {
     const int nraw = model_nraw_rt(model_id);
     if (nraw < 0 || !raw || !y || T <= 0) return fail(SMC_EINVAL, "smc_simulate: bad argument");
@@ -1868,7 +1879,8 @@ extern "C" int smc_simulate(int model_id, const double* raw, int64_t T, uint64_t
     switch (model_id) {
     case MODEL_LG1D: simulate_t<MODEL_LG1D>(p, T, seed, x, y); break;
     case MODEL_SV1D: simulate_t<MODEL_SV1D>(p, T, seed, x, y); break;
-    default: simulate_t<MODEL_UCSV3D>(p, T, seed, x, y); break;
+    case MODEL_UCSV3D: simulate_t<MODEL_UCSV3D>(p, T, seed, x, y); break;
+    case MODEL_UCSV_RB: simulate_t<MODEL_UCSV3D>(p, T, seed, x, y); break;   // the data-generating model is UCSV: x is [3][T] (smc_simulate_dim)
     }
     return SMC_OK;
 }
@@ -1977,6 +1989,50 @@ extern "C" int smc_device_guided_step(int model_id, const double* raw, int kind,
     if (e == hipSuccess) e = hipMemcpy(logw, dlw, (size_t)n * 8, hipMemcpyDeviceToHost);
     (void)hipFree(dxp); (void)hipFree(dz); (void)hipFree(dx); (void)hipFree(dlw);
     HIPCHK(e);
+    return SMC_OK;
+}
+
+// the marginal step (smc_spec.h "marginal families"), one particle on the host / n particles on a device
+extern "C" int smc_host_rb_step(const double* raw, const double* sp, const double* z, double y, int first, double* s, double* logw) {
+    if (!raw || !sp || !z || !s || !logw) return fail(SMC_EINVAL, "smc_host_rb_step: NULL argument");
+    Params P;
+    for (int k = 0; k < NPARAM; ++k) P.raw[k] = k < model_nraw_rt(MODEL_UCSV_RB) ? raw[k] : 0.0;
+    derive_params(MODEL_UCSV_RB, P.raw, P.der);
+    double a[4] = {sp[0], sp[1], sp[2], sp[3]}, o[4];
+    *logw = model_marginal_step<MODEL_UCSV_RB>(P, first != 0, a, z, y, o);
+    for (int c = 0; c < 4; ++c) s[c] = o[c];
+    return SMC_OK;
+}
+__global__ void k_rb_step(Params P, int first, const double* sp, const double* z, double y, int64_t n, double* s, double* logw) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double a[4], zz[2], o[4];
+    for (int c = 0; c < 4; ++c) a[c] = sp[(size_t)c * n + i];
+    for (int c = 0; c < 2; ++c) zz[c] = z[(size_t)c * n + i];
+    logw[i] = model_marginal_step<MODEL_UCSV_RB>(P, first != 0, a, zz, y, o);
+    for (int c = 0; c < 4; ++c) s[(size_t)c * n + i] = o[c];
+}
+extern "C" int smc_device_rb_step(const double* raw, const double* sp, const double* z, double y, int first, int64_t n, double* s, double* logw,
+                                  int device) {
+    if (!raw || !sp || !z || !s || !logw || n <= 0) return fail(SMC_EINVAL, "smc_device_rb_step: bad argument");
+    Params P;
+    for (int k = 0; k < NPARAM; ++k) P.raw[k] = k < model_nraw_rt(MODEL_UCSV_RB) ? raw[k] : 0.0;
+    derive_params(MODEL_UCSV_RB, P.raw, P.der);
+    hipStream_t st = nullptr;
+    HIPCHK(util_stream(device, &st));
+    DevBuf dsp(0), dz(1), ds(2), dlw(3);
+    HIPCHK(dsp.alloc((size_t)4 * n * 8));
+    HIPCHK(dz.alloc((size_t)2 * n * 8));
+    HIPCHK(ds.alloc((size_t)4 * n * 8));
+    HIPCHK(dlw.alloc((size_t)n * 8));
+    HIPCHK(hipMemcpyAsync(dsp.p, sp, (size_t)4 * n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dz.p, z, (size_t)2 * n * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_rb_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, first, dsp.as<double>(), dz.as<double>(), y, n,
+                       ds.as<double>(), dlw.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(s, ds.p, (size_t)4 * n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(logw, dlw.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return SMC_OK;
 }
 

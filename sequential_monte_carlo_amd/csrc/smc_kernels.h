@@ -814,7 +814,7 @@ __device__ __forceinline__ int logical_segment(int bid, int nseg) {
 // ---------------------------------------------------------------------------------------------
 template <int MODEL, int THREADS, int NP>
 __global__ __launch_bounds__(THREADS) void k_init(FilterView v, int nxt, double y) {
-    constexpr int D = model_dim<MODEL>::value;
+    constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint64_t* scr = (uint64_t*)smem;
     const int sb = logical_segment(blockIdx.x, v.nseg), th = blockIdx.y, tid = smc_tid();
@@ -828,17 +828,22 @@ __global__ __launch_bounds__(THREADS) void k_init(FilterView v, int nxt, double 
         const int pl = tid + k * THREADS;            // pair within segment
         const int64_t i0 = seg0 + 2 * pl;            // first particle of the pair
         const uint32_t pg = (uint32_t)(i0 >> 1);     // pair index within the filter
-        double z[D][2], xn[2][D];
+        double z[NZ][2], xn[2][D];
 #pragma unroll
-        for (int c = 0; c < D; ++c) box_muller(draw(v.seed, pg, stream, 0u, SLOT_NORMAL0 + c), z[c][0], z[c][1]);
+        for (int c = 0; c < NZ; ++c) box_muller(draw(v.seed, pg, stream, 0u, SLOT_NORMAL0 + c), z[c][0], z[c][1]);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            double zz[D];
+            double zz[NZ];
 #pragma unroll
-            for (int c = 0; c < D; ++c) zz[c] = z[c][j];
-            model_initial<MODEL>(prm, zz, xn[j]);
+            for (int c = 0; c < NZ; ++c) zz[c] = z[c][j];
             const bool valid = (i0 + j) < v.n;
-            lw[k][j] = valid ? model_logobs<MODEL>(prm, xn[j], y) : nan_mask();
+            if constexpr (model_marginal<MODEL>::value) {   // the first step of a marginal family sees y (smc_spec.h)
+                const double l = model_marginal_step<MODEL>(prm, true, xn[j], zz, y, xn[j]);
+                lw[k][j] = valid ? l : nan_mask();
+            } else {
+                model_initial<MODEL>(prm, zz, xn[j]);
+                lw[k][j] = valid ? model_logobs<MODEL>(prm, xn[j], y) : nan_mask();
+            }
         }
 #pragma unroll
         for (int c = 0; c < D; ++c) {
@@ -890,7 +895,8 @@ template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS, bool PERSIST, cl
 __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, int emit_prev, double yval, char* smem) {
     static_assert(!GTAB || (MULTI && !PERSIST), "global table: multi-segment launches");
     static_assert(RPT == 1 || (RPT == 2 && MULTI && !GTAB && !PERSIST), "two records per thread: multi-segment launches");
-    constexpr int D = model_dim<MODEL>::value;
+    constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
+    static_assert(!(GUIDED && model_marginal<MODEL>::value), "marginal families have no proposals");
     constexpr int SEG = 2 * NP * THREADS;
     constexpr int NQ = 2 * NP;   // particles per thread
     constexpr int NSTAGE = nstage_for(SEG);
@@ -985,14 +991,15 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
     // ---- the state normals of this thread's children (under the loads of the records, the break points and the staged segments) ----------------
     // (three state coordinates, two pairs per thread: twelve normals held across the table, the targets and the search push the
     //  kernel to 183 vector registers - ONE workgroup per CU; they are computed next to their use instead, below)
-    constexpr bool LATE_Z = D == 3 && NP >= 2 && !SYS;
-    double z[NP][D][2];
+    //  (four state rows - the marginal UCSV family - hold eight gathered doubles per pair instead: late as well)
+    constexpr bool LATE_Z = D >= 3 && NP >= 2 && !SYS;
+    double z[NP][NZ][2];
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
         if (LATE_Z) break;
         const uint32_t pg = (uint32_t)((seg0 >> 1) + tid + k * THREADS);
 #pragma unroll
-        for (int c = 0; c < D; ++c) {
+        for (int c = 0; c < NZ; ++c) {
             if (SMC_ABL(v, 2)) { z[k][c][0] = 1e-3 * (double)(pg & 1023); z[k][c][1] = -z[k][c][0]; }
             else if (SMC_ABL(v, 6)) { const u32x4 w4 = draw(v.seed, pg, stream, t, SLOT_NORMAL0 + c); z[k][c][0] = 1e-9 * (double)w4.v[0]; z[k][c][1] = 1e-9 * (double)w4.v[2]; }
             else box_muller(draw(v.seed, pg, stream, t, SLOT_NORMAL0 + c), z[k][c][0], z[k][c][1]);
@@ -1287,14 +1294,16 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
         if (LATE_Z) {
             const uint32_t pg = (uint32_t)((seg0 >> 1) + tid + k * THREADS);
 #pragma unroll
-            for (int c = 0; c < D; ++c) box_muller(draw(v.seed, pg, stream, t, SLOT_NORMAL0 + c), z[k][c][0], z[k][c][1]);
+            for (int c = 0; c < NZ; ++c) box_muller(draw(v.seed, pg, stream, t, SLOT_NORMAL0 + c), z[k][c][0], z[k][c][1]);
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            double zz[D];
+            double zz[NZ];
 #pragma unroll
-            for (int c = 0; c < D; ++c) zz[c] = z[k][c][j];
-            if constexpr (GUIDED) {
+            for (int c = 0; c < NZ; ++c) zz[c] = z[k][c][j];
+            if constexpr (model_marginal<MODEL>::value) {
+                lw[k][j] = model_marginal_step<MODEL>(prm, false, xp[2 * k + j], zz, y, xn[j]);
+            } else if constexpr (GUIDED) {
                 lw[k][j] = model_guided<MODEL>(prm, prw, xp[2 * k + j], zz, y, xn[j]);
             } else {
                 model_transition<MODEL>(prm, xp[2 * k + j], zz, xn[j]);

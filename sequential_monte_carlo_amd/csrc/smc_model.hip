@@ -1,5 +1,5 @@
-// smc_model.hip -- instantiates the kernels of ONE model family (-DSMC_MODEL=1|2|3) for every
-// workgroup geometry.  Three objects are built in parallel and linked into libsmchip.so.
+// smc_model.hip -- instantiates the kernels of ONE model family (-DSMC_MODEL=1|2|3|4) for every
+// workgroup geometry.  One object per family, built in parallel and linked into libsmchip.so.
 #include "smc_launch.h"
 #include <cstdlib>
 
@@ -156,7 +156,9 @@ hipError_t SMC_LAUNCH_RESIDENT<SMC_MODEL>(const FilterView& v, int T, StepRec* r
     case 512: return resident_t<256, 1>(v, T, recs, s);
     case 1024: return np == 1 ? resident_t<512, 1>(v, T, recs, s) : np == 4 ? resident_t<128, 4>(v, T, recs, s) : resident_t<256, 2>(v, T, recs, s);
     case 2048: return np == 1 ? resident_t<1024, 1>(v, T, recs, s) : np == 4 ? resident_t<256, 4>(v, T, recs, s) : resident_t<512, 2>(v, T, recs, s);
-    case 4096: return np == 4 ? resident_t<512, 4>(v, T, recs, s) : resident_t<1024, 2>(v, T, recs, s);   // (1024 x 2 spills a little and still wins: +5-10 %, scripts/dbg/res4096.py)
+    case 4096:   // (four state rows: 4096 particles and their prefix sums exceed the 160 KiB of LDS - resident_supported says so first)
+        if constexpr (model_dim<SMC_MODEL>::value > 3) return hipErrorInvalidValue;
+        else return np == 4 ? resident_t<512, 4>(v, T, recs, s) : resident_t<1024, 2>(v, T, recs, s);   // (1024 x 2 spills a little and still wins: +5-10 %, scripts/dbg/res4096.py)
     case 8192:
         if constexpr (model_dim<SMC_MODEL>::value == 1) return resident_t<1024, 4>(v, T, recs, s);
         else return hipErrorInvalidValue;
@@ -188,8 +190,12 @@ hipError_t launch_summ_once<SMC_MODEL>(const FilterView& v, int cur, hipStream_t
     case 512: return summ_once_t<256, 1>(v, cur, s);
     case 1024: return summ_once_t<512, 1>(v, cur, s);
     case 2048: return summ_once_t<512, 2>(v, cur, s);
-    case 4096: return summ_once_t<512, 4>(v, cur, s);
-    case 8192: return summ_once_t<1024, 4>(v, cur, s);
+    case 4096:
+        if constexpr (model_dim<SMC_MODEL>::value > 3) return hipErrorInvalidValue;   // (does not fit LDS: the streaming kernels serve it)
+        else return summ_once_t<512, 4>(v, cur, s);
+    case 8192:
+        if constexpr (model_dim<SMC_MODEL>::value > 3) return hipErrorInvalidValue;
+        else return summ_once_t<1024, 4>(v, cur, s);
     }
     return hipErrorInvalidValue;
 }
@@ -203,7 +209,9 @@ hipError_t SMC_LAUNCH_WINDOW<SMC_MODEL>(const FilterView& v, int T, StepRec* rec
     case 512: return window_t<256, 1>(v, T, recs, t0, bin, bout, win, s);
     case 1024: return np == 1 ? window_t<512, 1>(v, T, recs, t0, bin, bout, win, s) : window_t<256, 2>(v, T, recs, t0, bin, bout, win, s);
     case 2048: return window_t<512, 2>(v, T, recs, t0, bin, bout, win, s);
-    case 4096: return np == 4 ? window_t<512, 4>(v, T, recs, t0, bin, bout, win, s) : window_t<1024, 2>(v, T, recs, t0, bin, bout, win, s);
+    case 4096:
+        if constexpr (model_dim<SMC_MODEL>::value > 3) return hipErrorInvalidValue;
+        else return np == 4 ? window_t<512, 4>(v, T, recs, t0, bin, bout, win, s) : window_t<1024, 2>(v, T, recs, t0, bin, bout, win, s);
     case 8192:
         if constexpr (model_dim<SMC_MODEL>::value == 1) return window_t<1024, 4>(v, T, recs, t0, bin, bout, win, s);
         else return hipErrorInvalidValue;

@@ -17,10 +17,12 @@ constexpr int SUMM_BINS = 1024, SUMM_CAND = 64;
 __host__ __device__ inline size_t summary_lds_words(int nq) {
     return (size_t)nq * 256 + 3 * QMAX + 2 * 3 * 16 + SUMM_BINS + (size_t)nq * SUMM_CAND * 2 + 2 * QMAX + 2 * 16;
 }
+// ... of a family with d state rows: the partial sums of the moments are [2][max(d, 3)][16], 32 more words per row beyond three
+__host__ __device__ inline size_t summary_lds_words(int nq, int d) { return summary_lds_words(nq) + (d > 3 ? (size_t)(d - 3) * 2 * 16 : 0); }
 template <int MODEL>
 __host__ __device__ inline size_t resident_lds_bytes(int seg, int threads, int np, int sum_nq = -1) {
     return (size_t)lds_padded_len(seg) * 8 * (1 + model_dim<MODEL>::value) + scr_words(threads, np) * 8 +
-           (sum_nq >= 0 ? summary_lds_words(sum_nq) * 8 : 0);
+           (sum_nq >= 0 ? summary_lds_words(sum_nq, model_dim<MODEL>::value) * 8 : 0);
 }
 
 // Per-step filtered summaries of ONE single-segment filter whose weights (inclusive fixed-point sums Cs) and states xs sit in
@@ -50,13 +52,14 @@ template <int THREADS, int NP, int D, bool UNW = false>
 __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, int64_t row, const uint64_t* Cs, const double* xs, int SEGP,
                                                    uint64_t S, uint64_t* sm) {
     constexpr int NW = THREADS / WAVE, NQ = 2 * NP;
+    constexpr int RD = D > 3 ? D : 3;   // rows of the moments' partial sums (summary_lds_words)
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     const int nq = v.sum_np;
     unsigned long long* hist = (unsigned long long*)sm;   // [nq][256]
     uint64_t* st_prefix = sm + (size_t)nq * 256;          // [QMAX]
     uint64_t* st_below = st_prefix + QMAX;                // [QMAX]
     uint64_t* st_target = st_below + QMAX;                // [QMAX]
-    double* red = (double*)(st_target + QMAX);            // [2][3][16]
+    double* red = (double*)(st_target + QMAX);            // [2][RD][16]
     uint64_t q[NQ];
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
@@ -92,7 +95,7 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
                 }
             }
             m = wave_sum_f64(m);
-            if (lane == 0) red[(0 * 3 + c) * 16 + wave] = m;
+            if (lane == 0) red[(0 * RD + c) * 16 + wave] = m;
         }
     }
     if (nq > 0 && S == 0) {   // collapsed filter: no quantile (workgroup-uniform)
@@ -109,7 +112,7 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
             key[2 * k + 1] = order_key(xv[2 * k + 1]);
         }
         // ---- the usual path: selection through equal-width value bins ----
-        unsigned long long* hbin = (unsigned long long*)(red + 2 * 3 * 16);   // [SUMM_BINS]
+        unsigned long long* hbin = (unsigned long long*)(red + 2 * RD * 16);   // [SUMM_BINS]
         uint64_t* cand = (uint64_t*)(hbin + SUMM_BINS);                        // [nq][SUMM_CAND][2]
         uint64_t* st_bin = cand + (size_t)nq * SUMM_CAND * 2;                  // [QMAX]
         unsigned* cnt = (unsigned*)(st_bin + QMAX);                            // [QMAX] (two per word)
@@ -271,7 +274,7 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
         for (int c = 0; c < D; ++c) {   // second pass, after the quantiles' selection: every thread sums the waves' partials in wave
                                         // order (the same mean everywhere), then w (x - mean)^2
             double a = 0.0;
-            for (int w = 0; w < NW; ++w) a += red[(0 * 3 + c) * 16 + w];
+            for (int w = 0; w < NW; ++w) a += red[(0 * RD + c) * 16 + w];
             if (UNW) a = a / (double)v.n;
             double m2 = 0.0;
 #pragma unroll
@@ -284,12 +287,12 @@ __device__ __forceinline__ void resident_summaries(const FilterView& v, int th, 
                 }
             }
             m2 = wave_sum_f64(m2);
-            if (lane == 0) red[(1 * 3 + c) * 16 + wave] = m2;
+            if (lane == 0) red[(1 * RD + c) * 16 + wave] = m2;
         }
         __syncthreads();
         if (tid < D) {
             double a = 0.0, b2 = 0.0;
-            for (int w = 0; w < NW; ++w) { a += red[(0 * 3 + tid) * 16 + w]; b2 += red[(1 * 3 + tid) * 16 + w]; }
+            for (int w = 0; w < NW; ++w) { a += red[(0 * RD + tid) * 16 + w]; b2 += red[(1 * RD + tid) * 16 + w]; }
             const double nan = bits2d(0x7ff8000000000000ULL);   // collapsed filter: no moments
             if (UNW) { a = a / (double)v.n; b2 = b2 / (double)(v.n - 1); }   // (n == 1: 0 / 0, NaN as Statistics.var)
             v.sum_m[(((size_t)row * 2 + 0) * D + tid) * v.ntheta + th] = S ? a : nan;
@@ -316,12 +319,12 @@ __global__ __launch_bounds__(THREADS) void k_summ_once(FilterView v, int cur) {
             *reinterpret_cast<double2*>(xs + c * SEGP + lds_pad(i0)) = *reinterpret_cast<const double2*>(v.x[cur] + ((size_t)c * v.ntheta + th) * v.npad + i0);
         *reinterpret_cast<ulonglong2*>(Cs + lds_pad(i0)) = *reinterpret_cast<const ulonglong2*>(v.C[cur] + (size_t)th * v.npad + i0);
     }
-    for (int i = tid; i < (int)summary_lds_words(v.sum_np); i += THREADS) sm[i] = 0;
+    for (int i = tid; i < (int)summary_lds_words(v.sum_np, D); i += THREADS) sm[i] = 0;
     __syncthreads();
     resident_summaries<THREADS, NP, D, UNW>(v, th, 0, Cs, xs, SEGP, v.segS[cur][th], sm);
 }
 template <int D>
-__host__ inline size_t summ_once_lds_bytes(int seg, int nq) { return (size_t)lds_padded_len(seg) * 8 * (1 + D) + summary_lds_words(nq) * 8; }
+__host__ inline size_t summ_once_lds_bytes(int seg, int nq) { return (size_t)lds_padded_len(seg) * 8 * (1 + D) + summary_lds_words(nq, D) * 8; }
 
 // Window mode (WIN): the same loop over the steps [t0, t0 + T) of filters that already exist (t0 >= 1): the state is
 // read from buffer `bin`, the T steps run in LDS, the state after them goes to buffer `bout`, and (logmu_t, ess_t) of
@@ -342,7 +345,9 @@ constexpr int resident_min_waves() {
 template <int MODEL, int THREADS, int NP, bool SYS = false, bool WIN = false, bool SUMM = false, bool UNW = false, bool GUIDED = false>
 __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())) void k_resident(FilterView v, int T, StepRec* recs /*[ntheta][T]*/, int t0, int bin, int bout,
                                                       double* win) {
-    constexpr int D = model_dim<MODEL>::value;
+    constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
+    constexpr bool MARG = model_marginal<MODEL>::value;   // marginal families: every step, the first too, sees y and returns the weight
+    static_assert(!(GUIDED && MARG), "marginal families have no proposals");
     constexpr int SEG = 2 * NP * THREADS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int SEGP = lds_padded_len(SEG);
@@ -407,7 +412,7 @@ __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())
     }
 
     if (SUMM) {   // the histograms start out empty (every selection leaves them empty again)
-        for (int i = tid; i < (int)summary_lds_words(v.sum_np); i += THREADS) sm[i] = 0;
+        for (int i = tid; i < (int)summary_lds_words(v.sum_np, D); i += THREADS) sm[i] = 0;
     }
     const bool ragged = (int)v.n != SEG;   // workgroup-uniform
     for (int t = t0; t < t0 + T; ++t) {
@@ -481,22 +486,23 @@ __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())
 #pragma unroll
             for (int i = 0; i < NQ; ++i) anc[i] = lds_pad(2 * (tid + (i >> 1) * THREADS) + (i & 1));
         }
-        double z[NP][D][2];
+        double z[NP][NZ][2];
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
             const uint32_t pg = (uint32_t)(tid + k * THREADS);
 #pragma unroll
-            for (int c = 0; c < D; ++c) box_muller(draw(v.seed, pg, stream, (uint32_t)t, SLOT_NORMAL0 + c), z[k][c][0], z[k][c][1]);
+            for (int c = 0; c < NZ; ++c) box_muller(draw(v.seed, pg, stream, (uint32_t)t, SLOT_NORMAL0 + c), z[k][c][0], z[k][c][1]);
         }
         if (t > 0) {
 #pragma unroll
             for (int k = 0; k < NP; ++k)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    double zz[D];
+                    double zz[NZ];
 #pragma unroll
-                    for (int c = 0; c < D; ++c) zz[c] = z[k][c][j];
-                    if constexpr (GUIDED) lw[k][j] = model_guided<MODEL>(prm, prw, xp[2 * k + j], zz, y, xn[k][j]);
+                    for (int c = 0; c < NZ; ++c) zz[c] = z[k][c][j];
+                    if constexpr (MARG) lw[k][j] = model_marginal_step<MODEL>(prm, false, xp[2 * k + j], zz, y, xn[k][j]);
+                    else if constexpr (GUIDED) lw[k][j] = model_guided<MODEL>(prm, prw, xp[2 * k + j], zz, y, xn[k][j]);
                     else model_transition<MODEL>(prm, xp[2 * k + j], zz, xn[k][j]);
                 }
         } else {
@@ -507,17 +513,20 @@ __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())
             for (int k = 0; k < NP; ++k)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    double zz[D];
+                    double zz[NZ];
 #pragma unroll
-                    for (int c = 0; c < D; ++c) zz[c] = z[k][c][j];
-                    model_initial<MODEL>(prm, zz, xn[k][j]);
+                    for (int c = 0; c < NZ; ++c) zz[c] = z[k][c][j];
+                    if constexpr (MARG) lw[k][j] = model_marginal_step<MODEL>(prm, true, xn[k][j], zz, y, xn[k][j]);
+                    else model_initial<MODEL>(prm, zz, xn[k][j]);
                 }
         }
-        if (!GUIDED || t == 0) {
+        if constexpr (!MARG) {
+            if (!GUIDED || t == 0) {
 #pragma unroll
-            for (int k = 0; k < NP; ++k)
+                for (int k = 0; k < NP; ++k)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) lw[k][j] = model_logobs<MODEL>(prm, xn[k][j], y);
+                    for (int j = 0; j < 2; ++j) lw[k][j] = model_logobs<MODEL>(prm, xn[k][j], y);
+            }
         }
         if (ragged) {   // n < SEG: the particles beyond n carry NaN weights and zero states (a real branch: the samplers' filters are full)
             asm volatile("; ragged");
@@ -637,7 +646,7 @@ __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())
 inline bool resident_supported(int model, int seg) {
     const int d = model_dim_rt(model);
     if (d < 0) return false;
-    return (size_t)lds_padded_len(seg) * 8 * (1 + d) + 2048 <= 160 * 1024;
+    return (size_t)lds_padded_len(seg) * 8 * (1 + d) + 2048 <= 160 * 1024;   // (four rows: 2048 particles, 4096 do not fit)
 }
 
 }  // namespace smc

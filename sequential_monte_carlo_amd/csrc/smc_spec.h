@@ -19,13 +19,14 @@ namespace smc {
 constexpr int MODEL_LG1D = 1;    // UnivariateLinearGaussian  ssm.jl:74-109
 constexpr int MODEL_SV1D = 2;    // stochastic volatility (SURVEY A7'; obs template ssm.jl:244-247)
 constexpr int MODEL_UCSV3D = 3;  // UCSV                      ssm.jl:215-263
+constexpr int MODEL_UCSV_RB = 4;  // UCSV with the trend integrated out: a scalar Kalman filter inside every particle ("marginal families")
 constexpr int NPARAM = 8;        // padded row length of raw / derived parameter tables
 
 constexpr int FIX_BITS = 48;     // q = rint(p * 2^(48 + k - kb)),  exp(logw) = p * 2^k
 constexpr int MAX_SEG = 8192;
 constexpr uint32_t SIM_STREAM = 0xFFFFFFFFu;
 constexpr uint32_t SLOT_RESAMPLE = 0u;   // within-segment pick of child j
-constexpr uint32_t SLOT_NORMAL0 = 1u;    // slots 1..d: state normals
+constexpr uint32_t SLOT_NORMAL0 = 1u;    // slots 1..nz: state normals (nz = model_nz: d, but 2 for UCSV_RB)
 constexpr uint32_t SLOT_OBS = 8u;        // simulate(): observation noise
 constexpr uint32_t SLOT_COUNT = 9u;      // segment pick of draw i (multi-segment filters)
 constexpr uint32_t SLOT_SYS = 10u;       // the one uniform of a systematic resampling step (opt-in)
@@ -46,10 +47,18 @@ constexpr double TWO_P48 = 0x1p+48;
 constexpr double TWO_M96 = 0x1p-96;
 constexpr double TWO_P64 = 0x1p+64;
 
-template <int MODEL> struct model_dim { static constexpr int value = (MODEL == MODEL_UCSV3D) ? 3 : 1; };
+template <int MODEL> struct model_dim { static constexpr int value = (MODEL == MODEL_UCSV_RB) ? 4 : (MODEL == MODEL_UCSV3D) ? 3 : 1; };
+// normals a particle consumes per step (Philox slots SLOT_NORMAL0 .. SLOT_NORMAL0 + nz - 1): one per state coordinate, except
+// for a marginal family, whose Kalman rows (m, P) are computed and not drawn
+template <int MODEL> struct model_nz { static constexpr int value = (MODEL == MODEL_UCSV_RB) ? 2 : model_dim<MODEL>::value; };
+// marginal families: the step sees y and returns the log-weight (model_marginal_step below); the first step too
+template <int MODEL> struct model_marginal { static constexpr bool value = MODEL == MODEL_UCSV_RB; };
+constexpr int MAX_DIM = 4;       // largest state dimension of a family
 
-SMC_HD int model_dim_rt(int id) { return id == MODEL_UCSV3D ? 3 : (id == MODEL_LG1D || id == MODEL_SV1D) ? 1 : -1; }
-SMC_HD int model_nraw_rt(int id) { return id == MODEL_LG1D ? 6 : id == MODEL_SV1D ? 3 : id == MODEL_UCSV3D ? 5 : -1; }
+SMC_HD int model_dim_rt(int id) { return id == MODEL_UCSV_RB ? 4 : id == MODEL_UCSV3D ? 3 : (id == MODEL_LG1D || id == MODEL_SV1D) ? 1 : -1; }
+SMC_HD int model_nraw_rt(int id) {
+    return id == MODEL_LG1D ? 6 : id == MODEL_SV1D ? 3 : (id == MODEL_UCSV3D || id == MODEL_UCSV_RB) ? 5 : -1;
+}
 
 // ---- bit casts -------------------------------------------------------------------------
 SMC_HD double bits2d(uint64_t b) { return __builtin_bit_cast(double, b); }
@@ -469,7 +478,7 @@ SMC_HD int ceil_log2_i64(int64_t n) {
 // ---- models ------------------------------------------------------------------------------
 // raw rows:  LG1D (A,B,Q,R,x0,sigma0)  Q,R,sigma0 VARIANCES (ssm.jl:93,102,108)
 //            SV1D (mu,rho,sigma)
-//            UCSV (gamma_eps,gamma_eta,x0,lse0,lsn0)  gammas STD-DEVs (ssm.jl:239-240)
+//            UCSV (gamma_eps,gamma_eta,x0,lse0,lsn0)  gammas STD-DEVs (ssm.jl:239-240); UCSV_RB: the same row
 // der rows:  LG1D (sQ,sR,s0,1/sR,c_obs)   SV1D (s0)
 struct Params {
     double raw[NPARAM];
@@ -637,6 +646,42 @@ SMC_HD double model_guided(const Params& p, const PropRow& q, const double* xp, 
         x[0] = xp[0] + z[0] * y;   // (no proposal for this family: never instantiated by the library)
         return bits2d(0x7ff8000000000000ULL);
     }
+}
+
+// ---- marginal families: the Rao-Blackwellised UCSV filter (MODEL_UCSV_RB) -------------------------------------------------
+// Given the two log-volatility paths of UCSV (ssm.jl:215-263) the pair (x, y) is linear-Gaussian with A = B = 1, so the trend
+// x is integrated out exactly by the scalar Kalman recursion (kalman_filter.jl:29-53) carried inside each particle.  State rows
+// (m, lse, lsn, P): rows 1, 2 are UCSV's log-volatilities, row 0 the filtered MEAN of the trend, row 3 its filtered VARIANCE -
+// always the posterior after the step's y.  The parameter row is UCSV's, with the reference's conventions: x moves with the
+// PREVIOUS lse, the gammas are standard deviations, x_1 ~ N(x0, exp(lse0 / 2)).
+// One step, given y (sp = the ancestor's state; `first`: t = 1, where sp is not read):
+//     (m, a, b, P-) = first ? (x0, lse0, lsn0, Q) : (sp[0], sp[1], sp[2], sp[3] + Q),   Q = sp_exp(a)
+//     s[1] = fma(g_eps, z[0], a);  s[2] = fma(g_eta, z[1], b)                           (UCSV's transition of the volatilities)
+//     R = sp_exp(s[2]);  S = P- + R;  iS = 1 / S;  e = y - m;  K = P- iS
+//     s[0] = fma(K, e, m);  s[3] = min(K R, P-)
+//     logw = fma(-0.5 (e iS), e, fma(-0.5, sp_log(S), -HALF_LOG2PI))                   (log N(y; m, S), as the guided UCSV step)
+// P' = P- R / S in PRODUCT form (never P- - K P-, which cancels and can turn negative): K <= 1 and R iS <= 1 as rounded values,
+// so 0 < P' <= R; the minimum with P- removes the last-place excess the two roundings of K R can leave when R >> P-.
+// Normals: TWO per particle and step, z[0] for lse (Philox slot SLOT_NORMAL0) and z[1] for lsn (slot SLOT_NORMAL0 + 1), each slot
+// a Box-Muller pair shared by the particles 2p, 2p + 1 like every state normal - one Philox call and one Box-Muller per particle
+// and step, none discarded.  (Bootstrap UCSV draws three: slots 1, 2, 3 = x, lse, lsn.)
+// model_obs_moments is UCSV's (mean = row 0, sd = exp(row 2 / 2)): the observation given the filtered mean.  No proposals.
+template <int MODEL>
+SMC_HD double model_marginal_step(const Params& p, bool first, const double* sp, const double* z, double y, double* s) {
+    static_assert(MODEL == MODEL_UCSV_RB, "marginal families");
+    const double m = first ? p.raw[2] : sp[0];
+    const double a = first ? p.raw[3] : sp[1];
+    const double b = first ? p.raw[4] : sp[2];
+    const double Q = sp_exp(a);
+    const double Pm = first ? Q : sp[3] + Q;
+    s[1] = fma(p.raw[0], z[0], a);
+    s[2] = fma(p.raw[1], z[1], b);
+    const double R = sp_exp(s[2]);
+    const double S = Pm + R, iS = 1.0 / S, e = y - m;
+    const double K = Pm * iS, KR = K * R;
+    s[0] = fma(K, e, m);
+    s[3] = KR < Pm ? KR : Pm;
+    return fma(-0.5 * (e * iS), e, fma(-0.5, sp_log(S), -HALF_LOG2PI));
 }
 
 // ---- PMMH rejuvenation of the samplers (src/smc_samplers.jl:103-146), one parameter particle ------------------

@@ -131,11 +131,11 @@ __device__ __forceinline__ void ms_for_each(const FilterView& v, int cur, int th
 template <bool UNW>
 __global__ __launch_bounds__(MS_STREAM) void k_ms_range(FilterView v, int cur, int d, MsScratch ms) {
     constexpr int NW = MS_STREAM / WAVE;
-    __shared__ double red[5][NW];
+    __shared__ double red[2 + MAX_DIM][NW];
     const int g = blockIdx.x, G = gridDim.x, th = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     const uint64_t Dtot = v.last_D[th];
     const double Dd = (double)Dtot * pow2i(v.SH - 48);
-    double vhi = -inf(), vlo = -inf(), mo[3] = {0.0, 0.0, 0.0};
+    double vhi = -inf(), vlo = -inf(), mo[MAX_DIM] = {};
     bool odd = false;
     const bool want_q = v.sum_np != 0, want_m = v.sum_mom != 0;
     ms_for_each(v, cur, th, v.sum_comp, [&](int64_t i, uint64_t q, double xq, const MsSeg& sg) {
@@ -186,11 +186,11 @@ __global__ __launch_bounds__(MS_STREAM) void k_ms_range(FilterView v, int cur, i
 template <bool UNW>
 __global__ __launch_bounds__(MS_STREAM) void k_ms_center(FilterView v, int cur, int d, MsScratch ms, const double* mean) {
     constexpr int NW = MS_STREAM / WAVE;
-    __shared__ double red[3][NW];
+    __shared__ double red[MAX_DIM][NW];
     const int g = blockIdx.x, G = gridDim.x, th = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     const uint64_t Dtot = v.last_D[th];
     const double Dd = (double)Dtot * pow2i(v.SH - 48);
-    double mu[3] = {0.0, 0.0, 0.0}, mo2[3] = {0.0, 0.0, 0.0};
+    double mu[MAX_DIM] = {}, mo2[MAX_DIM] = {};
     for (int c = 0; c < d; ++c) mu[c] = mean[(size_t)c * v.ntheta + th];
     ms_for_each(v, cur, th, 0, [&](int64_t i, uint64_t q, double x0, const MsSeg& sg) {
         const double w = UNW ? 1.0 : Dtot ? ((double)q * sg.sc) / Dd : 0.0;

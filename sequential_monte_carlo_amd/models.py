@@ -77,15 +77,26 @@ class UCSV(StateSpaceModel):
         return [self.gamma[0], self.gamma[1], self.x0, self.log_sigma0[0], self.log_sigma0[1]]
 
 
-def unobserved_components_stochastic_volatility(*, x0, gamma_eps, gamma_eta, log_sigma_eps, log_sigma_eta):
-    """unobserved_components_stochastic_volatility(;x0,γε,γη,log_σε,log_ση)   (ssm.jl:225-227)"""
-    return UCSV((gamma_eps, gamma_eta), x0, (log_sigma_eps, log_sigma_eta))
+class MarginalUCSV(UCSV):
+    """The same model with the trend integrated out (Rao-Blackwellised): given the two log-volatility paths (x, y) is
+    linear-Gaussian, so every particle carries (m, log s_eps, log s_eta, P) - the exact Kalman mean and variance of the trend
+    beside the volatilities it samples - and is weighted by the one-step predictive density N(y; m, P + exp(log s_eps_prev) +
+    exp(log s_eta)).  An unbiased estimator of the same p(y) as the UCSV filter in which the trend adds no Monte-Carlo variance; same parameter row.
+    Takes no proposal.  particles.trend_moments gives the trend's filtered mean and variance."""
+    model_id = _lib.MODEL_UCSV_RB
+    dim = 4
+
+
+def unobserved_components_stochastic_volatility(*, x0, gamma_eps, gamma_eta, log_sigma_eps, log_sigma_eta, marginal=False):
+    """unobserved_components_stochastic_volatility(;x0,γε,γη,log_σε,log_ση)   (ssm.jl:225-227)
+    marginal=True: the MarginalUCSV filter family for the same model"""
+    return (MarginalUCSV if marginal else UCSV)((gamma_eps, gamma_eta), x0, (log_sigma_eps, log_sigma_eta))
 
 
 def simulate(model, T, seed=1998):
     """simulate(rng, model, T) -> (x, y)   (ssm.jl:11-26).  x is [T] for scalar states, [T, d] otherwise.
     Host code (no GPU): the spec's Philox / Box-Muller stream keyed by `seed`."""
-    x, y = _lib.simulate(model.model_id, model.raw(), int(T), int(seed))
+    x, y = _lib.simulate(model.model_id, model.raw(), int(T), int(seed))    # (MarginalUCSV: UCSV's states, [T, 3])
     return (x[0] if model.dim == 1 else x.T.copy()), y
 
 

@@ -78,6 +78,17 @@ def proposal_rows(proposal, n_theta):
     raise ValueError("proposal must be None, OptimalProposal(), an AffineGaussianProposal or a list of them, one per model")
 
 
+def trend_moments(mean, var):
+    """(mean, variance) of the trend x under a MarginalUCSV filter from the moments of its state rows (m, lse, lsn, P): the mean
+    of m, and the variance of the mixture of the particles' Gaussians - between (the variance of m) plus within (the mean of
+    P).  `mean`, `var` are what Particles.moments() returns, or s["mean"][t], s["var"][t] of log_likelihood(..., moments=True):
+    the state rows on the LAST axis ([4], or [n_theta][4])."""
+    mean, var = np.asarray(mean, dtype=np.float64), np.asarray(var, dtype=np.float64)
+    if mean.shape != var.shape or mean.shape[-1] != 4:
+        raise ValueError("trend_moments takes the moments of the four state rows of a MarginalUCSV filter")
+    return mean[..., 0], var[..., 0] + mean[..., 3]
+
+
 class _Filters:
     """Device state shared by the Particles / Weights views of one bootstrap_filter call."""
 

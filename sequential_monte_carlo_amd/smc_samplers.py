@@ -53,7 +53,8 @@ class ThetaMap:
     """smc.model(theta) in a form the device can evaluate: parameter row k of the model family `model_id` is
     theta[raw_from[k]] when raw_from[k] >= 0, else the constant raw_const[k].
     README.md:75-79 (LinearGaussian(theta1, 1.0, theta2, theta3, 0.0)):  ThetaMap(LG, [0,-1,1,2,-1,-1], [0,1,0,0,0,1]);
-    examples/inflation_example.jl:227-230 (UCSV(theta1, theta2, (theta3, theta4))):  ThetaMap(UCSV, [0,0,1,2,3], [0]*5)."""
+    examples/inflation_example.jl:227-230 (UCSV(theta1, theta2, (theta3, theta4))):  ThetaMap(UCSV, [0,0,1,2,3], [0]*5);
+    the same map with MODEL_UCSV_RB runs the Rao-Blackwellised filter (models.MarginalUCSV) on the same parameter rows."""
 
     def __init__(self, model_id, raw_from, raw_const):
         self.model_id = int(model_id)
@@ -362,7 +363,7 @@ def estimated_trend(smc):
     mid, rows = _rows(smc._models(smc.theta[smc.lo:smc.hi]))
     if mid == _lib.MODEL_LG1D:
         obs = rows[:, 1] * np.asarray(mean)[0]
-    elif mid == _lib.MODEL_UCSV3D:
+    elif mid in (_lib.MODEL_UCSV3D, _lib.MODEL_UCSV_RB):    # (the marginal family: row 0 is the trend's filtered mean)
         obs = np.asarray(mean)[0]
     else:
         obs = np.zeros(rows.shape[0])
