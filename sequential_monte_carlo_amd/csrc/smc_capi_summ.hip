@@ -1,0 +1,213 @@
+// smc_capi_summ.hip -- summaries of the particle clouds: quantiles and moments per step inside the multi-step calls
+// (smc_set_summaries / smc_get_summaries) and of the current state (smc_get_moments / smc_get_quantiles).
+// The only translation unit that includes smc_summ_kernels.h.
+#include "smc_host.h"
+#include "smc_summ_kernels.h"
+
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+
+using namespace smc;
+
+// ---- per-step summaries inside the multi-step calls ------------------------------------------------------------------
+// whether the LDS-resident kernels have room for the summaries' histograms next to the filter's state (160 KiB per workgroup)
+bool summaries_fit_lds(const smc_filter_s* h) {
+    return (size_t)lds_padded_len(h->v.seg) * 8 * (size_t)(1 + h->d) + scr_words(1024, 4) * 8 + summary_lds_words(h->summ.np, h->d) * 8 <= (size_t)160 * 1024;
+}
+int ensure_summaries(smc_handle h, int64_t T) {
+    if (T > h->summ.cap) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        (void)hipFree(h->summ.d_q); (void)hipFree(h->summ.d_m);
+        h->summ.d_q = h->summ.d_m = nullptr;
+        h->summ.cap = 0;
+        HIPCHK(dalloc(&h->summ.d_q, (size_t)T * h->v.ntheta * QMAX));
+        HIPCHK(dalloc(&h->summ.d_m, (size_t)T * 2 * h->d * h->v.ntheta));
+        h->summ.cap = T;
+    }
+    return SMC_OK;
+}
+// what the launches of a multi-step call need to know about the summaries (the scope of the call resets it)
+void view_summaries(smc_handle h) {
+    FilterView& v = h->v;
+    v.sum_np = h->summ.np; v.sum_comp = h->summ.comp; v.sum_mom = h->summ.mom;
+    for (int j = 0; j < QMAX; ++j) v.sum_p64[j] = h->summ.mode == SMC_SUMM_UNWEIGHTED ? d2bits(h->summ.p[j]) : h->summ.p64[j];
+    v.sum_q = h->summ.d_q; v.sum_m = h->summ.d_m;
+}
+// the levels of a request in the form the kernels of the handle's mode read (FilterView::sum_p64)
+static void level_words(const smc_filter_s* h, const double* p, int np, uint64_t* out) {
+    for (int j = 0; j < QMAX; ++j) out[j] = j >= np ? 0 : h->summ.mode == SMC_SUMM_UNWEIGHTED ? d2bits(q7_level(p[j])) : prob_to_u64(p[j]);
+}
+// The summaries of the CURRENT weights of filters of any size, enqueued on the handle's stream behind the launch that produced
+// them (no host synchronisation): smc_summ_kernels.h.  q_out [ntheta][np], mean / var [d][ntheta] are device pointers.  The
+// weights must have been emitted (last_K, last_D describe them).
+static int ensure_ms(smc_handle h) {
+    const size_t nth = (size_t)h->v.ntheta, words = ms_words(nth, (size_t)h->v.nseg, (size_t)h->d);
+    if (!h->summ.d_ms) {
+        HIPCHK(hipMalloc((void**)&h->summ.d_ms, (words + nth * QMAX) * 8));
+        HIPCHK(hipMemsetAsync(h->summ.d_ms, 0, (words + nth * QMAX) * 8, h->stream));
+    }
+    return SMC_OK;
+}
+template <bool UNW>
+static int enqueue_ms_t(smc_handle h, int component, int np, const uint64_t* p64, bool mom, double* q_out, double* mean, double* var) {
+    const size_t nth = (size_t)h->v.ntheta;
+    int rc = ensure_ms(h);
+    if (rc) return rc;
+    const MsScratch ms = ms_carve(h->summ.d_ms, nth, (size_t)h->v.nseg, (size_t)h->d);
+    FilterView v = h->v;
+    v.sum_np = np; v.sum_comp = np > 0 ? component : 0; v.sum_mom = mom ? 1 : 0;
+    for (int j = 0; j < QMAX; ++j) v.sum_p64[j] = j < np ? p64[j] : 0;
+    // streaming kernels: workgroups of 1024 threads over consecutive segments - about 256 workgroups in all for the passes that
+    // only read, about 64 for the histogram (every workgroup flushes its occupied bins with device-scope atomics)
+    auto groups = [&](int want) {
+        int g = want / h->v.ntheta;
+        g = g < 1 ? 1 : g;
+        return g > h->v.nseg ? h->v.nseg : g;
+    };
+    const int g_read = groups(256), g_hist = groups(64);
+    hipLaunchKernelGGL(k_ms_range<UNW>, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, h->d, ms);
+    if (np > 0) hipLaunchKernelGGL(k_ms_hist<UNW>, dim3(g_hist, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, g_read, ms);
+    hipLaunchKernelGGL(k_ms_pick<UNW>, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, h->d, g_read, ms, q_out, mean);
+    if (mom) {   // the variance centred on that mean: a second read of the cloud
+        hipLaunchKernelGGL(k_ms_center<UNW>, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, h->d, ms, (const double*)mean);
+        hipLaunchKernelGGL(k_ms_var<UNW>, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, h->d, g_read, ms, var);
+    }
+    int64_t two_level = MS_TWO_LEVEL;
+    if (const char* e = getenv("SMC_MS_TWO_LEVEL")) two_level = atoll(e);   // tuning / test knob: results do not depend on it
+    if (np > 0 && h->v.n > two_level) {   // big filters: the chosen bins cut a second time before the candidates are collected
+        hipLaunchKernelGGL(k_ms_hist2<UNW>, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, ms);
+        hipLaunchKernelGGL(k_ms_pick2, dim3(np, h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, ms);
+        hipLaunchKernelGGL((k_ms_collect<true, UNW>), dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, ms);
+    } else if (np > 0) {
+        hipLaunchKernelGGL((k_ms_collect<false, UNW>), dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, ms);
+    }
+    if (np > 0) {
+        hipLaunchKernelGGL(k_ms_select<UNW>, dim3(np, h->v.ntheta), dim3(MS_SEL_THREADS), 0, h->stream, v, h->cur, ms, q_out);
+        if (UNW) {   // the neighbour x_(j+1) of every level, then the interpolation
+            hipLaunchKernelGGL(k_ms_succ, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, ms);
+            hipLaunchKernelGGL(k_ms_interp, dim3(h->v.ntheta), dim3(WAVE), 0, h->stream, v, ms, q_out);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return SMC_OK;
+}
+static int enqueue_ms(smc_handle h, int component, int np, const uint64_t* p64, bool mom, double* q_out, double* mean, double* var) {
+    return h->summ.mode == SMC_SUMM_UNWEIGHTED ? enqueue_ms_t<true>(h, component, np, p64, mom, q_out, mean, var)
+                                              : enqueue_ms_t<false>(h, component, np, p64, mom, q_out, mean, var);
+}
+// ... into row `row` of the traces of a multi-step call
+int enqueue_step_summaries(smc_handle h, int64_t row) {
+    const size_t nth = (size_t)h->v.ntheta, nout = (size_t)h->d * nth;
+    double* mbase = h->summ.d_m + (size_t)row * 2 * nout;
+    uint64_t pw[QMAX];
+    level_words(h, h->summ.p, h->summ.np, pw);
+    return enqueue_ms(h, h->summ.comp, h->summ.np, pw, h->summ.mom != 0, h->summ.d_q + (size_t)row * nth * h->summ.np, mbase, mbase + nout);
+}
+
+extern "C" int smc_set_summaries(smc_handle h, int component, const double* p, int np, int moments) {
+    if (!h) return fail(SMC_EINVAL, "smc_set_summaries: NULL handle");
+    if (np < 0 || np > QMAX || (np > 0 && !p)) return fail(SMC_EINVAL, "smc_set_summaries: 0 <= np <= 8");
+    if (np > 0 && (component < 0 || component >= h->d)) return fail(SMC_EINVAL, "smc_set_summaries: component out of range");
+    h->summ.np = np; h->summ.comp = np > 0 ? component : 0; h->summ.mom = moments ? 1 : 0;
+    for (int j = 0; j < QMAX; ++j) { h->summ.p64[j] = j < np ? prob_to_u64(p[j]) : 0; h->summ.p[j] = j < np ? q7_level(p[j]) : 0.0; }
+    h->summ.T = 0;
+    return SMC_OK;
+}
+
+extern "C" int smc_set_summary_mode(smc_handle h, int mode) {
+    if (!h) return fail(SMC_EINVAL, "smc_set_summary_mode: NULL handle");
+    if (mode != SMC_SUMM_WEIGHTED && mode != SMC_SUMM_UNWEIGHTED) return fail(SMC_EINVAL, "smc_set_summary_mode: unknown mode");
+    h->summ.mode = mode;
+    h->v.sum_unw = mode == SMC_SUMM_UNWEIGHTED ? 1 : 0;
+    h->summ.T = 0;   // (rows recorded in the other mode are not handed out as this one's)
+    return SMC_OK;
+}
+
+extern "C" int smc_get_summaries(smc_handle h, int64_t T, double* q, double* mean, double* var) {
+    if (!h) return fail(SMC_EINVAL, "smc_get_summaries: NULL handle");
+    if (T < 1 || T > h->summ.T) return fail(SMC_ESTATE, "smc_get_summaries: more steps than the last multi-step call recorded");
+    if ((q && h->summ.np == 0) || ((mean || var) && !h->summ.mom)) return fail(SMC_ESTATE, "smc_get_summaries: not recorded (smc_set_summaries)");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t nth = (size_t)h->v.ntheta, nout = (size_t)h->d * nth;
+    if (q) HIPCHK(hipMemcpy(q, h->summ.d_q, (size_t)T * nth * h->summ.np * 8, hipMemcpyDeviceToHost));
+    if (mean) HIPCHK(hipMemcpy2D(mean, nout * 8, h->summ.d_m, 2 * nout * 8, nout * 8, (size_t)T, hipMemcpyDeviceToHost));
+    if (var) HIPCHK(hipMemcpy2D(var, nout * 8, h->summ.d_m + nout, 2 * nout * 8, nout * 8, (size_t)T, hipMemcpyDeviceToHost));
+    if (!h->summ.skip.empty()) {   // filters the call left out have no summaries: NaN (the device rows hold whatever was there)
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (size_t m = 0; m < nth; ++m) {
+            if (!h->summ.skip[m]) continue;
+            for (int64_t t = 0; t < T; ++t) {
+                if (q) for (int j = 0; j < h->summ.np; ++j) q[((size_t)t * nth + m) * h->summ.np + j] = nan;
+                for (int c = 0; c < h->d; ++c) {
+                    if (mean) mean[(size_t)t * nout + (size_t)c * nth + m] = nan;
+                    if (var) var[(size_t)t * nout + (size_t)c * nth + m] = nan;
+                }
+            }
+        }
+    }
+    return SMC_OK;
+}
+
+// Quantiles and / or moments of the CURRENT state of single-segment filters in ONE launch that writes to pinned host memory
+// (the README loop asks for them after every bootstrap_filter!: one launch and one synchronisation per request instead of
+// sixteen launches and a copy).  done = false: no such kernel for this handle (several segments, or the state does not fit LDS).
+static int summaries_once(smc_handle h, int component, const double* p, int np, bool mom, double* q_out, double* mean, double* var, bool& done) {
+    done = false;
+    if (h->v.nseg != 1) return SMC_OK;
+    const size_t nth = (size_t)h->v.ntheta, nout = (size_t)h->d * nth;
+    if (!h->summ.h_once) HIPCHK(hipHostMalloc((void**)&h->summ.h_once, ((size_t)QMAX * nth + 2 * nout) * 8, hipHostMallocDefault));
+    FilterView v = h->v;
+    v.sum_np = np; v.sum_comp = component; v.sum_mom = mom ? 1 : 0;
+    level_words(h, p, np, v.sum_p64);
+    v.sum_q = h->summ.h_once; v.sum_m = h->summ.h_once + (size_t)QMAX * nth;
+    const hipError_t e = by_model(h->model, [&](auto M) { return launch_summ_once<decltype(M)::value>(v, h->cur, h->stream); });
+    if (e == hipErrorInvalidValue) return SMC_OK;
+    HIPCHK(e);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (q_out) memcpy(q_out, h->summ.h_once, nth * np * 8);
+    if (mean) memcpy(mean, h->summ.h_once + (size_t)QMAX * nth, nout * 8);
+    if (var) memcpy(var, h->summ.h_once + (size_t)QMAX * nth + nout, nout * 8);
+    done = true;
+    return SMC_OK;
+}
+
+extern "C" int smc_get_moments(smc_handle h, double* mean, double* var) {
+    if (!h || !mean || !var) return fail(SMC_EINVAL, "smc_get_moments: NULL argument");
+    if (!h->inited) return fail(SMC_ESTATE, "smc_get_moments: filter not initialised");
+    HIPCHK(hipSetDevice(h->device));
+    int rc = emit_if_needed(h);
+    if (rc) return rc;
+    bool done = false;
+    if ((rc = summaries_once(h, 0, nullptr, 0, true, nullptr, mean, var, done)) || done) return rc;
+    const size_t nout = (size_t)h->d * h->v.ntheta;
+    if (!h->d_wdense) HIPCHK(dalloc(&h->d_wdense, (size_t)h->v.ntheta * h->v.n + 2 * nout));
+    double *d_mean = h->d_wdense, *d_var = h->d_wdense + nout;
+    if ((rc = enqueue_ms(h, 0, 0, nullptr, true, nullptr, d_mean, d_var))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(mean, d_mean, nout * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(var, d_var, nout * 8, hipMemcpyDeviceToHost));
+    return SMC_OK;
+}
+
+extern "C" int smc_get_quantiles(smc_handle h, int component, const double* p, int np, double* out) {
+    if (!h || !p || !out) return fail(SMC_EINVAL, "smc_get_quantiles: NULL argument");
+    if (!h->inited) return fail(SMC_ESTATE, "smc_get_quantiles: filter not initialised");
+    if (component < 0 || component >= h->d) return fail(SMC_EINVAL, "smc_get_quantiles: component out of range");
+    if (np < 1 || np > QMAX) return fail(SMC_EINVAL, "smc_get_quantiles: 1 <= np <= 8");
+    HIPCHK(hipSetDevice(h->device));
+    int rc = emit_if_needed(h);
+    if (rc) return rc;
+    bool done = false;
+    if ((rc = summaries_once(h, component, p, np, false, out, nullptr, nullptr, done)) || done) return rc;
+    const size_t nth = (size_t)h->v.ntheta, nst = nth * np;
+    uint64_t hp[QMAX];
+    level_words(h, p, np, hp);
+    if ((rc = ensure_ms(h))) return rc;
+    double* d_out = (double*)(h->summ.d_ms + ms_words(nth, (size_t)h->v.nseg, (size_t)h->d));
+    if ((rc = enqueue_ms(h, component, np, hp, false, d_out, nullptr, nullptr))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out, d_out, nst * 8, hipMemcpyDeviceToHost));
+    return SMC_OK;
+}

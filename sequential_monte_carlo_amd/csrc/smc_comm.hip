@@ -7,16 +7,13 @@
 //                           ranks, pack -> grouped ncclSend/ncclRecv (an all-to-all) -> unpack
 // RCCL is opened with dlopen at the first smc_comm_* call: libsmchip.so itself links only libamdhip64, loads on a
 // box without RCCL, and shares the copy a host process may already have loaded (PyTorch bundles its own).
-#include "../../include/smc_hip.h"
-#include <hip/hip_runtime.h>
+#include "smc_host.h"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 
 #include <cstring>
 #include <string>
 #include <vector>
-
-extern "C" int smc_set_error_(int code, const char* msg);   // smc_capi.hip: thread-local message behind smc_last_error()
 
 namespace {
 
@@ -41,12 +38,12 @@ int load_rccl() {
         lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
         if (lib) break;
     }
-    if (!lib) return smc_set_error_(SMC_EHIP, "smc_comm: librccl.so not found (dlopen)");
+    if (!lib) return fail(SMC_EHIP, "smc_comm: librccl.so not found (dlopen)");
     Rccl r;
     r.lib = lib;
 #define SYM(field, name)                                                                      \
     *(void**)(&r.field) = dlsym(lib, name);                                                   \
-    if (!r.field) return smc_set_error_(SMC_EHIP, "smc_comm: symbol " name " missing in librccl.so");
+    if (!r.field) return fail(SMC_EHIP, "smc_comm: symbol " name " missing in librccl.so");
     SYM(GetUniqueId, "ncclGetUniqueId")
     SYM(CommInitRank, "ncclCommInitRank")
     SYM(CommDestroy, "ncclCommDestroy")
@@ -75,20 +72,15 @@ struct smc_comm_s {
     size_t xcap = 0;            // bytes
 };
 
-#define HIPC(expr)                                                                                   \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess) return smc_set_error_(SMC_EHIP, (std::string(#expr) + ": " + hipGetErrorString(_e)).c_str()); \
-    } while (0)
 #define NCCLC(expr)                                                                                  \
     do {                                                                                             \
         ncclResult_t _r = (expr);                                                                    \
-        if (_r != ncclSuccess) return smc_set_error_(SMC_EHIP, (std::string(#expr) + ": " + g_rccl.GetErrorString(_r)).c_str()); \
+        if (_r != ncclSuccess) return fail(SMC_EHIP, std::string(#expr) + ": " + g_rccl.GetErrorString(_r)); \
     } while (0)
 
 extern "C" int smc_comm_unique_id(void* id) {
     static_assert(sizeof(ncclUniqueId) == SMC_COMM_ID_BYTES, "ncclUniqueId size");
-    if (!id) return smc_set_error_(SMC_EINVAL, "smc_comm_unique_id: NULL argument");
+    if (!id) return fail(SMC_EINVAL, "smc_comm_unique_id: NULL argument");
     int rc = load_rccl();
     if (rc) return rc;
     ncclUniqueId u;
@@ -98,11 +90,11 @@ extern "C" int smc_comm_unique_id(void* id) {
 }
 
 extern "C" int smc_comm_create(const void* id, int rank, int world, int device, smc_comm* out) {
-    if (!id || !out || world < 1 || rank < 0 || rank >= world) return smc_set_error_(SMC_EINVAL, "smc_comm_create: bad argument");
+    if (!id || !out || world < 1 || rank < 0 || rank >= world) return fail(SMC_EINVAL, "smc_comm_create: bad argument");
     *out = nullptr;
     int rc = load_rccl();
     if (rc) return rc;
-    HIPC(hipSetDevice(device));
+    HIPCHK(hipSetDevice(device));
     smc_comm_s* c = new smc_comm_s();
     c->rank = rank; c->world = world; c->device = device;
     ncclUniqueId u;
@@ -110,13 +102,13 @@ extern "C" int smc_comm_create(const void* id, int rank, int world, int device, 
     ncclResult_t r = g_rccl.CommInitRank(&c->comm, world, u, rank);
     if (r != ncclSuccess) {
         delete c;
-        return smc_set_error_(SMC_EHIP, (std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(r)).c_str());
+        return fail(SMC_EHIP, std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(r));
     }
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         g_rccl.CommDestroy(c->comm);
         delete c;
-        return smc_set_error_(SMC_EHIP, hipGetErrorString(e));
+        return fail(SMC_EHIP, hipGetErrorString(e));
     }
     *out = c;
     return SMC_OK;
@@ -133,7 +125,7 @@ extern "C" int smc_comm_destroy(smc_comm c) {
 }
 
 extern "C" int smc_comm_rank(smc_comm c, int* rank, int* world) {
-    if (!c) return smc_set_error_(SMC_EINVAL, "smc_comm_rank: NULL communicator");
+    if (!c) return fail(SMC_EINVAL, "smc_comm_rank: NULL communicator");
     if (rank) *rank = c->rank;
     if (world) *world = c->world;
     return SMC_OK;
@@ -141,25 +133,25 @@ extern "C" int smc_comm_rank(smc_comm c, int* rank, int* world) {
 
 static int ensure_staging(smc_comm c, size_t n) {
     if (n <= c->cap) return SMC_OK;
-    HIPC(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     (void)hipFree(c->d_send); (void)hipFree(c->d_recv);
     c->d_send = c->d_recv = nullptr; c->cap = 0;
-    HIPC(hipMalloc((void**)&c->d_send, n * 8));
-    HIPC(hipMalloc((void**)&c->d_recv, n * 8 * (size_t)c->world));
+    HIPCHK(hipMalloc((void**)&c->d_send, n * 8));
+    HIPCHK(hipMalloc((void**)&c->d_recv, n * 8 * (size_t)c->world));
     c->cap = n;
     return SMC_OK;
 }
 
 // every rank contributes n doubles; all [world][n] come back on every rank (rank order)
 extern "C" int smc_comm_all_gather(smc_comm c, const double* local, int64_t n, double* all) {
-    if (!c || !local || !all || n <= 0) return smc_set_error_(SMC_EINVAL, "smc_comm_all_gather: bad argument");
-    HIPC(hipSetDevice(c->device));
+    if (!c || !local || !all || n <= 0) return fail(SMC_EINVAL, "smc_comm_all_gather: bad argument");
+    HIPCHK(hipSetDevice(c->device));
     int rc = ensure_staging(c, (size_t)n);
     if (rc) return rc;
-    HIPC(hipMemcpyAsync(c->d_send, local, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_send, local, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     NCCLC(g_rccl.AllGather(c->d_send, c->d_recv, (size_t)n, ncclFloat64, c->comm, c->stream));
-    HIPC(hipMemcpyAsync(all, c->d_recv, (size_t)n * 8 * (size_t)c->world, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(all, c->d_recv, (size_t)n * 8 * (size_t)c->world, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return SMC_OK;
 }
 
@@ -169,7 +161,7 @@ extern "C" int smc_comm_all_gather(smc_comm c, const double* local, int64_t n, d
 // segment records travel (32 bytes per SMC_OUTER_SEG entries); otherwise the slices themselves.
 extern "C" int smc_outer_reweight(smc_comm c, const double* logw_local, int64_t n_local, double* logw_all, double* w_all,
                                   double* logmu, double* ess) {
-    if (!c || !logw_local || n_local <= 0) return smc_set_error_(SMC_EINVAL, "smc_outer_reweight: bad argument");
+    if (!c || !logw_local || n_local <= 0) return fail(SMC_EINVAL, "smc_outer_reweight: bad argument");
     const int64_t n = n_local * c->world;
     if (!w_all && !logw_all && n_local % SMC_OUTER_SEG == 0) {
         const int64_t ns = n_local / SMC_OUTER_SEG;
@@ -196,7 +188,7 @@ extern "C" int smc_outer_reweight(smc_comm c, const double* logw_local, int64_t 
 extern "C" int smc_comm_plan_exchange(const int32_t* a, int64_t M, int rank, int world, int32_t* send_idx, int64_t* send_cnt,
                                       int64_t* n_send, int32_t* dest_idx, int64_t* recv_cnt) {
     if (!a || !send_idx || !send_cnt || !n_send || !dest_idx || !recv_cnt || M <= 0 || world < 1 || rank < 0 || rank >= world || M % world)
-        return smc_set_error_(SMC_EINVAL, "smc_comm_plan_exchange: bad argument");
+        return fail(SMC_EINVAL, "smc_comm_plan_exchange: bad argument");
     const int64_t per = M / world, lo = rank * per;
     int64_t ns = 0, nr = 0;
     for (int r = 0; r < world; ++r) {
@@ -216,12 +208,12 @@ extern "C" int smc_comm_plan_exchange(const int32_t* a, int64_t M, int rank, int
 // resample!(smc) with the filters of `h` sharded over the ranks: a[m] (m = 0..M-1, GLOBAL indices, the same vector on
 // every rank) is the ancestor of global slot m; rank r holds the slots [r M/world, (r+1) M/world).  Value copies.
 extern "C" int smc_comm_exchange_slots(smc_comm c, smc_handle h, const int32_t* a, int64_t M) {
-    if (!c || !h || !a || M <= 0 || M % c->world) return smc_set_error_(SMC_EINVAL, "smc_comm_exchange_slots: bad argument");
-    HIPC(hipSetDevice(c->device));
+    if (!c || !h || !a || M <= 0 || M % c->world) return fail(SMC_EINVAL, "smc_comm_exchange_slots: bad argument");
+    HIPCHK(hipSetDevice(c->device));
     const int W = c->world;
     const int64_t per = M / W;
     for (int64_t m = 0; m < M; ++m)
-        if (a[m] < 0 || a[m] >= M) return smc_set_error_(SMC_EINVAL, "smc_comm_exchange_slots: ancestor out of range");
+        if (a[m] < 0 || a[m] >= M) return fail(SMC_EINVAL, "smc_comm_exchange_slots: ancestor out of range");
     int64_t sb = 0;
     int rc = smc_slot_bytes(h, &sb);
     if (rc) return rc;
@@ -234,11 +226,11 @@ extern "C" int smc_comm_exchange_slots(smc_comm c, smc_handle h, const int32_t* 
     const size_t ns = send_idx.size(), nr = dest_idx.size();   // nr == per
     const size_t need = (ns > nr ? ns : nr) * (size_t)sb;
     if (need > c->xcap) {
-        HIPC(hipStreamSynchronize(c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
         (void)hipFree(c->d_xs); (void)hipFree(c->d_xr);
         c->d_xs = c->d_xr = nullptr; c->xcap = 0;
-        HIPC(hipMalloc(&c->d_xs, need));
-        HIPC(hipMalloc(&c->d_xr, need));
+        HIPCHK(hipMalloc(&c->d_xs, need));
+        HIPCHK(hipMalloc(&c->d_xr, need));
         c->xcap = need;
     }
     if (ns && (rc = smc_pack_slots(h, send_idx.data(), (int64_t)ns, c->d_xs))) return rc;   // synchronises the handle's stream
@@ -260,10 +252,10 @@ extern "C" int smc_comm_exchange_slots(smc_comm c, smc_handle h, const int32_t* 
     }
     if (first != ncclSuccess) {
         (void)hipStreamSynchronize(c->stream);
-        return smc_set_error_(SMC_EHIP, (std::string("smc_comm_exchange_slots: ") + where + ": " + g_rccl.GetErrorString(first) +
-                                         " (the filter slots of the handle are undefined now)").c_str());
+        return fail(SMC_EHIP, std::string("smc_comm_exchange_slots: ") + where + ": " + g_rccl.GetErrorString(first) +
+                                  " (the filter slots of the handle are undefined now)");
     }
-    HIPC(hipStreamSynchronize(c->stream));     // the unpack kernel runs on the handle's own stream
+    HIPCHK(hipStreamSynchronize(c->stream));     // the unpack kernel runs on the handle's own stream
     if (nr && (rc = smc_unpack_slots(h, dest_idx.data(), (int64_t)nr, c->d_xr))) return rc;
     return SMC_OK;
 }

@@ -1,0 +1,151 @@
+// smc_host.h -- what the host-side translation units of libsmchip.so share: the error string behind smc_last_error(), HIPCHK,
+// the filter handle, and the few helpers that cross files.  Internal: not installed, not part of the ABI (include/smc_hip.h).
+// The entry points on a handle: smc_capi.hip (core), smc_capi_series.hip, smc_capi_summ.hip, smc_capi_pmmh.hip,
+// smc_capi_slots.hip; without one: smc_util.hip.
+#pragma once
+#include "../../include/smc_hip.h"
+#include "smc_launch.h"
+
+#include <string>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+
+// ---- errors --------------------------------------------------------------------------------------
+// stores msg as the calling thread's smc_last_error() and returns code (smc_capi.hip)
+int fail(int code, const std::string& msg);
+#define HIPCHK(expr)                                                                                          \
+    do {                                                                                                      \
+        hipError_t _e = (expr);                                                                               \
+        if (_e != hipSuccess)                                                                                 \
+            return fail(SMC_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" +      \
+                                      std::to_string(__LINE__) + ")");                                        \
+    } while (0)
+
+template <class T>
+inline hipError_t dalloc(T** p, size_t count) {
+    return hipMalloc((void**)p, count * sizeof(T) > 0 ? count * sizeof(T) : 16);
+}
+
+// ---- the filter handle ---------------------------------------------------------------------------
+namespace smc {
+// device block of the PMMH rejuvenation (smc_pmmh_kernels.h); the handle of the proposal filters owns it
+struct PmmhDev {
+    double* theta;        // [ntheta][MAX_DTHETA] current parameter particles
+    double* prop;         // [ntheta][MAX_DTHETA] proposals of this chain position
+    double* logZ;         // [ntheta] log-likelihood estimates of the current particles
+    double* lp;           // [ntheta][2] log prior of (proposal, current)
+    unsigned char* skip;  // [ntheta] proposal outside the support: its filter is not run
+    unsigned char* mask;  // [ntheta] accepted at this chain position
+    unsigned char* any;   // [ntheta] accepted at least once in this rejuvenation (acc_array, :135)
+    unsigned long long* nrun;   // [1] proposal filters executed so far
+    double* chol;         // [d][d] lower Cholesky factor of the random-walk covariance (:95-100)
+    int32_t* order;       // [ntheta] the filters of this chain position, those to run first (FilterView::order)
+    int32_t* counts;      // [2] how many are to run / skipped (filled by k_pmmh_propose, cleared by k_pmmh_accept)
+};
+}  // namespace smc
+
+struct smc_filter_s {
+    int model = 0, d = 0, device = 0;
+    uint32_t flags = 0;
+    smc::FilterView v{};
+    smc::Params* d_params = nullptr;
+    uint32_t* d_stream = nullptr;
+    int32_t* d_perm = nullptr;
+    double* d_logZ_tmp = nullptr;
+    double* d_y = nullptr;
+    int64_t ycap = 0;
+    double *d_tr_logmu = nullptr, *d_tr_ess = nullptr;
+    int64_t trcap = 0;
+    double* d_wdense = nullptr;
+    smc::StepRec* d_recs = nullptr;
+    int64_t reccap = 0;
+    double* h_pin = nullptr;                   // pinned host mirror [4][ntheta]: logZ | last_logmu | last_ess | ticket of the step API
+    uint32_t seq = 0;                          // last ticket handed to a step-API launch
+    size_t slab_bytes = 0, pin_bytes = 0;
+    char* d_slab = nullptr;                    // ONE allocation behind x, C, the segment records, the per-filter scalars, params / streams / perm
+    uint64_t* d_brk = nullptr;                 // break points of the steps [v.brk_t0, v.brk_t0 + brk_count)
+    uint32_t brk_cap = 0, brk_count = 0;
+    int32_t* h_perm = nullptr;                 // pinned copy of smc_permute's index vector (the call does not wait for the device)
+    std::vector<double> prop_par;              // smc_set_proposal(AFFINE): the rows [ntheta][SMC_PROP_NPAR] as given (v.prop_kind: the kind)
+    smc::PropRow *d_prop = nullptr, *h_prop = nullptr;   //   the proposal rows of a guided handle (v.prop) and their pinned twin; bootstrap: none
+    smc::Params* h_params = nullptr;           // pinned twin of d_params (smc_set_params does not wait either)
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    int cur = 0;
+    uint32_t t = 0;        // index of the next observation
+    bool inited = false;   // weights exist
+    bool emitted = false;  // logmu/ess of the current weights already produced
+    bool have_params = false;
+    bool resident_ok = false;
+    smc::Geo geo{0, 0};
+    double last_ms = 0.0;
+
+    struct {   // smc_set_skip: filters log_likelihood leaves out
+        unsigned char* d_mask = nullptr;
+        int32_t* d_order = nullptr;            // the order the one-workgroup-per-filter kernel takes them in: [ntheta] | n_active
+        bool on = false;
+        std::vector<uint8_t> h_mask;           // host copy of the mask: the skipped filters' trace columns and summary rows are set to NaN on the host
+    } skip;
+    struct {   // summaries (smc_capi_summ.hip): per step inside the multi-step calls (smc_set_summaries / smc_get_summaries), and one-shot
+        int np = 0, comp = 0, mom = 0;
+        uint64_t p64[smc::QMAX] = {};
+        double p[smc::QMAX] = {};              // the same levels as doubles in [0, 1]: what the unweighted mode reads
+        int mode = SMC_SUMM_WEIGHTED;          // smc_set_summary_mode (v.sum_unw mirrors it)
+        double *d_q = nullptr, *d_m = nullptr; // [T][ntheta][np] | [T][2][d][ntheta]
+        int64_t cap = 0, T = 0;                // steps the traces hold / steps the last call recorded
+        std::vector<uint8_t> skip;             // the skip mask of the call whose summaries smc_get_summaries hands over (empty: none)
+        uint64_t* d_ms = nullptr;              // scratch of the summaries of multi-segment filters (smc_summ_kernels.h) + [ntheta][QMAX] results
+        double* h_once = nullptr;              // pinned [QMAX + 2 d][ntheta]: quantiles / moments of the current state (k_summ_once)
+    } summ;
+    struct {   // opt-in persistent step kernel (SMC_PERSIST=1)
+        unsigned* d_flags = nullptr;           // completion flags [2][ntheta * nseg]
+        int* h_err = nullptr;                  // its pinned "a spin expired" word
+        int on = -1;                           // -1 not decided yet, 0 off / unavailable, 1 on
+    } persist;
+    struct {   // smc_step_window / smc_step_commit
+        double* h_out = nullptr;               // pinned [2][WIN_MAX][ntheta]: (logmu, ess) of the steps of a window
+        int k = 0;                             // steps of the pending window, 0 = none
+    } win;
+    struct {   // PMMH rejuvenation (smc_capi_pmmh.hip): this handle holds the proposal filters
+        smc::PmmhSpec spec{};
+        bool cfg = false;
+        smc::PmmhDev dev{};
+        double* h_out = nullptr;               // pinned mirror: theta [ntheta][d] | logZ [ntheta] | any [ntheta] | nrun
+        double* d_in = nullptr;                // ONE device block: dev.theta | dev.logZ | dev.chol | dev.nrun | dev.counts | dev.any -
+        double* h_in = nullptr;                //   a rejuvenation call fills its pinned twin and uploads it in one copy
+        size_t in_words = 0;
+    } pm;
+};
+
+// a row of smc_set_proposal(AFFINE) is usable (smc_capi.hip, and the guided probes of smc_util.hip)
+inline bool affine_row_ok(const double* par) {
+    for (int k = 0; k < smc::PROP_NPAR; ++k)
+        if (!smc::finite_d(par[k])) return false;
+    return par[3] > 0.0;
+}
+
+// ---- helpers that cross files ----------------------------------------------------------------------
+// smc_capi.hip: the launches of one particle step on the handle's stream, and what they need
+hipError_t do_init(smc_filter_s* h, double y);
+hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y);
+hipError_t do_finalize(smc_filter_s* h, int first_emit, uint32_t t_emit);
+hipError_t ensure_breaks(smc_filter_s* h, uint32_t t, uint32_t t_end);
+int ensure_y(smc_handle h, int64_t T);
+int ensure_recs(smc_handle h, int64_t T);
+int emit_if_needed(smc_handle h);
+// closes the timed region opened at ev0 (records ev1, waits for the stream, stores the elapsed time in last_ms) and hands the
+// requested per-filter vectors over from the pinned mirror
+int finish_elapsed(smc_handle h, double* logZ = nullptr, double* logmu = nullptr, double* ess = nullptr);
+// smc_capi_series.hip
+int enqueue_log_likelihood(smc_handle h, double y0, int64_t T, bool want_trace, bool summ = false);
+// smc_capi_summ.hip: the per-step summaries of the multi-step calls
+inline bool summaries_on(const smc_filter_s* h) { return h->summ.np > 0 || h->summ.mom != 0; }
+bool summaries_fit_lds(const smc_filter_s* h);
+int ensure_summaries(smc_handle h, int64_t T);
+void view_summaries(smc_handle h);
+int enqueue_step_summaries(smc_handle h, int64_t row);
+// smc_capi_slots.hip: k_copy_slots on stream s (slot th of dst <- slot th of src where mask[th])
+hipError_t copy_slots(const smc::FilterView& dst, int dcur, const smc::FilterView& src, int scur, int d, const unsigned char* mask, hipStream_t s);
+
+#pragma GCC visibility pop

@@ -1,6 +1,6 @@
 // smc_ibis.hip -- C ABI of the IBIS sampler (include/smc_hip.h "IBIS"; src/ibis.jl): the handle that keeps a cloud of
 // parameter particles with their exact Kalman state on the device, and the launches of smc_ibis_kernels.h.
-#include "../../include/smc_hip.h"
+#include "smc_host.h"
 #include "smc_ibis_kernels.h"
 
 #include <cmath>
@@ -9,20 +9,7 @@
 #include <string>
 #include <vector>
 
-extern "C" int smc_set_error_(int code, const char* msg);   // smc_capi.hip
-
 using namespace smc;
-
-namespace {
-int fail(int code, const std::string& msg) { return smc_set_error_(code, msg.c_str()); }
-}  // namespace
-#define HIPCHK(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t _e = (expr);                                                                               \
-        if (_e != hipSuccess)                                                                                 \
-            return fail(SMC_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" +      \
-                                      std::to_string(__LINE__) + ")");                                        \
-    } while (0)
 
 struct smc_ibis_s {
     uint32_t magic = 0x53494249u;   // "IBIS": the boundary type is void*, so a foreign pointer is at least noticed

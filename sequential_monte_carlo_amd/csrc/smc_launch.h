@@ -3,8 +3,46 @@
 #pragma once
 #include "smc_kernels.h"
 #include "smc_resident.h"
+#include <type_traits>
 
 namespace smc {
+
+// The ONE place that knows the list of model families: turns the runtime id into a compile-time tag and calls f with it,
+//     by_model(id, [&](auto M) { return launch_step<decltype(M)::value>(...); })
+// hipErrorInvalidValue for an id that names no family.  A new family is one line here (and its object in the Makefile).
+template <class F>
+inline hipError_t by_model(int id, F&& f) {
+    switch (id) {
+    case MODEL_LG1D: return f(std::integral_constant<int, MODEL_LG1D>{});
+    case MODEL_SV1D: return f(std::integral_constant<int, MODEL_SV1D>{});
+    case MODEL_UCSV3D: return f(std::integral_constant<int, MODEL_UCSV3D>{});
+    case MODEL_UCSV_RB: return f(std::integral_constant<int, MODEL_UCSV_RB>{});
+    }
+    return hipErrorInvalidValue;
+}
+// ... and the families that have proposals (proposal_supported, smc_spec.h): the GUIDED kernels exist for these
+template <class F>
+inline hipError_t by_guided_model(int id, F&& f) {
+    switch (id) {
+    case MODEL_LG1D: return f(std::integral_constant<int, MODEL_LG1D>{});
+    case MODEL_UCSV3D: return f(std::integral_constant<int, MODEL_UCSV3D>{});
+    }
+    return hipErrorInvalidValue;
+}
+
+// Kernels that ask for more than the default 64 KiB of dynamic LDS.  The attribute is per device: raise it wherever this
+// process has not done so yet (cheap: a table lookup afterwards).  raised: one table per kernel instantiation.
+template <class K>
+inline hipError_t raise_lds_limit(K kernel, size_t lds, bool (&raised)[16]) {
+    if (lds <= 64 * 1024) return hipSuccess;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev >= 0 && dev < 16 && raised[dev]) return hipSuccess;
+    e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess && dev >= 0 && dev < 16) raised[dev] = true;
+    return e;
+}
 
 // geometry of a workgroup: SEG = 2 * np * threads
 struct Geo {

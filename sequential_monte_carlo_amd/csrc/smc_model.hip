@@ -15,20 +15,6 @@
 
 namespace smc {
 
-// the attribute is per device: raise it wherever this process has not done so yet (cheap: a table lookup afterwards)
-template <class K>
-static hipError_t raise_lds_limit(K kernel, size_t lds, bool (&raised)[16]) {
-    if (lds <= 64 * 1024) return hipSuccess;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 16 && raised[dev]) return hipSuccess;
-    e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess && dev >= 0 && dev < 16) raised[dev] = true;
-    return e;
-}
-
-
 #if !SMC_G
 template <int THREADS, int NP>
 static hipError_t init_t(const FilterView& v, int nxt, double y, hipStream_t s) {

@@ -17,8 +17,7 @@
 // parameter particles and step) and every rank combines them to the same (logmu, ess).  The online sampler carries the
 // UN-NORMALISED log-weights logw (the reference re-normalises at every step, :338, and takes log.(omega) again, :324: the same
 // weights up to a common factor, which reweight removes anyway), so that a step is one addition per parameter particle.
-#include "../../include/smc_hip.h"
-#include "smc_spec.h"
+#include "smc_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -26,8 +25,6 @@
 #include <cstring>
 #include <string>
 #include <vector>
-
-extern "C" int smc_set_error_(int code, const char* msg);   // smc_capi.hip
 
 using namespace smc;
 
@@ -217,7 +214,7 @@ Combined combine(const ORec* rec, int64_t nseg, int64_t n_total) {
     return c;
 }
 
-int fail(const std::string& m) { return smc_set_error_(SMC_EINVAL, m.c_str()); }
+int fail(const std::string& m) { return ::fail(SMC_EINVAL, m); }
 
 // normalised weights w_i = q_i 2^(-48 - (K - kb)) / (Dtot 2^(SH - 48)), the inner filter's dense weights (k_dense_weights)
 void dense_weights(const uint64_t* q, int64_t n, const ORec* rec, const Combined& c, double* w) {

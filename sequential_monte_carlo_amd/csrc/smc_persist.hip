@@ -8,18 +8,6 @@
 
 namespace smc {
 
-template <class K>
-static hipError_t raise_lds_limit(K kernel, size_t lds, bool (&raised)[16]) {
-    if (lds <= 64 * 1024) return hipSuccess;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 16 && raised[dev]) return hipSuccess;
-    e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess && dev >= 0 && dev < 16) raised[dev] = true;
-    return e;
-}
-
 template <int SMC_MODEL, int THREADS, int NP>
 static hipError_t persist_t(const FilterView& v, int cur, uint32_t t0, uint32_t t1, PersistCtl pc, hipStream_t s) {
     const size_t lds = step_lds_bytes(v.nseg_p2, THREADS, NP, true);

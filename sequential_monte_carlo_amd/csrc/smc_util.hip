@@ -1,0 +1,424 @@
+// smc_util.hip -- the entry points that take no filter handle: stand-alone normalize / resample / Kalman (with their
+// thread-local scratch), simulation, and the host (smc_host_*) and device (smc_device_*) probes of the numerical spec that the
+// tests use.  Kernels in smc_util_kernels.h and below.
+#include "smc_host.h"
+#include "smc_util_kernels.h"
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+using namespace smc;
+
+// ---- stand-alone normalize / resample ------------------------------------------------------------
+static int fix_bits_for(int64_t n) {
+    const int k = 61 - ceil_log2_i64(n);
+    return k > FIX_BITS ? FIX_BITS : k;
+}
+
+// Scratch of the stand-alone entry points: device buffers kept per (host thread, slot) and grown on demand - hipMalloc / hipFree of a
+// whole cloud's worth on every call cost 30 ms per normalize at 2^20 entries, ten times the work - released when the thread
+// ends; and a private non-blocking stream per (host thread, device) so that these calls never serialise against the null stream.
+namespace {
+struct ScratchSlot {
+    void* p = nullptr;
+    size_t cap = 0;
+    int device = -1;
+    ~ScratchSlot() { if (p) (void)hipFree(p); }
+};
+struct DevBuf {   // a view of one cached slot: alloc() may be called once per call and slot
+    void* p = nullptr;
+    int slot;
+    explicit DevBuf(int s) : slot(s) {}
+    hipError_t alloc(size_t bytes) {
+        static thread_local ScratchSlot slots[8];
+        ScratchSlot& c = slots[slot];
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return e;
+        bytes = bytes ? bytes : 16;
+        if (c.cap < bytes || c.device != dev) {
+            if (c.p) { (void)hipFree(c.p); c.p = nullptr; c.cap = 0; }
+            e = hipMalloc(&c.p, bytes);
+            if (e != hipSuccess) return e;
+            c.cap = bytes;
+            c.device = dev;
+        }
+        p = c.p;
+        return hipSuccess;
+    }
+    template <class T> T* as() const { return (T*)p; }
+};
+hipError_t util_stream(int device, hipStream_t* out) {
+    static thread_local hipStream_t streams[16] = {};
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return e;
+    if (device < 0 || device >= 16) { *out = nullptr; return hipSuccess; }
+    if (!streams[device]) {
+        e = hipStreamCreateWithFlags(&streams[device], hipStreamNonBlocking);
+        if (e != hipSuccess) return e;
+    }
+    *out = streams[device];
+    return hipSuccess;
+}
+}  // namespace
+
+extern "C" int smc_normalize(const double* logw, int64_t n, double* w, double* logmu, double* ess, int device) {
+    if (!logw || !w || n <= 0) return fail(SMC_EINVAL, "smc_normalize: bad argument");
+    hipStream_t st = nullptr;
+    HIPCHK(util_stream(device, &st));
+    DevBuf d_in(0), d_w(1), d_o(2);
+    HIPCHK(d_in.alloc((size_t)n * 8));
+    HIPCHK(d_w.alloc((size_t)n * 8));
+    HIPCHK(d_o.alloc(16));
+    HIPCHK(hipMemcpyAsync(d_in.p, logw, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    if (n <= 16384) {
+        // one workgroup: the outer reweight works on n_theta-vectors (a few thousand entries)
+        hipLaunchKernelGGL((k_normalize<1024>), dim3(1), dim3(1024), 0, st, d_in.as<double>(), n, fix_bits_for(n), d_w.as<double>(), d_o.as<double>());
+        HIPCHK(hipGetLastError());
+    } else {
+        // a whole cloud's log-weights: three grid-wide passes, every cross-workgroup combination an integer one (same bits)
+        DevBuf d_acc(3);
+        HIPCHK(d_acc.alloc(5 * 8));
+        unsigned long long* acc = d_acc.as<unsigned long long>();
+        int* kmax_i = reinterpret_cast<int*>(acc + 4);
+        HIPCHK(hipMemsetAsync(acc, 0, 32, st));
+        HIPCHK(hipMemsetD32Async(kmax_i, NORM_DEAD, 1, st));
+        int64_t nb = (n + 4 * 256 - 1) / (4 * 256);
+        nb = nb > 2048 ? 2048 : nb;
+        const int K = fix_bits_for(n);
+        hipLaunchKernelGGL((k_normalize_max<256>), dim3((unsigned)nb), dim3(256), 0, st, d_in.as<double>(), n, kmax_i);
+        hipLaunchKernelGGL((k_normalize_sum<256>), dim3((unsigned)nb), dim3(256), 0, st, d_in.as<double>(), n, K, kmax_i, acc);
+        hipLaunchKernelGGL((k_normalize_write<256>), dim3((unsigned)nb), dim3(256), 0, st, d_in.as<double>(), n, K, kmax_i, acc,
+                           d_w.as<double>(), d_o.as<double>());
+        HIPCHK(hipGetLastError());   // (d_acc is a cached slot of this thread: it outlives the block)
+    }
+    double o[2];
+    HIPCHK(hipMemcpyAsync(w, d_w.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(o, d_o.p, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (logmu) *logmu = o[0];
+    if (ess) *ess = o[1];
+    return SMC_OK;
+}
+
+extern "C" int smc_resample(const double* w, int64_t n, int64_t ndraw, uint64_t seed, uint32_t stream, uint32_t t,
+                            int32_t* a, int device) {
+    if (!w || !a || n <= 0 || ndraw < 0) return fail(SMC_EINVAL, "smc_resample: bad argument");
+    if (n > ((int64_t)1 << 31)) return fail(SMC_EINVAL, "smc_resample: n > 2^31");
+    if (ndraw == 0) return SMC_OK;
+    hipStream_t st = nullptr;
+    HIPCHK(util_stream(device, &st));
+    DevBuf d_w(0), d_C(1), d_a(2), d_st(3);
+    HIPCHK(d_w.alloc((size_t)n * 8));
+    HIPCHK(d_C.alloc((size_t)n * 8));
+    HIPCHK(d_a.alloc((size_t)ndraw * 4));
+    HIPCHK(d_st.alloc(4));
+    HIPCHK(hipMemcpyAsync(d_w.p, w, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    if (n <= 65536) {
+        hipLaunchKernelGGL((k_resample_cdf<1024>), dim3(1), dim3(1024), 0, st, d_w.as<double>(), n, fix_bits_for(n), d_C.as<uint64_t>(), d_st.as<int>());
+    } else {   // a whole cloud's weights: the inclusive sums grid-wide (the same integers)
+        constexpr int TH = 256;
+        int nb = (int)((n + 4 * TH - 1) / (4 * TH));
+        nb = nb > 2048 ? 2048 : nb;
+        const int64_t chunk = ((n + nb - 1) / nb + TH - 1) / TH * TH;   // contiguous, a multiple of the workgroup
+        nb = (int)((n + chunk - 1) / chunk);
+        DevBuf d_bs(4);
+        HIPCHK(d_bs.alloc(((size_t)nb + 1) * 8));
+        unsigned long long* mbits = d_bs.as<unsigned long long>() + nb;
+        HIPCHK(hipMemsetAsync(mbits, 0, 8, st));
+        hipLaunchKernelGGL((k_rs_max<TH>), dim3((unsigned)nb), dim3(TH), 0, st, d_w.as<double>(), n, mbits);
+        hipLaunchKernelGGL((k_rs_chunk_sums<TH>), dim3((unsigned)nb), dim3(TH), 0, st, d_w.as<double>(), n, fix_bits_for(n), mbits, chunk, d_bs.as<uint64_t>());
+        hipLaunchKernelGGL((k_rs_scan_chunks<1024>), dim3(1), dim3(1024), 0, st, mbits, nb, d_bs.as<uint64_t>(), d_st.as<int>());
+        hipLaunchKernelGGL((k_rs_write<TH>), dim3((unsigned)nb), dim3(TH), 0, st, d_w.as<double>(), n, fix_bits_for(n), mbits, chunk, d_bs.as<uint64_t>(), d_C.as<uint64_t>());
+    }
+    HIPCHK(hipGetLastError());
+    int status = 0;
+    HIPCHK(hipMemcpyAsync(&status, d_st.p, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (status != 0) return fail(SMC_EINVAL, "smc_resample: weights must be finite with a positive maximum");
+    hipLaunchKernelGGL(k_resample_draw, dim3((unsigned)((ndraw + 255) / 256)), dim3(256), 0, st, d_C.as<uint64_t>(), n, ndraw, seed,
+                       stream, t, d_a.as<int32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(a, d_a.p, (size_t)ndraw * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+
+extern "C" int smc_kalman_log_likelihood(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first,
+                                         double* out, int device) {
+    if (!raw || !y || !out || n_theta <= 0 || T <= 0) return fail(SMC_EINVAL, "smc_kalman_log_likelihood: bad argument");
+    hipStream_t st = nullptr;
+    HIPCHK(util_stream(device, &st));
+    DevBuf d_raw(0), d_y(1), d_out(2);
+    HIPCHK(d_raw.alloc((size_t)n_theta * 48));
+    HIPCHK(d_y.alloc((size_t)T * 8));
+    HIPCHK(d_out.alloc((size_t)n_theta * 24));
+    HIPCHK(hipMemcpyAsync(d_raw.p, raw, (size_t)n_theta * 48, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_y.p, y, (size_t)T * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_kalman, dim3((unsigned)((n_theta + 63) / 64)), dim3(64), 0, st, d_raw.as<double>(), n_theta, d_y.as<double>(), T,
+                       predict_first, d_out.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out.p, (size_t)n_theta * 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+
+// ---- host-side helpers ---------------------------------------------------------------------------
+// The unweighted summaries' definition on the host, by sorting (include/smc_hip.h "summary modes"): the spec's twin of the UNW kernels.
+extern "C" int smc_host_quantile7(const double* x, int64_t n, const double* p, int np, double* out) {
+    if (!x || !p || !out || n < 1 || np < 0) return fail(SMC_EINVAL, "smc_host_quantile7: bad argument");
+    for (int j = 0; j < np; ++j)
+        if (!(p[j] >= 0.0 && p[j] <= 1.0)) return fail(SMC_EINVAL, "smc_host_quantile7: levels must lie in [0, 1]");
+    std::vector<uint64_t> k((size_t)n);
+    for (int64_t i = 0; i < n; ++i) k[(size_t)i] = order_key(x[i]);
+    std::sort(k.begin(), k.end());
+    for (int j = 0; j < np; ++j) {
+        const Q7Rank r = q7_rank(n, p[j]);
+        const uint64_t ka = k[(size_t)(r.j > 1 ? r.j - 1 : 0)], kb = n == 1 ? ka : k[(size_t)r.j];
+        out[j] = q7_interp(key_value(ka), key_value(kb), r.g);
+    }
+    return SMC_OK;
+}
+extern "C" int smc_host_sample_moments(const double* x, int64_t n, double* mean, double* var) {
+    if (!x || !mean || !var || n < 1) return fail(SMC_EINVAL, "smc_host_sample_moments: bad argument");
+    double s = 0.0, s2 = 0.0;
+    for (int64_t i = 0; i < n; ++i) s += x[i];
+    double m = s / (double)n, r = 0.0;
+    for (int64_t i = 0; i < n; ++i) r += x[i] - m;   // (the rounding of the first sum, taken back)
+    m += r / (double)n;
+    for (int64_t i = 0; i < n; ++i) { const double e = x[i] - m; s2 += e * e; }
+    *mean = m;
+    *var = s2 / (double)(n - 1);   // (n == 1: 0 / 0, NaN as Statistics.var)
+    return SMC_OK;
+}
+template <int MODEL>
+static void simulate_t(const Params& p, int64_t T, uint64_t seed, double* x, double* y) {
+    constexpr int D = model_dim<MODEL>::value;
+    double xc[D], xn[D], z[D], z1, mean, sd;
+    for (int64_t t = 0; t < T; ++t) {
+        for (int c = 0; c < D; ++c) box_muller(draw(seed, 0u, SIM_STREAM, (uint32_t)t, SLOT_NORMAL0 + c), z[c], z1);
+        if (t == 0) model_initial<MODEL>(p, z, xn); else model_transition<MODEL>(p, xc, z, xn);
+        model_obs_moments<MODEL>(p, xn, mean, sd);
+        double e;
+        box_muller(draw(seed, 0u, SIM_STREAM, (uint32_t)t, SLOT_OBS), e, z1);
+        y[t] = fma(sd, e, mean);
+        for (int c = 0; c < D; ++c) { xc[c] = xn[c]; if (x) x[(size_t)c * T + t] = xn[c]; }
+    }
+}
+
+extern "C" int smc_simulate_dim(int model_id) { return model_id == MODEL_UCSV_RB ? model_dim_rt(MODEL_UCSV3D) : model_dim_rt(model_id); }
+extern "C" int smc_simulate(int model_id, const double* raw, int64_t T, uint64_t seed, double* x, double* y) {
+    const int nraw = model_nraw_rt(model_id);
+    if (nraw < 0 || !raw || !y || T <= 0) return fail(SMC_EINVAL, "smc_simulate: bad argument");
+    Params p;
+    for (int k = 0; k < NPARAM; ++k) p.raw[k] = k < nraw ? raw[k] : 0.0;
+    derive_params(model_id, p.raw, p.der);
+    (void)by_model(model_id, [&](auto M) {
+        // the data-generating model of the marginal family is UCSV: x is [3][T] (smc_simulate_dim)
+        constexpr int SIM = decltype(M)::value == MODEL_UCSV_RB ? MODEL_UCSV3D : decltype(M)::value;
+        simulate_t<SIM>(p, T, seed, x, y);
+        return hipSuccess;
+    });
+    return SMC_OK;
+}
+
+extern "C" double smc_host_exp(double x) { return sp_exp(x); }
+extern "C" double smc_host_log(double x) { return sp_log(x); }
+extern "C" void smc_host_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+    const u32x4 r = philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1]);
+    for (int i = 0; i < 4; ++i) out[i] = r.v[i];
+}
+extern "C" void smc_host_box_muller(const uint32_t w[4], double* z0, double* z1) {
+    box_muller(u32x4{{w[0], w[1], w[2], w[3]}}, *z0, *z1);
+}
+
+extern "C" int smc_host_pmmh_propose(int d_theta, uint64_t move_seed, uint32_t stream, uint32_t c, const double* theta,
+                                     const double* chol, double scale, double* prop) {
+    if (d_theta < 1 || d_theta > MAX_DTHETA || !theta || !chol || !prop) return fail(SMC_EINVAL, "smc_host_pmmh_propose: bad argument");
+    PmmhSpec sp{};
+    sp.d = d_theta;
+    pmmh_propose(sp, move_seed, stream, c, theta, chol, sqrt(scale), prop);
+    return SMC_OK;
+}
+extern "C" double smc_host_pmmh_log_uniform(uint64_t move_seed, uint32_t stream, uint32_t c) { return pmmh_log_uniform(move_seed, stream, c); }
+extern "C" double smc_host_prior_logpdf(int family, const double* par, double x) {
+    return prior_insupport(family, par, x) ? prior_logpdf(family, par, x) : -inf();
+}
+
+__global__ void k_device_math(int which, const double* a, const double* b, int64_t n, double* out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double x = a[i];
+    double r = 0.0;
+    if (which == 0) r = sp_exp(x);
+    else if (which == 1) r = sp_log(x);
+    else if (which == 2) r = sqrt(x);
+    else if (which == 3 || which == 4) {
+        const uint64_t ua = d2bits(x), ub = d2bits(b[i]);
+        double z0, z1;
+        box_muller(u32x4{{(uint32_t)ua, (uint32_t)(ua >> 32), (uint32_t)ub, (uint32_t)(ub >> 32)}}, z0, z1);
+        r = which == 3 ? z0 : z1;
+    } else if (which == 5) r = x / b[i];
+    out[i] = r;
+}
+
+__global__ void k_sys_targets(uint64_t Dtot, uint32_t n, uint64_t u, uint64_t j0, int nk, uint64_t* out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < nk) out[k] = sys_target(sys_base(Dtot, n, 1.0 / (double)n, u, j0), (uint32_t)k);
+}
+// T_{j0+k} = floor(((j0+k) Dtot + mulhi64(u, Dtot)) / n), k < nk <= 8192: the division-free evaluation the
+// systematic kernels use, on the host (device < 0) or on a device - tests compare both with exact integers
+extern "C" int smc_sys_targets(uint64_t Dtot, uint32_t n, uint64_t u, uint64_t j0, int nk, uint64_t* out, int device) {
+    if (!out || nk < 1 || nk > 8192 || n < 1 || n >= (1u << 31) || Dtot >= (1ull << 63) || j0 + (uint64_t)nk > n)
+        return fail(SMC_EINVAL, "smc_sys_targets: bad argument");
+    if (device < 0) {
+        const SysBase sb = sys_base(Dtot, n, 1.0 / (double)n, u, j0);
+        for (int k = 0; k < nk; ++k) out[k] = sys_target(sb, (uint32_t)k);
+        return SMC_OK;
+    }
+    hipStream_t st = nullptr;
+    HIPCHK(util_stream(device, &st));
+    DevBuf d(0);
+    HIPCHK(d.alloc((size_t)nk * 8));
+    hipLaunchKernelGGL(k_sys_targets, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, Dtot, n, u, j0, nk, d.as<uint64_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d.p, (size_t)nk * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+
+// the proposals (smc_spec.h "proposals"), one particle on the host / n particles on a device
+extern "C" int smc_host_optimal_proposal(int model_id, const double* raw, double* par) {
+    if (!raw || !par) return fail(SMC_EINVAL, "smc_host_optimal_proposal: NULL argument");
+    if (model_id != MODEL_LG1D) return fail(SMC_EINVAL, "smc_host_optimal_proposal: LG1D only (the UCSV proposal has no parameters)");
+    optimal_proposal_lg(raw, par);
+    return SMC_OK;
+}
+// the parameter and proposal rows of one guided particle step from (raw, kind, par); false: refused
+static bool guided_params(int model_id, const double* raw, int kind, const double* par, Params& P, PropRow& R) {
+    const int nraw = model_nraw_rt(model_id);
+    if (nraw < 0 || !raw || kind == PROP_NONE || !proposal_supported(model_id, kind)) return false;
+    if ((kind == PROP_AFFINE) != (par != nullptr)) return false;
+    if (kind == PROP_AFFINE && !affine_row_ok(par)) return false;
+    for (int k = 0; k < NPARAM; ++k) { P.raw[k] = k < nraw ? raw[k] : 0.0; R.p[k] = 0.0; }
+    derive_params(model_id, P.raw, P.der);
+    if (kind == PROP_AFFINE)
+        for (int k = 0; k < PROP_NPAR; ++k) R.p[k] = par[k];
+    derive_proposal(model_id, kind, P.raw, P.der, R.p);
+    return true;
+}
+extern "C" int smc_host_guided_step(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z,
+                                    double y, double* x, double* logw) {
+    if (!xp || !z || !x || !logw) return fail(SMC_EINVAL, "smc_host_guided_step: NULL argument");
+    Params P;
+    PropRow R;
+    if (!guided_params(model_id, raw, kind, par, P, R)) return fail(SMC_EINVAL, "smc_host_guided_step: bad model, kind or row");
+    (void)by_guided_model(model_id, [&](auto M) {   // (guided_params has refused every other family)
+        *logw = model_guided<decltype(M)::value>(P, R, xp, z, y, x);
+        return hipSuccess;
+    });
+    return SMC_OK;
+}
+
+template <int MODEL>
+__global__ void k_guided_step(Params P, PropRow R, const double* xp, const double* z, double y, int64_t n, double* x, double* logw) {
+    constexpr int D = model_dim<MODEL>::value;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double a[D], zz[D], xn[D];
+    for (int c = 0; c < D; ++c) { a[c] = xp[(size_t)c * n + i]; zz[c] = z[(size_t)c * n + i]; }
+    logw[i] = model_guided<MODEL>(P, R, a, zz, y, xn);
+    for (int c = 0; c < D; ++c) x[(size_t)c * n + i] = xn[c];
+}
+extern "C" int smc_device_guided_step(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z,
+                                      double y, int64_t n, double* x, double* logw, int device) {
+    if (!xp || !z || !x || !logw || n <= 0) return fail(SMC_EINVAL, "smc_device_guided_step: bad argument");
+    Params P;
+    PropRow R;
+    if (!guided_params(model_id, raw, kind, par, P, R)) return fail(SMC_EINVAL, "smc_device_guided_step: bad model, kind or row");
+    const int d = model_dim_rt(model_id);
+    HIPCHK(hipSetDevice(device));
+    double *dxp = nullptr, *dz = nullptr, *dx = nullptr, *dlw = nullptr;
+    const size_t bytes = (size_t)d * n * 8;
+    hipError_t e = hipMalloc((void**)&dxp, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&dz, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&dx, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&dlw, (size_t)n * 8);
+    if (e == hipSuccess) e = hipMemcpy(dxp, xp, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dz, z, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        e = by_guided_model(model_id, [&](auto M) {
+            hipLaunchKernelGGL(k_guided_step<decltype(M)::value>, grid, block, 0, 0, P, R, dxp, dz, y, n, dx, dlw);
+            return hipGetLastError();
+        });
+    }
+    if (e == hipSuccess) e = hipMemcpy(x, dx, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(logw, dlw, (size_t)n * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(dxp); (void)hipFree(dz); (void)hipFree(dx); (void)hipFree(dlw);
+    HIPCHK(e);
+    return SMC_OK;
+}
+
+// the marginal step (smc_spec.h "marginal families"), one particle on the host / n particles on a device
+extern "C" int smc_host_rb_step(const double* raw, const double* sp, const double* z, double y, int first, double* s, double* logw) {
+    if (!raw || !sp || !z || !s || !logw) return fail(SMC_EINVAL, "smc_host_rb_step: NULL argument");
+    Params P;
+    for (int k = 0; k < NPARAM; ++k) P.raw[k] = k < model_nraw_rt(MODEL_UCSV_RB) ? raw[k] : 0.0;
+    derive_params(MODEL_UCSV_RB, P.raw, P.der);
+    double a[4] = {sp[0], sp[1], sp[2], sp[3]}, o[4];
+    *logw = model_marginal_step<MODEL_UCSV_RB>(P, first != 0, a, z, y, o);
+    for (int c = 0; c < 4; ++c) s[c] = o[c];
+    return SMC_OK;
+}
+__global__ void k_rb_step(Params P, int first, const double* sp, const double* z, double y, int64_t n, double* s, double* logw) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double a[4], zz[2], o[4];
+    for (int c = 0; c < 4; ++c) a[c] = sp[(size_t)c * n + i];
+    for (int c = 0; c < 2; ++c) zz[c] = z[(size_t)c * n + i];
+    logw[i] = model_marginal_step<MODEL_UCSV_RB>(P, first != 0, a, zz, y, o);
+    for (int c = 0; c < 4; ++c) s[(size_t)c * n + i] = o[c];
+}
+extern "C" int smc_device_rb_step(const double* raw, const double* sp, const double* z, double y, int first, int64_t n, double* s, double* logw,
+                                  int device) {
+    if (!raw || !sp || !z || !s || !logw || n <= 0) return fail(SMC_EINVAL, "smc_device_rb_step: bad argument");
+    Params P;
+    for (int k = 0; k < NPARAM; ++k) P.raw[k] = k < model_nraw_rt(MODEL_UCSV_RB) ? raw[k] : 0.0;
+    derive_params(MODEL_UCSV_RB, P.raw, P.der);
+    hipStream_t st = nullptr;
+    HIPCHK(util_stream(device, &st));
+    DevBuf dsp(0), dz(1), ds(2), dlw(3);
+    HIPCHK(dsp.alloc((size_t)4 * n * 8));
+    HIPCHK(dz.alloc((size_t)2 * n * 8));
+    HIPCHK(ds.alloc((size_t)4 * n * 8));
+    HIPCHK(dlw.alloc((size_t)n * 8));
+    HIPCHK(hipMemcpyAsync(dsp.p, sp, (size_t)4 * n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dz.p, z, (size_t)2 * n * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_rb_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, first, dsp.as<double>(), dz.as<double>(), y, n,
+                       ds.as<double>(), dlw.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(s, ds.p, (size_t)4 * n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(logw, dlw.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+
+extern "C" int smc_device_math(int which, const double* a, const double* b, int64_t n, double* out, int device) {
+    if (!a || !out || n <= 0 || which < 0 || which > 5) return fail(SMC_EINVAL, "smc_device_math: bad argument");
+    if (which >= 3 && !b) return fail(SMC_EINVAL, "smc_device_math: b required");
+    hipStream_t st = nullptr;
+    HIPCHK(util_stream(device, &st));
+    DevBuf da(0), db(1), dout(2);
+    HIPCHK(da.alloc((size_t)n * 8));
+    HIPCHK(db.alloc((size_t)n * 8));
+    HIPCHK(dout.alloc((size_t)n * 8));
+    HIPCHK(hipMemcpyAsync(da.p, a, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    if (b) HIPCHK(hipMemcpyAsync(db.p, b, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_device_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, which, da.as<double>(), db.as<double>(), n, dout.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
