@@ -272,6 +272,11 @@ int smc_host_outer_resample(const double* logw, int64_t n, int64_t m, uint64_t s
  * covariance 2.83^2/d cov(theta) + 1e-10 I (1e-2 I when norm(cov) < 1e-8) from the cloud theta [n][d], fixed order of
  * operations; d = 1: L = [[2.83^2 var + 1e-10]] handed to Normal() as a standard deviation (:87-92), *univariate = 1 */
 int smc_host_rw_factor(const double* theta, int64_t n, int d, double* L /*[d][d]*/, int* univariate);
+/* the tail of smc_host_rw_factor from a covariance cov [d][d] (symmetric): Frobenius norm and collapse rule, the 2.83^2/d
+ * scaling, the 1e-10 jitter, the Cholesky factorisation column by column.  smc_host_rw_factor is its serial index-order
+ * covariance followed by this call; the IBIS sampler with device_moves hands it the covariance of smc_ibis_theta_moments.
+ * An error (not an abort) when the scaled covariance is not positive definite. */
+int smc_host_rw_factor_cov(const double* cov /*[d][d]*/, int d, double* L /*[d][d]*/, int* univariate);
 /* the spec's PMMH pieces on the host (parity tests): proposal, log prior (NaN-free; -inf outside the support) */
 int smc_host_pmmh_propose(int d_theta, uint64_t move_seed, uint32_t stream, uint32_t c, const double* theta,
                           const double* chol, double scale, double* prop);
@@ -411,6 +416,37 @@ int smc_ibis_summary(void* h, int ahead, double* out /*[8]*/);
 int smc_ibis_set_summaries(void* h, int on, int ahead);
 int smc_ibis_get_summaries(void* h, int j, double* out /*[j][8]*/);
 int smc_host_ibis_summary(const double* rows, const double* x, const double* S, const double* logw, int64_t M, int ahead, double* out /*[8]*/);
+/* The resample-move loop of the IBIS sampler without a read of the cloud (IBIS(..., device_moves=True)): what the host does
+ * on O(M) numbers after smc_ibis_window, smc_ibis_get and smc_ibis_rejuvenate, as reductions, scans and searches on the
+ * device.  The integer parts give the bits of their host functions; the moments have a specification of their own.
+ *   smc_ibis_window_ess     smc_ibis_window, but the records stay on the device: per step the three integers of the segment
+ *                           combine (K = max kb, D = sum seg_Q, R = sum seg_R: integer maxima and sums, any order) are
+ *                           reduced there, k x 20 bytes come back, and the walk stops at the first step with ess < ess_min.
+ *                           ess_out [k] (the first *j_out are set), *j_out: bit for bit smc_host_outer_walk on the records
+ *                           smc_ibis_window returns for the same state and y.  smc_ibis_commit and the recording of the
+ *                           summaries behave as after smc_ibis_window.
+ *   smc_ibis_resample       the index draw of resample! (:73-84) for the committed logw and its gather: the ancestors of
+ *                           smc_host_outer_resample(logw, M, M, seed), bit for bit and in ascending order (fixed-point weights
+ *                           and segment sums, an integer scan of the segment table, per draw a binary search for the segment
+ *                           and a count inside it, an integer histogram, its scan, its expansion), then smc_ibis_permute's
+ *                           value copy with the ancestors left on the device.  a_out [n_theta] or NULL: nothing else crosses
+ *                           the bus.  No live particle: the identity.
+ *   smc_ibis_theta_moments  mean [d] and cov [d][d] of the theta cloud.  weighted = 0: the sample mean and the corrected
+ *                           covariance (divisor M - 1), what random_walk_kernel (smc_samplers.jl:87-101) takes of the
+ *                           resampled cloud; weighted = 1: mean = sum omega theta, cov = sum omega (theta - mean)(theta - mean)'
+ *                           (uncorrected, the convention of smc_get_moments) with omega the normalised weights of logw - a
+ *                           dead particle contributes nothing whatever its theta; NaN when none is alive.  Order of operations:
+ *                           csrc/smc_spec.h "moments of the theta cloud" (chunks of 64, a tree within the chunk, chunks left to
+ *                           right, a centred second pass): a function of the arrays alone, no atomics on floats.  This is NOT
+ *                           the serial index-order sum of smc_host_rw_factor.  Accuracy: the bounds of smc_get_moments below.
+ *   smc_host_theta_moments  the same specification on the host (no GPU), the same bits: theta [M][d], logw [M] (NULL when
+ *                           weighted = 0)
+ *   smc_ibis_get_moved      the moved mask [n_theta] of the last smc_ibis_rejuvenate (which accepts moved = NULL) */
+int smc_ibis_window_ess(void* h, const double* y /*[k]*/, int k, double ess_min, double* ess_out /*[k]*/, int* j_out);
+int smc_ibis_resample(void* h, uint64_t seed, int32_t* a_out /*[n_theta] or NULL*/);
+int smc_ibis_theta_moments(void* h, int weighted, double* mean /*[d_theta]*/, double* cov /*[d_theta][d_theta]*/);
+int smc_host_theta_moments(const double* theta, const double* logw, int64_t M, int d, int weighted, double* mean, double* cov);
+int smc_ibis_get_moved(void* h, uint8_t* moved /*[n_theta]*/);
 /* filtered mean and variance of every state coordinate under the current weights, on the device
  * (README.md:41,51 summaries; src/plotting_utils.jl:116-124 estimated_trend). mean, var: [d][n_theta].
  * Definition: StatsBase's uncorrected weighted moments with the dense weights w of smc_get_state, mean = sum w x and

@@ -872,3 +872,51 @@ function density_tempered(ib::HipIBIS, y::Vector{Float64}, verbose=true)
     end
     return ib
 end
+
+# ---- the resample-move loop without a read of the cloud (the Python twin: IBIS(..., device_moves=true)).  The ccall methods of
+# smc_ibis_window_ess, smc_ibis_resample, smc_ibis_theta_moments, smc_ibis_get_moved and smc_host_rw_factor_cov; a loop built from
+# them touches k + 1 numbers per window and dθ + dθ² + 1 per move instead of O(M).
+# (ess [j], j) of k steps: the walk of ibis_window! on three integers per step reduced on the device; follow with the commit
+function ibis_window_ess!(ib::HipIBIS, yk::Vector{Float64}, ess_min::Float64)
+    k = length(yk); e = Vector{Float64}(undef, k); j = Ref{Cint}(0)
+    GC.@preserve yk e smc_check(ccall((:smc_ibis_window_ess, LIBSMC), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Float64, Ptr{Float64}, Ptr{Cint}),
+        ib.h, yk, k, ess_min, e, j))
+    smc_check(ccall((:smc_ibis_commit, LIBSMC), Cint, (Ptr{Cvoid}, Cint), ib.h, j[]))
+    return e[1:j[]], Int(j[])
+end
+# resample!(ibis) with the index draw on the device: the ancestors of outer_resample(logw, M, seed) for the committed logw
+function resample_device!(ib::HipIBIS)                                           # ibis.jl:73-84
+    smc_check(ccall((:smc_ibis_resample, LIBSMC), Cint, (Ptr{Cvoid}, UInt64, Ptr{Int32}), ib.h, next_seed!(ib), C_NULL))
+    return ib
+end
+# (mean [dθ], cov [dθ x dθ]) of the θ cloud: weighted=false the sample moments (divisor M - 1), true under the normalised ω
+function theta_moments(ib::HipIBIS; weighted::Bool=false)
+    mean = Vector{Float64}(undef, ib.dθ); cov = Matrix{Float64}(undef, ib.dθ, ib.dθ)
+    GC.@preserve mean cov smc_check(ccall((:smc_ibis_theta_moments, LIBSMC), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}),
+        ib.h, weighted ? 1 : 0, mean, cov))
+    return mean, cov                                                              # (symmetric: row- and column-major agree)
+end
+posterior_moments(ib::HipIBIS) = theta_moments(ib; weighted=true)
+# the tail of rw_factor from a covariance: (L, univariate)
+function rw_factor_cov(cov::Matrix{Float64})
+    d = size(cov, 1); L = Matrix{Float64}(undef, d, d); uni = Ref{Cint}(0)
+    GC.@preserve cov L smc_check(ccall((:smc_host_rw_factor_cov, LIBSMC), Cint, (Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Cint}), cov, d, L, uni))
+    return L, uni[] != 0                                                          # L as the C side wrote it: row-major, as rw_factor hands it on
+end
+function ibis_moved(ib::HipIBIS)                                                  # acc_array of the last rejuvenate! (ibis.jl:87)
+    moved = Vector{UInt8}(undef, ib.M)
+    GC.@preserve moved smc_check(ccall((:smc_ibis_get_moved, LIBSMC), Cint, (Ptr{Cvoid}, Ptr{UInt8}), ib.h, moved))
+    return moved .!= 0
+end
+# rejuvenate!(ibis, y, ξ) with ibis.kernel(ibis.θ) from the device's covariance: dθ + dθ² doubles and the count come back
+function rejuvenate_device!(ib::HipIBIS, y::Vector{Float64}, ξ::Float64=1.0)
+    L, uni = rw_factor_cov(theta_moments(ib)[2])
+    scales = 0.5 * reverse(1:ib.chain)
+    s = uni ? scales .^ 2 : collect(scales)
+    acc = Ref{Int64}(0)
+    GC.@preserve y L s smc_check(ccall((:smc_ibis_rejuvenate, LIBSMC), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Float64, Ptr{Float64}, Ptr{Float64}, Cint, UInt64, Ptr{Int64}, Ptr{UInt8}),
+        ib.h, y, length(y), ξ, L, s, ib.chain, next_seed!(ib), acc, C_NULL))
+    ib.acc_ratio = acc[] / ib.M
+    return ib
+end

@@ -33,6 +33,8 @@ EXPORTS = [
     "smc_ibis_create", "smc_ibis_destroy", "smc_ibis_configure", "smc_ibis_set_theta", "smc_ibis_window", "smc_ibis_commit",
     "smc_ibis_filter", "smc_ibis_permute", "smc_ibis_set_logw", "smc_ibis_rejuvenate", "smc_ibis_get",
     "smc_ibis_summary", "smc_ibis_set_summaries", "smc_ibis_get_summaries", "smc_host_ibis_summary",
+    "smc_ibis_window_ess", "smc_ibis_resample", "smc_ibis_theta_moments", "smc_ibis_get_moved", "smc_host_theta_moments",
+    "smc_host_rw_factor_cov",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -182,6 +184,12 @@ def lib():
     L.smc_ibis_set_summaries.argtypes = [h, C.c_int, C.c_int]
     L.smc_ibis_get_summaries.argtypes = [h, C.c_int, _dp]
     L.smc_host_ibis_summary.argtypes = [_dp, _dp, _dp, _dp, C.c_int64, C.c_int, _dp]
+    L.smc_ibis_window_ess.argtypes = [h, _dp, C.c_int, C.c_double, _dp, _ip]
+    L.smc_ibis_resample.argtypes = [h, C.c_uint64, _i32p]
+    L.smc_ibis_theta_moments.argtypes = [h, C.c_int, _dp, _dp]
+    L.smc_ibis_get_moved.argtypes = [h, C.POINTER(C.c_uint8)]
+    L.smc_host_theta_moments.argtypes = [_dp, _dp, C.c_int64, C.c_int, C.c_int, _dp, _dp]
+    L.smc_host_rw_factor_cov.argtypes = [_dp, C.c_int, _dp, _ip]
     L.smc_last_error.restype = C.c_char_p
     L.smc_version.restype = C.c_char_p
     _lib = L
@@ -419,6 +427,30 @@ def host_rw_factor(theta):
     uni = C.c_int()
     check(lib().smc_host_rw_factor(_d(theta), n, d, _d(L), C.byref(uni)))
     return L, bool(uni.value)
+
+
+def host_rw_factor_cov(cov):
+    """(L [d][d], univariate): the tail of random_walk_kernel from a covariance [d][d]   (smc_host_rw_factor_cov)"""
+    cov = np.ascontiguousarray(cov, dtype=np.float64)
+    d = cov.shape[0]
+    assert cov.shape == (d, d)
+    L = np.zeros((d, d))
+    uni = C.c_int()
+    check(lib().smc_host_rw_factor_cov(_d(cov), d, _d(L), C.byref(uni)))
+    return L, bool(uni.value)
+
+
+def host_theta_moments(theta, logw=None, weighted=False):
+    """(mean [d], cov [d][d]) of a theta cloud [M][d]: the sample moments (divisor M - 1), or with weighted=True the moments
+    under the normalised weights of logw (smc_host_theta_moments: the device's specification on the host; no GPU)"""
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    M, d = theta.shape
+    if weighted:
+        logw = np.ascontiguousarray(logw, dtype=np.float64)
+        assert logw.size == M
+    mean, cov = np.zeros(d), np.zeros((d, d))
+    check(lib().smc_host_theta_moments(_d(theta), _d(logw) if weighted else None, M, d, int(bool(weighted)), _d(mean), _d(cov)))
+    return mean, cov
 
 
 def comm_unique_id():
@@ -778,16 +810,44 @@ class IbisHandle:
         assert logw.size == self.M
         check(lib().smc_ibis_set_logw(self._h, _d(logw)))
 
-    def rejuvenate(self, y, xi, chol, scales, move_seed):
-        """rejuvenate!(ibis, y, xi) in one launch -> (number of particles that moved, moved mask [M])"""
+    def window_ess(self, y, ess_min):
+        """window(y) with the walk's integers reduced on the device: (ess [j], j) of host_outer_walk on its records, which stay
+        on the device (smc_ibis_window_ess); follow with commit(j)"""
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        ess = np.zeros(y.size)
+        j = C.c_int()
+        check(lib().smc_ibis_window_ess(self._h, _d(y), y.size, float(ess_min), _d(ess), C.byref(j)))
+        return ess[:j.value], j.value
+
+    def resample(self, seed, want_a=False):
+        """resample!(ibis) on the device: the ancestors of host_outer_resample(logw, M, seed) and their gather
+        (smc_ibis_resample) -> the ancestors [M] when asked for, else None"""
+        a = np.empty(self.M, dtype=np.int32) if want_a else None
+        check(lib().smc_ibis_resample(self._h, int(seed), a.ctypes.data_as(_i32p) if want_a else None))
+        return a
+
+    def theta_moments(self, weighted=False):
+        """(mean [d], cov [d][d]) of the committed theta cloud, reduced on the device (smc_ibis_theta_moments)"""
+        mean, cov = np.zeros(self.d), np.zeros((self.d, self.d))
+        check(lib().smc_ibis_theta_moments(self._h, int(bool(weighted)), _d(mean), _d(cov)))
+        return mean, cov
+
+    def get_moved(self):
+        """the moved mask [M] of the last rejuvenate (smc_ibis_get_moved)"""
+        moved = np.zeros(self.M, dtype=np.uint8)
+        check(lib().smc_ibis_get_moved(self._h, moved.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return moved.astype(bool)
+
+    def rejuvenate(self, y, xi, chol, scales, move_seed, want_moved=True):
+        """rejuvenate!(ibis, y, xi) in one launch -> (number of particles that moved, moved mask [M] or None)"""
         y = np.ascontiguousarray(y, dtype=np.float64)
         chol = np.ascontiguousarray(chol, dtype=np.float64).reshape(self.d, self.d)
         scales = np.ascontiguousarray(scales, dtype=np.float64)
         n = C.c_int64()
-        moved = np.zeros(self.M, dtype=np.uint8)
+        moved = np.zeros(self.M, dtype=np.uint8) if want_moved else None
         check(lib().smc_ibis_rejuvenate(self._h, _d(y), y.size, float(xi), _d(chol), _d(scales), scales.size, int(move_seed), C.byref(n),
-                                        moved.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return int(n.value), moved.astype(bool)
+                                        moved.ctypes.data_as(C.POINTER(C.c_uint8)) if want_moved else None))
+        return int(n.value), (moved.astype(bool) if want_moved else None)
 
     def get(self, theta=False, x=False, S=False, logZ=False, logw=False):
         """the requested arrays from the device, as a dict"""

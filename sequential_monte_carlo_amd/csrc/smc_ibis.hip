@@ -38,6 +38,16 @@ struct smc_ibis_s {
     double* d_one = nullptr; size_t one_cap = 0;     // [IBIS_SUM_NCOL][nchunk] | [IBIS_SUM_NOUT]: smc_ibis_summary
     double srow[IBIS_MAX_WINDOW * IBIS_SUM_NOUT];
     int srow_k = 0;                                  // rows of srow that are set
+    // the resample-move loop on the device (smc_ibis_window_ess / smc_ibis_resample / smc_ibis_theta_moments)
+    bool have_moved = false;                         // d_moved holds the mask of a rejuvenation
+    uint32_t* d_K = nullptr;                         // [IBIS_MAX_WINDOW] biased K of every step of a window | [0] of the cloud
+    unsigned long long* d_DR = nullptr;              // [IBIS_MAX_WINDOW][2] (D, R) of every step
+    uint64_t* d_q = nullptr;                         // [M] fixed-point weights | then the inclusive scan of cnt
+    uint64_t* d_seg = nullptr;                       // [nseg] S | [nseg] Dcum | [ntile(M)] tile sums of the scans
+    uint32_t* d_skb = nullptr;                       // [nseg] biased kb
+    int32_t* d_cnt = nullptr;                        // [M] draws per particle
+    double* d_mpart = nullptr;                       // [THETA_MOM_NTRI][nchunk] chunk sums of the moments
+    double* d_mom = nullptr;                         // [IBIS_MOM_N]
 };
 typedef smc_ibis_s* ibis_t;
 
@@ -67,6 +77,8 @@ void release(ibis_t h) {
     (void)hipFree(h->d_y); (void)hipFree(h->d_lik); (void)hipFree(h->d_rec); (void)hipFree(h->d_a);
     (void)hipFree(h->d_moved); (void)hipFree(h->d_count); (void)hipFree(h->d_chol);
     (void)hipFree(h->d_part); (void)hipFree(h->d_srow); (void)hipFree(h->d_one);
+    (void)hipFree(h->d_K); (void)hipFree(h->d_DR); (void)hipFree(h->d_q); (void)hipFree(h->d_seg); (void)hipFree(h->d_skb);
+    (void)hipFree(h->d_cnt); (void)hipFree(h->d_mpart); (void)hipFree(h->d_mom);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -135,6 +147,9 @@ extern "C" int smc_ibis_create(int64_t n_theta, uint64_t seed, int device, int p
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_count, 8);
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_chol, (MAX_DTHETA * MAX_DTHETA + IBIS_MAX_CHAIN) * 8);
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_srow, IBIS_MAX_WINDOW * IBIS_SUM_NOUT * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_K, IBIS_MAX_WINDOW * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_DR, IBIS_MAX_WINDOW * 2 * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_mom, IBIS_MOM_N * 8);
     if (e != hipSuccess) {
         release(h);
         return fail(e == hipErrorOutOfMemory ? SMC_ENOMEM : SMC_EHIP, std::string("smc_ibis_create: ") + hipGetErrorString(e));
@@ -199,14 +214,15 @@ extern "C" int smc_ibis_set_theta(void* hp, const double* theta) {
     h->t = 0;
     h->win_k = 0;
     h->srow_k = 0;
+    h->have_moved = false;
     return SMC_OK;
 }
 
-extern "C" int smc_ibis_window(void* hp, const double* y, int k, double* lik, uint64_t* rec) {
-    ibis_t h = as_ibis(hp);
-    if (!h || !y || !rec) return fail(SMC_EINVAL, "smc_ibis_window: bad argument");
-    if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_window: smc_ibis_set_theta has not been called");
-    if (k < 1 || k > IBIS_MAX_WINDOW) return fail(SMC_EINVAL, "smc_ibis_window: 1 <= k <= 64");
+// the launches of a window of k steps from the committed state: the records go to d_rec, lik (optional) to d_lik, the rows of
+// the summaries (when recording) to srow.  Nothing is waited for.
+static int enqueue_window(ibis_t h, const char* who, const double* y, int k, bool lik) {
+    if (!h->have_theta) return fail(SMC_ESTATE, std::string(who) + ": smc_ibis_set_theta has not been called");
+    if (k < 1 || k > IBIS_MAX_WINDOW) return fail(SMC_EINVAL, std::string(who) + ": 1 <= k <= 64");
     HIPCHK(hipSetDevice(h->device));
     h->win_k = 0;
     const size_t M = (size_t)h->v.M, nseg = (M + IBIS_OSEG - 1) / IBIS_OSEG;
@@ -232,12 +248,56 @@ extern "C" int smc_ibis_window(void* hp, const double* y, int k, double* lik, ui
                            (double*)nullptr, 0);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipMemcpyAsync(rec, h->d_rec, (size_t)k * nseg * 32, hipMemcpyDeviceToHost, h->stream));
-    if (lik) HIPCHK(hipMemcpyAsync(lik, h->d_lik, (size_t)k * M * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    return SMC_OK;
+}
+// the window is pending: smc_ibis_commit may keep a prefix of it
+static void window_pending(ibis_t h, const double* y, int k) {
     h->win_y.assign(y, y + k);
     h->win_k = k;
     if (h->summ_on) h->srow_k = k;
+}
+
+extern "C" int smc_ibis_window(void* hp, const double* y, int k, double* lik, uint64_t* rec) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !y || !rec) return fail(SMC_EINVAL, "smc_ibis_window: bad argument");
+    if (const int rc = enqueue_window(h, "smc_ibis_window", y, k, lik != nullptr)) return rc;
+    const size_t M = (size_t)h->v.M, nseg = (M + IBIS_OSEG - 1) / IBIS_OSEG;
+    HIPCHK(hipMemcpyAsync(rec, h->d_rec, (size_t)k * nseg * 32, hipMemcpyDeviceToHost, h->stream));
+    if (lik) HIPCHK(hipMemcpyAsync(lik, h->d_lik, (size_t)k * M * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    window_pending(h, y, k);
+    return SMC_OK;
+}
+
+// smc_ibis_window with the walk's three integers per step reduced on the device: k x 20 bytes come back instead of the records
+extern "C" int smc_ibis_window_ess(void* hp, const double* y, int k, double ess_min, double* ess_out, int* j_out) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !y || !ess_out || !j_out) return fail(SMC_EINVAL, "smc_ibis_window_ess: bad argument");
+    if (const int rc = enqueue_window(h, "smc_ibis_window_ess", y, k, false)) return rc;
+    const int64_t M = h->v.M, nseg = (M + IBIS_OSEG - 1) / IBIS_OSEG;
+    const int SH = table_shift_extra(nseg * IBIS_OSEG);
+    int64_t gx = (nseg + IBIS_RED_THREADS - 1) / IBIS_RED_THREADS;
+    gx = gx > 128 ? 128 : gx;
+    HIPCHK(hipMemsetAsync(h->d_K, 0, (size_t)k * 4, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_DR, 0, (size_t)k * 16, h->stream));
+    hipLaunchKernelGGL(k_ibis_rec_kmax, dim3((unsigned)gx, (unsigned)k), dim3(IBIS_RED_THREADS), 0, h->stream, h->d_rec, nseg, h->d_K);
+    hipLaunchKernelGGL(k_ibis_rec_sums, dim3((unsigned)gx, (unsigned)k), dim3(IBIS_RED_THREADS), 0, h->stream, h->d_rec, nseg, SH, h->d_K,
+                       h->d_DR);
+    HIPCHK(hipGetLastError());
+    uint32_t Kb[IBIS_MAX_WINDOW];
+    unsigned long long DR[IBIS_MAX_WINDOW * 2];
+    HIPCHK(hipMemcpyAsync(Kb, h->d_K, (size_t)k * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(DR, h->d_DR, (size_t)k * 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    int j = 0;
+    while (j < k) {          // smc_host_outer_walk
+        double logmu, ess;
+        combine_outputs(ibis_unbias_k(Kb[j]), DR[2 * j], DR[2 * j + 1], SH, M, logmu, ess);
+        ess_out[j++] = ess;
+        if (ess < ess_min) break;
+    }
+    *j_out = j;
+    window_pending(h, y, k);
     return SMC_OK;
 }
 
@@ -428,6 +488,105 @@ extern "C" int smc_ibis_rejuvenate(void* hp, const double* y, int64_t T, double 
     if (moved) HIPCHK(hipMemcpyAsync(moved, h->d_moved, (size_t)h->v.M, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (accepted) *accepted = (int64_t)n;
+    h->have_moved = true;
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_get_moved(void* hp, uint8_t* moved) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !moved) return fail(SMC_EINVAL, "smc_ibis_get_moved: bad argument");
+    if (!h->have_moved) return fail(SMC_ESTATE, "smc_ibis_get_moved: smc_ibis_rejuvenate has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(moved, h->d_moved, (size_t)h->v.M, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return SMC_OK;
+}
+
+namespace {
+// inclusive scan of f(0 .. n) into out [n]; tsum: ceil(n / IBIS_RED_THREADS) words of scratch
+template <class F>
+void launch_scan(ibis_t h, F f, int64_t n, uint64_t* tsum, uint64_t* out) {
+    const int64_t ntile = (n + IBIS_RED_THREADS - 1) / IBIS_RED_THREADS;
+    hipLaunchKernelGGL((k_ibis_scan_sums<F>), dim3((unsigned)ntile), dim3(IBIS_RED_THREADS), 0, h->stream, f, n, tsum);
+    hipLaunchKernelGGL(k_ibis_scan_offsets, dim3(1), dim3(IBIS_RED_THREADS), 0, h->stream, tsum, ntile);
+    hipLaunchKernelGGL((k_ibis_scan_tiles<F>), dim3((unsigned)ntile), dim3(IBIS_RED_THREADS), 0, h->stream, f, n, (const uint64_t*)tsum, out);
+}
+template <int D>
+void launch_moments(ibis_t h, int weighted, int64_t nchunk) {
+    const int64_t M = h->v.M;
+    const int ntri = D * (D + 1) / 2;
+    hipLaunchKernelGGL((k_ibis_mom_chunks<D, 1>), dim3((unsigned)nchunk), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, weighted,
+                       (const uint32_t*)h->d_K, (const double*)h->d_mom, h->d_mpart);
+    hipLaunchKernelGGL(k_ibis_mom_combine, dim3(1), dim3(IBIS_THREADS), 0, h->stream, (const double*)h->d_mpart, D, nchunk,
+                       h->d_mom + IBIS_MOM_MEAN, weighted ? 0 : 1, (double)M, weighted, (const double*)h->d_mom);
+    hipLaunchKernelGGL((k_ibis_mom_chunks<D, 2>), dim3((unsigned)nchunk), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, weighted,
+                       (const uint32_t*)h->d_K, (const double*)h->d_mom, h->d_mpart);
+    hipLaunchKernelGGL(k_ibis_mom_combine, dim3(1), dim3(IBIS_THREADS), 0, h->stream, (const double*)h->d_mpart, ntri, nchunk,
+                       h->d_mom + IBIS_MOM_COV, weighted ? 0 : 1, (double)(M - 1), weighted, (const double*)h->d_mom);
+}
+}  // namespace
+
+// resample!(ibis) without the host: the ancestors of smc_host_outer_resample(logw, M, M, seed) for the committed logw, bit for
+// bit (steps 1-6 of its specification as kernels), then the gather of smc_ibis_permute with `a` left on the device
+extern "C" int smc_ibis_resample(void* hp, uint64_t seed, int32_t* a_out) {
+    ibis_t h = as_ibis(hp);
+    if (!h) return fail(SMC_EINVAL, "smc_ibis_resample: not an IBIS handle");
+    if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_resample: smc_ibis_set_theta has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    h->win_k = 0;
+    const int64_t M = h->v.M, nseg = (M + IBIS_OSEG - 1) / IBIS_OSEG, ntile = (M + IBIS_RED_THREADS - 1) / IBIS_RED_THREADS;
+    const int SH = table_shift_extra(nseg * IBIS_OSEG);
+    // (each buffer on its own: a call that ran out of memory half way leaves the rest to the next one)
+    if (!h->d_q) HIPCHK(hipMalloc((void**)&h->d_q, (size_t)M * 8));
+    if (!h->d_seg) HIPCHK(hipMalloc((void**)&h->d_seg, (size_t)(2 * nseg + ntile) * 8));
+    if (!h->d_skb) HIPCHK(hipMalloc((void**)&h->d_skb, (size_t)nseg * 4));
+    if (!h->d_cnt) HIPCHK(hipMalloc((void**)&h->d_cnt, (size_t)M * 4));
+    uint64_t *sS = h->d_seg, *Dcum = h->d_seg + nseg, *tsum = h->d_seg + 2 * nseg;
+    HIPCHK(hipMemsetAsync(h->d_K, 0, 4, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_cnt, 0, (size_t)M * 4, h->stream));
+    hipLaunchKernelGGL(k_ibis_rs_weights, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cs, h->d_q, h->d_skb, sS, h->d_K);
+    launch_scan(h, IbisSegQ{h->d_skb, sS, h->d_K, SH}, nseg, tsum, Dcum);
+    hipLaunchKernelGGL(k_ibis_rs_draw, dim3(grid_of((M + 1) / 2)), dim3(IBIS_THREADS), 0, h->stream, M, seed, (const uint64_t*)h->d_q,
+                       (const uint32_t*)h->d_skb, (const uint32_t*)h->d_K, SH, (const uint64_t*)Dcum, nseg, h->d_cnt);
+    launch_scan(h, IbisCount{h->d_cnt}, M, tsum, h->d_q);          // (the weights are spent: their array takes the scan of cnt)
+    hipLaunchKernelGGL(k_ibis_rs_expand, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, M, (const uint64_t*)h->d_q, h->d_a);
+    hipLaunchKernelGGL(k_ibis_permute, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->d_a);
+    HIPCHK(hipGetLastError());
+    if (a_out) HIPCHK(hipMemcpyAsync(a_out, h->d_a, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->cp ^= 1;
+    h->cs ^= 1;
+    return SMC_OK;
+}
+
+// mean [d] and cov [d][d] of the committed theta cloud (smc_spec.h "moments of the theta cloud"); (d + d^2) doubles come back
+extern "C" int smc_ibis_theta_moments(void* hp, int weighted, double* mean, double* cov) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !mean || !cov) return fail(SMC_EINVAL, "smc_ibis_theta_moments: bad argument");
+    if (weighted != 0 && weighted != 1) return fail(SMC_EINVAL, "smc_ibis_theta_moments: weighted is 0 or 1");
+    if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_theta_moments: smc_ibis_set_theta has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t nchunk = grid_of(h->v.M);
+    const int d = h->spec.d;
+    if (!h->d_mpart) HIPCHK(hipMalloc((void**)&h->d_mpart, (size_t)THETA_MOM_NTRI * (size_t)nchunk * 8));
+    if (weighted) {
+        HIPCHK(hipMemsetAsync(h->d_K, 0, 4, h->stream));
+        hipLaunchKernelGGL(k_ibis_kmax, dim3((unsigned)nchunk), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cs, h->d_K);
+        hipLaunchKernelGGL(k_ibis_mom_w, dim3((unsigned)nchunk), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cs, (const uint32_t*)h->d_K,
+                           h->d_mpart);
+        hipLaunchKernelGGL(k_ibis_mom_combine, dim3(1), dim3(IBIS_THREADS), 0, h->stream, (const double*)h->d_mpart, 1, nchunk, h->d_mom, 0,
+                           0.0, 0, (const double*)h->d_mom);
+    }
+#define IBIS_CALL_MOM(D) launch_moments<D>(h, weighted, nchunk)
+    IBIS_BY_D(d, IBIS_CALL_MOM)
+    HIPCHK(hipGetLastError());
+    double mom[IBIS_MOM_N];
+    HIPCHK(hipMemcpyAsync(mom, h->d_mom, sizeof(mom), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < d; ++i) {
+        mean[i] = mom[IBIS_MOM_MEAN + i];
+        for (int j = 0; j <= i; ++j) cov[i * d + j] = cov[j * d + i] = mom[IBIS_MOM_COV + i * (i + 1) / 2 + j];
+    }
     return SMC_OK;
 }
 

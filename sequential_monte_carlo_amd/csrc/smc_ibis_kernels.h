@@ -365,4 +365,253 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_permute(IbisView v, int c
     v.logw[cs ^ 1][m] = v.logw[cs][src];
 }
 
+// ---- the resample-move loop without a read of the cloud (IBIS(..., device_moves=True)) ---------------------------------------
+// Everything here is a reduction, a scan or a search over the cloud in INTEGER arithmetic (any order gives the same bits), or the
+// chunk / tree / left-to-right sums of smc_spec.h "moments of the theta cloud".  No float atomics.
+constexpr int IBIS_RED_THREADS = 256;
+constexpr uint32_t IBIS_KBIAS = 1u << 30;   // an exponent k, |k| < 2^30, travels as the unsigned k + 2^30 >= 1; 0: no live entry
+
+SMC_HD uint32_t ibis_bias_k(int k) { return k == IBIS_SUM_DEADK ? 0u : (uint32_t)k + IBIS_KBIAS; }
+SMC_HD int ibis_unbias_ki(uint32_t kb) { return kb ? (int)(kb - IBIS_KBIAS) : IBIS_SUM_DEADK; }
+SMC_HD double ibis_unbias_k(uint32_t kb) { return kb ? (double)(int)(kb - IBIS_KBIAS) : -inf(); }
+
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, s, 64);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, s, 64); v = o > v ? o : v; }
+    return v;
+}
+
+// K = max kb of every step's records (smc_outer.hip combine()); rec [k][nseg][4], Kb [k] zeroed by the caller.  grid (x, k)
+__global__ __launch_bounds__(IBIS_RED_THREADS) void k_ibis_rec_kmax(const uint64_t* rec, int64_t nseg, uint32_t* Kb) {
+    const uint64_t* r = rec + (size_t)blockIdx.y * (size_t)nseg * 4;
+    uint32_t v = 0;
+    for (int64_t b = (int64_t)blockIdx.x * IBIS_RED_THREADS + threadIdx.x; b < nseg; b += (int64_t)gridDim.x * IBIS_RED_THREADS) {
+        const double kb = bits2d(r[b * 4]);
+        const uint32_t o = kb > -inf() ? ibis_bias_k((int)kb) : 0u;
+        v = o > v ? o : v;
+    }
+    v = wave_max_u32(v);
+    if ((threadIdx.x & 63) == 0 && v) atomicMax(&Kb[blockIdx.y], v);
+}
+// D = sum seg_Q(S_b, sh_b), R = sum seg_R(hi_b, lo_b, sh_b, SH) of every step; DR [k][2] zeroed by the caller
+__global__ __launch_bounds__(IBIS_RED_THREADS) void k_ibis_rec_sums(const uint64_t* rec, int64_t nseg, int SH, const uint32_t* Kb,
+                                                                   unsigned long long* DR) {
+    const uint64_t* r = rec + (size_t)blockIdx.y * (size_t)nseg * 4;
+    const double K = ibis_unbias_k(Kb[blockIdx.y]);
+    uint64_t D = 0, R = 0;
+    for (int64_t b = (int64_t)blockIdx.x * IBIS_RED_THREADS + threadIdx.x; b < nseg; b += (int64_t)gridDim.x * IBIS_RED_THREADS) {
+        const int sh = seg_shift(K, bits2d(r[b * 4]), SH);
+        D += seg_Q(r[b * 4 + 1], sh);
+        R += seg_R(r[b * 4 + 2], r[b * 4 + 3], sh, SH);
+    }
+    D = wave_sum_u64(D);
+    R = wave_sum_u64(R);
+    if ((threadIdx.x & 63) == 0) {
+        if (D) atomicAdd(&DR[2 * blockIdx.y], (unsigned long long)D);
+        if (R) atomicAdd(&DR[2 * blockIdx.y + 1], (unsigned long long)R);
+    }
+}
+
+// resample!(ibis), step 1 (smc_host_outer_resample): the fixed-point weight q of every particle of the committed logw, the
+// (kb, S) of every segment of 8, and the cloud's K (Kb zeroed by the caller)
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rs_weights(IbisView v, int cs, uint64_t* q, uint32_t* skb, uint64_t* sS, uint32_t* Kb) {
+    const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
+    const bool valid = m < v.M;
+    const int64_t mm = valid ? m : v.M - 1;
+    const double logw = v.logw[cs][mm];
+    const bool alive = valid && lw_alive(logw);
+    double kd = 0.0;
+    const double p = sp_exp_parts(alive ? logw : 0.0, kd);
+    const int ki = alive ? (int)kd : IBIS_SUM_DEADK;
+    const int kb = seg8_max(ki);
+    const uint64_t qi = alive ? fix_weight_i(p, ki - kb, FIX_BITS) : 0;
+    const uint64_t Ssum = seg8_sum(qi);
+    if (valid) q[m] = qi;
+    if (valid && (threadIdx.x & (IBIS_OSEG - 1)) == 0) {
+        skb[m / IBIS_OSEG] = ibis_bias_k(kb);
+        sS[m / IBIS_OSEG] = kb == IBIS_SUM_DEADK ? 0 : Ssum;
+    }
+    const uint32_t K = wave_max_u32(ibis_bias_k(kb));
+    if (threadIdx.x == 0 && K) atomicMax(Kb, K);
+}
+
+// the addends of the two scans: seg_Q(S_b, sh_b) of segment b, and the number of draws that fell on particle i
+struct IbisSegQ {
+    const uint32_t* skb; const uint64_t* sS; const uint32_t* Kb; int SH;
+    __device__ __forceinline__ uint64_t operator()(int64_t b) const { return seg_Q(sS[b], seg_shift(ibis_unbias_k(*Kb), ibis_unbias_k(skb[b]), SH)); }
+};
+struct IbisCount {
+    const int32_t* cnt;
+    __device__ __forceinline__ uint64_t operator()(int64_t i) const { return (uint64_t)cnt[i]; }
+};
+
+// inclusive scan over the workgroup (IBIS_RED_THREADS lanes); total: the sum of all of them.  Integers: the order is free.
+__device__ __forceinline__ uint64_t block_scan_u64(uint64_t v, uint64_t* wsum /*[IBIS_RED_THREADS / 64] in LDS*/, uint64_t& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const uint64_t o = (uint64_t)__shfl_up((unsigned long long)v, s, 64);
+        v += lane >= s ? o : 0;
+    }
+    __syncthreads();                    // (a caller in a loop: the sums of the last round have been read)
+    if (lane == 63) wsum[w] = v;
+    __syncthreads();
+    uint64_t off = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < IBIS_RED_THREADS / 64; ++i) { off += i < w ? wsum[i] : 0; tot += wsum[i]; }
+    total = tot;
+    return v + off;
+}
+// reduce-then-scan of f(0..n): tile sums, their exclusive scan by one workgroup, then the scan of every tile on top of its offset
+template <class F>
+__global__ __launch_bounds__(IBIS_RED_THREADS) void k_ibis_scan_sums(F f, int64_t n, uint64_t* tsum) {
+    __shared__ uint64_t wsum[IBIS_RED_THREADS / 64];
+    const int64_t i = (int64_t)blockIdx.x * IBIS_RED_THREADS + threadIdx.x;
+    uint64_t total;
+    block_scan_u64(i < n ? f(i) : 0, wsum, total);
+    if (threadIdx.x == 0) tsum[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(IBIS_RED_THREADS) void k_ibis_scan_offsets(uint64_t* tsum, int64_t ntile) {
+    __shared__ uint64_t wsum[IBIS_RED_THREADS / 64];
+    uint64_t carry = 0;
+    for (int64_t base = 0; base < ntile; base += IBIS_RED_THREADS) {
+        const int64_t i = base + threadIdx.x;
+        const uint64_t v = i < ntile ? tsum[i] : 0;
+        uint64_t total;
+        const uint64_t incl = block_scan_u64(v, wsum, total);
+        if (i < ntile) tsum[i] = carry + incl - v;
+        carry += total;
+    }
+}
+template <class F>
+__global__ __launch_bounds__(IBIS_RED_THREADS) void k_ibis_scan_tiles(F f, int64_t n, const uint64_t* tsum, uint64_t* out) {
+    __shared__ uint64_t wsum[IBIS_RED_THREADS / 64];
+    const int64_t i = (int64_t)blockIdx.x * IBIS_RED_THREADS + threadIdx.x;
+    uint64_t total;
+    const uint64_t incl = block_scan_u64(i < n ? f(i) : 0, wsum, total);
+    if (i < n) out[i] = tsum[blockIdx.x] + incl;
+}
+
+// first index with c[i] > T in the non-decreasing c [n]; the caller guarantees T < c[n - 1], so the result is in [0, n)
+__device__ __forceinline__ int64_t first_greater(const uint64_t* c, int64_t n, uint64_t T) {
+    int64_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (c[mid] > T) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+// step 5: lane p takes the draws 2p and 2p + 1 (the two 64-bit halves of one Philox call); cnt [M] zeroed by the caller.
+// Dtot = 0 (no live particle): every particle is drawn once, the identity.
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rs_draw(int64_t M, uint64_t seed, const uint64_t* q, const uint32_t* skb,
+                                                              const uint32_t* Kb, int SH, const uint64_t* Dcum, int64_t nseg, int32_t* cnt) {
+    const int64_t pr = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x, j0 = 2 * pr;
+    if (j0 >= M) return;
+    const uint64_t Dtot = Dcum[nseg - 1];
+    if (Dtot == 0) {
+        cnt[j0] = 1;
+        if (j0 + 1 < M) cnt[j0 + 1] = 1;
+        return;
+    }
+    const double K = ibis_unbias_k(*Kb);
+    const u32x4 w = draw(seed, (uint32_t)pr, OUTER_STREAM, 0u, SLOT_OUTER);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (j0 + h >= M) break;
+        const uint64_t pick = ((uint64_t)w.v[2 * h + 1] << 32) | w.v[2 * h];
+        uint64_t T, lo;
+        mul64wide(pick, Dtot, T, lo);
+        const int64_t b = first_greater(Dcum, nseg, T);                       // T < Dtot = Dcum[nseg - 1]
+        const uint64_t thr = sys_threshold(T - (b ? Dcum[b - 1] : 0), seg_shift(K, ibis_unbias_k(skb[b]), SH));
+        const int64_t i0 = b * IBIS_OSEG;
+        const int cn = (int)(M - i0 < IBIS_OSEG ? M - i0 : IBIS_OSEG);
+        uint64_t C = 0;
+        int i = 0;
+#pragma unroll
+        for (int t = 0; t < IBIS_OSEG; ++t)
+            if (t < cn) { C += q[i0 + t]; i += C <= thr ? 1 : 0; }
+        atomicAdd(&cnt[i0 + (i < cn ? i : cn - 1)], 1);
+    }
+}
+// step 6: a = the expansion of cnt in index order; cincl [M] the inclusive scan of cnt (cincl[M - 1] = M)
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rs_expand(int64_t M, const uint64_t* cincl, int32_t* a) {
+    const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
+    if (m >= M) return;
+    a[m] = (int32_t)first_greater(cincl, M, (uint64_t)m);
+}
+
+// ---- moments of the theta cloud (smc_spec.h) -----------------------------------------------------------------------------------
+// mom: [0] W | [1 .. 8] mean | [9 .. 9 + 36) cov, lower triangle row by row.  part: [column][nchunk].  One wave per chunk.
+constexpr int IBIS_MOM_MEAN = 1, IBIS_MOM_COV = 1 + MAX_DTHETA, IBIS_MOM_N = 1 + MAX_DTHETA + THETA_MOM_NTRI;
+
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_kmax(IbisView v, int cs, uint32_t* Kb) {
+    const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
+    const bool valid = m < v.M;
+    int k;
+    (void)ibis_sum_parts(v.logw[cs][valid ? m : v.M - 1], valid, k);
+    const uint32_t K = wave_max_u32(ibis_bias_k(k));
+    if (threadIdx.x == 0 && K) atomicMax(Kb, K);
+}
+// u of the calling lane (weighted mode)
+__device__ __forceinline__ double ibis_mom_u(const IbisView& v, int cs, int64_t mm, bool valid, const uint32_t* Kb) {
+    int k;
+    const double p = ibis_sum_parts(v.logw[cs][mm], valid, k);
+    return theta_mom_u(p, k, ibis_unbias_ki(*Kb));
+}
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_mom_w(IbisView v, int cs, const uint32_t* Kb, double* part) {
+    const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
+    const bool valid = m < v.M;
+    const double t = wave_tree_sum(ibis_mom_u(v, cs, valid ? m : v.M - 1, valid, Kb));
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+// PASS 1: the sums of c theta_i; PASS 2: the sums of c (d_i d_j), j <= i, about the means in mom
+template <int D, int PASS>
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_mom_chunks(IbisView v, int cp, int cs, int weighted, const uint32_t* Kb, const double* mom,
+                                                                 double* part) {
+    const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x, nchunk = gridDim.x;
+    const bool valid = m < v.M;
+    const int64_t mm = valid ? m : v.M - 1;
+    double c = valid ? 1.0 : 0.0;
+    if (weighted) {
+        const double u = ibis_mom_u(v, cs, mm, valid, Kb);
+        c = u > 0.0 ? u / mom[0] : 0.0;
+    }
+    const bool on = c > 0.0;
+    double th[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) th[i] = v.theta[cp][mm * MAX_DTHETA + i];
+    if (PASS == 1) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            const double t = wave_tree_sum(theta_mom_term(on, c, th[i]));
+            if (threadIdx.x == 0) part[i * nchunk + blockIdx.x] = t;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < D; ++i) th[i] = th[i] - mom[IBIS_MOM_MEAN + i];
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) {
+                const double t = wave_tree_sum(theta_mom_term(on, c, th[i] * th[j]));
+                if (threadIdx.x == 0) part[(i * (i + 1) / 2 + j) * nchunk + blockIdx.x] = t;
+            }
+    }
+}
+// lane t sums column t of part over the chunks, left to right, and finishes it (theta_mom_finish) into out[t]
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_mom_combine(const double* part, int ncol, int64_t nchunk, double* out, int div_on, double div,
+                                                                  int weighted, const double* W) {
+    const int t = threadIdx.x;
+    if (t >= ncol) return;
+    const double s = left_to_right_sum(part + (size_t)t * (size_t)nchunk, nchunk);
+    out[t] = theta_mom_finish(s, div_on != 0, div, weighted != 0, weighted ? *W : 1.0);
+}
+
 }  // namespace smc

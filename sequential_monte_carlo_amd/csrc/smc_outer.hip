@@ -32,8 +32,6 @@ namespace {
 
 constexpr int OSEG = SMC_OUTER_SEG;
 constexpr int DEADK = -(1 << 30);
-constexpr uint32_t OUTER_STREAM = 0xFFFFFFFEu;   // Philox stream id of the outer level (theta particles use 0 .. M-1, simulate() 0xFFFFFFFF)
-constexpr uint32_t SLOT_OUTER = 34u;             // the pick numbers of resample!(smc)
 
 struct ORec {
     double kb;        // integral, or -inf for a segment without a live entry
@@ -436,19 +434,30 @@ extern "C" int smc_host_rw_factor(const double* theta, int64_t n, int d, double*
             for (int64_t m = 0; m < n; ++m) s = s + (theta[(size_t)m * d + i] - mean[i]) * (theta[(size_t)m * d + j] - mean[j]);
             cov[i][j] = cov[j][i] = s / (double)(n - 1);
         }
+    double flat[MAX_DTHETA * MAX_DTHETA];
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) flat[i * d + j] = cov[i][j];
+    return smc_host_rw_factor_cov(flat, d, L, univariate);
+}
+
+// The tail of random_walk_kernel from a covariance cov [d][d] (symmetric; smc_host_rw_factor's own, or the device's
+// smc_ibis_theta_moments): the Frobenius norm and the collapse rule, the 2.83^2 / d scaling, the 1e-10 jitter and the Cholesky
+// factorisation column by column.  Returns an error (and leaves L unspecified) when the scaled covariance is not positive definite.
+extern "C" int smc_host_rw_factor_cov(const double* cov, int d, double* L, int* univariate) {
+    if (!cov || !L || d < 1 || d > MAX_DTHETA) return fail("smc_host_rw_factor_cov: bad argument");
     double fro = 0.0;
     for (int i = 0; i < d; ++i)
-        for (int j = 0; j < d; ++j) fro = fro + cov[i][j] * cov[i][j];
+        for (int j = 0; j < d; ++j) fro = fro + cov[i * d + j] * cov[i * d + j];
     const bool collapsed = sqrt(fro) < 1e-8;
     const double dth = 2.83 * 2.83;
     if (univariate) *univariate = d == 1 ? 1 : 0;
     if (d == 1) {
-        L[0] = collapsed ? 1e-2 : dth * cov[0][0] + 1e-10;
+        L[0] = collapsed ? 1e-2 : dth * cov[0] + 1e-10;
         return SMC_OK;
     }
     double S[MAX_DTHETA][MAX_DTHETA];
     for (int i = 0; i < d; ++i)
-        for (int j = 0; j < d; ++j) S[i][j] = collapsed ? (i == j ? 1e-2 : 0.0) : (dth / (double)d) * cov[i][j] + (i == j ? 1e-10 : 0.0);
+        for (int j = 0; j < d; ++j) S[i][j] = collapsed ? (i == j ? 1e-2 : 0.0) : (dth / (double)d) * cov[i * d + j] + (i == j ? 1e-10 : 0.0);
     for (int i = 0; i < d * d; ++i) L[i] = 0.0;
     for (int j = 0; j < d; ++j) {
         double s = S[j][j];
@@ -462,5 +471,57 @@ extern "C" int smc_host_rw_factor(const double* theta, int64_t n, int d, double*
             L[i * d + j] = t / ljj;
         }
     }
+    return SMC_OK;
+}
+
+// Moments of a theta cloud [M][d] (smc_spec.h "moments of the theta cloud"): the host twin of smc_ibis_theta_moments, the same
+// bits.  logw [M] is read in the weighted mode only (NULL otherwise).  mean [d], cov [d][d].
+extern "C" int smc_host_theta_moments(const double* theta, const double* logw, int64_t M, int d, int weighted, double* mean, double* cov) {
+    if (!theta || !mean || !cov || M < 1 || d < 1 || d > MAX_DTHETA || (weighted && !logw)) return fail("smc_host_theta_moments: bad argument");
+    const int64_t nchunk = (M + IBIS_SUM_CHUNK - 1) / IBIS_SUM_CHUNK;
+    const bool wt = weighted != 0;
+    std::vector<double> cf((size_t)M, 1.0);          // c_m; 0 for a particle that takes no part
+    // sum over the cloud of term(l, m) for the lanes l of every chunk: the tree within the chunk, the chunks left to right
+    auto cloud_sum = [&](auto term) {
+        double acc = 0.0;
+        for (int64_t c = 0; c < nchunk; ++c) {
+            double t[IBIS_SUM_CHUNK];
+            for (int l = 0; l < IBIS_SUM_CHUNK; ++l) {
+                const int64_t m = c * IBIS_SUM_CHUNK + l;
+                t[l] = m < M ? term(m) : 0.0;
+            }
+            for (int s = 1; s < IBIS_SUM_CHUNK; s <<= 1)
+                for (int l = 0; l < IBIS_SUM_CHUNK; l += 2 * s) t[l] = t[l] + t[l + s];
+            acc = acc + t[0];
+        }
+        return acc;
+    };
+    double W = 1.0;
+    if (wt) {
+        std::vector<double> p((size_t)M);
+        std::vector<int> k((size_t)M);
+        int K = IBIS_SUM_DEADK;
+        for (int64_t m = 0; m < M; ++m) {
+            p[(size_t)m] = ibis_sum_parts(logw[m], true, k[(size_t)m]);
+            K = k[(size_t)m] > K ? k[(size_t)m] : K;
+        }
+        for (int64_t m = 0; m < M; ++m) cf[(size_t)m] = theta_mom_u(p[(size_t)m], k[(size_t)m], K);
+        W = cloud_sum([&](int64_t m) { return cf[(size_t)m]; });
+        for (int64_t m = 0; m < M; ++m) cf[(size_t)m] = cf[(size_t)m] > 0.0 ? cf[(size_t)m] / W : 0.0;
+    }
+    double mu[MAX_DTHETA];
+    for (int i = 0; i < d; ++i) {
+        const double s = cloud_sum([&](int64_t m) { return theta_mom_term(cf[(size_t)m] > 0.0, cf[(size_t)m], theta[(size_t)m * d + i]); });
+        mu[i] = theta_mom_finish(s, !wt, (double)M, wt, W);
+        mean[i] = mu[i];
+    }
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j <= i; ++j) {
+            const double s = cloud_sum([&](int64_t m) {
+                const double di = theta[(size_t)m * d + i] - mu[i], dj = theta[(size_t)m * d + j] - mu[j];
+                return theta_mom_term(cf[(size_t)m] > 0.0, cf[(size_t)m], di * dj);
+            });
+            cov[i * d + j] = cov[j * d + i] = theta_mom_finish(s, !wt, (double)(M - 1), wt, W);
+        }
     return SMC_OK;
 }

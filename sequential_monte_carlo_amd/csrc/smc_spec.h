@@ -33,6 +33,8 @@ constexpr uint32_t SLOT_SYS = 10u;       // the one uniform of a systematic resa
 constexpr uint32_t SLOT_BREAK = 16u;     // block break points: 16+2i normal, 17+2i uniform, i < 8; pair = block
 constexpr uint32_t SLOT_PMMH_Z = 32u;    // PMMH proposal normals of a parameter particle: pair k holds z[2k], z[2k+1]
 constexpr uint32_t SLOT_PMMH_U = 33u;    // the uniform of its accept test
+constexpr uint32_t SLOT_OUTER = 34u;     // the pick numbers of resample!(smc) / resample!(ibis), stream OUTER_STREAM
+constexpr uint32_t OUTER_STREAM = 0xFFFFFFFEu;   // Philox stream id of the outer level (theta particles use 0 .. M-1, simulate() 0xFFFFFFFF)
 constexpr int MAX_DTHETA = 8;            // parameter dimension of the samplers (SMC_MAX_DTHETA)
 
 constexpr double HALF_LOG2PI = 0x1.d67f1c864beb5p-1;
@@ -869,6 +871,31 @@ SMC_HD void ibis_sum_second(const double* r, double f, double D, double y, doubl
     const double ey = r[ISF_CY] - y, ex = r[ISF_CX] - xbar;
     b[0] = on ? ((f * r[ISF_MY]) / D + (2.0 * ey) * ((f * r[ISF_DY]) / D)) + Om * (ey * ey) : 0.0;
     b[1] = on ? ((f * r[ISF_MX]) / D + (2.0 * ex) * ((f * r[ISF_DX]) / D)) + Om * (ex * ex) : 0.0;
+}
+
+// ---- moments of the theta cloud of an IBIS sampler (random_walk_kernel, smc_samplers.jl:87-101; expected_parameters, ibis.jl:60-64) --
+// theta [M][d], outer log-weights logw [M].  Two modes, one order of operations - a function of the arrays alone:
+//   unweighted:  c_m = 1 for every particle;                       mean = (sum theta) / M,   cov = (sum dd') / (M - 1)  (corrected)
+//   weighted:    c_m = u_m / W, u_m = p_m 2^(k_m - K), W = sum u;  mean = sum c theta,       cov = sum c dd'            (uncorrected)
+// with d = theta - mean (the CENTRED second pass), exp(logw) = p 2^k (ibis_sum_parts; a particle takes part iff lw_alive),
+// K = max k over the live particles (an integer maximum: any order) and u = 0 for a dead particle or k - K <= THETA_MOM_MINK.
+// A particle with u = 0 contributes +0.0 to every sum whatever its theta (NaN included).  Every sum - W, then the d sums of
+// c theta_i, then the d (d + 1) / 2 sums of c (d_i d_j), j <= i - is taken the way the summaries above take theirs: CHUNKS of
+// IBIS_SUM_CHUNK = 64 consecutive particles (the last one padded with +0.0), the butterfly TREE a[i] += a[i ^ 1], ^ 2, .., ^ 32
+// within a chunk, the chunks LEFT TO RIGHT from 0.0.  The weights are normalised before they multiply (c = u / W), so a cloud
+// whose weight sits on one particle has c = 1 there: mean = that theta exactly and cov = 0 exactly.  W = 0 (no live particle), and
+// M = 1 in the unweighted mode, give NaN.  smc_host_theta_moments is this paragraph on the host, smc_ibis_theta_moments on the device.
+constexpr int THETA_MOM_MINK = -960;     // (u / W stays a normal number: W < 2^31)
+constexpr int THETA_MOM_NTRI = MAX_DTHETA * (MAX_DTHETA + 1) / 2;
+SMC_HD double theta_mom_u(double p, int k, int K) { return (k != IBIS_SUM_DEADK && k - K > THETA_MOM_MINK) ? scale2(p, k - K) : 0.0; }
+// the addend of a particle with coefficient c (on: it takes part) for the value v
+SMC_HD double theta_mom_term(bool on, double c, double v) { return on ? c * v : 0.0; }
+// what a finished sum s becomes: s / div when div_on (NaN for div = 0), and NaN for a weighted cloud without a live particle
+SMC_HD double theta_mom_finish(double s, bool div_on, double div, bool weighted, double W) {
+    const double nan = bits2d(0x7ff8000000000000ULL);
+    if (div_on) s = div > 0.0 ? s / div : nan;
+    if (weighted) s = W > 0.0 ? s : nan;
+    return s;
 }
 
 // ---- segment combine (integers only) ----------------------------------------------------------

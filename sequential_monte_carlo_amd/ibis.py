@@ -3,6 +3,7 @@ the univariate LinearModel (UnivariateLinearGaussian, unobserved_components).
 
     IBIS(M, model, prior, chain, ess_threshold, min_ar=-1.0)        ibis.jl:26-58
     smc2 / smc2_step / smc2_run, resample_, rejuvenate_, expected_parameters, density_tempered   (smc_samplers.py dispatches here)
+    posterior_moments: the weighted mean and covariance of the theta cloud, reduced on the device
     observation_dist, estimated_trend, quantile (plotting_utils.jl:94-137), filtered_state: reductions over the cloud on the device
 
 A parameter particle owns O(1) state - theta, its model row, (x, Sigma), logZ, logw - and all of it lives on the device for the
@@ -11,6 +12,13 @@ one launch that also computes the outer reweight's segment records, and rejuvena
 re-filters included.  So the cloud can be very large (M = 2^20 is 16 MB of state).  The host keeps what the reference keeps
 outside the loop over m: the ESS decision, the index draw of resample! and the random-walk factor (one read of theta per
 rejuvenation), all by the library's outer-level routines, as for SMC.
+
+device_moves=True keeps those three on the device as well (smc_ibis_window_ess, smc_ibis_resample, smc_ibis_theta_moments): a
+whole smc2_run then reads no array of length M and no record array - per window ess [k] and j, per resample-move d + d^2
+doubles and the acceptance count, and the rows of the summaries when they are recorded.  The ESS walk and the index draw are
+the same integer functions on both paths, the same bits; the covariance of the random-walk factor is summed in the device's
+order (chunks of 64, a tree within, chunks left to right) instead of the host's index order, so after the first rejuvenation
+the two paths agree up to that rounding only.  That is why the flag is opt-in; the default makes the calls it always made.
 
 `model` is the reference's closure and is kept for the caller; the device evaluates `theta_map` (ThetaMap to LG1D rows) and a
 prior of the enumerated families instead - a GPU cannot call a closure, so both are required.
@@ -34,7 +42,8 @@ class IBIS:
     as SMC draws it (the same cloud for the same seed).  Arrays (theta, x, Sigma, logZ, logw, omega) are read from the device
     on access; no device call is made before the first sampler call."""
 
-    def __init__(self, M, model, prior, chain, ess_threshold, min_ar=-1.0, seed=1, theta_map=None, device=0, predict_first=False):
+    def __init__(self, M, model, prior, chain, ess_threshold, min_ar=-1.0, seed=1, theta_map=None, device=0, predict_first=False,
+                 device_moves=False):
         self.M, self.model, self.prior, self.chain = int(M), model, prior, int(chain)
         if theta_map is None or getattr(theta_map, "model_id", None) != _lib.MODEL_LG1D:
             raise TypeError("IBIS needs theta_map=ThetaMap(LG1D rows): the Kalman filter inside runs on the GPU, which cannot call "
@@ -55,7 +64,7 @@ class IBIS:
             raise TypeError("the prior's spec() must describe every component of theta (at most %d)" % _lib.MAX_DTHETA)
         if self.chain > 64:
             raise ValueError("chain <= 64")
-        self.device, self.predict_first = int(device), bool(predict_first)
+        self.device, self.predict_first, self.device_moves = int(device), bool(predict_first), bool(device_moves)
         self.ess = float(self.M)
         self.ess_min = self.M * float(ess_threshold)
         self.acc_threshold, self.acc_ratio = float(min_ar), 0.0
@@ -78,6 +87,7 @@ class IBIS:
 
     def close(self):
         if self._h is not None:
+            self._keep_accepted()
             self._h.close()
             self._h = None
 
@@ -92,6 +102,25 @@ class IBIS:
             rows = self.theta_map.rows(self._theta0)
             return {"x": rows[:, 4].copy(), "S": rows[:, 5].copy()}.get(name, np.zeros(self.M))
         return self._h.get(**{name: True})[name]
+
+    @property
+    def accepted(self):
+        """acc_array of the last rejuvenate! (ibis.jl:87); with device_moves the mask stays on the device until it is asked for"""
+        if self._accepted is None:
+            self._accepted = self._h.get_moved() if self._h is not None else np.zeros(self.M, dtype=bool)
+        return self._accepted
+
+    def _keep_accepted(self):
+        """fetch a mask that is still on the device, before the handle forgets it (close, a new set_theta)"""
+        if self._accepted is None and self._h is not None:
+            try:
+                self._accepted = self._h.get_moved()
+            except _lib.SmcError:                          # the handle was reset behind the sampler's back: no mask to keep
+                self._accepted = np.zeros(self.M, dtype=bool)
+
+    @accepted.setter
+    def accepted(self, value):
+        self._accepted = value
 
     theta = property(lambda self: self._get("theta"))
     x = property(lambda self: self._get("x"))
@@ -132,8 +161,11 @@ def _window(ibis, y, ess_min, t=None):
     if want != getattr(h, "_recording", (False, 0)):       # (a run without summaries makes the calls it made before)
         h.set_summaries(*want)
         h._recording = want
-    rec, _ = h.window(y)
-    ess, j = _lib.host_outer_walk(rec, ibis.M, ess_min)
+    if ibis.device_moves:
+        ess, j = h.window_ess(y, ess_min)                  # the same walk, on three integers per step reduced on the device
+    else:
+        rec, _ = h.window(y)
+        ess, j = _lib.host_outer_walk(rec, ibis.M, ess_min)
     if summ is not None:
         for i, r in enumerate(h.get_summaries(j)):
             q = None if summ["p"] is None else _normal_quantiles(r[0], r[1], summ["p"])
@@ -202,6 +234,7 @@ def smc2(ibis, y):
     y = np.asarray(y, dtype=np.float64)
     h = ibis._handle()
     if ibis.t != 0:
+        ibis._keep_accepted()
         h.set_theta(ibis.theta)           # again from (x0, sigma0), logZ = logw = 0
     ibis.summary_trace = []
     ess, _ = _window(ibis, y[:1], 0.0, 1)
@@ -211,7 +244,13 @@ def smc2(ibis, y):
 
 
 def resample_(ibis, logw=None):
-    """resample!(ibis)   ibis.jl:73-84 - value copies (the reference's aliasing of equal ancestors is not inherited)"""
+    """resample!(ibis)   ibis.jl:73-84 - value copies (the reference's aliasing of equal ancestors is not inherited).
+    With device_moves the draw and the gather stay on the device (given log-weights are set first) and None is returned."""
+    if ibis.device_moves:
+        if logw is not None:
+            ibis._handle().set_logw(logw)
+        ibis._handle().resample(ibis._next_seed())
+        return None
     lw = ibis.logw if logw is None else logw
     a = np.asarray(_lib.host_outer_resample(lw, ibis.M, ibis._next_seed()), dtype=np.int32)
     ibis._handle().permute(a)
@@ -224,8 +263,15 @@ def rejuvenate_(ibis, y, xi=1.0, verbose=False, out=sys.stdout):
     y = np.asarray(y, dtype=np.float64)
     if verbose:
         out.write("\t[rejuvenating]")
-    L, s = random_walk_factor(ibis.theta, 0.5 * np.arange(ibis.chain, 0, -1))       # ibis.kernel(ibis.θ), 0.5*reverse(1:chain)
-    n, ibis.accepted = ibis._handle().rejuvenate(y, float(xi), L, s, ibis._next_seed())
+    scales = 0.5 * np.arange(ibis.chain, 0, -1)                                     # 0.5*reverse(1:chain)
+    if ibis.device_moves:                                  # ibis.kernel(ibis.θ) from d + d^2 doubles: the covariance summed on the device
+        if ibis.M < 2:
+            raise ValueError("rejuvenate_ needs M >= 2: the covariance of one parameter particle is undefined")
+        L, uni = _lib.host_rw_factor_cov(ibis._handle().theta_moments(weighted=False)[1])
+        s = scales * scales if uni else scales
+    else:
+        L, s = random_walk_factor(ibis.theta, scales)                               # ibis.kernel(ibis.θ)
+    n, ibis.accepted = ibis._handle().rejuvenate(y, float(xi), L, s, ibis._next_seed(), want_moved=not ibis.device_moves)
     ibis.acc_ratio = float(n) / ibis.M
     ibis.n_rejuvenations += 1
     if verbose:
@@ -289,9 +335,19 @@ def expected_parameters(ibis):
     return (ibis.theta * w[:, None]).sum(axis=0)
 
 
+def posterior_moments(ibis):
+    """(mean [d], cov [d][d]) of theta under the normalised outer weights: mean = sum omega theta (expected_parameters up to
+    rounding), cov = sum omega (theta - mean)(theta - mean)' (uncorrected), reduced on the device - d + d^2 doubles come back
+    (smc_ibis_theta_moments).  Before the first sampler call: the same specification on the host over the initial cloud."""
+    if ibis._h is None:
+        return _lib.host_theta_moments(ibis._theta0, np.zeros(ibis.M), weighted=True)
+    return ibis._h.theta_moments(weighted=True)
+
+
 def density_tempered(ibis, y, verbose=True, out=sys.stdout):
     """density_tempered(ibis, y): the loop of smc_samplers.jl:222-281 with logZ from one whole-series Kalman pass per particle
-    (ibis.jl exports the name and has rejuvenate!(ibis, y, ξ, verbose) for it)."""
+    (ibis.jl exports the name and has rejuvenate!(ibis, y, ξ, verbose) for it).  With device_moves the resample-move of every
+    stage stays on the device; the bisection for the next exponent still reads logZ once per stage (not moved to the device)."""
     y = np.asarray(y, dtype=np.float64)
     h = ibis._handle()
     h.filter(y)

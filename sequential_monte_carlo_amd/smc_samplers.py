@@ -283,6 +283,13 @@ def expected_parameters(smc):
     return (smc.theta * w[:, None]).sum(axis=0)
 
 
+def posterior_moments(ibis):
+    """(mean [d], cov [d][d]) of theta under the normalised outer weights of an IBIS sampler, reduced on the device (ibis.py)"""
+    if not isinstance(ibis, IBIS):
+        raise TypeError("posterior_moments is defined for an IBIS sampler")
+    return _ibis.posterior_moments(ibis)
+
+
 def _per_theta(smc, local):
     """[M_local, k] rows of per-filter summaries of this rank -> [M, k] on every rank"""
     local = np.ascontiguousarray(local, dtype=np.float64)
