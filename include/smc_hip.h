@@ -63,6 +63,12 @@ int smc_set_params(smc_handle h, const double* raw /*[n_theta][n_raw]*/);
 /* Philox stream id per filter (e.g. the GLOBAL theta index when theta is sharded over GPUs). */
 int smc_set_streams(smc_handle h, const uint32_t* stream /*[n_theta]*/);
 int smc_reseed(smc_handle h, uint64_t seed);
+/* Diagnostic.  *by_value = 1 when the step launches of the next smc_step / smc_log_likelihood take the filter's stream id, parameter
+ * row and observation BY VALUE in the kernel arguments (one filter per handle, no skip mask, the host's copies of row 0 current:
+ * set through smc_set_params / smc_set_streams and not since rewritten on the device by the PMMH kernels, smc_permute,
+ * smc_copy_from, smc_unpack_slots or the exchange); 0 when they read them through device pointers.  Results never depend on it.
+ * SMC_STEP_BY_VALUE=0 in the environment at smc_create: always 0. */
+int smc_step_by_value(smc_handle h, int* by_value);
 
 /* ---- proposals: the guided particle filter ----------------------------------------------------
  * particle_filter(N, y, model, proposal) / particle_filter!(x, w, y, model, proposal)          src/particles.jl:28-84

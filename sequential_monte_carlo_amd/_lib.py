@@ -16,7 +16,7 @@ FLAG_ANCESTORS, FLAG_NO_RESIDENT, FLAG_SYSTEMATIC = 1, 2, 4
 
 # every symbol include/smc_hip.h declares
 EXPORTS = [
-    "smc_create", "smc_destroy", "smc_set_params", "smc_set_streams", "smc_reseed", "smc_init", "smc_step",
+    "smc_create", "smc_destroy", "smc_set_params", "smc_set_streams", "smc_reseed", "smc_step_by_value", "smc_init", "smc_step",
     "smc_log_likelihood", "smc_get_state", "smc_get_logZ", "smc_permute", "smc_copy_from", "smc_slot_bytes", "smc_pack_slots", "smc_unpack_slots", "smc_get_weights_raw", "smc_get_geometry",
     "smc_last_elapsed_ms", "smc_synchronize", "smc_time_step_kernel", "smc_event_overhead_ms", "smc_normalize", "smc_resample", "smc_kalman_log_likelihood", "smc_get_moments", "smc_get_quantiles", "smc_simulate", "smc_simulate_dim", "smc_model_dim",
     "smc_model_nraw", "smc_auto_seg", "smc_device_count", "smc_host_exp", "smc_host_log", "smc_host_philox4x32_10",
@@ -92,6 +92,7 @@ def lib():
     L.smc_set_params.argtypes = [h, _dp]
     L.smc_set_streams.argtypes = [h, _u32p]
     L.smc_reseed.argtypes = [h, C.c_uint64]
+    L.smc_step_by_value.argtypes = [h, C.POINTER(C.c_int)]
     L.smc_init.argtypes = [h, C.c_double, _dp]
     L.smc_step.argtypes = [h, C.c_double, _dp, _dp]
     L.smc_log_likelihood.argtypes = [h, _dp, C.c_int64, _dp, _dp, _dp]
@@ -553,6 +554,13 @@ class Handle:
 
     def reseed(self, seed):
         check(lib().smc_reseed(self._h, seed))
+
+    @property
+    def step_by_value(self):
+        """diagnostic: the next step launches take the filter's row by value in the kernel arguments (smc_step_by_value)"""
+        b = C.c_int()
+        check(lib().smc_step_by_value(self._h, C.byref(b)))
+        return bool(b.value)
 
     def init(self, y1):
         lm = np.zeros(self.n_theta)

@@ -102,15 +102,25 @@ static hipError_t do_table(smc_filter_s* h, int emit, int first_emit, uint32_t t
     hipLaunchKernelGGL((k_table<TH>), dim3(h->v.ntheta), dim3(TH), 0, h->stream, h->v, h->cur, emit, first_emit, t_emit);
     return hipGetLastError();
 }
-hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y) {
+hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y, const double* y_host) {
     if (h->v.tabD) {
         hipError_t e = do_table(h, emit_prev, t == 1u ? 1 : 0, t - 1u);
         if (e != hipSuccess) return e;
         emit_prev = 0;
     }
+    // By value (StepHot): ONE filter, no skip mask in force, the host copies of its row and stream id valid, and the observation
+    // at hand (the step API's y, or the host's copy of the series).  The results do not depend on the choice.
+    StepHot hot{};
+    hot.seed = h->v.seed; hot.t = t; hot.nseg = h->v.nseg; hot.cur = h->cur; hot.emit_prev = emit_prev; hot.yval = y;
+    if (hot_legal(h) && !h->v.skip && (!h->v.y || y_host)) {
+        hot.by_value = 1;
+        hot.stream0 = h->hot.stream0;
+        hot.prm0 = h->hot.prm0;
+        if (h->v.y) hot.yval = y_host[t];
+    }
     if (h->v.prop_kind)   // a handle with a proposal: the guided kernels (the families smc_set_proposal accepts)
-        return by_guided_model(h->model, [&](auto M) { return launch_step_g<decltype(M)::value>(h->v, h->geo, h->cur, t, emit_prev, y, h->stream); });
-    return by_model(h->model, [&](auto M) { return launch_step<decltype(M)::value>(h->v, h->geo, h->cur, t, emit_prev, y, h->stream); });
+        return by_guided_model(h->model, [&](auto M) { return launch_step_g<decltype(M)::value>(h->v, h->geo, hot, h->stream); });
+    return by_model(h->model, [&](auto M) { return launch_step<decltype(M)::value>(h->v, h->geo, hot, h->stream); });
 }
 // Break points of the multinomial resampling steps (multi-segment filters; smc_spec.h): computed by k_breaks
 // for a window of steps ahead of time - they depend on (seed, stream, t) only.  Called before every step
@@ -315,6 +325,9 @@ extern "C" int smc_create(int model_id, int64_t n_theta, int64_t n_x, int seg, u
     TRY(hipMemcpyAsync(h->d_stream, st.data(), nt * 4, hipMemcpyHostToDevice, h->stream));
     TRY(hipStreamSynchronize(h->stream));
 #undef TRY
+    h->hot.stream0 = 0u;
+    h->hot.stream_ok = true;
+    if (const char* e = getenv("SMC_STEP_BY_VALUE")) h->hot.allow = atoi(e) != 0;   // 0: every step launch through the pointers
     v.params = h->d_params;
     v.stream = h->d_stream;
     *out = h;
@@ -390,6 +403,8 @@ extern "C" int smc_set_params(smc_handle h, const double* raw) {
         if (h->v.prop_kind) fill_proposal(h, m);
     }
     HIPCHK(hipMemcpyAsync(h->d_params, P, (size_t)h->v.ntheta * sizeof(Params), hipMemcpyHostToDevice, h->stream));
+    h->hot.prm0 = P[0];
+    h->hot.prm_ok = true;
     if (h->v.prop_kind)   // a guided handle: the proposal rows follow the parameter rows
         HIPCHK(hipMemcpyAsync(h->d_prop, h->h_prop, (size_t)h->v.ntheta * sizeof(PropRow), hipMemcpyHostToDevice, h->stream));
     h->have_params = true;
@@ -437,7 +452,15 @@ extern "C" int smc_set_streams(smc_handle h, const uint32_t* s) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(h->d_stream, s, (size_t)h->v.ntheta * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    h->hot.stream0 = s[0];
+    h->hot.stream_ok = true;
     h->brk_count = 0;    // cached break points belong to the old stream ids
+    return SMC_OK;
+}
+
+extern "C" int smc_step_by_value(smc_handle h, int* by_value) {
+    if (!h || !by_value) return fail(SMC_EINVAL, "smc_step_by_value: NULL argument");
+    *by_value = hot_legal(h) && !h->skip.on ? 1 : 0;
     return SMC_OK;
 }
 
@@ -758,6 +781,21 @@ static void abl_report(smc_filter_s* h) {
             if (st[w * 8] < t0) t0 = st[w * 8];
             if (st[w * 8 + 7] > t7) t7 = st[w * 8 + 7];
             for (int k = 1; k < 8; ++k) ph[k] += (double)(st[w * 8 + k] - st[w * 8 + k - 1]) * 0.01;
+        }
+        {   // start-up latency of the LAST k_step launch: entry of a workgroup's first wave -> its first pick numbers drawn
+            std::vector<unsigned long long> sd(nwg * 8);
+            (void)hipMemcpy(sd.data(), h->v.dbg + nwg * 8, nwg * 64, hipMemcpyDeviceToHost);
+            if (sd[7] != 0x5045525349535421ull && sd[0] != 0 && sd[1] != 0) {   // (systematic launches draw no pick numbers: no stamp)
+                double sum = 0, mn = 1e30, mx = 0;
+                std::vector<double> all(nwg);
+                for (size_t w = 0; w < nwg; ++w) {
+                    const double us = (double)(sd[w * 8] - sd[w * 8 + 1]) * 0.01;
+                    all[w] = us; sum += us; mn = std::min(mn, us); mx = std::max(mx, us);
+                }
+                std::sort(all.begin(), all.end());
+                fprintf(stderr, "[dbg] k_step start-up, entry -> first pick numbers drawn, over %zu workgroups (us, 10 ns clock): mean %.3f min %.3f "
+                                "median %.3f 90%% %.3f max %.3f\n", nwg, sum / nwg, mn, all[nwg / 2], all[(size_t)((nwg - 1) * 0.9)], mx);
+            }
         }
         double start_spread = 0, life = 0;
         for (size_t w = 0; w < nwg; ++w) { start_spread += (double)(st[w * 8] - t0) * 0.01; life += (double)(st[w * 8 + 7] - st[w * 8]) * 0.01; }

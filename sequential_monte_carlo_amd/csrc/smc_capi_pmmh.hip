@@ -107,6 +107,7 @@ extern "C" int smc_pmmh_rejuvenate(smc_handle h, smc_handle main, const double* 
                            sqrt(scales[c]), h->d_params);   // (derives the proposal rows of a guided handle too)
         HIPCHK(hipGetLastError());
         h->have_params = true;
+        hot_invalidate(h);                     // the rows were written on the device
         h->v.seed = filter_seeds[c];
         h->brk_count = 0;                      // cached break points belong to the previous seed
         h->v.skip = h->pm.dev.skip; h->v.order = h->pm.dev.order; h->v.n_active = h->pm.dev.counts;
@@ -116,7 +117,10 @@ extern "C" int smc_pmmh_rejuvenate(smc_handle h, smc_handle main, const double* 
         hipLaunchKernelGGL(k_pmmh_accept, grid, block, 0, h->stream, h->v, h->pm.dev, d, move_seed, (uint32_t)c, xi);
         HIPCHK(hipGetLastError());
         // smc.x[m], smc.w[m] <- x_prop, w_prop of the accepted particles (smc_samplers.jl:132-133)
-        if (main) HIPCHK(copy_slots(main->v, main->cur, h->v, h->cur, main->d, h->pm.dev.mask, h->stream));
+        if (main) {
+            HIPCHK(copy_slots(main->v, main->cur, h->v, h->cur, main->d, h->pm.dev.mask, h->stream));
+            hot_invalidate(main);
+        }
     }
     hipLaunchKernelGGL(k_pmmh_export, grid, block, 0, h->stream, nt, d, h->pm.dev, h->pm.h_out);
     HIPCHK(hipGetLastError());

@@ -43,7 +43,7 @@ static hipError_t do_resident(smc_filter_s* h, int T) {
 }
 // The launches of log_likelihood(N, y, model) (particles.jl:132-147) for every filter of the handle, enqueued on
 // its stream: nothing here waits for the device.  y must already be in h->d_y (ensure_y + copy by the caller).
-int enqueue_log_likelihood(smc_handle h, double y0, int64_t T, bool want_trace, bool summ) {
+int enqueue_log_likelihood(smc_handle h, double y0, int64_t T, bool want_trace, bool summ, const double* y_host) {
     // (systematic resampling with per-step summaries: the LDS-resident summary kernels exist for the default law only)
     const bool resident = h->resident_ok && resident_supported(h->model, h->v.seg) && !(summ && (h->v.systematic || !summaries_fit_lds(h)));
     SeriesScope scope(h->v);
@@ -64,7 +64,7 @@ int enqueue_log_likelihood(smc_handle h, double y0, int64_t T, bool want_trace, 
         if ((rc = enqueue_step_summaries(h, 0))) return rc;
         for (int64_t t = 1; t < T; ++t) {
             HIPCHK(ensure_breaks(h, (uint32_t)t, (uint32_t)T));
-            HIPCHK(do_step(h, (uint32_t)t, 0, 0.0));
+            HIPCHK(do_step(h, (uint32_t)t, 0, 0.0, y_host));
             h->cur ^= 1; h->t += 1; h->emitted = false;
             if ((rc = emit_if_needed(h))) return rc;
             if ((rc = enqueue_step_summaries(h, t))) return rc;
@@ -108,7 +108,7 @@ int enqueue_log_likelihood(smc_handle h, double y0, int64_t T, bool want_trace, 
             const int emit = h->v.want_s2 ? 1 : 2;   // 2: the records of step t-1 carry no sum of squares - (logmu, 0) from the totals alone
             if (t == T - 1) h->v.want_s2 = 1;
             HIPCHK(ensure_breaks(h, (uint32_t)t, (uint32_t)T));
-            HIPCHK(do_step(h, (uint32_t)t, emit, 0.0));
+            HIPCHK(do_step(h, (uint32_t)t, emit, 0.0, y_host));
             h->cur ^= 1; h->t += 1;
         }
         h->v.want_s2 = 1;
@@ -139,7 +139,7 @@ extern "C" int smc_log_likelihood(smc_handle h, const double* y, int64_t T, doub
     if (h->skip.on) { h->v.skip = h->skip.d_mask; h->v.order = h->skip.d_order; h->v.n_active = h->skip.d_order + h->v.ntheta; }
     const int cur0 = h->cur;   // where the state of the filters the call leaves out stays
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    rc = enqueue_log_likelihood(h, y[0], T, want_trace, summ);
+    rc = enqueue_log_likelihood(h, y[0], T, want_trace, summ, y);
     h->v.skip = nullptr; h->v.order = nullptr; h->v.n_active = nullptr;
     if (rc) return rc;
     // the call ends in the other buffer: the skipped filters' untouched state goes with it
@@ -203,7 +203,7 @@ extern "C" int smc_time_step_kernel(smc_handle h, const double* y, int64_t T, in
             HIPCHK(hipEventRecord(e0[k], h->stream));
             open_left = G;
         }
-        HIPCHK(do_step(h, (uint32_t)t, emit, 0.0));
+        HIPCHK(do_step(h, (uint32_t)t, emit, 0.0, y));
         if (open_left && --open_left == 0) { HIPCHK(hipEventRecord(e1[k], h->stream)); ++k; }
         h->cur ^= 1; h->t += 1;
     }

@@ -61,6 +61,7 @@ extern "C" int smc_permute(smc_handle h, const int32_t* a) {
     hipLaunchKernelGGL(k_permute, dim3((unsigned)((v.npad + 255) / 256), v.ntheta), dim3(256), 0, h->stream, v, h->cur, h->d,
                        h->d_perm, h->d_logZ_tmp);
     HIPCHK(hipGetLastError());
+    hot_invalidate(h);   // slots moved on the device
     h->cur ^= 1;
     // last_* (g, D, logmu, ess) describe slot-local weights: recompute them for the new layout
     HIPCHK(hipMemcpyAsync(h->d_logZ_tmp, v.logZ, (size_t)v.ntheta * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -86,6 +87,7 @@ extern "C" int smc_copy_from(smc_handle dst, smc_handle src, const uint8_t* mask
     unsigned char* d_mask = reinterpret_cast<unsigned char*>(dst->d_perm);   // n_theta bytes fit in n_theta int32
     HIPCHK(hipMemcpyAsync(d_mask, mask, (size_t)a.ntheta, hipMemcpyHostToDevice, dst->stream));
     HIPCHK(copy_slots(a, dst->cur, b, src->cur, dst->d, d_mask, dst->stream));
+    hot_invalidate(dst);
     HIPCHK(hipStreamSynchronize(dst->stream));
     dst->t = src->t;   // the accepted filters have seen the same observations
     return SMC_OK;
@@ -102,6 +104,7 @@ static int pack_unpack(smc_handle h, const int32_t* idx, int64_t k, void* buf, b
     if (!h->inited) return fail(SMC_ESTATE, "smc_pack/unpack_slots: filter not initialised");
     if (!pack) h->win.k = 0;
     if (k == 0) return SMC_OK;
+    if (!pack) hot_invalidate(h);   // slots written on the device (the exchange of smc_comm.hip ends here too)
     for (int64_t i = 0; i < k; ++i)
         if (idx[i] < 0 || idx[i] >= h->v.ntheta) return fail(SMC_EINVAL, "smc_pack/unpack_slots: index out of range");
     HIPCHK(hipSetDevice(h->device));

@@ -80,6 +80,12 @@ struct smc_filter_s {
     bool resident_ok = false;
     smc::Geo geo{0, 0};
     double last_ms = 0.0;
+    struct {   // single-filter step launches take filter 0's parameter row and stream id BY VALUE (StepHot, smc_kernels.h): the host's copies
+        smc::Params prm0{};
+        uint32_t stream0 = 0;
+        bool prm_ok = false, stream_ok = false;   // the copy equals the device row; hot_invalidate() after anything the device wrote
+        bool allow = true;                        // SMC_STEP_BY_VALUE=0 at smc_create: always through the pointers (tests, measurements)
+    } hot;
 
     struct {   // smc_set_skip: filters log_likelihood leaves out
         unsigned char* d_mask = nullptr;
@@ -128,7 +134,14 @@ inline bool affine_row_ok(const double* par) {
 // ---- helpers that cross files ----------------------------------------------------------------------
 // smc_capi.hip: the launches of one particle step on the handle's stream, and what they need
 hipError_t do_init(smc_filter_s* h, double y);
-hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y);
+// y: the observation of the step API (v.y == nullptr); y_host: the host's copy of the series v.y points at, or nullptr - with it a
+// single-filter launch passes y_host[t] by value as well
+hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y, const double* y_host = nullptr);
+// The host copies of row 0 (hot) no longer describe the device rows: whoever writes parameters, streams or filter slots on the
+// device calls this; the next smc_set_params / smc_set_streams makes its half valid again
+inline void hot_invalidate(smc_filter_s* h) { h->hot.prm_ok = h->hot.stream_ok = false; }
+// a step launch of this handle may take row 0 by value: one filter, both host copies valid (the launch also wants no skip mask)
+inline bool hot_legal(const smc_filter_s* h) { return h->hot.allow && h->hot.prm_ok && h->hot.stream_ok && h->v.ntheta == 1; }
 hipError_t do_finalize(smc_filter_s* h, int first_emit, uint32_t t_emit);
 hipError_t ensure_breaks(smc_filter_s* h, uint32_t t, uint32_t t_end);
 int ensure_y(smc_handle h, int64_t T);
@@ -138,7 +151,8 @@ int emit_if_needed(smc_handle h);
 // requested per-filter vectors over from the pinned mirror
 int finish_elapsed(smc_handle h, double* logZ = nullptr, double* logmu = nullptr, double* ess = nullptr);
 // smc_capi_series.hip
-int enqueue_log_likelihood(smc_handle h, double y0, int64_t T, bool want_trace, bool summ = false);
+// (y_host: the host copy of the series in h->d_y, alive until the launches are enqueued, or nullptr)
+int enqueue_log_likelihood(smc_handle h, double y0, int64_t T, bool want_trace, bool summ = false, const double* y_host = nullptr);
 // smc_capi_summ.hip: the per-step summaries of the multi-step calls
 inline bool summaries_on(const smc_filter_s* h) { return h->summ.np > 0 || h->summ.mom != 0; }
 bool summaries_fit_lds(const smc_filter_s* h);

@@ -22,6 +22,7 @@
 // All searches of a thread advance level by level together (2*NP independent loads in flight).
 #pragma once
 #include "smc_spec.h"
+#include <type_traits>
 
 namespace smc {
 
@@ -134,9 +135,24 @@ struct FilterView {
         if ((v).dbg && threadIdx.x == 0)                                                                  \
             (v).dbg[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
+// start-up latency of a step launch: SMC_CLOCK reads the clock where it stands (no pointer needed: the entry clock is taken before
+// the kernel-argument block has arrived), SMC_STAMP_START stores (first pick numbers drawn, entry) in words 0 and 1 of the
+// workgroup's row in the SECOND half of the stamp buffer (k_persist's accumulators otherwise)
+#define SMC_CLOCK() __builtin_amdgcn_s_memrealtime()
+#define SMC_STAMP_START(v, t_draw, t_entry)                                                               \
+    do {                                                                                                  \
+        if ((v).dbg && threadIdx.x == 0) {                                                                \
+            unsigned long long* d_ = (v).dbg + ((size_t)gridDim.y * gridDim.x + (size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8; \
+            d_[0] = (t_draw); d_[1] = (t_entry);                                                          \
+        }                                                                                                 \
+    } while (0)
+#define SMC_ORDER_AFTER(x) asm volatile("" : : "v"(x))   // what follows is issued after the instruction that produced x
 #else
+#define SMC_ORDER_AFTER(x) do { } while (0)
 #define SMC_ABL(v, bit) 0
 #define SMC_STAMP(v, k) do { } while (0)
+#define SMC_CLOCK() 0ull
+#define SMC_STAMP_START(v, t_draw, t_entry) do { (void)(t_draw); (void)(t_entry); } while (0)
 #endif
 // ---- weighted quantiles: helpers shared by the stand-alone kernels (smc_aux_kernels.h) and the per-step summaries --------
 // (logZ, logmu, ess) of filter th into the pinned host mirror; with a ticket (step API) the values are released to the host
@@ -891,8 +907,20 @@ __host__ __device__ inline size_t step_lds_bytes(int nseg_p2, int threads, int n
 // (no k_table launch yet; the rare full table in LDS as ever).
 // GUIDED: the state comes from the filter's proposal and the weight carries the correction (smc_spec.h "proposals"; the parameter
 // row's prop entries): the guided handles' instantiations - bootstrap handles run the GUIDED = false ones, which never read them.
-template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS, bool PERSIST, class VIEW, bool GTAB = false, int RPT = 1, bool GUIDED = false>
-__device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, int emit_prev, double yval, char* smem) {
+// What a step launch needs FIRST, handed over by value at the head of the kernel-argument block (the host's side of it: StepHot,
+// below): the leading scalars are preloaded into scalar registers at wave launch (csrc/Makefile, kernel-argument preload).  BYV
+// (single-filter launches, gridDim.y == 1, whose stream id, parameter row and observation the host holds): stream0, *prm0 and yval
+// ARE the filter's - v.stream, v.params, v.y and v.skip are never touched, so the first Philox call waits for ONE trip to memory
+// (the rest of the kernel-argument block: the pointers behind the loads issued ahead of it), not for a second, dependent one.
+// Otherwise they are read through the view's pointers as ever (batched launches, skip masks, rows written on the device).
+// A template parameter, not a workgroup-uniform branch: with both routes in one kernel the wait for the pointer route's loads
+// lands in front of the first draw of either, and the parameter row moves to vector registers (129 of them: three waves per
+// SIMD).  seed, t and nseg (= v.nseg: the block -> segment map) are taken from here on both routes.
+template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS, bool PERSIST, class VIEW, bool GTAB = false, int RPT = 1, bool GUIDED = false, bool BYV = false>
+__device__ __forceinline__ void step_body(const VIEW& v, uint64_t seed, uint32_t t, uint32_t stream0, int nseg, int cur, int emit_prev,
+                                          double yval, const Params* prm0, char* smem) {
+    static_assert(!(BYV && PERSIST), "by value: one launch per step");
+    const unsigned long long t_entry = SMC_CLOCK();
     static_assert(!GTAB || (MULTI && !PERSIST), "global table: multi-segment launches");
     static_assert(RPT == 1 || (RPT == 2 && MULTI && !GTAB && !PERSIST), "two records per thread: multi-segment launches");
     constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
@@ -901,20 +929,27 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
     constexpr int NQ = 2 * NP;   // particles per thread
     constexpr int NSTAGE = nstage_for(SEG);
     constexpr int SEGP = lds_padded_len(SEG);   // padded length of a staged segment in LDS
-    int sb_ = logical_segment(blockIdx.x, v.nseg), th_ = blockIdx.y, tid_ = smc_tid();
+    int sb_ = logical_segment(blockIdx.x, nseg), th_ = blockIdx.y, tid_ = smc_tid();
     if (PERSIST) {   // opaque per iteration: the loop around this body must not hoist everything derived from them into registers
         asm volatile("" : "+v"(tid_));
     }
     const int sb = sb_, th = th_, tid = tid_;
-    if (!PERSIST && v.skip && v.skip[th]) return;   // workgroup-uniform
+    if (!PERSIST && !BYV && v.skip && v.skip[th]) return;   // workgroup-uniform
     const int nxt = cur ^ 1;
-    const Params prm = v.params[th];
+    uint32_t stream;
+    if constexpr (BYV) stream = stream0;
+    else stream = v.stream[th];
+    // particle indices fit 32 bits (smc_create: n_x <= 2^31): index arithmetic in 32 bits, 64 bits only in the addresses
+    const uint32_t seg0 = (uint32_t)sb * (uint32_t)SEG;
+    uint64_t rr[NQ];
+    u32x4 rw[NP] = {};
+    Params prm;
+    double y;
+    if constexpr (BYV) { prm = *prm0; y = yval; }
+    else { prm = v.params[th]; y = v.y ? v.y[t] : yval; }
     PropRow prw;
     if constexpr (GUIDED) prw = v.prop[th];
-    const uint32_t stream = v.stream[th];
-    const double y = v.y ? v.y[t] : yval;
-    // particle indices fit 32 bits (smc_create: n_x <= 2^31): index arithmetic in 32 bits, 64 bits only in the addresses
-    const uint32_t seg0 = (uint32_t)sb * (uint32_t)SEG, n32 = (uint32_t)v.n;
+    const uint32_t n32 = (uint32_t)v.n;
     const uint64_t* Cprev = v.C[cur] + (size_t)th * v.npad;
     const double* xprev = v.x[cur];
     uint64_t* scr;
@@ -938,14 +973,19 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
     }
     const TablePre tpre = (MULTI && !GTAB) ? table_preload<THREADS, VIEW, RPT>(v, cur, th, emit_prev && sb == 0) : TablePre{-inf(), 0, 0, 0, -inf(), 0};
     // (2) the 64-bit pick numbers of this thread's children
-    uint64_t rr[NQ];
+    unsigned long long t_draw = 0;
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
         if (SYS) { rr[2 * k] = rr[2 * k + 1] = 0; continue; }
         const uint32_t pg = (uint32_t)((seg0 >> 1) + tid + k * THREADS);
-        const u32x4 rw = SMC_ABL(v, 3) ? u32x4{{pg * 2654435761u, pg ^ t, pg * 40503u, ~pg}} : draw(v.seed, pg, stream, t, SLOT_RESAMPLE);
-        rr[2 * k] = ((uint64_t)rw.v[1] << 32) | rw.v[0];
-        rr[2 * k + 1] = ((uint64_t)rw.v[3] << 32) | rw.v[2];
+        rw[k] = draw(seed, pg, stream, t, SLOT_RESAMPLE);
+        if (k == 0) {   // (profiling builds: the clock once the first pick numbers exist)
+            SMC_ORDER_AFTER(rw[0].v[3]);
+            t_draw = SMC_CLOCK();
+        }
+        if (SMC_ABL(v, 3)) rw[k] = u32x4{{pg * 2654435761u, pg ^ t, pg * 40503u, ~pg}};
+        rr[2 * k] = ((uint64_t)rw[k].v[1] << 32) | rw[k].v[0];
+        rr[2 * k + 1] = ((uint64_t)rw[k].v[3] << 32) | rw[k].v[2];
     }
     // this thread's child indices relative to the workgroup's first child (masked children j >= n take
     // the last real child's target: they are never stored as real particles)
@@ -1001,8 +1041,8 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
 #pragma unroll
         for (int c = 0; c < NZ; ++c) {
             if (SMC_ABL(v, 2)) { z[k][c][0] = 1e-3 * (double)(pg & 1023); z[k][c][1] = -z[k][c][0]; }
-            else if (SMC_ABL(v, 6)) { const u32x4 w4 = draw(v.seed, pg, stream, t, SLOT_NORMAL0 + c); z[k][c][0] = 1e-9 * (double)w4.v[0]; z[k][c][1] = 1e-9 * (double)w4.v[2]; }
-            else box_muller(draw(v.seed, pg, stream, t, SLOT_NORMAL0 + c), z[k][c][0], z[k][c][1]);
+            else if (SMC_ABL(v, 6)) { const u32x4 w4 = draw(seed, pg, stream, t, SLOT_NORMAL0 + c); z[k][c][0] = 1e-9 * (double)w4.v[0]; z[k][c][1] = 1e-9 * (double)w4.v[2]; }
+            else box_muller(draw(seed, pg, stream, t, SLOT_NORMAL0 + c), z[k][c][0], z[k][c][1]);
             // systematic: keep the normals HERE, under the load latencies.  multinomial: measured faster when the
             // compiler sinks them next to their use, where they fill the waits of the LDS search
             if (SYS || SMC_NORMALS_EARLY) asm volatile("" : "+v"(z[k][c][0]), "+v"(z[k][c][1]));
@@ -1028,7 +1068,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
         // not spend) and published through LDS across the barriers of the table prologue
         uint64_t* sysw = L.scr + scr_words(THREADS, NP) - 8;   // tail words nobody else uses
         if (SYS && tid == 0) {
-            const u32x4 uw = draw(v.seed, 0u, stream, t, SLOT_SYS);
+            const u32x4 uw = draw(seed, 0u, stream, t, SLOT_SYS);
             sysw[0] = ((uint64_t)uw.v[1] << 32) | uw.v[0];
         }
         // What this workgroup needs of the segment table of the weights being resampled.  Usual case: only its speculative
@@ -1175,7 +1215,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
         if (SYS) {   // one segment: K = kb, shift = SH, table = (S >> SH)
             const int sh = seg_shift(0.0, 0.0, v.SH);
             const uint64_t Dtot = seg_Q(alive, sh);
-            const u32x4 uw = draw(v.seed, 0u, stream, t, SLOT_SYS);
+            const u32x4 uw = draw(seed, 0u, stream, t, SLOT_SYS);
             const SysBase sbase = sys_base(Dtot, n32, v.inv_n, ((uint64_t)uw.v[1] << 32) | uw.v[0], 0u);
 #pragma unroll
             for (int i = 0; i < NQ; ++i) Tg[i] = sys_threshold(sys_target(sbase, kk[i]), sh);
@@ -1184,6 +1224,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
     }
 
     SMC_STAMP(v, 2);
+    SMC_STAMP_START(v, t_draw, t_entry);
     SMC_STAMP(v, 3);
     // ---- a = resample(weights), level 2: iid pick inside the child's segment -------------------
     uint64_t T2[NQ];
@@ -1294,7 +1335,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
         if (LATE_Z) {
             const uint32_t pg = (uint32_t)((seg0 >> 1) + tid + k * THREADS);
 #pragma unroll
-            for (int c = 0; c < NZ; ++c) box_muller(draw(v.seed, pg, stream, t, SLOT_NORMAL0 + c), z[k][c][0], z[k][c][1]);
+            for (int c = 0; c < NZ; ++c) box_muller(draw(seed, pg, stream, t, SLOT_NORMAL0 + c), z[k][c][0], z[k][c][1]);
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -1348,10 +1389,26 @@ __device__ __forceinline__ void step_body(const VIEW& v, int cur, uint32_t t, in
     SMC_STAMP(v, 7);
 }
 
-template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS = false, bool GTAB = false, int RPT = 1, bool GUIDED = false>
-__global__ __launch_bounds__(THREADS) void k_step(FilterView v, int cur, uint32_t t, int emit_prev, double yval) {
+// The host's side of a step launch's by-value arguments (smc_model.hip spreads them over the head of the parameter list: only
+// scalar parameters are preloaded into registers, so the struct does not travel as one)
+struct StepHot {
+    uint64_t seed;
+    uint32_t t;
+    uint32_t stream0;    // by_value: the filter's stream id
+    int nseg;            // = FilterView::nseg
+    int cur, emit_prev;
+    int by_value;        // 1: stream0, prm0 and yval are filter 0's (single-filter launch, no skip mask, host copies valid): the BYV kernels
+    double yval;         // by_value: y[t]; else the step API's observation (v.y == nullptr)
+    Params prm0;         // by_value: the filter's parameter row
+};
+static_assert(std::is_trivially_copyable<StepHot>::value, "passed by value");
+
+// (seed .. yval: 10 dwords at the head of the kernel-argument block, preloaded; then the parameter row, then the view)
+template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS = false, bool GTAB = false, int RPT = 1, bool GUIDED = false, bool BYV = false>
+__global__ __launch_bounds__(THREADS) void k_step(uint64_t seed, uint32_t t, uint32_t stream0, int nseg, int cur, int emit_prev, double yval,
+                                                  Params prm0, FilterView v) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    step_body<MODEL, THREADS, NP, MULTI, SYS, false, FilterView, GTAB, RPT, GUIDED>(v, cur, t, emit_prev, yval, smem);
+    step_body<MODEL, THREADS, NP, MULTI, SYS, false, FilterView, GTAB, RPT, GUIDED, BYV>(v, seed, t, stream0, nseg, cur, emit_prev, yval, &prm0, smem);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1408,7 +1465,7 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 512 ? 4 : (THREADS >= 256 ? 4 
             }
         }
         if (v.dbg && tid == 0) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); acc[0] += now - acc[3]; acc[3] = now; }
-        step_body<MODEL, THREADS, NP, true, false, true>(v, cur, t, 2, 0.0, smem);
+        step_body<MODEL, THREADS, NP, true, false, true>(v, v.seed, t, 0u, v.nseg, cur, 2, 0.0, (const Params*)nullptr, smem);
         if (v.dbg && tid == 0) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); acc[1] += now - acc[3]; acc[3] = now; }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains its write-through stores
         __syncthreads();

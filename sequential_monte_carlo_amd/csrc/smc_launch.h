@@ -53,7 +53,8 @@ bool geo_default(int seg, Geo& g);
 bool geo_valid(int seg, int np, Geo& g);
 
 template <int MODEL> hipError_t launch_init(const FilterView& v, Geo g, int nxt, double y, hipStream_t s);
-template <int MODEL> hipError_t launch_step(const FilterView& v, Geo g, int cur, uint32_t t, int emit_prev, double y, hipStream_t s);
+// hot: the launch's by-value arguments (StepHot, smc_kernels.h); hot.seed and hot.nseg repeat the view's
+template <int MODEL> hipError_t launch_step(const FilterView& v, Geo g, const StepHot& hot, hipStream_t s);
 template <int MODEL> hipError_t launch_resident(const FilterView& v, int T, StepRec* recs, hipStream_t s);
 // opt-in persistent step kernel: the steps [t0, t1) of a multi-segment filter in one launch; hipErrorCooperativeLaunchTooLarge when
 // the grid cannot be resident all at once (or the geometry has no instantiation): the caller then launches step by step
@@ -65,7 +66,7 @@ template <int MODEL> hipError_t launch_summ_once(const FilterView& v, int cur, h
 template <int MODEL> hipError_t launch_window(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
 // the same three for a handle with a proposal (smc_set_proposal): the GUIDED kernels, instantiated for the families that have
 // proposals (LG1D, UCSV3D) in translation units of their own (smc_model.hip with -DSMC_GUIDED=1)
-template <int MODEL> hipError_t launch_step_g(const FilterView& v, Geo g, int cur, uint32_t t, int emit_prev, double y, hipStream_t s);
+template <int MODEL> hipError_t launch_step_g(const FilterView& v, Geo g, const StepHot& hot, hipStream_t s);
 template <int MODEL> hipError_t launch_resident_g(const FilterView& v, int T, StepRec* recs, hipStream_t s);
 template <int MODEL> hipError_t launch_window_g(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
 

@@ -23,42 +23,31 @@ static hipError_t init_t(const FilterView& v, int nxt, double y, hipStream_t s) 
     return hipGetLastError();
 }
 #endif
-template <int THREADS, int NP, bool SYS>
-static hipError_t step_sys_t(const FilterView& v, int cur, uint32_t t, int emit_prev, double y, hipStream_t s) {
-    if (v.tabD) {   // the table comes from k_table (launched by the caller before this step): no table in LDS, nothing to emit
-        const size_t lds = step_lds_bytes(0, THREADS, NP, true);
-        static bool raised[16] = {};
-        hipError_t e = raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, true, SYS, true, 1, SMC_G>, lds, raised);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, true, SYS, true, 1, SMC_G>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, cur, t, 0, y);
-        return hipGetLastError();
-    }
-    const size_t lds = step_lds_bytes(v.nseg_p2, THREADS, NP, v.nseg > 1);
-    if (v.nseg_p2 > THREADS) {   // up to twice as many segments as threads: the window prologue with two records per thread
-        static bool raised[16] = {};
-        hipError_t e = raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, true, SYS, false, 2, SMC_G>, lds, raised);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, true, SYS, false, 2, SMC_G>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, cur, t, emit_prev, y);
-        return hipGetLastError();
-    }
-    {
-        static bool raised[2][16] = {};   // per instantiation, variant and device
-        hipError_t e = v.nseg > 1 ? raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, true, SYS, false, 1, SMC_G>, lds, raised[1])
-                                  : raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, false, SYS, false, 1, SMC_G>, lds, raised[0]);
-        if (e != hipSuccess) return e;
-    }
-    if (v.nseg > 1)
-        hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, true, SYS, false, 1, SMC_G>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, cur, t,
-                           emit_prev, y);
-    else
-        hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, false, SYS, false, 1, SMC_G>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, cur, t,
-                           emit_prev, y);
+// one launch of k_step<..., BYV>: the kernel's parameter list is the hot scalars one by one at the head (what the wave finds
+// preloaded), the parameter row, the view
+template <int THREADS, int NP, bool MULTI, bool SYS, bool GTAB, int RPT, bool BYV>
+static hipError_t step_launch(const FilterView& v, const StepHot& hot, int emit_prev, size_t lds, hipStream_t s) {
+    static bool raised[16] = {};   // per instantiation and device
+    hipError_t e = raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, SMC_G, BYV>, lds, raised);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, SMC_G, BYV>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, hot.seed, hot.t,
+                       hot.stream0, hot.nseg, hot.cur, emit_prev, hot.yval, hot.prm0, v);
     return hipGetLastError();
 }
+template <int THREADS, int NP, bool SYS, bool BYV>
+static hipError_t step_sys_t(const FilterView& v, const StepHot& hot, hipStream_t s) {
+    if (v.tabD)   // the table comes from k_table (launched by the caller before this step): no table in LDS, nothing to emit
+        return step_launch<THREADS, NP, true, SYS, true, 1, BYV>(v, hot, 0, step_lds_bytes(0, THREADS, NP, true), s);
+    const size_t lds = step_lds_bytes(v.nseg_p2, THREADS, NP, v.nseg > 1);
+    if (v.nseg_p2 > THREADS)   // up to twice as many segments as threads: the window prologue with two records per thread
+        return step_launch<THREADS, NP, true, SYS, false, 2, BYV>(v, hot, hot.emit_prev, lds, s);
+    return v.nseg > 1 ? step_launch<THREADS, NP, true, SYS, false, 1, BYV>(v, hot, hot.emit_prev, lds, s)
+                      : step_launch<THREADS, NP, false, SYS, false, 1, BYV>(v, hot, hot.emit_prev, lds, s);
+}
 template <int THREADS, int NP>
-static hipError_t step_t(const FilterView& v, int cur, uint32_t t, int emit_prev, double y, hipStream_t s) {
-    return v.systematic ? step_sys_t<THREADS, NP, true>(v, cur, t, emit_prev, y, s)
-                        : step_sys_t<THREADS, NP, false>(v, cur, t, emit_prev, y, s);
+static hipError_t step_t(const FilterView& v, const StepHot& hot, hipStream_t s) {
+    if (hot.by_value) return v.systematic ? step_sys_t<THREADS, NP, true, true>(v, hot, s) : step_sys_t<THREADS, NP, false, true>(v, hot, s);
+    return v.systematic ? step_sys_t<THREADS, NP, true, false>(v, hot, s) : step_sys_t<THREADS, NP, false, false>(v, hot, s);
 }
 
 #define SMC_GEO_SWITCH(FN, ...)                                                   \
@@ -93,8 +82,9 @@ hipError_t launch_init<SMC_MODEL>(const FilterView& v, Geo g, int nxt, double y,
 #define SMC_LAUNCH_WINDOW launch_window_g
 #endif
 template <>
-hipError_t SMC_LAUNCH_STEP<SMC_MODEL>(const FilterView& v, Geo g, int cur, uint32_t t, int emit_prev, double y, hipStream_t s) {
-    SMC_GEO_SWITCH(step_t, v, cur, t, emit_prev, y, s)
+hipError_t SMC_LAUNCH_STEP<SMC_MODEL>(const FilterView& v, Geo g, const StepHot& hot, hipStream_t s) {
+    if (hot.by_value && v.ntheta != 1) return hipErrorInvalidValue;   // by value: ONE filter per launch
+    SMC_GEO_SWITCH(step_t, v, hot, s)
 }
 
 template <int THREADS, int NP, bool SYS, bool WIN, bool SUMM = false, bool UNW = false>
