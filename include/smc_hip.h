@@ -105,6 +105,9 @@ int smc_host_optimal_proposal(int model_id, const double* raw, double* par /*[SM
 /* one particle, one step, on the host: the specification's guided draw and log-weight (tests, Julia-side checks) */
 int smc_host_guided_step(int model_id, const double* raw, int kind, const double* par, const double* xp /*[d]*/,
                          const double* z /*[d]*/, double y, double* x /*[d]*/, double* logw);
+/* the same for n particles, xp z x [d][n], in a loop on the host: one call per step of a filter instead of one per particle */
+int smc_host_guided_steps(int model_id, const double* raw, int kind, const double* par, const double* xp,
+                          const double* z, double y, int64_t n, double* x, double* logw);
 /* the same for n particles on the device, xp z x [d][n] (parity tests; the twin of smc_device_math) */
 int smc_device_guided_step(int model_id, const double* raw, int kind, const double* par, const double* xp,
                            const double* z, double y, int64_t n, double* x, double* logw, int device);
@@ -127,6 +130,9 @@ int smc_device_guided_step(int model_id, const double* raw, int kind, const doub
 /* one particle, one step, on the host: sp (m, lse, lsn, P) of the ancestor (not read when first != 0), z the two normals */
 int smc_host_rb_step(const double* raw /*[5]*/, const double* sp /*[4]*/, const double* z /*[2]*/, double y, int first,
                      double* s /*[4]*/, double* logw);
+/* the same for n particles, sp s [4][n], z [2][n], in a loop on the host */
+int smc_host_rb_steps(const double* raw, const double* sp, const double* z, double y, int first, int64_t n, double* s,
+                      double* logw);
 /* the same for n particles on the device, sp s [4][n], z [2][n] (parity tests) */
 int smc_device_rb_step(const double* raw, const double* sp, const double* z, double y, int first, int64_t n, double* s,
                        double* logw, int device);

@@ -47,6 +47,14 @@ def lib():
         L.orc_normalize.argtypes = [_dp, C.c_int64, _dp, _dp, _dp]
         L.orc_resample.argtypes = [_dp, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint32, _i64p]
         L.orc_auto_seg.argtypes = [C.c_int, C.c_int64]
+        L.orc_auto_seg_rows.argtypes = [C.c_int, C.c_int64]
+        L.orc_filter_create_external.restype = C.c_void_p
+        L.orc_filter_create_external.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_uint64, C.c_uint32]
+        L.orc_filter_draw_ancestors.argtypes = [C.c_void_p, _i64p]
+        L.orc_filter_put_step.restype = C.c_double
+        L.orc_filter_put_step.argtypes = [C.c_void_p, _dp, _dp, _dp]
+        L.orc_state_normals.restype = None
+        L.orc_state_normals.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64, _dp]
         L.orc_filter_create.restype = C.c_void_p
         L.orc_filter_create.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_uint64, C.c_uint32]
         L.orc_filter_destroy.argtypes = [C.c_void_p]
@@ -261,6 +269,52 @@ class Filter:
         lib().orc_filter_get_weights_raw(self._h, Cc.ctypes.data_as(_u64p), _d(m), S.ctypes.data_as(_u64p),
                                          hi.ctypes.data_as(_u64p), lo.ctypes.data_as(_u64p))
         return Cc, m, S, hi, lo
+
+
+SLOT_NORMAL0 = 1
+
+
+def state_normals(seed, stream, t, slot, n):
+    """the state normals of Philox slot `slot` at step t of the particles 0..n-1 of a filter (element i & 1 of pair i >> 1)"""
+    z = np.zeros(int(n))
+    lib().orc_state_normals(int(seed), int(stream), int(t), int(slot), int(n), _d(z))
+    return z
+
+
+class ExternalFilter(Filter):
+    """The model-free weight track of the oracle: d state rows, the filter's resampler, normalisation and time index, and a step
+    whose states and log-weights the caller computes (orc_filter_draw_ancestors / orc_filter_put_step).  The getters, set_rng and
+    export / import are Filter's; it has no model, so Filter's own steps are refused."""
+
+    def __init__(self, d, n, seg=0, seed=1, stream=0, systematic=False):
+        self.model, self.n, self.d = None, int(n), int(d)
+        self._h = lib().orc_filter_create_external(self.d, self.n, seg, seed, stream)
+        if not self._h:
+            raise ValueError("orc_filter_create_external failed")
+        self.seg = lib().orc_filter_seg(self._h)
+        self.nseg = (self.n + self.seg - 1) // self.seg
+        if systematic:
+            lib().orc_filter_set_systematic(self._h, 1)
+
+    def draw_ancestors(self):
+        a = np.zeros(self.n, dtype=np.int64)
+        if lib().orc_filter_draw_ancestors(self._h, a.ctypes.data_as(_i64p)) != 0:
+            raise ValueError("no weights yet: put_step first")
+        return a
+
+    def put_step(self, x, logw):
+        """-> (logmu, ess)"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        logw = np.ascontiguousarray(logw, dtype=np.float64)
+        assert x.shape == (self.d, self.n) and logw.shape == (self.n,)
+        ess = C.c_double()
+        lm = lib().orc_filter_put_step(self._h, _d(x), _d(logw), C.byref(ess))
+        return lm, ess.value
+
+    def _no_model(self, *a, **k):
+        raise TypeError("an external filter has no model")
+
+    set_params = bootstrap_filter = step = log_likelihood = reseed = _no_model
 
 
 def log_likelihood_batch(model, raw, n, y, seg=0, seed=1, stream0=0):

@@ -661,19 +661,22 @@ typedef struct {
 
 void orc_filter_set_systematic(orc_filter* f, int on) { f->systematic = on ? 1 : 0; }
 
-int orc_auto_seg(int model, int64_t n) {   /* the same rule as smc_auto_seg (the segment length is part of the spec) */
-    const int d3 = model == ORC_UCSV3D;
+/* the same rule as smc_auto_seg (the segment length is part of the spec), by the number of state rows d: one segment up to
+ * 8192 particles of one row, 4096 of three, 2048 of four (the marginal family, which otherwise follows the three-row rule) */
+int orc_auto_seg_rows(int d, int64_t n) {
+    const int d3 = d >= 3;
     if (n > (int64_t)16384 * 4096) return 8192;   /* at most 16384 segments */
     if (n > (int64_t)16384 * 2048) return 4096;
     if (n > (int64_t)16384 * 1024) return 2048;
     if (n > ((int64_t)1 << 19)) return d3 ? 1024 : 2048;
     if (n > ((int64_t)1 << 17)) return 1024;
     if (n > ((int64_t)1 << 15)) return 512;
-    if (n > (d3 ? 4096 : MAX_SEG)) return 256;
+    if (n > (d > 3 ? 2048 : d3 ? 4096 : MAX_SEG)) return 256;
     int s = 256;
     while (s < n) s <<= 1;
     return s;
 }
+int orc_auto_seg(int model, int64_t n) { return orc_auto_seg_rows(orc_model_dim(model), n); }
 
 orc_filter* orc_filter_create(int model, const double* raw, int64_t n, int seg, uint64_t seed, uint32_t stream) {
     if (n <= 0) return NULL;
@@ -691,6 +694,65 @@ orc_filter* orc_filter_create(int model, const double* raw, int64_t n, int seg, 
     return f;
 }
 
+/* ------------------------------------------------------------------------------------ */
+/* the model-free weight track: a filter whose step arithmetic lives OUTSIDE this file     */
+/* (families the oracle does not restate: the tests compose resample / normals / normalize */
+/* from here with the library's host twins of the step, tests/composed_reference.py).      */
+/* model.id = 0; d state rows; seg = 0 follows the library's rule for d rows.              */
+/* ------------------------------------------------------------------------------------ */
+void orc_filter_destroy(orc_filter* f);
+orc_filter* orc_filter_create_external(int d, int64_t n, int seg, uint64_t seed, uint32_t stream) {
+    if (n <= 0 || d < 1 || d > 8) return NULL;
+    if (seg == 0) seg = orc_auto_seg_rows(d, n);
+    if (seg < 256 || seg > MAX_SEG || (seg & (seg - 1))) return NULL;   /* the library's range: a power of two in [256, 8192] */
+    orc_filter* f = (orc_filter*)calloc(1, sizeof *f);
+    if (!f) return NULL;
+    f->model.id = 0; f->model.d = d;
+    f->n = n; f->seed = seed; f->stream = stream; f->t = 0;
+    f->x = (double*)calloc((size_t)d * (size_t)n, 8);
+    f->xp = (double*)calloc((size_t)d * (size_t)n, 8);
+    f->logw = (double*)calloc((size_t)n, 8);
+    f->a = (int64_t*)calloc((size_t)n, 8);
+    weights_alloc(&f->W, n, seg);
+    if (!f->x || !f->xp || !f->logw || !f->a || !f->W.C || !f->W.kb || !f->W.S || !f->W.S2hi || !f->W.S2lo || !f->W.Dcum || !f->W.cnt) {
+        orc_filter_destroy(f);
+        return NULL;
+    }
+    return f;
+}
+
+/* a = resample(weights) at the filter's current t (the ancestors of the step that orc_filter_put_step completes): multinomial,
+ * or systematic after orc_filter_set_systematic.  Stored, and copied to a when it is not NULL.  -1 before the first step. */
+int orc_filter_draw_ancestors(orc_filter* f, int64_t* a) {
+    if (f->t == 0) return -1;
+    if (f->systematic) weights_resample_systematic(&f->W, f->seed, f->stream, f->t, f->a);
+    else weights_resample(&f->W, f->seed, f->stream, f->t, f->a);
+    if (a) memcpy(a, f->a, sizeof(int64_t) * (size_t)f->n);
+    return 0;
+}
+
+/* the rest of a step whose states x [d][n] and log-weights logw [n] were computed elsewhere: store them, normalize, advance t.
+ * The first call is the step at t = 0 (identity ancestors).  -> logmu */
+double orc_filter_put_step(orc_filter* f, const double* x, const double* logw, double* ess) {
+    const int64_t n = f->n;
+    memcpy(f->x, x, sizeof(double) * (size_t)f->model.d * (size_t)n);
+    memcpy(f->logw, logw, sizeof(double) * (size_t)n);
+    if (f->t == 0) for (int64_t i = 0; i < n; ++i) f->a[i] = i;
+    weights_normalize(&f->W, f->logw);
+    f->t += 1;
+    if (ess) *ess = f->W.ess;
+    return f->W.logmu;
+}
+
+/* the state normals of slot `slot` at step t of the particles 0..n-1 of a filter: particle i takes element i & 1 of its pair's */
+void orc_state_normals(uint64_t seed, uint32_t stream, uint32_t t, uint32_t slot, int64_t n, double* z) {
+    double zp[2];
+    for (int64_t i = 0; i < n; ++i) {
+        if (!(i & 1)) normal_pair(seed, i >> 1, stream, t, slot, zp);
+        z[i] = zp[i & 1];
+    }
+}
+
 void orc_filter_destroy(orc_filter* f) {
     if (!f) return;
     free(f->x); free(f->xp); free(f->logw); free(f->a);
@@ -699,7 +761,7 @@ void orc_filter_destroy(orc_filter* f) {
 }
 
 /* smc.model(theta[m]) changed (PMMH accept / per-step parameter refresh): same particles, new parameters */
-int orc_filter_set_params(orc_filter* f, const double* raw) { return model_init(&f->model, f->model.id, raw); }
+int orc_filter_set_params(orc_filter* f, const double* raw) { return f->model.id ? model_init(&f->model, f->model.id, raw) : -1; }
 
 /* value copy of the filter STATE (x cloud, weights, t) from src into dst; dst keeps its own seed,
  * stream and parameters (resample!(smc) smc_samplers.jl:74-84 and the PMMH accept :130-133) */
@@ -754,6 +816,7 @@ void orc_filter_set_rng(orc_filter* f, uint64_t seed, uint32_t stream) { f->seed
 
 /* bootstrap_filter(N, y, model)  particles.jl:87-105  -> logmu */
 double orc_bootstrap_filter(orc_filter* f, double y) {
+    if (!f->model.id) return NAN;                               /* a model-free track has no step of its own */
     const int d = f->model.d;
     const int64_t n = f->n;
     double z[3], xi[3], zp[3][2];
@@ -772,6 +835,7 @@ double orc_bootstrap_filter(orc_filter* f, double y) {
 
 /* bootstrap_filter!(x, w, y, model)  particles.jl:107-129  -> (logmu, ess) */
 double orc_bootstrap_filter_step(orc_filter* f, double y, double* ess) {
+    if (!f->model.id) return NAN;
     const int d = f->model.d;
     const int64_t n = f->n;
     double z[3], xpi[3], xi[3], zp[3][2];

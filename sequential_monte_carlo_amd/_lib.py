@@ -29,7 +29,7 @@ EXPORTS = [
     "smc_host_outer_advance", "smc_host_outer_temper", "smc_host_outer_resample", "smc_host_rw_factor",
     "smc_set_summaries", "smc_get_summaries", "smc_set_summary_mode", "smc_host_quantile7", "smc_host_sample_moments",
     "smc_set_proposal", "smc_host_optimal_proposal", "smc_host_guided_step", "smc_device_guided_step",
-    "smc_host_rb_step", "smc_device_rb_step",
+    "smc_host_rb_step", "smc_device_rb_step", "smc_host_guided_steps", "smc_host_rb_steps",
     "smc_ibis_create", "smc_ibis_destroy", "smc_ibis_configure", "smc_ibis_set_theta", "smc_ibis_window", "smc_ibis_commit",
     "smc_ibis_filter", "smc_ibis_permute", "smc_ibis_set_logw", "smc_ibis_rejuvenate", "smc_ibis_get",
     "smc_ibis_summary", "smc_ibis_set_summaries", "smc_ibis_get_summaries", "smc_host_ibis_summary",
@@ -124,6 +124,8 @@ def lib():
     L.smc_device_guided_step.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int64, _dp, _dp, C.c_int]
     L.smc_host_rb_step.argtypes = [_dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp]
     L.smc_device_rb_step.argtypes = [_dp, _dp, _dp, C.c_double, C.c_int, C.c_int64, _dp, _dp, C.c_int]
+    L.smc_host_guided_steps.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int64, _dp, _dp]
+    L.smc_host_rb_steps.argtypes = [_dp, _dp, _dp, C.c_double, C.c_int, C.c_int64, _dp, _dp]
     L.smc_get_summaries.argtypes = [h, C.c_int64, _dp, _dp, _dp]
     L.smc_sys_targets.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.c_int]
     L.smc_simulate.argtypes = [C.c_int, _dp, C.c_int64, C.c_uint64, _dp, _dp]
@@ -286,6 +288,21 @@ def host_guided_step(model_id, raw, kind, par, xp, z, y):
     return x, lw.value
 
 
+def host_guided_steps(model_id, raw, kind, par, xp, z, y):
+    """host_guided_step for n particles in one call: xp, z [d][n] -> (x [d][n], logw [n]) (smc_host_guided_steps; no GPU)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    par = _row_or_none(par)
+    d = lib().smc_model_dim(int(model_id))
+    xp = np.ascontiguousarray(xp, dtype=np.float64).reshape(d, -1)
+    z = np.ascontiguousarray(z, dtype=np.float64).reshape(d, -1)
+    assert xp.shape == z.shape
+    n = xp.shape[1]
+    x = np.zeros((d, n))
+    lw = np.zeros(n)
+    check(lib().smc_host_guided_steps(int(model_id), _d(raw), int(kind), _d(par), _d(xp), _d(z), float(y), n, _d(x), _d(lw)))
+    return x, lw
+
+
 def device_guided_step(model_id, raw, kind, par, xp, z, y, device=0):
     """the same for n particles on the device: xp, z [d][n] -> (x [d][n], logw [n]) (smc_device_guided_step)"""
     raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
@@ -312,6 +329,19 @@ def host_rb_step(raw, sp, z, y, first=False):
     lw = C.c_double()
     check(lib().smc_host_rb_step(_d(raw), _d(sp), _d(z), float(y), int(bool(first)), _d(s), C.byref(lw)))
     return s, lw.value
+
+
+def host_rb_steps(raw, sp, z, y, first=False):
+    """host_rb_step for n particles in one call: sp [4][n], z [2][n] -> (state [4][n], logw [n]) (smc_host_rb_steps; no GPU)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    sp = np.ascontiguousarray(sp, dtype=np.float64).reshape(4, -1)
+    z = np.ascontiguousarray(z, dtype=np.float64).reshape(2, -1)
+    assert raw.size == 5 and sp.shape[1] == z.shape[1]
+    n = sp.shape[1]
+    s = np.zeros((4, n))
+    lw = np.zeros(n)
+    check(lib().smc_host_rb_steps(_d(raw), _d(sp), _d(z), float(y), int(bool(first)), n, _d(s), _d(lw)))
+    return s, lw
 
 
 def device_rb_step(raw, sp, z, y, first=False, device=0):

@@ -320,6 +320,25 @@ extern "C" int smc_host_guided_step(int model_id, const double* raw, int kind, c
     });
     return SMC_OK;
 }
+// the same for n particles in the device twin's layouts, a plain loop on the host (the composed references of the tests)
+extern "C" int smc_host_guided_steps(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z,
+                                     double y, int64_t n, double* x, double* logw) {
+    if (!xp || !z || !x || !logw || n <= 0) return fail(SMC_EINVAL, "smc_host_guided_steps: bad argument");
+    Params P;
+    PropRow R;
+    if (!guided_params(model_id, raw, kind, par, P, R)) return fail(SMC_EINVAL, "smc_host_guided_steps: bad model, kind or row");
+    (void)by_guided_model(model_id, [&](auto M) {
+        constexpr int D = model_dim<decltype(M)::value>::value;
+        for (int64_t i = 0; i < n; ++i) {
+            double a[D], zz[D], xn[D];
+            for (int c = 0; c < D; ++c) { a[c] = xp[(size_t)c * n + i]; zz[c] = z[(size_t)c * n + i]; }
+            logw[i] = model_guided<decltype(M)::value>(P, R, a, zz, y, xn);
+            for (int c = 0; c < D; ++c) x[(size_t)c * n + i] = xn[c];
+        }
+        return hipSuccess;
+    });
+    return SMC_OK;
+}
 
 template <int MODEL>
 __global__ void k_guided_step(Params P, PropRow R, const double* xp, const double* z, double y, int64_t n, double* x, double* logw) {
@@ -370,6 +389,22 @@ extern "C" int smc_host_rb_step(const double* raw, const double* sp, const doubl
     double a[4] = {sp[0], sp[1], sp[2], sp[3]}, o[4];
     *logw = model_marginal_step<MODEL_UCSV_RB>(P, first != 0, a, z, y, o);
     for (int c = 0; c < 4; ++c) s[c] = o[c];
+    return SMC_OK;
+}
+// the same for n particles in the device twin's layouts, a plain loop on the host (the composed references of the tests)
+extern "C" int smc_host_rb_steps(const double* raw, const double* sp, const double* z, double y, int first, int64_t n, double* s,
+                                 double* logw) {
+    if (!raw || !sp || !z || !s || !logw || n <= 0) return fail(SMC_EINVAL, "smc_host_rb_steps: bad argument");
+    Params P;
+    for (int k = 0; k < NPARAM; ++k) P.raw[k] = k < model_nraw_rt(MODEL_UCSV_RB) ? raw[k] : 0.0;
+    derive_params(MODEL_UCSV_RB, P.raw, P.der);
+    for (int64_t i = 0; i < n; ++i) {
+        double a[4], zz[2], o[4];
+        for (int c = 0; c < 4; ++c) a[c] = sp[(size_t)c * n + i];
+        for (int c = 0; c < 2; ++c) zz[c] = z[(size_t)c * n + i];
+        logw[i] = model_marginal_step<MODEL_UCSV_RB>(P, first != 0, a, zz, y, o);
+        for (int c = 0; c < 4; ++c) s[(size_t)c * n + i] = o[c];
+    }
     return SMC_OK;
 }
 __global__ void k_rb_step(Params P, int first, const double* sp, const double* z, double y, int64_t n, double* s, double* logw) {

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import guided_reference as G
+import step_edge_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -123,22 +124,9 @@ def run(L, model, path, kind, rows, seed=7, T=12, nth=3):
 # ---- 4. device twin == host twin ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("model,kind", [(1, AFFINE), (1, OPTIMAL), (3, OPTIMAL)])
 def test_device_guided_step_equals_host(L, model, kind):
-    r = np.random.default_rng(100 * model + kind)
-    n, d = 4096, (3 if model == 3 else 1)
-    raw = [0.93, 1.3, 0.37, 0.11, 0.0, 1.0] if model == 1 else UC
-    par = POOR if kind == AFFINE else None
-    xp = r.normal(size=(d, n)) * 2
-    xp[0] += np.repeat([0.0, 1e2, 1e5, -1e5], n // 4)
-    if model == 3:
-        xp[1:] = r.uniform(-12, 4, size=(2, n))
-    z = r.normal(size=(d, n))
-    z[:, :8] = 0.0
-    z[:, 8:12] = -0.0
-    xp[0, :4] = 0.0
-    xp[0, 8:10] = -0.0
-    y = 0.7
+    raw, par, xp, z, y = step_edge_inputs.guided(model, kind)
     x, lw = L.device_guided_step(model, raw, kind, par, xp, z, y)
-    for i in range(n):
+    for i in range(xp.shape[1]):
         hx, hl = L.host_guided_step(model, raw, kind, par, xp[:, i], z[:, i], y)
         assert same(x[:, i], hx) and same([lw[i]], [hl]), (i, x[:, i], hx, lw[i], hl)
 

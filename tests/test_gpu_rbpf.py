@@ -16,6 +16,7 @@ import math
 import numpy as np
 import pytest
 
+import step_edge_inputs
 import test_gpu_guided as TG
 from quantile7_reference import check_sample_moments, quantile7
 from summary_reference import check_moments, check_quantiles, quantile_delta
@@ -79,18 +80,9 @@ def run(L, path, model=RB, seed=7, T=12, nth=3):
 # ---- 1. device twin == host twin ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("first", [False, True])
 def test_device_rb_step_equals_host(L, first):
-    r = np.random.default_rng(40 + first)
-    n = 4096
-    sp = np.stack([r.normal(size=n) * 2 + np.repeat([0.0, 1e2, 1e5, -1e5], n // 4), r.uniform(-12, 4, size=n), r.uniform(-12, 4, size=n),
-                   np.exp(r.uniform(-14, 4, size=n))])
-    z = r.normal(size=(2, n))
-    z[:, :8] = 0.0
-    z[:, 8:12] = -0.0
-    sp[0, :4] = 0.0
-    sp[0, 8:10] = -0.0
-    raw = [0.2, 0.35, 1e5 if first else 3.0, -11.5, 3.5]
-    s, lw = L.device_rb_step(raw, sp, z, 0.7, first)
-    for i in range(n):
+    raw, sp, z, y = step_edge_inputs.rb(first)
+    s, lw = L.device_rb_step(raw, sp, z, y, first)
+    for i in range(sp.shape[1]):
         hs, hl = L.host_rb_step(raw, sp[:, i], z[:, i], 0.7, first)
         assert same(s[:, i], hs) and same([lw[i]], [hl]), (i, s[:, i], hs, lw[i], hl)
 
