@@ -102,22 +102,40 @@ static hipError_t do_table(smc_filter_s* h, int emit, int first_emit, uint32_t t
     hipLaunchKernelGGL((k_table<TH>), dim3(h->v.ntheta), dim3(TH), 0, h->stream, h->v, h->cur, emit, first_emit, t_emit);
     return hipGetLastError();
 }
+// The by-value arguments of the launch of step t (StepHot, smc_kernels.h), derived HERE at every launch from the view, the current
+// buffer and t - never kept in the handle: the break points are allocated lazily and refilled (ensure_breaks), the buffers flip, and
+// smc_permute, slot copies and the bundle a new handle takes over change what the view's pointers mean.
+static StepHot step_hot(const smc_filter_s* h, uint32_t t, int emit_prev, double y, const double* y_host) {
+    const FilterView& v = h->v;
+    StepHot hot{};
+    StepLead& l = hot.lead;
+    l.seed = v.seed; l.t = t;
+    // the addresses of what the kernel loads before its first draw (StepEarly); filter th adds th (nseg + 1) resp. th nseg, th npad
+    const bool breaks = v.nseg > 1 && !v.systematic;   // (as ensure_breaks: the caller has made step t's row current)
+    l.brow = breaks ? v.brk + (size_t)(t - v.brk_t0) * (size_t)v.ntheta * ((size_t)v.nseg + 1) : nullptr;
+    l.rec0 = v.tabD ? (const void*)v.tabD : (const void*)v.segk[h->cur];
+    l.rec1 = v.tabD ? (const void*)v.tabsh : (const void*)v.segS[h->cur];
+    l.C = v.C[h->cur];
+    l.n32 = (uint32_t)v.n;
+    hot.nseg = v.nseg; hot.cur = h->cur; hot.emit_prev = emit_prev; hot.yval = y;
+    l.pack = step_pack(hot.nseg, hot.cur, hot.emit_prev);
+    // By value: ONE filter, no skip mask in force, the host copies of its row and stream id valid, and the observation
+    // at hand (the step API's y, or the host's copy of the series).  The results do not depend on the choice.
+    if (hot_legal(h) && !v.skip && (!v.y || y_host)) {
+        hot.by_value = 1;
+        l.stream0 = h->hot.stream0;
+        hot.prm0 = h->hot.prm0;
+        if (v.y) hot.yval = y_host[t];
+    }
+    return hot;
+}
 hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y, const double* y_host) {
     if (h->v.tabD) {
         hipError_t e = do_table(h, emit_prev, t == 1u ? 1 : 0, t - 1u);
         if (e != hipSuccess) return e;
         emit_prev = 0;
     }
-    // By value (StepHot): ONE filter, no skip mask in force, the host copies of its row and stream id valid, and the observation
-    // at hand (the step API's y, or the host's copy of the series).  The results do not depend on the choice.
-    StepHot hot{};
-    hot.seed = h->v.seed; hot.t = t; hot.nseg = h->v.nseg; hot.cur = h->cur; hot.emit_prev = emit_prev; hot.yval = y;
-    if (hot_legal(h) && !h->v.skip && (!h->v.y || y_host)) {
-        hot.by_value = 1;
-        hot.stream0 = h->hot.stream0;
-        hot.prm0 = h->hot.prm0;
-        if (h->v.y) hot.yval = y_host[t];
-    }
+    const StepHot hot = step_hot(h, t, emit_prev, y, y_host);
     if (h->v.prop_kind)   // a handle with a proposal: the guided kernels (the families smc_set_proposal accepts)
         return by_guided_model(h->model, [&](auto M) { return launch_step_g<decltype(M)::value>(h->v, h->geo, hot, h->stream); });
     return by_model(h->model, [&](auto M) { return launch_step<decltype(M)::value>(h->v, h->geo, hot, h->stream); });

@@ -22,6 +22,7 @@
 // All searches of a thread advance level by level together (2*NP independent loads in flight).
 #pragma once
 #include "smc_spec.h"
+#include <cstddef>
 #include <type_traits>
 
 namespace smc {
@@ -139,6 +140,12 @@ struct FilterView {
 // the kernel-argument block has arrived), SMC_STAMP_START stores (first pick numbers drawn, entry) in words 0 and 1 of the
 // workgroup's row in the SECOND half of the stamp buffer (k_persist's accumulators otherwise)
 #define SMC_CLOCK() __builtin_amdgcn_s_memrealtime()
+// phase stamp k with a clock value read earlier (stamp 0 of k_step: read at entry, stored once the view has arrived)
+#define SMC_STAMP_AT(v, k, clk)                                                                           \
+    do {                                                                                                  \
+        if ((v).dbg && threadIdx.x == 0)                                                                  \
+            (v).dbg[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (k)] = (clk);                     \
+    } while (0)
 #define SMC_STAMP_START(v, t_draw, t_entry)                                                               \
     do {                                                                                                  \
         if ((v).dbg && threadIdx.x == 0) {                                                                \
@@ -151,6 +158,7 @@ struct FilterView {
 #define SMC_ORDER_AFTER(x) do { } while (0)
 #define SMC_ABL(v, bit) 0
 #define SMC_STAMP(v, k) do { } while (0)
+#define SMC_STAMP_AT(v, k, clk) do { (void)(clk); } while (0)
 #define SMC_CLOCK() 0ull
 #define SMC_STAMP_START(v, t_draw, t_entry) do { (void)(t_draw); (void)(t_entry); } while (0)
 #endif
@@ -459,19 +467,22 @@ struct TablePre {
     uint64_t S2;    // 2 tid (k1, S1) and 2 tid + 1 (k2, S2)
 };
 // (VIEW: FilterView, or the same struct read in place from the kernel-argument segment - the persistent step kernel)
+// segk, segS, nseg: v.segk[cur], v.segS[cur] and v.nseg, which the callers hold before the view has arrived (k_step: by value at
+// the head of its arguments) - the two loads every workgroup waits for take no address from memory; the emitter's sums of squares
+// (full records only) are read through the view
 template <int THREADS, class VIEW, int RPT = 1>
-__device__ __forceinline__ TablePre table_preload(const VIEW& v, int cur, int th, bool emit) {
+__device__ __forceinline__ TablePre table_preload(const VIEW& v, const double* segk, const uint64_t* segS, int nseg, int cur, int th, bool emit) {
     TablePre p{-inf(), 0, 0, 0, -inf(), 0};
     const int tid = smc_tid();
-    const size_t base = (size_t)th * v.nseg;
+    const size_t base = (size_t)th * nseg;
     if (RPT == 2) {   // records 2 tid and 2 tid + 1 (the table itself, when somebody needs it, is built by table_prologue from memory)
-        if (2 * tid < v.nseg) { p.k1 = v.segk[cur][base + 2 * tid]; p.S1 = v.segS[cur][base + 2 * tid]; }
-        if (2 * tid + 1 < v.nseg) { p.k2 = v.segk[cur][base + 2 * tid + 1]; p.S2 = v.segS[cur][base + 2 * tid + 1]; }
+        if (2 * tid < nseg) { p.k1 = segk[base + 2 * tid]; p.S1 = segS[base + 2 * tid]; }
+        if (2 * tid + 1 < nseg) { p.k2 = segk[base + 2 * tid + 1]; p.S2 = segS[base + 2 * tid + 1]; }
         return p;
     }
-    if (v.nseg_p2 <= THREADS && tid < v.nseg) {
-        p.k1 = v.segk[cur][base + tid];
-        p.S1 = v.segS[cur][base + tid];
+    if (nseg <= THREADS && tid < nseg) {   // (nseg_p2 <= THREADS: THREADS is a power of two)
+        p.k1 = segk[base + tid];
+        p.S1 = segS[base + tid];
         if (emit) { p.hi1 = v.segS2hi[cur][base + tid]; p.lo1 = v.segS2lo[cur][base + tid]; }
     }
     return p;
@@ -487,7 +498,7 @@ __device__ __forceinline__ uint64_t table_prologue(const VIEW& v, int cur, int t
     double* red = (double*)L.scr;
 
     const bool one = v.nseg_p2 <= THREADS;
-    const TablePre pl = pre ? *pre : table_preload<THREADS>(v, cur, th, emit);
+    const TablePre pl = pre ? *pre : table_preload<THREADS>(v, v.segk[cur], v.segS[cur], v.nseg, cur, th, emit);
     const double k1 = pl.k1;
     const uint64_t S1 = pl.S1, hi1 = pl.hi1, lo1 = pl.lo1;
     double K = k1;
@@ -916,8 +927,19 @@ __host__ __device__ inline size_t step_lds_bytes(int nseg_p2, int threads, int n
 // A template parameter, not a workgroup-uniform branch: with both routes in one kernel the wait for the pointer route's loads
 // lands in front of the first draw of either, and the parameter row moves to vector registers (129 of them: three waves per
 // SIMD).  seed, t and nseg (= v.nseg: the block -> segment map) are taken from here on both routes.
+// EVERY launch (batched ones too) also finds there the ADDRESSES of what it loads before its first draw (StepEarly): the break-point
+// row of the step, the segment records (GTAB: the table), C of the buffer being resampled, and the particle count for the ragged
+// test.  The host derives them per launch (step_hot, smc_capi.hip); the kernel adds its filter's offsets from nseg and SEG.  No
+// load issued ahead of the draws takes its address from memory, and the first wait for the rest of the view stands behind them.
+struct StepEarly {
+    const uint64_t* brow;   // break points of step t: [ntheta][nseg + 1] (v.brk + (t - v.brk_t0) ntheta (nseg + 1)); nullptr: systematic
+    const void* rec0;       // v.segk[cur] (double);   GTAB launches: v.tabD (uint64_t)
+    const void* rec1;       // v.segS[cur] (uint64_t); GTAB launches: v.tabsh (int)
+    const uint64_t* C;      // v.C[cur]
+    uint32_t n32;           // v.n (<= 2^31)
+};
 template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS, bool PERSIST, class VIEW, bool GTAB = false, int RPT = 1, bool GUIDED = false, bool BYV = false>
-__device__ __forceinline__ void step_body(const VIEW& v, uint64_t seed, uint32_t t, uint32_t stream0, int nseg, int cur, int emit_prev,
+__device__ __forceinline__ void step_body(const VIEW& v, const StepEarly& ea, uint64_t seed, uint32_t t, uint32_t stream0, int nseg, int cur, int emit_prev,
                                           double yval, const Params* prm0, char* smem) {
     static_assert(!(BYV && PERSIST), "by value: one launch per step");
     const unsigned long long t_entry = SMC_CLOCK();
@@ -929,7 +951,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, uint64_t seed, uint32_t
     constexpr int NQ = 2 * NP;   // particles per thread
     constexpr int NSTAGE = nstage_for(SEG);
     constexpr int SEGP = lds_padded_len(SEG);   // padded length of a staged segment in LDS
-    int sb_ = logical_segment(blockIdx.x, nseg), th_ = blockIdx.y, tid_ = smc_tid();
+    int sb_ = logical_segment(blockIdx.x, nseg), th_ = BYV ? 0 : blockIdx.y, tid_ = smc_tid();   // (by value: ONE filter per launch)
     if (PERSIST) {   // opaque per iteration: the loop around this body must not hoist everything derived from them into registers
         asm volatile("" : "+v"(tid_));
     }
@@ -949,29 +971,23 @@ __device__ __forceinline__ void step_body(const VIEW& v, uint64_t seed, uint32_t
     else { prm = v.params[th]; y = v.y ? v.y[t] : yval; }
     PropRow prw;
     if constexpr (GUIDED) prw = v.prop[th];
-    const uint32_t n32 = (uint32_t)v.n;
-    const uint64_t* Cprev = v.C[cur] + (size_t)th * v.npad;
+    const uint32_t n32 = ea.n32;
+    const uint64_t* Cprev = ea.C + (size_t)th * ((size_t)nseg * SEG);   // (v.npad = nseg * SEG)
     const double* xprev = v.x[cur];
     uint64_t* scr;
-#ifdef SMC_ABLATE
-    if (SMC_ABL(v, 8) && (blockIdx.x & 8)) {   // experiment: stagger half of the workgroups by ~3.4 us
-        __builtin_amdgcn_s_sleep(127);
-        __builtin_amdgcn_s_sleep(127);
-    }
-#endif
-    SMC_STAMP(v, 0);
     SMC_PRIO(0);
 
     // Issue-early / use-late: every load whose address is known is issued BEFORE the random-number
     // work (Philox + Box-Muller is most of this kernel's VALU), which then runs under the latency.
     // (1) the break points of this workgroup's block of sorted uniforms (multinomial, MULTI)
     uint64_t F0 = 0, F1 = 0;
-    if (MULTI && !SYS) {
-        const uint64_t* Fb = v.brk + ((size_t)(t - v.brk_t0) * v.ntheta + th) * ((size_t)v.nseg + 1) + sb;
+    if (MULTI && !SYS) {   // (wave-uniform: first used behind the window prologue, and not waited for before)
+        const uint64_t* Fb = ea.brow + (size_t)th * ((size_t)nseg + 1) + sb;
         F0 = Fb[0];
         F1 = Fb[1];
     }
-    const TablePre tpre = (MULTI && !GTAB) ? table_preload<THREADS, VIEW, RPT>(v, cur, th, emit_prev && sb == 0) : TablePre{-inf(), 0, 0, 0, -inf(), 0};
+    const TablePre tpre = (MULTI && !GTAB) ? table_preload<THREADS, VIEW, RPT>(v, (const double*)ea.rec0, (const uint64_t*)ea.rec1, nseg, cur, th, emit_prev == 1 && sb == 0)   // (the sums of squares: full records only)
+                                           : TablePre{-inf(), 0, 0, 0, -inf(), 0};
     // (2) the 64-bit pick numbers of this thread's children
     unsigned long long t_draw = 0;
 #pragma unroll
@@ -987,6 +1003,12 @@ __device__ __forceinline__ void step_body(const VIEW& v, uint64_t seed, uint32_t
         rr[2 * k] = ((uint64_t)rw[k].v[1] << 32) | rw[k].v[0];
         rr[2 * k + 1] = ((uint64_t)rw[k].v[3] << 32) | rw[k].v[2];
     }
+#ifdef SMC_ABLATE
+    if (SMC_ABL(v, 8) && (blockIdx.x & 8)) {   // experiment: stagger half of the workgroups by ~3.4 us (behind the pick numbers: the
+        __builtin_amdgcn_s_sleep(127);         // switch is the view's, and nothing ahead of them waits for the view)
+        __builtin_amdgcn_s_sleep(127);
+    }
+#endif
     // this thread's child indices relative to the workgroup's first child (masked children j >= n take
     // the last real child's target: they are never stored as real particles)
     const uint32_t m_blk = (seg0 + SEG < n32 ? seg0 + SEG : n32) - seg0;   // children of this block (>= 1)
@@ -1009,12 +1031,12 @@ __device__ __forceinline__ void step_body(const VIEW& v, uint64_t seed, uint32_t
     int spec_lo = 0;
     if (SPEC) {
         spec_lo = sb - 1 < 0 ? 0 : sb - 1;
-        spec_lo = spec_lo + NSTAGE > v.nseg ? (v.nseg - NSTAGE < 0 ? 0 : v.nseg - NSTAGE) : spec_lo;
+        spec_lo = spec_lo + NSTAGE > nseg ? (nseg - NSTAGE < 0 ? 0 : nseg - NSTAGE) : spec_lo;
 #pragma unroll
         for (int sg = 0; sg < NSTAGE; ++sg) {
 #pragma unroll
             for (int k = 0; k < NP; ++k) stg[sg][k] = ulonglong2{0, 0};
-            if (spec_lo + sg < v.nseg) {
+            if (spec_lo + sg < nseg) {
                 const ulonglong2* src = reinterpret_cast<const ulonglong2*>(Cprev + (size_t)(spec_lo + sg) * SEG);
 #pragma unroll
                 for (int k = 0; k < NP; ++k) stg[sg][k] = src[tid + k * THREADS];
@@ -1059,9 +1081,10 @@ __device__ __forceinline__ void step_body(const VIEW& v, uint64_t seed, uint32_t
     const int tab_p2 = GTAB ? 0 : v.nseg_p2;   // table entries in LDS
     if (MULTI) {
         TableLds L = carve(smem, tab_p2);
-        if (GTAB) {
-            L.Dcum = v.tabD + (size_t)th * v.nseg_p2;
-            L.sh = v.tabsh + (size_t)th * v.nseg_p2;
+        if (GTAB) {   // (nseg > THREADS >= 2: v.nseg_p2, the next power of two, from the count at hand)
+            const size_t p2 = (size_t)1 << (32 - __builtin_clz((unsigned)(nseg - 1)));
+            L.Dcum = (uint64_t*)ea.rec0 + (size_t)th * p2;
+            L.sh = (int*)ea.rec1 + (size_t)th * p2;
         }
         scr = L.scr;
         // systematic: the step's one uniform, drawn by ONE thread (75 VALU instructions the other waves do
@@ -1209,7 +1232,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, uint64_t seed, uint32_t
         const TableLds L = carve(smem, v.nseg_p2);
         scr = L.scr;
         if (emit_prev && sb == 0) table_prologue<THREADS>(v, cur, th, L, true, t == 1u, t - 1u);
-        alive = v.segS[cur][(size_t)th * v.nseg];
+        alive = ((const uint64_t*)ea.rec1)[(size_t)th * nseg];
 #pragma unroll
         for (int i = 0; i < NQ; ++i) { bseg[i] = 0; Sseg[i] = alive; }
         if (SYS) {   // one segment: K = kb, shift = SH, table = (S >> SH)
@@ -1224,6 +1247,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, uint64_t seed, uint32_t
     }
 
     SMC_STAMP(v, 2);
+    SMC_STAMP_AT(v, 0, t_entry);   // (the phase profile starts at the entry clock: no stamp is stored ahead of the draws, the buffer is the view's)
     SMC_STAMP_START(v, t_draw, t_entry);
     SMC_STAMP(v, 3);
     // ---- a = resample(weights), level 2: iid pick inside the child's segment -------------------
@@ -1389,26 +1413,41 @@ __device__ __forceinline__ void step_body(const VIEW& v, uint64_t seed, uint32_t
     SMC_STAMP(v, 7);
 }
 
-// The host's side of a step launch's by-value arguments (smc_model.hip spreads them over the head of the parameter list: only
-// scalar parameters are preloaded into registers, so the struct does not travel as one)
-struct StepHot {
+// The head of k_step's kernel-argument block: its leading SCALAR parameters in this order (only scalars and pointers are
+// preloaded into registers, so the struct does not travel as one - smc_model.hip spreads it over the parameter list).  14 dwords,
+// no holes: what gfx950 preloads at most.
+struct StepLead {
     uint64_t seed;
     uint32_t t;
-    uint32_t stream0;    // by_value: the filter's stream id
-    int nseg;            // = FilterView::nseg
-    int cur, emit_prev;
+    uint32_t stream0;       // by_value: the filter's stream id
+    const uint64_t* brow;   // StepEarly, as the host derives it for this launch (step_hot, smc_capi.hip)
+    const void* rec0;
+    const void* rec1;
+    const uint64_t* C;
+    uint32_t pack;          // nseg (= FilterView::nseg <= 16384) | cur << 16 | emit_prev << 17
+    uint32_t n32;
+};
+static_assert(sizeof(StepLead) == 56 && offsetof(StepLead, brow) == 16 && offsetof(StepLead, C) == 40 && offsetof(StepLead, pack) == 48 &&
+              offsetof(StepLead, n32) == 52, "the leading scalars of k_step: 14 dwords without holes");
+__host__ __device__ constexpr uint32_t step_pack(int nseg, int cur, int emit_prev) { return (uint32_t)nseg | (uint32_t)cur << 16 | (uint32_t)emit_prev << 17; }
+// The host's side of a step launch's by-value arguments
+struct StepHot {
+    StepLead lead;
+    int nseg, cur, emit_prev;   // what lead.pack carries (launchers that emit nothing repack)
     int by_value;        // 1: stream0, prm0 and yval are filter 0's (single-filter launch, no skip mask, host copies valid): the BYV kernels
     double yval;         // by_value: y[t]; else the step API's observation (v.y == nullptr)
     Params prm0;         // by_value: the filter's parameter row
 };
 static_assert(std::is_trivially_copyable<StepHot>::value, "passed by value");
 
-// (seed .. yval: 10 dwords at the head of the kernel-argument block, preloaded; then the parameter row, then the view)
+// (seed .. n32: StepLead, 14 dwords at the head of the kernel-argument block, preloaded; then the observation, the parameter row, the view)
 template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS = false, bool GTAB = false, int RPT = 1, bool GUIDED = false, bool BYV = false>
-__global__ __launch_bounds__(THREADS) void k_step(uint64_t seed, uint32_t t, uint32_t stream0, int nseg, int cur, int emit_prev, double yval,
-                                                  Params prm0, FilterView v) {
+__global__ __launch_bounds__(THREADS) void k_step(uint64_t seed, uint32_t t, uint32_t stream0, const uint64_t* __restrict__ brow, const void* rec0, const void* rec1,
+                                                  const uint64_t* C, uint32_t pack, uint32_t n32, double yval, Params prm0, FilterView v) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    step_body<MODEL, THREADS, NP, MULTI, SYS, false, FilterView, GTAB, RPT, GUIDED, BYV>(v, seed, t, stream0, nseg, cur, emit_prev, yval, &prm0, smem);
+    const StepEarly ea{brow, rec0, rec1, C, n32};
+    step_body<MODEL, THREADS, NP, MULTI, SYS, false, FilterView, GTAB, RPT, GUIDED, BYV>(v, ea, seed, t, stream0, (int)(pack & 0xffffu), (int)(pack >> 16 & 1u),
+                                                                                         (int)(pack >> 17), yval, &prm0, smem);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1465,7 +1504,8 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 512 ? 4 : (THREADS >= 256 ? 4 
             }
         }
         if (v.dbg && tid == 0) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); acc[0] += now - acc[3]; acc[3] = now; }
-        step_body<MODEL, THREADS, NP, true, false, true>(v, v.seed, t, 0u, v.nseg, cur, 2, 0.0, (const Params*)nullptr, smem);
+        const StepEarly ea{v.brk + (size_t)(t - v.brk_t0) * v.ntheta * ((size_t)v.nseg + 1), v.segk[cur], v.segS[cur], v.C[cur], (uint32_t)v.n};
+        step_body<MODEL, THREADS, NP, true, false, true>(v, ea, v.seed, t, 0u, v.nseg, cur, 2, 0.0, (const Params*)nullptr, smem);
         if (v.dbg && tid == 0) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); acc[1] += now - acc[3]; acc[3] = now; }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains its write-through stores
         __syncthreads();

@@ -53,7 +53,8 @@ bool geo_default(int seg, Geo& g);
 bool geo_valid(int seg, int np, Geo& g);
 
 template <int MODEL> hipError_t launch_init(const FilterView& v, Geo g, int nxt, double y, hipStream_t s);
-// hot: the launch's by-value arguments (StepHot, smc_kernels.h); hot.seed and hot.nseg repeat the view's
+// hot: the launch's by-value arguments (StepHot, smc_kernels.h); hot.lead repeats the view's seed and carries the addresses of the
+// kernel's early loads as the caller derived them for THIS launch (the view's pointers, the current buffer, t)
 template <int MODEL> hipError_t launch_step(const FilterView& v, Geo g, const StepHot& hot, hipStream_t s);
 template <int MODEL> hipError_t launch_resident(const FilterView& v, int T, StepRec* recs, hipStream_t s);
 // opt-in persistent step kernel: the steps [t0, t1) of a multi-segment filter in one launch; hipErrorCooperativeLaunchTooLarge when

@@ -23,15 +23,16 @@ static hipError_t init_t(const FilterView& v, int nxt, double y, hipStream_t s) 
     return hipGetLastError();
 }
 #endif
-// one launch of k_step<..., BYV>: the kernel's parameter list is the hot scalars one by one at the head (what the wave finds
-// preloaded), the parameter row, the view
+// one launch of k_step<..., BYV>: the kernel's parameter list is the leading scalars (StepLead) one by one at the head (what the
+// wave finds preloaded), the observation, the parameter row, the view
 template <int THREADS, int NP, bool MULTI, bool SYS, bool GTAB, int RPT, bool BYV>
 static hipError_t step_launch(const FilterView& v, const StepHot& hot, int emit_prev, size_t lds, hipStream_t s) {
     static bool raised[16] = {};   // per instantiation and device
     hipError_t e = raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, SMC_G, BYV>, lds, raised);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, SMC_G, BYV>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, hot.seed, hot.t,
-                       hot.stream0, hot.nseg, hot.cur, emit_prev, hot.yval, hot.prm0, v);
+    const StepLead& l = hot.lead;
+    hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, SMC_G, BYV>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, l.seed, l.t,
+                       l.stream0, l.brow, l.rec0, l.rec1, l.C, step_pack(hot.nseg, hot.cur, emit_prev), l.n32, hot.yval, hot.prm0, v);
     return hipGetLastError();
 }
 template <int THREADS, int NP, bool SYS, bool BYV>
