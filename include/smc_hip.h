@@ -477,6 +477,50 @@ int smc_get_moments(smc_handle h, double* mean, double* var);
  * the SMC_SUMM_UNWEIGHTED mode (smc_set_summary_mode, which also names the one variant not offered). */
 int smc_get_quantiles(smc_handle h, int component, const double* p, int np, double* out);
 
+/* ---- the smoother: forward filtering, backward smoothing (FFBS; Kitagawa 1996, Doucet, Godsill and Andrieu 2000) -------------
+ * Everything above describes p(x_t | y_1:t).  The reference has no smoother: examples/inflation_example.jl:153-176 draws a
+ * "filtered trend".  The smoothed weights ws_t of p(x_t | y_1:T) on the clouds of a step-by-step run are
+ *     ws_T = w_T,    ws_t^i = w_t^i sum_j ws_{t+1}^j f(x_{t+1}^j | x_t^i) / sum_l w_t^l f(x_{t+1}^j | x_t^l),    t = T-1 .. 1,
+ * with w the dense weights of smc_get_state and f the model's transition density, evaluated in the log domain with the row
+ * maximum; no renormalisation.  Particles with w = 0 (sources) or ws = 0 (targets) are left out of every sum whatever their
+ * states.  The order of every sum is fixed (csrc/smc_spec.h "the smoother": chunks of 128 consecutive particles summed in
+ * ascending order with plain adds, chunk partials in ascending order), so the weights are a function of the recorded clouds and
+ * the parameter row alone: the same bits from the device, from the host twin, for a filter alone and inside a batch.
+ * A filter that collapsed at a recorded step (every weight 0 there) has NaN smoothed weights and moments at every step.
+ *   smc_history_begin  arms the record: T_cap slabs of x [d][n_theta][n_x] and w [n_theta][n_x] on the device (SMC_ENOMEM when
+ *                      they cannot be allocated: the handle is unchanged).  Every following smc_init / smc_step appends the
+ *                      state it leaves (a device-to-device copy and the dense weights, on the handle's stream, no host
+ *                      synchronisation); smc_init restarts the record.  Arming an armed handle replaces its record by an empty
+ *                      one.  While armed, the calls that would change the state without a recordable step return SMC_ESTATE and
+ *                      change nothing: smc_log_likelihood, smc_step_window, smc_step_commit, smc_permute, smc_copy_from (into
+ *                      the handle), smc_unpack_slots, smc_comm_exchange_slots, smc_pmmh_rejuvenate (either handle),
+ *                      smc_time_step_kernel, and smc_step beyond T_cap.
+ *   smc_history_len    steps recorded so far (0 for a handle that is not armed)
+ *   smc_history_get    the recorded state of step t (0-based): bit for bit what smc_get_state gave after that step.  x [d][n_theta][n_x],
+ *                      w [n_theta][n_x]; either may be NULL.  SMC_ESTATE when not armed, SMC_EINVAL for t outside the record
+ *   smc_history_end    frees the record and disarms; the handle then runs exactly the code of a handle that was never armed.  A
+ *                      fresh handle, and one that smc_create recycles from destroyed ones, is disarmed
+ *   smc_smooth         the backward pass over the recorded steps, T = smc_history_len: ws [T][n_theta][n_x], mean and var
+ *                      [T][d][n_theta] (any may be NULL).  The moments are those of smc_get_moments applied to (x_t, ws_t): mean =
+ *                      sum ws x, var = sum ws (x - mean)^2 (centred second pass, the fixed order above, the accuracy stated there;
+ *                      NaN when every ws is 0).  The handle's parameter rows must be those the steps ran with.  Any proposal and
+ *                      either resampler: the backward pass uses the transition only.  May be called again after more steps.
+ *                      SMC_EINVAL: SMC_MODEL_UCSV_RB (its rows m and P are functions of the whole path: no transition density);
+ *                      a parameter row whose transition scale (Q; sigma; gamma_eps, gamma_eta) is not a positive finite number.
+ *                      SMC_ESTATE: nothing recorded.  Cost: 2 n_x^2 (T - 1) n_theta transition densities, measured in
+ *                      profiles/smoother_cost.log (DESIGN.md 2e "Cost"); at most 65535 chunks of 128 particles per filter
+ *   smc_host_transition_logpdf  logpdf(transition(model, xp), x) by the specification on the host (no GPU): xp, x [d]
+ *   smc_host_smooth    the same specification for ONE filter on the host (no GPU), the same bits: x [T][d][n], w [T][n] ->
+ *                      ws [T][n], mean / var [T][d] (both or neither NULL) */
+int smc_history_begin(smc_handle h, int64_t T_cap);
+int smc_history_len(smc_handle h, int64_t* len);
+int smc_history_get(smc_handle h, int64_t t, double* x /*[d][n_theta][n_x]*/, double* w /*[n_theta][n_x]*/);
+int smc_history_end(smc_handle h);
+int smc_smooth(smc_handle h, double* ws /*[T][n_theta][n_x] or NULL*/, double* mean /*[T][d][n_theta] or NULL*/, double* var /*[T][d][n_theta] or NULL*/);
+int smc_host_transition_logpdf(int model_id, const double* raw, const double* xp /*[d]*/, const double* x /*[d]*/, double* out);
+int smc_host_smooth(int model_id, const double* raw, int64_t T, int64_t n, const double* x /*[T][d][n]*/, const double* w /*[T][n]*/,
+                    double* ws /*[T][n]*/, double* mean /*[T][d] or NULL*/, double* var /*[T][d] or NULL*/);
+
 /* ---- host-side helpers (no GPU needed) ---------------------------------------------------------*/
 /* simulate(rng, model, T) -> (x, y)                         src/state_space_models.jl:11-26 */
 int smc_simulate(int model_id, const double* raw, int64_t T, uint64_t seed, double* x /*[smc_simulate_dim][T] or NULL*/, double* y /*[T]*/);

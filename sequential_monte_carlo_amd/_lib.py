@@ -35,6 +35,8 @@ EXPORTS = [
     "smc_ibis_summary", "smc_ibis_set_summaries", "smc_ibis_get_summaries", "smc_host_ibis_summary",
     "smc_ibis_window_ess", "smc_ibis_resample", "smc_ibis_theta_moments", "smc_ibis_get_moved", "smc_host_theta_moments",
     "smc_host_rw_factor_cov",
+    "smc_history_begin", "smc_history_len", "smc_history_get", "smc_history_end", "smc_smooth", "smc_host_transition_logpdf",
+    "smc_host_smooth",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -193,6 +195,13 @@ def lib():
     L.smc_ibis_get_moved.argtypes = [h, C.POINTER(C.c_uint8)]
     L.smc_host_theta_moments.argtypes = [_dp, _dp, C.c_int64, C.c_int, C.c_int, _dp, _dp]
     L.smc_host_rw_factor_cov.argtypes = [_dp, C.c_int, _dp, _ip]
+    L.smc_history_begin.argtypes = [h, C.c_int64]
+    L.smc_history_len.argtypes = [h, C.POINTER(C.c_int64)]
+    L.smc_history_get.argtypes = [h, C.c_int64, _dp, _dp]
+    L.smc_history_end.argtypes = [h]
+    L.smc_smooth.argtypes = [h, _dp, _dp, _dp]
+    L.smc_host_transition_logpdf.argtypes = [C.c_int, _dp, _dp, _dp, _dp]
+    L.smc_host_smooth.argtypes = [C.c_int, _dp, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp]
     L.smc_last_error.restype = C.c_char_p
     L.smc_version.restype = C.c_char_p
     _lib = L
@@ -357,6 +366,7 @@ def device_rb_step(raw, sp, z, y, first=False, device=0):
     return s, lw
 
 
+SMOOTH_CH = 128   # SMOOTH_CH of csrc/smc_spec.h: particles per chunk of the smoother's sums (part of its numerical contract)
 OUTER_SEG = 8     # SMC_OUTER_SEG: entries per segment of the outer level's integer normalisation
 
 
@@ -779,6 +789,61 @@ class Handle:
 
     def synchronize(self):
         check(lib().smc_synchronize(self._h))
+
+    def history_begin(self, T_cap):
+        """record the state every following init / step leaves, up to T_cap steps (smc_history_begin); init restarts the record"""
+        check(lib().smc_history_begin(self._h, int(T_cap)))
+
+    def history_len(self):
+        n = C.c_int64()
+        check(lib().smc_history_len(self._h, C.byref(n)))
+        return n.value
+
+    def history_get(self, t):
+        """(x [d][n_theta][n_x], w [n_theta][n_x]) of recorded step t (0-based): what state() gave after that step"""
+        x = np.zeros((self.d, self.n_theta, self.n_x))
+        w = np.zeros((self.n_theta, self.n_x))
+        check(lib().smc_history_get(self._h, int(t), _d(x), _d(w)))
+        return x, w
+
+    def history_end(self):
+        check(lib().smc_history_end(self._h))
+
+    def smooth(self, weights=True, moments=True):
+        """the FFBS backward pass over the recorded steps (smc_smooth): (ws [T][n_theta][n_x] or None, mean [T][d][n_theta] or
+        None, var or None)"""
+        T = self.history_len()
+        ws = np.zeros((T, self.n_theta, self.n_x)) if weights else None
+        mean = np.zeros((T, self.d, self.n_theta)) if moments else None
+        var = np.zeros((T, self.d, self.n_theta)) if moments else None
+        check(lib().smc_smooth(self._h, _d(ws), _d(mean), _d(var)))
+        return ws, mean, var
+
+
+def host_transition_logpdf(model_id, raw, xp, x):
+    """logpdf(transition(model, xp), x) by the specification on the host (smc_host_transition_logpdf; no GPU)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    xp = np.ascontiguousarray(xp, dtype=np.float64).ravel()
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    d = lib().smc_model_dim(int(model_id))
+    assert xp.size == d and x.size == d
+    out = C.c_double()
+    check(lib().smc_host_transition_logpdf(int(model_id), _d(raw), _d(xp), _d(x), C.byref(out)))
+    return out.value
+
+
+def host_smooth(model_id, raw, x, w, moments=True):
+    """the FFBS smoother of ONE filter by the specification on the host (smc_host_smooth; no GPU): x [T][d][n], w [T][n] ->
+    (ws [T][n], mean [T][d], var [T][d]); moments=False: (ws, None, None)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    d = lib().smc_model_dim(int(model_id))
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    T, n = w.shape
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(T, d, n)
+    ws = np.zeros((T, n))
+    mean, var = (np.zeros((T, d)), np.zeros((T, d))) if moments else (None, None)
+    check(lib().smc_host_smooth(int(model_id), _d(raw), T, n, _d(x), _d(w), _d(ws), _d(mean), _d(var)))
+    return ws, mean, var
 
 
 def host_ibis_summary(rows, x, S, logw, ahead=0):

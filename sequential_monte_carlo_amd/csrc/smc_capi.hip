@@ -375,6 +375,7 @@ extern "C" int smc_destroy(smc_handle h) {
     if (h->h_params && !kept) (void)hipHostFree(h->h_params);
     if (h->d_prop) (void)hipFree(h->d_prop);
     if (h->h_prop) (void)hipHostFree(h->h_prop);
+    history_free(h);
     (void)hipFree(h->skip.d_mask); (void)hipFree(h->skip.d_order);
     if (h->win.h_out) (void)hipHostFree(h->win.h_out);
     if (h->summ.h_once) (void)hipHostFree(h->summ.h_once);
@@ -587,6 +588,10 @@ extern "C" int smc_init(smc_handle h, double y1, double* logmu) {
     h->v.host_seq = 0;
     HIPCHK(le);
     if (rc) return rc;
+    if (history_armed(h)) {   // smc_init restarts the record
+        h->hist.len = 0;
+        if (const int hr = history_append(h)) return hr;
+    }
     return seq ? wait_ticket(h, seq, logmu, nullptr) : finish_elapsed(h, nullptr, logmu, nullptr);
 }
 
@@ -594,6 +599,7 @@ extern "C" int smc_init(smc_handle h, double y1, double* logmu) {
 extern "C" int smc_step(smc_handle h, double y_t, double* logmu, double* ess) {
     if (!h) return fail(SMC_EINVAL, "smc_step: NULL handle");
     if (!h->inited) return fail(SMC_ESTATE, "smc_step: call smc_init (bootstrap_filter) first");
+    if (history_armed(h) && h->hist.len >= h->hist.cap) return fail(SMC_ESTATE, "smc_step: the record is full (smc_history_begin's T_cap)");
     h->win.k = 0;   // an uncommitted window is dropped
     HIPCHK(hipSetDevice(h->device));
     h->v.y = nullptr; h->v.trace_logmu = nullptr; h->v.trace_ess = nullptr;
@@ -611,6 +617,7 @@ extern "C" int smc_step(smc_handle h, double y_t, double* logmu, double* ess) {
     h->v.host_seq = 0;
     HIPCHK(le);
     if (rc) return rc;
+    if (history_armed(h) && (rc = history_append(h))) return rc;
     return seq ? wait_ticket(h, seq, logmu, ess) : finish_elapsed(h, nullptr, logmu, ess);
 }
 
@@ -624,6 +631,7 @@ static int launch_window_steps(smc_handle h, int k) {
 extern "C" int smc_step_window(smc_handle h, const double* y, int k, double* logmu, double* ess) {
     if (!h || !y) return fail(SMC_EINVAL, "smc_step_window: NULL argument");
     if (!h->inited) return fail(SMC_ESTATE, "smc_step_window: call smc_init (bootstrap_filter) first");
+    if (history_armed(h)) return history_refuse("smc_step_window");
     if (k < 1 || k > WIN_MAX) return fail(SMC_EINVAL, "smc_step_window: 1 <= k <= 64");
     if (h->v.nseg != 1 || !resident_supported(h->model, h->v.seg))
         return fail(SMC_EINVAL, "smc_step_window: needs filters that fit the LDS-resident kernel (one segment); use smc_step");
@@ -656,6 +664,7 @@ extern "C" int smc_step_window(smc_handle h, const double* y, int k, double* log
 }
 extern "C" int smc_step_commit(smc_handle h, int j) {
     if (!h) return fail(SMC_EINVAL, "smc_step_commit: NULL handle");
+    if (history_armed(h)) return history_refuse("smc_step_commit");
     if (h->win.k == 0) return fail(SMC_ESTATE, "smc_step_commit: no window pending (smc_step_window)");
     if (j < 0 || j > h->win.k) return fail(SMC_EINVAL, "smc_step_commit: 0 <= j <= steps of the window");
     HIPCHK(hipSetDevice(h->device));

@@ -67,6 +67,7 @@ extern "C" int smc_pmmh_rejuvenate(smc_handle h, smc_handle main, const double* 
     if (!h || !y || !chol || !scales || !filter_seeds || !theta || !logZ) return fail(SMC_EINVAL, "smc_pmmh_rejuvenate: NULL argument");
     if (!h->pm.cfg) return fail(SMC_ESTATE, "smc_pmmh_rejuvenate: smc_pmmh_configure has not been called");
     if (T <= 0 || chain < 0) return fail(SMC_EINVAL, "smc_pmmh_rejuvenate: bad T or chain");
+    if (history_armed(h) || (main && history_armed(main))) return history_refuse("smc_pmmh_rejuvenate");
     if (main) {
         if (main == h) return fail(SMC_EINVAL, "smc_pmmh_rejuvenate: main and proposal handles are the same");
         const FilterView &a = main->v, &b = h->v;

@@ -123,6 +123,7 @@ extern "C" int smc_log_likelihood(smc_handle h, const double* y, int64_t T, doub
     if (!h || !y) return fail(SMC_EINVAL, "smc_log_likelihood: NULL argument");
     if (T <= 0) return fail(SMC_EINVAL, "smc_log_likelihood: T must be positive");
     if (!h->have_params) return fail(SMC_ESTATE, "smc_log_likelihood: smc_set_params has not been called");
+    if (history_armed(h)) return history_refuse("smc_log_likelihood");
     h->win.k = 0;   // an uncommitted window is dropped
     HIPCHK(hipSetDevice(h->device));
     int rc = ensure_y(h, T);
@@ -177,6 +178,7 @@ extern "C" int smc_time_step_kernel(smc_handle h, const double* y, int64_t T, in
                                     double* min_ms) {
     if (!h || !y || T < 2 || nsample < 1) return fail(SMC_EINVAL, "smc_time_step_kernel: bad argument");
     if (!h->have_params) return fail(SMC_ESTATE, "smc_time_step_kernel: smc_set_params has not been called");
+    if (history_armed(h)) return history_refuse("smc_time_step_kernel");
     HIPCHK(hipSetDevice(h->device));
     int rc = ensure_y(h, T);
     if (rc) return rc;

@@ -13,6 +13,12 @@ hipError_t copy_slots(const FilterView& dst, int dcur, const FilterView& src, in
     return hipGetLastError();
 }
 
+hipError_t enqueue_dense_weights(smc_filter_s* h, double* w) {
+    const FilterView& v = h->v;
+    hipLaunchKernelGGL(k_dense_weights, dim3((unsigned)((v.n + 255) / 256), v.ntheta), dim3(256), 0, h->stream, v, h->cur, w);
+    return hipGetLastError();
+}
+
 extern "C" int smc_get_state(smc_handle h, double* x, double* w, int32_t* anc) {
     if (!h) return fail(SMC_EINVAL, "smc_get_state: NULL handle");
     if (!h->inited) return fail(SMC_ESTATE, "smc_get_state: filter not initialised");
@@ -44,6 +50,7 @@ extern "C" int smc_get_state(smc_handle h, double* x, double* w, int32_t* anc) {
 extern "C" int smc_permute(smc_handle h, const int32_t* a) {
     if (!h || !a) return fail(SMC_EINVAL, "smc_permute: NULL argument");
     if (!h->inited) return fail(SMC_ESTATE, "smc_permute: filter not initialised");
+    if (history_armed(h)) return history_refuse("smc_permute");
     h->win.k = 0;
     for (int m = 0; m < h->v.ntheta; ++m)
         if (a[m] < 0 || a[m] >= h->v.ntheta) return fail(SMC_EINVAL, "smc_permute: index out of range");
@@ -74,6 +81,7 @@ extern "C" int smc_copy_from(smc_handle dst, smc_handle src, const uint8_t* mask
     if (!dst || !src || !mask) return fail(SMC_EINVAL, "smc_copy_from: NULL argument");
     if (dst == src) return fail(SMC_EINVAL, "smc_copy_from: dst and src are the same handle");
     if (!dst->inited || !src->inited) return fail(SMC_ESTATE, "smc_copy_from: filter not initialised");
+    if (history_armed(dst)) return history_refuse("smc_copy_from");
     dst->win.k = 0;
     const FilterView &a = dst->v, &b = src->v;
     if (dst->model != src->model || a.n != b.n || a.seg != b.seg || a.ntheta != b.ntheta || dst->device != src->device)
@@ -102,6 +110,7 @@ extern "C" int smc_slot_bytes(smc_handle h, int64_t* bytes) {
 static int pack_unpack(smc_handle h, const int32_t* idx, int64_t k, void* buf, bool pack) {
     if (!h || k < 0 || (k > 0 && (!idx || !buf))) return fail(SMC_EINVAL, "smc_pack/unpack_slots: bad argument");
     if (!h->inited) return fail(SMC_ESTATE, "smc_pack/unpack_slots: filter not initialised");
+    if (!pack && history_armed(h)) return history_refuse("smc_unpack_slots");
     if (!pack) h->win.k = 0;
     if (k == 0) return SMC_OK;
     if (!pack) hot_invalidate(h);   // slots written on the device (the exchange of smc_comm.hip ends here too)

@@ -1,0 +1,222 @@
+// smc_capi_smooth.hip -- the record of a step-by-step run (smc_history_*) and the FFBS particle smoother over it (smc_smooth):
+// forward filtering by the step kernels as they are, backward smoothing by the all-pairs kernels of smc_smooth_kernels.h.
+// Specification: smc_spec.h "the smoother"; the host twin (smc_host_smooth) lives in smc_util.hip.
+#include "smc_host.h"
+#include "smc_smooth_kernels.h"
+
+#include <cstring>
+#include <vector>
+
+using namespace smc;
+
+int history_refuse(const char* who) {
+    return fail(SMC_ESTATE, std::string(who) + ": the handle records its steps (smc_history_begin) and this call would change the state "
+                                               "without a recordable step; call smc_history_end first");
+}
+
+void history_free(smc_filter_s* h) {
+    (void)hipFree(h->hist.d_x);   // (d_w lives in the same allocation)
+    (void)hipFree(h->hist.d_ws);
+    (void)hipFree(h->hist.d_tmp);
+    h->hist = {};
+}
+
+static size_t cloud_words(const smc_filter_s* h) { return (size_t)h->v.ntheta * (size_t)h->v.n; }
+
+extern "C" int smc_history_begin(smc_handle h, int64_t T_cap) {
+    if (!h) return fail(SMC_EINVAL, "smc_history_begin: NULL handle");
+    if (T_cap < 1) return fail(SMC_EINVAL, "smc_history_begin: T_cap must be positive");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nw = cloud_words(h), per_step = nw * ((size_t)h->d + 1);
+    if (per_step > ((size_t)1 << 60) / 8 / (size_t)T_cap) return fail(SMC_ENOMEM, "smc_history_begin: a record of that many bytes cannot be allocated");
+    double* slab = nullptr;
+    const hipError_t e = hipMalloc((void**)&slab, per_step * (size_t)T_cap * 8);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();   // (the failed allocation is this call's result, not the next call's)
+        return fail(SMC_ENOMEM, std::string("smc_history_begin: hipMalloc of the record: ") + hipGetErrorString(e));
+    }
+    if (h->hist.d_x) {   // armed before: the new record replaces the old one
+        HIPCHK(hipStreamSynchronize(h->stream));
+        (void)hipFree(h->hist.d_x);
+    }
+    h->hist.d_x = slab;
+    h->hist.d_w = slab + nw * (size_t)h->d * (size_t)T_cap;
+    h->hist.cap = T_cap;
+    h->hist.len = 0;
+    h->hist.armed = true;
+    return SMC_OK;
+}
+
+extern "C" int smc_history_end(smc_handle h) {
+    if (!h) return fail(SMC_EINVAL, "smc_history_end: NULL handle");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));
+    history_free(h);
+    return SMC_OK;
+}
+
+extern "C" int smc_history_len(smc_handle h, int64_t* len) {
+    if (!h || !len) return fail(SMC_EINVAL, "smc_history_len: NULL argument");
+    *len = h->hist.armed ? h->hist.len : 0;
+    return SMC_OK;
+}
+
+// the state smc_init / smc_step just left, appended on the handle's stream: a device-to-device copy of x and the dense weights
+int history_append(smc_handle h) {
+    if (h->hist.len >= h->hist.cap) return fail(SMC_ESTATE, "step API: the record is full (smc_history_begin's T_cap)");
+    const FilterView& v = h->v;
+    const size_t nw = cloud_words(h), t = (size_t)h->hist.len;
+    HIPCHK(hipMemcpy2DAsync(h->hist.d_x + t * nw * (size_t)h->d, (size_t)v.n * 8, v.x[h->cur], (size_t)v.npad * 8, (size_t)v.n * 8,
+                            (size_t)h->d * v.ntheta, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(enqueue_dense_weights(h, h->hist.d_w + t * nw));
+    h->hist.len += 1;
+    return SMC_OK;
+}
+
+extern "C" int smc_history_get(smc_handle h, int64_t t, double* x, double* w) {
+    if (!h) return fail(SMC_EINVAL, "smc_history_get: NULL handle");
+    if (!h->hist.armed) return fail(SMC_ESTATE, "smc_history_get: the handle does not record (smc_history_begin)");
+    if (t < 0 || t >= h->hist.len) return fail(SMC_EINVAL, "smc_history_get: step out of range");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t nw = cloud_words(h);
+    if (x) HIPCHK(hipMemcpy(x, h->hist.d_x + (size_t)t * nw * (size_t)h->d, nw * (size_t)h->d * 8, hipMemcpyDeviceToHost));
+    if (w) HIPCHK(hipMemcpy(w, h->hist.d_w + (size_t)t * nw, nw * 8, hipMemcpyDeviceToHost));
+    return SMC_OK;
+}
+
+// ---- the backward pass ---------------------------------------------------------------------------------------------------
+namespace {
+struct SmoothPlan {
+    int nchunk;
+    size_t o_pmax, o_part, o_logD, o_rmax, o_mom, o_rows, o_dead, bytes;   // offsets into hist.d_tmp, in bytes
+};
+SmoothPlan plan_of(const smc_filter_s* h, int64_t T) {
+    SmoothPlan p{};
+    const size_t nw = cloud_words(h), nt = (size_t)h->v.ntheta;
+    p.nchunk = (int)((h->v.n + SMOOTH_CH - 1) / SMOOTH_CH);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    p.o_pmax = take((size_t)p.nchunk * nw * 8);
+    p.o_part = take((size_t)p.nchunk * nw * 8);
+    p.o_logD = take(nw * 8);
+    p.o_rmax = take(nw * 8);
+    p.o_mom = take((size_t)T * nt * (size_t)p.nchunk * 8);
+    p.o_rows = take(nt * sizeof(SmoothRow));
+    p.o_dead = take(nt * sizeof(int));
+    p.bytes = off;
+    return p;
+}
+
+template <int MODEL, int PASS>
+hipError_t launch_pairs(const SmoothArgs& a, int threads, hipStream_t s) {
+    const dim3 grid((unsigned)((a.n + threads - 1) / threads), (unsigned)a.ntheta, (unsigned)a.nchunk);
+    hipLaunchKernelGGL((k_smooth_pairs<MODEL, PASS>), grid, dim3(threads), 0, s, a);
+    return hipGetLastError();
+}
+template <int MODEL>
+hipError_t backward_step(const SmoothArgs& a01, const SmoothArgs& a2, int threads, double* logD, double* rowmax, const double* w_t,
+                         const int* dead, double* ws_t, hipStream_t s) {
+    hipError_t e;
+    const dim3 g1((unsigned)((a01.n + 255) / 256), (unsigned)a01.ntheta);
+    if ((e = launch_pairs<MODEL, 0>(a01, threads, s)) != hipSuccess) return e;
+    if (a01.nmax == 1 && a01.rmax == rowmax) {   // many chunks: the row maxima once per target
+        hipLaunchKernelGGL(k_smooth_rowmax, g1, dim3(256), 0, s, a01.n, a01.ntheta, a01.nchunk, a01.pmax, rowmax);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if ((e = launch_pairs<MODEL, 1>(a01, threads, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_smooth_logd, g1, dim3(256), 0, s, a01.n, a01.ntheta, a01.nchunk, a01.rmax, a01.nmax, a01.part, logD);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_pairs<MODEL, 2>(a2, threads, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_smooth_finish, g1, dim3(256), 0, s, a2.n, a2.ntheta, a2.nchunk, a2.part, w_t, dead, ws_t);
+    return hipGetLastError();
+}
+}  // namespace
+
+extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
+    if (!h) return fail(SMC_EINVAL, "smc_smooth: NULL handle");
+    if (h->model != MODEL_LG1D && h->model != MODEL_SV1D && h->model != MODEL_UCSV3D)
+        return fail(SMC_EINVAL, "smc_smooth: SMC_MODEL_UCSV_RB has no transition density of its state rows (m and P are functions of the whole "
+                                "path); smooth a UCSV3D filter instead");
+    if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, "smc_smooth: nothing is recorded (smc_history_begin, then smc_init / smc_step)");
+    const FilterView& v = h->v;
+    const int64_t T = h->hist.len, n = v.n;
+    const size_t nw = cloud_words(h), nt = (size_t)v.ntheta, d = (size_t)h->d;
+    if ((n + SMOOTH_CH - 1) / SMOOTH_CH > 65535) return fail(SMC_EINVAL, "smc_smooth: more than 65535 chunks of particles (the backward pass is quadratic in n_x)");
+    HIPCHK(hipSetDevice(h->device));
+    // the rows the steps ran with, as the device holds them (the PMMH kernels write them there), and their constants
+    std::vector<Params> prm(nt);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(prm.data(), h->d_params, nt * sizeof(Params), hipMemcpyDeviceToHost));
+    std::vector<SmoothRow> rows(nt);
+    for (size_t m = 0; m < nt; ++m)
+        if (!smooth_row(h->model, prm[m].raw, rows[m]))
+            return fail(SMC_EINVAL, "smc_smooth: the transition scale of filter " + std::to_string(m) + " is not a positive finite number");
+    const SmoothPlan p = plan_of(h, T);
+    if (p.bytes > h->hist.tmp_bytes) {
+        (void)hipFree(h->hist.d_tmp);
+        h->hist.d_tmp = nullptr; h->hist.tmp_bytes = 0;
+        if (hipMalloc((void**)&h->hist.d_tmp, p.bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SMC_ENOMEM, "smc_smooth: hipMalloc of the scratch of the backward pass");
+        }
+        h->hist.tmp_bytes = p.bytes;
+    }
+    const size_t mom_words = 2 * d * nt;
+    if (T > h->hist.ws_cap) {
+        (void)hipFree(h->hist.d_ws);
+        h->hist.d_ws = nullptr; h->hist.ws_cap = 0;
+        if (hipMalloc((void**)&h->hist.d_ws, (size_t)h->hist.cap * (nw + mom_words) * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SMC_ENOMEM, "smc_smooth: hipMalloc of the smoothed weights");
+        }
+        h->hist.ws_cap = h->hist.cap;
+    }
+    char* tmp = (char*)h->hist.d_tmp;
+    double *pmax = (double*)(tmp + p.o_pmax), *part = (double*)(tmp + p.o_part), *logD = (double*)(tmp + p.o_logD), *rowmax = (double*)(tmp + p.o_rmax), *momtmp = (double*)(tmp + p.o_mom);
+    SmoothRow* d_rows = (SmoothRow*)(tmp + p.o_rows);
+    int* dead = (int*)(tmp + p.o_dead);
+    double *d_ws = h->hist.d_ws, *d_mom = h->hist.d_ws + (size_t)h->hist.ws_cap * nw;
+    hipStream_t s = h->stream;
+    HIPCHK(hipEventRecord(h->ev0, s));
+    HIPCHK(hipMemcpyAsync(d_rows, rows.data(), nt * sizeof(SmoothRow), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(dead, 0, nt * sizeof(int), s));
+    hipLaunchKernelGGL(k_smooth_dead, dim3((unsigned)T, (unsigned)nt), dim3(256), 0, s, n, (int)nt, h->hist.d_w, dead);
+    HIPCHK(hipGetLastError());
+    // a lone small filter is cut into tiles of one wave, so that its few chunks still spread over the chip; the bits do not depend on it
+    const int64_t wg256 = ((n + 255) / 256) * (int64_t)nt * p.nchunk;
+    const int threads = wg256 >= 1024 ? 256 : 64;
+    const dim3 g1((unsigned)((n + 255) / 256), (unsigned)nt);
+    hipLaunchKernelGGL(k_smooth_finish, g1, dim3(256), 0, s, n, (int)nt, p.nchunk, (const double*)nullptr, h->hist.d_w + (size_t)(T - 1) * nw, dead,
+                       d_ws + (size_t)(T - 1) * nw);
+    HIPCHK(hipGetLastError());
+    for (int64_t t = T - 2; t >= 0; --t) {
+        const double *x_t = h->hist.d_x + (size_t)t * nw * d, *x_n = x_t + nw * d, *w_t = h->hist.d_w + (size_t)t * nw;
+        double *ws_t = d_ws + (size_t)t * nw, *ws_n = ws_t + nw;
+        const bool direct = p.nchunk <= SMOOTH_MAX_DIRECT;
+        const SmoothArgs a01{n, (int)nt, p.nchunk, x_n, x_t, w_t, nullptr, pmax, direct ? pmax : rowmax, direct ? p.nchunk : 1, part, d_rows};
+        const SmoothArgs a2{n, (int)nt, p.nchunk, x_t, x_n, ws_n, logD, pmax, nullptr, 0, part, d_rows};
+        hipError_t e = hipErrorInvalidValue;
+        if (h->model == MODEL_LG1D) e = backward_step<MODEL_LG1D>(a01, a2, threads, logD, rowmax, w_t, dead, ws_t, s);
+        else if (h->model == MODEL_SV1D) e = backward_step<MODEL_SV1D>(a01, a2, threads, logD, rowmax, w_t, dead, ws_t, s);
+        else e = backward_step<MODEL_UCSV3D>(a01, a2, threads, logD, rowmax, w_t, dead, ws_t, s);
+        HIPCHK(e);
+    }
+    if (mean || var) {
+        hipLaunchKernelGGL(k_smooth_moments, dim3((unsigned)T, (unsigned)nt), dim3(256), 0, s, n, (int)nt, p.nchunk, (int)d, h->hist.d_x, d_ws, dead,
+                           momtmp, d_mom);
+        HIPCHK(hipGetLastError());
+    }
+    int rc = finish_elapsed(h);
+    if (rc) return rc;
+    if (ws) HIPCHK(hipMemcpy(ws, d_ws, (size_t)T * nw * 8, hipMemcpyDeviceToHost));
+    if (mean || var) {
+        std::vector<double> mv((size_t)T * mom_words);
+        HIPCHK(hipMemcpy(mv.data(), d_mom, mv.size() * 8, hipMemcpyDeviceToHost));
+        for (int64_t t = 0; t < T; ++t) {
+            if (mean) memcpy(mean + (size_t)t * d * nt, mv.data() + (size_t)t * mom_words, d * nt * 8);
+            if (var) memcpy(var + (size_t)t * d * nt, mv.data() + (size_t)t * mom_words + d * nt, d * nt * 8);
+        }
+    }
+    return SMC_OK;
+}

@@ -209,6 +209,7 @@ extern "C" int smc_comm_plan_exchange(const int32_t* a, int64_t M, int rank, int
 // every rank) is the ancestor of global slot m; rank r holds the slots [r M/world, (r+1) M/world).  Value copies.
 extern "C" int smc_comm_exchange_slots(smc_comm c, smc_handle h, const int32_t* a, int64_t M) {
     if (!c || !h || !a || M <= 0 || M % c->world) return fail(SMC_EINVAL, "smc_comm_exchange_slots: bad argument");
+    if (history_armed(h)) return history_refuse("smc_comm_exchange_slots");   // before anything is packed or sent
     HIPCHK(hipSetDevice(c->device));
     const int W = c->world;
     const int64_t per = M / W;

@@ -1,7 +1,7 @@
 // smc_host.h -- what the host-side translation units of libsmchip.so share: the error string behind smc_last_error(), HIPCHK,
 // the filter handle, and the few helpers that cross files.  Internal: not installed, not part of the ABI (include/smc_hip.h).
 // The entry points on a handle: smc_capi.hip (core), smc_capi_series.hip, smc_capi_summ.hip, smc_capi_pmmh.hip,
-// smc_capi_slots.hip; without one: smc_util.hip.
+// smc_capi_slots.hip, smc_capi_smooth.hip; without one: smc_util.hip.
 #pragma once
 #include "../../include/smc_hip.h"
 #include "smc_launch.h"
@@ -113,6 +113,15 @@ struct smc_filter_s {
         double* h_out = nullptr;               // pinned [2][WIN_MAX][ntheta]: (logmu, ess) of the steps of a window
         int k = 0;                             // steps of the pending window, 0 = none
     } win;
+    struct {   // the record of a step-by-step run and the smoother over it (smc_capi_smooth.hip); a fresh handle is disarmed
+        bool armed = false;
+        int64_t cap = 0, len = 0;              // steps the slabs hold / steps recorded so far
+        double *d_x = nullptr, *d_w = nullptr; // [cap][d][ntheta][n] | [cap][ntheta][n]
+        double* d_ws = nullptr;                // the smoother's results: ws [len][ntheta][n] | mean, var [len][2][d][ntheta]
+        double* d_tmp = nullptr;               // its scratch: chunk maxima and chunk partials [2][nchunk][ntheta][n] | logD [ntheta][n] |
+        int64_t ws_cap = 0;                    //   partials of the moments [len][ntheta][nchunk] | rows [ntheta] | dead [ntheta]
+        size_t tmp_bytes = 0;
+    } hist;
     struct {   // PMMH rejuvenation (smc_capi_pmmh.hip): this handle holds the proposal filters
         smc::PmmhSpec spec{};
         bool cfg = false;
@@ -159,6 +168,14 @@ bool summaries_fit_lds(const smc_filter_s* h);
 int ensure_summaries(smc_handle h, int64_t T);
 void view_summaries(smc_handle h);
 int enqueue_step_summaries(smc_handle h, int64_t row);
+// smc_capi_slots.hip: the dense weights of the current state into w [ntheta][n], on the handle's stream (k_dense_weights)
+hipError_t enqueue_dense_weights(smc_filter_s* h, double* w);
+// smc_capi_smooth.hip: appends the state smc_init / smc_step leave to the record of an armed handle (no host synchronisation);
+// the calls that would change the state of an armed handle without a recordable step refuse with history_refuse()
+int history_append(smc_handle h);
+void history_free(smc_filter_s* h);
+inline bool history_armed(const smc_filter_s* h) { return h->hist.armed; }
+int history_refuse(const char* who);
 // smc_capi_slots.hip: k_copy_slots on stream s (slot th of dst <- slot th of src where mask[th])
 hipError_t copy_slots(const smc::FilterView& dst, int dcur, const smc::FilterView& src, int scur, int d, const unsigned char* mask, hipStream_t s);
 

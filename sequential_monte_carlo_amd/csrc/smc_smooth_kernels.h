@@ -1,0 +1,210 @@
+// smc_smooth_kernels.h -- the backward pass of the FFBS smoother (smc_spec.h "the smoother"): all-pairs transition
+// densities between the recorded clouds of two consecutive steps, wave64, f64, no MFMA.  Included by smc_capi_smooth.hip only.
+//
+// One thread owns one particle of the OWNER side; a workgroup owns blockDim.x consecutive owners of one filter and ONE chunk of
+// SMOOTH_CH particles of the STAGED side, which it puts into LDS with everything that depends on the staged particle alone
+// hoisted.  Every lane reads the same LDS address in the inner loop (a broadcast).  grid = (owner tiles, ntheta, chunks): a chunk
+// is the unit of the summation order, so the bits depend neither on the tile length nor on the batch.
+//   PASS 0  owners = targets j (step t+1), staged = sources l (step t):  chunk maximum of a_lj            -> pmax [chunk][th][j]
+//   k_smooth_rowmax (filters of more than SMOOTH_MAX_DIRECT chunks): M_j = max over the chunk maxima, once per target      -> rmax [th][j]
+//   PASS 1  the same roles: M_j (from rmax, or the maximum over the few chunk maxima), chunk partial of sum_l sp_exp(a_lj - M_j)
+//                                                                                                            -> part [chunk][th][j]
+//   k_smooth_logd: logD_j = M_j + sp_log(sum of the partials in ascending order)
+//   PASS 2  owners = sources i (step t), staged = targets j (step t+1): chunk partial of sum_j ws_j sp_exp(logf_ij - logD_j)
+//   k_smooth_finish: ws_t^i = w_t^i > 0 ? w_t^i * (sum of the partials in ascending order) : 0;  NaN for a collapsed filter
+// No floating-point atomics, no spinning: the partials go through scratch owned by the handle, the kernels follow each other on
+// the handle's stream.
+#pragma once
+#include "smc_spec.h"
+
+namespace smc {
+
+struct SmoothArgs {
+    int64_t n;             // particles per filter
+    int ntheta, nchunk;    // filters, chunks of SMOOTH_CH particles
+    const double* x_own;   // [d][ntheta][n] states of the owner side
+    const double* x_st;    // [d][ntheta][n] states of the staged side
+    const double* w_st;    // [ntheta][n] PASS 0, 1: filter weights of the sources; PASS 2: smoothed weights of the targets
+    const double* logD;    // [ntheta][n] PASS 2
+    double* pmax;          // [nchunk][ntheta][n] chunk maxima (PASS 0 writes them)
+    const double* rmax;    // [nmax][ntheta][n] what PASS 1 takes M_j from: pmax with nmax = nchunk, or the row maxima with nmax = 1
+    int nmax;
+    double* part;          // [nchunk][ntheta][n]
+    const SmoothRow* rows; // [ntheta]
+};
+
+template <int MODEL, int PASS>
+__global__ void k_smooth_pairs(SmoothArgs a) {
+    constexpr int D = model_dim<MODEL>::value;
+    constexpr int NV = D + 2;
+    __shared__ double sm[SMOOTH_CH][NV];   // PASS 0, 1: (m[D], s, g);  PASS 2: (x[D], ws, logD)
+    const int th = blockIdx.y, ch = blockIdx.z;
+    const int64_t n = a.n;
+    const size_t row = (size_t)th * n, plane = (size_t)a.ntheta * n;
+    const SmoothRow k = a.rows[th];
+    for (int q = threadIdx.x; q < SMOOTH_CH; q += blockDim.x) {
+        const int64_t l = (int64_t)ch * SMOOTH_CH + q;
+        double v[NV];
+        const double wl = l < n ? a.w_st[row + l] : 0.0;
+        if (wl > 0.0) {   // (false for a NaN weight as well)
+            double xs[D];
+            for (int r = 0; r < D; ++r) xs[r] = a.x_st[(size_t)r * plane + row + l];
+            if constexpr (PASS < 2) {
+                double c;
+                logf_source<MODEL>(k, xs, v, v[D], c);
+                v[D + 1] = sp_log(wl) + c;
+            } else {
+                for (int r = 0; r < D; ++r) v[r] = xs[r];
+                v[D] = wl;
+                v[D + 1] = a.logD[row + l];
+            }
+        } else {          // left out: every term it enters is exactly +0.0, and it never is the maximum
+            for (int r = 0; r < D + 1; ++r) v[r] = 0.0;
+            v[D + 1] = PASS < 2 ? -inf() : inf();
+        }
+        for (int r = 0; r < NV; ++r) sm[q][r] = v[r];
+    }
+    __syncthreads();
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    double xo[D];
+    for (int r = 0; r < D; ++r) xo[r] = a.x_own[(size_t)r * plane + row + j];
+    const size_t o = ((size_t)ch * a.ntheta + th) * n + j;
+    if constexpr (PASS == 0) {
+        double M = -inf();
+#pragma unroll 8
+        for (int q = 0; q < SMOOTH_CH; ++q) {
+            const double al = logf_pair<MODEL>(k, sm[q], sm[q][D], sm[q][D + 1], xo);
+            M = al > M ? al : M;
+        }
+        a.pmax[o] = M;
+    } else if constexpr (PASS == 1) {
+        double M = -inf();
+        for (int c = 0; c < a.nmax; ++c) {
+            const double pm = a.rmax[((size_t)c * a.ntheta + th) * n + j];
+            M = pm > M ? pm : M;
+        }
+        double S = 0.0;
+#pragma unroll 4
+        for (int q = 0; q < SMOOTH_CH; ++q) {
+            const double al = logf_pair<MODEL>(k, sm[q], sm[q][D], sm[q][D + 1], xo);
+            S += sp_exp(al - M);
+        }
+        a.part[o] = S;
+    } else {
+        double m[D], s, c;
+        logf_source<MODEL>(k, xo, m, s, c);
+        double S = 0.0;
+#pragma unroll 4
+        for (int q = 0; q < SMOOTH_CH; ++q) {
+            const double lf = logf_pair<MODEL>(k, m, s, c, sm[q]);
+            S += sm[q][D] * sp_exp(lf - sm[q][D + 1]);
+        }
+        a.part[o] = S;
+    }
+}
+
+// Every PASS 1 workgroup of a target needs M_j; with many chunks each of them would read all the chunk maxima again (n_x nchunk^2
+// doubles per step and filter: 268 MB at 8192 particles).  Beyond this many chunks the maximum is taken once per target instead
+// (one more small launch per step; a maximum is exact in any order, so the bits do not depend on the choice).
+constexpr int SMOOTH_MAX_DIRECT = 8;
+__global__ void k_smooth_rowmax(int64_t n, int ntheta, int nchunk, const double* pmax, double* rmax) {
+    const int th = blockIdx.y;
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    double M = -inf();
+    for (int c = 0; c < nchunk; ++c) {
+        const double pm = pmax[((size_t)c * ntheta + th) * n + j];
+        M = pm > M ? pm : M;
+    }
+    rmax[(size_t)th * n + j] = M;
+}
+
+// logD_j = M_j + sp_log(S_j): the maximum (as PASS 1 took it) and the chunk partials of target j in ascending chunk order
+__global__ void k_smooth_logd(int64_t n, int ntheta, int nchunk, const double* rmax, int nmax, const double* part, double* logD) {
+    const int th = blockIdx.y;
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    double M = -inf(), S = 0.0;
+    for (int c = 0; c < nmax; ++c) {
+        const double pm = rmax[((size_t)c * ntheta + th) * n + j];
+        M = pm > M ? pm : M;
+    }
+    for (int c = 0; c < nchunk; ++c) S += part[((size_t)c * ntheta + th) * n + j];
+    logD[(size_t)th * n + j] = M + sp_log(S);
+}
+
+// ws_t^i from the chunk partials of source i; part == nullptr: the last recorded step, ws = w.  dead[th] != 0: NaN
+__global__ void k_smooth_finish(int64_t n, int ntheta, int nchunk, const double* part, const double* w, const int* dead, double* ws) {
+    const int th = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double wi = w[(size_t)th * n + i];
+    double r = wi;
+    if (part) {
+        double S = 0.0;
+        for (int c = 0; c < nchunk; ++c) S += part[((size_t)c * ntheta + th) * n + i];
+        r = wi > 0.0 ? wi * S : 0.0;
+    }
+    ws[(size_t)th * n + i] = dead[th] ? bits2d(0x7ff8000000000000ULL) : r;
+}
+
+// dead[th] = 1 when filter th has a recorded step at which every weight is 0 (a collapsed filter).  grid (T, ntheta); an
+// integer flag, set by whoever finds such a step (dead is cleared before the launch)
+__global__ void k_smooth_dead(int64_t n, int ntheta, const double* w /*[T][ntheta][n]*/, int* dead) {
+    __shared__ int any;
+    const int t = blockIdx.x, th = blockIdx.y;
+    if (threadIdx.x == 0) any = 0;
+    __syncthreads();
+    const double* wt = w + ((size_t)t * ntheta + th) * n;
+    int mine = 0;
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) mine |= wt[i] > 0.0 ? 1 : 0;
+    if (mine) any = 1;   // (every writer stores the same value)
+    __syncthreads();
+    if (threadIdx.x == 0 && !any) atomicOr(dead + th, 1);
+}
+
+// smoothed mean and variance of every coordinate at every step: smc_get_moments' definitions on (x_t, ws_t) in the smoother's
+// order of summation (smooth_sum: chunks of SMOOTH_CH, plain adds, partials in ascending order).  grid (T, ntheta), one
+// workgroup per cloud; tmp [T][ntheta][nchunk] holds the chunk partials.  out [T][2][d][ntheta]
+__global__ void k_smooth_moments(int64_t n, int ntheta, int nchunk, int d, const double* x /*[T][d][ntheta][n]*/,
+                                 const double* ws /*[T][ntheta][n]*/, const int* dead, double* tmp, double* out) {
+    __shared__ double s_mean;
+    __shared__ int s_any;
+    const int t = blockIdx.x, th = blockIdx.y;
+    const double* wt = ws + ((size_t)t * ntheta + th) * n;
+    double* part = tmp + ((size_t)t * ntheta + th) * nchunk;
+    const double nan = bits2d(0x7ff8000000000000ULL);
+    if (threadIdx.x == 0) s_any = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) mine |= wt[i] > 0.0 ? 1 : 0;
+    if (mine) s_any = 1;
+    __syncthreads();
+    const bool none = dead[th] || !s_any;
+    for (int r = 0; r < d; ++r) {
+        const double* xr = x + (((size_t)t * d + r) * ntheta + th) * n;
+        for (int pass = 0; pass < 2; ++pass) {
+            const double mean = pass ? s_mean : 0.0;
+            for (int c = threadIdx.x; c < nchunk; c += blockDim.x) {
+                const int64_t i0 = (int64_t)c * SMOOTH_CH, i1 = i0 + SMOOTH_CH < n ? i0 + SMOOTH_CH : n;
+                double s = 0.0;
+                for (int64_t i = i0; i < i1; ++i) {
+                    const double e = xr[i] - mean;
+                    s += wt[i] > 0.0 ? (pass ? wt[i] * (e * e) : wt[i] * xr[i]) : 0.0;
+                }
+                part[c] = s;
+            }
+            __syncthreads();   // (the partials a workgroup wrote to global memory are visible to its own threads after the barrier)
+            if (threadIdx.x == 0) {
+                double tot = 0.0;
+                for (int c = 0; c < nchunk; ++c) tot += part[c];
+                if (!pass) s_mean = tot;
+                out[(((size_t)t * 2 + pass) * d + r) * ntheta + th] = none ? nan : tot;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+}  // namespace smc

@@ -927,4 +927,103 @@ SMC_HD void combine_outputs(double K, uint64_t Dtot, uint64_t Rtot, int SH, int6
     ess = Rtot ? Dd * Dd / Rd : 0.0;
 }
 
+// ---- the smoother: forward filtering, backward smoothing ------------------------------------------------------
+// Given the clouds (x_t, w_t), t = 1..T, of a step-by-step run (w the dense weights of smc_get_state) the smoothed weights are
+//     ws_T = w_T,   and for t = T-1 .. 1, with "source" l, i a particle of step t and "target" j a particle of step t+1:
+//     a_lj   = fma chain of logf(x_{t+1}^j | x_t^l) started from g_l = sp_log(w_t^l) + c_l        (log w + logf, one constant)
+//     M_j    = max_l a_lj,   S_j = sum_l sp_exp(a_lj - M_j),   logD_j = M_j + sp_log(S_j)
+//     ws_t^i = w_t^i > 0 ? w_t^i * sum_j ws_{t+1}^j * sp_exp(logf(x_{t+1}^j | x_t^i) - logD_j) : 0
+// Sources with w = 0 and targets with ws = 0 (NaN compares false: they count as 0) are left out of every sum and maximum,
+// whatever their states; there is no renormalisation.  Order: the summed index is cut into chunks of SMOOTH_CH consecutive
+// particles; a chunk is summed in ascending index order with plain adds starting from +0.0, the chunk partials are summed in
+// ascending order starting from +0.0; the maximum is exact in any order.  (The kernels give a left-out particle the log-weight
+// -inf resp. the weight 0 and logD = +inf with a zero state: its terms are exactly +0.0, which changes no partial sum.)
+// logf is split into what depends on the source alone (centres m, the scale s, the constant c) and a chain of fma over the pair:
+//   LG1D    m = A xp,  s = nh0 = -0.5 / Q,  c = c0 = -HALF_LOG2PI - sp_log(sqrt(Q))
+//   SV1D    m = fma(rho, xp - mu, mu),  s = nh0 = -0.5 / (sigma sigma),  c = c0 = -HALF_LOG2PI - sp_log(sigma)
+//   UCSV3D  m = xp (three rows),  s = -0.5 sp_exp(-xp[1]),  c = fma(-0.5, xp[1], c0),  nh1 = -0.5 / (g_eps g_eps),
+//           nh2 = -0.5 / (g_eta g_eta),  c0 = ((-HALF_LOG2PI - sp_log(g_eps)) + (-HALF_LOG2PI - sp_log(g_eta))) - HALF_LOG2PI
+//           (the reference's conventions: the trend moves with the PREVIOUS lse, sd exp(lse / 2); the gammas are standard deviations)
+//   pair    d_r = x[r] - m[r];   one row: fma(d0 d0, s, g);   UCSV3D: fma(d0 d0, s, fma(d1 d1, nh1, fma(d2 d2, nh2, g)))
+// with g = c for logf itself and g = sp_log(w) + c for a_lj.  MODEL_UCSV_RB has no transition density of its rows (m and P are
+// functions of the whole path): no smoother.
+#ifndef SMC_SMOOTH_CH
+#define SMC_SMOOTH_CH 128
+#endif
+constexpr int SMOOTH_CH = SMC_SMOOTH_CH;   // 64, 128 or 256 (profiles/smoother_cost.log); part of the numerical contract
+static_assert(SMOOTH_CH == 64 || SMOOTH_CH == 128 || SMOOTH_CH == 256, "SMOOTH_CH: 64, 128 or 256");
+struct SmoothRow {   // the constants of a parameter row, derived once per filter on the host
+    double a, mu, nh0, nh1, nh2, c0;
+};
+// false: the family has no transition density, or the row's transition scale is not a positive finite number (host only)
+inline bool smooth_row(int model, const double* raw, SmoothRow& k) {
+    k = SmoothRow{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    auto scale_ok = [](double s) { return s == s && s > 0.0 && s != inf(); };
+    if (model == MODEL_LG1D) {
+        if (!scale_ok(raw[2])) return false;
+        k.a = raw[0];
+        k.nh0 = -0.5 / raw[2];
+        k.c0 = -HALF_LOG2PI - sp_log(sqrt(raw[2]));
+        return true;
+    }
+    if (model == MODEL_SV1D) {
+        if (!scale_ok(raw[2])) return false;
+        k.a = raw[1]; k.mu = raw[0];
+        k.nh0 = -0.5 / (raw[2] * raw[2]);
+        k.c0 = -HALF_LOG2PI - sp_log(raw[2]);
+        return true;
+    }
+    if (model == MODEL_UCSV3D) {
+        if (!scale_ok(raw[0]) || !scale_ok(raw[1])) return false;
+        k.nh1 = -0.5 / (raw[0] * raw[0]);
+        k.nh2 = -0.5 / (raw[1] * raw[1]);
+        k.c0 = ((-HALF_LOG2PI - sp_log(raw[0])) + (-HALF_LOG2PI - sp_log(raw[1]))) - HALF_LOG2PI;
+        return true;
+    }
+    return false;
+}
+// what logf(. | xp) needs of the source xp alone
+template <int MODEL>
+SMC_HD void logf_source(const SmoothRow& k, const double* xp, double* m /*[d]*/, double& s, double& c) {
+    if constexpr (MODEL == MODEL_LG1D) {
+        m[0] = k.a * xp[0]; s = k.nh0; c = k.c0;
+    } else if constexpr (MODEL == MODEL_SV1D) {
+        m[0] = fma(k.a, xp[0] - k.mu, k.mu); s = k.nh0; c = k.c0;
+    } else {
+        m[0] = xp[0]; m[1] = xp[1]; m[2] = xp[2];
+        s = -0.5 * sp_exp(-xp[1]);
+        c = fma(-0.5, xp[1], k.c0);
+    }
+}
+// g + (logf(x | xp) - c): the chain over the pair
+template <int MODEL>
+SMC_HD double logf_pair(const SmoothRow& k, const double* m, double s, double g, const double* x) {
+    const double d0 = x[0] - m[0];
+    if constexpr (MODEL == MODEL_UCSV3D) {
+        const double d1 = x[1] - m[1], d2 = x[2] - m[2];
+        return fma(d0 * d0, s, fma(d1 * d1, k.nh1, fma(d2 * d2, k.nh2, g)));
+    } else {
+        return fma(d0 * d0, s, g);
+    }
+}
+// logpdf(transition(model, xp), x)          ssm.jl:87-94, 233-242
+template <int MODEL>
+SMC_HD double model_logf(const SmoothRow& k, const double* xp, const double* x) {
+    double m[3], s, c;
+    logf_source<MODEL>(k, xp, m, s, c);
+    return logf_pair<MODEL>(k, m, s, c, x);
+}
+// sum of n terms term(i), i = 0..n-1, in the smoother's order (chunks of SMOOTH_CH, plain adds, partials in ascending order)
+template <class F>
+inline double smooth_sum(int64_t n, F term) {
+    double tot = 0.0;
+    for (int64_t c0 = 0; c0 < n; c0 += SMOOTH_CH) {
+        double s = 0.0;
+        const int64_t c1 = c0 + SMOOTH_CH < n ? c0 + SMOOTH_CH : n;
+        for (int64_t i = c0; i < c1; ++i) s += term(i);
+        tot += s;
+    }
+    return tot;
+}
+
 }  // namespace smc

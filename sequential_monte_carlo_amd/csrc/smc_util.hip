@@ -457,3 +457,100 @@ extern "C" int smc_device_math(int which, const double* a, const double* b, int6
     HIPCHK(hipStreamSynchronize(st));
     return SMC_OK;
 }
+
+// ---- the smoother on the host (smc_spec.h "the smoother"): the twin the device is compared with, statement by statement ------
+extern "C" int smc_host_transition_logpdf(int model_id, const double* raw, const double* xp, const double* x, double* out) {
+    if (!raw || !xp || !x || !out) return fail(SMC_EINVAL, "smc_host_transition_logpdf: NULL argument");
+    SmoothRow k;
+    if (!smooth_row(model_id, raw, k))
+        return fail(SMC_EINVAL, "smc_host_transition_logpdf: no transition density for this family, or a transition scale that is not positive and finite");
+    if (model_id == MODEL_LG1D) *out = model_logf<MODEL_LG1D>(k, xp, x);
+    else if (model_id == MODEL_SV1D) *out = model_logf<MODEL_SV1D>(k, xp, x);
+    else *out = model_logf<MODEL_UCSV3D>(k, xp, x);
+    return SMC_OK;
+}
+
+// smoothed moments of one step: smc_get_moments' definitions on (x, ws) in the smoother's order of summation
+static void host_smooth_moments(int d, int64_t n, const double* x /*[d][n]*/, const double* ws, bool dead, double* mean /*[d]*/, double* var) {
+    const double nan = bits2d(0x7ff8000000000000ULL);
+    bool any = false;
+    for (int64_t i = 0; i < n; ++i) any = any || ws[i] > 0.0;
+    for (int r = 0; r < d; ++r) {
+        const double* xr = x + (size_t)r * n;
+        const double m = smooth_sum(n, [&](int64_t i) { return ws[i] > 0.0 ? ws[i] * xr[i] : 0.0; });
+        const double v = smooth_sum(n, [&](int64_t i) {
+            const double e = xr[i] - m;
+            return ws[i] > 0.0 ? ws[i] * (e * e) : 0.0;
+        });
+        mean[r] = (dead || !any) ? nan : m;
+        var[r] = (dead || !any) ? nan : v;
+    }
+}
+
+template <int MODEL>
+static void host_smooth_t(const SmoothRow& k, int64_t T, int64_t n, const double* x, const double* w, double* ws) {
+    constexpr int D = model_dim<MODEL>::value;
+    const size_t sx = (size_t)D * n;
+    for (int64_t i = 0; i < n; ++i) ws[(size_t)(T - 1) * n + i] = w[(size_t)(T - 1) * n + i];
+    std::vector<double> m((size_t)D * n), s((size_t)n), c((size_t)n), g((size_t)n), logD((size_t)n);
+    for (int64_t t = T - 2; t >= 0; --t) {
+        const double *xs = x + (size_t)t * sx, *xt = x + (size_t)(t + 1) * sx;   // sources (step t), targets (step t + 1)
+        const double *wt = w + (size_t)t * n, *wn = ws + (size_t)(t + 1) * n;
+        double* out = ws + (size_t)t * n;
+        for (int64_t l = 0; l < n; ++l) {
+            double xp[D], ml[D];
+            for (int r = 0; r < D; ++r) xp[r] = xs[(size_t)r * n + l];
+            if (!(wt[l] > 0.0)) { g[l] = -inf(); continue; }
+            logf_source<MODEL>(k, xp, ml, s[l], c[l]);
+            for (int r = 0; r < D; ++r) m[(size_t)r * n + l] = ml[r];
+            g[l] = sp_log(wt[l]) + c[l];
+        }
+        auto pair = [&](int64_t l, int64_t j, double gl) {
+            double ml[D], xj[D];
+            for (int r = 0; r < D; ++r) { ml[r] = m[(size_t)r * n + l]; xj[r] = xt[(size_t)r * n + j]; }
+            return logf_pair<MODEL>(k, ml, s[l], gl, xj);
+        };
+        for (int64_t j = 0; j < n; ++j) {
+            if (!(wn[j] > 0.0)) continue;
+            double M = -inf();
+            for (int64_t l = 0; l < n; ++l) {
+                if (!(wt[l] > 0.0)) continue;
+                const double a = pair(l, j, g[l]);
+                M = a > M ? a : M;
+            }
+            const double S = smooth_sum(n, [&](int64_t l) { return wt[l] > 0.0 ? sp_exp(pair(l, j, g[l]) - M) : 0.0; });
+            logD[j] = M + sp_log(S);
+        }
+        for (int64_t i = 0; i < n; ++i) {
+            if (!(wt[i] > 0.0)) { out[i] = 0.0; continue; }
+            const double S = smooth_sum(n, [&](int64_t j) { return wn[j] > 0.0 ? wn[j] * sp_exp(pair(i, j, c[i]) - logD[j]) : 0.0; });
+            out[i] = wt[i] * S;
+        }
+    }
+}
+
+extern "C" int smc_host_smooth(int model_id, const double* raw, int64_t T, int64_t n, const double* x, const double* w, double* ws,
+                               double* mean, double* var) {
+    if (!raw || !x || !w || !ws) return fail(SMC_EINVAL, "smc_host_smooth: NULL argument");
+    if (T < 1 || n < 1) return fail(SMC_EINVAL, "smc_host_smooth: T and n must be positive");
+    SmoothRow k;
+    if (!smooth_row(model_id, raw, k))
+        return fail(SMC_EINVAL, "smc_host_smooth: no transition density for this family, or a transition scale that is not positive and finite");
+    const int d = model_dim_rt(model_id);
+    if (model_id == MODEL_LG1D) host_smooth_t<MODEL_LG1D>(k, T, n, x, w, ws);
+    else if (model_id == MODEL_SV1D) host_smooth_t<MODEL_SV1D>(k, T, n, x, w, ws);
+    else host_smooth_t<MODEL_UCSV3D>(k, T, n, x, w, ws);
+    // a filter that collapsed at a recorded step (all of its weights 0 there): NaN everywhere
+    bool dead = false;
+    for (int64_t t = 0; t < T && !dead; ++t) {
+        bool any = false;
+        for (int64_t i = 0; i < n; ++i) any = any || w[(size_t)t * n + i] > 0.0;
+        dead = !any;
+    }
+    if (dead)
+        for (size_t q = 0; q < (size_t)T * n; ++q) ws[q] = bits2d(0x7ff8000000000000ULL);
+    if (mean && var)
+        for (int64_t t = 0; t < T; ++t)
+            host_smooth_moments(d, n, x + (size_t)t * d * n, ws + (size_t)t * n, dead, mean + (size_t)t * d, var + (size_t)t * d);
+    return SMC_OK;
+}

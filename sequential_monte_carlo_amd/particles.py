@@ -5,6 +5,7 @@
     bootstrap_filter(N, y1, model)       -> (x, w, logmu)       particles.jl:87-105
     bootstrap_filter_(x, w, y, model)    -> (logmu, w, ess)     particles.jl:107-129   ("bootstrap_filter!")
     log_likelihood(N, y, model)          -> (x, w, logZ)        particles.jl:132-147
+    smoother(N, y, model)                -> (x, w, logZ, s)     (no counterpart: the FFBS particle smoother)
     particle_filter(N, y1, model, proposal)       -> (x, w, logmu)     particles.jl:28-52
     particle_filter_(x, w, y, model, proposal)    -> (logmu, w, ess)   particles.jl:54-84    ("particle_filter!")
 
@@ -92,9 +93,13 @@ def trend_moments(mean, var):
 class _Filters:
     """Device state shared by the Particles / Weights views of one bootstrap_filter call."""
 
-    def __init__(self, N, models, seed, seg, device, streams, ancestors, resampler="multinomial", proposal=None):
-        mid, raw = params_matrix(models)
-        self.single = not isinstance(models, (list, tuple))
+    def __init__(self, N, models, seed, seg, device, streams, ancestors, resampler="multinomial", proposal=None, rows=None):
+        """rows=(model id, [n_theta][n_raw] parameter rows): a batch given as rows instead of `models` (then None)"""
+        if rows is not None:
+            mid, raw = int(rows[0]), np.ascontiguousarray(rows[1], dtype=np.float64)
+        else:
+            mid, raw = params_matrix(models)
+        self.single = rows is None and not isinstance(models, (list, tuple))
         if resampler not in ("multinomial", "systematic"):
             raise ValueError("resampler must be 'multinomial' (the reference's law) or 'systematic' (opt-in)")
         flags = (_lib.FLAG_ANCESTORS if ancestors else 0) | (_lib.FLAG_SYSTEMATIC if resampler == "systematic" else 0)
@@ -303,3 +308,48 @@ def log_likelihood(N, y, model, seed=None, seg=0, device=0, streams=None, ancest
         return Particles(f), Weights(f), f.out(logZ), lm, es
     logZ = f.h.log_likelihood(y)
     return Particles(f), Weights(f), f.out(logZ)
+
+
+def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="multinomial", proposal=None, weights=False, rows=None):
+    """x, w, logZ, s = smoother(N, y, model): the particle filter of log_likelihood run step by step with its clouds recorded on
+    the device, then the FFBS backward pass over them (forward filtering, backward smoothing).  x, w, logZ are the
+    filter's, as log_likelihood returns them; s describes p(x_t | y_1:T):
+        s["mean"][t], s["var"][t]   smoothed mean and variance of the state, shaped like the per-step summaries of log_likelihood
+                                    ([T], or [T][d]; with a list of models a batch axis follows T)
+        s["logmu"], s["ess"]        the filter's per-step log-likelihood increments and effective sample sizes, [T] or [T][n_theta]
+        s["weights"], s["x"]        (weights=True) the smoothed weights [T][N] and the recorded clouds [T][N] or [T][N][d] they
+                                    belong to (batch axis after T)
+    The backward pass costs 2 N^2 (T - 1) transition densities per filter.  Any proposal, either resampler; MarginalUCSV has no
+    smoother (its state rows have no transition density): smooth a UCSV filter.
+    rows=(model id, parameter rows [n_theta][n_raw]) with model=None: a batch given as rows (what the samplers hold)."""
+    if seed is None:
+        seed = next(_seed_counter)
+    f = _Filters(int(N), model, seed, seg, device, streams, False, resampler, proposal, rows=rows)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    T, h = y.size, f.h
+    if T < 1:
+        raise ValueError("smoother needs at least one observation")
+    h.history_begin(T)
+    try:
+        lm, es = np.zeros((T, h.n_theta)), np.zeros((T, h.n_theta))
+        lm[0] = h.init(float(y[0]))
+        es[0] = h.logZ()[1]
+        for t in range(1, T):
+            lm[t], es[t] = h.step(float(y[t]))
+        logZ = h.logZ()[0]
+        ws, mean, var = h.smooth(weights=weights, moments=True)
+        s = {}
+        mean, var = np.moveaxis(mean, 1, -1), np.moveaxis(var, 1, -1)      # [T][n_theta][d]
+        if mean.shape[-1] == 1:
+            mean, var = mean[..., 0], var[..., 0]
+        s["mean"], s["var"] = (mean[:, 0], var[:, 0]) if f.single else (mean, var)
+        s["logmu"], s["ess"] = (lm[:, 0], es[:, 0]) if f.single else (lm, es)
+        if weights:
+            xs = np.array([h.history_get(t)[0] for t in range(T)])        # [T][d][n_theta][N]
+            xs = np.moveaxis(xs, 1, -1)                                    # [T][n_theta][N][d]
+            if xs.shape[-1] == 1:
+                xs = xs[..., 0]
+            s["weights"], s["x"] = (ws[:, 0], xs[:, 0]) if f.single else (ws, xs)
+    finally:
+        h.history_end()
+    return Particles(f), Weights(f), f.out(logZ), s

@@ -565,6 +565,43 @@ def smc2_step(smc, y, t, verbose=True, out=sys.stdout):
     return smc
 
 
+def smoothed_state(smc, y, N=None, max_bytes=2 ** 31, seed=None):
+    """(mean [T], var [T]) of p(x_t | y_1:T, theta) integrated over the sampler's current parameter cloud ([T][d] for a state of d
+    coordinates): fresh batched smoothers (particles.smoother: a particle filter of N particles per parameter particle, default
+    the sampler's N, and the FFBS backward pass) at the current theta, in blocks of parameter particles whose recorded history
+    stays under max_bytes, then mean = sum_m omega_m mean_m and var = sum_m omega_m var_m (within) + sum_m omega_m (mean_m - mean)^2
+    (between), as trend_moments combines a mixture.  Filters with omega = 0 are left out, as in filtered_summaries.  Filter m uses
+    Philox stream m, so the result does not depend on the blocks; seed: the Philox seed of the filters (default: derived from the
+    sampler's seed; the sampler's own state is not touched).  All parameter particles are smoothed on this process's GPU.
+    IBIS is out of scope: its exact smoother is RTS, a different feature."""
+    if isinstance(smc, IBIS):
+        raise TypeError("smoothed_state: IBIS is out of scope: its exact smoother is RTS, a different feature")
+    from .particles import smoother
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    N = smc.N if N is None else int(N)
+    om = np.asarray(smc.omega, dtype=np.float64)
+    mid, raw = _rows(smc._models(smc.theta))
+    d = _lib.lib().smc_model_dim(int(mid))
+    per_theta = y.size * N * (d + 2) * 8                  # recorded x and w, and the smoothed weights
+    blk = max(1, min(smc.M, int(max_bytes) // max(per_theta, 1)))
+    seed = ((smc.seed << 20) | 0xF5B00) if seed is None else int(seed)
+    means, vars_ = [], []
+    for m0 in range(0, smc.M, blk):
+        m1 = min(smc.M, m0 + blk)
+        _, _, _, s = smoother(N, y, None, rows=(int(mid), raw[m0:m1]), seed=seed, device=getattr(smc.backend, "device", 0),
+                              streams=np.arange(m0, m1, dtype=np.uint32))
+        means.append(s["mean"])
+        vars_.append(s["var"])
+    mean_m, var_m = np.concatenate(means, axis=1), np.concatenate(vars_, axis=1)     # [T][M] or [T][M][d]
+    keep = om > 0
+    wk = om[keep].reshape((1, -1) + (1,) * (mean_m.ndim - 2))
+    mean = np.add.reduce(wk * mean_m[:, keep], axis=1)
+    within = np.add.reduce(wk * var_m[:, keep], axis=1)
+    dev = mean_m[:, keep] - mean[:, None]
+    between = np.add.reduce(wk * (dev * dev), axis=1)
+    return mean, within + between
+
+
 def _integrate(w, rows):
     """[M][np + 1] per-filter (quantiles | variance) rows of every rank -> their omega-weighted means (quantiles [np], variance);
     the products summed over the parameter particles in index order (one definition for every caller: no BLAS in between).
