@@ -94,8 +94,7 @@ int smc_step_by_value(smc_handle h, int* by_value);
  * is dropped).  smc_set_params after SMC_PROP_OPTIMAL derives the proposal of the new rows; AFFINE rows stay as given.  Like
  * parameters and stream ids a proposal stays with its slot under smc_permute, smc_copy_from, smc_pack_slots / smc_unpack_slots
  * and smc_comm_exchange_slots: only the state travels.  smc_pmmh_rejuvenate on a handle with SMC_PROP_OPTIMAL derives the
- * proposal of every theta' on the device; AFFINE rows stay as set.  The opt-in persistent step kernel is declined by a handle
- * with a proposal (one launch per step instead). */
+ * proposal of every theta' on the device; AFFINE rows stay as set. */
 #define SMC_PROP_NONE 0
 #define SMC_PROP_AFFINE 1
 #define SMC_PROP_OPTIMAL 2

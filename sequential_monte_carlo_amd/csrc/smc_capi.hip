@@ -270,7 +270,7 @@ extern "C" int smc_create(int model_id, int64_t n_theta, int64_t n_x, int seg, u
 #ifdef SMC_ABLATE
     v.abl = h_abl_tmp;
     if (getenv("SMC_DBG")) {
-        if (hipMalloc((void**)&v.dbg, (size_t)v.ntheta * v.nseg * 128) != hipSuccess) v.dbg = nullptr;   // second half: k_persist's accumulators
+        if (hipMalloc((void**)&v.dbg, (size_t)v.ntheta * v.nseg * 128) != hipSuccess) v.dbg = nullptr;   // second half: the start-up stamps
         else (void)hipMemset(v.dbg, 0, (size_t)v.ntheta * v.nseg * 128);
     }
 #endif
@@ -386,8 +386,7 @@ extern "C" int smc_destroy(smc_handle h) {
     if (h->summ.d_ms) (void)hipFree(h->summ.d_ms);
     if (!kept) (void)hipFree(h->d_y);
     (void)hipFree(h->d_tr_logmu); (void)hipFree(h->d_tr_ess); (void)hipFree(h->d_wdense); if (!kept) (void)hipFree(h->d_recs);
-    (void)hipFree(h->summ.d_q); (void)hipFree(h->summ.d_m); (void)hipFree(h->persist.d_flags);
-    if (h->persist.h_err) (void)hipHostFree(h->persist.h_err);
+    (void)hipFree(h->summ.d_q); (void)hipFree(h->summ.d_m);
     if (!kept) {
         if (h->ev0) (void)hipEventDestroy(h->ev0);
         if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -786,21 +785,6 @@ static void abl_report(smc_filter_s* h) {
     if (h->v.dbg) {   // phase profile of the LAST k_step launch: mean over workgroups, in microseconds
         const size_t nwg = (size_t)h->v.ntheta * h->v.nseg;
         std::vector<unsigned long long> st(nwg * 8);
-        (void)hipMemcpy(st.data(), h->v.dbg + nwg * 8, nwg * 64, hipMemcpyDeviceToHost);
-        if (st[7] == 0x5045525349535421ull) {   // the persistent step kernel ran: its own accumulators
-            double wait = 0, body = 0, pub = 0, mx_wait = 0;
-            for (size_t w = 0; w < nwg; ++w) {
-                const double steps = (double)st[w * 8];
-                wait += st[w * 8 + 1] * 0.01 / steps; body += st[w * 8 + 2] * 0.01 / steps; pub += st[w * 8 + 3] * 0.01 / steps;
-                mx_wait = std::max(mx_wait, st[w * 8 + 1] * 0.01 / steps);
-            }
-            fprintf(stderr, "[dbg] k_persist, mean over %zu workgroups, us per step: wait (poll + acquire + barrier) %.2f (max %.2f), step body %.2f, "
-                            "drain + barrier + publish %.2f\n", nwg, wait / nwg, mx_wait, body / nwg, pub / nwg);
-        }
-    }
-    if (h->v.dbg) {
-        const size_t nwg = (size_t)h->v.ntheta * h->v.nseg;
-        std::vector<unsigned long long> st(nwg * 8);
         (void)hipMemcpy(st.data(), h->v.dbg, nwg * 64, hipMemcpyDeviceToHost);
         unsigned long long t0 = ~0ull, t7 = 0;
         double ph[8] = {0};
@@ -812,7 +796,7 @@ static void abl_report(smc_filter_s* h) {
         {   // start-up latency of the LAST k_step launch: entry of a workgroup's first wave -> its first pick numbers drawn
             std::vector<unsigned long long> sd(nwg * 8);
             (void)hipMemcpy(sd.data(), h->v.dbg + nwg * 8, nwg * 64, hipMemcpyDeviceToHost);
-            if (sd[7] != 0x5045525349535421ull && sd[0] != 0 && sd[1] != 0) {   // (systematic launches draw no pick numbers: no stamp)
+            if (sd[0] != 0 && sd[1] != 0) {   // (systematic launches draw no pick numbers: no stamp)
                 double sum = 0, mn = 1e30, mx = 0;
                 std::vector<double> all(nwg);
                 for (size_t w = 0; w < nwg; ++w) {

@@ -29,13 +29,6 @@ struct SeriesScope {
     ~SeriesScope() { v.want_s2 = 1; v.y = nullptr; v.trace_logmu = nullptr; v.trace_ess = nullptr; v.sum_np = v.sum_mom = 0; v.sum_q = v.sum_m = nullptr; }
 };
 
-static hipError_t do_persist(smc_filter_s* h, uint32_t t0, uint32_t t1, PersistCtl pc) {
-    return by_model(h->model, [&](auto M) {
-        // (no persistent kernel for the marginal family: one launch per step)
-        if constexpr (decltype(M)::value == MODEL_UCSV_RB) return hipErrorCooperativeLaunchTooLarge;
-        else return launch_persist<decltype(M)::value>(h->v, h->geo, h->cur, t0, t1, pc, h->stream);
-    });
-}
 static hipError_t do_resident(smc_filter_s* h, int T) {
     if (h->v.prop_kind)
         return by_guided_model(h->model, [&](auto M) { return launch_resident_g<decltype(M)::value>(h->v, T, h->d_recs, h->stream); });
@@ -78,33 +71,7 @@ int enqueue_log_likelihood(smc_handle h, double y0, int64_t T, bool want_trace, 
         if (T == 1) h->v.want_s2 = 1;
         HIPCHK(do_init(h, y0));
         h->t = 1; h->inited = true; h->emitted = false;
-        int64_t t_first = 1;
-        // OPT-IN (SMC_PERSIST=1; measured slower than one launch per step): the steps 1 .. T-2 in persistent
-        // launches, one per window of prepared break points; the last step (which carries the sum of squares) by its own launch
-        if (h->persist.on < 0) { const char* e = getenv("SMC_PERSIST"); h->persist.on = (e && atoi(e) == 1) ? 1 : 0; }
-        // (a handle with a proposal declines it: k_persist exists for the bootstrap step only - one launch per step instead)
-        if (h->persist.on == 1 && !h->v.prop_kind && !want_trace && h->v.nseg > 1 && !h->v.skip && !h->v.anc && T > 3) {
-            const size_t nfl = (size_t)h->v.ntheta * h->v.nseg;
-            if (!h->persist.d_flags) {
-                HIPCHK(dalloc(&h->persist.d_flags, 2 * nfl));
-                HIPCHK(hipHostMalloc((void**)&h->persist.h_err, 16, hipHostMallocDefault));
-            }
-            *h->persist.h_err = 0;
-            while (t_first < T - 1) {
-                HIPCHK(ensure_breaks(h, (uint32_t)t_first, (uint32_t)T));
-                int64_t t_end = (int64_t)h->v.brk_t0 + h->brk_count;
-                t_end = t_end > T - 1 ? T - 1 : t_end;
-                HIPCHK(hipMemsetAsync(h->persist.d_flags, 0, 2 * nfl * 4, h->stream));
-                PersistCtl pc{{h->persist.d_flags, h->persist.d_flags + nfl}, h->persist.h_err};
-                const hipError_t pe = do_persist(h, (uint32_t)t_first, (uint32_t)t_end, pc);
-                if (pe == hipErrorCooperativeLaunchTooLarge) { h->persist.on = 0; break; }   // not available for this filter: step by step
-                HIPCHK(pe);
-                if ((t_end - t_first) & 1) h->cur ^= 1;
-                h->t += (uint32_t)(t_end - t_first);
-                t_first = t_end;
-            }
-        }
-        for (int64_t t = t_first; t < T; ++t) {
+        for (int64_t t = 1; t < T; ++t) {
             const int emit = h->v.want_s2 ? 1 : 2;   // 2: the records of step t-1 carry no sum of squares - (logmu, 0) from the totals alone
             if (t == T - 1) h->v.want_s2 = 1;
             HIPCHK(ensure_breaks(h, (uint32_t)t, (uint32_t)T));
@@ -151,13 +118,6 @@ extern "C" int smc_log_likelihood(smc_handle h, const double* y, int64_t T, doub
     }
     rc = finish_elapsed(h, logZ);
     if (rc) return rc;
-    if (h->persist.h_err && *h->persist.h_err) {
-        *h->persist.h_err = 0;
-        h->persist.on = 0;
-        h->inited = false;
-        return fail(SMC_EHIP, "smc_log_likelihood: the persistent step kernel gave up (a workgroup waited 100 ms for the previous step: "
-                              "not every workgroup resident?); the handle falls back to one launch per step - call again");
-    }
     if (logmu_trace) HIPCHK(hipMemcpy(logmu_trace, h->d_tr_logmu, (size_t)T * h->v.ntheta * 8, hipMemcpyDeviceToHost));
     if (ess_trace) HIPCHK(hipMemcpy(ess_trace, h->d_tr_ess, (size_t)T * h->v.ntheta * 8, hipMemcpyDeviceToHost));
     if (h->skip.on && want_trace) {   // filters the call left out have no steps: NaN in their trace columns

@@ -104,11 +104,6 @@ struct smc_filter_s {
         uint64_t* d_ms = nullptr;              // scratch of the summaries of multi-segment filters (smc_summ_kernels.h) + [ntheta][QMAX] results
         double* h_once = nullptr;              // pinned [QMAX + 2 d][ntheta]: quantiles / moments of the current state (k_summ_once)
     } summ;
-    struct {   // opt-in persistent step kernel (SMC_PERSIST=1)
-        unsigned* d_flags = nullptr;           // completion flags [2][ntheta * nseg]
-        int* h_err = nullptr;                  // its pinned "a spin expired" word
-        int on = -1;                           // -1 not decided yet, 0 off / unavailable, 1 on
-    } persist;
     struct {   // smc_step_window / smc_step_commit
         double* h_out = nullptr;               // pinned [2][WIN_MAX][ntheta]: (logmu, ess) of the steps of a window
         int k = 0;                             // steps of the pending window, 0 = none

@@ -51,23 +51,10 @@ __device__ __forceinline__ uint64_t lds_load_u64(lds_byte* p) { return *(lds_u64
 // the Infinity Cache anyway; written this way they leave the XCD's write-back L2 during the launch instead of at its end,
 // which shortens the gap between two dependent launches (measured on C2: 16.3 -> 15.5 us per step, same kernel span).
 typedef unsigned long long nt_v2u64 __attribute__((ext_vector_type(2)));
-// WT (the persistent step kernel, k_persist): write-through (sc1) stores - what another workgroup of the SAME launch is to read
-// must leave this XCD's write-back L2 (MI355X_MICROARCH.md, inter-workgroup visibility: sc1 payload, drained, then the flag)
-template <bool WT = false, class T>
+template <class T>
 __device__ __forceinline__ void store_out(T* p, const T& val) {
     static_assert(sizeof(T) == 16, "16-byte stores");
-    if (WT) {
-        const nt_v2u64 v2 = *reinterpret_cast<const nt_v2u64*>(&val);
-        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v2) : "memory");
-    } else {
-        __builtin_nontemporal_store(*reinterpret_cast<const nt_v2u64*>(&val), reinterpret_cast<nt_v2u64*>(p));
-    }
-}
-template <bool WT, class T>
-__device__ __forceinline__ void store_word(T* p, T val) {   // an 8-byte record word
-    static_assert(sizeof(T) == 8, "8-byte words");
-    if (WT) __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = val;
+    __builtin_nontemporal_store(*reinterpret_cast<const nt_v2u64*>(&val), reinterpret_cast<nt_v2u64*>(p));
 }
 
 struct FilterView {
@@ -138,7 +125,7 @@ struct FilterView {
     } while (0)
 // start-up latency of a step launch: SMC_CLOCK reads the clock where it stands (no pointer needed: the entry clock is taken before
 // the kernel-argument block has arrived), SMC_STAMP_START stores (first pick numbers drawn, entry) in words 0 and 1 of the
-// workgroup's row in the SECOND half of the stamp buffer (k_persist's accumulators otherwise)
+// workgroup's row in the SECOND half of the stamp buffer (the first half holds the phase stamps)
 #define SMC_CLOCK() __builtin_amdgcn_s_memrealtime()
 // phase stamp k with a clock value read earlier (stamp 0 of k_step: read at entry, stored once the view has arrived)
 #define SMC_STAMP_AT(v, k, clk)                                                                           \
@@ -165,8 +152,7 @@ struct FilterView {
 // ---- weighted quantiles: helpers shared by the stand-alone kernels (smc_aux_kernels.h) and the per-step summaries --------
 // (logZ, logmu, ess) of filter th into the pinned host mirror; with a ticket (step API) the values are released to the host
 // before the ticket is: the host reads them as soon as it sees the ticket, without a stream synchronisation
-template <class VIEW>
-__device__ __forceinline__ void host_emit(const VIEW& v, int th, double z, double logmu, double ess) {
+__device__ __forceinline__ void host_emit(const FilterView& v, int th, double z, double logmu, double ess) {
     if (!v.host_out) return;
     v.host_out[th] = z;
     v.host_out[(size_t)v.ntheta + th] = logmu;
@@ -212,21 +198,7 @@ __host__ __device__ inline double q7_level(double p) { return p > 0.0 ? (p < 1.0
 // workgroups share a CU; the arbiter otherwise favours the older one, which then finishes ~4 us before its neighbour
 // and leaves it to run the tail of the launch alone at half occupancy.  With this rule whoever has fallen behind catches
 // up and both end together (measured on C2: end-time spread of the workgroups 4.8 -> 2.1 us, 17.65 -> 16.3 us per step).
-#ifndef SMC_NORMALS_EARLY
-#define SMC_NORMALS_EARLY 0
-#endif
 #define SMC_PRIO(ph) __builtin_amdgcn_s_setprio((short)(3 - (ph)))
-
-// threadIdx.x as the helpers below read it.  SMC_TID_OPAQUE (the translation unit of the persistent step kernel): behind an empty
-// `asm volatile`, so that a loop around the step cannot hoist the lane / wave numbers and every LDS offset derived from them
-// out of it and keep them in registers the step needs (k_persist: 22 spilled registers otherwise).
-__device__ __forceinline__ int smc_tid() {
-    int t = (int)threadIdx.x;
-#if defined(SMC_TID_OPAQUE)
-    asm volatile("" : "+v"(t));
-#endif
-    return t;
-}
 
 // ---------------------------------------------------------------------------------------------
 // wave / block primitives (wave64)
@@ -409,7 +381,7 @@ __device__ __forceinline__ double wave_max(double v) {
 template <int THREADS>
 __device__ __forceinline__ double block_max(double v, double* red) {
     constexpr int NW = THREADS / WAVE;
-    const int tid_ = smc_tid(), lane = tid_ & (WAVE - 1), wave = tid_ / WAVE;
+    const int tid_ = (int)threadIdx.x, lane = tid_ & (WAVE - 1), wave = tid_ / WAVE;
     v = wave_max(v);
     if (lane == 0) red[wave] = v;
     __syncthreads();
@@ -423,7 +395,7 @@ __device__ __forceinline__ double block_max(double v, double* red) {
 template <int THREADS>
 __device__ __forceinline__ int block_max_i32(int v, int* red) {
     constexpr int NW = THREADS / WAVE;
-    const int tid_ = smc_tid(), lane = tid_ & (WAVE - 1), wave = tid_ / WAVE;
+    const int tid_ = (int)threadIdx.x, lane = tid_ & (WAVE - 1), wave = tid_ / WAVE;
     v = wave_max_i32(v);
     if (lane == 0) red[wave] = v;
     __syncthreads();
@@ -466,14 +438,13 @@ struct TablePre {
     double k2;      // RPT = 2 (two records per thread: filters with up to twice as many segments as threads): this thread's records are
     uint64_t S2;    // 2 tid (k1, S1) and 2 tid + 1 (k2, S2)
 };
-// (VIEW: FilterView, or the same struct read in place from the kernel-argument segment - the persistent step kernel)
 // segk, segS, nseg: v.segk[cur], v.segS[cur] and v.nseg, which the callers hold before the view has arrived (k_step: by value at
 // the head of its arguments) - the two loads every workgroup waits for take no address from memory; the emitter's sums of squares
 // (full records only) are read through the view
-template <int THREADS, class VIEW, int RPT = 1>
-__device__ __forceinline__ TablePre table_preload(const VIEW& v, const double* segk, const uint64_t* segS, int nseg, int cur, int th, bool emit) {
+template <int THREADS, int RPT = 1>
+__device__ __forceinline__ TablePre table_preload(const FilterView& v, const double* segk, const uint64_t* segS, int nseg, int cur, int th, bool emit) {
     TablePre p{-inf(), 0, 0, 0, -inf(), 0};
-    const int tid = smc_tid();
+    const int tid = (int)threadIdx.x;
     const size_t base = (size_t)th * nseg;
     if (RPT == 2) {   // records 2 tid and 2 tid + 1 (the table itself, when somebody needs it, is built by table_prologue from memory)
         if (2 * tid < nseg) { p.k1 = segk[base + 2 * tid]; p.S1 = segS[base + 2 * tid]; }
@@ -487,11 +458,11 @@ __device__ __forceinline__ TablePre table_preload(const VIEW& v, const double* s
     }
     return p;
 }
-template <int THREADS, class VIEW>
-__device__ __forceinline__ uint64_t table_prologue(const VIEW& v, int cur, int th, const TableLds& L, bool emit,
+template <int THREADS>
+__device__ __forceinline__ uint64_t table_prologue(const FilterView& v, int cur, int th, const TableLds& L, bool emit,
                                                    bool first_emit, uint32_t t_emit, const TablePre* pre = nullptr, double* Kout = nullptr) {
     constexpr int NW = THREADS / WAVE;
-    const int tid = smc_tid(), lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     const size_t base = (size_t)th * v.nseg;
     const double* sk = v.segk[cur] + base;
     const uint64_t* sS = v.segS[cur] + base;
@@ -583,12 +554,12 @@ __device__ __forceinline__ uint64_t table_prologue(const VIEW& v, int cur, int t
 // one record per thread (nseg_p2 <= THREADS), the exponent maximum, one wave scan of the Q_b, the wave totals, and the NE + 1
 // values picked out of the lanes that hold them.  Two barriers (the full prologue: three, plus the table traffic).  The
 // numbers are the same integers table_prologue produces.  P0 = Dcum[lo-1] (0 for lo = 0), Dc[r] = Dcum[lo+r].
-template <int THREADS, int NE, class VIEW, int RPT = 1>
-__device__ __forceinline__ uint64_t window_prologue(const VIEW& v, uint64_t* scr, const TablePre& pre, int lo, uint64_t& P0,
+template <int THREADS, int NE, int RPT = 1>
+__device__ __forceinline__ uint64_t window_prologue(const FilterView& v, uint64_t* scr, const TablePre& pre, int lo, uint64_t& P0,
                                                     uint64_t (&Dc)[NE], int (&shw)[NE], double& Kout) {
     constexpr int NW = THREADS / WAVE;
     constexpr int DEADK = (int)0x80000000;
-    const int tid = smc_tid(), lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     // RPT = 1: thread t holds the record of segment t; RPT = 2: of segments 2 t and 2 t + 1 (nseg <= 2 THREADS)
     const bool live = RPT * tid < v.nseg, live2 = RPT == 2 && 2 * tid + 1 < v.nseg;
     int ki = (!live || pre.k1 == -inf()) ? DEADK : (int)pre.k1;
@@ -655,10 +626,10 @@ struct SegRec {
 
 // Cout: where the segment's inclusive sums go (global buffer or LDS), 16-B aligned.
 // PADDED: Cout is an LDS copy indexed through lds_pad().
-template <int THREADS, int NP, bool PADDED = false, bool WT = false>
+template <int THREADS, int NP, bool PADDED = false>
 __device__ __forceinline__ SegRec segment_normalize(double (&lw)[NP][2], uint64_t* scr, uint64_t* Cout, bool want_s2) {
     constexpr int NW = THREADS / WAVE;
-    const int tid = smc_tid(), lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     // exp(logw) = p 2^k for every particle: independent of the maximum, so it overlaps the reduction
     // a dead particle (NaN, infinite or absurd log-weight) takes p = 0 and the exponent DEAD = -2^30, below every live one
     // (lw_alive: |k| < 2^30), so that k - kb never wraps: nothing after the maximum has to ask again who is alive
@@ -754,7 +725,7 @@ __device__ __forceinline__ SegRec segment_normalize(double (&lw)[NP][2], uint64_
         cc.x = excl + q[k][0];
         cc.y = cc.x + q[k][1];
         if (PADDED) *reinterpret_cast<ulonglong2*>(Cout + lds_pad(2 * (tid + k * THREADS))) = cc;
-        else store_out<WT>(reinterpret_cast<ulonglong2*>(Cout + 2 * (tid + k * THREADS)), cc);
+        else store_out(reinterpret_cast<ulonglong2*>(Cout + 2 * (tid + k * THREADS)), cc);
         basek += ktot;
     }
     if (MERGED) basek = readlane_u64(tt, NP * NW - 1);
@@ -773,25 +744,24 @@ __device__ __forceinline__ SegRec segment_normalize(double (&lw)[NP][2], uint64_
 }
 
 // normalize() of one segment into the global ping-pong buffers
-template <int THREADS, int NP, bool WT = false, class VIEW>
-__device__ __forceinline__ SegRec segment_epilogue(const VIEW& v, int nxt, int th, int sb, double (&lw)[NP][2],
+template <int THREADS, int NP>
+__device__ __forceinline__ SegRec segment_epilogue(const FilterView& v, int nxt, int th, int sb, double (&lw)[NP][2],
                                                    uint64_t* scr) {
     uint64_t* Cout = v.C[nxt] + (size_t)th * v.npad + (size_t)sb * v.seg;
-    const SegRec rec = segment_normalize<THREADS, NP, false, WT>(lw, scr, Cout, v.want_s2 != 0);
-    if (smc_tid() == 0) {
+    const SegRec rec = segment_normalize<THREADS, NP>(lw, scr, Cout, v.want_s2 != 0);
+    if (threadIdx.x == 0) {
         const size_t r = (size_t)th * v.nseg + sb;
-        store_word<WT>(&v.segk[nxt][r], rec.kb);
-        store_word<WT>(&v.segS[nxt][r], rec.S);
-        store_word<WT>(&v.segS2hi[nxt][r], rec.hi);
-        store_word<WT>(&v.segS2lo[nxt][r], rec.lo);
+        v.segk[nxt][r] = rec.kb;
+        v.segS[nxt][r] = rec.S;
+        v.segS2hi[nxt][r] = rec.hi;
+        v.segS2lo[nxt][r] = rec.lo;
     }
     return rec;
 }
 
 // (logmu, ess) of a single-segment filter from its own record: exactly what table_prologue's emit
 // computes for a one-entry table (K = kb).  Thread 0 only.
-template <class VIEW>
-__device__ __forceinline__ void emit_own(const VIEW& v, int th, const SegRec& rec, uint32_t t_emit, bool first_emit) {
+__device__ __forceinline__ void emit_own(const FilterView& v, int th, const SegRec& rec, uint32_t t_emit, bool first_emit) {
     const int sh = seg_shift(rec.kb, rec.kb, v.SH);
     const uint64_t D = seg_Q(rec.S, sh), R = seg_R(rec.hi, rec.lo, sh, v.SH);
     double logmu, ess;
@@ -810,8 +780,7 @@ __device__ __forceinline__ void emit_own(const VIEW& v, int th, const SegRec& re
 // (logmu, ess = 0) of the previous step from the totals (K, Dtot) alone: what table_prologue's emit produces when the
 // records carry no sum of squares (want_s2 = 0 at that step: log_likelihood without traces, particles.jl:142 discards
 // ess).  Thread 0 of the emitting workgroup; no table, no extra barrier.
-template <class VIEW>
-__device__ __forceinline__ void emit_from_totals(const VIEW& v, int th, double K, uint64_t Dtot, bool first_emit, uint32_t t_emit) {
+__device__ __forceinline__ void emit_from_totals(const FilterView& v, int th, double K, uint64_t Dtot, bool first_emit, uint32_t t_emit) {
     double logmu, ess;
     combine_outputs(K, Dtot, 0, v.SH, v.n, logmu, ess);
     v.last_logmu[th] = logmu;
@@ -844,7 +813,7 @@ __global__ __launch_bounds__(THREADS) void k_init(FilterView v, int nxt, double 
     constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint64_t* scr = (uint64_t*)smem;
-    const int sb = logical_segment(blockIdx.x, v.nseg), th = blockIdx.y, tid = smc_tid();
+    const int sb = logical_segment(blockIdx.x, v.nseg), th = blockIdx.y, tid = (int)threadIdx.x;
     if (v.skip && v.skip[th]) return;   // workgroup-uniform
     const Params prm = v.params[th];
     const uint32_t stream = v.stream[th];
@@ -909,9 +878,6 @@ __host__ __device__ inline size_t step_lds_bytes(int nseg_p2, int threads, int n
 // ---------------------------------------------------------------------------------------------
 // SYS = opt-in systematic resampling (SMC_FLAG_SYSTEMATIC): child j takes the point T_j = floor((j Dtot + v0) / n)
 // instead of the multinomial targets between the block's break points.
-// PERSIST: the body as one iteration of the persistent step kernel (k_persist below): every store another workgroup of the
-// same launch reads (x, C, the segment record) is a write-through store; the loads are plain - the caller has polled the
-// previous step's completion flags and made an agent-scope acquire before the call.
 // GTAB: the segment table comes from global memory (v.tabD, v.tabsh; k_table built it before this launch and emitted the previous
 // step): filters with more segments than the workgroup has threads.  No table in LDS, no emission here.
 // RPT = 2: filters with more segments than threads, but at most twice as many: the window prologue with TWO records per thread
@@ -938,25 +904,20 @@ struct StepEarly {
     const uint64_t* C;      // v.C[cur]
     uint32_t n32;           // v.n (<= 2^31)
 };
-template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS, bool PERSIST, class VIEW, bool GTAB = false, int RPT = 1, bool GUIDED = false, bool BYV = false>
-__device__ __forceinline__ void step_body(const VIEW& v, const StepEarly& ea, uint64_t seed, uint32_t t, uint32_t stream0, int nseg, int cur, int emit_prev,
+template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS, bool GTAB = false, int RPT = 1, bool GUIDED = false, bool BYV = false>
+__device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& ea, uint64_t seed, uint32_t t, uint32_t stream0, int nseg, int cur, int emit_prev,
                                           double yval, const Params* prm0, char* smem) {
-    static_assert(!(BYV && PERSIST), "by value: one launch per step");
     const unsigned long long t_entry = SMC_CLOCK();
-    static_assert(!GTAB || (MULTI && !PERSIST), "global table: multi-segment launches");
-    static_assert(RPT == 1 || (RPT == 2 && MULTI && !GTAB && !PERSIST), "two records per thread: multi-segment launches");
+    static_assert(!GTAB || MULTI, "global table: multi-segment launches");
+    static_assert(RPT == 1 || (RPT == 2 && MULTI && !GTAB), "two records per thread: multi-segment launches");
     constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
     static_assert(!(GUIDED && model_marginal<MODEL>::value), "marginal families have no proposals");
     constexpr int SEG = 2 * NP * THREADS;
     constexpr int NQ = 2 * NP;   // particles per thread
     constexpr int NSTAGE = nstage_for(SEG);
     constexpr int SEGP = lds_padded_len(SEG);   // padded length of a staged segment in LDS
-    int sb_ = logical_segment(blockIdx.x, nseg), th_ = BYV ? 0 : blockIdx.y, tid_ = smc_tid();   // (by value: ONE filter per launch)
-    if (PERSIST) {   // opaque per iteration: the loop around this body must not hoist everything derived from them into registers
-        asm volatile("" : "+v"(tid_));
-    }
-    const int sb = sb_, th = th_, tid = tid_;
-    if (!PERSIST && !BYV && v.skip && v.skip[th]) return;   // workgroup-uniform
+    const int sb = logical_segment(blockIdx.x, nseg), th = BYV ? 0 : blockIdx.y, tid = (int)threadIdx.x;   // (by value: ONE filter per launch)
+    if (!BYV && v.skip && v.skip[th]) return;   // workgroup-uniform
     const int nxt = cur ^ 1;
     uint32_t stream;
     if constexpr (BYV) stream = stream0;
@@ -986,7 +947,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, const StepEarly& ea, ui
         F0 = Fb[0];
         F1 = Fb[1];
     }
-    const TablePre tpre = (MULTI && !GTAB) ? table_preload<THREADS, VIEW, RPT>(v, (const double*)ea.rec0, (const uint64_t*)ea.rec1, nseg, cur, th, emit_prev == 1 && sb == 0)   // (the sums of squares: full records only)
+    const TablePre tpre = (MULTI && !GTAB) ? table_preload<THREADS, RPT>(v, (const double*)ea.rec0, (const uint64_t*)ea.rec1, nseg, cur, th, emit_prev == 1 && sb == 0)   // (the sums of squares: full records only)
                                            : TablePre{-inf(), 0, 0, 0, -inf(), 0};
     // (2) the 64-bit pick numbers of this thread's children
     unsigned long long t_draw = 0;
@@ -1067,7 +1028,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, const StepEarly& ea, ui
             else box_muller(draw(seed, pg, stream, t, SLOT_NORMAL0 + c), z[k][c][0], z[k][c][1]);
             // systematic: keep the normals HERE, under the load latencies.  multinomial: measured faster when the
             // compiler sinks them next to their use, where they fill the waits of the LDS search
-            if (SYS || SMC_NORMALS_EARLY) asm volatile("" : "+v"(z[k][c][0]), "+v"(z[k][c][1]));
+            if (SYS) asm volatile("" : "+v"(z[k][c][0]), "+v"(z[k][c][1]));
         }
     }
 
@@ -1116,7 +1077,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, const StepEarly& ea, ui
             if (SYS) __syncthreads();   // (the step's uniform in LDS: the prologues' barriers otherwise)
         } else if (use_fast) {
             double Kw;
-            alive = window_prologue<THREADS, NSTAGE, VIEW, RPT>(v, L.scr, tpre, spec_lo, P0, Dc, shw, Kw);
+            alive = window_prologue<THREADS, NSTAGE, RPT>(v, L.scr, tpre, spec_lo, P0, Dc, shw, Kw);
             if (emit_totals && tid == 0) emit_from_totals(v, th, Kw, alive, t == 1u, t - 1u);
         } else {
             alive = table_prologue<THREADS>(v, cur, th, L, emitter, t == 1u, t - 1u, RPT == 1 ? &tpre : nullptr);
@@ -1184,11 +1145,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, const StepEarly& ea, ui
                 Tg[i] = sys_target(sbase, kk[i]);
             } else {   // the block's largest uniform is its break point; the others are iid below it
                 uint64_t pick;
-#if SMC_EXP_PICKF64
-                pick = (uint64_t)(fma((double)(uint32_t)(rr[i] >> 32), 0x1p-32, (double)((uint32_t)rr[i] >> 11) * 0x1p-53) * (double)(Tlast - Tfirst));
-#else
                 mul64wide(rr[i], Tlast - Tfirst, pick, lo_);
-#endif
                 Tg[i] = kk[i] == m_blk - 1 ? Tlast : Tfirst + pick;
             }
             pos[i] = b_lo;
@@ -1390,7 +1347,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, const StepEarly& ea, ui
             double2 o;
             o.x = xn[0][c];
             o.y = xn[1][c];
-            store_out<PERSIST>(reinterpret_cast<double2*>(v.x[nxt] + ((size_t)c * v.ntheta + th) * v.npad + i0), o);
+            store_out(reinterpret_cast<double2*>(v.x[nxt] + ((size_t)c * v.ntheta + th) * v.npad + i0), o);
         }
         if (v.anc) {
             int2 o;
@@ -1408,7 +1365,7 @@ __device__ __forceinline__ void step_body(const VIEW& v, const StepEarly& ea, ui
         if (acc == 1.2345) v.logZ[th] = acc;
         return;
     }
-    const SegRec rec = segment_epilogue<THREADS, NP, PERSIST>(v, nxt, th, sb, lw, scr);
+    const SegRec rec = segment_epilogue<THREADS, NP>(v, nxt, th, sb, lw, scr);
     if (!MULTI && v.emit_now && tid == 0) emit_own(v, th, rec, t, false);
     SMC_STAMP(v, 7);
 }
@@ -1446,77 +1403,8 @@ __global__ __launch_bounds__(THREADS) void k_step(uint64_t seed, uint32_t t, uin
                                                   const uint64_t* C, uint32_t pack, uint32_t n32, double yval, Params prm0, FilterView v) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const StepEarly ea{brow, rec0, rec1, C, n32};
-    step_body<MODEL, THREADS, NP, MULTI, SYS, false, FilterView, GTAB, RPT, GUIDED, BYV>(v, ea, seed, t, stream0, (int)(pack & 0xffffu), (int)(pack >> 16 & 1u),
-                                                                                         (int)(pack >> 17), yval, &prm0, smem);
-}
-
-// ---------------------------------------------------------------------------------------------
-// k_persist : the steps [t0, t1) of log_likelihood's loop (particles.jl:141-144) for a multi-segment filter in ONE launch -
-// OPT-IN (SMC_PERSIST=1), measured SLOWER than one launch per step on MI355X ("persistent step kernel"):
-// kept as the measured form of that negative result.  grid (nseg, ntheta), every workgroup resident (the host checks the
-// occupancy; every spin is bounded).  Between two steps: the storing waves drain their write-through stores, a barrier, ONE
-// lane publishes the workgroup's completion flag (tag = next step); thread i of every workgroup of the filter polls the flag
-// of segment i (relaxed sc1 loads, s_sleep), one lane's agent-scope acquire, a barrier - then the step's plain loads.
-// ---------------------------------------------------------------------------------------------
-struct PersistCtl {
-    unsigned* flags[2];   // [ntheta * nseg] per buffer: t + 1 once step t of that segment is complete and visible
-    int* err;             // pinned host word: != 0 when a spin expired (not every workgroup resident)
-};
-// (second launch bound: as many waves per SIMD as two workgroups per CU need - the loop otherwise hoists its invariants into 225 registers)
-template <int MODEL, int THREADS, int NP>
-__global__ __launch_bounds__(THREADS, (THREADS >= 512 ? 4 : (THREADS >= 256 ? 4 : 2))) void k_persist(FilterView v_arg, int cur, uint32_t t0, uint32_t t1, PersistCtl pc) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    // The view is read IN PLACE from the kernel-argument segment at every step, through a pointer the compiler cannot see through:
-    // everything derived from it (Philox key schedule, base addresses, flags) is then loaded and computed where the step uses it, as
-    // in k_step - hoisted out of the loop it does not fit the scalar registers (110 spilled lanes, 45 spilled vector registers).
-    typedef __attribute__((address_space(4))) const char karg_byte;
-    karg_byte* ka = (karg_byte*)__builtin_amdgcn_kernarg_segment_ptr();   // v_arg is the first argument: offset 0
-    // a word of the LDS scratch nobody else uses (the last tail word: the systematic kernels' only): "a spin of this workgroup expired"
-    int* expired_flag = (int*)((uint64_t*)(smem + (size_t)v_arg.nseg_p2 * 16) + scr_words(THREADS, NP) - 1);
-    if (tid == 0) *expired_flag = 0;
-    // diagnostic builds (FilterView::dbg, allocated by the profiling build's smc_create only): where a workgroup's time goes -
-    // accumulated in four more of those LDS words (wait, body, publish, last stamp), not in registers the step needs
-    unsigned long long* acc = (unsigned long long*)((uint64_t*)(smem + (size_t)v_arg.nseg_p2 * 16) + scr_words(THREADS, NP) - 5);
-    if (v_arg.dbg && tid == 0) { acc[0] = acc[1] = acc[2] = 0; acc[3] = __builtin_amdgcn_s_memrealtime(); }
-    for (uint32_t t = t0; t < t1; ++t) {
-        asm volatile("" : "+s"(ka));
-        typedef __attribute__((address_space(4))) const FilterView karg_view;
-        karg_view& v = *(karg_view*)ka;
-        const int sb = logical_segment(blockIdx.x, v.nseg), th = blockIdx.y;
-        if (t > t0) {
-            if (tid < v.nseg) {
-                const unsigned* f = pc.flags[cur] + (size_t)th * v.nseg + tid;
-                const unsigned long long start = __builtin_amdgcn_s_memrealtime();
-                while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != t) {
-                    if (__builtin_amdgcn_s_memrealtime() - start > 10000000ull) { *expired_flag = 1; break; }   // 100 ms: give up
-                    __builtin_amdgcn_s_sleep(2);
-                }
-            }
-            if (tid == 0) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            __syncthreads();
-            if (*expired_flag) {   // workgroup-uniform (read behind the barrier): this workgroup leaves; the others' spins expire in turn
-                if (tid == 0) *pc.err = 1;
-                return;
-            }
-        }
-        if (v.dbg && tid == 0) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); acc[0] += now - acc[3]; acc[3] = now; }
-        const StepEarly ea{v.brk + (size_t)(t - v.brk_t0) * v.ntheta * ((size_t)v.nseg + 1), v.segk[cur], v.segS[cur], v.C[cur], (uint32_t)v.n};
-        step_body<MODEL, THREADS, NP, true, false, true>(v, ea, v.seed, t, 0u, v.nseg, cur, 2, 0.0, (const Params*)nullptr, smem);
-        if (v.dbg && tid == 0) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); acc[1] += now - acc[3]; acc[3] = now; }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains its write-through stores
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(pc.flags[cur ^ 1] + (size_t)th * v.nseg + sb, t + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (v.dbg && tid == 0) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); acc[2] += now - acc[3]; acc[3] = now; }
-        cur ^= 1;
-    }
-    if (v_arg.dbg && tid == 0) {   // [steps, wait (poll + acquire + barrier), step body, drain + barrier + publish] in 10 ns units; marker in word 7
-        unsigned long long* d = v_arg.dbg + ((size_t)gridDim.y * gridDim.x + (size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8;   // second half of the buffer
-        d[0] = t1 - t0; d[1] = acc[0]; d[2] = acc[1]; d[3] = acc[2]; d[7] = 0x5045525349535421ull;
-    }
+    step_body<MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, GUIDED, BYV>(v, ea, seed, t, stream0, (int)(pack & 0xffffu), (int)(pack >> 16 & 1u),
+                                                                      (int)(pack >> 17), yval, &prm0, smem);
 }
 
 // ---------------------------------------------------------------------------------------------

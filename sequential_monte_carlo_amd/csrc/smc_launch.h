@@ -57,9 +57,6 @@ template <int MODEL> hipError_t launch_init(const FilterView& v, Geo g, int nxt,
 // kernel's early loads as the caller derived them for THIS launch (the view's pointers, the current buffer, t)
 template <int MODEL> hipError_t launch_step(const FilterView& v, Geo g, const StepHot& hot, hipStream_t s);
 template <int MODEL> hipError_t launch_resident(const FilterView& v, int T, StepRec* recs, hipStream_t s);
-// opt-in persistent step kernel: the steps [t0, t1) of a multi-segment filter in one launch; hipErrorCooperativeLaunchTooLarge when
-// the grid cannot be resident all at once (or the geometry has no instantiation): the caller then launches step by step
-template <int MODEL> hipError_t launch_persist(const FilterView& v, Geo g, int cur, uint32_t t0, uint32_t t1, PersistCtl pc, hipStream_t s);
 // summaries (quantile levels / moments named by the view's sum_* fields, row 0) of the current state of single-segment filters in
 // one launch; hipErrorInvalidValue when the segment length has no instantiation or the state does not fit LDS
 template <int MODEL> hipError_t launch_summ_once(const FilterView& v, int cur, hipStream_t s);

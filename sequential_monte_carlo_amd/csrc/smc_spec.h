@@ -110,17 +110,9 @@ SMC_HD uint32_t xor_and(uint32_t a, uint32_t b, uint32_t c) {
 #endif
 }
 
-// SMC_EXP_ROUNDS / SMC_EXP_PICKF64: timing experiments of `make exp` only (scripts/dbg/exp_spec.sh: what a cheaper numerical
-// specification would buy); the product and the oracle are Philox4x32-10 and 64 x 64 -> 128-bit integer picks
-#ifndef SMC_EXP_ROUNDS
-#define SMC_EXP_ROUNDS 10
-#endif
-#ifndef SMC_EXP_PICKF64
-#define SMC_EXP_PICKF64 0
-#endif
 SMC_HD u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
-    for (int r = 0; r < SMC_EXP_ROUNDS; ++r) {
+    for (int r = 0; r < 10; ++r) {
         // full 32x32 -> 64 products (one v_mad_u64_u32 each on the device)
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
         const uint32_t h0 = (uint32_t)(p0 >> 32), l0 = (uint32_t)p0;
@@ -146,15 +138,8 @@ template <uint64_t BITS>
 __device__ __forceinline__ double fma_const(double p, double r) {
     uint32_t lo, hi;
     double d;
-    // SMC_FMAK_PINNED (the translation unit of the persistent step kernel): `volatile` keeps the constants where they are used - a
-    // loop around the step would otherwise hoist all ~60 of them into scalar registers it does not have (134 spilled lanes)
-#if defined(SMC_FMAK_PINNED)
-    asm volatile("s_mov_b32 %0, %1" : "=s"(lo) : "n"((uint32_t)BITS));
-    asm volatile("s_mov_b32 %0, %1" : "=s"(hi) : "n"((uint32_t)(BITS >> 32)));
-#else
     asm("s_mov_b32 %0, %1" : "=s"(lo) : "n"((uint32_t)BITS));
     asm("s_mov_b32 %0, %1" : "=s"(hi) : "n"((uint32_t)(BITS >> 32)));
-#endif
     const double c = __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(p), "v"(r), "s"(c));
     return d;

@@ -6,7 +6,6 @@ library's host twin of the step -> the oracle's normalisation.  Compared on ever
 the four laws lg-optimal, lg-poor, ucsv-optimal and rb: the logmu trace, the ess trace at every kept step, logZ, x in all rows,
 w, ancestors and the raw fixed-point weights C, m, S, S2hi, S2lo.  No tolerances.  tests/test_composed_host.py ties the pieces
 and the driver to the pinned oracle on the CPU."""
-import os
 import time
 
 import numpy as np
@@ -182,17 +181,12 @@ def test_batched_proposal_rows(L, ob, flags):
     assert_series(dev, _REF[key], ("batched rows", flags))
 
 
-# ---- SMC_PERSIST=1 ---------------------------------------------------------------------------------------------------------
+# ---- several segments, no traces, no ancestors -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("law", list(LAWS))
-def test_persistent_opt_in_changes_no_bits(L, ob, law):
-    """the persistent step kernel exists for the bootstrap step of the first three families: a handle with a proposal declines it,
-    and the marginal family has no instantiation (do_persist answers "not available" and the series goes on one launch per step).
-    With the variable set as test_gpu_parity.test_persistent_step_kernel_opt_in_is_bit_identical sets it, and a call that would
-    take that path (several segments, no traces, no ancestors), every law gives the reference's bits."""
+def test_multi_segment_series_without_traces(L, ob, law):
+    """the whole-series call of a multi-segment handle that keeps neither traces nor ancestors (the geometry of the path
+    "multi-seg256", which records both): no step but the last accumulates the sum of squares, and (logmu, 0) of the steps before
+    follow from the totals alone.  Every law gives the reference's bits."""
     n, seg, nth, T = 3000, 256, 3, 12
-    try:
-        os.environ["SMC_PERSIST"] = "1"
-        dev = series_on(L, law, n, seg, 0, nth, T, trace=False)
-    finally:
-        os.environ.pop("SMC_PERSIST", None)
-    assert_series(dev, reference(L, ob, law, n, seg, False, nth, T), (law, "SMC_PERSIST=1"), traces=False)
+    dev = series_on(L, law, n, seg, 0, nth, T, trace=False)
+    assert_series(dev, reference(L, ob, law, n, seg, False, nth, T), (law, "no traces"), traces=False)

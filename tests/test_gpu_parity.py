@@ -802,44 +802,40 @@ def test_launch_geometry_knobs_do_not_change_results(L, ob):
         os.environ.pop("SMC_RES_NP", None)
 
 
-def test_persistent_step_kernel_opt_in_is_bit_identical(L, ob):
-    """SMC_PERSIST=1 (opt-in; measured slower than one launch per step): the steps 1 .. T-2 of a multi-segment
-    filter run in ONE launch - write-through stores, a completion flag per workgroup and step, bounded spins.  Same step body,
-    same bits: against the oracle, and against the default path on filters the oracle would take too long for (uneven weights
-    that leave the staged window, ragged last segment, several filters per handle, every model family)."""
-    import os
+def test_multi_segment_series_leaves_no_residue_on_the_handle(L, ob):
+    """The default whole-series path of multi-segment filters (one k_step launch per step) on shapes with uneven weights that
+    leave the staged window, a ragged last segment, several filters per handle and every model family.  A handle that has run
+    log_likelihood(y) and then runs a second, shorter series gives the bits of a fresh handle that runs the shorter series alone
+    (logZ, state, raw weights C): the cached break points, the flipped buffers and the segment records of the first call leave
+    no residue.  Where the oracle is quick enough (n <= 20000), logZ, x and w of the whole series against the oracle as well."""
     cases = ((1, LG, 20000, 256, 2, 14), (1, LG, 300000, 1024, 1, 40), (2, SV, 70000, 512, 1, 25), (3, UC, 50000, 1024, 2, 20),
              (1, [0.9, 1.0, 1.0, 1e-5, 0.0, 4.0], 70000, 2048, 1, 12))
-    try:
-        for model, raw, n, seg, nth, T in cases:
-            _, y = ob.simulate(model, raw if raw[3:4] != [1e-5] else [0.9, 1.0, 1.0, 0.5, 0.0, 4.0], T, 7)
-            res = []
-            for mode in ("0", "1"):
-                os.environ["SMC_PERSIST"] = mode
-                h = L.Handle(model, nth, n, seg=seg, seed=13)
-                h.set_params(np.tile(raw, (nth, 1)))
-                z = h.log_likelihood(y)
-                z2 = h.log_likelihood(y[: T - 3])          # a second, shorter series on the same handle (flags re-initialised)
-                x, w, _ = h.state(want_anc=False)
-                Craw = h.weights_raw()[0]
-                res.append((z, z2, x, w, Craw))
-                h.close()
-            for a, b in zip(res[0], res[1]):
-                assert np.array_equal(a.view(np.uint64) if a.dtype != np.uint64 else a, b.view(np.uint64) if b.dtype != np.uint64 else b), (model, n, seg)
-            if n <= 20000:
-                os.environ["SMC_PERSIST"] = "1"
-                h = L.Handle(model, nth, n, seg=seg, seed=13)
-                h.set_params(np.tile(raw, (nth, 1)))
-                z = h.log_likelihood(y)
-                x, w, _ = h.state(want_anc=False)
-                for th in range(nth):
-                    f = ob.Filter(model, raw, n, seg=seg, seed=13, stream=th)
-                    oz = f.log_likelihood(y)
-                    ox, ow, _, _ = f.state()
-                    assert bits([z[th]])[0] == bits([oz])[0] and same(x[:, th], ox) and same(w[th], ow)
-                h.close()
-    finally:
-        os.environ.pop("SMC_PERSIST", None)
+    for model, raw, n, seg, nth, T in cases:
+        _, y = ob.simulate(model, raw if raw[3:4] != [1e-5] else [0.9, 1.0, 1.0, 0.5, 0.0, 4.0], T, 7)
+        res = []
+        for used in (True, False):
+            h = L.Handle(model, nth, n, seg=seg, seed=13)
+            h.set_params(np.tile(raw, (nth, 1)))
+            if used:
+                h.log_likelihood(y)
+            z2 = h.log_likelihood(y[: T - 3])
+            x, w, _ = h.state(want_anc=False)
+            Craw = h.weights_raw()[0]
+            res.append((z2, x, w, Craw))
+            h.close()
+        for a, b in zip(res[0], res[1]):
+            assert np.array_equal(a.view(np.uint64) if a.dtype != np.uint64 else a, b.view(np.uint64) if b.dtype != np.uint64 else b), (model, n, seg)
+        if n <= 20000:
+            h = L.Handle(model, nth, n, seg=seg, seed=13)
+            h.set_params(np.tile(raw, (nth, 1)))
+            z = h.log_likelihood(y)
+            x, w, _ = h.state(want_anc=False)
+            for th in range(nth):
+                f = ob.Filter(model, raw, n, seg=seg, seed=13, stream=th)
+                oz = f.log_likelihood(y)
+                ox, ow, _, _ = f.state()
+                assert bits([z[th]])[0] == bits([oz])[0] and same(x[:, th], ox) and same(w[th], ow)
+            h.close()
 
 
 def test_sv_full_size_against_grid_filter(L):
