@@ -497,6 +497,13 @@ int smc_get_quantiles(smc_handle h, int component, const double* p, int np, doub
  *   smc_history_len    steps recorded so far (0 for a handle that is not armed)
  *   smc_history_get    the recorded state of step t (0-based): bit for bit what smc_get_state gave after that step.  x [d][n_theta][n_x],
  *                      w [n_theta][n_x]; either may be NULL.  SMC_ESTATE when not armed, SMC_EINVAL for t outside the record
+ *   smc_history_put    overwrites recorded step t of an armed handle with the caller's clouds, in smc_history_get's layouts; NULL
+ *                      leaves that part alone (both NULL: nothing happens).  It exists so that the backward pass can be run on
+ *                      clouds that a filter would not produce (states that are not finite on zero-weight particles, a step at which
+ *                      every weight is 0, subnormal weights: tests/smoother_planted.py), as smc_device_math, smc_device_guided_step
+ *                      and smc_device_rb_step exist for the step's arithmetic.  It waits for the handle's stream, then copies; the
+ *                      length of the record, the filter state and everything else of the handle stay as they are.  SMC_ESTATE when
+ *                      not armed, SMC_EINVAL for t outside the record
  *   smc_history_end    frees the record and disarms; the handle then runs exactly the code of a handle that was never armed.  A
  *                      fresh handle, and one that smc_create recycles from destroyed ones, is disarmed
  *   smc_smooth         the backward pass over the recorded steps, T = smc_history_len: ws [T][n_theta][n_x], mean and var
@@ -514,6 +521,7 @@ int smc_get_quantiles(smc_handle h, int component, const double* p, int np, doub
 int smc_history_begin(smc_handle h, int64_t T_cap);
 int smc_history_len(smc_handle h, int64_t* len);
 int smc_history_get(smc_handle h, int64_t t, double* x /*[d][n_theta][n_x]*/, double* w /*[n_theta][n_x]*/);
+int smc_history_put(smc_handle h, int64_t t, const double* x /*[d][n_theta][n_x] or NULL*/, const double* w /*[n_theta][n_x] or NULL*/);
 int smc_history_end(smc_handle h);
 int smc_smooth(smc_handle h, double* ws /*[T][n_theta][n_x] or NULL*/, double* mean /*[T][d][n_theta] or NULL*/, double* var /*[T][d][n_theta] or NULL*/);
 int smc_host_transition_logpdf(int model_id, const double* raw, const double* xp /*[d]*/, const double* x /*[d]*/, double* out);

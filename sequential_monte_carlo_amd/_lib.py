@@ -35,7 +35,7 @@ EXPORTS = [
     "smc_ibis_summary", "smc_ibis_set_summaries", "smc_ibis_get_summaries", "smc_host_ibis_summary",
     "smc_ibis_window_ess", "smc_ibis_resample", "smc_ibis_theta_moments", "smc_ibis_get_moved", "smc_host_theta_moments",
     "smc_host_rw_factor_cov",
-    "smc_history_begin", "smc_history_len", "smc_history_get", "smc_history_end", "smc_smooth", "smc_host_transition_logpdf",
+    "smc_history_begin", "smc_history_len", "smc_history_get", "smc_history_put", "smc_history_end", "smc_smooth", "smc_host_transition_logpdf",
     "smc_host_smooth",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
@@ -198,6 +198,7 @@ def lib():
     L.smc_history_begin.argtypes = [h, C.c_int64]
     L.smc_history_len.argtypes = [h, C.POINTER(C.c_int64)]
     L.smc_history_get.argtypes = [h, C.c_int64, _dp, _dp]
+    L.smc_history_put.argtypes = [h, C.c_int64, _dp, _dp]
     L.smc_history_end.argtypes = [h]
     L.smc_smooth.argtypes = [h, _dp, _dp, _dp]
     L.smc_host_transition_logpdf.argtypes = [C.c_int, _dp, _dp, _dp, _dp]
@@ -805,6 +806,19 @@ class Handle:
         w = np.zeros((self.n_theta, self.n_x))
         check(lib().smc_history_get(self._h, int(t), _d(x), _d(w)))
         return x, w
+
+    def history_put(self, t, x=None, w=None):
+        """overwrite recorded step t with x [d][n_theta][n_x] and / or w [n_theta][n_x] (smc_history_put; None: left alone):
+        clouds that no filter run leaves, for the tests of the backward pass"""
+        if x is not None:
+            x = np.ascontiguousarray(x, dtype=np.float64)
+            if x.shape != (self.d, self.n_theta, self.n_x):
+                raise ValueError("x must be [d][n_theta][n_x]")
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.shape != (self.n_theta, self.n_x):
+                raise ValueError("w must be [n_theta][n_x]")
+        check(lib().smc_history_put(self._h, int(t), _d(x), _d(w)))
 
     def history_end(self):
         check(lib().smc_history_end(self._h))

@@ -85,6 +85,19 @@ extern "C" int smc_history_get(smc_handle h, int64_t t, double* x, double* w) {
     return SMC_OK;
 }
 
+// overwrites step t of the record (either part may be NULL): the way clouds that no filter run leaves reach the backward pass
+extern "C" int smc_history_put(smc_handle h, int64_t t, const double* x, const double* w) {
+    if (!h) return fail(SMC_EINVAL, "smc_history_put: NULL handle");
+    if (!h->hist.armed) return fail(SMC_ESTATE, "smc_history_put: the handle does not record (smc_history_begin)");
+    if (t < 0 || t >= h->hist.len) return fail(SMC_EINVAL, "smc_history_put: step out of range");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t nw = cloud_words(h);
+    if (x) HIPCHK(hipMemcpy(h->hist.d_x + (size_t)t * nw * (size_t)h->d, x, nw * (size_t)h->d * 8, hipMemcpyHostToDevice));
+    if (w) HIPCHK(hipMemcpy(h->hist.d_w + (size_t)t * nw, w, nw * 8, hipMemcpyHostToDevice));
+    return SMC_OK;
+}
+
 // ---- the backward pass ---------------------------------------------------------------------------------------------------
 namespace {
 struct SmoothPlan {

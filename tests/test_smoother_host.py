@@ -3,6 +3,7 @@ that share no arithmetic with the library (tests/smoother_reference.py).  No GPU
 import numpy as np
 import pytest
 
+import smoother_planted as P
 import smoother_reference as R
 
 EPS = 2.0 ** -52
@@ -135,6 +136,65 @@ def test_host_smooth_sharp_observation(L, ob, n, T):
         assert (w == 0).mean() > 0.5
     ws = check_against_reference(L, R.LG1D, raw, x, w)
     assert np.all(np.isfinite(ws))
+
+
+SHARP = [0.5, 1.0, 0.9, 1e-4, 0.0, 1.0]
+PLANTED = [(model, ROWS[model], name) for model in (R.LG1D, R.SV1D, R.UCSV3D) for name in P.ALIVE]
+PLANTED += [(R.LG1D, SHARP, name) for name in P.ON_ZERO + P.ALIVE]
+
+
+@pytest.mark.parametrize("n", [65, 300])
+@pytest.mark.parametrize("model,raw,name", PLANTED, ids=lambda v: v if isinstance(v, str) else ("sharp" if v is SHARP else None))
+def test_planted_clouds_against_longdouble_recursion(L, ob, model, raw, name, n):
+    """tests/smoother_planted.py: clouds no filter leaves (states that are not finite on zero-weight particles, two groups whose
+    cross terms underflow, a target far from every source, tied states, subnormal weights, one particle alive), host twin against
+    the long-double recursion with the bounds of every other record"""
+    T = 6
+    x, w = recorded_clouds(L, ob, model, raw, n, T)
+    assert np.all((w > 0).any(axis=1))
+    px, pw = P.variant(name, model, raw, x, w)
+    assert np.all((pw > 0).any(axis=1))
+    if name in P.ON_ZERO:
+        assert (pw == 0).mean() > 0.5 and not np.all(np.isfinite(px))
+    if name == "tiny_weights":
+        assert (pw[P.mid(T)] > 0).sum() >= 2 and np.sort(pw[P.mid(T)])[-2] < 2.0 ** -1022
+    if name == "one_alive":
+        assert (pw[P.mid(T)] > 0).sum() == 1
+    ref = R.ffbs_ref(model, raw, px, pw)
+    assert np.all(np.isfinite(ref.astype(np.float64)))                # the reference itself stays finite
+    ws = check_against_reference(L, model, raw, px, pw)
+    assert np.all(np.isfinite(ws)) and np.all(ws[pw == 0] == 0)
+    if name in P.ON_ZERO:                                             # left out whatever their states: the bits of the plain record
+        ws0, mean0, var0 = L.host_smooth(model, raw, x, w)
+        ws1, mean1, var1 = L.host_smooth(model, raw, px, pw)
+        assert np.array_equal(bits(ws0), bits(ws1)) and np.array_equal(bits(mean0), bits(mean1)) and np.array_equal(bits(var0), bits(var1))
+    if name == "far_apart":                                           # the planted distances do what they are there for
+        ts, d = max(T // 2 - 1, 0), R.DIM[model]
+        F = R.logf_ref(model, raw, [px[ts, r][:, None] for r in range(d)], [px[ts + 1, r][None, :] for r in range(d)])
+        group = (np.arange(n) // P.BLOCK) % 2
+        cross = group[:, None] != group[None, :]
+        assert np.all(np.isfinite(F.astype(np.float64)))
+        with np.errstate(divide="ignore"):
+            A = np.log(pw[ts].astype(R.LD))[:, None] + F
+        assert np.all((A - A.max(axis=0)[None, :])[cross] < -746)      # every cross term underflows against the row maximum: exp(-746) = 0
+        if raw is not SHARP:                                          # both groups are alive on both sides
+            assert all((pw[ts][group == g] > 0).any() and (pw[ts + 1][group == g] > 0).any() for g in (0, 1))
+        j = int(np.argmax(w[T - 1]))
+        Fl = R.logf_ref(model, raw, [px[T - 2, r] for r in range(d)], [px[T - 1, r, j] for r in range(d)])
+        assert np.all(Fl < -1000) and np.all(np.isfinite(Fl.astype(np.float64)))
+
+
+@pytest.mark.parametrize("n", [65, 300])
+@pytest.mark.parametrize("model", [R.LG1D, R.SV1D, R.UCSV3D])
+def test_planted_dead_steps(L, ob, model, n):
+    """a step at which every weight is 0, at the first, a middle and the last step: NaN everywhere, in the twin and the reference"""
+    T = 6
+    x, w = recorded_clouds(L, ob, model, ROWS[model], n, T)
+    for t_dead in P.dead_steps(T):
+        px, pw = P.dead_at(x, w, t_dead)
+        ws, mean, var = L.host_smooth(model, ROWS[model], px, pw)
+        assert np.all(np.isnan(ws)) and np.all(np.isnan(mean)) and np.all(np.isnan(var)), t_dead
+        assert np.all(np.isnan(R.ffbs_ref(model, ROWS[model], px, pw).astype(np.float64))), t_dead
 
 
 def test_rts_pin(L, ob):
