@@ -528,6 +528,42 @@ int smc_host_transition_logpdf(int model_id, const double* raw, const double* xp
 int smc_host_smooth(int model_id, const double* raw, int64_t T, int64_t n, const double* x /*[T][d][n]*/, const double* w /*[T][n]*/,
                     double* ws /*[T][n]*/, double* mean /*[T][d] or NULL*/, double* var /*[T][d] or NULL*/);
 
+/* ---- backward simulation: joint smoothing paths (FFBSi; Godsill, Doucet and West 2004) --------------------------------------
+ * smc_smooth gives the marginals p(x_t | y_1:T).  Whatever depends on two or more times at once (the smoothed change of the
+ * trend, the cycle as a path, lag covariances, the complete-data sums of a particle EM or Gibbs step) needs whole trajectories
+ * from p(x_1:T | y_1:T).  Backward simulation draws them by walking back through the recorded clouds: the index of path p at
+ * the last step is a draw from w_T, and the index at step t given the state x_{t+1} it chose is a draw from the weights
+ * proportional to w_t^l f(x_{t+1} | x_t^l).  Every step is an exact integer computation on the log-weights the smoother forms
+ * (csrc/smc_spec.h "backward simulation": the log-weights minus their maximum become integers on a 2^-40 grid, their integer
+ * sum S and ONE counter-based 64-bit uniform u per path and step select the smallest index whose running sum exceeds
+ * floor(u S / 2^64)), so path p is a function of the recorded clouds, the parameter row, the path seed and the filter's Philox
+ * stream id (smc_set_streams; its index by default) alone: the same bits from the device and from the host twin, for any
+ * number of paths, for a filter alone and inside a batch.  The marginal law of a path's index at step t, given the clouds, is
+ * the smoothed weight ws_t of smc_smooth (up to the 2^-40 grid).  Particles of weight 0 are never chosen, whatever their states.
+ *   smc_sample_paths   M paths per filter over the record of an armed handle, T = smc_history_len, with the parameter rows the
+ *                      device holds (they must be those the steps ran with).  idx [T][n_theta][M]: the particle of recorded step t
+ *                      that path p of filter th passes through; xs [T][d][n_theta][M]: its state, copied bit for bit from the
+ *                      record (either may be NULL).  counts [n_theta] (NULL: M everywhere): only the first counts[th] paths of
+ *                      filter th are drawn, the slots behind them read -1 and NaN; the drawn ones are those of a call with M
+ *                      everywhere.  A filter that collapsed at a recorded step (every weight 0 there) has -1 / NaN everywhere; a
+ *                      path whose target no live source reaches (every log-weight -inf) reads -1 / NaN from that step back.  Any
+ *                      proposal and either resampler.  It may be called again with other seeds and after more steps, and neither
+ *                      needs smc_smooth nor disturbs it (its scratch is its own).  Memory: idx and xs are T n_theta M entries on
+ *                      the device as well, so a batch wants a small M.  Cost: 2 M n_x T n_theta pair evaluations (two passes over M x n_x pairs
+ *                      at every recorded step; the last step, whose weights need no pair, runs the same kernels), measured
+ *                      in profiles/paths_cost.log.
+ *                      SMC_EINVAL: SMC_MODEL_UCSV_RB; a transition scale that is not a positive finite number; M outside
+ *                      [1, 2^30]; a count outside [0, M]; n_x > 2^20 (the integer sum of a step must stay below 2^61).
+ *                      SMC_ESTATE: the handle is not armed or nothing is recorded.  SMC_ENOMEM: the paths and the scratch cannot be
+ *                      allocated; the handle is as it was
+ *   smc_host_sample_paths  the same specification for ONE filter on the host (no GPU), the same bits: x [T][d][n], w [T][n],
+ *                      the filter's Philox stream id -> idx [T][M], xs [T][d][M] (or NULL).  SMC_EINVAL as smc_host_smooth, and
+ *                      for M < 1 and n > 2^20 */
+int smc_sample_paths(smc_handle h, int64_t M, uint64_t path_seed, const int32_t* counts /*[n_theta] or NULL*/,
+                     int32_t* idx /*[T][n_theta][M] or NULL*/, double* xs /*[T][d][n_theta][M] or NULL*/);
+int smc_host_sample_paths(int model_id, const double* raw, int64_t T, int64_t n, const double* x /*[T][d][n]*/, const double* w /*[T][n]*/,
+                          int64_t M, uint64_t path_seed, uint32_t stream, int32_t* idx /*[T][M]*/, double* xs /*[T][d][M] or NULL*/);
+
 /* ---- host-side helpers (no GPU needed) ---------------------------------------------------------*/
 /* simulate(rng, model, T) -> (x, y)                         src/state_space_models.jl:11-26 */
 int smc_simulate(int model_id, const double* raw, int64_t T, uint64_t seed, double* x /*[smc_simulate_dim][T] or NULL*/, double* y /*[T]*/);

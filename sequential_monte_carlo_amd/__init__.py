@@ -14,6 +14,6 @@ from .particles import (AffineGaussianProposal, OptimalProposal, bootstrap_filte
                         optimal_proposal, particle_filter, particle_filter_, resample, reweight, smoother, trend_moments)
 from .smc_samplers import (SMC, ThetaMap, density_tempered, estimated_trend, expected_parameters, filtered_state,  # noqa: F401
                            filtered_summaries, observation_dist, posterior_moments, quantile, rejuvenate_, resample_, smc2, smc2_run, smc2_step,
-                           smoothed_state)
+                           smoothed_paths, smoothed_state)
 
 __version__ = "0.1.0"

@@ -36,7 +36,7 @@ EXPORTS = [
     "smc_ibis_window_ess", "smc_ibis_resample", "smc_ibis_theta_moments", "smc_ibis_get_moved", "smc_host_theta_moments",
     "smc_host_rw_factor_cov",
     "smc_history_begin", "smc_history_len", "smc_history_get", "smc_history_put", "smc_history_end", "smc_smooth", "smc_host_transition_logpdf",
-    "smc_host_smooth",
+    "smc_host_smooth", "smc_sample_paths", "smc_host_sample_paths",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -203,6 +203,8 @@ def lib():
     L.smc_smooth.argtypes = [h, _dp, _dp, _dp]
     L.smc_host_transition_logpdf.argtypes = [C.c_int, _dp, _dp, _dp, _dp]
     L.smc_host_smooth.argtypes = [C.c_int, _dp, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp]
+    L.smc_sample_paths.argtypes = [h, C.c_int64, C.c_uint64, _i32p, _i32p, _dp]
+    L.smc_host_sample_paths.argtypes = [C.c_int, _dp, C.c_int64, C.c_int64, _dp, _dp, C.c_int64, C.c_uint64, C.c_uint32, _i32p, _dp]
     L.smc_last_error.restype = C.c_char_p
     L.smc_version.restype = C.c_char_p
     _lib = L
@@ -832,6 +834,38 @@ class Handle:
         var = np.zeros((T, self.d, self.n_theta)) if moments else None
         check(lib().smc_smooth(self._h, _d(ws), _d(mean), _d(var)))
         return ws, mean, var
+
+    def sample_paths(self, M, seed, counts=None, want_x=True):
+        """M backward-simulated paths per filter over the recorded steps (smc_sample_paths): (idx [T][n_theta][M] int32, xs
+        [T][d][n_theta][M] or None).  counts [n_theta]: only the first counts[th] paths of filter th are drawn, the other slots
+        read -1 / NaN"""
+        T, M = self.history_len(), int(M)
+        if M < 1:
+            raise ValueError("M must be positive")
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            if counts.shape != (self.n_theta,):
+                raise ValueError("counts must be [n_theta]")
+        idx = np.zeros((T, self.n_theta, M), dtype=np.int32)
+        xs = np.zeros((T, self.d, self.n_theta, M)) if want_x else None
+        check(lib().smc_sample_paths(self._h, M, int(seed), counts.ctypes.data_as(_i32p) if counts is not None else None,
+                                     idx.ctypes.data_as(_i32p), _d(xs)))
+        return idx, xs
+
+
+def host_sample_paths(model_id, raw, x, w, M, seed, stream=0, want_x=True):
+    """M backward-simulated paths of ONE filter by the specification on the host (smc_host_sample_paths; no GPU): x [T][d][n],
+    w [T][n] -> (idx [T][M] int32, xs [T][d][M] or None)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    d = lib().smc_model_dim(int(model_id))
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    T, n = w.shape
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(T, d, n) if d > 0 else np.ascontiguousarray(x, dtype=np.float64)
+    idx = np.zeros((T, max(int(M), 0)), dtype=np.int32)
+    xs = np.zeros((T, d, max(int(M), 0))) if want_x else None
+    check(lib().smc_host_sample_paths(int(model_id), _d(raw), T, n, _d(x), _d(w), int(M), int(seed), int(stream),
+                                      idx.ctypes.data_as(_i32p), _d(xs)))
+    return idx, xs
 
 
 def host_transition_logpdf(model_id, raw, xp, x):

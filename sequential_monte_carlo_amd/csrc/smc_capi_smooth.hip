@@ -1,8 +1,10 @@
 // smc_capi_smooth.hip -- the record of a step-by-step run (smc_history_*) and the FFBS particle smoother over it (smc_smooth):
-// forward filtering by the step kernels as they are, backward smoothing by the all-pairs kernels of smc_smooth_kernels.h.
+// forward filtering by the step kernels as they are, backward smoothing by the all-pairs kernels of smc_smooth_kernels.h, and
+// backward simulation over the same record (smc_sample_paths, smc_path_kernels.h).
 // Specification: smc_spec.h "the smoother"; the host twin (smc_host_smooth) lives in smc_util.hip.
 #include "smc_host.h"
 #include "smc_smooth_kernels.h"
+#include "smc_path_kernels.h"
 
 #include <cstring>
 #include <vector>
@@ -18,6 +20,7 @@ void history_free(smc_filter_s* h) {
     (void)hipFree(h->hist.d_x);   // (d_w lives in the same allocation)
     (void)hipFree(h->hist.d_ws);
     (void)hipFree(h->hist.d_tmp);
+    (void)hipFree(h->hist.d_path);
     h->hist = {};
 }
 
@@ -231,5 +234,127 @@ extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
             if (var) memcpy(var + (size_t)t * d * nt, mv.data() + (size_t)t * mom_words + d * nt, d * nt * 8);
         }
     }
+    return SMC_OK;
+}
+
+// ---- backward simulation ---------------------------------------------------------------------------------------------------
+namespace {
+struct PathPlan {
+    int nchunk;
+    size_t o_cur, o_pmax, o_psum, o_rmax, o_rows, o_dead, o_counts, o_idx, o_xs, bytes;   // offsets into hist.d_path, in bytes
+};
+// false: the sizes do not fit size_t arithmetic
+bool path_plan(const smc_filter_s* h, int64_t T, int64_t M, bool want_x, PathPlan& p) {
+    const size_t nt = (size_t)h->v.ntheta, d = (size_t)h->d, pw = nt * (size_t)M;
+    p.nchunk = (int)((h->v.n + SMOOTH_CH - 1) / SMOOTH_CH);
+    if (pw > ((size_t)1 << 56) / ((size_t)T * (d + 1)) || pw > ((size_t)1 << 56) / (size_t)p.nchunk) return false;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    p.o_cur = take(d * pw * 8);
+    p.o_pmax = take((size_t)p.nchunk * pw * 8);
+    p.o_psum = take((size_t)p.nchunk * pw * 8);
+    p.o_rmax = take(pw * 8);
+    p.o_rows = take(nt * sizeof(SmoothRow));
+    p.o_dead = take(nt * sizeof(int));
+    p.o_counts = take(nt * sizeof(int32_t));
+    p.o_idx = take((size_t)T * pw * 4);
+    p.o_xs = take(want_x ? (size_t)T * d * pw * 8 : 0);
+    p.bytes = off;
+    return true;
+}
+
+template <int MODEL>
+hipError_t path_step(const PathArgs& a, int threads, double* rowmax, hipStream_t s) {
+    hipError_t e;
+    const dim3 grid((unsigned)((a.M + threads - 1) / threads), (unsigned)a.ntheta, (unsigned)a.nchunk), g1((unsigned)((a.M + 255) / 256), (unsigned)a.ntheta);
+    hipLaunchKernelGGL((k_path_pairs<MODEL, 0>), grid, dim3(threads), 0, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (a.nmax == 1 && a.rmax == rowmax) {   // many chunks: the maximum once per path, as the smoother takes it once per target
+        hipLaunchKernelGGL(k_smooth_rowmax, g1, dim3(256), 0, s, a.M, a.ntheta, a.nchunk, a.pmax, rowmax);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((k_path_pairs<MODEL, 1>), grid, dim3(threads), 0, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (a.M * (int64_t)a.ntheta < PATH_WAVE_SELECT)   // few paths: one wave per path (four per workgroup)
+        hipLaunchKernelGGL((k_path_select_wave<MODEL>), dim3((unsigned)((a.M + 3) / 4), (unsigned)a.ntheta), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_path_select<MODEL>), dim3((unsigned)((a.M + 63) / 64), (unsigned)a.ntheta), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+}  // namespace
+
+extern "C" int smc_sample_paths(smc_handle h, int64_t M, uint64_t path_seed, const int32_t* counts, int32_t* idx, double* xs) {
+    if (!h) return fail(SMC_EINVAL, "smc_sample_paths: NULL handle");
+    if (h->model != MODEL_LG1D && h->model != MODEL_SV1D && h->model != MODEL_UCSV3D)
+        return fail(SMC_EINVAL, "smc_sample_paths: SMC_MODEL_UCSV_RB has no transition density of its state rows (m and P are functions of the "
+                                "whole path); draw the paths of a UCSV3D filter instead");
+    if (M < 1 || M > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_sample_paths: M must be in [1, 2^30]");
+    if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, "smc_sample_paths: nothing is recorded (smc_history_begin, then smc_init / smc_step)");
+    const FilterView& v = h->v;
+    const int64_t T = h->hist.len, n = v.n;
+    const size_t nw = cloud_words(h), nt = (size_t)v.ntheta, d = (size_t)h->d, pw = nt * (size_t)M;
+    if (n > PATH_MAX_N) return fail(SMC_EINVAL, "smc_sample_paths: more than 2^20 particles per filter (the integer weights of a step would not fit their sum)");
+    std::vector<int32_t> cnt(nt, (int32_t)M);
+    for (size_t m = 0; counts && m < nt; ++m) {
+        if (counts[m] < 0 || counts[m] > M) return fail(SMC_EINVAL, "smc_sample_paths: counts[" + std::to_string(m) + "] is outside [0, M]");
+        cnt[m] = counts[m];
+    }
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<Params> prm(nt);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(prm.data(), h->d_params, nt * sizeof(Params), hipMemcpyDeviceToHost));
+    std::vector<SmoothRow> rows(nt);
+    for (size_t m = 0; m < nt; ++m)
+        if (!smooth_row(h->model, prm[m].raw, rows[m]))
+            return fail(SMC_EINVAL, "smc_sample_paths: the transition scale of filter " + std::to_string(m) + " is not a positive finite number");
+    PathPlan p{};
+    if (!path_plan(h, T, M, xs != nullptr, p)) return fail(SMC_ENOMEM, "smc_sample_paths: paths of that many bytes cannot be allocated");
+    if (p.bytes > h->hist.path_bytes) {   // (the new block first: a failed allocation leaves the handle as it was)
+        char* blk = nullptr;
+        if (hipMalloc((void**)&blk, p.bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SMC_ENOMEM, "smc_sample_paths: hipMalloc of the paths and the scratch of the backward walk");
+        }
+        (void)hipFree(h->hist.d_path);
+        h->hist.d_path = blk;
+        h->hist.path_bytes = p.bytes;
+    }
+    char* base = h->hist.d_path;
+    double *cur = (double*)(base + p.o_cur), *pmax = (double*)(base + p.o_pmax), *rowmax = (double*)(base + p.o_rmax);
+    uint64_t* psum = (uint64_t*)(base + p.o_psum);
+    SmoothRow* d_rows = (SmoothRow*)(base + p.o_rows);
+    int* dead = (int*)(base + p.o_dead);
+    int32_t *d_counts = (int32_t*)(base + p.o_counts), *d_idx = (int32_t*)(base + p.o_idx);
+    double* d_xs = xs ? (double*)(base + p.o_xs) : nullptr;
+    hipStream_t s = h->stream;
+    HIPCHK(hipEventRecord(h->ev0, s));
+    HIPCHK(hipMemcpyAsync(d_rows, rows.data(), nt * sizeof(SmoothRow), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_counts, cnt.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(dead, 0, nt * sizeof(int), s));
+    hipLaunchKernelGGL(k_smooth_dead, dim3((unsigned)T, (unsigned)nt), dim3(256), 0, s, n, (int)nt, h->hist.d_w, dead);
+    HIPCHK(hipGetLastError());
+    // the smoother's rule: a launch of few workgroups is cut into tiles of one wave; the bits do not depend on it
+    const int64_t wg256 = ((M + 255) / 256) * (int64_t)nt * p.nchunk;
+    const int threads = wg256 >= 1024 ? 256 : 64;
+    const bool direct = p.nchunk <= SMOOTH_MAX_DIRECT;
+    for (int64_t t = T - 1; t >= 0; --t) {
+        PathArgs a{};
+        a.n = n; a.M = M; a.ntheta = (int)nt; a.nchunk = p.nchunk;
+        a.last = t == T - 1; a.t = (uint32_t)t; a.seed = path_seed;
+        a.x_t = h->hist.d_x + (size_t)t * nw * d; a.w_t = h->hist.d_w + (size_t)t * nw;
+        a.cur = cur; a.pmax = pmax; a.rmax = direct ? pmax : rowmax; a.nmax = direct ? p.nchunk : 1; a.psum = psum;
+        a.rows = d_rows; a.dead = dead; a.counts = d_counts; a.stream = h->d_stream;
+        a.idx_n = d_idx + (size_t)(t + 1 < T ? t + 1 : t) * pw; a.idx_t = d_idx + (size_t)t * pw;
+        a.xs_t = d_xs ? d_xs + (size_t)t * d * pw : nullptr;
+        hipError_t e = hipErrorInvalidValue;
+        if (h->model == MODEL_LG1D) e = path_step<MODEL_LG1D>(a, threads, rowmax, s);
+        else if (h->model == MODEL_SV1D) e = path_step<MODEL_SV1D>(a, threads, rowmax, s);
+        else e = path_step<MODEL_UCSV3D>(a, threads, rowmax, s);
+        HIPCHK(e);
+    }
+    int rc = finish_elapsed(h);
+    if (rc) return rc;
+    if (idx) HIPCHK(hipMemcpy(idx, d_idx, (size_t)T * pw * 4, hipMemcpyDeviceToHost));
+    if (xs) HIPCHK(hipMemcpy(xs, d_xs, (size_t)T * d * pw * 8, hipMemcpyDeviceToHost));
     return SMC_OK;
 }

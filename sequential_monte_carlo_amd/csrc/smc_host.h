@@ -116,6 +116,8 @@ struct smc_filter_s {
         double* d_tmp = nullptr;               // its scratch: chunk maxima and chunk partials [2][nchunk][ntheta][n] | logD [ntheta][n] |
         int64_t ws_cap = 0;                    //   partials of the moments [len][ntheta][nchunk] | rows [ntheta] | dead [ntheta]
         size_t tmp_bytes = 0;
+        char* d_path = nullptr;                // backward simulation (smc_sample_paths), its own block: cur | pmax | psum | rmax | rows |
+        size_t path_bytes = 0;                 //   dead | counts | idx [T][ntheta][M] | xs [T][d][ntheta][M]
     } hist;
     struct {   // PMMH rejuvenation (smc_capi_pmmh.hip): this handle holds the proposal filters
         smc::PmmhSpec spec{};

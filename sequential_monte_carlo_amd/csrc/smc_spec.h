@@ -1011,4 +1011,55 @@ inline double smooth_sum(int64_t n, F term) {
     return tot;
 }
 
+// ---- backward simulation: joint smoothing paths (FFBSi; Godsill, Doucet and West 2004) --------------------------
+// Inputs: the recorded clouds (x_t, w_t), t = 0..T-1, of one filter (w the dense weights), its SmoothRow, a path seed and the
+// filter's Philox stream id.  Path p (0-based) is a function of these alone: not of the number of paths, of the other paths,
+// of the batch or of any launch geometry.  For t = T-1 .. 0, with j = idx[t+1][p] when t < T-1:
+//   a source l is live iff w_t^l > 0 (NaN compares false)
+//   b_l = sp_log(w_t^l)                                    at the last step
+//   b_l = logf_pair(k, m_l, s_l, g_l, x_{t+1}^j),  (m_l, s_l, c_l) = logf_source(x_t^l),  g_l = sp_log(w_t^l) + c_l   before it
+//         (bit for bit the a_lj of the smoother)
+//   M_p = max of b_l over the live sources, taken with b > M ? b : M from -inf (a NaN is dropped; exact in any order)
+//   q_l = path_weight(b_l, M_p): with e = b_l - M_p and (pp, kk) = sp_exp_parts(e), fix_weight(pp, kk, PATH_BITS) when e <= 0,
+//         else 0 (a NaN b_l, an infinite M_p); 0 for a source that is not live.  The heaviest source has e = 0: q = 2^PATH_BITS
+//   S   = sum of q_l, an INTEGER sum (exact in any order and any split); n <= PATH_MAX_N keeps it below 2^61
+//   u   = a 64-bit half of draw(path_seed, p >> 1, stream, t, SLOT_PATH): v[1] << 32 | v[0] for an even p, v[3] << 32 | v[2] for
+//         an odd one (the convention of the outer level's pick numbers)
+//   r   = the high 64 bits of the 128-bit product u S
+//   idx[t][p] = the smallest i with C_i > r, C_i = sum_{l <= i} q_l in ascending index order; the path's state is x_t^i, copied
+// A path ends where S = 0 (no live source reaches the target: M_p = -inf): index -1 and NaN states there and at every earlier
+// step.  A filter that collapsed at any recorded step (every weight 0 there; the smoother's dead flag) has -1 / NaN everywhere.
+// The marginal law of idx[t][p] given the clouds is the smoothed weight ws_t of the smoother, up to the 2^-PATH_BITS grid.
+constexpr int PATH_BITS = 40;
+constexpr uint32_t SLOT_PATH = 35u;               // no other draw uses it (the step, PMMH and outer-level slots end at 34)
+constexpr int64_t PATH_MAX_N = (int64_t)1 << 20;  // particles per filter: S < 2^61
+SMC_HD uint64_t path_weight(double b, double M) {
+    const double e = b - M;
+    double kk;
+    const double pp = sp_exp_parts(e, kk);
+#if defined(__HIP_DEVICE_COMPILE__)
+    // branch-free: the exponent is clamped to fix_weight's range BEFORE the conversion (a NaN becomes the lower end), the value
+    // is rounded and converted by one addition as in fix_weight_i, and the two conditions select afterwards
+    double kc = kk >= -(double)(PATH_BITS + 2) ? kk : -(double)(PATH_BITS + 2);
+    kc = kc <= 0.0 ? kc : 0.0;
+    const uint64_t q = d2bits(scale2(pp, PATH_BITS + (int)kc) + 0x1p52) & 0x000fffffffffffffULL;
+    return (e <= 0.0 && kk >= -(double)(PATH_BITS + 2)) ? q : 0;
+#else
+    if (!(e <= 0.0)) return 0;
+    return fix_weight(pp, kk, PATH_BITS);
+#endif
+}
+// the 64-bit uniform of path p at step t
+SMC_HD uint64_t path_uniform(uint64_t seed, int64_t p, uint32_t stream, uint32_t t) {
+    const u32x4 v = draw(seed, (uint32_t)(p >> 1), stream, t, SLOT_PATH);
+    return (p & 1) ? ((uint64_t)v.v[3] << 32) | v.v[2] : ((uint64_t)v.v[1] << 32) | v.v[0];
+}
+SMC_HD uint64_t mulhi64(uint64_t a, uint64_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul64hi(a, b);
+#else
+    return (uint64_t)(((unsigned __int128)a * b) >> 64);
+#endif
+}
+
 }  // namespace smc

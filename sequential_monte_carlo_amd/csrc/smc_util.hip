@@ -554,3 +554,79 @@ extern "C" int smc_host_smooth(int model_id, const double* raw, int64_t T, int64
             host_smooth_moments(d, n, x + (size_t)t * d * n, ws + (size_t)t * n, dead, mean + (size_t)t * d, var + (size_t)t * d);
     return SMC_OK;
 }
+
+// ---- backward simulation on the host (smc_spec.h "backward simulation"): the specification as plain loops, one filter --------
+template <int MODEL>
+static void host_paths_t(const SmoothRow& k, int64_t T, int64_t n, const double* x, const double* w, int64_t M, uint64_t seed, uint32_t stream,
+                         int32_t* idx, double* xs) {
+    constexpr int D = model_dim<MODEL>::value;
+    const size_t sx = (size_t)D * n;
+    const double nan = bits2d(0x7ff8000000000000ULL);
+    bool dead = false;   // a filter that collapsed at a recorded step: no path
+    for (int64_t t = 0; t < T && !dead; ++t) {
+        bool any = false;
+        for (int64_t i = 0; i < n; ++i) any = any || w[(size_t)t * n + i] > 0.0;
+        dead = !any;
+    }
+    std::vector<double> m((size_t)D * n), s((size_t)n), g((size_t)n), b((size_t)n);
+    for (int64_t t = T - 1; t >= 0; --t) {
+        const bool last = t == T - 1;
+        const double *xt = x + (size_t)t * sx, *xn = xt + sx, *wt = w + (size_t)t * n;
+        for (int64_t l = 0; l < n; ++l) {
+            if (!(wt[l] > 0.0)) continue;
+            if (last) { g[l] = sp_log(wt[l]); continue; }
+            double xp[D], ml[D], c;
+            for (int r = 0; r < D; ++r) xp[r] = xt[(size_t)r * n + l];
+            logf_source<MODEL>(k, xp, ml, s[l], c);
+            for (int r = 0; r < D; ++r) m[(size_t)r * n + l] = ml[r];
+            g[l] = sp_log(wt[l]) + c;
+        }
+        for (int64_t p = 0; p < M; ++p) {
+            int64_t pick = -1;
+            const int64_t j = last ? 0 : idx[(size_t)(t + 1) * M + p];
+            if (!dead && j >= 0) {
+                double Mx = -inf();
+                for (int64_t l = 0; l < n; ++l) {
+                    if (!(wt[l] > 0.0)) continue;
+                    if (last) b[l] = g[l];
+                    else {
+                        double ml[D], xj[D];
+                        for (int r = 0; r < D; ++r) { ml[r] = m[(size_t)r * n + l]; xj[r] = xn[(size_t)r * n + j]; }
+                        b[l] = logf_pair<MODEL>(k, ml, s[l], g[l], xj);
+                    }
+                    Mx = b[l] > Mx ? b[l] : Mx;
+                }
+                uint64_t S = 0;
+                for (int64_t l = 0; l < n; ++l)
+                    if (wt[l] > 0.0) S += path_weight(b[l], Mx);
+                if (S) {
+                    const uint64_t r = mulhi64(path_uniform(seed, p, stream, (uint32_t)t), S);
+                    uint64_t C = 0;
+                    for (int64_t l = 0; l < n; ++l) {
+                        if (!(wt[l] > 0.0)) continue;
+                        C += path_weight(b[l], Mx);
+                        if (C > r) { pick = l; break; }
+                    }
+                }
+            }
+            idx[(size_t)t * M + p] = (int32_t)pick;
+            if (xs)
+                for (int r = 0; r < D; ++r) xs[((size_t)t * D + r) * M + p] = pick >= 0 ? xt[(size_t)r * n + pick] : nan;
+        }
+    }
+}
+
+extern "C" int smc_host_sample_paths(int model_id, const double* raw, int64_t T, int64_t n, const double* x, const double* w, int64_t M,
+                                     uint64_t path_seed, uint32_t stream, int32_t* idx, double* xs) {
+    if (!raw || !x || !w || !idx) return fail(SMC_EINVAL, "smc_host_sample_paths: NULL argument");
+    if (T < 1 || n < 1) return fail(SMC_EINVAL, "smc_host_sample_paths: T and n must be positive");
+    if (M < 1) return fail(SMC_EINVAL, "smc_host_sample_paths: M must be positive");
+    if (n > PATH_MAX_N) return fail(SMC_EINVAL, "smc_host_sample_paths: more than 2^20 particles");
+    SmoothRow k;
+    if (!smooth_row(model_id, raw, k))
+        return fail(SMC_EINVAL, "smc_host_sample_paths: no transition density for this family, or a transition scale that is not positive and finite");
+    if (model_id == MODEL_LG1D) host_paths_t<MODEL_LG1D>(k, T, n, x, w, M, path_seed, stream, idx, xs);
+    else if (model_id == MODEL_SV1D) host_paths_t<MODEL_SV1D>(k, T, n, x, w, M, path_seed, stream, idx, xs);
+    else host_paths_t<MODEL_UCSV3D>(k, T, n, x, w, M, path_seed, stream, idx, xs);
+    return SMC_OK;
+}

@@ -310,7 +310,21 @@ def log_likelihood(N, y, model, seed=None, seg=0, device=0, streams=None, ancest
     return Particles(f), Weights(f), f.out(logZ)
 
 
-def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="multinomial", proposal=None, weights=False, rows=None):
+def _path_seed(seed):
+    """the default path seed of a filter seed: another 64-bit word, so that the walk's draws are not the filter's"""
+    return (int(seed) * 0x9E3779B97F4A7C15 + 0xBAC4) & 0xFFFFFFFFFFFFFFFF
+
+
+def _paths_out(idx, xs, single):
+    """sample_paths' arrays in the shapes of s["x"]: index [T][M], states [T][M] or [T][M][d]; a batch axis follows T"""
+    xs = np.moveaxis(xs, 1, -1)                                        # [T][n_theta][M][d]
+    if xs.shape[-1] == 1:
+        xs = xs[..., 0]
+    return (idx[:, 0], xs[:, 0]) if single else (idx, xs)
+
+
+def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="multinomial", proposal=None, weights=False, rows=None,
+             paths=0, path_seed=None, path_counts=None, smooth=True):
     """x, w, logZ, s = smoother(N, y, model): the particle filter of log_likelihood run step by step with its clouds recorded on
     the device, then the FFBS backward pass over them (forward filtering, backward smoothing).  x, w, logZ are the
     filter's, as log_likelihood returns them; s describes p(x_t | y_1:T):
@@ -319,6 +333,13 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
         s["logmu"], s["ess"]        the filter's per-step log-likelihood increments and effective sample sizes, [T] or [T][n_theta]
         s["weights"], s["x"]        (weights=True) the smoothed weights [T][N] and the recorded clouds [T][N] or [T][N][d] they
                                     belong to (batch axis after T)
+        s["paths"], s["path_index"] (paths=M > 0) M trajectories drawn from p(x_1:T | y_1:T) by backward simulation:
+                                    their states [T][M] or [T][M][d] and the particles they pass through [T][M] (int32; batch
+                                    axis after T).  Unlike the marginals they carry the dependence between times: differences,
+                                    lag covariances, whole-path functionals.  path_seed: the seed of the walk's draws (default:
+                                    derived from the filter seed); path_counts [n_theta]: draw only that many paths of each filter
+                                    (the other slots read -1 / NaN); smooth=False skips the backward pass of the marginals (no
+                                    s["mean"], s["var"]).  A batch holds T n_theta M entries: keep M small there.
     The backward pass costs 2 N^2 (T - 1) transition densities per filter.  Any proposal, either resampler; MarginalUCSV has no
     smoother (its state rows have no transition density): smooth a UCSV filter.
     rows=(model id, parameter rows [n_theta][n_raw]) with model=None: a batch given as rows (what the samplers hold)."""
@@ -337,12 +358,16 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
         for t in range(1, T):
             lm[t], es[t] = h.step(float(y[t]))
         logZ = h.logZ()[0]
-        ws, mean, var = h.smooth(weights=weights, moments=True)
         s = {}
-        mean, var = np.moveaxis(mean, 1, -1), np.moveaxis(var, 1, -1)      # [T][n_theta][d]
-        if mean.shape[-1] == 1:
-            mean, var = mean[..., 0], var[..., 0]
-        s["mean"], s["var"] = (mean[:, 0], var[:, 0]) if f.single else (mean, var)
+        if smooth or weights:
+            ws, mean, var = h.smooth(weights=weights, moments=True)
+            mean, var = np.moveaxis(mean, 1, -1), np.moveaxis(var, 1, -1)      # [T][n_theta][d]
+            if mean.shape[-1] == 1:
+                mean, var = mean[..., 0], var[..., 0]
+            s["mean"], s["var"] = (mean[:, 0], var[:, 0]) if f.single else (mean, var)
+        if paths:
+            idx, xp = h.sample_paths(int(paths), _path_seed(seed) if path_seed is None else int(path_seed), counts=path_counts)
+            s["path_index"], s["paths"] = _paths_out(idx, xp, f.single)
         s["logmu"], s["ess"] = (lm[:, 0], es[:, 0]) if f.single else (lm, es)
         if weights:
             xs = np.array([h.history_get(t)[0] for t in range(T)])        # [T][d][n_theta][N]

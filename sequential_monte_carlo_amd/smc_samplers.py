@@ -602,6 +602,54 @@ def smoothed_state(smc, y, N=None, max_bytes=2 ** 31, seed=None):
     return mean, within + between
 
 
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def smoothed_paths(smc, y, M, N=None, max_bytes=2 ** 31, seed=None):
+    """M trajectories [T][M] ([T][M][d] for a state of d coordinates) from p(x_1:T | y_1:T) integrated over the sampler's current
+    parameter cloud, by backward simulation (particles.smoother(paths=...)): the parameter particle of every path
+    is drawn from omega through the library's own outer resampler (host_outer_resample: M ancestors in ascending order, so the
+    paths of one parameter particle are neighbours), which gives a count per parameter particle; fresh batched recorded filters
+    (N particles each, default the sampler's N) run only over the parameter particles with a positive count, in blocks whose
+    record and paths stay under max_bytes, and filter m draws its count of paths.  Filter m uses Philox stream m, so the result
+    does not depend on the blocks; particles with omega = 0 are never drawn.  seed: the Philox seed of the filters, of the
+    ancestors and of the walk (default: derived from the sampler's seed; the sampler's own state is not touched).
+    IBIS is out of scope: its exact smoother is RTS, a different feature."""
+    if isinstance(smc, IBIS):
+        raise TypeError("smoothed_paths: IBIS is out of scope: its exact smoother is RTS, a different feature")
+    from .particles import smoother
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    M = int(M)
+    if M < 1:
+        raise ValueError("M must be positive")
+    N = smc.N if N is None else int(N)
+    seed = (((smc.seed << 20) | 0xBAC45) if seed is None else int(seed)) & _U64       # (one 64-bit word for the filters as well)
+    smc._sync_outer()
+    anc = np.asarray(_lib.host_outer_resample(smc.logw, M, (seed + 1) & _U64), dtype=np.int64)     # ascending
+    counts = np.bincount(anc, minlength=smc.M).astype(np.int32)
+    used = np.flatnonzero(counts)
+    mid, raw = _rows(smc._models(smc.theta))
+    d = _lib.lib().smc_model_dim(int(mid))
+    out = np.zeros((y.size, M, d))
+    first = np.concatenate([[0], np.cumsum(counts)])                  # path slots of parameter particle m: first[m] .. first[m + 1]
+    b0 = 0
+    while b0 < used.size:                                             # greedy blocks: every filter of a block holds max-count slots
+        b1, cmax = b0, 0
+        while b1 < used.size:
+            c = max(cmax, int(counts[used[b1]]))
+            if b1 > b0 and (b1 + 1 - b0) * y.size * (N * (d + 1) * 8 + c * (4 + 8 * d)) > int(max_bytes):
+                break
+            b1, cmax = b1 + 1, c
+        ms = used[b0:b1]
+        _, _, _, s = smoother(N, y, None, rows=(int(mid), raw[ms]), seed=seed, device=getattr(smc.backend, "device", 0),
+                              streams=ms.astype(np.uint32), paths=cmax, path_seed=(seed + 2) & _U64, path_counts=counts[ms], smooth=False)
+        xs = s["paths"].reshape(y.size, ms.size, cmax, d)
+        for k, m in enumerate(ms):
+            out[:, first[m]:first[m + 1]] = xs[:, k, :counts[m]]
+        b0 = b1
+    return out[..., 0] if d == 1 else out
+
+
 def _integrate(w, rows):
     """[M][np + 1] per-filter (quantiles | variance) rows of every rank -> their omega-weighted means (quantiles [np], variance);
     the products summed over the parameter particles in index order (one definition for every caller: no BLAS in between).
