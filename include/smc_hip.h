@@ -458,6 +458,52 @@ int smc_ibis_resample(void* h, uint64_t seed, int32_t* a_out /*[n_theta] or NULL
 int smc_ibis_theta_moments(void* h, int weighted, double* mean /*[d_theta]*/, double* cov /*[d_theta][d_theta]*/);
 int smc_host_theta_moments(const double* theta, const double* logw, int64_t M, int d, int weighted, double* mean, double* cov);
 int smc_ibis_get_moved(void* h, uint8_t* moved /*[n_theta]*/);
+/* The RTS smoother of an IBIS cloud and its backward-sampled paths (Rauch, Tung and Striebel 1965).  smc_ibis_summary gives
+ * the filtered state p(x_t | y_1:t) integrated over the cloud; for a linear-Gaussian row the smoothed state p(x_t | y_1:T)
+ * is exact as well: one backward recursion per parameter particle over its own filtered record, O(T) per particle, nothing
+ * is a Monte-Carlo estimate.  Per particle, with (xf_t, Sf_t) the state kalman_filter leaves after step t from (x0, sigma0)
+ * under the handle's predict_first:
+ *     xs_T = xf_T, Ps_T = Sf_T;   Sp = A^2 Sf_t + Q,  G = Sf_t A / Sp,  V = Sf_t Q / Sp  (Sp = 0: G = 0, V = Sf_t),
+ *     xs_t = xf_t + G (xs_{t+1} - A xf_t),   Ps_t = V + G^2 Ps_{t+1}    (a sum of non-negative terms)
+ * and per period the cloud is integrated exactly as smc_ibis_summary does at ahead = 0, with (xs_t, Ps_t) in the place of
+ * (x, Sigma) and the particle's own logw: the order of every operation is fixed by csrc/smc_spec.h ("the RTS smoother of an
+ * IBIS cloud"), so the device, the host twin and any launch geometry give the same bits.  The handle is read and never
+ * written; the device memory of a call (the record, 16 T n_theta bytes, and 128 T ceil(n_theta / 64) bytes of chunk records)
+ * is allocated by the call and freed before it returns.  Cost: profiles/ibis_smoother_cost.log.
+ *   smc_ibis_smooth        re-filters y[0:T) for every particle of the committed cloud, walks back, and reduces every period:
+ *                          out [T][8] = rows of (y, Sigma, between, xbar, Sbar, between_x, K, D) as smc_ibis_summary names
+ *                          them - the smoothed fitted observation and the smoothed state; row T-1 is the filtered cloud after
+ *                          y[0:T).  xs, Ps [T][n_theta]: the smoothed mean and variance per particle, or NULL.  A particle
+ *                          whose logw is -inf or NaN contributes nothing whatever its row; NaN rows when none is alive.
+ *                          SMC_EINVAL: T < 1.  SMC_ESTATE: no theta yet, or a window is pending (smc_ibis_commit first).
+ *                          SMC_ENOMEM: the record cannot be allocated; the handle is as it was
+ *   smc_ibis_sample_paths  Mp trajectories from p(x_1:T | y_1:T, theta), path p under the row of parameter particle which[p]
+ *                          (the caller draws `which` from the outer weights, smc_host_outer_resample): x_T = xf_T +
+ *                          sqrt(Sf_T) z, x_t = xf_t + G (x_{t+1} - A xf_t) + sqrt(V) z, with z the Box-Muller normal of the
+ *                          Philox draw keyed by (path_seed, p >> 1, stream which[p], t, a slot no other draw uses), z0 for an
+ *                          even p and z1 for an odd one.  paths [T][Mp].  Path p is a function of (row, y, path_seed, p,
+ *                          which[p]) alone.  SMC_EINVAL: T < 1, Mp < 1, a which entry outside [0, n_theta).  SMC_ESTATE and
+ *                          SMC_ENOMEM as above
+ *   smc_kalman_smooth      the per-row half without a handle, the counterpart of smc_kalman_log_likelihood: raw [n_theta][6]
+ *                          = (A,B,Q,R,x0,sigma0) -> xs, Ps [T][n_theta], bit for bit the xs, Ps of smc_ibis_smooth for a cloud
+ *                          of these rows
+ *   smc_host_ibis_smooth   the same specification on the host (no GPU), the same bits: rows [M][6], logw [M] -> out [T][8];
+ *                          xs, Ps [T][M] or NULL; xf, Sf [T][M] or NULL: the filtered record the backward pass ran over
+ *   smc_host_ibis_sample_paths  likewise for the paths; z [T][Mp] or NULL: the normal every entry used
+ *   smc_ibis_last_elapsed_ms  what the kernels of the last completed smc_ibis_smooth / smc_ibis_sample_paths call of this handle
+ *                          took, by device events on its stream (allocation and copies excluded): the measurement behind
+ *                          profiles/ibis_smoother_cost.log, as smc_last_elapsed_ms is for a filter handle.  SMC_ESTATE: no such call */
+int smc_ibis_smooth(void* h, const double* y, int64_t T, double* out /*[T][8]*/, double* xs /*[T][n_theta] or NULL*/,
+                    double* Ps /*[T][n_theta] or NULL*/);
+int smc_ibis_sample_paths(void* h, const double* y, int64_t T, int64_t Mp, uint64_t path_seed, const int32_t* which /*[Mp]*/,
+                          double* paths /*[T][Mp]*/);
+int smc_ibis_last_elapsed_ms(void* h, double* ms);
+int smc_kalman_smooth(const double* raw /*[n_theta][6]*/, int64_t n_theta, const double* y, int64_t T, int predict_first,
+                      double* xs /*[T][n_theta]*/, double* Ps /*[T][n_theta]*/, int device);
+int smc_host_ibis_smooth(const double* rows /*[M][6]*/, const double* logw /*[M]*/, int64_t M, const double* y, int64_t T, int predict_first,
+                         double* out /*[T][8]*/, double* xs /*or NULL*/, double* Ps /*or NULL*/, double* xf /*or NULL*/, double* Sf /*or NULL*/);
+int smc_host_ibis_sample_paths(const double* rows, int64_t M, const double* y, int64_t T, int predict_first, int64_t Mp, uint64_t path_seed,
+                               const int32_t* which, double* paths /*[T][Mp]*/, double* z /*[T][Mp] or NULL*/);
 /* filtered mean and variance of every state coordinate under the current weights, on the device
  * (README.md:41,51 summaries; src/plotting_utils.jl:116-124 estimated_trend). mean, var: [d][n_theta].
  * Definition: StatsBase's uncorrected weighted moments with the dense weights w of smc_get_state, mean = sum w x and

@@ -7,7 +7,8 @@ There is no CPU fallback: importing works anywhere, running a filter needs the G
 """
 from .distributions import LogNormal, Normal, TruncatedNormal, Uniform, product_distribution  # noqa: F401
 from .ibis import IBIS  # noqa: F401
-from .kalman_filter import log_likelihood_kalman  # noqa: F401
+from .ibis import rts_quantile, rts_smoothed_paths, rts_smoothed_state  # noqa: F401
+from .kalman_filter import kalman_smoother, log_likelihood_kalman  # noqa: F401
 from .models import (UCSV, LinearModel, MarginalUCSV, StateSpaceModel, StochasticVolatility, UnivariateLinearGaussian,  # noqa: F401
                      simulate, unobserved_components, unobserved_components_stochastic_volatility)
 from .particles import (AffineGaussianProposal, OptimalProposal, bootstrap_filter, bootstrap_filter_, log_likelihood, normalize,  # noqa: F401

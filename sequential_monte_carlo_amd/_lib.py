@@ -35,6 +35,7 @@ EXPORTS = [
     "smc_ibis_summary", "smc_ibis_set_summaries", "smc_ibis_get_summaries", "smc_host_ibis_summary",
     "smc_ibis_window_ess", "smc_ibis_resample", "smc_ibis_theta_moments", "smc_ibis_get_moved", "smc_host_theta_moments",
     "smc_host_rw_factor_cov",
+    "smc_ibis_smooth", "smc_ibis_sample_paths", "smc_ibis_last_elapsed_ms", "smc_kalman_smooth", "smc_host_ibis_smooth", "smc_host_ibis_sample_paths",
     "smc_history_begin", "smc_history_len", "smc_history_get", "smc_history_put", "smc_history_end", "smc_smooth", "smc_host_transition_logpdf",
     "smc_host_smooth", "smc_sample_paths", "smc_host_sample_paths",
 ]
@@ -193,6 +194,12 @@ def lib():
     L.smc_ibis_resample.argtypes = [h, C.c_uint64, _i32p]
     L.smc_ibis_theta_moments.argtypes = [h, C.c_int, _dp, _dp]
     L.smc_ibis_get_moved.argtypes = [h, C.POINTER(C.c_uint8)]
+    L.smc_ibis_smooth.argtypes = [h, _dp, C.c_int64, _dp, _dp, _dp]
+    L.smc_ibis_sample_paths.argtypes = [h, _dp, C.c_int64, C.c_int64, C.c_uint64, _i32p, _dp]
+    L.smc_ibis_last_elapsed_ms.argtypes = [h, _dp]
+    L.smc_kalman_smooth.argtypes = [_dp, C.c_int64, _dp, C.c_int64, C.c_int, _dp, _dp, C.c_int]
+    L.smc_host_ibis_smooth.argtypes = [_dp, _dp, C.c_int64, _dp, C.c_int64, C.c_int, _dp, _dp, _dp, _dp, _dp]
+    L.smc_host_ibis_sample_paths.argtypes = [_dp, C.c_int64, _dp, C.c_int64, C.c_int, C.c_int64, C.c_uint64, _i32p, _dp, _dp]
     L.smc_host_theta_moments.argtypes = [_dp, _dp, C.c_int64, C.c_int, C.c_int, _dp, _dp]
     L.smc_host_rw_factor_cov.argtypes = [_dp, C.c_int, _dp, _ip]
     L.smc_history_begin.argtypes = [h, C.c_int64]
@@ -264,6 +271,15 @@ def kalman_log_likelihood(raw, y, predict_first=False, device=0):
     out = np.zeros((raw.shape[0], 3))
     check(lib().smc_kalman_log_likelihood(_d(raw), raw.shape[0], _d(y), y.size, int(predict_first), _d(out), device))
     return out
+
+
+def kalman_smooth(raw, y, predict_first=False, device=0):
+    """Batched exact RTS smoother of LG1D rows (smc_kalman_smooth): (xs, Ps), each [T][n_theta]."""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1, 6)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    xs, Ps = np.zeros((y.size, raw.shape[0])), np.zeros((y.size, raw.shape[0]))
+    check(lib().smc_kalman_smooth(_d(raw), raw.shape[0], _d(y), y.size, int(bool(predict_first)), _d(xs), _d(Ps), int(device)))
+    return xs, Ps
 
 
 def device_math(which, a, b=None, device=0):
@@ -905,6 +921,33 @@ def host_ibis_summary(rows, x, S, logw, ahead=0):
     return out
 
 
+def host_ibis_smooth(rows, logw, y, predict_first=False, states=False, filtered=False):
+    """the RTS smoother of a cloud of LG1D rows [M][6] with outer log-weights logw over y (smc_host_ibis_smooth: the device's
+    specification on the host; no GPU) -> out [T][8], the rows of host_ibis_summary per period; with states also xs, Ps [T][M];
+    with filtered also the filtered record xf, Sf [T][M] the backward pass ran over"""
+    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 6)
+    logw, y = np.ascontiguousarray(logw, dtype=np.float64), np.ascontiguousarray(y, dtype=np.float64).ravel()
+    M, T = rows.shape[0], y.size
+    assert logw.size == M
+    out = np.zeros((T, 8))
+    xs, Ps = (np.zeros((T, M)), np.zeros((T, M))) if states else (None, None)
+    xf, Sf = (np.zeros((T, M)), np.zeros((T, M))) if filtered else (None, None)
+    check(lib().smc_host_ibis_smooth(_d(rows), _d(logw), M, _d(y), T, int(bool(predict_first)), _d(out), _d(xs), _d(Ps), _d(xf), _d(Sf)))
+    return (out,) + ((xs, Ps) if states else ()) + ((xf, Sf) if filtered else ()) if states or filtered else out
+
+
+def host_ibis_sample_paths(rows, y, which, path_seed, predict_first=False, want_z=False):
+    """paths [T][Mp] of smc_host_ibis_sample_paths: path p under row which[p] (no GPU); with want_z also the normals z [T][Mp]"""
+    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 6)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    which = np.ascontiguousarray(which, dtype=np.int32).ravel()
+    paths = np.zeros((y.size, which.size))
+    z = np.zeros((y.size, which.size)) if want_z else None
+    check(lib().smc_host_ibis_sample_paths(_d(rows), rows.shape[0], _d(y), y.size, int(bool(predict_first)), which.size, int(path_seed),
+                                           which.ctypes.data_as(_i32p), _d(paths), _d(z)))
+    return (paths, z) if want_z else paths
+
+
 class IbisHandle:
     """The device half of the IBIS sampler (smc_ibis_*): M parameter particles with their exact Kalman state, resident on one
     GPU.  d: parameter dimension; families / pars: the prior (distributions.py spec()); raw_from / raw_const: ThetaMap to LG1D rows."""
@@ -1016,6 +1059,29 @@ class IbisHandle:
         out = np.zeros(8)
         check(lib().smc_ibis_summary(self._h, int(ahead), _d(out)))
         return out
+
+    def smooth(self, y, states=False):
+        """the RTS smoother of the committed cloud over y (smc_ibis_smooth): out [T][8], the rows of summary() per period for the
+        smoothed state; with states also xs, Ps [T][M] per particle.  The handle is not changed."""
+        y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        out = np.zeros((y.size, 8))
+        xs, Ps = (np.zeros((y.size, self.M)), np.zeros((y.size, self.M))) if states else (None, None)
+        check(lib().smc_ibis_smooth(self._h, _d(y), y.size, _d(out), _d(xs), _d(Ps)))
+        return (out, xs, Ps) if states else out
+
+    def sample_paths(self, y, which, path_seed):
+        """paths [T][Mp] from p(x_1:T | y_1:T), path p under the row of parameter particle which[p] (smc_ibis_sample_paths)"""
+        y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        which = np.ascontiguousarray(which, dtype=np.int32).ravel()
+        paths = np.zeros((y.size, which.size))
+        check(lib().smc_ibis_sample_paths(self._h, _d(y), y.size, which.size, int(path_seed), which.ctypes.data_as(_i32p), _d(paths)))
+        return paths
+
+    def last_elapsed_ms(self):
+        """device-event time of the kernels of the last smooth / sample_paths call (smc_ibis_last_elapsed_ms)"""
+        ms = C.c_double()
+        check(lib().smc_ibis_last_elapsed_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def set_summaries(self, on, ahead=0):
         """record the row of summaries after every step of the windows that follow (smc_ibis_set_summaries)"""

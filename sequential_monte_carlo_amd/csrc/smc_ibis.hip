@@ -2,6 +2,7 @@
 // parameter particles with their exact Kalman state on the device, and the launches of smc_ibis_kernels.h.
 #include "smc_host.h"
 #include "smc_ibis_kernels.h"
+#include "smc_ibis_smooth_kernels.h"
 
 #include <cmath>
 #include <cstring>
@@ -48,6 +49,7 @@ struct smc_ibis_s {
     int32_t* d_cnt = nullptr;                        // [M] draws per particle
     double* d_mpart = nullptr;                       // [THETA_MOM_NTRI][nchunk] chunk sums of the moments
     double* d_mom = nullptr;                         // [IBIS_MOM_N]
+    double rts_ms = -1.0;                            // device-event time of the kernels of the last smooth / sample_paths call
 };
 typedef smc_ibis_s* ibis_t;
 
@@ -610,6 +612,199 @@ extern "C" int smc_ibis_get(void* hp, double* theta, double* x, double* S, doubl
         const int d = h->spec.d;
         for (size_t m = 0; m < M; ++m)
             for (int i = 0; i < d; ++i) theta[m * d + i] = pad[m * MAX_DTHETA + i];
+    }
+    return SMC_OK;
+}
+
+// ---- the RTS smoother of the cloud and its backward-sampled paths (smc_spec.h "the RTS smoother of an IBIS cloud") -------------
+// Everything these calls need on the device is allocated by the call and freed before it returns: the handle is read only.
+namespace {
+struct CallBlock {   // one device allocation for the life of a call
+    char* p = nullptr;
+    ~CallBlock() { if (p) (void)hipFree(p); }
+    int alloc(const char* who, size_t bytes) {
+        const hipError_t e = hipMalloc((void**)&p, bytes ? bytes : 16);
+        if (e == hipSuccess) return SMC_OK;
+        p = nullptr;
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? SMC_ENOMEM : SMC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+};
+struct CallEvents {   // the bracket of a call's kernels on the handle's stream
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~CallEvents() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    hipError_t create() { const hipError_t e = hipEventCreate(&e0); return e != hipSuccess ? e : hipEventCreate(&e1); }
+    double ms() const { float f = 0.0f; return hipEventElapsedTime(&f, e0, e1) == hipSuccess ? (double)f : -1.0; }
+};
+size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+constexpr int64_t RTS_MAX_T = (int64_t)1 << 31;   // the step index is a 32-bit word of the Philox counter
+}  // namespace
+
+extern "C" int smc_ibis_smooth(void* hp, const double* y, int64_t T, double* out, double* xs, double* Ps) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !y || !out) return fail(SMC_EINVAL, "smc_ibis_smooth: bad argument");
+    if (T < 1 || T > RTS_MAX_T) return fail(SMC_EINVAL, "smc_ibis_smooth: 1 <= T <= 2^31");
+    if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_smooth: smc_ibis_set_theta has not been called");
+    if (h->win_k > 0) return fail(SMC_ESTATE, "smc_ibis_smooth: a window is pending (smc_ibis_commit first)");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t M = (size_t)h->v.M, nchunk = grid_of(h->v.M), sT = (size_t)T;
+    const size_t b_y = up256(sT * 8), b_rec = up256(sT * M * 8), b_part = up256(sT * IBIS_SUM_NCOL * nchunk * 8), b_out = sT * IBIS_SUM_NOUT * 8;
+    CallBlock blk;
+    if (const int rc = blk.alloc("smc_ibis_smooth", b_y + 2 * b_rec + b_part + b_out)) return rc;
+    double *d_y = (double*)blk.p, *d_xf = (double*)(blk.p + b_y), *d_Sf = (double*)(blk.p + b_y + b_rec);
+    double *d_part = (double*)(blk.p + b_y + 2 * b_rec), *d_out = (double*)(blk.p + b_y + 2 * b_rec + b_part);
+    const bool store = xs != nullptr || Ps != nullptr;
+    CallEvents ev;
+    HIPCHK(ev.create());
+    HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(ev.e0, h->stream));
+    hipLaunchKernelGGL(k_ibis_rts_forward, dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, (const double*)h->v.raw[h->cp], h->v.M,
+                       (const double*)d_y, T, h->predict_first, d_xf, d_Sf);
+    if (store)
+        hipLaunchKernelGGL((k_ibis_rts_backward<true, true>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream,
+                           (const double*)h->v.raw[h->cp], (const double*)h->v.logw[h->cs], h->v.M, T, d_xf, d_Sf, d_part);
+    else
+        hipLaunchKernelGGL((k_ibis_rts_backward<true, false>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream,
+                           (const double*)h->v.raw[h->cp], (const double*)h->v.logw[h->cs], h->v.M, T, d_xf, d_Sf, d_part);
+    hipLaunchKernelGGL(k_ibis_sum_combine, dim3((unsigned)T), dim3(IBIS_SUM_CTHREADS), 0, h->stream, d_part, (int64_t)nchunk, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev.e1, h->stream));
+    HIPCHK(hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, h->stream));
+    if (xs) HIPCHK(hipMemcpyAsync(xs, d_xf, sT * M * 8, hipMemcpyDeviceToHost, h->stream));
+    if (Ps) HIPCHK(hipMemcpyAsync(Ps, d_Sf, sT * M * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->rts_ms = ev.ms();
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_sample_paths(void* hp, const double* y, int64_t T, int64_t Mp, uint64_t path_seed, const int32_t* which,
+                                     double* paths) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !y || !which || !paths) return fail(SMC_EINVAL, "smc_ibis_sample_paths: bad argument");
+    if (T < 1 || T > RTS_MAX_T) return fail(SMC_EINVAL, "smc_ibis_sample_paths: 1 <= T <= 2^31");
+    if (Mp < 1 || Mp > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_ibis_sample_paths: 1 <= Mp <= 2^30");
+    if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_sample_paths: smc_ibis_set_theta has not been called");
+    if (h->win_k > 0) return fail(SMC_ESTATE, "smc_ibis_sample_paths: a window is pending (smc_ibis_commit first)");
+    for (int64_t p = 0; p < Mp; ++p)
+        if (which[p] < 0 || which[p] >= h->v.M) return fail(SMC_EINVAL, "smc_ibis_sample_paths: which entry outside [0, n_theta)");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t sM = (size_t)Mp, sT = (size_t)T;
+    const size_t b_y = up256(sT * 8), b_w = up256(sM * 4), b_rec = up256(sT * sM * 8);
+    CallBlock blk;
+    if (const int rc = blk.alloc("smc_ibis_sample_paths", b_y + b_w + 2 * b_rec)) return rc;
+    double* d_y = (double*)blk.p;
+    int32_t* d_w = (int32_t*)(blk.p + b_y);
+    double *d_paths = (double*)(blk.p + b_y + b_w), *d_Sf = (double*)(blk.p + b_y + b_w + b_rec);
+    HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, h->stream));
+    CallEvents ev;
+    HIPCHK(ev.create());
+    HIPCHK(hipMemcpyAsync(d_w, which, sM * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(ev.e0, h->stream));
+    hipLaunchKernelGGL(k_ibis_rts_paths, dim3(grid_of(Mp)), dim3(IBIS_THREADS), 0, h->stream, (const double*)h->v.raw[h->cp],
+                       (const int32_t*)d_w, Mp, (const double*)d_y, T, h->predict_first, path_seed, d_paths, d_Sf);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev.e1, h->stream));
+    HIPCHK(hipMemcpyAsync(paths, d_paths, sT * sM * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->rts_ms = ev.ms();
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_last_elapsed_ms(void* hp, double* ms) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !ms) return fail(SMC_EINVAL, "smc_ibis_last_elapsed_ms: bad argument");
+    if (h->rts_ms < 0.0) return fail(SMC_ESTATE, "smc_ibis_last_elapsed_ms: no smc_ibis_smooth / smc_ibis_sample_paths call has completed");
+    *ms = h->rts_ms;
+    return SMC_OK;
+}
+
+// the per-row half of smc_ibis_smooth without a handle: the counterpart of smc_kalman_log_likelihood
+extern "C" int smc_kalman_smooth(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first, double* xs, double* Ps,
+                                 int device) {
+    if (!raw || !y || !xs || !Ps) return fail(SMC_EINVAL, "smc_kalman_smooth: bad argument");
+    if (n_theta < 1 || n_theta > ((int64_t)1 << 30) || T < 1 || T > RTS_MAX_T) return fail(SMC_EINVAL, "smc_kalman_smooth: 1 <= n_theta <= 2^30, 1 <= T <= 2^31");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(SMC_EHIP, "smc_kalman_smooth: no HIP device");
+    if (device < 0 || device >= ndev) return fail(SMC_EINVAL, "smc_kalman_smooth: bad device");
+    HIPCHK(hipSetDevice(device));
+    const size_t M = (size_t)n_theta, sT = (size_t)T;
+    const size_t b_y = up256(sT * 8), b_raw = up256(M * IBIS_NRAW * 8), b_rec = up256(sT * M * 8);
+    CallBlock blk;
+    if (const int rc = blk.alloc("smc_kalman_smooth", b_y + b_raw + 2 * b_rec)) return rc;
+    double *d_y = (double*)blk.p, *d_raw = (double*)(blk.p + b_y), *d_xf = (double*)(blk.p + b_y + b_raw), *d_Sf = (double*)(blk.p + b_y + b_raw + b_rec);
+    hipStream_t st = nullptr;   // the default stream: the call owns nothing that outlives it
+    HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_raw, raw, M * IBIS_NRAW * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_ibis_rts_forward, dim3(grid_of(n_theta)), dim3(IBIS_THREADS), 0, st, (const double*)d_raw, n_theta, (const double*)d_y, T,
+                       predict_first ? 1 : 0, d_xf, d_Sf);
+    hipLaunchKernelGGL((k_ibis_rts_backward<false, true>), dim3(grid_of(n_theta)), dim3(IBIS_THREADS), 0, st, (const double*)d_raw,
+                       (const double*)nullptr, n_theta, T, d_xf, d_Sf, (double*)nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(xs, d_xf, sT * M * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(Ps, d_Sf, sT * M * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+
+// The same specification on the host (no GPU), the same bits.  xf, Sf: the filtered record the backward pass ran over.
+extern "C" int smc_host_ibis_smooth(const double* rows, const double* logw, int64_t M, const double* y, int64_t T, int predict_first,
+                                    double* out, double* xs, double* Ps, double* xf, double* Sf) {
+    if (!rows || !logw || !y || !out || M < 1) return fail(SMC_EINVAL, "smc_host_ibis_smooth: bad argument");
+    if (T < 1 || T > RTS_MAX_T) return fail(SMC_EINVAL, "smc_host_ibis_smooth: 1 <= T <= 2^31");
+    const size_t sM = (size_t)M, sT = (size_t)T;
+    std::vector<double> bx, bP;
+    if (!xs) { bx.resize(sT * sM); xs = bx.data(); }
+    if (!Ps) { bP.resize(sT * sM); Ps = bP.data(); }
+    for (size_t m = 0; m < sM; ++m) {
+        const double* r = rows + m * IBIS_NRAW;
+        double x = r[4], S = r[5];
+        for (size_t t = 0; t < sT; ++t) {
+            (void)kalman_step(r[0], r[1], r[2], r[3], t > 0 || predict_first != 0, y[t], x, S);
+            xs[t * sM + m] = x;
+            Ps[t * sM + m] = S;
+            if (xf) xf[t * sM + m] = x;
+            if (Sf) Sf[t * sM + m] = S;
+        }
+        double a = x, P = S;
+        for (size_t t = sT - 1; t-- > 0;) {
+            rts_back(r[0], r[2], xs[t * sM + m], Ps[t * sM + m], a, P);
+            xs[t * sM + m] = a;
+            Ps[t * sM + m] = P;
+        }
+    }
+    for (size_t t = 0; t < sT; ++t)
+        if (const int rc = smc_host_ibis_summary(rows, xs + t * sM, Ps + t * sM, logw, M, 0, out + t * IBIS_SUM_NOUT)) return rc;
+    return SMC_OK;
+}
+
+extern "C" int smc_host_ibis_sample_paths(const double* rows, int64_t M, const double* y, int64_t T, int predict_first, int64_t Mp,
+                                          uint64_t path_seed, const int32_t* which, double* paths, double* z) {
+    if (!rows || !y || !which || !paths || M < 1) return fail(SMC_EINVAL, "smc_host_ibis_sample_paths: bad argument");
+    if (T < 1 || T > RTS_MAX_T) return fail(SMC_EINVAL, "smc_host_ibis_sample_paths: 1 <= T <= 2^31");
+    if (Mp < 1 || Mp > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_host_ibis_sample_paths: 1 <= Mp <= 2^30");
+    for (int64_t p = 0; p < Mp; ++p)
+        if (which[p] < 0 || which[p] >= M) return fail(SMC_EINVAL, "smc_host_ibis_sample_paths: which entry outside [0, M)");
+    const size_t sM = (size_t)Mp, sT = (size_t)T;
+    std::vector<double> Sf(sT);
+    for (int64_t p = 0; p < Mp; ++p) {
+        const double* r = rows + (size_t)which[p] * IBIS_NRAW;
+        const uint32_t stream = (uint32_t)which[p];
+        double x = r[4], S = r[5];
+        for (size_t t = 0; t < sT; ++t) {
+            (void)kalman_step(r[0], r[1], r[2], r[3], t > 0 || predict_first != 0, y[t], x, S);
+            paths[t * sM + (size_t)p] = x;
+            Sf[t] = S;
+        }
+        double zt = rts_normal(path_seed, p, stream, (uint32_t)(T - 1));
+        double xp = rts_path_last(x, S, zt);
+        paths[(sT - 1) * sM + (size_t)p] = xp;
+        if (z) z[(sT - 1) * sM + (size_t)p] = zt;
+        for (size_t t = sT - 1; t-- > 0;) {
+            zt = rts_normal(path_seed, p, stream, (uint32_t)t);
+            xp = rts_path_back(r[0], r[2], paths[t * sM + (size_t)p], Sf[t], xp, zt);
+            paths[t * sM + (size_t)p] = xp;
+            if (z) z[t * sM + (size_t)p] = zt;
+        }
     }
     return SMC_OK;
 }

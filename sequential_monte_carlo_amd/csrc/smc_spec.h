@@ -858,6 +858,51 @@ SMC_HD void ibis_sum_second(const double* r, double f, double D, double y, doubl
     b[1] = on ? ((f * r[ISF_MX]) / D + (2.0 * ex) * ((f * r[ISF_DX]) / D)) + Om * (ex * ex) : 0.0;
 }
 
+// ---- the RTS smoother of an IBIS cloud (Rauch, Tung and Striebel 1965) -----------------------------------------
+// Particle m has the row (A, B, Q, R, x0, sigma0).  Its filtered record (xf_t, Sf_t), t = 0..T-1, is what kalman_step leaves
+// after step t from (x0, sigma0): step 0 predicts iff predict_first, every later step predicts.  The backward pass, t = T-2 .. 0
+// from xs_{T-1} = xf_{T-1}, Ps_{T-1} = Sf_{T-1}, in this order of operations (rts_gain, rts_back):
+//   Sp = (A A) Sf_t + Q                          the predicted variance of step t+1, as kalman_step forms it
+//   G  = Sp > 0 ? (Sf_t A) / Sp : 0
+//   V  = Sp > 0 ? (Sf_t Q) / Sp : Sf_t           the variance of x_t given x_{t+1} and y_1:t
+//   xs_t = xf_t + G (xs_{t+1} - A xf_t)
+//   Ps_t = V + (G G) Ps_{t+1}                    a sum of non-negative terms (Sf + G^2 (Ps' - Sp) would cancel)
+// The cloud at period t is integrated by "summaries of an IBIS cloud" above with ahead = 0, (x, S) := (xs_t, Ps_t) and the
+// particle's own logw: the same chunks, tree and left-to-right combine, so row t of the output is the eight numbers of
+// smc_ibis_summary, now the smoothed fitted observation and the smoothed state.
+// Paths: path p (0-based) belongs to parameter particle m = which[p] and is, from t = T-1 down,
+//   x_{T-1} = xf_{T-1} + sd(Sf_{T-1}) z
+//   x_t     = (xf_t + G (x_{t+1} - A xf_t)) + sd(V) z,    sd(v) = v > 0 ? sqrt(v) : 0  (correctly rounded)
+//   z       = box_muller(draw(path_seed, p >> 1, stream = which[p], t, SLOT_RTS)): z0 for an even p, z1 for an odd one
+// so a path is a function of (row, y, path_seed, p, which[p]) alone: not of the number of paths, the cloud or the launch.
+constexpr uint32_t SLOT_RTS = 36u;                // no other draw uses it (SLOT_PATH is 35; the others end at 34)
+SMC_HD void rts_gain(double A, double Q, double Sf, double& G, double& V) {
+    const double Sp = (A * A) * Sf + Q;
+    const bool on = Sp > 0.0;
+    G = on ? (Sf * A) / Sp : 0.0;
+    V = on ? (Sf * Q) / Sp : Sf;
+}
+// (xs, Ps) of step t+1 in, of step t out
+SMC_HD void rts_back(double A, double Q, double xf, double Sf, double& xs, double& Ps) {
+    double G, V;
+    rts_gain(A, Q, Sf, G, V);
+    xs = xf + G * (xs - A * xf);
+    Ps = V + (G * G) * Ps;
+}
+SMC_HD double rts_sd(double v) { return v > 0.0 ? sqrt(v) : 0.0; }
+SMC_HD double rts_normal(uint64_t seed, int64_t p, uint32_t stream, uint32_t t) {
+    double z0, z1;
+    box_muller(draw(seed, (uint32_t)(p >> 1), stream, t, SLOT_RTS), z0, z1);
+    return (p & 1) ? z1 : z0;
+}
+SMC_HD double rts_path_last(double xf, double Sf, double z) { return xf + rts_sd(Sf) * z; }
+// x_{t+1} of the path in, x_t out
+SMC_HD double rts_path_back(double A, double Q, double xf, double Sf, double xnext, double z) {
+    double G, V;
+    rts_gain(A, Q, Sf, G, V);
+    return (xf + G * (xnext - A * xf)) + rts_sd(V) * z;
+}
+
 // ---- moments of the theta cloud of an IBIS sampler (random_walk_kernel, smc_samplers.jl:87-101; expected_parameters, ibis.jl:60-64) --
 // theta [M][d], outer log-weights logw [M].  Two modes, one order of operations - a function of the arrays alone:
 //   unweighted:  c_m = 1 for every particle;                       mean = (sum theta) / M,   cov = (sum dd') / (M - 1)  (corrected)

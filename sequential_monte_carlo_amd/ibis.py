@@ -5,6 +5,8 @@ the univariate LinearModel (UnivariateLinearGaussian, unobserved_components).
     smc2 / smc2_step / smc2_run, resample_, rejuvenate_, expected_parameters, density_tempered   (smc_samplers.py dispatches here)
     posterior_moments: the weighted mean and covariance of the theta cloud, reduced on the device
     observation_dist, estimated_trend, quantile (plotting_utils.jl:94-137), filtered_state: reductions over the cloud on the device
+    rts_smoothed_state, rts_quantile, rts_smoothed_paths: the exact RTS smoother of every parameter particle, integrated over the
+    cloud per period, and trajectories by backward sampling - the smoothed trend and trend paths
 
 A parameter particle owns O(1) state - theta, its model row, (x, Sigma), logZ, logw - and all of it lives on the device for the
 life of the sampler (smc_ibis_*, csrc/smc_ibis_kernels.h): an online step is one Kalman update per particle, a window of steps
@@ -227,6 +229,63 @@ def quantile(ibis, p, ahead=0, total=False):
     y, S, b = observation_dist(ibis, ahead, between=True)
     q = _normal_quantiles(y, S + b if total else S, [float(v) for v in np.atleast_1d(p)])
     return float(q[0]) if np.ndim(p) == 0 else q
+
+
+_U64 = 0xFFFFFFFFFFFFFFFF
+_RTS_COLUMNS = ("y", "Sigma", "between", "xbar", "Sbar", "between_x")
+
+
+def _rts_rows(ibis, y):
+    """out [T][8] of smc_ibis_smooth on the resident cloud; before the first sampler call the host twin over the initial cloud"""
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    if y.size < 1:
+        raise ValueError("y must hold at least one observation")
+    if ibis._h is None:
+        return _lib.host_ibis_smooth(ibis.theta_map.rows(ibis._theta0), np.zeros(ibis.M), y, ibis.predict_first)
+    return ibis._h.smooth(y)
+
+
+def rts_smoothed_state(ibis, y, parts=False):
+    """(mean [T], var [T]) of p(x_t | y_1:T) integrated over the sampler's current parameter cloud, exactly: the RTS smoother of
+    every parameter particle over y (a Kalman re-filter from (x0, sigma0) and one backward recursion, O(T) per particle) and one
+    reduction over the cloud per period, all on the device (smc_ibis_smooth).  mean = sum omega xs_m = xbar and var = Sbar +
+    between_x, within plus between, as smoothed_state combines a mixture.  parts=True: a dict of the six columns per period,
+    y, Sigma, between (the smoothed fitted observation B x, as observation_dist names them) and xbar, Sbar, between_x.
+    y is the caller's series (the sampler keeps none): pass the observations the cloud has seen, y[:ibis.t].  The sampler is
+    not changed."""
+    r = _rts_rows(ibis, y)
+    if parts:
+        return {name: r[:, i].copy() for i, name in enumerate(_RTS_COLUMNS)}
+    return r[:, 3].copy(), r[:, 4] + r[:, 5]
+
+
+def rts_quantile(ibis, y, p, total=True):
+    """quantiles of the smoothed state per period, [T][len(p)] at the levels p in ascending order ([T] for a scalar p; the caller's
+    p is left as it is, as in quantile(ibis, p)): of Normal(xbar_t, sqrt(Sbar_t + between_x_t)), the moment-matched normal of the
+    mixture (total=True), or of Normal(xbar_t, sqrt(Sbar_t)) (total=False)."""
+    r = _rts_rows(ibis, y)
+    levels = [float(v) for v in np.atleast_1d(p)]
+    q = np.array([_normal_quantiles(float(row[3]), float(row[4] + row[5]) if total else float(row[4]), levels) for row in r])
+    return q[:, 0].copy() if np.ndim(p) == 0 else q
+
+
+def rts_smoothed_paths(ibis, y, M, seed=None):
+    """M trajectories [T][M] from p(x_1:T | y_1:T) integrated over the sampler's current parameter cloud: the parameter particle of
+    every path is drawn from omega through the library's own outer resampler (host_outer_resample(logw, M, seed + 1): ascending,
+    exactly as smoothed_paths draws them; particles with omega = 0 are never drawn), and every path is drawn exactly by backward
+    sampling under its particle's row (smc_ibis_sample_paths, Philox seed + 2).  seed: default derived from the sampler's seed;
+    the sampler's own rng and state are not touched."""
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    M = int(M)
+    if M < 1:
+        raise ValueError("M must be positive")
+    if y.size < 1:
+        raise ValueError("y must hold at least one observation")
+    seed = (((ibis.seed << 20) | 0x4754B) if seed is None else int(seed)) & _U64
+    which = np.asarray(_lib.host_outer_resample(ibis.logw, M, (seed + 1) & _U64), dtype=np.int32)
+    if ibis._h is None:
+        return _lib.host_ibis_sample_paths(ibis.theta_map.rows(ibis._theta0), y, which, (seed + 2) & _U64, ibis.predict_first)
+    return ibis._h.sample_paths(y, which, (seed + 2) & _U64)
 
 
 def smc2(ibis, y):

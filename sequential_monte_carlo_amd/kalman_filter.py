@@ -1,6 +1,7 @@
 """Host mirror of src/kalman_filter.jl for the univariate LinearModel, batched on the GPU.
 
     log_likelihood_kalman(y, model)   -> (x_T, Sigma_T, logZ)       kalman_filter.jl:55-70
+    kalman_smoother(y, model)         -> (xs [T], Ps [T])           the exact RTS smoother over the same filter
 
 `model` may be a list of LinearModels (one lane per parameter row): the O(1)-per-theta inner "filter"
 of the IBIS sampler (src/ibis.jl:134-189).  predict_first=True reproduces the reference loop literally
@@ -22,3 +23,14 @@ def log_likelihood_kalman(y, model, predict_first=False, device=0):
     if single:
         return float(out[0, 0]), float(out[0, 1]), float(out[0, 2])
     return out[:, 0], out[:, 1], out[:, 2]
+
+
+def kalman_smoother(y, model, predict_first=False, device=0):
+    """(xs, Ps): mean and variance of p(x_t | y_1:T) for a LinearModel, [T] each; for a list of LinearModels [T][n], one lane per
+    parameter row (smc_kalman_smooth).  predict_first as in log_likelihood_kalman."""
+    single = isinstance(model, LinearModel)
+    models = [model] if single else list(model)
+    if not models or not all(isinstance(m, LinearModel) for m in models):
+        raise TypeError("the Kalman smoother needs LinearModel(s)")
+    xs, Ps = _lib.kalman_smooth(np.array([m.raw() for m in models]), y, predict_first, device)
+    return (xs[:, 0].copy(), Ps[:, 0].copy()) if single else (xs, Ps)

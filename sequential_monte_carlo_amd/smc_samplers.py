@@ -573,9 +573,9 @@ def smoothed_state(smc, y, N=None, max_bytes=2 ** 31, seed=None):
     (between), as trend_moments combines a mixture.  Filters with omega = 0 are left out, as in filtered_summaries.  Filter m uses
     Philox stream m, so the result does not depend on the blocks; seed: the Philox seed of the filters (default: derived from the
     sampler's seed; the sampler's own state is not touched).  All parameter particles are smoothed on this process's GPU.
-    IBIS is out of scope: its exact smoother is RTS, a different feature."""
+    IBIS is out of scope: its exact smoother is RTS, a different feature (rts_smoothed_state)."""
     if isinstance(smc, IBIS):
-        raise TypeError("smoothed_state: IBIS is out of scope: its exact smoother is RTS, a different feature")
+        raise TypeError("smoothed_state: IBIS is out of scope: its exact smoother is RTS, a different feature (rts_smoothed_state)")
     from .particles import smoother
     y = np.ascontiguousarray(y, dtype=np.float64).ravel()
     N = smc.N if N is None else int(N)
@@ -614,9 +614,9 @@ def smoothed_paths(smc, y, M, N=None, max_bytes=2 ** 31, seed=None):
     record and paths stay under max_bytes, and filter m draws its count of paths.  Filter m uses Philox stream m, so the result
     does not depend on the blocks; particles with omega = 0 are never drawn.  seed: the Philox seed of the filters, of the
     ancestors and of the walk (default: derived from the sampler's seed; the sampler's own state is not touched).
-    IBIS is out of scope: its exact smoother is RTS, a different feature."""
+    IBIS is out of scope: its exact smoother is RTS, a different feature (rts_smoothed_paths)."""
     if isinstance(smc, IBIS):
-        raise TypeError("smoothed_paths: IBIS is out of scope: its exact smoother is RTS, a different feature")
+        raise TypeError("smoothed_paths: IBIS is out of scope: its exact smoother is RTS, a different feature (rts_smoothed_paths)")
     from .particles import smoother
     y = np.ascontiguousarray(y, dtype=np.float64).ravel()
     M = int(M)
