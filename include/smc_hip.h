@@ -610,6 +610,45 @@ int smc_sample_paths(smc_handle h, int64_t M, uint64_t path_seed, const int32_t*
 int smc_host_sample_paths(int model_id, const double* raw, int64_t T, int64_t n, const double* x /*[T][d][n]*/, const double* w /*[T][n]*/,
                           int64_t M, uint64_t path_seed, uint32_t stream, int32_t* idx /*[T][M]*/, double* xs /*[T][d][M] or NULL*/);
 
+/* ---- Rao-Blackwellised backward simulation: smoothing the marginal UCSV filter (Lindsten et al. 2016) ---------------------------
+ * SMC_MODEL_UCSV_RB carries the Kalman mean and variance of the trend inside every particle, and those two rows are functions of
+ * the whole volatility path: smc_smooth and smc_sample_paths refuse the family.  But the two log-volatilities are an autonomous
+ * Markov chain, and given their path the trend is linear-Gaussian.  So the backward walk runs over the VOLATILITIES alone: the
+ * weight of source l at step t is w_t^l f(lse+, lsn+ | lse_l, lsn_l) times the Gaussian density of everything the later
+ * observations say about the trend, N(mu; m_l, P_l + exp(lse_l) + tau), where (mu, tau) is one scalar information pair per path
+ * updated after every pick (csrc/smc_spec.h "Rao-Blackwellised backward simulation": one log and one division per pair on top
+ * of backward simulation's chain; the integers, the uniform and the selection are backward simulation's).  The paths are draws
+ * from p(lse_1:T, lsn_1:T | y_1:T); the trend then comes EXACTLY given each path, from a Kalman filter and an RTS pass along
+ * it - no Monte-Carlo noise in the trend given the volatilities.  Path p is a function of the record, the parameter row, y, the
+ * path seed and the filter's Philox stream id alone: the same bits from the device and the host twin, for any M, alone or in a batch.
+ *   smc_rb_sample_paths  M paths per filter over the record of an armed SMC_MODEL_UCSV_RB handle; y [T] are the observations the
+ *                      recorded steps saw, T = smc_history_len.  idx [T][n_theta][M]: the particle of step t the path passes
+ *                      through; vol [T][2][n_theta][M]: its (lse, lsn); tmean, tvar [T][n_theta][M]: mean and variance of
+ *                      p(x_t | the path's volatilities, y_1:T); tdraw: one joint draw of the trend path given the volatilities
+ *                      (backward sampling, Philox slot 37); out [T][n_theta][8]: per filter and step, over the complete paths
+ *                      among the first counts[th], (trend mean, within = mean of tvar, between = population variance of tmean,
+ *                      mean and variance of lse, mean and variance of lsn, the number of complete paths) - the smoothed trend
+ *                      has mean out[0] and variance out[1] + out[2].  Every output may be NULL.  counts as in smc_sample_paths.
+ *                      A collapsed filter reads -1 / NaN everywhere; a path no live source reaches reads -1 / NaN in idx / vol
+ *                      from that step back and NaN in tmean, tvar, tdraw at every step, and is left out of `out`; no complete
+ *                      path: NaN and the count 0.  Either resampler.  It may be called again with other seeds and after more
+ *                      steps, and disturbs nothing on the handle (its scratch is its own).  Cost: 2 M n_x T n_theta pair
+ *                      evaluations plus O(M T n_theta) for the trend (profiles/rb_paths_cost.log).
+ *                      SMC_EINVAL: a handle that is not SMC_MODEL_UCSV_RB; T != smc_history_len; a y that is not finite; a gamma
+ *                      that is not a positive finite number; M outside [1, 2^30]; a count outside [0, M]; n_x > 2^20.
+ *                      SMC_ESTATE: the handle is not armed or nothing is recorded.  SMC_ENOMEM: the paths and the scratch cannot
+ *                      be allocated; the handle is as it was
+ *   smc_host_rb_sample_paths  the same specification for ONE filter on the host (no GPU), the same bits: raw [5] UCSV's row,
+ *                      x [T][4][n], w [T][n], y [T], the filter's Philox stream id -> idx [T][M], vol [T][2][M], tmean, tvar
+ *                      [T][M], tdraw [T][M] or NULL, out [T][8] or NULL */
+int smc_rb_sample_paths(smc_handle h, const double* y /*[T]*/, int64_t T, int64_t M, uint64_t path_seed, const int32_t* counts /*[n_theta] or NULL*/,
+                        int32_t* idx /*[T][n_theta][M]*/, double* vol /*[T][2][n_theta][M]*/, double* tmean /*[T][n_theta][M]*/,
+                        double* tvar /*[T][n_theta][M]*/, double* tdraw /*[T][n_theta][M] or NULL*/, double* out /*[T][n_theta][8] or NULL*/);
+int smc_host_rb_sample_paths(const double* raw /*[5]*/, int64_t T, int64_t n, const double* x /*[T][4][n]*/, const double* w /*[T][n]*/,
+                             const double* y /*[T]*/, int64_t M, uint64_t path_seed, uint32_t stream, int32_t* idx /*[T][M]*/,
+                             double* vol /*[T][2][M]*/, double* tmean /*[T][M]*/, double* tvar /*[T][M]*/, double* tdraw /*[T][M] or NULL*/,
+                             double* out /*[T][8] or NULL*/);
+
 /* ---- host-side helpers (no GPU needed) ---------------------------------------------------------*/
 /* simulate(rng, model, T) -> (x, y)                         src/state_space_models.jl:11-26 */
 int smc_simulate(int model_id, const double* raw, int64_t T, uint64_t seed, double* x /*[smc_simulate_dim][T] or NULL*/, double* y /*[T]*/);

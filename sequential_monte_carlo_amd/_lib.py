@@ -37,7 +37,7 @@ EXPORTS = [
     "smc_host_rw_factor_cov",
     "smc_ibis_smooth", "smc_ibis_sample_paths", "smc_ibis_last_elapsed_ms", "smc_kalman_smooth", "smc_host_ibis_smooth", "smc_host_ibis_sample_paths",
     "smc_history_begin", "smc_history_len", "smc_history_get", "smc_history_put", "smc_history_end", "smc_smooth", "smc_host_transition_logpdf",
-    "smc_host_smooth", "smc_sample_paths", "smc_host_sample_paths",
+    "smc_host_smooth", "smc_sample_paths", "smc_host_sample_paths", "smc_rb_sample_paths", "smc_host_rb_sample_paths",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -212,6 +212,8 @@ def lib():
     L.smc_host_smooth.argtypes = [C.c_int, _dp, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp]
     L.smc_sample_paths.argtypes = [h, C.c_int64, C.c_uint64, _i32p, _i32p, _dp]
     L.smc_host_sample_paths.argtypes = [C.c_int, _dp, C.c_int64, C.c_int64, _dp, _dp, C.c_int64, C.c_uint64, C.c_uint32, _i32p, _dp]
+    L.smc_rb_sample_paths.argtypes = [h, _dp, C.c_int64, C.c_int64, C.c_uint64, _i32p, _i32p, _dp, _dp, _dp, _dp, _dp]
+    L.smc_host_rb_sample_paths.argtypes = [_dp, C.c_int64, C.c_int64, _dp, _dp, _dp, C.c_int64, C.c_uint64, C.c_uint32, _i32p, _dp, _dp, _dp, _dp, _dp]
     L.smc_last_error.restype = C.c_char_p
     L.smc_version.restype = C.c_char_p
     _lib = L
@@ -867,6 +869,61 @@ class Handle:
         check(lib().smc_sample_paths(self._h, M, int(seed), counts.ctypes.data_as(_i32p) if counts is not None else None,
                                      idx.ctypes.data_as(_i32p), _d(xs)))
         return idx, xs
+
+
+    def rb_sample_paths(self, y, M, seed, counts=None, draws=False, per_path=True, summary=True):
+        """M Rao-Blackwellised backward-simulated paths per filter over the record of a MODEL_UCSV_RB handle
+        (smc_rb_sample_paths; y [T]: the observations the recorded steps saw): a dict with "idx" [T][n_theta][M] int32, "vol"
+        [T][2][n_theta][M] the (lse, lsn) of every path, "tmean", "tvar" [T][n_theta][M] the exact trend moments given each path
+        (per_path=False leaves these four out), "tdraw" [T][n_theta][M] a joint trend draw per path (draws=True) and "out"
+        [T][n_theta][8] the summary over the paths (summary=True).  counts as in sample_paths"""
+        y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        T, M = y.size, int(M)
+        if M < 1:
+            raise ValueError("M must be positive")
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            if counts.shape != (self.n_theta,):
+                raise ValueError("counts must be [n_theta]")
+        r = {}
+        if per_path:
+            r["idx"] = np.zeros((T, self.n_theta, M), dtype=np.int32)
+            r["vol"] = np.zeros((T, 2, self.n_theta, M))
+            r["tmean"], r["tvar"] = np.zeros((T, self.n_theta, M)), np.zeros((T, self.n_theta, M))
+        if draws:
+            r["tdraw"] = np.zeros((T, self.n_theta, M))
+            if "vol" not in r:
+                r["vol"] = np.zeros((T, 2, self.n_theta, M))
+        if summary:
+            r["out"] = np.zeros((T, self.n_theta, 8))
+        check(lib().smc_rb_sample_paths(self._h, _d(y), T, M, int(seed), counts.ctypes.data_as(_i32p) if counts is not None else None,
+                                        r["idx"].ctypes.data_as(_i32p) if "idx" in r else None, _d(r.get("vol")), _d(r.get("tmean")),
+                                        _d(r.get("tvar")), _d(r.get("tdraw")), _d(r.get("out"))))
+        return r
+
+
+def host_rb_sample_paths(raw, x, w, y, M, seed, stream=0, draws=True, summary=True):
+    """M Rao-Blackwellised backward-simulated paths of ONE MODEL_UCSV_RB filter by the specification on the host
+    (smc_host_rb_sample_paths; no GPU): raw [5], x [T][4][n], w [T][n], y [T] -> a dict with "idx" [T][M] int32, "vol" [T][2][M],
+    "tmean", "tvar" [T][M], "tdraw" [T][M] (draws) and "out" [T][8] (summary)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    if raw.size != 5:
+        raise ValueError("raw must be UCSV's five parameters")
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    T, n = w.shape
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(T, 4, n)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    if y.size != T:
+        raise ValueError("y must be [T]")
+    Mz = max(int(M), 0)
+    r = {"idx": np.zeros((T, Mz), dtype=np.int32), "vol": np.zeros((T, 2, Mz)), "tmean": np.zeros((T, Mz)), "tvar": np.zeros((T, Mz))}
+    if draws:
+        r["tdraw"] = np.zeros((T, Mz))
+    if summary:
+        r["out"] = np.zeros((T, 8))
+    check(lib().smc_host_rb_sample_paths(_d(raw), T, n, _d(x), _d(w), _d(y), int(M), int(seed), int(stream), r["idx"].ctypes.data_as(_i32p),
+                                         _d(r["vol"]), _d(r["tmean"]), _d(r["tvar"]), _d(r.get("tdraw")), _d(r.get("out"))))
+    return r
 
 
 def host_sample_paths(model_id, raw, x, w, M, seed, stream=0, want_x=True):

@@ -1,10 +1,12 @@
 // smc_capi_smooth.hip -- the record of a step-by-step run (smc_history_*) and the FFBS particle smoother over it (smc_smooth):
-// forward filtering by the step kernels as they are, backward smoothing by the all-pairs kernels of smc_smooth_kernels.h, and
-// backward simulation over the same record (smc_sample_paths, smc_path_kernels.h).
+// forward filtering by the step kernels as they are, backward smoothing by the all-pairs kernels of smc_smooth_kernels.h,
+// backward simulation over the same record (smc_sample_paths, smc_path_kernels.h) and its Rao-Blackwellised form for
+// MODEL_UCSV_RB (smc_rb_sample_paths, smc_rb_kernels.h).
 // Specification: smc_spec.h "the smoother"; the host twin (smc_host_smooth) lives in smc_util.hip.
 #include "smc_host.h"
 #include "smc_smooth_kernels.h"
 #include "smc_path_kernels.h"
+#include "smc_rb_kernels.h"
 
 #include <cstring>
 #include <vector>
@@ -21,6 +23,7 @@ void history_free(smc_filter_s* h) {
     (void)hipFree(h->hist.d_ws);
     (void)hipFree(h->hist.d_tmp);
     (void)hipFree(h->hist.d_path);
+    (void)hipFree(h->hist.d_rb);
     h->hist = {};
 }
 
@@ -153,7 +156,7 @@ extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
     if (!h) return fail(SMC_EINVAL, "smc_smooth: NULL handle");
     if (h->model != MODEL_LG1D && h->model != MODEL_SV1D && h->model != MODEL_UCSV3D)
         return fail(SMC_EINVAL, "smc_smooth: SMC_MODEL_UCSV_RB has no transition density of its state rows (m and P are functions of the whole "
-                                "path); smooth a UCSV3D filter instead");
+                                "path); smooth a UCSV3D filter instead, or draw Rao-Blackwellised paths (smc_rb_sample_paths)");
     if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, "smc_smooth: nothing is recorded (smc_history_begin, then smc_init / smc_step)");
     const FilterView& v = h->v;
     const int64_t T = h->hist.len, n = v.n;
@@ -287,7 +290,7 @@ extern "C" int smc_sample_paths(smc_handle h, int64_t M, uint64_t path_seed, con
     if (!h) return fail(SMC_EINVAL, "smc_sample_paths: NULL handle");
     if (h->model != MODEL_LG1D && h->model != MODEL_SV1D && h->model != MODEL_UCSV3D)
         return fail(SMC_EINVAL, "smc_sample_paths: SMC_MODEL_UCSV_RB has no transition density of its state rows (m and P are functions of the "
-                                "whole path); draw the paths of a UCSV3D filter instead");
+                                "whole path); draw the paths of a UCSV3D filter instead, or call smc_rb_sample_paths");
     if (M < 1 || M > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_sample_paths: M must be in [1, 2^30]");
     if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, "smc_sample_paths: nothing is recorded (smc_history_begin, then smc_init / smc_step)");
     const FilterView& v = h->v;
@@ -356,5 +359,128 @@ extern "C" int smc_sample_paths(smc_handle h, int64_t M, uint64_t path_seed, con
     if (rc) return rc;
     if (idx) HIPCHK(hipMemcpy(idx, d_idx, (size_t)T * pw * 4, hipMemcpyDeviceToHost));
     if (xs) HIPCHK(hipMemcpy(xs, d_xs, (size_t)T * d * pw * 8, hipMemcpyDeviceToHost));
+    return SMC_OK;
+}
+
+// ---- Rao-Blackwellised backward simulation (MODEL_UCSV_RB) ---------------------------------------------------------------------
+namespace {
+struct RbPlan {
+    int nchunk, mchunk;   // chunks of particles (the walk), chunks of paths (the summary)
+    size_t o_cur, o_pmax, o_psum, o_rmax, o_rows, o_dead, o_counts, o_y, o_idx, o_vol, o_tmean, o_tvar, o_tdraw, o_stmp, o_out, bytes;
+};
+// false: the sizes do not fit size_t arithmetic
+bool rb_plan(const smc_filter_s* h, int64_t T, int64_t M, bool want_draw, RbPlan& p) {
+    const size_t nt = (size_t)h->v.ntheta, pw = nt * (size_t)M;
+    p.nchunk = (int)((h->v.n + SMOOTH_CH - 1) / SMOOTH_CH);
+    p.mchunk = (int)((M + SMOOTH_CH - 1) / SMOOTH_CH);
+    if (pw > ((size_t)1 << 56) / ((size_t)T * 8) || pw > ((size_t)1 << 56) / (size_t)p.nchunk) return false;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    p.o_cur = take(4 * pw * 8);
+    p.o_pmax = take((size_t)p.nchunk * pw * 8);
+    p.o_psum = take((size_t)p.nchunk * pw * 8);
+    p.o_rmax = take(pw * 8);
+    p.o_rows = take(nt * sizeof(SmoothRow));
+    p.o_dead = take(nt * sizeof(int));
+    p.o_counts = take(nt * sizeof(int32_t));
+    p.o_y = take((size_t)T * 8);
+    p.o_idx = take((size_t)T * pw * 4);
+    p.o_vol = take((size_t)T * 2 * pw * 8);
+    p.o_tmean = take((size_t)T * pw * 8);
+    p.o_tvar = take((size_t)T * pw * 8);
+    p.o_tdraw = take(want_draw ? (size_t)T * pw * 8 : 0);
+    p.o_stmp = take((size_t)T * nt * (size_t)p.mchunk * 8);
+    p.o_out = take((size_t)T * nt * 8 * 8);
+    p.bytes = off;
+    return true;
+}
+}  // namespace
+
+extern "C" int smc_rb_sample_paths(smc_handle h, const double* y, int64_t T, int64_t M, uint64_t path_seed, const int32_t* counts, int32_t* idx,
+                                   double* vol, double* tmean, double* tvar, double* tdraw, double* out) {
+    if (!h) return fail(SMC_EINVAL, "smc_rb_sample_paths: NULL handle");
+    if (h->model != MODEL_UCSV_RB)
+        return fail(SMC_EINVAL, "smc_rb_sample_paths: the handle is not SMC_MODEL_UCSV_RB (the other families have a transition density: smc_sample_paths)");
+    if (!y) return fail(SMC_EINVAL, "smc_rb_sample_paths: NULL y");
+    if (M < 1 || M > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_rb_sample_paths: M must be in [1, 2^30]");
+    if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, "smc_rb_sample_paths: nothing is recorded (smc_history_begin, then smc_init / smc_step)");
+    if (T != h->hist.len) return fail(SMC_EINVAL, "smc_rb_sample_paths: T is not the number of recorded steps (smc_history_len)");
+    for (int64_t t = 0; t < T; ++t)
+        if (!(y[t] - y[t] == 0.0)) return fail(SMC_EINVAL, "smc_rb_sample_paths: y[" + std::to_string(t) + "] is not finite");
+    const FilterView& v = h->v;
+    const int64_t n = v.n;
+    const size_t nw = cloud_words(h), nt = (size_t)v.ntheta, d = (size_t)h->d, pw = nt * (size_t)M;
+    if (n > PATH_MAX_N) return fail(SMC_EINVAL, "smc_rb_sample_paths: more than 2^20 particles per filter (the integer weights of a step would not fit their sum)");
+    std::vector<int32_t> cnt(nt, (int32_t)M);
+    for (size_t m = 0; counts && m < nt; ++m) {
+        if (counts[m] < 0 || counts[m] > M) return fail(SMC_EINVAL, "smc_rb_sample_paths: counts[" + std::to_string(m) + "] is outside [0, M]");
+        cnt[m] = counts[m];
+    }
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<Params> prm(nt);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(prm.data(), h->d_params, nt * sizeof(Params), hipMemcpyDeviceToHost));
+    std::vector<SmoothRow> rows(nt);
+    for (size_t m = 0; m < nt; ++m)   // (the two gammas are UCSV3D's: nh1, nh2)
+        if (!smooth_row(MODEL_UCSV3D, prm[m].raw, rows[m]))
+            return fail(SMC_EINVAL, "smc_rb_sample_paths: a gamma of filter " + std::to_string(m) + " is not a positive finite number");
+    RbPlan p{};
+    if (!rb_plan(h, T, M, tdraw != nullptr, p)) return fail(SMC_ENOMEM, "smc_rb_sample_paths: paths of that many bytes cannot be allocated");
+    if (p.bytes > h->hist.rb_bytes) {   // (the new block first: a failed allocation leaves the handle as it was)
+        char* blk = nullptr;
+        if (hipMalloc((void**)&blk, p.bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SMC_ENOMEM, "smc_rb_sample_paths: hipMalloc of the paths and the scratch of the backward walk");
+        }
+        (void)hipFree(h->hist.d_rb);
+        h->hist.d_rb = blk;
+        h->hist.rb_bytes = p.bytes;
+    }
+    char* base = h->hist.d_rb;
+    double *cur = (double*)(base + p.o_cur), *pmax = (double*)(base + p.o_pmax), *rowmax = (double*)(base + p.o_rmax), *d_y = (double*)(base + p.o_y);
+    uint64_t* psum = (uint64_t*)(base + p.o_psum);
+    SmoothRow* d_rows = (SmoothRow*)(base + p.o_rows);
+    int* dead = (int*)(base + p.o_dead);
+    int32_t *d_counts = (int32_t*)(base + p.o_counts), *d_idx = (int32_t*)(base + p.o_idx);
+    double *d_vol = (double*)(base + p.o_vol), *d_tmean = (double*)(base + p.o_tmean), *d_tvar = (double*)(base + p.o_tvar);
+    double *d_tdraw = tdraw ? (double*)(base + p.o_tdraw) : nullptr, *d_stmp = (double*)(base + p.o_stmp), *d_out = (double*)(base + p.o_out);
+    hipStream_t s = h->stream;
+    HIPCHK(hipEventRecord(h->ev0, s));
+    HIPCHK(hipMemcpyAsync(d_rows, rows.data(), nt * sizeof(SmoothRow), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_counts, cnt.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_y, y, (size_t)T * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(dead, 0, nt * sizeof(int), s));
+    hipLaunchKernelGGL(k_smooth_dead, dim3((unsigned)T, (unsigned)nt), dim3(256), 0, s, n, (int)nt, h->hist.d_w, dead);
+    HIPCHK(hipGetLastError());
+    const int64_t wg256 = ((M + 255) / 256) * (int64_t)nt * p.nchunk;
+    const int threads = wg256 >= 1024 ? 256 : 64;
+    const bool direct = p.nchunk <= SMOOTH_MAX_DIRECT;
+    for (int64_t t = T - 1; t >= 0; --t) {
+        PathArgs a{};
+        a.n = n; a.M = M; a.ntheta = (int)nt; a.nchunk = p.nchunk;
+        a.last = t == T - 1; a.t = (uint32_t)t; a.seed = path_seed; a.y = y[t];
+        a.x_t = h->hist.d_x + (size_t)t * nw * d; a.w_t = h->hist.d_w + (size_t)t * nw;
+        a.cur = cur; a.pmax = pmax; a.rmax = direct ? pmax : rowmax; a.nmax = direct ? p.nchunk : 1; a.psum = psum;
+        a.rows = d_rows; a.dead = dead; a.counts = d_counts; a.stream = h->d_stream;
+        a.idx_n = d_idx + (size_t)(t + 1 < T ? t + 1 : t) * pw; a.idx_t = d_idx + (size_t)t * pw;
+        a.xs_t = d_vol + (size_t)t * 2 * pw;
+        HIPCHK(path_step<MODEL_UCSV_RB>(a, threads, rowmax, s));
+    }
+    RbTrendArgs ta{T, M, (int)nt, path_seed, h->d_params, h->d_stream, d_y, d_idx, d_vol, d_tmean, d_tvar, d_tdraw};
+    hipLaunchKernelGGL(k_rb_trend, dim3((unsigned)((M + 63) / 64), (unsigned)nt), dim3(64), 0, s, ta);
+    HIPCHK(hipGetLastError());
+    if (out) {
+        hipLaunchKernelGGL(k_rb_summary, dim3((unsigned)T, (unsigned)nt), dim3(256), 0, s, M, (int)nt, p.mchunk, d_idx, d_counts, d_tmean, d_tvar, d_vol,
+                           d_stmp, d_out);
+        HIPCHK(hipGetLastError());
+    }
+    int rc = finish_elapsed(h);
+    if (rc) return rc;
+    if (idx) HIPCHK(hipMemcpy(idx, d_idx, (size_t)T * pw * 4, hipMemcpyDeviceToHost));
+    if (vol) HIPCHK(hipMemcpy(vol, d_vol, (size_t)T * 2 * pw * 8, hipMemcpyDeviceToHost));
+    if (tmean) HIPCHK(hipMemcpy(tmean, d_tmean, (size_t)T * pw * 8, hipMemcpyDeviceToHost));
+    if (tvar) HIPCHK(hipMemcpy(tvar, d_tvar, (size_t)T * pw * 8, hipMemcpyDeviceToHost));
+    if (tdraw) HIPCHK(hipMemcpy(tdraw, d_tdraw, (size_t)T * pw * 8, hipMemcpyDeviceToHost));
+    if (out) HIPCHK(hipMemcpy(out, d_out, (size_t)T * nt * 8 * 8, hipMemcpyDeviceToHost));
     return SMC_OK;
 }

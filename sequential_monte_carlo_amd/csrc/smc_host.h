@@ -118,6 +118,8 @@ struct smc_filter_s {
         size_t tmp_bytes = 0;
         char* d_path = nullptr;                // backward simulation (smc_sample_paths), its own block: cur | pmax | psum | rmax | rows |
         size_t path_bytes = 0;                 //   dead | counts | idx [T][ntheta][M] | xs [T][d][ntheta][M]
+        char* d_rb = nullptr;                  // Rao-Blackwellised backward simulation (smc_rb_sample_paths), its own block
+        size_t rb_bytes = 0;
     } hist;
     struct {   // PMMH rejuvenation (smc_capi_pmmh.hip): this handle holds the proposal filters
         smc::PmmhSpec spec{};

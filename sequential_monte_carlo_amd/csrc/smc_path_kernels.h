@@ -38,8 +38,14 @@ struct PathArgs {
     const uint32_t* stream;// [ntheta] Philox stream ids
     const int32_t* idx_n;  // [ntheta][M] idx[t + 1] (unused at the last step)
     int32_t* idx_t;        // [ntheta][M] idx[t]
-    double* xs_t;          // [d][ntheta][M] the paths' states at step t, or nullptr
+    double* xs_t;          // [d][ntheta][M] the paths' states at step t, or nullptr (MODEL_UCSV_RB: [2][ntheta][M], the chosen lse, lsn)
+    double y;              // MODEL_UCSV_RB: the observation of step t
 };
+
+// The pair policy of a family.  The three families with a transition density stage (m[D], s, g) and own the state x_{t+1}
+// (logf_source / logf_pair); MODEL_UCSV_RB (smc_spec.h "Rao-Blackwellised backward simulation") stages
+// (m, V, lse, lsn, g) and owns (a+, b+, mu, tau): the same passes and the same selection over another chain.
+template <int MODEL> struct path_nv { static constexpr int value = MODEL == MODEL_UCSV_RB ? RB_NV : model_dim<MODEL>::value + 2; };
 
 // (m[D], s, g) of source l as the pair chain wants them; false: not live
 template <int MODEL>
@@ -47,7 +53,11 @@ __device__ __forceinline__ bool path_source(const PathArgs& a, const SmoothRow& 
     constexpr int D = model_dim<MODEL>::value;
     const double wl = l < a.n ? a.w_t[row + l] : 0.0;
     if (!(wl > 0.0)) return false;
-    if (a.last) {
+    if constexpr (MODEL == MODEL_UCSV_RB) {
+        double xs[D];
+        for (int r = 0; r < D; ++r) xs[r] = a.last ? 0.0 : a.x_t[(size_t)r * plane + row + l];
+        rb_source(a.last, xs, wl, v);
+    } else if (a.last) {
         for (int r = 0; r < D + 1; ++r) v[r] = 0.0;
         v[D + 1] = sp_log(wl);
     } else {
@@ -58,11 +68,50 @@ __device__ __forceinline__ bool path_source(const PathArgs& a, const SmoothRow& 
     }
     return true;
 }
+// a source that is left out: never the maximum, q = 0
+template <int MODEL>
+__device__ __forceinline__ void path_no_source(double* v) {
+    constexpr int NV = path_nv<MODEL>::value;
+    for (int r = 0; r < NV - 1; ++r) v[r] = 0.0;
+    v[NV - 1] = -inf();
+}
+// what the owner holds of step t + 1; at the last step the values with which the chain returns g
+template <int MODEL>
+__device__ __forceinline__ void path_owner(const PathArgs& a, size_t pplane, size_t prow, int64_t p, double* xo) {
+    constexpr int D = model_dim<MODEL>::value;
+    for (int r = 0; r < D; ++r) xo[r] = a.last ? (MODEL == MODEL_UCSV_RB && r == 3 ? 1.0 : 0.0) : a.cur[(size_t)r * pplane + prow + p];
+}
+template <int MODEL>
+__device__ __forceinline__ double path_pair(const SmoothRow& k, const double* v, const double* xo) {
+    constexpr int D = model_dim<MODEL>::value;
+    if constexpr (MODEL == MODEL_UCSV_RB) return rb_pair(k, v, xo);
+    else return logf_pair<MODEL>(k, v, v[D], v[D + 1], xo);
+}
+// MODEL_UCSV_RB, after the pick: the information update of the owner and the chosen volatilities (one thread per path)
+__device__ __forceinline__ void rb_commit(const PathArgs& a, size_t row, size_t plane, size_t prow, size_t pplane, int64_t p, int64_t pick) {
+    const double nan = bits2d(0x7ff8000000000000ULL);
+    double lse = nan, lsn = nan, mu = nan, tau = nan;
+    if (pick >= 0) {
+        lse = a.x_t[plane + row + pick];
+        lsn = a.x_t[2 * plane + row + pick];
+        mu = a.last ? 0.0 : a.cur[2 * pplane + prow + p];
+        tau = a.last ? 0.0 : a.cur[3 * pplane + prow + p];
+        rb_info(a.last, lse, lsn, a.y, mu, tau);
+    }
+    a.cur[prow + p] = lse;
+    a.cur[pplane + prow + p] = lsn;
+    a.cur[2 * pplane + prow + p] = mu;
+    a.cur[3 * pplane + prow + p] = tau;
+    if (a.xs_t) {
+        a.xs_t[prow + p] = lse;
+        a.xs_t[pplane + prow + p] = lsn;
+    }
+}
 
 template <int MODEL, int PASS>
 __global__ void k_path_pairs(PathArgs a) {
     constexpr int D = model_dim<MODEL>::value;
-    constexpr int NV = D + 2;
+    constexpr int NV = path_nv<MODEL>::value;
     __shared__ double sm[SMOOTH_CH][NV];
     const int th = blockIdx.y, ch = blockIdx.z;
     // (uniform over the workgroup: nobody waits at the barrier below)
@@ -72,23 +121,20 @@ __global__ void k_path_pairs(PathArgs a) {
     const SmoothRow k = a.rows[th];
     for (int q = threadIdx.x; q < SMOOTH_CH; q += blockDim.x) {
         double v[NV];
-        if (!path_source<MODEL>(a, k, row, plane, (int64_t)ch * SMOOTH_CH + q, v)) {   // left out: never the maximum, q = 0
-            for (int r = 0; r < D + 1; ++r) v[r] = 0.0;
-            v[D + 1] = -inf();
-        }
+        if (!path_source<MODEL>(a, k, row, plane, (int64_t)ch * SMOOTH_CH + q, v)) path_no_source<MODEL>(v);
         for (int r = 0; r < NV; ++r) sm[q][r] = v[r];
     }
     __syncthreads();
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= a.M) return;
     double xo[D];
-    for (int r = 0; r < D; ++r) xo[r] = a.last ? 0.0 : a.cur[(size_t)r * pplane + prow + p];
+    path_owner<MODEL>(a, pplane, prow, p, xo);
     const size_t o = ((size_t)ch * a.ntheta + th) * a.M + p;
     if constexpr (PASS == 0) {
         double M = -inf();
 #pragma unroll 8
         for (int q = 0; q < SMOOTH_CH; ++q) {
-            const double b = logf_pair<MODEL>(k, sm[q], sm[q][D], sm[q][D + 1], xo);
+            const double b = path_pair<MODEL>(k, sm[q], xo);
             M = b > M ? b : M;
         }
         a.pmax[o] = M;
@@ -101,7 +147,7 @@ __global__ void k_path_pairs(PathArgs a) {
         uint64_t S = 0;
 #pragma unroll 4
         for (int q = 0; q < SMOOTH_CH; ++q) {
-            const double b = logf_pair<MODEL>(k, sm[q], sm[q][D], sm[q][D + 1], xo);
+            const double b = path_pair<MODEL>(k, sm[q], xo);
             S += path_weight(b, M);
         }
         a.psum[o] = S;
@@ -140,21 +186,25 @@ __global__ void k_path_select(PathArgs a) {
                 C += s;
             }
             double xo[D];
-            for (int r2 = 0; r2 < D; ++r2) xo[r2] = a.last ? 0.0 : a.cur[(size_t)r2 * pplane + prow + p];
+            path_owner<MODEL>(a, pplane, prow, p, xo);
             const int64_t l0 = (int64_t)ch * SMOOTH_CH, l1 = l0 + SMOOTH_CH < a.n ? l0 + SMOOTH_CH : a.n;
             for (int64_t l = l0; l < l1; ++l) {
-                double v[D + 2];
+                double v[path_nv<MODEL>::value];
                 if (!path_source<MODEL>(a, k, row, plane, l, v)) continue;
-                C += path_weight(logf_pair<MODEL>(k, v, v[D], v[D + 1], xo), M);
+                C += path_weight(path_pair<MODEL>(k, v, xo), M);
                 if (C > r) { pick = l; break; }
             }
         }
     }
     a.idx_t[prow + p] = (int32_t)pick;
-    for (int r = 0; r < D; ++r) {
-        const double xv = pick >= 0 ? a.x_t[(size_t)r * plane + row + pick] : bits2d(0x7ff8000000000000ULL);
-        a.cur[(size_t)r * pplane + prow + p] = xv;
-        if (a.xs_t) a.xs_t[(size_t)r * pplane + prow + p] = xv;
+    if constexpr (MODEL == MODEL_UCSV_RB) {
+        rb_commit(a, row, plane, prow, pplane, p, pick);
+    } else {
+        for (int r = 0; r < D; ++r) {
+            const double xv = pick >= 0 ? a.x_t[(size_t)r * plane + row + pick] : bits2d(0x7ff8000000000000ULL);
+            a.cur[(size_t)r * pplane + prow + p] = xv;
+            if (a.xs_t) a.xs_t[(size_t)r * pplane + prow + p] = xv;
+        }
     }
 }
 
@@ -224,12 +274,12 @@ __global__ void k_path_select_wave(PathArgs a) {
                 }
             }
             double xo[D];
-            for (int r2 = 0; r2 < D; ++r2) xo[r2] = a.last ? 0.0 : a.cur[(size_t)r2 * pplane + prow + p];
+            path_owner<MODEL>(a, pplane, prow, p, xo);
             for (int b = 0; b < SMOOTH_CH / 64 && ch >= 0 && pick < 0; ++b) {
                 const int64_t l0 = (int64_t)ch * SMOOTH_CH + b * 64;
-                double v[D + 2];
+                double v[path_nv<MODEL>::value];
                 uint64_t q = 0;
-                if (path_source<MODEL>(a, k, row, plane, l0 + lane, v)) q = path_weight(logf_pair<MODEL>(k, v, v[D], v[D + 1], xo), M);
+                if (path_source<MODEL>(a, k, row, plane, l0 + lane, v)) q = path_weight(path_pair<MODEL>(k, v, xo), M);
                 const uint64_t inc = wave_scan_u64(q, lane);
                 const unsigned long long hit = __ballot(C + inc > r);
                 if (hit) pick = l0 + (__ffsll((long long)hit) - 1);
@@ -238,7 +288,9 @@ __global__ void k_path_select_wave(PathArgs a) {
         }
     }
     if (lane == 0) a.idx_t[prow + p] = (int32_t)pick;
-    if (lane < D) {
+    if constexpr (MODEL == MODEL_UCSV_RB) {
+        if (lane == 0) rb_commit(a, row, plane, prow, pplane, p, pick);
+    } else if (lane < D) {
         const double xv = pick >= 0 ? a.x_t[(size_t)lane * plane + row + pick] : bits2d(0x7ff8000000000000ULL);
         a.cur[(size_t)lane * pplane + prow + p] = xv;
         if (a.xs_t) a.xs_t[(size_t)lane * pplane + prow + p] = xv;

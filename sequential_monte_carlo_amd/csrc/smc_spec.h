@@ -976,7 +976,7 @@ SMC_HD void combine_outputs(double K, uint64_t Dtot, uint64_t Rtot, int SH, int6
 //           (the reference's conventions: the trend moves with the PREVIOUS lse, sd exp(lse / 2); the gammas are standard deviations)
 //   pair    d_r = x[r] - m[r];   one row: fma(d0 d0, s, g);   UCSV3D: fma(d0 d0, s, fma(d1 d1, nh1, fma(d2 d2, nh2, g)))
 // with g = c for logf itself and g = sp_log(w) + c for a_lj.  MODEL_UCSV_RB has no transition density of its rows (m and P are
-// functions of the whole path): no smoother.
+// functions of the whole path): no smoother of this kind; "Rao-Blackwellised backward simulation" below is its smoother.
 #ifndef SMC_SMOOTH_CH
 #define SMC_SMOOTH_CH 128
 #endif
@@ -1105,6 +1105,80 @@ SMC_HD uint64_t mulhi64(uint64_t a, uint64_t b) {
 #else
     return (uint64_t)(((unsigned __int128)a * b) >> 64);
 #endif
+}
+
+// ---- Rao-Blackwellised backward simulation (Lindsten, Bunch, Saerkkae, Schoen and Godsill 2016) ---------------
+// MODEL_UCSV_RB has no transition density of its four rows, but its two log-volatilities are an autonomous Markov chain and the
+// trend is linear-Gaussian given their path.  So the walk of "backward simulation" above runs over the VOLATILITIES alone, with
+// the trend integrated out on both sides: forward by the rows (m, P) the filter recorded, backward by one scalar information
+// recursion per path.  Inputs: the recorded clouds (rows (m, lse, lsn, P), the posterior after y_t; dense weights w_t),
+// t = 0..T-1, of one filter, UCSV's parameter row (g_eps, g_eta, x0, lse0, lsn0), y, a path seed and the filter's Philox stream
+// id.  Path p is a function of these alone: not of M, the other paths, the batch or the launch geometry.
+// THE WALK, t = T-1 .. 0.  The owner holds (a+, b+, mu, tau): the lse and lsn of the particle chosen at t+1, and the information
+// of y_{t+1:T} about x_{t+1} as a pseudo-observation mu of x_{t+1} with variance tau.
+//   a source l is live iff w_t^l > 0
+//   staged (rb_source): (m_l, V_l = P_l + sp_exp(lse_l), lse_l, lsn_l, g_l = sp_log(w_t^l));  V_l is the predictive variance of
+//         x_{t+1}.  At the last step (0, 0, 0, 0, g_l), and the owner reads (0, 0, 0, 1): the chain below returns g_l exactly
+//   b_l = rb_pair: with d1 = a+ - lse_l, d2 = b+ - lsn_l, e = mu - m_l, D = V_l + tau, nh1 = -0.5 / g_eps^2, nh2 = -0.5 / g_eta^2,
+//         fma(d1 d1, nh1, fma(d2 d2, nh2, fma(-0.5, sp_log(D), fma(-0.5, (e e) / D, g_l))))        ONE log and ONE division;
+//         NaN when D is not a positive finite number: such a source is left out (q = 0, never the maximum).  The terms common
+//         to all sources (-log g_eps - log g_eta - 3 HALF_LOG2PI) are dropped
+//   M_p, q_l = path_weight(b_l, M_p), S, u = path_uniform(seed, p, stream, t), r and idx[t][p] exactly as in backward simulation
+//   after the pick i (rb_info), R = sp_exp(lsn_i):
+//         last step:  mu <- y_t,  tau <- R
+//         before it:  tau' = tau + sp_exp(lse_i);  K = R / (R + tau');  mu <- fma(K, mu - y_t, y_t);  tau <- min(K tau', R)
+//   vol[t][.][p] = (lse_i, lsn_i)
+// Zero-weight sources are never chosen whatever their states; a path with S = 0 reads -1 / NaN from there back; a filter that
+// collapsed at any recorded step reads -1 / NaN everywhere.
+// THE TREND PASS, once per complete path (idx[0][p] >= 0), serial in t.  Forward (rb_trend_step, model_marginal_step's order):
+//   Q = sp_exp(t == 0 ? lse0 : lse_{t-1});  (m-, P-) = t == 0 ? (x0, Q) : (m_{t-1}, P_{t-1} + Q);  R = sp_exp(lsn_t)
+//   S = P- + R;  iS = 1 / S;  K = P- iS;  m_t = fma(K, y_t - m-, m-);  P_t = min(K R, P-)
+// then rts_back(A = 1, Q = sp_exp(lse_t), m_t, P_t) from (m_{T-1}, P_{T-1}) gives tmean[t][p], tvar[t][p], and the joint draw
+//   tdraw[T-1] = rts_path_last(m, P, z),  tdraw[t] = rts_path_back(1, sp_exp(lse_t), m_t, P_t, tdraw[t+1], z)
+//   z = box_muller(draw(seed, p >> 1, stream, t, SLOT_RB_TREND)): z0 for an even p, z1 for an odd one
+// (x_t = m_t + G (x_{t+1} - m_t) + sqrt(G Q) z with G = P_t / P-_{t+1}; G Q is formed as (P_t Q) / P-_{t+1}, rts_gain's V.)
+// An incomplete path reads NaN at every t.
+// THE SUMMARY over the complete paths p < count of one filter, per step: out[t][0..7] = mean of tmean, mean of tvar (within),
+// population variance of tmean (between), mean and population variance of lse, of lsn, the number of complete paths.  Every sum
+// runs in the smoother's order (smooth_sum over p: chunks of SMOOTH_CH, ascending; an incomplete path adds +0.0), is divided by
+// the count, and the variances are CENTRED second passes.  No complete path: NaN, and the count 0.
+constexpr uint32_t SLOT_RB_TREND = 37u;           // no other draw uses it (SLOT_PATH is 35, SLOT_RTS 36)
+constexpr int RB_NV = 5;                          // doubles staged per source
+SMC_HD void rb_source(bool last, const double* xs /*(m, lse, lsn, P)*/, double wl, double* v /*[RB_NV]*/) {
+    v[0] = last ? 0.0 : xs[0];
+    v[1] = last ? 0.0 : xs[3] + sp_exp(xs[1]);
+    v[2] = last ? 0.0 : xs[1];
+    v[3] = last ? 0.0 : xs[2];
+    v[4] = sp_log(wl);
+}
+SMC_HD double rb_pair(const SmoothRow& k, const double* v /*[RB_NV]*/, const double* o /*(a+, b+, mu, tau)*/) {
+    const double d1 = o[0] - v[2], d2 = o[1] - v[3], e = o[2] - v[0], D = v[1] + o[3];
+    const bool ok = D > 0.0 && D < inf();
+    const double Ds = ok ? D : 1.0;
+    const double b = fma(d1 * d1, k.nh1, fma(d2 * d2, k.nh2, fma(-0.5, sp_log(Ds), fma(-0.5, (e * e) / Ds, v[4]))));
+    return ok ? b : bits2d(0x7ff8000000000000ULL);
+}
+// (mu, tau): the information about x_{t+1} in, about x_t out, once the particle (lse, lsn) of step t is chosen
+SMC_HD void rb_info(bool last, double lse, double lsn, double y, double& mu, double& tau) {
+    const double R = sp_exp(lsn);
+    const double tp = tau + sp_exp(lse), K = R / (R + tp), Kt = K * tp;
+    mu = last ? y : fma(K, mu - y, y);
+    tau = last ? R : (Kt < R ? Kt : R);
+}
+// (m, P) of step t-1 in (not read when first), of step t out
+SMC_HD void rb_trend_step(const double* raw, bool first, double lse_prev, double lsn, double y, double& m, double& P) {
+    const double Q = sp_exp(first ? raw[3] : lse_prev);
+    const double m0 = first ? raw[2] : m, Pm = first ? Q : P + Q;
+    const double R = sp_exp(lsn);
+    const double S = Pm + R, iS = 1.0 / S, e = y - m0;
+    const double K = Pm * iS, KR = K * R;
+    m = fma(K, e, m0);
+    P = KR < Pm ? KR : Pm;
+}
+SMC_HD double rb_trend_normal(uint64_t seed, int64_t p, uint32_t stream, uint32_t t) {
+    double z0, z1;
+    box_muller(draw(seed, (uint32_t)(p >> 1), stream, t, SLOT_RB_TREND), z0, z1);
+    return (p & 1) ? z1 : z0;
 }
 
 }  // namespace smc

@@ -630,3 +630,121 @@ extern "C" int smc_host_sample_paths(int model_id, const double* raw, int64_t T,
     else host_paths_t<MODEL_UCSV3D>(k, T, n, x, w, M, path_seed, stream, idx, xs);
     return SMC_OK;
 }
+
+// ---- Rao-Blackwellised backward simulation on the host (smc_spec.h; the twin of smc_rb_sample_paths for ONE filter) -------------
+extern "C" int smc_host_rb_sample_paths(const double* raw, int64_t T, int64_t n, const double* x, const double* w, const double* y, int64_t M,
+                                        uint64_t path_seed, uint32_t stream, int32_t* idx, double* vol, double* tmean, double* tvar, double* tdraw,
+                                        double* out) {
+    if (!raw || !x || !w || !y || !idx || !vol || !tmean || !tvar) return fail(SMC_EINVAL, "smc_host_rb_sample_paths: NULL argument");
+    if (T < 1 || n < 1) return fail(SMC_EINVAL, "smc_host_rb_sample_paths: T and n must be positive");
+    if (M < 1 || M > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_host_rb_sample_paths: M must be in [1, 2^30]");
+    if (n > PATH_MAX_N) return fail(SMC_EINVAL, "smc_host_rb_sample_paths: more than 2^20 particles");
+    for (int64_t t = 0; t < T; ++t)
+        if (!(y[t] - y[t] == 0.0)) return fail(SMC_EINVAL, "smc_host_rb_sample_paths: y is not finite");
+    SmoothRow k;
+    if (!smooth_row(MODEL_UCSV3D, raw, k)) return fail(SMC_EINVAL, "smc_host_rb_sample_paths: a gamma is not a positive finite number");
+    const size_t sx = (size_t)4 * n;
+    const double nan = bits2d(0x7ff8000000000000ULL);
+    bool dead = false;   // a filter that collapsed at a recorded step: no path
+    for (int64_t t = 0; t < T && !dead; ++t) {
+        bool any = false;
+        for (int64_t i = 0; i < n; ++i) any = any || w[(size_t)t * n + i] > 0.0;
+        dead = !any;
+    }
+    std::vector<double> sv((size_t)RB_NV * n), b((size_t)n), own((size_t)4 * M, 0.0);
+    for (int64_t t = T - 1; t >= 0; --t) {
+        const bool last = t == T - 1;
+        const double *xt = x + (size_t)t * sx, *wt = w + (size_t)t * n;
+        for (int64_t l = 0; l < n; ++l) {
+            if (!(wt[l] > 0.0)) continue;
+            const double xs[4] = {xt[l], xt[(size_t)n + l], xt[(size_t)2 * n + l], xt[(size_t)3 * n + l]};
+            rb_source(last, xs, wt[l], &sv[(size_t)RB_NV * l]);
+        }
+        for (int64_t p = 0; p < M; ++p) {
+            int64_t pick = -1;
+            double* o = &own[(size_t)4 * p];
+            if (!dead && (last || idx[(size_t)(t + 1) * M + p] >= 0)) {
+                const double first[4] = {0.0, 0.0, 0.0, 1.0};
+                const double* oo = last ? first : o;
+                double Mx = -inf();
+                for (int64_t l = 0; l < n; ++l) {
+                    if (!(wt[l] > 0.0)) continue;
+                    b[l] = rb_pair(k, &sv[(size_t)RB_NV * l], oo);
+                    Mx = b[l] > Mx ? b[l] : Mx;
+                }
+                uint64_t S = 0;
+                for (int64_t l = 0; l < n; ++l)
+                    if (wt[l] > 0.0) S += path_weight(b[l], Mx);
+                if (S) {
+                    const uint64_t r = mulhi64(path_uniform(path_seed, p, stream, (uint32_t)t), S);
+                    uint64_t C = 0;
+                    for (int64_t l = 0; l < n; ++l) {
+                        if (!(wt[l] > 0.0)) continue;
+                        C += path_weight(b[l], Mx);
+                        if (C > r) { pick = l; break; }
+                    }
+                }
+            }
+            idx[(size_t)t * M + p] = (int32_t)pick;
+            double lse = nan, lsn = nan;
+            if (pick >= 0) {
+                lse = xt[(size_t)n + pick];
+                lsn = xt[(size_t)2 * n + pick];
+                double mu = last ? 0.0 : o[2], tau = last ? 0.0 : o[3];
+                rb_info(last, lse, lsn, y[t], mu, tau);
+                o[0] = lse; o[1] = lsn; o[2] = mu; o[3] = tau;
+            }
+            vol[((size_t)t * 2) * M + p] = lse;
+            vol[((size_t)t * 2 + 1) * M + p] = lsn;
+        }
+    }
+    // the trend pass
+    for (int64_t p = 0; p < M; ++p) {
+        if (idx[p] < 0) {
+            for (int64_t t = 0; t < T; ++t) {
+                tmean[(size_t)t * M + p] = tvar[(size_t)t * M + p] = nan;
+                if (tdraw) tdraw[(size_t)t * M + p] = nan;
+            }
+            continue;
+        }
+        double m = 0.0, P = 0.0, lse_prev = 0.0;
+        for (int64_t t = 0; t < T; ++t) {
+            rb_trend_step(raw, t == 0, lse_prev, vol[((size_t)t * 2 + 1) * M + p], y[t], m, P);
+            tmean[(size_t)t * M + p] = m;
+            tvar[(size_t)t * M + p] = P;
+            lse_prev = vol[((size_t)t * 2) * M + p];
+        }
+        double xs = m, Ps = P, xd = 0.0;
+        if (tdraw) tdraw[(size_t)(T - 1) * M + p] = xd = rts_path_last(m, P, rb_trend_normal(path_seed, p, stream, (uint32_t)(T - 1)));
+        for (int64_t t = T - 2; t >= 0; --t) {
+            const double Q = sp_exp(vol[((size_t)t * 2) * M + p]);
+            const double mf = tmean[(size_t)t * M + p], Pf = tvar[(size_t)t * M + p];
+            rts_back(1.0, Q, mf, Pf, xs, Ps);
+            tmean[(size_t)t * M + p] = xs;
+            tvar[(size_t)t * M + p] = Ps;
+            if (tdraw) tdraw[(size_t)t * M + p] = xd = rts_path_back(1.0, Q, mf, Pf, xd, rb_trend_normal(path_seed, p, stream, (uint32_t)t));
+        }
+    }
+    // the summary over the complete paths
+    if (out) {
+        int64_t cnt = 0;
+        for (int64_t p = 0; p < M; ++p) cnt += idx[p] >= 0 ? 1 : 0;
+        const double dcnt = (double)cnt;
+        for (int64_t t = 0; t < T; ++t) {
+            const double* series[4] = {tmean + (size_t)t * M, tvar + (size_t)t * M, vol + ((size_t)t * 2) * M, vol + ((size_t)t * 2 + 1) * M};
+            const int col_mean[4] = {0, 1, 3, 5}, col_var[4] = {2, -1, 4, 6};
+            double* o = out + (size_t)t * 8;
+            for (int r = 0; r < 4; ++r) {
+                const double* v = series[r];
+                const double mean = smooth_sum(M, [&](int64_t p) { return idx[p] >= 0 ? v[p] : 0.0; }) / dcnt;
+                o[col_mean[r]] = cnt ? mean : nan;
+                if (col_var[r] >= 0) {
+                    const double var = smooth_sum(M, [&](int64_t p) { const double e = v[p] - mean; return idx[p] >= 0 ? e * e : 0.0; }) / dcnt;
+                    o[col_var[r]] = cnt ? var : nan;
+                }
+            }
+            o[7] = dcnt;
+        }
+    }
+    return SMC_OK;
+}

@@ -341,7 +341,7 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
                                     (the other slots read -1 / NaN); smooth=False skips the backward pass of the marginals (no
                                     s["mean"], s["var"]).  A batch holds T n_theta M entries: keep M small there.
     The backward pass costs 2 N^2 (T - 1) transition densities per filter.  Any proposal, either resampler; MarginalUCSV has no
-    smoother (its state rows have no transition density): smooth a UCSV filter.
+    smoother of this kind (its state rows have no transition density): rb_smoother is its smoother.
     rows=(model id, parameter rows [n_theta][n_raw]) with model=None: a batch given as rows (what the samplers hold)."""
     if seed is None:
         seed = next(_seed_counter)
@@ -377,4 +377,53 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
             s["weights"], s["x"] = (ws[:, 0], xs[:, 0]) if f.single else (ws, xs)
     finally:
         h.history_end()
+    return Particles(f), Weights(f), f.out(logZ), s
+
+
+def rb_smoother(N, y, model, paths=256, seed=None, path_seed=None, draws=False, per_path=False, path_counts=None, seg=0, device=0,
+                streams=None, resampler="multinomial", rows=None):
+    """x, w, logZ, s = rb_smoother(N, y, model, paths=M): the smoother of MarginalUCSV (one model or a list of them).  The marginal
+    filter of log_likelihood is run step by step with its clouds recorded on the device; then M volatility paths per filter are
+    drawn from p(lse_1:T, lsn_1:T | y_1:T) by Rao-Blackwellised backward simulation, and the trend comes exactly given each path
+    from a Kalman filter and an RTS pass along it.  x, w, logZ are the filter's; s describes the smoothed law:
+        s["trend_mean"][t], s["trend_var"][t]  mean and variance of p(x_t | y_1:T): the mean over the paths of the per-path mean,
+                                    and within (mean of the per-path variances) + between (variance of the per-path means)
+        s["vol_mean"], s["vol_var"] [T][2]: smoothed mean and variance of (lse, lsn)
+        s["n_paths"]                [T]: the number of complete paths behind them
+        s["logmu"], s["ess"]        the filter's per-step log-likelihood increments and effective sample sizes
+        per_path=True:  s["path_index"] [T][M] int32, s["vol_paths"] [T][M][2], s["path_trend_mean"], s["path_trend_var"] [T][M]
+        draws=True:     s["paths"] [T][M][3]: joint draws of (x, lse, lsn) from p(x_1:T, lse_1:T, lsn_1:T | y_1:T)
+    With a list of models a batch axis follows T everywhere, as in smoother.  path_seed: the seed of the walk's draws (default:
+    derived from the filter seed); path_counts [n_theta]: draw only that many paths of each filter.  Either resampler.
+    rows=(model id, parameter rows [n_theta][5]) with model=None: a batch given as rows (what the samplers hold)."""
+    if seed is None:
+        seed = next(_seed_counter)
+    f = _Filters(int(N), model, seed, seg, device, streams, False, resampler, None, rows=rows)
+    if f.model_id != _lib.MODEL_UCSV_RB:
+        raise TypeError("rb_smoother is the smoother of MarginalUCSV; the other families have a transition density: smoother")
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    T, h = y.size, f.h
+    if T < 1:
+        raise ValueError("rb_smoother needs at least one observation")
+    h.history_begin(T)
+    try:
+        lm, es = np.zeros((T, h.n_theta)), np.zeros((T, h.n_theta))
+        lm[0] = h.init(float(y[0]))
+        es[0] = h.logZ()[1]
+        for t in range(1, T):
+            lm[t], es[t] = h.step(float(y[t]))
+        logZ = h.logZ()[0]
+        r = h.rb_sample_paths(y, int(paths), _path_seed(seed) if path_seed is None else int(path_seed), counts=path_counts, draws=draws,
+                              per_path=per_path)
+    finally:
+        h.history_end()
+    pick = (lambda a: a[:, 0]) if f.single else (lambda a: a)
+    o = r["out"]
+    s = {"trend_mean": pick(o[..., 0]), "trend_var": pick(o[..., 1] + o[..., 2]), "vol_mean": pick(o[..., [3, 5]]), "vol_var": pick(o[..., [4, 6]]),
+         "n_paths": pick(o[..., 7]), "logmu": pick(lm), "ess": pick(es)}
+    if per_path:
+        s["path_index"], s["path_trend_mean"], s["path_trend_var"] = pick(r["idx"]), pick(r["tmean"]), pick(r["tvar"])
+        s["vol_paths"] = pick(np.moveaxis(r["vol"], 1, -1))                          # [T][n_theta][M][2]
+    if draws:
+        s["paths"] = pick(np.concatenate([r["tdraw"][..., None], np.moveaxis(r["vol"], 1, -1)], axis=-1))   # [T][n_theta][M][3]
     return Particles(f), Weights(f), f.out(logZ), s

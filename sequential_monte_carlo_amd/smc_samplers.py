@@ -650,6 +650,76 @@ def smoothed_paths(smc, y, M, N=None, max_bytes=2 ** 31, seed=None):
     return out[..., 0] if d == 1 else out
 
 
+def rb_smoothed_state(smc, y, M, N=None, max_bytes=2 ** 31, seed=None):
+    """The smoothed trend and volatilities of a sampler over MarginalUCSV, integrated over its current parameter cloud by
+    Rao-Blackwellised backward simulation (particles.rb_smoother): a dict with "trend_mean", "trend_var" [T],
+    "vol_mean", "vol_var" [T][2] and "n_paths" [T].  The parameter particle of each of the M paths is drawn from omega through the
+    library's own outer resampler, as smoothed_paths draws it, which gives a count per parameter particle; fresh batched recorded
+    filters (N particles each, default the sampler's N) run over the parameter particles with a positive count, in blocks whose
+    record and paths stay under max_bytes, and filter m draws its count of paths.  Every complete path weighs the same: with
+    c_m complete paths of parameter particle m, mean = sum c_m mean_m / sum c_m and var = within + between of that mixture, for
+    the trend var = sum c_m (within_m + between_m + (mean_m - mean)^2) / sum c_m.  Filter m uses Philox stream m, so the result
+    does not depend on the blocks.  seed: the Philox seed of the filters, the ancestors and the walk (default: derived from the
+    sampler's seed; the sampler's own state is not touched)."""
+    if isinstance(smc, IBIS):
+        raise TypeError("rb_smoothed_state: IBIS is out of scope: its exact smoother is RTS (rts_smoothed_state)")
+    from .particles import rb_smoother
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    M = int(M)
+    if M < 1:
+        raise ValueError("M must be positive")
+    N = smc.N if N is None else int(N)
+    mid, raw = _rows(smc._models(smc.theta))
+    if int(mid) != _lib.MODEL_UCSV_RB:
+        raise TypeError("rb_smoothed_state needs a sampler over MarginalUCSV; the other families have smoothed_state")
+    seed = (((smc.seed << 20) | 0x4B5A7) if seed is None else int(seed)) & _U64
+    smc._sync_outer()
+    anc = np.asarray(_lib.host_outer_resample(smc.logw, M, (seed + 1) & _U64), dtype=np.int64)
+    counts = np.bincount(anc, minlength=smc.M).astype(np.int32)
+    used = np.flatnonzero(counts)
+    T = y.size
+    outs = np.zeros((T, used.size, 8))
+    b0 = 0
+    while b0 < used.size:                                             # greedy blocks: every filter of a block holds max-count slots
+        b1, cmax = b0, 0
+        while b1 < used.size:
+            c = max(cmax, int(counts[used[b1]]))
+            if b1 > b0 and (b1 + 1 - b0) * T * (N * 5 * 8 + c * (4 + 8 * 4)) > int(max_bytes):
+                break
+            b1, cmax = b1 + 1, c
+        ms = used[b0:b1]
+        h_res = rb_smoother(N, y, None, rows=(int(mid), raw[ms]), seed=seed, device=getattr(smc.backend, "device", 0),
+                            streams=ms.astype(np.uint32), paths=cmax, path_seed=(seed + 2) & _U64, path_counts=counts[ms])[3]
+        outs[:, b0:b1, 0] = h_res["trend_mean"]
+        outs[:, b0:b1, 1] = h_res["trend_var"]
+        outs[:, b0:b1, [3, 5]] = h_res["vol_mean"]
+        outs[:, b0:b1, [4, 6]] = h_res["vol_var"]
+        outs[:, b0:b1, 7] = h_res["n_paths"]
+        b0 = b1
+    return _rb_combine(outs)
+
+
+def _rb_combine(outs):
+    """the mixture over filters of per-filter (mean, variance) pairs weighted by their numbers of complete paths; outs [T][K][8]:
+    columns 0, 1 the trend's mean and total variance, (3, 4) and (5, 6) those of lse and lsn, 7 the count.  Summed in index order"""
+    c = outs[..., 7]
+    keep = c > 0                                                      # (a filter without a complete path has NaN moments)
+    tot = np.add.reduce(c, axis=1)
+    res = {"n_paths": tot}
+    cols = {}
+    for name, (im, iv) in (("trend", (0, 1)), ("lse", (3, 4)), ("lsn", (5, 6))):
+        mk, vk = np.where(keep, outs[..., im], 0.0), np.where(keep, outs[..., iv], 0.0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = np.add.reduce(c * mk, axis=1) / tot
+            dev = np.where(keep, mk - mean[:, None], 0.0)
+            var = np.add.reduce(c * (vk + dev * dev), axis=1) / tot
+        cols[name] = (mean, var)
+    res["trend_mean"], res["trend_var"] = cols["trend"]
+    res["vol_mean"] = np.stack([cols["lse"][0], cols["lsn"][0]], axis=-1)
+    res["vol_var"] = np.stack([cols["lse"][1], cols["lsn"][1]], axis=-1)
+    return res
+
+
 def _integrate(w, rows):
     """[M][np + 1] per-filter (quantiles | variance) rows of every rank -> their omega-weighted means (quantiles [np], variance);
     the products summed over the parameter particles in index order (one definition for every caller: no BLAS in between).
