@@ -14,6 +14,7 @@
  * thread-local message.  Never aborts.  Indices are 0-based int32 (the Julia wrapper adds 1).
  * Layouts: params [n_theta][n_raw] row-major; x [d][n_theta][n_x]; w, anc [n_theta][n_x].
  * A handle is used from one host thread at a time; different handles are independent.
+ * (The threading contract as tested: DESIGN.md, "Host threads".)
  */
 #ifndef SMC_HIP_H
 #define SMC_HIP_H

@@ -160,7 +160,7 @@ hipError_t ensure_breaks(smc_filter_s* h, uint32_t t, uint32_t t_end) {
     cnt = cnt > h->brk_cap ? h->brk_cap : cnt;
     constexpr int TH = 256;
     const size_t lds = ((size_t)v.nseg + 1 + TH / WAVE) * 8;
-    static bool raised[16] = {};   // filters of more than 8187 segments: beyond the default limit of dynamic LDS
+    static std::atomic<bool> raised[16] = {};   // filters of more than 8187 segments: beyond the default limit of dynamic LDS
     hipError_t e = raise_lds_limit(k_breaks<TH>, lds, raised);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_breaks<TH>), dim3(cnt, v.ntheta), dim3(TH), lds, h->stream, v, t, h->d_brk);

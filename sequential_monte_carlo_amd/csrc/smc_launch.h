@@ -3,6 +3,7 @@
 #pragma once
 #include "smc_kernels.h"
 #include "smc_resident.h"
+#include <atomic>
 #include <type_traits>
 
 namespace smc {
@@ -31,16 +32,18 @@ inline hipError_t by_guided_model(int id, F&& f) {
 }
 
 // Kernels that ask for more than the default 64 KiB of dynamic LDS.  The attribute is per device: raise it wherever this
-// process has not done so yet (cheap: a table lookup afterwards).  raised: one table per kernel instantiation.
+// process has not done so yet (cheap: a table lookup afterwards).  raised: one table per kernel instantiation, atomic because
+// handles of different host threads launch the same instantiation (DESIGN.md "Host threads"); two threads that both find it
+// unset both raise the limit, which is harmless.
 template <class K>
-inline hipError_t raise_lds_limit(K kernel, size_t lds, bool (&raised)[16]) {
+inline hipError_t raise_lds_limit(K kernel, size_t lds, std::atomic<bool> (&raised)[16]) {
     if (lds <= 64 * 1024) return hipSuccess;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 16 && raised[dev]) return hipSuccess;
+    if (dev >= 0 && dev < 16 && raised[dev].load(std::memory_order_acquire)) return hipSuccess;
     e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess && dev >= 0 && dev < 16) raised[dev] = true;
+    if (e == hipSuccess && dev >= 0 && dev < 16) raised[dev].store(true, std::memory_order_release);
     return e;
 }
 

@@ -27,7 +27,7 @@ static hipError_t init_t(const FilterView& v, int nxt, double y, hipStream_t s) 
 // wave finds preloaded), the observation, the parameter row, the view
 template <int THREADS, int NP, bool MULTI, bool SYS, bool GTAB, int RPT, bool BYV>
 static hipError_t step_launch(const FilterView& v, const StepHot& hot, int emit_prev, size_t lds, hipStream_t s) {
-    static bool raised[16] = {};   // per instantiation and device
+    static std::atomic<bool> raised[16] = {};   // per instantiation and device
     hipError_t e = raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, SMC_G, BYV>, lds, raised);
     if (e != hipSuccess) return e;
     const StepLead& l = hot.lead;
@@ -92,7 +92,7 @@ template <int THREADS, int NP, bool SYS, bool WIN, bool SUMM = false, bool UNW =
 static hipError_t resident_sys_t(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s) {
     const size_t lds = resident_lds_bytes<SMC_MODEL>(2 * NP * THREADS, THREADS, NP, SUMM ? v.sum_np : -1);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    static bool raised[16] = {};   // per instantiation and device
+    static std::atomic<bool> raised[16] = {};   // per instantiation and device
     hipError_t e = raise_lds_limit(k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW, SMC_G>, lds, raised);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW, SMC_G>), dim3(v.ntheta), dim3(THREADS), lds, s, v, T, recs, t0, bin, bout, win);
@@ -149,7 +149,7 @@ static hipError_t summ_once_m(const FilterView& v, int cur, hipStream_t s) {
     constexpr int D = model_dim<SMC_MODEL>::value;
     const size_t lds = summ_once_lds_bytes<D>(2 * NP * THREADS, v.sum_np);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    static bool raised[16] = {};
+    static std::atomic<bool> raised[16] = {};
     hipError_t e = raise_lds_limit(k_summ_once<THREADS, NP, D, UNW>, lds, raised);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_summ_once<THREADS, NP, D, UNW>), dim3(v.ntheta), dim3(THREADS), lds, s, v, cur);
