@@ -59,7 +59,32 @@ int smc_create(int model_id, int64_t n_theta, int64_t n_x, int seg, uint64_t see
  * a handle per call costs 0.02 ms instead of 0.6 ms. */
 int smc_destroy(smc_handle h);
 
-/* smc.model(theta[m]) for every m (src/smc_samplers.jl:120,178,227,293,330): raw parameter rows. */
+/* smc.model(theta[m]) for every m (src/smc_samplers.jl:120,178,227,293,330): raw parameter rows.
+ * NON-FINITE INPUTS.  Neither this call nor smc_init / smc_step / smc_step_window / smc_log_likelihood refuses a value: a row is
+ * derived as it stands (sqrt(Q), 1 / sqrt(R), sigma / sqrt(1 - rho^2)) and any y is taken.  What follows is defined, the same on
+ * the device and in the CPU oracle bit for bit (NaN positions included), and pinned by tests/test_gpu_nonfinite.py:
+ *   - a particle whose log-weight is NaN, infinite or beyond 7e8 in magnitude takes no part in the normalisation.  A step that
+ *     leaves no particle alive is DEAD: logmu = -inf, ess = 0, every weight 0, logZ = -inf from then on, weighted summaries NaN,
+ *     and the next step's ancestors are the identity.  Nothing faults; the states may hold NaN or +-inf.
+ *   - an observation that is NaN, +inf or -inf kills the step it arrives at, in every family.  The bootstrap families (LG1D,
+ *     SV1D, UCSV3D) keep finite states through it and weigh again at the next finite observation (logZ stays -inf).  The guided
+ *     filters (LG1D AFFINE - also with c2 = 0, since 0 * y is NaN - LG1D OPTIMAL, UCSV OPTIMAL) and SMC_MODEL_UCSV_RB carry y
+ *     into the state (the proposal mean; the Kalman mean m): dead from that step on.  The first step of a guided filter is the
+ *     bootstrap first step, so a bad y_1 costs a guided filter that step alone; SMC_MODEL_UCSV_RB is dead from it on.
+ *     There are no missing-data semantics: a gap in the series must be left out by the caller, not passed as NaN.
+ *   - a row outside its family's domain makes its filter dead: LG1D R <= 0 or a NaN B, SV1D |rho| >= 1 or a NaN sigma, UCSV a NaN
+ *     x0, lse0 = +inf (and for the bootstrap filter lsn0 = -inf) from the first step; LG1D Q < 0, Q = +inf or a NaN A from the
+ *     second (the first step does not move the particles).  LG1D sigma0 = 0 is valid (x_1 = x0).  A NEGATIVE UCSV gamma is a live
+ *     filter: the sign only flips a normal.  lsn0 = -inf (observation noise 0) is a live SMC_MODEL_UCSV_RB filter, and under UCSV
+ *     OPTIMAL dead at the first step alone.
+ *   - the other filters of the batch are untouched bit for bit, and a later smc_set_params with valid rows leaves nothing of the
+ *     dead filter behind on the handle.
+ *   - the samplers never accept such a filter: the accept test of the PMMH move requires logZ' + log prior' > -inf
+ *     (src/smc_samplers.jl:129), which a dead filter's logZ = -inf fails.  With a prior that puts mass outside a parameter's
+ *     domain (PRIOR_NORMAL on a variance) such parameter particles enter with weight 0 and are resampled away.  The Python model
+ *     constructors do refuse such parameters (ValueError); only rows built on the device from theta (ThetaMap) get this far.
+ *   - smc_smooth and smc_sample_paths refuse a row whose transition scale is not a positive finite number (below); a filter that
+ *     was dead at a recorded step reads NaN / -1 at every step. */
 int smc_set_params(smc_handle h, const double* raw /*[n_theta][n_raw]*/);
 /* Philox stream id per filter (e.g. the GLOBAL theta index when theta is sharded over GPUs). */
 int smc_set_streams(smc_handle h, const uint32_t* stream /*[n_theta]*/);
@@ -662,7 +687,12 @@ int smc_model_nraw(int model_id);
 int smc_auto_seg(int model_id, int64_t n_x);
 int smc_device_count(void);
 /* the SMC_SUMM_UNWEIGHTED definitions (smc_set_summary_mode) on the host, by sorting: the type-7 quantiles of x [n] at the levels
- * p [np] in [0, 1] (else SMC_EINVAL), and the sample mean and corrected variance (n == 1: var NaN) */
+ * p [np] in [0, 1] (else SMC_EINVAL), and the sample mean and corrected variance (n == 1: var NaN).  Values that are not numbers:
+ * the quantiles order by the IEEE total order of the bits, so a NaN sorts by its sign bit (below -inf when it is set, above +inf
+ * when it is not) - a cloud of NaNs has NaN quantiles, a cloud with some has numbers at the levels whose neighbours are numbers
+ * (np.quantile would return NaN at every level); mean and variance are NaN as soon as one value is NaN, and a cloud with
+ * infinities of one sign has that infinity as its mean and a NaN variance, as mean(x) and var(x).  The device's unweighted
+ * summaries order the same way (tests/test_gpu_nonfinite.py). */
 int smc_host_quantile7(const double* x, int64_t n, const double* p, int np, double* out);
 int smc_host_sample_moments(const double* x, int64_t n, double* mean, double* var);
 /* the spec's elementary functions on the host (parity tests of the host build) */

@@ -186,7 +186,7 @@ extern "C" int smc_host_sample_moments(const double* x, int64_t n, double* mean,
     for (int64_t i = 0; i < n; ++i) s += x[i];
     double m = s / (double)n, r = 0.0;
     for (int64_t i = 0; i < n; ++i) r += x[i] - m;   // (the rounding of the first sum, taken back)
-    m += r / (double)n;
+    if (r - r == 0.0) m += r / (double)n;   // (a cloud that holds +inf or -inf: inf - inf here; its mean stays the +-inf of the sum, as mean(x))
     for (int64_t i = 0; i < n; ++i) { const double e = x[i] - m; s2 += e * e; }
     *mean = m;
     *var = s2 / (double)(n - 1);   // (n == 1: 0 / 0, NaN as Statistics.var)
