@@ -857,19 +857,24 @@ class Handle:
         """M backward-simulated paths per filter over the recorded steps (smc_sample_paths): (idx [T][n_theta][M] int32, xs
         [T][d][n_theta][M] or None).  counts [n_theta]: only the first counts[th] paths of filter th are drawn, the other slots
         read -1 / NaN"""
-        T, M = self.history_len(), int(M)
-        if M < 1:
-            raise ValueError("M must be positive")
-        if counts is not None:
-            counts = np.ascontiguousarray(counts, dtype=np.int32)
-            if counts.shape != (self.n_theta,):
-                raise ValueError("counts must be [n_theta]")
+        T = self.history_len()
+        M, counts, cp = self._path_args(M, counts)
         idx = np.zeros((T, self.n_theta, M), dtype=np.int32)
         xs = np.zeros((T, self.d, self.n_theta, M)) if want_x else None
-        check(lib().smc_sample_paths(self._h, M, int(seed), counts.ctypes.data_as(_i32p) if counts is not None else None,
-                                     idx.ctypes.data_as(_i32p), _d(xs)))
+        check(lib().smc_sample_paths(self._h, M, int(seed), cp, idx.ctypes.data_as(_i32p), _d(xs)))
         return idx, xs
 
+    def _path_args(self, M, counts):
+        """the checks the two path calls share: (M, counts as int32 [n_theta] or None, its pointer or None)"""
+        M = int(M)
+        if M < 1:
+            raise ValueError("M must be positive")
+        if counts is None:
+            return M, None, None
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        if counts.shape != (self.n_theta,):
+            raise ValueError("counts must be [n_theta]")
+        return M, counts, counts.ctypes.data_as(_i32p)
 
     def rb_sample_paths(self, y, M, seed, counts=None, draws=False, per_path=True, summary=True):
         """M Rao-Blackwellised backward-simulated paths per filter over the record of a MODEL_UCSV_RB handle
@@ -878,13 +883,8 @@ class Handle:
         (per_path=False leaves these four out), "tdraw" [T][n_theta][M] a joint trend draw per path (draws=True) and "out"
         [T][n_theta][8] the summary over the paths (summary=True).  counts as in sample_paths"""
         y = np.ascontiguousarray(y, dtype=np.float64).ravel()
-        T, M = y.size, int(M)
-        if M < 1:
-            raise ValueError("M must be positive")
-        if counts is not None:
-            counts = np.ascontiguousarray(counts, dtype=np.int32)
-            if counts.shape != (self.n_theta,):
-                raise ValueError("counts must be [n_theta]")
+        T = y.size
+        M, counts, cp = self._path_args(M, counts)
         r = {}
         if per_path:
             r["idx"] = np.zeros((T, self.n_theta, M), dtype=np.int32)
@@ -896,9 +896,8 @@ class Handle:
                 r["vol"] = np.zeros((T, 2, self.n_theta, M))
         if summary:
             r["out"] = np.zeros((T, self.n_theta, 8))
-        check(lib().smc_rb_sample_paths(self._h, _d(y), T, M, int(seed), counts.ctypes.data_as(_i32p) if counts is not None else None,
-                                        r["idx"].ctypes.data_as(_i32p) if "idx" in r else None, _d(r.get("vol")), _d(r.get("tmean")),
-                                        _d(r.get("tvar")), _d(r.get("tdraw")), _d(r.get("out"))))
+        check(lib().smc_rb_sample_paths(self._h, _d(y), T, M, int(seed), cp, r["idx"].ctypes.data_as(_i32p) if "idx" in r else None,
+                                        _d(r.get("vol")), _d(r.get("tmean")), _d(r.get("tvar")), _d(r.get("tdraw")), _d(r.get("out"))))
         return r
 
 

@@ -292,20 +292,19 @@ extern "C" int smc_create(int model_id, int64_t n_theta, int64_t n_x, int seg, u
     {   // every array the handle always owns, in ONE device allocation (smc_create + smc_destroy of a 1024-particle filter: 0.63 ->
         // 0.55 ms; thirty-odd hipMalloc / hipFree calls cost more than the filter's hundred steps)
         const bool gtab = v.nseg_p2 > 2 * g.threads;   // more than twice as many segments as a workgroup has threads: the segment table is built once per step (k_table)
-        size_t off = 0;
-        auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-        const size_t o_params = take(nt * sizeof(*h->d_params)), o_stream = take(nt * sizeof(*h->d_stream)), o_perm = take(nt * sizeof(*h->d_perm)),
-                     o_ztmp = take(nt * 8);
+        OffsetPlan slab;
+        const size_t o_params = slab.take(nt * sizeof(*h->d_params)), o_stream = slab.take(nt * sizeof(*h->d_stream)), o_perm = slab.take(nt * sizeof(*h->d_perm)),
+                     o_ztmp = slab.take(nt * 8);
         size_t o_x[2], o_C[2], o_k[2], o_S[2], o_hi[2], o_lo[2];
         for (int b = 0; b < 2; ++b) {
-            o_x[b] = take(np * (size_t)d * 8); o_C[b] = take(np * 8);
-            o_k[b] = take(ns * 8); o_S[b] = take(ns * 8); o_hi[b] = take(ns * 8); o_lo[b] = take(ns * 8);
+            o_x[b] = slab.take(np * (size_t)d * 8); o_C[b] = slab.take(np * 8);
+            o_k[b] = slab.take(ns * 8); o_S[b] = slab.take(ns * 8); o_hi[b] = slab.take(ns * 8); o_lo[b] = slab.take(ns * 8);
         }
-        const size_t o_anc = (flags & SMC_FLAG_ANCESTORS) ? take(np * 4) : 0;
-        const size_t o_logZ = take(nt * 8), o_lm = take(nt * 8), o_es = take(nt * 8), o_K = take(nt * 8), o_D = take(nt * 8);
-        const size_t o_tD = gtab ? take(nt * (size_t)v.nseg_p2 * 8) : 0, o_tsh = gtab ? take(nt * (size_t)v.nseg_p2 * 4) : 0;
-        h->slab_bytes = off;
-        if (bundle_cache().take(device, off, 4 * nt * 8, bun)) {
+        const size_t o_anc = (flags & SMC_FLAG_ANCESTORS) ? slab.take(np * 4) : 0;
+        const size_t o_logZ = slab.take(nt * 8), o_lm = slab.take(nt * 8), o_es = slab.take(nt * 8), o_K = slab.take(nt * 8), o_D = slab.take(nt * 8);
+        const size_t o_tD = gtab ? slab.take(nt * (size_t)v.nseg_p2 * 8) : 0, o_tsh = gtab ? slab.take(nt * (size_t)v.nseg_p2 * 4) : 0;
+        h->slab_bytes = slab.bytes;
+        if (bundle_cache().take(device, slab.bytes, 4 * nt * 8, bun)) {
             h->d_slab = bun.slab; h->slab_bytes = bun.slab_bytes; h->stream = bun.stream; h->ev0 = bun.ev0; h->ev1 = bun.ev1;
             h->h_pin = bun.pin; h->pin_bytes = bun.pin_bytes;
             h->d_y = bun.d_y; h->ycap = bun.ycap;
@@ -316,9 +315,9 @@ extern "C" int smc_create(int model_id, int64_t n_theta, int64_t n_x, int seg, u
             TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
             TRY(hipEventCreate(&h->ev0));
             TRY(hipEventCreate(&h->ev1));
-            TRY(hipMalloc((void**)&h->d_slab, off));
+            TRY(hipMalloc((void**)&h->d_slab, slab.bytes));
         }
-        TRY(hipMemsetAsync(h->d_slab, 0, off, h->stream));
+        TRY(hipMemsetAsync(h->d_slab, 0, slab.bytes, h->stream));
         char* base = h->d_slab;
         h->d_params = (decltype(h->d_params))(base + o_params); h->d_stream = (decltype(h->d_stream))(base + o_stream);
         h->d_perm = (decltype(h->d_perm))(base + o_perm); h->d_logZ_tmp = (double*)(base + o_ztmp);

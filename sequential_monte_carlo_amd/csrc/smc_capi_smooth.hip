@@ -1,8 +1,10 @@
-// smc_capi_smooth.hip -- the record of a step-by-step run (smc_history_*) and the FFBS particle smoother over it (smc_smooth):
-// forward filtering by the step kernels as they are, backward smoothing by the all-pairs kernels of smc_smooth_kernels.h,
-// backward simulation over the same record (smc_sample_paths, smc_path_kernels.h) and its Rao-Blackwellised form for
-// MODEL_UCSV_RB (smc_rb_sample_paths, smc_rb_kernels.h).
-// Specification: smc_spec.h "the smoother"; the host twin (smc_host_smooth) lives in smc_util.hip.
+// smc_capi_smooth.hip -- the record of a step-by-step run (smc_history_*) and the backward passes over it.  smc_smooth: the FFBS
+// particle smoother, forward filtering by the step kernels as they are, backward smoothing by the all-pairs kernels of
+// smc_smooth_kernels.h.  smc_sample_paths and smc_rb_sample_paths (MODEL_UCSV_RB): backward simulation, ONE walk over the record
+// (backward_walk: the refusals, the plan of the block, the uploads, the dead scan and the loop over the steps, smc_path_kernels.h)
+// that each of the two entry points wraps with the tail of its plan and with what follows the walk (smc_rb_kernels.h).
+// Specification: smc_spec.h "the smoother", "backward simulation"; the host twins (smc_host_smooth, smc_host_sample_paths,
+// smc_host_rb_sample_paths) live in smc_util.hip.
 #include "smc_host.h"
 #include "smc_smooth_kernels.h"
 #include "smc_path_kernels.h"
@@ -23,7 +25,6 @@ void history_free(smc_filter_s* h) {
     (void)hipFree(h->hist.d_ws);
     (void)hipFree(h->hist.d_tmp);
     (void)hipFree(h->hist.d_path);
-    (void)hipFree(h->hist.d_rb);
     h->hist = {};
 }
 
@@ -106,6 +107,20 @@ extern "C" int smc_history_put(smc_handle h, int64_t t, const double* x, const d
 
 // ---- the backward pass ---------------------------------------------------------------------------------------------------
 namespace {
+// the rows the steps ran with, as the device holds them (the PMMH kernels write them there), and their constants as smooth_row
+// derives them for the family `model`; who / what: the caller's name and its wording for a row that is refused
+int fetch_rows(smc_handle h, int model, const char* who, const char* what, std::vector<SmoothRow>& rows) {
+    const size_t nt = (size_t)h->v.ntheta;
+    std::vector<Params> prm(nt);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(prm.data(), h->d_params, nt * sizeof(Params), hipMemcpyDeviceToHost));
+    rows.resize(nt);
+    for (size_t m = 0; m < nt; ++m)
+        if (!smooth_row(model, prm[m].raw, rows[m]))
+            return fail(SMC_EINVAL, std::string(who) + ": " + what + " of filter " + std::to_string(m) + " is not a positive finite number");
+    return SMC_OK;
+}
+
 struct SmoothPlan {
     int nchunk;
     size_t o_pmax, o_part, o_logD, o_rmax, o_mom, o_rows, o_dead, bytes;   // offsets into hist.d_tmp, in bytes
@@ -114,16 +129,15 @@ SmoothPlan plan_of(const smc_filter_s* h, int64_t T) {
     SmoothPlan p{};
     const size_t nw = cloud_words(h), nt = (size_t)h->v.ntheta;
     p.nchunk = (int)((h->v.n + SMOOTH_CH - 1) / SMOOTH_CH);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    p.o_pmax = take((size_t)p.nchunk * nw * 8);
-    p.o_part = take((size_t)p.nchunk * nw * 8);
-    p.o_logD = take(nw * 8);
-    p.o_rmax = take(nw * 8);
-    p.o_mom = take((size_t)T * nt * (size_t)p.nchunk * 8);
-    p.o_rows = take(nt * sizeof(SmoothRow));
-    p.o_dead = take(nt * sizeof(int));
-    p.bytes = off;
+    OffsetPlan o;
+    p.o_pmax = o.take((size_t)p.nchunk * nw * 8);
+    p.o_part = o.take((size_t)p.nchunk * nw * 8);
+    p.o_logD = o.take(nw * 8);
+    p.o_rmax = o.take(nw * 8);
+    p.o_mom = o.take((size_t)T * nt * (size_t)p.nchunk * 8);
+    p.o_rows = o.take(nt * sizeof(SmoothRow));
+    p.o_dead = o.take(nt * sizeof(int));
+    p.bytes = o.bytes;
     return p;
 }
 
@@ -154,7 +168,7 @@ hipError_t backward_step(const SmoothArgs& a01, const SmoothArgs& a2, int thread
 
 extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
     if (!h) return fail(SMC_EINVAL, "smc_smooth: NULL handle");
-    if (h->model != MODEL_LG1D && h->model != MODEL_SV1D && h->model != MODEL_UCSV3D)
+    if (!has_density(h->model))
         return fail(SMC_EINVAL, "smc_smooth: SMC_MODEL_UCSV_RB has no transition density of its state rows (m and P are functions of the whole "
                                 "path); smooth a UCSV3D filter instead, or draw Rao-Blackwellised paths (smc_rb_sample_paths)");
     if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, "smc_smooth: nothing is recorded (smc_history_begin, then smc_init / smc_step)");
@@ -163,16 +177,11 @@ extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
     const size_t nw = cloud_words(h), nt = (size_t)v.ntheta, d = (size_t)h->d;
     if ((n + SMOOTH_CH - 1) / SMOOTH_CH > 65535) return fail(SMC_EINVAL, "smc_smooth: more than 65535 chunks of particles (the backward pass is quadratic in n_x)");
     HIPCHK(hipSetDevice(h->device));
-    // the rows the steps ran with, as the device holds them (the PMMH kernels write them there), and their constants
-    std::vector<Params> prm(nt);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(prm.data(), h->d_params, nt * sizeof(Params), hipMemcpyDeviceToHost));
-    std::vector<SmoothRow> rows(nt);
-    for (size_t m = 0; m < nt; ++m)
-        if (!smooth_row(h->model, prm[m].raw, rows[m]))
-            return fail(SMC_EINVAL, "smc_smooth: the transition scale of filter " + std::to_string(m) + " is not a positive finite number");
+    std::vector<SmoothRow> rows;
+    int rc = fetch_rows(h, h->model, "smc_smooth", "the transition scale", rows);
+    if (rc) return rc;
     const SmoothPlan p = plan_of(h, T);
-    if (p.bytes > h->hist.tmp_bytes) {
+    if (p.bytes > h->hist.tmp_bytes) {   // (the old block first, unlike the walk's: DESIGN.md "History on a handle")
         (void)hipFree(h->hist.d_tmp);
         h->hist.d_tmp = nullptr; h->hist.tmp_bytes = 0;
         if (hipMalloc((void**)&h->hist.d_tmp, p.bytes) != hipSuccess) {
@@ -215,19 +224,14 @@ extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
         const bool direct = p.nchunk <= SMOOTH_MAX_DIRECT;
         const SmoothArgs a01{n, (int)nt, p.nchunk, x_n, x_t, w_t, nullptr, pmax, direct ? pmax : rowmax, direct ? p.nchunk : 1, part, d_rows};
         const SmoothArgs a2{n, (int)nt, p.nchunk, x_t, x_n, ws_n, logD, pmax, nullptr, 0, part, d_rows};
-        hipError_t e = hipErrorInvalidValue;
-        if (h->model == MODEL_LG1D) e = backward_step<MODEL_LG1D>(a01, a2, threads, logD, rowmax, w_t, dead, ws_t, s);
-        else if (h->model == MODEL_SV1D) e = backward_step<MODEL_SV1D>(a01, a2, threads, logD, rowmax, w_t, dead, ws_t, s);
-        else e = backward_step<MODEL_UCSV3D>(a01, a2, threads, logD, rowmax, w_t, dead, ws_t, s);
-        HIPCHK(e);
+        HIPCHK(by_density_model(h->model, [&](auto Mt) { return backward_step<decltype(Mt)::value>(a01, a2, threads, logD, rowmax, w_t, dead, ws_t, s); }));
     }
     if (mean || var) {
         hipLaunchKernelGGL(k_smooth_moments, dim3((unsigned)T, (unsigned)nt), dim3(256), 0, s, n, (int)nt, p.nchunk, (int)d, h->hist.d_x, d_ws, dead,
                            momtmp, d_mom);
         HIPCHK(hipGetLastError());
     }
-    int rc = finish_elapsed(h);
-    if (rc) return rc;
+    if ((rc = finish_elapsed(h))) return rc;
     if (ws) HIPCHK(hipMemcpy(ws, d_ws, (size_t)T * nw * 8, hipMemcpyDeviceToHost));
     if (mean || var) {
         std::vector<double> mv((size_t)T * mom_words);
@@ -242,30 +246,6 @@ extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
 
 // ---- backward simulation ---------------------------------------------------------------------------------------------------
 namespace {
-struct PathPlan {
-    int nchunk;
-    size_t o_cur, o_pmax, o_psum, o_rmax, o_rows, o_dead, o_counts, o_idx, o_xs, bytes;   // offsets into hist.d_path, in bytes
-};
-// false: the sizes do not fit size_t arithmetic
-bool path_plan(const smc_filter_s* h, int64_t T, int64_t M, bool want_x, PathPlan& p) {
-    const size_t nt = (size_t)h->v.ntheta, d = (size_t)h->d, pw = nt * (size_t)M;
-    p.nchunk = (int)((h->v.n + SMOOTH_CH - 1) / SMOOTH_CH);
-    if (pw > ((size_t)1 << 56) / ((size_t)T * (d + 1)) || pw > ((size_t)1 << 56) / (size_t)p.nchunk) return false;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    p.o_cur = take(d * pw * 8);
-    p.o_pmax = take((size_t)p.nchunk * pw * 8);
-    p.o_psum = take((size_t)p.nchunk * pw * 8);
-    p.o_rmax = take(pw * 8);
-    p.o_rows = take(nt * sizeof(SmoothRow));
-    p.o_dead = take(nt * sizeof(int));
-    p.o_counts = take(nt * sizeof(int32_t));
-    p.o_idx = take((size_t)T * pw * 4);
-    p.o_xs = take(want_x ? (size_t)T * d * pw * 8 : 0);
-    p.bytes = off;
-    return true;
-}
-
 template <int MODEL>
 hipError_t path_step(const PathArgs& a, int threads, double* rowmax, hipStream_t s) {
     hipError_t e;
@@ -284,198 +264,160 @@ hipError_t path_step(const PathArgs& a, int threads, double* rowmax, hipStream_t
         hipLaunchKernelGGL((k_path_select<MODEL>), dim3((unsigned)((a.M + 63) / 64), (unsigned)a.ntheta), dim3(64), 0, s, a);
     return hipGetLastError();
 }
-}  // namespace
 
-extern "C" int smc_sample_paths(smc_handle h, int64_t M, uint64_t path_seed, const int32_t* counts, int32_t* idx, double* xs) {
-    if (!h) return fail(SMC_EINVAL, "smc_sample_paths: NULL handle");
-    if (h->model != MODEL_LG1D && h->model != MODEL_SV1D && h->model != MODEL_UCSV3D)
-        return fail(SMC_EINVAL, "smc_sample_paths: SMC_MODEL_UCSV_RB has no transition density of its state rows (m and P are functions of the "
-                                "whole path); draw the paths of a UCSV3D filter instead, or call smc_rb_sample_paths");
-    if (M < 1 || M > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_sample_paths: M must be in [1, 2^30]");
-    if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, "smc_sample_paths: nothing is recorded (smc_history_begin, then smc_init / smc_step)");
+// One backward walk over the record, M paths per filter: what its caller sets ...
+struct Walk {
+    const char *who, *what;   // the entry point, at the head of every message, and its wording for a row smooth_row refuses
+    int row_model;            // the family whose constants smooth_row derives from the rows
+    size_t cur_rows;          // state rows a path carries from step to step
+    size_t step_words;        // words per path and step over everything the block holds (the check that its sizes fit size_t)
+    const double* y;          // the observations the recorded steps saw, T of them (PathArgs::y, checked against the record), or nullptr
+    int64_t T;
+    // ... what the tail of its plan adds: the observations on the device (with y) and the states of the paths, xs_rows per step (0: none)
+    size_t o_y, o_xs, xs_rows;
+    // ... and what the walk leaves in hist.d_path for what follows it (offsets in bytes)
+    size_t o_counts, o_idx;
+};
+// The refusals the two entry points share, the plan of the block (the common prefix cur | pmax | psum | rmax | rows | dead | counts |
+// idx, then tail(plan, T, pw): the caller's arrays), the block itself, the uploads, the dead scan and the loop over the steps, all on
+// the handle's stream behind ev0.  The caller adds what follows and closes the timed region (finish_elapsed).
+template <class Tail>
+int backward_walk(smc_handle h, Walk& k, int64_t M, uint64_t path_seed, const int32_t* counts, Tail&& tail) {
+    const std::string who = std::string(k.who) + ": ";
+    if (M < 1 || M > ((int64_t)1 << 30)) return fail(SMC_EINVAL, who + "M must be in [1, 2^30]");
+    if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, who + "nothing is recorded (smc_history_begin, then smc_init / smc_step)");
     const FilterView& v = h->v;
     const int64_t T = h->hist.len, n = v.n;
+    if (k.y) {
+        if (k.T != T) return fail(SMC_EINVAL, who + "T is not the number of recorded steps (smc_history_len)");
+        for (int64_t t = 0; t < T; ++t)
+            if (!(k.y[t] - k.y[t] == 0.0)) return fail(SMC_EINVAL, who + "y[" + std::to_string(t) + "] is not finite");
+    }
     const size_t nw = cloud_words(h), nt = (size_t)v.ntheta, d = (size_t)h->d, pw = nt * (size_t)M;
-    if (n > PATH_MAX_N) return fail(SMC_EINVAL, "smc_sample_paths: more than 2^20 particles per filter (the integer weights of a step would not fit their sum)");
+    if (n > PATH_MAX_N) return fail(SMC_EINVAL, who + "more than 2^20 particles per filter (the integer weights of a step would not fit their sum)");
     std::vector<int32_t> cnt(nt, (int32_t)M);
     for (size_t m = 0; counts && m < nt; ++m) {
-        if (counts[m] < 0 || counts[m] > M) return fail(SMC_EINVAL, "smc_sample_paths: counts[" + std::to_string(m) + "] is outside [0, M]");
+        if (counts[m] < 0 || counts[m] > M) return fail(SMC_EINVAL, who + "counts[" + std::to_string(m) + "] is outside [0, M]");
         cnt[m] = counts[m];
     }
     HIPCHK(hipSetDevice(h->device));
-    std::vector<Params> prm(nt);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(prm.data(), h->d_params, nt * sizeof(Params), hipMemcpyDeviceToHost));
-    std::vector<SmoothRow> rows(nt);
-    for (size_t m = 0; m < nt; ++m)
-        if (!smooth_row(h->model, prm[m].raw, rows[m]))
-            return fail(SMC_EINVAL, "smc_sample_paths: the transition scale of filter " + std::to_string(m) + " is not a positive finite number");
-    PathPlan p{};
-    if (!path_plan(h, T, M, xs != nullptr, p)) return fail(SMC_ENOMEM, "smc_sample_paths: paths of that many bytes cannot be allocated");
+    std::vector<SmoothRow> rows;
+    const int rc = fetch_rows(h, k.row_model, k.who, k.what, rows);
+    if (rc) return rc;
+    const int nchunk = (int)((n + SMOOTH_CH - 1) / SMOOTH_CH);
+    if (pw > ((size_t)1 << 56) / ((size_t)T * k.step_words) || pw > ((size_t)1 << 56) / (size_t)nchunk)
+        return fail(SMC_ENOMEM, who + "paths of that many bytes cannot be allocated");
+    OffsetPlan p;
+    const size_t o_cur = p.take(k.cur_rows * pw * 8), o_pmax = p.take((size_t)nchunk * pw * 8), o_psum = p.take((size_t)nchunk * pw * 8),
+                 o_rmax = p.take(pw * 8), o_rows = p.take(nt * sizeof(SmoothRow)), o_dead = p.take(nt * sizeof(int));
+    k.o_counts = p.take(nt * sizeof(int32_t));
+    k.o_idx = p.take((size_t)T * pw * 4);
+    tail(p, (size_t)T, pw);
     if (p.bytes > h->hist.path_bytes) {   // (the new block first: a failed allocation leaves the handle as it was)
         char* blk = nullptr;
         if (hipMalloc((void**)&blk, p.bytes) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(SMC_ENOMEM, "smc_sample_paths: hipMalloc of the paths and the scratch of the backward walk");
+            return fail(SMC_ENOMEM, who + "hipMalloc of the paths and the scratch of the backward walk");
         }
         (void)hipFree(h->hist.d_path);
         h->hist.d_path = blk;
         h->hist.path_bytes = p.bytes;
     }
     char* base = h->hist.d_path;
-    double *cur = (double*)(base + p.o_cur), *pmax = (double*)(base + p.o_pmax), *rowmax = (double*)(base + p.o_rmax);
-    uint64_t* psum = (uint64_t*)(base + p.o_psum);
-    SmoothRow* d_rows = (SmoothRow*)(base + p.o_rows);
-    int* dead = (int*)(base + p.o_dead);
-    int32_t *d_counts = (int32_t*)(base + p.o_counts), *d_idx = (int32_t*)(base + p.o_idx);
-    double* d_xs = xs ? (double*)(base + p.o_xs) : nullptr;
+    double *cur = (double*)(base + o_cur), *pmax = (double*)(base + o_pmax), *rowmax = (double*)(base + o_rmax);
+    uint64_t* psum = (uint64_t*)(base + o_psum);
+    SmoothRow* d_rows = (SmoothRow*)(base + o_rows);
+    int* dead = (int*)(base + o_dead);
+    int32_t *d_counts = (int32_t*)(base + k.o_counts), *d_idx = (int32_t*)(base + k.o_idx);
+    double* d_xs = k.xs_rows ? (double*)(base + k.o_xs) : nullptr;
     hipStream_t s = h->stream;
     HIPCHK(hipEventRecord(h->ev0, s));
     HIPCHK(hipMemcpyAsync(d_rows, rows.data(), nt * sizeof(SmoothRow), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_counts, cnt.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (k.y) HIPCHK(hipMemcpyAsync(base + k.o_y, k.y, (size_t)T * 8, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(dead, 0, nt * sizeof(int), s));
     hipLaunchKernelGGL(k_smooth_dead, dim3((unsigned)T, (unsigned)nt), dim3(256), 0, s, n, (int)nt, h->hist.d_w, dead);
     HIPCHK(hipGetLastError());
     // the smoother's rule: a launch of few workgroups is cut into tiles of one wave; the bits do not depend on it
-    const int64_t wg256 = ((M + 255) / 256) * (int64_t)nt * p.nchunk;
+    const int64_t wg256 = ((M + 255) / 256) * (int64_t)nt * nchunk;
     const int threads = wg256 >= 1024 ? 256 : 64;
-    const bool direct = p.nchunk <= SMOOTH_MAX_DIRECT;
+    const bool direct = nchunk <= SMOOTH_MAX_DIRECT;
     for (int64_t t = T - 1; t >= 0; --t) {
         PathArgs a{};
-        a.n = n; a.M = M; a.ntheta = (int)nt; a.nchunk = p.nchunk;
+        a.n = n; a.M = M; a.ntheta = (int)nt; a.nchunk = nchunk;
         a.last = t == T - 1; a.t = (uint32_t)t; a.seed = path_seed;
+        if (k.y) a.y = k.y[t];
         a.x_t = h->hist.d_x + (size_t)t * nw * d; a.w_t = h->hist.d_w + (size_t)t * nw;
-        a.cur = cur; a.pmax = pmax; a.rmax = direct ? pmax : rowmax; a.nmax = direct ? p.nchunk : 1; a.psum = psum;
+        a.cur = cur; a.pmax = pmax; a.rmax = direct ? pmax : rowmax; a.nmax = direct ? nchunk : 1; a.psum = psum;
         a.rows = d_rows; a.dead = dead; a.counts = d_counts; a.stream = h->d_stream;
         a.idx_n = d_idx + (size_t)(t + 1 < T ? t + 1 : t) * pw; a.idx_t = d_idx + (size_t)t * pw;
-        a.xs_t = d_xs ? d_xs + (size_t)t * d * pw : nullptr;
-        hipError_t e = hipErrorInvalidValue;
-        if (h->model == MODEL_LG1D) e = path_step<MODEL_LG1D>(a, threads, rowmax, s);
-        else if (h->model == MODEL_SV1D) e = path_step<MODEL_SV1D>(a, threads, rowmax, s);
-        else e = path_step<MODEL_UCSV3D>(a, threads, rowmax, s);
-        HIPCHK(e);
+        a.xs_t = d_xs ? d_xs + (size_t)t * k.xs_rows * pw : nullptr;
+        HIPCHK(by_model(h->model, [&](auto Mt) { return path_step<decltype(Mt)::value>(a, threads, rowmax, s); }));
     }
-    int rc = finish_elapsed(h);
-    if (rc) return rc;
-    if (idx) HIPCHK(hipMemcpy(idx, d_idx, (size_t)T * pw * 4, hipMemcpyDeviceToHost));
-    if (xs) HIPCHK(hipMemcpy(xs, d_xs, (size_t)T * d * pw * 8, hipMemcpyDeviceToHost));
+    return SMC_OK;
+}
+}  // namespace
+
+extern "C" int smc_sample_paths(smc_handle h, int64_t M, uint64_t path_seed, const int32_t* counts, int32_t* idx, double* xs) {
+    if (!h) return fail(SMC_EINVAL, "smc_sample_paths: NULL handle");
+    if (!has_density(h->model))
+        return fail(SMC_EINVAL, "smc_sample_paths: SMC_MODEL_UCSV_RB has no transition density of its state rows (m and P are functions of the "
+                                "whole path); draw the paths of a UCSV3D filter instead, or call smc_rb_sample_paths");
+    const size_t d = (size_t)h->d;
+    Walk k{"smc_sample_paths", "the transition scale", h->model, d, d + 1, nullptr, 0};
+    size_t T = 0, pw = 0;
+    int rc = backward_walk(h, k, M, path_seed, counts, [&](OffsetPlan& p, size_t T_, size_t pw_) {
+        T = T_; pw = pw_;
+        k.xs_rows = xs ? d : 0;
+        k.o_xs = p.take(xs ? T * d * pw * 8 : 0);
+    });
+    if (rc || (rc = finish_elapsed(h))) return rc;
+    const char* base = h->hist.d_path;
+    if (idx) HIPCHK(hipMemcpy(idx, base + k.o_idx, T * pw * 4, hipMemcpyDeviceToHost));
+    if (xs) HIPCHK(hipMemcpy(xs, base + k.o_xs, T * d * pw * 8, hipMemcpyDeviceToHost));
     return SMC_OK;
 }
 
 // ---- Rao-Blackwellised backward simulation (MODEL_UCSV_RB) ---------------------------------------------------------------------
-namespace {
-struct RbPlan {
-    int nchunk, mchunk;   // chunks of particles (the walk), chunks of paths (the summary)
-    size_t o_cur, o_pmax, o_psum, o_rmax, o_rows, o_dead, o_counts, o_y, o_idx, o_vol, o_tmean, o_tvar, o_tdraw, o_stmp, o_out, bytes;
-};
-// false: the sizes do not fit size_t arithmetic
-bool rb_plan(const smc_filter_s* h, int64_t T, int64_t M, bool want_draw, RbPlan& p) {
-    const size_t nt = (size_t)h->v.ntheta, pw = nt * (size_t)M;
-    p.nchunk = (int)((h->v.n + SMOOTH_CH - 1) / SMOOTH_CH);
-    p.mchunk = (int)((M + SMOOTH_CH - 1) / SMOOTH_CH);
-    if (pw > ((size_t)1 << 56) / ((size_t)T * 8) || pw > ((size_t)1 << 56) / (size_t)p.nchunk) return false;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    p.o_cur = take(4 * pw * 8);
-    p.o_pmax = take((size_t)p.nchunk * pw * 8);
-    p.o_psum = take((size_t)p.nchunk * pw * 8);
-    p.o_rmax = take(pw * 8);
-    p.o_rows = take(nt * sizeof(SmoothRow));
-    p.o_dead = take(nt * sizeof(int));
-    p.o_counts = take(nt * sizeof(int32_t));
-    p.o_y = take((size_t)T * 8);
-    p.o_idx = take((size_t)T * pw * 4);
-    p.o_vol = take((size_t)T * 2 * pw * 8);
-    p.o_tmean = take((size_t)T * pw * 8);
-    p.o_tvar = take((size_t)T * pw * 8);
-    p.o_tdraw = take(want_draw ? (size_t)T * pw * 8 : 0);
-    p.o_stmp = take((size_t)T * nt * (size_t)p.mchunk * 8);
-    p.o_out = take((size_t)T * nt * 8 * 8);
-    p.bytes = off;
-    return true;
-}
-}  // namespace
-
 extern "C" int smc_rb_sample_paths(smc_handle h, const double* y, int64_t T, int64_t M, uint64_t path_seed, const int32_t* counts, int32_t* idx,
                                    double* vol, double* tmean, double* tvar, double* tdraw, double* out) {
     if (!h) return fail(SMC_EINVAL, "smc_rb_sample_paths: NULL handle");
     if (h->model != MODEL_UCSV_RB)
         return fail(SMC_EINVAL, "smc_rb_sample_paths: the handle is not SMC_MODEL_UCSV_RB (the other families have a transition density: smc_sample_paths)");
     if (!y) return fail(SMC_EINVAL, "smc_rb_sample_paths: NULL y");
-    if (M < 1 || M > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_rb_sample_paths: M must be in [1, 2^30]");
-    if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, "smc_rb_sample_paths: nothing is recorded (smc_history_begin, then smc_init / smc_step)");
-    if (T != h->hist.len) return fail(SMC_EINVAL, "smc_rb_sample_paths: T is not the number of recorded steps (smc_history_len)");
-    for (int64_t t = 0; t < T; ++t)
-        if (!(y[t] - y[t] == 0.0)) return fail(SMC_EINVAL, "smc_rb_sample_paths: y[" + std::to_string(t) + "] is not finite");
-    const FilterView& v = h->v;
-    const int64_t n = v.n;
-    const size_t nw = cloud_words(h), nt = (size_t)v.ntheta, d = (size_t)h->d, pw = nt * (size_t)M;
-    if (n > PATH_MAX_N) return fail(SMC_EINVAL, "smc_rb_sample_paths: more than 2^20 particles per filter (the integer weights of a step would not fit their sum)");
-    std::vector<int32_t> cnt(nt, (int32_t)M);
-    for (size_t m = 0; counts && m < nt; ++m) {
-        if (counts[m] < 0 || counts[m] > M) return fail(SMC_EINVAL, "smc_rb_sample_paths: counts[" + std::to_string(m) + "] is outside [0, M]");
-        cnt[m] = counts[m];
-    }
-    HIPCHK(hipSetDevice(h->device));
-    std::vector<Params> prm(nt);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(prm.data(), h->d_params, nt * sizeof(Params), hipMemcpyDeviceToHost));
-    std::vector<SmoothRow> rows(nt);
-    for (size_t m = 0; m < nt; ++m)   // (the two gammas are UCSV3D's: nh1, nh2)
-        if (!smooth_row(MODEL_UCSV3D, prm[m].raw, rows[m]))
-            return fail(SMC_EINVAL, "smc_rb_sample_paths: a gamma of filter " + std::to_string(m) + " is not a positive finite number");
-    RbPlan p{};
-    if (!rb_plan(h, T, M, tdraw != nullptr, p)) return fail(SMC_ENOMEM, "smc_rb_sample_paths: paths of that many bytes cannot be allocated");
-    if (p.bytes > h->hist.rb_bytes) {   // (the new block first: a failed allocation leaves the handle as it was)
-        char* blk = nullptr;
-        if (hipMalloc((void**)&blk, p.bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SMC_ENOMEM, "smc_rb_sample_paths: hipMalloc of the paths and the scratch of the backward walk");
-        }
-        (void)hipFree(h->hist.d_rb);
-        h->hist.d_rb = blk;
-        h->hist.rb_bytes = p.bytes;
-    }
-    char* base = h->hist.d_rb;
-    double *cur = (double*)(base + p.o_cur), *pmax = (double*)(base + p.o_pmax), *rowmax = (double*)(base + p.o_rmax), *d_y = (double*)(base + p.o_y);
-    uint64_t* psum = (uint64_t*)(base + p.o_psum);
-    SmoothRow* d_rows = (SmoothRow*)(base + p.o_rows);
-    int* dead = (int*)(base + p.o_dead);
-    int32_t *d_counts = (int32_t*)(base + p.o_counts), *d_idx = (int32_t*)(base + p.o_idx);
-    double *d_vol = (double*)(base + p.o_vol), *d_tmean = (double*)(base + p.o_tmean), *d_tvar = (double*)(base + p.o_tvar);
-    double *d_tdraw = tdraw ? (double*)(base + p.o_tdraw) : nullptr, *d_stmp = (double*)(base + p.o_stmp), *d_out = (double*)(base + p.o_out);
+    // (the two gammas are UCSV3D's: nh1, nh2; a path carries (lse, lsn, mu, tau) and records (lse, lsn))
+    Walk k{"smc_rb_sample_paths", "a gamma", MODEL_UCSV3D, 4, 8, y, T};
+    const size_t nt = (size_t)h->v.ntheta;
+    int mchunk = 0;   // chunks of paths (the summary)
+    size_t pw = 0, o_tmean = 0, o_tvar = 0, o_tdraw = 0, o_stmp = 0, o_out = 0;
+    int rc = backward_walk(h, k, M, path_seed, counts, [&](OffsetPlan& p, size_t, size_t pw_) {
+        pw = pw_;
+        mchunk = (int)((M + SMOOTH_CH - 1) / SMOOTH_CH);
+        k.o_y = p.take((size_t)T * 8);
+        k.xs_rows = 2;
+        k.o_xs = p.take((size_t)T * 2 * pw * 8);
+        o_tmean = p.take((size_t)T * pw * 8);
+        o_tvar = p.take((size_t)T * pw * 8);
+        o_tdraw = p.take(tdraw ? (size_t)T * pw * 8 : 0);
+        o_stmp = p.take((size_t)T * nt * (size_t)mchunk * 8);
+        o_out = p.take((size_t)T * nt * 8 * 8);
+    });
+    if (rc) return rc;
+    char* base = h->hist.d_path;
+    const double* d_y = (const double*)(base + k.o_y);
+    const int32_t *d_counts = (const int32_t*)(base + k.o_counts), *d_idx = (const int32_t*)(base + k.o_idx);
+    double *d_vol = (double*)(base + k.o_xs), *d_tmean = (double*)(base + o_tmean), *d_tvar = (double*)(base + o_tvar);
+    double *d_tdraw = tdraw ? (double*)(base + o_tdraw) : nullptr, *d_stmp = (double*)(base + o_stmp), *d_out = (double*)(base + o_out);
     hipStream_t s = h->stream;
-    HIPCHK(hipEventRecord(h->ev0, s));
-    HIPCHK(hipMemcpyAsync(d_rows, rows.data(), nt * sizeof(SmoothRow), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_counts, cnt.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_y, y, (size_t)T * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(dead, 0, nt * sizeof(int), s));
-    hipLaunchKernelGGL(k_smooth_dead, dim3((unsigned)T, (unsigned)nt), dim3(256), 0, s, n, (int)nt, h->hist.d_w, dead);
-    HIPCHK(hipGetLastError());
-    const int64_t wg256 = ((M + 255) / 256) * (int64_t)nt * p.nchunk;
-    const int threads = wg256 >= 1024 ? 256 : 64;
-    const bool direct = p.nchunk <= SMOOTH_MAX_DIRECT;
-    for (int64_t t = T - 1; t >= 0; --t) {
-        PathArgs a{};
-        a.n = n; a.M = M; a.ntheta = (int)nt; a.nchunk = p.nchunk;
-        a.last = t == T - 1; a.t = (uint32_t)t; a.seed = path_seed; a.y = y[t];
-        a.x_t = h->hist.d_x + (size_t)t * nw * d; a.w_t = h->hist.d_w + (size_t)t * nw;
-        a.cur = cur; a.pmax = pmax; a.rmax = direct ? pmax : rowmax; a.nmax = direct ? p.nchunk : 1; a.psum = psum;
-        a.rows = d_rows; a.dead = dead; a.counts = d_counts; a.stream = h->d_stream;
-        a.idx_n = d_idx + (size_t)(t + 1 < T ? t + 1 : t) * pw; a.idx_t = d_idx + (size_t)t * pw;
-        a.xs_t = d_vol + (size_t)t * 2 * pw;
-        HIPCHK(path_step<MODEL_UCSV_RB>(a, threads, rowmax, s));
-    }
     RbTrendArgs ta{T, M, (int)nt, path_seed, h->d_params, h->d_stream, d_y, d_idx, d_vol, d_tmean, d_tvar, d_tdraw};
     hipLaunchKernelGGL(k_rb_trend, dim3((unsigned)((M + 63) / 64), (unsigned)nt), dim3(64), 0, s, ta);
     HIPCHK(hipGetLastError());
     if (out) {
-        hipLaunchKernelGGL(k_rb_summary, dim3((unsigned)T, (unsigned)nt), dim3(256), 0, s, M, (int)nt, p.mchunk, d_idx, d_counts, d_tmean, d_tvar, d_vol,
+        hipLaunchKernelGGL(k_rb_summary, dim3((unsigned)T, (unsigned)nt), dim3(256), 0, s, M, (int)nt, mchunk, d_idx, d_counts, d_tmean, d_tvar, d_vol,
                            d_stmp, d_out);
         HIPCHK(hipGetLastError());
     }
-    int rc = finish_elapsed(h);
-    if (rc) return rc;
+    if ((rc = finish_elapsed(h))) return rc;
     if (idx) HIPCHK(hipMemcpy(idx, d_idx, (size_t)T * pw * 4, hipMemcpyDeviceToHost));
     if (vol) HIPCHK(hipMemcpy(vol, d_vol, (size_t)T * 2 * pw * 8, hipMemcpyDeviceToHost));
     if (tmean) HIPCHK(hipMemcpy(tmean, d_tmean, (size_t)T * pw * 8, hipMemcpyDeviceToHost));

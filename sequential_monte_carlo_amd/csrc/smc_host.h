@@ -27,6 +27,12 @@ inline hipError_t dalloc(T** p, size_t count) {
     return hipMalloc((void**)p, count * sizeof(T) > 0 ? count * sizeof(T) : 16);
 }
 
+// the offsets of the arrays that share ONE allocation: take(n) is where the next n bytes start (256-byte aligned), bytes the total
+struct OffsetPlan {
+    size_t bytes = 0;
+    size_t take(size_t n) { const size_t o = bytes; bytes += (n + 255) & ~(size_t)255; return o; }
+};
+
 // ---- the filter handle ---------------------------------------------------------------------------
 namespace smc {
 // device block of the PMMH rejuvenation (smc_pmmh_kernels.h); the handle of the proposal filters owns it
@@ -116,10 +122,8 @@ struct smc_filter_s {
         double* d_tmp = nullptr;               // its scratch: chunk maxima and chunk partials [2][nchunk][ntheta][n] | logD [ntheta][n] |
         int64_t ws_cap = 0;                    //   partials of the moments [len][ntheta][nchunk] | rows [ntheta] | dead [ntheta]
         size_t tmp_bytes = 0;
-        char* d_path = nullptr;                // backward simulation (smc_sample_paths), its own block: cur | pmax | psum | rmax | rows |
-        size_t path_bytes = 0;                 //   dead | counts | idx [T][ntheta][M] | xs [T][d][ntheta][M]
-        char* d_rb = nullptr;                  // Rao-Blackwellised backward simulation (smc_rb_sample_paths), its own block
-        size_t rb_bytes = 0;
+        char* d_path = nullptr;                // the backward walk (smc_sample_paths, or smc_rb_sample_paths on a MODEL_UCSV_RB handle), its own
+        size_t path_bytes = 0;                 //   block: cur | pmax | psum | rmax | rows | dead | counts | idx [T][ntheta][M] | the caller's tail
     } hist;
     struct {   // PMMH rejuvenation (smc_capi_pmmh.hip): this handle holds the proposal filters
         smc::PmmhSpec spec{};

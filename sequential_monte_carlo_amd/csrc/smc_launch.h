@@ -30,6 +30,20 @@ inline hipError_t by_guided_model(int id, F&& f) {
     }
     return hipErrorInvalidValue;
 }
+// ... and the families whose state rows have a transition density (smooth_row, smc_spec.h, yields their constants): the smoother
+// and backward simulation, on the device and in their host twins, exist for these
+template <class F>
+inline hipError_t by_density_model(int id, F&& f) {
+    switch (id) {
+    case MODEL_LG1D: return f(std::integral_constant<int, MODEL_LG1D>{});
+    case MODEL_SV1D: return f(std::integral_constant<int, MODEL_SV1D>{});
+    case MODEL_UCSV3D: return f(std::integral_constant<int, MODEL_UCSV3D>{});
+    }
+    return hipErrorInvalidValue;
+}
+inline bool has_density(int id) {
+    return by_density_model(id, [](auto) { return hipSuccess; }) == hipSuccess;
+}
 
 // Kernels that ask for more than the default 64 KiB of dynamic LDS.  The attribute is per device: raise it wherever this
 // process has not done so yet (cheap: a table lookup afterwards).  raised: one table per kernel instantiation, atomic because

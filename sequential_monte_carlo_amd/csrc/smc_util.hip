@@ -464,10 +464,36 @@ extern "C" int smc_host_transition_logpdf(int model_id, const double* raw, const
     SmoothRow k;
     if (!smooth_row(model_id, raw, k))
         return fail(SMC_EINVAL, "smc_host_transition_logpdf: no transition density for this family, or a transition scale that is not positive and finite");
-    if (model_id == MODEL_LG1D) *out = model_logf<MODEL_LG1D>(k, xp, x);
-    else if (model_id == MODEL_SV1D) *out = model_logf<MODEL_SV1D>(k, xp, x);
-    else *out = model_logf<MODEL_UCSV3D>(k, xp, x);
+    (void)by_density_model(model_id, [&](auto Mt) { *out = model_logf<decltype(Mt)::value>(k, xp, x); return hipSuccess; });
     return SMC_OK;
+}
+
+// a filter that collapsed at a recorded step (all of its weights 0 there): the smoother answers NaN, the walks draw no path
+static bool host_dead(int64_t T, int64_t n, const double* w /*[T][n]*/) {
+    for (int64_t t = 0; t < T; ++t) {
+        bool any = false;
+        for (int64_t i = 0; i < n; ++i) any = any || w[(size_t)t * n + i] > 0.0;
+        if (!any) return true;
+    }
+    return false;
+}
+
+// the selection of backward simulation (smc_spec.h): the integer weights q_l = path_weight(b[l], Mx) of the sources of positive
+// weight wt[l], their sum S, r = mulhi64(path p's uniform of step t, S), and the first source at which the running sum passes r;
+// -1 when S == 0
+static int64_t host_path_pick(int64_t n, const double* wt, const double* b, double Mx, uint64_t seed, int64_t p, uint32_t stream, int64_t t) {
+    uint64_t S = 0;
+    for (int64_t l = 0; l < n; ++l)
+        if (wt[l] > 0.0) S += path_weight(b[l], Mx);
+    if (!S) return -1;
+    const uint64_t r = mulhi64(path_uniform(seed, p, stream, (uint32_t)t), S);
+    uint64_t C = 0;
+    for (int64_t l = 0; l < n; ++l) {
+        if (!(wt[l] > 0.0)) continue;
+        C += path_weight(b[l], Mx);
+        if (C > r) return l;
+    }
+    return -1;
 }
 
 // smoothed moments of one step: smc_get_moments' definitions on (x, ws) in the smoother's order of summation
@@ -537,16 +563,8 @@ extern "C" int smc_host_smooth(int model_id, const double* raw, int64_t T, int64
     if (!smooth_row(model_id, raw, k))
         return fail(SMC_EINVAL, "smc_host_smooth: no transition density for this family, or a transition scale that is not positive and finite");
     const int d = model_dim_rt(model_id);
-    if (model_id == MODEL_LG1D) host_smooth_t<MODEL_LG1D>(k, T, n, x, w, ws);
-    else if (model_id == MODEL_SV1D) host_smooth_t<MODEL_SV1D>(k, T, n, x, w, ws);
-    else host_smooth_t<MODEL_UCSV3D>(k, T, n, x, w, ws);
-    // a filter that collapsed at a recorded step (all of its weights 0 there): NaN everywhere
-    bool dead = false;
-    for (int64_t t = 0; t < T && !dead; ++t) {
-        bool any = false;
-        for (int64_t i = 0; i < n; ++i) any = any || w[(size_t)t * n + i] > 0.0;
-        dead = !any;
-    }
+    (void)by_density_model(model_id, [&](auto Mt) { host_smooth_t<decltype(Mt)::value>(k, T, n, x, w, ws); return hipSuccess; });
+    const bool dead = host_dead(T, n, w);   // NaN everywhere
     if (dead)
         for (size_t q = 0; q < (size_t)T * n; ++q) ws[q] = bits2d(0x7ff8000000000000ULL);
     if (mean && var)
@@ -562,12 +580,7 @@ static void host_paths_t(const SmoothRow& k, int64_t T, int64_t n, const double*
     constexpr int D = model_dim<MODEL>::value;
     const size_t sx = (size_t)D * n;
     const double nan = bits2d(0x7ff8000000000000ULL);
-    bool dead = false;   // a filter that collapsed at a recorded step: no path
-    for (int64_t t = 0; t < T && !dead; ++t) {
-        bool any = false;
-        for (int64_t i = 0; i < n; ++i) any = any || w[(size_t)t * n + i] > 0.0;
-        dead = !any;
-    }
+    const bool dead = host_dead(T, n, w);   // no path
     std::vector<double> m((size_t)D * n), s((size_t)n), g((size_t)n), b((size_t)n);
     for (int64_t t = T - 1; t >= 0; --t) {
         const bool last = t == T - 1;
@@ -596,18 +609,7 @@ static void host_paths_t(const SmoothRow& k, int64_t T, int64_t n, const double*
                     }
                     Mx = b[l] > Mx ? b[l] : Mx;
                 }
-                uint64_t S = 0;
-                for (int64_t l = 0; l < n; ++l)
-                    if (wt[l] > 0.0) S += path_weight(b[l], Mx);
-                if (S) {
-                    const uint64_t r = mulhi64(path_uniform(seed, p, stream, (uint32_t)t), S);
-                    uint64_t C = 0;
-                    for (int64_t l = 0; l < n; ++l) {
-                        if (!(wt[l] > 0.0)) continue;
-                        C += path_weight(b[l], Mx);
-                        if (C > r) { pick = l; break; }
-                    }
-                }
+                pick = host_path_pick(n, wt, b.data(), Mx, seed, p, stream, t);
             }
             idx[(size_t)t * M + p] = (int32_t)pick;
             if (xs)
@@ -625,9 +627,7 @@ extern "C" int smc_host_sample_paths(int model_id, const double* raw, int64_t T,
     SmoothRow k;
     if (!smooth_row(model_id, raw, k))
         return fail(SMC_EINVAL, "smc_host_sample_paths: no transition density for this family, or a transition scale that is not positive and finite");
-    if (model_id == MODEL_LG1D) host_paths_t<MODEL_LG1D>(k, T, n, x, w, M, path_seed, stream, idx, xs);
-    else if (model_id == MODEL_SV1D) host_paths_t<MODEL_SV1D>(k, T, n, x, w, M, path_seed, stream, idx, xs);
-    else host_paths_t<MODEL_UCSV3D>(k, T, n, x, w, M, path_seed, stream, idx, xs);
+    (void)by_density_model(model_id, [&](auto Mt) { host_paths_t<decltype(Mt)::value>(k, T, n, x, w, M, path_seed, stream, idx, xs); return hipSuccess; });
     return SMC_OK;
 }
 
@@ -645,12 +645,7 @@ extern "C" int smc_host_rb_sample_paths(const double* raw, int64_t T, int64_t n,
     if (!smooth_row(MODEL_UCSV3D, raw, k)) return fail(SMC_EINVAL, "smc_host_rb_sample_paths: a gamma is not a positive finite number");
     const size_t sx = (size_t)4 * n;
     const double nan = bits2d(0x7ff8000000000000ULL);
-    bool dead = false;   // a filter that collapsed at a recorded step: no path
-    for (int64_t t = 0; t < T && !dead; ++t) {
-        bool any = false;
-        for (int64_t i = 0; i < n; ++i) any = any || w[(size_t)t * n + i] > 0.0;
-        dead = !any;
-    }
+    const bool dead = host_dead(T, n, w);   // no path
     std::vector<double> sv((size_t)RB_NV * n), b((size_t)n), own((size_t)4 * M, 0.0);
     for (int64_t t = T - 1; t >= 0; --t) {
         const bool last = t == T - 1;
@@ -672,18 +667,7 @@ extern "C" int smc_host_rb_sample_paths(const double* raw, int64_t T, int64_t n,
                     b[l] = rb_pair(k, &sv[(size_t)RB_NV * l], oo);
                     Mx = b[l] > Mx ? b[l] : Mx;
                 }
-                uint64_t S = 0;
-                for (int64_t l = 0; l < n; ++l)
-                    if (wt[l] > 0.0) S += path_weight(b[l], Mx);
-                if (S) {
-                    const uint64_t r = mulhi64(path_uniform(path_seed, p, stream, (uint32_t)t), S);
-                    uint64_t C = 0;
-                    for (int64_t l = 0; l < n; ++l) {
-                        if (!(wt[l] > 0.0)) continue;
-                        C += path_weight(b[l], Mx);
-                        if (C > r) { pick = l; break; }
-                    }
-                }
+                pick = host_path_pick(n, wt, b.data(), Mx, path_seed, p, stream, t);
             }
             idx[(size_t)t * M + p] = (int32_t)pick;
             double lse = nan, lsn = nan;

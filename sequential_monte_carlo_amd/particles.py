@@ -323,6 +323,17 @@ def _paths_out(idx, xs, single):
     return (idx[:, 0], xs[:, 0]) if single else (idx, xs)
 
 
+def _run_recorded(h, y):
+    """the filter of log_likelihood over y step by step on a handle that records (history_begin by the caller, who also ends it):
+    the per-step (logmu [T][n_theta], ess [T][n_theta]) and logZ [n_theta]"""
+    lm, es = np.zeros((y.size, h.n_theta)), np.zeros((y.size, h.n_theta))
+    lm[0] = h.init(float(y[0]))
+    es[0] = h.logZ()[1]
+    for t in range(1, y.size):
+        lm[t], es[t] = h.step(float(y[t]))
+    return lm, es, h.logZ()[0]
+
+
 def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="multinomial", proposal=None, weights=False, rows=None,
              paths=0, path_seed=None, path_counts=None, smooth=True):
     """x, w, logZ, s = smoother(N, y, model): the particle filter of log_likelihood run step by step with its clouds recorded on
@@ -352,12 +363,7 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
         raise ValueError("smoother needs at least one observation")
     h.history_begin(T)
     try:
-        lm, es = np.zeros((T, h.n_theta)), np.zeros((T, h.n_theta))
-        lm[0] = h.init(float(y[0]))
-        es[0] = h.logZ()[1]
-        for t in range(1, T):
-            lm[t], es[t] = h.step(float(y[t]))
-        logZ = h.logZ()[0]
+        lm, es, logZ = _run_recorded(h, y)
         s = {}
         if smooth or weights:
             ws, mean, var = h.smooth(weights=weights, moments=True)
@@ -407,12 +413,7 @@ def rb_smoother(N, y, model, paths=256, seed=None, path_seed=None, draws=False, 
         raise ValueError("rb_smoother needs at least one observation")
     h.history_begin(T)
     try:
-        lm, es = np.zeros((T, h.n_theta)), np.zeros((T, h.n_theta))
-        lm[0] = h.init(float(y[0]))
-        es[0] = h.logZ()[1]
-        for t in range(1, T):
-            lm[t], es[t] = h.step(float(y[t]))
-        logZ = h.logZ()[0]
+        lm, es, logZ = _run_recorded(h, y)
         r = h.rb_sample_paths(y, int(paths), _path_seed(seed) if path_seed is None else int(path_seed), counts=path_counts, draws=draws,
                               per_path=per_path)
     finally:

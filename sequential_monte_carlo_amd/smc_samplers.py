@@ -605,6 +605,30 @@ def smoothed_state(smc, y, N=None, max_bytes=2 ** 31, seed=None):
 _U64 = 0xFFFFFFFFFFFFFFFF
 
 
+def _path_counts(smc, M, seed):
+    """(counts [smc.M] int32, the parameter particles with a positive count): the parameter particle of each of M paths drawn from
+    omega through the library's own outer resampler (M ancestors in ascending order)"""
+    smc._sync_outer()
+    anc = np.asarray(_lib.host_outer_resample(smc.logw, M, (seed + 1) & _U64), dtype=np.int64)
+    counts = np.bincount(anc, minlength=smc.M).astype(np.int32)
+    return counts, np.flatnonzero(counts)
+
+
+def _greedy_blocks(counts, nbytes, max_bytes):
+    """yields (b0, b1, cmax): consecutive blocks of the filters with path counts `counts`, each as long as nbytes(filters, largest
+    count) stays within max_bytes (a block holds at least one filter); every filter of a block holds cmax path slots"""
+    b0 = 0
+    while b0 < counts.size:
+        b1, cmax = b0, 0
+        while b1 < counts.size:
+            c = max(cmax, int(counts[b1]))
+            if b1 > b0 and nbytes(b1 + 1 - b0, c) > int(max_bytes):
+                break
+            b1, cmax = b1 + 1, c
+        yield b0, b1, cmax
+        b0 = b1
+
+
 def smoothed_paths(smc, y, M, N=None, max_bytes=2 ** 31, seed=None):
     """M trajectories [T][M] ([T][M][d] for a state of d coordinates) from p(x_1:T | y_1:T) integrated over the sampler's current
     parameter cloud, by backward simulation (particles.smoother(paths=...)): the parameter particle of every path
@@ -624,29 +648,18 @@ def smoothed_paths(smc, y, M, N=None, max_bytes=2 ** 31, seed=None):
         raise ValueError("M must be positive")
     N = smc.N if N is None else int(N)
     seed = (((smc.seed << 20) | 0xBAC45) if seed is None else int(seed)) & _U64       # (one 64-bit word for the filters as well)
-    smc._sync_outer()
-    anc = np.asarray(_lib.host_outer_resample(smc.logw, M, (seed + 1) & _U64), dtype=np.int64)     # ascending
-    counts = np.bincount(anc, minlength=smc.M).astype(np.int32)
-    used = np.flatnonzero(counts)
+    counts, used = _path_counts(smc, M, seed)
     mid, raw = _rows(smc._models(smc.theta))
     d = _lib.lib().smc_model_dim(int(mid))
     out = np.zeros((y.size, M, d))
     first = np.concatenate([[0], np.cumsum(counts)])                  # path slots of parameter particle m: first[m] .. first[m + 1]
-    b0 = 0
-    while b0 < used.size:                                             # greedy blocks: every filter of a block holds max-count slots
-        b1, cmax = b0, 0
-        while b1 < used.size:
-            c = max(cmax, int(counts[used[b1]]))
-            if b1 > b0 and (b1 + 1 - b0) * y.size * (N * (d + 1) * 8 + c * (4 + 8 * d)) > int(max_bytes):
-                break
-            b1, cmax = b1 + 1, c
+    for b0, b1, cmax in _greedy_blocks(counts[used], lambda k, c: k * y.size * (N * (d + 1) * 8 + c * (4 + 8 * d)), max_bytes):
         ms = used[b0:b1]
         _, _, _, s = smoother(N, y, None, rows=(int(mid), raw[ms]), seed=seed, device=getattr(smc.backend, "device", 0),
                               streams=ms.astype(np.uint32), paths=cmax, path_seed=(seed + 2) & _U64, path_counts=counts[ms], smooth=False)
         xs = s["paths"].reshape(y.size, ms.size, cmax, d)
         for k, m in enumerate(ms):
             out[:, first[m]:first[m + 1]] = xs[:, k, :counts[m]]
-        b0 = b1
     return out[..., 0] if d == 1 else out
 
 
@@ -673,20 +686,10 @@ def rb_smoothed_state(smc, y, M, N=None, max_bytes=2 ** 31, seed=None):
     if int(mid) != _lib.MODEL_UCSV_RB:
         raise TypeError("rb_smoothed_state needs a sampler over MarginalUCSV; the other families have smoothed_state")
     seed = (((smc.seed << 20) | 0x4B5A7) if seed is None else int(seed)) & _U64
-    smc._sync_outer()
-    anc = np.asarray(_lib.host_outer_resample(smc.logw, M, (seed + 1) & _U64), dtype=np.int64)
-    counts = np.bincount(anc, minlength=smc.M).astype(np.int32)
-    used = np.flatnonzero(counts)
+    counts, used = _path_counts(smc, M, seed)
     T = y.size
     outs = np.zeros((T, used.size, 8))
-    b0 = 0
-    while b0 < used.size:                                             # greedy blocks: every filter of a block holds max-count slots
-        b1, cmax = b0, 0
-        while b1 < used.size:
-            c = max(cmax, int(counts[used[b1]]))
-            if b1 > b0 and (b1 + 1 - b0) * T * (N * 5 * 8 + c * (4 + 8 * 4)) > int(max_bytes):
-                break
-            b1, cmax = b1 + 1, c
+    for b0, b1, cmax in _greedy_blocks(counts[used], lambda k, c: k * T * (N * 5 * 8 + c * (4 + 8 * 4)), max_bytes):
         ms = used[b0:b1]
         h_res = rb_smoother(N, y, None, rows=(int(mid), raw[ms]), seed=seed, device=getattr(smc.backend, "device", 0),
                             streams=ms.astype(np.uint32), paths=cmax, path_seed=(seed + 2) & _U64, path_counts=counts[ms])[3]
@@ -695,7 +698,6 @@ def rb_smoothed_state(smc, y, M, N=None, max_bytes=2 ** 31, seed=None):
         outs[:, b0:b1, [3, 5]] = h_res["vol_mean"]
         outs[:, b0:b1, [4, 6]] = h_res["vol_var"]
         outs[:, b0:b1, 7] = h_res["n_paths"]
-        b0 = b1
     return _rb_combine(outs)
 
 

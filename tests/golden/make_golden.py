@@ -10,7 +10,11 @@ Sources of truth:
   * sampler_* : the PMMH pieces (proposal, accept uniform, prior log densities) of the oracle, and whole small sampler
                 runs (density_tempered, online SMC^2) of the host mirror over the oracle backend with the device-style
                 rejuvenation; the HIP backend must reproduce theta / logZ / ladder bit for bit.
+  * backward_twins.npz : the host twins of the smoother and of backward simulation on seeded clouds, inputs and outputs, taken
+                once with the library as it was before the twins shared their helpers (backward_twins below; not part of a
+                plain run).
 Run:  python tests/golden/make_golden.py      (from the repo root)
+      python tests/golden/make_golden.py backward_twins      (that file alone)
 """
 import json
 import os
@@ -138,5 +142,62 @@ def sampler_vectors():
         json.dump(out, f, indent=1)
 
 
+BACKWARD_T, BACKWARD_M, BACKWARD_SEED, BACKWARD_STREAM, BACKWARD_DEAD_T = 12, 65, 0x5EEDC0FFEE12345, 3, 5
+RB = [0.2, 0.3, 1.0, -1.0, -0.5]        # (g_eps, g_eta, x0, lse0, lsn0)
+# family -> (model id or None for the Rao-Blackwellised twin, row, state rows, sizes): with SMOOTH_CH = 128, 65 is one short chunk
+# and 130 two chunks with a short tail
+BACKWARD_FAMILIES = {"lg": (1, LG, 1, (1, 65, 130)), "sv": (2, SV, 1, (1, 65, 130)), "ucsv": (3, UC, 3, (1, 65, 130)),
+                     "rb": (None, RB, 4, (1, 65, 130))}
+
+
+def backward_twin_outputs(L, fam, x, w, y):
+    """every array the host twins of the backward walk return for one record, by name"""
+    model, raw = BACKWARD_FAMILIES[fam][:2]
+    if model is None:
+        return L.host_rb_sample_paths(raw, x, w, y, BACKWARD_M, BACKWARD_SEED, BACKWARD_STREAM)
+    ws, mean, var = L.host_smooth(model, raw, x, w)
+    idx, xs = L.host_sample_paths(model, raw, x, w, BACKWARD_M, BACKWARD_SEED, BACKWARD_STREAM)
+    return {"ws": ws, "mean": mean, "var": var, "idx": idx, "xs": xs}
+
+
+def backward_twins():
+    """backward_twins.npz: the host twins of the backward walk (smc_host_smooth, smc_host_sample_paths, smc_host_rb_sample_paths)
+    on seeded clouds, inputs and outputs.  Taken ONCE, with the library of the commit before the twins came to share their
+    helpers, so that a changed order of summation or selection shows as changed bits; regenerating it with a later library
+    would only pin that library to itself.  Keys: <family>_n<n>/<array>, and <family>_dead/<array> for the n = 65 record with
+    the weights of step BACKWARD_DEAD_T set to 0 (its inputs are not stored again)."""
+    from sequential_monte_carlo_amd import _lib as L
+    rng = np.random.default_rng(20261019)
+    arrs = {"y": rng.normal(size=BACKWARD_T).astype(np.float32).astype(np.float64)}
+    for fam, (model, raw, d, sizes) in BACKWARD_FAMILIES.items():
+        complete = missing = 0
+        for n in sizes:
+            # (states with a float32 mantissa: the file compresses, the twins do not care)
+            x = (rng.normal(size=(BACKWARD_T, d, n)) * (0.3 if d > 1 else 1.0)).astype(np.float32).astype(np.float64)
+            if model is None:
+                x[:, 3] = np.exp(x[:, 3]).astype(np.float32)           # the trend's variance row is positive
+            w = rng.uniform(0.5, 1.5, size=(BACKWARD_T, n))
+            if n > 1:
+                w[:, ::7] = 0.0                                        # every seventh weight exactly 0
+            w /= w.sum(axis=1, keepdims=True)
+            records = [("%s_n%d" % (fam, n), w)]
+            if n == 65:
+                wd = w.copy()
+                wd[BACKWARD_DEAD_T] = 0.0
+                records.append((fam + "_dead", wd))
+            for name, wr in records:
+                if not name.endswith("_dead"):
+                    arrs[name + "/x"], arrs[name + "/w"] = x, wr
+                for k, v in backward_twin_outputs(L, fam, x, wr, arrs["y"]).items():
+                    arrs[name + "/" + k] = v
+                complete += int(np.sum(np.all(arrs[name + "/idx"] >= 0, axis=0)))
+                missing += int(np.sum(arrs[name + "/idx"] == -1))
+        assert complete > 0 and missing > 0, (fam, complete, missing)     # (a run that refused everything would pin nothing)
+    path = os.path.join(OUT, "backward_twins.npz")
+    np.savez_compressed(path, **arrs)
+    assert os.path.getsize(path) <= os.path.getsize(os.path.join(OUT, "filter_vectors.npz")), os.path.getsize(path)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    backward_twins() if sys.argv[1:] == ["backward_twins"] else main()
