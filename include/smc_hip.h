@@ -71,7 +71,8 @@ int smc_destroy(smc_handle h);
  *     filters (LG1D AFFINE - also with c2 = 0, since 0 * y is NaN - LG1D OPTIMAL, UCSV OPTIMAL) and SMC_MODEL_UCSV_RB carry y
  *     into the state (the proposal mean; the Kalman mean m): dead from that step on.  The first step of a guided filter is the
  *     bootstrap first step, so a bad y_1 costs a guided filter that step alone; SMC_MODEL_UCSV_RB is dead from it on.
- *     There are no missing-data semantics: a gap in the series must be left out by the caller, not passed as NaN.
+ *     There are no missing-data semantics: a gap in the series must be left out by the caller, not passed as NaN.  (Looking past
+ *     the END of the series is smc_forecast, "forecasts" below: it propagates the cloud without observations.)
  *   - a row outside its family's domain makes its filter dead: LG1D R <= 0 or a NaN B, SV1D |rho| >= 1 or a NaN sigma, UCSV a NaN
  *     x0, lse0 = +inf (and for the bootstrap filter lsn0 = -inf) from the first step; LG1D Q < 0, Q = +inf or a NaN A from the
  *     second (the first step does not move the particles).  LG1D sigma0 = 0 is valid (x_1 = x0).  A NEGATIVE UCSV gamma is a live
@@ -547,6 +548,56 @@ int smc_get_moments(smc_handle h, double* mean, double* var);
  * out [n_theta][np]; NaN for a collapsed filter.  The README's unweighted, interpolating quantile(x, p) is
  * the SMC_SUMM_UNWEIGHTED mode (smc_set_summary_mode, which also names the one variant not offered). */
 int smc_get_quantiles(smc_handle h, int component, const double* p, int np, double* out);
+
+/* ---- forecasts: the cloud propagated past the last observation ---------------------------------------------------------------
+ * p(x_{T+k} | y_1:T) and p(y_{T+k} | y_1:T), k = 1..H, from the current state of the handle (the x, w of smc_get_state) without a
+ * copy of the cloud to the host.  Without an observation there is nothing to weigh: no resampling, no normalisation.  Every
+ * particle is a chain of its own - its states over the H horizons are ONE coherent trajectory - and keeps its weight.
+ * Specification (csrc/smc_spec.h "forecasts"), one step of one particle:
+ *   LG1D, SV1D, UCSV3D   x_k = rand(transition(x_{k-1}));  (ym, sd) = mean and standard deviation of observation(x_k);
+ *                        yv = sd sd;  yf = fma(sd, e, ym)
+ *   UCSV_RB              the marginal step with the measurement update left out.  With (m, a, b, P) = x_{k-1}:
+ *                        P- = P + exp(a);  lse = fma(g_eps, z0, a);  lsn = fma(g_eta, z1, b);  x_k = (m, lse, lsn, P-);
+ *                        ym = m;  yv = P- + exp(lsn);  yf = fma(sqrt(yv), e, ym)
+ * A handle with a proposal (smc_set_proposal) forecasts by the TRANSITION law like any other: a proposal has no role without y.
+ * Random numbers: particle i of filter m at horizon k (1-based) takes element i & 1 of the Box-Muller pair of
+ * Philox(key = forecast_seed; pair i >> 1, stream[m], k, slot 1 + c) for state normal c, and of slot 8 for e: the convention
+ * of the filter's own steps under a seed of the caller's (use one that is not the filter's).  Trajectory i is a function of
+ * (parameter row, x_T[i], forecast_seed, stream, i) alone: it does not depend on H, on the launch geometry or on how the
+ * horizons are blocked (below), and smc_host_forecast reproduces it bit for bit.
+ *
+ * smc_forecast: per horizon and filter, under the handle's CURRENT weights (emitted first, as smc_get_moments does) and always
+ * by the WEIGHTED definitions - the handle's summary mode is neither consulted nor changed:
+ *   mean, var   [H][d][n_theta]   smc_get_moments' definition and accuracy, of every state row of the propagated cloud
+ *   q           [H][n_theta][np]  smc_get_quantiles' definition (inverse of the weighted empirical CDF in the integer weights, no
+ *                                 interpolation) of state row `component`
+ *   obs_q       [H][n_theta][np]  the same definition applied to the predictive draws yf
+ *   obs_mean    [H][n_theta]      sum w ym
+ *   obs_var     [H][n_theta]      sum w yv + sum w (ym - obs_mean)^2: the variance of the mixture, within plus between,
+ *                                 Rao-Blackwellised over the observation noise (each term with smc_get_moments' accuracy)
+ * Any output may be NULL; p [np], np <= 8 (0: no quantiles).  A collapsed filter (every weight 0) reads NaN in every row, like its
+ * filtered summaries.  For UCSV_RB the forecast trend is a mixture as well: mean = mean of row 0, variance = var of row 0 + mean of
+ * row 3.  SMC_ESTATE before smc_init; SMC_EINVAL for H < 1, np outside 0..8, and with np > 0 for a component outside [0, d) or p
+ * NULL.  An error leaves the state of the handle, and the results of a following call, as they were.
+ * smc_forecast_cloud: the propagated clouds themselves, xf [H][d][n_theta][n_x] and the predictive draws yf [H][n_theta][n_x], dense
+ * (no padding); either may be NULL.  With the w of smc_get_state these are weighted trajectories: fan charts, x_{T+k} - x_T,
+ * functionals of the whole path.
+ * Both READ the handle: x, the weights and their records, logZ, the ancestors, a pending window (smc_step_window) and the record
+ * of an armed handle (smc_history_begin) are untouched, and the steps that follow give the bits they would have given.
+ * Memory: the clouds of a BLOCK of horizons (8, fewer while a block would exceed 512 MiB; [block][d + 3][n_theta][n_pad] doubles),
+ * the scratch of the summaries and the results of the H horizons live in ONE device block owned by the handle: grown on demand,
+ * kept between calls, freed by smc_destroy and never handed to the pool of recycled handles.  A block is summarised (or copied
+ * out) before the next overwrites it, so the block bounds the memory whatever H.  SMC_ENOMEM leaves the handle usable and without
+ * that block.  The environment variable SMC_FORECAST_BLOCK, read at the call, overrides the block length (tuning / tests): the
+ * results are the same bits for every block length.
+ * smc_host_forecast: the same specification for n particles x [d][n] of ONE filter (parameter row raw, Philox stream `stream`) on
+ * the host, no GPU needed: xf [H][d][n], yf, ym, yv [H][n] (NULL: not wanted).  The device clouds equal it bit for bit. */
+int smc_forecast(smc_handle h, int64_t H, uint64_t forecast_seed, int component, const double* p /*[np]*/, int np,
+                 double* mean, double* var /*[H][d][n_theta]*/, double* q /*[H][n_theta][np]*/,
+                 double* obs_mean, double* obs_var /*[H][n_theta]*/, double* obs_q /*[H][n_theta][np]*/);
+int smc_forecast_cloud(smc_handle h, int64_t H, uint64_t forecast_seed, double* xf /*[H][d][n_theta][n_x]*/, double* yf /*[H][n_theta][n_x]*/);
+int smc_host_forecast(int model_id, const double* raw, const double* x /*[d][n]*/, int64_t n, int64_t H, uint64_t forecast_seed, uint32_t stream,
+                      double* xf /*[H][d][n]*/, double* yf /*[H][n]*/, double* ym /*[H][n]*/, double* yv /*[H][n]*/);
 
 /* ---- the smoother: forward filtering, backward smoothing (FFBS; Kitagawa 1996, Doucet, Godsill and Andrieu 2000) -------------
  * Everything above describes p(x_t | y_1:t).  The reference has no smoother: examples/inflation_example.jl:153-176 draws a

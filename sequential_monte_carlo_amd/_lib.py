@@ -38,6 +38,7 @@ EXPORTS = [
     "smc_ibis_smooth", "smc_ibis_sample_paths", "smc_ibis_last_elapsed_ms", "smc_kalman_smooth", "smc_host_ibis_smooth", "smc_host_ibis_sample_paths",
     "smc_history_begin", "smc_history_len", "smc_history_get", "smc_history_put", "smc_history_end", "smc_smooth", "smc_host_transition_logpdf",
     "smc_host_smooth", "smc_sample_paths", "smc_host_sample_paths", "smc_rb_sample_paths", "smc_host_rb_sample_paths",
+    "smc_forecast", "smc_forecast_cloud", "smc_host_forecast",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -214,6 +215,9 @@ def lib():
     L.smc_host_sample_paths.argtypes = [C.c_int, _dp, C.c_int64, C.c_int64, _dp, _dp, C.c_int64, C.c_uint64, C.c_uint32, _i32p, _dp]
     L.smc_rb_sample_paths.argtypes = [h, _dp, C.c_int64, C.c_int64, C.c_uint64, _i32p, _i32p, _dp, _dp, _dp, _dp, _dp]
     L.smc_host_rb_sample_paths.argtypes = [_dp, C.c_int64, C.c_int64, _dp, _dp, _dp, C.c_int64, C.c_uint64, C.c_uint32, _i32p, _dp, _dp, _dp, _dp, _dp]
+    L.smc_forecast.argtypes = [h, C.c_int64, C.c_uint64, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
+    L.smc_forecast_cloud.argtypes = [h, C.c_int64, C.c_uint64, _dp, _dp]
+    L.smc_host_forecast.argtypes = [C.c_int, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, _dp]
     L.smc_last_error.restype = C.c_char_p
     L.smc_version.restype = C.c_char_p
     _lib = L
@@ -723,6 +727,32 @@ class Handle:
         check(lib().smc_get_summaries(self._h, int(T), _d(q), _d(mean), _d(var)))
         return q, mean, var
 
+    def forecast(self, H, seed, p=None, component=0, obs=True):
+        """the cloud propagated H steps past the last observation, summarised per horizon on the device under the current weights
+        (smc_forecast; always the weighted definitions): a dict of mean, var [H][d][n_theta], q [H][n_theta][len(p)] (p given) and,
+        with obs, obs_mean, obs_var [H][n_theta] and obs_q of the predictive law of y.  seed: the Philox key of the forecast draws."""
+        H = int(H)
+        p = np.ascontiguousarray([] if p is None else p, dtype=np.float64).ravel()
+        out = {"mean": np.zeros((H, self.d, self.n_theta)), "var": np.zeros((H, self.d, self.n_theta))}
+        if p.size:
+            out["q"] = np.zeros((H, self.n_theta, p.size))
+        if obs:
+            out["obs_mean"], out["obs_var"] = np.zeros((H, self.n_theta)), np.zeros((H, self.n_theta))
+            if p.size:
+                out["obs_q"] = np.zeros((H, self.n_theta, p.size))
+        check(lib().smc_forecast(self._h, H, int(seed) & 0xFFFFFFFFFFFFFFFF, int(component), _d(p) if p.size else None, p.size, _d(out["mean"]),
+                                 _d(out["var"]), _d(out.get("q")), _d(out.get("obs_mean")), _d(out.get("obs_var")), _d(out.get("obs_q"))))
+        return out
+
+    def forecast_cloud(self, H, seed, want_y=True):
+        """(xf [H][d][n_theta][n_x], yf [H][n_theta][n_x] or None): the propagated clouds themselves and the predictive draws of y
+        (smc_forecast_cloud); with the w of state() they are weighted trajectories"""
+        H = int(H)
+        xf = np.zeros((H, self.d, self.n_theta, self.n_x))
+        yf = np.zeros((H, self.n_theta, self.n_x)) if want_y else None
+        check(lib().smc_forecast_cloud(self._h, H, int(seed) & 0xFFFFFFFFFFFFFFFF, _d(xf), _d(yf)))
+        return xf, yf
+
     def copy_from(self, src, mask):
         m = np.ascontiguousarray(mask, dtype=np.uint8)
         assert m.size == self.n_theta
@@ -923,6 +953,19 @@ def host_rb_sample_paths(raw, x, w, y, M, seed, stream=0, draws=True, summary=Tr
     check(lib().smc_host_rb_sample_paths(_d(raw), T, n, _d(x), _d(w), _d(y), int(M), int(seed), int(stream), r["idx"].ctypes.data_as(_i32p),
                                          _d(r["vol"]), _d(r["tmean"]), _d(r["tvar"]), _d(r.get("tdraw")), _d(r.get("out"))))
     return r
+
+
+def host_forecast(model_id, raw, x, H, seed, stream=0):
+    """the forecast specification on the host (smc_host_forecast): x [d][n] (or [n] for a scalar state) of ONE filter ->
+    (xf [H][d][n], yf, ym, yv [H][n]); the device clouds equal it bit for bit"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    d = lib().smc_model_dim(model_id)
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(d, -1)
+    n, H = x.shape[1], int(H)
+    xf = np.zeros((H, d, n))
+    yf, ym, yv = np.zeros((H, n)), np.zeros((H, n)), np.zeros((H, n))
+    check(lib().smc_host_forecast(model_id, _d(raw), _d(x), n, H, int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), _d(xf), _d(yf), _d(ym), _d(yv)))
+    return xf, yf, ym, yv
 
 
 def host_sample_paths(model_id, raw, x, w, M, seed, stream=0, want_x=True):

@@ -383,6 +383,7 @@ extern "C" int smc_destroy(smc_handle h) {
     (void)hipFree(h->pm.dev.prop); (void)hipFree(h->pm.dev.lp); (void)hipFree(h->pm.dev.skip); (void)hipFree(h->pm.dev.mask);
     if (h->d_brk) (void)hipFree(h->d_brk);
     if (h->summ.d_ms) (void)hipFree(h->summ.d_ms);
+    if (h->fc.d_buf) (void)hipFree(h->fc.d_buf);
     if (!kept) (void)hipFree(h->d_y);
     (void)hipFree(h->d_tr_logmu); (void)hipFree(h->d_tr_ess); (void)hipFree(h->d_wdense); if (!kept) (void)hipFree(h->d_recs);
     (void)hipFree(h->summ.d_q); (void)hipFree(h->summ.d_m);

@@ -49,15 +49,12 @@ static int ensure_ms(smc_handle h) {
     }
     return SMC_OK;
 }
+// v: the view whose sum_* fields name the request and whose x[cur] points at the cloud, `rows` state rows [rows][ntheta][npad] under
+// the handle's current weights; ms: scratch carved for `rows` rows
 template <bool UNW>
-static int enqueue_ms_t(smc_handle h, int component, int np, const uint64_t* p64, bool mom, double* q_out, double* mean, double* var) {
-    const size_t nth = (size_t)h->v.ntheta;
-    int rc = ensure_ms(h);
-    if (rc) return rc;
-    const MsScratch ms = ms_carve(h->summ.d_ms, nth, (size_t)h->v.nseg, (size_t)h->d);
-    FilterView v = h->v;
-    v.sum_np = np; v.sum_comp = np > 0 ? component : 0; v.sum_mom = mom ? 1 : 0;
-    for (int j = 0; j < QMAX; ++j) v.sum_p64[j] = j < np ? p64[j] : 0;
+static int enqueue_ms_view(smc_handle h, const FilterView& v, int rows, const MsScratch& ms, double* q_out, double* mean, double* var) {
+    const int np = v.sum_np;
+    const bool mom = v.sum_mom != 0;
     // streaming kernels: workgroups of 1024 threads over consecutive segments - about 256 workgroups in all for the passes that
     // only read, about 64 for the histogram (every workgroup flushes its occupied bins with device-scope atomics)
     auto groups = [&](int want) {
@@ -66,12 +63,12 @@ static int enqueue_ms_t(smc_handle h, int component, int np, const uint64_t* p64
         return g > h->v.nseg ? h->v.nseg : g;
     };
     const int g_read = groups(256), g_hist = groups(64);
-    hipLaunchKernelGGL(k_ms_range<UNW>, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, h->d, ms);
+    hipLaunchKernelGGL(k_ms_range<UNW>, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, rows, ms);
     if (np > 0) hipLaunchKernelGGL(k_ms_hist<UNW>, dim3(g_hist, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, g_read, ms);
-    hipLaunchKernelGGL(k_ms_pick<UNW>, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, h->d, g_read, ms, q_out, mean);
+    hipLaunchKernelGGL(k_ms_pick<UNW>, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, rows, g_read, ms, q_out, mean);
     if (mom) {   // the variance centred on that mean: a second read of the cloud
-        hipLaunchKernelGGL(k_ms_center<UNW>, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, h->d, ms, (const double*)mean);
-        hipLaunchKernelGGL(k_ms_var<UNW>, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, h->d, g_read, ms, var);
+        hipLaunchKernelGGL(k_ms_center<UNW>, dim3(g_read, h->v.ntheta), dim3(MS_STREAM), 0, h->stream, v, h->cur, rows, ms, (const double*)mean);
+        hipLaunchKernelGGL(k_ms_var<UNW>, dim3(h->v.ntheta), dim3(MS_THREADS), 0, h->stream, v, rows, g_read, ms, var);
     }
     int64_t two_level = MS_TWO_LEVEL;
     if (const char* e = getenv("SMC_MS_TWO_LEVEL")) two_level = atoll(e);   // tuning / test knob: results do not depend on it
@@ -91,6 +88,38 @@ static int enqueue_ms_t(smc_handle h, int component, int np, const uint64_t* p64
     }
     HIPCHK(hipGetLastError());
     return SMC_OK;
+}
+// the request as a view of the handle: levels p64 of `component`, moments or not
+static FilterView summary_view(const smc_filter_s* h, int component, int np, const uint64_t* p64, bool mom) {
+    FilterView v = h->v;
+    v.sum_np = np; v.sum_comp = np > 0 ? component : 0; v.sum_mom = mom ? 1 : 0;
+    for (int j = 0; j < QMAX; ++j) v.sum_p64[j] = j < np ? p64[j] : 0;
+    return v;
+}
+template <bool UNW>
+static int enqueue_ms_t(smc_handle h, int component, int np, const uint64_t* p64, bool mom, double* q_out, double* mean, double* var) {
+    const size_t nth = (size_t)h->v.ntheta;
+    int rc = ensure_ms(h);
+    if (rc) return rc;
+    const MsScratch ms = ms_carve(h->summ.d_ms, nth, (size_t)h->v.nseg, (size_t)h->d);
+    return enqueue_ms_view<UNW>(h, summary_view(h, component, np, p64, mom), h->d, ms, q_out, mean, var);
+}
+// The WEIGHTED summaries (whatever the handle's summary mode) of another cloud under the handle's current weights: `rows` <= MAX_DIM
+// rows [rows][ntheta][npad] on the device, e.g. one horizon of a forecast (smc_capi_forecast.hip).  scratch: cloud_summary_words(h,
+// scratch_rows) words, scratch_rows >= rows, zeroed once by the caller and always carved for scratch_rows (the kernels leave their
+// histograms and counters zeroed for the next request only where THIS carving keeps them); results as enqueue_ms leaves them
+// (device pointers; q_out [ntheta][np], mean / var [rows][ntheta]).
+size_t cloud_summary_words(const smc_filter_s* h, int rows) { return ms_words((size_t)h->v.ntheta, (size_t)h->v.nseg, (size_t)rows); }
+int enqueue_cloud_summaries(smc_handle h, const double* cloud, int rows, uint64_t* scratch, int scratch_rows, int component, const double* p, int np,
+                            bool mom, double* q_out, double* mean, double* var) {
+    if (rows < 1 || rows > MAX_DIM || rows > scratch_rows || np < 0 || np > QMAX) return fail(SMC_EINVAL, "cloud summaries: rows / levels out of range");
+    uint64_t pw[QMAX];
+    for (int j = 0; j < QMAX; ++j) pw[j] = j < np ? prob_to_u64(p[j]) : 0;
+    FilterView v = summary_view(h, component, np, pw, mom);
+    v.sum_unw = 0;
+    v.x[h->cur] = const_cast<double*>(cloud);   // (the summary kernels only read it)
+    const MsScratch ms = ms_carve(scratch, (size_t)h->v.ntheta, (size_t)h->v.nseg, (size_t)scratch_rows);
+    return enqueue_ms_view<false>(h, v, rows, ms, q_out, mean, var);
 }
 static int enqueue_ms(smc_handle h, int component, int np, const uint64_t* p64, bool mom, double* q_out, double* mean, double* var) {
     return h->summ.mode == SMC_SUMM_UNWEIGHTED ? enqueue_ms_t<true>(h, component, np, p64, mom, q_out, mean, var)

@@ -1,7 +1,7 @@
 // smc_host.h -- what the host-side translation units of libsmchip.so share: the error string behind smc_last_error(), HIPCHK,
 // the filter handle, and the few helpers that cross files.  Internal: not installed, not part of the ABI (include/smc_hip.h).
 // The entry points on a handle: smc_capi.hip (core), smc_capi_series.hip, smc_capi_summ.hip, smc_capi_pmmh.hip,
-// smc_capi_slots.hip, smc_capi_smooth.hip; without one: smc_util.hip.
+// smc_capi_slots.hip, smc_capi_smooth.hip, smc_capi_forecast.hip; without one: smc_util.hip.
 #pragma once
 #include "../../include/smc_hip.h"
 #include "smc_launch.h"
@@ -125,6 +125,10 @@ struct smc_filter_s {
         char* d_path = nullptr;                // the backward walk (smc_sample_paths, or smc_rb_sample_paths on a MODEL_UCSV_RB handle), its own
         size_t path_bytes = 0;                 //   block: cur | pmax | psum | rmax | rows | dead | counts | idx [T][ntheta][M] | the caller's tail
     } hist;
+    struct {   // forecasts (smc_capi_forecast.hip): ONE block, grown on demand and freed by smc_destroy
+        char* d_buf = nullptr;                 // clouds [block][d + 3][ntheta][npad] | summary scratch | results of every horizon
+        size_t bytes = 0;
+    } fc;
     struct {   // PMMH rejuvenation (smc_capi_pmmh.hip): this handle holds the proposal filters
         smc::PmmhSpec spec{};
         bool cfg = false;
@@ -171,6 +175,10 @@ bool summaries_fit_lds(const smc_filter_s* h);
 int ensure_summaries(smc_handle h, int64_t T);
 void view_summaries(smc_handle h);
 int enqueue_step_summaries(smc_handle h, int64_t row);
+// ... and the weighted summaries of another cloud [rows][ntheta][npad] under the handle's current weights (forecasts)
+size_t cloud_summary_words(const smc_filter_s* h, int rows);
+int enqueue_cloud_summaries(smc_handle h, const double* cloud, int rows, uint64_t* scratch, int scratch_rows, int component, const double* p, int np,
+                            bool mom, double* q_out, double* mean, double* var);
 // smc_capi_slots.hip: the dense weights of the current state into w [ntheta][n], on the handle's stream (k_dense_weights)
 hipError_t enqueue_dense_weights(smc_filter_s* h, double* w);
 // smc_capi_smooth.hip: appends the state smc_init / smc_step leave to the record of an armed handle (no host synchronisation);

@@ -83,6 +83,9 @@ template <int MODEL> hipError_t launch_window(const FilterView& v, int T, StepRe
 // proposals (LG1D, UCSV3D) in translation units of their own (smc_model.hip with -DSMC_GUIDED=1)
 template <int MODEL> hipError_t launch_step_g(const FilterView& v, Geo g, const StepHot& hot, hipStream_t s);
 template <int MODEL> hipError_t launch_resident_g(const FilterView& v, int T, StepRec* recs, hipStream_t s);
+// forecasts (smc_forecast_kernels.h): nk horizons k0 .. k0 + nk - 1 of every particle from the state rows src [d][ntheta][npad] into
+// out [nk][d + 3][ntheta][npad]; hipErrorInvalidValue when g is not the geometry of the view's segment length
+template <int MODEL> hipError_t launch_forecast(const FilterView& v, Geo g, const double* src, uint64_t fseed, uint32_t k0, int nk, double* out, hipStream_t s);
 template <int MODEL> hipError_t launch_window_g(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
 
 }  // namespace smc

@@ -1,6 +1,7 @@
 // smc_model.hip -- instantiates the kernels of ONE model family (-DSMC_MODEL=1|2|3|4) for every
 // workgroup geometry.  One object per family, built in parallel and linked into libsmchip.so.
 #include "smc_launch.h"
+#include "smc_forecast_kernels.h"
 #include <cstdlib>
 
 #ifndef SMC_MODEL
@@ -73,6 +74,16 @@ static hipError_t step_t(const FilterView& v, const StepHot& hot, hipStream_t s)
 template <>
 hipError_t launch_init<SMC_MODEL>(const FilterView& v, Geo g, int nxt, double y, hipStream_t s) {
     SMC_GEO_SWITCH(init_t, v, nxt, y, s)
+}
+template <int THREADS, int NP>
+static hipError_t forecast_t(const FilterView& v, const double* src, uint64_t fseed, uint32_t k0, int nk, double* out, hipStream_t s) {
+    hipLaunchKernelGGL((k_forecast<SMC_MODEL, THREADS, NP>), dim3(v.nseg, v.ntheta), dim3(THREADS), 0, s, v, src, fseed, k0, nk, out);
+    return hipGetLastError();
+}
+template <>
+hipError_t launch_forecast<SMC_MODEL>(const FilterView& v, Geo g, const double* src, uint64_t fseed, uint32_t k0, int nk, double* out, hipStream_t s) {
+    if (2 * g.np * g.threads != v.seg || nk < 1) return hipErrorInvalidValue;   // (a workgroup covers exactly one segment)
+    SMC_GEO_SWITCH(forecast_t, v, src, fseed, k0, nk, out, s)
 }
 #define SMC_LAUNCH_STEP launch_step
 #define SMC_LAUNCH_RESIDENT launch_resident

@@ -671,6 +671,47 @@ SMC_HD double model_marginal_step(const Params& p, bool first, const double* sp,
     return fma(-0.5 * (e * iS), e, fma(-0.5, sp_log(S), -HALF_LOG2PI));
 }
 
+// ---- forecasts: the cloud propagated past the last observation -----------------------------------------------------------------
+// p(x_{T+k} | y_1:T) and p(y_{T+k} | y_1:T), k = 1..H, from the filtered cloud (x_T, w_T).  Without an observation there is
+// nothing to weigh: no resampling, no normalisation - every particle is a chain of its own that moves by the TRANSITION law
+// (a guided handle too: a proposal has no role without y) and keeps the weight it has.  One forecast step of one particle:
+//   bootstrap families   x_k = model_transition(x_{k-1}, z);  (ym, sd) = model_obs_moments(x_k);  yv = sd sd;  yf = fma(sd, e, ym)
+//   MODEL_UCSV_RB        model_marginal_step with the measurement update left out.  With (m, a, b, P) = x_{k-1}:
+//                        P- = P + sp_exp(a);  lse = fma(g_eps, z[0], a);  lsn = fma(g_eta, z[1], b);  x_k = (m, lse, lsn, P-);
+//                        ym = m;  yv = P- + sp_exp(lsn);  yf = fma(sqrt(yv), e, ym)
+// (ym, yv): mean and variance of y_{T+k} given the particle (Rao-Blackwellised over the observation noise); yf: one draw of it.
+// Normals: particle i of filter m at horizon k (1-based) takes element i & 1 of
+//     box_muller(draw(forecast_seed, i >> 1, stream[m], k, SLOT_NORMAL0 + c))      for the state normal c < model_nz
+// and the same element of slot SLOT_OBS for e - the pair convention of the filter's own steps, under a seed of the caller's.  So
+// trajectory i is a function of (parameter row, x_T[i], forecast_seed, stream, i) alone: not of H, of the launch geometry or of
+// how the horizons are blocked.
+template <int MODEL>
+SMC_HD void model_marginal_predict(const Params& p, const double* sp, const double* z, double* s, double& ym, double& yv) {
+    static_assert(MODEL == MODEL_UCSV_RB, "marginal families");
+    const double m = sp[0], a = sp[1], b = sp[2];
+    const double Pm = sp[3] + sp_exp(a);
+    s[0] = m;
+    s[1] = fma(p.raw[0], z[0], a);
+    s[2] = fma(p.raw[1], z[1], b);
+    s[3] = Pm;
+    ym = m;
+    yv = Pm + sp_exp(s[2]);
+}
+// x (not aliasing xp) = the state one horizon on; (yf, ym, yv) its observation rows
+template <int MODEL>
+SMC_HD void model_forecast_step(const Params& p, const double* xp, const double* z, double e, double* x, double& yf, double& ym, double& yv) {
+    if constexpr (model_marginal<MODEL>::value) {
+        model_marginal_predict<MODEL>(p, xp, z, x, ym, yv);
+        yf = fma(sqrt(yv), e, ym);
+    } else {
+        double sd;
+        model_transition<MODEL>(p, xp, z, x);
+        model_obs_moments<MODEL>(p, x, ym, sd);
+        yv = sd * sd;
+        yf = fma(sd, e, ym);
+    }
+}
+
 // ---- PMMH rejuvenation of the samplers (src/smc_samplers.jl:103-146), one parameter particle ------------------
 // Random numbers are counter based like everything else: key = the move's seed, stream = GLOBAL index of the
 // parameter particle (so results do not depend on how theta is sharded), t = chain position.

@@ -223,6 +223,50 @@ extern "C" int smc_simulate(int model_id, const double* raw, int64_t T, uint64_t
     return SMC_OK;
 }
 
+// the forecast specification on the host (smc_spec.h "forecasts"): the twin of k_forecast, particle pairs sharing their Box-Muller pairs
+template <int MODEL>
+static void host_forecast_t(const Params& p, const double* x, int64_t n, int64_t H, uint64_t seed, uint32_t stream, double* xf, double* yf,
+                            double* ym, double* yv) {
+    constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
+    for (int64_t i0 = 0; i0 < n; i0 += 2) {
+        const int np = i0 + 1 < n ? 2 : 1;
+        double xs[2][D] = {};
+        for (int q = 0; q < np; ++q)
+            for (int c = 0; c < D; ++c) xs[q][c] = x[(size_t)c * n + i0 + q];
+        for (int64_t k = 1; k <= H; ++k) {
+            double z[NZ][2], e[2];
+            for (int c = 0; c < NZ; ++c) box_muller(draw(seed, (uint32_t)(i0 >> 1), stream, (uint32_t)k, SLOT_NORMAL0 + c), z[c][0], z[c][1]);
+            box_muller(draw(seed, (uint32_t)(i0 >> 1), stream, (uint32_t)k, SLOT_OBS), e[0], e[1]);
+            for (int q = 0; q < np; ++q) {
+                double zz[NZ], xn[D], f, m, v;
+                for (int c = 0; c < NZ; ++c) zz[c] = z[c][q];
+                model_forecast_step<MODEL>(p, xs[q], zz, e[q], xn, f, m, v);
+                const size_t at = (size_t)(k - 1) * n + i0 + q;
+                for (int c = 0; c < D; ++c) {
+                    xs[q][c] = xn[c];
+                    if (xf) xf[((size_t)(k - 1) * D + c) * n + i0 + q] = xn[c];
+                }
+                if (yf) yf[at] = f;
+                if (ym) ym[at] = m;
+                if (yv) yv[at] = v;
+            }
+        }
+    }
+}
+extern "C" int smc_host_forecast(int model_id, const double* raw, const double* x, int64_t n, int64_t H, uint64_t forecast_seed, uint32_t stream,
+                                 double* xf, double* yf, double* ym, double* yv) {
+    const int nraw = model_nraw_rt(model_id);
+    if (nraw < 0 || !raw || !x || n < 1 || n > ((int64_t)1 << 31) || H < 1 || H > 0x7fffffff) return fail(SMC_EINVAL, "smc_host_forecast: bad argument");
+    Params p;
+    for (int k = 0; k < NPARAM; ++k) p.raw[k] = k < nraw ? raw[k] : 0.0;
+    derive_params(model_id, p.raw, p.der);
+    (void)by_model(model_id, [&](auto M) {
+        host_forecast_t<decltype(M)::value>(p, x, n, H, forecast_seed, stream, xf, yf, ym, yv);
+        return hipSuccess;
+    });
+    return SMC_OK;
+}
+
 extern "C" double smc_host_exp(double x) { return sp_exp(x); }
 extern "C" double smc_host_log(double x) { return sp_log(x); }
 extern "C" void smc_host_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {

@@ -6,6 +6,7 @@
     bootstrap_filter_(x, w, y, model)    -> (logmu, w, ess)     particles.jl:107-129   ("bootstrap_filter!")
     log_likelihood(N, y, model)          -> (x, w, logZ)        particles.jl:132-147
     smoother(N, y, model)                -> (x, w, logZ, s)     (no counterpart: the FFBS particle smoother)
+    forecast(x, w, H)                    -> dict                (no counterpart: the cloud propagated H steps ahead)
     particle_filter(N, y1, model, proposal)       -> (x, w, logmu)     particles.jl:28-52
     particle_filter_(x, w, y, model, proposal)    -> (logmu, w, ess)   particles.jl:54-84    ("particle_filter!")
 
@@ -108,6 +109,7 @@ class _Filters:
         if streams is not None:
             self.h.set_streams(streams)
         self.model_id, self.raw = mid, raw
+        self.seed = int(seed)
         self.proposal = None
         self.set_proposal(proposal)
 
@@ -313,6 +315,58 @@ def log_likelihood(N, y, model, seed=None, seg=0, device=0, streams=None, ancest
 def _path_seed(seed):
     """the default path seed of a filter seed: another 64-bit word, so that the walk's draws are not the filter's"""
     return (int(seed) * 0x9E3779B97F4A7C15 + 0xBAC4) & 0xFFFFFFFFFFFFFFFF
+
+
+def _forecast_seed(seed):
+    """the default forecast seed of a filter seed: another 64-bit word again, so that the forecast draws are neither the filter's
+    nor the backward walk's"""
+    return (int(seed) * 0xD1342543DE82EF95 + 0xF0CA) & 0xFFFFFFFFFFFFFFFF
+
+
+def _state_last(a, single):
+    """[H][d][n_theta] -> [H][n_theta][d], the state axis dropped for a scalar state and the batch axis for a single model"""
+    a = np.moveaxis(a, 1, -1)
+    if a.shape[-1] == 1:
+        a = a[..., 0]
+    return a[:, 0] if single else a
+
+
+def forecast(x, w, H, quantiles=None, component=0, seed=None, clouds=False):
+    """f = forecast(x, w, H): the forecast fan of the filter behind the Particles / Weights of any filter call (one model or a list,
+    any family, any proposal, either resampler) - p(x_{T+k} | y_1:T) and p(y_{T+k} | y_1:T), k = 1..H, by propagating the
+    weighted cloud on the device (smc_forecast, DESIGN.md 2i): every particle moves by the transition law and keeps its weight;
+    nothing is resampled, and the filter is left exactly as it was.  f[...][k] belongs to horizon k + 1:
+        f["mean"], f["var"]           weighted mean and variance of the state, [H] (scalar state) or [H][d]
+        f["quantiles"]                (quantiles=[...], at most 8 levels) weighted quantiles of state coordinate `component`, [H][len(p)]
+        f["obs_mean"], f["obs_var"]   mean and variance of the predictive law of y, [H]: sum w E[y | particle], and the variance of
+                                      the mixture - within (sum w Var[y | particle]) plus between
+        f["obs_quantiles"]            weighted quantiles of one predictive draw of y per particle, [H][len(p)]
+        f["x"], f["y"]                (clouds=True) the propagated clouds [H][N] or [H][N][d] and the predictive draws [H][N]:
+                                      with np.asarray(w) they are weighted trajectories (particle i is ONE path over the horizons)
+    With a list of models a batch axis follows H everywhere.  seed: the Philox seed of the forecast draws (default: derived from
+    the filter's seed); trajectory i depends on it, on the particle and on its filter's stream alone, not on H.
+    MarginalUCSV: the state rows are (m, lse, lsn, P), and trend_moments(f["mean"][k], f["var"][k]) is the forecast trend: the
+    mean of row 0, and the variance of row 0 plus the mean of row 3."""
+    f = x._f
+    if w._f is not f:
+        raise ValueError("states and weights belong to different filters")
+    H = int(H)
+    if H < 1:
+        raise ValueError("forecast needs H >= 1")
+    seed = _forecast_seed(f.seed) if seed is None else int(seed)
+    r = f.h.forecast(H, seed, p=quantiles, component=component, obs=True)
+    out = {"mean": _state_last(r["mean"], f.single), "var": _state_last(r["var"], f.single)}
+    pick = (lambda a: a[:, 0]) if f.single else (lambda a: a)
+    out["obs_mean"], out["obs_var"] = pick(r["obs_mean"]), pick(r["obs_var"])
+    if "q" in r:
+        out["quantiles"], out["obs_quantiles"] = pick(r["q"]), pick(r["obs_q"])
+    if clouds:
+        xf, yf = f.h.forecast_cloud(H, seed)
+        xf = np.moveaxis(xf, 1, -1)                                    # [H][n_theta][N][d]
+        if xf.shape[-1] == 1:
+            xf = xf[..., 0]
+        out["x"], out["y"] = pick(xf), pick(yf)
+    return out
 
 
 def _paths_out(idx, xs, single):

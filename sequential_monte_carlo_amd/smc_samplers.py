@@ -605,6 +605,56 @@ def smoothed_state(smc, y, N=None, max_bytes=2 ** 31, seed=None):
 _U64 = 0xFFFFFFFFFFFFFFFF
 
 
+def forecast_state(smc, H, quantiles=None, component=0, seed=None):
+    """The forecast fan of an SMC sampler after smc2 / smc2_run, integrated over its parameter cloud: every online filter
+    (smc._main) propagates its cloud H steps ahead on the device (particles.forecast) and the per-filter forecasts
+    are combined with the normalised omega exactly as smoothed_state / filtered_summaries combine theirs.  A dict, [k] = horizon k + 1:
+        "mean", "var"                [H] or [H][d]: mean = sum_m omega_m mean_m, var = within (sum_m omega_m var_m) + between
+                                     (sum_m omega_m (mean_m - mean)^2)
+        "obs_mean", "obs_var"        [H]: the predictive law of y, combined the same way
+        "quantiles", "obs_quantiles" (quantiles=[...]) [H][len(p)]: the omega-weighted means of the per-filter weighted quantiles of
+                                     state coordinate `component` / of the predictive draws (the statistic of filtered_summaries)
+    The deviation stated at filtered_summaries holds here too: omega is the normalised one (the example multiplies by the raw
+    smc.ω).  Filters of omega = 0 do not enter (a collapsed filter has NaN rows).  Filter m draws with Philox stream m, so the
+    result does not depend on how theta is sharded; seed: the Philox seed of the forecast draws (default: derived from the
+    sampler's seed).  The sampler and its filters are left as they were.
+    An IBIS sampler has the exact one-step prediction instead: ahead=1 of observation_dist / quantile / smc2_run; a multi-step
+    IBIS forecast is not offered."""
+    if isinstance(smc, IBIS):
+        raise TypeError("forecast_state is defined for an SMC sampler; IBIS has the exact one-step Kalman prediction: ahead=1 "
+                        "(observation_dist, quantile, smc2_run)")
+    if smc._main is None:
+        raise ValueError("forecast_state needs the online sampler's filters (call smc2 first)")
+    if not hasattr(smc._main, "forecast"):
+        raise NotImplementedError("forecast_state needs the device's forecast (smc_forecast)")
+    H = int(H)
+    seed = (((smc.seed << 20) | 0xF0CA5) if seed is None else int(seed)) & _U64
+    p = [] if quantiles is None else list(quantiles)
+    r = smc._main.forecast(H, seed, p=p or None, component=component, obs=True)
+    d, per, nq = r["mean"].shape[1], r["mean"].shape[2], len(p)
+    # per filter: mean [H][d] | var [H][d] | obs_mean [H] | obs_var [H] | q [H][nq] | obs_q [H][nq]
+    cols = [np.moveaxis(r["mean"], 2, 0).reshape(per, H * d), np.moveaxis(r["var"], 2, 0).reshape(per, H * d), r["obs_mean"].T, r["obs_var"].T]
+    if nq:
+        cols += [np.moveaxis(r["q"], 1, 0).reshape(per, H * nq), np.moveaxis(r["obs_q"], 1, 0).reshape(per, H * nq)]
+    rows = _per_theta(smc, np.column_stack(cols))                       # [M][...]
+    om = np.asarray(smc.omega, dtype=np.float64)
+    head, last = _integrate(om, rows)
+    tot = np.append(head, last)
+    o = np.cumsum([0, H * d, H * d, H, H, H * nq, H * nq])
+    mean, within = tot[o[0]:o[1]], tot[o[1]:o[2]]
+    omean, owithin = tot[o[2]:o[3]], tot[o[3]:o[4]]
+    keep = om > 0
+    dev = rows[keep][:, o[0]:o[1]] - mean
+    odev = rows[keep][:, o[2]:o[3]] - omean
+    between = np.add.reduce(om[keep, None] * (dev * dev), axis=0)
+    obetween = np.add.reduce(om[keep, None] * (odev * odev), axis=0)
+    shape = (H,) if d == 1 else (H, d)
+    out = {"mean": mean.reshape(shape), "var": (within + between).reshape(shape), "obs_mean": omean, "obs_var": owithin + obetween}
+    if nq:
+        out["quantiles"], out["obs_quantiles"] = tot[o[4]:o[5]].reshape(H, nq), tot[o[5]:o[6]].reshape(H, nq)
+    return out
+
+
 def _path_counts(smc, M, seed):
     """(counts [smc.M] int32, the parameter particles with a positive count): the parameter particle of each of M paths drawn from
     omega through the library's own outer resampler (M ancestors in ascending order)"""
