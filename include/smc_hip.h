@@ -43,6 +43,8 @@ extern "C" {
                                 * resample (particles.jl:17-19 draws iid): one uniform per step, child j takes
                                 * the point (j + u)/N of the weight CDF.  Same expectation N w_i of every
                                 * particle's children, lower variance, a different law - never the default. */
+#define SMC_FLAG_NAN_MISSING 8u /* OPT-IN: a NaN observation is a MISSING one ("missing observations" below): its step moves
+                                 * the cloud by the transition and weighs nothing.  Without the flag a NaN kills its step. */
 
 typedef struct smc_filter_s* smc_handle;
 
@@ -71,8 +73,9 @@ int smc_destroy(smc_handle h);
  *     filters (LG1D AFFINE - also with c2 = 0, since 0 * y is NaN - LG1D OPTIMAL, UCSV OPTIMAL) and SMC_MODEL_UCSV_RB carry y
  *     into the state (the proposal mean; the Kalman mean m): dead from that step on.  The first step of a guided filter is the
  *     bootstrap first step, so a bad y_1 costs a guided filter that step alone; SMC_MODEL_UCSV_RB is dead from it on.
- *     There are no missing-data semantics: a gap in the series must be left out by the caller, not passed as NaN.  (Looking past
- *     the END of the series is smc_forecast, "forecasts" below: it propagates the cloud without observations.)
+ *     This holds on a handle WITHOUT SMC_FLAG_NAN_MISSING and is not a missing-data rule; with the flag a NaN is a gap
+ *     ("missing observations" below; +-inf still kill the step).  (Looking past the END of the series is smc_forecast,
+ *     "forecasts" below: it propagates the cloud without observations.)
  *   - a row outside its family's domain makes its filter dead: LG1D R <= 0 or a NaN B, SV1D |rho| >= 1 or a NaN sigma, UCSV a NaN
  *     x0, lse0 = +inf (and for the bootstrap filter lsn0 = -inf) from the first step; LG1D Q < 0, Q = +inf or a NaN A from the
  *     second (the first step does not move the particles).  LG1D sigma0 = 0 is valid (x_1 = x0).  A NEGATIVE UCSV gamma is a live
@@ -163,7 +166,36 @@ int smc_host_rb_steps(const double* raw, const double* sp, const double* z, doub
 int smc_device_rb_step(const double* raw, const double* sp, const double* z, double y, int first, int64_t n, double* s,
                        double* logw, int device);
 
+/* ---- missing observations -------------------------------------------------------------------------
+ * A handle created with SMC_FLAG_NAN_MISSING reads a NaN observation - in smc_init, smc_step, smc_step_window / smc_step_commit,
+ * smc_log_likelihood and smc_pmmh_rejuvenate - as a period WITHOUT an observation.  The missing step is the ordinary step with
+ * the observation's part left out: the same resampling from the current weights (either resampler, the same random numbers), the
+ * same state normals, the time index advances by one; every particle moves by the TRANSITION (the initial distribution at the
+ * first step; a guided handle too: a proposal has no role without y) and takes the log-weight +0.0, so logmu = +0.0, ess = n_x
+ * and w = 1 / n_x exactly and the step adds nothing to logZ.  SMC_MODEL_UCSV_RB: the volatilities move as ever, row 0 (the mean
+ * of the trend) stays, row 3 becomes P- = P + exp(lse_prev): after a gap rows 0 and 3 are the PREDICTIVE moments.  A filter that
+ * is collapsed when it meets a gap leaves it with uniform weights; its logZ stays -inf (a running sum).  This is not the same
+ * model as leaving the period out, which applies the transition once where the model applies it twice.  +-inf observations
+ * still kill their step.  A flagged handle launches the same kernels as an unflagged one at every observed step, and for a
+ * whole series or window without a NaN.  Per-step summaries, smc_forecast, the record of a step-by-step run, smc_smooth and
+ * smc_sample_paths read clouds and weights and need no rule of their own (the smoothed state at a gap is the interpolation).
+ * NOT covered: smc_rb_sample_paths (its Kalman / RTS pass along each path reads y: SMC_EINVAL on a flagged handle when y holds a
+ * NaN), smc_time_step_kernel (the same refusal), and the exact-Kalman entry points - smc_ibis_*, smc_kalman_log_likelihood,
+ * smc_kalman_smooth - which have no flag and keep their behaviour. */
+/* the flags the handle was created with */
+int smc_get_flags(smc_handle h, uint32_t* flags);
+/* The whole step of n particles on the host, for every family and proposal: xp x [d][n], z [nz][n] (nz = d; 2 for
+ * SMC_MODEL_UCSV_RB), logw [n].  kind / par as smc_host_guided_steps (SMC_PROP_NONE: the bootstrap step; SMC_MODEL_UCSV_RB takes
+ * SMC_PROP_NONE only).  first != 0: the first step (xp is not read; a guided filter's first step is the bootstrap one).  With
+ * nan_missing != 0 and a NaN y: the missing step (logw = +0.0). */
+int smc_host_filter_steps(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z,
+                          double y, int first, int nan_missing, int64_t n, double* x, double* logw);
+/* the same on the device in one launch (parity tests; the twin of smc_device_guided_step) */
+int smc_device_filter_steps(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z,
+                            double y, int first, int nan_missing, int64_t n, double* x, double* logw, int device);
+
 /* ---- the hot path ----------------------------------------------------------------------------*/
+/* (all of these: a NaN observation on a handle with SMC_FLAG_NAN_MISSING is a missing step, "missing observations" above) */
 /* bootstrap_filter(N, y, model) -> (x, w, logmu)            src/particles.jl:87-105 */
 int smc_init(smc_handle h, double y1, double* logmu /*[n_theta]*/);
 /* bootstrap_filter!(x, w, y, model) -> (logmu, w, ess)      src/particles.jl:107-129 */

@@ -31,7 +31,9 @@ mutable struct HipFilter
     h::Ptr{Cvoid}; N::Int; M::Int; d::Int; id::Cint
     xcache::Union{Nothing,Array{Float64}}      # host copy of the cloud, valid until the filters move again
     wcache::Union{Nothing,Array{Float64}}
-    function HipFilter(id::Cint, M::Int, N::Int; seed::UInt64=rand(UInt64), device::Int=0, flags::UInt32=UInt32(0))
+    # missing=true: SMC_FLAG_NAN_MISSING (8) - a NaN observation is a period without one (include/smc_hip.h "missing observations")
+    function HipFilter(id::Cint, M::Int, N::Int; seed::UInt64=rand(UInt64), device::Int=0, flags::UInt32=UInt32(0), missing::Bool=false)
+        flags |= missing ? UInt32(8) : UInt32(0)
         out = Ref{Ptr{Cvoid}}(C_NULL)
         smc_check(ccall((:smc_create, LIBSMC), Cint,
             (Cint, Int64, Int64, Cint, UInt64, Cint, UInt32, Ref{Ptr{Cvoid}}),
@@ -129,8 +131,8 @@ end
 
 # ---- particles.jl --------------------------------------------------------------------------------------------------
 # bootstrap_filter(N, y, model) -> (x, w, logμ)                      particles.jl:87-105
-function bootstrap_filter(N::Int64, y::Float64, model::HipModels)
-    f = set_models!(HipFilter(hip_model(model)[1], 1, N), [model])
+function bootstrap_filter(N::Int64, y::Float64, model::HipModels; missing::Bool=false)
+    f = set_models!(HipFilter(hip_model(model)[1], 1, N; missing=missing), [model])
     logμ = Ref{Float64}()
     smc_check(ccall((:smc_init, LIBSMC), Cint, (Ptr{Cvoid}, Float64, Ptr{Float64}), f.h, y, logμ))
     return HipParticles(f, 1), HipWeights(f, 1), logμ[]
@@ -170,8 +172,8 @@ function optimal_proposal(model::HipModels)
 end
 # particle_filter(N, y, model, proposal) -> (x, w, logμ): the first step is bootstrap_filter's (the reference adds
 # logpdf(initial_dist, x) there, particles.jl:41-44, a slip - see include/smc_hip.h)
-function particle_filter(N::Int64, y::Float64, model::HipModels, proposal::HipProposals)
-    f = set_proposal!(set_models!(HipFilter(hip_model(model)[1], 1, N), [model]), proposal)
+function particle_filter(N::Int64, y::Float64, model::HipModels, proposal::HipProposals; missing::Bool=false)
+    f = set_proposal!(set_models!(HipFilter(hip_model(model)[1], 1, N; missing=missing), [model]), proposal)
     logμ = Ref{Float64}()
     smc_check(ccall((:smc_init, LIBSMC), Cint, (Ptr{Cvoid}, Float64, Ptr{Float64}), f.h, y, logμ))
     return HipParticles(f, 1), HipWeights(f, 1), logμ[]
@@ -184,8 +186,8 @@ function particle_filter!(states::HipParticles, weights::HipWeights, y::Float64,
     return logμ[], HipWeights(f, states.m), ess[]
 end
 # log_likelihood(N, y, model, proposal) -> (x, w, logZ)
-function log_likelihood(N::Int64, y::Vector{Float64}, model::HipModels, proposal::Union{AffineGaussianProposal,OptimalProposal})
-    f = set_proposal!(set_models!(HipFilter(hip_model(model)[1], 1, N), [model]), proposal)
+function log_likelihood(N::Int64, y::Vector{Float64}, model::HipModels, proposal::Union{AffineGaussianProposal,OptimalProposal}; missing::Bool=false)
+    f = set_proposal!(set_models!(HipFilter(hip_model(model)[1], 1, N; missing=missing), [model]), proposal)
     logZ = Ref{Float64}()
     GC.@preserve y smc_check(ccall((:smc_log_likelihood, LIBSMC), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
@@ -194,8 +196,8 @@ function log_likelihood(N::Int64, y::Vector{Float64}, model::HipModels, proposal
 end
 
 # log_likelihood(N, y, model) -> (x, w, logZ)                         particles.jl:132-147
-function log_likelihood(N::Int64, y::Vector{Float64}, model::HipModels)
-    f = set_models!(HipFilter(hip_model(model)[1], 1, N), [model])
+function log_likelihood(N::Int64, y::Vector{Float64}, model::HipModels; missing::Bool=false)
+    f = set_models!(HipFilter(hip_model(model)[1], 1, N; missing=missing), [model])
     logZ = Ref{Float64}()
     GC.@preserve y smc_check(ccall((:smc_log_likelihood, LIBSMC), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
@@ -206,8 +208,8 @@ end
 # the README loop (README.md:33-61: bootstrap_filter!, then quantile(x, ...) at every observation) as ONE call: the weighted
 # quantiles of state coordinate `component` (0-based) at the levels p and / or mean and variance of every coordinate after
 # every step, recorded on the device inside the filter loop -> (x, w, logZ, q [np x T], mean [d x T], var [d x T])
-function log_likelihood(N::Int64, y::Vector{Float64}, model::HipModels, p::Vector{Float64}; component::Int=0, moments::Bool=true)
-    f = set_models!(HipFilter(hip_model(model)[1], 1, N), [model])
+function log_likelihood(N::Int64, y::Vector{Float64}, model::HipModels, p::Vector{Float64}; component::Int=0, moments::Bool=true, missing::Bool=false)
+    f = set_models!(HipFilter(hip_model(model)[1], 1, N; missing=missing), [model])
     T = length(y); logZ = Ref{Float64}()
     GC.@preserve p smc_check(ccall((:smc_set_summaries, LIBSMC), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Cint),
                                     f.h, component, p, length(p), moments ? 1 : 0))

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMC_LIB") or os.path.join(_HERE, "lib", "libsmchip.so")   # SMC_LIB: profiling builds
 
 MODEL_LG1D, MODEL_SV1D, MODEL_UCSV3D, MODEL_UCSV_RB = 1, 2, 3, 4
-FLAG_ANCESTORS, FLAG_NO_RESIDENT, FLAG_SYSTEMATIC = 1, 2, 4
+FLAG_ANCESTORS, FLAG_NO_RESIDENT, FLAG_SYSTEMATIC, FLAG_NAN_MISSING = 1, 2, 4, 8
 
 # every symbol include/smc_hip.h declares
 EXPORTS = [
@@ -39,6 +39,7 @@ EXPORTS = [
     "smc_history_begin", "smc_history_len", "smc_history_get", "smc_history_put", "smc_history_end", "smc_smooth", "smc_host_transition_logpdf",
     "smc_host_smooth", "smc_sample_paths", "smc_host_sample_paths", "smc_rb_sample_paths", "smc_host_rb_sample_paths",
     "smc_forecast", "smc_forecast_cloud", "smc_host_forecast",
+    "smc_get_flags", "smc_host_filter_steps", "smc_device_filter_steps",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -129,6 +130,9 @@ def lib():
     L.smc_host_rb_step.argtypes = [_dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp]
     L.smc_device_rb_step.argtypes = [_dp, _dp, _dp, C.c_double, C.c_int, C.c_int64, _dp, _dp, C.c_int]
     L.smc_host_guided_steps.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int64, _dp, _dp]
+    L.smc_get_flags.argtypes = [h, _u32p]
+    L.smc_host_filter_steps.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int64, _dp, _dp]
+    L.smc_device_filter_steps.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int64, _dp, _dp, C.c_int]
     L.smc_host_rb_steps.argtypes = [_dp, _dp, _dp, C.c_double, C.c_int, C.c_int64, _dp, _dp]
     L.smc_get_summaries.argtypes = [h, C.c_int64, _dp, _dp, _dp]
     L.smc_sys_targets.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.c_int]
@@ -350,6 +354,35 @@ def device_guided_step(model_id, raw, kind, par, xp, z, y, device=0):
     lw = np.zeros(n)
     check(lib().smc_device_guided_step(int(model_id), _d(raw), int(kind), _d(par), _d(xp), _d(z), float(y), n, _d(x), _d(lw), device))
     return x, lw
+
+
+def _filter_steps(fn, model_id, raw, kind, par, xp, z, y, first, missing, *tail):
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    par = _row_or_none(par)
+    d = lib().smc_model_dim(int(model_id))
+    if d < 1:
+        raise SmcError("unknown model id %d" % int(model_id))
+    nz = 2 if int(model_id) == MODEL_UCSV_RB else d
+    z = np.ascontiguousarray(z, dtype=np.float64).reshape(nz, -1)
+    n = z.shape[1]
+    xp = np.zeros((d, n)) if xp is None else np.ascontiguousarray(xp, dtype=np.float64).reshape(d, -1)
+    assert xp.shape[1] == n
+    x = np.zeros((d, n))
+    lw = np.zeros(n)
+    check(fn(int(model_id), _d(raw), int(kind), _d(par), _d(xp), _d(z), float(y), int(bool(first)), int(bool(missing)), n, _d(x), _d(lw), *tail))
+    return x, lw
+
+
+def host_filter_steps(model_id, raw, kind, par, xp, z, y, first=False, missing=False):
+    """the whole step of n particles by the specification on the host, every family and proposal: xp [d][n] (None at the first
+    step), z [nz][n] -> (x [d][n], logw [n]); kind = PROP_NONE: the bootstrap (or marginal) step.  missing=True and a NaN y: the
+    missing step, logw = +0.0 (smc_host_filter_steps; no GPU)"""
+    return _filter_steps(lib().smc_host_filter_steps, model_id, raw, kind, par, xp, z, y, first, missing)
+
+
+def device_filter_steps(model_id, raw, kind, par, xp, z, y, first=False, missing=False, device=0):
+    """the same on the device in one launch (smc_device_filter_steps)"""
+    return _filter_steps(lib().smc_device_filter_steps, model_id, raw, kind, par, xp, z, y, first, missing, device)
 
 
 def host_rb_step(raw, sp, z, y, first=False):
@@ -578,6 +611,13 @@ class Handle:
         check(lib().smc_get_geometry(self._h, C.byref(seg_), C.byref(nseg), C.byref(d), C.byref(res)))
         self.seg, self.nseg, self.d, self.resident = seg_.value, nseg.value, d.value, bool(res.value)
         self.flags = flags
+
+    @property
+    def missing(self):
+        """the handle reads a NaN observation as a missing one (FLAG_NAN_MISSING, read back from the library)"""
+        f = C.c_uint32()
+        check(lib().smc_get_flags(self._h, C.byref(f)))
+        return bool(f.value & FLAG_NAN_MISSING)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -92,7 +92,10 @@ extern "C" int smc_device_count(void) {
 }
 
 // ---- kernel dispatch -------------------------------------------------------------------------
+// (a flagged handle whose observation is NaN: the missing step, smc_spec.h "missing observations" - the MISS kernels)
 hipError_t do_init(smc_filter_s* h, double y) {
+    if (nan_missing(h) && y != y)
+        return by_model(h->model, [&](auto M) { return launch_init_m<decltype(M)::value>(h->v, h->geo, h->cur, y, h->stream); });
     return by_model(h->model, [&](auto M) { return launch_init<decltype(M)::value>(h->v, h->geo, h->cur, y, h->stream); });
 }
 // filters with more segments than threads per workgroup (v.tabD): the segment table of the current weights, built once (k_table;
@@ -136,6 +139,10 @@ hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y, const d
         emit_prev = 0;
     }
     const StepHot hot = step_hot(h, t, emit_prev, y, y_host);
+    // the step API's observation, or the series' (gap_y: set only when a flagged handle's series holds a NaN)
+    const bool gap = h->v.y ? (h->gap_y && h->gap_y[t] != h->gap_y[t]) : (nan_missing(h) && y != y);
+    if (gap)   // uniform over the launch: the missing step's own kernel, for a handle with a proposal too
+        return by_model(h->model, [&](auto M) { return launch_step_m<decltype(M)::value>(h->v, h->geo, hot, h->stream); });
     if (h->v.prop_kind)   // a handle with a proposal: the guided kernels (the families smc_set_proposal accepts)
         return by_guided_model(h->model, [&](auto M) { return launch_step_g<decltype(M)::value>(h->v, h->geo, hot, h->stream); });
     return by_model(h->model, [&](auto M) { return launch_step<decltype(M)::value>(h->v, h->geo, hot, h->stream); });
@@ -169,6 +176,15 @@ hipError_t ensure_breaks(smc_filter_s* h, uint32_t t, uint32_t t_end) {
     return hipGetLastError();
 }
 static hipError_t do_window(smc_filter_s* h, int k, int bout) {
+    if (h->win.gap) {   // a flagged handle's window with a NaN in it: the kernels that test every step's observation
+        if (h->v.prop_kind)
+            return by_guided_model(h->model, [&](auto M) {
+                return launch_window_gm<decltype(M)::value>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->win.h_out, h->stream);
+            });
+        return by_model(h->model, [&](auto M) {
+            return launch_window_m<decltype(M)::value>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->win.h_out, h->stream);
+        });
+    }
     if (h->v.prop_kind)
         return by_guided_model(h->model, [&](auto M) {
             return launch_window_g<decltype(M)::value>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->win.h_out, h->stream);
@@ -650,6 +666,7 @@ extern "C" int smc_step_window(smc_handle h, const double* y, int k, double* log
     HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)k * 8, hipMemcpyHostToDevice, h->stream));
     h->v.y = h->d_y;
     if (summ) view_summaries(h);
+    h->win.gap = series_has_gap(h, y, k);
     rc = launch_window_steps(h, k);
     h->v.y = nullptr;
     h->v.sum_np = h->v.sum_mom = 0; h->v.sum_q = h->v.sum_m = nullptr;
@@ -715,6 +732,12 @@ extern "C" int smc_get_logZ(smc_handle h, double* logZ, double* ess) {
     HIPCHK(hipStreamSynchronize(h->stream));
     if (logZ) HIPCHK(hipMemcpy(logZ, h->v.logZ, (size_t)h->v.ntheta * 8, hipMemcpyDeviceToHost));
     if (ess) HIPCHK(hipMemcpy(ess, h->v.last_ess, (size_t)h->v.ntheta * 8, hipMemcpyDeviceToHost));
+    return SMC_OK;
+}
+
+extern "C" int smc_get_flags(smc_handle h, uint32_t* flags) {
+    if (!h || !flags) return fail(SMC_EINVAL, "smc_get_flags: NULL argument");
+    *flags = h->flags;
     return SMC_OK;
 }
 

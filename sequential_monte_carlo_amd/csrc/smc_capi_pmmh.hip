@@ -103,6 +103,7 @@ extern "C" int smc_pmmh_rejuvenate(smc_handle h, smc_handle main, const double* 
     HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->pm.d_in, h->pm.h_in, h->pm.in_words * 8, hipMemcpyHostToDevice, h->stream));
     const dim3 grid((unsigned)((nt + 127) / 128)), block(128);
+    GapScope gaps(h, y, T);   // (a flagged handle: the proposal filters read a NaN as a gap, like smc_log_likelihood)
     for (int c = 0; c < chain; ++c) {
         hipLaunchKernelGGL(k_pmmh_propose, grid, block, 0, h->stream, h->v, sp, h->pm.dev, h->model, move_seed, (uint32_t)c,
                            sqrt(scales[c]), h->d_params);   // (derives the proposal rows of a guided handle too)

@@ -30,6 +30,11 @@ struct SeriesScope {
 };
 
 static hipError_t do_resident(smc_filter_s* h, int T) {
+    if (h->gap_y) {   // a flagged handle's series with a NaN in it (GapScope): the kernels that test every step's observation
+        if (h->v.prop_kind)
+            return by_guided_model(h->model, [&](auto M) { return launch_resident_gm<decltype(M)::value>(h->v, T, h->d_recs, h->stream); });
+        return by_model(h->model, [&](auto M) { return launch_resident_m<decltype(M)::value>(h->v, T, h->d_recs, h->stream); });
+    }
     if (h->v.prop_kind)
         return by_guided_model(h->model, [&](auto M) { return launch_resident_g<decltype(M)::value>(h->v, T, h->d_recs, h->stream); });
     return by_model(h->model, [&](auto M) { return launch_resident<decltype(M)::value>(h->v, T, h->d_recs, h->stream); });
@@ -107,7 +112,10 @@ extern "C" int smc_log_likelihood(smc_handle h, const double* y, int64_t T, doub
     if (h->skip.on) { h->v.skip = h->skip.d_mask; h->v.order = h->skip.d_order; h->v.n_active = h->skip.d_order + h->v.ntheta; }
     const int cur0 = h->cur;   // where the state of the filters the call leaves out stays
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    rc = enqueue_log_likelihood(h, y[0], T, want_trace, summ, y);
+    {
+        GapScope gaps(h, y, T);
+        rc = enqueue_log_likelihood(h, y[0], T, want_trace, summ, y);
+    }
     h->v.skip = nullptr; h->v.order = nullptr; h->v.n_active = nullptr;
     if (rc) return rc;
     // the call ends in the other buffer: the skipped filters' untouched state goes with it
@@ -139,6 +147,7 @@ extern "C" int smc_time_step_kernel(smc_handle h, const double* y, int64_t T, in
     if (!h || !y || T < 2 || nsample < 1) return fail(SMC_EINVAL, "smc_time_step_kernel: bad argument");
     if (!h->have_params) return fail(SMC_ESTATE, "smc_time_step_kernel: smc_set_params has not been called");
     if (history_armed(h)) return history_refuse("smc_time_step_kernel");
+    if (series_has_gap(h, y, T)) return fail(SMC_EINVAL, "smc_time_step_kernel: the series holds a NaN and the handle reads NaN as missing (SMC_FLAG_NAN_MISSING); it times the ordinary step");
     HIPCHK(hipSetDevice(h->device));
     int rc = ensure_y(h, T);
     if (rc) return rc;

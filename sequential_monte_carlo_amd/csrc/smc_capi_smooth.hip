@@ -385,6 +385,9 @@ extern "C" int smc_rb_sample_paths(smc_handle h, const double* y, int64_t T, int
     if (h->model != MODEL_UCSV_RB)
         return fail(SMC_EINVAL, "smc_rb_sample_paths: the handle is not SMC_MODEL_UCSV_RB (the other families have a transition density: smc_sample_paths)");
     if (!y) return fail(SMC_EINVAL, "smc_rb_sample_paths: NULL y");
+    if (T > 0 && series_has_gap(h, y, T))
+        return fail(SMC_EINVAL, "smc_rb_sample_paths: y holds a NaN and the handle reads NaN as missing (SMC_FLAG_NAN_MISSING): the Kalman / RTS pass "
+                                "along a path has no rule for a gap yet");
     // (the two gammas are UCSV3D's: nh1, nh2; a path carries (lse, lsn, mu, tau) and records (lse, lsn))
     Walk k{"smc_rb_sample_paths", "a gamma", MODEL_UCSV3D, 4, 8, y, T};
     const size_t nt = (size_t)h->v.ntheta;

@@ -80,6 +80,8 @@ struct smc_filter_s {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int cur = 0;
     uint32_t t = 0;        // index of the next observation
+    const double* gap_y = nullptr;   // SMC_FLAG_NAN_MISSING: the host's copy of the series a whole-series call is enqueueing, when it holds a
+                                     //    NaN (GapScope; indexed by t) - its launches take the MISS kernels; nullptr: today's kernels
     bool inited = false;   // weights exist
     bool emitted = false;  // logmu/ess of the current weights already produced
     bool have_params = false;
@@ -113,6 +115,7 @@ struct smc_filter_s {
     struct {   // smc_step_window / smc_step_commit
         double* h_out = nullptr;               // pinned [2][WIN_MAX][ntheta]: (logmu, ess) of the steps of a window
         int k = 0;                             // steps of the pending window, 0 = none
+        bool gap = false;                      // SMC_FLAG_NAN_MISSING: the pending window's observations hold a NaN (the MISS window kernel)
     } win;
     struct {   // the record of a step-by-step run and the smoother over it (smc_capi_smooth.hip); a fresh handle is disarmed
         bool armed = false;
@@ -158,6 +161,20 @@ hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y, const d
 inline void hot_invalidate(smc_filter_s* h) { h->hot.prm_ok = h->hot.stream_ok = false; }
 // a step launch of this handle may take row 0 by value: one filter, both host copies valid (the launch also wants no skip mask)
 inline bool hot_legal(const smc_filter_s* h) { return h->hot.allow && h->hot.prm_ok && h->hot.stream_ok && h->v.ntheta == 1; }
+// missing observations (include/smc_hip.h): the handle reads NaN as a gap; the series y[0..T) holds one
+inline bool nan_missing(const smc_filter_s* h) { return (h->flags & SMC_FLAG_NAN_MISSING) != 0; }
+inline bool series_has_gap(const smc_filter_s* h, const double* y, int64_t T) {
+    if (!nan_missing(h)) return false;
+    for (int64_t t = 0; t < T; ++t)
+        if (y[t] != y[t]) return true;
+    return false;
+}
+// names the series of a whole-series call for its launches (h->gap_y) when the handle is flagged and the series holds a NaN
+struct GapScope {
+    smc_filter_s* h;
+    GapScope(smc_filter_s* hh, const double* y, int64_t T) : h(hh) { h->gap_y = series_has_gap(h, y, T) ? y : nullptr; }
+    ~GapScope() { h->gap_y = nullptr; }
+};
 hipError_t do_finalize(smc_filter_s* h, int first_emit, uint32_t t_emit);
 hipError_t ensure_breaks(smc_filter_s* h, uint32_t t, uint32_t t_end);
 int ensure_y(smc_handle h, int64_t T);

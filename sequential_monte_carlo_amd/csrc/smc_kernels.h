@@ -808,7 +808,9 @@ __device__ __forceinline__ int logical_segment(int bid, int nseg) {
 // ---------------------------------------------------------------------------------------------
 // k_init : bootstrap_filter  (particles.jl:87-105)    grid (nseg, ntheta)
 // ---------------------------------------------------------------------------------------------
-template <int MODEL, int THREADS, int NP>
+// MISS: the missing first step (smc_spec.h "missing observations"; launched by the host when the handle has SMC_FLAG_NAN_MISSING
+// and y is NaN): model_missing_step, log-weight +0.0 - y is never read.
+template <int MODEL, int THREADS, int NP, bool MISS = false>
 __global__ __launch_bounds__(THREADS) void k_init(FilterView v, int nxt, double y) {
     constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -833,7 +835,10 @@ __global__ __launch_bounds__(THREADS) void k_init(FilterView v, int nxt, double 
 #pragma unroll
             for (int c = 0; c < NZ; ++c) zz[c] = z[c][j];
             const bool valid = (i0 + j) < v.n;
-            if constexpr (model_marginal<MODEL>::value) {   // the first step of a marginal family sees y (smc_spec.h)
+            if constexpr (MISS) {
+                model_missing_step<MODEL>(prm, true, xn[j], zz, xn[j]);
+                lw[k][j] = valid ? 0.0 : nan_mask();
+            } else if constexpr (model_marginal<MODEL>::value) {   // the first step of a marginal family sees y (smc_spec.h)
                 const double l = model_marginal_step<MODEL>(prm, true, xn[j], zz, y, xn[j]);
                 lw[k][j] = valid ? l : nan_mask();
             } else {
@@ -904,7 +909,11 @@ struct StepEarly {
     const uint64_t* C;      // v.C[cur]
     uint32_t n32;           // v.n (<= 2^31)
 };
-template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS, bool GTAB = false, int RPT = 1, bool GUIDED = false, bool BYV = false>
+// MISS: the missing step (smc_spec.h "missing observations"): model_missing_step and the log-weight +0.0 in place of the
+// transition and the observation density; everything else is the step's.  Instantiated by k_step_miss only, which the host
+// launches when the handle has SMC_FLAG_NAN_MISSING and the step's observation is NaN - the observation is uniform over the
+// launch, so there is no branch, and y is never read.
+template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS, bool GTAB = false, int RPT = 1, bool GUIDED = false, bool BYV = false, bool MISS = false>
 __device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& ea, uint64_t seed, uint32_t t, uint32_t stream0, int nseg, int cur, int emit_prev,
                                           double yval, const Params* prm0, char* smem) {
     const unsigned long long t_entry = SMC_CLOCK();
@@ -912,6 +921,7 @@ __device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& 
     static_assert(RPT == 1 || (RPT == 2 && MULTI && !GTAB), "two records per thread: multi-segment launches");
     constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
     static_assert(!(GUIDED && model_marginal<MODEL>::value), "marginal families have no proposals");
+    static_assert(!(MISS && GUIDED), "a missing step has no proposal");
     constexpr int SEG = 2 * NP * THREADS;
     constexpr int NQ = 2 * NP;   // particles per thread
     constexpr int NSTAGE = nstage_for(SEG);
@@ -1323,7 +1333,10 @@ __device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& 
             double zz[NZ];
 #pragma unroll
             for (int c = 0; c < NZ; ++c) zz[c] = z[k][c][j];
-            if constexpr (model_marginal<MODEL>::value) {
+            if constexpr (MISS) {
+                model_missing_step<MODEL>(prm, false, xp[2 * k + j], zz, xn[j]);
+                lw[k][j] = 0.0;
+            } else if constexpr (model_marginal<MODEL>::value) {
                 lw[k][j] = model_marginal_step<MODEL>(prm, false, xp[2 * k + j], zz, y, xn[j]);
             } else if constexpr (GUIDED) {
                 lw[k][j] = model_guided<MODEL>(prm, prw, xp[2 * k + j], zz, y, xn[j]);
@@ -1405,6 +1418,17 @@ __global__ __launch_bounds__(THREADS) void k_step(uint64_t seed, uint32_t t, uin
     const StepEarly ea{brow, rec0, rec1, C, n32};
     step_body<MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, GUIDED, BYV>(v, ea, seed, t, stream0, (int)(pack & 0xffffu), (int)(pack >> 16 & 1u),
                                                                       (int)(pack >> 17), yval, &prm0, smem);
+}
+
+// the missing step: the same argument block (the launchers share StepHot), the filter's stream id and parameter row always through
+// the view's pointers, yval and prm0 unused
+template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS = false, bool GTAB = false, int RPT = 1>
+__global__ __launch_bounds__(THREADS) void k_step_miss(uint64_t seed, uint32_t t, uint32_t stream0, const uint64_t* __restrict__ brow, const void* rec0, const void* rec1,
+                                                       const uint64_t* C, uint32_t pack, uint32_t n32, double yval, Params prm0, FilterView v) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const StepEarly ea{brow, rec0, rec1, C, n32};
+    step_body<MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, false, false, true>(v, ea, seed, t, stream0, (int)(pack & 0xffffu), (int)(pack >> 16 & 1u),
+                                                                             (int)(pack >> 17), yval, &prm0, smem);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -87,5 +87,16 @@ template <int MODEL> hipError_t launch_resident_g(const FilterView& v, int T, St
 // out [nk][d + 3][ntheta][npad]; hipErrorInvalidValue when g is not the geometry of the view's segment length
 template <int MODEL> hipError_t launch_forecast(const FilterView& v, Geo g, const double* src, uint64_t fseed, uint32_t k0, int nk, double* out, hipStream_t s);
 template <int MODEL> hipError_t launch_window_g(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
+// missing observations (smc_spec.h; handles with SMC_FLAG_NAN_MISSING): the MISS kernels, translation units of their own
+// (smc_model.hip with -DSMC_MISSING=1).  launch_init_m / launch_step_m: the missing step itself, launched for a step whose
+// observation is NaN (a guided handle too: a missing step has no proposal).  launch_resident_m / launch_window_m: the LDS-resident
+// loop that tests every step's observation, launched when the series or window holds a NaN; _gm: their twins for a handle with
+// a proposal (bootstrap step at gaps, guided step elsewhere; the families of by_guided_model)
+template <int MODEL> hipError_t launch_init_m(const FilterView& v, Geo g, int nxt, double y, hipStream_t s);
+template <int MODEL> hipError_t launch_step_m(const FilterView& v, Geo g, const StepHot& hot, hipStream_t s);
+template <int MODEL> hipError_t launch_resident_m(const FilterView& v, int T, StepRec* recs, hipStream_t s);
+template <int MODEL> hipError_t launch_window_m(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
+template <int MODEL> hipError_t launch_resident_gm(const FilterView& v, int T, StepRec* recs, hipStream_t s);
+template <int MODEL> hipError_t launch_window_gm(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
 
 }  // namespace smc

@@ -13,6 +13,14 @@
 #define SMC_GUIDED 0
 #endif
 #define SMC_G (SMC_GUIDED != 0)
+// -DSMC_MISSING=1: the same launchers again for the MISS kernels (handles with SMC_FLAG_NAN_MISSING; smc_spec.h "missing
+// observations"), translation units of their own as well: build/missing<model>.o (launch_init_m, launch_step_m, launch_resident_m,
+// launch_window_m) and, with -DSMC_GUIDED=1 on top, build/missingg<model>.o (launch_resident_gm, launch_window_gm - the missing
+// step itself has no proposal).  Without it: the kernels every other handle launches, untouched by the variant.
+#ifndef SMC_MISSING
+#define SMC_MISSING 0
+#endif
+#define SMC_M (SMC_MISSING != 0)
 
 namespace smc {
 
@@ -20,12 +28,26 @@ namespace smc {
 template <int THREADS, int NP>
 static hipError_t init_t(const FilterView& v, int nxt, double y, hipStream_t s) {
     const size_t lds = scr_words(THREADS, NP) * 8;
-    hipLaunchKernelGGL((k_init<SMC_MODEL, THREADS, NP>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, nxt, y);
+    hipLaunchKernelGGL((k_init<SMC_MODEL, THREADS, NP, SMC_M>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, nxt, y);
     return hipGetLastError();
 }
 #endif
 // one launch of k_step<..., BYV>: the kernel's parameter list is the leading scalars (StepLead) one by one at the head (what the
 // wave finds preloaded), the observation, the parameter row, the view
+#if SMC_M && !SMC_G
+// (the missing step reads the filter's row and stream id through the view on every launch: BYV is not instantiated)
+template <int THREADS, int NP, bool MULTI, bool SYS, bool GTAB, int RPT, bool BYV>
+static hipError_t step_launch(const FilterView& v, const StepHot& hot, int emit_prev, size_t lds, hipStream_t s) {
+    static_assert(!BYV, "missing step: through the pointers");
+    static std::atomic<bool> raised[16] = {};   // per instantiation and device
+    hipError_t e = raise_lds_limit(k_step_miss<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT>, lds, raised);
+    if (e != hipSuccess) return e;
+    const StepLead& l = hot.lead;
+    hipLaunchKernelGGL((k_step_miss<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, l.seed, l.t,
+                       l.stream0, l.brow, l.rec0, l.rec1, l.C, step_pack(hot.nseg, hot.cur, emit_prev), l.n32, hot.yval, hot.prm0, v);
+    return hipGetLastError();
+}
+#elif !SMC_M
 template <int THREADS, int NP, bool MULTI, bool SYS, bool GTAB, int RPT, bool BYV>
 static hipError_t step_launch(const FilterView& v, const StepHot& hot, int emit_prev, size_t lds, hipStream_t s) {
     static std::atomic<bool> raised[16] = {};   // per instantiation and device
@@ -36,6 +58,8 @@ static hipError_t step_launch(const FilterView& v, const StepHot& hot, int emit_
                        l.stream0, l.brow, l.rec0, l.rec1, l.C, step_pack(hot.nseg, hot.cur, emit_prev), l.n32, hot.yval, hot.prm0, v);
     return hipGetLastError();
 }
+#endif
+#if !(SMC_M && SMC_G)
 template <int THREADS, int NP, bool SYS, bool BYV>
 static hipError_t step_sys_t(const FilterView& v, const StepHot& hot, hipStream_t s) {
     if (v.tabD)   // the table comes from k_table (launched by the caller before this step): no table in LDS, nothing to emit
@@ -48,9 +72,14 @@ static hipError_t step_sys_t(const FilterView& v, const StepHot& hot, hipStream_
 }
 template <int THREADS, int NP>
 static hipError_t step_t(const FilterView& v, const StepHot& hot, hipStream_t s) {
+#if SMC_M
+    return v.systematic ? step_sys_t<THREADS, NP, true, false>(v, hot, s) : step_sys_t<THREADS, NP, false, false>(v, hot, s);
+#else
     if (hot.by_value) return v.systematic ? step_sys_t<THREADS, NP, true, true>(v, hot, s) : step_sys_t<THREADS, NP, false, true>(v, hot, s);
     return v.systematic ? step_sys_t<THREADS, NP, true, false>(v, hot, s) : step_sys_t<THREADS, NP, false, false>(v, hot, s);
+#endif
 }
+#endif
 
 #define SMC_GEO_SWITCH(FN, ...)                                                   \
     switch (g.threads * 8 + g.np) {                                               \
@@ -70,7 +99,15 @@ static hipError_t step_t(const FilterView& v, const StepHot& hot, hipStream_t s)
     }                                                                             \
     return hipErrorInvalidValue;
 
-#if !SMC_G
+#if !SMC_G && SMC_M
+template <>
+hipError_t launch_init_m<SMC_MODEL>(const FilterView& v, Geo g, int nxt, double y, hipStream_t s) {
+    SMC_GEO_SWITCH(init_t, v, nxt, y, s)
+}
+#define SMC_LAUNCH_STEP launch_step_m
+#define SMC_LAUNCH_RESIDENT launch_resident_m
+#define SMC_LAUNCH_WINDOW launch_window_m
+#elif !SMC_G
 template <>
 hipError_t launch_init<SMC_MODEL>(const FilterView& v, Geo g, int nxt, double y, hipStream_t s) {
     SMC_GEO_SWITCH(init_t, v, nxt, y, s)
@@ -88,25 +125,30 @@ hipError_t launch_forecast<SMC_MODEL>(const FilterView& v, Geo g, const double* 
 #define SMC_LAUNCH_STEP launch_step
 #define SMC_LAUNCH_RESIDENT launch_resident
 #define SMC_LAUNCH_WINDOW launch_window
+#elif SMC_M
+#define SMC_LAUNCH_RESIDENT launch_resident_gm
+#define SMC_LAUNCH_WINDOW launch_window_gm
 #else
 #define SMC_LAUNCH_STEP launch_step_g
 #define SMC_LAUNCH_RESIDENT launch_resident_g
 #define SMC_LAUNCH_WINDOW launch_window_g
 #endif
+#ifdef SMC_LAUNCH_STEP
 template <>
 hipError_t SMC_LAUNCH_STEP<SMC_MODEL>(const FilterView& v, Geo g, const StepHot& hot, hipStream_t s) {
     if (hot.by_value && v.ntheta != 1) return hipErrorInvalidValue;   // by value: ONE filter per launch
     SMC_GEO_SWITCH(step_t, v, hot, s)
 }
+#endif
 
 template <int THREADS, int NP, bool SYS, bool WIN, bool SUMM = false, bool UNW = false>
 static hipError_t resident_sys_t(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s) {
     const size_t lds = resident_lds_bytes<SMC_MODEL>(2 * NP * THREADS, THREADS, NP, SUMM ? v.sum_np : -1);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     static std::atomic<bool> raised[16] = {};   // per instantiation and device
-    hipError_t e = raise_lds_limit(k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW, SMC_G>, lds, raised);
+    hipError_t e = raise_lds_limit(k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW, SMC_G, SMC_M>, lds, raised);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW, SMC_G>), dim3(v.ntheta), dim3(THREADS), lds, s, v, T, recs, t0, bin, bout, win);
+    hipLaunchKernelGGL((k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW, SMC_G, SMC_M>), dim3(v.ntheta), dim3(THREADS), lds, s, v, T, recs, t0, bin, bout, win);
     return hipGetLastError();
 }
 // per-step summaries (smc_set_summaries) select the SUMM kernels; they exist for the multinomial default only (the C ABI sends
@@ -154,7 +196,7 @@ hipError_t SMC_LAUNCH_RESIDENT<SMC_MODEL>(const FilterView& v, int T, StepRec* r
     return hipErrorInvalidValue;
 }
 
-#if !SMC_G
+#if !SMC_G && !SMC_M
 template <int THREADS, int NP, bool UNW>
 static hipError_t summ_once_m(const FilterView& v, int cur, hipStream_t s) {
     constexpr int D = model_dim<SMC_MODEL>::value;

@@ -342,7 +342,9 @@ constexpr int resident_min_waves() {
 // SUMM: per-step summaries (resident_summaries) after every step, for the levels / coordinate the view names; UNW: its mode
 // GUIDED: as in step_body (smc_kernels.h) - the steps after the first draw from the proposal; the weight is complete when the
 // draw is, so the ancestors' states are used where they are gathered and nothing of them is kept for the observation loop
-template <int MODEL, int THREADS, int NP, bool SYS = false, bool WIN = false, bool SUMM = false, bool UNW = false, bool GUIDED = false>
+// MISS (handles with SMC_FLAG_NAN_MISSING, launched only when the series or window holds a NaN): a step whose observation is NaN
+// is the missing step (smc_spec.h "missing observations") - one workgroup-uniform test per step; MISS = false is the code as it was
+template <int MODEL, int THREADS, int NP, bool SYS = false, bool WIN = false, bool SUMM = false, bool UNW = false, bool GUIDED = false, bool MISS = false>
 __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())) void k_resident(FilterView v, int T, StepRec* recs /*[ntheta][T]*/, int t0, int bin, int bout,
                                                       double* win) {
     constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
@@ -488,6 +490,21 @@ __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())
 #pragma unroll
             for (int c = 0; c < NZ; ++c) box_muller(draw(v.seed, pg, stream, (uint32_t)t, SLOT_NORMAL0 + c), z[k][c][0], z[k][c][1]);
         }
+        const bool gap = MISS && y != y;   // workgroup-uniform; MISS = false: never
+        if (gap) {   // the missing step: no observation, log-weight +0.0 (a real branch, as t = 0 below)
+            asm volatile("; gap");
+#pragma unroll
+            for (int k = 0; k < NP; ++k)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    double zz[NZ];
+#pragma unroll
+                    for (int c = 0; c < NZ; ++c) zz[c] = z[k][c][j];
+                    if (t > 0) model_missing_step<MODEL>(prm, false, xp[2 * k + j], zz, xn[k][j]);
+                    else model_missing_step<MODEL>(prm, true, xn[k][j], zz, xn[k][j]);
+                    lw[k][j] = 0.0;
+                }
+        } else {
         if (t > 0) {
 #pragma unroll
             for (int k = 0; k < NP; ++k)
@@ -523,6 +540,7 @@ __global__ __launch_bounds__(THREADS, (resident_min_waves<MODEL, THREADS, NP>())
                     for (int j = 0; j < 2; ++j) lw[k][j] = model_logobs<MODEL>(prm, xn[k][j], y);
             }
         }
+        }   // (!gap)
         if (ragged) {   // n < SEG: the particles beyond n carry NaN weights and zero states (a real branch: the samplers' filters are full)
             asm volatile("; ragged");
 #pragma unroll

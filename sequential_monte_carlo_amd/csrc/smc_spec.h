@@ -712,6 +712,39 @@ SMC_HD void model_forecast_step(const Params& p, const double* xp, const double*
     }
 }
 
+// ---- missing observations (opt-in per handle: SMC_FLAG_NAN_MISSING) ---------------------------------------------------------
+// With the flag, a step whose observation is NaN is a MISSING step (+-inf still kill the step; without the flag a NaN kills it
+// too).  It is the ordinary step with the observation's part left out: the resampling from the current weights (either resampler,
+// the same Philox slots), the ancestors, the state normals of (seed, stream, t, SLOT_NORMAL0 + c) in the pair convention, the
+// masking of a ragged last segment, the segment normalisation, the records and the emission are the ordinary step's, and the time
+// index advances by one.  Per particle:
+//   bootstrap families     x = model_transition(xp, z), or model_initial(z) at the first step
+//   guided handles         the same: a proposal has no role without y (as in the forecasts)
+//   MODEL_UCSV_RB          rows 1, 2 as in model_marginal_step; row 0 = m unchanged (x0 at the first step); row 3 = P- =
+//                          sp[3] + sp_exp(sp[1]) (sp_exp(lse0) at the first step): model_marginal_predict without its observation
+//                          rows - rows 0 and 3 are then the PREDICTIVE moments of the trend, not a posterior
+// and the log-weight is +0.0.  The normalisation of n log-weights +0.0 gives logmu = +0.0, ess = n and w = 1/n exactly, so a
+// missing step adds nothing to logZ, bit for bit.  A filter that is collapsed when it meets a gap takes identity ancestors (as at
+// every step) and leaves the gap with uniform weights; its logZ stays -inf, because it is a running sum.
+// x may alias xp.
+template <int MODEL>
+SMC_HD void model_missing_step(const Params& p, bool first, const double* xp, const double* z, double* x) {
+    if constexpr (model_marginal<MODEL>::value) {
+        const double m = first ? p.raw[2] : xp[0];
+        const double a = first ? p.raw[3] : xp[1];
+        const double b = first ? p.raw[4] : xp[2];
+        const double Q = sp_exp(a);
+        const double Pm = first ? Q : xp[3] + Q;
+        x[0] = m;
+        x[1] = fma(p.raw[0], z[0], a);
+        x[2] = fma(p.raw[1], z[1], b);
+        x[3] = Pm;
+    } else {
+        if (first) model_initial<MODEL>(p, z, x);
+        else model_transition<MODEL>(p, xp, z, x);
+    }
+}
+
 // ---- PMMH rejuvenation of the samplers (src/smc_samplers.jl:103-146), one parameter particle ------------------
 // Random numbers are counter based like everything else: key = the move's seed, stream = GLOBAL index of the
 // parameter particle (so results do not depend on how theta is sharded), t = chain position.

@@ -484,6 +484,93 @@ extern "C" int smc_device_rb_step(const double* raw, const double* sp, const dou
     return SMC_OK;
 }
 
+// the whole step of a filter (include/smc_hip.h "missing observations"): every family and proposal, the first step and the missing
+// step included - what k_init, k_step and k_resident do to one particle, for n particles on the host / on a device
+template <int MODEL>
+SMC_HD double filter_step_one(const Params& P, const PropRow& R, bool guided, bool first, bool miss, const double* xp, const double* z, double y,
+                              double* x) {
+    if (miss) {
+        model_missing_step<MODEL>(P, first, xp, z, x);
+        return 0.0;
+    }
+    if constexpr (model_marginal<MODEL>::value) {
+        return model_marginal_step<MODEL>(P, first, xp, z, y, x);
+    } else {
+        if (first) model_initial<MODEL>(P, z, x);
+        else if (guided) return model_guided<MODEL>(P, R, xp, z, y, x);
+        else model_transition<MODEL>(P, xp, z, x);
+        return model_logobs<MODEL>(P, x, y);
+    }
+}
+static bool filter_step_params(int model_id, const double* raw, int kind, const double* par, Params& P, PropRow& R) {
+    if (kind != PROP_NONE) return guided_params(model_id, raw, kind, par, P, R);
+    const int nraw = model_nraw_rt(model_id);
+    if (nraw < 0 || !raw || par) return false;
+    for (int k = 0; k < NPARAM; ++k) { P.raw[k] = k < nraw ? raw[k] : 0.0; R.p[k] = 0.0; }
+    derive_params(model_id, P.raw, P.der);
+    return true;
+}
+extern "C" int smc_host_filter_steps(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z, double y,
+                                     int first, int nan_missing, int64_t n, double* x, double* logw) {
+    if (!z || !x || !logw || n <= 0 || (!first && !xp)) return fail(SMC_EINVAL, "smc_host_filter_steps: bad argument");
+    Params P;
+    PropRow R;
+    if (!filter_step_params(model_id, raw, kind, par, P, R)) return fail(SMC_EINVAL, "smc_host_filter_steps: bad model, kind or row");
+    const bool miss = nan_missing && y != y, guided = kind != PROP_NONE;
+    (void)by_model(model_id, [&](auto M) {
+        constexpr int MODEL = decltype(M)::value, D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
+        for (int64_t i = 0; i < n; ++i) {
+            double a[D] = {}, zz[NZ], xn[D];
+            for (int c = 0; c < D && !first; ++c) a[c] = xp[(size_t)c * n + i];
+            for (int c = 0; c < NZ; ++c) zz[c] = z[(size_t)c * n + i];
+            logw[i] = filter_step_one<MODEL>(P, R, guided, first != 0, miss, a, zz, y, xn);
+            for (int c = 0; c < D; ++c) x[(size_t)c * n + i] = xn[c];
+        }
+        return hipSuccess;
+    });
+    return SMC_OK;
+}
+template <int MODEL>
+__global__ void k_filter_steps(Params P, PropRow R, int guided, int first, int miss, const double* xp, const double* z, double y, int64_t n, double* x,
+                               double* logw) {
+    constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double a[D] = {}, zz[NZ], xn[D];
+    for (int c = 0; c < D; ++c) a[c] = first ? 0.0 : xp[(size_t)c * n + i];
+    for (int c = 0; c < NZ; ++c) zz[c] = z[(size_t)c * n + i];
+    logw[i] = filter_step_one<MODEL>(P, R, guided != 0, first != 0, miss != 0, a, zz, y, xn);
+    for (int c = 0; c < D; ++c) x[(size_t)c * n + i] = xn[c];
+}
+extern "C" int smc_device_filter_steps(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z, double y,
+                                       int first, int nan_missing, int64_t n, double* x, double* logw, int device) {
+    if (!z || !x || !logw || n <= 0 || (!first && !xp)) return fail(SMC_EINVAL, "smc_device_filter_steps: bad argument");
+    Params P;
+    PropRow R;
+    if (!filter_step_params(model_id, raw, kind, par, P, R)) return fail(SMC_EINVAL, "smc_device_filter_steps: bad model, kind or row");
+    const int miss = (nan_missing && y != y) ? 1 : 0, guided = kind != PROP_NONE ? 1 : 0;
+    const size_t d = (size_t)model_dim_rt(model_id), nz = model_id == MODEL_UCSV_RB ? 2 : d;
+    hipStream_t st = nullptr;
+    HIPCHK(util_stream(device, &st));
+    DevBuf dxp(0), dz(1), dx(2), dlw(3);
+    HIPCHK(dxp.alloc(d * n * 8));
+    HIPCHK(dz.alloc(nz * n * 8));
+    HIPCHK(dx.alloc(d * n * 8));
+    HIPCHK(dlw.alloc((size_t)n * 8));
+    if (!first) HIPCHK(hipMemcpyAsync(dxp.p, xp, d * n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dz.p, z, nz * n * 8, hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    HIPCHK(by_model(model_id, [&](auto M) {
+        hipLaunchKernelGGL(k_filter_steps<decltype(M)::value>, grid, block, 0, st, P, R, guided, first, miss, dxp.as<double>(), dz.as<double>(), y, n,
+                           dx.as<double>(), dlw.as<double>());
+        return hipGetLastError();
+    }));
+    HIPCHK(hipMemcpyAsync(x, dx.p, d * n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(logw, dlw.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+
 extern "C" int smc_device_math(int which, const double* a, const double* b, int64_t n, double* out, int device) {
     if (!a || !out || n <= 0 || which < 0 || which > 5) return fail(SMC_EINVAL, "smc_device_math: bad argument");
     if (which >= 3 && !b) return fail(SMC_EINVAL, "smc_device_math: b required");

@@ -94,8 +94,9 @@ def trend_moments(mean, var):
 class _Filters:
     """Device state shared by the Particles / Weights views of one bootstrap_filter call."""
 
-    def __init__(self, N, models, seed, seg, device, streams, ancestors, resampler="multinomial", proposal=None, rows=None):
-        """rows=(model id, [n_theta][n_raw] parameter rows): a batch given as rows instead of `models` (then None)"""
+    def __init__(self, N, models, seed, seg, device, streams, ancestors, resampler="multinomial", proposal=None, rows=None, missing=False):
+        """rows=(model id, [n_theta][n_raw] parameter rows): a batch given as rows instead of `models` (then None)
+        missing=True: a NaN observation is a missing one (FLAG_NAN_MISSING)"""
         if rows is not None:
             mid, raw = int(rows[0]), np.ascontiguousarray(rows[1], dtype=np.float64)
         else:
@@ -103,7 +104,8 @@ class _Filters:
         self.single = rows is None and not isinstance(models, (list, tuple))
         if resampler not in ("multinomial", "systematic"):
             raise ValueError("resampler must be 'multinomial' (the reference's law) or 'systematic' (opt-in)")
-        flags = (_lib.FLAG_ANCESTORS if ancestors else 0) | (_lib.FLAG_SYSTEMATIC if resampler == "systematic" else 0)
+        flags = (_lib.FLAG_ANCESTORS if ancestors else 0) | (_lib.FLAG_SYSTEMATIC if resampler == "systematic" else 0) | (
+            _lib.FLAG_NAN_MISSING if missing else 0)
         self.h = _lib.Handle(mid, raw.shape[0], N, seg=seg, seed=seed, device=device, flags=flags)
         self.h.set_params(raw)
         if streams is not None:
@@ -212,12 +214,15 @@ class Weights:
         return self._f.h.n_x
 
 
-def bootstrap_filter(N, y, model, seed=None, seg=0, device=0, streams=None, ancestors=False, resampler="multinomial"):
+def bootstrap_filter(N, y, model, seed=None, seg=0, device=0, streams=None, ancestors=False, resampler="multinomial", missing=False):
     """x, w, logmu = bootstrap_filter(N, y[1], model)   particles.jl:87-105
-    resampler="systematic" (opt-in, not the reference's law) applies to the following bootstrap_filter_ steps."""
+    resampler="systematic" (opt-in, not the reference's law) applies to the following bootstrap_filter_ steps.
+    missing=True (opt-in): a NaN observation, here and in the bootstrap_filter_ steps that follow (they read it from the handle
+    behind x), is a period without an observation - the cloud moves by the transition, the weights become uniform, logmu = 0
+    (DESIGN.md 2j).  Without it a NaN kills its step."""
     if seed is None:
         seed = next(_seed_counter)
-    f = _Filters(int(N), model, seed, seg, device, streams, ancestors, resampler)
+    f = _Filters(int(N), model, seed, seg, device, streams, ancestors, resampler, missing=missing)
     logmu = f.h.init(float(y))
     return Particles(f), Weights(f), f.out(logmu)
 
@@ -233,14 +238,16 @@ def bootstrap_filter_(states, weights, y, model):
     return f.out(logmu), Weights(f), f.out(ess)
 
 
-def particle_filter(N, y, model, proposal=None, seed=None, seg=0, device=0, streams=None, ancestors=False, resampler="multinomial"):
+def particle_filter(N, y, model, proposal=None, seed=None, seg=0, device=0, streams=None, ancestors=False, resampler="multinomial",
+                    missing=False):
     """x, w, logmu = particle_filter(N, y[1], model, proposal)   particles.jl:28-52
     The first step draws from initial_dist and weights by the observation density, exactly bootstrap_filter (the reference
     adds logpdf(initial_dist, x) there, a slip: DESIGN.md "Guided filters"); the proposal applies to the particle_filter_ steps
-    that follow.  proposal=None is bootstrap_filter."""
+    that follow.  proposal=None is bootstrap_filter.  missing=True: as in bootstrap_filter; a missing step moves the particles by
+    the transition, not by the proposal (a proposal has no role without y)."""
     if seed is None:
         seed = next(_seed_counter)
-    f = _Filters(int(N), model, seed, seg, device, streams, ancestors, resampler, proposal)
+    f = _Filters(int(N), model, seed, seg, device, streams, ancestors, resampler, proposal, missing=missing)
     logmu = f.h.init(float(y))
     return Particles(f), Weights(f), f.out(logmu)
 
@@ -274,7 +281,7 @@ def _summaries_out(f, T):
 
 
 def log_likelihood(N, y, model, seed=None, seg=0, device=0, streams=None, ancestors=False, trace=False,
-                   resampler="multinomial", quantiles=None, component=0, moments=False, weighted=True, proposal=None):
+                   resampler="multinomial", quantiles=None, component=0, moments=False, weighted=True, proposal=None, missing=False):
     """x, w, logZ = log_likelihood(N, y, model)   particles.jl:132-147
     trace=True additionally returns the per-step (logmu_t, ess_t).  resampler="systematic": opt-in systematic
     resampling (same expectation, lower variance, one launch per step for big filters; not the reference's law).
@@ -283,10 +290,12 @@ def log_likelihood(N, y, model, seed=None, seg=0, device=0, streams=None, ancest
     on the device inside the filter loop and returned as a dict behind the usual results.  weighted=False gives the README's own
     numbers: the unweighted type-7 `quantile(x, p)` and the corrected `var(x)` of the cloud (see Particles.quantile);
     weighted=True (the default) the weighted inverse CDF and the uncorrected weighted variance.
-    proposal: the guided filter (particle_filter_ at every step after the first) instead of the bootstrap filter."""
+    proposal: the guided filter (particle_filter_ at every step after the first) instead of the bootstrap filter.
+    missing=True (opt-in): NaN entries of y are periods without an observation: they add nothing to logZ, and the
+    per-step summaries there are those of the propagated cloud."""
     if seed is None:
         seed = next(_seed_counter)
-    f = _Filters(int(N), model, seed, seg, device, streams, ancestors, resampler, proposal)
+    f = _Filters(int(N), model, seed, seg, device, streams, ancestors, resampler, proposal, missing=missing)
     y = np.ascontiguousarray(y, dtype=np.float64)
     summ = quantiles is not None or moments
     if summ:
@@ -389,7 +398,7 @@ def _run_recorded(h, y):
 
 
 def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="multinomial", proposal=None, weights=False, rows=None,
-             paths=0, path_seed=None, path_counts=None, smooth=True):
+             paths=0, path_seed=None, path_counts=None, smooth=True, missing=False):
     """x, w, logZ, s = smoother(N, y, model): the particle filter of log_likelihood run step by step with its clouds recorded on
     the device, then the FFBS backward pass over them (forward filtering, backward smoothing).  x, w, logZ are the
     filter's, as log_likelihood returns them; s describes p(x_t | y_1:T):
@@ -407,10 +416,12 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
                                     s["mean"], s["var"]).  A batch holds T n_theta M entries: keep M small there.
     The backward pass costs 2 N^2 (T - 1) transition densities per filter.  Any proposal, either resampler; MarginalUCSV has no
     smoother of this kind (its state rows have no transition density): rb_smoother is its smoother.
-    rows=(model id, parameter rows [n_theta][n_raw]) with model=None: a batch given as rows (what the samplers hold)."""
+    rows=(model id, parameter rows [n_theta][n_raw]) with model=None: a batch given as rows (what the samplers hold).
+    missing=True (opt-in): NaN entries of y are periods without an observation; s["mean"], s["var"] and the paths
+    there are the interpolated state."""
     if seed is None:
         seed = next(_seed_counter)
-    f = _Filters(int(N), model, seed, seg, device, streams, False, resampler, proposal, rows=rows)
+    f = _Filters(int(N), model, seed, seg, device, streams, False, resampler, proposal, rows=rows, missing=missing)
     y = np.ascontiguousarray(y, dtype=np.float64).ravel()
     T, h = y.size, f.h
     if T < 1:
@@ -441,7 +452,7 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
 
 
 def rb_smoother(N, y, model, paths=256, seed=None, path_seed=None, draws=False, per_path=False, path_counts=None, seg=0, device=0,
-                streams=None, resampler="multinomial", rows=None):
+                streams=None, resampler="multinomial", rows=None, missing=False):
     """x, w, logZ, s = rb_smoother(N, y, model, paths=M): the smoother of MarginalUCSV (one model or a list of them).  The marginal
     filter of log_likelihood is run step by step with its clouds recorded on the device; then M volatility paths per filter are
     drawn from p(lse_1:T, lsn_1:T | y_1:T) by Rao-Blackwellised backward simulation, and the trend comes exactly given each path
@@ -455,10 +466,12 @@ def rb_smoother(N, y, model, paths=256, seed=None, path_seed=None, draws=False, 
         draws=True:     s["paths"] [T][M][3]: joint draws of (x, lse, lsn) from p(x_1:T, lse_1:T, lsn_1:T | y_1:T)
     With a list of models a batch axis follows T everywhere, as in smoother.  path_seed: the seed of the walk's draws (default:
     derived from the filter seed); path_counts [n_theta]: draw only that many paths of each filter.  Either resampler.
-    rows=(model id, parameter rows [n_theta][5]) with model=None: a batch given as rows (what the samplers hold)."""
+    rows=(model id, parameter rows [n_theta][5]) with model=None: a batch given as rows (what the samplers hold).
+    missing=True: the filter reads NaN as missing, but the Kalman / RTS pass along a path has no rule for a gap yet: a NaN in y
+    raises (SmcError)."""
     if seed is None:
         seed = next(_seed_counter)
-    f = _Filters(int(N), model, seed, seg, device, streams, False, resampler, None, rows=rows)
+    f = _Filters(int(N), model, seed, seg, device, streams, False, resampler, None, rows=rows, missing=missing)
     if f.model_id != _lib.MODEL_UCSV_RB:
         raise TypeError("rb_smoother is the smoother of MarginalUCSV; the other families have a transition density: smoother")
     y = np.ascontiguousarray(y, dtype=np.float64).ravel()

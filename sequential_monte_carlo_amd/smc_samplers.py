@@ -111,14 +111,17 @@ class LibOuter:
 class HipBackend:
     """Runs the batched inner filters on one GPU through the C ABI (no CPU fallback).
     proposal: OptimalProposal() or an AffineGaussianProposal (particles.py) makes every inner filter - the main, proposal and
-    exchange handles alike, and the device PMMH - a guided particle filter; None (the default) the bootstrap filter."""
+    exchange handles alike, and the device PMMH - a guided particle filter; None (the default) the bootstrap filter.
+    missing=True (opt-in): every inner filter reads a NaN observation as a missing one (FLAG_NAN_MISSING)."""
 
     outer = LibOuter()
 
-    def __init__(self, device=0, seg=0, resampler="multinomial", proposal=None):
+    def __init__(self, device=0, seg=0, resampler="multinomial", proposal=None, missing=False):
         self.device, self.seg = device, seg
         self.proposal = proposal
+        self.missing = bool(missing)
         self.flags = _lib.FLAG_SYSTEMATIC if resampler == "systematic" else 0   # opt-in; default = the reference's law
+        self.flags |= _lib.FLAG_NAN_MISSING if self.missing else 0
         self._handles = {}
 
     def _handle(self, key, model_id, n_theta, N, seed):
@@ -183,8 +186,10 @@ class SMC:
     StateSpaceModel (the reference's closure smc.model(theta))."""
 
     def __init__(self, N, M, model, prior, chain, ess_threshold, min_ar=-1.0, seed=1, backend=None, comm=None,
-                 raw_fn=None, theta_map=None):
-        """theta_map (optional): ThetaMap, the device-evaluable form of `model`; with a prior of enumerated families it
+                 raw_fn=None, theta_map=None, missing=False):
+        """missing=True (opt-in): NaN entries of the series are periods without an observation in every inner
+        filter; the default backend is created that way, a backend given by the caller must have been (HipBackend(missing=True)).
+        theta_map (optional): ThetaMap, the device-evaluable form of `model`; with a prior of enumerated families it
         moves rejuvenate! onto the device.  raw_fn (optional): vectorised shortcut for `model`: maps an [m, d_theta]
         array to (model_id, [m, n_raw] parameter rows) without building m model objects per evaluation."""
         self.N, self.M, self.model, self.prior, self.chain = int(N), int(M), model, prior, int(chain)
@@ -204,7 +209,10 @@ class SMC:
         self.ess = float(self.M)
         self.ess_min = self.M * float(ess_threshold)
         self.acc_threshold, self.acc_ratio = float(min_ar), 0.0
-        self.backend = backend if backend is not None else HipBackend()
+        self.backend = backend if backend is not None else HipBackend(missing=missing)
+        if bool(missing) != bool(getattr(self.backend, "missing", False)):
+            raise ValueError("SMC(missing=...) and the backend disagree: create the backend with the same missing=")
+        self.missing = bool(missing)
         self.outer = getattr(self.backend, "outer", None) or LibOuter()
         self._outer_local = False           # True: only this rank's slice of logw / logZ is current (sharded online steps)
         self.prior_spec = prior.spec() if hasattr(prior, "spec") else None
