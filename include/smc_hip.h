@@ -45,6 +45,8 @@ extern "C" {
                                 * particle's children, lower variance, a different law - never the default. */
 #define SMC_FLAG_NAN_MISSING 8u /* OPT-IN: a NaN observation is a MISSING one ("missing observations" below): its step moves
                                  * the cloud by the transition and weighs nothing.  Without the flag a NaN kills its step. */
+#define SMC_FLAG_CONDITIONAL 16u /* OPT-IN: the conditional particle filter ("the conditional particle filter" below): one slot of every
+                                 * step is pinned to a reference trajectory.  Without the flag nothing changes. */
 
 typedef struct smc_filter_s* smc_handle;
 
@@ -718,6 +720,33 @@ int smc_sample_paths(smc_handle h, int64_t M, uint64_t path_seed, const int32_t*
                      int32_t* idx /*[T][n_theta][M] or NULL*/, double* xs /*[T][d][n_theta][M] or NULL*/);
 int smc_host_sample_paths(int model_id, const double* raw, int64_t T, int64_t n, const double* x /*[T][d][n]*/, const double* w /*[T][n]*/,
                           int64_t M, uint64_t path_seed, uint32_t stream, int32_t* idx /*[T][M]*/, double* xs /*[T][d][M] or NULL*/);
+
+/* ---- the conditional particle filter: particle Gibbs with backward simulation (Andrieu, Doucet and Holenstein 2010) -------------
+ * A handle created with SMC_FLAG_CONDITIONAL holds a reference trajectory xref [T][d][n_theta] on the device.  smc_init and every
+ * smc_step are the ordinary bootstrap step with ONE slot overridden: slot k*_t = mulhi64(u, n_x), u the first 64-bit word of the
+ * Philox draw (seed, pair 0, stream, t, slot 38) - smc_host_conditional_slot - takes the state xref[t] bit for bit, the log-weight
+ * logpdf(observation(xref[t]), y_t) - smc_host_logobs - and, with SMC_FLAG_ANCESTORS, the ancestor k*_{t-1} (k*_0 at the first
+ * step).  Everything else is the ordinary step's, with the same random numbers.  The slot is random because the multinomial
+ * resampler sorts its uniforms: see csrc/smc_spec.h.  Run with the record armed (smc_history_begin), then ONE path of
+ * smc_sample_paths adopted with smc_reference_from_paths: together a Markov kernel that leaves p(x_1:T | y_1:T, theta) invariant
+ * for any n_x >= 2.  Reseed between sweeps (smc_reseed, and another path seed): a sweep must not reuse its counters.
+ * Refused: at smc_create the flag with SMC_FLAG_SYSTEMATIC, SMC_FLAG_NAN_MISSING, SMC_MODEL_UCSV_RB or n_x > 2^20 (SMC_EINVAL);
+ * smc_set_proposal with a kind other than SMC_PROP_NONE (SMC_EINVAL); smc_log_likelihood, smc_step_window, smc_step_commit,
+ * smc_pmmh_rejuvenate (either role) and smc_time_step_kernel (SMC_ESTATE: they would launch kernels without the override, and the
+ * logZ of a conditional run is not a likelihood estimate); smc_init without a reference and smc_step at a time index >= T
+ * (SMC_ESTATE).  A conditional handle runs one launch per step, for every segment geometry smc_create accepts. */
+/* host -> device; a non-finite entry is refused (SMC_EINVAL); replaces any earlier reference */
+int smc_set_reference(smc_handle h, const double* xref /*[T][d][n_theta]*/, int64_t T);
+/* path p of the last smc_sample_paths walk over the handle's current record becomes the reference: a device gather from the record
+ * through the walk's indices into the reference's own buffer (the next sweep overwrites the record).  A filter whose path p is
+ * dead (index -1) keeps its reference; *kept (may be NULL): the number of such filters.  SMC_ESTATE without such a walk, or when a
+ * dead path has no reference of that length to keep. */
+int smc_reference_from_paths(smc_handle h, int64_t p, int64_t* kept);
+/* the reference read back: *T its length (either may be NULL) */
+int smc_get_reference(smc_handle h, double* xref /*[T][d][n_theta]*/, int64_t* T);
+/* the slot rule and the log-weight of a reference row on the host, no GPU (LG1D, SV1D, UCSV3D) */
+int smc_host_conditional_slot(uint64_t seed, uint32_t stream, uint32_t t, int64_t n_x, int64_t* k);
+int smc_host_logobs(int model_id, const double* raw, const double* x /*[d]*/, double y, double* out);
 
 /* ---- Rao-Blackwellised backward simulation: smoothing the marginal UCSV filter (Lindsten et al. 2016) ---------------------------
  * SMC_MODEL_UCSV_RB carries the Kalman mean and variance of the trend inside every particle, and those two rows are functions of

@@ -11,7 +11,7 @@ from .ibis import rts_quantile, rts_smoothed_paths, rts_smoothed_state  # noqa: 
 from .kalman_filter import kalman_smoother, log_likelihood_kalman  # noqa: F401
 from .models import (UCSV, LinearModel, MarginalUCSV, StateSpaceModel, StochasticVolatility, UnivariateLinearGaussian,  # noqa: F401
                      simulate, unobserved_components, unobserved_components_stochastic_volatility)
-from .particles import (AffineGaussianProposal, OptimalProposal, bootstrap_filter, bootstrap_filter_, forecast, log_likelihood, normalize,  # noqa: F401
+from .particles import (AffineGaussianProposal, OptimalProposal, ParticleGibbs, bootstrap_filter, bootstrap_filter_, forecast, log_likelihood, normalize,  # noqa: F401
                         optimal_proposal, particle_filter, particle_filter_, rb_smoother, resample, reweight, smoother, trend_moments)
 from .smc_samplers import (SMC, ThetaMap, density_tempered, estimated_trend, expected_parameters, filtered_state, forecast_state,  # noqa: F401
                            filtered_summaries, observation_dist, posterior_moments, quantile, rejuvenate_, resample_, smc2, smc2_run, smc2_step,

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMC_LIB") or os.path.join(_HERE, "lib", "libsmchip.so")   # SMC_LIB: profiling builds
 
 MODEL_LG1D, MODEL_SV1D, MODEL_UCSV3D, MODEL_UCSV_RB = 1, 2, 3, 4
-FLAG_ANCESTORS, FLAG_NO_RESIDENT, FLAG_SYSTEMATIC, FLAG_NAN_MISSING = 1, 2, 4, 8
+FLAG_ANCESTORS, FLAG_NO_RESIDENT, FLAG_SYSTEMATIC, FLAG_NAN_MISSING, FLAG_CONDITIONAL = 1, 2, 4, 8, 16
 
 # every symbol include/smc_hip.h declares
 EXPORTS = [
@@ -40,6 +40,7 @@ EXPORTS = [
     "smc_host_smooth", "smc_sample_paths", "smc_host_sample_paths", "smc_rb_sample_paths", "smc_host_rb_sample_paths",
     "smc_forecast", "smc_forecast_cloud", "smc_host_forecast",
     "smc_get_flags", "smc_host_filter_steps", "smc_device_filter_steps",
+    "smc_set_reference", "smc_reference_from_paths", "smc_get_reference", "smc_host_conditional_slot", "smc_host_logobs",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -131,6 +132,11 @@ def lib():
     L.smc_device_rb_step.argtypes = [_dp, _dp, _dp, C.c_double, C.c_int, C.c_int64, _dp, _dp, C.c_int]
     L.smc_host_guided_steps.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int64, _dp, _dp]
     L.smc_get_flags.argtypes = [h, _u32p]
+    L.smc_set_reference.argtypes = [h, _dp, C.c_int64]
+    L.smc_reference_from_paths.argtypes = [h, C.c_int64, C.POINTER(C.c_int64)]
+    L.smc_get_reference.argtypes = [h, _dp, C.POINTER(C.c_int64)]
+    L.smc_host_conditional_slot.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int64, C.POINTER(C.c_int64)]
+    L.smc_host_logobs.argtypes = [C.c_int, _dp, _dp, C.c_double, _dp]
     L.smc_host_filter_steps.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int64, _dp, _dp]
     L.smc_device_filter_steps.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int64, _dp, _dp, C.c_int]
     L.smc_host_rb_steps.argtypes = [_dp, _dp, _dp, C.c_double, C.c_int, C.c_int64, _dp, _dp]
@@ -385,6 +391,24 @@ def device_filter_steps(model_id, raw, kind, par, xp, z, y, first=False, missing
     return _filter_steps(lib().smc_device_filter_steps, model_id, raw, kind, par, xp, z, y, first, missing, device)
 
 
+def host_conditional_slot(seed, stream, t, n_x):
+    """the retained slot k*_t of a conditional step (smc_host_conditional_slot; no GPU): a function of (seed, stream, t, n_x)"""
+    k = C.c_int64()
+    check(lib().smc_host_conditional_slot(int(seed), int(stream), int(t), int(n_x), C.byref(k)))
+    return k.value
+
+
+def host_logobs(model_id, raw, x, y):
+    """logpdf(observation(x), y) of one state x [d] by the specification on the host (smc_host_logobs; LG1D, SV1D, UCSV3D)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    if x.size != lib().smc_model_dim(int(model_id)):
+        raise ValueError("x must be [d]")
+    out = np.zeros(1)
+    check(lib().smc_host_logobs(int(model_id), _d(raw), _d(x), float(y), _d(out)))
+    return float(out[0])
+
+
 def host_rb_step(raw, sp, z, y, first=False):
     """one particle, one step of the marginal UCSV family by the specification on the host: state (m, lse, lsn, P) [4] and two
     normals -> (state [4], logw) (smc_host_rb_step; no GPU).  first=True: the step at t = 1, which does not read sp"""
@@ -618,6 +642,35 @@ class Handle:
         f = C.c_uint32()
         check(lib().smc_get_flags(self._h, C.byref(f)))
         return bool(f.value & FLAG_NAN_MISSING)
+
+    @property
+    def conditional(self):
+        """the handle runs the conditional particle filter (FLAG_CONDITIONAL, read back from the library)"""
+        f = C.c_uint32()
+        check(lib().smc_get_flags(self._h, C.byref(f)))
+        return bool(f.value & FLAG_CONDITIONAL)
+
+    def set_reference(self, xref):
+        """the reference trajectory of a conditional handle, xref [T][d][n_theta] (smc_set_reference); replaces any earlier one"""
+        xref = np.ascontiguousarray(xref, dtype=np.float64)
+        if xref.ndim != 3 or xref.shape[1:] != (self.d, self.n_theta):
+            raise ValueError("xref must be [T][d][n_theta]")
+        check(lib().smc_set_reference(self._h, _d(xref), xref.shape[0]))
+
+    def get_reference(self):
+        """the reference [T][d][n_theta] as the device holds it (smc_get_reference)"""
+        T = C.c_int64()
+        check(lib().smc_get_reference(self._h, None, C.byref(T)))
+        xref = np.zeros((T.value, self.d, self.n_theta))
+        check(lib().smc_get_reference(self._h, _d(xref), None))
+        return xref
+
+    def reference_from_paths(self, p=0):
+        """path p of the last sample_paths walk becomes the reference, gathered on the device (smc_reference_from_paths); returns
+        the number of filters whose path was dead and that kept their reference"""
+        kept = C.c_int64()
+        check(lib().smc_reference_from_paths(self._h, int(p), C.byref(kept)))
+        return kept.value
 
     def close(self):
         if getattr(self, "_h", None):

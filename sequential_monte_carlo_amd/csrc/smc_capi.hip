@@ -91,9 +91,17 @@ extern "C" int smc_device_count(void) {
     return n;
 }
 
+int cond_refuse(const char* who) {
+    return fail(SMC_ESTATE, std::string(who) + ": the handle is conditional (SMC_FLAG_CONDITIONAL): it runs smc_init / smc_step only, one launch per step "
+                                               "with the reference pinned, and its logZ is not a likelihood estimate");
+}
+
 // ---- kernel dispatch -------------------------------------------------------------------------
 // (a flagged handle whose observation is NaN: the missing step, smc_spec.h "missing observations" - the MISS kernels)
+// (a conditional handle: the COND kernels, with the reference row of the step as their last argument)
 hipError_t do_init(smc_filter_s* h, double y) {
+    if (conditional(h))
+        return by_density_model(h->model, [&](auto M) { return launch_init_c<decltype(M)::value>(h->v, h->geo, h->cur, y, h->cond.d_xref, h->stream); });
     if (nan_missing(h) && y != y)
         return by_model(h->model, [&](auto M) { return launch_init_m<decltype(M)::value>(h->v, h->geo, h->cur, y, h->stream); });
     return by_model(h->model, [&](auto M) { return launch_init<decltype(M)::value>(h->v, h->geo, h->cur, y, h->stream); });
@@ -139,6 +147,11 @@ hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y, const d
         emit_prev = 0;
     }
     const StepHot hot = step_hot(h, t, emit_prev, y, y_host);
+    if (conditional(h)) {
+        if (!h->cond.d_xref || (int64_t)t >= h->cond.T) return hipErrorInvalidValue;   // (smc_step has refused with a message)
+        const double* xrow = h->cond.d_xref + (size_t)t * (size_t)h->d * (size_t)h->v.ntheta;
+        return by_density_model(h->model, [&](auto M) { return launch_step_c<decltype(M)::value>(h->v, h->geo, hot, xrow, h->stream); });
+    }
     // the step API's observation, or the series' (gap_y: set only when a flagged handle's series holds a NaN)
     const bool gap = h->v.y ? (h->gap_y && h->gap_y[t] != h->gap_y[t]) : (nan_missing(h) && y != y);
     if (gap)   // uniform over the launch: the missing step's own kernel, for a handle with a proposal too
@@ -267,6 +280,14 @@ extern "C" int smc_create(int model_id, int64_t n_theta, int64_t n_x, int seg, u
     const int64_t nseg = (n_x + seg - 1) / seg;
     if (nseg > MAX_NSEG) return fail(SMC_EINVAL, "smc_create: more than 16384 segments; use a larger seg");
     if (n_x > ((int64_t)1 << 31)) return fail(SMC_EINVAL, "smc_create: n_x > 2^31");
+    if (flags & SMC_FLAG_CONDITIONAL) {   // the conditional particle filter (include/smc_hip.h): what it does not cover
+        if (flags & SMC_FLAG_SYSTEMATIC)
+            return fail(SMC_EINVAL, "smc_create: SMC_FLAG_CONDITIONAL with SMC_FLAG_SYSTEMATIC (conditional systematic resampling is another algorithm)");
+        if (flags & SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_create: SMC_FLAG_CONDITIONAL with SMC_FLAG_NAN_MISSING (no gaps in conditional runs)");
+        if (!has_density(model_id))
+            return fail(SMC_EINVAL, "smc_create: SMC_FLAG_CONDITIONAL with SMC_MODEL_UCSV_RB (its state rows have no transition density: no backward simulation)");
+        if (n_x > PATH_MAX_N) return fail(SMC_EINVAL, "smc_create: SMC_FLAG_CONDITIONAL with n_x > 2^20 (the limit of the backward walk, smc_sample_paths)");
+    }
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
     if (ndev == 0) return fail(SMC_EHIP, "smc_create: no HIP device; this library has no CPU fallback");
@@ -290,7 +311,7 @@ extern "C" int smc_create(int model_id, int64_t n_theta, int64_t n_x, int seg, u
         else (void)hipMemset(v.dbg, 0, (size_t)v.ntheta * v.nseg * 128);
     }
 #endif
-    h->resident_ok = (v.nseg == 1) && !(flags & SMC_FLAG_NO_RESIDENT);
+    h->resident_ok = (v.nseg == 1) && !(flags & (SMC_FLAG_NO_RESIDENT | SMC_FLAG_CONDITIONAL));   // (conditional: one launch per step only)
     v.systematic = (flags & SMC_FLAG_SYSTEMATIC) ? 1 : 0;
     v.inv_n = 1.0 / (double)n_x;
 
@@ -389,6 +410,7 @@ extern "C" int smc_destroy(smc_handle h) {
     if (h->h_perm) (void)hipHostFree(h->h_perm);
     if (h->h_params && !kept) (void)hipHostFree(h->h_params);
     if (h->d_prop) (void)hipFree(h->d_prop);
+    (void)hipFree(h->cond.d_xref);   // (the reference never travels with the bundle)
     if (h->h_prop) (void)hipHostFree(h->h_prop);
     history_free(h);
     (void)hipFree(h->skip.d_mask); (void)hipFree(h->skip.d_order);
@@ -448,6 +470,8 @@ extern "C" int smc_set_params(smc_handle h, const double* raw) {
 extern "C" int smc_set_proposal(smc_handle h, int kind, const double* par) {
     if (!h) return fail(SMC_EINVAL, "smc_set_proposal: NULL handle");
     if (kind != PROP_NONE && kind != PROP_AFFINE && kind != PROP_OPTIMAL) return fail(SMC_EINVAL, "smc_set_proposal: unknown kind");
+    if (conditional(h) && kind != PROP_NONE)
+        return fail(SMC_EINVAL, "smc_set_proposal: the handle is conditional (SMC_FLAG_CONDITIONAL): guided conditional filters are not covered");
     if (h->model == MODEL_UCSV_RB && kind != PROP_NONE)
         return fail(SMC_EINVAL, "smc_set_proposal: SMC_MODEL_UCSV_RB takes no proposal (its step already conditions on y: the trend is integrated out)");
     if (!proposal_supported(h->model, kind)) return fail(SMC_EINVAL, "smc_set_proposal: this model family has no proposal of that kind");
@@ -587,6 +611,8 @@ int emit_if_needed(smc_handle h) {
 extern "C" int smc_init(smc_handle h, double y1, double* logmu) {
     if (!h) return fail(SMC_EINVAL, "smc_init: NULL handle");
     if (!h->have_params) return fail(SMC_ESTATE, "smc_init: smc_set_params has not been called");
+    if (conditional(h) && !h->cond.d_xref)
+        return fail(SMC_ESTATE, "smc_init: the handle is conditional (SMC_FLAG_CONDITIONAL) and has no reference (smc_set_reference)");
     h->win.k = 0;   // an uncommitted window is dropped
     HIPCHK(hipSetDevice(h->device));
     h->v.y = nullptr; h->v.trace_logmu = nullptr; h->v.trace_ess = nullptr;
@@ -605,6 +631,7 @@ extern "C" int smc_init(smc_handle h, double y1, double* logmu) {
     if (rc) return rc;
     if (history_armed(h)) {   // smc_init restarts the record
         h->hist.len = 0;
+        h->hist.walk_M = 0;   // (the last walk's indices belonged to the record this run overwrites)
         if (const int hr = history_append(h)) return hr;
     }
     return seq ? wait_ticket(h, seq, logmu, nullptr) : finish_elapsed(h, nullptr, logmu, nullptr);
@@ -615,6 +642,8 @@ extern "C" int smc_step(smc_handle h, double y_t, double* logmu, double* ess) {
     if (!h) return fail(SMC_EINVAL, "smc_step: NULL handle");
     if (!h->inited) return fail(SMC_ESTATE, "smc_step: call smc_init (bootstrap_filter) first");
     if (history_armed(h) && h->hist.len >= h->hist.cap) return fail(SMC_ESTATE, "smc_step: the record is full (smc_history_begin's T_cap)");
+    if (conditional(h) && (!h->cond.d_xref || (int64_t)h->t >= h->cond.T))
+        return fail(SMC_ESTATE, "smc_step: the reference of the conditional handle ends before this step (smc_set_reference's T)");
     h->win.k = 0;   // an uncommitted window is dropped
     HIPCHK(hipSetDevice(h->device));
     h->v.y = nullptr; h->v.trace_logmu = nullptr; h->v.trace_ess = nullptr;
@@ -645,6 +674,7 @@ static int launch_window_steps(smc_handle h, int k) {
 }
 extern "C" int smc_step_window(smc_handle h, const double* y, int k, double* logmu, double* ess) {
     if (!h || !y) return fail(SMC_EINVAL, "smc_step_window: NULL argument");
+    if (conditional(h)) return cond_refuse("smc_step_window");
     if (!h->inited) return fail(SMC_ESTATE, "smc_step_window: call smc_init (bootstrap_filter) first");
     if (history_armed(h)) return history_refuse("smc_step_window");
     if (k < 1 || k > WIN_MAX) return fail(SMC_EINVAL, "smc_step_window: 1 <= k <= 64");
@@ -680,6 +710,7 @@ extern "C" int smc_step_window(smc_handle h, const double* y, int k, double* log
 }
 extern "C" int smc_step_commit(smc_handle h, int j) {
     if (!h) return fail(SMC_EINVAL, "smc_step_commit: NULL handle");
+    if (conditional(h)) return cond_refuse("smc_step_commit");
     if (history_armed(h)) return history_refuse("smc_step_commit");
     if (h->win.k == 0) return fail(SMC_ESTATE, "smc_step_commit: no window pending (smc_step_window)");
     if (j < 0 || j > h->win.k) return fail(SMC_EINVAL, "smc_step_commit: 0 <= j <= steps of the window");

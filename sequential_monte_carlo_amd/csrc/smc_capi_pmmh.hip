@@ -65,6 +65,7 @@ extern "C" int smc_pmmh_rejuvenate(smc_handle h, smc_handle main, const double* 
                                    const double* scales, int chain, const uint64_t* filter_seeds, uint64_t move_seed,
                                    double* theta, double* logZ, uint8_t* accepted, int64_t* filters_run) {
     if (!h || !y || !chol || !scales || !filter_seeds || !theta || !logZ) return fail(SMC_EINVAL, "smc_pmmh_rejuvenate: NULL argument");
+    if (conditional(h) || (main && conditional(main))) return cond_refuse("smc_pmmh_rejuvenate");
     if (!h->pm.cfg) return fail(SMC_ESTATE, "smc_pmmh_rejuvenate: smc_pmmh_configure has not been called");
     if (T <= 0 || chain < 0) return fail(SMC_EINVAL, "smc_pmmh_rejuvenate: bad T or chain");
     if (history_armed(h) || (main && history_armed(main))) return history_refuse("smc_pmmh_rejuvenate");

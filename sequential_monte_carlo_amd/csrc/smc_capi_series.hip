@@ -94,6 +94,7 @@ extern "C" int smc_log_likelihood(smc_handle h, const double* y, int64_t T, doub
                                   double* ess_trace) {
     if (!h || !y) return fail(SMC_EINVAL, "smc_log_likelihood: NULL argument");
     if (T <= 0) return fail(SMC_EINVAL, "smc_log_likelihood: T must be positive");
+    if (conditional(h)) return cond_refuse("smc_log_likelihood");
     if (!h->have_params) return fail(SMC_ESTATE, "smc_log_likelihood: smc_set_params has not been called");
     if (history_armed(h)) return history_refuse("smc_log_likelihood");
     h->win.k = 0;   // an uncommitted window is dropped
@@ -145,6 +146,7 @@ extern "C" int smc_log_likelihood(smc_handle h, const double* y, int64_t T, doub
 extern "C" int smc_time_step_kernel(smc_handle h, const double* y, int64_t T, int nsample, double* avg_ms,
                                     double* min_ms) {
     if (!h || !y || T < 2 || nsample < 1) return fail(SMC_EINVAL, "smc_time_step_kernel: bad argument");
+    if (conditional(h)) return cond_refuse("smc_time_step_kernel");
     if (!h->have_params) return fail(SMC_ESTATE, "smc_time_step_kernel: smc_set_params has not been called");
     if (history_armed(h)) return history_refuse("smc_time_step_kernel");
     if (series_has_gap(h, y, T)) return fail(SMC_EINVAL, "smc_time_step_kernel: the series holds a NaN and the handle reads NaN as missing (SMC_FLAG_NAN_MISSING); it times the ordinary step");

@@ -50,6 +50,7 @@ extern "C" int smc_history_begin(smc_handle h, int64_t T_cap) {
     h->hist.d_w = slab + nw * (size_t)h->d * (size_t)T_cap;
     h->hist.cap = T_cap;
     h->hist.len = 0;
+    h->hist.walk_M = 0;
     h->hist.armed = true;
     return SMC_OK;
 }
@@ -371,7 +372,9 @@ extern "C" int smc_sample_paths(smc_handle h, int64_t M, uint64_t path_seed, con
         k.xs_rows = xs ? d : 0;
         k.o_xs = p.take(xs ? T * d * pw * 8 : 0);
     });
+    h->hist.walk_M = 0;   // (a walk that fails leaves nothing to gather through)
     if (rc || (rc = finish_elapsed(h))) return rc;
+    h->hist.walk_M = M; h->hist.walk_T = (int64_t)T; h->hist.walk_idx = k.o_idx;   // smc_reference_from_paths
     const char* base = h->hist.d_path;
     if (idx) HIPCHK(hipMemcpy(idx, base + k.o_idx, T * pw * 4, hipMemcpyDeviceToHost));
     if (xs) HIPCHK(hipMemcpy(xs, base + k.o_xs, T * d * pw * 8, hipMemcpyDeviceToHost));
@@ -390,6 +393,7 @@ extern "C" int smc_rb_sample_paths(smc_handle h, const double* y, int64_t T, int
                                 "along a path has no rule for a gap yet");
     // (the two gammas are UCSV3D's: nh1, nh2; a path carries (lse, lsn, mu, tau) and records (lse, lsn))
     Walk k{"smc_rb_sample_paths", "a gamma", MODEL_UCSV3D, 4, 8, y, T};
+    h->hist.walk_M = 0;   // (the block is laid out anew)
     const size_t nt = (size_t)h->v.ntheta;
     int mchunk = 0;   // chunks of paths (the summary)
     size_t pw = 0, o_tmean = 0, o_tvar = 0, o_tdraw = 0, o_stmp = 0, o_out = 0;

@@ -127,7 +127,13 @@ struct smc_filter_s {
         size_t tmp_bytes = 0;
         char* d_path = nullptr;                // the backward walk (smc_sample_paths, or smc_rb_sample_paths on a MODEL_UCSV_RB handle), its own
         size_t path_bytes = 0;                 //   block: cur | pmax | psum | rmax | rows | dead | counts | idx [T][ntheta][M] | the caller's tail
+        int64_t walk_M = 0, walk_T = 0;        // the last smc_sample_paths walk over this record (0: none): paths per filter, steps, and where
+        size_t walk_idx = 0;                   //   its index block starts in d_path (smc_reference_from_paths gathers through it)
     } hist;
+    struct {   // the conditional particle filter (SMC_FLAG_CONDITIONAL; smc_capi_cond.hip): the reference, an allocation of its own
+        double* d_xref = nullptr;              // [T][d][ntheta]; nullptr: none yet (a recycled bundle never carries one)
+        int64_t T = 0;
+    } cond;
     struct {   // forecasts (smc_capi_forecast.hip): ONE block, grown on demand and freed by smc_destroy
         char* d_buf = nullptr;                 // clouds [block][d + 3][ntheta][npad] | summary scratch | results of every horizon
         size_t bytes = 0;
@@ -175,6 +181,10 @@ struct GapScope {
     GapScope(smc_filter_s* hh, const double* y, int64_t T) : h(hh) { h->gap_y = series_has_gap(h, y, T) ? y : nullptr; }
     ~GapScope() { h->gap_y = nullptr; }
 };
+// the conditional particle filter (include/smc_hip.h): the handle runs the COND kernels, one launch per step
+inline bool conditional(const smc_filter_s* h) { return (h->flags & SMC_FLAG_CONDITIONAL) != 0; }
+// the refusal of the calls that would launch kernels without the override (or read a conditional logZ as a likelihood)
+int cond_refuse(const char* who);
 hipError_t do_finalize(smc_filter_s* h, int first_emit, uint32_t t_emit);
 hipError_t ensure_breaks(smc_filter_s* h, uint32_t t, uint32_t t_end);
 int ensure_y(smc_handle h, int64_t T);

@@ -810,8 +810,14 @@ __device__ __forceinline__ int logical_segment(int bid, int nseg) {
 // ---------------------------------------------------------------------------------------------
 // MISS: the missing first step (smc_spec.h "missing observations"; launched by the host when the handle has SMC_FLAG_NAN_MISSING
 // and y is NaN): model_missing_step, log-weight +0.0 - y is never read.
-template <int MODEL, int THREADS, int NP, bool MISS = false>
-__global__ __launch_bounds__(THREADS) void k_init(FilterView v, int nxt, double y) {
+// COND = a trailing argument is given (k_init<.., false, const double*>; smc_spec.h "the conditional particle filter", handles with
+// SMC_FLAG_CONDITIONAL): slot k*_0 takes the reference row xrow [d][ntheta] and its log-weight, ancestor k*_0 (the identity, as
+// every slot's).  The row is an argument of the COND kernels alone, not a field of the view and not a parameter of the others: either
+// would move kernel arguments in instantiations that exist.  Without it: the code as it was.
+template <int MODEL, int THREADS, int NP, bool MISS = false, class... XROW>
+__global__ __launch_bounds__(THREADS) void k_init(FilterView v, int nxt, double y, XROW... xrow) {
+    constexpr bool COND = sizeof...(XROW) != 0;
+    static_assert(sizeof...(XROW) <= 1 && !(COND && (MISS || model_marginal<MODEL>::value)), "conditional steps: one row; bootstrap families, no gaps");
     constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint64_t* scr = (uint64_t*)smem;
@@ -821,6 +827,15 @@ __global__ __launch_bounds__(THREADS) void k_init(FilterView v, int nxt, double 
     const uint32_t stream = v.stream[th];
     const int64_t seg0 = (int64_t)sb * v.seg;
     double lw[NP][2];
+    double xr[D] = {}, lwr = 0.0;   // COND: the reference row, its log-weight and the retained slot (workgroup-uniform)
+    int64_t kst = -1;
+    if constexpr (COND) {
+        const double* row = (xrow, ...);
+#pragma unroll
+        for (int c = 0; c < D; ++c) xr[c] = row[(size_t)c * v.ntheta + th];
+        kst = (int64_t)cond_slot(v.seed, stream, 0u, (uint32_t)v.n);
+        lwr = model_logobs<MODEL>(prm, xr, y);
+    }
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
         const int pl = tid + k * THREADS;            // pair within segment
@@ -844,6 +859,12 @@ __global__ __launch_bounds__(THREADS) void k_init(FilterView v, int nxt, double 
             } else {
                 model_initial<MODEL>(prm, zz, xn[j]);
                 lw[k][j] = valid ? model_logobs<MODEL>(prm, xn[j], y) : nan_mask();
+            }
+            if constexpr (COND) {   // one compare per particle, selected in place (k* < n: never a masked slot)
+                const bool keep = (i0 + j) == kst;
+#pragma unroll
+                for (int c = 0; c < D; ++c) xn[j][c] = keep ? xr[c] : xn[j][c];
+                lw[k][j] = keep ? lwr : lw[k][j];
             }
         }
 #pragma unroll
@@ -913,15 +934,22 @@ struct StepEarly {
 // transition and the observation density; everything else is the step's.  Instantiated by k_step_miss only, which the host
 // launches when the handle has SMC_FLAG_NAN_MISSING and the step's observation is NaN - the observation is uniform over the
 // launch, so there is no branch, and y is never read.
-template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS, bool GTAB = false, int RPT = 1, bool GUIDED = false, bool BYV = false, bool MISS = false>
+// COND: the conditional step (smc_spec.h "the conditional particle filter"; k_step_cond only, the launches of a handle with
+// SMC_FLAG_CONDITIONAL): the reference row xrow [d][ntheta] (the kernel's last argument) is loaded before the draws, the retained
+// slot k*_t drawn under the gathers; behind the transition and the observation density one compare per pair finds the wave that
+// holds the slot, which selects the row, its log-weight and the ancestor k*_{t-1} in place.
+template <int MODEL, int THREADS, int NP, bool MULTI, bool SYS, bool GTAB = false, int RPT = 1, bool GUIDED = false, bool BYV = false, bool MISS = false,
+          bool COND = false>
 __device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& ea, uint64_t seed, uint32_t t, uint32_t stream0, int nseg, int cur, int emit_prev,
-                                          double yval, const Params* prm0, char* smem) {
+                                          double yval, const Params* prm0, char* smem, const double* xrow = nullptr) {
     const unsigned long long t_entry = SMC_CLOCK();
     static_assert(!GTAB || MULTI, "global table: multi-segment launches");
     static_assert(RPT == 1 || (RPT == 2 && MULTI && !GTAB), "two records per thread: multi-segment launches");
     constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
     static_assert(!(GUIDED && model_marginal<MODEL>::value), "marginal families have no proposals");
     static_assert(!(MISS && GUIDED), "a missing step has no proposal");
+    static_assert(!(COND && (MISS || GUIDED || SYS || BYV || model_marginal<MODEL>::value)),
+                  "conditional steps: bootstrap families, multinomial resampling, no gaps, through the pointers");
     constexpr int SEG = 2 * NP * THREADS;
     constexpr int NQ = 2 * NP;   // particles per thread
     constexpr int NSTAGE = nstage_for(SEG);
@@ -943,6 +971,18 @@ __device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& 
     PropRow prw;
     if constexpr (GUIDED) prw = v.prop[th];
     const uint32_t n32 = ea.n32;
+    // COND: the reference row of this step, loaded early like the break points and the records below.  One state coordinate: through
+    // the VECTOR memory path (the offset sits in a vector register) - the row is new at every step, a miss all the way to HBM, and
+    // as a scalar load its wait stands in front of the first draw with the waits for the stream id and the parameter row.  Three
+    // coordinates would hold six vector registers across the kernel (UCSV3D 512 x 1, two records per thread: 129 of them, one
+    // workgroup per CU): scalar loads there, and the wait is paid
+    double xr[D] = {};
+    if constexpr (COND) {
+        uint32_t lane0 = 0u;
+        if constexpr (D == 1) asm volatile("" : "+v"(lane0));
+#pragma unroll
+        for (int c = 0; c < D; ++c) xr[c] = xrow[(size_t)c * v.ntheta + th + lane0];
+    }
     const uint64_t* Cprev = ea.C + (size_t)th * ((size_t)nseg * SEG);   // (v.npad = nseg * SEG)
     const double* xprev = v.x[cur];
     uint64_t* scr;
@@ -1317,6 +1357,11 @@ __device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& 
         for (int c = 0; c < D; ++c) xp[i][c] = SMC_ABL(v, 1) ? 0.25 * (double)(a & 7) : xprev[((size_t)c * v.ntheta + th) * v.npad + a];
     }
 
+    // COND: the retained slot k*_t (workgroup-uniform, on the scalar unit), drawn HERE, under the latency of the gathers just issued:
+    // ten dependent Philox rounds ahead of the resampling draws cost every wave a microsecond of its start
+    uint32_t kst = 0;
+    if constexpr (COND) kst = cond_slot(seed, stream, t, n32);
+
     // ---- x[i] = rand(transition(xp[i])); logw[i] = logpdf(observation(x[i]), y) ---------------
     double lw[NP][2];
 #pragma unroll
@@ -1343,6 +1388,23 @@ __device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& 
             } else {
                 model_transition<MODEL>(prm, xp[2 * k + j], zz, xn[j]);
                 lw[k][j] = model_logobs<MODEL>(prm, xn[j], y);
+            }
+        }
+        if constexpr (COND) {
+            // one compare per pair; the ONE wave of the filter that holds the retained slot computes the row's log-weight (and, for
+            // recorded ancestors, the retained slot of the step before) and selects in place - k* < n: never a masked child
+            if (__builtin_amdgcn_ballot_w64((kst & ~1u) == i0)) {
+                asm volatile("; retained slot");
+                const double lwr = model_logobs<MODEL>(prm, xr, y);
+                const uint32_t kprev = v.anc ? cond_slot(seed, stream, t - 1u, n32) : 0u;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const bool keep = (i0 + j) == kst;
+#pragma unroll
+                    for (int c = 0; c < D; ++c) xn[j][c] = keep ? xr[c] : xn[j][c];
+                    lw[k][j] = keep ? lwr : lw[k][j];
+                    anc[2 * k + j] = keep ? kprev : anc[2 * k + j];
+                }
             }
         }
         if (ragged) {   // masked children: NaN weight, zero state
@@ -1429,6 +1491,18 @@ __global__ __launch_bounds__(THREADS) void k_step_miss(uint64_t seed, uint32_t t
     const StepEarly ea{brow, rec0, rec1, C, n32};
     step_body<MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, false, false, true>(v, ea, seed, t, stream0, (int)(pack & 0xffffu), (int)(pack >> 16 & 1u),
                                                                              (int)(pack >> 17), yval, &prm0, smem);
+}
+
+// the conditional step: the same argument block again and the reference row of the step behind it; stream id and parameter row
+// through the view's pointers
+template <int MODEL, int THREADS, int NP, bool MULTI, bool GTAB = false, int RPT = 1>
+__global__ __launch_bounds__(THREADS) void k_step_cond(uint64_t seed, uint32_t t, uint32_t stream0, const uint64_t* __restrict__ brow, const void* rec0, const void* rec1,
+                                                       const uint64_t* C, uint32_t pack, uint32_t n32, double yval, Params prm0, FilterView v,
+                                                       const double* xrow) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const StepEarly ea{brow, rec0, rec1, C, n32};
+    step_body<MODEL, THREADS, NP, MULTI, false, GTAB, RPT, false, false, false, true>(v, ea, seed, t, stream0, (int)(pack & 0xffffu), (int)(pack >> 16 & 1u),
+                                                                                      (int)(pack >> 17), yval, &prm0, smem, xrow);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -98,5 +98,10 @@ template <int MODEL> hipError_t launch_resident_m(const FilterView& v, int T, St
 template <int MODEL> hipError_t launch_window_m(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
 template <int MODEL> hipError_t launch_resident_gm(const FilterView& v, int T, StepRec* recs, hipStream_t s);
 template <int MODEL> hipError_t launch_window_gm(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
+// the conditional particle filter (smc_spec.h; handles with SMC_FLAG_CONDITIONAL): the COND kernels, translation units of their
+// own (smc_model.hip with -DSMC_COND=1: build/cond<model>.o), for the families of by_density_model.  One launch per step only;
+// xrow [d][ntheta]: the reference row of the step on the device (xref + t d ntheta)
+template <int MODEL> hipError_t launch_init_c(const FilterView& v, Geo g, int nxt, double y, const double* xrow, hipStream_t s);
+template <int MODEL> hipError_t launch_step_c(const FilterView& v, Geo g, const StepHot& hot, const double* xrow, hipStream_t s);
 
 }  // namespace smc

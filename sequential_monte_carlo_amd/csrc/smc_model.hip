@@ -21,8 +21,70 @@
 #define SMC_MISSING 0
 #endif
 #define SMC_M (SMC_MISSING != 0)
+// -DSMC_COND=1: the COND kernels alone (handles with SMC_FLAG_CONDITIONAL; smc_spec.h "the conditional particle filter"):
+// build/cond<model>.o with launch_init_c and launch_step_c - one launch per step, multinomial resampling, the filter's stream id
+// and rows through the view's pointers.  Nothing else of this file is compiled into those objects.
+#ifndef SMC_COND
+#define SMC_COND 0
+#endif
 
 namespace smc {
+
+#if SMC_COND
+template <int THREADS, int NP>
+static hipError_t init_c_t(const FilterView& v, int nxt, double y, const double* xrow, hipStream_t s) {
+    const size_t lds = scr_words(THREADS, NP) * 8;
+    hipLaunchKernelGGL((k_init<SMC_MODEL, THREADS, NP, false, const double*>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, nxt, y, xrow);
+    return hipGetLastError();
+}
+template <int THREADS, int NP, bool MULTI, bool GTAB, int RPT>
+static hipError_t step_c_launch(const FilterView& v, const StepHot& hot, const double* xrow, int emit_prev, size_t lds, hipStream_t s) {
+    static std::atomic<bool> raised[16] = {};   // per instantiation and device
+    hipError_t e = raise_lds_limit(k_step_cond<SMC_MODEL, THREADS, NP, MULTI, GTAB, RPT>, lds, raised);
+    if (e != hipSuccess) return e;
+    const StepLead& l = hot.lead;
+    hipLaunchKernelGGL((k_step_cond<SMC_MODEL, THREADS, NP, MULTI, GTAB, RPT>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, l.seed, l.t, l.stream0,
+                       l.brow, l.rec0, l.rec1, l.C, step_pack(hot.nseg, hot.cur, emit_prev), l.n32, hot.yval, hot.prm0, v, xrow);
+    return hipGetLastError();
+}
+// (the geometries of step_sys_t below)
+template <int THREADS, int NP>
+static hipError_t step_c_t(const FilterView& v, const StepHot& hot, const double* xrow, hipStream_t s) {
+    if (v.tabD) return step_c_launch<THREADS, NP, true, true, 1>(v, hot, xrow, 0, step_lds_bytes(0, THREADS, NP, true), s);
+    const size_t lds = step_lds_bytes(v.nseg_p2, THREADS, NP, v.nseg > 1);
+    if (v.nseg_p2 > THREADS) return step_c_launch<THREADS, NP, true, false, 2>(v, hot, xrow, hot.emit_prev, lds, s);
+    return v.nseg > 1 ? step_c_launch<THREADS, NP, true, false, 1>(v, hot, xrow, hot.emit_prev, lds, s)
+                      : step_c_launch<THREADS, NP, false, false, 1>(v, hot, xrow, hot.emit_prev, lds, s);
+}
+#define SMC_COND_GEO_SWITCH(FN, ...)                                              \
+    switch (g.threads * 8 + g.np) {                                               \
+    case 64 * 8 + 2: return FN<64, 2>(__VA_ARGS__);                               \
+    case 128 * 8 + 1: return FN<128, 1>(__VA_ARGS__);                             \
+    case 128 * 8 + 2: return FN<128, 2>(__VA_ARGS__);                             \
+    case 128 * 8 + 4: return FN<128, 4>(__VA_ARGS__);                             \
+    case 256 * 8 + 1: return FN<256, 1>(__VA_ARGS__);                             \
+    case 256 * 8 + 2: return FN<256, 2>(__VA_ARGS__);                             \
+    case 256 * 8 + 4: return FN<256, 4>(__VA_ARGS__);                             \
+    case 512 * 8 + 1: return FN<512, 1>(__VA_ARGS__);                             \
+    case 512 * 8 + 2: return FN<512, 2>(__VA_ARGS__);                             \
+    case 512 * 8 + 4: return FN<512, 4>(__VA_ARGS__);                             \
+    case 1024 * 8 + 1: return FN<1024, 1>(__VA_ARGS__);                           \
+    case 1024 * 8 + 2: return FN<1024, 2>(__VA_ARGS__);                           \
+    case 1024 * 8 + 4: return FN<1024, 4>(__VA_ARGS__);                           \
+    }                                                                             \
+    return hipErrorInvalidValue;
+template <>
+hipError_t launch_init_c<SMC_MODEL>(const FilterView& v, Geo g, int nxt, double y, const double* xrow, hipStream_t s) {
+    if (!xrow) return hipErrorInvalidValue;
+    SMC_COND_GEO_SWITCH(init_c_t, v, nxt, y, xrow, s)
+}
+template <>
+hipError_t launch_step_c<SMC_MODEL>(const FilterView& v, Geo g, const StepHot& hot, const double* xrow, hipStream_t s) {
+    if (!xrow || v.systematic) return hipErrorInvalidValue;
+    SMC_COND_GEO_SWITCH(step_c_t, v, hot, xrow, s)
+}
+}  // namespace smc
+#else
 
 #if !SMC_G
 template <int THREADS, int NP>
@@ -250,3 +312,4 @@ hipError_t SMC_LAUNCH_WINDOW<SMC_MODEL>(const FilterView& v, int T, StepRec* rec
 }
 
 }  // namespace smc
+#endif   // !SMC_COND

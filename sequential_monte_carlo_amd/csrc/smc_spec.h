@@ -33,6 +33,7 @@ constexpr uint32_t SLOT_SYS = 10u;       // the one uniform of a systematic resa
 constexpr uint32_t SLOT_BREAK = 16u;     // block break points: 16+2i normal, 17+2i uniform, i < 8; pair = block
 constexpr uint32_t SLOT_PMMH_Z = 32u;    // PMMH proposal normals of a parameter particle: pair k holds z[2k], z[2k+1]
 constexpr uint32_t SLOT_PMMH_U = 33u;    // the uniform of its accept test
+constexpr uint32_t SLOT_COND = 38u;      // the retained slot of a conditional step ("the conditional particle filter" below), pair 0
 constexpr uint32_t SLOT_OUTER = 34u;     // the pick numbers of resample!(smc) / resample!(ibis), stream OUTER_STREAM
 constexpr uint32_t OUTER_STREAM = 0xFFFFFFFEu;   // Philox stream id of the outer level (theta particles use 0 .. M-1, simulate() 0xFFFFFFFF)
 constexpr int MAX_DTHETA = 8;            // parameter dimension of the samplers (SMC_MAX_DTHETA)
@@ -1253,6 +1254,38 @@ SMC_HD double rb_trend_normal(uint64_t seed, int64_t p, uint32_t stream, uint32_
     double z0, z1;
     box_muller(draw(seed, (uint32_t)(p >> 1), stream, t, SLOT_RB_TREND), z0, z1);
     return (p & 1) ? z1 : z0;
+}
+
+// ---- the conditional particle filter (opt-in per handle: SMC_FLAG_CONDITIONAL) ---------------------------------
+// Andrieu, Doucet and Holenstein (2010): the bootstrap filter with ONE particle of every step pinned to a reference trajectory
+// xref [T][d].  With one backward-simulated path drawn from its record it is a Markov kernel on trajectories that leaves
+// p(x_1:T | y_1:T, theta) invariant for any n >= 2 (particle Gibbs with backward simulation; Whiteley; Lindsten and Schoen).
+// At every time index t, the first step included, the step is the ordinary bootstrap step - the same Philox slots: the other
+// slots' ancestors, the state normals in the pair convention, the masking of a ragged last segment, the segment normalisation,
+// the records, the emission, the time index - with one slot overridden:
+//   k*_t = cond_slot(seed, stream, t, n) = mulhi64(u, n),  u = v[1] << 32 | v[0] of draw(seed, 0, stream, t, SLOT_COND)
+//          one draw per filter and step, workgroup-uniform; k*_t < n, never a masked child
+//   x_t^{k*}    = xref[t], copied bit for bit (the transition of that slot is computed and discarded, its normal with it)
+//   logw_t^{k*} = model_logobs(prm, xref[t], y_t)
+//   ancestor    = k*_{t-1}, recomputed from the draw of step t - 1 (k*_0 at t = 0); recorded with SMC_FLAG_ANCESTORS only
+// WHY THE SLOT IS RANDOM.  The multinomial resampler is block-sorted: child j takes the j-th order statistic of n uniforms.
+// Overriding a FIXED slot (say the last) leaves the n - 1 smallest of n draws, which are not n - 1 iid draws; dropping a
+// uniformly random slot leaves n - 1 iid draws as a multiset, and only the multiset matters, because backward simulation
+// ignores labels.  Bootstrap families with a transition density only (LG1D, SV1D, UCSV3D), multinomial resampling, no gaps.
+// The draw is workgroup-uniform, so the kernels want it on the scalar unit: philox4x32_10's words by plain integer operators
+// (its xor3 is v_bitop3_b32, a vector instruction, and drags the ten rounds - 64 quarter-rate multiplies per wave - into the
+// vector unit with it).  The same integers; tests/test_conditional_host.py pins cond_slot to smc_host_philox4x32_10.
+SMC_HD uint32_t cond_slot(uint64_t seed, uint32_t stream, uint32_t t, uint32_t n) {
+    uint32_t c0 = 0u, c1 = stream, c2 = t, c3 = SLOT_COND, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return (uint32_t)mulhi64(((uint64_t)c1 << 32) | c0, (uint64_t)n);
 }
 
 }  // namespace smc

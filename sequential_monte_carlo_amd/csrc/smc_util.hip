@@ -530,6 +530,24 @@ extern "C" int smc_host_filter_steps(int model_id, const double* raw, int kind, 
     });
     return SMC_OK;
 }
+// the conditional particle filter (include/smc_hip.h): the retained slot and the log-weight of the reference row on the host
+extern "C" int smc_host_conditional_slot(uint64_t seed, uint32_t stream, uint32_t t, int64_t n_x, int64_t* k) {
+    if (!k || n_x < 1 || n_x > ((int64_t)1 << 31)) return fail(SMC_EINVAL, "smc_host_conditional_slot: bad argument");
+    *k = (int64_t)cond_slot(seed, stream, t, (uint32_t)n_x);
+    return SMC_OK;
+}
+extern "C" int smc_host_logobs(int model_id, const double* raw, const double* x, double y, double* out) {
+    if (!x || !out) return fail(SMC_EINVAL, "smc_host_logobs: NULL argument");
+    Params P;
+    PropRow R;
+    if (!has_density(model_id) || !filter_step_params(model_id, raw, PROP_NONE, nullptr, P, R))
+        return fail(SMC_EINVAL, "smc_host_logobs: bad model or row (the families with an observation density of the state: LG1D, SV1D, UCSV3D)");
+    (void)by_density_model(model_id, [&](auto M) {
+        *out = model_logobs<decltype(M)::value>(P, x, y);
+        return hipSuccess;
+    });
+    return SMC_OK;
+}
 template <int MODEL>
 __global__ void k_filter_steps(Params P, PropRow R, int guided, int first, int miss, const double* xp, const double* z, double y, int64_t n, double* x,
                                double* logw) {

@@ -6,6 +6,7 @@
     bootstrap_filter_(x, w, y, model)    -> (logmu, w, ess)     particles.jl:107-129   ("bootstrap_filter!")
     log_likelihood(N, y, model)          -> (x, w, logZ)        particles.jl:132-147
     smoother(N, y, model)                -> (x, w, logZ, s)     (no counterpart: the FFBS particle smoother)
+    ParticleGibbs(N, y, model)           -> sampler             (no counterpart: the conditional particle filter)
     forecast(x, w, H)                    -> dict                (no counterpart: the cloud propagated H steps ahead)
     particle_filter(N, y1, model, proposal)       -> (x, w, logmu)     particles.jl:28-52
     particle_filter_(x, w, y, model, proposal)    -> (logmu, w, ess)   particles.jl:54-84    ("particle_filter!")
@@ -94,9 +95,11 @@ def trend_moments(mean, var):
 class _Filters:
     """Device state shared by the Particles / Weights views of one bootstrap_filter call."""
 
-    def __init__(self, N, models, seed, seg, device, streams, ancestors, resampler="multinomial", proposal=None, rows=None, missing=False):
+    def __init__(self, N, models, seed, seg, device, streams, ancestors, resampler="multinomial", proposal=None, rows=None, missing=False,
+                 conditional=False):
         """rows=(model id, [n_theta][n_raw] parameter rows): a batch given as rows instead of `models` (then None)
-        missing=True: a NaN observation is a missing one (FLAG_NAN_MISSING)"""
+        missing=True: a NaN observation is a missing one (FLAG_NAN_MISSING)
+        conditional=True: the conditional particle filter (FLAG_CONDITIONAL): the caller sets the reference"""
         if rows is not None:
             mid, raw = int(rows[0]), np.ascontiguousarray(rows[1], dtype=np.float64)
         else:
@@ -105,7 +108,7 @@ class _Filters:
         if resampler not in ("multinomial", "systematic"):
             raise ValueError("resampler must be 'multinomial' (the reference's law) or 'systematic' (opt-in)")
         flags = (_lib.FLAG_ANCESTORS if ancestors else 0) | (_lib.FLAG_SYSTEMATIC if resampler == "systematic" else 0) | (
-            _lib.FLAG_NAN_MISSING if missing else 0)
+            _lib.FLAG_NAN_MISSING if missing else 0) | (_lib.FLAG_CONDITIONAL if conditional else 0)
         self.h = _lib.Handle(mid, raw.shape[0], N, seg=seg, seed=seed, device=device, flags=flags)
         self.h.set_params(raw)
         if streams is not None:
@@ -397,8 +400,27 @@ def _run_recorded(h, y):
     return lm, es, h.logZ()[0]
 
 
+def _reference_in(reference, f, T):
+    """a reference trajectory as the callers give it - [T] or [T][d]; with a list of models a batch axis after T: [T][n_theta] or
+    [T][n_theta][d], the shape of s["paths"][:, ..., 0, ...] - as the handle takes it: [T][d][n_theta]"""
+    r = np.asarray(reference, dtype=np.float64)
+    d, nt = f.h.d, f.h.n_theta
+    want = (T,) + (() if f.single else (nt,)) + (() if d == 1 else (d,))
+    if r.shape != want:
+        raise ValueError("reference must have the shape %r (time, then the batch, then the state), not %r" % (want, r.shape))
+    return np.ascontiguousarray(np.moveaxis(r.reshape(T, nt, d), 1, -1))
+
+
+def _reference_out(xref, single):
+    """[T][d][n_theta] -> [T] or [T][d]; a batch axis follows T"""
+    r = np.moveaxis(xref, 1, -1)                                       # [T][n_theta][d]
+    if r.shape[-1] == 1:
+        r = r[..., 0]
+    return r[:, 0] if single else r
+
+
 def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="multinomial", proposal=None, weights=False, rows=None,
-             paths=0, path_seed=None, path_counts=None, smooth=True, missing=False):
+             paths=0, path_seed=None, path_counts=None, smooth=True, missing=False, reference=None):
     """x, w, logZ, s = smoother(N, y, model): the particle filter of log_likelihood run step by step with its clouds recorded on
     the device, then the FFBS backward pass over them (forward filtering, backward smoothing).  x, w, logZ are the
     filter's, as log_likelihood returns them; s describes p(x_t | y_1:T):
@@ -418,14 +440,20 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
     smoother of this kind (its state rows have no transition density): rb_smoother is its smoother.
     rows=(model id, parameter rows [n_theta][n_raw]) with model=None: a batch given as rows (what the samplers hold).
     missing=True (opt-in): NaN entries of y are periods without an observation; s["mean"], s["var"] and the paths
-    there are the interpolated state."""
+    there are the interpolated state.
+    reference=[T] or [T][d] (a batch axis after T, as in s["paths"]): the run is the CONDITIONAL particle filter - one
+    slot of every step is pinned to that trajectory; everything returned is shaped as ever, but logZ is not a likelihood estimate.
+    One path of it (paths=1) is one sweep of particle Gibbs: ParticleGibbs keeps the handle between sweeps."""
     if seed is None:
         seed = next(_seed_counter)
-    f = _Filters(int(N), model, seed, seg, device, streams, False, resampler, proposal, rows=rows, missing=missing)
+    f = _Filters(int(N), model, seed, seg, device, streams, False, resampler, proposal, rows=rows, missing=missing,
+                 conditional=reference is not None)
     y = np.ascontiguousarray(y, dtype=np.float64).ravel()
     T, h = y.size, f.h
     if T < 1:
         raise ValueError("smoother needs at least one observation")
+    if reference is not None:
+        h.set_reference(_reference_in(reference, f, T))
     h.history_begin(T)
     try:
         lm, es, logZ = _run_recorded(h, y)
@@ -449,6 +477,72 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
     finally:
         h.history_end()
     return Particles(f), Weights(f), f.out(logZ), s
+
+
+class ParticleGibbs:
+    """pg = ParticleGibbs(N, y, model): particle Gibbs with backward simulation (Andrieu, Doucet and Holenstein 2010; Whiteley;
+    Lindsten and Schoen) for one model or a list of them (one chain each), on ONE conditional handle that lives as
+    long as the sampler.  pg.sweep() runs the conditional particle filter over y with the current path pinned, draws ONE
+    backward-simulated path per filter and adopts it on the device: a Markov kernel that leaves p(x_1:T | y_1:T, theta) invariant
+    for any N >= 2.  Alternate it with the user's own draw of theta given pg.path, handed back with pg.set_model(...).
+        reference        the starting path, [T] or [T][d] (a batch axis after T); None: one path of an unconditional
+                         smoother(paths=1, smooth=False) under sweep_seed(0)
+        pg.sweep()       -> the new path, shaped like reference; sweep k (1, 2, ...) runs under the filter seed pg.sweep_seed(k) and the
+                         path seed derived from it as smoother derives it, so smoother(..., seed=pg.sweep_seed(k), reference=previous
+                         path, paths=1) reproduces it bit for bit
+        pg.set_model(m)  a model, a list of them, or parameter rows [n_theta][n_raw]: theta for the next sweep
+        pg.path, pg.logmu, pg.ess, pg.sweeps, pg.kept   the current path; the last sweep's per-step increments and effective sample
+                         sizes; sweeps done; filters whose path was dead in the last sweep and that kept their path (0 in practice)
+    Bootstrap families with a transition density (UnivariateLinearGaussian, StochasticVolatility, UCSV), multinomial resampling."""
+
+    def __init__(self, N, y, model, reference=None, seed=None, seg=0, device=0, streams=None, rows=None):
+        self.seed = next(_seed_counter) if seed is None else int(seed)
+        self.y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        T = self.y.size
+        if T < 1:
+            raise ValueError("ParticleGibbs needs at least one observation")
+        if reference is None:
+            reference = smoother(N, self.y, model, seed=self.sweep_seed(0), seg=seg, device=device, streams=streams, rows=rows, paths=1,
+                                 smooth=False)[3]["paths"]
+            reference = reference[:, 0] if rows is None and not isinstance(model, (list, tuple)) else reference[:, :, 0]
+        self._f = _Filters(int(N), model, self.sweep_seed(1), seg, device, streams, False, rows=rows, conditional=True)
+        h = self._f.h
+        h.set_reference(_reference_in(reference, self._f, T))
+        h.history_begin(T)
+        self.sweeps, self.kept = 0, 0
+        self.logmu = self.ess = None
+
+    def sweep_seed(self, k):
+        """the filter seed of sweep k (k = 0: the unconditional start): seed + k * 0x9E3779B97F4A7C15 mod 2^64, so that every sweep
+        draws from fresh Philox counters"""
+        return (self.seed + int(k) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+    def sweep(self):
+        h = self._f.h
+        sd = self.sweep_seed(self.sweeps + 1)
+        h.reseed(sd)
+        lm, es, _ = _run_recorded(h, self.y)                           # (smc_init restarts the record)
+        h.sample_paths(1, _path_seed(sd), want_x=False)
+        self.kept = h.reference_from_paths(0)
+        self.sweeps += 1
+        pick = (lambda a: a[:, 0]) if self._f.single else (lambda a: a)
+        self.logmu, self.ess = pick(lm), pick(es)
+        return self.path
+
+    @property
+    def path(self):
+        return _reference_out(self._f.h.get_reference(), self._f.single)
+
+    def set_model(self, model):
+        if isinstance(model, np.ndarray):
+            raw = np.ascontiguousarray(model, dtype=np.float64).reshape(self._f.h.n_theta, -1)
+            self._f.h.set_params(raw)
+            self._f.raw = raw
+        else:
+            self._f.check_model(model)
+
+    def close(self):
+        self._f.h.close()
 
 
 def rb_smoother(N, y, model, paths=256, seed=None, path_seed=None, draws=False, per_path=False, path_counts=None, seg=0, device=0,
