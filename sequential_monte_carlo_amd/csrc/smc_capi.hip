@@ -32,6 +32,7 @@ int fail(int code, const std::string& msg) {
 
 // ---- geometry ------------------------------------------------------------------------------
 namespace smc {
+// (threads, np) is an instantiated geometry: the cases of SMC_GEO_SWITCH (smc_model.hip), which is the other statement of the list
 bool geo_valid(int seg, int np, Geo& g) {
     if (np != 1 && np != 2 && np != 4) return false;
     const int th = seg / (2 * np);
@@ -97,14 +98,11 @@ int cond_refuse(const char* who) {
 }
 
 // ---- kernel dispatch -------------------------------------------------------------------------
-// (a flagged handle whose observation is NaN: the missing step, smc_spec.h "missing observations" - the MISS kernels)
-// (a conditional handle: the COND kernels, with the reference row of the step as their last argument)
+// (which kernels a launch means: pick_variant, smc_host.h; a conditional handle's take the reference row of the step as their
+// last argument)
 hipError_t do_init(smc_filter_s* h, double y) {
-    if (conditional(h))
-        return by_density_model(h->model, [&](auto M) { return launch_init_c<decltype(M)::value>(h->v, h->geo, h->cur, y, h->cond.d_xref, h->stream); });
-    if (nan_missing(h) && y != y)
-        return by_model(h->model, [&](auto M) { return launch_init_m<decltype(M)::value>(h->v, h->geo, h->cur, y, h->stream); });
-    return by_model(h->model, [&](auto M) { return launch_init<decltype(M)::value>(h->v, h->geo, h->cur, y, h->stream); });
+    return by_variant<ENTRY_INIT>(h->model, pick_variant(h, ENTRY_INIT, nan_missing(h) && y != y),
+                                  [&](auto L) { return L.init(h->v, h->geo, h->cur, y, h->cond.d_xref, h->stream); });
 }
 // filters with more segments than threads per workgroup (v.tabD): the segment table of the current weights, built once (k_table;
 // emit as k_step's emit_prev: 0 nothing, 1 (logmu, ess) from the full records, 2 from the totals)
@@ -147,18 +145,14 @@ hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y, const d
         emit_prev = 0;
     }
     const StepHot hot = step_hot(h, t, emit_prev, y, y_host);
+    const double* xrow = nullptr;
     if (conditional(h)) {
         if (!h->cond.d_xref || (int64_t)t >= h->cond.T) return hipErrorInvalidValue;   // (smc_step has refused with a message)
-        const double* xrow = h->cond.d_xref + (size_t)t * (size_t)h->d * (size_t)h->v.ntheta;
-        return by_density_model(h->model, [&](auto M) { return launch_step_c<decltype(M)::value>(h->v, h->geo, hot, xrow, h->stream); });
+        xrow = h->cond.d_xref + (size_t)t * (size_t)h->d * (size_t)h->v.ntheta;
     }
     // the step API's observation, or the series' (gap_y: set only when a flagged handle's series holds a NaN)
     const bool gap = h->v.y ? (h->gap_y && h->gap_y[t] != h->gap_y[t]) : (nan_missing(h) && y != y);
-    if (gap)   // uniform over the launch: the missing step's own kernel, for a handle with a proposal too
-        return by_model(h->model, [&](auto M) { return launch_step_m<decltype(M)::value>(h->v, h->geo, hot, h->stream); });
-    if (h->v.prop_kind)   // a handle with a proposal: the guided kernels (the families smc_set_proposal accepts)
-        return by_guided_model(h->model, [&](auto M) { return launch_step_g<decltype(M)::value>(h->v, h->geo, hot, h->stream); });
-    return by_model(h->model, [&](auto M) { return launch_step<decltype(M)::value>(h->v, h->geo, hot, h->stream); });
+    return by_variant<ENTRY_STEP>(h->model, pick_variant(h, ENTRY_STEP, gap), [&](auto L) { return L.step(h->v, h->geo, hot, xrow, h->stream); });
 }
 // Break points of the multinomial resampling steps (multi-segment filters; smc_spec.h): computed by k_breaks
 // for a window of steps ahead of time - they depend on (seed, stream, t) only.  Called before every step
@@ -188,23 +182,9 @@ hipError_t ensure_breaks(smc_filter_s* h, uint32_t t, uint32_t t_end) {
     h->brk_count = cnt;
     return hipGetLastError();
 }
-static hipError_t do_window(smc_filter_s* h, int k, int bout) {
-    if (h->win.gap) {   // a flagged handle's window with a NaN in it: the kernels that test every step's observation
-        if (h->v.prop_kind)
-            return by_guided_model(h->model, [&](auto M) {
-                return launch_window_gm<decltype(M)::value>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->win.h_out, h->stream);
-            });
-        return by_model(h->model, [&](auto M) {
-            return launch_window_m<decltype(M)::value>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->win.h_out, h->stream);
-        });
-    }
-    if (h->v.prop_kind)
-        return by_guided_model(h->model, [&](auto M) {
-            return launch_window_g<decltype(M)::value>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->win.h_out, h->stream);
-        });
-    return by_model(h->model, [&](auto M) {
-        return launch_window<decltype(M)::value>(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->win.h_out, h->stream);
-    });
+static hipError_t do_window(smc_filter_s* h, int k, int bout) {   // (win.gap: a flagged handle's window with a NaN in it)
+    return by_variant<ENTRY_WINDOW>(h->model, pick_variant(h, ENTRY_WINDOW, h->win.gap),
+                                    [&](auto L) { return L.window(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->win.h_out, h->stream); });
 }
 
 hipError_t do_finalize(smc_filter_s* h, int first_emit, uint32_t t_emit) {

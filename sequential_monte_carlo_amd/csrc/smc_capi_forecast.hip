@@ -1,7 +1,7 @@
 // smc_capi_forecast.hip -- forecasts: the filtered cloud propagated H steps past the last observation (smc_spec.h "forecasts").
 // smc_forecast summarises every horizon on the device under the handle's current weights (the streaming summary kernels of
 // smc_capi_summ.hip, pointed at one horizon of the propagated cloud); smc_forecast_cloud hands the clouds themselves over.
-// The kernel: smc_forecast_kernels.h, instantiated per family by smc_model.hip and reached through by_model.
+// The kernel: smc_forecast_kernels.h, instantiated per family by smc_model.hip (the plain objects) and reached through by_variant.
 #include "smc_host.h"
 
 #include <cstdlib>
@@ -71,7 +71,7 @@ static int ensure_forecast(smc_handle h, size_t bytes) {
 static int enqueue_forecast_block(smc_handle h, const Plan& p, uint64_t seed, int64_t k0, int nk, int nk_prev) {
     double* out = (double*)h->fc.d_buf;
     const double* src = k0 == 1 ? h->v.x[h->cur] : out + (size_t)(nk_prev - 1) * p.rows * p.plane;
-    HIPCHK(by_model(h->model, [&](auto M) { return launch_forecast<decltype(M)::value>(h->v, h->geo, src, seed, (uint32_t)k0, nk, out, h->stream); }));
+    HIPCHK(by_variant<ENTRY_FORECAST>(h->model, VARIANT_PLAIN, [&](auto L) { return L.forecast(h->v, h->geo, src, seed, (uint32_t)k0, nk, out, h->stream); }));
     return SMC_OK;
 }
 

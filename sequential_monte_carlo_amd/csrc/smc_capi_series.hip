@@ -29,15 +29,9 @@ struct SeriesScope {
     ~SeriesScope() { v.want_s2 = 1; v.y = nullptr; v.trace_logmu = nullptr; v.trace_ess = nullptr; v.sum_np = v.sum_mom = 0; v.sum_q = v.sum_m = nullptr; }
 };
 
-static hipError_t do_resident(smc_filter_s* h, int T) {
-    if (h->gap_y) {   // a flagged handle's series with a NaN in it (GapScope): the kernels that test every step's observation
-        if (h->v.prop_kind)
-            return by_guided_model(h->model, [&](auto M) { return launch_resident_gm<decltype(M)::value>(h->v, T, h->d_recs, h->stream); });
-        return by_model(h->model, [&](auto M) { return launch_resident_m<decltype(M)::value>(h->v, T, h->d_recs, h->stream); });
-    }
-    if (h->v.prop_kind)
-        return by_guided_model(h->model, [&](auto M) { return launch_resident_g<decltype(M)::value>(h->v, T, h->d_recs, h->stream); });
-    return by_model(h->model, [&](auto M) { return launch_resident<decltype(M)::value>(h->v, T, h->d_recs, h->stream); });
+static hipError_t do_resident(smc_filter_s* h, int T) {   // (gap_y: a flagged handle's series with a NaN in it, GapScope)
+    return by_variant<ENTRY_RESIDENT>(h->model, pick_variant(h, ENTRY_RESIDENT, h->gap_y != nullptr),
+                                      [&](auto L) { return L.resident(h->v, T, h->d_recs, h->stream); });
 }
 // The launches of log_likelihood(N, y, model) (particles.jl:132-147) for every filter of the handle, enqueued on
 // its stream: nothing here waits for the device.  y must already be in h->d_y (ensure_y + copy by the caller).

@@ -191,7 +191,7 @@ static int summaries_once(smc_handle h, int component, const double* p, int np, 
     v.sum_np = np; v.sum_comp = component; v.sum_mom = mom ? 1 : 0;
     level_words(h, p, np, v.sum_p64);
     v.sum_q = h->summ.h_once; v.sum_m = h->summ.h_once + (size_t)QMAX * nth;
-    const hipError_t e = by_model(h->model, [&](auto M) { return launch_summ_once<decltype(M)::value>(v, h->cur, h->stream); });
+    const hipError_t e = by_variant<ENTRY_SUMM_ONCE>(h->model, VARIANT_PLAIN, [&](auto L) { return L.summ_once(v, h->cur, h->stream); });
     if (e == hipErrorInvalidValue) return SMC_OK;
     HIPCHK(e);
     HIPCHK(hipStreamSynchronize(h->stream));

@@ -1,5 +1,6 @@
 // smc_host.h -- what the host-side translation units of libsmchip.so share: the error string behind smc_last_error(), HIPCHK,
 // the filter handle, and the few helpers that cross files.  Internal: not installed, not part of the ABI (include/smc_hip.h).
+// Which kernel variant a launch of a handle means: pick_variant, here.
 // The entry points on a handle: smc_capi.hip (core), smc_capi_series.hip, smc_capi_summ.hip, smc_capi_pmmh.hip,
 // smc_capi_slots.hip, smc_capi_smooth.hip, smc_capi_forecast.hip; without one: smc_util.hip.
 #pragma once
@@ -183,6 +184,16 @@ struct GapScope {
 };
 // the conditional particle filter (include/smc_hip.h): the handle runs the COND kernels, one launch per step
 inline bool conditional(const smc_filter_s* h) { return (h->flags & SMC_FLAG_CONDITIONAL) != 0; }
+// The ONE place that decides which kernels a launch of this handle means: the variant whose object serves entry (LAUNCH_OBJECT,
+// smc_launch.h; NO_OBJECT: the handle has no such launch).  gap: this launch covers a missing observation - the step's own is
+// NaN, or the series / window of a resident launch holds one (the caller knows from where); false for every unflagged handle.
+// Conditional wins; a gap step is the missing step, with a proposal too (LAUNCH_OBJECT says so).
+inline int pick_variant(const smc_filter_s* h, int entry, bool gap) {
+    using namespace smc;
+    const bool guided = h->v.prop_kind != 0;   // (smc_set_proposal: the families of by_guided_model)
+    const int variant = conditional(h) ? VARIANT_COND : gap ? (guided ? VARIANT_MISSING_GUIDED : VARIANT_MISSING) : guided ? VARIANT_GUIDED : VARIANT_PLAIN;
+    return LAUNCH_OBJECT[variant][entry];
+}
 // the refusal of the calls that would launch kernels without the override (or read a conditional logZ as a likelihood)
 int cond_refuse(const char* who);
 hipError_t do_finalize(smc_filter_s* h, int first_emit, uint32_t t_emit);

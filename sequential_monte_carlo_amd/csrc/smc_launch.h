@@ -1,5 +1,6 @@
-// smc_launch.h -- launch entry points, one explicit specialisation set per model family
-// (smc_model.hip is compiled once per model with -DSMC_MODEL=<id>, in parallel).
+// smc_launch.h -- the launch entry points of the kernel objects: Launch<MODEL, VARIANT>, one explicit instantiation per
+// (variant, model family) pair of LAUNCH_FAMILIES (smc_model.hip is compiled once per pair with -DSMC_VARIANT=<id>
+// -DSMC_MODEL=<id>, in parallel), and by_variant, which turns the two run-time ids into that type.
 #pragma once
 #include "smc_kernels.h"
 #include "smc_resident.h"
@@ -9,7 +10,7 @@
 namespace smc {
 
 // The ONE place that knows the list of model families: turns the runtime id into a compile-time tag and calls f with it,
-//     by_model(id, [&](auto M) { return launch_step<decltype(M)::value>(...); })
+//     by_model(id, [&](auto M) { return path_step<decltype(M)::value>(...); })
 // hipErrorInvalidValue for an id that names no family.  A new family is one line here (and its object in the Makefile).
 template <class F>
 inline hipError_t by_model(int id, F&& f) {
@@ -69,39 +70,86 @@ struct Geo {
 bool geo_default(int seg, Geo& g);
 bool geo_valid(int seg, int np, Geo& g);
 
-template <int MODEL> hipError_t launch_init(const FilterView& v, Geo g, int nxt, double y, hipStream_t s);
-// hot: the launch's by-value arguments (StepHot, smc_kernels.h); hot.lead repeats the view's seed and carries the addresses of the
-// kernel's early loads as the caller derived them for THIS launch (the view's pointers, the current buffer, t)
-template <int MODEL> hipError_t launch_step(const FilterView& v, Geo g, const StepHot& hot, hipStream_t s);
-template <int MODEL> hipError_t launch_resident(const FilterView& v, int T, StepRec* recs, hipStream_t s);
-// summaries (quantile levels / moments named by the view's sum_* fields, row 0) of the current state of single-segment filters in
-// one launch; hipErrorInvalidValue when the segment length has no instantiation or the state does not fit LDS
-template <int MODEL> hipError_t launch_summ_once(const FilterView& v, int cur, hipStream_t s);
-// window mode: steps [t0, t0 + T) from the state in buffer bin to buffer bout, (logmu, ess) of every step to win
-template <int MODEL> hipError_t launch_window(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
-// the same three for a handle with a proposal (smc_set_proposal): the GUIDED kernels, instantiated for the families that have
-// proposals (LG1D, UCSV3D) in translation units of their own (smc_model.hip with -DSMC_GUIDED=1)
-template <int MODEL> hipError_t launch_step_g(const FilterView& v, Geo g, const StepHot& hot, hipStream_t s);
-template <int MODEL> hipError_t launch_resident_g(const FilterView& v, int T, StepRec* recs, hipStream_t s);
-// forecasts (smc_forecast_kernels.h): nk horizons k0 .. k0 + nk - 1 of every particle from the state rows src [d][ntheta][npad] into
-// out [nk][d + 3][ntheta][npad]; hipErrorInvalidValue when g is not the geometry of the view's segment length
-template <int MODEL> hipError_t launch_forecast(const FilterView& v, Geo g, const double* src, uint64_t fseed, uint32_t k0, int nk, double* out, hipStream_t s);
-template <int MODEL> hipError_t launch_window_g(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
-// missing observations (smc_spec.h; handles with SMC_FLAG_NAN_MISSING): the MISS kernels, translation units of their own
-// (smc_model.hip with -DSMC_MISSING=1).  launch_init_m / launch_step_m: the missing step itself, launched for a step whose
-// observation is NaN (a guided handle too: a missing step has no proposal).  launch_resident_m / launch_window_m: the LDS-resident
-// loop that tests every step's observation, launched when the series or window holds a NaN; _gm: their twins for a handle with
-// a proposal (bootstrap step at gaps, guided step elsewhere; the families of by_guided_model)
-template <int MODEL> hipError_t launch_init_m(const FilterView& v, Geo g, int nxt, double y, hipStream_t s);
-template <int MODEL> hipError_t launch_step_m(const FilterView& v, Geo g, const StepHot& hot, hipStream_t s);
-template <int MODEL> hipError_t launch_resident_m(const FilterView& v, int T, StepRec* recs, hipStream_t s);
-template <int MODEL> hipError_t launch_window_m(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
-template <int MODEL> hipError_t launch_resident_gm(const FilterView& v, int T, StepRec* recs, hipStream_t s);
-template <int MODEL> hipError_t launch_window_gm(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
-// the conditional particle filter (smc_spec.h; handles with SMC_FLAG_CONDITIONAL): the COND kernels, translation units of their
-// own (smc_model.hip with -DSMC_COND=1: build/cond<model>.o), for the families of by_density_model.  One launch per step only;
-// xrow [d][ntheta]: the reference row of the step on the device (xref + t d ntheta)
-template <int MODEL> hipError_t launch_init_c(const FilterView& v, Geo g, int nxt, double y, const double* xrow, hipStream_t s);
-template <int MODEL> hipError_t launch_step_c(const FilterView& v, Geo g, const StepHot& hot, const double* xrow, hipStream_t s);
+// ---- kernel variants ---------------------------------------------------------------------------------
+// What a handle's options make of its kernels; every variant is a set of translation units of its own (never a run-time branch
+// in the bodies the other handles run).  The ids are the Makefile's -DSMC_VARIANT.
+enum Variant : int {
+    VARIANT_PLAIN = 0,            // the bootstrap kernels
+    VARIANT_GUIDED = 1,           // handles with a proposal (smc_set_proposal): the GUIDED kernels
+    VARIANT_MISSING = 2,          // SMC_FLAG_NAN_MISSING (smc_spec.h "missing observations"): the missing step, launched for a step
+                                  // whose observation is NaN, and the LDS-resident loops that test every step's observation
+    VARIANT_MISSING_GUIDED = 3,   // ... those loops for a handle with a proposal (bootstrap step at gaps, guided step elsewhere)
+    VARIANT_COND = 4,             // SMC_FLAG_CONDITIONAL (smc_spec.h "the conditional particle filter"): one launch per step only
+    VARIANT_COUNT
+};
+enum Entry : int { ENTRY_INIT, ENTRY_STEP, ENTRY_RESIDENT, ENTRY_WINDOW, ENTRY_FORECAST, ENTRY_SUMM_ONCE, ENTRY_COUNT };
+constexpr int NO_OBJECT = -1;
+// The (variant, family) pairs that have an object, one bit per model id - the SAME list as KERNELS in the Makefile: a pair
+// missing there is an undefined symbol when the library is loaded, a pair missing here a static_assert in smc_model.hip.
+// Guided: the families with proposals (by_guided_model); conditional: those with a transition density (by_density_model).
+constexpr unsigned family_bits(int a, int b = 0, int c = 0, int d = 0) { return (1u << a | 1u << b | 1u << c | 1u << d) & ~1u; }
+constexpr unsigned LAUNCH_FAMILIES[VARIANT_COUNT] = {
+    /* plain          */ family_bits(MODEL_LG1D, MODEL_SV1D, MODEL_UCSV3D, MODEL_UCSV_RB),
+    /* guided         */ family_bits(MODEL_LG1D, MODEL_UCSV3D),
+    /* missing        */ family_bits(MODEL_LG1D, MODEL_SV1D, MODEL_UCSV3D, MODEL_UCSV_RB),
+    /* missing+guided */ family_bits(MODEL_LG1D, MODEL_UCSV3D),
+    /* conditional    */ family_bits(MODEL_LG1D, MODEL_SV1D, MODEL_UCSV3D),
+};
+// ... and the variant whose object serves each entry point of a variant: itself where its object defines the entry point, another
+// where the kernels would be the same ones (a first step has no proposal; neither has a missing step), none where the handle
+// has no such launch (a conditional handle; forecasts and one-launch summaries run the plain kernels whatever the handle)
+// (missing init: the first step of a flagged handle whose first observation is NaN - the gap bit of pick_variant, smc_host.h)
+constexpr int LAUNCH_OBJECT[VARIANT_COUNT][ENTRY_COUNT] = {
+    //                     init             step             resident                window                  forecast       summ_once
+    /* plain          */ {VARIANT_PLAIN,   VARIANT_PLAIN,   VARIANT_PLAIN,          VARIANT_PLAIN,          VARIANT_PLAIN, VARIANT_PLAIN},
+    /* guided         */ {VARIANT_PLAIN,   VARIANT_GUIDED,  VARIANT_GUIDED,         VARIANT_GUIDED,         NO_OBJECT,     NO_OBJECT},
+    /* missing        */ {VARIANT_MISSING, VARIANT_MISSING, VARIANT_MISSING,        VARIANT_MISSING,        NO_OBJECT,     NO_OBJECT},
+    /* missing+guided */ {VARIANT_MISSING, VARIANT_MISSING, VARIANT_MISSING_GUIDED, VARIANT_MISSING_GUIDED, NO_OBJECT,     NO_OBJECT},
+    /* conditional    */ {VARIANT_COND,    VARIANT_COND,    NO_OBJECT,              NO_OBJECT,              NO_OBJECT,     NO_OBJECT},
+};
+constexpr bool launch_has_object(int variant, int model) { return model > 0 && model < 32 && (LAUNCH_FAMILIES[variant] >> model & 1u) != 0; }
+constexpr bool launch_defines(int variant, int entry) { return LAUNCH_OBJECT[variant][entry] == variant; }
+
+// The entry points of the object of one pair (smc_model.hip).  An entry point that launch_defines denies the variant refuses and
+// instantiates no kernel; by_variant never names it.
+template <int MODEL, int VARIANT>
+struct Launch {
+    // xrow [d][ntheta]: the reference row of the step on the device (xref + t d ntheta) - the conditional variant's; the others ignore it
+    static hipError_t init(const FilterView& v, Geo g, int nxt, double y, const double* xrow, hipStream_t s);
+    // hot: the launch's by-value arguments (StepHot, smc_kernels.h); hot.lead repeats the view's seed and carries the addresses of
+    // the kernel's early loads as the caller derived them for THIS launch (the view's pointers, the current buffer, t)
+    static hipError_t step(const FilterView& v, Geo g, const StepHot& hot, const double* xrow, hipStream_t s);
+    static hipError_t resident(const FilterView& v, int T, StepRec* recs, hipStream_t s);
+    // window mode: steps [t0, t0 + T) from the state in buffer bin to buffer bout, (logmu, ess) of every step to win
+    static hipError_t window(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s);
+    // forecasts (smc_forecast_kernels.h): nk horizons k0 .. k0 + nk - 1 of every particle from the state rows src [d][ntheta][npad]
+    // into out [nk][d + 3][ntheta][npad]; hipErrorInvalidValue when g is not the geometry of the view's segment length
+    static hipError_t forecast(const FilterView& v, Geo g, const double* src, uint64_t fseed, uint32_t k0, int nk, double* out, hipStream_t s);
+    // summaries (quantile levels / moments named by the view's sum_* fields, row 0) of the current state of single-segment filters
+    // in one launch; hipErrorInvalidValue when the segment length has no instantiation or the state does not fit LDS
+    static hipError_t summ_once(const FilterView& v, int cur, hipStream_t s);
+};
+
+// Calls f with the Launch<MODEL, VARIANT> of the object that defines ENTRY for (model id, variant):
+//     by_variant<ENTRY_STEP>(id, variant, [&](auto L) { return L.step(...); })
+// variant: as LAUNCH_OBJECT gives it (pick_variant, smc_host.h).  hipErrorInvalidValue for a pair without an object.
+template <int ENTRY, int VARIANT, class F>
+inline hipError_t by_variant_model(int id, F&& f) {
+    return by_model(id, [&](auto M) {
+        if constexpr (launch_defines(VARIANT, ENTRY) && launch_has_object(VARIANT, decltype(M)::value)) return f(Launch<decltype(M)::value, VARIANT>{});
+        else return hipErrorInvalidValue;
+    });
+}
+template <int ENTRY, class F>
+inline hipError_t by_variant(int id, int variant, F&& f) {
+    switch (variant) {
+    case VARIANT_PLAIN: return by_variant_model<ENTRY, VARIANT_PLAIN>(id, f);
+    case VARIANT_GUIDED: return by_variant_model<ENTRY, VARIANT_GUIDED>(id, f);
+    case VARIANT_MISSING: return by_variant_model<ENTRY, VARIANT_MISSING>(id, f);
+    case VARIANT_MISSING_GUIDED: return by_variant_model<ENTRY, VARIANT_MISSING_GUIDED>(id, f);
+    case VARIANT_COND: return by_variant_model<ENTRY, VARIANT_COND>(id, f);
+    }
+    return hipErrorInvalidValue;
+}
 
 }  // namespace smc

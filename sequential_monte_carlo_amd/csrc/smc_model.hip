@@ -1,5 +1,6 @@
-// smc_model.hip -- instantiates the kernels of ONE model family (-DSMC_MODEL=1|2|3|4) for every
-// workgroup geometry.  One object per family, built in parallel and linked into libsmchip.so.
+// smc_model.hip -- instantiates the kernels of ONE variant of ONE model family (-DSMC_VARIANT=<Variant id, smc_launch.h>
+// -DSMC_MODEL=1|2|3|4) for every workgroup geometry, behind Launch<SMC_MODEL, SMC_VARIANT>.  One object per pair (KERNELS in the
+// Makefile, LAUNCH_FAMILIES in smc_launch.h), built in parallel and linked into libsmchip.so.
 #include "smc_launch.h"
 #include "smc_forecast_kernels.h"
 #include <cstdlib>
@@ -7,142 +8,80 @@
 #ifndef SMC_MODEL
 #error "compile with -DSMC_MODEL=<model id>"
 #endif
-// -DSMC_GUIDED=1: the same launchers for the GUIDED kernels (handles with a proposal, smc_set_proposal), as translation units
-// of their own (build/guided<model>.o): launch_step_g, launch_resident_g, launch_window_g.  Without it: the bootstrap kernels.
-#ifndef SMC_GUIDED
-#define SMC_GUIDED 0
-#endif
-#define SMC_G (SMC_GUIDED != 0)
-// -DSMC_MISSING=1: the same launchers again for the MISS kernels (handles with SMC_FLAG_NAN_MISSING; smc_spec.h "missing
-// observations"), translation units of their own as well: build/missing<model>.o (launch_init_m, launch_step_m, launch_resident_m,
-// launch_window_m) and, with -DSMC_GUIDED=1 on top, build/missingg<model>.o (launch_resident_gm, launch_window_gm - the missing
-// step itself has no proposal).  Without it: the kernels every other handle launches, untouched by the variant.
-#ifndef SMC_MISSING
-#define SMC_MISSING 0
-#endif
-#define SMC_M (SMC_MISSING != 0)
-// -DSMC_COND=1: the COND kernels alone (handles with SMC_FLAG_CONDITIONAL; smc_spec.h "the conditional particle filter"):
-// build/cond<model>.o with launch_init_c and launch_step_c - one launch per step, multinomial resampling, the filter's stream id
-// and rows through the view's pointers.  Nothing else of this file is compiled into those objects.
-#ifndef SMC_COND
-#define SMC_COND 0
+#ifndef SMC_VARIANT   // (the plain kernels: what scripts/dbg/isa.sh and a bare -DSMC_MODEL=<id> compile)
+#define SMC_VARIANT 0
 #endif
 
 namespace smc {
 
-#if SMC_COND
-template <int THREADS, int NP>
-static hipError_t init_c_t(const FilterView& v, int nxt, double y, const double* xrow, hipStream_t s) {
-    const size_t lds = scr_words(THREADS, NP) * 8;
-    hipLaunchKernelGGL((k_init<SMC_MODEL, THREADS, NP, false, const double*>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, nxt, y, xrow);
-    return hipGetLastError();
-}
-template <int THREADS, int NP, bool MULTI, bool GTAB, int RPT>
-static hipError_t step_c_launch(const FilterView& v, const StepHot& hot, const double* xrow, int emit_prev, size_t lds, hipStream_t s) {
-    static std::atomic<bool> raised[16] = {};   // per instantiation and device
-    hipError_t e = raise_lds_limit(k_step_cond<SMC_MODEL, THREADS, NP, MULTI, GTAB, RPT>, lds, raised);
-    if (e != hipSuccess) return e;
-    const StepLead& l = hot.lead;
-    hipLaunchKernelGGL((k_step_cond<SMC_MODEL, THREADS, NP, MULTI, GTAB, RPT>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, l.seed, l.t, l.stream0,
-                       l.brow, l.rec0, l.rec1, l.C, step_pack(hot.nseg, hot.cur, emit_prev), l.n32, hot.yval, hot.prm0, v, xrow);
-    return hipGetLastError();
-}
-// (the geometries of step_sys_t below)
-template <int THREADS, int NP>
-static hipError_t step_c_t(const FilterView& v, const StepHot& hot, const double* xrow, hipStream_t s) {
-    if (v.tabD) return step_c_launch<THREADS, NP, true, true, 1>(v, hot, xrow, 0, step_lds_bytes(0, THREADS, NP, true), s);
-    const size_t lds = step_lds_bytes(v.nseg_p2, THREADS, NP, v.nseg > 1);
-    if (v.nseg_p2 > THREADS) return step_c_launch<THREADS, NP, true, false, 2>(v, hot, xrow, hot.emit_prev, lds, s);
-    return v.nseg > 1 ? step_c_launch<THREADS, NP, true, false, 1>(v, hot, xrow, hot.emit_prev, lds, s)
-                      : step_c_launch<THREADS, NP, false, false, 1>(v, hot, xrow, hot.emit_prev, lds, s);
-}
-#define SMC_COND_GEO_SWITCH(FN, ...)                                              \
-    switch (g.threads * 8 + g.np) {                                               \
-    case 64 * 8 + 2: return FN<64, 2>(__VA_ARGS__);                               \
-    case 128 * 8 + 1: return FN<128, 1>(__VA_ARGS__);                             \
-    case 128 * 8 + 2: return FN<128, 2>(__VA_ARGS__);                             \
-    case 128 * 8 + 4: return FN<128, 4>(__VA_ARGS__);                             \
-    case 256 * 8 + 1: return FN<256, 1>(__VA_ARGS__);                             \
-    case 256 * 8 + 2: return FN<256, 2>(__VA_ARGS__);                             \
-    case 256 * 8 + 4: return FN<256, 4>(__VA_ARGS__);                             \
-    case 512 * 8 + 1: return FN<512, 1>(__VA_ARGS__);                             \
-    case 512 * 8 + 2: return FN<512, 2>(__VA_ARGS__);                             \
-    case 512 * 8 + 4: return FN<512, 4>(__VA_ARGS__);                             \
-    case 1024 * 8 + 1: return FN<1024, 1>(__VA_ARGS__);                           \
-    case 1024 * 8 + 2: return FN<1024, 2>(__VA_ARGS__);                           \
-    case 1024 * 8 + 4: return FN<1024, 4>(__VA_ARGS__);                           \
-    }                                                                             \
-    return hipErrorInvalidValue;
-template <>
-hipError_t launch_init_c<SMC_MODEL>(const FilterView& v, Geo g, int nxt, double y, const double* xrow, hipStream_t s) {
-    if (!xrow) return hipErrorInvalidValue;
-    SMC_COND_GEO_SWITCH(init_c_t, v, nxt, y, xrow, s)
-}
-template <>
-hipError_t launch_step_c<SMC_MODEL>(const FilterView& v, Geo g, const StepHot& hot, const double* xrow, hipStream_t s) {
-    if (!xrow || v.systematic) return hipErrorInvalidValue;
-    SMC_COND_GEO_SWITCH(step_c_t, v, hot, xrow, s)
-}
-}  // namespace smc
-#else
+// What the variant makes of the kernels below; which entry points this object defines: launch_defines (smc_launch.h).
+// Everything that depends on these is selected with if constexpr INSIDE templates: a discarded branch instantiates no kernel.
+constexpr int VAR = SMC_VARIANT;
+constexpr bool VAR_GUIDED = VAR == VARIANT_GUIDED || VAR == VARIANT_MISSING_GUIDED;   // k_step / k_resident<..., GUIDED>
+constexpr bool VAR_MISS = VAR == VARIANT_MISSING || VAR == VARIANT_MISSING_GUIDED;    // k_init<..., MISS>, k_step_miss, k_resident<..., MISS>
+constexpr bool VAR_COND = VAR == VARIANT_COND;   // k_init<..., const double*> and k_step_cond: the reference row as their last argument
+// the missing step reads the filter's row and stream id through the view on every launch, and so does the conditional step,
+// which resamples by the multinomial law only: BYV resp. SYS are not instantiated for them
+constexpr bool STEP_BYV = !VAR_MISS && !VAR_COND;
+constexpr bool STEP_SYS = !VAR_COND;
+static_assert(launch_has_object(VAR, SMC_MODEL), "this (variant, family) pair is not in LAUNCH_FAMILIES (smc_launch.h)");
 
-#if !SMC_G
 template <int THREADS, int NP>
-static hipError_t init_t(const FilterView& v, int nxt, double y, hipStream_t s) {
+static hipError_t init_t(const FilterView& v, int nxt, double y, const double* xrow, hipStream_t s) {
     const size_t lds = scr_words(THREADS, NP) * 8;
-    hipLaunchKernelGGL((k_init<SMC_MODEL, THREADS, NP, SMC_M>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, nxt, y);
+    if constexpr (VAR_COND) hipLaunchKernelGGL((k_init<SMC_MODEL, THREADS, NP, false, const double*>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, nxt, y, xrow);
+    else hipLaunchKernelGGL((k_init<SMC_MODEL, THREADS, NP, VAR_MISS>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, v, nxt, y);
     return hipGetLastError();
 }
-#endif
-// one launch of k_step<..., BYV>: the kernel's parameter list is the leading scalars (StepLead) one by one at the head (what the
-// wave finds preloaded), the observation, the parameter row, the view
-#if SMC_M && !SMC_G
-// (the missing step reads the filter's row and stream id through the view on every launch: BYV is not instantiated)
 template <int THREADS, int NP, bool MULTI, bool SYS, bool GTAB, int RPT, bool BYV>
-static hipError_t step_launch(const FilterView& v, const StepHot& hot, int emit_prev, size_t lds, hipStream_t s) {
-    static_assert(!BYV, "missing step: through the pointers");
+constexpr auto step_kernel() {
+    if constexpr (VAR_COND) return &k_step_cond<SMC_MODEL, THREADS, NP, MULTI, GTAB, RPT>;
+    else if constexpr (VAR_MISS) return &k_step_miss<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT>;
+    else return &k_step<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, VAR_GUIDED, BYV>;
+}
+// one launch of the step kernel: its parameter list is the leading scalars (StepLead) one by one at the head (what the wave finds
+// preloaded), the observation, the parameter row, the view (and the reference row, conditional)
+template <int THREADS, int NP, bool MULTI, bool SYS, bool GTAB, int RPT, bool BYV>
+static hipError_t step_launch(const FilterView& v, const StepHot& hot, const double* xrow, int emit_prev, size_t lds, hipStream_t s) {
+    static_assert((STEP_SYS || !SYS) && (STEP_BYV || !BYV), "not instantiated for this variant");
+    constexpr auto kernel = step_kernel<THREADS, NP, MULTI, SYS, GTAB, RPT, BYV>();
     static std::atomic<bool> raised[16] = {};   // per instantiation and device
-    hipError_t e = raise_lds_limit(k_step_miss<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT>, lds, raised);
+    hipError_t e = raise_lds_limit(kernel, lds, raised);
     if (e != hipSuccess) return e;
     const StepLead& l = hot.lead;
-    hipLaunchKernelGGL((k_step_miss<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, l.seed, l.t,
-                       l.stream0, l.brow, l.rec0, l.rec1, l.C, step_pack(hot.nseg, hot.cur, emit_prev), l.n32, hot.yval, hot.prm0, v);
+    auto launch = [&](auto... tail) {
+        hipLaunchKernelGGL(kernel, dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, l.seed, l.t, l.stream0, l.brow, l.rec0, l.rec1, l.C,
+                           step_pack(hot.nseg, hot.cur, emit_prev), l.n32, hot.yval, hot.prm0, v, tail...);
+    };
+    if constexpr (VAR_COND) launch(xrow);
+    else launch();
     return hipGetLastError();
 }
-#elif !SMC_M
-template <int THREADS, int NP, bool MULTI, bool SYS, bool GTAB, int RPT, bool BYV>
-static hipError_t step_launch(const FilterView& v, const StepHot& hot, int emit_prev, size_t lds, hipStream_t s) {
-    static std::atomic<bool> raised[16] = {};   // per instantiation and device
-    hipError_t e = raise_lds_limit(k_step<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, SMC_G, BYV>, lds, raised);
-    if (e != hipSuccess) return e;
-    const StepLead& l = hot.lead;
-    hipLaunchKernelGGL((k_step<SMC_MODEL, THREADS, NP, MULTI, SYS, GTAB, RPT, SMC_G, BYV>), dim3(v.nseg, v.ntheta), dim3(THREADS), lds, s, l.seed, l.t,
-                       l.stream0, l.brow, l.rec0, l.rec1, l.C, step_pack(hot.nseg, hot.cur, emit_prev), l.n32, hot.yval, hot.prm0, v);
-    return hipGetLastError();
-}
-#endif
-#if !(SMC_M && SMC_G)
 template <int THREADS, int NP, bool SYS, bool BYV>
-static hipError_t step_sys_t(const FilterView& v, const StepHot& hot, hipStream_t s) {
+static hipError_t step_sys_t(const FilterView& v, const StepHot& hot, const double* xrow, hipStream_t s) {
     if (v.tabD)   // the table comes from k_table (launched by the caller before this step): no table in LDS, nothing to emit
-        return step_launch<THREADS, NP, true, SYS, true, 1, BYV>(v, hot, 0, step_lds_bytes(0, THREADS, NP, true), s);
+        return step_launch<THREADS, NP, true, SYS, true, 1, BYV>(v, hot, xrow, 0, step_lds_bytes(0, THREADS, NP, true), s);
     const size_t lds = step_lds_bytes(v.nseg_p2, THREADS, NP, v.nseg > 1);
     if (v.nseg_p2 > THREADS)   // up to twice as many segments as threads: the window prologue with two records per thread
-        return step_launch<THREADS, NP, true, SYS, false, 2, BYV>(v, hot, hot.emit_prev, lds, s);
-    return v.nseg > 1 ? step_launch<THREADS, NP, true, SYS, false, 1, BYV>(v, hot, hot.emit_prev, lds, s)
-                      : step_launch<THREADS, NP, false, SYS, false, 1, BYV>(v, hot, hot.emit_prev, lds, s);
+        return step_launch<THREADS, NP, true, SYS, false, 2, BYV>(v, hot, xrow, hot.emit_prev, lds, s);
+    return v.nseg > 1 ? step_launch<THREADS, NP, true, SYS, false, 1, BYV>(v, hot, xrow, hot.emit_prev, lds, s)
+                      : step_launch<THREADS, NP, false, SYS, false, 1, BYV>(v, hot, xrow, hot.emit_prev, lds, s);
 }
 template <int THREADS, int NP>
-static hipError_t step_t(const FilterView& v, const StepHot& hot, hipStream_t s) {
-#if SMC_M
-    return v.systematic ? step_sys_t<THREADS, NP, true, false>(v, hot, s) : step_sys_t<THREADS, NP, false, false>(v, hot, s);
-#else
-    if (hot.by_value) return v.systematic ? step_sys_t<THREADS, NP, true, true>(v, hot, s) : step_sys_t<THREADS, NP, false, true>(v, hot, s);
-    return v.systematic ? step_sys_t<THREADS, NP, true, false>(v, hot, s) : step_sys_t<THREADS, NP, false, false>(v, hot, s);
-#endif
+static hipError_t step_t(const FilterView& v, const StepHot& hot, const double* xrow, hipStream_t s) {
+    if constexpr (STEP_BYV)
+        if (hot.by_value) return v.systematic ? step_sys_t<THREADS, NP, true, true>(v, hot, xrow, s) : step_sys_t<THREADS, NP, false, true>(v, hot, xrow, s);
+    if constexpr (STEP_SYS)
+        if (v.systematic) return step_sys_t<THREADS, NP, true, false>(v, hot, xrow, s);
+    return step_sys_t<THREADS, NP, false, false>(v, hot, xrow, s);
 }
-#endif
+template <int THREADS, int NP>
+static hipError_t forecast_t(const FilterView& v, const double* src, uint64_t fseed, uint32_t k0, int nk, double* out, hipStream_t s) {
+    hipLaunchKernelGGL((k_forecast<SMC_MODEL, THREADS, NP>), dim3(v.nseg, v.ntheta), dim3(THREADS), 0, s, v, src, fseed, k0, nk, out);
+    return hipGetLastError();
+}
 
+// The instantiated geometries of the one-launch-per-step kernels (what geo_valid, smc_capi.hip, accepts is this list)
 #define SMC_GEO_SWITCH(FN, ...)                                                   \
     switch (g.threads * 8 + g.np) {                                               \
     case 64 * 8 + 2: return FN<64, 2>(__VA_ARGS__);                               \
@@ -158,59 +97,43 @@ static hipError_t step_t(const FilterView& v, const StepHot& hot, hipStream_t s)
     case 1024 * 8 + 1: return FN<1024, 1>(__VA_ARGS__);                           \
     case 1024 * 8 + 2: return FN<1024, 2>(__VA_ARGS__);                           \
     case 1024 * 8 + 4: return FN<1024, 4>(__VA_ARGS__);                           \
-    }                                                                             \
-    return hipErrorInvalidValue;
+    }
 
-#if !SMC_G && SMC_M
-template <>
-hipError_t launch_init_m<SMC_MODEL>(const FilterView& v, Geo g, int nxt, double y, hipStream_t s) {
-    SMC_GEO_SWITCH(init_t, v, nxt, y, s)
+// The entry points.  Templates only for the sake of if constexpr: instantiated for <SMC_MODEL, VAR> alone, at the end of this file.
+template <int MODEL, int VARIANT>
+hipError_t Launch<MODEL, VARIANT>::init(const FilterView& v, Geo g, int nxt, double y, const double* xrow, hipStream_t s) {
+    if constexpr (launch_defines(VARIANT, ENTRY_INIT)) {
+        if (VAR_COND && !xrow) return hipErrorInvalidValue;
+        SMC_GEO_SWITCH(init_t, v, nxt, y, xrow, s)
+    }
+    return hipErrorInvalidValue;
 }
-#define SMC_LAUNCH_STEP launch_step_m
-#define SMC_LAUNCH_RESIDENT launch_resident_m
-#define SMC_LAUNCH_WINDOW launch_window_m
-#elif !SMC_G
-template <>
-hipError_t launch_init<SMC_MODEL>(const FilterView& v, Geo g, int nxt, double y, hipStream_t s) {
-    SMC_GEO_SWITCH(init_t, v, nxt, y, s)
+template <int MODEL, int VARIANT>
+hipError_t Launch<MODEL, VARIANT>::step(const FilterView& v, Geo g, const StepHot& hot, const double* xrow, hipStream_t s) {
+    if constexpr (launch_defines(VARIANT, ENTRY_STEP)) {
+        if (VAR_COND && (!xrow || v.systematic)) return hipErrorInvalidValue;
+        if (!VAR_COND && hot.by_value && v.ntheta != 1) return hipErrorInvalidValue;   // by value: ONE filter per launch
+        SMC_GEO_SWITCH(step_t, v, hot, xrow, s)
+    }
+    return hipErrorInvalidValue;
 }
-template <int THREADS, int NP>
-static hipError_t forecast_t(const FilterView& v, const double* src, uint64_t fseed, uint32_t k0, int nk, double* out, hipStream_t s) {
-    hipLaunchKernelGGL((k_forecast<SMC_MODEL, THREADS, NP>), dim3(v.nseg, v.ntheta), dim3(THREADS), 0, s, v, src, fseed, k0, nk, out);
-    return hipGetLastError();
+template <int MODEL, int VARIANT>
+hipError_t Launch<MODEL, VARIANT>::forecast(const FilterView& v, Geo g, const double* src, uint64_t fseed, uint32_t k0, int nk, double* out, hipStream_t s) {
+    if constexpr (launch_defines(VARIANT, ENTRY_FORECAST)) {
+        if (2 * g.np * g.threads != v.seg || nk < 1) return hipErrorInvalidValue;   // (a workgroup covers exactly one segment)
+        SMC_GEO_SWITCH(forecast_t, v, src, fseed, k0, nk, out, s)
+    }
+    return hipErrorInvalidValue;
 }
-template <>
-hipError_t launch_forecast<SMC_MODEL>(const FilterView& v, Geo g, const double* src, uint64_t fseed, uint32_t k0, int nk, double* out, hipStream_t s) {
-    if (2 * g.np * g.threads != v.seg || nk < 1) return hipErrorInvalidValue;   // (a workgroup covers exactly one segment)
-    SMC_GEO_SWITCH(forecast_t, v, src, fseed, k0, nk, out, s)
-}
-#define SMC_LAUNCH_STEP launch_step
-#define SMC_LAUNCH_RESIDENT launch_resident
-#define SMC_LAUNCH_WINDOW launch_window
-#elif SMC_M
-#define SMC_LAUNCH_RESIDENT launch_resident_gm
-#define SMC_LAUNCH_WINDOW launch_window_gm
-#else
-#define SMC_LAUNCH_STEP launch_step_g
-#define SMC_LAUNCH_RESIDENT launch_resident_g
-#define SMC_LAUNCH_WINDOW launch_window_g
-#endif
-#ifdef SMC_LAUNCH_STEP
-template <>
-hipError_t SMC_LAUNCH_STEP<SMC_MODEL>(const FilterView& v, Geo g, const StepHot& hot, hipStream_t s) {
-    if (hot.by_value && v.ntheta != 1) return hipErrorInvalidValue;   // by value: ONE filter per launch
-    SMC_GEO_SWITCH(step_t, v, hot, s)
-}
-#endif
 
 template <int THREADS, int NP, bool SYS, bool WIN, bool SUMM = false, bool UNW = false>
 static hipError_t resident_sys_t(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s) {
     const size_t lds = resident_lds_bytes<SMC_MODEL>(2 * NP * THREADS, THREADS, NP, SUMM ? v.sum_np : -1);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     static std::atomic<bool> raised[16] = {};   // per instantiation and device
-    hipError_t e = raise_lds_limit(k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW, SMC_G, SMC_M>, lds, raised);
+    hipError_t e = raise_lds_limit(k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW, VAR_GUIDED, VAR_MISS>, lds, raised);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW, SMC_G, SMC_M>), dim3(v.ntheta), dim3(THREADS), lds, s, v, T, recs, t0, bin, bout, win);
+    hipLaunchKernelGGL((k_resident<SMC_MODEL, THREADS, NP, SYS, WIN, SUMM, UNW, VAR_GUIDED, VAR_MISS>), dim3(v.ntheta), dim3(THREADS), lds, s, v, T, recs, t0, bin, bout, win);
     return hipGetLastError();
 }
 // per-step summaries (smc_set_summaries) select the SUMM kernels; they exist for the multinomial default only (the C ABI sends
@@ -240,25 +163,46 @@ static int resident_np(const FilterView& v) {
     return e ? atoi(e) : (v.seg == 1024 && v.ntheta <= 512) ? 1 : 0;
 }
 
-template <>
-hipError_t SMC_LAUNCH_RESIDENT<SMC_MODEL>(const FilterView& v, int T, StepRec* recs, hipStream_t s) {
-    const int np = resident_np(v);
-    switch (v.seg) {
-    case 256: return resident_t<128, 1>(v, T, recs, s);
-    case 512: return resident_t<256, 1>(v, T, recs, s);
-    case 1024: return np == 1 ? resident_t<512, 1>(v, T, recs, s) : np == 4 ? resident_t<128, 4>(v, T, recs, s) : resident_t<256, 2>(v, T, recs, s);
-    case 2048: return np == 1 ? resident_t<1024, 1>(v, T, recs, s) : np == 4 ? resident_t<256, 4>(v, T, recs, s) : resident_t<512, 2>(v, T, recs, s);
-    case 4096:   // (four state rows: 4096 particles and their prefix sums exceed the 160 KiB of LDS - resident_supported says so first)
-        if constexpr (model_dim<SMC_MODEL>::value > 3) return hipErrorInvalidValue;
-        else return np == 4 ? resident_t<512, 4>(v, T, recs, s) : resident_t<1024, 2>(v, T, recs, s);   // (1024 x 2 spills a little and still wins: +5-10 %, scripts/dbg/res4096.py)
-    case 8192:
-        if constexpr (model_dim<SMC_MODEL>::value == 1) return resident_t<1024, 4>(v, T, recs, s);
-        else return hipErrorInvalidValue;
+// (the geometry tables of resident and window differ on purpose: window has no np == 4 at 1024 and only 512 x 2 at 2048)
+template <int MODEL, int VARIANT>
+hipError_t Launch<MODEL, VARIANT>::resident(const FilterView& v, int T, StepRec* recs, hipStream_t s) {
+    if constexpr (launch_defines(VARIANT, ENTRY_RESIDENT)) {
+        const int np = resident_np(v);
+        switch (v.seg) {
+        case 256: return resident_t<128, 1>(v, T, recs, s);
+        case 512: return resident_t<256, 1>(v, T, recs, s);
+        case 1024: return np == 1 ? resident_t<512, 1>(v, T, recs, s) : np == 4 ? resident_t<128, 4>(v, T, recs, s) : resident_t<256, 2>(v, T, recs, s);
+        case 2048: return np == 1 ? resident_t<1024, 1>(v, T, recs, s) : np == 4 ? resident_t<256, 4>(v, T, recs, s) : resident_t<512, 2>(v, T, recs, s);
+        case 4096:   // (four state rows: 4096 particles and their prefix sums exceed the 160 KiB of LDS - resident_supported says so first)
+            if constexpr (model_dim<MODEL>::value > 3) return hipErrorInvalidValue;
+            else return np == 4 ? resident_t<512, 4>(v, T, recs, s) : resident_t<1024, 2>(v, T, recs, s);   // (1024 x 2 spills a little and still wins: +5-10 %, scripts/dbg/res4096.py)
+        case 8192:
+            if constexpr (model_dim<MODEL>::value == 1) return resident_t<1024, 4>(v, T, recs, s);
+            else return hipErrorInvalidValue;
+        }
+    }
+    return hipErrorInvalidValue;
+}
+template <int MODEL, int VARIANT>
+hipError_t Launch<MODEL, VARIANT>::window(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s) {
+    if constexpr (launch_defines(VARIANT, ENTRY_WINDOW)) {
+        const int np = resident_np(v);
+        switch (v.seg) {
+        case 256: return window_t<128, 1>(v, T, recs, t0, bin, bout, win, s);
+        case 512: return window_t<256, 1>(v, T, recs, t0, bin, bout, win, s);
+        case 1024: return np == 1 ? window_t<512, 1>(v, T, recs, t0, bin, bout, win, s) : window_t<256, 2>(v, T, recs, t0, bin, bout, win, s);
+        case 2048: return window_t<512, 2>(v, T, recs, t0, bin, bout, win, s);
+        case 4096:
+            if constexpr (model_dim<MODEL>::value > 3) return hipErrorInvalidValue;
+            else return np == 4 ? window_t<512, 4>(v, T, recs, t0, bin, bout, win, s) : window_t<1024, 2>(v, T, recs, t0, bin, bout, win, s);
+        case 8192:
+            if constexpr (model_dim<MODEL>::value == 1) return window_t<1024, 4>(v, T, recs, t0, bin, bout, win, s);
+            else return hipErrorInvalidValue;
+        }
     }
     return hipErrorInvalidValue;
 }
 
-#if !SMC_G && !SMC_M
 template <int THREADS, int NP, bool UNW>
 static hipError_t summ_once_m(const FilterView& v, int cur, hipStream_t s) {
     constexpr int D = model_dim<SMC_MODEL>::value;
@@ -274,42 +218,27 @@ template <int THREADS, int NP>
 static hipError_t summ_once_t(const FilterView& v, int cur, hipStream_t s) {
     return v.sum_unw ? summ_once_m<THREADS, NP, true>(v, cur, s) : summ_once_m<THREADS, NP, false>(v, cur, s);
 }
-template <>
-hipError_t launch_summ_once<SMC_MODEL>(const FilterView& v, int cur, hipStream_t s) {
-    if (v.nseg != 1) return hipErrorInvalidValue;
-    switch (v.seg) {
-    case 256: return summ_once_t<128, 1>(v, cur, s);
-    case 512: return summ_once_t<256, 1>(v, cur, s);
-    case 1024: return summ_once_t<512, 1>(v, cur, s);
-    case 2048: return summ_once_t<512, 2>(v, cur, s);
-    case 4096:
-        if constexpr (model_dim<SMC_MODEL>::value > 3) return hipErrorInvalidValue;   // (does not fit LDS: the streaming kernels serve it)
-        else return summ_once_t<512, 4>(v, cur, s);
-    case 8192:
-        if constexpr (model_dim<SMC_MODEL>::value > 3) return hipErrorInvalidValue;
-        else return summ_once_t<1024, 4>(v, cur, s);
+template <int MODEL, int VARIANT>
+hipError_t Launch<MODEL, VARIANT>::summ_once(const FilterView& v, int cur, hipStream_t s) {
+    if constexpr (launch_defines(VARIANT, ENTRY_SUMM_ONCE)) {
+        if (v.nseg != 1) return hipErrorInvalidValue;
+        switch (v.seg) {
+        case 256: return summ_once_t<128, 1>(v, cur, s);
+        case 512: return summ_once_t<256, 1>(v, cur, s);
+        case 1024: return summ_once_t<512, 1>(v, cur, s);
+        case 2048: return summ_once_t<512, 2>(v, cur, s);
+        case 4096:
+            if constexpr (model_dim<MODEL>::value > 3) return hipErrorInvalidValue;   // (does not fit LDS: the streaming kernels serve it)
+            else return summ_once_t<512, 4>(v, cur, s);
+        case 8192:
+            if constexpr (model_dim<MODEL>::value > 3) return hipErrorInvalidValue;
+            else return summ_once_t<1024, 4>(v, cur, s);
+        }
     }
     return hipErrorInvalidValue;
 }
-#endif
 
-template <>
-hipError_t SMC_LAUNCH_WINDOW<SMC_MODEL>(const FilterView& v, int T, StepRec* recs, int t0, int bin, int bout, double* win, hipStream_t s) {
-    const int np = resident_np(v);
-    switch (v.seg) {
-    case 256: return window_t<128, 1>(v, T, recs, t0, bin, bout, win, s);
-    case 512: return window_t<256, 1>(v, T, recs, t0, bin, bout, win, s);
-    case 1024: return np == 1 ? window_t<512, 1>(v, T, recs, t0, bin, bout, win, s) : window_t<256, 2>(v, T, recs, t0, bin, bout, win, s);
-    case 2048: return window_t<512, 2>(v, T, recs, t0, bin, bout, win, s);
-    case 4096:
-        if constexpr (model_dim<SMC_MODEL>::value > 3) return hipErrorInvalidValue;
-        else return np == 4 ? window_t<512, 4>(v, T, recs, t0, bin, bout, win, s) : window_t<1024, 2>(v, T, recs, t0, bin, bout, win, s);
-    case 8192:
-        if constexpr (model_dim<SMC_MODEL>::value == 1) return window_t<1024, 4>(v, T, recs, t0, bin, bout, win, s);
-        else return hipErrorInvalidValue;
-    }
-    return hipErrorInvalidValue;
-}
+// this object's entry points
+template struct Launch<SMC_MODEL, VAR>;
 
 }  // namespace smc
-#endif   // !SMC_COND
