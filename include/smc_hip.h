@@ -182,8 +182,8 @@ int smc_device_rb_step(const double* raw, const double* sp, const double* z, dou
  * whole series or window without a NaN.  Per-step summaries, smc_forecast, the record of a step-by-step run, smc_smooth and
  * smc_sample_paths read clouds and weights and need no rule of their own (the smoothed state at a gap is the interpolation).
  * NOT covered: smc_rb_sample_paths (its Kalman / RTS pass along each path reads y: SMC_EINVAL on a flagged handle when y holds a
- * NaN), smc_time_step_kernel (the same refusal), and the exact-Kalman entry points - smc_ibis_*, smc_kalman_log_likelihood,
- * smc_kalman_smooth - which have no flag and keep their behaviour. */
+ * NaN) and smc_time_step_kernel (the same refusal).  The exact-Kalman entry points have the rule as well, opt-in in the same
+ * way: "missing observations of the exact Kalman filter" below (smc_ibis_set_flags and the *_flags calls). */
 /* the flags the handle was created with */
 int smc_get_flags(smc_handle h, uint32_t* flags);
 /* The whole step of n particles on the host, for every family and proposal: xp x [d][n], z [nz][n] (nz = d; 2 for
@@ -422,6 +422,41 @@ int smc_resample(const double* w, int64_t n, int64_t ndraw, uint64_t seed, uint3
  * reference loop; 0 starts at x_1 ~ N(x0, sigma0) like bootstrap_filter. */
 int smc_kalman_log_likelihood(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first,
                               double* out /*[n_theta][3]*/, int device);
+/* ---- missing observations of the exact Kalman filter ---------------------------------------------------------------
+ * Opt-in, as for the particle filters: with SMC_FLAG_NAN_MISSING - set on an IBIS handle by smc_ibis_set_flags, or passed as
+ * the trailing `flags` of the *_flags calls, whose unsuffixed names are their flags = 0 call - a NaN observation is a period
+ * WITHOUT an observation.  The missing Kalman step (csrc/smc_spec.h, beside kalman_step) is kalman_step with the observation's
+ * part left out: the prediction x <- A x, Sigma <- A^2 Sigma + Q as kalman_step forms it (none at the first step of a filter
+ * with predict_first = 0: the state stays (x0, sigma0)), no update, and the value +0.0.  So logZ and logw gain +0.0 and keep
+ * their bits, the outer weights and hence the ESS of a missing step are the previous step's (a gap never triggers a
+ * resample-move by itself), the filtered record at a gap is the predictive pair, the RTS backward pass and the backward-sampled
+ * paths run over that record unchanged (the smoothed state at a gap is the interpolation), and a summary row at a gap is, at
+ * ahead = 0, the predictive law of the unobserved y_t.  Only NaN is missing: +-inf takes the ordinary step.  A NaN WITHOUT the flag
+ * behaves as it always did (it poisons x, Sigma, logZ and logw of every particle).  Every call that runs kalman_step takes the
+ * rule: smc_ibis_window / _window_ess / _commit / _filter / _rejuvenate (so the online logZ and a re-filter of the same
+ * observations stay the same number) / _smooth / _sample_paths on a flagged handle, and the calls below.  The kernels with the
+ * test (a compile-time twin; the test is uniform over a wave) are launched only when the flag is set AND the observations of the
+ * launch hold a NaN: every other launch is the kernel an unflagged handle runs.  Cost: profiles/ibis_missing_cost.log.
+ * NOT covered: smc_rb_sample_paths (above).
+ *   smc_ibis_set_flags   flags = 0 or SMC_FLAG_NAN_MISSING (anything else: SMC_EINVAL).  Only while the handle is at t = 0 with no
+ *                        window pending (else SMC_ESTATE): a series is filtered under one rule from its first step
+ *   smc_ibis_get_flags   the flags of the handle
+ *   smc_host_kalman_steps  the step loop of ONE row on the host (no GPU): row [6], y [T] -> xf, Sf, lik [T] (each or NULL), the
+ *                        filtered record and the value of every step - the host array for every device array of these calls */
+int smc_ibis_set_flags(void* h, uint32_t flags);
+int smc_ibis_get_flags(void* h, uint32_t* flags);
+int smc_kalman_log_likelihood_flags(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first,
+                                    double* out /*[n_theta][3]*/, int device, uint32_t flags);
+int smc_kalman_smooth_flags(const double* raw /*[n_theta][6]*/, int64_t n_theta, const double* y, int64_t T, int predict_first,
+                            double* xs /*[T][n_theta]*/, double* Ps /*[T][n_theta]*/, int device, uint32_t flags);
+int smc_host_ibis_smooth_flags(const double* rows /*[M][6]*/, const double* logw /*[M]*/, int64_t M, const double* y, int64_t T,
+                               int predict_first, double* out /*[T][8]*/, double* xs /*or NULL*/, double* Ps /*or NULL*/,
+                               double* xf /*or NULL*/, double* Sf /*or NULL*/, uint32_t flags);
+int smc_host_ibis_sample_paths_flags(const double* rows, int64_t M, const double* y, int64_t T, int predict_first, int64_t Mp,
+                                     uint64_t path_seed, const int32_t* which, double* paths /*[T][Mp]*/, double* z /*[T][Mp] or NULL*/,
+                                     uint32_t flags);
+int smc_host_kalman_steps(const double* row /*[6]*/, const double* y, int64_t T, int predict_first, uint32_t flags,
+                          double* xf /*[T] or NULL*/, double* Sf /*[T] or NULL*/, double* lik /*[T] or NULL*/);
 /* ---- the IBIS sampler: src/ibis.jl (SMC^2 with the exact Kalman filter inside) ------------------------------------
  * A handle of its own (opaque; `void*` at this boundary) keeps M parameter particles on the device for its whole life:
  * theta, the LinearModel row smc.model(theta) = (A,B,Q,R,x0,sigma0), the Kalman state (x, Sigma), logZ and the

@@ -719,7 +719,7 @@ next_seed!(s::HipIBIS) = (s.calls += 1; (s.seed << 20) + s.calls)
 
 # IBIS(M, model, prior, chain, ess_threshold, min_ar=-1.0)   ibis.jl:26-58
 function HipIBIS(M::Int64, model::SSM, prior::Sampleable, chain::Int64, ess_threshold::Float64, min_ar::Float64=-1.0;
-                 seed::UInt64=rand(UInt64), device::Int=0, predict_first::Bool=false) where SSM
+                 seed::UInt64=rand(UInt64), device::Int=0, predict_first::Bool=false, missing::Bool=false) where SSM
     θ = map(m -> rand(prior), 1:M)                                                # :35
     comps = prior_components(prior)
     specs = comps === nothing ? nothing : hip_prior.(comps)
@@ -729,6 +729,9 @@ function HipIBIS(M::Int64, model::SSM, prior::Sampleable, chain::Int64, ess_thre
     (tm === nothing || tm[1] != 1) && error("IBIS on the GPU needs model(θ) to be a univariate LinearModel row map")
     h = Ref{Ptr{Cvoid}}(C_NULL)
     smc_check(ccall((:smc_ibis_create, LIBSMC), Cint, (Int64, UInt64, Cint, Cint, Ptr{Cvoid}), M, seed, device, predict_first ? 1 : 0, h))
+    # missing=true: SMC_FLAG_NAN_MISSING (8) on the handle, set at t = 0 - a NaN observation is the missing Kalman step (the prediction
+    # alone, +0.0 to logZ and logw) in every call below that takes y: the windows, smc_ibis_filter, the re-filters of rejuvenate!
+    missing && smc_check(ccall((:smc_ibis_set_flags, LIBSMC), Cint, (Ptr{Cvoid}, UInt32), h[], UInt32(8)))
     fam = Int32[s[1] for s in specs]; par = reduce(hcat, [s[2] for s in specs]); rf = Int32.(tm[2]); rc = Float64.(tm[3])
     GC.@preserve fam par rf rc smc_check(ccall((:smc_ibis_configure, LIBSMC), Cint,
         (Ptr{Cvoid}, Cint, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}), h[], dθ, fam, par, rf, rc))

@@ -40,6 +40,8 @@ EXPORTS = [
     "smc_host_smooth", "smc_sample_paths", "smc_host_sample_paths", "smc_rb_sample_paths", "smc_host_rb_sample_paths",
     "smc_forecast", "smc_forecast_cloud", "smc_host_forecast",
     "smc_get_flags", "smc_host_filter_steps", "smc_device_filter_steps",
+    "smc_ibis_set_flags", "smc_ibis_get_flags", "smc_kalman_log_likelihood_flags", "smc_kalman_smooth_flags",
+    "smc_host_ibis_smooth_flags", "smc_host_ibis_sample_paths_flags", "smc_host_kalman_steps",
     "smc_set_reference", "smc_reference_from_paths", "smc_get_reference", "smc_host_conditional_slot", "smc_host_logobs",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
@@ -211,6 +213,13 @@ def lib():
     L.smc_kalman_smooth.argtypes = [_dp, C.c_int64, _dp, C.c_int64, C.c_int, _dp, _dp, C.c_int]
     L.smc_host_ibis_smooth.argtypes = [_dp, _dp, C.c_int64, _dp, C.c_int64, C.c_int, _dp, _dp, _dp, _dp, _dp]
     L.smc_host_ibis_sample_paths.argtypes = [_dp, C.c_int64, _dp, C.c_int64, C.c_int, C.c_int64, C.c_uint64, _i32p, _dp, _dp]
+    L.smc_ibis_set_flags.argtypes = [h, C.c_uint32]
+    L.smc_ibis_get_flags.argtypes = [h, _u32p]
+    L.smc_kalman_log_likelihood_flags.argtypes = L.smc_kalman_log_likelihood.argtypes + [C.c_uint32]
+    L.smc_kalman_smooth_flags.argtypes = L.smc_kalman_smooth.argtypes + [C.c_uint32]
+    L.smc_host_ibis_smooth_flags.argtypes = L.smc_host_ibis_smooth.argtypes + [C.c_uint32]
+    L.smc_host_ibis_sample_paths_flags.argtypes = L.smc_host_ibis_sample_paths.argtypes + [C.c_uint32]
+    L.smc_host_kalman_steps.argtypes = [_dp, _dp, C.c_int64, C.c_int, C.c_uint32, _dp, _dp, _dp]
     L.smc_host_theta_moments.argtypes = [_dp, _dp, C.c_int64, C.c_int, C.c_int, _dp, _dp]
     L.smc_host_rw_factor_cov.argtypes = [_dp, C.c_int, _dp, _ip]
     L.smc_history_begin.argtypes = [h, C.c_int64]
@@ -280,21 +289,38 @@ def resample(w, ndraw=None, seed=0, stream=0, t=0, device=0):
     return a
 
 
-def kalman_log_likelihood(raw, y, predict_first=False, device=0):
+def _kalman_flags(missing):
+    """the `flags` word of the exact-Kalman calls: missing=True reads a NaN observation as a missing one"""
+    return FLAG_NAN_MISSING if missing else 0
+
+
+def kalman_log_likelihood(raw, y, predict_first=False, device=0, missing=False):
     """Batched exact scalar Kalman filter (src/kalman_filter.jl:29-70): rows of (x_T, Sigma_T, logZ)."""
     raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1, 6)
     y = np.ascontiguousarray(y, dtype=np.float64)
     out = np.zeros((raw.shape[0], 3))
-    check(lib().smc_kalman_log_likelihood(_d(raw), raw.shape[0], _d(y), y.size, int(predict_first), _d(out), device))
+    check(lib().smc_kalman_log_likelihood_flags(_d(raw), raw.shape[0], _d(y), y.size, int(predict_first), _d(out), device,
+                                                _kalman_flags(missing)))
     return out
 
 
-def kalman_smooth(raw, y, predict_first=False, device=0):
+def host_kalman_steps(row, y, predict_first=False, missing=False):
+    """(xf, Sf, lik), each [T]: the filtered record and the value of every Kalman step of ONE LG1D row over y on the host
+    (smc_host_kalman_steps; no GPU) - the loop every exact-Kalman kernel runs per lane"""
+    row = np.ascontiguousarray(row, dtype=np.float64).reshape(6)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    xf, Sf, lik = np.zeros(y.size), np.zeros(y.size), np.zeros(y.size)
+    check(lib().smc_host_kalman_steps(_d(row), _d(y), y.size, int(bool(predict_first)), _kalman_flags(missing), _d(xf), _d(Sf), _d(lik)))
+    return xf, Sf, lik
+
+
+def kalman_smooth(raw, y, predict_first=False, device=0, missing=False):
     """Batched exact RTS smoother of LG1D rows (smc_kalman_smooth): (xs, Ps), each [T][n_theta]."""
     raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1, 6)
     y = np.ascontiguousarray(y, dtype=np.float64).ravel()
     xs, Ps = np.zeros((y.size, raw.shape[0])), np.zeros((y.size, raw.shape[0]))
-    check(lib().smc_kalman_smooth(_d(raw), raw.shape[0], _d(y), y.size, int(bool(predict_first)), _d(xs), _d(Ps), int(device)))
+    check(lib().smc_kalman_smooth_flags(_d(raw), raw.shape[0], _d(y), y.size, int(bool(predict_first)), _d(xs), _d(Ps), int(device),
+                                        _kalman_flags(missing)))
     return xs, Ps
 
 
@@ -1113,7 +1139,7 @@ def host_ibis_summary(rows, x, S, logw, ahead=0):
     return out
 
 
-def host_ibis_smooth(rows, logw, y, predict_first=False, states=False, filtered=False):
+def host_ibis_smooth(rows, logw, y, predict_first=False, states=False, filtered=False, missing=False):
     """the RTS smoother of a cloud of LG1D rows [M][6] with outer log-weights logw over y (smc_host_ibis_smooth: the device's
     specification on the host; no GPU) -> out [T][8], the rows of host_ibis_summary per period; with states also xs, Ps [T][M];
     with filtered also the filtered record xf, Sf [T][M] the backward pass ran over"""
@@ -1124,19 +1150,20 @@ def host_ibis_smooth(rows, logw, y, predict_first=False, states=False, filtered=
     out = np.zeros((T, 8))
     xs, Ps = (np.zeros((T, M)), np.zeros((T, M))) if states else (None, None)
     xf, Sf = (np.zeros((T, M)), np.zeros((T, M))) if filtered else (None, None)
-    check(lib().smc_host_ibis_smooth(_d(rows), _d(logw), M, _d(y), T, int(bool(predict_first)), _d(out), _d(xs), _d(Ps), _d(xf), _d(Sf)))
+    check(lib().smc_host_ibis_smooth_flags(_d(rows), _d(logw), M, _d(y), T, int(bool(predict_first)), _d(out), _d(xs), _d(Ps), _d(xf), _d(Sf),
+                                           _kalman_flags(missing)))
     return (out,) + ((xs, Ps) if states else ()) + ((xf, Sf) if filtered else ()) if states or filtered else out
 
 
-def host_ibis_sample_paths(rows, y, which, path_seed, predict_first=False, want_z=False):
+def host_ibis_sample_paths(rows, y, which, path_seed, predict_first=False, want_z=False, missing=False):
     """paths [T][Mp] of smc_host_ibis_sample_paths: path p under row which[p] (no GPU); with want_z also the normals z [T][Mp]"""
     rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 6)
     y = np.ascontiguousarray(y, dtype=np.float64).ravel()
     which = np.ascontiguousarray(which, dtype=np.int32).ravel()
     paths = np.zeros((y.size, which.size))
     z = np.zeros((y.size, which.size)) if want_z else None
-    check(lib().smc_host_ibis_sample_paths(_d(rows), rows.shape[0], _d(y), y.size, int(bool(predict_first)), which.size, int(path_seed),
-                                           which.ctypes.data_as(_i32p), _d(paths), _d(z)))
+    check(lib().smc_host_ibis_sample_paths_flags(_d(rows), rows.shape[0], _d(y), y.size, int(bool(predict_first)), which.size, int(path_seed),
+                                                 which.ctypes.data_as(_i32p), _d(paths), _d(z), _kalman_flags(missing)))
     return (paths, z) if want_z else paths
 
 
@@ -1144,7 +1171,7 @@ class IbisHandle:
     """The device half of the IBIS sampler (smc_ibis_*): M parameter particles with their exact Kalman state, resident on one
     GPU.  d: parameter dimension; families / pars: the prior (distributions.py spec()); raw_from / raw_const: ThetaMap to LG1D rows."""
 
-    def __init__(self, M, d, families, pars, raw_from, raw_const, seed=1, device=0, predict_first=False):
+    def __init__(self, M, d, families, pars, raw_from, raw_const, seed=1, device=0, predict_first=False, flags=0):
         self._h = C.c_void_p()
         self.M, self.d = int(M), int(d)
         self.nseg = (self.M + OUTER_SEG - 1) // OUTER_SEG
@@ -1155,6 +1182,18 @@ class IbisHandle:
         rc = np.ascontiguousarray(raw_const, dtype=np.float64)
         assert fam.size == self.d and rf.size == rc.size == 6
         check(lib().smc_ibis_configure(self._h, self.d, fam.ctypes.data_as(_i32p), _d(par), rf.ctypes.data_as(_i32p), _d(rc)))
+        if flags:                                          # (an unflagged handle makes the calls it made before)
+            self.set_flags(flags)
+
+    def set_flags(self, flags):
+        """0 or FLAG_NAN_MISSING: a NaN observation is a missing Kalman step (smc_ibis_set_flags; only at t = 0)"""
+        check(lib().smc_ibis_set_flags(self._h, int(flags)))
+
+    @property
+    def flags(self):
+        f = C.c_uint32()
+        check(lib().smc_ibis_get_flags(self._h, C.byref(f)))
+        return int(f.value)
 
     def close(self):
         if getattr(self, "_h", None):

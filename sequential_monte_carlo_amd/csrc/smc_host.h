@@ -176,6 +176,13 @@ inline bool series_has_gap(const smc_filter_s* h, const double* y, int64_t T) {
         if (y[t] != y[t]) return true;
     return false;
 }
+// the same decision for the exact-Kalman calls (an IBIS handle's flags, or the `flags` argument of a call without a handle)
+inline bool kalman_has_gap(uint32_t flags, const double* y, int64_t T) {
+    if (!(flags & SMC_FLAG_NAN_MISSING)) return false;
+    for (int64_t t = 0; t < T; ++t)
+        if (y[t] != y[t]) return true;
+    return false;
+}
 // names the series of a whole-series call for its launches (h->gap_y) when the handle is flagged and the series holds a NaN
 struct GapScope {
     smc_filter_s* h;

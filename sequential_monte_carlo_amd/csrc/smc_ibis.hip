@@ -16,6 +16,7 @@ struct smc_ibis_s {
     uint32_t magic = 0x53494249u;   // "IBIS": the boundary type is void*, so a foreign pointer is at least noticed
     int device = 0;
     int predict_first = 0;
+    uint32_t flags = 0;             // smc_ibis_set_flags: 0 or SMC_FLAG_NAN_MISSING (a NaN observation is a missing Kalman step)
     hipStream_t stream = nullptr;
     IbisView v{};
     int cp = 0, cs = 0;             // current (theta, raw) set and current (x, S, logZ, logw) set
@@ -89,11 +90,34 @@ template <int D>
 void launch_init(ibis_t h) {
     hipLaunchKernelGGL((k_ibis_init<D>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->spec);
 }
-template <int D>
-void launch_rejuvenate(ibis_t h, int64_t T, double xi, int chain, uint64_t move_seed) {
-    hipLaunchKernelGGL((k_ibis_rejuvenate<D>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->spec,
+// miss (every launcher below): the handle is flagged AND the observations of this launch hold a NaN - the MISS twin; else the
+// kernels an unflagged handle runs
+template <int D, bool MISS>
+void launch_rejuvenate_as(ibis_t h, int64_t T, double xi, int chain, uint64_t move_seed) {
+    hipLaunchKernelGGL((k_ibis_rejuvenate<D, MISS>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->spec,
                        h->d_y, T, h->predict_first, xi, h->d_chol, h->d_chol + MAX_DTHETA * MAX_DTHETA, chain, move_seed, h->d_moved,
                        h->d_count);
+}
+template <int D>
+void launch_rejuvenate(ibis_t h, bool miss, int64_t T, double xi, int chain, uint64_t move_seed) {
+    if (miss) launch_rejuvenate_as<D, true>(h, T, xi, chain, move_seed);
+    else launch_rejuvenate_as<D, false>(h, T, xi, chain, move_seed);
+}
+template <bool RECORD, bool SUMM>
+void launch_window(ibis_t h, bool miss, int dst, const double* d_y, int k, int predict0, double* lik, uint64_t* rec, double* part, int ahead) {
+    if (miss)
+        hipLaunchKernelGGL((k_ibis_window<RECORD, SUMM, true>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs,
+                           dst, d_y, k, predict0, lik, rec, part, ahead);
+    else
+        hipLaunchKernelGGL((k_ibis_window<RECORD, SUMM, false>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs,
+                           dst, d_y, k, predict0, lik, rec, part, ahead);
+}
+void launch_rts_forward(hipStream_t st, bool miss, const double* raw, int64_t M, const double* d_y, int64_t T, int predict_first, double* xf,
+                        double* Sf) {
+    if (miss)
+        hipLaunchKernelGGL((k_ibis_rts_forward<true>), dim3(grid_of(M)), dim3(IBIS_THREADS), 0, st, raw, M, d_y, T, predict_first, xf, Sf);
+    else
+        hipLaunchKernelGGL((k_ibis_rts_forward<false>), dim3(grid_of(M)), dim3(IBIS_THREADS), 0, st, raw, M, d_y, T, predict_first, xf, Sf);
 }
 #define IBIS_BY_D(d, CALL)                                                                                      \
     switch (d) {                                                                                                \
@@ -108,9 +132,8 @@ int steps_in_place(ibis_t h, const double* y, int64_t steps) {
     int64_t done = 0;
     while (done < steps) {   // (the kernel's step count is an int)
         const int k = (int)(steps - done > (1 << 20) ? (1 << 20) : steps - done);
-        hipLaunchKernelGGL((k_ibis_window<false>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->cs,
-                           h->d_y + done, k, (h->t + done > 0 || h->predict_first) ? 1 : 0, (double*)nullptr, (uint64_t*)nullptr,
-                           (double*)nullptr, 0);
+        launch_window<false, false>(h, kalman_has_gap(h->flags, y + done, k), h->cs, h->d_y + done, k,
+                                    (h->t + done > 0 || h->predict_first) ? 1 : 0, nullptr, nullptr, nullptr, 0);
         HIPCHK(hipGetLastError());
         done += k;
     }
@@ -235,19 +258,17 @@ static int enqueue_window(ibis_t h, const char* who, const double* y, int k, boo
     h->srow_k = 0;
     if (h->summ_on) HIPCHK(grow(&h->d_part, &h->part_cap, (size_t)k * IBIS_SUM_NCOL * nchunk));
     HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)k * 8, hipMemcpyHostToDevice, h->stream));
+    const bool miss = kalman_has_gap(h->flags, y, k);
+    const int predict0 = (h->t > 0 || h->predict_first) ? 1 : 0;
     if (h->summ_on) {   // the same steps, and the chunk records of the summaries after each; then one workgroup per row combines them
-        hipLaunchKernelGGL((k_ibis_window<true, true>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs,
-                           h->cs ^ 1, h->d_y, k, (h->t > 0 || h->predict_first) ? 1 : 0, lik ? h->d_lik : (double*)nullptr, h->d_rec,
-                           h->d_part, h->summ_ahead);
+        launch_window<true, true>(h, miss, h->cs ^ 1, h->d_y, k, predict0, lik ? h->d_lik : nullptr, h->d_rec, h->d_part, h->summ_ahead);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_ibis_sum_combine, dim3((unsigned)k), dim3(IBIS_SUM_CTHREADS), 0, h->stream, h->d_part, (int64_t)nchunk,
                            h->d_srow);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h->srow, h->d_srow, (size_t)k * IBIS_SUM_NOUT * 8, hipMemcpyDeviceToHost, h->stream));
     } else {
-        hipLaunchKernelGGL((k_ibis_window<true>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->cs ^ 1,
-                           h->d_y, k, (h->t > 0 || h->predict_first) ? 1 : 0, lik ? h->d_lik : (double*)nullptr, h->d_rec,
-                           (double*)nullptr, 0);
+        launch_window<true, false>(h, miss, h->cs ^ 1, h->d_y, k, predict0, lik ? h->d_lik : nullptr, h->d_rec, nullptr, 0);
         HIPCHK(hipGetLastError());
     }
     return SMC_OK;
@@ -310,6 +331,25 @@ extern "C" int smc_ibis_set_summaries(void* hp, int on, int ahead) {
     h->summ_on = on != 0;
     h->summ_ahead = ahead;
     h->srow_k = 0;
+    return SMC_OK;
+}
+
+// SMC_FLAG_NAN_MISSING for the handle: a series is filtered under one rule from its first step, so only at t = 0 with no window
+// pending
+extern "C" int smc_ibis_set_flags(void* hp, uint32_t flags) {
+    ibis_t h = as_ibis(hp);
+    if (!h) return fail(SMC_EINVAL, "smc_ibis_set_flags: not an IBIS handle");
+    if (flags & ~SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_ibis_set_flags: flags is 0 or SMC_FLAG_NAN_MISSING");
+    if (h->t != 0 || h->win_k > 0)
+        return fail(SMC_ESTATE, "smc_ibis_set_flags: observations have been taken (or a window is pending): the flag is set at t = 0");
+    h->flags = flags;
+    return SMC_OK;
+}
+
+extern "C" int smc_ibis_get_flags(void* hp, uint32_t* flags) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !flags) return fail(SMC_EINVAL, "smc_ibis_get_flags: bad argument");
+    *flags = h->flags;
     return SMC_OK;
 }
 
@@ -482,7 +522,8 @@ extern "C" int smc_ibis_rejuvenate(void* hp, const double* y, int64_t T, double 
     HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_chol, par, sizeof(par), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->d_count, 0, 8, h->stream));
-#define IBIS_CALL_REJ(D) launch_rejuvenate<D>(h, T, xi, chain, move_seed)
+    const bool miss = kalman_has_gap(h->flags, y, T);
+#define IBIS_CALL_REJ(D) launch_rejuvenate<D>(h, miss, T, xi, chain, move_seed)
     IBIS_BY_D(d, IBIS_CALL_REJ)
     HIPCHK(hipGetLastError());
     unsigned long long n = 0;
@@ -658,8 +699,7 @@ extern "C" int smc_ibis_smooth(void* hp, const double* y, int64_t T, double* out
     HIPCHK(ev.create());
     HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipEventRecord(ev.e0, h->stream));
-    hipLaunchKernelGGL(k_ibis_rts_forward, dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, (const double*)h->v.raw[h->cp], h->v.M,
-                       (const double*)d_y, T, h->predict_first, d_xf, d_Sf);
+    launch_rts_forward(h->stream, kalman_has_gap(h->flags, y, T), h->v.raw[h->cp], h->v.M, d_y, T, h->predict_first, d_xf, d_Sf);
     if (store)
         hipLaunchKernelGGL((k_ibis_rts_backward<true, true>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream,
                            (const double*)h->v.raw[h->cp], (const double*)h->v.logw[h->cs], h->v.M, T, d_xf, d_Sf, d_part);
@@ -700,8 +740,12 @@ extern "C" int smc_ibis_sample_paths(void* hp, const double* y, int64_t T, int64
     HIPCHK(ev.create());
     HIPCHK(hipMemcpyAsync(d_w, which, sM * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipEventRecord(ev.e0, h->stream));
-    hipLaunchKernelGGL(k_ibis_rts_paths, dim3(grid_of(Mp)), dim3(IBIS_THREADS), 0, h->stream, (const double*)h->v.raw[h->cp],
-                       (const int32_t*)d_w, Mp, (const double*)d_y, T, h->predict_first, path_seed, d_paths, d_Sf);
+    if (kalman_has_gap(h->flags, y, T))
+        hipLaunchKernelGGL((k_ibis_rts_paths<true>), dim3(grid_of(Mp)), dim3(IBIS_THREADS), 0, h->stream, (const double*)h->v.raw[h->cp],
+                           (const int32_t*)d_w, Mp, (const double*)d_y, T, h->predict_first, path_seed, d_paths, d_Sf);
+    else
+        hipLaunchKernelGGL((k_ibis_rts_paths<false>), dim3(grid_of(Mp)), dim3(IBIS_THREADS), 0, h->stream, (const double*)h->v.raw[h->cp],
+                           (const int32_t*)d_w, Mp, (const double*)d_y, T, h->predict_first, path_seed, d_paths, d_Sf);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev.e1, h->stream));
     HIPCHK(hipMemcpyAsync(paths, d_paths, sT * sM * 8, hipMemcpyDeviceToHost, h->stream));
@@ -719,8 +763,9 @@ extern "C" int smc_ibis_last_elapsed_ms(void* hp, double* ms) {
 }
 
 // the per-row half of smc_ibis_smooth without a handle: the counterpart of smc_kalman_log_likelihood
-extern "C" int smc_kalman_smooth(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first, double* xs, double* Ps,
-                                 int device) {
+extern "C" int smc_kalman_smooth_flags(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first, double* xs,
+                                       double* Ps, int device, uint32_t flags) {
+    if (flags & ~SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_kalman_smooth: flags is 0 or SMC_FLAG_NAN_MISSING");
     if (!raw || !y || !xs || !Ps) return fail(SMC_EINVAL, "smc_kalman_smooth: bad argument");
     if (n_theta < 1 || n_theta > ((int64_t)1 << 30) || T < 1 || T > RTS_MAX_T) return fail(SMC_EINVAL, "smc_kalman_smooth: 1 <= n_theta <= 2^30, 1 <= T <= 2^31");
     int ndev = 0;
@@ -735,8 +780,7 @@ extern "C" int smc_kalman_smooth(const double* raw, int64_t n_theta, const doubl
     hipStream_t st = nullptr;   // the default stream: the call owns nothing that outlives it
     HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_raw, raw, M * IBIS_NRAW * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_ibis_rts_forward, dim3(grid_of(n_theta)), dim3(IBIS_THREADS), 0, st, (const double*)d_raw, n_theta, (const double*)d_y, T,
-                       predict_first ? 1 : 0, d_xf, d_Sf);
+    launch_rts_forward(st, kalman_has_gap(flags, y, T), d_raw, n_theta, d_y, T, predict_first ? 1 : 0, d_xf, d_Sf);
     hipLaunchKernelGGL((k_ibis_rts_backward<false, true>), dim3(grid_of(n_theta)), dim3(IBIS_THREADS), 0, st, (const double*)d_raw,
                        (const double*)nullptr, n_theta, T, d_xf, d_Sf, (double*)nullptr);
     HIPCHK(hipGetLastError());
@@ -745,10 +789,40 @@ extern "C" int smc_kalman_smooth(const double* raw, int64_t n_theta, const doubl
     HIPCHK(hipStreamSynchronize(st));
     return SMC_OK;
 }
+extern "C" int smc_kalman_smooth(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first, double* xs, double* Ps,
+                                 int device) {
+    return smc_kalman_smooth_flags(raw, n_theta, y, T, predict_first, xs, Ps, device, 0);
+}
+
+namespace {
+// one step of a host twin: the flag read once per series (a NaN without it takes the ordinary step)
+inline double host_kalman_step(bool miss, const double* r, bool predict, double y, double& x, double& S) {
+    return miss ? kalman_step_gaps<true>(r[0], r[1], r[2], r[3], predict, y, x, S) : kalman_step(r[0], r[1], r[2], r[3], predict, y, x, S);
+}
+}  // namespace
+
+// The step loop of one row on the host (no GPU): the filtered record and the value of every step, so that every array the
+// device calls produce has a host array to be compared with.  row [6], y [T] -> xf, Sf, lik [T] (each optional)
+extern "C" int smc_host_kalman_steps(const double* row, const double* y, int64_t T, int predict_first, uint32_t flags, double* xf,
+                                     double* Sf, double* lik) {
+    if (!row || !y || T < 1) return fail(SMC_EINVAL, "smc_host_kalman_steps: bad argument");
+    if (flags & ~SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_host_kalman_steps: flags is 0 or SMC_FLAG_NAN_MISSING");
+    const bool miss = (flags & SMC_FLAG_NAN_MISSING) != 0;
+    double x = row[4], S = row[5];
+    for (int64_t t = 0; t < T; ++t) {
+        const double l = host_kalman_step(miss, row, t > 0 || predict_first != 0, y[t], x, S);
+        if (xf) xf[t] = x;
+        if (Sf) Sf[t] = S;
+        if (lik) lik[t] = l;
+    }
+    return SMC_OK;
+}
 
 // The same specification on the host (no GPU), the same bits.  xf, Sf: the filtered record the backward pass ran over.
-extern "C" int smc_host_ibis_smooth(const double* rows, const double* logw, int64_t M, const double* y, int64_t T, int predict_first,
-                                    double* out, double* xs, double* Ps, double* xf, double* Sf) {
+extern "C" int smc_host_ibis_smooth_flags(const double* rows, const double* logw, int64_t M, const double* y, int64_t T, int predict_first,
+                                          double* out, double* xs, double* Ps, double* xf, double* Sf, uint32_t flags) {
+    if (flags & ~SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_host_ibis_smooth: flags is 0 or SMC_FLAG_NAN_MISSING");
+    const bool miss = (flags & SMC_FLAG_NAN_MISSING) != 0;
     if (!rows || !logw || !y || !out || M < 1) return fail(SMC_EINVAL, "smc_host_ibis_smooth: bad argument");
     if (T < 1 || T > RTS_MAX_T) return fail(SMC_EINVAL, "smc_host_ibis_smooth: 1 <= T <= 2^31");
     const size_t sM = (size_t)M, sT = (size_t)T;
@@ -759,7 +833,7 @@ extern "C" int smc_host_ibis_smooth(const double* rows, const double* logw, int6
         const double* r = rows + m * IBIS_NRAW;
         double x = r[4], S = r[5];
         for (size_t t = 0; t < sT; ++t) {
-            (void)kalman_step(r[0], r[1], r[2], r[3], t > 0 || predict_first != 0, y[t], x, S);
+            (void)host_kalman_step(miss, r, t > 0 || predict_first != 0, y[t], x, S);
             xs[t * sM + m] = x;
             Ps[t * sM + m] = S;
             if (xf) xf[t * sM + m] = x;
@@ -776,9 +850,15 @@ extern "C" int smc_host_ibis_smooth(const double* rows, const double* logw, int6
         if (const int rc = smc_host_ibis_summary(rows, xs + t * sM, Ps + t * sM, logw, M, 0, out + t * IBIS_SUM_NOUT)) return rc;
     return SMC_OK;
 }
+extern "C" int smc_host_ibis_smooth(const double* rows, const double* logw, int64_t M, const double* y, int64_t T, int predict_first,
+                                    double* out, double* xs, double* Ps, double* xf, double* Sf) {
+    return smc_host_ibis_smooth_flags(rows, logw, M, y, T, predict_first, out, xs, Ps, xf, Sf, 0);
+}
 
-extern "C" int smc_host_ibis_sample_paths(const double* rows, int64_t M, const double* y, int64_t T, int predict_first, int64_t Mp,
-                                          uint64_t path_seed, const int32_t* which, double* paths, double* z) {
+extern "C" int smc_host_ibis_sample_paths_flags(const double* rows, int64_t M, const double* y, int64_t T, int predict_first, int64_t Mp,
+                                                uint64_t path_seed, const int32_t* which, double* paths, double* z, uint32_t flags) {
+    if (flags & ~SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_host_ibis_sample_paths: flags is 0 or SMC_FLAG_NAN_MISSING");
+    const bool miss = (flags & SMC_FLAG_NAN_MISSING) != 0;
     if (!rows || !y || !which || !paths || M < 1) return fail(SMC_EINVAL, "smc_host_ibis_sample_paths: bad argument");
     if (T < 1 || T > RTS_MAX_T) return fail(SMC_EINVAL, "smc_host_ibis_sample_paths: 1 <= T <= 2^31");
     if (Mp < 1 || Mp > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_host_ibis_sample_paths: 1 <= Mp <= 2^30");
@@ -791,7 +871,7 @@ extern "C" int smc_host_ibis_sample_paths(const double* rows, int64_t M, const d
         const uint32_t stream = (uint32_t)which[p];
         double x = r[4], S = r[5];
         for (size_t t = 0; t < sT; ++t) {
-            (void)kalman_step(r[0], r[1], r[2], r[3], t > 0 || predict_first != 0, y[t], x, S);
+            (void)host_kalman_step(miss, r, t > 0 || predict_first != 0, y[t], x, S);
             paths[t * sM + (size_t)p] = x;
             Sf[t] = S;
         }
@@ -807,4 +887,8 @@ extern "C" int smc_host_ibis_sample_paths(const double* rows, int64_t M, const d
         }
     }
     return SMC_OK;
+}
+extern "C" int smc_host_ibis_sample_paths(const double* rows, int64_t M, const double* y, int64_t T, int predict_first, int64_t Mp,
+                                          uint64_t path_seed, const int32_t* which, double* paths, double* z) {
+    return smc_host_ibis_sample_paths_flags(rows, M, y, T, predict_first, Mp, path_seed, which, paths, z, 0);
 }

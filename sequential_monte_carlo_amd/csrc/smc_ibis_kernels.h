@@ -243,7 +243,10 @@ __global__ __launch_bounds__(IBIS_SUM_CTHREADS) void k_ibis_sum_combine(double* 
 // predict0: whether the first of the k steps predicts (false only at t = 1 of a sampler with predict_first = 0).
 // SUMM: also the chunk record of the summaries after every step (row j of part), from the registers the step left: the
 // operands the stand-alone k_ibis_sum_chunks reads back after the same steps, so the same bits.
-template <bool RECORD, bool SUMM = false>
+// MISS (handles with SMC_FLAG_NAN_MISSING, launched only when the window holds a NaN): a NaN y[j] is the missing Kalman step of
+// smc_spec.h - y[j] is one address for all lanes, so the test is uniform over the wave.  logw gains +0.0, so the record of
+// such a step is the previous step's.  MISS = false is the kernel as it always was.
+template <bool RECORD, bool SUMM = false, bool MISS = false>
 __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_window(IbisView v, int cp, int cs, int dst, const double* y, int k, int predict0,
                                                              double* lik /*[k][M] or null*/, uint64_t* rec /*[k][nseg][4]*/,
                                                              double* part /*[k][IBIS_SUM_NCOL][nchunk]*/, int ahead) {
@@ -255,7 +258,7 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_window(IbisView v, int cp
     double x = v.x[cs][mm], S = v.S[cs][mm], logZ = v.logZ[cs][mm], logw = v.logw[cs][mm];
     const int64_t nseg = (v.M + IBIS_OSEG - 1) / IBIS_OSEG;
     for (int j = 0; j < k; ++j) {
-        const double l = kalman_step(A, B, Q, R, j > 0 || predict0 != 0, y[j], x, S);
+        const double l = kalman_step_gaps<MISS>(A, B, Q, R, j > 0 || predict0 != 0, y[j], x, S);
         logw = logw + l;
         logZ = logZ + l;
         if (RECORD) {
@@ -298,7 +301,8 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_window(IbisView v, int cp
 //           then theta, logZ, x, S <- theta', logZ', x', S'; acc_array[m] = 1          :102-115
 //   omega[m] = 1                                          logw[m] = 0                  :118
 // y[t] is the same address in every lane (the compiler reads it through the scalar cache); chol [D][D] and sq [chain] likewise.
-template <int D>
+// MISS: as in k_ibis_window - the re-filter skips the update at a NaN y[t], the same steps the online logZ took.
+template <int D, bool MISS = false>
 __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rejuvenate(IbisView v, int cp, int cs, PmmhSpec s, const double* y, int64_t T,
                                                                  int predict_first, double xi, const double* chol, const double* sq,
                                                                  int chain, uint64_t move_seed, unsigned char* moved,
@@ -321,7 +325,7 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rejuvenate(IbisView v, in
         ibis_row<D>(s, pr, prow);
         const double lpp = pmmh_logprior<D>(s, pr), lpc = pmmh_logprior<D>(s, th);
         double xp = prow[4], Sp = prow[5], logZp = 0.0;
-        for (int64_t t = 0; t < T; ++t) logZp += kalman_step(prow[0], prow[1], prow[2], prow[3], predict_first != 0 || t > 0, y[t], xp, Sp);
+        for (int64_t t = 0; t < T; ++t) logZp += kalman_step_gaps<MISS>(prow[0], prow[1], prow[2], prow[3], predict_first != 0 || t > 0, y[t], xp, Sp);
         const double likelihood_ratio = xi * (logZp - logZ), prior_ratio = lpp - lpc;
         const double acc_ratio = likelihood_ratio + prior_ratio, log_post_prop = logZp + lpp;
         const bool acc = ok && log_post_prop > -inf() && pmmh_log_uniform(move_seed, stream, (uint32_t)c) < acc_ratio;

@@ -18,6 +18,9 @@
 
 namespace smc {
 
+// MISS (both filters of this file; launched only for a flagged call whose series holds a NaN): the missing Kalman step of
+// smc_spec.h at a NaN y[t] - the record at a gap is the predictive pair, and the backward passes run over it as they are
+template <bool MISS = false>
 __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rts_forward(const double* raw /*[M][IBIS_NRAW]*/, int64_t M, const double* y,
                                                                   int64_t T, int predict_first, double* xf, double* Sf) {
     const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
@@ -26,7 +29,7 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rts_forward(const double*
     const double A = row[0], B = row[1], Q = row[2], R = row[3];
     double x = row[4], S = row[5];
     for (int64_t t = 0; t < T; ++t) {
-        (void)kalman_step(A, B, Q, R, t > 0 || predict_first != 0, y[t], x, S);
+        (void)kalman_step_gaps<MISS>(A, B, Q, R, t > 0 || predict_first != 0, y[t], x, S);
         xf[(size_t)t * (size_t)M + (size_t)m] = x;
         Sf[(size_t)t * (size_t)M + (size_t)m] = S;
     }
@@ -63,6 +66,7 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rts_backward(const double
 }
 
 // paths [T][Mp]: holds xf of the path's particle on the way forward, the path on the way back; Sf [T][Mp] scratch
+template <bool MISS = false>
 __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rts_paths(const double* raw, const int32_t* which, int64_t Mp, const double* y,
                                                                 int64_t T, int predict_first, uint64_t path_seed, double* paths,
                                                                 double* Sf) {
@@ -75,7 +79,7 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rts_paths(const double* r
     const size_t sM = (size_t)Mp, sp = (size_t)p;
     double x = row[4], S = row[5];
     for (int64_t t = 0; t < T; ++t) {
-        (void)kalman_step(A, B, Q, R, t > 0 || predict_first != 0, y[t], x, S);
+        (void)kalman_step_gaps<MISS>(A, B, Q, R, t > 0 || predict_first != 0, y[t], x, S);
         if (t < T - 1) {                               // (the last entry stays in registers)
             paths[(size_t)t * sM + sp] = x;
             Sf[(size_t)t * sM + sp] = S;

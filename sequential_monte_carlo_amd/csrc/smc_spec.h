@@ -855,6 +855,23 @@ SMC_HD double kalman_step(double A, double B, double Q, double R, bool predict, 
     S = S - (K * K) * inv;
     return -0.5 * (0x1.d67f1c864beb5p+0 + sp_log(s) + (dy / s) * dy);
 }
+// The MISSING Kalman step (opt-in: SMC_FLAG_NAN_MISSING on an IBIS handle, `flags` of the calls without one): kalman_step with the
+// observation's part left out.  The prediction is kalman_step's, the same expressions in the same association; there is no
+// update; the step's value is +0.0, so logZ and logw gain +0.0 and a finite value keeps its bits.  With `predict` false (the first
+// step of a filter with predict_first = 0) the state stays (x0, sigma0).  Consequences: logw is unchanged, so the ESS record of a
+// missing step is the previous step's; the filtered record (xf_t, Sf_t) at a gap is the predictive pair, over which rts_gain /
+// rts_back / rts_path_* run as they are (the backward pass interpolates through the gap); ibis_obs_moments at ahead = 0 gives the
+// predictive law of the unobserved y_t.
+SMC_HD double kalman_step_missing(double A, double Q, bool predict, double& x, double& S) {
+    if (predict) { x = A * x; S = (A * A) * S + Q; }
+    return 0.0;
+}
+// One step of a series under the flag: only a NaN y is missing (+-inf takes the ordinary step).  MISS = false is kalman_step.
+template <bool MISS>
+SMC_HD double kalman_step_gaps(double A, double B, double Q, double R, bool predict, double y, double& x, double& S) {
+    if (MISS && y != y) return kalman_step_missing(A, Q, predict, x, S);
+    return kalman_step(A, B, Q, R, predict, y, x, S);
+}
 
 // ---- summaries of an IBIS cloud (src/plotting_utils.jl:94-137: observation_dist, estimated_trend, quantile) -----------------
 // Particle m: row (A, B, Q, R), filtered state (x, S), outer log-weight logw.  With omega_m the normalised weight of logw:

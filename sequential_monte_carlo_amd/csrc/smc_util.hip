@@ -145,8 +145,9 @@ extern "C" int smc_resample(const double* w, int64_t n, int64_t ndraw, uint64_t 
     return SMC_OK;
 }
 
-extern "C" int smc_kalman_log_likelihood(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first,
-                                         double* out, int device) {
+extern "C" int smc_kalman_log_likelihood_flags(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first,
+                                               double* out, int device, uint32_t flags) {
+    if (flags & ~SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_kalman_log_likelihood: flags is 0 or SMC_FLAG_NAN_MISSING");
     if (!raw || !y || !out || n_theta <= 0 || T <= 0) return fail(SMC_EINVAL, "smc_kalman_log_likelihood: bad argument");
     hipStream_t st = nullptr;
     HIPCHK(util_stream(device, &st));
@@ -156,12 +157,20 @@ extern "C" int smc_kalman_log_likelihood(const double* raw, int64_t n_theta, con
     HIPCHK(d_out.alloc((size_t)n_theta * 24));
     HIPCHK(hipMemcpyAsync(d_raw.p, raw, (size_t)n_theta * 48, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_y.p, y, (size_t)T * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_kalman, dim3((unsigned)((n_theta + 63) / 64)), dim3(64), 0, st, d_raw.as<double>(), n_theta, d_y.as<double>(), T,
-                       predict_first, d_out.as<double>());
+    if (kalman_has_gap(flags, y, T))   // the MISS twin only for a flagged call whose series holds a NaN
+        hipLaunchKernelGGL((k_kalman<true>), dim3((unsigned)((n_theta + 63) / 64)), dim3(64), 0, st, d_raw.as<double>(), n_theta,
+                           d_y.as<double>(), T, predict_first, d_out.as<double>());
+    else
+        hipLaunchKernelGGL((k_kalman<false>), dim3((unsigned)((n_theta + 63) / 64)), dim3(64), 0, st, d_raw.as<double>(), n_theta,
+                           d_y.as<double>(), T, predict_first, d_out.as<double>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out.p, (size_t)n_theta * 24, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return SMC_OK;
+}
+extern "C" int smc_kalman_log_likelihood(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first,
+                                         double* out, int device) {
+    return smc_kalman_log_likelihood_flags(raw, n_theta, y, T, predict_first, out, device, 0);
 }
 
 // ---- host-side helpers ---------------------------------------------------------------------------

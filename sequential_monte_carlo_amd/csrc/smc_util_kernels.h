@@ -5,13 +5,15 @@
 namespace smc {
 
 // exact scalar Kalman filter, one lane per parameter row   kalman_filter.jl:29-70
+// MISS (smc_kalman_log_likelihood_flags with SMC_FLAG_NAN_MISSING and a NaN in y): a NaN y[t] is the missing Kalman step
+template <bool MISS = false>
 __global__ void k_kalman(const double* raw, int64_t ntheta, const double* y, int64_t T, int predict_first, double* out) {
     const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= ntheta) return;
     const double A = raw[m * 6 + 0], B = raw[m * 6 + 1], Q = raw[m * 6 + 2], R = raw[m * 6 + 3];
     double x = raw[m * 6 + 4], S = raw[m * 6 + 5], logZ = 0.0;
     for (int64_t t = 0; t < T; ++t) {
-        logZ += kalman_step(A, B, Q, R, predict_first || t > 0, y[t], x, S);
+        logZ += kalman_step_gaps<MISS>(A, B, Q, R, predict_first || t > 0, y[t], x, S);
     }
     out[m * 3 + 0] = x; out[m * 3 + 1] = S; out[m * 3 + 2] = logZ;
 }

@@ -25,6 +25,11 @@ the two paths agree up to that rounding only.  That is why the flag is opt-in; t
 `model` is the reference's closure and is kept for the caller; the device evaluates `theta_map` (ThetaMap to LG1D rows) and a
 prior of the enumerated families instead - a GPU cannot call a closure, so both are required.
 
+missing=True (opt-in, as for SMC): a NaN in y is a period without an observation.  Every Kalman step of the sampler - online,
+in the re-filters of rejuvenate_ and density_tempered, in the RTS smoother and the paths - is then the missing step at a NaN:
+the prediction alone, +0.0 to logZ and logw, so the ESS of a gap is the previous period's and a gap never starts a
+resample-move by itself.  Every function of this module reads the flag from the sampler.
+
 predict_first: the reference's smc²(ibis, y) runs kalman_filter on y[1], which predicts before the first update
 (kalman_filter.jl:39-40).  As in log_likelihood_kalman the default (False) starts from x_1 ~ N(x0, sigma0), the limit of the
 particle filters; True is the literal loop.  The flag holds online and in every re-filter alike, so logZ[m] always equals
@@ -45,7 +50,7 @@ class IBIS:
     on access; no device call is made before the first sampler call."""
 
     def __init__(self, M, model, prior, chain, ess_threshold, min_ar=-1.0, seed=1, theta_map=None, device=0, predict_first=False,
-                 device_moves=False):
+                 device_moves=False, missing=False):
         self.M, self.model, self.prior, self.chain = int(M), model, prior, int(chain)
         if theta_map is None or getattr(theta_map, "model_id", None) != _lib.MODEL_LG1D:
             raise TypeError("IBIS needs theta_map=ThetaMap(LG1D rows): the Kalman filter inside runs on the GPU, which cannot call "
@@ -67,6 +72,7 @@ class IBIS:
         if self.chain > 64:
             raise ValueError("chain <= 64")
         self.device, self.predict_first, self.device_moves = int(device), bool(predict_first), bool(device_moves)
+        self.missing = bool(missing)
         self.ess = float(self.M)
         self.ess_min = self.M * float(ess_threshold)
         self.acc_threshold, self.acc_ratio = float(min_ar), 0.0
@@ -83,7 +89,8 @@ class IBIS:
         if self._h is None:
             fam, par = self.prior_spec
             self._h = _lib.IbisHandle(self.M, self._theta0.shape[1], fam, par, self.theta_map.raw_from, self.theta_map.raw_const,
-                                      seed=self.seed, device=self.device, predict_first=self.predict_first)
+                                      seed=self.seed, device=self.device, predict_first=self.predict_first,
+                                      flags=_lib.FLAG_NAN_MISSING if self.missing else 0)
             self._h.set_theta(self._theta0)
         return self._h
 
@@ -241,7 +248,7 @@ def _rts_rows(ibis, y):
     if y.size < 1:
         raise ValueError("y must hold at least one observation")
     if ibis._h is None:
-        return _lib.host_ibis_smooth(ibis.theta_map.rows(ibis._theta0), np.zeros(ibis.M), y, ibis.predict_first)
+        return _lib.host_ibis_smooth(ibis.theta_map.rows(ibis._theta0), np.zeros(ibis.M), y, ibis.predict_first, missing=ibis.missing)
     return ibis._h.smooth(y)
 
 
@@ -284,7 +291,8 @@ def rts_smoothed_paths(ibis, y, M, seed=None):
     seed = (((ibis.seed << 20) | 0x4754B) if seed is None else int(seed)) & _U64
     which = np.asarray(_lib.host_outer_resample(ibis.logw, M, (seed + 1) & _U64), dtype=np.int32)
     if ibis._h is None:
-        return _lib.host_ibis_sample_paths(ibis.theta_map.rows(ibis._theta0), y, which, (seed + 2) & _U64, ibis.predict_first)
+        return _lib.host_ibis_sample_paths(ibis.theta_map.rows(ibis._theta0), y, which, (seed + 2) & _U64, ibis.predict_first,
+                                           missing=ibis.missing)
     return ibis._h.sample_paths(y, which, (seed + 2) & _U64)
 
 
