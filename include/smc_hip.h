@@ -720,6 +720,29 @@ int smc_host_transition_logpdf(int model_id, const double* raw, const double* xp
 int smc_host_smooth(int model_id, const double* raw, int64_t T, int64_t n, const double* x /*[T][d][n]*/, const double* w /*[T][n]*/,
                     double* ws /*[T][n]*/, double* mean /*[T][d] or NULL*/, double* var /*[T][d] or NULL*/);
 
+/* ---- the smoother: lag-one pair moments (csrc/smc_spec.h "lag-one pair moments") -------------------------------
+ * The backward pass forms every pair probability p_ij = P(particle i at t, particle j at t+1 | y_1:T) on its way to ws_t and keeps
+ * only the row sums.  smc_smooth_pairs keeps two moments of the pairs as well, at the precision of the marginals and without paths:
+ *     cross[t][a][c] = sum_ij p_ij x_t^{i,a} x_{t+1}^{j,c}            = E[x_t^a x_{t+1}^c | y_1:T]
+ *     resid2[t][c]   = sum_ij p_ij (x_{t+1}^{j,c} - m_c(x_t^i))^2     = E[(x_{t+1}^c - m_c(x_t))^2 | y_1:T]
+ * for t = 0 .. T-2, m the centre of the transition (LG1D: A x; SV1D: mu + rho (x - mu); UCSV3D: x): the E-step of a state-space
+ * EM, and with the marginal means the lag-one smoothed covariance cross - mean_t mean_{t+1}.
+ *   smc_smooth_pairs       smc_smooth (its refusals, its state rules, its results: ws, mean, var are bit for bit smc_smooth's) with
+ *                          cross [T-1][d][d][n_theta] and resid2 [T-1][d][n_theta]; either may be NULL, with both NULL the call IS
+ *                          smc_smooth.  Particles of weight 0 are left out whatever their states; no renormalisation; NaN everywhere
+ *                          for a filter that collapsed at a recorded step; T = 1: nothing is written.  Any record: guided, systematic,
+ *                          with gaps, conditional, or planted (smc_history_put).  May be repeated, also after more steps.  The
+ *                          chunk partials, (1 + 2 d) n_chunks n_theta n_x doubles, live in a block of their own that the first
+ *                          such call allocates: handles that never ask for pairs allocate and launch what they always did.
+ *                          Cost: profiles/pairs_cost.log (DESIGN.md 2m "Cost")
+ *   smc_host_smooth_pairs  the same specification for ONE filter on the host (no GPU), the same bits: cross [T-1][d][d], resid2
+ *                          [T-1][d] (NULL only when T = 1); ws, mean, var as smc_host_smooth */
+int smc_smooth_pairs(smc_handle h, double* ws /*[T][n_theta][n_x] or NULL*/, double* mean /*[T][d][n_theta] or NULL*/, double* var /*[T][d][n_theta] or NULL*/,
+                     double* cross /*[T-1][d][d][n_theta] or NULL*/, double* resid2 /*[T-1][d][n_theta] or NULL*/);
+int smc_host_smooth_pairs(int model_id, const double* raw, int64_t T, int64_t n, const double* x /*[T][d][n]*/, const double* w /*[T][n]*/,
+                          double* ws /*[T][n]*/, double* mean /*[T][d] or NULL*/, double* var /*[T][d] or NULL*/,
+                          double* cross /*[T-1][d][d]*/, double* resid2 /*[T-1][d]*/);
+
 /* ---- backward simulation: joint smoothing paths (FFBSi; Godsill, Doucet and West 2004) --------------------------------------
  * smc_smooth gives the marginals p(x_t | y_1:T).  Whatever depends on two or more times at once (the smoothed change of the
  * trend, the cycle as a path, lag covariances, the complete-data sums of a particle EM or Gibbs step) needs whole trajectories

@@ -13,6 +13,7 @@ from .models import (UCSV, LinearModel, MarginalUCSV, StateSpaceModel, Stochasti
                      simulate, unobserved_components, unobserved_components_stochastic_volatility)
 from .particles import (AffineGaussianProposal, OptimalProposal, ParticleGibbs, bootstrap_filter, bootstrap_filter_, forecast, log_likelihood, normalize,  # noqa: F401
                         optimal_proposal, particle_filter, particle_filter_, rb_smoother, resample, reweight, smoother, trend_moments)
+from .particles import em_mstep, particle_em  # noqa: F401
 from .smc_samplers import (SMC, ThetaMap, density_tempered, estimated_trend, expected_parameters, filtered_state, forecast_state,  # noqa: F401
                            filtered_summaries, observation_dist, posterior_moments, quantile, rejuvenate_, resample_, smc2, smc2_run, smc2_step,
                            rb_smoothed_state, smoothed_paths, smoothed_state)

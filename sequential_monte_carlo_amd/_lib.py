@@ -43,6 +43,7 @@ EXPORTS = [
     "smc_ibis_set_flags", "smc_ibis_get_flags", "smc_kalman_log_likelihood_flags", "smc_kalman_smooth_flags",
     "smc_host_ibis_smooth_flags", "smc_host_ibis_sample_paths_flags", "smc_host_kalman_steps",
     "smc_set_reference", "smc_reference_from_paths", "smc_get_reference", "smc_host_conditional_slot", "smc_host_logobs",
+    "smc_smooth_pairs", "smc_host_smooth_pairs",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -230,6 +231,8 @@ def lib():
     L.smc_smooth.argtypes = [h, _dp, _dp, _dp]
     L.smc_host_transition_logpdf.argtypes = [C.c_int, _dp, _dp, _dp, _dp]
     L.smc_host_smooth.argtypes = [C.c_int, _dp, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp]
+    L.smc_smooth_pairs.argtypes = [h, _dp, _dp, _dp, _dp, _dp]
+    L.smc_host_smooth_pairs.argtypes = L.smc_host_smooth.argtypes + [_dp, _dp]
     L.smc_sample_paths.argtypes = [h, C.c_int64, C.c_uint64, _i32p, _i32p, _dp]
     L.smc_host_sample_paths.argtypes = [C.c_int, _dp, C.c_int64, C.c_int64, _dp, _dp, C.c_int64, C.c_uint64, C.c_uint32, _i32p, _dp]
     L.smc_rb_sample_paths.argtypes = [h, _dp, C.c_int64, C.c_int64, C.c_uint64, _i32p, _i32p, _dp, _dp, _dp, _dp, _dp]
@@ -992,15 +995,21 @@ class Handle:
     def history_end(self):
         check(lib().smc_history_end(self._h))
 
-    def smooth(self, weights=True, moments=True):
+    def smooth(self, weights=True, moments=True, pairs=False):
         """the FFBS backward pass over the recorded steps (smc_smooth): (ws [T][n_theta][n_x] or None, mean [T][d][n_theta] or
-        None, var or None)"""
+        None, var or None); pairs=True (smc_smooth_pairs): the lag-one pair moments follow, (..., cross [T-1][d][d][n_theta],
+        resid2 [T-1][d][n_theta])"""
         T = self.history_len()
         ws = np.zeros((T, self.n_theta, self.n_x)) if weights else None
         mean = np.zeros((T, self.d, self.n_theta)) if moments else None
         var = np.zeros((T, self.d, self.n_theta)) if moments else None
-        check(lib().smc_smooth(self._h, _d(ws), _d(mean), _d(var)))
-        return ws, mean, var
+        if not pairs:
+            check(lib().smc_smooth(self._h, _d(ws), _d(mean), _d(var)))
+            return ws, mean, var
+        cross = np.zeros((max(T - 1, 0), self.d, self.d, self.n_theta))
+        resid2 = np.zeros((max(T - 1, 0), self.d, self.n_theta))
+        check(lib().smc_smooth_pairs(self._h, _d(ws), _d(mean), _d(var), _d(cross), _d(resid2)))
+        return ws, mean, var, cross, resid2
 
     def sample_paths(self, M, seed, counts=None, want_x=True):
         """M backward-simulated paths per filter over the recorded steps (smc_sample_paths): (idx [T][n_theta][M] int32, xs
@@ -1126,6 +1135,20 @@ def host_smooth(model_id, raw, x, w, moments=True):
     mean, var = (np.zeros((T, d)), np.zeros((T, d))) if moments else (None, None)
     check(lib().smc_host_smooth(int(model_id), _d(raw), T, n, _d(x), _d(w), _d(ws), _d(mean), _d(var)))
     return ws, mean, var
+
+
+def host_smooth_pairs(model_id, raw, x, w):
+    """host_smooth with the lag-one pair moments of the same filter (smc_host_smooth_pairs; no GPU): (ws [T][n], mean [T][d],
+    var [T][d], cross [T-1][d][d], resid2 [T-1][d])"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    d = lib().smc_model_dim(int(model_id))
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    T, n = w.shape
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(T, d, n)
+    ws, mean, var = np.zeros((T, n)), np.zeros((T, d)), np.zeros((T, d))
+    cross, resid2 = np.zeros((max(T - 1, 0), d, d)), np.zeros((max(T - 1, 0), d))
+    check(lib().smc_host_smooth_pairs(int(model_id), _d(raw), T, n, _d(x), _d(w), _d(ws), _d(mean), _d(var), _d(cross), _d(resid2)))
+    return ws, mean, var, cross, resid2
 
 
 def host_ibis_summary(rows, x, S, logw, ahead=0):

@@ -24,6 +24,7 @@ void history_free(smc_filter_s* h) {
     (void)hipFree(h->hist.d_x);   // (d_w lives in the same allocation)
     (void)hipFree(h->hist.d_ws);
     (void)hipFree(h->hist.d_tmp);
+    (void)hipFree(h->hist.d_pair);
     (void)hipFree(h->hist.d_path);
     h->hist = {};
 }
@@ -148,9 +149,11 @@ hipError_t launch_pairs(const SmoothArgs& a, int threads, hipStream_t s) {
     hipLaunchKernelGGL((k_smooth_pairs<MODEL, PASS>), grid, dim3(threads), 0, s, a);
     return hipGetLastError();
 }
+// cross_t (smc_smooth_pairs): PASS 3 in PASS 2's place (a2.part is then its 1 + 2 d planes), plane 0 through k_smooth_finish as ever,
+// the others into cross_t, resid_t
 template <int MODEL>
 hipError_t backward_step(const SmoothArgs& a01, const SmoothArgs& a2, int threads, double* logD, double* rowmax, const double* w_t,
-                         const int* dead, double* ws_t, hipStream_t s) {
+                         const int* dead, double* ws_t, double* cross_t, double* resid_t, hipStream_t s) {
     hipError_t e;
     const dim3 g1((unsigned)((a01.n + 255) / 256), (unsigned)a01.ntheta);
     if ((e = launch_pairs<MODEL, 0>(a01, threads, s)) != hipSuccess) return e;
@@ -161,25 +164,32 @@ hipError_t backward_step(const SmoothArgs& a01, const SmoothArgs& a2, int thread
     if ((e = launch_pairs<MODEL, 1>(a01, threads, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_smooth_logd, g1, dim3(256), 0, s, a01.n, a01.ntheta, a01.nchunk, a01.rmax, a01.nmax, a01.part, logD);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = launch_pairs<MODEL, 2>(a2, threads, s)) != hipSuccess) return e;
+    if ((e = cross_t ? launch_pairs<MODEL, 3>(a2, threads, s) : launch_pairs<MODEL, 2>(a2, threads, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_smooth_finish, g1, dim3(256), 0, s, a2.n, a2.ntheta, a2.nchunk, a2.part, w_t, dead, ws_t);
+    if ((e = hipGetLastError()) != hipSuccess || !cross_t) return e;
+    hipLaunchKernelGGL((k_smooth_pair_moments<model_dim<MODEL>::value>), dim3((unsigned)a2.ntheta), dim3(PAIR_GROUP * SMOOTH_CH), 0, s, a2.n, a2.ntheta, a2.nchunk,
+                       (const double*)a2.part, a2.x_own, w_t, dead, cross_t, resid_t);
     return hipGetLastError();
 }
-}  // namespace
 
-extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
-    if (!h) return fail(SMC_EINVAL, "smc_smooth: NULL handle");
+// smc_smooth, and with cross or resid2 smc_smooth_pairs: the same refusals, plan and launches; the pair moments add a block of
+// their own (hist.d_pair: the chunk partials of PASS 3 and the results), so that a handle that never asks for them allocates and
+// launches what it always did
+int smooth_run(smc_handle h, const char* name, double* ws, double* mean, double* var, double* cross, double* resid2) {
+    const std::string who = std::string(name) + ": ";
+    if (!h) return fail(SMC_EINVAL, who + "NULL handle");
     if (!has_density(h->model))
-        return fail(SMC_EINVAL, "smc_smooth: SMC_MODEL_UCSV_RB has no transition density of its state rows (m and P are functions of the whole "
-                                "path); smooth a UCSV3D filter instead, or draw Rao-Blackwellised paths (smc_rb_sample_paths)");
-    if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, "smc_smooth: nothing is recorded (smc_history_begin, then smc_init / smc_step)");
+        return fail(SMC_EINVAL, who + "SMC_MODEL_UCSV_RB has no transition density of its state rows (m and P are functions of the whole "
+                                      "path); smooth a UCSV3D filter instead, or draw Rao-Blackwellised paths (smc_rb_sample_paths)");
+    if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, who + "nothing is recorded (smc_history_begin, then smc_init / smc_step)");
     const FilterView& v = h->v;
     const int64_t T = h->hist.len, n = v.n;
     const size_t nw = cloud_words(h), nt = (size_t)v.ntheta, d = (size_t)h->d;
-    if ((n + SMOOTH_CH - 1) / SMOOTH_CH > 65535) return fail(SMC_EINVAL, "smc_smooth: more than 65535 chunks of particles (the backward pass is quadratic in n_x)");
+    const bool pairs = cross || resid2;
+    if ((n + SMOOTH_CH - 1) / SMOOTH_CH > 65535) return fail(SMC_EINVAL, who + "more than 65535 chunks of particles (the backward pass is quadratic in n_x)");
     HIPCHK(hipSetDevice(h->device));
     std::vector<SmoothRow> rows;
-    int rc = fetch_rows(h, h->model, "smc_smooth", "the transition scale", rows);
+    int rc = fetch_rows(h, h->model, name, "the transition scale", rows);
     if (rc) return rc;
     const SmoothPlan p = plan_of(h, T);
     if (p.bytes > h->hist.tmp_bytes) {   // (the old block first, unlike the walk's: DESIGN.md "History on a handle")
@@ -187,7 +197,7 @@ extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
         h->hist.d_tmp = nullptr; h->hist.tmp_bytes = 0;
         if (hipMalloc((void**)&h->hist.d_tmp, p.bytes) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(SMC_ENOMEM, "smc_smooth: hipMalloc of the scratch of the backward pass");
+            return fail(SMC_ENOMEM, who + "hipMalloc of the scratch of the backward pass");
         }
         h->hist.tmp_bytes = p.bytes;
     }
@@ -197,9 +207,27 @@ extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
         h->hist.d_ws = nullptr; h->hist.ws_cap = 0;
         if (hipMalloc((void**)&h->hist.d_ws, (size_t)h->hist.cap * (nw + mom_words) * 8) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(SMC_ENOMEM, "smc_smooth: hipMalloc of the smoothed weights");
+            return fail(SMC_ENOMEM, who + "hipMalloc of the smoothed weights");
         }
         h->hist.ws_cap = h->hist.cap;
+    }
+    // the pair moments: partials [1 + 2 d][nchunk][ntheta][n] | cross [cap - 1][d][d][ntheta] | resid2 [cap - 1][d][ntheta]
+    const size_t cross_words = d * d * nt, resid_words = d * nt;
+    double *d_pair = nullptr, *d_cross = nullptr, *d_resid = nullptr;
+    if (pairs) {
+        OffsetPlan o;
+        const size_t steps = (size_t)h->hist.cap - 1;
+        const size_t o_part = o.take((1 + 2 * d) * (size_t)p.nchunk * nw * 8), o_cross = o.take(steps * cross_words * 8), o_resid = o.take(steps * resid_words * 8);
+        if (o.bytes > h->hist.pair_bytes) {
+            (void)hipFree(h->hist.d_pair);
+            h->hist.d_pair = nullptr; h->hist.pair_bytes = 0;
+            if (hipMalloc((void**)&h->hist.d_pair, o.bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(SMC_ENOMEM, who + "hipMalloc of the chunk partials of the pair moments");
+            }
+            h->hist.pair_bytes = o.bytes;
+        }
+        d_pair = (double*)(h->hist.d_pair + o_part); d_cross = (double*)(h->hist.d_pair + o_cross); d_resid = (double*)(h->hist.d_pair + o_resid);
     }
     char* tmp = (char*)h->hist.d_tmp;
     double *pmax = (double*)(tmp + p.o_pmax), *part = (double*)(tmp + p.o_part), *logD = (double*)(tmp + p.o_logD), *rowmax = (double*)(tmp + p.o_rmax), *momtmp = (double*)(tmp + p.o_mom);
@@ -224,8 +252,11 @@ extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
         double *ws_t = d_ws + (size_t)t * nw, *ws_n = ws_t + nw;
         const bool direct = p.nchunk <= SMOOTH_MAX_DIRECT;
         const SmoothArgs a01{n, (int)nt, p.nchunk, x_n, x_t, w_t, nullptr, pmax, direct ? pmax : rowmax, direct ? p.nchunk : 1, part, d_rows};
-        const SmoothArgs a2{n, (int)nt, p.nchunk, x_t, x_n, ws_n, logD, pmax, nullptr, 0, part, d_rows};
-        HIPCHK(by_density_model(h->model, [&](auto Mt) { return backward_step<decltype(Mt)::value>(a01, a2, threads, logD, rowmax, w_t, dead, ws_t, s); }));
+        const SmoothArgs a2{n, (int)nt, p.nchunk, x_t, x_n, ws_n, logD, pmax, nullptr, 0, pairs ? d_pair : part, d_rows};
+        double *cross_t = pairs ? d_cross + (size_t)t * cross_words : nullptr, *resid_t = pairs ? d_resid + (size_t)t * resid_words : nullptr;
+        HIPCHK(by_density_model(h->model, [&](auto Mt) {
+            return backward_step<decltype(Mt)::value>(a01, a2, threads, logD, rowmax, w_t, dead, ws_t, cross_t, resid_t, s);
+        }));
     }
     if (mean || var) {
         hipLaunchKernelGGL(k_smooth_moments, dim3((unsigned)T, (unsigned)nt), dim3(256), 0, s, n, (int)nt, p.nchunk, (int)d, h->hist.d_x, d_ws, dead,
@@ -242,7 +273,16 @@ extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
             if (var) memcpy(var + (size_t)t * d * nt, mv.data() + (size_t)t * mom_words + d * nt, d * nt * 8);
         }
     }
+    if (cross && T > 1) HIPCHK(hipMemcpy(cross, d_cross, (size_t)(T - 1) * cross_words * 8, hipMemcpyDeviceToHost));
+    if (resid2 && T > 1) HIPCHK(hipMemcpy(resid2, d_resid, (size_t)(T - 1) * resid_words * 8, hipMemcpyDeviceToHost));
     return SMC_OK;
+}
+}  // namespace
+
+extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) { return smooth_run(h, "smc_smooth", ws, mean, var, nullptr, nullptr); }
+
+extern "C" int smc_smooth_pairs(smc_handle h, double* ws, double* mean, double* var, double* cross, double* resid2) {
+    return smooth_run(h, "smc_smooth_pairs", ws, mean, var, cross, resid2);
 }
 
 // ---- backward simulation ---------------------------------------------------------------------------------------------------

@@ -126,7 +126,9 @@ struct smc_filter_s {
         double* d_tmp = nullptr;               // its scratch: chunk maxima and chunk partials [2][nchunk][ntheta][n] | logD [ntheta][n] |
         int64_t ws_cap = 0;                    //   partials of the moments [len][ntheta][nchunk] | rows [ntheta] | dead [ntheta]
         size_t tmp_bytes = 0;
-        char* d_path = nullptr;                // the backward walk (smc_sample_paths, or smc_rb_sample_paths on a MODEL_UCSV_RB handle), its own
+        char* d_pair = nullptr;                // the pair moments (smc_smooth_pairs), a block of their own: chunk partials [1 + 2 d][nchunk][ntheta][n] |
+        size_t pair_bytes = 0;                 //   cross [cap - 1][d][d][ntheta] | resid2 [cap - 1][d][ntheta]; nullptr until the first such call
+        char* d_path = nullptr;               // the backward walk (smc_sample_paths, or smc_rb_sample_paths on a MODEL_UCSV_RB handle), its own
         size_t path_bytes = 0;                 //   block: cur | pmax | psum | rmax | rows | dead | counts | idx [T][ntheta][M] | the caller's tail
         int64_t walk_M = 0, walk_T = 0;        // the last smc_sample_paths walk over this record (0: none): paths per filter, steps, and where
         size_t walk_idx = 0;                   //   its index block starts in d_path (smc_reference_from_paths gathers through it)

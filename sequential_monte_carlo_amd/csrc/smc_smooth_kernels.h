@@ -12,6 +12,9 @@
 //   k_smooth_logd: logD_j = M_j + sp_log(sum of the partials in ascending order)
 //   PASS 2  owners = sources i (step t), staged = targets j (step t+1): chunk partial of sum_j ws_j sp_exp(logf_ij - logD_j)
 //   k_smooth_finish: ws_t^i = w_t^i > 0 ? w_t^i * (sum of the partials in ascending order) : 0;  NaN for a collapsed filter
+//   PASS 3  (smc_smooth_pairs only, in PASS 2's place) PASS 2 with 2 d accumulators more: the chunk partials of
+//           p_ij, p_ij x_j^c and p_ij d_c^2                                                        -> part [1 + 2 d][chunk][th][i]
+//   k_smooth_pair_moments: cross[t], resid2[t] from those partials, one workgroup per filter (plane 0 goes through k_smooth_finish)
 // No floating-point atomics, no spinning: the partials go through scratch owned by the handle, the kernels follow each other on
 // the handle's stream.
 #pragma once
@@ -24,20 +27,20 @@ struct SmoothArgs {
     int ntheta, nchunk;    // filters, chunks of SMOOTH_CH particles
     const double* x_own;   // [d][ntheta][n] states of the owner side
     const double* x_st;    // [d][ntheta][n] states of the staged side
-    const double* w_st;    // [ntheta][n] PASS 0, 1: filter weights of the sources; PASS 2: smoothed weights of the targets
-    const double* logD;    // [ntheta][n] PASS 2
+    const double* w_st;    // [ntheta][n] PASS 0, 1: filter weights of the sources; PASS 2, 3: smoothed weights of the targets
+    const double* logD;    // [ntheta][n] PASS 2, 3
     double* pmax;          // [nchunk][ntheta][n] chunk maxima (PASS 0 writes them)
     const double* rmax;    // [nmax][ntheta][n] what PASS 1 takes M_j from: pmax with nmax = nchunk, or the row maxima with nmax = 1
     int nmax;
-    double* part;          // [nchunk][ntheta][n]
-    const SmoothRow* rows; // [ntheta]
+    double* part;          // [nchunk][ntheta][n];  PASS 3: [1 + 2 d][nchunk][ntheta][n], plane 0 what PASS 2 writes, then the chunk
+    const SmoothRow* rows; // [ntheta]                                                     partials of X^c and of R^c
 };
 
 template <int MODEL, int PASS>
 __global__ void k_smooth_pairs(SmoothArgs a) {
     constexpr int D = model_dim<MODEL>::value;
     constexpr int NV = D + 2;
-    __shared__ double sm[SMOOTH_CH][NV];   // PASS 0, 1: (m[D], s, g);  PASS 2: (x[D], ws, logD)
+    __shared__ double sm[SMOOTH_CH][NV];   // PASS 0, 1: (m[D], s, g);  PASS 2, 3: (x[D], ws, logD)
     const int th = blockIdx.y, ch = blockIdx.z;
     const int64_t n = a.n;
     const size_t row = (size_t)th * n, plane = (size_t)a.ntheta * n;
@@ -91,7 +94,7 @@ __global__ void k_smooth_pairs(SmoothArgs a) {
             S += sp_exp(al - M);
         }
         a.part[o] = S;
-    } else {
+    } else if constexpr (PASS == 2) {
         double m[D], s, c;
         logf_source<MODEL>(k, xo, m, s, c);
         double S = 0.0;
@@ -101,6 +104,22 @@ __global__ void k_smooth_pairs(SmoothArgs a) {
             S += sm[q][D] * sp_exp(lf - sm[q][D + 1]);
         }
         a.part[o] = S;
+    } else {   // PASS 3: PASS 2 with the pair moments (smc_spec.h "lag-one pair moments"); acc[0] is PASS 2's S, bit for bit
+        double m[D], s, c;
+        logf_source<MODEL>(k, xo, m, s, c);
+        double acc[1 + 2 * D];
+        for (int v = 0; v < 1 + 2 * D; ++v) acc[v] = 0.0;
+#pragma unroll 4
+        for (int q = 0; q < SMOOTH_CH; ++q) {
+            const double p = pair_prob<MODEL>(k, m, s, c, sm[q], sm[q][D], sm[q][D + 1]);
+            acc[0] += p;
+            for (int r = 0; r < D; ++r) {
+                acc[1 + r] += pair_x_term(p, sm[q][r]);
+                acc[1 + D + r] += pair_r_term(p, sm[q][r], m[r]);
+            }
+        }
+        const size_t vplane = (size_t)a.nchunk * plane;
+        for (int v = 0; v < 1 + 2 * D; ++v) a.part[(size_t)v * vplane + o] = acc[v];
     }
 }
 
@@ -204,6 +223,63 @@ __global__ void k_smooth_moments(int64_t n, int ntheta, int nchunk, int d, const
             }
             __syncthreads();
         }
+    }
+}
+
+// cross[a][c] and resid2[c] of one backward step from the chunk partials PASS 3 left (planes 1 .. 2 D of pair): X_i^c and R_i^c
+// are the partials of source i in ascending chunk order, the sums over i run in smooth_sum's order.  One workgroup per filter,
+// PAIR_GROUP chunks of sources at a time: every thread forms the D D + D terms of its source (the loads of its partials are
+// independent: unrolled, many in flight), thread (g, k) sums term k of chunk g in ascending order, and thread k adds the chunk
+// sums, in ascending order again, to the total it keeps.  dead[th] != 0: NaN.  cross [D][D][ntheta], resid2 [D][ntheta]
+constexpr int PAIR_GROUP = 512 / SMOOTH_CH;   // a workgroup of 512 threads whatever the chunk length (48 KB of LDS for three rows)
+template <int D>
+__global__ void __launch_bounds__(PAIR_GROUP * SMOOTH_CH)
+k_smooth_pair_moments(int64_t n, int ntheta, int nchunk, const double* pair, const double* x /*[D][ntheta][n]*/,
+                      const double* w /*[ntheta][n]*/, const int* dead, double* cross, double* resid2) {
+    constexpr int NT = D * D + D;
+    __shared__ double sm[PAIR_GROUP * SMOOTH_CH][NT];
+    __shared__ double cs[PAIR_GROUP][NT];
+    const int th = blockIdx.x, tid = threadIdx.x;
+    const size_t row = (size_t)th * n, plane = (size_t)ntheta * n, vplane = (size_t)nchunk * plane;
+    double tot = 0.0;
+    for (int c0 = 0; c0 < nchunk; c0 += PAIR_GROUP) {
+        const int64_t i = (int64_t)c0 * SMOOTH_CH + tid;
+        double term[NT];
+        for (int q = 0; q < NT; ++q) term[q] = 0.0;
+        const double wi = i < n ? w[row + i] : 0.0;
+        if (wi > 0.0) {   // (a source that is left out, or past the end: +0.0 whatever its partials hold)
+            double X[D], R[D];
+            for (int c = 0; c < D; ++c) X[c] = R[c] = 0.0;
+            const double* pi = pair + vplane + row + i;
+#pragma unroll 4
+            for (int cc = 0; cc < nchunk; ++cc)
+                for (int c = 0; c < D; ++c) {
+                    X[c] += pi[(size_t)c * vplane + (size_t)cc * plane];
+                    R[c] += pi[(size_t)(D + c) * vplane + (size_t)cc * plane];
+                }
+            for (int r = 0; r < D; ++r) {
+                const double xr = x[(size_t)r * plane + row + i];
+                for (int c = 0; c < D; ++c) term[r * D + c] = pair_cross_term(wi, xr, X[c]);
+            }
+            for (int c = 0; c < D; ++c) term[D * D + c] = pair_resid_term(wi, R[c]);
+        }
+        for (int q = 0; q < NT; ++q) sm[tid][q] = term[q];
+        __syncthreads();
+        if (tid < PAIR_GROUP * NT) {
+            const int g = tid / NT, q = tid % NT;
+            double s = 0.0;
+#pragma unroll 8
+            for (int p = 0; p < SMOOTH_CH; ++p) s += sm[g * SMOOTH_CH + p][q];
+            cs[g][q] = s;
+        }
+        __syncthreads();   // (cs is written again only behind the next iteration's first barrier, which its readers below have passed)
+        if (tid < NT)
+            for (int g = 0; g < PAIR_GROUP && c0 + g < nchunk; ++g) tot += cs[g][tid];
+    }
+    if (tid < NT) {
+        const double r = dead[th] ? bits2d(0x7ff8000000000000ULL) : tot;
+        if (tid < D * D) cross[(size_t)tid * ntheta + th] = r;
+        else resid2[(size_t)(tid - D * D) * ntheta + th] = r;
     }
 }
 

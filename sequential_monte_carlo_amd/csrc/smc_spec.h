@@ -1148,6 +1148,32 @@ inline double smooth_sum(int64_t n, F term) {
     return tot;
 }
 
+// ---- the smoother: lag-one pair moments ----------------------------------------------------------------------------
+// The quantities of the smoother above: source i at step t, target j at step t+1, d state rows, and the centres m_c(x_t^i) of
+// logf_source (LG1D: A x;  SV1D: fma(rho, x - mu, mu);  UCSV3D: x in all three rows).  For t = 0 .. T-2:
+//     p_ij  = ws_{t+1}^j * sp_exp(logf(x_{t+1}^j | x_t^i) - logD_j)                  (pair_prob: bit for bit the term ws_t^i sums)
+//     X_i^c = sum_j p_ij * x_{t+1}^{j,c}                                              (pair_x_term)
+//     R_i^c = sum_j p_ij * (d_c * d_c),   d_c = x_{t+1}^{j,c} - m_c(x_t^i)           (pair_r_term: the d_r of logf_pair, same bits)
+//     cross[t][a][c] = sum_i (w_t^i * x_t^{i,a}) * X_i^c      -> E[x_t^a x_{t+1}^c | y_1:T]                     (pair_cross_term)
+//     resid2[t][c]   = sum_i  w_t^i * R_i^c                   -> E[(x_{t+1}^c - m_c(x_t))^2 | y_1:T]            (pair_resid_term)
+// The sums over j run in the smoother's order (chunks of SMOOTH_CH, plain adds from +0.0, partials in ascending order), the sums
+// over i in smooth_sum's.  A target with ws = 0 and a source with w = 0 (NaN compares false) contribute exactly +0.0 whatever
+// their states: by a select, not by a product with zero, on the owner side as well.  (The kernels stage a left-out target as the
+// smoother does - weight 0, logD = +inf, a zero state - so that its three terms are exactly +0.0, and select on w in the kernel
+// that finishes a step.)  There is no renormalisation; a filter that collapsed at any recorded step reads NaN everywhere; T = 1
+// has no pair.  MODEL_UCSV_RB has no pair moments, as it has no smoother of this kind.
+template <int MODEL>
+SMC_HD double pair_prob(const SmoothRow& k, const double* m, double s, double c, const double* xj, double wsj, double logDj) {
+    return wsj * sp_exp(logf_pair<MODEL>(k, m, s, c, xj) - logDj);
+}
+SMC_HD double pair_x_term(double p, double xjc) { return p * xjc; }
+SMC_HD double pair_r_term(double p, double xjc, double mc) {
+    const double dc = xjc - mc;
+    return p * (dc * dc);
+}
+SMC_HD double pair_cross_term(double wi, double xia, double Xc) { return wi > 0.0 ? (wi * xia) * Xc : 0.0; }
+SMC_HD double pair_resid_term(double wi, double Rc) { return wi > 0.0 ? wi * Rc : 0.0; }
+
 // ---- backward simulation: joint smoothing paths (FFBSi; Godsill, Doucet and West 2004) --------------------------
 // Inputs: the recorded clouds (x_t, w_t), t = 0..T-1, of one filter (w the dense weights), its SmoothRow, a path seed and the
 // filter's Philox stream id.  Path p (0-based) is a function of these alone: not of the number of paths, of the other paths,

@@ -671,10 +671,13 @@ static void host_smooth_moments(int d, int64_t n, const double* x /*[d][n]*/, co
     }
 }
 
+// cross [T-1][D][D] and resid2 [T-1][D] (both or neither): the lag-one pair moments (smc_spec.h "lag-one pair moments")
 template <int MODEL>
-static void host_smooth_t(const SmoothRow& k, int64_t T, int64_t n, const double* x, const double* w, double* ws) {
+static void host_smooth_t(const SmoothRow& k, int64_t T, int64_t n, const double* x, const double* w, double* ws, double* cross = nullptr,
+                          double* resid2 = nullptr) {
     constexpr int D = model_dim<MODEL>::value;
     const size_t sx = (size_t)D * n;
+    std::vector<double> X(cross ? (size_t)D * n : 0), Rs(cross ? (size_t)D * n : 0), pj(cross ? (size_t)n : 0);
     for (int64_t i = 0; i < n; ++i) ws[(size_t)(T - 1) * n + i] = w[(size_t)(T - 1) * n + i];
     std::vector<double> m((size_t)D * n), s((size_t)n), c((size_t)n), g((size_t)n), logD((size_t)n);
     for (int64_t t = T - 2; t >= 0; --t) {
@@ -710,6 +713,29 @@ static void host_smooth_t(const SmoothRow& k, int64_t T, int64_t n, const double
             const double S = smooth_sum(n, [&](int64_t j) { return wn[j] > 0.0 ? wn[j] * sp_exp(pair(i, j, c[i]) - logD[j]) : 0.0; });
             out[i] = wt[i] * S;
         }
+        if (!cross) continue;
+        for (int64_t i = 0; i < n; ++i) {
+            if (!(wt[i] > 0.0)) continue;   // (left out below by the select on w)
+            double mi[D];
+            for (int r = 0; r < D; ++r) mi[r] = m[(size_t)r * n + i];
+            for (int64_t j = 0; j < n; ++j) {   // p_ij, once per pair
+                if (!(wn[j] > 0.0)) continue;
+                double xj[D];
+                for (int r = 0; r < D; ++r) xj[r] = xt[(size_t)r * n + j];
+                pj[j] = pair_prob<MODEL>(k, mi, s[i], c[i], xj, wn[j], logD[j]);
+            }
+            for (int r = 0; r < D; ++r) {
+                const double* xr = xt + (size_t)r * n;
+                X[(size_t)r * n + i] = smooth_sum(n, [&](int64_t j) { return wn[j] > 0.0 ? pair_x_term(pj[j], xr[j]) : 0.0; });
+                Rs[(size_t)r * n + i] = smooth_sum(n, [&](int64_t j) { return wn[j] > 0.0 ? pair_r_term(pj[j], xr[j], mi[r]) : 0.0; });
+            }
+        }
+        for (int a = 0; a < D; ++a)
+            for (int r = 0; r < D; ++r)
+                cross[((size_t)t * D + a) * D + r] =
+                    smooth_sum(n, [&](int64_t i) { return wt[i] > 0.0 ? pair_cross_term(wt[i], xs[(size_t)a * n + i], X[(size_t)r * n + i]) : 0.0; });
+        for (int r = 0; r < D; ++r)
+            resid2[(size_t)t * D + r] = smooth_sum(n, [&](int64_t i) { return wt[i] > 0.0 ? pair_resid_term(wt[i], Rs[(size_t)r * n + i]) : 0.0; });
     }
 }
 
@@ -725,6 +751,29 @@ extern "C" int smc_host_smooth(int model_id, const double* raw, int64_t T, int64
     const bool dead = host_dead(T, n, w);   // NaN everywhere
     if (dead)
         for (size_t q = 0; q < (size_t)T * n; ++q) ws[q] = bits2d(0x7ff8000000000000ULL);
+    if (mean && var)
+        for (int64_t t = 0; t < T; ++t)
+            host_smooth_moments(d, n, x + (size_t)t * d * n, ws + (size_t)t * n, dead, mean + (size_t)t * d, var + (size_t)t * d);
+    return SMC_OK;
+}
+
+extern "C" int smc_host_smooth_pairs(int model_id, const double* raw, int64_t T, int64_t n, const double* x, const double* w, double* ws,
+                                     double* mean, double* var, double* cross, double* resid2) {
+    if (!raw || !x || !w || !ws || (T > 1 && (!cross || !resid2))) return fail(SMC_EINVAL, "smc_host_smooth_pairs: NULL argument");
+    if (T < 1 || n < 1) return fail(SMC_EINVAL, "smc_host_smooth_pairs: T and n must be positive");
+    if (T == 1) return smc_host_smooth(model_id, raw, T, n, x, w, ws, mean, var);   // no pair: cross and resid2 are empty
+    SmoothRow k;
+    if (!smooth_row(model_id, raw, k))
+        return fail(SMC_EINVAL, "smc_host_smooth_pairs: no transition density for this family, or a transition scale that is not positive and finite");
+    const int d = model_dim_rt(model_id);
+    (void)by_density_model(model_id, [&](auto Mt) { host_smooth_t<decltype(Mt)::value>(k, T, n, x, w, ws, cross, resid2); return hipSuccess; });
+    const bool dead = host_dead(T, n, w);   // NaN everywhere
+    if (dead) {
+        const double nan = bits2d(0x7ff8000000000000ULL);
+        for (size_t q = 0; q < (size_t)T * n; ++q) ws[q] = nan;
+        for (size_t q = 0; q < (size_t)(T - 1) * d * d; ++q) cross[q] = nan;
+        for (size_t q = 0; q < (size_t)(T - 1) * d; ++q) resid2[q] = nan;
+    }
     if (mean && var)
         for (int64_t t = 0; t < T; ++t)
             host_smooth_moments(d, n, x + (size_t)t * d * n, ws + (size_t)t * n, dead, mean + (size_t)t * d, var + (size_t)t * d);

@@ -7,6 +7,8 @@
     log_likelihood(N, y, model)          -> (x, w, logZ)        particles.jl:132-147
     smoother(N, y, model)                -> (x, w, logZ, s)     (no counterpart: the FFBS particle smoother)
     ParticleGibbs(N, y, model)           -> sampler             (no counterpart: the conditional particle filter)
+    particle_em(N, y, model, iters)      -> dict                (no counterpart: maximum likelihood by particle EM on the smoother's
+    em_mstep(model, y, s)                -> model                lag-one pair moments)
     forecast(x, w, H)                    -> dict                (no counterpart: the cloud propagated H steps ahead)
     particle_filter(N, y1, model, proposal)       -> (x, w, logmu)     particles.jl:28-52
     particle_filter_(x, w, y, model, proposal)    -> (logmu, w, ess)   particles.jl:54-84    ("particle_filter!")
@@ -420,7 +422,7 @@ def _reference_out(xref, single):
 
 
 def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="multinomial", proposal=None, weights=False, rows=None,
-             paths=0, path_seed=None, path_counts=None, smooth=True, missing=False, reference=None):
+             paths=0, path_seed=None, path_counts=None, smooth=True, missing=False, reference=None, pairs=False):
     """x, w, logZ, s = smoother(N, y, model): the particle filter of log_likelihood run step by step with its clouds recorded on
     the device, then the FFBS backward pass over them (forward filtering, backward smoothing).  x, w, logZ are the
     filter's, as log_likelihood returns them; s describes p(x_t | y_1:T):
@@ -436,6 +438,11 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
                                     derived from the filter seed); path_counts [n_theta]: draw only that many paths of each filter
                                     (the other slots read -1 / NaN); smooth=False skips the backward pass of the marginals (no
                                     s["mean"], s["var"]).  A batch holds T n_theta M entries: keep M small there.
+        s["cross"], s["resid2"], s["lag1_cov"]  (pairs=True) the lag-one pair moments of the backward pass itself, no
+                                    paths and none of their noise: cross[t] = E[x_t x_{t+1} | y_1:T], [T-1] or [T-1][d][d] (row:
+                                    the coordinate of x_t); resid2[t] = E[(x_{t+1} - m(x_t))^2 | y_1:T] with m the transition's
+                                    centre, [T-1] or [T-1][d]; lag1_cov[t] = cross[t] - mean[t] (x) mean[t+1].  The batch axis
+                                    follows T, as in s["mean"].  They are the E-step of em_mstep / particle_em.
     The backward pass costs 2 N^2 (T - 1) transition densities per filter.  Any proposal, either resampler; MarginalUCSV has no
     smoother of this kind (its state rows have no transition density): rb_smoother is its smoother.
     rows=(model id, parameter rows [n_theta][n_raw]) with model=None: a batch given as rows (what the samplers hold).
@@ -444,6 +451,8 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
     reference=[T] or [T][d] (a batch axis after T, as in s["paths"]): the run is the CONDITIONAL particle filter - one
     slot of every step is pinned to that trajectory; everything returned is shaped as ever, but logZ is not a likelihood estimate.
     One path of it (paths=1) is one sweep of particle Gibbs: ParticleGibbs keeps the handle between sweeps."""
+    if pairs and not smooth:
+        raise ValueError("pairs=True needs the backward pass of the marginals (smooth=True): the pair moments are formed inside it")
     if seed is None:
         seed = next(_seed_counter)
     f = _Filters(int(N), model, seed, seg, device, streams, False, resampler, proposal, rows=rows, missing=missing,
@@ -459,11 +468,20 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
         lm, es, logZ = _run_recorded(h, y)
         s = {}
         if smooth or weights:
-            ws, mean, var = h.smooth(weights=weights, moments=True)
+            ws, mean, var, *pm = h.smooth(weights=weights, moments=True, pairs=pairs)
             mean, var = np.moveaxis(mean, 1, -1), np.moveaxis(var, 1, -1)      # [T][n_theta][d]
             if mean.shape[-1] == 1:
                 mean, var = mean[..., 0], var[..., 0]
             s["mean"], s["var"] = (mean[:, 0], var[:, 0]) if f.single else (mean, var)
+            if pairs:
+                cross, resid2 = np.moveaxis(pm[0], 3, 1), np.moveaxis(pm[1], 1, -1)   # [T-1][n_theta][d][d], [T-1][n_theta][d]
+                if h.d == 1:
+                    cross, resid2 = cross[..., 0, 0], resid2[..., 0]
+                    outer = mean[:-1] * mean[1:]
+                else:
+                    outer = mean[:-1][..., :, None] * mean[1:][..., None, :]
+                lag = cross - outer
+                s["cross"], s["resid2"], s["lag1_cov"] = (cross[:, 0], resid2[:, 0], lag[:, 0]) if f.single else (cross, resid2, lag)
         if paths:
             idx, xp = h.sample_paths(int(paths), _path_seed(seed) if path_seed is None else int(path_seed), counts=path_counts)
             s["path_index"], s["paths"] = _paths_out(idx, xp, f.single)
@@ -543,6 +561,133 @@ class ParticleGibbs:
 
     def close(self):
         self._f.h.close()
+
+
+EM_FREE = {_lib.MODEL_LG1D: ("A", "Q", "R"), _lib.MODEL_SV1D: ("mu", "rho", "sigma"), _lib.MODEL_UCSV3D: ("gamma_eps", "gamma_eta")}
+
+
+def _em_free(model, free):
+    """the names em_mstep updates, in the order of EM_FREE (the order of the columns of particle_em's theta)"""
+    from .models import MarginalUCSV
+    if isinstance(model, MarginalUCSV) or getattr(model, "model_id", None) not in EM_FREE:
+        raise TypeError("em_mstep: UnivariateLinearGaussian, StochasticVolatility and UCSV have a closed-form M-step on the pair moments; "
+                        "MarginalUCSV has no pair moments (its state rows have no transition density)")
+    names = EM_FREE[model.model_id]
+    if free is None:
+        return names
+    free = (free,) if isinstance(free, str) else tuple(free)
+    bad = [p for p in free if p not in names]
+    if bad:
+        raise ValueError("em_mstep: %r is not among the parameters of this family that the M-step updates, %r" % (bad, names))
+    return tuple(p for p in names if p in free)
+
+
+def _em_theta(model, names):
+    get = {"A": lambda m: m.A, "Q": lambda m: m.Q, "R": lambda m: m.R, "mu": lambda m: m.mu, "rho": lambda m: m.rho,
+           "sigma": lambda m: m.sigma, "gamma_eps": lambda m: m.gamma[0], "gamma_eta": lambda m: m.gamma[1]}
+    return np.array([get[p](model) for p in names])
+
+
+def em_mstep(model, y, s, free=None, missing=False):
+    """The M-step of particle EM as a pure function (no GPU): the model whose parameters `free` maximise the expected complete-data
+    log-likelihood under the smoothed law that s describes - s of smoother(N, y, model, pairs=True) for ONE model: s["mean"],
+    s["var"], s["cross"], s["resid2"] (or the exact moments of a Kalman / RTS pass in the same shapes).  free: the names to update,
+    default all of the family's; every other parameter stays.  With E x_t^2 = var_t + mean_t^2,
+    S00 = sum_{t<T-1} E x_t^2, S11 = sum_{t>=1} E x_t^2, S10 = sum_t cross[t], m0 = sum_{t<T-1} mean_t, m1 = sum_{t>=1} mean_t:
+        UnivariateLinearGaussian {A, Q, R}:  A = S10 / S00;  Q = (S11 - 2 A S10 + A^2 S00) / (T - 1) with the A in force;  R = the
+            mean over the observed periods of (y_t - B mean_t)^2 + B^2 var_t (missing=True: a NaN in y is a period without one)
+        StochasticVolatility {mu, rho, sigma}:  least squares of x_{t+1} on (1, x_t): rho = ((T-1) S10 - m0 m1) / ((T-1) S00 - m0^2),
+            alpha = (m1 - rho m0) / (T - 1), mu = alpha / (1 - rho) (with one of the two held, the other one's conditional
+            minimiser), sigma^2 = the mean residual square with the (mu, rho) in force.  The single term of the stationary initial
+            law, log N(x_1; mu, sigma^2 / (1 - rho^2)), is LEFT OUT of the M-step: with it the maximiser has no closed form, and
+            its weight is 1 / T of the whole.
+        UCSV {gamma_eps, gamma_eta}:  gamma_c^2 = (var_0^c + (mean_0^c - l0_c)^2 + sum_t resid2[t][c]) / T for c = lse, lsn (the
+            centre of a log-volatility is the previous one whatever the parameters, so resid2 is the whole statistic): exact.
+    MarginalUCSV: TypeError.  B, x0, sigma0 and the initial laws are not estimated."""
+    from .models import UCSV, LinearModel, StochasticVolatility
+    names = _em_free(model, free)
+    y = np.asarray(y, dtype=np.float64).ravel()
+    T = y.size
+    mean, var = np.asarray(s["mean"], dtype=np.float64), np.asarray(s["var"], dtype=np.float64)
+    cross, resid2 = np.asarray(s["cross"], dtype=np.float64), np.asarray(s["resid2"], dtype=np.float64)
+    d = model.dim
+    want = {"mean": (T,) + (() if d == 1 else (d,)), "cross": (T - 1,) + (() if d == 1 else (d, d)), "resid2": (T - 1,) + (() if d == 1 else (d,))}
+    for key, a in (("mean", mean), ("var", var), ("cross", cross), ("resid2", resid2)):
+        if a.shape != want["mean" if key == "var" else key]:
+            raise ValueError("em_mstep: s[%r] has the shape %r, not %r (the moments of ONE model over y)" % (key, a.shape, want["mean" if key == "var" else key]))
+    seen = np.isfinite(y)
+    if not missing and not seen.all():
+        raise ValueError("em_mstep: y holds a value that is not finite (missing=True reads a NaN as a period without an observation)")
+    if model.model_id == _lib.MODEL_UCSV3D:
+        g = list(model.gamma)
+        for k, (name, c) in enumerate((("gamma_eps", 1), ("gamma_eta", 2))):
+            if name in names:
+                g[k] = float(np.sqrt((var[0, c] + (mean[0, c] - model.log_sigma0[k]) ** 2 + resid2[:, c].sum()) / T))
+        return UCSV(tuple(g), model.x0, model.log_sigma0)
+    if T < 2:
+        raise ValueError("em_mstep: the transition parameters need at least two periods")
+    n = T - 1
+    ex2 = var + mean * mean
+    S00, S11, S10, m0, m1 = ex2[:-1].sum(), ex2[1:].sum(), cross.sum(), mean[:-1].sum(), mean[1:].sum()
+    if model.model_id == _lib.MODEL_LG1D:
+        A, Q, R = model.A, model.Q, model.R
+        if "A" in names:
+            A = S10 / S00
+        if "Q" in names:
+            Q = (S11 - 2.0 * A * S10 + A * A * S00) / n
+        if "R" in names:
+            if not seen.any():
+                raise ValueError("em_mstep: no observed period to estimate R from")
+            B = model.B
+            R = float(np.mean((y[seen] - B * mean[seen]) ** 2 + B * B * var[seen]))
+        return LinearModel(float(A), model.B, float(Q), float(R), model.x0, model.sigma0)
+    mu, rho, sigma = model.mu, model.rho, model.sigma
+    if "mu" in names and "rho" in names:
+        rho = (n * S10 - m0 * m1) / (n * S00 - m0 * m0)
+        mu = (m1 - rho * m0) / n / (1.0 - rho)
+    elif "rho" in names:
+        rho = (S10 - mu * (m0 + m1) + n * mu * mu) / (S00 - 2.0 * mu * m0 + n * mu * mu)
+    elif "mu" in names:
+        mu = (m1 - rho * m0) / n / (1.0 - rho)
+    if "sigma" in names:
+        al = mu * (1.0 - rho)
+        sigma = np.sqrt((S11 - 2.0 * al * m1 - 2.0 * rho * S10 + n * al * al + 2.0 * al * rho * m0 + rho * rho * S00) / n)
+    return StochasticVolatility(float(mu), float(rho), float(sigma))
+
+
+def particle_em(N, y, model, iters, seed=None, free=None, missing=False, **filter_kw):
+    """r = particle_em(N, y, model, iters): maximum likelihood by particle EM for one model, or a list of models with
+    one EM chain each (one batch on the device).  Iteration k = 0 .. iters-1 runs smoother(N, y, model_k, pairs=True, seed=seed_k,
+    missing=missing, **filter_kw) - the E-step: the smoothed marginals and the lag-one pair moments of the FFBS backward pass - and
+    then em_mstep(model_k, y, s, free, missing) per chain.  seed_k = seed + k * 0x9E3779B97F4A7C15 mod 2^64, as
+    ParticleGibbs.sweep_seed derives its own: every iteration draws from fresh Philox counters, and iteration 0 is smoother(...,
+    seed=seed) itself.
+        r["models"]  [iters + 1]: the starting model and the one after every iteration (lists of chains, given a list)
+        r["theta"]   [iters + 1][n_free]: their free parameters in the family's order ([iters + 1][n_chains][n_free], given a list)
+        r["logZ"]    [iters]: the filter's log-likelihood estimate at model_k, the model each E-step ran under ([iters][n_chains])
+    The estimate carries the Monte-Carlo noise of N particles per iteration: it settles around the MLE, it does not converge to it;
+    average the last iterations, or raise N.  filter_kw: smoother's filter keywords (seg, device, streams, resampler, proposal)."""
+    single = not isinstance(model, (list, tuple))
+    chain = [model] if single else list(model)
+    names = _em_free(chain[0], free)
+    for m in chain:
+        _em_free(m, free)
+    seed = next(_seed_counter) if seed is None else int(seed)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    models, theta, logZ = [chain], [np.array([_em_theta(m, names) for m in chain])], []
+    for k in range(int(iters)):
+        sd = (seed + k * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        _, _, lz, s = smoother(N, y, chain, seed=sd, pairs=True, missing=missing, **filter_kw)
+        chain = [em_mstep(m, y, {key: s[key][:, c] for key in ("mean", "var", "cross", "resid2")}, names, missing)
+                 for c, m in enumerate(chain)]
+        models.append(chain)
+        theta.append(np.array([_em_theta(m, names) for m in chain]))
+        logZ.append(np.asarray(lz, dtype=np.float64))
+    theta = np.array(theta)
+    logZ = np.array(logZ).reshape(int(iters), len(chain))
+    if single:
+        return {"models": [c[0] for c in models], "theta": theta[:, 0], "logZ": logZ[:, 0]}
+    return {"models": models, "theta": theta, "logZ": logZ}
 
 
 def rb_smoother(N, y, model, paths=256, seed=None, path_seed=None, draws=False, per_path=False, path_counts=None, seg=0, device=0,
