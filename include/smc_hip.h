@@ -195,6 +195,10 @@ int smc_host_filter_steps(int model_id, const double* raw, int kind, const doubl
 /* the same on the device in one launch (parity tests; the twin of smc_device_guided_step) */
 int smc_device_filter_steps(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z,
                             double y, int first, int nan_missing, int64_t n, double* x, double* logw, int device);
+/* Device and pinned host bytes that the handles, communicators and bundles of this process hold right now (allocated and not yet
+ * freed; process-wide, every device; the cache of destroyed handles' bundles included, the per-thread scratch of the calls
+ * without a handle not).  A probe for tests: a leak shows as a difference that grows.  Either pointer may be NULL. */
+int smc_live_bytes(int64_t* device_bytes, int64_t* pinned_bytes);
 
 /* ---- the hot path ----------------------------------------------------------------------------*/
 /* (all of these: a NaN observation on a handle with SMC_FLAG_NAN_MISSING is a missing step, "missing observations" above) */

@@ -44,6 +44,7 @@ EXPORTS = [
     "smc_host_ibis_smooth_flags", "smc_host_ibis_sample_paths_flags", "smc_host_kalman_steps",
     "smc_set_reference", "smc_reference_from_paths", "smc_get_reference", "smc_host_conditional_slot", "smc_host_logobs",
     "smc_smooth_pairs", "smc_host_smooth_pairs",
+    "smc_live_bytes",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -135,6 +136,7 @@ def lib():
     L.smc_device_rb_step.argtypes = [_dp, _dp, _dp, C.c_double, C.c_int, C.c_int64, _dp, _dp, C.c_int]
     L.smc_host_guided_steps.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int64, _dp, _dp]
     L.smc_get_flags.argtypes = [h, _u32p]
+    L.smc_live_bytes.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.smc_set_reference.argtypes = [h, _dp, C.c_int64]
     L.smc_reference_from_paths.argtypes = [h, C.c_int64, C.POINTER(C.c_int64)]
     L.smc_get_reference.argtypes = [h, _dp, C.POINTER(C.c_int64)]
@@ -374,6 +376,13 @@ def host_guided_steps(model_id, raw, kind, par, xp, z, y):
     lw = np.zeros(n)
     check(lib().smc_host_guided_steps(int(model_id), _d(raw), int(kind), _d(par), _d(xp), _d(z), float(y), n, _d(x), _d(lw)))
     return x, lw
+
+
+def live_bytes():
+    """(device bytes, pinned host bytes) the handles, communicators and cached bundles of this process hold (smc_live_bytes)"""
+    dev, pin = C.c_int64(0), C.c_int64(0)
+    check(lib().smc_live_bytes(C.byref(dev), C.byref(pin)))
+    return int(dev.value), int(pin.value)
 
 
 def device_guided_step(model_id, raw, kind, par, xp, z, y, device=0):

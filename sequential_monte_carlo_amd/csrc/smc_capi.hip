@@ -102,7 +102,7 @@ int cond_refuse(const char* who) {
 // last argument)
 hipError_t do_init(smc_filter_s* h, double y) {
     return by_variant<ENTRY_INIT>(h->model, pick_variant(h, ENTRY_INIT, nan_missing(h) && y != y),
-                                  [&](auto L) { return L.init(h->v, h->geo, h->cur, y, h->cond.d_xref, h->stream); });
+                                  [&](auto L) { return L.init(h->v, h->geo, h->cur, y, h->cond.d_xref.as<double>(), h->stream); });
 }
 // filters with more segments than threads per workgroup (v.tabD): the segment table of the current weights, built once (k_table;
 // emit as k_step's emit_prev: 0 nothing, 1 (logmu, ess) from the full records, 2 from the totals)
@@ -148,7 +148,7 @@ hipError_t do_step(smc_filter_s* h, uint32_t t, int emit_prev, double y, const d
     const double* xrow = nullptr;
     if (conditional(h)) {
         if (!h->cond.d_xref || (int64_t)t >= h->cond.T) return hipErrorInvalidValue;   // (smc_step has refused with a message)
-        xrow = h->cond.d_xref + (size_t)t * (size_t)h->d * (size_t)h->v.ntheta;
+        xrow = h->cond.d_xref.as<double>() + (size_t)t * (size_t)h->d * (size_t)h->v.ntheta;
     }
     // the step API's observation, or the series' (gap_y: set only when a flagged handle's series holds a NaN)
     const bool gap = h->v.y ? (h->gap_y && h->gap_y[t] != h->gap_y[t]) : (nan_missing(h) && y != y);
@@ -165,10 +165,10 @@ hipError_t ensure_breaks(smc_filter_s* h, uint32_t t, uint32_t t_end) {
     if (!h->d_brk) {
         size_t steps = ((size_t)32 << 20) / (per_step * 8);    // <= 32 MiB of break points at a time
         steps = steps < 1 ? 1 : (steps > 1024 ? 1024 : steps);
-        hipError_t e = hipMalloc((void**)&h->d_brk, steps * per_step * 8);
+        hipError_t e = h->d_brk.grow(steps * per_step * 8);
         if (e != hipSuccess) return e;
         h->brk_cap = (uint32_t)steps;
-        v.brk = h->d_brk;
+        v.brk = h->d_brk.as<uint64_t>();
     }
     uint32_t cnt = t_end > t ? t_end - t : 1;                  // no further than the caller will go
     cnt = cnt > h->brk_cap ? h->brk_cap : cnt;
@@ -177,14 +177,14 @@ hipError_t ensure_breaks(smc_filter_s* h, uint32_t t, uint32_t t_end) {
     static std::atomic<bool> raised[16] = {};   // filters of more than 8187 segments: beyond the default limit of dynamic LDS
     hipError_t e = raise_lds_limit(k_breaks<TH>, lds, raised);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_breaks<TH>), dim3(cnt, v.ntheta), dim3(TH), lds, h->stream, v, t, h->d_brk);
+    hipLaunchKernelGGL((k_breaks<TH>), dim3(cnt, v.ntheta), dim3(TH), lds, h->stream, v, t, h->d_brk.as<uint64_t>());
     v.brk_t0 = t;
     h->brk_count = cnt;
     return hipGetLastError();
 }
 static hipError_t do_window(smc_filter_s* h, int k, int bout) {   // (win.gap: a flagged handle's window with a NaN in it)
     return by_variant<ENTRY_WINDOW>(h->model, pick_variant(h, ENTRY_WINDOW, h->win.gap),
-                                    [&](auto L) { return L.window(h->v, k, h->d_recs, (int)h->t, h->cur, bout, h->win.h_out, h->stream); });
+                                    [&](auto L) { return L.window(h->v, k, h->d_recs.as<StepRec>(), (int)h->t, h->cur, bout, h->win.h_out.as<double>(), h->stream); });
 }
 
 hipError_t do_finalize(smc_filter_s* h, int first_emit, uint32_t t_emit) {
@@ -198,17 +198,18 @@ hipError_t do_finalize(smc_filter_s* h, int first_emit, uint32_t t_emit) {
 // ---- lifetime ----------------------------------------------------------------------------------
 // What every handle needs and the runtime is slow to give back (hipFree, hipStreamDestroy and hipHostFree made smc_destroy cost
 // 0.48 ms - twice the hundred steps of a 1024-particle filter): the slab, the stream, the two events and the pinned mirror of a
-// destroyed handle are kept (a few, bounded in bytes) and handed to the next smc_create that fits them.
+// destroyed handle are kept (a few, bounded in bytes) and handed to the next smc_create that fits them.  The blocks MOVE between
+// handle, bundle and cache; a bundle that is dropped frees them.  The stream and the events are plain handles here: whoever
+// holds the bundle last (smc_destroy, when the cache refuses it) destroys them.
 namespace {
 struct Bundle {
     int device = -1;
-    char* slab = nullptr; size_t slab_bytes = 0;
-    double* pin = nullptr; size_t pin_bytes = 0;
+    DevBlock slab;
+    PinBlock pin;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double* d_y = nullptr; int64_t ycap = 0;          // the series buffer and the per-step records of the whole-series calls
-    void* d_recs = nullptr; size_t rec_bytes = 0;     // (whatever the destroyed handle had grown them to)
-    void* h_params = nullptr; size_t params_bytes = 0;   // pinned twin of the parameter rows
+    DevBlock d_y, d_recs;   // the series buffer and the per-step records of the whole-series calls (whatever the destroyed handle had grown them to)
+    PinBlock h_params;      // pinned twin of the parameter rows
 };
 struct BundleCache {
     std::mutex mu;
@@ -218,21 +219,21 @@ struct BundleCache {
     bool take(int device, size_t slab_bytes, size_t pin_bytes, Bundle& out) {
         std::lock_guard<std::mutex> g(mu);
         for (size_t i = 0; i < free_list.size(); ++i) {
-            const Bundle& b = free_list[i];
-            if (b.device == device && b.slab_bytes >= slab_bytes && b.slab_bytes <= 2 * slab_bytes + 4096 && b.pin_bytes >= pin_bytes) {
-                out = b;
-                bytes -= b.slab_bytes;
+            Bundle& b = free_list[i];
+            if (b.device == device && b.slab.bytes() >= slab_bytes && b.slab.bytes() <= 2 * slab_bytes + 4096 && b.pin.bytes() >= pin_bytes) {
+                bytes -= b.slab.bytes();
+                out = std::move(b);
                 free_list.erase(free_list.begin() + (long)i);
                 return true;
             }
         }
         return false;
     }
-    bool give(const Bundle& b) {
+    bool give(Bundle& b) {   // false: refused, b is untouched
         std::lock_guard<std::mutex> g(mu);
-        if (free_list.size() >= MAX_COUNT || bytes + b.slab_bytes > MAX_BYTES) return false;
-        free_list.push_back(b);
-        bytes += b.slab_bytes;
+        if (free_list.size() >= MAX_COUNT || bytes + b.slab.bytes() > MAX_BYTES) return false;
+        bytes += b.slab.bytes();
+        free_list.push_back(std::move(b));
         return true;
     }
 };
@@ -320,22 +321,20 @@ extern "C" int smc_create(int model_id, int64_t n_theta, int64_t n_x, int seg, u
         const size_t o_anc = (flags & SMC_FLAG_ANCESTORS) ? slab.take(np * 4) : 0;
         const size_t o_logZ = slab.take(nt * 8), o_lm = slab.take(nt * 8), o_es = slab.take(nt * 8), o_K = slab.take(nt * 8), o_D = slab.take(nt * 8);
         const size_t o_tD = gtab ? slab.take(nt * (size_t)v.nseg_p2 * 8) : 0, o_tsh = gtab ? slab.take(nt * (size_t)v.nseg_p2 * 4) : 0;
-        h->slab_bytes = slab.bytes;
         if (bundle_cache().take(device, slab.bytes, 4 * nt * 8, bun)) {
-            h->d_slab = bun.slab; h->slab_bytes = bun.slab_bytes; h->stream = bun.stream; h->ev0 = bun.ev0; h->ev1 = bun.ev1;
-            h->h_pin = bun.pin; h->pin_bytes = bun.pin_bytes;
-            h->d_y = bun.d_y; h->ycap = bun.ycap;
-            h->d_recs = (decltype(h->d_recs))bun.d_recs; h->reccap = (int64_t)(bun.rec_bytes / (nt * sizeof(*h->d_recs)));
-            if (bun.params_bytes >= nt * sizeof(Params)) h->h_params = (Params*)bun.h_params;
-            else if (bun.h_params) (void)hipHostFree(bun.h_params);
+            h->d_slab = std::move(bun.slab); h->stream = bun.stream; h->ev0 = bun.ev0; h->ev1 = bun.ev1;
+            h->h_pin = std::move(bun.pin);
+            h->d_y = std::move(bun.d_y);
+            h->d_recs = std::move(bun.d_recs);   // (how many steps it holds for THIS handle's n_theta: ensure_recs)
+            if (bun.h_params.bytes() >= nt * sizeof(Params)) h->h_params = std::move(bun.h_params);   // (else freed with bun)
         } else {
             TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
             TRY(hipEventCreate(&h->ev0));
             TRY(hipEventCreate(&h->ev1));
-            TRY(hipMalloc((void**)&h->d_slab, slab.bytes));
+            TRY(h->d_slab.grow(slab.bytes));
         }
-        TRY(hipMemsetAsync(h->d_slab, 0, slab.bytes, h->stream));
-        char* base = h->d_slab;
+        TRY(hipMemsetAsync(h->d_slab.as<char>(), 0, slab.bytes, h->stream));
+        char* base = h->d_slab.as<char>();
         h->d_params = (decltype(h->d_params))(base + o_params); h->d_stream = (decltype(h->d_stream))(base + o_stream);
         h->d_perm = (decltype(h->d_perm))(base + o_perm); h->d_logZ_tmp = (double*)(base + o_ztmp);
         for (int b = 0; b < 2; ++b) {
@@ -348,12 +347,9 @@ extern "C" int smc_create(int model_id, int64_t n_theta, int64_t n_x, int seg, u
         v.last_K = (double*)(base + o_K); v.last_D = (uint64_t*)(base + o_D);
         if (gtab) { v.tabD = (uint64_t*)(base + o_tD); v.tabsh = (int*)(base + o_tsh); }
     }
-    if (!h->h_pin) {
-        TRY(hipHostMalloc((void**)&h->h_pin, 4 * nt * 8, hipHostMallocDefault));   // coherent, device-visible
-        h->pin_bytes = 4 * nt * 8;
-    }
-    memset(h->h_pin, 0, 4 * nt * 8);
-    v.host_out = h->h_pin;
+    TRY(h->h_pin.grow(4 * nt * 8));   // (a recycled one holds at least that: take)
+    memset(h->h_pin.as<double>(), 0, 4 * nt * 8);
+    v.host_out = h->h_pin.as<double>();
     std::vector<uint32_t> st(nt);
     for (size_t m = 0; m < nt; ++m) st[m] = (uint32_t)m;
     TRY(hipMemcpyAsync(h->d_stream, st.data(), nt * 4, hipMemcpyHostToDevice, h->stream));
@@ -375,36 +371,14 @@ extern "C" int smc_destroy(smc_handle h) {
 #ifdef SMC_ABLATE
     abl_report(h);
 #endif
-    Bundle bun;
-    bun.device = h->device; bun.slab = h->d_slab; bun.slab_bytes = h->slab_bytes; bun.pin = h->h_pin; bun.pin_bytes = h->pin_bytes;
-    bun.stream = h->stream; bun.ev0 = h->ev0; bun.ev1 = h->ev1;
-    bun.d_y = h->d_y; bun.ycap = h->ycap; bun.d_recs = h->d_recs; bun.rec_bytes = (size_t)h->reccap * (size_t)h->v.ntheta * sizeof(*h->d_recs);
-    bun.h_params = h->h_params; bun.params_bytes = h->h_params ? (size_t)h->v.ntheta * sizeof(Params) : 0;
-    const bool kept = h->d_slab && h->h_pin && h->stream && h->ev0 && h->ev1 && bundle_cache().give(bun);   // (the stream is idle: synchronised above)
-    if (!kept) {
-        (void)hipFree(h->d_slab);   // x, C, the records, the per-filter scalars, the segment table, params / streams / perm
-        if (h->h_pin) (void)hipHostFree(h->h_pin);
+    // a whole handle (smc_create's TRY comes here with half of one) offers the cache its bundle (the stream is idle: synchronised
+    // above); one the cache refuses is freed here, and everything else the handle owns with the handle
+    bool kept = false;
+    if (h->d_slab && h->h_pin && h->stream && h->ev0 && h->ev1) {
+        Bundle bun{h->device, std::move(h->d_slab), std::move(h->h_pin), h->stream, h->ev0, h->ev1, std::move(h->d_y), std::move(h->d_recs),
+                   std::move(h->h_params)};
+        kept = bundle_cache().give(bun);
     }
-    if (h->pm.h_out) (void)hipHostFree(h->pm.h_out);
-    if (h->pm.h_in) (void)hipHostFree(h->pm.h_in);
-    if (h->h_perm) (void)hipHostFree(h->h_perm);
-    if (h->h_params && !kept) (void)hipHostFree(h->h_params);
-    if (h->d_prop) (void)hipFree(h->d_prop);
-    (void)hipFree(h->cond.d_xref);   // (the reference never travels with the bundle)
-    if (h->h_prop) (void)hipHostFree(h->h_prop);
-    history_free(h);
-    (void)hipFree(h->skip.d_mask); (void)hipFree(h->skip.d_order);
-    if (h->win.h_out) (void)hipHostFree(h->win.h_out);
-    if (h->summ.h_once) (void)hipHostFree(h->summ.h_once);
-    (void)hipFree(h->pm.dev.order);
-    (void)hipFree(h->pm.d_in);   // pm.theta, pm.logZ, pm.chol, pm.nrun, pm.counts, pm.any live in this block
-    (void)hipFree(h->pm.dev.prop); (void)hipFree(h->pm.dev.lp); (void)hipFree(h->pm.dev.skip); (void)hipFree(h->pm.dev.mask);
-    if (h->d_brk) (void)hipFree(h->d_brk);
-    if (h->summ.d_ms) (void)hipFree(h->summ.d_ms);
-    if (h->fc.d_buf) (void)hipFree(h->fc.d_buf);
-    if (!kept) (void)hipFree(h->d_y);
-    (void)hipFree(h->d_tr_logmu); (void)hipFree(h->d_tr_ess); (void)hipFree(h->d_wdense); if (!kept) (void)hipFree(h->d_recs);
-    (void)hipFree(h->summ.d_q); (void)hipFree(h->summ.d_m);
     if (!kept) {
         if (h->ev0) (void)hipEventDestroy(h->ev0);
         if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -416,8 +390,8 @@ extern "C" int smc_destroy(smc_handle h) {
 
 // the proposal row of filter m from its parameter row (and, AFFINE, from the stored row): smc_spec.h "proposals"
 static void fill_proposal(smc_handle h, int m) {
-    const Params& P = h->h_params[m];
-    double* q = h->h_prop[m].p;
+    const Params& P = h->h_params.as<Params>()[m];
+    double* q = h->h_prop.as<PropRow>()[m].p;
     for (int k = 0; k < NPARAM; ++k) q[k] = 0.0;
     if (h->v.prop_kind == PROP_AFFINE)
         for (int k = 0; k < PROP_NPAR; ++k) q[k] = h->prop_par[(size_t)m * PROP_NPAR + k];
@@ -430,9 +404,9 @@ extern "C" int smc_set_params(smc_handle h, const double* raw) {
     const int nraw = model_nraw_rt(h->model);
     // the rows are derived into a pinned twin and copied from there: the call does not wait for the device (what follows on the
     // handle is ordered behind the copy); a previous copy out of the twin has completed once the stream is idle
-    if (!h->h_params) HIPCHK(hipHostMalloc((void**)&h->h_params, (size_t)h->v.ntheta * sizeof(Params), hipHostMallocDefault));
+    if (!h->h_params) HIPCHK(h->h_params.grow((size_t)h->v.ntheta * sizeof(Params)));
     else HIPCHK(hipStreamSynchronize(h->stream));
-    Params* P = h->h_params;
+    Params* P = h->h_params.as<Params>();
     for (int m = 0; m < h->v.ntheta; ++m) {
         for (int k = 0; k < NPARAM; ++k) P[m].raw[k] = k < nraw ? raw[(size_t)m * nraw + k] : 0.0;
         derive_params(h->model, P[m].raw, P[m].der);
@@ -442,7 +416,7 @@ extern "C" int smc_set_params(smc_handle h, const double* raw) {
     h->hot.prm0 = P[0];
     h->hot.prm_ok = true;
     if (h->v.prop_kind)   // a guided handle: the proposal rows follow the parameter rows
-        HIPCHK(hipMemcpyAsync(h->d_prop, h->h_prop, (size_t)h->v.ntheta * sizeof(PropRow), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_prop.as<PropRow>(), h->h_prop.as<PropRow>(), (size_t)h->v.ntheta * sizeof(PropRow), hipMemcpyHostToDevice, h->stream));
     h->have_params = true;
     return SMC_OK;
 }
@@ -462,26 +436,26 @@ extern "C" int smc_set_proposal(smc_handle h, int kind, const double* par) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     const size_t nt = (size_t)h->v.ntheta;
-    if (kind != PROP_NONE && !h->d_prop) {
-        HIPCHK(hipMalloc((void**)&h->d_prop, nt * sizeof(PropRow)));
-        HIPCHK(hipHostMalloc((void**)&h->h_prop, nt * sizeof(PropRow), hipHostMallocDefault));
+    if (kind != PROP_NONE) {
+        HIPCHK(h->d_prop.grow(nt * sizeof(PropRow)));
+        HIPCHK(h->h_prop.grow(nt * sizeof(PropRow)));
     }
     if (kind == PROP_AFFINE) h->prop_par.assign(par, par + nt * PROP_NPAR);
     else h->prop_par.clear();
     h->v.prop_kind = kind;
-    h->v.prop = kind != PROP_NONE ? h->d_prop : nullptr;
+    h->v.prop = kind != PROP_NONE ? h->d_prop.as<PropRow>() : nullptr;
     h->win.k = 0;   // an uncommitted window belongs to the previous proposal
     if (kind == PROP_NONE) return SMC_OK;
     // the rows on the device.  The parameter rows they derive from are read back first: a proposal handle of the device PMMH had
     // them written there (k_pmmh_propose), not through the pinned twin.  Without parameters yet: the rows as given, the
     // constants follow with smc_set_params / the device PMMH
     if (!h->h_params) {
-        HIPCHK(hipHostMalloc((void**)&h->h_params, nt * sizeof(Params), hipHostMallocDefault));
-        memset(h->h_params, 0, nt * sizeof(Params));
+        HIPCHK(h->h_params.grow(nt * sizeof(Params)));
+        memset(h->h_params.as<Params>(), 0, nt * sizeof(Params));
     }
-    if (h->have_params) HIPCHK(hipMemcpy(h->h_params, h->d_params, nt * sizeof(Params), hipMemcpyDeviceToHost));
+    if (h->have_params) HIPCHK(hipMemcpy(h->h_params.as<Params>(), h->d_params, nt * sizeof(Params), hipMemcpyDeviceToHost));
     for (int m = 0; m < h->v.ntheta; ++m) fill_proposal(h, m);
-    HIPCHK(hipMemcpyAsync(h->d_prop, h->h_prop, nt * sizeof(PropRow), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_prop.as<PropRow>(), h->h_prop.as<PropRow>(), nt * sizeof(PropRow), hipMemcpyHostToDevice, h->stream));
     return SMC_OK;
 }
 
@@ -509,27 +483,16 @@ extern "C" int smc_reseed(smc_handle h, uint64_t seed) {
     return SMC_OK;
 }
 
-int ensure_y(smc_handle h, int64_t T) {
-    if (T > h->ycap) {
+// the blocks of the whole-series calls hold T steps (old block first, behind an idle stream; almost always a no-op)
+static int ensure_steps(smc_handle h, DevBlock& b, size_t bytes) {
+    if (bytes > b.bytes()) {
         HIPCHK(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->d_y);
-        h->d_y = nullptr;
-        HIPCHK(dalloc(&h->d_y, (size_t)T));
-        h->ycap = T;
+        HIPCHK(b.grow(bytes));
     }
     return SMC_OK;
 }
-
-int ensure_recs(smc_handle h, int64_t T) {
-    if (T > h->reccap) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->d_recs);
-        h->d_recs = nullptr;
-        HIPCHK(dalloc(&h->d_recs, (size_t)T * h->v.ntheta));
-        h->reccap = T;
-    }
-    return SMC_OK;
-}
+int ensure_y(smc_handle h, int64_t T) { return ensure_steps(h, h->d_y, (size_t)T * 8); }
+int ensure_recs(smc_handle h, int64_t T) { return ensure_steps(h, h->d_recs, (size_t)T * (size_t)h->v.ntheta * sizeof(StepRec)); }
 
 // Close the timed region (ev1) and hand the requested per-filter result vectors to the caller from the
 // pinned mirror (FilterView::host_out): ONE stream synchronisation, no copy commands.
@@ -540,9 +503,10 @@ int finish_elapsed(smc_handle h, double* logZ, double* logmu, double* ess) {
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     h->last_ms = ms;
-    if (logZ) memcpy(logZ, h->h_pin, nt * 8);
-    if (logmu) memcpy(logmu, h->h_pin + nt, nt * 8);
-    if (ess) memcpy(ess, h->h_pin + 2 * nt, nt * 8);
+    const double* pin = h->h_pin.as<double>();
+    if (logZ) memcpy(logZ, pin, nt * 8);
+    if (logmu) memcpy(logmu, pin + nt, nt * 8);
+    if (ess) memcpy(ess, pin + 2 * nt, nt * 8);
     return SMC_OK;
 }
 
@@ -551,7 +515,8 @@ int finish_elapsed(smc_handle h, double* logZ, double* logmu, double* ess) {
 // that does not show up within 50 ms is looked for once more after a real synchronisation (a faulted launch reports there).
 static int wait_ticket(smc_handle h, uint32_t seq, double* logmu, double* ess) {
     const size_t nt = (size_t)h->v.ntheta;
-    const volatile double* tk = h->h_pin + 3 * nt;
+    const double* pin = h->h_pin.as<double>();
+    const volatile double* tk = pin + 3 * nt;
     const double want = (double)seq;
     const auto t0 = std::chrono::steady_clock::now();
     bool synced = false;
@@ -566,8 +531,8 @@ static int wait_ticket(smc_handle h, uint32_t seq, double* logmu, double* ess) {
         __builtin_ia32_pause();
     }
     std::atomic_thread_fence(std::memory_order_acquire);
-    if (logmu) memcpy(logmu, h->h_pin + nt, nt * 8);
-    if (ess) memcpy(ess, h->h_pin + 2 * nt, nt * 8);
+    if (logmu) memcpy(logmu, pin + nt, nt * 8);
+    if (ess) memcpy(ess, pin + 2 * nt, nt * 8);
     h->last_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();   // host clock of the wait
     return SMC_OK;
 }
@@ -666,15 +631,15 @@ extern "C" int smc_step_window(smc_handle h, const double* y, int k, double* log
     if ((rc = ensure_y(h, WIN_MAX))) return rc;
     if ((rc = ensure_recs(h, WIN_MAX))) return rc;
     const size_t nt = (size_t)h->v.ntheta;
-    if (!h->win.h_out) HIPCHK(hipHostMalloc((void**)&h->win.h_out, 2 * (size_t)WIN_MAX * nt * 8, hipHostMallocDefault));
+    HIPCHK(h->win.h_out.grow(2 * (size_t)WIN_MAX * nt * 8));
     const bool summ = summaries_on(h);
     if (summ && h->v.systematic) return fail(SMC_EINVAL, "smc_step_window: per-step summaries need the default (multinomial) resampler");
     if (summ && !summaries_fit_lds(h)) return fail(SMC_EINVAL, "smc_step_window: no LDS left for the summaries of filters this long; fewer levels, or smc_step");
     if (summ && (rc = ensure_summaries(h, WIN_MAX))) return rc;
     h->summ.T = 0;
     h->summ.skip.clear();   // (the skip mask applies to smc_log_likelihood only)
-    HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)k * 8, hipMemcpyHostToDevice, h->stream));
-    h->v.y = h->d_y;
+    HIPCHK(hipMemcpyAsync(h->d_y.as<double>(), y, (size_t)k * 8, hipMemcpyHostToDevice, h->stream));
+    h->v.y = h->d_y.as<double>();
     if (summ) view_summaries(h);
     h->win.gap = series_has_gap(h, y, k);
     rc = launch_window_steps(h, k);
@@ -683,8 +648,8 @@ extern "C" int smc_step_window(smc_handle h, const double* y, int k, double* log
     if (rc) return rc;
     if (summ) h->summ.T = k;
     if ((rc = finish_elapsed(h))) return rc;
-    if (logmu) memcpy(logmu, h->win.h_out, (size_t)k * nt * 8);
-    if (ess) memcpy(ess, h->win.h_out + (size_t)k * nt, (size_t)k * nt * 8);
+    if (logmu) memcpy(logmu, h->win.h_out.as<double>(), (size_t)k * nt * 8);
+    if (ess) memcpy(ess, h->win.h_out.as<double>() + (size_t)k * nt, (size_t)k * nt * 8);
     h->win.k = k;
     return SMC_OK;
 }
@@ -699,12 +664,12 @@ extern "C" int smc_step_commit(smc_handle h, int j) {
     h->win.k = 0;
     if (j == 0) return SMC_OK;            // nothing kept: the filters stand where they stood before the window
     if (j < k) {                          // keep a prefix: the same j steps again (counter-based random numbers: the same bits)
-        h->v.y = h->d_y;
+        h->v.y = h->d_y.as<double>();
         int rc = launch_window_steps(h, j);
         h->v.y = nullptr;
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_commit, dim3((unsigned)((h->v.ntheta + 127) / 128)), dim3(128), 0, h->stream, h->v, j, h->d_recs);
+    hipLaunchKernelGGL(k_commit, dim3((unsigned)((h->v.ntheta + 127) / 128)), dim3(128), 0, h->stream, h->v, j, h->d_recs.as<StepRec>());
     HIPCHK(hipGetLastError());
     h->cur ^= 1; h->t += (uint32_t)j; h->emitted = true;
     return SMC_OK;      // no wait: whatever the caller does next with this handle is ordered behind on its stream
@@ -717,8 +682,8 @@ extern "C" int smc_set_skip(smc_handle h, const uint8_t* skip) {
     HIPCHK(hipSetDevice(h->device));
     if (!skip) { h->skip.on = false; h->skip.h_mask.clear(); return SMC_OK; }
     const int nt = h->v.ntheta;
-    if (!h->skip.d_mask) HIPCHK(dalloc(&h->skip.d_mask, (size_t)nt));
-    if (!h->skip.d_order) HIPCHK(dalloc(&h->skip.d_order, (size_t)nt + 1));
+    HIPCHK(h->skip.d_mask.grow((size_t)nt));
+    HIPCHK(h->skip.d_order.grow(((size_t)nt + 1) * 4));
     std::vector<int32_t> ord((size_t)nt + 1);
     int na = 0, ns = 0;
     for (int m = 0; m < nt; ++m) {
@@ -726,8 +691,8 @@ extern "C" int smc_set_skip(smc_handle h, const uint8_t* skip) {
         else ord[(size_t)na++] = m;
     }
     ord[(size_t)nt] = na;
-    HIPCHK(hipMemcpyAsync(h->skip.d_mask, skip, (size_t)nt, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->skip.d_order, ord.data(), ord.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->skip.d_mask.as<unsigned char>(), skip, (size_t)nt, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->skip.d_order.as<int32_t>(), ord.data(), ord.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->skip.h_mask.assign(skip, skip + nt);
     h->skip.on = true;

@@ -43,17 +43,10 @@ extern "C" int smc_set_reference(smc_handle h, const double* xref, int64_t T) {
         if (!finite_d(xref[i])) return fail(SMC_EINVAL, "smc_set_reference: entry " + std::to_string(i) + " of the reference is not finite");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (T != h->cond.T || !h->cond.d_xref) {   // (the new block first: a failed allocation leaves the handle as it was)
-        double* blk = nullptr;
-        if (hipMalloc((void**)&blk, words * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SMC_ENOMEM, "smc_set_reference: hipMalloc of the reference");
-        }
-        (void)hipFree(h->cond.d_xref);
-        h->cond.d_xref = blk;
-        h->cond.T = T;
-    }
-    HIPCHK(hipMemcpy(h->cond.d_xref, xref, words * 8, hipMemcpyHostToDevice));
+    // (the new block first: a failed allocation leaves the handle as it was)
+    if (h->cond.d_xref.grow_keep(words * 8) != hipSuccess) return fail(SMC_ENOMEM, "smc_set_reference: hipMalloc of the reference");
+    h->cond.T = T;
+    HIPCHK(hipMemcpy(h->cond.d_xref.as<double>(), xref, words * 8, hipMemcpyHostToDevice));
     return SMC_OK;
 }
 
@@ -65,7 +58,7 @@ extern "C" int smc_get_reference(smc_handle h, double* xref, int64_t* T) {
     if (!xref) return SMC_OK;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(xref, h->cond.d_xref, (size_t)h->cond.T * (size_t)h->d * (size_t)h->v.ntheta * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(xref, h->cond.d_xref.as<double>(), (size_t)h->cond.T * (size_t)h->d * (size_t)h->v.ntheta * 8, hipMemcpyDeviceToHost));
     return SMC_OK;
 }
 
@@ -79,7 +72,7 @@ extern "C" int smc_reference_from_paths(smc_handle h, int64_t p, int64_t* kept) 
     const size_t nt = (size_t)h->v.ntheta, d = (size_t)h->d;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const int32_t* d_idx = (const int32_t*)(h->hist.d_path + h->hist.walk_idx);
+    const int32_t* d_idx = (const int32_t*)(h->hist.d_path.as<char>() + h->hist.walk_idx);
     // the filters whose path is dead keep their reference: they are counted first, because a reference of another length (or none)
     // has nothing for them to keep
     std::vector<int32_t> first(nt);
@@ -89,18 +82,10 @@ extern "C" int smc_reference_from_paths(smc_handle h, int64_t p, int64_t* kept) 
     if (nkept && (!h->cond.d_xref || h->cond.T != T))
         return fail(SMC_ESTATE, "smc_reference_from_paths: path p of " + std::to_string(nkept) + " filter(s) is dead and the handle has no reference of " +
                                     std::to_string(T) + " steps for them to keep");
-    if (!h->cond.d_xref || h->cond.T != T) {
-        double* blk = nullptr;
-        if (hipMalloc((void**)&blk, (size_t)T * d * nt * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SMC_ENOMEM, "smc_reference_from_paths: hipMalloc of the reference");
-        }
-        (void)hipFree(h->cond.d_xref);
-        h->cond.d_xref = blk;
-        h->cond.T = T;
-    }
+    if (h->cond.d_xref.grow_keep((size_t)T * d * nt * 8) != hipSuccess) return fail(SMC_ENOMEM, "smc_reference_from_paths: hipMalloc of the reference");
+    h->cond.T = T;
     hipLaunchKernelGGL(k_reference_gather, dim3((unsigned)((nt + 127) / 128), (unsigned)(T < 65535 ? T : 65535)), dim3(128), 0, h->stream, T, (int64_t)h->v.n, (int)nt, (int)d, M, p,
-                       (const double*)h->hist.d_x, d_idx, h->cond.d_xref);
+                       (const double*)h->hist.d_x, d_idx, h->cond.d_xref.as<double>());
     HIPCHK(hipGetLastError());
     if (kept) *kept = nkept;
     return SMC_OK;   // no wait: the next sweep's launches are ordered behind the gather on the handle's stream

@@ -50,26 +50,19 @@ Plan make_plan(const smc_filter_s* h, int64_t H, bool summaries) {
 }
 }  // namespace
 
-// the handle's forecast block holds `bytes`: grown on demand; SMC_ENOMEM leaves the handle without one, otherwise as it was
+// the handle's forecast block holds `bytes`: grown on demand (old block first); SMC_ENOMEM leaves the handle without one, otherwise as it was
 static int ensure_forecast(smc_handle h, size_t bytes) {
-    if (bytes <= h->fc.bytes) return SMC_OK;
+    if (bytes <= h->fc.d_buf.bytes()) return SMC_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->fc.d_buf) (void)hipFree(h->fc.d_buf);
-    h->fc.d_buf = nullptr;
-    h->fc.bytes = 0;
-    if (hipMalloc((void**)&h->fc.d_buf, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->fc.d_buf = nullptr;
+    if (h->fc.d_buf.grow(bytes) != hipSuccess)
         return fail(SMC_ENOMEM, "forecast: out of device memory for the propagated clouds (" + std::to_string(bytes) + " bytes); a smaller SMC_FORECAST_BLOCK needs less");
-    }
-    h->fc.bytes = bytes;
     return SMC_OK;
 }
 
 // horizons k0 .. k0 + nk - 1 (1-based) into the block's clouds, from the handle's state (k0 == 1) or from the last horizon of the
 // block before
 static int enqueue_forecast_block(smc_handle h, const Plan& p, uint64_t seed, int64_t k0, int nk, int nk_prev) {
-    double* out = (double*)h->fc.d_buf;
+    double* out = h->fc.d_buf.as<double>();
     const double* src = k0 == 1 ? h->v.x[h->cur] : out + (size_t)(nk_prev - 1) * p.rows * p.plane;
     HIPCHK(by_variant<ENTRY_FORECAST>(h->model, VARIANT_PLAIN, [&](auto L) { return L.forecast(h->v, h->geo, src, seed, (uint32_t)k0, nk, out, h->stream); }));
     return SMC_OK;
@@ -90,8 +83,8 @@ extern "C" int smc_forecast(smc_handle h, int64_t H, uint64_t forecast_seed, int
     if ((rc = ensure_forecast(h, pl.bytes))) return rc;
     const size_t nth = (size_t)h->v.ntheta, d = (size_t)h->d;
     const bool want_q = np > 0 && q, want_oq = np > 0 && obs_q, want_m = mean || var, want_om = obs_mean || obs_var;
-    uint64_t* ms = (uint64_t*)(h->fc.d_buf + pl.off_ms);
-    double* res = (double*)(h->fc.d_buf + pl.off_res);
+    uint64_t* ms = (uint64_t*)(h->fc.d_buf.as<char>() + pl.off_ms);
+    double* res = (double*)(h->fc.d_buf.as<char>() + pl.off_res);
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     // (the summary kernels want their histograms and counters zero and leave them so: once per call is enough, and cheap)
     HIPCHK(hipMemsetAsync(ms, 0, pl.off_res - pl.off_ms, h->stream));
@@ -101,7 +94,7 @@ extern "C" int smc_forecast(smc_handle h, int64_t H, uint64_t forecast_seed, int
         if ((rc = enqueue_forecast_block(h, pl, forecast_seed, k0, nk, nk_prev))) return rc;
         nk_prev = nk;
         for (int j = 0; j < nk; ++j) {
-            const double* cloud = (const double*)h->fc.d_buf + (size_t)j * pl.rows * pl.plane;
+            const double* cloud = h->fc.d_buf.as<double>() + (size_t)j * pl.rows * pl.plane;
             double* r = res + (size_t)(k0 - 1 + j) * pl.res_per;
             double *r_q = r, *r_m = r_q + nth * QMAX, *r_v = r_m + d * nth, *r_oq = r_v + d * nth, *r_om = r_oq + nth * QMAX, *r_ov = r_om + 3 * nth;
             if ((want_q || want_m) && (rc = enqueue_cloud_summaries(h, cloud, h->d, ms, pl.ms_rows, component, p, want_q ? np : 0, want_m, r_q, r_m, r_v))) return rc;
@@ -147,7 +140,7 @@ extern "C" int smc_forecast_cloud(smc_handle h, int64_t H, uint64_t forecast_see
         if ((rc = finish_elapsed(h))) return rc;
         total_ms += h->last_ms;
         for (int j = 0; j < nk; ++j) {   // dense rows out of the padded ones, as smc_get_state copies x
-            const double* cloud = (const double*)h->fc.d_buf + (size_t)j * pl.rows * pl.plane;
+            const double* cloud = h->fc.d_buf.as<double>() + (size_t)j * pl.rows * pl.plane;
             const size_t k = (size_t)(k0 - 1 + j);
             if (xf) HIPCHK(hipMemcpy2D(xf + k * d * nth * n, n * 8, cloud, (size_t)v.npad * 8, n * 8, d * nth, hipMemcpyDeviceToHost));
             if (yf) HIPCHK(hipMemcpy2D(yf + k * nth * n, n * 8, cloud + d * pl.plane, (size_t)v.npad * 8, n * 8, nth, hipMemcpyDeviceToHost));

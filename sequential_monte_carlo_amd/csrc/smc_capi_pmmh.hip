@@ -31,21 +31,24 @@ extern "C" int smc_pmmh_configure(smc_handle h, int d_theta, const int32_t* prio
     if (!h->pm.d_in) {
         // what a rejuvenation call uploads or clears sits in ONE block (8-byte words): theta | logZ | chol | nrun | counts | any
         const size_t w_theta = nt * MAX_DTHETA, w_chol = (size_t)MAX_DTHETA * MAX_DTHETA, w_any = (nt + 7) / 8;
-        h->pm.in_words = w_theta + nt + w_chol + 2 + w_any;
-        HIPCHK(dalloc(&h->pm.d_in, h->pm.in_words));
-        HIPCHK(hipHostMalloc((void**)&h->pm.h_in, h->pm.in_words * 8, hipHostMallocDefault));
-        h->pm.dev.theta = h->pm.d_in;
+        const size_t in_bytes = (w_theta + nt + w_chol + 2 + w_any) * 8;
+        HIPCHK(h->pm.d_in.grow(in_bytes));
+        HIPCHK(h->pm.h_in.grow(in_bytes));
+        h->pm.dev.theta = h->pm.d_in.as<double>();
         h->pm.dev.logZ = h->pm.dev.theta + w_theta;
         h->pm.dev.chol = h->pm.dev.logZ + nt;
         h->pm.dev.nrun = (unsigned long long*)(h->pm.dev.chol + w_chol);
         h->pm.dev.counts = (int32_t*)(h->pm.dev.nrun + 1);
         h->pm.dev.any = (unsigned char*)(h->pm.dev.nrun + 2);
-        HIPCHK(dalloc(&h->pm.dev.prop, nt * MAX_DTHETA));
-        HIPCHK(dalloc(&h->pm.dev.lp, nt * 2));
-        HIPCHK(dalloc(&h->pm.dev.skip, nt));
-        HIPCHK(dalloc(&h->pm.dev.mask, nt));
-        HIPCHK(dalloc(&h->pm.dev.order, nt));
-        HIPCHK(hipHostMalloc((void**)&h->pm.h_out, (nt * (MAX_DTHETA + 2) + 1) * 8, hipHostMallocDefault));
+        HIPCHK(h->pm.d_prop.grow(nt * MAX_DTHETA * 8));
+        HIPCHK(h->pm.d_lp.grow(nt * 2 * 8));
+        HIPCHK(h->pm.d_skip.grow(nt));
+        HIPCHK(h->pm.d_mask.grow(nt));
+        HIPCHK(h->pm.d_order.grow(nt * 4));
+        h->pm.dev.prop = h->pm.d_prop.as<double>(); h->pm.dev.lp = h->pm.d_lp.as<double>();
+        h->pm.dev.skip = h->pm.d_skip.as<unsigned char>(); h->pm.dev.mask = h->pm.d_mask.as<unsigned char>();
+        h->pm.dev.order = h->pm.d_order.as<int32_t>();
+        HIPCHK(h->pm.h_out.grow((nt * (MAX_DTHETA + 2) + 1) * 8));
     }
     h->pm.spec = sp;
     h->pm.cfg = true;
@@ -91,8 +94,8 @@ extern "C" int smc_pmmh_rejuvenate(smc_handle h, smc_handle main, const double* 
     }
     {   // theta (rows padded to MAX_DTHETA), logZ, the Cholesky factor and the zeros of nrun / counts / any: one pinned block, one copy
         // (the previous call's copy has completed: every call ends with a stream synchronisation)
-        double* in = h->pm.h_in;
-        memset(in, 0, h->pm.in_words * 8);
+        double* in = h->pm.h_in.as<double>();
+        memset(in, 0, h->pm.h_in.bytes());
         for (int m = 0; m < nt; ++m)
             for (int i = 0; i < d; ++i) in[(size_t)m * MAX_DTHETA + i] = theta[(size_t)m * d + i];
         double* in_logZ = in + (size_t)nt * MAX_DTHETA;
@@ -101,8 +104,8 @@ extern "C" int smc_pmmh_rejuvenate(smc_handle h, smc_handle main, const double* 
         for (int i = 0; i < d * d; ++i) in_chol[i] = chol[i];
     }
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->pm.d_in, h->pm.h_in, h->pm.in_words * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_y.as<double>(), y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->pm.d_in.as<double>(), h->pm.h_in.as<double>(), h->pm.h_in.bytes(), hipMemcpyHostToDevice, h->stream));
     const dim3 grid((unsigned)((nt + 127) / 128)), block(128);
     GapScope gaps(h, y, T);   // (a flagged handle: the proposal filters read a NaN as a gap, like smc_log_likelihood)
     for (int c = 0; c < chain; ++c) {
@@ -125,14 +128,15 @@ extern "C" int smc_pmmh_rejuvenate(smc_handle h, smc_handle main, const double* 
             hot_invalidate(main);
         }
     }
-    hipLaunchKernelGGL(k_pmmh_export, grid, block, 0, h->stream, nt, d, h->pm.dev, h->pm.h_out);
+    hipLaunchKernelGGL(k_pmmh_export, grid, block, 0, h->stream, nt, d, h->pm.dev, h->pm.h_out.as<double>());
     HIPCHK(hipGetLastError());
     if ((rc = finish_elapsed(h))) return rc;
     if (main && chain > 0) main->t = h->t;
-    memcpy(theta, h->pm.h_out, (size_t)nt * d * 8);
-    memcpy(logZ, h->pm.h_out + (size_t)nt * d, (size_t)nt * 8);
+    const double* res = h->pm.h_out.as<double>();
+    memcpy(theta, res, (size_t)nt * d * 8);
+    memcpy(logZ, res + (size_t)nt * d, (size_t)nt * 8);
     if (accepted)
-        for (int m = 0; m < nt; ++m) accepted[m] = h->pm.h_out[(size_t)nt * (d + 1) + m] != 0.0 ? 1 : 0;
-    if (filters_run) *filters_run = (int64_t)h->pm.h_out[(size_t)nt * (d + 2)];
+        for (int m = 0; m < nt; ++m) accepted[m] = res[(size_t)nt * (d + 1) + m] != 0.0 ? 1 : 0;
+    if (filters_run) *filters_run = (int64_t)res[(size_t)nt * (d + 2)];
     return SMC_OK;
 }

@@ -9,14 +9,13 @@
 
 using namespace smc;
 
-static int ensure_trace(smc_handle h, int64_t T) {
-    if (T > h->trcap) {
+static int ensure_trace(smc_handle h, int64_t T) {   // (the two traces grow together: old blocks first)
+    const size_t bytes = (size_t)T * (size_t)h->v.ntheta * 8;
+    if (bytes > h->d_tr_logmu.bytes() || bytes > h->d_tr_ess.bytes()) {
         HIPCHK(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->d_tr_logmu); (void)hipFree(h->d_tr_ess);
-        h->d_tr_logmu = h->d_tr_ess = nullptr;
-        HIPCHK(dalloc(&h->d_tr_logmu, (size_t)T * h->v.ntheta));
-        HIPCHK(dalloc(&h->d_tr_ess, (size_t)T * h->v.ntheta));
-        h->trcap = T;
+        h->d_tr_logmu.reset(); h->d_tr_ess.reset();
+        HIPCHK(h->d_tr_logmu.grow(bytes));
+        HIPCHK(h->d_tr_ess.grow(bytes));
     }
     return SMC_OK;
 }
@@ -31,7 +30,7 @@ struct SeriesScope {
 
 static hipError_t do_resident(smc_filter_s* h, int T) {   // (gap_y: a flagged handle's series with a NaN in it, GapScope)
     return by_variant<ENTRY_RESIDENT>(h->model, pick_variant(h, ENTRY_RESIDENT, h->gap_y != nullptr),
-                                      [&](auto L) { return L.resident(h->v, T, h->d_recs, h->stream); });
+                                      [&](auto L) { return L.resident(h->v, T, h->d_recs.as<StepRec>(), h->stream); });
 }
 // The launches of log_likelihood(N, y, model) (particles.jl:132-147) for every filter of the handle, enqueued on
 // its stream: nothing here waits for the device.  y must already be in h->d_y (ensure_y + copy by the caller).
@@ -39,9 +38,9 @@ int enqueue_log_likelihood(smc_handle h, double y0, int64_t T, bool want_trace, 
     // (systematic resampling with per-step summaries: the LDS-resident summary kernels exist for the default law only)
     const bool resident = h->resident_ok && resident_supported(h->model, h->v.seg) && !(summ && (h->v.systematic || !summaries_fit_lds(h)));
     SeriesScope scope(h->v);
-    h->v.y = h->d_y;
-    h->v.trace_logmu = want_trace ? h->d_tr_logmu : nullptr;
-    h->v.trace_ess = want_trace ? h->d_tr_ess : nullptr;
+    h->v.y = h->d_y.as<double>();
+    h->v.trace_logmu = want_trace ? h->d_tr_logmu.as<double>() : nullptr;
+    h->v.trace_ess = want_trace ? h->d_tr_ess.as<double>() : nullptr;
     h->cur = 0;
     h->v.want_s2 = want_trace ? 1 : 0;   // ess_t is read only through the traces; the last step always has it
     int rc = SMC_OK;
@@ -103,8 +102,8 @@ extern "C" int smc_log_likelihood(smc_handle h, const double* y, int64_t T, doub
     if (summ && (rc = ensure_summaries(h, T))) return rc;
     h->summ.T = 0;
     h->summ.skip.clear();
-    HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
-    if (h->skip.on) { h->v.skip = h->skip.d_mask; h->v.order = h->skip.d_order; h->v.n_active = h->skip.d_order + h->v.ntheta; }
+    HIPCHK(hipMemcpyAsync(h->d_y.as<double>(), y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
+    if (h->skip.on) { h->v.skip = h->skip.d_mask.as<unsigned char>(); h->v.order = h->skip.d_order.as<int32_t>(); h->v.n_active = h->v.order + h->v.ntheta; }
     const int cur0 = h->cur;   // where the state of the filters the call leaves out stays
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     {
@@ -114,15 +113,15 @@ extern "C" int smc_log_likelihood(smc_handle h, const double* y, int64_t T, doub
     h->v.skip = nullptr; h->v.order = nullptr; h->v.n_active = nullptr;
     if (rc) return rc;
     // the call ends in the other buffer: the skipped filters' untouched state goes with it
-    if (h->skip.on && h->cur != cur0) HIPCHK(copy_slots(h->v, h->cur, h->v, cur0, h->d, h->skip.d_mask, h->stream));
+    if (h->skip.on && h->cur != cur0) HIPCHK(copy_slots(h->v, h->cur, h->v, cur0, h->d, h->skip.d_mask.as<unsigned char>(), h->stream));
     if (summ) {
         h->summ.T = T;
         if (h->skip.on) h->summ.skip = h->skip.h_mask;
     }
     rc = finish_elapsed(h, logZ);
     if (rc) return rc;
-    if (logmu_trace) HIPCHK(hipMemcpy(logmu_trace, h->d_tr_logmu, (size_t)T * h->v.ntheta * 8, hipMemcpyDeviceToHost));
-    if (ess_trace) HIPCHK(hipMemcpy(ess_trace, h->d_tr_ess, (size_t)T * h->v.ntheta * 8, hipMemcpyDeviceToHost));
+    if (logmu_trace) HIPCHK(hipMemcpy(logmu_trace, h->d_tr_logmu.as<double>(), (size_t)T * h->v.ntheta * 8, hipMemcpyDeviceToHost));
+    if (ess_trace) HIPCHK(hipMemcpy(ess_trace, h->d_tr_ess.as<double>(), (size_t)T * h->v.ntheta * 8, hipMemcpyDeviceToHost));
     if (h->skip.on && want_trace) {   // filters the call left out have no steps: NaN in their trace columns
         const double nan = std::numeric_limits<double>::quiet_NaN();
         const size_t nt = (size_t)h->v.ntheta;
@@ -153,9 +152,9 @@ extern "C" int smc_time_step_kernel(smc_handle h, const double* y, int64_t T, in
     if ((int64_t)nsample * G > T - 1) nsample = (int)((T - 1) / G);
     std::vector<hipEvent_t> e0((size_t)nsample), e1((size_t)nsample);
     for (int i = 0; i < nsample; ++i) { HIPCHK(hipEventCreate(&e0[i])); HIPCHK(hipEventCreate(&e1[i])); }
-    HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_y.as<double>(), y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
     SeriesScope scope(h->v);
-    h->v.y = h->d_y; h->v.trace_logmu = nullptr; h->v.trace_ess = nullptr;
+    h->v.y = h->d_y.as<double>(); h->v.trace_logmu = nullptr; h->v.trace_ess = nullptr;
     h->cur = 0;
     h->v.want_s2 = 0;   // exactly the launches of log_likelihood without traces (enqueue_log_likelihood)
     HIPCHK(do_init(h, y[0]));

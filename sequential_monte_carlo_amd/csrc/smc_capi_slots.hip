@@ -13,6 +13,11 @@ hipError_t copy_slots(const FilterView& dst, int dcur, const FilterView& src, in
     return hipGetLastError();
 }
 
+int ensure_wdense(smc_handle h) {   // [ntheta][n] dense weights, with room for the moments [2][d][ntheta] (smc_get_moments) from the start
+    HIPCHK(h->d_wdense.grow(((size_t)h->v.ntheta * (size_t)h->v.n + 2 * (size_t)h->d * (size_t)h->v.ntheta) * 8));
+    return SMC_OK;
+}
+
 hipError_t enqueue_dense_weights(smc_filter_s* h, double* w) {
     const FilterView& v = h->v;
     hipLaunchKernelGGL(k_dense_weights, dim3((unsigned)((v.n + 255) / 256), v.ntheta), dim3(256), 0, h->stream, v, h->cur, w);
@@ -37,12 +42,10 @@ extern "C" int smc_get_state(smc_handle h, double* x, double* w, int32_t* anc) {
     if (w) {
         int rc = emit_if_needed(h);
         if (rc) return rc;
-        if (!h->d_wdense) HIPCHK(dalloc(&h->d_wdense, (size_t)v.ntheta * v.n + 2 * (size_t)h->d * v.ntheta));
-        hipLaunchKernelGGL(k_dense_weights, dim3((unsigned)((v.n + 255) / 256), v.ntheta), dim3(256), 0, h->stream, v,
-                           h->cur, h->d_wdense);
-        HIPCHK(hipGetLastError());
+        if ((rc = ensure_wdense(h))) return rc;
+        HIPCHK(enqueue_dense_weights(h, h->d_wdense.as<double>()));
         HIPCHK(hipStreamSynchronize(h->stream));
-        HIPCHK(hipMemcpy(w, h->d_wdense, (size_t)v.ntheta * v.n * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(w, h->d_wdense.as<double>(), (size_t)v.ntheta * v.n * 8, hipMemcpyDeviceToHost));
     }
     return SMC_OK;
 }
@@ -60,10 +63,10 @@ extern "C" int smc_permute(smc_handle h, const int32_t* a) {
     const FilterView& v = h->v;
     // The call returns without waiting for the device (whatever follows on this handle is ordered behind on its stream; the host
     // goes on with the random-walk covariance meanwhile): the indices travel from a pinned copy the handle owns.
-    if (!h->h_perm) HIPCHK(hipHostMalloc((void**)&h->h_perm, (size_t)v.ntheta * 4, hipHostMallocDefault));
+    if (!h->h_perm) HIPCHK(h->h_perm.grow((size_t)v.ntheta * 4));
     else HIPCHK(hipStreamSynchronize(h->stream));   // (a previous permutation's copy out of the same buffer has completed)
-    memcpy(h->h_perm, a, (size_t)v.ntheta * 4);
-    HIPCHK(hipMemcpyAsync(h->d_perm, h->h_perm, (size_t)v.ntheta * 4, hipMemcpyHostToDevice, h->stream));
+    memcpy(h->h_perm.as<int32_t>(), a, (size_t)v.ntheta * 4);
+    HIPCHK(hipMemcpyAsync(h->d_perm, h->h_perm.as<int32_t>(), (size_t)v.ntheta * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_logZ_tmp, v.logZ, (size_t)v.ntheta * 8, hipMemcpyDeviceToDevice, h->stream));
     hipLaunchKernelGGL(k_permute, dim3((unsigned)((v.npad + 255) / 256), v.ntheta), dim3(256), 0, h->stream, v, h->cur, h->d,
                        h->d_perm, h->d_logZ_tmp);

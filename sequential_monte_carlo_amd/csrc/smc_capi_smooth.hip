@@ -20,14 +20,7 @@ int history_refuse(const char* who) {
                                                "without a recordable step; call smc_history_end first");
 }
 
-void history_free(smc_filter_s* h) {
-    (void)hipFree(h->hist.d_x);   // (d_w lives in the same allocation)
-    (void)hipFree(h->hist.d_ws);
-    (void)hipFree(h->hist.d_tmp);
-    (void)hipFree(h->hist.d_pair);
-    (void)hipFree(h->hist.d_path);
-    h->hist = {};
-}
+void history_free(smc_filter_s* h) { h->hist = {}; }   // (a disarmed record: its blocks are freed as they are replaced by empty ones)
 
 static size_t cloud_words(const smc_filter_s* h) { return (size_t)h->v.ntheta * (size_t)h->v.n; }
 
@@ -37,18 +30,14 @@ extern "C" int smc_history_begin(smc_handle h, int64_t T_cap) {
     HIPCHK(hipSetDevice(h->device));
     const size_t nw = cloud_words(h), per_step = nw * ((size_t)h->d + 1);
     if (per_step > ((size_t)1 << 60) / 8 / (size_t)T_cap) return fail(SMC_ENOMEM, "smc_history_begin: a record of that many bytes cannot be allocated");
-    double* slab = nullptr;
-    const hipError_t e = hipMalloc((void**)&slab, per_step * (size_t)T_cap * 8);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();   // (the failed allocation is this call's result, not the next call's)
-        return fail(SMC_ENOMEM, std::string("smc_history_begin: hipMalloc of the record: ") + hipGetErrorString(e));
-    }
-    if (h->hist.d_x) {   // armed before: the new record replaces the old one
-        HIPCHK(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->hist.d_x);
-    }
-    h->hist.d_x = slab;
-    h->hist.d_w = slab + nw * (size_t)h->d * (size_t)T_cap;
+    // the new block first: a failed allocation leaves the handle as it was.  Armed before: the new record replaces the old one,
+    // which the stream may still read
+    const size_t bytes = per_step * (size_t)T_cap * 8;
+    if (h->hist.rec && bytes > h->hist.rec.bytes()) HIPCHK(hipStreamSynchronize(h->stream));
+    const hipError_t e = h->hist.rec.grow_keep(bytes);
+    if (e != hipSuccess) return fail(SMC_ENOMEM, std::string("smc_history_begin: hipMalloc of the record: ") + hipGetErrorString(e));
+    h->hist.d_x = h->hist.rec.as<double>();
+    h->hist.d_w = h->hist.d_x + nw * (size_t)h->d * (size_t)T_cap;
     h->hist.cap = T_cap;
     h->hist.len = 0;
     h->hist.walk_M = 0;
@@ -192,23 +181,13 @@ int smooth_run(smc_handle h, const char* name, double* ws, double* mean, double*
     int rc = fetch_rows(h, h->model, name, "the transition scale", rows);
     if (rc) return rc;
     const SmoothPlan p = plan_of(h, T);
-    if (p.bytes > h->hist.tmp_bytes) {   // (the old block first, unlike the walk's: DESIGN.md "History on a handle")
-        (void)hipFree(h->hist.d_tmp);
-        h->hist.d_tmp = nullptr; h->hist.tmp_bytes = 0;
-        if (hipMalloc((void**)&h->hist.d_tmp, p.bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SMC_ENOMEM, who + "hipMalloc of the scratch of the backward pass");
-        }
-        h->hist.tmp_bytes = p.bytes;
-    }
+    // (the smoother's blocks: the old block first, unlike the walk's - DESIGN.md "Memory of a handle")
+    if (h->hist.d_tmp.grow(p.bytes) != hipSuccess) return fail(SMC_ENOMEM, who + "hipMalloc of the scratch of the backward pass");
     const size_t mom_words = 2 * d * nt;
     if (T > h->hist.ws_cap) {
-        (void)hipFree(h->hist.d_ws);
-        h->hist.d_ws = nullptr; h->hist.ws_cap = 0;
-        if (hipMalloc((void**)&h->hist.d_ws, (size_t)h->hist.cap * (nw + mom_words) * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SMC_ENOMEM, who + "hipMalloc of the smoothed weights");
-        }
+        h->hist.d_ws.reset();
+        h->hist.ws_cap = 0;
+        if (h->hist.d_ws.grow((size_t)h->hist.cap * (nw + mom_words) * 8) != hipSuccess) return fail(SMC_ENOMEM, who + "hipMalloc of the smoothed weights");
         h->hist.ws_cap = h->hist.cap;
     }
     // the pair moments: partials [1 + 2 d][nchunk][ntheta][n] | cross [cap - 1][d][d][ntheta] | resid2 [cap - 1][d][ntheta]
@@ -218,22 +197,15 @@ int smooth_run(smc_handle h, const char* name, double* ws, double* mean, double*
         OffsetPlan o;
         const size_t steps = (size_t)h->hist.cap - 1;
         const size_t o_part = o.take((1 + 2 * d) * (size_t)p.nchunk * nw * 8), o_cross = o.take(steps * cross_words * 8), o_resid = o.take(steps * resid_words * 8);
-        if (o.bytes > h->hist.pair_bytes) {
-            (void)hipFree(h->hist.d_pair);
-            h->hist.d_pair = nullptr; h->hist.pair_bytes = 0;
-            if (hipMalloc((void**)&h->hist.d_pair, o.bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(SMC_ENOMEM, who + "hipMalloc of the chunk partials of the pair moments");
-            }
-            h->hist.pair_bytes = o.bytes;
-        }
-        d_pair = (double*)(h->hist.d_pair + o_part); d_cross = (double*)(h->hist.d_pair + o_cross); d_resid = (double*)(h->hist.d_pair + o_resid);
+        if (h->hist.d_pair.grow(o.bytes) != hipSuccess) return fail(SMC_ENOMEM, who + "hipMalloc of the chunk partials of the pair moments");
+        char* pair = h->hist.d_pair.as<char>();
+        d_pair = (double*)(pair + o_part); d_cross = (double*)(pair + o_cross); d_resid = (double*)(pair + o_resid);
     }
-    char* tmp = (char*)h->hist.d_tmp;
+    char* tmp = h->hist.d_tmp.as<char>();
     double *pmax = (double*)(tmp + p.o_pmax), *part = (double*)(tmp + p.o_part), *logD = (double*)(tmp + p.o_logD), *rowmax = (double*)(tmp + p.o_rmax), *momtmp = (double*)(tmp + p.o_mom);
     SmoothRow* d_rows = (SmoothRow*)(tmp + p.o_rows);
     int* dead = (int*)(tmp + p.o_dead);
-    double *d_ws = h->hist.d_ws, *d_mom = h->hist.d_ws + (size_t)h->hist.ws_cap * nw;
+    double *d_ws = h->hist.d_ws.as<double>(), *d_mom = d_ws + (size_t)h->hist.ws_cap * nw;
     hipStream_t s = h->stream;
     HIPCHK(hipEventRecord(h->ev0, s));
     HIPCHK(hipMemcpyAsync(d_rows, rows.data(), nt * sizeof(SmoothRow), hipMemcpyHostToDevice, s));
@@ -354,17 +326,9 @@ int backward_walk(smc_handle h, Walk& k, int64_t M, uint64_t path_seed, const in
     k.o_counts = p.take(nt * sizeof(int32_t));
     k.o_idx = p.take((size_t)T * pw * 4);
     tail(p, (size_t)T, pw);
-    if (p.bytes > h->hist.path_bytes) {   // (the new block first: a failed allocation leaves the handle as it was)
-        char* blk = nullptr;
-        if (hipMalloc((void**)&blk, p.bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SMC_ENOMEM, who + "hipMalloc of the paths and the scratch of the backward walk");
-        }
-        (void)hipFree(h->hist.d_path);
-        h->hist.d_path = blk;
-        h->hist.path_bytes = p.bytes;
-    }
-    char* base = h->hist.d_path;
+    // (the new block first: a failed allocation leaves the handle as it was)
+    if (h->hist.d_path.grow_keep(p.bytes) != hipSuccess) return fail(SMC_ENOMEM, who + "hipMalloc of the paths and the scratch of the backward walk");
+    char* base = h->hist.d_path.as<char>();
     double *cur = (double*)(base + o_cur), *pmax = (double*)(base + o_pmax), *rowmax = (double*)(base + o_rmax);
     uint64_t* psum = (uint64_t*)(base + o_psum);
     SmoothRow* d_rows = (SmoothRow*)(base + o_rows);
@@ -415,7 +379,7 @@ extern "C" int smc_sample_paths(smc_handle h, int64_t M, uint64_t path_seed, con
     h->hist.walk_M = 0;   // (a walk that fails leaves nothing to gather through)
     if (rc || (rc = finish_elapsed(h))) return rc;
     h->hist.walk_M = M; h->hist.walk_T = (int64_t)T; h->hist.walk_idx = k.o_idx;   // smc_reference_from_paths
-    const char* base = h->hist.d_path;
+    const char* base = h->hist.d_path.as<char>();
     if (idx) HIPCHK(hipMemcpy(idx, base + k.o_idx, T * pw * 4, hipMemcpyDeviceToHost));
     if (xs) HIPCHK(hipMemcpy(xs, base + k.o_xs, T * d * pw * 8, hipMemcpyDeviceToHost));
     return SMC_OK;
@@ -450,7 +414,7 @@ extern "C" int smc_rb_sample_paths(smc_handle h, const double* y, int64_t T, int
         o_out = p.take((size_t)T * nt * 8 * 8);
     });
     if (rc) return rc;
-    char* base = h->hist.d_path;
+    char* base = h->hist.d_path.as<char>();
     const double* d_y = (const double*)(base + k.o_y);
     const int32_t *d_counts = (const int32_t*)(base + k.o_counts), *d_idx = (const int32_t*)(base + k.o_idx);
     double *d_vol = (double*)(base + k.o_xs), *d_tmean = (double*)(base + o_tmean), *d_tvar = (double*)(base + o_tvar);

@@ -16,13 +16,12 @@ bool summaries_fit_lds(const smc_filter_s* h) {
     return (size_t)lds_padded_len(h->v.seg) * 8 * (size_t)(1 + h->d) + scr_words(1024, 4) * 8 + summary_lds_words(h->summ.np, h->d) * 8 <= (size_t)160 * 1024;
 }
 int ensure_summaries(smc_handle h, int64_t T) {
-    if (T > h->summ.cap) {
+    if (T > h->summ.cap) {   // (the two traces grow together: old blocks first)
         HIPCHK(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->summ.d_q); (void)hipFree(h->summ.d_m);
-        h->summ.d_q = h->summ.d_m = nullptr;
+        h->summ.d_q.reset(); h->summ.d_m.reset();
         h->summ.cap = 0;
-        HIPCHK(dalloc(&h->summ.d_q, (size_t)T * h->v.ntheta * QMAX));
-        HIPCHK(dalloc(&h->summ.d_m, (size_t)T * 2 * h->d * h->v.ntheta));
+        HIPCHK(h->summ.d_q.grow((size_t)T * h->v.ntheta * QMAX * 8));
+        HIPCHK(h->summ.d_m.grow((size_t)T * 2 * h->d * h->v.ntheta * 8));
         h->summ.cap = T;
     }
     return SMC_OK;
@@ -32,7 +31,7 @@ void view_summaries(smc_handle h) {
     FilterView& v = h->v;
     v.sum_np = h->summ.np; v.sum_comp = h->summ.comp; v.sum_mom = h->summ.mom;
     for (int j = 0; j < QMAX; ++j) v.sum_p64[j] = h->summ.mode == SMC_SUMM_UNWEIGHTED ? d2bits(h->summ.p[j]) : h->summ.p64[j];
-    v.sum_q = h->summ.d_q; v.sum_m = h->summ.d_m;
+    v.sum_q = h->summ.d_q.as<double>(); v.sum_m = h->summ.d_m.as<double>();
 }
 // the levels of a request in the form the kernels of the handle's mode read (FilterView::sum_p64)
 static void level_words(const smc_filter_s* h, const double* p, int np, uint64_t* out) {
@@ -44,8 +43,8 @@ static void level_words(const smc_filter_s* h, const double* p, int np, uint64_t
 static int ensure_ms(smc_handle h) {
     const size_t nth = (size_t)h->v.ntheta, words = ms_words(nth, (size_t)h->v.nseg, (size_t)h->d);
     if (!h->summ.d_ms) {
-        HIPCHK(hipMalloc((void**)&h->summ.d_ms, (words + nth * QMAX) * 8));
-        HIPCHK(hipMemsetAsync(h->summ.d_ms, 0, (words + nth * QMAX) * 8, h->stream));
+        HIPCHK(h->summ.d_ms.grow((words + nth * QMAX) * 8));
+        HIPCHK(hipMemsetAsync(h->summ.d_ms.as<uint64_t>(), 0, (words + nth * QMAX) * 8, h->stream));
     }
     return SMC_OK;
 }
@@ -101,7 +100,7 @@ static int enqueue_ms_t(smc_handle h, int component, int np, const uint64_t* p64
     const size_t nth = (size_t)h->v.ntheta;
     int rc = ensure_ms(h);
     if (rc) return rc;
-    const MsScratch ms = ms_carve(h->summ.d_ms, nth, (size_t)h->v.nseg, (size_t)h->d);
+    const MsScratch ms = ms_carve(h->summ.d_ms.as<uint64_t>(), nth, (size_t)h->v.nseg, (size_t)h->d);
     return enqueue_ms_view<UNW>(h, summary_view(h, component, np, p64, mom), h->d, ms, q_out, mean, var);
 }
 // The WEIGHTED summaries (whatever the handle's summary mode) of another cloud under the handle's current weights: `rows` <= MAX_DIM
@@ -128,10 +127,10 @@ static int enqueue_ms(smc_handle h, int component, int np, const uint64_t* p64, 
 // ... into row `row` of the traces of a multi-step call
 int enqueue_step_summaries(smc_handle h, int64_t row) {
     const size_t nth = (size_t)h->v.ntheta, nout = (size_t)h->d * nth;
-    double* mbase = h->summ.d_m + (size_t)row * 2 * nout;
+    double* mbase = h->summ.d_m.as<double>() + (size_t)row * 2 * nout;
     uint64_t pw[QMAX];
     level_words(h, h->summ.p, h->summ.np, pw);
-    return enqueue_ms(h, h->summ.comp, h->summ.np, pw, h->summ.mom != 0, h->summ.d_q + (size_t)row * nth * h->summ.np, mbase, mbase + nout);
+    return enqueue_ms(h, h->summ.comp, h->summ.np, pw, h->summ.mom != 0, h->summ.d_q.as<double>() + (size_t)row * nth * h->summ.np, mbase, mbase + nout);
 }
 
 extern "C" int smc_set_summaries(smc_handle h, int component, const double* p, int np, int moments) {
@@ -160,9 +159,9 @@ extern "C" int smc_get_summaries(smc_handle h, int64_t T, double* q, double* mea
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     const size_t nth = (size_t)h->v.ntheta, nout = (size_t)h->d * nth;
-    if (q) HIPCHK(hipMemcpy(q, h->summ.d_q, (size_t)T * nth * h->summ.np * 8, hipMemcpyDeviceToHost));
-    if (mean) HIPCHK(hipMemcpy2D(mean, nout * 8, h->summ.d_m, 2 * nout * 8, nout * 8, (size_t)T, hipMemcpyDeviceToHost));
-    if (var) HIPCHK(hipMemcpy2D(var, nout * 8, h->summ.d_m + nout, 2 * nout * 8, nout * 8, (size_t)T, hipMemcpyDeviceToHost));
+    if (q) HIPCHK(hipMemcpy(q, h->summ.d_q.as<double>(), (size_t)T * nth * h->summ.np * 8, hipMemcpyDeviceToHost));
+    if (mean) HIPCHK(hipMemcpy2D(mean, nout * 8, h->summ.d_m.as<double>(), 2 * nout * 8, nout * 8, (size_t)T, hipMemcpyDeviceToHost));
+    if (var) HIPCHK(hipMemcpy2D(var, nout * 8, h->summ.d_m.as<double>() + nout, 2 * nout * 8, nout * 8, (size_t)T, hipMemcpyDeviceToHost));
     if (!h->summ.skip.empty()) {   // filters the call left out have no summaries: NaN (the device rows hold whatever was there)
         const double nan = std::numeric_limits<double>::quiet_NaN();
         for (size_t m = 0; m < nth; ++m) {
@@ -186,18 +185,19 @@ static int summaries_once(smc_handle h, int component, const double* p, int np, 
     done = false;
     if (h->v.nseg != 1) return SMC_OK;
     const size_t nth = (size_t)h->v.ntheta, nout = (size_t)h->d * nth;
-    if (!h->summ.h_once) HIPCHK(hipHostMalloc((void**)&h->summ.h_once, ((size_t)QMAX * nth + 2 * nout) * 8, hipHostMallocDefault));
+    HIPCHK(h->summ.h_once.grow(((size_t)QMAX * nth + 2 * nout) * 8));
+    double* once = h->summ.h_once.as<double>();
     FilterView v = h->v;
     v.sum_np = np; v.sum_comp = component; v.sum_mom = mom ? 1 : 0;
     level_words(h, p, np, v.sum_p64);
-    v.sum_q = h->summ.h_once; v.sum_m = h->summ.h_once + (size_t)QMAX * nth;
+    v.sum_q = once; v.sum_m = once + (size_t)QMAX * nth;
     const hipError_t e = by_variant<ENTRY_SUMM_ONCE>(h->model, VARIANT_PLAIN, [&](auto L) { return L.summ_once(v, h->cur, h->stream); });
     if (e == hipErrorInvalidValue) return SMC_OK;
     HIPCHK(e);
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (q_out) memcpy(q_out, h->summ.h_once, nth * np * 8);
-    if (mean) memcpy(mean, h->summ.h_once + (size_t)QMAX * nth, nout * 8);
-    if (var) memcpy(var, h->summ.h_once + (size_t)QMAX * nth + nout, nout * 8);
+    if (q_out) memcpy(q_out, once, nth * np * 8);
+    if (mean) memcpy(mean, once + (size_t)QMAX * nth, nout * 8);
+    if (var) memcpy(var, once + (size_t)QMAX * nth + nout, nout * 8);
     done = true;
     return SMC_OK;
 }
@@ -211,8 +211,8 @@ extern "C" int smc_get_moments(smc_handle h, double* mean, double* var) {
     bool done = false;
     if ((rc = summaries_once(h, 0, nullptr, 0, true, nullptr, mean, var, done)) || done) return rc;
     const size_t nout = (size_t)h->d * h->v.ntheta;
-    if (!h->d_wdense) HIPCHK(dalloc(&h->d_wdense, (size_t)h->v.ntheta * h->v.n + 2 * nout));
-    double *d_mean = h->d_wdense, *d_var = h->d_wdense + nout;
+    if ((rc = ensure_wdense(h))) return rc;
+    double *d_mean = h->d_wdense.as<double>(), *d_var = d_mean + nout;
     if ((rc = enqueue_ms(h, 0, 0, nullptr, true, nullptr, d_mean, d_var))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(mean, d_mean, nout * 8, hipMemcpyDeviceToHost));
@@ -234,7 +234,7 @@ extern "C" int smc_get_quantiles(smc_handle h, int component, const double* p, i
     uint64_t hp[QMAX];
     level_words(h, p, np, hp);
     if ((rc = ensure_ms(h))) return rc;
-    double* d_out = (double*)(h->summ.d_ms + ms_words(nth, (size_t)h->v.nseg, (size_t)h->d));
+    double* d_out = (double*)(h->summ.d_ms.as<uint64_t>() + ms_words(nth, (size_t)h->v.nseg, (size_t)h->d));
     if ((rc = enqueue_ms(h, component, np, hp, false, d_out, nullptr, nullptr))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out, d_out, nst * 8, hipMemcpyDeviceToHost));

@@ -64,12 +64,8 @@ struct smc_comm_s {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1, device = 0;
     hipStream_t stream = nullptr;
-    double* d_send = nullptr;   // device staging of the all-gathers
-    double* d_recv = nullptr;
-    size_t cap = 0;             // doubles per rank the staging holds
-    void* d_xs = nullptr;       // packed filter slots going out / coming in (exchange_slots)
-    void* d_xr = nullptr;
-    size_t xcap = 0;            // bytes
+    DevBlock d_send, d_recv;    // device staging of the all-gathers: double [n] | [world][n] (grown together, old blocks first)
+    DevBlock d_xs, d_xr;        // packed filter slots going out / coming in (exchange_slots; likewise)
 };
 
 #define NCCLC(expr)                                                                                  \
@@ -118,9 +114,8 @@ extern "C" int smc_comm_destroy(smc_comm c) {
     if (!c) return SMC_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    (void)hipFree(c->d_send); (void)hipFree(c->d_recv); (void)hipFree(c->d_xs); (void)hipFree(c->d_xr);
     if (c->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(c->comm);
-    delete c;
+    delete c;   // (the staging blocks go with it, on the device selected above)
     return SMC_OK;
 }
 
@@ -132,13 +127,11 @@ extern "C" int smc_comm_rank(smc_comm c, int* rank, int* world) {
 }
 
 static int ensure_staging(smc_comm c, size_t n) {
-    if (n <= c->cap) return SMC_OK;
+    if (n * 8 <= c->d_send.bytes() && n * 8 * (size_t)c->world <= c->d_recv.bytes()) return SMC_OK;
     HIPCHK(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_send); (void)hipFree(c->d_recv);
-    c->d_send = c->d_recv = nullptr; c->cap = 0;
-    HIPCHK(hipMalloc((void**)&c->d_send, n * 8));
-    HIPCHK(hipMalloc((void**)&c->d_recv, n * 8 * (size_t)c->world));
-    c->cap = n;
+    c->d_send.reset(); c->d_recv.reset();
+    HIPCHK(c->d_send.grow(n * 8));
+    HIPCHK(c->d_recv.grow(n * 8 * (size_t)c->world));
     return SMC_OK;
 }
 
@@ -148,9 +141,9 @@ extern "C" int smc_comm_all_gather(smc_comm c, const double* local, int64_t n, d
     HIPCHK(hipSetDevice(c->device));
     int rc = ensure_staging(c, (size_t)n);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(c->d_send, local, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    NCCLC(g_rccl.AllGather(c->d_send, c->d_recv, (size_t)n, ncclFloat64, c->comm, c->stream));
-    HIPCHK(hipMemcpyAsync(all, c->d_recv, (size_t)n * 8 * (size_t)c->world, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_send.as<double>(), local, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    NCCLC(g_rccl.AllGather(c->d_send.as<double>(), c->d_recv.as<double>(), (size_t)n, ncclFloat64, c->comm, c->stream));
+    HIPCHK(hipMemcpyAsync(all, c->d_recv.as<double>(), (size_t)n * 8 * (size_t)c->world, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return SMC_OK;
 }
@@ -226,15 +219,13 @@ extern "C" int smc_comm_exchange_slots(smc_comm c, smc_handle h, const int32_t* 
     send_idx.resize((size_t)n_send);
     const size_t ns = send_idx.size(), nr = dest_idx.size();   // nr == per
     const size_t need = (ns > nr ? ns : nr) * (size_t)sb;
-    if (need > c->xcap) {
+    if (need > c->d_xs.bytes() || need > c->d_xr.bytes()) {
         HIPCHK(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_xs); (void)hipFree(c->d_xr);
-        c->d_xs = c->d_xr = nullptr; c->xcap = 0;
-        HIPCHK(hipMalloc(&c->d_xs, need));
-        HIPCHK(hipMalloc(&c->d_xr, need));
-        c->xcap = need;
+        c->d_xs.reset(); c->d_xr.reset();
+        HIPCHK(c->d_xs.grow(need));
+        HIPCHK(c->d_xr.grow(need));
     }
-    if (ns && (rc = smc_pack_slots(h, send_idx.data(), (int64_t)ns, c->d_xs))) return rc;   // synchronises the handle's stream
+    if (ns && (rc = smc_pack_slots(h, send_idx.data(), (int64_t)ns, c->d_xs.as<void>()))) return rc;   // synchronises the handle's stream
     // every Send / Recv sits between GroupStart and GroupEnd, and GroupEnd runs whatever happened in between: a group left open on
     // this thread would swallow every later collective of the communicator (and the peers would wait for ever).  The first error
     // is reported after the group has been closed; the filter slots of `h` are then undefined (some may have been received).
@@ -244,8 +235,8 @@ extern "C" int smc_comm_exchange_slots(smc_comm c, smc_handle h, const int32_t* 
         size_t so = 0, ro = 0;
         for (int r = 0; r < W; ++r) {
             const size_t nsb = (size_t)send_cnt[(size_t)r] * (size_t)sb, nrb = (size_t)recv_cnt[(size_t)r] * (size_t)sb;
-            if (nsb && first == ncclSuccess) { first = g_rccl.Send((const char*)c->d_xs + so, nsb, ncclUint8, r, c->comm, c->stream); where = "ncclSend"; }
-            if (nrb && first == ncclSuccess) { first = g_rccl.Recv((char*)c->d_xr + ro, nrb, ncclUint8, r, c->comm, c->stream); where = "ncclRecv"; }
+            if (nsb && first == ncclSuccess) { first = g_rccl.Send(c->d_xs.as<const char>() + so, nsb, ncclUint8, r, c->comm, c->stream); where = "ncclSend"; }
+            if (nrb && first == ncclSuccess) { first = g_rccl.Recv(c->d_xr.as<char>() + ro, nrb, ncclUint8, r, c->comm, c->stream); where = "ncclRecv"; }
             so += nsb; ro += nrb;
         }
         const ncclResult_t end = g_rccl.GroupEnd();
@@ -257,6 +248,6 @@ extern "C" int smc_comm_exchange_slots(smc_comm c, smc_handle h, const int32_t* 
                                   " (the filter slots of the handle are undefined now)");
     }
     HIPCHK(hipStreamSynchronize(c->stream));     // the unpack kernel runs on the handle's own stream
-    if (nr && (rc = smc_unpack_slots(h, dest_idx.data(), (int64_t)nr, c->d_xr))) return rc;
+    if (nr && (rc = smc_unpack_slots(h, dest_idx.data(), (int64_t)nr, c->d_xr.as<void>()))) return rc;
     return SMC_OK;
 }

@@ -7,6 +7,7 @@
 #include "../../include/smc_hip.h"
 #include "smc_launch.h"
 
+#include <atomic>
 #include <string>
 #include <vector>
 
@@ -23,10 +24,62 @@ int fail(int code, const std::string& msg);
                                       std::to_string(__LINE__) + ")");                                        \
     } while (0)
 
-template <class T>
-inline hipError_t dalloc(T** p, size_t count) {
-    return hipMalloc((void**)p, count * sizeof(T) > 0 ? count * sizeof(T) : 16);
-}
+// ---- memory ----------------------------------------------------------------------------------------
+// Every device and pinned allocation of the library is a Block: it owns one pointer and its size in bytes, moves (the source is
+// left empty), does not copy, and frees in its destructor.  The only calls of hipMalloc / hipHostMalloc / hipFree / hipHostFree
+// outside the per-thread scratch of smc_util.hip and the SMC_ABLATE stamps.  A block never synchronises and never selects a
+// device: whoever replaces a block the stream may still read waits for the stream first, and whoever lets a handle go selects
+// its device first.  Two ways to grow, both no-ops (no runtime call) when the block already holds `need` bytes, both returning
+// HIP's error with the sticky error cleared; 0 bytes are allocated as 16.  Kernels only ever see views: plain pointers into blocks.
+inline std::atomic<int64_t> g_live_bytes[2];   // [0] device, [1] pinned: allocated and not yet freed (smc_live_bytes)
+template <bool PINNED>
+class Block {
+    void* p_ = nullptr;
+    size_t bytes_ = 0;
+    hipError_t adopt_new(size_t need) {   // a fresh allocation in place of whatever the block holds; on failure the block is untouched
+        void* q = nullptr;
+        need = need ? need : 16;
+        const hipError_t e = PINNED ? hipHostMalloc(&q, need, hipHostMallocDefault) : hipMalloc(&q, need);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();   // (the failed allocation is this call's result, not the next call's)
+            return e;
+        }
+        reset();
+        p_ = q; bytes_ = need;
+        g_live_bytes[PINNED].fetch_add((int64_t)need, std::memory_order_relaxed);
+        return hipSuccess;
+    }
+
+public:
+    Block() = default;
+    Block(Block&& o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr; o.bytes_ = 0; }
+    Block& operator=(Block&& o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; bytes_ = o.bytes_; o.p_ = nullptr; o.bytes_ = 0; }
+        return *this;
+    }
+    Block(const Block&) = delete;
+    Block& operator=(const Block&) = delete;
+    ~Block() { reset(); }
+    void reset() {
+        if (!p_) return;
+        (void)(PINNED ? hipHostFree(p_) : hipFree(p_));
+        g_live_bytes[PINNED].fetch_sub((int64_t)bytes_, std::memory_order_relaxed);
+        p_ = nullptr; bytes_ = 0;
+    }
+    // old block first: the old allocation is freed before the new one is made (the peak is one block); on failure the block is empty
+    hipError_t grow(size_t need) {
+        if (p_ && bytes_ >= need) return hipSuccess;
+        reset();
+        return adopt_new(need);
+    }
+    // new block first: the old allocation is freed only once the new one exists; on failure the block is as it was
+    hipError_t grow_keep(size_t need) { return p_ && bytes_ >= need ? hipSuccess : adopt_new(need); }
+    size_t bytes() const { return bytes_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    template <class T> T* as() const { return (T*)p_; }
+};
+using DevBlock = Block<false>;   // hipMalloc / hipFree
+using PinBlock = Block<true>;    // hipHostMalloc(hipHostMallocDefault) / hipHostFree: coherent, device-visible
 
 // the offsets of the arrays that share ONE allocation: take(n) is where the next n bytes start (256-byte aligned), bytes the total
 struct OffsetPlan {
@@ -56,27 +109,25 @@ struct smc_filter_s {
     int model = 0, d = 0, device = 0;
     uint32_t flags = 0;
     smc::FilterView v{};
-    smc::Params* d_params = nullptr;
+    // Memory (DESIGN.md "Memory of a handle"): every allocation is a block, freed when the handle is deleted; plain pointers are views
+    DevBlock d_slab;                           // ONE allocation behind x, C, the segment records, the per-filter scalars, params / streams / perm
+    smc::Params* d_params = nullptr;           //   views into the slab
     uint32_t* d_stream = nullptr;
     int32_t* d_perm = nullptr;
     double* d_logZ_tmp = nullptr;
-    double* d_y = nullptr;
-    int64_t ycap = 0;
-    double *d_tr_logmu = nullptr, *d_tr_ess = nullptr;
-    int64_t trcap = 0;
-    double* d_wdense = nullptr;
-    smc::StepRec* d_recs = nullptr;
-    int64_t reccap = 0;
-    double* h_pin = nullptr;                   // pinned host mirror [4][ntheta]: logZ | last_logmu | last_ess | ticket of the step API
+    DevBlock d_y;                              // double [T]: the series of the whole-series calls and the windows (ensure_y)
+    DevBlock d_tr_logmu, d_tr_ess;             // double [T][ntheta] each: the traces of smc_log_likelihood
+    DevBlock d_wdense;                         // double [ntheta][n] dense weights | [2][d][ntheta] moments (ensure_wdense)
+    DevBlock d_recs;                           // smc::StepRec [T][ntheta]: the per-step records of the resident kernels (ensure_recs)
+    PinBlock h_pin;                            // pinned host mirror double [4][ntheta]: logZ | last_logmu | last_ess | ticket of the step API
     uint32_t seq = 0;                          // last ticket handed to a step-API launch
-    size_t slab_bytes = 0, pin_bytes = 0;
-    char* d_slab = nullptr;                    // ONE allocation behind x, C, the segment records, the per-filter scalars, params / streams / perm
-    uint64_t* d_brk = nullptr;                 // break points of the steps [v.brk_t0, v.brk_t0 + brk_count)
+    DevBlock d_brk;                            // uint64_t: break points of the steps [v.brk_t0, v.brk_t0 + brk_count)
     uint32_t brk_cap = 0, brk_count = 0;
-    int32_t* h_perm = nullptr;                 // pinned copy of smc_permute's index vector (the call does not wait for the device)
+    PinBlock h_perm;                           // pinned copy of smc_permute's index vector (the call does not wait for the device)
     std::vector<double> prop_par;              // smc_set_proposal(AFFINE): the rows [ntheta][SMC_PROP_NPAR] as given (v.prop_kind: the kind)
-    smc::PropRow *d_prop = nullptr, *h_prop = nullptr;   //   the proposal rows of a guided handle (v.prop) and their pinned twin; bootstrap: none
-    smc::Params* h_params = nullptr;           // pinned twin of d_params (smc_set_params does not wait either)
+    DevBlock d_prop;                           // smc::PropRow [ntheta]: the proposal rows of a guided handle (v.prop) ...
+    PinBlock h_prop;                           //   ... and their pinned twin; bootstrap: none
+    PinBlock h_params;                         // smc::Params [ntheta]: pinned twin of d_params (smc_set_params does not wait either)
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int cur = 0;
@@ -97,8 +148,8 @@ struct smc_filter_s {
     } hot;
 
     struct {   // smc_set_skip: filters log_likelihood leaves out
-        unsigned char* d_mask = nullptr;
-        int32_t* d_order = nullptr;            // the order the one-workgroup-per-filter kernel takes them in: [ntheta] | n_active
+        DevBlock d_mask;                       // unsigned char [ntheta]
+        DevBlock d_order;                      // int32_t: the order the one-workgroup-per-filter kernel takes them in: [ntheta] | n_active
         bool on = false;
         std::vector<uint8_t> h_mask;           // host copy of the mask: the skipped filters' trace columns and summary rows are set to NaN on the host
     } skip;
@@ -107,48 +158,48 @@ struct smc_filter_s {
         uint64_t p64[smc::QMAX] = {};
         double p[smc::QMAX] = {};              // the same levels as doubles in [0, 1]: what the unweighted mode reads
         int mode = SMC_SUMM_WEIGHTED;          // smc_set_summary_mode (v.sum_unw mirrors it)
-        double *d_q = nullptr, *d_m = nullptr; // [T][ntheta][np] | [T][2][d][ntheta]
+        DevBlock d_q, d_m;                     // double [T][ntheta][QMAX] | [T][2][d][ntheta]
         int64_t cap = 0, T = 0;                // steps the traces hold / steps the last call recorded
         std::vector<uint8_t> skip;             // the skip mask of the call whose summaries smc_get_summaries hands over (empty: none)
-        uint64_t* d_ms = nullptr;              // scratch of the summaries of multi-segment filters (smc_summ_kernels.h) + [ntheta][QMAX] results
-        double* h_once = nullptr;              // pinned [QMAX + 2 d][ntheta]: quantiles / moments of the current state (k_summ_once)
+        DevBlock d_ms;                         // uint64_t: scratch of the summaries of multi-segment filters (smc_summ_kernels.h) + [ntheta][QMAX] results
+        PinBlock h_once;                       // double [QMAX + 2 d][ntheta]: quantiles / moments of the current state (k_summ_once)
     } summ;
     struct {   // smc_step_window / smc_step_commit
-        double* h_out = nullptr;               // pinned [2][WIN_MAX][ntheta]: (logmu, ess) of the steps of a window
+        PinBlock h_out;                        // double [2][WIN_MAX][ntheta]: (logmu, ess) of the steps of a window
         int k = 0;                             // steps of the pending window, 0 = none
         bool gap = false;                      // SMC_FLAG_NAN_MISSING: the pending window's observations hold a NaN (the MISS window kernel)
     } win;
     struct {   // the record of a step-by-step run and the smoother over it (smc_capi_smooth.hip); a fresh handle is disarmed
         bool armed = false;
         int64_t cap = 0, len = 0;              // steps the slabs hold / steps recorded so far
-        double *d_x = nullptr, *d_w = nullptr; // [cap][d][ntheta][n] | [cap][ntheta][n]
-        double* d_ws = nullptr;                // the smoother's results: ws [len][ntheta][n] | mean, var [len][2][d][ntheta]
-        double* d_tmp = nullptr;               // its scratch: chunk maxima and chunk partials [2][nchunk][ntheta][n] | logD [ntheta][n] |
-        int64_t ws_cap = 0;                    //   partials of the moments [len][ntheta][nchunk] | rows [ntheta] | dead [ntheta]
-        size_t tmp_bytes = 0;
-        char* d_pair = nullptr;                // the pair moments (smc_smooth_pairs), a block of their own: chunk partials [1 + 2 d][nchunk][ntheta][n] |
-        size_t pair_bytes = 0;                 //   cross [cap - 1][d][d][ntheta] | resid2 [cap - 1][d][ntheta]; nullptr until the first such call
-        char* d_path = nullptr;               // the backward walk (smc_sample_paths, or smc_rb_sample_paths on a MODEL_UCSV_RB handle), its own
-        size_t path_bytes = 0;                 //   block: cur | pmax | psum | rmax | rows | dead | counts | idx [T][ntheta][M] | the caller's tail
+        DevBlock rec;                          // the record, ONE allocation (new block first): d_x | d_w
+        double *d_x = nullptr, *d_w = nullptr; //   its views [cap][d][ntheta][n] | [cap][ntheta][n]
+        DevBlock d_ws;                         // the smoother's results (old block first): ws [ws_cap][ntheta][n] | mean, var [len][2][d][ntheta]
+        int64_t ws_cap = 0;                    //   steps d_ws was laid out for
+        DevBlock d_tmp;                        // its scratch (old block first): chunk maxima and chunk partials [2][nchunk][ntheta][n] | logD [ntheta][n] |
+                                               //   partials of the moments [len][ntheta][nchunk] | rows [ntheta] | dead [ntheta]
+        DevBlock d_pair;                       // the pair moments (smc_smooth_pairs), a block of their own (old block first): chunk partials
+                                               //   [1 + 2 d][nchunk][ntheta][n] | cross [cap - 1][d][d][ntheta] | resid2 [cap - 1][d][ntheta]; empty until the first such call
+        DevBlock d_path;                       // the backward walk (smc_sample_paths, or smc_rb_sample_paths on a MODEL_UCSV_RB handle), its own block
+                                               //   (new block first): cur | pmax | psum | rmax | rows | dead | counts | idx [T][ntheta][M] | the caller's tail
         int64_t walk_M = 0, walk_T = 0;        // the last smc_sample_paths walk over this record (0: none): paths per filter, steps, and where
         size_t walk_idx = 0;                   //   its index block starts in d_path (smc_reference_from_paths gathers through it)
     } hist;
     struct {   // the conditional particle filter (SMC_FLAG_CONDITIONAL; smc_capi_cond.hip): the reference, an allocation of its own
-        double* d_xref = nullptr;              // [T][d][ntheta]; nullptr: none yet (a recycled bundle never carries one)
+        DevBlock d_xref;                       // double [T][d][ntheta] (new block first); empty: none yet (a recycled bundle never carries one)
         int64_t T = 0;
     } cond;
-    struct {   // forecasts (smc_capi_forecast.hip): ONE block, grown on demand and freed by smc_destroy
-        char* d_buf = nullptr;                 // clouds [block][d + 3][ntheta][npad] | summary scratch | results of every horizon
-        size_t bytes = 0;
+    struct {   // forecasts (smc_capi_forecast.hip): ONE block, grown on demand (old block first)
+        DevBlock d_buf;                        // clouds [block][d + 3][ntheta][npad] | summary scratch | results of every horizon
     } fc;
     struct {   // PMMH rejuvenation (smc_capi_pmmh.hip): this handle holds the proposal filters
         smc::PmmhSpec spec{};
         bool cfg = false;
-        smc::PmmhDev dev{};
-        double* h_out = nullptr;               // pinned mirror: theta [ntheta][d] | logZ [ntheta] | any [ntheta] | nrun
-        double* d_in = nullptr;                // ONE device block: dev.theta | dev.logZ | dev.chol | dev.nrun | dev.counts | dev.any -
-        double* h_in = nullptr;                //   a rejuvenation call fills its pinned twin and uploads it in one copy
-        size_t in_words = 0;
+        smc::PmmhDev dev{};                    // views into the blocks below, as the kernels take them
+        PinBlock h_out;                        // pinned mirror double: theta [ntheta][d] | logZ [ntheta] | any [ntheta] | nrun
+        DevBlock d_in;                         // ONE device block: dev.theta | dev.logZ | dev.chol | dev.nrun | dev.counts | dev.any -
+        PinBlock h_in;                         //   a rejuvenation call fills its pinned twin (the same bytes) and uploads it in one copy
+        DevBlock d_prop, d_lp, d_skip, d_mask, d_order;   // dev.prop, dev.lp, dev.skip, dev.mask, dev.order
     } pm;
 };
 
@@ -228,10 +279,12 @@ int enqueue_cloud_summaries(smc_handle h, const double* cloud, int rows, uint64_
                             bool mom, double* q_out, double* mean, double* var);
 // smc_capi_slots.hip: the dense weights of the current state into w [ntheta][n], on the handle's stream (k_dense_weights)
 hipError_t enqueue_dense_weights(smc_filter_s* h, double* w);
+// ... and the block smc_get_state and smc_get_moments put them (and the moments behind them) in: h->d_wdense, allocated once
+int ensure_wdense(smc_handle h);
 // smc_capi_smooth.hip: appends the state smc_init / smc_step leave to the record of an armed handle (no host synchronisation);
 // the calls that would change the state of an armed handle without a recordable step refuse with history_refuse()
 int history_append(smc_handle h);
-void history_free(smc_filter_s* h);
+void history_free(smc_filter_s* h);   // (frees the record and every block over it: the handle is disarmed)
 inline bool history_armed(const smc_filter_s* h) { return h->hist.armed; }
 int history_refuse(const char* who);
 // smc_capi_slots.hip: k_copy_slots on stream s (slot th of dst <- slot th of src where mask[th])

@@ -18,38 +18,40 @@ struct smc_ibis_s {
     int predict_first = 0;
     uint32_t flags = 0;             // smc_ibis_set_flags: 0 or SMC_FLAG_NAN_MISSING (a NaN observation is a missing Kalman step)
     hipStream_t stream = nullptr;
-    IbisView v{};
+    IbisView v{};                   // views of the two sets below, as the kernels take them
+    DevBlock d_theta[2], d_raw[2], d_x[2], d_S[2], d_logZ[2], d_logw[2];   // double [M][MAX_DTHETA] | [M][IBIS_NRAW] | [M] each
     int cp = 0, cs = 0;             // current (theta, raw) set and current (x, S, logZ, logw) set
     PmmhSpec spec{};
     bool configured = false, have_theta = false;
     int64_t t = 0;                  // observations committed so far
     int win_k = 0;                  // steps of the pending window (its end state sits in set cs ^ 1); 0: none
     std::vector<double> win_y;
-    double* d_y = nullptr;   size_t y_cap = 0;
-    double* d_lik = nullptr; size_t lik_cap = 0;
-    uint64_t* d_rec = nullptr; size_t rec_cap = 0;
-    int32_t* d_a = nullptr;
-    unsigned char* d_moved = nullptr;
-    unsigned long long* d_count = nullptr;
-    double* d_chol = nullptr;       // [MAX_DTHETA^2] | sq [IBIS_MAX_CHAIN]
+    // every block below is freed with the handle; those without a size here grow on demand (old block first)
+    DevBlock d_y;                   // double [T] or [k]
+    DevBlock d_lik;                 // double [k][M]
+    DevBlock d_rec;                 // uint64_t [k][nseg][4]
+    DevBlock d_a;                   // int32_t [M]
+    DevBlock d_moved;               // unsigned char [M]
+    DevBlock d_count;               // unsigned long long [1]
+    DevBlock d_chol;                // double [MAX_DTHETA^2] | sq [IBIS_MAX_CHAIN]
     // summaries (smc_ibis_set_summaries / smc_ibis_summary): chunk records and scratch, rows of the last window
     bool summ_on = false;
     int summ_ahead = 0;
-    double* d_part = nullptr; size_t part_cap = 0;   // [rows][IBIS_SUM_NCOL][nchunk]
-    double* d_srow = nullptr;                        // [IBIS_MAX_WINDOW][IBIS_SUM_NOUT]
-    double* d_one = nullptr; size_t one_cap = 0;     // [IBIS_SUM_NCOL][nchunk] | [IBIS_SUM_NOUT]: smc_ibis_summary
+    DevBlock d_part;                                 // double [rows][IBIS_SUM_NCOL][nchunk]
+    DevBlock d_srow;                                 // double [IBIS_MAX_WINDOW][IBIS_SUM_NOUT]
+    DevBlock d_one;                                  // double [IBIS_SUM_NCOL][nchunk] | [IBIS_SUM_NOUT]: smc_ibis_summary
     double srow[IBIS_MAX_WINDOW * IBIS_SUM_NOUT];
     int srow_k = 0;                                  // rows of srow that are set
     // the resample-move loop on the device (smc_ibis_window_ess / smc_ibis_resample / smc_ibis_theta_moments)
     bool have_moved = false;                         // d_moved holds the mask of a rejuvenation
-    uint32_t* d_K = nullptr;                         // [IBIS_MAX_WINDOW] biased K of every step of a window | [0] of the cloud
-    unsigned long long* d_DR = nullptr;              // [IBIS_MAX_WINDOW][2] (D, R) of every step
-    uint64_t* d_q = nullptr;                         // [M] fixed-point weights | then the inclusive scan of cnt
-    uint64_t* d_seg = nullptr;                       // [nseg] S | [nseg] Dcum | [ntile(M)] tile sums of the scans
-    uint32_t* d_skb = nullptr;                       // [nseg] biased kb
-    int32_t* d_cnt = nullptr;                        // [M] draws per particle
-    double* d_mpart = nullptr;                       // [THETA_MOM_NTRI][nchunk] chunk sums of the moments
-    double* d_mom = nullptr;                         // [IBIS_MOM_N]
+    DevBlock d_K;                                    // uint32_t [IBIS_MAX_WINDOW] biased K of every step of a window | [0] of the cloud
+    DevBlock d_DR;                                   // unsigned long long [IBIS_MAX_WINDOW][2] (D, R) of every step
+    DevBlock d_q;                                    // uint64_t [M] fixed-point weights | then the inclusive scan of cnt
+    DevBlock d_seg;                                  // uint64_t [nseg] S | [nseg] Dcum | [ntile(M)] tile sums of the scans
+    DevBlock d_skb;                                  // uint32_t [nseg] biased kb
+    DevBlock d_cnt;                                  // int32_t [M] draws per particle
+    DevBlock d_mpart;                                // double [THETA_MOM_NTRI][nchunk] chunk sums of the moments
+    DevBlock d_mom;                                  // double [IBIS_MOM_N]
     double rts_ms = -1.0;                            // device-event time of the kernels of the last smooth / sample_paths call
 };
 typedef smc_ibis_s* ibis_t;
@@ -63,25 +65,7 @@ ibis_t as_ibis(void* p) {
 }
 unsigned grid_of(int64_t M) { return (unsigned)((M + IBIS_THREADS - 1) / IBIS_THREADS); }
 
-template <class T>
-hipError_t grow(T** p, size_t* cap, size_t count) {
-    if (*cap >= count) return hipSuccess;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-    if (e == hipSuccess) *cap = count;
-    return e;
-}
-
-void release(ibis_t h) {
-    for (int b = 0; b < 2; ++b) {
-        (void)hipFree(h->v.theta[b]); (void)hipFree(h->v.raw[b]); (void)hipFree(h->v.x[b]);
-        (void)hipFree(h->v.S[b]); (void)hipFree(h->v.logZ[b]); (void)hipFree(h->v.logw[b]);
-    }
-    (void)hipFree(h->d_y); (void)hipFree(h->d_lik); (void)hipFree(h->d_rec); (void)hipFree(h->d_a);
-    (void)hipFree(h->d_moved); (void)hipFree(h->d_count); (void)hipFree(h->d_chol);
-    (void)hipFree(h->d_part); (void)hipFree(h->d_srow); (void)hipFree(h->d_one);
-    (void)hipFree(h->d_K); (void)hipFree(h->d_DR); (void)hipFree(h->d_q); (void)hipFree(h->d_seg); (void)hipFree(h->d_skb);
-    (void)hipFree(h->d_cnt); (void)hipFree(h->d_mpart); (void)hipFree(h->d_mom);
+void release(ibis_t h) {   // (the blocks go with the handle)
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -95,8 +79,8 @@ void launch_init(ibis_t h) {
 template <int D, bool MISS>
 void launch_rejuvenate_as(ibis_t h, int64_t T, double xi, int chain, uint64_t move_seed) {
     hipLaunchKernelGGL((k_ibis_rejuvenate<D, MISS>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->spec,
-                       h->d_y, T, h->predict_first, xi, h->d_chol, h->d_chol + MAX_DTHETA * MAX_DTHETA, chain, move_seed, h->d_moved,
-                       h->d_count);
+                       h->d_y.as<double>(), T, h->predict_first, xi, h->d_chol.as<double>(), h->d_chol.as<double>() + MAX_DTHETA * MAX_DTHETA, chain, move_seed, h->d_moved.as<unsigned char>(),
+                       h->d_count.as<unsigned long long>());
 }
 template <int D>
 void launch_rejuvenate(ibis_t h, bool miss, int64_t T, double xi, int chain, uint64_t move_seed) {
@@ -127,12 +111,12 @@ void launch_rts_forward(hipStream_t st, bool miss, const double* raw, int64_t M,
 
 // run `steps` observations from the committed state in place (no records): the prefix of a window that is kept, or a whole series
 int steps_in_place(ibis_t h, const double* y, int64_t steps) {
-    HIPCHK(grow(&h->d_y, &h->y_cap, (size_t)steps));
-    HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)steps * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h->d_y.grow((size_t)steps * 8));
+    HIPCHK(hipMemcpyAsync(h->d_y.as<double>(), y, (size_t)steps * 8, hipMemcpyHostToDevice, h->stream));
     int64_t done = 0;
     while (done < steps) {   // (the kernel's step count is an int)
         const int k = (int)(steps - done > (1 << 20) ? (1 << 20) : steps - done);
-        launch_window<false, false>(h, kalman_has_gap(h->flags, y + done, k), h->cs, h->d_y + done, k,
+        launch_window<false, false>(h, kalman_has_gap(h->flags, y + done, k), h->cs, h->d_y.as<double>() + done, k,
                                     (h->t + done > 0 || h->predict_first) ? 1 : 0, nullptr, nullptr, nullptr, 0);
         HIPCHK(hipGetLastError());
         done += k;
@@ -160,21 +144,23 @@ extern "C" int smc_ibis_create(int64_t n_theta, uint64_t seed, int device, int p
     const size_t M = (size_t)n_theta;
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     for (int b = 0; b < 2 && e == hipSuccess; ++b) {
-        if (e == hipSuccess) e = hipMalloc((void**)&h->v.theta[b], M * MAX_DTHETA * 8);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->v.raw[b], M * IBIS_NRAW * 8);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->v.x[b], M * 8);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->v.S[b], M * 8);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->v.logZ[b], M * 8);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->v.logw[b], M * 8);
+        if (e == hipSuccess) e = h->d_theta[b].grow(M * MAX_DTHETA * 8);
+        if (e == hipSuccess) e = h->d_raw[b].grow(M * IBIS_NRAW * 8);
+        if (e == hipSuccess) e = h->d_x[b].grow(M * 8);
+        if (e == hipSuccess) e = h->d_S[b].grow(M * 8);
+        if (e == hipSuccess) e = h->d_logZ[b].grow(M * 8);
+        if (e == hipSuccess) e = h->d_logw[b].grow(M * 8);
+        h->v.theta[b] = h->d_theta[b].as<double>(); h->v.raw[b] = h->d_raw[b].as<double>(); h->v.x[b] = h->d_x[b].as<double>();
+        h->v.S[b] = h->d_S[b].as<double>(); h->v.logZ[b] = h->d_logZ[b].as<double>(); h->v.logw[b] = h->d_logw[b].as<double>();
     }
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_a, M * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_moved, M);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_count, 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_chol, (MAX_DTHETA * MAX_DTHETA + IBIS_MAX_CHAIN) * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_srow, IBIS_MAX_WINDOW * IBIS_SUM_NOUT * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_K, IBIS_MAX_WINDOW * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_DR, IBIS_MAX_WINDOW * 2 * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_mom, IBIS_MOM_N * 8);
+    if (e == hipSuccess) e = h->d_a.grow(M * 4);
+    if (e == hipSuccess) e = h->d_moved.grow(M);
+    if (e == hipSuccess) e = h->d_count.grow(8);
+    if (e == hipSuccess) e = h->d_chol.grow((MAX_DTHETA * MAX_DTHETA + IBIS_MAX_CHAIN) * 8);
+    if (e == hipSuccess) e = h->d_srow.grow(IBIS_MAX_WINDOW * IBIS_SUM_NOUT * 8);
+    if (e == hipSuccess) e = h->d_K.grow(IBIS_MAX_WINDOW * 4);
+    if (e == hipSuccess) e = h->d_DR.grow(IBIS_MAX_WINDOW * 2 * 8);
+    if (e == hipSuccess) e = h->d_mom.grow(IBIS_MOM_N * 8);
     if (e != hipSuccess) {
         release(h);
         return fail(e == hipErrorOutOfMemory ? SMC_ENOMEM : SMC_EHIP, std::string("smc_ibis_create: ") + hipGetErrorString(e));
@@ -251,24 +237,24 @@ static int enqueue_window(ibis_t h, const char* who, const double* y, int k, boo
     HIPCHK(hipSetDevice(h->device));
     h->win_k = 0;
     const size_t M = (size_t)h->v.M, nseg = (M + IBIS_OSEG - 1) / IBIS_OSEG;
-    HIPCHK(grow(&h->d_y, &h->y_cap, (size_t)k));
-    HIPCHK(grow(&h->d_rec, &h->rec_cap, (size_t)k * nseg * 4));
-    if (lik) HIPCHK(grow(&h->d_lik, &h->lik_cap, (size_t)k * M));
+    HIPCHK(h->d_y.grow((size_t)k * 8));
+    HIPCHK(h->d_rec.grow((size_t)k * nseg * 4 * 8));
+    if (lik) HIPCHK(h->d_lik.grow((size_t)k * M * 8));
     const size_t nchunk = grid_of(h->v.M);
     h->srow_k = 0;
-    if (h->summ_on) HIPCHK(grow(&h->d_part, &h->part_cap, (size_t)k * IBIS_SUM_NCOL * nchunk));
-    HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)k * 8, hipMemcpyHostToDevice, h->stream));
+    if (h->summ_on) HIPCHK(h->d_part.grow((size_t)k * IBIS_SUM_NCOL * nchunk * 8));
+    HIPCHK(hipMemcpyAsync(h->d_y.as<double>(), y, (size_t)k * 8, hipMemcpyHostToDevice, h->stream));
     const bool miss = kalman_has_gap(h->flags, y, k);
     const int predict0 = (h->t > 0 || h->predict_first) ? 1 : 0;
     if (h->summ_on) {   // the same steps, and the chunk records of the summaries after each; then one workgroup per row combines them
-        launch_window<true, true>(h, miss, h->cs ^ 1, h->d_y, k, predict0, lik ? h->d_lik : nullptr, h->d_rec, h->d_part, h->summ_ahead);
+        launch_window<true, true>(h, miss, h->cs ^ 1, h->d_y.as<double>(), k, predict0, lik ? h->d_lik.as<double>() : nullptr, h->d_rec.as<uint64_t>(), h->d_part.as<double>(), h->summ_ahead);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_ibis_sum_combine, dim3((unsigned)k), dim3(IBIS_SUM_CTHREADS), 0, h->stream, h->d_part, (int64_t)nchunk,
-                           h->d_srow);
+        hipLaunchKernelGGL(k_ibis_sum_combine, dim3((unsigned)k), dim3(IBIS_SUM_CTHREADS), 0, h->stream, h->d_part.as<double>(), (int64_t)nchunk,
+                           h->d_srow.as<double>());
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h->srow, h->d_srow, (size_t)k * IBIS_SUM_NOUT * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(h->srow, h->d_srow.as<double>(), (size_t)k * IBIS_SUM_NOUT * 8, hipMemcpyDeviceToHost, h->stream));
     } else {
-        launch_window<true, false>(h, miss, h->cs ^ 1, h->d_y, k, predict0, lik ? h->d_lik : nullptr, h->d_rec, nullptr, 0);
+        launch_window<true, false>(h, miss, h->cs ^ 1, h->d_y.as<double>(), k, predict0, lik ? h->d_lik.as<double>() : nullptr, h->d_rec.as<uint64_t>(), nullptr, 0);
         HIPCHK(hipGetLastError());
     }
     return SMC_OK;
@@ -285,8 +271,8 @@ extern "C" int smc_ibis_window(void* hp, const double* y, int k, double* lik, ui
     if (!h || !y || !rec) return fail(SMC_EINVAL, "smc_ibis_window: bad argument");
     if (const int rc = enqueue_window(h, "smc_ibis_window", y, k, lik != nullptr)) return rc;
     const size_t M = (size_t)h->v.M, nseg = (M + IBIS_OSEG - 1) / IBIS_OSEG;
-    HIPCHK(hipMemcpyAsync(rec, h->d_rec, (size_t)k * nseg * 32, hipMemcpyDeviceToHost, h->stream));
-    if (lik) HIPCHK(hipMemcpyAsync(lik, h->d_lik, (size_t)k * M * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(rec, h->d_rec.as<uint64_t>(), (size_t)k * nseg * 32, hipMemcpyDeviceToHost, h->stream));
+    if (lik) HIPCHK(hipMemcpyAsync(lik, h->d_lik.as<double>(), (size_t)k * M * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     window_pending(h, y, k);
     return SMC_OK;
@@ -301,16 +287,16 @@ extern "C" int smc_ibis_window_ess(void* hp, const double* y, int k, double ess_
     const int SH = table_shift_extra(nseg * IBIS_OSEG);
     int64_t gx = (nseg + IBIS_RED_THREADS - 1) / IBIS_RED_THREADS;
     gx = gx > 128 ? 128 : gx;
-    HIPCHK(hipMemsetAsync(h->d_K, 0, (size_t)k * 4, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_DR, 0, (size_t)k * 16, h->stream));
-    hipLaunchKernelGGL(k_ibis_rec_kmax, dim3((unsigned)gx, (unsigned)k), dim3(IBIS_RED_THREADS), 0, h->stream, h->d_rec, nseg, h->d_K);
-    hipLaunchKernelGGL(k_ibis_rec_sums, dim3((unsigned)gx, (unsigned)k), dim3(IBIS_RED_THREADS), 0, h->stream, h->d_rec, nseg, SH, h->d_K,
-                       h->d_DR);
+    HIPCHK(hipMemsetAsync(h->d_K.as<uint32_t>(), 0, (size_t)k * 4, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_DR.as<unsigned long long>(), 0, (size_t)k * 16, h->stream));
+    hipLaunchKernelGGL(k_ibis_rec_kmax, dim3((unsigned)gx, (unsigned)k), dim3(IBIS_RED_THREADS), 0, h->stream, h->d_rec.as<uint64_t>(), nseg, h->d_K.as<uint32_t>());
+    hipLaunchKernelGGL(k_ibis_rec_sums, dim3((unsigned)gx, (unsigned)k), dim3(IBIS_RED_THREADS), 0, h->stream, h->d_rec.as<uint64_t>(), nseg, SH, h->d_K.as<uint32_t>(),
+                       h->d_DR.as<unsigned long long>());
     HIPCHK(hipGetLastError());
     uint32_t Kb[IBIS_MAX_WINDOW];
     unsigned long long DR[IBIS_MAX_WINDOW * 2];
-    HIPCHK(hipMemcpyAsync(Kb, h->d_K, (size_t)k * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(DR, h->d_DR, (size_t)k * 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(Kb, h->d_K.as<uint32_t>(), (size_t)k * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(DR, h->d_DR.as<unsigned long long>(), (size_t)k * 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     int j = 0;
     while (j < k) {          // smc_host_outer_walk
@@ -369,8 +355,8 @@ extern "C" int smc_ibis_summary(void* hp, int ahead, double* out) {
     HIPCHK(hipSetDevice(h->device));
     const size_t nchunk = grid_of(h->v.M);
     // (a buffer of its own: the rows of a pending window stay intact)
-    HIPCHK(grow(&h->d_one, &h->one_cap, IBIS_SUM_NCOL * nchunk + IBIS_SUM_NOUT));
-    double* d_one = h->d_one;
+    HIPCHK(h->d_one.grow((IBIS_SUM_NCOL * nchunk + IBIS_SUM_NOUT) * 8));
+    double* d_one = h->d_one.as<double>();
     hipLaunchKernelGGL(k_ibis_sum_chunks, dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, ahead, d_one);
     hipLaunchKernelGGL(k_ibis_sum_combine, dim3(1), dim3(IBIS_SUM_CTHREADS), 0, h->stream, d_one, (int64_t)nchunk,
                        d_one + IBIS_SUM_NCOL * nchunk);
@@ -486,8 +472,8 @@ extern "C" int smc_ibis_permute(void* hp, const int32_t* a) {
         if (a[m] < 0 || a[m] >= M) return fail(SMC_EINVAL, "smc_ibis_permute: ancestor index out of range");
     HIPCHK(hipSetDevice(h->device));
     h->win_k = 0;
-    HIPCHK(hipMemcpyAsync(h->d_a, a, (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_ibis_permute, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->d_a);
+    HIPCHK(hipMemcpyAsync(h->d_a.as<int32_t>(), a, (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_ibis_permute, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->d_a.as<int32_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     h->cp ^= 1;
@@ -518,17 +504,17 @@ extern "C" int smc_ibis_rejuvenate(void* hp, const double* y, int64_t T, double 
     double par[MAX_DTHETA * MAX_DTHETA + IBIS_MAX_CHAIN] = {0.0};
     for (int i = 0; i < d * d; ++i) par[i] = chol[i];
     for (int c = 0; c < chain; ++c) par[MAX_DTHETA * MAX_DTHETA + c] = sqrt(scales[c]);
-    HIPCHK(grow(&h->d_y, &h->y_cap, (size_t)T));
-    HIPCHK(hipMemcpyAsync(h->d_y, y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_chol, par, sizeof(par), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_count, 0, 8, h->stream));
+    HIPCHK(h->d_y.grow((size_t)T * 8));
+    HIPCHK(hipMemcpyAsync(h->d_y.as<double>(), y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_chol.as<double>(), par, sizeof(par), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_count.as<unsigned long long>(), 0, 8, h->stream));
     const bool miss = kalman_has_gap(h->flags, y, T);
 #define IBIS_CALL_REJ(D) launch_rejuvenate<D>(h, miss, T, xi, chain, move_seed)
     IBIS_BY_D(d, IBIS_CALL_REJ)
     HIPCHK(hipGetLastError());
     unsigned long long n = 0;
-    HIPCHK(hipMemcpyAsync(&n, h->d_count, 8, hipMemcpyDeviceToHost, h->stream));
-    if (moved) HIPCHK(hipMemcpyAsync(moved, h->d_moved, (size_t)h->v.M, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&n, h->d_count.as<unsigned long long>(), 8, hipMemcpyDeviceToHost, h->stream));
+    if (moved) HIPCHK(hipMemcpyAsync(moved, h->d_moved.as<unsigned char>(), (size_t)h->v.M, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (accepted) *accepted = (int64_t)n;
     h->have_moved = true;
@@ -540,7 +526,7 @@ extern "C" int smc_ibis_get_moved(void* hp, uint8_t* moved) {
     if (!h || !moved) return fail(SMC_EINVAL, "smc_ibis_get_moved: bad argument");
     if (!h->have_moved) return fail(SMC_ESTATE, "smc_ibis_get_moved: smc_ibis_rejuvenate has not been called");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(moved, h->d_moved, (size_t)h->v.M, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(moved, h->d_moved.as<unsigned char>(), (size_t)h->v.M, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SMC_OK;
 }
@@ -559,13 +545,13 @@ void launch_moments(ibis_t h, int weighted, int64_t nchunk) {
     const int64_t M = h->v.M;
     const int ntri = D * (D + 1) / 2;
     hipLaunchKernelGGL((k_ibis_mom_chunks<D, 1>), dim3((unsigned)nchunk), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, weighted,
-                       (const uint32_t*)h->d_K, (const double*)h->d_mom, h->d_mpart);
-    hipLaunchKernelGGL(k_ibis_mom_combine, dim3(1), dim3(IBIS_THREADS), 0, h->stream, (const double*)h->d_mpart, D, nchunk,
-                       h->d_mom + IBIS_MOM_MEAN, weighted ? 0 : 1, (double)M, weighted, (const double*)h->d_mom);
+                       h->d_K.as<const uint32_t>(), h->d_mom.as<const double>(), h->d_mpart.as<double>());
+    hipLaunchKernelGGL(k_ibis_mom_combine, dim3(1), dim3(IBIS_THREADS), 0, h->stream, h->d_mpart.as<const double>(), D, nchunk,
+                       h->d_mom.as<double>() + IBIS_MOM_MEAN, weighted ? 0 : 1, (double)M, weighted, h->d_mom.as<const double>());
     hipLaunchKernelGGL((k_ibis_mom_chunks<D, 2>), dim3((unsigned)nchunk), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, weighted,
-                       (const uint32_t*)h->d_K, (const double*)h->d_mom, h->d_mpart);
-    hipLaunchKernelGGL(k_ibis_mom_combine, dim3(1), dim3(IBIS_THREADS), 0, h->stream, (const double*)h->d_mpart, ntri, nchunk,
-                       h->d_mom + IBIS_MOM_COV, weighted ? 0 : 1, (double)(M - 1), weighted, (const double*)h->d_mom);
+                       h->d_K.as<const uint32_t>(), h->d_mom.as<const double>(), h->d_mpart.as<double>());
+    hipLaunchKernelGGL(k_ibis_mom_combine, dim3(1), dim3(IBIS_THREADS), 0, h->stream, h->d_mpart.as<const double>(), ntri, nchunk,
+                       h->d_mom.as<double>() + IBIS_MOM_COV, weighted ? 0 : 1, (double)(M - 1), weighted, h->d_mom.as<const double>());
 }
 }  // namespace
 
@@ -580,22 +566,22 @@ extern "C" int smc_ibis_resample(void* hp, uint64_t seed, int32_t* a_out) {
     const int64_t M = h->v.M, nseg = (M + IBIS_OSEG - 1) / IBIS_OSEG, ntile = (M + IBIS_RED_THREADS - 1) / IBIS_RED_THREADS;
     const int SH = table_shift_extra(nseg * IBIS_OSEG);
     // (each buffer on its own: a call that ran out of memory half way leaves the rest to the next one)
-    if (!h->d_q) HIPCHK(hipMalloc((void**)&h->d_q, (size_t)M * 8));
-    if (!h->d_seg) HIPCHK(hipMalloc((void**)&h->d_seg, (size_t)(2 * nseg + ntile) * 8));
-    if (!h->d_skb) HIPCHK(hipMalloc((void**)&h->d_skb, (size_t)nseg * 4));
-    if (!h->d_cnt) HIPCHK(hipMalloc((void**)&h->d_cnt, (size_t)M * 4));
-    uint64_t *sS = h->d_seg, *Dcum = h->d_seg + nseg, *tsum = h->d_seg + 2 * nseg;
-    HIPCHK(hipMemsetAsync(h->d_K, 0, 4, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_cnt, 0, (size_t)M * 4, h->stream));
-    hipLaunchKernelGGL(k_ibis_rs_weights, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cs, h->d_q, h->d_skb, sS, h->d_K);
-    launch_scan(h, IbisSegQ{h->d_skb, sS, h->d_K, SH}, nseg, tsum, Dcum);
-    hipLaunchKernelGGL(k_ibis_rs_draw, dim3(grid_of((M + 1) / 2)), dim3(IBIS_THREADS), 0, h->stream, M, seed, (const uint64_t*)h->d_q,
-                       (const uint32_t*)h->d_skb, (const uint32_t*)h->d_K, SH, (const uint64_t*)Dcum, nseg, h->d_cnt);
-    launch_scan(h, IbisCount{h->d_cnt}, M, tsum, h->d_q);          // (the weights are spent: their array takes the scan of cnt)
-    hipLaunchKernelGGL(k_ibis_rs_expand, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, M, (const uint64_t*)h->d_q, h->d_a);
-    hipLaunchKernelGGL(k_ibis_permute, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->d_a);
+    HIPCHK(h->d_q.grow((size_t)M * 8));
+    HIPCHK(h->d_seg.grow((size_t)(2 * nseg + ntile) * 8));
+    HIPCHK(h->d_skb.grow((size_t)nseg * 4));
+    HIPCHK(h->d_cnt.grow((size_t)M * 4));
+    uint64_t *sS = h->d_seg.as<uint64_t>(), *Dcum = sS + nseg, *tsum = sS + 2 * nseg;
+    HIPCHK(hipMemsetAsync(h->d_K.as<uint32_t>(), 0, 4, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_cnt.as<int32_t>(), 0, (size_t)M * 4, h->stream));
+    hipLaunchKernelGGL(k_ibis_rs_weights, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cs, h->d_q.as<uint64_t>(), h->d_skb.as<uint32_t>(), sS, h->d_K.as<uint32_t>());
+    launch_scan(h, IbisSegQ{h->d_skb.as<uint32_t>(), sS, h->d_K.as<uint32_t>(), SH}, nseg, tsum, Dcum);
+    hipLaunchKernelGGL(k_ibis_rs_draw, dim3(grid_of((M + 1) / 2)), dim3(IBIS_THREADS), 0, h->stream, M, seed, h->d_q.as<const uint64_t>(),
+                       h->d_skb.as<const uint32_t>(), h->d_K.as<const uint32_t>(), SH, (const uint64_t*)Dcum, nseg, h->d_cnt.as<int32_t>());
+    launch_scan(h, IbisCount{h->d_cnt.as<int32_t>()}, M, tsum, h->d_q.as<uint64_t>());          // (the weights are spent: their array takes the scan of cnt)
+    hipLaunchKernelGGL(k_ibis_rs_expand, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, M, h->d_q.as<const uint64_t>(), h->d_a.as<int32_t>());
+    hipLaunchKernelGGL(k_ibis_permute, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->d_a.as<int32_t>());
     HIPCHK(hipGetLastError());
-    if (a_out) HIPCHK(hipMemcpyAsync(a_out, h->d_a, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
+    if (a_out) HIPCHK(hipMemcpyAsync(a_out, h->d_a.as<int32_t>(), (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->cp ^= 1;
     h->cs ^= 1;
@@ -611,20 +597,20 @@ extern "C" int smc_ibis_theta_moments(void* hp, int weighted, double* mean, doub
     HIPCHK(hipSetDevice(h->device));
     const int64_t nchunk = grid_of(h->v.M);
     const int d = h->spec.d;
-    if (!h->d_mpart) HIPCHK(hipMalloc((void**)&h->d_mpart, (size_t)THETA_MOM_NTRI * (size_t)nchunk * 8));
+    HIPCHK(h->d_mpart.grow((size_t)THETA_MOM_NTRI * (size_t)nchunk * 8));
     if (weighted) {
-        HIPCHK(hipMemsetAsync(h->d_K, 0, 4, h->stream));
-        hipLaunchKernelGGL(k_ibis_kmax, dim3((unsigned)nchunk), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cs, h->d_K);
-        hipLaunchKernelGGL(k_ibis_mom_w, dim3((unsigned)nchunk), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cs, (const uint32_t*)h->d_K,
-                           h->d_mpart);
-        hipLaunchKernelGGL(k_ibis_mom_combine, dim3(1), dim3(IBIS_THREADS), 0, h->stream, (const double*)h->d_mpart, 1, nchunk, h->d_mom, 0,
-                           0.0, 0, (const double*)h->d_mom);
+        HIPCHK(hipMemsetAsync(h->d_K.as<uint32_t>(), 0, 4, h->stream));
+        hipLaunchKernelGGL(k_ibis_kmax, dim3((unsigned)nchunk), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cs, h->d_K.as<uint32_t>());
+        hipLaunchKernelGGL(k_ibis_mom_w, dim3((unsigned)nchunk), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cs, h->d_K.as<const uint32_t>(),
+                           h->d_mpart.as<double>());
+        hipLaunchKernelGGL(k_ibis_mom_combine, dim3(1), dim3(IBIS_THREADS), 0, h->stream, h->d_mpart.as<const double>(), 1, nchunk, h->d_mom.as<double>(), 0,
+                           0.0, 0, h->d_mom.as<const double>());
     }
 #define IBIS_CALL_MOM(D) launch_moments<D>(h, weighted, nchunk)
     IBIS_BY_D(d, IBIS_CALL_MOM)
     HIPCHK(hipGetLastError());
     double mom[IBIS_MOM_N];
-    HIPCHK(hipMemcpyAsync(mom, h->d_mom, sizeof(mom), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(mom, h->d_mom.as<double>(), sizeof(mom), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int i = 0; i < d; ++i) {
         mean[i] = mom[IBIS_MOM_MEAN + i];
@@ -660,17 +646,12 @@ extern "C" int smc_ibis_get(void* hp, double* theta, double* x, double* S, doubl
 // ---- the RTS smoother of the cloud and its backward-sampled paths (smc_spec.h "the RTS smoother of an IBIS cloud") -------------
 // Everything these calls need on the device is allocated by the call and freed before it returns: the handle is read only.
 namespace {
-struct CallBlock {   // one device allocation for the life of a call
-    char* p = nullptr;
-    ~CallBlock() { if (p) (void)hipFree(p); }
-    int alloc(const char* who, size_t bytes) {
-        const hipError_t e = hipMalloc((void**)&p, bytes ? bytes : 16);
-        if (e == hipSuccess) return SMC_OK;
-        p = nullptr;
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? SMC_ENOMEM : SMC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
-    }
-};
+// one device allocation for the life of a call: a local block, freed when the call returns
+int call_alloc(DevBlock& blk, const char* who, size_t bytes) {
+    const hipError_t e = blk.grow(bytes);
+    if (e == hipSuccess) return SMC_OK;
+    return fail(e == hipErrorOutOfMemory ? SMC_ENOMEM : SMC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+}
 struct CallEvents {   // the bracket of a call's kernels on the handle's stream
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~CallEvents() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
@@ -690,10 +671,11 @@ extern "C" int smc_ibis_smooth(void* hp, const double* y, int64_t T, double* out
     HIPCHK(hipSetDevice(h->device));
     const size_t M = (size_t)h->v.M, nchunk = grid_of(h->v.M), sT = (size_t)T;
     const size_t b_y = up256(sT * 8), b_rec = up256(sT * M * 8), b_part = up256(sT * IBIS_SUM_NCOL * nchunk * 8), b_out = sT * IBIS_SUM_NOUT * 8;
-    CallBlock blk;
-    if (const int rc = blk.alloc("smc_ibis_smooth", b_y + 2 * b_rec + b_part + b_out)) return rc;
-    double *d_y = (double*)blk.p, *d_xf = (double*)(blk.p + b_y), *d_Sf = (double*)(blk.p + b_y + b_rec);
-    double *d_part = (double*)(blk.p + b_y + 2 * b_rec), *d_out = (double*)(blk.p + b_y + 2 * b_rec + b_part);
+    DevBlock blk;
+    if (const int rc = call_alloc(blk, "smc_ibis_smooth", b_y + 2 * b_rec + b_part + b_out)) return rc;
+    char* const base = blk.as<char>();
+    double *d_y = (double*)base, *d_xf = (double*)(base + b_y), *d_Sf = (double*)(base + b_y + b_rec);
+    double *d_part = (double*)(base + b_y + 2 * b_rec), *d_out = (double*)(base + b_y + 2 * b_rec + b_part);
     const bool store = xs != nullptr || Ps != nullptr;
     CallEvents ev;
     HIPCHK(ev.create());
@@ -730,11 +712,12 @@ extern "C" int smc_ibis_sample_paths(void* hp, const double* y, int64_t T, int64
     HIPCHK(hipSetDevice(h->device));
     const size_t sM = (size_t)Mp, sT = (size_t)T;
     const size_t b_y = up256(sT * 8), b_w = up256(sM * 4), b_rec = up256(sT * sM * 8);
-    CallBlock blk;
-    if (const int rc = blk.alloc("smc_ibis_sample_paths", b_y + b_w + 2 * b_rec)) return rc;
-    double* d_y = (double*)blk.p;
-    int32_t* d_w = (int32_t*)(blk.p + b_y);
-    double *d_paths = (double*)(blk.p + b_y + b_w), *d_Sf = (double*)(blk.p + b_y + b_w + b_rec);
+    DevBlock blk;
+    if (const int rc = call_alloc(blk, "smc_ibis_sample_paths", b_y + b_w + 2 * b_rec)) return rc;
+    char* const base = blk.as<char>();
+    double* d_y = (double*)base;
+    int32_t* d_w = (int32_t*)(base + b_y);
+    double *d_paths = (double*)(base + b_y + b_w), *d_Sf = (double*)(base + b_y + b_w + b_rec);
     HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, h->stream));
     CallEvents ev;
     HIPCHK(ev.create());
@@ -774,9 +757,10 @@ extern "C" int smc_kalman_smooth_flags(const double* raw, int64_t n_theta, const
     HIPCHK(hipSetDevice(device));
     const size_t M = (size_t)n_theta, sT = (size_t)T;
     const size_t b_y = up256(sT * 8), b_raw = up256(M * IBIS_NRAW * 8), b_rec = up256(sT * M * 8);
-    CallBlock blk;
-    if (const int rc = blk.alloc("smc_kalman_smooth", b_y + b_raw + 2 * b_rec)) return rc;
-    double *d_y = (double*)blk.p, *d_raw = (double*)(blk.p + b_y), *d_xf = (double*)(blk.p + b_y + b_raw), *d_Sf = (double*)(blk.p + b_y + b_raw + b_rec);
+    DevBlock blk;
+    if (const int rc = call_alloc(blk, "smc_kalman_smooth", b_y + b_raw + 2 * b_rec)) return rc;
+    char* const base = blk.as<char>();
+    double *d_y = (double*)base, *d_raw = (double*)(base + b_y), *d_xf = (double*)(base + b_y + b_raw), *d_Sf = (double*)(base + b_y + b_raw + b_rec);
     hipStream_t st = nullptr;   // the default stream: the call owns nothing that outlives it
     HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_raw, raw, M * IBIS_NRAW * 8, hipMemcpyHostToDevice, st));

@@ -410,26 +410,31 @@ extern "C" int smc_device_guided_step(int model_id, const double* raw, int kind,
     PropRow R;
     if (!guided_params(model_id, raw, kind, par, P, R)) return fail(SMC_EINVAL, "smc_device_guided_step: bad model, kind or row");
     const int d = model_dim_rt(model_id);
-    HIPCHK(hipSetDevice(device));
-    double *dxp = nullptr, *dz = nullptr, *dx = nullptr, *dlw = nullptr;
+    hipStream_t st = nullptr;
+    HIPCHK(util_stream(device, &st));
     const size_t bytes = (size_t)d * n * 8;
-    hipError_t e = hipMalloc((void**)&dxp, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&dz, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&dx, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&dlw, (size_t)n * 8);
-    if (e == hipSuccess) e = hipMemcpy(dxp, xp, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dz, z, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-        e = by_guided_model(model_id, [&](auto M) {
-            hipLaunchKernelGGL(k_guided_step<decltype(M)::value>, grid, block, 0, 0, P, R, dxp, dz, y, n, dx, dlw);
-            return hipGetLastError();
-        });
-    }
-    if (e == hipSuccess) e = hipMemcpy(x, dx, bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(logw, dlw, (size_t)n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(dxp); (void)hipFree(dz); (void)hipFree(dx); (void)hipFree(dlw);
-    HIPCHK(e);
+    DevBuf dxp(0), dz(1), dx(2), dlw(3);
+    HIPCHK(dxp.alloc(bytes));
+    HIPCHK(dz.alloc(bytes));
+    HIPCHK(dx.alloc(bytes));
+    HIPCHK(dlw.alloc((size_t)n * 8));
+    HIPCHK(hipMemcpyAsync(dxp.p, xp, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dz.p, z, bytes, hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    HIPCHK(by_guided_model(model_id, [&](auto M) {
+        hipLaunchKernelGGL(k_guided_step<decltype(M)::value>, grid, block, 0, st, P, R, dxp.as<double>(), dz.as<double>(), y, n, dx.as<double>(), dlw.as<double>());
+        return hipGetLastError();
+    }));
+    HIPCHK(hipMemcpyAsync(x, dx.p, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(logw, dlw.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+
+// what the blocks of smc_host.h hold right now, process-wide (include/smc_hip.h)
+extern "C" int smc_live_bytes(int64_t* device_bytes, int64_t* pinned_bytes) {
+    if (device_bytes) *device_bytes = g_live_bytes[0].load(std::memory_order_relaxed);
+    if (pinned_bytes) *pinned_bytes = g_live_bytes[1].load(std::memory_order_relaxed);
     return SMC_OK;
 }
 
