@@ -101,6 +101,14 @@ int smc_reseed(smc_handle h, uint64_t seed);
  * smc_copy_from, smc_unpack_slots or the exchange); 0 when they read them through device pointers.  Results never depend on it.
  * SMC_STEP_BY_VALUE=0 in the environment at smc_create: always 0. */
 int smc_step_by_value(smc_handle h, int* by_value);
+/* Diagnostic.  The workgroup geometry of the handle's launches (any pointer may be NULL).  *threads, *np: threads per workgroup and
+ * particle pairs per thread of the one-launch-per-step kernels (init, step, forecast), seg = 2 * np * threads: the default of the
+ * segment length, or what SMC_NP (1, 2 or 4) in the environment at smc_create selected; a value the segment length has no kernels
+ * for leaves the default.  *resident_np: the pairs per thread the LDS-resident whole-series and window kernels would be asked for
+ * if launched now - SMC_RES_NP (1, 2 or 4) as the environment holds it at THIS call (the launches read it at every call), else 1
+ * for segments of 1024 with at most 512 filters, else 0 = the kernels' own choice for the segment length; a value without a kernel
+ * at the segment length runs the neighbour its table documents.  Results never depend on either knob. */
+int smc_get_launch_geometry(smc_handle h, int* threads, int* np, int* resident_np);
 
 /* ---- proposals: the guided particle filter ----------------------------------------------------
  * particle_filter(N, y, model, proposal) / particle_filter!(x, w, y, model, proposal)          src/particles.jl:28-84

@@ -16,7 +16,7 @@ FLAG_ANCESTORS, FLAG_NO_RESIDENT, FLAG_SYSTEMATIC, FLAG_NAN_MISSING, FLAG_CONDIT
 
 # every symbol include/smc_hip.h declares
 EXPORTS = [
-    "smc_create", "smc_destroy", "smc_set_params", "smc_set_streams", "smc_reseed", "smc_step_by_value", "smc_init", "smc_step",
+    "smc_create", "smc_destroy", "smc_set_params", "smc_set_streams", "smc_reseed", "smc_step_by_value", "smc_get_launch_geometry", "smc_init", "smc_step",
     "smc_log_likelihood", "smc_get_state", "smc_get_logZ", "smc_permute", "smc_copy_from", "smc_slot_bytes", "smc_pack_slots", "smc_unpack_slots", "smc_get_weights_raw", "smc_get_geometry",
     "smc_last_elapsed_ms", "smc_synchronize", "smc_time_step_kernel", "smc_event_overhead_ms", "smc_normalize", "smc_resample", "smc_kalman_log_likelihood", "smc_get_moments", "smc_get_quantiles", "smc_simulate", "smc_simulate_dim", "smc_model_dim",
     "smc_model_nraw", "smc_auto_seg", "smc_device_count", "smc_host_exp", "smc_host_log", "smc_host_philox4x32_10",
@@ -103,6 +103,7 @@ def lib():
     L.smc_set_streams.argtypes = [h, _u32p]
     L.smc_reseed.argtypes = [h, C.c_uint64]
     L.smc_step_by_value.argtypes = [h, C.POINTER(C.c_int)]
+    L.smc_get_launch_geometry.argtypes = [h, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.smc_init.argtypes = [h, C.c_double, _dp]
     L.smc_step.argtypes = [h, C.c_double, _dp, _dp]
     L.smc_log_likelihood.argtypes = [h, _dp, C.c_int64, _dp, _dp, _dp]
@@ -757,6 +758,14 @@ class Handle:
         b = C.c_int()
         check(lib().smc_step_by_value(self._h, C.byref(b)))
         return bool(b.value)
+
+    def launch_geometry(self):
+        """diagnostic: (threads, np, resident_np) - the workgroup geometry of the step launches as SMC_NP left it at smc_create, and
+        the pairs per thread the LDS-resident kernels would be asked for now (SMC_RES_NP read at this call; 0 = their own choice)
+        (smc_get_launch_geometry)"""
+        t, k, r = C.c_int(), C.c_int(), C.c_int()
+        check(lib().smc_get_launch_geometry(self._h, C.byref(t), C.byref(k), C.byref(r)))
+        return t.value, k.value, r.value
 
     def init(self, y1):
         lm = np.zeros(self.n_theta)

@@ -476,6 +476,17 @@ extern "C" int smc_step_by_value(smc_handle h, int* by_value) {
     return SMC_OK;
 }
 
+extern "C" int smc_get_launch_geometry(smc_handle h, int* threads, int* np, int* resident_np) {
+    if (!h) return fail(SMC_EINVAL, "smc_get_launch_geometry: NULL handle");
+    if (threads) *threads = h->geo.threads;
+    if (np) *np = h->geo.np;
+    if (resident_np) {
+        const int r = smc::resident_np(h->v);   // the environment as the launch would read it now
+        *resident_np = (r == 1 || r == 2 || r == 4) ? r : 0;   // (any other value selects what 0 does)
+    }
+    return SMC_OK;
+}
+
 extern "C" int smc_reseed(smc_handle h, uint64_t seed) {
     if (!h) return fail(SMC_EINVAL, "smc_reseed: NULL handle");
     h->v.seed = seed;

@@ -5,6 +5,7 @@
 #include "smc_kernels.h"
 #include "smc_resident.h"
 #include <atomic>
+#include <cstdlib>
 #include <type_traits>
 
 namespace smc {
@@ -69,6 +70,17 @@ struct Geo {
 // the default geometry of a segment size, and whether (threads, np) is an instantiated one
 bool geo_default(int seg, Geo& g);
 bool geo_valid(int seg, int np, Geo& g);
+// Particle pairs per thread of the LDS-resident kernels (Launch<>::resident / ::window pick (threads, np) for the view's segment
+// length by it; 0: no preference, the table's own choice).  Measured (scripts/res_tune.py, scripts/prof_c2.py,
+// scripts/dbg/res1024.py): with at most two workgroups per CU in flight (n_theta <= 512) every model runs faster with one pair per
+// thread (twice the waves: 512 UCSV filters 2.05 -> 1.81 ms); beyond, workgroups of half the size with two pairs per thread pack
+// the CUs without a ragged last round (576 .. 768 filters: +30 % LG, +11 % UCSV; 1024: +8 %).  SMC_RES_NP (1, 2 or 4), read at
+// every launch, overrides the choice for tuning runs; results do not depend on it (tests/test_gpu_geometry.py).  The ONE statement
+// of the rule: the launchers and smc_get_launch_geometry call it.
+inline int resident_np(const FilterView& v) {
+    const char* e = getenv("SMC_RES_NP");
+    return e ? atoi(e) : (v.seg == 1024 && v.ntheta <= 512) ? 1 : 0;
+}
 
 // ---- kernel variants ---------------------------------------------------------------------------------
 // What a handle's options make of its kernels; every variant is a set of translation units of its own (never a run-time branch

@@ -59,11 +59,20 @@ static hipError_t step_launch(const FilterView& v, const StepHot& hot, const dou
 }
 template <int THREADS, int NP, bool SYS, bool BYV>
 static hipError_t step_sys_t(const FilterView& v, const StepHot& hot, const double* xrow, hipStream_t s) {
-    if (v.tabD)   // the table comes from k_table (launched by the caller before this step): no table in LDS, nothing to emit
-        return step_launch<THREADS, NP, true, SYS, true, 1, BYV>(v, hot, xrow, 0, step_lds_bytes(0, THREADS, NP, true), s);
+    // A conditional handle holds at most PATH_MAX_N particles (smc_create refuses more): a table shape that takes more segments of
+    // this length than that many particles fill is never launched for it, and not instantiated (DESIGN.md 2l lists them)
+    constexpr int64_t SEG = 2 * NP * THREADS;
+    constexpr bool HAS_GTAB = !VAR_COND || 2 * THREADS * SEG < PATH_MAX_N;   // (more than 2 THREADS segments)
+    constexpr bool HAS_RPT2 = !VAR_COND || THREADS * SEG < PATH_MAX_N;       // (more than THREADS segments)
+    if (v.tabD) {   // the table comes from k_table (launched by the caller before this step): no table in LDS, nothing to emit
+        if constexpr (HAS_GTAB) return step_launch<THREADS, NP, true, SYS, true, 1, BYV>(v, hot, xrow, 0, step_lds_bytes(0, THREADS, NP, true), s);
+        else return hipErrorInvalidValue;
+    }
     const size_t lds = step_lds_bytes(v.nseg_p2, THREADS, NP, v.nseg > 1);
-    if (v.nseg_p2 > THREADS)   // up to twice as many segments as threads: the window prologue with two records per thread
-        return step_launch<THREADS, NP, true, SYS, false, 2, BYV>(v, hot, xrow, hot.emit_prev, lds, s);
+    if (v.nseg_p2 > THREADS) {   // up to twice as many segments as threads: the window prologue with two records per thread
+        if constexpr (HAS_RPT2) return step_launch<THREADS, NP, true, SYS, false, 2, BYV>(v, hot, xrow, hot.emit_prev, lds, s);
+        else return hipErrorInvalidValue;
+    }
     return v.nseg > 1 ? step_launch<THREADS, NP, true, SYS, false, 1, BYV>(v, hot, xrow, hot.emit_prev, lds, s)
                       : step_launch<THREADS, NP, false, SYS, false, 1, BYV>(v, hot, xrow, hot.emit_prev, lds, s);
 }
@@ -153,16 +162,7 @@ static hipError_t window_t(const FilterView& v, int T, StepRec* recs, int t0, in
                         : resident_sys_t<THREADS, NP, false, true>(v, T, recs, t0, bin, bout, win, s);
 }
 
-// threads / particle pairs per thread of the LDS-resident kernels for a segment length.  Measured (scripts/res_tune.py,
-// scripts/prof_c2.py, scripts/dbg/res1024.py): with at most two workgroups per CU in flight (n_theta <= 512) every model runs faster
-// with one pair per thread (twice the waves: 512 UCSV filters 2.05 -> 1.81 ms); beyond, workgroups of half the size with two
-// pairs per thread pack the CUs without a ragged last round (576 .. 768 filters: +30 % LG, +11 % UCSV; 1024: +8 %).  SMC_RES_NP
-// (1, 2 or 4) overrides the choice for tuning runs; results do not depend on it (tests/test_gpu_parity.py::test_launch_geometry_knobs).
-static int resident_np(const FilterView& v) {
-    const char* e = getenv("SMC_RES_NP");
-    return e ? atoi(e) : (v.seg == 1024 && v.ntheta <= 512) ? 1 : 0;
-}
-
+// threads / particle pairs per thread of the LDS-resident kernels for a segment length: by resident_np (smc_launch.h).
 // (the geometry tables of resident and window differ on purpose: window has no np == 4 at 1024 and only 512 x 2 at 2048)
 template <int MODEL, int VARIANT>
 hipError_t Launch<MODEL, VARIANT>::resident(const FilterView& v, int T, StepRec* recs, hipStream_t s) {
