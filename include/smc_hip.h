@@ -501,7 +501,7 @@ int smc_host_kalman_steps(const double* row /*[6]*/, const double* y, int64_t T,
 int smc_ibis_create(int64_t n_theta, uint64_t seed, int device, int predict_first, void* out);
 int smc_ibis_destroy(void* h);
 int smc_ibis_configure(void* h, int d_theta, const int32_t* prior_family /*[d_theta]*/, const double* prior_par /*[d_theta][SMC_PRIOR_NPAR]*/,
-                       const int32_t* raw_from /*[6]*/, const double* raw_const /*[6]*/);
+                       const int32_t* raw_from /*[6]; [15] on a two-state handle*/, const double* raw_const /*likewise*/);
 int smc_ibis_set_theta(void* h, const double* theta /*[n_theta][d_theta]*/);
 int smc_ibis_window(void* h, const double* y /*[k]*/, int k, double* lik /*[k][n_theta] or NULL*/, uint64_t* rec /*[k][nseg][4]*/);
 int smc_ibis_commit(void* h, int j);
@@ -512,6 +512,48 @@ int smc_ibis_rejuvenate(void* h, const double* y, int64_t T, double xi, const do
                         const double* scales /*[chain]*/, int chain, uint64_t move_seed, int64_t* accepted /*or NULL*/,
                         uint8_t* moved /*[n_theta] or NULL*/);
 int smc_ibis_get(void* h, double* theta, double* x, double* S, double* logZ, double* logw);
+/* ---- two-state linear models: the exact Kalman side (src/state_space_models.jl:137-202, src/kalman_filter.jl:3-27) -----
+ * MultivariateLinearGaussian with a 2 x 2 transition and a scalar observation, hodrick_prescott among them:
+ *   x_t ~ N(A x_{t-1}, Q),  y_t ~ N(B x_t, R),  x_1 ~ N(x0, Sigma0)
+ * as a row of 15 doubles (A11,A12,A21,A22, B1,B2, Q11,Q21,Q22, R, x01,x02, S11,S21,S22).  Q and Sigma0 are symmetric, stored
+ * as their lower triangle, and may be singular (hodrick_prescott: Q = [1/lambda 0; 0 0]).  The row's id, SMC_MODEL_LG2D, is no
+ * particle-filter family - a singular Q has no transition density - so smc_create, smc_simulate, smc_model_dim and
+ * smc_model_nraw refuse it; these models run through the exact filter below.  One order of operations on host and device
+ * (csrc/smc_spec.h kalman2_step, rts2_step).  predict_first as in smc_kalman_log_likelihood.  A step whose innovation variance
+ * is not a positive finite number poisons logZ (NaN) as the scalar step does; nothing faults.
+ *   smc_kalman2_log_likelihood  log_likelihood(y, model) (:55-70) for n rows, one lane each: out [n][6] = (x1, x2, S11, S21, S22, logZ)
+ *   smc_kalman2_smooth          the RTS smoother of every row: xs [T][n][2], Ps [T][n][3] (lower triangle).  A period whose
+ *                               predicted covariance has a determinant that is <= 0 or not finite has no smoothed state: it
+ *                               and every earlier period are NaN; the last period is the filtered state.  That cannot happen
+ *                               when A is invertible and Sigma0 positive definite, or Q is positive definite.
+ *   smc_host_kalman2_steps      the step loop of ONE row on the host (no GPU): xf [T][2], Sf [T][3], lik [T], each or NULL.
+ *                               Every device array of the two-state calls has the bits of a composition of this call.
+ *   smc_host_kalman2_smooth     the backward walk of ONE row on the host: xs [T][2], Ps [T][3], the bits of smc_kalman2_smooth
+ *   smc_simulate_lg2            simulate(rng, model, T) on the host: x [2][T] (or NULL), y [T].  The factor of a singular
+ *                               covariance C is l11 = sqrt(C11), l21 = C21 / l11 (0 when C11 = 0), l22 = sqrt(max(C22 - l21^2, 0));
+ *                               the normals are the Philox slots smc_simulate uses
+ * SMC_EINVAL: a NULL array, n outside [1, 2^30], T outside [1, 2^31], a bad device.  SMC_ENOMEM: the device arrays of the call.
+ *
+ * The IBIS sampler over such rows is the same handle type, created with
+ *   smc_ibis_create_rows        smc_ibis_create with the row id of the particles: SMC_MODEL_LG1D (what smc_ibis_create makes) or
+ *                               SMC_MODEL_LG2D.  Every smc_ibis_* signature is as it is.  On a two-state handle
+ *                               smc_ibis_configure reads 15 raw_from / raw_const entries, smc_ibis_get gives x [n_theta][2] and
+ *                               S [n_theta][3], and smc_ibis_set_theta, _window, _window_ess, _commit, _filter, _rejuvenate,
+ *                               _permute, _resample run kalman2_step in place of the scalar step; smc_ibis_set_logw,
+ *                               _theta_moments, _get_moved are the same code for both.  Refused on a two-state handle with
+ *                               SMC_EINVAL, the handle unchanged (follow-ups): smc_ibis_set_flags with SMC_FLAG_NAN_MISSING,
+ *                               smc_ibis_summary, smc_ibis_set_summaries, smc_ibis_get_summaries, smc_ibis_smooth,
+ *                               smc_ibis_sample_paths. */
+#define SMC_MODEL_LG2D 16
+int smc_kalman2_log_likelihood(const double* raw /*[n][15]*/, int64_t n, const double* y, int64_t T, int predict_first, double* out /*[n][6]*/,
+                               int device);
+int smc_kalman2_smooth(const double* raw /*[n][15]*/, int64_t n, const double* y, int64_t T, int predict_first, double* xs /*[T][n][2]*/,
+                       double* Ps /*[T][n][3]*/, int device);
+int smc_host_kalman2_steps(const double* row /*[15]*/, const double* y, int64_t T, int predict_first, double* xf /*[T][2] or NULL*/,
+                           double* Sf /*[T][3] or NULL*/, double* lik /*[T] or NULL*/);
+int smc_host_kalman2_smooth(const double* row /*[15]*/, const double* y, int64_t T, int predict_first, double* xs /*[T][2]*/, double* Ps /*[T][3]*/);
+int smc_simulate_lg2(const double* row /*[15]*/, int64_t T, uint64_t seed, double* x /*[2][T] or NULL*/, double* y /*[T]*/);
+int smc_ibis_create_rows(int64_t n_theta, uint64_t seed, int device, int predict_first, int row_id, void* out);
 /* Summaries of an IBIS cloud, on the device (src/plotting_utils.jl:94-137: observation_dist, estimated_trend, quantile).  With
  * omega the normalised weights of logw and, per particle, ym = B x, vm = B^2 Sigma + R (ahead = 0) or the same after one
  * Kalman prediction x <- A x, Sigma <- A^2 Sigma + Q (ahead = 1, the one-step forecast the comment at :126-127 asks for):

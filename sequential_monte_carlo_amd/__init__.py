@@ -9,7 +9,7 @@ from .distributions import LogNormal, Normal, TruncatedNormal, Uniform, product_
 from .ibis import IBIS  # noqa: F401
 from .ibis import rts_quantile, rts_smoothed_paths, rts_smoothed_state  # noqa: F401
 from .kalman_filter import kalman_smoother, log_likelihood_kalman  # noqa: F401
-from .models import (UCSV, LinearModel, MarginalUCSV, StateSpaceModel, StochasticVolatility, UnivariateLinearGaussian,  # noqa: F401
+from .models import (UCSV, LinearModel, LinearModel2D, MarginalUCSV, MultivariateLinearGaussian, hodrick_prescott, StateSpaceModel, StochasticVolatility, UnivariateLinearGaussian,  # noqa: F401
                      simulate, unobserved_components, unobserved_components_stochastic_volatility)
 from .particles import (AffineGaussianProposal, OptimalProposal, ParticleGibbs, bootstrap_filter, bootstrap_filter_, forecast, log_likelihood, normalize,  # noqa: F401
                         optimal_proposal, particle_filter, particle_filter_, rb_smoother, resample, reweight, smoother, trend_moments)

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMC_LIB") or os.path.join(_HERE, "lib", "libsmchip.so")   # SMC_LIB: profiling builds
 
 MODEL_LG1D, MODEL_SV1D, MODEL_UCSV3D, MODEL_UCSV_RB = 1, 2, 3, 4
+MODEL_LG2D, LG2_NRAW = 16, 15   # a two-state linear row of the exact-Kalman side (no particle-filter family)
 FLAG_ANCESTORS, FLAG_NO_RESIDENT, FLAG_SYSTEMATIC, FLAG_NAN_MISSING, FLAG_CONDITIONAL = 1, 2, 4, 8, 16
 
 # every symbol include/smc_hip.h declares
@@ -45,6 +46,8 @@ EXPORTS = [
     "smc_set_reference", "smc_reference_from_paths", "smc_get_reference", "smc_host_conditional_slot", "smc_host_logobs",
     "smc_smooth_pairs", "smc_host_smooth_pairs",
     "smc_live_bytes",
+    "smc_kalman2_log_likelihood", "smc_kalman2_smooth", "smc_host_kalman2_steps", "smc_host_kalman2_smooth", "smc_simulate_lg2",
+    "smc_ibis_create_rows",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -243,6 +246,12 @@ def lib():
     L.smc_forecast.argtypes = [h, C.c_int64, C.c_uint64, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
     L.smc_forecast_cloud.argtypes = [h, C.c_int64, C.c_uint64, _dp, _dp]
     L.smc_host_forecast.argtypes = [C.c_int, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, _dp]
+    L.smc_kalman2_log_likelihood.argtypes = [_dp, C.c_int64, _dp, C.c_int64, C.c_int, _dp, C.c_int]
+    L.smc_kalman2_smooth.argtypes = [_dp, C.c_int64, _dp, C.c_int64, C.c_int, _dp, _dp, C.c_int]
+    L.smc_host_kalman2_steps.argtypes = [_dp, _dp, C.c_int64, C.c_int, _dp, _dp, _dp]
+    L.smc_host_kalman2_smooth.argtypes = [_dp, _dp, C.c_int64, C.c_int, _dp, _dp]
+    L.smc_simulate_lg2.argtypes = [_dp, C.c_int64, C.c_uint64, _dp, _dp]
+    L.smc_ibis_create_rows.argtypes = [C.c_int64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(h)]
     L.smc_last_error.restype = C.c_char_p
     L.smc_version.restype = C.c_char_p
     _lib = L
@@ -328,6 +337,51 @@ def kalman_smooth(raw, y, predict_first=False, device=0, missing=False):
     check(lib().smc_kalman_smooth_flags(_d(raw), raw.shape[0], _d(y), y.size, int(bool(predict_first)), _d(xs), _d(Ps), int(device),
                                         _kalman_flags(missing)))
     return xs, Ps
+
+
+def kalman2_log_likelihood(raw, y, predict_first=False, device=0):
+    """Batched exact Kalman filter of two-state rows [n][15] (smc_kalman2_log_likelihood): rows of (x1, x2, S11, S21, S22, logZ)."""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1, LG2_NRAW)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    out = np.zeros((raw.shape[0], 6))
+    check(lib().smc_kalman2_log_likelihood(_d(raw), raw.shape[0], _d(y), y.size, int(bool(predict_first)), _d(out), int(device)))
+    return out
+
+
+def kalman2_smooth(raw, y, predict_first=False, device=0):
+    """Batched exact RTS smoother of two-state rows (smc_kalman2_smooth): (xs [T][n][2], Ps [T][n][3], the lower triangle)."""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1, LG2_NRAW)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    xs, Ps = np.zeros((y.size, raw.shape[0], 2)), np.zeros((y.size, raw.shape[0], 3))
+    check(lib().smc_kalman2_smooth(_d(raw), raw.shape[0], _d(y), y.size, int(bool(predict_first)), _d(xs), _d(Ps), int(device)))
+    return xs, Ps
+
+
+def host_kalman2_steps(row, y, predict_first=False):
+    """(xf [T][2], Sf [T][3], lik [T]): the filtered record and the value of every Kalman step of ONE two-state row over y on the
+    host (smc_host_kalman2_steps; no GPU) - the loop every two-state kernel runs per lane"""
+    row = np.ascontiguousarray(row, dtype=np.float64).reshape(LG2_NRAW)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    xf, Sf, lik = np.zeros((y.size, 2)), np.zeros((y.size, 3)), np.zeros(y.size)
+    check(lib().smc_host_kalman2_steps(_d(row), _d(y), y.size, int(bool(predict_first)), _d(xf), _d(Sf), _d(lik)))
+    return xf, Sf, lik
+
+
+def host_kalman2_smooth(row, y, predict_first=False):
+    """(xs [T][2], Ps [T][3]) of ONE two-state row on the host (smc_host_kalman2_smooth; no GPU)"""
+    row = np.ascontiguousarray(row, dtype=np.float64).reshape(LG2_NRAW)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    xs, Ps = np.zeros((y.size, 2)), np.zeros((y.size, 3))
+    check(lib().smc_host_kalman2_smooth(_d(row), _d(y), y.size, int(bool(predict_first)), _d(xs), _d(Ps)))
+    return xs, Ps
+
+
+def simulate_lg2(row, T, seed):
+    """simulate(rng, model, T) for a two-state row -> (x [2][T], y [T]) (smc_simulate_lg2; host code)"""
+    row = np.ascontiguousarray(row, dtype=np.float64).reshape(LG2_NRAW)
+    x, y = np.zeros((2, int(T))), np.zeros(int(T))
+    check(lib().smc_simulate_lg2(_d(row), int(T), int(seed) & 0xFFFFFFFFFFFFFFFF, _d(x), _d(y)))
+    return x, y
 
 
 def device_math(which, a, b=None, device=0):
@@ -1210,18 +1264,24 @@ def host_ibis_sample_paths(rows, y, which, path_seed, predict_first=False, want_
 
 class IbisHandle:
     """The device half of the IBIS sampler (smc_ibis_*): M parameter particles with their exact Kalman state, resident on one
-    GPU.  d: parameter dimension; families / pars: the prior (distributions.py spec()); raw_from / raw_const: ThetaMap to LG1D rows."""
+    GPU.  d: parameter dimension; families / pars: the prior (distributions.py spec()); raw_from / raw_const: ThetaMap to LG1D rows.
+    row_id=MODEL_LG2D: two-state rows of 15 entries (smc_ibis_create_rows); x is then [M][2] and S [M][3], the lower triangle."""
 
-    def __init__(self, M, d, families, pars, raw_from, raw_const, seed=1, device=0, predict_first=False, flags=0):
+    def __init__(self, M, d, families, pars, raw_from, raw_const, seed=1, device=0, predict_first=False, flags=0, row_id=MODEL_LG1D):
         self._h = C.c_void_p()
         self.M, self.d = int(M), int(d)
         self.nseg = (self.M + OUTER_SEG - 1) // OUTER_SEG
-        check(lib().smc_ibis_create(self.M, int(seed), int(device), int(bool(predict_first)), C.byref(self._h)))
+        self.row_id = int(row_id)
+        self.nraw, self.nx, self.nS = (LG2_NRAW, 2, 3) if self.row_id == MODEL_LG2D else (6, 1, 1)
+        if self.row_id == MODEL_LG1D:                      # (a scalar handle makes the calls it made before)
+            check(lib().smc_ibis_create(self.M, int(seed), int(device), int(bool(predict_first)), C.byref(self._h)))
+        else:
+            check(lib().smc_ibis_create_rows(self.M, int(seed), int(device), int(bool(predict_first)), self.row_id, C.byref(self._h)))
         fam = np.ascontiguousarray(families, dtype=np.int32)
         par = np.ascontiguousarray(pars, dtype=np.float64).reshape(fam.size, PRIOR_NPAR)
         rf = np.ascontiguousarray(raw_from, dtype=np.int32)
         rc = np.ascontiguousarray(raw_const, dtype=np.float64)
-        assert fam.size == self.d and rf.size == rc.size == 6
+        assert fam.size == self.d and rf.size == rc.size == self.nraw
         check(lib().smc_ibis_configure(self._h, self.d, fam.ctypes.data_as(_i32p), _d(par), rf.ctypes.data_as(_i32p), _d(rc)))
         if flags:                                          # (an unflagged handle makes the calls it made before)
             self.set_flags(flags)
@@ -1320,9 +1380,9 @@ class IbisHandle:
         out = {}
         if theta:
             out["theta"] = np.zeros((self.M, self.d))
-        for name, want in (("x", x), ("S", S), ("logZ", logZ), ("logw", logw)):
+        for name, want, n in (("x", x, self.nx), ("S", S, self.nS), ("logZ", logZ, 1), ("logw", logw, 1)):
             if want:
-                out[name] = np.zeros(self.M)
+                out[name] = np.zeros(self.M) if n == 1 else np.zeros((self.M, n))
         check(lib().smc_ibis_get(self._h, _d(out.get("theta")), _d(out.get("x")), _d(out.get("S")), _d(out.get("logZ")), _d(out.get("logw"))))
         return out
 

@@ -19,9 +19,11 @@ struct smc_ibis_s {
     uint32_t flags = 0;             // smc_ibis_set_flags: 0 or SMC_FLAG_NAN_MISSING (a NaN observation is a missing Kalman step)
     hipStream_t stream = nullptr;
     IbisView v{};                   // views of the two sets below, as the kernels take them
-    DevBlock d_theta[2], d_raw[2], d_x[2], d_S[2], d_logZ[2], d_logw[2];   // double [M][MAX_DTHETA] | [M][IBIS_NRAW] | [M] each
+    int row_id = MODEL_LG1D;        // what a parameter particle filters: scalar LG1D rows (smc_ibis_create) or two-state MODEL_LG2D rows
+    DevBlock d_theta[2], d_raw[2], d_x[2], d_S[2], d_logZ[2], d_logw[2];   // double [M][MAX_DTHETA] | [M][nraw] | [M][nx] | [M][nS] | [M] each
     int cp = 0, cs = 0;             // current (theta, raw) set and current (x, S, logZ, logw) set
     PmmhSpec spec{};
+    Lg2Map map2{};                  // smc.model(theta) of a two-state handle (spec keeps the prior)
     bool configured = false, have_theta = false;
     int64_t t = 0;                  // observations committed so far
     int win_k = 0;                  // steps of the pending window (its end state sits in set cs ^ 1); 0: none
@@ -64,6 +66,16 @@ ibis_t as_ibis(void* p) {
     return (h && h->magic == 0x53494249u) ? h : nullptr;
 }
 unsigned grid_of(int64_t M) { return (unsigned)((M + IBIS_THREADS - 1) / IBIS_THREADS); }
+// a handle of two-state rows: its init / reset / window / rejuvenate / permute launches are the ibis2_launch_* of smc_kalman2.hip, and
+// a particle holds LG2_NRAW row entries, x [2] and the lower triangle S [3]; every other launch of this file serves it unchanged
+bool two_state(const smc_ibis_s* h) { return h->row_id == MODEL_LG2D; }
+size_t row_len(const smc_ibis_s* h) { return two_state(h) ? LG2_NRAW : IBIS_NRAW; }
+size_t x_len(const smc_ibis_s* h) { return two_state(h) ? 2 : 1; }
+size_t S_len(const smc_ibis_s* h) { return two_state(h) ? 3 : 1; }
+// what a two-state handle does not have (gaps, cloud summaries, the cloud's RTS smoother and its paths): SMC_EINVAL, handle unchanged
+int refuse_two_state(const char* who, const char* what) {
+    return fail(SMC_EINVAL, std::string(who) + ": " + what + " is not implemented for a handle of two-state rows (smc_ibis_create_rows with SMC_MODEL_LG2D)");
+}
 
 void release(ibis_t h) {   // (the blocks go with the handle)
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -116,8 +128,9 @@ int steps_in_place(ibis_t h, const double* y, int64_t steps) {
     int64_t done = 0;
     while (done < steps) {   // (the kernel's step count is an int)
         const int k = (int)(steps - done > (1 << 20) ? (1 << 20) : steps - done);
-        launch_window<false, false>(h, kalman_has_gap(h->flags, y + done, k), h->cs, h->d_y.as<double>() + done, k,
-                                    (h->t + done > 0 || h->predict_first) ? 1 : 0, nullptr, nullptr, nullptr, 0);
+        const int predict0 = (h->t + done > 0 || h->predict_first) ? 1 : 0;
+        if (two_state(h)) ibis2_launch_window(h->stream, h->v, h->cp, h->cs, h->cs, h->d_y.as<double>() + done, k, predict0, nullptr, nullptr);
+        else launch_window<false, false>(h, kalman_has_gap(h->flags, y + done, k), h->cs, h->d_y.as<double>() + done, k, predict0, nullptr, nullptr, nullptr, 0);
         HIPCHK(hipGetLastError());
         done += k;
     }
@@ -128,9 +141,14 @@ int steps_in_place(ibis_t h, const double* y, int64_t steps) {
 }  // namespace
 
 extern "C" int smc_ibis_create(int64_t n_theta, uint64_t seed, int device, int predict_first, void* out) {
+    return smc_ibis_create_rows(n_theta, seed, device, predict_first, MODEL_LG1D, out);
+}
+
+extern "C" int smc_ibis_create_rows(int64_t n_theta, uint64_t seed, int device, int predict_first, int row_id, void* out) {
     (void)seed;   // every random number of the device side is keyed by the move_seed of its call
     if (!out) return fail(SMC_EINVAL, "smc_ibis_create: NULL out");
     *(void**)out = nullptr;
+    if (row_id != MODEL_LG1D && row_id != MODEL_LG2D) return fail(SMC_EINVAL, "smc_ibis_create_rows: row_id is SMC_MODEL_LG1D or SMC_MODEL_LG2D");
     if (n_theta < 1 || n_theta > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_ibis_create: 1 <= n_theta <= 2^30");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(SMC_EHIP, "smc_ibis_create: no HIP device");
@@ -141,13 +159,14 @@ extern "C" int smc_ibis_create(int64_t n_theta, uint64_t seed, int device, int p
     h->device = device;
     h->predict_first = predict_first ? 1 : 0;
     h->v.M = n_theta;
+    h->row_id = row_id;
     const size_t M = (size_t)n_theta;
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     for (int b = 0; b < 2 && e == hipSuccess; ++b) {
         if (e == hipSuccess) e = h->d_theta[b].grow(M * MAX_DTHETA * 8);
-        if (e == hipSuccess) e = h->d_raw[b].grow(M * IBIS_NRAW * 8);
-        if (e == hipSuccess) e = h->d_x[b].grow(M * 8);
-        if (e == hipSuccess) e = h->d_S[b].grow(M * 8);
+        if (e == hipSuccess) e = h->d_raw[b].grow(M * row_len(h) * 8);
+        if (e == hipSuccess) e = h->d_x[b].grow(M * x_len(h) * 8);
+        if (e == hipSuccess) e = h->d_S[b].grow(M * S_len(h) * 8);
         if (e == hipSuccess) e = h->d_logZ[b].grow(M * 8);
         if (e == hipSuccess) e = h->d_logw[b].grow(M * 8);
         h->v.theta[b] = h->d_theta[b].as<double>(); h->v.raw[b] = h->d_raw[b].as<double>(); h->v.x[b] = h->d_x[b].as<double>();
@@ -193,13 +212,24 @@ extern "C" int smc_ibis_configure(void* hp, int d_theta, const int32_t* prior_fa
         sp.family[i] = prior_family[i];
         for (int k = 0; k < PRIOR_NPAR; ++k) sp.par[i][k] = prior_par[(size_t)i * PRIOR_NPAR + k];
     }
-    sp.nraw = IBIS_NRAW;
-    for (int k = 0; k < IBIS_NRAW; ++k) {
-        if (raw_from[k] >= d_theta) return fail(SMC_EINVAL, "smc_ibis_configure: raw_from index out of range");
-        sp.raw_from[k] = raw_from[k];
-        sp.raw_const[k] = raw_const[k];
+    Lg2Map map{};
+    if (two_state(h)) {       // LG2_NRAW entries: they do not fit the PmmhSpec and travel in the handle's Lg2Map
+        sp.nraw = 0;
+        for (int k = 0; k < LG2_NRAW; ++k) {
+            if (raw_from[k] >= d_theta) return fail(SMC_EINVAL, "smc_ibis_configure: raw_from index out of range");
+            map.raw_from[k] = raw_from[k];
+            map.raw_const[k] = raw_const[k];
+        }
+    } else {
+        sp.nraw = IBIS_NRAW;
+        for (int k = 0; k < IBIS_NRAW; ++k) {
+            if (raw_from[k] >= d_theta) return fail(SMC_EINVAL, "smc_ibis_configure: raw_from index out of range");
+            sp.raw_from[k] = raw_from[k];
+            sp.raw_const[k] = raw_const[k];
+        }
     }
     h->spec = sp;
+    h->map2 = map;
     h->configured = true;
     h->have_theta = false;
     h->win_k = 0;
@@ -218,7 +248,8 @@ extern "C" int smc_ibis_set_theta(void* hp, const double* theta) {
         for (int i = 0; i < d; ++i) pad[m * MAX_DTHETA + i] = theta[m * d + i];
     HIPCHK(hipMemcpyAsync(h->v.theta[h->cp], pad.data(), pad.size() * 8, hipMemcpyHostToDevice, h->stream));
 #define IBIS_CALL_INIT(D) launch_init<D>(h)
-    IBIS_BY_D(d, IBIS_CALL_INIT)
+    if (two_state(h)) ibis2_launch_init(h->stream, h->v, h->cp, h->cs, h->spec, h->map2);
+    else IBIS_BY_D(d, IBIS_CALL_INIT)
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_theta = true;
@@ -253,6 +284,9 @@ static int enqueue_window(ibis_t h, const char* who, const double* y, int k, boo
                            h->d_srow.as<double>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h->srow, h->d_srow.as<double>(), (size_t)k * IBIS_SUM_NOUT * 8, hipMemcpyDeviceToHost, h->stream));
+    } else if (two_state(h)) {
+        ibis2_launch_window(h->stream, h->v, h->cp, h->cs, h->cs ^ 1, h->d_y.as<double>(), k, predict0, lik ? h->d_lik.as<double>() : nullptr, h->d_rec.as<uint64_t>());
+        HIPCHK(hipGetLastError());
     } else {
         launch_window<true, false>(h, miss, h->cs ^ 1, h->d_y.as<double>(), k, predict0, lik ? h->d_lik.as<double>() : nullptr, h->d_rec.as<uint64_t>(), nullptr, 0);
         HIPCHK(hipGetLastError());
@@ -313,6 +347,7 @@ extern "C" int smc_ibis_window_ess(void* hp, const double* y, int k, double ess_
 extern "C" int smc_ibis_set_summaries(void* hp, int on, int ahead) {
     ibis_t h = as_ibis(hp);
     if (!h) return fail(SMC_EINVAL, "smc_ibis_set_summaries: not an IBIS handle");
+    if (two_state(h)) return refuse_two_state("smc_ibis_set_summaries", "the summary of the cloud");
     if (ahead != 0 && ahead != 1) return fail(SMC_EINVAL, "smc_ibis_set_summaries: ahead is 0 or 1");
     h->summ_on = on != 0;
     h->summ_ahead = ahead;
@@ -326,6 +361,7 @@ extern "C" int smc_ibis_set_flags(void* hp, uint32_t flags) {
     ibis_t h = as_ibis(hp);
     if (!h) return fail(SMC_EINVAL, "smc_ibis_set_flags: not an IBIS handle");
     if (flags & ~SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_ibis_set_flags: flags is 0 or SMC_FLAG_NAN_MISSING");
+    if (flags && two_state(h)) return refuse_two_state("smc_ibis_set_flags", "SMC_FLAG_NAN_MISSING (the missing Kalman step)");
     if (h->t != 0 || h->win_k > 0)
         return fail(SMC_ESTATE, "smc_ibis_set_flags: observations have been taken (or a window is pending): the flag is set at t = 0");
     h->flags = flags;
@@ -342,6 +378,7 @@ extern "C" int smc_ibis_get_flags(void* hp, uint32_t* flags) {
 extern "C" int smc_ibis_get_summaries(void* hp, int j, double* out) {
     ibis_t h = as_ibis(hp);
     if (!h || !out) return fail(SMC_EINVAL, "smc_ibis_get_summaries: bad argument");
+    if (two_state(h)) return refuse_two_state("smc_ibis_get_summaries", "the summary of the cloud");
     if (j < 0 || j > h->srow_k) return fail(SMC_ESTATE, "smc_ibis_get_summaries: the last window recorded fewer steps (is recording on?)");
     memcpy(out, h->srow, (size_t)j * IBIS_SUM_NOUT * 8);
     return SMC_OK;
@@ -350,6 +387,7 @@ extern "C" int smc_ibis_get_summaries(void* hp, int j, double* out) {
 extern "C" int smc_ibis_summary(void* hp, int ahead, double* out) {
     ibis_t h = as_ibis(hp);
     if (!h || !out) return fail(SMC_EINVAL, "smc_ibis_summary: bad argument");
+    if (two_state(h)) return refuse_two_state("smc_ibis_summary", "the summary of the cloud");
     if (ahead != 0 && ahead != 1) return fail(SMC_EINVAL, "smc_ibis_summary: ahead is 0 or 1");
     if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_summary: smc_ibis_set_theta has not been called");
     HIPCHK(hipSetDevice(h->device));
@@ -457,7 +495,8 @@ extern "C" int smc_ibis_filter(void* hp, const double* y, int64_t T) {
     if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_filter: smc_ibis_set_theta has not been called");
     HIPCHK(hipSetDevice(h->device));
     h->win_k = 0;
-    hipLaunchKernelGGL(k_ibis_reset, dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs);
+    if (two_state(h)) ibis2_launch_reset(h->stream, h->v, h->cp, h->cs);
+    else hipLaunchKernelGGL(k_ibis_reset, dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs);
     HIPCHK(hipGetLastError());
     h->t = 0;
     return steps_in_place(h, y, T);
@@ -473,7 +512,8 @@ extern "C" int smc_ibis_permute(void* hp, const int32_t* a) {
     HIPCHK(hipSetDevice(h->device));
     h->win_k = 0;
     HIPCHK(hipMemcpyAsync(h->d_a.as<int32_t>(), a, (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_ibis_permute, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->d_a.as<int32_t>());
+    if (two_state(h)) ibis2_launch_permute(h->stream, h->v, h->cp, h->cs, h->d_a.as<int32_t>());
+    else hipLaunchKernelGGL(k_ibis_permute, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->d_a.as<int32_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     h->cp ^= 1;
@@ -510,7 +550,11 @@ extern "C" int smc_ibis_rejuvenate(void* hp, const double* y, int64_t T, double 
     HIPCHK(hipMemsetAsync(h->d_count.as<unsigned long long>(), 0, 8, h->stream));
     const bool miss = kalman_has_gap(h->flags, y, T);
 #define IBIS_CALL_REJ(D) launch_rejuvenate<D>(h, miss, T, xi, chain, move_seed)
-    IBIS_BY_D(d, IBIS_CALL_REJ)
+    if (two_state(h))
+        ibis2_launch_rejuvenate(h->stream, h->v, h->cp, h->cs, h->spec, h->map2, h->d_y.as<double>(), T, h->predict_first, xi, h->d_chol.as<double>(),
+                                h->d_chol.as<double>() + MAX_DTHETA * MAX_DTHETA, chain, move_seed, h->d_moved.as<unsigned char>(),
+                                h->d_count.as<unsigned long long>());
+    else IBIS_BY_D(d, IBIS_CALL_REJ)
     HIPCHK(hipGetLastError());
     unsigned long long n = 0;
     HIPCHK(hipMemcpyAsync(&n, h->d_count.as<unsigned long long>(), 8, hipMemcpyDeviceToHost, h->stream));
@@ -579,7 +623,8 @@ extern "C" int smc_ibis_resample(void* hp, uint64_t seed, int32_t* a_out) {
                        h->d_skb.as<const uint32_t>(), h->d_K.as<const uint32_t>(), SH, (const uint64_t*)Dcum, nseg, h->d_cnt.as<int32_t>());
     launch_scan(h, IbisCount{h->d_cnt.as<int32_t>()}, M, tsum, h->d_q.as<uint64_t>());          // (the weights are spent: their array takes the scan of cnt)
     hipLaunchKernelGGL(k_ibis_rs_expand, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, M, h->d_q.as<const uint64_t>(), h->d_a.as<int32_t>());
-    hipLaunchKernelGGL(k_ibis_permute, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->d_a.as<int32_t>());
+    if (two_state(h)) ibis2_launch_permute(h->stream, h->v, h->cp, h->cs, h->d_a.as<int32_t>());
+    else hipLaunchKernelGGL(k_ibis_permute, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->d_a.as<int32_t>());
     HIPCHK(hipGetLastError());
     if (a_out) HIPCHK(hipMemcpyAsync(a_out, h->d_a.as<int32_t>(), (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -630,8 +675,8 @@ extern "C" int smc_ibis_get(void* hp, double* theta, double* x, double* S, doubl
         pad.resize(M * MAX_DTHETA);
         HIPCHK(hipMemcpyAsync(pad.data(), h->v.theta[h->cp], pad.size() * 8, hipMemcpyDeviceToHost, h->stream));
     }
-    if (x) HIPCHK(hipMemcpyAsync(x, h->v.x[h->cs], M * 8, hipMemcpyDeviceToHost, h->stream));
-    if (S) HIPCHK(hipMemcpyAsync(S, h->v.S[h->cs], M * 8, hipMemcpyDeviceToHost, h->stream));
+    if (x) HIPCHK(hipMemcpyAsync(x, h->v.x[h->cs], M * x_len(h) * 8, hipMemcpyDeviceToHost, h->stream));
+    if (S) HIPCHK(hipMemcpyAsync(S, h->v.S[h->cs], M * S_len(h) * 8, hipMemcpyDeviceToHost, h->stream));
     if (logZ) HIPCHK(hipMemcpyAsync(logZ, h->v.logZ[h->cs], M * 8, hipMemcpyDeviceToHost, h->stream));
     if (logw) HIPCHK(hipMemcpyAsync(logw, h->v.logw[h->cs], M * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -665,6 +710,7 @@ constexpr int64_t RTS_MAX_T = (int64_t)1 << 31;   // the step index is a 32-bit 
 extern "C" int smc_ibis_smooth(void* hp, const double* y, int64_t T, double* out, double* xs, double* Ps) {
     ibis_t h = as_ibis(hp);
     if (!h || !y || !out) return fail(SMC_EINVAL, "smc_ibis_smooth: bad argument");
+    if (two_state(h)) return refuse_two_state("smc_ibis_smooth", "the RTS smoother of the cloud (smc_kalman2_smooth smooths rows)");
     if (T < 1 || T > RTS_MAX_T) return fail(SMC_EINVAL, "smc_ibis_smooth: 1 <= T <= 2^31");
     if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_smooth: smc_ibis_set_theta has not been called");
     if (h->win_k > 0) return fail(SMC_ESTATE, "smc_ibis_smooth: a window is pending (smc_ibis_commit first)");
@@ -703,6 +749,7 @@ extern "C" int smc_ibis_sample_paths(void* hp, const double* y, int64_t T, int64
                                      double* paths) {
     ibis_t h = as_ibis(hp);
     if (!h || !y || !which || !paths) return fail(SMC_EINVAL, "smc_ibis_sample_paths: bad argument");
+    if (two_state(h)) return refuse_two_state("smc_ibis_sample_paths", "backward sampling of paths");
     if (T < 1 || T > RTS_MAX_T) return fail(SMC_EINVAL, "smc_ibis_sample_paths: 1 <= T <= 2^31");
     if (Mp < 1 || Mp > ((int64_t)1 << 30)) return fail(SMC_EINVAL, "smc_ibis_sample_paths: 1 <= Mp <= 2^30");
     if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_sample_paths: smc_ibis_set_theta has not been called");

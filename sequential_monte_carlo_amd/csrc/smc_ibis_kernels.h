@@ -11,53 +11,9 @@
 // Random numbers: pmmh_propose / pmmh_log_uniform keyed by (move_seed, stream = index of the parameter particle, chain
 // position) and nothing else, so no result depends on the launch geometry.  Every store is a plain vector store.
 #pragma once
-#include "smc_kernels.h"
+#include "smc_ibis_view.h"
 
 namespace smc {
-
-constexpr int IBIS_OSEG = 8;              // SMC_OUTER_SEG: entries per segment record of the outer reweight
-constexpr int IBIS_NRAW = 6;              // LinearModel row (A, B, Q, R, x0, sigma0)
-constexpr int IBIS_THREADS = 64;          // one wave per workgroup: a cloud of a few hundred particles still spreads over the CUs
-constexpr int IBIS_MAX_WINDOW = 64;
-
-struct IbisView {
-    int64_t M;
-    double* theta[2];     // [M][MAX_DTHETA]   (theta, raw) and (x, S, logZ, logw) are double-buffered separately:
-    double* raw[2];       // [M][IBIS_NRAW]     a window leaves its end state in the other (x, S, logZ, logw) set,
-    double* x[2];         // [M]                a permutation gathers both
-    double* S[2];         // [M]
-    double* logZ[2];      // [M]
-    double* logw[2];      // [M]
-};
-
-// reductions over the 8 consecutive lanes of a segment (lane & ~7 .. lane | 7), result in every one of them: quad_perm
-// [1,0,3,2], quad_perm [2,3,0,1] and row_half_mirror (lane i <-> 7 - i of each half row) as DPP moves
-template <int CTRL>
-__device__ __forceinline__ uint32_t seg8_move(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-template <int CTRL>
-__device__ __forceinline__ uint64_t seg8_move64(uint64_t v) {
-    return ((uint64_t)seg8_move<CTRL>((uint32_t)(v >> 32)) << 32) | seg8_move<CTRL>((uint32_t)v);
-}
-__device__ __forceinline__ int seg8_max(int v) {
-    int o = (int)seg8_move<0xB1>((uint32_t)v); v = o > v ? o : v;
-    o = (int)seg8_move<0x4E>((uint32_t)v); v = o > v ? o : v;
-    o = (int)seg8_move<0x141>((uint32_t)v); v = o > v ? o : v;
-    return v;
-}
-__device__ __forceinline__ uint64_t seg8_sum(uint64_t v) {
-    v += seg8_move64<0xB1>(v);
-    v += seg8_move64<0x4E>(v);
-    v += seg8_move64<0x141>(v);
-    return v;
-}
-__device__ __forceinline__ U128 seg8_sum128(U128 v) {
-    v = add128(v, U128{seg8_move64<0xB1>(v.lo), seg8_move64<0xB1>(v.hi)});
-    v = add128(v, U128{seg8_move64<0x4E>(v.lo), seg8_move64<0x4E>(v.hi)});
-    v = add128(v, U128{seg8_move64<0x141>(v.lo), seg8_move64<0x141>(v.hi)});
-    return v;
-}
 
 // smc.model(theta) as a gather without a run-time index into registers: row[k] = theta[raw_from[k]] or raw_const[k]
 template <int D>
@@ -263,22 +219,7 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_window(IbisView v, int cp
         logZ = logZ + l;
         if (RECORD) {
             if (lik && valid) lik[(size_t)j * (size_t)v.M + (size_t)m] = l;
-            const bool alive = valid && lw_alive(logw);
-            double kd = 0.0;
-            const double p = sp_exp_parts(alive ? logw : 0.0, kd);
-            const int ki = alive ? (int)kd : -(1 << 30);
-            const int kb = seg8_max(ki);
-            const uint64_t q = alive ? fix_weight_i(p, ki - kb, FIX_BITS) : 0;
-            const uint64_t Ssum = seg8_sum(q);
-            const U128 s2 = seg8_sum128(sq128(q));
-            if (valid && (threadIdx.x & (IBIS_OSEG - 1)) == 0) {
-                uint64_t* r = rec + ((size_t)j * (size_t)nseg + (size_t)(m / IBIS_OSEG)) * 4;
-                const bool live = kb != -(1 << 30);
-                r[0] = d2bits(live ? (double)kb : -inf());
-                r[1] = live ? Ssum : 0;
-                r[2] = live ? s2.hi : 0;
-                r[3] = live ? s2.lo : 0;
-            }
+            ibis_outer_record(logw, valid, m, rec + (size_t)j * (size_t)nseg * 4);
         }
         if (SUMM)
             ibis_chunk_record(A, B, Q, R, x, S, logw, valid, ahead, part + (size_t)j * IBIS_SUM_NCOL * (size_t)gridDim.x, gridDim.x,

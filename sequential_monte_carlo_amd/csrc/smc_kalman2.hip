@@ -1,0 +1,140 @@
+// smc_kalman2.hip -- C ABI of the two-state exact Kalman side (include/smc_hip.h "two-state linear models"): the batched filter
+// and RTS smoother on the device (smc_kalman2_kernels.h), their host twins, and the simulation of such a row.
+#include "smc_host.h"
+#include "smc_kalman2_kernels.h"
+
+#include <string>
+#include <vector>
+
+using namespace smc;
+
+namespace {
+constexpr int64_t K2_MAX_N = (int64_t)1 << 30, K2_MAX_T = (int64_t)1 << 31;
+size_t k2_up256(size_t b) { return (b + 255) & ~(size_t)255; }
+unsigned k2_grid(int64_t n) { return (unsigned)((n + KALMAN2_THREADS - 1) / KALMAN2_THREADS); }
+
+// the checks every device call of this file shares, and the call's one allocation (freed when the call returns)
+int k2_begin(const char* who, int64_t n, int64_t T, int device, DevBlock& blk, size_t bytes) {
+    if (n < 1 || n > K2_MAX_N || T < 1 || T > K2_MAX_T) return fail(SMC_EINVAL, std::string(who) + ": 1 <= n <= 2^30, 1 <= T <= 2^31");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(SMC_EHIP, std::string(who) + ": no HIP device");
+    if (device < 0 || device >= ndev) return fail(SMC_EINVAL, std::string(who) + ": bad device");
+    HIPCHK(hipSetDevice(device));
+    const hipError_t e = blk.grow(bytes);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SMC_ENOMEM : SMC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+    return SMC_OK;
+}
+}  // namespace
+
+// ---- the launches of an IBIS handle of two-state rows (declared in smc_ibis_view.h; the handle: smc_ibis.hip) ------------------
+#define K2_BY_D(d, CALL)                                                                                        \
+    switch (d) {                                                                                                \
+    case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;             \
+    case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; default: CALL(8); break;            \
+    }
+namespace smc {
+void ibis2_launch_init(hipStream_t st, const IbisView& v, int cp, int cs, const PmmhSpec& s, const Lg2Map& map) {
+#define K2_CALL_INIT(D) hipLaunchKernelGGL((k_ibis2_init<D>), dim3(k2_grid(v.M)), dim3(IBIS_THREADS), 0, st, v, cp, cs, map)
+    K2_BY_D(s.d, K2_CALL_INIT)
+}
+void ibis2_launch_reset(hipStream_t st, const IbisView& v, int cp, int cs) {
+    hipLaunchKernelGGL(k_ibis2_reset, dim3(k2_grid(v.M)), dim3(IBIS_THREADS), 0, st, v, cp, cs);
+}
+void ibis2_launch_window(hipStream_t st, const IbisView& v, int cp, int cs, int dst, const double* d_y, int k, int predict0, double* lik,
+                         uint64_t* rec) {
+    if (rec) hipLaunchKernelGGL((k_ibis2_window<true>), dim3(k2_grid(v.M)), dim3(IBIS_THREADS), 0, st, v, cp, cs, dst, d_y, k, predict0, lik, rec);
+    else hipLaunchKernelGGL((k_ibis2_window<false>), dim3(k2_grid(v.M)), dim3(IBIS_THREADS), 0, st, v, cp, cs, dst, d_y, k, predict0, lik, rec);
+}
+void ibis2_launch_rejuvenate(hipStream_t st, const IbisView& v, int cp, int cs, const PmmhSpec& s, const Lg2Map& map, const double* d_y, int64_t T,
+                             int predict_first, double xi, const double* chol, const double* sq, int chain, uint64_t move_seed,
+                             unsigned char* moved, unsigned long long* n_moved) {
+#define K2_CALL_REJ(D)                                                                                                                  \
+    hipLaunchKernelGGL((k_ibis2_rejuvenate<D>), dim3(k2_grid(v.M)), dim3(IBIS_THREADS), 0, st, v, cp, cs, s, map, d_y, T, predict_first, xi, \
+                       chol, sq, chain, move_seed, moved, n_moved)
+    K2_BY_D(s.d, K2_CALL_REJ)
+}
+void ibis2_launch_permute(hipStream_t st, const IbisView& v, int cp, int cs, const int32_t* a) {
+    hipLaunchKernelGGL(k_ibis2_permute, dim3(k2_grid(v.M)), dim3(IBIS_THREADS), 0, st, v, cp, cs, a);
+}
+}  // namespace smc
+
+extern "C" int smc_kalman2_log_likelihood(const double* raw, int64_t n, const double* y, int64_t T, int predict_first, double* out, int device) {
+    if (!raw || !y || !out) return fail(SMC_EINVAL, "smc_kalman2_log_likelihood: bad argument");
+    const size_t sn = n > 0 ? (size_t)n : 0, sT = T > 0 ? (size_t)T : 0;
+    const size_t b_y = k2_up256(sT * 8), b_raw = k2_up256(sn * LG2_NRAW * 8), b_out = sn * 6 * 8;
+    DevBlock blk;
+    if (const int rc = k2_begin("smc_kalman2_log_likelihood", n, T, device, blk, b_y + b_raw + b_out)) return rc;
+    char* const base = blk.as<char>();
+    double *d_y = (double*)base, *d_raw = (double*)(base + b_y), *d_out = (double*)(base + b_y + b_raw);
+    hipStream_t st = nullptr;   // the default stream: the call owns nothing that outlives it
+    HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_raw, raw, sn * LG2_NRAW * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_kalman2_loglik, dim3(k2_grid(n)), dim3(KALMAN2_THREADS), 0, st, (const double*)d_raw, n, (const double*)d_y, T,
+                       predict_first ? 1 : 0, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+
+extern "C" int smc_kalman2_smooth(const double* raw, int64_t n, const double* y, int64_t T, int predict_first, double* xs, double* Ps, int device) {
+    if (!raw || !y || !xs || !Ps) return fail(SMC_EINVAL, "smc_kalman2_smooth: bad argument");
+    const size_t sn = n > 0 ? (size_t)n : 0, sT = T > 0 ? (size_t)T : 0;
+    const size_t b_y = k2_up256(sT * 8), b_raw = k2_up256(sn * LG2_NRAW * 8), b_xs = k2_up256(sT * sn * 2 * 8), b_Ps = sT * sn * 3 * 8;
+    DevBlock blk;
+    if (const int rc = k2_begin("smc_kalman2_smooth", n, T, device, blk, b_y + b_raw + b_xs + b_Ps)) return rc;
+    char* const base = blk.as<char>();
+    double *d_y = (double*)base, *d_raw = (double*)(base + b_y), *d_xs = (double*)(base + b_y + b_raw), *d_Ps = (double*)(base + b_y + b_raw + b_xs);
+    hipStream_t st = nullptr;
+    HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_raw, raw, sn * LG2_NRAW * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_kalman2_smooth, dim3(k2_grid(n)), dim3(KALMAN2_THREADS), 0, st, (const double*)d_raw, n, (const double*)d_y, T,
+                       predict_first ? 1 : 0, d_xs, d_Ps);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(xs, d_xs, sT * sn * 2 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(Ps, d_Ps, b_Ps, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+
+// The step loop of ONE row on the host (no GPU): the filtered record and the value of every step.  Every device array of the
+// two-state calls has the bits of a composition of this call.
+extern "C" int smc_host_kalman2_steps(const double* row, const double* y, int64_t T, int predict_first, double* xf, double* Sf, double* lik) {
+    if (!row || !y || T < 1) return fail(SMC_EINVAL, "smc_host_kalman2_steps: bad argument");
+    double x1 = row[LG2_X1], x2 = row[LG2_X2], S11 = row[LG2_S11], S21 = row[LG2_S21], S22 = row[LG2_S22];
+    for (int64_t t = 0; t < T; ++t) {
+        const double l = kalman2_step(row, t > 0 || predict_first != 0, y[t], x1, x2, S11, S21, S22);
+        if (xf) { xf[2 * t] = x1; xf[2 * t + 1] = x2; }
+        if (Sf) { Sf[3 * t] = S11; Sf[3 * t + 1] = S21; Sf[3 * t + 2] = S22; }
+        if (lik) lik[t] = l;
+    }
+    return SMC_OK;
+}
+
+// The backward walk of ONE row on the host: the filter's record, then rts2_step from the last period down
+extern "C" int smc_host_kalman2_smooth(const double* row, const double* y, int64_t T, int predict_first, double* xs, double* Ps) {
+    if (!row || !y || !xs || !Ps || T < 1) return fail(SMC_EINVAL, "smc_host_kalman2_smooth: bad argument");
+    if (const int rc = smc_host_kalman2_steps(row, y, T, predict_first, xs, Ps, nullptr)) return rc;
+    double a1 = xs[2 * (T - 1)], a2 = xs[2 * (T - 1) + 1], P11 = Ps[3 * (T - 1)], P21 = Ps[3 * (T - 1) + 1], P22 = Ps[3 * (T - 1) + 2];
+    for (int64_t t = T - 2; t >= 0; --t) {
+        rts2_step(row, xs[2 * t], xs[2 * t + 1], Ps[3 * t], Ps[3 * t + 1], Ps[3 * t + 2], a1, a2, P11, P21, P22);
+        xs[2 * t] = a1; xs[2 * t + 1] = a2;
+        Ps[3 * t] = P11; Ps[3 * t + 1] = P21; Ps[3 * t + 2] = P22;
+    }
+    return SMC_OK;
+}
+
+// simulate(rng, model, T) for a two-state row, on the host: x [2][T] (or NULL), y [T]
+extern "C" int smc_simulate_lg2(const double* row, int64_t T, uint64_t seed, double* x, double* y) {
+    if (!row || !y || T < 1 || T > K2_MAX_T) return fail(SMC_EINVAL, "smc_simulate_lg2: bad argument");
+    double x1 = 0.0, x2 = 0.0;
+    for (int64_t t = 0; t < T; ++t) {
+        double z0, z1, e, spare;
+        box_muller(draw(seed, 0u, SIM_STREAM, (uint32_t)t, SLOT_NORMAL0), z0, spare);
+        box_muller(draw(seed, 0u, SIM_STREAM, (uint32_t)t, SLOT_NORMAL0 + 1), z1, spare);
+        box_muller(draw(seed, 0u, SIM_STREAM, (uint32_t)t, SLOT_OBS), e, spare);
+        lg2_sim_step(row, t == 0, z0, z1, e, x1, x2, y[t]);
+        if (x) { x[t] = x1; x[(size_t)T + (size_t)t] = x2; }
+    }
+    return SMC_OK;
+}

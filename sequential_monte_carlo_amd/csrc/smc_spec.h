@@ -873,6 +873,106 @@ SMC_HD double kalman_step_gaps(double A, double B, double Q, double R, bool pred
     return kalman_step(A, B, Q, R, predict, y, x, S);
 }
 
+// ---- the exact Kalman filter of a TWO-STATE linear model with a scalar observation (src/kalman_filter.jl:3-27, d = 2) ---------
+// The models of MultivariateLinearGaussian / hodrick_prescott (state_space_models.jl:137-202) with a 2 x 2 transition:
+//   x_t ~ N(A x_{t-1}, Q),  y_t ~ N(B x_t, R),  x_1 ~ N(x0, Sigma0)
+// as a row of LG2_NRAW = 15 doubles
+//   (A11,A12,A21,A22, B1,B2, Q11,Q21,Q22, R, x01,x02, S11,S21,S22)
+// Q and Sigma0 are symmetric, stored as their lower triangle, and may be singular (hodrick_prescott: Q = [1/lambda 0; 0 0]).
+// The row's id is MODEL_LG2D: a row of the exact-Kalman side only.  It is no particle-filter family (a singular Q has no
+// transition density): smc_create, smc_simulate and every model table refuse it.
+// One step, every product of two sums written as fma(a, b, c * d) with the SECOND term of the sum in the fma:
+//   predict (left out when `predict` is false: the first step of a filter that starts at x_1 ~ N(x0, Sigma0)):
+//     x- = A x;  M = A Sigma (four entries);  P = M A' + Q, its lower triangle (P11, P21, P22)
+//   k = P B' (two entries);  s = B k + R;  e = y - B x-;  inv = 1 / s (the step's ONE division);  g = k inv
+//   x = x- + g e;  Sigma = P - k g' (lower triangle);  value = -1/2 (log 2 pi + log s + (e inv) e)
+// A covariance is carried as its lower triangle, so it is symmetric by construction.  s that is not a positive finite number
+// does what kalman_step does with it: sp_log and the division make the value and the state NaN or infinite, logZ is poisoned from
+// there on, nothing is tested and nothing faults.
+constexpr int MODEL_LG2D = 16;
+constexpr int LG2_NRAW = 15;
+enum { LG2_A11 = 0, LG2_A12, LG2_A21, LG2_A22, LG2_B1, LG2_B2, LG2_Q11, LG2_Q21, LG2_Q22, LG2_R, LG2_X1, LG2_X2, LG2_S11, LG2_S21, LG2_S22 };
+// x <- A x, M = A S, P = M A' + Q: the prediction, shared by the filter's step and the backward recursion
+SMC_HD void kalman2_predict(const double* r, double& x1, double& x2, double S11, double S21, double S22, double* M /*[4]*/, double& P11,
+                            double& P21, double& P22) {
+    const double A11 = r[LG2_A11], A12 = r[LG2_A12], A21 = r[LG2_A21], A22 = r[LG2_A22];
+    const double p1 = fma(A12, x2, A11 * x1), p2 = fma(A22, x2, A21 * x1);
+    x1 = p1; x2 = p2;
+    M[0] = fma(A12, S21, A11 * S11); M[1] = fma(A12, S22, A11 * S21);
+    M[2] = fma(A22, S21, A21 * S11); M[3] = fma(A22, S22, A21 * S21);
+    P11 = fma(M[1], A12, M[0] * A11) + r[LG2_Q11];
+    P21 = fma(M[3], A12, M[2] * A11) + r[LG2_Q21];
+    P22 = fma(M[3], A22, M[2] * A21) + r[LG2_Q22];
+}
+SMC_HD double kalman2_step(const double* r /*[LG2_NRAW], entries 0..9 are read*/, bool predict, double y, double& x1, double& x2, double& S11,
+                           double& S21, double& S22) {
+    double P11 = S11, P21 = S21, P22 = S22;
+    if (predict) { double M[4]; kalman2_predict(r, x1, x2, S11, S21, S22, M, P11, P21, P22); }
+    const double B1 = r[LG2_B1], B2 = r[LG2_B2];
+    const double k1 = fma(P21, B2, P11 * B1), k2 = fma(P22, B2, P21 * B1);
+    const double s = fma(B2, k2, B1 * k1) + r[LG2_R], e = y - fma(B2, x2, B1 * x1);
+    const double inv = 1.0 / s, g1 = k1 * inv, g2 = k2 * inv;
+    x1 = fma(g1, e, x1);
+    x2 = fma(g2, e, x2);
+    S11 = fma(-k1, g1, P11);
+    S21 = fma(-k2, g1, P21);
+    S22 = fma(-k2, g2, P22);
+    return -0.5 * (0x1.d67f1c864beb5p+0 + sp_log(s) + (e * inv) * e);
+}
+// The RTS backward recursion over the filtered record (xf_t, Sf_t) of kalman2_step: (xs, Ps) of step t+1 in, of step t out.
+//   x-, M, P = kalman2_predict(xf_t, Sf_t)        the prediction of step t+1, as the filter formed it
+//   det = P11 P22 - P21 P21;  G = Sf_t A' P^-1 = M' adj(P) / det        (adjugate and determinant, ONE division)
+//   xs_t = xf_t + G (xs_{t+1} - x-)
+//   Ps_t = Sf_t + (G D) G',  D = Ps_{t+1} - P      lower triangle only: symmetric by construction
+// RULE for a predicted covariance that cannot be inverted - det <= 0, or det not finite: there is no smoothed state; xs_t and
+// Ps_t are NaN, and so is everything before t (the recursion carries the NaN backwards).  The last period, xs = xf, is always
+// defined.  It cannot happen (in exact arithmetic) when P is positive definite: A invertible with Sigma0 positive definite
+// (hodrick_prescott: det A = 1), or Q positive definite.  It does happen for a row whose second state is identically zero
+// (A = diag(a, 0), Q = diag(q, 0), Sigma0 = diag(s0, 0)): P = diag(p, 0) at every step.
+SMC_HD void rts2_step(const double* r, double xf1, double xf2, double F11, double F21, double F22, double& xs1, double& xs2, double& Ps11,
+                      double& Ps21, double& Ps22) {
+    double M[4], P11, P21, P22, p1 = xf1, p2 = xf2;
+    kalman2_predict(r, p1, p2, F11, F21, F22, M, P11, P21, P22);
+    const double det = fma(P11, P22, -(P21 * P21));
+    const bool ok = det > 0.0 && det - det == 0.0;
+    const double idet = 1.0 / det;
+    const double G11 = fma(M[0], P22, -(M[2] * P21)) * idet, G12 = fma(M[2], P11, -(M[0] * P21)) * idet;
+    const double G21 = fma(M[1], P22, -(M[3] * P21)) * idet, G22 = fma(M[3], P11, -(M[1] * P21)) * idet;
+    const double d1 = xs1 - p1, d2 = xs2 - p2;
+    const double D11 = Ps11 - P11, D21 = Ps21 - P21, D22 = Ps22 - P22;
+    const double E11 = fma(G12, D21, G11 * D11), E12 = fma(G12, D22, G11 * D21);
+    const double E21 = fma(G22, D21, G21 * D11), E22 = fma(G22, D22, G21 * D21);
+    const double nan = bits2d(0x7ff8000000000000ULL);
+    xs1 = ok ? fma(G12, d2, fma(G11, d1, xf1)) : nan;
+    xs2 = ok ? fma(G22, d2, fma(G21, d1, xf2)) : nan;
+    Ps11 = ok ? F11 + fma(E12, G12, E11 * G11) : nan;
+    Ps21 = ok ? F21 + fma(E22, G12, E21 * G11) : nan;
+    Ps22 = ok ? F22 + fma(E22, G22, E21 * G21) : nan;
+}
+// Simulation of such a row (simulate, state_space_models.jl:11-26).  The lower factor L of a covariance C that may be singular:
+//   l11 = sqrt(C11);  l21 = C11 > 0 ? C21 / l11 : 0;  l22 = sqrt(max(C22 - l21 l21, 0))
+// x_1 = x0 + L(Sigma0) z, x_t = A x_{t-1} + L(Q) z, y_t = B x_t + sqrt(R) e with z = (z0 of slot SLOT_NORMAL0, z0 of slot
+// SLOT_NORMAL0 + 1) and e = z0 of slot SLOT_OBS of draw(seed, 0, SIM_STREAM, t, slot): the slots smc_simulate uses.
+SMC_HD void lg2_factor(double C11, double C21, double C22, double& l11, double& l21, double& l22) {
+    l11 = sqrt(C11);
+    l21 = C11 > 0.0 ? C21 / l11 : 0.0;
+    const double v = fma(-l21, l21, C22);
+    l22 = sqrt(v > 0.0 ? v : 0.0);
+}
+SMC_HD void lg2_sim_step(const double* r, bool first, double z0, double z1, double e, double& x1, double& x2, double& y) {
+    double l11, l21, l22, m1, m2;
+    if (first) {
+        lg2_factor(r[LG2_S11], r[LG2_S21], r[LG2_S22], l11, l21, l22);
+        m1 = r[LG2_X1]; m2 = r[LG2_X2];
+    } else {
+        lg2_factor(r[LG2_Q11], r[LG2_Q21], r[LG2_Q22], l11, l21, l22);
+        m1 = fma(r[LG2_A12], x2, r[LG2_A11] * x1); m2 = fma(r[LG2_A22], x2, r[LG2_A21] * x1);
+    }
+    x1 = fma(l11, z0, m1);
+    x2 = fma(l22, z1, fma(l21, z0, m2));
+    y = fma(sqrt(r[LG2_R]), e, fma(r[LG2_B2], x2, r[LG2_B1] * x1));
+}
+
 // ---- summaries of an IBIS cloud (src/plotting_utils.jl:94-137: observation_dist, estimated_trend, quantile) -----------------
 // Particle m: row (A, B, Q, R), filtered state (x, S), outer log-weight logw.  With omega_m the normalised weight of logw:
 //   ahead = 0:  ym = B x,        vm = (B B) S + R                         (:104-105)

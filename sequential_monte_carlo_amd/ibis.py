@@ -1,5 +1,8 @@
 """Host mirror of src/ibis.jl: the IBIS sampler - Chopin's SMC² with the exact scalar Kalman filter as the inner "filter" - for
-the univariate LinearModel (UnivariateLinearGaussian, unobserved_components).
+the univariate LinearModel (UnivariateLinearGaussian, unobserved_components), and with the exact two-state filter of
+kalman_filter.jl:3-27 for MultivariateLinearGaussian / hodrick_prescott rows (theta_map=ThetaMap(MODEL_LG2D, raw_from[15],
+raw_const[15])): the same sampler calls, ib.x [M][2] and ib.Sigma [M][2][2]; gaps, the cloud summaries and the rts_*
+calls are scalar-only.
 
     IBIS(M, model, prior, chain, ess_threshold, min_ar=-1.0)        ibis.jl:26-58
     smc2 / smc2_step / smc2_run, resample_, rejuvenate_, expected_parameters, density_tempered   (smc_samplers.py dispatches here)
@@ -44,6 +47,16 @@ import numpy as np
 from . import _lib
 
 
+_SCALAR_ONLY = ("%s is implemented for the scalar LinearModel only, not for a sampler over two-state rows "
+                "(MultivariateLinearGaussian, hodrick_prescott): gaps, cloud summaries and smoothed paths of two-state rows are not "
+                "built yet")
+
+
+def _scalar_only(ibis, what):
+    if getattr(ibis, "two_state", False):
+        raise ValueError(_SCALAR_ONLY % what)
+
+
 class IBIS:
     """IBIS(M, model, prior, chain, ess_threshold, min_ar=-1.0)   ibis.jl:3-58.  M parameter particles; theta is drawn exactly
     as SMC draws it (the same cloud for the same seed).  Arrays (theta, x, Sigma, logZ, logw, omega) are read from the device
@@ -52,9 +65,15 @@ class IBIS:
     def __init__(self, M, model, prior, chain, ess_threshold, min_ar=-1.0, seed=1, theta_map=None, device=0, predict_first=False,
                  device_moves=False, missing=False):
         self.M, self.model, self.prior, self.chain = int(M), model, prior, int(chain)
-        if theta_map is None or getattr(theta_map, "model_id", None) != _lib.MODEL_LG1D:
-            raise TypeError("IBIS needs theta_map=ThetaMap(LG1D rows): the Kalman filter inside runs on the GPU, which cannot call "
-                            "the `model` closure, and it is exact for the univariate LinearModel only")
+        if theta_map is None or getattr(theta_map, "model_id", None) not in (_lib.MODEL_LG1D, _lib.MODEL_LG2D):
+            raise TypeError("IBIS needs theta_map=ThetaMap(LG1D rows) or ThetaMap(MODEL_LG2D, two-state rows of 15 entries): the Kalman "
+                            "filter inside runs on the GPU, which cannot call the `model` closure, and it is exact for linear "
+                            "Gaussian models only")
+        self.two_state = theta_map.model_id == _lib.MODEL_LG2D
+        if theta_map.raw_from.size != (_lib.LG2_NRAW if self.two_state else 6):
+            raise ValueError("theta_map needs %d row entries for this family" % (_lib.LG2_NRAW if self.two_state else 6))
+        if self.two_state and missing:
+            raise ValueError(_SCALAR_ONLY % "missing=True")
         spec = prior.spec() if hasattr(prior, "spec") else None
         if spec is None:
             raise TypeError("IBIS needs a prior of the enumerated families (Uniform, Normal, TruncatedNormal, LogNormal or their "
@@ -90,7 +109,8 @@ class IBIS:
             fam, par = self.prior_spec
             self._h = _lib.IbisHandle(self.M, self._theta0.shape[1], fam, par, self.theta_map.raw_from, self.theta_map.raw_const,
                                       seed=self.seed, device=self.device, predict_first=self.predict_first,
-                                      flags=_lib.FLAG_NAN_MISSING if self.missing else 0)
+                                      flags=_lib.FLAG_NAN_MISSING if self.missing else 0,
+                                      row_id=_lib.MODEL_LG2D if self.two_state else _lib.MODEL_LG1D)
             self._h.set_theta(self._theta0)
         return self._h
 
@@ -109,8 +129,11 @@ class IBIS:
             if name == "theta":
                 return self._theta0.copy()
             rows = self.theta_map.rows(self._theta0)
+            if self.two_state:
+                return {"x": rows[:, 10:12].copy(), "S": _full2(rows[:, 12:15])}.get(name, np.zeros(self.M))
             return {"x": rows[:, 4].copy(), "S": rows[:, 5].copy()}.get(name, np.zeros(self.M))
-        return self._h.get(**{name: True})[name]
+        out = self._h.get(**{name: True})[name]
+        return _full2(out) if self.two_state and name == "S" else out      # two-state: x [M][2], Sigma [M][2][2]
 
     @property
     def accepted(self):
@@ -149,6 +172,7 @@ class IBIS:
         if summaries is None or summaries is False:
             self._summ = None
         else:
+            _scalar_only(self, "summaries=")
             if ahead not in (0, 1):
                 raise ValueError("ahead is 0 (the filtered observation) or 1 (the one-step forecast)")
             self._summ = {"p": None if summaries is True else [float(v) for v in np.atleast_1d(summaries)], "ahead": int(ahead)}
@@ -157,6 +181,12 @@ class IBIS:
     def __repr__(self):
         w = self.omega
         return "ess     = %.3f\nmean(theta) = %s" % (self.ess, np.array2string((self.theta * w[:, None]).sum(axis=0)))
+
+
+def _full2(S):
+    """[M][3] lower triangles (S11, S21, S22) -> [M][2][2]"""
+    S = np.asarray(S)
+    return np.stack([np.stack([S[:, 0], S[:, 1]], axis=-1), np.stack([S[:, 1], S[:, 2]], axis=-1)], axis=-2)
 
 
 def _window(ibis, y, ess_min, t=None):
@@ -186,6 +216,7 @@ def _window(ibis, y, ess_min, t=None):
 def _summary(ibis, ahead=0):
     """(y, Sigma, between, xbar, Sbar, between_x, K, D): smc_ibis_summary on the resident cloud; before the first sampler call
     the same specification on the host (smc_host_ibis_summary) over the initial cloud - no device call"""
+    _scalar_only(ibis, "observation_dist / estimated_trend / quantile / filtered_state")
     if ahead not in (0, 1):
         raise ValueError("ahead is 0 (the filtered observation) or 1 (the one-step forecast)")
     if ibis._h is None:
@@ -244,6 +275,7 @@ _RTS_COLUMNS = ("y", "Sigma", "between", "xbar", "Sbar", "between_x")
 
 def _rts_rows(ibis, y):
     """out [T][8] of smc_ibis_smooth on the resident cloud; before the first sampler call the host twin over the initial cloud"""
+    _scalar_only(ibis, "rts_smoothed_state / rts_quantile")
     y = np.ascontiguousarray(y, dtype=np.float64).ravel()
     if y.size < 1:
         raise ValueError("y must hold at least one observation")
@@ -282,6 +314,7 @@ def rts_smoothed_paths(ibis, y, M, seed=None):
     exactly as smoothed_paths draws them; particles with omega = 0 are never drawn), and every path is drawn exactly by backward
     sampling under its particle's row (smc_ibis_sample_paths, Philox seed + 2).  seed: default derived from the sampler's seed;
     the sampler's own rng and state are not touched."""
+    _scalar_only(ibis, "rts_smoothed_paths")
     y = np.ascontiguousarray(y, dtype=np.float64).ravel()
     M = int(M)
     if M < 1:

@@ -93,9 +93,83 @@ def unobserved_components_stochastic_volatility(*, x0, gamma_eps, gamma_eta, log
     return (MarginalUCSV if marginal else UCSV)((gamma_eps, gamma_eta), x0, (log_sigma_eps, log_sigma_eta))
 
 
+_KALMAN_ONLY = ("%s: a two-state linear model (MultivariateLinearGaussian, hodrick_prescott) is not a particle-filter family - its "
+                "transition covariance may be singular, so it has no transition density; run it through the exact Kalman "
+                "filter: log_likelihood_kalman / kalman_smoother, and IBIS for its parameters")
+
+
+class LinearModel2D(StateSpaceModel):
+    """LinearModel with a 2 x 2 transition and a scalar observation (ssm.jl:137-185): x[t] ~ N(A x[t-1], Q), y[t] ~ N(B x[t], R),
+    x[1] ~ N(X0, Sigma0).  Q and Sigma0 are symmetric positive SEMI-definite (hodrick_prescott's Q is singular).  A row of the
+    exact-Kalman side only: log_likelihood_kalman, kalman_smoother, IBIS, simulate.  raw() is the row of 15 entries
+    (A11,A12,A21,A22, B1,B2, Q11,Q21,Q22, R, x01,x02, S11,S21,S22), the covariances as their lower triangle."""
+    model_id = _lib.MODEL_LG2D
+    dim = 2
+
+    def __init__(self, A, B, Q, R, X0=None, Sigma0=None):
+        A = np.asarray(A, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] != A.shape[1]:
+            raise ValueError("A must be a square matrix")
+        d = A.shape[0]
+        if d != 2:
+            raise ValueError("state dimension %d: only two-state models (A 2 x 2) are implemented" % d)
+        B = np.asarray(B, dtype=np.float64)
+        if B.ndim == 1:
+            B = B[None, :]
+        if B.ndim != 2 or B.shape[1] != d:
+            raise ValueError("B must have one column per state")
+        R = np.asarray(R, dtype=np.float64)
+        if B.shape[0] != 1 or R.size != 1:
+            raise ValueError("observation dimension %d: only a scalar observation (B 1 x 2, R a number) is implemented" % max(B.shape[0], R.shape[0] if R.ndim else 1))
+        Q = np.asarray(Q, dtype=np.float64)
+        X0 = np.zeros(d) if X0 is None else np.asarray(X0, dtype=np.float64).ravel()
+        Sigma0 = np.eye(d) if Sigma0 is None else np.asarray(Sigma0, dtype=np.float64)
+        if Q.shape != (d, d) or Sigma0.shape != (d, d) or X0.shape != (d,):
+            raise ValueError("Q and Sigma0 must be 2 x 2 and X0 of length 2")
+        for name, v in (("A", A), ("B", B), ("Q", Q), ("R", R), ("X0", X0), ("Sigma0", Sigma0)):
+            if not np.all(np.isfinite(v)):
+                raise ValueError("%s has an entry that is not finite" % name)
+        for name, C in (("Q", Q), ("Sigma0", Sigma0)):
+            if C[0, 1] != C[1, 0]:
+                raise ValueError("%s is not symmetric" % name)
+            # positive semi-definite: both diagonal entries and the determinant non-negative (the determinant up to its rounding)
+            if C[0, 0] < 0 or C[1, 1] < 0 or C[0, 0] * C[1, 1] - C[1, 0] * C[1, 0] < -4 * np.finfo(float).eps * C[0, 0] * C[1, 1]:
+                raise ValueError("%s is not positive semi-definite" % name)
+        self.R = float(R.ravel()[0])
+        if not self.R > 0:
+            raise ValueError("R is a variance and must be positive")
+        self.A, self.B, self.Q, self.X0, self.Sigma0 = A.copy(), B.copy(), Q.copy(), X0.copy(), Sigma0.copy()
+
+    def raw(self):
+        A, B, Q, S = self.A, self.B, self.Q, self.Sigma0
+        return [A[0, 0], A[0, 1], A[1, 0], A[1, 1], B[0, 0], B[0, 1], Q[0, 0], Q[1, 0], Q[1, 1], self.R, self.X0[0], self.X0[1],
+                S[0, 0], S[1, 0], S[1, 1]]
+
+
+def MultivariateLinearGaussian(*, A, B, Q, R, X0=None, Sigma0=None):
+    """MultivariateLinearGaussian(;A,B,Q,R,X0=zeros,Σ0=I)   (ssm.jl:137-153), for two states and a scalar observation"""
+    return LinearModel2D(A, B, Q, R, X0, Sigma0)
+
+
+def hodrick_prescott(*, lam, y, init_cov=1000.0):
+    """hodrick_prescott(;λ,y,init_cov=1000.0)   (ssm.jl:193-202): x[t] ~ N(2 x[t-1] - x[t-2], 1/λ), y[t] ~ N(x[t], 1).  The
+    smoothed first state, kalman_smoother(y, model)[0][:, 0], is the Hodrick-Prescott trend of y."""
+    y = np.asarray(y, dtype=np.float64).ravel()
+    if y.size < 2:
+        raise ValueError("hodrick_prescott needs y[0] and y[1] for the initial state")
+    lam = float(lam)
+    if not lam > 0:
+        raise ValueError("lam must be positive")
+    return MultivariateLinearGaussian(A=[[2.0, -1.0], [1.0, 0.0]], B=[[1.0, 0.0]], Q=[[1 / lam, 0.0], [0.0, 0.0]], R=[1.0],
+                                      X0=[3 * y[0] - 2 * y[1], 2 * y[0] - y[1]], Sigma0=float(init_cov) * np.eye(2))
+
+
 def simulate(model, T, seed=1998):
     """simulate(rng, model, T) -> (x, y)   (ssm.jl:11-26).  x is [T] for scalar states, [T, d] otherwise.
     Host code (no GPU): the spec's Philox / Box-Muller stream keyed by `seed`."""
+    if isinstance(model, LinearModel2D):
+        x, y = _lib.simulate_lg2(model.raw(), int(T), int(seed))
+        return x.T.copy(), y
     x, y = _lib.simulate(model.model_id, model.raw(), int(T), int(seed))    # (MarginalUCSV: UCSV's states, [T, 3])
     return (x[0] if model.dim == 1 else x.T.copy()), y
 
@@ -104,6 +178,8 @@ def params_matrix(models):
     """[n_theta][n_raw] parameter rows of a list of models of one family."""
     if isinstance(models, StateSpaceModel):
         models = [models]
+    if any(isinstance(m, LinearModel2D) for m in models):
+        raise TypeError(_KALMAN_ONLY % "params_matrix")
     ids = {m.model_id for m in models}
     if len(ids) != 1:
         raise ValueError("all models of a batch must belong to one family")

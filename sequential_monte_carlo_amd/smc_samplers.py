@@ -193,6 +193,9 @@ class SMC:
         moves rejuvenate! onto the device.  raw_fn (optional): vectorised shortcut for `model`: maps an [m, d_theta]
         array to (model_id, [m, n_raw] parameter rows) without building m model objects per evaluation."""
         self.N, self.M, self.model, self.prior, self.chain = int(N), int(M), model, prior, int(chain)
+        if theta_map is not None and getattr(theta_map, "model_id", None) == _lib.MODEL_LG2D:
+            from .models import _KALMAN_ONLY
+            raise TypeError(_KALMAN_ONLY % "SMC")
         self.theta_map = theta_map
         if raw_fn is None and theta_map is not None:
             def raw_fn(th, _t=theta_map):
