@@ -47,6 +47,9 @@ extern "C" {
                                  * the cloud by the transition and weighs nothing.  Without the flag a NaN kills its step. */
 #define SMC_FLAG_CONDITIONAL 16u /* OPT-IN: the conditional particle filter ("the conditional particle filter" below): one slot of every
                                  * step is pinned to a reference trajectory.  Without the flag nothing changes. */
+#define SMC_FLAG_ANCESTOR_SAMPLING 32u /* OPT-IN, with SMC_FLAG_CONDITIONAL only (else SMC_EINVAL): particle Gibbs with ancestor sampling
+                                 * ("ancestor sampling" below).  Implies SMC_FLAG_ANCESTORS (smc_get_flags reports both); the record
+                                 * keeps the ancestor vectors.  The steps are those of a handle with CONDITIONAL | ANCESTORS, bit for bit. */
 
 typedef struct smc_filter_s* smc_handle;
 
@@ -859,6 +862,39 @@ int smc_get_reference(smc_handle h, double* xref /*[T][d][n_theta]*/, int64_t* T
 /* the slot rule and the log-weight of a reference row on the host, no GPU (LG1D, SV1D, UCSV3D) */
 int smc_host_conditional_slot(uint64_t seed, uint32_t stream, uint32_t t, int64_t n_x, int64_t* k);
 int smc_host_logobs(int model_id, const double* raw, const double* x /*[d]*/, double y, double* out);
+
+/* ---- ancestor sampling: particle Gibbs without the backward walk (Lindsten, Jordan and Schoen 2014) -----------------------------
+ * Backward simulation walks the record from the last step to the first, every step waiting for the one behind it.  A handle created
+ * with SMC_FLAG_CONDITIONAL | SMC_FLAG_ANCESTOR_SAMPLING draws its next reference without that chain (csrc/smc_spec.h "ancestor
+ * sampling"): at every step t >= 1 the pinned particle redraws its ancestor J_t from the weights proportional to
+ * w_{t-1}^l f(xref[t] | x_{t-1}^l) - one step of backward simulation with xref[t] as its target, the same integers - and the new
+ * path is the ancestor lineage of ONE particle drawn from the last weights, followed through the recorded ancestor vectors, with
+ * J_t in the place of the retained slot's ancestor.  The reference is fixed while the draws are made, so they are independent
+ * given the record: ONE launch over (t, filter), then one thread per filter for the T lookups and the gather.  It leaves
+ * p(x_1:T | y_1:T, theta) invariant for any n_x >= 2, as smc_sample_paths + smc_reference_from_paths do.
+ *   the record         smc_history_begin on such a handle also arms an ancestor plane int32 [T_cap][n_theta][n_x]; every smc_step
+ *                      appends the ancestor vector it leaves (what smc_get_state gives), row 0 reads -1
+ *   smc_history_get_ancestors   row t of the plane.  smc_history_put_ancestors overwrites it (the planted cases of the tests); an
+ *                      entry outside [0, n_x) is SMC_EINVAL.  Both: SMC_ESTATE on a handle without the flag or without an armed
+ *                      record, SMC_EINVAL for t outside the record
+ *   smc_ancestor_sweep the sweep over the handle's record, under its current filter seed (smc_reseed) and stream ids, with the
+ *                      parameter rows the device holds: J [T][n_theta] the ancestor draws (J[0] = -1), idx [T][n_theta] the
+ *                      particles the new path passes through, *kept the number of dead filters (every last weight 0: idx = -1
+ *                      at every step, the reference kept); any may be NULL.  idx[T-1] is idx[T-1][th][0] of
+ *                      smc_sample_paths(h, 1, path_seed) on a record without a collapsed step.  The new reference:
+ *                      smc_get_reference.  It reads the parameter rows back first (a wait for the steps before it, as in
+ *                      smc_sample_paths) and then does not wait for its own two launches unless J, idx or kept is asked for.
+ *                      SMC_ESTATE, nothing changed: a handle without the flag, no armed record, no reference, a record whose
+ *                      length is not the reference's.  SMC_EINVAL: a transition scale that is not a positive finite number
+ *   smc_host_ancestor_sweep  the same specification for ONE filter on the host (no GPU), the same bits: a [T][n] the ancestor
+ *                      vectors (row 0 is not read; an entry of a later row outside [0, n): SMC_EINVAL), xref [T][d] the reference
+ *                      the steps ran with, the filter seed and stream id -> J [T], idx [T], xref_out [T][d] */
+int smc_history_get_ancestors(smc_handle h, int64_t t, int32_t* a /*[n_theta][n_x]*/);
+int smc_history_put_ancestors(smc_handle h, int64_t t, const int32_t* a /*[n_theta][n_x]*/);
+int smc_ancestor_sweep(smc_handle h, uint64_t path_seed, int32_t* J /*[T][n_theta] or NULL*/, int32_t* idx /*[T][n_theta] or NULL*/, int64_t* kept /*or NULL*/);
+int smc_host_ancestor_sweep(int model_id, const double* raw, int64_t T, int64_t n, const double* x /*[T][d][n]*/, const double* w /*[T][n]*/,
+                            const int32_t* a /*[T][n]*/, const double* xref /*[T][d]*/, uint64_t seed, uint64_t path_seed, uint32_t stream,
+                            int32_t* J /*[T]*/, int32_t* idx /*[T]*/, double* xref_out /*[T][d]*/);
 
 /* ---- Rao-Blackwellised backward simulation: smoothing the marginal UCSV filter (Lindsten et al. 2016) ---------------------------
  * SMC_MODEL_UCSV_RB carries the Kalman mean and variance of the trend inside every particle, and those two rows are functions of

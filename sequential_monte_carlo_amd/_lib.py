@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("SMC_LIB") or os.path.join(_HERE, "lib", "libsmchip.so
 MODEL_LG1D, MODEL_SV1D, MODEL_UCSV3D, MODEL_UCSV_RB = 1, 2, 3, 4
 MODEL_LG2D, LG2_NRAW = 16, 15   # a two-state linear row of the exact-Kalman side (no particle-filter family)
 FLAG_ANCESTORS, FLAG_NO_RESIDENT, FLAG_SYSTEMATIC, FLAG_NAN_MISSING, FLAG_CONDITIONAL = 1, 2, 4, 8, 16
+FLAG_ANCESTOR_SAMPLING = 32   # with FLAG_CONDITIONAL: the record keeps the ancestors and ancestor_sweep draws the next reference
 
 # every symbol include/smc_hip.h declares
 EXPORTS = [
@@ -48,6 +49,7 @@ EXPORTS = [
     "smc_live_bytes",
     "smc_kalman2_log_likelihood", "smc_kalman2_smooth", "smc_host_kalman2_steps", "smc_host_kalman2_smooth", "smc_simulate_lg2",
     "smc_ibis_create_rows",
+    "smc_history_get_ancestors", "smc_history_put_ancestors", "smc_ancestor_sweep", "smc_host_ancestor_sweep",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -145,6 +147,10 @@ def lib():
     L.smc_reference_from_paths.argtypes = [h, C.c_int64, C.POINTER(C.c_int64)]
     L.smc_get_reference.argtypes = [h, _dp, C.POINTER(C.c_int64)]
     L.smc_host_conditional_slot.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int64, C.POINTER(C.c_int64)]
+    L.smc_history_get_ancestors.argtypes = [h, C.c_int64, _i32p]
+    L.smc_history_put_ancestors.argtypes = [h, C.c_int64, _i32p]
+    L.smc_ancestor_sweep.argtypes = [h, C.c_uint64, _i32p, _i32p, C.POINTER(C.c_int64)]
+    L.smc_host_ancestor_sweep.argtypes = [C.c_int, _dp, C.c_int64, C.c_int64, _dp, _dp, _i32p, _dp, C.c_uint64, C.c_uint64, C.c_uint32, _i32p, _i32p, _dp]
     L.smc_host_logobs.argtypes = [C.c_int, _dp, _dp, C.c_double, _dp]
     L.smc_host_filter_steps.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int64, _dp, _dp]
     L.smc_device_filter_steps.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int64, _dp, _dp, C.c_int]
@@ -727,7 +733,7 @@ class Handle:
         seg_, nseg, d, res = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         check(lib().smc_get_geometry(self._h, C.byref(seg_), C.byref(nseg), C.byref(d), C.byref(res)))
         self.seg, self.nseg, self.d, self.resident = seg_.value, nseg.value, d.value, bool(res.value)
-        self.flags = flags
+        self.flags = flags | (FLAG_ANCESTORS if flags & FLAG_ANCESTOR_SAMPLING else 0)   # (the library's own rule: smc_get_flags)
 
     @property
     def missing(self):
@@ -764,6 +770,38 @@ class Handle:
         kept = C.c_int64()
         check(lib().smc_reference_from_paths(self._h, int(p), C.byref(kept)))
         return kept.value
+
+    @property
+    def ancestor_sampling(self):
+        """the handle draws its next reference by ancestor sampling (FLAG_ANCESTOR_SAMPLING, read back from the library)"""
+        f = C.c_uint32()
+        check(lib().smc_get_flags(self._h, C.byref(f)))
+        return bool(f.value & FLAG_ANCESTOR_SAMPLING)
+
+    def history_get_ancestors(self, t):
+        """the ancestor vector [n_theta][n_x] (int32) of recorded step t of an ancestor-sampling handle: what state() gave after
+        that step; row 0 reads -1 (smc_history_get_ancestors)"""
+        a = np.zeros((self.n_theta, self.n_x), dtype=np.int32)
+        check(lib().smc_history_get_ancestors(self._h, int(t), a.ctypes.data_as(_i32p)))
+        return a
+
+    def history_put_ancestors(self, t, a):
+        """overwrite the ancestor vector of recorded step t (smc_history_put_ancestors): the planted cases of the tests"""
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        if a.shape != (self.n_theta, self.n_x):
+            raise ValueError("a must be [n_theta][n_x]")
+        check(lib().smc_history_put_ancestors(self._h, int(t), a.ctypes.data_as(_i32p)))
+
+    def ancestor_sweep(self, path_seed):
+        """the ancestor-sampling sweep over the record (smc_ancestor_sweep): the new reference replaces the old one on the device
+        (get_reference); returns (J [T][n_theta] the ancestor draws, idx [T][n_theta] the particles the new path passes through,
+        both int32, and the number of dead filters that kept their reference)"""
+        T = self.history_len()
+        J = np.zeros((T, self.n_theta), dtype=np.int32)
+        idx = np.zeros((T, self.n_theta), dtype=np.int32)
+        kept = C.c_int64()
+        check(lib().smc_ancestor_sweep(self._h, int(path_seed), J.ctypes.data_as(_i32p), idx.ctypes.data_as(_i32p), C.byref(kept)))
+        return J, idx, kept.value
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1181,6 +1219,22 @@ def host_sample_paths(model_id, raw, x, w, M, seed, stream=0, want_x=True):
     check(lib().smc_host_sample_paths(int(model_id), _d(raw), T, n, _d(x), _d(w), int(M), int(seed), int(stream),
                                       idx.ctypes.data_as(_i32p), _d(xs)))
     return idx, xs
+
+
+def host_ancestor_sweep(model_id, raw, x, w, a, xref, seed, path_seed, stream=0):
+    """the ancestor-sampling sweep of ONE filter by the specification on the host (smc_host_ancestor_sweep; no GPU): x [T][d][n],
+    w [T][n], a [T][n] int32 (row 0 is not read), xref [T][d] -> (J [T] int32, idx [T] int32, xref_out [T][d])"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    d = lib().smc_model_dim(int(model_id))
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    T, n = w.shape
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(T, max(d, 1), n)
+    a = np.ascontiguousarray(a, dtype=np.int32).reshape(T, n)
+    xref = np.ascontiguousarray(xref, dtype=np.float64).reshape(T, max(d, 1))
+    J, idx, out = np.zeros(T, dtype=np.int32), np.zeros(T, dtype=np.int32), np.zeros((T, max(d, 1)))
+    check(lib().smc_host_ancestor_sweep(int(model_id), _d(raw), T, n, _d(x), _d(w), a.ctypes.data_as(_i32p), _d(xref), int(seed), int(path_seed),
+                                        int(stream), J.ctypes.data_as(_i32p), idx.ctypes.data_as(_i32p), _d(out)))
+    return J, idx, out
 
 
 def host_transition_logpdf(model_id, raw, xp, x):

@@ -261,6 +261,11 @@ extern "C" int smc_create(int model_id, int64_t n_theta, int64_t n_x, int seg, u
     const int64_t nseg = (n_x + seg - 1) / seg;
     if (nseg > MAX_NSEG) return fail(SMC_EINVAL, "smc_create: more than 16384 segments; use a larger seg");
     if (n_x > ((int64_t)1 << 31)) return fail(SMC_EINVAL, "smc_create: n_x > 2^31");
+    if (flags & SMC_FLAG_ANCESTOR_SAMPLING) {   // ancestor sampling (include/smc_hip.h): a mode of the conditional filter, over recorded ancestors
+        if (!(flags & SMC_FLAG_CONDITIONAL))
+            return fail(SMC_EINVAL, "smc_create: SMC_FLAG_ANCESTOR_SAMPLING without SMC_FLAG_CONDITIONAL (it redraws the ancestors of a reference trajectory)");
+        flags |= SMC_FLAG_ANCESTORS;
+    }
     if (flags & SMC_FLAG_CONDITIONAL) {   // the conditional particle filter (include/smc_hip.h): what it does not cover
         if (flags & SMC_FLAG_SYSTEMATIC)
             return fail(SMC_EINVAL, "smc_create: SMC_FLAG_CONDITIONAL with SMC_FLAG_SYSTEMATIC (conditional systematic resampling is another algorithm)");

@@ -1,7 +1,8 @@
 // smc_capi_cond.hip -- the reference trajectory of a conditional handle (SMC_FLAG_CONDITIONAL; include/smc_hip.h "the conditional
 // particle filter"): smc_set_reference, smc_get_reference and smc_reference_from_paths, the device gather of one backward-simulated
 // path out of the record into the reference's own buffer.  The conditional step itself: smc_kernels.h (COND), launched by do_init /
-// do_step (smc_capi.hip).  Specification: smc_spec.h "the conditional particle filter".
+// do_step (smc_capi.hip).  Specification: smc_spec.h "the conditional particle filter".  Also smc_ancestor_sweep, the sweep of a
+// handle with SMC_FLAG_ANCESTOR_SAMPLING (smc_spec.h "ancestor sampling"): its refusals and results; its launches live with the record.
 #include "smc_host.h"
 
 #include <vector>
@@ -89,4 +90,31 @@ extern "C" int smc_reference_from_paths(smc_handle h, int64_t p, int64_t* kept) 
     HIPCHK(hipGetLastError());
     if (kept) *kept = nkept;
     return SMC_OK;   // no wait: the next sweep's launches are ordered behind the gather on the handle's stream
+}
+
+// ---- ancestor sampling (include/smc_hip.h "ancestor sampling"): the refusals and the results; the launches: smc_capi_smooth.hip ------
+extern "C" int smc_ancestor_sweep(smc_handle h, uint64_t path_seed, int32_t* J, int32_t* idx, int64_t* kept) {
+    if (!h) return fail(SMC_EINVAL, "smc_ancestor_sweep: NULL handle");
+    if (!ancestor_sampling(h)) return fail(SMC_ESTATE, "smc_ancestor_sweep: the handle was not created with SMC_FLAG_ANCESTOR_SAMPLING");
+    if (!h->cond.d_xref) return fail(SMC_ESTATE, "smc_ancestor_sweep: the handle has no reference (smc_set_reference)");
+    if (!h->hist.armed || !h->hist.d_a || h->hist.len < 1)
+        return fail(SMC_ESTATE, "smc_ancestor_sweep: nothing is recorded (smc_history_begin, then smc_init / smc_step)");
+    if (h->hist.len != h->cond.T)
+        return fail(SMC_ESTATE, "smc_ancestor_sweep: " + std::to_string(h->hist.len) + " steps are recorded and the reference has " + std::to_string(h->cond.T) +
+                                    " (the sweep wants the whole run over the reference)");
+    const int32_t *d_J = nullptr, *d_idx = nullptr;
+    const int* d_dead = nullptr;
+    const int rc = ancestor_sweep_enqueue(h, path_seed, &d_J, &d_idx, &d_dead);
+    if (rc || (!J && !idx && !kept)) return rc;   // nothing asked for: no wait, the next sweep's launches are ordered behind these
+    const size_t nt = (size_t)h->v.ntheta, words = (size_t)h->hist.len * nt;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (J) HIPCHK(hipMemcpy(J, d_J, words * 4, hipMemcpyDeviceToHost));
+    if (idx) HIPCHK(hipMemcpy(idx, d_idx, words * 4, hipMemcpyDeviceToHost));
+    if (kept) {
+        std::vector<int> dead(nt);
+        HIPCHK(hipMemcpy(dead.data(), d_dead, nt * sizeof(int), hipMemcpyDeviceToHost));
+        *kept = 0;
+        for (size_t m = 0; m < nt; ++m) *kept += dead[m] != 0;
+    }
+    return SMC_OK;
 }

@@ -3,12 +3,15 @@
 // smc_smooth_kernels.h.  smc_sample_paths and smc_rb_sample_paths (MODEL_UCSV_RB): backward simulation, ONE walk over the record
 // (backward_walk: the refusals, the plan of the block, the uploads, the dead scan and the loop over the steps, smc_path_kernels.h)
 // that each of the two entry points wraps with the tail of its plan and with what follows the walk (smc_rb_kernels.h).
+// The ancestor plane of the record of an SMC_FLAG_ANCESTOR_SAMPLING handle (smc_history_get_ancestors / _put_ancestors) and the two
+// launches of smc_ancestor_sweep over it (ancestor_sweep_enqueue, smc_anc_kernels.h; the entry point: smc_capi_cond.hip).
 // Specification: smc_spec.h "the smoother", "backward simulation"; the host twins (smc_host_smooth, smc_host_sample_paths,
 // smc_host_rb_sample_paths) live in smc_util.hip.
 #include "smc_host.h"
 #include "smc_smooth_kernels.h"
 #include "smc_path_kernels.h"
 #include "smc_rb_kernels.h"
+#include "smc_anc_kernels.h"
 
 #include <cstring>
 #include <vector>
@@ -30,14 +33,17 @@ extern "C" int smc_history_begin(smc_handle h, int64_t T_cap) {
     HIPCHK(hipSetDevice(h->device));
     const size_t nw = cloud_words(h), per_step = nw * ((size_t)h->d + 1);
     if (per_step > ((size_t)1 << 60) / 8 / (size_t)T_cap) return fail(SMC_ENOMEM, "smc_history_begin: a record of that many bytes cannot be allocated");
+    // an ancestor-sampling handle: the ancestor plane int32 [T_cap][n_theta][n] behind the weights, in the same allocation
+    const size_t anc_bytes = ancestor_sampling(h) ? nw * (size_t)T_cap * 4 : 0;
+    const size_t bytes = per_step * (size_t)T_cap * 8 + anc_bytes;
     // the new block first: a failed allocation leaves the handle as it was.  Armed before: the new record replaces the old one,
     // which the stream may still read
-    const size_t bytes = per_step * (size_t)T_cap * 8;
     if (h->hist.rec && bytes > h->hist.rec.bytes()) HIPCHK(hipStreamSynchronize(h->stream));
     const hipError_t e = h->hist.rec.grow_keep(bytes);
     if (e != hipSuccess) return fail(SMC_ENOMEM, std::string("smc_history_begin: hipMalloc of the record: ") + hipGetErrorString(e));
     h->hist.d_x = h->hist.rec.as<double>();
     h->hist.d_w = h->hist.d_x + nw * (size_t)h->d * (size_t)T_cap;
+    h->hist.d_a = anc_bytes ? (int32_t*)(h->hist.d_w + nw * (size_t)T_cap) : nullptr;
     h->hist.cap = T_cap;
     h->hist.len = 0;
     h->hist.walk_M = 0;
@@ -67,6 +73,11 @@ int history_append(smc_handle h) {
     HIPCHK(hipMemcpy2DAsync(h->hist.d_x + t * nw * (size_t)h->d, (size_t)v.n * 8, v.x[h->cur], (size_t)v.npad * 8, (size_t)v.n * 8,
                             (size_t)h->d * v.ntheta, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(enqueue_dense_weights(h, h->hist.d_w + t * nw));
+    if (h->hist.d_a) {   // the ancestor vector of this step; the first step has none: -1
+        int32_t* a_t = h->hist.d_a + t * nw;
+        if (t == 0) HIPCHK(hipMemsetAsync(a_t, 0xFF, nw * 4, h->stream));
+        else HIPCHK(hipMemcpy2DAsync(a_t, (size_t)v.n * 4, v.anc, (size_t)v.npad * 4, (size_t)v.n * 4, (size_t)v.ntheta, hipMemcpyDeviceToDevice, h->stream));
+    }
     h->hist.len += 1;
     return SMC_OK;
 }
@@ -93,6 +104,40 @@ extern "C" int smc_history_put(smc_handle h, int64_t t, const double* x, const d
     const size_t nw = cloud_words(h);
     if (x) HIPCHK(hipMemcpy(h->hist.d_x + (size_t)t * nw * (size_t)h->d, x, nw * (size_t)h->d * 8, hipMemcpyHostToDevice));
     if (w) HIPCHK(hipMemcpy(h->hist.d_w + (size_t)t * nw, w, nw * 8, hipMemcpyHostToDevice));
+    return SMC_OK;
+}
+
+// the ancestor plane of the record (SMC_FLAG_ANCESTOR_SAMPLING): row t as smc_get_state gave the ancestors after step t
+static int need_ancestor_plane(smc_handle h, const char* who, int64_t t) {
+    if (!h) return fail(SMC_EINVAL, std::string(who) + ": NULL handle");
+    if (!ancestor_sampling(h)) return fail(SMC_ESTATE, std::string(who) + ": the handle was not created with SMC_FLAG_ANCESTOR_SAMPLING");
+    if (!h->hist.armed || !h->hist.d_a) return fail(SMC_ESTATE, std::string(who) + ": the handle does not record (smc_history_begin)");
+    if (t < 0 || t >= h->hist.len) return fail(SMC_EINVAL, std::string(who) + ": step out of range");
+    return SMC_OK;
+}
+
+extern "C" int smc_history_get_ancestors(smc_handle h, int64_t t, int32_t* a) {
+    const int rc = need_ancestor_plane(h, "smc_history_get_ancestors", t);
+    if (rc) return rc;
+    if (!a) return fail(SMC_EINVAL, "smc_history_get_ancestors: NULL argument");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t nw = cloud_words(h);
+    HIPCHK(hipMemcpy(a, h->hist.d_a + (size_t)t * nw, nw * 4, hipMemcpyDeviceToHost));
+    return SMC_OK;
+}
+
+extern "C" int smc_history_put_ancestors(smc_handle h, int64_t t, const int32_t* a) {
+    const int rc = need_ancestor_plane(h, "smc_history_put_ancestors", t);
+    if (rc) return rc;
+    if (!a) return fail(SMC_EINVAL, "smc_history_put_ancestors: NULL argument");
+    const size_t nw = cloud_words(h);
+    for (size_t i = 0; i < nw; ++i)
+        if (a[i] < 0 || (int64_t)a[i] >= h->v.n)
+            return fail(SMC_EINVAL, "smc_history_put_ancestors: entry " + std::to_string(i) + " is not a particle (outside [0, n_x))");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(h->hist.d_a + (size_t)t * nw, a, nw * 4, hipMemcpyHostToDevice));
     return SMC_OK;
 }
 
@@ -435,5 +480,41 @@ extern "C" int smc_rb_sample_paths(smc_handle h, const double* y, int64_t T, int
     if (tvar) HIPCHK(hipMemcpy(tvar, d_tvar, (size_t)T * pw * 8, hipMemcpyDeviceToHost));
     if (tdraw) HIPCHK(hipMemcpy(tdraw, d_tdraw, (size_t)T * pw * 8, hipMemcpyDeviceToHost));
     if (out) HIPCHK(hipMemcpy(out, d_out, (size_t)T * nt * 8 * 8, hipMemcpyDeviceToHost));
+    return SMC_OK;
+}
+
+// ---- ancestor sampling: the sweep of a conditional handle without the walk (smc_spec.h "ancestor sampling") ------------
+int ancestor_sweep_enqueue(smc_handle h, uint64_t path_seed, const int32_t** d_J, const int32_t** d_idx, const int** d_dead) {
+    const FilterView& v = h->v;
+    const int64_t T = h->hist.len, n = v.n;
+    const size_t nt = (size_t)v.ntheta;
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<SmoothRow> rows;
+    const int rc = fetch_rows(h, h->model, "smc_ancestor_sweep", "the transition scale", rows);   // (waits for the steps)
+    if (rc) return rc;
+    OffsetPlan p;
+    const size_t o_J = p.take((size_t)T * nt * 4), o_idx = p.take((size_t)T * nt * 4), o_last = p.take(nt * 4), o_dead = p.take(nt * sizeof(int)),
+                 o_rows = p.take(nt * sizeof(SmoothRow));
+    // (the new block first: a failed allocation leaves the handle as it was; the stream is idle after fetch_rows)
+    if (h->cond.d_sweep.grow_keep(p.bytes) != hipSuccess) return fail(SMC_ENOMEM, "smc_ancestor_sweep: hipMalloc of the indices of the sweep");
+    char* base = h->cond.d_sweep.as<char>();
+    AncArgs a{};
+    a.n = n; a.T = T; a.ntheta = (int)nt; a.d = h->d;
+    a.seed = v.seed; a.path_seed = path_seed;
+    a.hx = h->hist.d_x; a.hw = h->hist.d_w; a.ha = h->hist.d_a;
+    a.xref = h->cond.d_xref.as<double>();
+    a.rows = (const SmoothRow*)(base + o_rows); a.stream = h->d_stream;
+    a.J = (int32_t*)(base + o_J); a.idx = (int32_t*)(base + o_idx); a.last = (int32_t*)(base + o_last); a.dead = (int*)(base + o_dead);
+    hipStream_t s = h->stream;
+    HIPCHK(hipMemcpyAsync(base + o_rows, rows.data(), nt * sizeof(SmoothRow), hipMemcpyHostToDevice, s));
+    // ONE launch for the T - 1 ancestor draws and the last pick: a workgroup per (step, filter); one wave when the cloud is small
+    const int threads = n <= ANC_WAVE_N ? 64 : 256;
+    HIPCHK(by_density_model(h->model, [&](auto Mt) {
+        hipLaunchKernelGGL((k_cond_ancestors<decltype(Mt)::value>), dim3((unsigned)T, (unsigned)nt), dim3(threads), 0, s, a);
+        return hipGetLastError();
+    }));
+    hipLaunchKernelGGL(k_cond_trace, dim3((unsigned)((nt + 63) / 64)), dim3(64), 0, s, a);
+    HIPCHK(hipGetLastError());
+    *d_J = a.J; *d_idx = a.idx; *d_dead = a.dead;
     return SMC_OK;
 }

@@ -172,8 +172,10 @@ struct smc_filter_s {
     struct {   // the record of a step-by-step run and the smoother over it (smc_capi_smooth.hip); a fresh handle is disarmed
         bool armed = false;
         int64_t cap = 0, len = 0;              // steps the slabs hold / steps recorded so far
-        DevBlock rec;                          // the record, ONE allocation (new block first): d_x | d_w
+        DevBlock rec;                          // the record, ONE allocation (new block first): d_x | d_w | d_a
         double *d_x = nullptr, *d_w = nullptr; //   its views [cap][d][ntheta][n] | [cap][ntheta][n]
+        int32_t* d_a = nullptr;                //   SMC_FLAG_ANCESTOR_SAMPLING: the ancestor plane [cap][ntheta][n], dense like d_w, row 0 reads -1;
+                                               //   nullptr (and no bytes) on every other handle
         DevBlock d_ws;                         // the smoother's results (old block first): ws [ws_cap][ntheta][n] | mean, var [len][2][d][ntheta]
         int64_t ws_cap = 0;                    //   steps d_ws was laid out for
         DevBlock d_tmp;                        // its scratch (old block first): chunk maxima and chunk partials [2][nchunk][ntheta][n] | logD [ntheta][n] |
@@ -188,6 +190,8 @@ struct smc_filter_s {
     struct {   // the conditional particle filter (SMC_FLAG_CONDITIONAL; smc_capi_cond.hip): the reference, an allocation of its own
         DevBlock d_xref;                       // double [T][d][ntheta] (new block first); empty: none yet (a recycled bundle never carries one)
         int64_t T = 0;
+        DevBlock d_sweep;                      // smc_ancestor_sweep (new block first): J [T][ntheta] | idx [T][ntheta] | last [ntheta] | dead [ntheta] |
+                                               //   rows [ntheta]; empty until the first sweep
     } cond;
     struct {   // forecasts (smc_capi_forecast.hip): ONE block, grown on demand (old block first)
         DevBlock d_buf;                        // clouds [block][d + 3][ntheta][npad] | summary scratch | results of every horizon
@@ -244,6 +248,8 @@ struct GapScope {
 };
 // the conditional particle filter (include/smc_hip.h): the handle runs the COND kernels, one launch per step
 inline bool conditional(const smc_filter_s* h) { return (h->flags & SMC_FLAG_CONDITIONAL) != 0; }
+// ... and draws its next reference by ancestor sampling: the record keeps the ancestor vectors (smc_capi_smooth.hip)
+inline bool ancestor_sampling(const smc_filter_s* h) { return (h->flags & SMC_FLAG_ANCESTOR_SAMPLING) != 0; }
 // The ONE place that decides which kernels a launch of this handle means: the variant whose object serves entry (LAUNCH_OBJECT,
 // smc_launch.h; NO_OBJECT: the handle has no such launch).  gap: this launch covers a missing observation - the step's own is
 // NaN, or the series / window of a resident launch holds one (the caller knows from where); false for every unflagged handle.
@@ -287,6 +293,9 @@ int history_append(smc_handle h);
 void history_free(smc_filter_s* h);   // (frees the record and every block over it: the handle is disarmed)
 inline bool history_armed(const smc_filter_s* h) { return h->hist.armed; }
 int history_refuse(const char* who);
+// smc_capi_smooth.hip: the two launches of smc_ancestor_sweep (smc_anc_kernels.h) over the record, on the handle's stream; its
+// refusals are the caller's (smc_capi_cond.hip).  Where the results lie in h->cond.d_sweep: J, idx [T][ntheta], dead [ntheta]
+int ancestor_sweep_enqueue(smc_handle h, uint64_t path_seed, const int32_t** d_J, const int32_t** d_idx, const int** d_dead);
 // smc_capi_slots.hip: k_copy_slots on stream s (slot th of dst <- slot th of src where mask[th])
 hipError_t copy_slots(const smc::FilterView& dst, int dcur, const smc::FilterView& src, int scur, int d, const unsigned char* mask, hipStream_t s);
 

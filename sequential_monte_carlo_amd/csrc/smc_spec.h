@@ -1431,4 +1431,42 @@ SMC_HD uint32_t cond_slot(uint64_t seed, uint32_t stream, uint32_t t, uint32_t n
     return (uint32_t)mulhi64(((uint64_t)c1 << 32) | c0, (uint64_t)n);
 }
 
+// ---- ancestor sampling (opt-in per handle: SMC_FLAG_ANCESTOR_SAMPLING; Lindsten, Jordan and Schoen 2014) ------------
+// Particle Gibbs WITHOUT the backward walk.  The steps are the conditional steps above, unchanged.  After the T recorded steps of
+// one filter - clouds (x_t, w_t) with w the dense weights, ancestor vectors a_t (a_t[i]: the particle of step t - 1 that particle i
+// of step t descends from; the retained slot's entry is k*_{t-1}), the reference xref the steps ran with, the filter seed, the
+// filter's stream id and a path seed - the sweep is:
+//   THE ANCESTOR DRAW, t = 1 .. T-1: the pinned particle of step t redraws its ancestor given where it sits,
+//       P(J_t = l) ~ w_{t-1}^l f(xref[t] | x_{t-1}^l).  It is ONE step of backward simulation over the cloud of step t - 1 with the
+//       target xref[t] in the place of x_{t+1}^j: live sources, b_l, M, q_l = path_weight(b_l, M), the integer sum S and "the smallest
+//       i with C_i > r" are those of "backward simulation" above, bit for bit; the uniform is
+//       u = anc_uniform(filter seed, stream, t) = v[1] << 32 | v[0] of draw(seed, 0, stream, t, SLOT_ANC),  r = mulhi64(u, S).
+//       S = 0 (no live source reaches xref[t]): J_t = k*_{t-1} = cond_slot(seed, stream, t - 1, n), the ancestor it has without
+//       sampling.  J_0 = -1.  Every J_t is a function of the OLD reference and of the record alone, not of another J: the T - 1
+//       draws are independent given the clouds, which is why the device makes them in one launch.
+//   THE LAST INDEX: idx[T-1] is backward simulation's last step for path 0 under the path seed: b_l = sp_log(w_{T-1}^l),
+//       u = path_uniform(path_seed, 0, stream, T - 1).  S = 0 there (the last cloud has no live particle): the filter is DEAD,
+//       idx[t] = -1 for every t, and it keeps its reference.
+//   THE TRACE, t = T-1 .. 1:  idx[t-1] = anc_trace: J_t when idx[t] is the retained slot k*_t, else a_t[idx[t]].
+//   THE NEW REFERENCE: xref[t] = x_t^{idx[t]}, copied bit for bit, after every J_t has been drawn from the old one.
+// The kernel on trajectories leaves p(x_1:T | y_1:T, theta) invariant for any n >= 2, as backward simulation does.
+constexpr uint32_t SLOT_ANC = 39u;   // no other draw uses it (the other slots end at 38)
+// v[1] << 32 | v[0] of draw(seed, 0, stream, t, slot) by plain integer operators: the loop of cond_slot (which is left as it
+// is, so that the step kernels compile from unchanged text), for a draw that is uniform over a workgroup and wants the scalar unit
+SMC_HD uint64_t scalar_draw64(uint64_t seed, uint32_t stream, uint32_t t, uint32_t slot) {
+    uint32_t c0 = 0u, c1 = stream, c2 = t, c3 = slot, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return ((uint64_t)c1 << 32) | c0;
+}
+SMC_HD uint64_t anc_uniform(uint64_t seed, uint32_t stream, uint32_t t) { return scalar_draw64(seed, stream, t, SLOT_ANC); }
+// one step of the trace: the particle of step t - 1 behind particle i of step t (kstar = k*_t, J = J_t, a_t the ancestors of step t)
+SMC_HD int32_t anc_trace(int32_t i, uint32_t kstar, int32_t J, const int32_t* a_t) { return (uint32_t)i == kstar ? J : a_t[i]; }
+
 }  // namespace smc

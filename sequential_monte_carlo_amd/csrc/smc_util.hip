@@ -642,14 +642,14 @@ static bool host_dead(int64_t T, int64_t n, const double* w /*[T][n]*/) {
 }
 
 // the selection of backward simulation (smc_spec.h): the integer weights q_l = path_weight(b[l], Mx) of the sources of positive
-// weight wt[l], their sum S, r = mulhi64(path p's uniform of step t, S), and the first source at which the running sum passes r;
-// -1 when S == 0
-static int64_t host_path_pick(int64_t n, const double* wt, const double* b, double Mx, uint64_t seed, int64_t p, uint32_t stream, int64_t t) {
+// weight wt[l], their sum S, r = mulhi64(u, S) for the 64-bit uniform u of the draw, and the first source at which the running sum
+// passes r; -1 when S == 0
+static int64_t host_path_pick_u(int64_t n, const double* wt, const double* b, double Mx, uint64_t u) {
     uint64_t S = 0;
     for (int64_t l = 0; l < n; ++l)
         if (wt[l] > 0.0) S += path_weight(b[l], Mx);
     if (!S) return -1;
-    const uint64_t r = mulhi64(path_uniform(seed, p, stream, (uint32_t)t), S);
+    const uint64_t r = mulhi64(u, S);
     uint64_t C = 0;
     for (int64_t l = 0; l < n; ++l) {
         if (!(wt[l] > 0.0)) continue;
@@ -657,6 +657,10 @@ static int64_t host_path_pick(int64_t n, const double* wt, const double* b, doub
         if (C > r) return l;
     }
     return -1;
+}
+// ... with the uniform of path p at step t (backward simulation)
+static int64_t host_path_pick(int64_t n, const double* wt, const double* b, double Mx, uint64_t seed, int64_t p, uint32_t stream, int64_t t) {
+    return host_path_pick_u(n, wt, b, Mx, path_uniform(seed, p, stream, (uint32_t)t));
 }
 
 // smoothed moments of one step: smc_get_moments' definitions on (x, ws) in the smoother's order of summation
@@ -840,6 +844,67 @@ extern "C" int smc_host_sample_paths(int model_id, const double* raw, int64_t T,
     if (!smooth_row(model_id, raw, k))
         return fail(SMC_EINVAL, "smc_host_sample_paths: no transition density for this family, or a transition scale that is not positive and finite");
     (void)by_density_model(model_id, [&](auto Mt) { host_paths_t<decltype(Mt)::value>(k, T, n, x, w, M, path_seed, stream, idx, xs); return hipSuccess; });
+    return SMC_OK;
+}
+
+// ---- ancestor sampling on the host (smc_spec.h "ancestor sampling"): the twin of smc_ancestor_sweep for ONE filter ----------------
+template <int MODEL>
+static void host_ancestor_sweep_t(const SmoothRow& k, int64_t T, int64_t n, const double* x, const double* w, const int32_t* a, const double* xref,
+                                  uint64_t seed, uint64_t path_seed, uint32_t stream, int32_t* J, int32_t* idx, double* xref_out) {
+    constexpr int D = model_dim<MODEL>::value;
+    const size_t sx = (size_t)D * n;
+    std::vector<double> b((size_t)n);
+    // the ancestor draws, every one from the OLD reference
+    J[0] = -1;
+    for (int64_t t = 1; t < T; ++t) {
+        const double *xs = x + (size_t)(t - 1) * sx, *ws = w + (size_t)(t - 1) * n, *xr = xref + (size_t)t * D;
+        double Mx = -inf();
+        for (int64_t l = 0; l < n; ++l) {
+            if (!(ws[l] > 0.0)) continue;
+            double xp[D], ml[D], s, c;
+            for (int r = 0; r < D; ++r) xp[r] = xs[(size_t)r * n + l];
+            logf_source<MODEL>(k, xp, ml, s, c);
+            b[l] = logf_pair<MODEL>(k, ml, s, sp_log(ws[l]) + c, xr);
+            Mx = b[l] > Mx ? b[l] : Mx;
+        }
+        const int64_t pick = host_path_pick_u(n, ws, b.data(), Mx, anc_uniform(seed, stream, (uint32_t)t));
+        J[t] = pick >= 0 ? (int32_t)pick : (int32_t)cond_slot(seed, stream, (uint32_t)(t - 1), (uint32_t)n);
+    }
+    // the last index: backward simulation's last step for path 0
+    const double* wl = w + (size_t)(T - 1) * n;
+    double Mx = -inf();
+    for (int64_t l = 0; l < n; ++l) {
+        if (!(wl[l] > 0.0)) continue;
+        b[l] = sp_log(wl[l]);
+        Mx = b[l] > Mx ? b[l] : Mx;
+    }
+    int32_t i = (int32_t)host_path_pick_u(n, wl, b.data(), Mx, path_uniform(path_seed, 0, stream, (uint32_t)(T - 1)));
+    for (size_t q = 0; q < (size_t)T * D; ++q) xref_out[q] = xref[q];
+    if (i < 0) {   // dead: the filter keeps its reference
+        for (int64_t t = 0; t < T; ++t) idx[t] = -1;
+        return;
+    }
+    idx[T - 1] = i;
+    for (int64_t t = T - 1; t >= 1; --t) idx[t - 1] = i = anc_trace(i, cond_slot(seed, stream, (uint32_t)t, (uint32_t)n), J[t], a + (size_t)t * n);
+    for (int64_t t = 0; t < T; ++t)
+        for (int r = 0; r < D; ++r) xref_out[(size_t)t * D + r] = x[(size_t)t * sx + (size_t)r * n + idx[t]];
+}
+
+extern "C" int smc_host_ancestor_sweep(int model_id, const double* raw, int64_t T, int64_t n, const double* x, const double* w, const int32_t* a,
+                                       const double* xref, uint64_t seed, uint64_t path_seed, uint32_t stream, int32_t* J, int32_t* idx,
+                                       double* xref_out) {
+    if (!raw || !x || !w || !a || !xref || !J || !idx || !xref_out) return fail(SMC_EINVAL, "smc_host_ancestor_sweep: NULL argument");
+    if (T < 1 || n < 1) return fail(SMC_EINVAL, "smc_host_ancestor_sweep: T and n must be positive");
+    if (n > PATH_MAX_N) return fail(SMC_EINVAL, "smc_host_ancestor_sweep: more than 2^20 particles");
+    SmoothRow k;
+    if (!smooth_row(model_id, raw, k))
+        return fail(SMC_EINVAL, "smc_host_ancestor_sweep: no transition density for this family, or a transition scale that is not positive and finite");
+    for (size_t q = (size_t)n; q < (size_t)T * n; ++q)
+        if (a[q] < 0 || (int64_t)a[q] >= n) return fail(SMC_EINVAL, "smc_host_ancestor_sweep: a[" + std::to_string(q / n) + "] holds an entry outside [0, n)");
+    (void)by_density_model(model_id, [&](auto Mt) {
+        host_ancestor_sweep_t<decltype(Mt)::value>(k, T, n, x, w, a, xref, seed, path_seed, stream, J, idx, xref_out);
+        return hipSuccess;
+    });
     return SMC_OK;
 }
 

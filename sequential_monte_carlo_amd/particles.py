@@ -98,10 +98,11 @@ class _Filters:
     """Device state shared by the Particles / Weights views of one bootstrap_filter call."""
 
     def __init__(self, N, models, seed, seg, device, streams, ancestors, resampler="multinomial", proposal=None, rows=None, missing=False,
-                 conditional=False):
+                 conditional=False, ancestor_sampling=False):
         """rows=(model id, [n_theta][n_raw] parameter rows): a batch given as rows instead of `models` (then None)
         missing=True: a NaN observation is a missing one (FLAG_NAN_MISSING)
-        conditional=True: the conditional particle filter (FLAG_CONDITIONAL): the caller sets the reference"""
+        conditional=True: the conditional particle filter (FLAG_CONDITIONAL): the caller sets the reference
+        ancestor_sampling=True (with conditional): the record keeps the ancestors (FLAG_ANCESTOR_SAMPLING)"""
         if rows is not None:
             mid, raw = int(rows[0]), np.ascontiguousarray(rows[1], dtype=np.float64)
         else:
@@ -110,7 +111,8 @@ class _Filters:
         if resampler not in ("multinomial", "systematic"):
             raise ValueError("resampler must be 'multinomial' (the reference's law) or 'systematic' (opt-in)")
         flags = (_lib.FLAG_ANCESTORS if ancestors else 0) | (_lib.FLAG_SYSTEMATIC if resampler == "systematic" else 0) | (
-            _lib.FLAG_NAN_MISSING if missing else 0) | (_lib.FLAG_CONDITIONAL if conditional else 0)
+            _lib.FLAG_NAN_MISSING if missing else 0) | (_lib.FLAG_CONDITIONAL if conditional else 0) | (
+            _lib.FLAG_ANCESTOR_SAMPLING if ancestor_sampling else 0)
         self.h = _lib.Handle(mid, raw.shape[0], N, seg=seg, seed=seed, device=device, flags=flags)
         self.h.set_params(raw)
         if streams is not None:
@@ -511,9 +513,16 @@ class ParticleGibbs:
         pg.set_model(m)  a model, a list of them, or parameter rows [n_theta][n_raw]: theta for the next sweep
         pg.path, pg.logmu, pg.ess, pg.sweeps, pg.kept   the current path; the last sweep's per-step increments and effective sample
                          sizes; sweeps done; filters whose path was dead in the last sweep and that kept their path (0 in practice)
+        ancestor_sampling=True   particle Gibbs with ANCESTOR SAMPLING (Lindsten, Jordan and Schoen 2014) instead of
+                         backward simulation: at every step the pinned particle redraws its ancestor given the old path, and the new
+                         path is the ancestor lineage of one particle drawn from the last weights.  The same invariance for any
+                         N >= 2, without the T dependent rounds of the backward walk: one launch over (step, filter) and T lookups per
+                         filter (Handle.ancestor_sweep under the path seed of the sweep).  Another kernel on paths: its sweeps are not
+                         those of the default.  pg.ancestor_sampling tells which one the chain uses.  Out of scope:
+                         smoother(reference=..., ancestor_sampling=...) and a Julia binding.
     Bootstrap families with a transition density (UnivariateLinearGaussian, StochasticVolatility, UCSV), multinomial resampling."""
 
-    def __init__(self, N, y, model, reference=None, seed=None, seg=0, device=0, streams=None, rows=None):
+    def __init__(self, N, y, model, reference=None, seed=None, seg=0, device=0, streams=None, rows=None, ancestor_sampling=False):
         self.seed = next(_seed_counter) if seed is None else int(seed)
         self.y = np.ascontiguousarray(y, dtype=np.float64).ravel()
         T = self.y.size
@@ -523,7 +532,9 @@ class ParticleGibbs:
             reference = smoother(N, self.y, model, seed=self.sweep_seed(0), seg=seg, device=device, streams=streams, rows=rows, paths=1,
                                  smooth=False)[3]["paths"]
             reference = reference[:, 0] if rows is None and not isinstance(model, (list, tuple)) else reference[:, :, 0]
-        self._f = _Filters(int(N), model, self.sweep_seed(1), seg, device, streams, False, rows=rows, conditional=True)
+        self.ancestor_sampling = bool(ancestor_sampling)
+        self._f = _Filters(int(N), model, self.sweep_seed(1), seg, device, streams, False, rows=rows, conditional=True,
+                           ancestor_sampling=self.ancestor_sampling)
         h = self._f.h
         h.set_reference(_reference_in(reference, self._f, T))
         h.history_begin(T)
@@ -540,8 +551,11 @@ class ParticleGibbs:
         sd = self.sweep_seed(self.sweeps + 1)
         h.reseed(sd)
         lm, es, _ = _run_recorded(h, self.y)                           # (smc_init restarts the record)
-        h.sample_paths(1, _path_seed(sd), want_x=False)
-        self.kept = h.reference_from_paths(0)
+        if self.ancestor_sampling:
+            self.kept = h.ancestor_sweep(_path_seed(sd))[2]
+        else:
+            h.sample_paths(1, _path_seed(sd), want_x=False)
+            self.kept = h.reference_from_paths(0)
         self.sweeps += 1
         pick = (lambda a: a[:, 0]) if self._f.single else (lambda a: a)
         self.logmu, self.ess = pick(lm), pick(es)
