@@ -2,11 +2,13 @@
 M in {512, 2^16, 2^20} parameter particles, T = 200, chain 3, one parameter in both samplers (scalar: theta = A of the LG1D row;
 two-state: theta = Q11 of the Hodrick-Prescott row), the same session, the same process.  Host clock around calls that end in a
 device synchronise, ms per call, the median of REPS repetitions after WARM warm-up ones, scalar and two-state alternating:
-  filter      smc_ibis_filter over y[0:200): 200 Kalman steps per particle in one launch (k_ibis_window / k_ibis2_window, no records)
+  filter      smc_ibis_filter over y[0:200): 200 Kalman steps per particle in one launch (k_ibis_window<Lg1Row, ..> / <Lg2Row, ..>,
+              no records)
   rejuvenate  smc_ibis_rejuvenate over y[0:200), chain 3: 600 Kalman steps per particle in one launch
   smooth      smc_kalman_smooth / smc_kalman2_smooth of n = M rows over y[0:200): the call allocates, copies the rows in and
               xs, Ps [T][n](x 2, x 3) out, so at large n it is the copies that are timed
-Nothing here is a pass condition.  `--resources` (needs hipcc, no GPU): registers, scratch and occupancy of the two-state kernels.
+Nothing here is a pass condition.  `--resources` (needs hipcc, no GPU): registers, scratch and occupancy of the IBIS kernels of
+smc_ibis.hip for both kinds of row, and of the stand-alone two-state and scalar Kalman kernels.
 usage: python scripts/dbg/ibis2_cost.py [--log FILE]"""
 import os
 import re
@@ -24,7 +26,7 @@ SIZES = (512, 1 << 16, 1 << 20)
 def resources():
     csrc = os.path.join(HERE, "sequential_monte_carlo_amd", "csrc")
     out = ["kernel resource use (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):"]
-    for src, pat in (("smc_kalman2.hip", r"k_kalman2|k_ibis2_(window|rejuvenate)"),):
+    for src, pat in (("smc_ibis.hip", r"k_ibis_(init|reset|window|rejuvenate|permute)<"), ("smc_kalman2.hip", r"k_kalman"), ("smc_util.hip", r"k_kalman")):
         with tempfile.TemporaryDirectory() as tmp:
             err = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fPIC",
                                   "-Rpass-analysis=kernel-resource-usage", "-c", "-o", os.path.join(tmp, "a.o"), src],
@@ -41,7 +43,7 @@ def resources():
                     rows[name][key] = int(m.group(1))
         for name, row in rows.items():
             dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip() or name
-            short = re.sub(r"\(smc::IbisView.*|\(double const\*.*", "", dem).replace("void smc::", "")
+            short = re.sub(r"\(smc::IbisView.*|\(double const\*.*", "", dem).replace("void smc::", "").replace("smc::", "")
             if re.search(pat, short):
                 out.append("  %-52s VGPRs %3d  SGPRs %3d  scratch %3d B/lane  VGPR spills %d  SGPR spills %3d  occupancy %d waves/SIMD" % (
                     short, row["VGPRs"], row["TotalSGPRs"], row["ScratchSize [bytes/lane]"], row["VGPRs Spill"], row["SGPRs Spill"],

@@ -37,8 +37,9 @@ def resources():
             if m and name:
                 row[key] = int(m.group(1))
                 if key == "VGPRs Spill" and re.search(r"k_ibis_(window|rejuvenate|permute)", name):
-                    short = re.sub(r"^_ZN3smc\d+", "", name)[:24]
-                    print("  %-26s VGPRs %3d  scratch %3d B/lane  VGPR spills %d  SGPR spills %3d  occupancy %d waves/SIMD" % (
+                    dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip() or name
+                    short = re.sub(r"\(.*", "", dem).replace("void smc::", "").replace("smc::", "")   # k_ibis_window<Lg1Row, true, false, false>
+                    print("  %-44s VGPRs %3d  scratch %3d B/lane  VGPR spills %d  SGPR spills %3d  occupancy %d waves/SIMD" % (
                         short, row["VGPRs"], row["ScratchSize [bytes/lane]"], row["VGPRs Spill"], row["SGPRs Spill"], row["Occupancy [waves/SIMD]"]))
 
 

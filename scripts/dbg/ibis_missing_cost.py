@@ -3,7 +3,7 @@ The sizes of profiles/ibis_cost.log: M in {512, 2^16, 2^20} parameter particles,
 handle, host clock around calls that end in a device synchronise, ms per call:
   filter      smc_ibis_filter over y[0:200): k_ibis_window without records, 200 steps in one launch
   windows     13 x (smc_ibis_window of 16 steps, the last of 8, + smc_ibis_commit): k_ibis_window with records
-  rejuvenate  smc_ibis_rejuvenate over y[0:200), chain 3: k_ibis_rejuvenate<3>, 600 Kalman steps per particle
+  rejuvenate  smc_ibis_rejuvenate over y[0:200), chain 3: k_ibis_rejuvenate<Lg1Row, 3, MISS>, 600 Kalman steps per particle
   series      u  unflagged handle, no NaN      f  flagged handle, no NaN (must launch the kernels of u)
               g  flagged handle, every tenth observation NaN (the MISS twins)
   layout      RUNS fresh processes per library, alternating (parent, new, parent, ...), one session; inside a process the series
@@ -51,8 +51,9 @@ def resources(out):
             if not re.search(r"k_(ibis_window|ibis_rejuvenate|ibis_rts_forward|ibis_rts_paths|kalman)", name):
                 continue
             dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip() or name
-            short = re.sub(r"\(.*", "", dem).replace("void smc::", "")
-            if not re.search(r"k_ibis_rejuvenate<[124-8],", short):              # (the README prior: D = 3)
+            short = re.sub(r"\(.*", "", dem).replace("void smc::", "").replace("smc::", "")
+            # scalar rows (the only kind with a MISS twin), and of the rejuvenation the README prior's D = 3
+            if "Lg2Row" not in short and not re.search(r"k_ibis_rejuvenate<Lg1Row, [124-8],", short):
                 out.append("  %-44s VGPRs %3d  SGPRs %3d  scratch %3d B/lane  VGPR spills %d  SGPR spills %3d  occupancy %d waves/SIMD" % (
                     short, row["VGPRs"], row["TotalSGPRs"], row["ScratchSize [bytes/lane]"], row["VGPRs Spill"], row["SGPRs Spill"],
                     row["Occupancy [waves/SIMD]"]))

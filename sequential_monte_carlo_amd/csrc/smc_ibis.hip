@@ -8,6 +8,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace smc;
@@ -22,8 +23,8 @@ struct smc_ibis_s {
     int row_id = MODEL_LG1D;        // what a parameter particle filters: scalar LG1D rows (smc_ibis_create) or two-state MODEL_LG2D rows
     DevBlock d_theta[2], d_raw[2], d_x[2], d_S[2], d_logZ[2], d_logw[2];   // double [M][MAX_DTHETA] | [M][nraw] | [M][nx] | [M][nS] | [M] each
     int cp = 0, cs = 0;             // current (theta, raw) set and current (x, S, logZ, logw) set
-    PmmhSpec spec{};
-    Lg2Map map2{};                  // smc.model(theta) of a two-state handle (spec keeps the prior)
+    PmmhSpec spec{};                // d and the prior
+    IbisRowMap map{};               // smc.model(theta): the first row_len(h) entries
     bool configured = false, have_theta = false;
     int64_t t = 0;                  // observations committed so far
     int win_k = 0;                  // steps of the pending window (its end state sits in set cs ^ 1); 0: none
@@ -66,12 +67,12 @@ ibis_t as_ibis(void* p) {
     return (h && h->magic == 0x53494249u) ? h : nullptr;
 }
 unsigned grid_of(int64_t M) { return (unsigned)((M + IBIS_THREADS - 1) / IBIS_THREADS); }
-// a handle of two-state rows: its init / reset / window / rejuvenate / permute launches are the ibis2_launch_* of smc_kalman2.hip, and
-// a particle holds LG2_NRAW row entries, x [2] and the lower triangle S [3]; every other launch of this file serves it unchanged
+// a handle of two-state rows: a particle holds Lg2Row::NRAW row entries, x [2] and the lower triangle S [3].  Asked for the
+// lengths of its buffers, for what it refuses, and by the dispatcher below; every other line of this file serves both kinds.
 bool two_state(const smc_ibis_s* h) { return h->row_id == MODEL_LG2D; }
-size_t row_len(const smc_ibis_s* h) { return two_state(h) ? LG2_NRAW : IBIS_NRAW; }
-size_t x_len(const smc_ibis_s* h) { return two_state(h) ? 2 : 1; }
-size_t S_len(const smc_ibis_s* h) { return two_state(h) ? 3 : 1; }
+size_t row_len(const smc_ibis_s* h) { return two_state(h) ? Lg2Row::NRAW : Lg1Row::NRAW; }
+size_t x_len(const smc_ibis_s* h) { return two_state(h) ? Lg2Row::NX : Lg1Row::NX; }
+size_t S_len(const smc_ibis_s* h) { return two_state(h) ? Lg2Row::NS : Lg1Row::NS; }
 // what a two-state handle does not have (gaps, cloud summaries, the cloud's RTS smoother and its paths): SMC_EINVAL, handle unchanged
 int refuse_two_state(const char* who, const char* what) {
     return fail(SMC_EINVAL, std::string(who) + ": " + what + " is not implemented for a handle of two-state rows (smc_ibis_create_rows with SMC_MODEL_LG2D)");
@@ -82,31 +83,73 @@ void release(ibis_t h) {   // (the blocks go with the handle)
     delete h;
 }
 
-template <int D>
+// f(D), D = std::integral_constant<int, d>: the dimension of theta as a compile-time constant
+template <class F>
+void by_d(int d, F f) {
+    switch (d) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
+// The dispatcher of the kernels that are templates on the kind of row: f(Row{}, D, MISS) for the handle's kind, its d, and
+// miss: the handle is flagged AND the observations of this launch hold a NaN - the MISS twin; else the kernels an unflagged handle
+// runs.  A two-state handle has no flag (smc_ibis_set_flags refuses it), so MISS is instantiated for scalar rows only.
+template <class F>
+void by_row_d(const smc_ibis_s* h, bool miss, F f) {
+    by_d(h->spec.d, [&](auto d) {
+        if (two_state(h)) f(Lg2Row{}, d, std::false_type{});
+        else if (miss) f(Lg1Row{}, d, std::true_type{});
+        else f(Lg1Row{}, d, std::false_type{});
+    });
+}
+
 void launch_init(ibis_t h) {
-    hipLaunchKernelGGL((k_ibis_init<D>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->spec);
+    by_row_d(h, false, [&](auto row, auto d, auto) {
+        hipLaunchKernelGGL((k_ibis_init<decltype(row), decltype(d)::value>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp,
+                           h->cs, h->map);
+    });
 }
-// miss (every launcher below): the handle is flagged AND the observations of this launch hold a NaN - the MISS twin; else the
-// kernels an unflagged handle runs
-template <int D, bool MISS>
-void launch_rejuvenate_as(ibis_t h, int64_t T, double xi, int chain, uint64_t move_seed) {
-    hipLaunchKernelGGL((k_ibis_rejuvenate<D, MISS>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->spec,
-                       h->d_y.as<double>(), T, h->predict_first, xi, h->d_chol.as<double>(), h->d_chol.as<double>() + MAX_DTHETA * MAX_DTHETA, chain, move_seed, h->d_moved.as<unsigned char>(),
-                       h->d_count.as<unsigned long long>());
+void launch_reset(ibis_t h) {
+    by_row_d(h, false, [&](auto row, auto, auto) {
+        hipLaunchKernelGGL((k_ibis_reset<decltype(row)>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs);
+    });
 }
-template <int D>
+// the gather through d_a into the other buffers (the caller flips cp and cs)
+void launch_permute(ibis_t h) {
+    by_row_d(h, false, [&](auto row, auto, auto) {
+        hipLaunchKernelGGL((k_ibis_permute<decltype(row)>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs,
+                           h->d_a.as<const int32_t>());
+    });
+}
 void launch_rejuvenate(ibis_t h, bool miss, int64_t T, double xi, int chain, uint64_t move_seed) {
-    if (miss) launch_rejuvenate_as<D, true>(h, T, xi, chain, move_seed);
-    else launch_rejuvenate_as<D, false>(h, T, xi, chain, move_seed);
+    by_row_d(h, miss, [&](auto row, auto d, auto m) {
+        hipLaunchKernelGGL((k_ibis_rejuvenate<decltype(row), decltype(d)::value, decltype(m)::value>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0,
+                           h->stream, h->v, h->cp, h->cs, h->spec, h->map, h->d_y.as<double>(), T, h->predict_first, xi, h->d_chol.as<double>(),
+                           h->d_chol.as<double>() + MAX_DTHETA * MAX_DTHETA, chain, move_seed, h->d_moved.as<unsigned char>(),
+                           h->d_count.as<unsigned long long>());
+    });
 }
-template <bool RECORD, bool SUMM>
+// rec: the segment records (RECORD; with them lik, optional); part: the chunk records of the summaries (SUMM: the handle records
+// them, so it is one of scalar rows); both null: the steps alone
 void launch_window(ibis_t h, bool miss, int dst, const double* d_y, int k, int predict0, double* lik, uint64_t* rec, double* part, int ahead) {
-    if (miss)
-        hipLaunchKernelGGL((k_ibis_window<RECORD, SUMM, true>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs,
-                           dst, d_y, k, predict0, lik, rec, part, ahead);
-    else
-        hipLaunchKernelGGL((k_ibis_window<RECORD, SUMM, false>), dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs,
-                           dst, d_y, k, predict0, lik, rec, part, ahead);
+    by_row_d(h, miss, [&](auto row, auto, auto m) {
+        using Row = decltype(row);
+        auto go = [&](auto record, auto summ) {
+            hipLaunchKernelGGL((k_ibis_window<Row, decltype(record)::value, decltype(summ)::value, decltype(m)::value>), dim3(grid_of(h->v.M)),
+                               dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, dst, d_y, k, predict0, lik, rec, part, ahead);
+        };
+        if constexpr (std::is_same_v<Row, Lg1Row>) {
+            if (part) return go(std::true_type{}, std::true_type{});
+        }
+        if (rec) go(std::true_type{}, std::false_type{});
+        else go(std::false_type{}, std::false_type{});
+    });
 }
 void launch_rts_forward(hipStream_t st, bool miss, const double* raw, int64_t M, const double* d_y, int64_t T, int predict_first, double* xf,
                         double* Sf) {
@@ -115,11 +158,6 @@ void launch_rts_forward(hipStream_t st, bool miss, const double* raw, int64_t M,
     else
         hipLaunchKernelGGL((k_ibis_rts_forward<false>), dim3(grid_of(M)), dim3(IBIS_THREADS), 0, st, raw, M, d_y, T, predict_first, xf, Sf);
 }
-#define IBIS_BY_D(d, CALL)                                                                                      \
-    switch (d) {                                                                                                \
-    case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;             \
-    case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; default: CALL(8); break;            \
-    }
 
 // run `steps` observations from the committed state in place (no records): the prefix of a window that is kept, or a whole series
 int steps_in_place(ibis_t h, const double* y, int64_t steps) {
@@ -129,8 +167,7 @@ int steps_in_place(ibis_t h, const double* y, int64_t steps) {
     while (done < steps) {   // (the kernel's step count is an int)
         const int k = (int)(steps - done > (1 << 20) ? (1 << 20) : steps - done);
         const int predict0 = (h->t + done > 0 || h->predict_first) ? 1 : 0;
-        if (two_state(h)) ibis2_launch_window(h->stream, h->v, h->cp, h->cs, h->cs, h->d_y.as<double>() + done, k, predict0, nullptr, nullptr);
-        else launch_window<false, false>(h, kalman_has_gap(h->flags, y + done, k), h->cs, h->d_y.as<double>() + done, k, predict0, nullptr, nullptr, nullptr, 0);
+        launch_window(h, kalman_has_gap(h->flags, y + done, k), h->cs, h->d_y.as<double>() + done, k, predict0, nullptr, nullptr, nullptr, 0);
         HIPCHK(hipGetLastError());
         done += k;
     }
@@ -212,24 +249,14 @@ extern "C" int smc_ibis_configure(void* hp, int d_theta, const int32_t* prior_fa
         sp.family[i] = prior_family[i];
         for (int k = 0; k < PRIOR_NPAR; ++k) sp.par[i][k] = prior_par[(size_t)i * PRIOR_NPAR + k];
     }
-    Lg2Map map{};
-    if (two_state(h)) {       // LG2_NRAW entries: they do not fit the PmmhSpec and travel in the handle's Lg2Map
-        sp.nraw = 0;
-        for (int k = 0; k < LG2_NRAW; ++k) {
-            if (raw_from[k] >= d_theta) return fail(SMC_EINVAL, "smc_ibis_configure: raw_from index out of range");
-            map.raw_from[k] = raw_from[k];
-            map.raw_const[k] = raw_const[k];
-        }
-    } else {
-        sp.nraw = IBIS_NRAW;
-        for (int k = 0; k < IBIS_NRAW; ++k) {
-            if (raw_from[k] >= d_theta) return fail(SMC_EINVAL, "smc_ibis_configure: raw_from index out of range");
-            sp.raw_from[k] = raw_from[k];
-            sp.raw_const[k] = raw_const[k];
-        }
+    IbisRowMap map{};
+    for (size_t k = 0; k < row_len(h); ++k) {
+        if (raw_from[k] >= d_theta) return fail(SMC_EINVAL, "smc_ibis_configure: raw_from index out of range");
+        map.from[k] = raw_from[k];
+        map.cst[k] = raw_const[k];
     }
     h->spec = sp;
-    h->map2 = map;
+    h->map = map;
     h->configured = true;
     h->have_theta = false;
     h->win_k = 0;
@@ -247,9 +274,7 @@ extern "C" int smc_ibis_set_theta(void* hp, const double* theta) {
     for (size_t m = 0; m < M; ++m)
         for (int i = 0; i < d; ++i) pad[m * MAX_DTHETA + i] = theta[m * d + i];
     HIPCHK(hipMemcpyAsync(h->v.theta[h->cp], pad.data(), pad.size() * 8, hipMemcpyHostToDevice, h->stream));
-#define IBIS_CALL_INIT(D) launch_init<D>(h)
-    if (two_state(h)) ibis2_launch_init(h->stream, h->v, h->cp, h->cs, h->spec, h->map2);
-    else IBIS_BY_D(d, IBIS_CALL_INIT)
+    launch_init(h);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_theta = true;
@@ -277,19 +302,15 @@ static int enqueue_window(ibis_t h, const char* who, const double* y, int k, boo
     HIPCHK(hipMemcpyAsync(h->d_y.as<double>(), y, (size_t)k * 8, hipMemcpyHostToDevice, h->stream));
     const bool miss = kalman_has_gap(h->flags, y, k);
     const int predict0 = (h->t > 0 || h->predict_first) ? 1 : 0;
-    if (h->summ_on) {   // the same steps, and the chunk records of the summaries after each; then one workgroup per row combines them
-        launch_window<true, true>(h, miss, h->cs ^ 1, h->d_y.as<double>(), k, predict0, lik ? h->d_lik.as<double>() : nullptr, h->d_rec.as<uint64_t>(), h->d_part.as<double>(), h->summ_ahead);
-        HIPCHK(hipGetLastError());
+    // with summaries: the same steps, and the chunk records of the summaries after each; then one workgroup per row combines them
+    launch_window(h, miss, h->cs ^ 1, h->d_y.as<double>(), k, predict0, lik ? h->d_lik.as<double>() : nullptr, h->d_rec.as<uint64_t>(),
+                  h->summ_on ? h->d_part.as<double>() : nullptr, h->summ_ahead);
+    HIPCHK(hipGetLastError());
+    if (h->summ_on) {
         hipLaunchKernelGGL(k_ibis_sum_combine, dim3((unsigned)k), dim3(IBIS_SUM_CTHREADS), 0, h->stream, h->d_part.as<double>(), (int64_t)nchunk,
                            h->d_srow.as<double>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h->srow, h->d_srow.as<double>(), (size_t)k * IBIS_SUM_NOUT * 8, hipMemcpyDeviceToHost, h->stream));
-    } else if (two_state(h)) {
-        ibis2_launch_window(h->stream, h->v, h->cp, h->cs, h->cs ^ 1, h->d_y.as<double>(), k, predict0, lik ? h->d_lik.as<double>() : nullptr, h->d_rec.as<uint64_t>());
-        HIPCHK(hipGetLastError());
-    } else {
-        launch_window<true, false>(h, miss, h->cs ^ 1, h->d_y.as<double>(), k, predict0, lik ? h->d_lik.as<double>() : nullptr, h->d_rec.as<uint64_t>(), nullptr, 0);
-        HIPCHK(hipGetLastError());
     }
     return SMC_OK;
 }
@@ -495,8 +516,7 @@ extern "C" int smc_ibis_filter(void* hp, const double* y, int64_t T) {
     if (!h->have_theta) return fail(SMC_ESTATE, "smc_ibis_filter: smc_ibis_set_theta has not been called");
     HIPCHK(hipSetDevice(h->device));
     h->win_k = 0;
-    if (two_state(h)) ibis2_launch_reset(h->stream, h->v, h->cp, h->cs);
-    else hipLaunchKernelGGL(k_ibis_reset, dim3(grid_of(h->v.M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs);
+    launch_reset(h);
     HIPCHK(hipGetLastError());
     h->t = 0;
     return steps_in_place(h, y, T);
@@ -512,8 +532,7 @@ extern "C" int smc_ibis_permute(void* hp, const int32_t* a) {
     HIPCHK(hipSetDevice(h->device));
     h->win_k = 0;
     HIPCHK(hipMemcpyAsync(h->d_a.as<int32_t>(), a, (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
-    if (two_state(h)) ibis2_launch_permute(h->stream, h->v, h->cp, h->cs, h->d_a.as<int32_t>());
-    else hipLaunchKernelGGL(k_ibis_permute, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->d_a.as<int32_t>());
+    launch_permute(h);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     h->cp ^= 1;
@@ -548,13 +567,7 @@ extern "C" int smc_ibis_rejuvenate(void* hp, const double* y, int64_t T, double 
     HIPCHK(hipMemcpyAsync(h->d_y.as<double>(), y, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_chol.as<double>(), par, sizeof(par), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->d_count.as<unsigned long long>(), 0, 8, h->stream));
-    const bool miss = kalman_has_gap(h->flags, y, T);
-#define IBIS_CALL_REJ(D) launch_rejuvenate<D>(h, miss, T, xi, chain, move_seed)
-    if (two_state(h))
-        ibis2_launch_rejuvenate(h->stream, h->v, h->cp, h->cs, h->spec, h->map2, h->d_y.as<double>(), T, h->predict_first, xi, h->d_chol.as<double>(),
-                                h->d_chol.as<double>() + MAX_DTHETA * MAX_DTHETA, chain, move_seed, h->d_moved.as<unsigned char>(),
-                                h->d_count.as<unsigned long long>());
-    else IBIS_BY_D(d, IBIS_CALL_REJ)
+    launch_rejuvenate(h, kalman_has_gap(h->flags, y, T), T, xi, chain, move_seed);
     HIPCHK(hipGetLastError());
     unsigned long long n = 0;
     HIPCHK(hipMemcpyAsync(&n, h->d_count.as<unsigned long long>(), 8, hipMemcpyDeviceToHost, h->stream));
@@ -623,8 +636,7 @@ extern "C" int smc_ibis_resample(void* hp, uint64_t seed, int32_t* a_out) {
                        h->d_skb.as<const uint32_t>(), h->d_K.as<const uint32_t>(), SH, (const uint64_t*)Dcum, nseg, h->d_cnt.as<int32_t>());
     launch_scan(h, IbisCount{h->d_cnt.as<int32_t>()}, M, tsum, h->d_q.as<uint64_t>());          // (the weights are spent: their array takes the scan of cnt)
     hipLaunchKernelGGL(k_ibis_rs_expand, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, M, h->d_q.as<const uint64_t>(), h->d_a.as<int32_t>());
-    if (two_state(h)) ibis2_launch_permute(h->stream, h->v, h->cp, h->cs, h->d_a.as<int32_t>());
-    else hipLaunchKernelGGL(k_ibis_permute, dim3(grid_of(M)), dim3(IBIS_THREADS), 0, h->stream, h->v, h->cp, h->cs, h->d_a.as<int32_t>());
+    launch_permute(h);
     HIPCHK(hipGetLastError());
     if (a_out) HIPCHK(hipMemcpyAsync(a_out, h->d_a.as<int32_t>(), (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -651,8 +663,7 @@ extern "C" int smc_ibis_theta_moments(void* hp, int weighted, double* mean, doub
         hipLaunchKernelGGL(k_ibis_mom_combine, dim3(1), dim3(IBIS_THREADS), 0, h->stream, h->d_mpart.as<const double>(), 1, nchunk, h->d_mom.as<double>(), 0,
                            0.0, 0, h->d_mom.as<const double>());
     }
-#define IBIS_CALL_MOM(D) launch_moments<D>(h, weighted, nchunk)
-    IBIS_BY_D(d, IBIS_CALL_MOM)
+    by_d(d, [&](auto D) { launch_moments<decltype(D)::value>(h, weighted, nchunk); });
     HIPCHK(hipGetLastError());
     double mom[IBIS_MOM_N];
     HIPCHK(hipMemcpyAsync(mom, h->d_mom.as<double>(), sizeof(mom), hipMemcpyDeviceToHost, h->stream));

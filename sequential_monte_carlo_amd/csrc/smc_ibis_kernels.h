@@ -1,8 +1,13 @@
-// smc_ibis_kernels.h -- the IBIS sampler (src/ibis.jl): SMC^2 whose inner "filter" is the exact scalar Kalman filter of the
-// univariate LinearModel.  One lane per parameter particle; the whole state of a particle is (theta, row, x, Sigma, logZ, logw),
-// resident on the device for the life of the handle.  Included by smc_ibis.hip only.
+// smc_ibis_kernels.h -- the IBIS sampler (src/ibis.jl): SMC^2 whose inner "filter" is an exact Kalman filter, of the univariate
+// LinearModel (Lg1Row) or of a two-state linear model (Lg2Row).  One lane per parameter particle; the whole state of a particle is
+// (theta, row, x, Sigma, logZ, logw), resident on the device for the life of the handle.  Included by smc_ibis.hip only.
 //
-//   k_ibis_init        theta -> model rows, (x, Sigma) = (x0, sigma0), logZ = logw = 0          ibis.jl:35-43
+// The five kernels that touch a row or a state are templates on the row kind (smc_kalman_rows.h): one text for both kinds, the
+// lengths and the step function from the trait.  Everything else (summaries, ESS records, resampling, moments of theta) reads
+// theta, logw and M alone - or is for scalar rows only, which the handle enforces.
+//
+//   k_ibis_init        theta -> model rows, (x, Sigma) = the row's initial state, logZ = logw = 0          ibis.jl:35-43
+//   k_ibis_reset       the same state from the rows alone
 //   k_ibis_window      k online steps smc²! (:166-187; smc², :134-147, is k = 1 from the initial state) and the segment
 //                      records of the outer reweight after every step
 //   k_ibis_rejuvenate  rejuvenate! (:86-125): the whole chain of PMMH moves of a particle, Kalman re-filters included
@@ -15,42 +20,58 @@
 
 namespace smc {
 
-// smc.model(theta) as a gather without a run-time index into registers: row[k] = theta[raw_from[k]] or raw_const[k]
-template <int D>
-__device__ __forceinline__ void ibis_row(const PmmhSpec& s, const double* th, double* row) {
+// smc.model(theta) as a gather without a run-time index into registers: row[k] = theta[from[k]] or cst[k]
+template <class Row, int D>
+__device__ __forceinline__ void ibis_row(const IbisRowMap& s, const double* th, double* row) {
 #pragma unroll
-    for (int k = 0; k < IBIS_NRAW; ++k) {
-        double v = s.raw_const[k];
-        const int from = s.raw_from[k];
+    for (int k = 0; k < Row::NRAW; ++k) {
+        double v = s.cst[k];
+        const int from = s.from[k];
 #pragma unroll
         for (int i = 0; i < D; ++i) v = from == i ? th[i] : v;
         row[k] = v;
     }
 }
 
+// (x, S) of particle m of a set of the view <-> the registers of its lane
+template <class Row>
+__device__ __forceinline__ void ibis_load_state(const IbisView& v, int cs, int64_t m, double* x, double* S) {
+#pragma unroll
+    for (int i = 0; i < Row::NX; ++i) x[i] = v.x[cs][m * Row::NX + i];
+#pragma unroll
+    for (int i = 0; i < Row::NS; ++i) S[i] = v.S[cs][m * Row::NS + i];
+}
+template <class Row>
+__device__ __forceinline__ void ibis_store_state(const IbisView& v, int cs, int64_t m, const double* x, const double* S) {
+#pragma unroll
+    for (int i = 0; i < Row::NX; ++i) v.x[cs][m * Row::NX + i] = x[i];
+#pragma unroll
+    for (int i = 0; i < Row::NS; ++i) v.S[cs][m * Row::NS + i] = S[i];
+}
+
 // theta -> rows and the initial state of every particle   ibis.jl:38-43
-template <int D>
-__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_init(IbisView v, int cp, int cs, PmmhSpec s) {
+template <class Row, int D>
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_init(IbisView v, int cp, int cs, IbisRowMap s) {
     const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
     if (m >= v.M) return;
-    double th[D], row[IBIS_NRAW];
+    double th[D], row[Row::NRAW];
 #pragma unroll
     for (int i = 0; i < D; ++i) th[i] = v.theta[cp][m * MAX_DTHETA + i];
-    ibis_row<D>(s, th, row);
+    ibis_row<Row, D>(s, th, row);
 #pragma unroll
-    for (int k = 0; k < IBIS_NRAW; ++k) v.raw[cp][m * IBIS_NRAW + k] = row[k];
-    v.x[cs][m] = row[4];
-    v.S[cs][m] = row[5];
+    for (int k = 0; k < Row::NRAW; ++k) v.raw[cp][m * Row::NRAW + k] = row[k];
+    ibis_store_state<Row>(v, cs, m, row + Row::X0, row + Row::S0);
     v.logZ[cs][m] = 0.0;
     v.logw[cs][m] = 0.0;
 }
 
 // The same state from the rows alone: the beginning of a whole-series filter (density_tempered's first pass)
+template <class Row>
 __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_reset(IbisView v, int cp, int cs) {
     const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
     if (m >= v.M) return;
-    v.x[cs][m] = v.raw[cp][m * IBIS_NRAW + 4];
-    v.S[cs][m] = v.raw[cp][m * IBIS_NRAW + 5];
+    const double* row = v.raw[cp] + m * Row::NRAW;
+    ibis_store_state<Row>(v, cs, m, row + Row::X0, row + Row::S0);
     v.logZ[cs][m] = 0.0;
     v.logw[cs][m] = 0.0;
 }
@@ -202,32 +223,35 @@ __global__ __launch_bounds__(IBIS_SUM_CTHREADS) void k_ibis_sum_combine(double* 
 // MISS (handles with SMC_FLAG_NAN_MISSING, launched only when the window holds a NaN): a NaN y[j] is the missing Kalman step of
 // smc_spec.h - y[j] is one address for all lanes, so the test is uniform over the wave.  logw gains +0.0, so the record of
 // such a step is the previous step's.  MISS = false is the kernel as it always was.
-template <bool RECORD, bool SUMM = false, bool MISS = false>
+// SUMM and MISS exist for scalar rows only (a handle of two-state rows refuses summaries and the flag).
+template <class Row, bool RECORD, bool SUMM = false, bool MISS = false>
 __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_window(IbisView v, int cp, int cs, int dst, const double* y, int k, int predict0,
                                                              double* lik /*[k][M] or null*/, uint64_t* rec /*[k][nseg][4]*/,
                                                              double* part /*[k][IBIS_SUM_NCOL][nchunk]*/, int ahead) {
+    static_assert(!SUMM || Row::NX == 1, "the summaries of the cloud are those of scalar rows");
     const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
     const bool valid = m < v.M;
     const int64_t mm = valid ? m : v.M - 1;            // lanes beyond the cloud compute on the last particle and store nothing
-    const double* row = v.raw[cp] + mm * IBIS_NRAW;
-    const double A = row[0], B = row[1], Q = row[2], R = row[3];
-    double x = v.x[cs][mm], S = v.S[cs][mm], logZ = v.logZ[cs][mm], logw = v.logw[cs][mm];
+    double r[Row::NSTEP], x[Row::NX], S[Row::NS];
+#pragma unroll
+    for (int i = 0; i < Row::NSTEP; ++i) r[i] = v.raw[cp][mm * Row::NRAW + i];
+    ibis_load_state<Row>(v, cs, mm, x, S);
+    double logZ = v.logZ[cs][mm], logw = v.logw[cs][mm];
     const int64_t nseg = (v.M + IBIS_OSEG - 1) / IBIS_OSEG;
     for (int j = 0; j < k; ++j) {
-        const double l = kalman_step_gaps<MISS>(A, B, Q, R, j > 0 || predict0 != 0, y[j], x, S);
+        const double l = Row::template step<MISS>(r, j > 0 || predict0 != 0, y[j], x, S);
         logw = logw + l;
         logZ = logZ + l;
         if (RECORD) {
             if (lik && valid) lik[(size_t)j * (size_t)v.M + (size_t)m] = l;
             ibis_outer_record(logw, valid, m, rec + (size_t)j * (size_t)nseg * 4);
         }
-        if (SUMM)
-            ibis_chunk_record(A, B, Q, R, x, S, logw, valid, ahead, part + (size_t)j * IBIS_SUM_NCOL * (size_t)gridDim.x, gridDim.x,
-                              blockIdx.x);
+        if constexpr (SUMM)
+            ibis_chunk_record(r[0], r[1], r[2], r[3], x[0], S[0], logw, valid, ahead, part + (size_t)j * IBIS_SUM_NCOL * (size_t)gridDim.x,
+                              gridDim.x, blockIdx.x);
     }
     if (valid) {
-        v.x[dst][m] = x;
-        v.S[dst][m] = S;
+        ibis_store_state<Row>(v, dst, m, x, S);
         v.logZ[dst][m] = logZ;
         v.logw[dst][m] = logw;
     }
@@ -242,41 +266,52 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_window(IbisView v, int cp
 //           then theta, logZ, x, S <- theta', logZ', x', S'; acc_array[m] = 1          :102-115
 //   omega[m] = 1                                          logw[m] = 0                  :118
 // y[t] is the same address in every lane (the compiler reads it through the scalar cache); chol [D][D] and sq [chain] likewise.
+// Row::SKIP_IDLE_WAVE (two-state rows): a wave none of whose lanes proposed inside the support leaves the re-filter of that
+// chain position out: the ballot is uniform over the wave, and a lane outside the support never accepts, so what its filter
+// would have returned is not read.  The results are the same with and without; scalar rows measured slower with it.
 // MISS: as in k_ibis_window - the re-filter skips the update at a NaN y[t], the same steps the online logZ took.
-template <int D, bool MISS = false>
-__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rejuvenate(IbisView v, int cp, int cs, PmmhSpec s, const double* y, int64_t T,
-                                                                 int predict_first, double xi, const double* chol, const double* sq,
-                                                                 int chain, uint64_t move_seed, unsigned char* moved,
+template <class Row, int D, bool MISS = false>
+__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rejuvenate(IbisView v, int cp, int cs, PmmhSpec s, IbisRowMap map, const double* y,
+                                                                 int64_t T, int predict_first, double xi, const double* chol,
+                                                                 const double* sq, int chain, uint64_t move_seed, unsigned char* moved,
                                                                  unsigned long long* n_moved) {
     const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
     const bool valid = m < v.M;
     const int64_t mm = valid ? m : v.M - 1;
     const uint32_t stream = (uint32_t)mm;
-    double th[D], row[IBIS_NRAW];
+    double th[D], row[Row::NRAW], x[Row::NX], S[Row::NS];
 #pragma unroll
     for (int i = 0; i < D; ++i) th[i] = v.theta[cp][mm * MAX_DTHETA + i];
 #pragma unroll
-    for (int k = 0; k < IBIS_NRAW; ++k) row[k] = v.raw[cp][mm * IBIS_NRAW + k];
-    double x = v.x[cs][mm], S = v.S[cs][mm], logZ = v.logZ[cs][mm];
+    for (int k = 0; k < Row::NRAW; ++k) row[k] = v.raw[cp][mm * Row::NRAW + k];
+    ibis_load_state<Row>(v, cs, mm, x, S);
+    double logZ = v.logZ[cs][mm];
     bool any = false;
     for (int c = 0; c < chain; ++c) {
-        double pr[D], prow[IBIS_NRAW];
+        double pr[D], prow[Row::NRAW], xp[Row::NX], Sp[Row::NS];
         pmmh_propose<D>(s, move_seed, stream, (uint32_t)c, th, chol, sq[c], pr);
         const bool ok = pmmh_insupport<D>(s, pr);
-        ibis_row<D>(s, pr, prow);
+        ibis_row<Row, D>(map, pr, prow);
         const double lpp = pmmh_logprior<D>(s, pr), lpc = pmmh_logprior<D>(s, th);
-        double xp = prow[4], Sp = prow[5], logZp = 0.0;
-        for (int64_t t = 0; t < T; ++t) logZp += kalman_step_gaps<MISS>(prow[0], prow[1], prow[2], prow[3], predict_first != 0 || t > 0, y[t], xp, Sp);
+#pragma unroll
+        for (int i = 0; i < Row::NX; ++i) xp[i] = prow[Row::X0 + i];
+#pragma unroll
+        for (int i = 0; i < Row::NS; ++i) Sp[i] = prow[Row::S0 + i];
+        double logZp = 0.0;
+        if (!Row::SKIP_IDLE_WAVE || __ballot(ok) != 0)
+            for (int64_t t = 0; t < T; ++t) logZp += Row::template step<MISS>(prow, predict_first != 0 || t > 0, y[t], xp, Sp);
         const double likelihood_ratio = xi * (logZp - logZ), prior_ratio = lpp - lpc;
         const double acc_ratio = likelihood_ratio + prior_ratio, log_post_prop = logZp + lpp;
         const bool acc = ok && log_post_prop > -inf() && pmmh_log_uniform(move_seed, stream, (uint32_t)c) < acc_ratio;
 #pragma unroll
         for (int i = 0; i < D; ++i) th[i] = acc ? pr[i] : th[i];
 #pragma unroll
-        for (int k = 0; k < IBIS_NRAW; ++k) row[k] = acc ? prow[k] : row[k];
+        for (int k = 0; k < Row::NRAW; ++k) row[k] = acc ? prow[k] : row[k];
         logZ = acc ? logZp : logZ;
-        x = acc ? xp : x;
-        S = acc ? Sp : S;
+#pragma unroll
+        for (int i = 0; i < Row::NX; ++i) x[i] = acc ? xp[i] : x[i];
+#pragma unroll
+        for (int i = 0; i < Row::NS; ++i) S[i] = acc ? Sp[i] : S[i];
         any = any || acc;
     }
     any = any && valid;
@@ -284,9 +319,8 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rejuvenate(IbisView v, in
 #pragma unroll
         for (int i = 0; i < D; ++i) v.theta[cp][m * MAX_DTHETA + i] = th[i];
 #pragma unroll
-        for (int k = 0; k < IBIS_NRAW; ++k) v.raw[cp][m * IBIS_NRAW + k] = row[k];
-        v.x[cs][m] = x;
-        v.S[cs][m] = S;
+        for (int k = 0; k < Row::NRAW; ++k) v.raw[cp][m * Row::NRAW + k] = row[k];
+        ibis_store_state<Row>(v, cs, m, x, S);
         v.logZ[cs][m] = logZ;
         v.logw[cs][m] = 0.0;
         moved[m] = any ? 1 : 0;
@@ -296,6 +330,7 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rejuvenate(IbisView v, in
 }
 
 // resample!(ibis) (ibis.jl:73-84): particle m <- particle a[m], a value copy of everything it owns, into the other buffers
+template <class Row>
 __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_permute(IbisView v, int cp, int cs, const int32_t* a) {
     const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
     if (m >= v.M) return;
@@ -303,9 +338,8 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_permute(IbisView v, int c
 #pragma unroll
     for (int i = 0; i < MAX_DTHETA; ++i) v.theta[cp ^ 1][m * MAX_DTHETA + i] = v.theta[cp][src * MAX_DTHETA + i];
 #pragma unroll
-    for (int k = 0; k < IBIS_NRAW; ++k) v.raw[cp ^ 1][m * IBIS_NRAW + k] = v.raw[cp][src * IBIS_NRAW + k];
-    v.x[cs ^ 1][m] = v.x[cs][src];
-    v.S[cs ^ 1][m] = v.S[cs][src];
+    for (int k = 0; k < Row::NRAW; ++k) v.raw[cp ^ 1][m * Row::NRAW + k] = v.raw[cp][src * Row::NRAW + k];
+    ibis_store_state<Row>(v, cs ^ 1, m, v.x[cs] + src * Row::NX, v.S[cs] + src * Row::NS);
     v.logZ[cs ^ 1][m] = v.logZ[cs][src];
     v.logw[cs ^ 1][m] = v.logw[cs][src];
 }

@@ -1,17 +1,18 @@
-// smc_ibis_view.h -- what the kernels of the IBIS sampler share whatever the dimension of the state inside a parameter particle:
-// the view of the resident cloud, the reductions over a segment of 8 lanes, and the segment record of the outer reweight.
-// Inline device code only (no kernel): included by smc_ibis_kernels.h (scalar rows) and smc_kalman2_kernels.h (two-state rows).
+// smc_ibis_view.h -- what the kernels of the IBIS sampler share whatever the kind of row (smc_kalman_rows.h) a parameter particle
+// filters: the view of the resident cloud, the map theta -> row, the reductions over a segment of 8 lanes, and the segment record
+// of the outer reweight.  Inline device code only (no kernel): included by smc_ibis_kernels.h.
 #pragma once
+#include "smc_kalman_rows.h"
 #include "smc_kernels.h"
 
 namespace smc {
 
 constexpr int IBIS_OSEG = 8;              // SMC_OUTER_SEG: entries per segment record of the outer reweight
-constexpr int IBIS_NRAW = 6;              // LinearModel row (A, B, Q, R, x0, sigma0)
+constexpr int IBIS_NRAW = Lg1Row::NRAW;   // LinearModel row (A, B, Q, R, x0, sigma0)
 constexpr int IBIS_THREADS = 64;          // one wave per workgroup: a cloud of a few hundred particles still spreads over the CUs
 constexpr int IBIS_MAX_WINDOW = 64;
 
-// nraw, nx, nS doubles per particle: (IBIS_NRAW, 1, 1) for a handle of scalar rows, (LG2_NRAW, 2, 3) for one of two-state rows
+// Row::NRAW, Row::NX, Row::NS doubles per particle, Row the kind of row of the handle
 struct IbisView {
     int64_t M;
     double* theta[2];     // [M][MAX_DTHETA]   (theta, raw) and (x, S, logZ, logw) are double-buffered separately:
@@ -22,12 +23,13 @@ struct IbisView {
     double* logw[2];      // [M]
 };
 
-// smc.model(theta) for a two-state row: PmmhSpec's raw_from [NPARAM] is too short for LG2_NRAW entries, so the map of such a
-// handle travels beside it (the prior, s.d / s.family / s.par, stays in the PmmhSpec)
-struct Lg2Map {
-    int raw_from[LG2_NRAW];
-    double raw_const[LG2_NRAW];
+// smc.model(theta) of a handle: row[k] = from[k] >= 0 ? theta[from[k]] : cst[k].  Long enough for either kind of row; a kernel
+// reads the first Row::NRAW entries.  (The prior, d / family / par, is the handle's PmmhSpec.)
+struct IbisRowMap {
+    int from[LG2_NRAW];
+    double cst[LG2_NRAW];
 };
+static_assert(Lg1Row::NRAW <= LG2_NRAW && Lg2Row::NRAW <= LG2_NRAW, "IbisRowMap holds the map of either kind of row");
 
 // reductions over the 8 consecutive lanes of a segment (lane & ~7 .. lane | 7), result in every one of them: quad_perm
 // [1,0,3,2], quad_perm [2,3,0,1] and row_half_mirror (lane i <-> 7 - i of each half row) as DPP moves
@@ -79,18 +81,5 @@ __device__ __forceinline__ void ibis_outer_record(double logw, bool valid, int64
         r[3] = live ? s2.lo : 0;
     }
 }
-
-// The launches of a handle of two-state rows (smc_kalman2.hip; the kernels: smc_kalman2_kernels.h).  The handle, its state
-// machine and every dimension-free call stay in smc_ibis.hip, which dispatches here on the handle's row id.  Nothing is waited for.
-#pragma GCC visibility push(hidden)
-void ibis2_launch_init(hipStream_t st, const IbisView& v, int cp, int cs, const PmmhSpec& s, const Lg2Map& map);
-void ibis2_launch_reset(hipStream_t st, const IbisView& v, int cp, int cs);
-void ibis2_launch_window(hipStream_t st, const IbisView& v, int cp, int cs, int dst, const double* d_y, int k, int predict0, double* lik,
-                         uint64_t* rec /*null: no records*/);
-void ibis2_launch_rejuvenate(hipStream_t st, const IbisView& v, int cp, int cs, const PmmhSpec& s, const Lg2Map& map, const double* d_y, int64_t T,
-                             int predict_first, double xi, const double* chol, const double* sq, int chain, uint64_t move_seed,
-                             unsigned char* moved, unsigned long long* n_moved);
-void ibis2_launch_permute(hipStream_t st, const IbisView& v, int cp, int cs, const int32_t* a);
-#pragma GCC visibility pop
 
 }  // namespace smc

@@ -11,7 +11,7 @@ using namespace smc;
 namespace {
 constexpr int64_t K2_MAX_N = (int64_t)1 << 30, K2_MAX_T = (int64_t)1 << 31;
 size_t k2_up256(size_t b) { return (b + 255) & ~(size_t)255; }
-unsigned k2_grid(int64_t n) { return (unsigned)((n + KALMAN2_THREADS - 1) / KALMAN2_THREADS); }
+unsigned k2_grid(int64_t n) { return (unsigned)((n + KALMAN_THREADS - 1) / KALMAN_THREADS); }
 
 // the checks every device call of this file shares, and the call's one allocation (freed when the call returns)
 int k2_begin(const char* who, int64_t n, int64_t T, int device, DevBlock& blk, size_t bytes) {
@@ -26,38 +26,6 @@ int k2_begin(const char* who, int64_t n, int64_t T, int device, DevBlock& blk, s
 }
 }  // namespace
 
-// ---- the launches of an IBIS handle of two-state rows (declared in smc_ibis_view.h; the handle: smc_ibis.hip) ------------------
-#define K2_BY_D(d, CALL)                                                                                        \
-    switch (d) {                                                                                                \
-    case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;             \
-    case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; default: CALL(8); break;            \
-    }
-namespace smc {
-void ibis2_launch_init(hipStream_t st, const IbisView& v, int cp, int cs, const PmmhSpec& s, const Lg2Map& map) {
-#define K2_CALL_INIT(D) hipLaunchKernelGGL((k_ibis2_init<D>), dim3(k2_grid(v.M)), dim3(IBIS_THREADS), 0, st, v, cp, cs, map)
-    K2_BY_D(s.d, K2_CALL_INIT)
-}
-void ibis2_launch_reset(hipStream_t st, const IbisView& v, int cp, int cs) {
-    hipLaunchKernelGGL(k_ibis2_reset, dim3(k2_grid(v.M)), dim3(IBIS_THREADS), 0, st, v, cp, cs);
-}
-void ibis2_launch_window(hipStream_t st, const IbisView& v, int cp, int cs, int dst, const double* d_y, int k, int predict0, double* lik,
-                         uint64_t* rec) {
-    if (rec) hipLaunchKernelGGL((k_ibis2_window<true>), dim3(k2_grid(v.M)), dim3(IBIS_THREADS), 0, st, v, cp, cs, dst, d_y, k, predict0, lik, rec);
-    else hipLaunchKernelGGL((k_ibis2_window<false>), dim3(k2_grid(v.M)), dim3(IBIS_THREADS), 0, st, v, cp, cs, dst, d_y, k, predict0, lik, rec);
-}
-void ibis2_launch_rejuvenate(hipStream_t st, const IbisView& v, int cp, int cs, const PmmhSpec& s, const Lg2Map& map, const double* d_y, int64_t T,
-                             int predict_first, double xi, const double* chol, const double* sq, int chain, uint64_t move_seed,
-                             unsigned char* moved, unsigned long long* n_moved) {
-#define K2_CALL_REJ(D)                                                                                                                  \
-    hipLaunchKernelGGL((k_ibis2_rejuvenate<D>), dim3(k2_grid(v.M)), dim3(IBIS_THREADS), 0, st, v, cp, cs, s, map, d_y, T, predict_first, xi, \
-                       chol, sq, chain, move_seed, moved, n_moved)
-    K2_BY_D(s.d, K2_CALL_REJ)
-}
-void ibis2_launch_permute(hipStream_t st, const IbisView& v, int cp, int cs, const int32_t* a) {
-    hipLaunchKernelGGL(k_ibis2_permute, dim3(k2_grid(v.M)), dim3(IBIS_THREADS), 0, st, v, cp, cs, a);
-}
-}  // namespace smc
-
 extern "C" int smc_kalman2_log_likelihood(const double* raw, int64_t n, const double* y, int64_t T, int predict_first, double* out, int device) {
     if (!raw || !y || !out) return fail(SMC_EINVAL, "smc_kalman2_log_likelihood: bad argument");
     const size_t sn = n > 0 ? (size_t)n : 0, sT = T > 0 ? (size_t)T : 0;
@@ -69,7 +37,7 @@ extern "C" int smc_kalman2_log_likelihood(const double* raw, int64_t n, const do
     hipStream_t st = nullptr;   // the default stream: the call owns nothing that outlives it
     HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_raw, raw, sn * LG2_NRAW * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_kalman2_loglik, dim3(k2_grid(n)), dim3(KALMAN2_THREADS), 0, st, (const double*)d_raw, n, (const double*)d_y, T,
+    hipLaunchKernelGGL((k_kalman_loglik<Lg2Row>), dim3(k2_grid(n)), dim3(KALMAN_THREADS), 0, st, (const double*)d_raw, n, (const double*)d_y, T,
                        predict_first ? 1 : 0, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, st));
@@ -88,7 +56,7 @@ extern "C" int smc_kalman2_smooth(const double* raw, int64_t n, const double* y,
     hipStream_t st = nullptr;
     HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_raw, raw, sn * LG2_NRAW * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_kalman2_smooth, dim3(k2_grid(n)), dim3(KALMAN2_THREADS), 0, st, (const double*)d_raw, n, (const double*)d_y, T,
+    hipLaunchKernelGGL(k_kalman2_smooth, dim3(k2_grid(n)), dim3(KALMAN_THREADS), 0, st, (const double*)d_raw, n, (const double*)d_y, T,
                        predict_first ? 1 : 0, d_xs, d_Ps);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(xs, d_xs, sT * sn * 2 * 8, hipMemcpyDeviceToHost, st));

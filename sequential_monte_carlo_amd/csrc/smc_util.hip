@@ -158,11 +158,11 @@ extern "C" int smc_kalman_log_likelihood_flags(const double* raw, int64_t n_thet
     HIPCHK(hipMemcpyAsync(d_raw.p, raw, (size_t)n_theta * 48, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_y.p, y, (size_t)T * 8, hipMemcpyHostToDevice, st));
     if (kalman_has_gap(flags, y, T))   // the MISS twin only for a flagged call whose series holds a NaN
-        hipLaunchKernelGGL((k_kalman<true>), dim3((unsigned)((n_theta + 63) / 64)), dim3(64), 0, st, d_raw.as<double>(), n_theta,
-                           d_y.as<double>(), T, predict_first, d_out.as<double>());
+        hipLaunchKernelGGL((k_kalman_loglik<Lg1Row, true>), dim3((unsigned)((n_theta + KALMAN_THREADS - 1) / KALMAN_THREADS)), dim3(KALMAN_THREADS), 0, st,
+                           d_raw.as<double>(), n_theta, d_y.as<double>(), T, predict_first, d_out.as<double>());
     else
-        hipLaunchKernelGGL((k_kalman<false>), dim3((unsigned)((n_theta + 63) / 64)), dim3(64), 0, st, d_raw.as<double>(), n_theta,
-                           d_y.as<double>(), T, predict_first, d_out.as<double>());
+        hipLaunchKernelGGL((k_kalman_loglik<Lg1Row, false>), dim3((unsigned)((n_theta + KALMAN_THREADS - 1) / KALMAN_THREADS)), dim3(KALMAN_THREADS), 0, st,
+                           d_raw.as<double>(), n_theta, d_y.as<double>(), T, predict_first, d_out.as<double>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out.p, (size_t)n_theta * 24, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

@@ -1,22 +1,10 @@
-// smc_util_kernels.h -- kernels of the stand-alone entry points (Kalman, normalize, resample).  Included by smc_util.hip only.
+// smc_util_kernels.h -- kernels of the stand-alone entry points (normalize, resample; the batched scalar Kalman filter is
+// k_kalman_loglik<Lg1Row> of smc_kalman_rows.h).  Included by smc_util.hip only.
 #pragma once
+#include "smc_kalman_rows.h"
 #include "smc_kernels.h"
 
 namespace smc {
-
-// exact scalar Kalman filter, one lane per parameter row   kalman_filter.jl:29-70
-// MISS (smc_kalman_log_likelihood_flags with SMC_FLAG_NAN_MISSING and a NaN in y): a NaN y[t] is the missing Kalman step
-template <bool MISS = false>
-__global__ void k_kalman(const double* raw, int64_t ntheta, const double* y, int64_t T, int predict_first, double* out) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= ntheta) return;
-    const double A = raw[m * 6 + 0], B = raw[m * 6 + 1], Q = raw[m * 6 + 2], R = raw[m * 6 + 3];
-    double x = raw[m * 6 + 4], S = raw[m * 6 + 5], logZ = 0.0;
-    for (int64_t t = 0; t < T; ++t) {
-        logZ += kalman_step_gaps<MISS>(A, B, Q, R, predict_first || t > 0, y[t], x, S);
-    }
-    out[m * 3 + 0] = x; out[m * 3 + 1] = S; out[m * 3 + 2] = logZ;
-}
 
 // ---------------------------------------------------------------------------------------------
 // stand-alone A1 / A2 (outer theta-level reweight / resample; n <= a few thousand): one

@@ -7,6 +7,7 @@ import pytest
 
 import sequential_monte_carlo_amd as smc
 from sequential_monte_carlo_amd import _lib as L
+from oracle import binding as ob
 from ibis_reference import IbisReference, LG_TRUE, Y_SEED, case_one_parameter, case_readme, grid_posterior_A
 
 pytestmark = pytest.mark.gpu
@@ -118,6 +119,84 @@ def test_resample_is_a_value_copy():
     for name, ref in (("theta", r.theta), ("x", r.x), ("Sigma", r.S), ("logZ", r.logZ), ("logw", r.logw)):
         assert np.array_equal(getattr(ib, name), ref), name
     ib.close()
+
+
+# ---- every d of the (row kind, d) dispatch: theta[i] is row entry i for i < min(d, 6), the rest of the row is constant ---------
+FIRST_D_CHAIN = 2
+
+
+def case_first_d(d):
+    """theta = the first d of (A, B, Q, R, x0, sigma0, -, -): with d = 7, 8 the surplus parameters reach no row entry and act
+    through the prior only.  Bounded priors on A and on the seventh parameter, a LogNormal on Q, R and sigma0"""
+    parts = [smc.TruncatedNormal(0, 1, -1, 1), smc.Normal(1.0, 0.2), smc.LogNormal(), smc.LogNormal(), smc.Normal(0.0, 1.0), smc.LogNormal(),
+             smc.Uniform(-1.0, 1.0), smc.Normal(0.0, 1.0)]
+    tmap = smc.ThetaMap(L.MODEL_LG1D, [i if i < d else -1 for i in range(6)], [0.5, 1.0, 0.9, 0.8, 0.0, 1.0])
+    return tmap, smc.product_distribution(parts[:d])
+
+
+def _snapshot(r):
+    return {name: getattr(r, name).copy() for name in ("theta", "x", "S", "logZ", "logw")}
+
+
+def restate_first_d(d, M, monkeypatch):
+    """the restatement alone (no GPU), T = 6, chain 2: its cloud after the filter, after the rejuvenation, and lik of a window of 2
+    steps after a permutation with repeats.  The factor of the random walk is the restatement's own; a cloud of one particle has
+    none, and takes 0.1 I"""
+    tmap, prior = case_first_d(d)
+    y = _y(8)
+    r = IbisReference(M, tmap, prior, FIRST_D_CHAIN, 0.5, seed=7)
+    out = {"r": r, "tmap": tmap, "prior": prior, "theta0": r.theta.copy(), "y": y}
+    for m in range(M):
+        r.x[m], r.S[m], r.logZ[m] = ob.kalman_log_likelihood(r._row(r.theta[m]), y[:6], predict_first=False)
+    r.logw = r.logZ.copy()
+    out["filtered"] = _snapshot(r)
+    chol, uni = ob.rw_factor(r.theta) if M >= 2 else (0.1 * np.eye(d), d == 1)
+    scales = 0.5 * np.arange(FIRST_D_CHAIN, 0, -1)
+    out["chol"], out["s"] = chol, (scales * scales if uni else scales)
+    out["move_seed"] = (r.seed << 20) + r._calls + 1                      # the restatement's next seed
+    with monkeypatch.context() as mp:
+        mp.setattr(ob, "rw_factor", lambda theta: (chol, uni))
+        r.rejuvenate(y[:6])
+    out["moved"] = _snapshot(r)
+    out["n_rejected"] = M * FIRST_D_CHAIN - r.n_accepted - r.n_out_of_support
+    out["a"] = a = np.array([(3 * m) % M if m % 4 else (M - 1 - m) // 2 for m in range(M)], dtype=np.int32)
+    for name in ("theta", "x", "S", "logZ", "logw"):
+        setattr(r, name, getattr(r, name)[a].copy())
+    out["wlik"] = np.zeros((2, M))
+    for m in range(M):                                                    # the host twin from the copied state on the copied row
+        row = np.array(r._row(r.theta[m]))
+        row[4], row[5] = r.x[m], r.S[m]
+        out["wlik"][:, m] = L.host_kalman_steps(row, y[6:8], True)[2]
+    return out
+
+
+def _same_arrays(h, snap):
+    g = h.get(theta=True, x=True, S=True, logZ=True, logw=True)
+    for name, ref in snap.items():
+        assert g[name].shape == ref.shape and np.array_equal(g[name], ref), name
+
+
+@pytest.mark.parametrize("M", [1, 65])
+@pytest.mark.parametrize("d", range(1, 9))
+def test_every_d_equals_restatement(d, M, monkeypatch):
+    """the dispatch on d for scalar rows, a lone lane and a ragged second wave: theta, x, S, logZ, logw after set_theta + filter and
+    after rejuvenate (with moved and its count) are the restatement's, and a window after a permutation with repeats gives the
+    twin's lik on the copied rows.  At M = 65 the restatement alone must hold accepted and rejected moves"""
+    w = restate_first_d(d, M, monkeypatch)
+    r, y = w["r"], w["y"]
+    assert M == 1 or (r.n_accepted >= 1 and w["n_rejected"] >= 1), (r.n_accepted, w["n_rejected"], r.n_out_of_support)
+    fam, par = w["prior"].spec()
+    h = L.IbisHandle(M, d, np.atleast_1d(fam), np.atleast_2d(par), w["tmap"].raw_from, w["tmap"].raw_const, seed=7)
+    h.set_theta(w["theta0"])
+    h.filter(y[:6])
+    _same_arrays(h, w["filtered"])
+    n, moved = h.rejuvenate(y[:6], 1.0, w["chol"], w["s"], w["move_seed"])
+    _same_arrays(h, w["moved"])
+    assert np.array_equal(moved, r.accepted) and n == int(r.accepted.sum())
+    h.permute(w["a"])
+    _, lik = h.window(y[6:8], want_lik=True)
+    assert np.array_equal(lik, w["wlik"])
+    h.close()
 
 
 @pytest.mark.parametrize("case,predict_first", [("readme", False), ("readme", True)])

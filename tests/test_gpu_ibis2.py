@@ -1,5 +1,5 @@
-"""GPU tests of the IBIS sampler over two-state rows (smc_ibis_create_rows with MODEL_LG2D; the k_ibis2_* kernels of
-csrc/smc_kalman2_kernels.h) against compositions of the host twin smc_host_kalman2_steps and the restatement of src/ibis.jl
+"""GPU tests of the IBIS sampler over two-state rows (smc_ibis_create_rows with MODEL_LG2D; the kernels of
+csrc/smc_ibis_kernels.h with Row = Lg2Row) against compositions of the host twin smc_host_kalman2_steps and the restatement of src/ibis.jl
 over it (tests/ibis2_reference.py): every float64 array compared bit for bit, never approx - the posterior mean is the one
 statistical check."""
 import numpy as np
@@ -106,6 +106,76 @@ def test_rejuvenate_equals_restatement(case, M, T, xi):
         assert min(r.n_accepted, r.n_rejected, r.n_out_of_support) >= need, (r.n_accepted, r.n_rejected, r.n_out_of_support)
     same_state(h, r)
     assert np.array_equal(moved, r.accepted) and n == int(r.accepted.sum()) and np.array_equal(h.get_moved(), r.accepted)
+    h.close()
+
+
+# ---- every d of the (row kind, d) dispatch: theta[i] is row entry i for i < d, the rest of the row is constant ------------------
+FIRST_D_CONST = np.array([0.5, -0.2, 1.0, 0.0, 1.0, 0.0, 0.4, 0.0, 0.3, 1.0, 0.0, 0.0, 4.0, 0.0, 4.0])
+FIRST_D_CHAIN = 2
+
+
+def case_first_d(d):
+    """theta = the first d of (A11, A12, A21, A22, B1, B2, Q11, Q21): bounded priors on A11, A12 and Q21 (proposals leave the
+    support at every d), a LogNormal on the variance Q11"""
+    parts = [smc.TruncatedNormal(0.5, 0.3, -1.0, 1.0), smc.Uniform(-0.6, 0.2), smc.Normal(1.0, 0.1), smc.Normal(0.0, 0.1), smc.Normal(1.0, 0.1),
+             smc.Normal(0.0, 0.1), smc.LogNormal(-1.0, 0.5), smc.Uniform(-0.05, 0.05)]
+    tmap = smc.ThetaMap(L.MODEL_LG2D, [i if i < d else -1 for i in range(L.LG2_NRAW)], FIRST_D_CONST)
+    return tmap, smc.product_distribution(parts[:d])
+
+
+def _snapshot(r):
+    return {name: getattr(r, name).copy() for name in ("theta", "x", "S", "logZ", "logw")}
+
+
+def restate_first_d(d, M):
+    """the restatement alone (no GPU), T = 6, chain 2: its cloud after the filter, after the rejuvenation, and lik of a window of 2
+    steps after a permutation with repeats"""
+    tmap, prior = case_first_d(d)
+    r = r2.Ibis2Reference(M, tmap, prior, FIRST_D_CHAIN, 0.5, seed=7)
+    out = {"r": r, "tmap": tmap, "prior": prior, "theta0": r.theta.copy()}
+    y = Y[:6]
+    for m in range(M):
+        r.x[m], r.S[m], r.logZ[m] = r2.kalman2(r._row(r.theta[m]), y, False)
+    r.logw = r.logZ.copy()
+    out["filtered"] = _snapshot(r)
+    chol, uni = L.host_rw_factor(r.theta) if M >= 2 else (0.1 * np.eye(d), d == 1)
+    scales = 0.5 * np.arange(FIRST_D_CHAIN, 0, -1)
+    out["chol"], out["s"] = chol, (scales * scales if uni else scales)
+    r.rejuvenate(y, 1.0, move_seed=1234, chol=chol, s=out["s"])
+    out["moved"] = _snapshot(r)
+    out["a"] = a = np.array([(3 * m) % M if m % 4 else (M - 1 - m) // 2 for m in range(M)], dtype=np.int32)
+    for name in ("theta", "x", "S", "logZ", "logw"):
+        setattr(r, name, getattr(r, name)[a].copy())
+    out["wlik"], _, _ = twin_window(r, Y[6:8], True)
+    return out
+
+
+def _same_arrays(h, snap):
+    g = h.get(theta=True, x=True, S=True, logZ=True, logw=True)
+    for name, ref in snap.items():
+        assert g[name].shape == ref.shape and np.array_equal(g[name], ref), name
+
+
+@pytest.mark.parametrize("M", [1, 65])
+@pytest.mark.parametrize("d", range(1, 9))
+def test_every_d_equals_restatement(d, M):
+    """the dispatch on d for two-state rows, a lone lane and a ragged second wave: theta, x, S, logZ, logw after set_theta + filter
+    and after rejuvenate (with moved and its count) are the restatement's, and a window after a permutation with repeats gives the
+    twin's lik on the copied rows.  At M = 65 the restatement alone must hold accepted and rejected moves"""
+    w = restate_first_d(d, M)
+    r = w["r"]
+    assert M == 1 or (r.n_accepted >= 1 and r.n_rejected >= 1), (r.n_accepted, r.n_rejected, r.n_out_of_support)
+    fam, par = w["prior"].spec()
+    h = L.IbisHandle(M, d, np.atleast_1d(fam), np.atleast_2d(par), w["tmap"].raw_from, w["tmap"].raw_const, seed=7, row_id=L.MODEL_LG2D)
+    h.set_theta(w["theta0"])
+    h.filter(Y[:6])
+    _same_arrays(h, w["filtered"])
+    n, moved = h.rejuvenate(Y[:6], 1.0, w["chol"], w["s"], 1234)
+    _same_arrays(h, w["moved"])
+    assert np.array_equal(moved, r.accepted) and n == int(r.accepted.sum())
+    h.permute(w["a"])
+    _, lik = h.window(Y[6:8], want_lik=True)
+    assert np.array_equal(lik, w["wlik"])
     h.close()
 
 
