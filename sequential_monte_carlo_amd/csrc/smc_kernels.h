@@ -200,6 +200,56 @@ __host__ __device__ inline double q7_level(double p) { return p > 0.0 ? (p < 1.0
 // up and both end together (measured on C2: end-time spread of the workgroups 4.8 -> 2.1 us, 17.65 -> 16.3 us per step).
 #define SMC_PRIO(ph) __builtin_amdgcn_s_setprio((short)(3 - (ph)))
 
+// ---- Box-Muller under the LDS ancestor search (step_body) -----------------------------------
+// The search is a chain of dependent LDS probes, one level of NQ reads per halving of the segment; between the reads of a
+// level and the compares that need them a wave has nothing to issue, and all waves of a CU are in this phase together.  The
+// slices of the staged Box-Muller (smc_spec.h) go there: level l of a search of NLEV levels runs the slices
+// [bm_first(l), bm_first(l + 1)) - all BM_NSLICE of them for every NLEV >= 1, front-loaded (10 slices over the 11 levels of a
+// segment of 2048: one per level, none under the last; over the 8 levels of 256: 2 1 1 1 2 1 1 1).
+// SMC_FILL_HEAD (timing builds only, the same bits: `make EXTRA=-DSMC_FILL_HEAD=2 build/plain.1.o`): the first slices of the pair
+// stay at the head of the kernel with the draws and only the rest is spread over the levels - how much to move was decided by
+// measurement (profiles/step_search_fill_phases.log)
+#ifndef SMC_FILL_HEAD
+#define SMC_FILL_HEAD 0
+#endif
+static_assert(SMC_FILL_HEAD >= 0 && SMC_FILL_HEAD < BM_NSLICE, "slices kept at the head");
+__host__ __device__ constexpr int bm_first(int l, int nlev) { return SMC_FILL_HEAD + (l * (BM_NSLICE - SMC_FILL_HEAD) + nlev - 1) / nlev; }
+__host__ __device__ constexpr int search_levels(int seg) { return seg <= 1 ? 0 : 1 + search_levels(seg >> 1); }
+// The values of the state that are live behind slice I (I = -1: ahead of slice 0), passed through an empty asm statement: the
+// slices between two such statements can neither be hoisted above the first nor sunk below the second, and the statements keep
+// their place among the barriers and the sched_barrier fences around them
+template <int I>
+__device__ __forceinline__ void bm_pin(BmState& b) {
+    if constexpr (I < 0) asm volatile("" : "+v"(b.w.v[0]), "+v"(b.w.v[1]), "+v"(b.w.v[2]), "+v"(b.w.v[3]));
+    else if constexpr (I == 0) asm volatile("" : "+v"(b.u1), "+v"(b.u2));
+    else if constexpr (I == 1) asm volatile("" : "+v"(b.u2), "+v"(b.e), "+v"(b.f), "+v"(b.s));
+    else if constexpr (I == 2) asm volatile("" : "+v"(b.u2), "+v"(b.e), "+v"(b.f), "+v"(b.s), "+v"(b.zl), "+v"(b.R));
+    else if constexpr (I == 3 || I == 4) asm volatile("" : "+v"(b.u2), "+v"(b.x));
+    else if constexpr (I == 5) asm volatile("" : "+v"(b.x), "+v"(b.oct), "+v"(b.y), "+v"(b.zs), "+v"(b.ps));
+    else if constexpr (I == 6 || I == 7) asm volatile("" : "+v"(b.x), "+v"(b.oct), "+v"(b.zs), "+v"(b.sy), "+v"(b.pc));
+    else if constexpr (I == 8) asm volatile("" : "+v"(b.x), "+v"(b.z0), "+v"(b.z1));
+    else asm volatile("" : "+v"(b.z0), "+v"(b.z1));
+}
+// the slices of search level l (a constant once the level loop is unrolled) of NZ states
+template <int NLEV, int NZ, int L = 0>
+__device__ __forceinline__ void bm_level(int l, BmState (&b)[NZ]) {
+    if constexpr (L < NLEV) {
+        if (l == L) {
+            constexpr int A = bm_first(L, NLEV), B = bm_first(L + 1, NLEV);
+            if constexpr (A < B) {
+#pragma unroll
+                for (int c = 0; c < NZ; ++c) {
+                    bm_pin<A - 1>(b[c]);
+                    bm_slices<A, B>(b[c]);
+                    bm_pin<B - 1>(b[c]);
+                }
+            }
+        } else {
+            bm_level<NLEV, NZ, L + 1>(l, b);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // wave / block primitives (wave64)
 // ---------------------------------------------------------------------------------------------
@@ -1066,7 +1116,18 @@ __device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& 
     //  kernel to 183 vector registers - ONE workgroup per CU; they are computed next to their use instead, below)
     //  (four state rows - the marginal UCSV family - hold eight gathered doubles per pair instead: late as well)
     constexpr bool LATE_Z = D >= 3 && NP >= 2 && !SYS;
+    // FILL (multinomial, one state coordinate - LG and SV): every Philox call stays here, but the Box-Muller of the LAST pair is
+    // only begun - its words wait in bm[] and its slices run under the probes of the LDS search below (bm_level), which is bound
+    // by the LDS array and its chain of dependent probes, not by the vector ALU ("What binds k_step").  The families
+    // with more coordinates keep their normals where they were: three states in flight would cost them registers they do not have
+    constexpr bool FILL = D == 1 && !SYS;
+    static_assert(!(FILL && LATE_Z), "late normals are not interleaved");
+    constexpr int NLEV = search_levels(SEG);
+    // every slice is mapped to a level of the search: behind its loop the normals are complete
+    static_assert(!FILL || (NLEV >= 1 && bm_first(0, NLEV) == SMC_FILL_HEAD && bm_first(NLEV, NLEV) == BM_NSLICE), "slice map of the search");
+    const bool fill = FILL && !SMC_ABL(v, 2) && !SMC_ABL(v, 6);   // (a constant outside the profiling build)
     double z[NP][NZ][2];
+    BmState bm[NZ];
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
         if (LATE_Z) break;
@@ -1075,9 +1136,13 @@ __device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& 
         for (int c = 0; c < NZ; ++c) {
             if (SMC_ABL(v, 2)) { z[k][c][0] = 1e-3 * (double)(pg & 1023); z[k][c][1] = -z[k][c][0]; }
             else if (SMC_ABL(v, 6)) { const u32x4 w4 = draw(seed, pg, stream, t, SLOT_NORMAL0 + c); z[k][c][0] = 1e-9 * (double)w4.v[0]; z[k][c][1] = 1e-9 * (double)w4.v[2]; }
+            else if (FILL && k == NP - 1) {
+                bm[c].w = draw(seed, pg, stream, t, SLOT_NORMAL0 + c);
+                bm_slices<0, SMC_FILL_HEAD>(bm[c]);
+                bm_pin<SMC_FILL_HEAD - 1>(bm[c]);
+            }
             else box_muller(draw(seed, pg, stream, t, SLOT_NORMAL0 + c), z[k][c][0], z[k][c][1]);
-            // systematic: keep the normals HERE, under the load latencies.  multinomial: measured faster when the
-            // compiler sinks them next to their use, where they fill the waits of the LDS search
+            // systematic: keep the normals HERE, under the load latencies
             if (SYS) asm volatile("" : "+v"(z[k][c][0]), "+v"(z[k][c][1]));
         }
     }
@@ -1289,6 +1354,10 @@ __device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& 
     if (SMC_ABL(v, 0)) {
 #pragma unroll
         for (int i = 0; i < NQ; ++i) pos[i] = (int)(T2[i] & (SEG - 1));
+        if (fill) {   // (no search to run under)
+#pragma unroll
+            for (int c = 0; c < NZ; ++c) bm_slices<SMC_FILL_HEAD, BM_NSLICE>(bm[c]);
+        }
     } else if (MULTI) {
         // branch-free search in the staged copy (LDS); lanes whose segment is not staged keep a
         // harmless in-range index and redo the search in global memory below
@@ -1305,10 +1374,16 @@ __device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& 
             pb[i] = pb0[i];
         }
 #pragma unroll
-        for (int s = SEG >> 1; s >= 1; s >>= 1) {
+        for (int s = SEG >> 1, l = 0; s >= 1; s >>= 1, ++l) {
             uint64_t val[NQ];
 #pragma unroll
             for (int i = 0; i < NQ; ++i) val[i] = lds_load_u64(pb[i] + 8 * lds_probe_off(s));
+            // the reads of this level are in flight: the level's share of the last pair's Box-Muller, then the compares
+            if constexpr (FILL) {   // (the fences too: the other instantiations keep the parent's schedule)
+                __builtin_amdgcn_sched_barrier(0);
+                if (fill) bm_level<NLEV>(l, bm);
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int i = 0; i < NQ; ++i) pb[i] += (val[i] <= T2[i]) ? 8 * lds_step_inc(s) : 0;
         }
@@ -1330,15 +1405,25 @@ __device__ __forceinline__ void step_body(const FilterView& v, const StepEarly& 
 #pragma unroll
         for (int i = 0; i < NQ; ++i) pb[i] = lds_ptr(Cst);
 #pragma unroll
-        for (int s = SEG >> 1; s >= 1; s >>= 1) {
+        for (int s = SEG >> 1, l = 0; s >= 1; s >>= 1, ++l) {
             uint64_t val[NQ];
 #pragma unroll
             for (int i = 0; i < NQ; ++i) val[i] = lds_load_u64(pb[i] + 8 * lds_probe_off(s));
+            // the reads of this level are in flight: the level's share of the last pair's Box-Muller, then the compares
+            if constexpr (FILL) {   // (the fences too: the other instantiations keep the parent's schedule)
+                __builtin_amdgcn_sched_barrier(0);
+                if (fill) bm_level<NLEV>(l, bm);
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int i = 0; i < NQ; ++i) pb[i] += (val[i] <= T2[i]) ? 8 * lds_step_inc(s) : 0;
         }
 #pragma unroll
         for (int i = 0; i < NQ; ++i) pos[i] = lds_unpad((int)(pb[i] - lds_ptr(Cst)) >> 3);
+    }
+    if (fill) {   // every slice has run (bm_first(NLEV) = BM_NSLICE): the last pair's normals are complete on every path below
+#pragma unroll
+        for (int c = 0; c < NZ; ++c) { z[NP - 1][c][0] = bm[c].z0; z[NP - 1][c][1] = bm[c].z1; }
     }
     SMC_STAMP(v, 5);
     uint32_t anc[NQ];

@@ -251,32 +251,45 @@ SMC_HD uint64_t fix_weight_i(double p, int dk, int bits) {
     return d2bits(p * pow2i(bits + dk) + 0x1p52) & 0x000fffffffffffffULL;
 }
 
-// log(x) for x positive, finite and normal (no special cases to test): the body of sp_log
-SMC_HD double sp_log_normal(double x, int e0) {
+// log(x) for x positive, finite and normal (no special cases to test): the body of sp_log, in the pieces the staged Box-Muller
+// below runs one at a time
+// x = m 2^e with m in (sqrt(1/2), sqrt(2)]; f = m - 1
+SMC_HD void log_split(double x, int e0, int& e, double& f) {
     const uint64_t b = d2bits(x);
     // m in (sqrt(1/2), sqrt(2)], x = m 2^e: the mantissa bits decide (m > sqrt 2 as doubles of equal exponent), and the
     // exponent field of m is written directly (0x3fe halves it)
     const uint64_t mant = b & 0x000fffffffffffffULL;
     const bool up = mant > (0x3ff6a09e667f3bcdULL & 0x000fffffffffffffULL);
-    const int e = e0 + (int)((b >> 52) & 0x7ff) - 1023 + (up ? 1 : 0);
+    e = e0 + (int)((b >> 52) & 0x7ff) - 1023 + (up ? 1 : 0);
     const double m = bits2d(mant | (up ? 0x3fe0000000000000ULL : 0x3ff0000000000000ULL));
-    const double f = m - 1.0;
+    f = m - 1.0;
+}
+constexpr double LOG_R0 = 0x1.642c8590b2164p-4;
+constexpr int LOG_NC = 10;
+constexpr double LOG_C[LOG_NC] = {0x1.8618618618618p-4, 0x1.af286bca1af28p-4, 0x1.e1e1e1e1e1e1ep-4, 0x1.1111111111111p-3,
+                                  0x1.3b13b13b13b14p-3, 0x1.745d1745d1746p-3, 0x1.c71c71c71c71cp-3, 0x1.2492492492492p-2,
+                                  0x1.999999999999ap-2, 0x1.5555555555555p-1};
+// Horner steps A .. B-1 of a polynomial with the coefficients C (compile-time constants: SMC_FMAK)
+#define SMC_POLY_STEPS(name, C)                                        \
+    template <int A, int B>                                            \
+    SMC_HD double name(double p, double z) {                           \
+        if constexpr (A < B) return name<A + 1, B>(SMC_FMAK(p, z, C[A]), z); \
+        else return p;                                                 \
+    }
+SMC_POLY_STEPS(log_poly, LOG_C)
+// log x from e, f, s = f / (2 + f) and the polynomial R(s^2) s^2
+SMC_HD double log_combine(int e, double f, double s, double Rz) {
+    const double dk = (double)e;
+    return dk * LN2_HI - ((s * (f - Rz) - dk * LN2_LO) - f);
+}
+SMC_HD double sp_log_normal(double x, int e0) {
+    int e;
+    double f;
+    log_split(x, e0, e, f);
     const double s = div_moderate(f, 2.0 + f);   // f in [-0.2929, 0.4143]: zero or of magnitude >= 2^-53
     const double z = s * s;
-    double R = 0x1.642c8590b2164p-4;
-    R = SMC_FMAK(R, z, 0x1.8618618618618p-4);
-    R = SMC_FMAK(R, z, 0x1.af286bca1af28p-4);
-    R = SMC_FMAK(R, z, 0x1.e1e1e1e1e1e1ep-4);
-    R = SMC_FMAK(R, z, 0x1.1111111111111p-3);
-    R = SMC_FMAK(R, z, 0x1.3b13b13b13b14p-3);
-    R = SMC_FMAK(R, z, 0x1.745d1745d1746p-3);
-    R = SMC_FMAK(R, z, 0x1.c71c71c71c71cp-3);
-    R = SMC_FMAK(R, z, 0x1.2492492492492p-2);
-    R = SMC_FMAK(R, z, 0x1.999999999999ap-2);
-    R = SMC_FMAK(R, z, 0x1.5555555555555p-1);
-    R = R * z;
-    const double dk = (double)e;
-    return dk * LN2_HI - ((s * (f - R) - dk * LN2_LO) - f);
+    const double R = log_poly<0, LOG_NC>(LOG_R0, z);
+    return log_combine(e, f, s, R * z);
 }
 
 SMC_HD double sp_log(double x) {
@@ -288,33 +301,31 @@ SMC_HD double sp_log(double x) {
     return sp_log_normal(x, e);
 }
 
-// cos, sin of 2*pi*u for u in [0,1) a multiple of 2^-53
-SMC_HD void sp_sincos2pi(double u, double& c, double& s) {
+// cos, sin of 2*pi*u for u in [0,1) a multiple of 2^-53, in pieces as well
+// the octant of u, y in [0, pi/4] and z = y^2
+SMC_HD void sc_reduce(double u, int& oct, double& y, double& z) {
     const double a = 8.0 * u;
-    const int oct = (int)a;
+    oct = (int)a;
     // g = a - oct in the even octants, 1 - (a - oct) in the odd ones: |(oct rounded up to even) - a|, exact either way
     const double g = fabs((double)(oct + (oct & 1)) - a);
-    const double y = g * PIO4;
-    const double z = y * y;
-    double ps = 0x1.952c77030ad4ap-49;
-    ps = SMC_FMAK(ps, z, -0x1.ae7f3e733b81fp-41);
-    ps = SMC_FMAK(ps, z, 0x1.6124613a86d09p-33);
-    ps = SMC_FMAK(ps, z, -0x1.ae64567f544e4p-26);
-    ps = SMC_FMAK(ps, z, 0x1.71de3a556c734p-19);
-    ps = SMC_FMAK(ps, z, -0x1.a01a01a01a01ap-13);
-    ps = SMC_FMAK(ps, z, 0x1.1111111111111p-7);
-    ps = SMC_FMAK(ps, z, -0x1.5555555555555p-3);
-    const double sy = fma(y * z, ps, y);
-    double pc = -0x1.6827863b97d97p-53;
-    pc = SMC_FMAK(pc, z, 0x1.ae7f3e733b81fp-45);
-    pc = SMC_FMAK(pc, z, -0x1.93974a8c07c9dp-37);
-    pc = SMC_FMAK(pc, z, 0x1.1eed8eff8d898p-29);
-    pc = SMC_FMAK(pc, z, -0x1.27e4fb7789f5cp-22);
-    pc = SMC_FMAK(pc, z, 0x1.a01a01a01a01ap-16);
-    pc = SMC_FMAK(pc, z, -0x1.6c16c16c16c17p-10);
-    pc = SMC_FMAK(pc, z, 0x1.5555555555555p-5);
-    pc = SMC_FMAK(pc, z, -0.5);
-    const double cy = SMC_FMAK(z, pc, 1.0);
+    y = g * PIO4;
+    z = y * y;
+}
+constexpr double SIN_P0 = 0x1.952c77030ad4ap-49;
+constexpr int SIN_NC = 7;
+constexpr double SIN_C[SIN_NC] = {-0x1.ae7f3e733b81fp-41, 0x1.6124613a86d09p-33, -0x1.ae64567f544e4p-26, 0x1.71de3a556c734p-19,
+                                  -0x1.a01a01a01a01ap-13, 0x1.1111111111111p-7, -0x1.5555555555555p-3};
+constexpr double COS_P0 = -0x1.6827863b97d97p-53;
+constexpr int COS_NC = 8;
+constexpr double COS_C[COS_NC] = {0x1.ae7f3e733b81fp-45, -0x1.93974a8c07c9dp-37, 0x1.1eed8eff8d898p-29, -0x1.27e4fb7789f5cp-22,
+                                  0x1.a01a01a01a01ap-16, -0x1.6c16c16c16c17p-10, 0x1.5555555555555p-5, -0.5};
+SMC_POLY_STEPS(sin_poly, SIN_C)
+SMC_POLY_STEPS(cos_poly, COS_C)
+#undef SMC_POLY_STEPS
+SMC_HD double sc_sin(double y, double z, double ps) { return fma(y * z, ps, y); }
+SMC_HD double sc_cos(double z, double pc) { return SMC_FMAK(z, pc, 1.0); }
+// (sin y, cos y) to (cos, sin) of the angle: swapped in the octants 1, 2, 5, 6, then the signs
+SMC_HD void sc_place(int oct, double sy, double cy, double& c, double& s) {
     const bool swap = ((oct + 1) & 2) != 0;
     double cc = swap ? sy : cy;
     double ss = swap ? cy : sy;
@@ -325,19 +336,82 @@ SMC_HD void sp_sincos2pi(double u, double& c, double& s) {
     c = bits2d(((uint64_t)ch << 32) | (uint32_t)cb);
     s = bits2d(((uint64_t)sh << 32) | (uint32_t)sb);
 }
+SMC_HD void sp_sincos2pi(double u, double& c, double& s) {
+    int oct;
+    double y, z;
+    sc_reduce(u, oct, y, z);
+    const double sy = sc_sin(y, z, sin_poly<0, SIN_NC>(SIN_P0, z));
+    const double cy = sc_cos(z, cos_poly<0, COS_NC>(COS_P0, z));
+    sc_place(oct, sy, cy, c, s);
+}
 
-// four Philox words -> (z0, z1) iid N(0,1); z0 belongs to particle 2p, z1 to 2p+1
+// four Philox words -> (z0, z1) iid N(0,1); z0 belongs to particle 2p, z1 to 2p+1:
+//     u1 = (n1 + 1) 2^-53, u2 = n2 2^-53 (n = the 53 high bits of a word pair)
+//     r = sqrt(-2 log u1), (c, s) = sp_sincos2pi(u2), z0 = r c, z1 = r s
+// written as BM_NSLICE straight-line slices over a small state: run in order they are the pieces of sp_log_normal,
+// sqrt_moderate_or_negzero and sp_sincos2pi above, each operation once and in the order of the plain formula (the radius first,
+// then the angle), so that box_muller, which runs them all, compiles to what the plain formula compiles to.  k_step runs the
+// slices of its last pair one at a time under the probes of its LDS ancestor search (step_body, smc_kernels.h).
+struct BmState {
+    u32x4 w;                  // the Philox words (consumed by slice 0)
+    double u1, u2;
+    int e;                    // logarithm: exponent, f = m - 1, s = f / (2 + f), z = s^2, R
+    double f, s, zl, R;
+    double x;                 // -2 log u1, then r = sqrt(x)
+    int oct;                  // sine and cosine: octant, y, z = y^2, the two polynomials, sin y
+    double y, zs, ps, pc, sy;
+    double z0, z1;            // slice 8: (cos, sin); slice 9: the normals
+};
+constexpr int BM_NSLICE = 10;
+template <int I>
+SMC_HD void bm_slice(BmState& b) {
+    static_assert(I >= 0 && I < BM_NSLICE, "slice index");
+    if constexpr (I == 0) {
+        // n = (hi:lo) >> 11 = hi 2^21 + (lo >> 11): two exact terms whose sum is representable, so one fma gives it exactly
+        // (instead of a 64-bit shift, a 64-bit add and a 64-bit conversion)
+        b.u1 = fma((double)b.w.v[1], 0x1p-32, (double)((b.w.v[0] >> 11) + 1u) * TWO_M53);
+        b.u2 = fma((double)b.w.v[3], 0x1p-32, (double)(b.w.v[2] >> 11) * TWO_M53);
+    } else if constexpr (I == 1) {
+        // u1 in [2^-53, 1] (positive, finite, normal): -2 log u1 is -0.0 (u1 = 1) or in [2.2e-16, 73.5]
+        log_split(b.u1, 0, b.e, b.f);
+        b.s = div_moderate(b.f, 2.0 + b.f);   // f in [-0.2929, 0.4143]: zero or of magnitude >= 2^-53
+    } else if constexpr (I == 2) {
+        b.zl = b.s * b.s;
+        b.R = log_poly<0, 7>(LOG_R0, b.zl);
+    } else if constexpr (I == 3) {
+        b.R = log_poly<7, LOG_NC>(b.R, b.zl);
+        b.x = -2.0 * log_combine(b.e, b.f, b.s, b.R * b.zl);
+    } else if constexpr (I == 4) {
+        b.x = sqrt_moderate_or_negzero(b.x);
+    } else if constexpr (I == 5) {
+        sc_reduce(b.u2, b.oct, b.y, b.zs);
+        b.ps = sin_poly<0, 4>(SIN_P0, b.zs);
+    } else if constexpr (I == 6) {
+        b.ps = sin_poly<4, SIN_NC>(b.ps, b.zs);
+        b.sy = sc_sin(b.y, b.zs, b.ps);
+        b.pc = cos_poly<0, 2>(COS_P0, b.zs);
+    } else if constexpr (I == 7) {
+        b.pc = cos_poly<2, COS_NC>(b.pc, b.zs);
+    } else if constexpr (I == 8) {
+        sc_place(b.oct, b.sy, sc_cos(b.zs, b.pc), b.z0, b.z1);
+    } else {
+        b.z0 = b.x * b.z0;
+        b.z1 = b.x * b.z1;
+    }
+}
+template <int A, int B>
+SMC_HD void bm_slices(BmState& b) {   // slices A .. B-1
+    if constexpr (A < B) {
+        bm_slice<A>(b);
+        bm_slices<A + 1, B>(b);
+    }
+}
 SMC_HD void box_muller(const u32x4& w, double& z0, double& z1) {
-    // u1 = (n1 + 1) 2^-53, u2 = n2 2^-53 with n = (hi:lo) >> 11 = hi 2^21 + (lo >> 11): two exact terms whose sum is
-    // representable, so one fma gives it exactly (instead of a 64-bit shift, a 64-bit add and a 64-bit conversion)
-    const double u1 = fma((double)w.v[1], 0x1p-32, (double)((w.v[0] >> 11) + 1u) * TWO_M53);
-    const double u2 = fma((double)w.v[3], 0x1p-32, (double)(w.v[2] >> 11) * TWO_M53);
-    // u1 in [2^-53, 1] (positive, finite, normal): -2 log u1 is -0.0 (u1 = 1) or in [2.2e-16, 73.5]
-    const double r = sqrt_moderate_or_negzero(-2.0 * sp_log_normal(u1, 0));
-    double c, s;
-    sp_sincos2pi(u2, c, s);
-    z0 = r * c;
-    z1 = r * s;
+    BmState b;
+    b.w = w;
+    bm_slices<0, BM_NSLICE>(b);
+    z0 = b.z0;
+    z1 = b.z1;
 }
 
 // ---- 64x64 -> 128 multiply ---------------------------------------------------------------
