@@ -543,7 +543,8 @@ int smc_ibis_get(void* h, double* theta, double* x, double* S, double* logZ, dou
  *                               smc_ibis_configure reads 15 raw_from / raw_const entries, smc_ibis_get gives x [n_theta][2] and
  *                               S [n_theta][3], and smc_ibis_set_theta, _window, _window_ess, _commit, _filter, _rejuvenate,
  *                               _permute, _resample run kalman2_step in place of the scalar step; smc_ibis_set_logw,
- *                               _theta_moments, _get_moved are the same code for both.  Refused on a two-state handle with
+ *                               _theta_moments, _theta_quantiles, _theta_histogram, _get_moved are the same code for both.
+ *                               Refused on a two-state handle with
  *                               SMC_EINVAL, the handle unchanged (follow-ups): smc_ibis_set_flags with SMC_FLAG_NAN_MISSING,
  *                               smc_ibis_summary, smc_ibis_set_summaries, smc_ibis_get_summaries, smc_ibis_smooth,
  *                               smc_ibis_sample_paths. */
@@ -611,6 +612,36 @@ int smc_ibis_resample(void* h, uint64_t seed, int32_t* a_out /*[n_theta] or NULL
 int smc_ibis_theta_moments(void* h, int weighted, double* mean /*[d_theta]*/, double* cov /*[d_theta][d_theta]*/);
 int smc_host_theta_moments(const double* theta, const double* logw, int64_t M, int d, int weighted, double* mean, double* cov);
 int smc_ibis_get_moved(void* h, uint8_t* moved /*[n_theta]*/);
+/* Quantiles and histograms of the theta cloud, on the device: what construct_histograms (src/plotting_utils.jl:5-37) and the
+ * README figures of examples/inflation_example.jl make from smc.theta and smc.omega - the median, a credible interval and the
+ * marginal histogram of every parameter - without a read of the cloud.  Integer arithmetic throughout (csrc/smc_spec.h
+ * "quantiles and histograms of the theta cloud"): particle m weighs q_m = rint(p_m 2^(32 + k_m - K)) with exp(logw_m) =
+ * p_m 2^k_m and K the largest k_m of a live particle, a dead particle (logw -inf, NaN or beyond 7e8 in magnitude) weighs 0
+ * whatever its theta, and W = sum q_m < 2^63.  Values are ordered by the IEEE total order of their bits (-0.0 below +0.0, a
+ * NaN that carries weight by its sign).  The result is a function of the arrays alone: no float atomics, the same bits from
+ * any launch geometry and from the host twins.
+ *   smc_ibis_theta_quantiles  out [d_theta][np]: for coordinate i and level p the smallest v among theta[.][i] with
+ *                             sum{q_m : theta_mi <= v} > floor(p 2^64) W / 2^64 (smc_get_quantiles' definition, its conversion of
+ *                             the level): p = 0 the smallest value that carries weight, p = 1 the largest, no interpolation; NaN
+ *                             at every level when no particle is alive.  A radix select over the 64-bit keys, 8 bits a pass, all
+ *                             coordinates and levels of the call together; d_theta np doubles come back.  1 <= np <= 8.
+ *   smc_ibis_theta_histogram  counts [nbins + 3] of one coordinate over [lo, hi) in nbins equal bins: the sums of q_m in the
+ *                             order under (theta < lo) | bins (min((int)((theta - lo) scale), nbins - 1), scale = nbins /
+ *                             (hi - lo) computed once) | over (theta >= hi) | nan.  They add up to *W exactly; normalising is
+ *                             the caller's division.  1 <= nbins <= 4096.
+ *   smc_host_theta_weights    q [M], *K and *W of logw [M] on the host (no GPU): the integers an independent reference starts
+ *                             from.  *K = -2^30 when no particle is alive.
+ *   smc_host_theta_quantiles, smc_host_theta_histogram   the same specification on the host (a sort), the same bits: theta [M][d]
+ * SMC_EINVAL: a NULL array, np or nbins out of range, a level outside [0, 1] or NaN, component outside [0, d), lo or hi not
+ * finite, hi <= lo (or hi - lo not finite).  SMC_ESTATE: before smc_ibis_set_theta, and while a window is pending
+ * (smc_ibis_commit first).  The handle is read and never written; both kinds of row (smc_ibis_create_rows).  The device scratch
+ * (8 n_theta bytes of weights, 0.2 MB of state) lives in the handle, grown at the first call and kept. */
+int smc_ibis_theta_quantiles(void* h, const double* p /*[np]*/, int np, double* out /*[d_theta][np]*/);
+int smc_ibis_theta_histogram(void* h, int component, double lo, double hi, int nbins, uint64_t* counts /*[nbins + 3]*/, uint64_t* W);
+int smc_host_theta_weights(const double* logw, int64_t M, uint64_t* q /*[M]*/, int32_t* K, uint64_t* W);
+int smc_host_theta_quantiles(const double* theta /*[M][d]*/, const double* logw, int64_t M, int d, const double* p, int np, double* out /*[d][np]*/);
+int smc_host_theta_histogram(const double* theta, const double* logw, int64_t M, int d, int component, double lo, double hi, int nbins,
+                             uint64_t* counts, uint64_t* W);
 /* The RTS smoother of an IBIS cloud and its backward-sampled paths (Rauch, Tung and Striebel 1965).  smc_ibis_summary gives
  * the filtered state p(x_t | y_1:t) integrated over the cloud; for a linear-Gaussian row the smoothed state p(x_t | y_1:T)
  * is exact as well: one backward recursion per parameter particle over its own filtered record, O(T) per particle, nothing

@@ -902,6 +902,52 @@ function theta_moments(ib::HipIBIS; weighted::Bool=false)
     return mean, cov                                                              # (symmetric: row- and column-major agree)
 end
 posterior_moments(ib::HipIBIS) = theta_moments(ib; weighted=true)
+# The weighted quantiles of every parameter under the normalised ω, selected on the device (smc_ibis_theta_quantiles): a vector
+# [dθ] for a level, a matrix [dθ x length(p)] for a vector of at most 8 levels.  No interpolation: the smallest θ with the
+# weight at or below it above p.  Not a method of Statistics.quantile - that name is the cloud's fitted observation
+# (plotting_utils.jl:119) - but one of its own.
+function posterior_quantiles(ib::HipIBIS, p::Vector{Float64})
+    out = Matrix{Float64}(undef, length(p), ib.dθ)                                # the C side writes [dθ][np] row-major
+    GC.@preserve p out smc_check(ccall((:smc_ibis_theta_quantiles, LIBSMC), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Ptr{Float64}),
+        ib.h, p, length(p), out))
+    return permutedims(out)
+end
+posterior_quantiles(ib::HipIBIS, p::Real) = posterior_quantiles(ib, [Float64(p)])[:, 1]
+# (mass [bins], edges [bins + 1], (under, over, nan)) of the marginal posterior of parameter `component` (1-based) over [lo, hi):
+# what construct_histograms (plotting_utils.jl:5-37) plots, binned on the device (smc_ibis_theta_histogram)
+function posterior_histogram(ib::HipIBIS, component::Int, lo::Float64, hi::Float64; bins::Int=50)
+    counts = Vector{UInt64}(undef, bins + 3); W = Ref{UInt64}(0)
+    GC.@preserve counts smc_check(ccall((:smc_ibis_theta_histogram, LIBSMC), Cint,
+        (Ptr{Cvoid}, Cint, Float64, Float64, Cint, Ptr{UInt64}, Ptr{UInt64}), ib.h, component - 1, lo, hi, bins, counts, W))
+    mass = counts ./ Float64(W[])
+    return mass[2:bins + 1], collect(range(lo, hi; length=bins + 1)), (mass[1], mass[bins + 2], mass[bins + 3])
+end
+# the marginal histogram over the span of the values that carry weight (the largest falls in the last bin; one value v: v ± 0.5)
+function posterior_histogram(ib::HipIBIS, component::Int; bins::Int=50)
+    q = posterior_quantiles(ib, [0.0, 1.0])
+    lo, hi = q[component, 1], q[component, 2]
+    lo == hi ? posterior_histogram(ib, component, lo - 0.5, hi + 0.5; bins=bins) : posterior_histogram(ib, component, lo, nextfloat(hi); bins=bins)
+end
+# the host twins (no GPU) over arrays a caller holds: θ [M x dθ] as the reference keeps it, logw [M]
+function host_theta_quantiles(θ::Matrix{Float64}, logw::Vector{Float64}, p::Vector{Float64})
+    M, d = size(θ); rows = permutedims(θ); out = Matrix{Float64}(undef, length(p), d)
+    GC.@preserve rows logw p out smc_check(ccall((:smc_host_theta_quantiles, LIBSMC), Cint,
+        (Ptr{Float64}, Ptr{Float64}, Int64, Cint, Ptr{Float64}, Cint, Ptr{Float64}), rows, logw, M, d, p, length(p), out))
+    return permutedims(out)
+end
+function host_theta_histogram(θ::Matrix{Float64}, logw::Vector{Float64}, component::Int, lo::Float64, hi::Float64, bins::Int)
+    M, d = size(θ); rows = permutedims(θ); counts = Vector{UInt64}(undef, bins + 3); W = Ref{UInt64}(0)
+    GC.@preserve rows logw counts smc_check(ccall((:smc_host_theta_histogram, LIBSMC), Cint,
+        (Ptr{Float64}, Ptr{Float64}, Int64, Cint, Cint, Float64, Float64, Cint, Ptr{UInt64}, Ptr{UInt64}),
+        rows, logw, M, d, component - 1, lo, hi, bins, counts, W))
+    return counts, W[]
+end
+function host_theta_weights(logw::Vector{Float64})
+    q = Vector{UInt64}(undef, length(logw)); K = Ref{Int32}(0); W = Ref{UInt64}(0)
+    GC.@preserve logw q smc_check(ccall((:smc_host_theta_weights, LIBSMC), Cint, (Ptr{Float64}, Int64, Ptr{UInt64}, Ptr{Int32}, Ptr{UInt64}),
+        logw, length(logw), q, K, W))
+    return q, K[], W[]
+end
 # the tail of rw_factor from a covariance: (L, univariate)
 function rw_factor_cov(cov::Matrix{Float64})
     d = size(cov, 1); L = Matrix{Float64}(undef, d, d); uni = Ref{Cint}(0)

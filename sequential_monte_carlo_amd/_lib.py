@@ -50,6 +50,7 @@ EXPORTS = [
     "smc_kalman2_log_likelihood", "smc_kalman2_smooth", "smc_host_kalman2_steps", "smc_host_kalman2_smooth", "smc_simulate_lg2",
     "smc_ibis_create_rows",
     "smc_history_get_ancestors", "smc_history_put_ancestors", "smc_ancestor_sweep", "smc_host_ancestor_sweep",
+    "smc_ibis_theta_quantiles", "smc_ibis_theta_histogram", "smc_host_theta_weights", "smc_host_theta_quantiles", "smc_host_theta_histogram",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -235,6 +236,11 @@ def lib():
     L.smc_host_kalman_steps.argtypes = [_dp, _dp, C.c_int64, C.c_int, C.c_uint32, _dp, _dp, _dp]
     L.smc_host_theta_moments.argtypes = [_dp, _dp, C.c_int64, C.c_int, C.c_int, _dp, _dp]
     L.smc_host_rw_factor_cov.argtypes = [_dp, C.c_int, _dp, _ip]
+    L.smc_ibis_theta_quantiles.argtypes = [h, _dp, C.c_int, _dp]
+    L.smc_ibis_theta_histogram.argtypes = [h, C.c_int, C.c_double, C.c_double, C.c_int, _u64p, _u64p]
+    L.smc_host_theta_weights.argtypes = [_dp, C.c_int64, _u64p, _i32p, _u64p]
+    L.smc_host_theta_quantiles.argtypes = [_dp, _dp, C.c_int64, C.c_int, _dp, C.c_int, _dp]
+    L.smc_host_theta_histogram.argtypes = [_dp, _dp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _u64p, _u64p]
     L.smc_history_begin.argtypes = [h, C.c_int64]
     L.smc_history_len.argtypes = [h, C.POINTER(C.c_int64)]
     L.smc_history_get.argtypes = [h, C.c_int64, _dp, _dp]
@@ -673,6 +679,44 @@ def host_theta_moments(theta, logw=None, weighted=False):
     mean, cov = np.zeros(d), np.zeros((d, d))
     check(lib().smc_host_theta_moments(_d(theta), _d(logw) if weighted else None, M, d, int(bool(weighted)), _d(mean), _d(cov)))
     return mean, cov
+
+
+def host_theta_weights(logw):
+    """(q [M] uint64, K, W): the integer weights of logw [M], their exponent maximum and their sum (smc_host_theta_weights)"""
+    logw = np.ascontiguousarray(logw, dtype=np.float64).reshape(-1)
+    q = np.zeros(logw.size, dtype=np.uint64)
+    K, W = C.c_int32(), C.c_uint64()
+    check(lib().smc_host_theta_weights(_d(logw), logw.size, q.ctypes.data_as(_u64p), C.byref(K), C.byref(W)))
+    return q, K.value, W.value
+
+
+def _theta_cloud(theta, logw):
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    logw = np.ascontiguousarray(logw, dtype=np.float64).reshape(-1)
+    assert theta.ndim == 2 and logw.size == theta.shape[0]
+    return theta, logw
+
+
+def host_theta_quantiles(theta, logw, p):
+    """out [d][np]: the weighted quantiles of every coordinate of a theta cloud [M][d] under logw [M] at the levels p
+    (smc_host_theta_quantiles: the device's specification on the host; no GPU)"""
+    theta, logw = _theta_cloud(theta, logw)
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
+    M, d = theta.shape
+    out = np.zeros((d, p.size))
+    check(lib().smc_host_theta_quantiles(_d(theta), _d(logw), M, d, _d(p), p.size, _d(out)))
+    return out
+
+
+def host_theta_histogram(theta, logw, component, lo, hi, nbins):
+    """(counts [nbins + 3] uint64 = under | bins | over | nan, W) of one coordinate of a theta cloud (smc_host_theta_histogram)"""
+    theta, logw = _theta_cloud(theta, logw)
+    M, d = theta.shape
+    counts = np.zeros(max(int(nbins), 0) + 3, dtype=np.uint64)
+    W = C.c_uint64()
+    check(lib().smc_host_theta_histogram(_d(theta), _d(logw), M, d, int(component), float(lo), float(hi), int(nbins),
+                                         counts.ctypes.data_as(_u64p), C.byref(W)))
+    return counts, W.value
 
 
 def comm_unique_id():
@@ -1411,6 +1455,22 @@ class IbisHandle:
         mean, cov = np.zeros(self.d), np.zeros((self.d, self.d))
         check(lib().smc_ibis_theta_moments(self._h, int(bool(weighted)), _d(mean), _d(cov)))
         return mean, cov
+
+    def theta_quantiles(self, p):
+        """out [d][np]: the weighted quantiles of every coordinate of the committed theta cloud at the levels p, selected on
+        the device (smc_ibis_theta_quantiles)"""
+        p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
+        out = np.zeros((self.d, p.size))
+        check(lib().smc_ibis_theta_quantiles(self._h, _d(p), p.size, _d(out)))
+        return out
+
+    def theta_histogram(self, component, lo, hi, nbins):
+        """(counts [nbins + 3] uint64 = under | bins | over | nan, W) of one coordinate of the committed theta cloud, binned on
+        the device (smc_ibis_theta_histogram)"""
+        counts = np.zeros(max(int(nbins), 0) + 3, dtype=np.uint64)
+        W = C.c_uint64()
+        check(lib().smc_ibis_theta_histogram(self._h, int(component), float(lo), float(hi), int(nbins), counts.ctypes.data_as(_u64p), C.byref(W)))
+        return counts, W.value
 
     def get_moved(self):
         """the moved mask [M] of the last rejuvenate (smc_ibis_get_moved)"""

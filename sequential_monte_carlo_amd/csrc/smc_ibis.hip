@@ -3,8 +3,10 @@
 #include "smc_host.h"
 #include "smc_ibis_kernels.h"
 #include "smc_ibis_smooth_kernels.h"
+#include "smc_theta_kernels.h"
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
@@ -55,6 +57,8 @@ struct smc_ibis_s {
     DevBlock d_cnt;                                  // int32_t [M] draws per particle
     DevBlock d_mpart;                                // double [THETA_MOM_NTRI][nchunk] chunk sums of the moments
     DevBlock d_mom;                                  // double [IBIS_MOM_N]
+    // quantiles and histograms of the theta cloud (smc_ibis_theta_quantiles / _histogram; their weights take d_q, their K d_K[0])
+    DevBlock d_tsel;                                 // uint64_t [THETA_SEL_WORDS] the select's state | [THETA_HIST_MAXBINS + 3] counts
     double rts_ms = -1.0;                            // device-event time of the kernels of the last smooth / sample_paths call
 };
 typedef smc_ibis_s* ibis_t;
@@ -672,6 +676,94 @@ extern "C" int smc_ibis_theta_moments(void* hp, int weighted, double* mean, doub
         mean[i] = mom[IBIS_MOM_MEAN + i];
         for (int j = 0; j <= i; ++j) cov[i * d + j] = cov[j * d + i] = mom[IBIS_MOM_COV + i * (i + 1) / 2 + j];
     }
+    return SMC_OK;
+}
+
+namespace {
+// What the two calls below share: the refusals, then K, q [M] (in d_q) and W of the committed logw enqueued on the stream.
+// groups: the workgroups of a streaming pass.  SMC_THETA_GROUPS caps them (a test knob: no result depends on it).
+int theta_weights_enqueue(ibis_t h, const char* who, ThetaSel& st, unsigned& groups) {
+    if (!h->have_theta) return fail(SMC_ESTATE, std::string(who) + ": smc_ibis_set_theta has not been called");
+    if (h->win_k > 0) return fail(SMC_ESTATE, std::string(who) + ": a window is pending (smc_ibis_commit first)");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t M = h->v.M;
+    HIPCHK(h->d_q.grow((size_t)M * 8));
+    HIPCHK(h->d_tsel.grow((THETA_SEL_WORDS + THETA_HIST_MAXBINS + 3) * 8));
+    st = theta_sel_carve(h->d_tsel.as<uint64_t>());
+    int64_t cap = THETA_MAX_GROUPS;
+    if (const char* e = getenv("SMC_THETA_GROUPS")) cap = atoll(e);
+    cap = cap < 1 ? 1 : cap > THETA_MAX_GROUPS ? THETA_MAX_GROUPS : cap;
+    const int64_t tiles = (M + IBIS_RED_THREADS - 1) / IBIS_RED_THREADS;
+    groups = (unsigned)(tiles < cap ? tiles : cap);
+    HIPCHK(hipMemsetAsync(h->d_K.as<uint32_t>(), 0, 4, h->stream));
+    HIPCHK(hipMemsetAsync(st.W, 0, 8, h->stream));
+    // (the grid of the passes, not one wave per workgroup: atomics on one word are served one after the other, 16 K of them in 188 us)
+    hipLaunchKernelGGL(k_ibis_kmax, dim3(groups), dim3(IBIS_RED_THREADS), 0, h->stream, h->v, h->cs, h->d_K.as<uint32_t>());
+    hipLaunchKernelGGL(k_theta_weights, dim3(groups), dim3(IBIS_RED_THREADS), 0, h->stream, h->v, h->cs, h->d_K.as<const uint32_t>(), h->d_q.as<uint64_t>(),
+                       st.W);
+    return SMC_OK;
+}
+template <int D>
+hipError_t launch_theta_select(ibis_t h, unsigned groups, int np, const ThetaLevels& lv, const ThetaSel& st) {
+    const size_t lds = (size_t)D * np * THETA_SEL_BINS * 8;
+    if (lds > 48 * 1024) {   // (up to 128 KiB at d = np = 8: one workgroup per CU)
+        const hipError_t e = hipFuncSetAttribute((const void*)k_theta_digits<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_theta_pick, dim3(1), dim3(IBIS_RED_THREADS), 0, h->stream, D, np, -1, lv, st);
+    for (int pass = 0; pass < THETA_SEL_PASSES; ++pass) {
+        hipLaunchKernelGGL((k_theta_digits<D>), dim3(groups), dim3(IBIS_RED_THREADS), lds, h->stream, (const double*)h->v.theta[h->cp],
+                           h->d_q.as<const uint64_t>(), h->v.M, np, pass, st);
+        hipLaunchKernelGGL(k_theta_pick, dim3(1), dim3(IBIS_RED_THREADS), 0, h->stream, D, np, pass, lv, st);
+    }
+    return hipGetLastError();
+}
+}  // namespace
+
+// weighted quantiles of every coordinate of the committed theta cloud (smc_spec.h "quantiles and histograms of the theta cloud"):
+// a radix select on the device, d np doubles come back
+extern "C" int smc_ibis_theta_quantiles(void* hp, const double* p, int np, double* out) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !p || !out) return fail(SMC_EINVAL, "smc_ibis_theta_quantiles: bad argument");
+    if (np < 1 || np > QMAX) return fail(SMC_EINVAL, "smc_ibis_theta_quantiles: 1 <= np <= 8");
+    ThetaLevels lv{};
+    for (int j = 0; j < np; ++j) {
+        if (!(p[j] >= 0.0 && p[j] <= 1.0)) return fail(SMC_EINVAL, "smc_ibis_theta_quantiles: levels must lie in [0, 1]");
+        lv.p64[j] = prob_to_u64(p[j]);
+    }
+    ThetaSel st;
+    unsigned groups = 0;
+    if (const int rc = theta_weights_enqueue(h, "smc_ibis_theta_quantiles", st, groups)) return rc;
+    const int d = h->spec.d;
+    hipError_t e = hipSuccess;
+    by_d(d, [&](auto D) { e = launch_theta_select<decltype(D)::value>(h, groups, np, lv, st); });
+    HIPCHK(e);
+    double res[THETA_SEL_SLOTS];
+    HIPCHK(hipMemcpyAsync(res, st.out, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < np; ++j) out[i * np + j] = res[i * QMAX + j];
+    return SMC_OK;
+}
+
+// the weighted histogram of one coordinate of the committed theta cloud: counts [nbins + 3] = under | bins | over | nan, and W
+extern "C" int smc_ibis_theta_histogram(void* hp, int component, double lo, double hi, int nbins, uint64_t* counts, uint64_t* W) {
+    ibis_t h = as_ibis(hp);
+    if (!h || !counts || !W) return fail(SMC_EINVAL, "smc_ibis_theta_histogram: bad argument");
+    if (nbins < 1 || nbins > THETA_HIST_MAXBINS) return fail(SMC_EINVAL, "smc_ibis_theta_histogram: 1 <= nbins <= 4096");
+    if (!theta_hist_range_ok(lo, hi)) return fail(SMC_EINVAL, "smc_ibis_theta_histogram: lo < hi, both finite (and hi - lo finite)");
+    if (h->have_theta && (component < 0 || component >= h->spec.d)) return fail(SMC_EINVAL, "smc_ibis_theta_histogram: component outside [0, d_theta)");
+    ThetaSel st;
+    unsigned groups = 0;
+    if (const int rc = theta_weights_enqueue(h, "smc_ibis_theta_histogram", st, groups)) return rc;
+    unsigned long long* d_counts = (unsigned long long*)(h->d_tsel.as<uint64_t>() + THETA_SEL_WORDS);
+    HIPCHK(hipMemsetAsync(d_counts, 0, (size_t)(nbins + 3) * 8, h->stream));
+    hipLaunchKernelGGL(k_theta_hist, dim3(groups), dim3(IBIS_RED_THREADS), 0, h->stream, (const double*)h->v.theta[h->cp], h->d_q.as<const uint64_t>(), h->v.M,
+                       component, lo, hi, (double)nbins / (hi - lo), nbins, d_counts);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(counts, d_counts, (size_t)(nbins + 3) * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(W, st.W, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return SMC_OK;
 }
 

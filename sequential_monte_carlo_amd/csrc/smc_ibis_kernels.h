@@ -530,13 +530,25 @@ __global__ __launch_bounds__(IBIS_THREADS) void k_ibis_rs_expand(int64_t M, cons
 // mom: [0] W | [1 .. 8] mean | [9 .. 9 + 36) cov, lower triangle row by row.  part: [column][nchunk].  One wave per chunk.
 constexpr int IBIS_MOM_MEAN = 1, IBIS_MOM_COV = 1 + MAX_DTHETA, IBIS_MOM_N = 1 + MAX_DTHETA + THETA_MOM_NTRI;
 
-__global__ __launch_bounds__(IBIS_THREADS) void k_ibis_kmax(IbisView v, int cs, uint32_t* Kb) {
-    const int64_t m = (int64_t)blockIdx.x * IBIS_THREADS + threadIdx.x;
-    const bool valid = m < v.M;
-    int k;
-    (void)ibis_sum_parts(v.logw[cs][valid ? m : v.M - 1], valid, k);
-    const uint32_t K = wave_max_u32(ibis_bias_k(k));
-    if (threadIdx.x == 0 && K) atomicMax(Kb, K);
+// any grid of workgroups of whole waves: the particles are strided over it, every workgroup publishes its maximum (an integer: any order)
+__global__ __launch_bounds__(IBIS_RED_THREADS) void k_ibis_kmax(IbisView v, int cs, uint32_t* Kb) {
+    uint32_t K = 0;
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < v.M; base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t m = base + threadIdx.x;
+        const bool valid = m < v.M;
+        int k;
+        (void)ibis_sum_parts(v.logw[cs][valid ? m : v.M - 1], valid, k);
+        const uint32_t kb = ibis_bias_k(k);
+        K = kb > K ? kb : K;
+    }
+    // one atomic per workgroup: thousands of them on one word are served one after the other (~12 ns each)
+    __shared__ uint32_t wg;
+    if (threadIdx.x == 0) wg = 0;
+    __syncthreads();
+    K = wave_max_u32(K);
+    if ((threadIdx.x & 63) == 0 && K) atomicMax(&wg, K);
+    __syncthreads();
+    if (threadIdx.x == 0 && wg) atomicMax(Kb, wg);
 }
 // u of the calling lane (weighted mode)
 __device__ __forceinline__ double ibis_mom_u(const IbisView& v, int cs, int64_t mm, bool valid, const uint32_t* Kb) {

@@ -525,3 +525,77 @@ extern "C" int smc_host_theta_moments(const double* theta, const double* logw, i
         }
     return SMC_OK;
 }
+
+// ---- quantiles and histograms of a theta cloud (smc_spec.h "quantiles and histograms of the theta cloud") ------------------------
+// The host twins of smc_ibis_theta_quantiles / smc_ibis_theta_histogram: the same integers by a sort where the device selects by
+// radix, so the same bits.
+// q [M], K (IBIS_SUM_DEADK = -2^30 when no particle is alive) and W = sum q of logw [M]
+extern "C" int smc_host_theta_weights(const double* logw, int64_t M, uint64_t* q, int32_t* K, uint64_t* W) {
+    if (!logw || !q || !K || !W || M < 1 || M > ((int64_t)1 << 30)) return fail("smc_host_theta_weights: bad argument");
+    int Kc = IBIS_SUM_DEADK;
+    for (int64_t m = 0; m < M; ++m) {
+        int k;
+        (void)ibis_sum_parts(logw[m], true, k);
+        Kc = k > Kc ? k : Kc;
+    }
+    uint64_t Wc = 0;
+    for (int64_t m = 0; m < M; ++m) {
+        int k;
+        const double p = ibis_sum_parts(logw[m], true, k);
+        q[m] = theta_q(p, k, Kc);
+        Wc += q[m];
+    }
+    *K = Kc;
+    *W = Wc;
+    return SMC_OK;
+}
+
+extern "C" int smc_host_theta_quantiles(const double* theta, const double* logw, int64_t M, int d, const double* p, int np, double* out) {
+    if (!theta || !logw || !p || !out || M < 1 || M > ((int64_t)1 << 30) || d < 1 || d > MAX_DTHETA) return fail("smc_host_theta_quantiles: bad argument");
+    if (np < 1 || np > QMAX) return fail("smc_host_theta_quantiles: 1 <= np <= 8");
+    for (int j = 0; j < np; ++j)
+        if (!(p[j] >= 0.0 && p[j] <= 1.0)) return fail("smc_host_theta_quantiles: levels must lie in [0, 1]");
+    std::vector<uint64_t> q((size_t)M);
+    int32_t K;
+    uint64_t W;
+    if (const int rc = smc_host_theta_weights(logw, M, q.data(), &K, &W)) return rc;
+    std::vector<std::pair<uint64_t, uint64_t>> kv;   // (key, weight) of the particles that carry weight
+    for (int i = 0; i < d; ++i) {
+        kv.clear();
+        for (int64_t m = 0; m < M; ++m)
+            if (q[(size_t)m]) kv.emplace_back(order_key(theta[(size_t)m * d + i]), q[(size_t)m]);
+        std::sort(kv.begin(), kv.end());
+        for (size_t a = 1; a < kv.size(); ++a) kv[a].second += kv[a - 1].second;   // inclusive sums: kv.back().second = W
+        for (int j = 0; j < np; ++j) {
+            if (!W) { out[i * np + j] = bits2d(0x7ff8000000000000ULL); continue; }
+            uint64_t T, lo;
+            mul64wide(prob_to_u64(p[j]), W, T, lo);
+            // the first entry with a sum above T (T < W: there is one); equal keys are adjacent, the last of them has the sum of
+            // all of them, so the entry's key is the smallest value with the weight at or below it above T
+            size_t a = 0, b = kv.size() - 1;
+            while (a < b) {
+                const size_t mid = (a + b) >> 1;
+                if (kv[mid].second > T) b = mid;
+                else a = mid + 1;
+            }
+            out[i * np + j] = key_value(kv[a].first);
+        }
+    }
+    return SMC_OK;
+}
+
+extern "C" int smc_host_theta_histogram(const double* theta, const double* logw, int64_t M, int d, int component, double lo, double hi, int nbins,
+                                        uint64_t* counts, uint64_t* W) {
+    if (!theta || !logw || !counts || !W || M < 1 || M > ((int64_t)1 << 30) || d < 1 || d > MAX_DTHETA) return fail("smc_host_theta_histogram: bad argument");
+    if (component < 0 || component >= d) return fail("smc_host_theta_histogram: component outside [0, d)");
+    if (nbins < 1 || nbins > THETA_HIST_MAXBINS) return fail("smc_host_theta_histogram: 1 <= nbins <= 4096");
+    if (!theta_hist_range_ok(lo, hi)) return fail("smc_host_theta_histogram: lo < hi, both finite (and hi - lo finite)");
+    std::vector<uint64_t> q((size_t)M);
+    int32_t K;
+    if (const int rc = smc_host_theta_weights(logw, M, q.data(), &K, W)) return rc;
+    const double scale = (double)nbins / (hi - lo);
+    for (int b = 0; b < nbins + 3; ++b) counts[b] = 0;
+    for (int64_t m = 0; m < M; ++m)
+        if (q[(size_t)m]) counts[theta_hist_slot(theta[(size_t)m * d + component], lo, hi, scale, nbins)] += q[(size_t)m];
+    return SMC_OK;
+}

@@ -1194,6 +1194,39 @@ SMC_HD double theta_mom_finish(double s, bool div_on, double div, bool weighted,
     return s;
 }
 
+// ---- quantiles and histograms of the theta cloud (construct_histograms, src/plotting_utils.jl:5-37) -----------------------------
+// theta [M][d], outer log-weights logw [M].  Everything is INTEGER arithmetic on values derived per particle, so the result is a
+// function of the arrays alone - any launch geometry, any order of evaluation, host and device the same bits.
+//   weight   (p_m, k_m) = ibis_sum_parts(logw_m), K = max k_m over the live particles (the K of the moments above),
+//            q_m = fix_weight_i(p_m, k_m - K, THETA_Q_BITS); a dead particle (!lw_alive) has q_m = 0 whatever its theta.
+//            sp_exp_parts returns p in [0.707, 1.415], so q_m <= 1.415 2^32 < 2^32.51 and W = sum q_m < 2^62.51 at M = 2^30: W
+//            fits 63 bits (and p 2^32 < 2^50 is what fix_weight_i asks for).  A live particle with k_m = K has q_m >= 0.707 2^32,
+//            so W > 0 exactly when some particle is alive, and then W >= 2^(THETA_Q_BITS - 1).
+//   order    the IEEE total order of the bits (smc_host_quantile7): order_key (smc_kernels.h) maps a double to a uint64 that
+//            compares the same way, key_value maps it back: -NaN < -inf < .. < -0.0 < +0.0 < .. < +inf < +NaN.  A NaN theta
+//            that carries weight sorts by its sign bit.
+//   quantile of coordinate i at level p: the smallest v among theta[.][i] with sum{q_m : key(theta_mi) <= key(v)} > T,
+//            T = umulhi64(prob_to_u64(p), W) < W (smc_get_quantiles' definition): p = 0 the smallest value that carries weight,
+//            p = 1 the largest, no interpolation.  W = 0: NaN at every level.
+//   histogram of coordinate i over [lo, hi) in nbins equal bins, scale = nbins / (hi - lo) computed once in double: slot 0
+//            "under" (theta < lo), slots 1 .. nbins the bins (min((int)((theta - lo) scale), nbins - 1): the ms_bin rule), slot
+//            nbins + 1 "over" (theta >= hi), slot nbins + 2 "nan".  counts [nbins + 3] are the sums of q_m: they add up to W.
+constexpr int THETA_Q_BITS = 32;
+constexpr int THETA_HIST_MAXBINS = 4096;
+SMC_HD uint64_t theta_q(double p, int k, int K) { return k != IBIS_SUM_DEADK ? fix_weight_i(p, k - K, THETA_Q_BITS) : 0; }
+// the range of a histogram: lo < hi, both finite, and a finite width (so that scale > 0 and (theta - lo) scale is a number)
+SMC_HD bool theta_hist_range_ok(double lo, double hi) {
+    const double w = hi - lo;
+    return lo < hi && w < inf() && lo > -inf() && hi < inf();
+}
+SMC_HD int theta_hist_slot(double v, double lo, double hi, double scale, int nbins) {
+    if (v != v) return nbins + 2;
+    if (v < lo) return 0;
+    if (v >= hi) return nbins + 1;
+    const int b = (int)((v - lo) * scale);
+    return 1 + (b < nbins - 1 ? b : nbins - 1);
+}
+
 // ---- segment combine (integers only) ----------------------------------------------------------
 // A segment record is (kb, S, S2): kb = max k_i of the segment (integral double, -inf if the segment
 // has no live particle), S = sum q, S2 = sum q^2 (128 bit).  With K = max kb:

@@ -7,6 +7,7 @@ calls are scalar-only.
     IBIS(M, model, prior, chain, ess_threshold, min_ar=-1.0)        ibis.jl:26-58
     smc2 / smc2_step / smc2_run, resample_, rejuvenate_, expected_parameters, density_tempered   (smc_samplers.py dispatches here)
     posterior_moments: the weighted mean and covariance of the theta cloud, reduced on the device
+    posterior_quantiles, posterior_histogram: weighted quantiles and marginal histograms of the theta cloud, selected on the device
     observation_dist, estimated_trend, quantile (plotting_utils.jl:94-137), filtered_state: reductions over the cloud on the device
     rts_smoothed_state, rts_quantile, rts_smoothed_paths: the exact RTS smoother of every parameter particle, integrated over the
     cloud per period, and trajectories by backward sampling - the smoothed trend and trend paths
@@ -442,6 +443,71 @@ def posterior_moments(ibis):
     if ibis._h is None:
         return _lib.host_theta_moments(ibis._theta0, np.zeros(ibis.M), weighted=True)
     return ibis._h.theta_moments(weighted=True)
+
+
+def _cloud_calls(ibis):
+    """(quantiles(p [np]) -> [d][np], histogram(component, lo, hi, bins) -> (counts, W), d) of the sampler's theta cloud: the
+    device calls, or before the first sampler call their host twins over the initial cloud"""
+    if ibis._h is None:
+        theta, logw = ibis._theta0, np.zeros(ibis.M)
+        return (lambda p: _lib.host_theta_quantiles(theta, logw, p),
+                lambda c, lo, hi, bins: _lib.host_theta_histogram(theta, logw, c, lo, hi, bins), theta.shape[1])
+    return ibis._h.theta_quantiles, ibis._h.theta_histogram, ibis._h.d
+
+
+def quantiles_from(quantiles, p):
+    """the shape rule of posterior_quantiles over a quantiles(p [np]) -> [d][np] call: [d] for a scalar level, [d][len(p)] for a
+    list; more than 8 levels take several calls"""
+    levels = np.atleast_1d(np.asarray(p, dtype=np.float64))
+    if levels.ndim != 1 or levels.size == 0:
+        raise ValueError("posterior_quantiles: p is a level or a non-empty list of levels")
+    out = np.concatenate([quantiles(levels[i:i + 8]) for i in range(0, levels.size, 8)], axis=1)
+    return out[:, 0] if np.ndim(p) == 0 else out
+
+
+def histogram_from(quantiles, histogram, d, component=None, bins=50, range=None, outside=False):
+    """posterior_histogram over the two calls of a cloud (_cloud_calls)"""
+    if component is None:
+        return [histogram_from(quantiles, histogram, d, c, bins, range, outside) for c in np.arange(d)]
+    component = int(component)
+    if not 0 <= component < d:
+        raise ValueError("posterior_histogram: component outside [0, d)")
+    if range is None:
+        lo, hi = quantiles(np.array([0.0, 1.0]))[component]
+        if lo != lo:
+            raise ValueError("posterior_histogram: no particle carries weight, so there is no range to take")
+        if lo == hi:
+            lo, hi = lo - 0.5, hi + 0.5                  # all the weight on one value: numpy's rule
+        else:
+            hi = np.nextafter(hi, np.inf)               # [lo, hi) with the largest value in the last bin
+    else:
+        lo, hi = float(range[0]), float(range[1])
+    counts, W = histogram(component, lo, hi, int(bins))
+    if W == 0:
+        raise ValueError("posterior_histogram: no particle carries weight")
+    mass = counts.astype(np.float64) / float(W)
+    edges = np.linspace(lo, hi, int(bins) + 1)
+    if outside:
+        return mass[1:-2], edges, (mass[0], mass[-2], mass[-1])
+    return mass[1:-2], edges
+
+
+def posterior_quantiles(ibis, p):
+    """the weighted quantiles of every parameter under the normalised outer weights: [d] for a level p, [d][len(p)] for a list -
+    the median and the ends of a credible interval without a read of the cloud.  For coordinate i the smallest theta[m][i] with
+    the weight at or below it above p (no interpolation; p = 0 and p = 1: the smallest and the largest value that carries
+    weight), on integer weights, so the same bits from every run and from the host (smc_ibis_theta_quantiles).
+    Before the first sampler call: the same specification on the host over the initial cloud."""
+    return quantiles_from(_cloud_calls(ibis)[0], p)
+
+
+def posterior_histogram(ibis, component=None, bins=50, range=None, outside=False):
+    """(mass [bins], edges [bins + 1]) of the marginal posterior of one parameter, or a list of d such pairs (component=None):
+    what construct_histograms (plotting_utils.jl:5-37) plots, binned on the device (smc_ibis_theta_histogram).  mass sums the
+    normalised weights per bin over [lo, hi) = range; range=None takes the smallest and the largest value that carries weight
+    (the largest falls in the last bin), and (v - 0.5, v + 0.5) for a cloud whose weight sits on one value v.  outside=True
+    also returns (under, over, nan): the mass below lo, at or above hi, and on NaN."""
+    return histogram_from(*_cloud_calls(ibis), component, bins, range, outside)
 
 
 def density_tempered(ibis, y, verbose=True, out=sys.stdout):

@@ -301,6 +301,33 @@ def posterior_moments(ibis):
     return _ibis.posterior_moments(ibis)
 
 
+def _host_cloud_calls(smc):
+    """the host twins over an SMC sampler's cloud: its theta lives on the host, its weights are log(omega)"""
+    if not (hasattr(smc, "theta") and hasattr(smc, "omega")):
+        raise TypeError("posterior_quantiles / posterior_histogram are defined for an IBIS or an SMC sampler")
+    theta = np.ascontiguousarray(smc.theta, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        logw = np.log(smc.omega)
+    return (lambda p: _lib.host_theta_quantiles(theta, logw, p),
+            lambda c, lo, hi, bins: _lib.host_theta_histogram(theta, logw, c, lo, hi, bins), theta.shape[1])
+
+
+def posterior_quantiles(smc, p):
+    """the weighted quantiles of every parameter: [d] for a level p, [d][len(p)] for a list.  IBIS: selected on the device
+    (ibis.py); SMC: the same specification on the host over smc.theta and log(smc.omega)"""
+    if isinstance(smc, IBIS):
+        return _ibis.posterior_quantiles(smc, p)
+    return _ibis.quantiles_from(_host_cloud_calls(smc)[0], p)
+
+
+def posterior_histogram(smc, component=None, bins=50, range=None, outside=False):
+    """(mass [bins], edges [bins + 1]) of the marginal posterior of one parameter, or a list of d pairs (ibis.py
+    posterior_histogram); SMC: the host twin over smc.theta and log(smc.omega)"""
+    if isinstance(smc, IBIS):
+        return _ibis.posterior_histogram(smc, component, bins, range, outside)
+    return _ibis.histogram_from(*_host_cloud_calls(smc), component, bins, range, outside)
+
+
 def _per_theta(smc, local):
     """[M_local, k] rows of per-filter summaries of this rank -> [M, k] on every rank"""
     local = np.ascontiguousarray(local, dtype=np.float64)
