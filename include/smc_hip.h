@@ -831,6 +831,37 @@ int smc_host_smooth_pairs(int model_id, const double* raw, int64_t T, int64_t n,
                           double* ws /*[T][n]*/, double* mean /*[T][d] or NULL*/, double* var /*[T][d] or NULL*/,
                           double* cross /*[T-1][d][d]*/, double* resid2 /*[T-1][d]*/);
 
+/* ---- the smoother: weighted quantiles of the smoothed state (csrc/smc_spec.h "quantiles of the smoothed state") ------
+ * smc_smooth describes p(x_t | y_1:T) by a mean and a variance.  The 25 / 50 / 75 % band of a skewed state (a log-volatility, the SV
+ * state after a large return) needs the quantiles of (x_t, ws_t), and the smoothed weights are on the device when the backward pass
+ * ends: smc_smooth_quantiles selects them there, for every recorded step and filter in one launch, instead of a copy of every weight
+ * and cloud to the host and a sort.  The quantile of a cloud is a function of its two arrays alone, in integer arithmetic: particle i
+ * takes part iff 0 < ws_i < +inf, whatever its state; ws_i = f_i 2^(e_i) with f_i in [0.5, 1), K = max e_i, q_i = rint(ws_i 2^(40 - K))
+ * (ties to even); the states in the IEEE total order of their bits (-NaN < -inf < .. < -0.0 < +0.0 < .. < +inf < +NaN); level p in
+ * [0, 1]: the smallest state v with sum{q_i : x_i <= v} > floor(p 2^64) W / 2^64 (rounded down), W = sum q_i - smc_get_quantiles'
+ * definition, no interpolation, p = 0 the smallest state that carries weight and p = 1 the largest.  A cloud in which nobody takes part,
+ * or with a NaN weight (a filter that collapsed at a recorded step), has NaN at every level.
+ *   smc_smooth_quantiles       smc_smooth_pairs (its refusals, its state rules, its results: ws, mean, var, cross, resid2 are bit for
+ *                              bit smc_smooth_pairs', each may be NULL; ONE backward pass) with q [T][n_theta][np]: the quantiles of
+ *                              state coordinate `component` at the levels p [np].  SMC_EINVAL, the handle unchanged: np outside
+ *                              [1, 8], component outside [0, d), a level outside [0, 1] (or NaN), p or q NULL.  Any record: guided,
+ *                              systematic, with gaps, conditional, or planted (smc_history_put).  May be repeated, also after more
+ *                              steps.  The results, 8 n_theta doubles per step of the record, live in a block of their own that the
+ *                              first such call allocates: handles that never ask for quantiles allocate and launch what they always
+ *                              did.  Cost: profiles/smooth_quantiles_cost.log (DESIGN.md 2q "Cost")
+ *   smc_host_smooth_quantiles  the same specification for ONE coordinate of ONE filter on the host (no GPU), the same bits: x, ws
+ *                              [T][n] -> q [T][np].  SMC_EINVAL: a NULL argument, T or n < 1, np or a level as above
+ *   smc_smooth_quantiles_info  the constants of the specification and of the kernel, and what a handle holds: scratch_bytes = the bytes
+ *                              of h's quantile block (0: it never asked for quantiles; h NULL: 0), q_bits = 40, lds_max = the largest
+ *                              n_x whose cloud the kernel stages in LDS (beyond it the same kernel reads global memory in every
+ *                              pass).  Any pointer may be NULL */
+int smc_smooth_quantiles(smc_handle h, double* ws /*[T][n_theta][n_x] or NULL*/, double* mean /*[T][d][n_theta] or NULL*/, double* var /*[T][d][n_theta] or NULL*/,
+                         double* cross /*[T-1][d][d][n_theta] or NULL*/, double* resid2 /*[T-1][d][n_theta] or NULL*/, int component,
+                         const double* p /*[np]*/, int np, double* q /*[T][n_theta][np]*/);
+int smc_host_smooth_quantiles(int64_t T, int64_t n, const double* x /*[T][n], one coordinate*/, const double* ws /*[T][n]*/, const double* p /*[np]*/,
+                              int np, double* q /*[T][np]*/);
+int smc_smooth_quantiles_info(smc_handle h /*or NULL*/, int64_t* scratch_bytes, int32_t* q_bits, int64_t* lds_max);
+
 /* ---- backward simulation: joint smoothing paths (FFBSi; Godsill, Doucet and West 2004) --------------------------------------
  * smc_smooth gives the marginals p(x_t | y_1:T).  Whatever depends on two or more times at once (the smoothed change of the
  * trend, the cycle as a path, lag covariances, the complete-data sums of a particle EM or Gibbs step) needs whole trajectories

@@ -16,6 +16,6 @@ from .particles import (AffineGaussianProposal, OptimalProposal, ParticleGibbs, 
 from .particles import em_mstep, particle_em  # noqa: F401
 from .smc_samplers import (SMC, ThetaMap, density_tempered, estimated_trend, expected_parameters, filtered_state, forecast_state,  # noqa: F401
                            filtered_summaries, observation_dist, posterior_histogram, posterior_moments, posterior_quantiles, quantile, rejuvenate_, resample_, smc2, smc2_run, smc2_step,
-                           rb_smoothed_state, smoothed_paths, smoothed_state)
+                           rb_smoothed_state, smoothed_paths, smoothed_quantiles, smoothed_state)
 
 __version__ = "0.1.0"

@@ -51,6 +51,7 @@ EXPORTS = [
     "smc_ibis_create_rows",
     "smc_history_get_ancestors", "smc_history_put_ancestors", "smc_ancestor_sweep", "smc_host_ancestor_sweep",
     "smc_ibis_theta_quantiles", "smc_ibis_theta_histogram", "smc_host_theta_weights", "smc_host_theta_quantiles", "smc_host_theta_histogram",
+    "smc_smooth_quantiles", "smc_host_smooth_quantiles", "smc_smooth_quantiles_info",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -251,6 +252,9 @@ def lib():
     L.smc_host_smooth.argtypes = [C.c_int, _dp, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp]
     L.smc_smooth_pairs.argtypes = [h, _dp, _dp, _dp, _dp, _dp]
     L.smc_host_smooth_pairs.argtypes = L.smc_host_smooth.argtypes + [_dp, _dp]
+    L.smc_smooth_quantiles.argtypes = L.smc_smooth_pairs.argtypes + [C.c_int, _dp, C.c_int, _dp]
+    L.smc_host_smooth_quantiles.argtypes = [C.c_int64, C.c_int64, _dp, _dp, _dp, C.c_int, _dp]
+    L.smc_smooth_quantiles_info.argtypes = [h, C.POINTER(C.c_int64), _i32p, C.POINTER(C.c_int64)]
     L.smc_sample_paths.argtypes = [h, C.c_int64, C.c_uint64, _i32p, _i32p, _dp]
     L.smc_host_sample_paths.argtypes = [C.c_int, _dp, C.c_int64, C.c_int64, _dp, _dp, C.c_int64, C.c_uint64, C.c_uint32, _i32p, _dp]
     L.smc_rb_sample_paths.argtypes = [h, _dp, C.c_int64, C.c_int64, C.c_uint64, _i32p, _i32p, _dp, _dp, _dp, _dp, _dp]
@@ -1149,21 +1153,34 @@ class Handle:
     def history_end(self):
         check(lib().smc_history_end(self._h))
 
-    def smooth(self, weights=True, moments=True, pairs=False):
+    def smooth(self, weights=True, moments=True, pairs=False, quantiles=None):
         """the FFBS backward pass over the recorded steps (smc_smooth): (ws [T][n_theta][n_x] or None, mean [T][d][n_theta] or
         None, var or None); pairs=True (smc_smooth_pairs): the lag-one pair moments follow, (..., cross [T-1][d][d][n_theta],
-        resid2 [T-1][d][n_theta])"""
+        resid2 [T-1][d][n_theta]); quantiles=(component, p) (smc_smooth_quantiles, the same pass): the weighted quantiles of that
+        state coordinate at the levels p come last, (..., q [T][n_theta][len(p)])"""
         T = self.history_len()
         ws = np.zeros((T, self.n_theta, self.n_x)) if weights else None
         mean = np.zeros((T, self.d, self.n_theta)) if moments else None
         var = np.zeros((T, self.d, self.n_theta)) if moments else None
-        if not pairs:
+        if not pairs and quantiles is None:
             check(lib().smc_smooth(self._h, _d(ws), _d(mean), _d(var)))
             return ws, mean, var
-        cross = np.zeros((max(T - 1, 0), self.d, self.d, self.n_theta))
-        resid2 = np.zeros((max(T - 1, 0), self.d, self.n_theta))
-        check(lib().smc_smooth_pairs(self._h, _d(ws), _d(mean), _d(var), _d(cross), _d(resid2)))
-        return ws, mean, var, cross, resid2
+        cross = np.zeros((max(T - 1, 0), self.d, self.d, self.n_theta)) if pairs else None
+        resid2 = np.zeros((max(T - 1, 0), self.d, self.n_theta)) if pairs else None
+        if quantiles is None:
+            check(lib().smc_smooth_pairs(self._h, _d(ws), _d(mean), _d(var), _d(cross), _d(resid2)))
+            return ws, mean, var, cross, resid2
+        component, p = quantiles
+        p = np.ascontiguousarray(p, dtype=np.float64).ravel()
+        q = np.zeros((T, self.n_theta, p.size))
+        check(lib().smc_smooth_quantiles(self._h, _d(ws), _d(mean), _d(var), _d(cross), _d(resid2), int(component), _d(p), int(p.size), _d(q)))
+        return (ws, mean, var, cross, resid2, q) if pairs else (ws, mean, var, q)
+
+    def smooth_quantiles_scratch(self):
+        """bytes of the handle's quantile block (smc_smooth_quantiles_info): 0 until smooth(quantiles=...) was asked for"""
+        b = C.c_int64()
+        check(lib().smc_smooth_quantiles_info(self._h, C.byref(b), None, None))
+        return b.value
 
     def sample_paths(self, M, seed, counts=None, want_x=True):
         """M backward-simulated paths per filter over the recorded steps (smc_sample_paths): (idx [T][n_theta][M] int32, xs
@@ -1319,6 +1336,26 @@ def host_smooth_pairs(model_id, raw, x, w):
     cross, resid2 = np.zeros((max(T - 1, 0), d, d)), np.zeros((max(T - 1, 0), d))
     check(lib().smc_host_smooth_pairs(int(model_id), _d(raw), T, n, _d(x), _d(w), _d(ws), _d(mean), _d(var), _d(cross), _d(resid2)))
     return ws, mean, var, cross, resid2
+
+
+def host_smooth_quantiles(x, ws, p):
+    """the weighted quantiles of ONE state coordinate of ONE filter under the smoothed weights by the specification on the host
+    (smc_host_smooth_quantiles; no GPU): x, ws [T][n], levels p -> q [T][len(p)]"""
+    ws = np.ascontiguousarray(ws, dtype=np.float64)
+    T, n = ws.shape
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(T, n)
+    p = np.ascontiguousarray(p, dtype=np.float64).ravel()
+    q = np.zeros((T, p.size))
+    check(lib().smc_host_smooth_quantiles(T, n, _d(x), _d(ws), _d(p), int(p.size), _d(q)))
+    return q
+
+
+def smooth_quantiles_constants():
+    """(SMOOTH_Q_BITS, SMOOTH_Q_LDS_MAX) of the library (smc_smooth_quantiles_info): the bits of an integer weight, and the
+    largest n_x whose cloud k_smooth_quantiles stages in LDS"""
+    bits, lds = C.c_int32(), C.c_int64()
+    check(lib().smc_smooth_quantiles_info(None, None, C.byref(bits), C.byref(lds)))
+    return bits.value, lds.value
 
 
 def host_ibis_summary(rows, x, S, logw, ahead=0):

@@ -1,12 +1,13 @@
 // smc_capi_smooth.hip -- the record of a step-by-step run (smc_history_*) and the backward passes over it.  smc_smooth: the FFBS
 // particle smoother, forward filtering by the step kernels as they are, backward smoothing by the all-pairs kernels of
-// smc_smooth_kernels.h.  smc_sample_paths and smc_rb_sample_paths (MODEL_UCSV_RB): backward simulation, ONE walk over the record
+// smc_smooth_kernels.h; smc_smooth_pairs and smc_smooth_quantiles are the same pass with more kept (smooth_run).
+// smc_sample_paths and smc_rb_sample_paths (MODEL_UCSV_RB): backward simulation, ONE walk over the record
 // (backward_walk: the refusals, the plan of the block, the uploads, the dead scan and the loop over the steps, smc_path_kernels.h)
 // that each of the two entry points wraps with the tail of its plan and with what follows the walk (smc_rb_kernels.h).
 // The ancestor plane of the record of an SMC_FLAG_ANCESTOR_SAMPLING handle (smc_history_get_ancestors / _put_ancestors) and the two
 // launches of smc_ancestor_sweep over it (ancestor_sweep_enqueue, smc_anc_kernels.h; the entry point: smc_capi_cond.hip).
-// Specification: smc_spec.h "the smoother", "backward simulation"; the host twins (smc_host_smooth, smc_host_sample_paths,
-// smc_host_rb_sample_paths) live in smc_util.hip.
+// Specification: smc_spec.h "the smoother", "quantiles of the smoothed state", "backward simulation"; the host twins
+// (smc_host_smooth, smc_host_smooth_quantiles, smc_host_sample_paths, smc_host_rb_sample_paths) live in smc_util.hip.
 #include "smc_host.h"
 #include "smc_smooth_kernels.h"
 #include "smc_path_kernels.h"
@@ -206,15 +207,34 @@ hipError_t backward_step(const SmoothArgs& a01, const SmoothArgs& a2, int thread
     return hipGetLastError();
 }
 
+// what smc_smooth_quantiles adds to a backward pass: np levels p of state coordinate `component` -> q [T][n_theta][np]
+struct SmoothQuantiles {
+    int component, np;
+    const double* p;
+    double* q;
+};
+
 // smc_smooth, and with cross or resid2 smc_smooth_pairs: the same refusals, plan and launches; the pair moments add a block of
 // their own (hist.d_pair: the chunk partials of PASS 3 and the results), so that a handle that never asks for them allocates and
-// launches what it always did
-int smooth_run(smc_handle h, const char* name, double* ws, double* mean, double* var, double* cross, double* resid2) {
+// launches what it always did.  With sq (smc_smooth_quantiles) ONE launch more behind the pass, k_smooth_quantiles over the
+// smoothed weights where the pass left them, and a block of its own again (hist.d_quant)
+int smooth_run(smc_handle h, const char* name, double* ws, double* mean, double* var, double* cross, double* resid2,
+               const SmoothQuantiles* sq = nullptr) {
     const std::string who = std::string(name) + ": ";
     if (!h) return fail(SMC_EINVAL, who + "NULL handle");
     if (!has_density(h->model))
         return fail(SMC_EINVAL, who + "SMC_MODEL_UCSV_RB has no transition density of its state rows (m and P are functions of the whole "
                                       "path); smooth a UCSV3D filter instead, or draw Rao-Blackwellised paths (smc_rb_sample_paths)");
+    SmoothQArgs qa{};
+    if (sq) {
+        if (!sq->p || !sq->q) return fail(SMC_EINVAL, who + "NULL p or q");
+        if (sq->np < 1 || sq->np > QMAX) return fail(SMC_EINVAL, who + "1 <= np <= 8");
+        if (sq->component < 0 || sq->component >= h->d) return fail(SMC_EINVAL, who + "component outside [0, d)");
+        for (int j = 0; j < sq->np; ++j) {
+            if (!(sq->p[j] >= 0.0 && sq->p[j] <= 1.0)) return fail(SMC_EINVAL, who + "levels must lie in [0, 1]");
+            qa.p64[j] = prob_to_u64(sq->p[j]);
+        }
+    }
     if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, who + "nothing is recorded (smc_history_begin, then smc_init / smc_step)");
     const FilterView& v = h->v;
     const int64_t T = h->hist.len, n = v.n;
@@ -245,6 +265,14 @@ int smooth_run(smc_handle h, const char* name, double* ws, double* mean, double*
         if (h->hist.d_pair.grow(o.bytes) != hipSuccess) return fail(SMC_ENOMEM, who + "hipMalloc of the chunk partials of the pair moments");
         char* pair = h->hist.d_pair.as<char>();
         d_pair = (double*)(pair + o_part); d_cross = (double*)(pair + o_cross); d_resid = (double*)(pair + o_resid);
+    }
+    // the quantiles: q [cap][ntheta][QMAX], and the kernel's LDS, all of it dynamic: the histograms and, for a cloud that is staged,
+    // 16 bytes per particle (above 64 KiB the limit is raised)
+    const size_t q_lds = SMOOTH_Q_FIXED_LDS + (n <= SMOOTH_Q_LDS_MAX ? (size_t)n * 16 : 0);
+    if (sq) {
+        static std::atomic<bool> raised[16];
+        if (h->hist.d_quant.grow((size_t)h->hist.cap * nt * QMAX * 8) != hipSuccess) return fail(SMC_ENOMEM, who + "hipMalloc of the quantiles of the smoothed state");
+        HIPCHK(raise_lds_limit(k_smooth_quantiles, q_lds, raised));
     }
     char* tmp = h->hist.d_tmp.as<char>();
     double *pmax = (double*)(tmp + p.o_pmax), *part = (double*)(tmp + p.o_part), *logD = (double*)(tmp + p.o_logD), *rowmax = (double*)(tmp + p.o_rmax), *momtmp = (double*)(tmp + p.o_mom);
@@ -280,7 +308,14 @@ int smooth_run(smc_handle h, const char* name, double* ws, double* mean, double*
                            momtmp, d_mom);
         HIPCHK(hipGetLastError());
     }
+    if (sq) {
+        qa.n = n; qa.ntheta = (int)nt; qa.d = (int)d; qa.component = sq->component; qa.np = sq->np;
+        qa.x = h->hist.d_x; qa.ws = d_ws; qa.out = h->hist.d_quant.as<double>();
+        hipLaunchKernelGGL(k_smooth_quantiles, dim3((unsigned)T, (unsigned)nt), dim3(SMOOTH_Q_THREADS), q_lds, s, qa);
+        HIPCHK(hipGetLastError());
+    }
     if ((rc = finish_elapsed(h))) return rc;
+    if (sq) HIPCHK(hipMemcpy(sq->q, h->hist.d_quant.as<double>(), (size_t)T * nt * (size_t)sq->np * 8, hipMemcpyDeviceToHost));
     if (ws) HIPCHK(hipMemcpy(ws, d_ws, (size_t)T * nw * 8, hipMemcpyDeviceToHost));
     if (mean || var) {
         std::vector<double> mv((size_t)T * mom_words);
@@ -300,6 +335,20 @@ extern "C" int smc_smooth(smc_handle h, double* ws, double* mean, double* var) {
 
 extern "C" int smc_smooth_pairs(smc_handle h, double* ws, double* mean, double* var, double* cross, double* resid2) {
     return smooth_run(h, "smc_smooth_pairs", ws, mean, var, cross, resid2);
+}
+
+extern "C" int smc_smooth_quantiles(smc_handle h, double* ws, double* mean, double* var, double* cross, double* resid2, int component,
+                                    const double* p, int np, double* q) {
+    const SmoothQuantiles sq{component, np, p, q};
+    return smooth_run(h, "smc_smooth_quantiles", ws, mean, var, cross, resid2, &sq);
+}
+
+// the constants of the quantiles of the smoothed state, and the bytes of the handle's quantile block (0: it never asked for them)
+extern "C" int smc_smooth_quantiles_info(smc_handle h, int64_t* scratch_bytes, int32_t* q_bits, int64_t* lds_max) {
+    if (scratch_bytes) *scratch_bytes = h ? (int64_t)h->hist.d_quant.bytes() : 0;
+    if (q_bits) *q_bits = SMOOTH_Q_BITS;
+    if (lds_max) *lds_max = SMOOTH_Q_LDS_MAX;
+    return SMC_OK;
 }
 
 // ---- backward simulation ---------------------------------------------------------------------------------------------------

@@ -182,6 +182,8 @@ struct smc_filter_s {
                                                //   partials of the moments [len][ntheta][nchunk] | rows [ntheta] | dead [ntheta]
         DevBlock d_pair;                       // the pair moments (smc_smooth_pairs), a block of their own (old block first): chunk partials
                                                //   [1 + 2 d][nchunk][ntheta][n] | cross [cap - 1][d][d][ntheta] | resid2 [cap - 1][d][ntheta]; empty until the first such call
+        DevBlock d_quant;                      // the quantiles of the smoothed state (smc_smooth_quantiles), a block of their own (old block
+                                               //   first): q [cap][ntheta][QMAX]; empty until the first such call
         DevBlock d_path;                       // the backward walk (smc_sample_paths, or smc_rb_sample_paths on a MODEL_UCSV_RB handle), its own block
                                                //   (new block first): cur | pmax | psum | rmax | rows | dead | counts | idx [T][ntheta][M] | the caller's tail
         int64_t walk_M = 0, walk_T = 0;        // the last smc_sample_paths walk over this record (0: none): paths per filter, steps, and where

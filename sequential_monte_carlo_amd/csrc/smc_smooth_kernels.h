@@ -19,6 +19,7 @@
 // the handle's stream.
 #pragma once
 #include "smc_spec.h"
+#include "smc_kernels.h"   // order_key, key_value, prob_to_u64, QMAX (k_smooth_quantiles)
 
 namespace smc {
 
@@ -280,6 +281,166 @@ k_smooth_pair_moments(int64_t n, int ntheta, int nchunk, const double* pair, con
         const double r = dead[th] ? bits2d(0x7ff8000000000000ULL) : tot;
         if (tid < D * D) cross[(size_t)tid * ntheta + th] = r;
         else resid2[(size_t)(tid - D * D) * ntheta + th] = r;
+    }
+}
+
+// ---- quantiles of the smoothed state (smc_spec.h "quantiles of the smoothed state") --------------------------------
+// Weighted quantiles of one state coordinate under the smoothed weights, at up to QMAX levels, for every recorded step and filter
+// in ONE launch: grid (T, ntheta) like k_smooth_moments, one workgroup per cloud.
+//   1. a pass over ws_t: K (integer LDS maximum) and the NaN test.  A NaN weight, or nobody who takes part: NaN at every level.
+//   2. a pass that forms q_i and, when the cloud fits (n <= SMOOTH_Q_LDS_MAX), stages (order_key(x_i), q_i) in dynamic LDS; W =
+//      sum q_i by 64-bit integer LDS atomics.  T_j = mulhi64(p64_j, W).
+//   3. an MSB-first radix select on the 64-bit keys, 8 bits a pass: a level keeps (prefix, weight below the prefix); levels
+//      with the same prefix share ONE 256-bin histogram of integer weights in LDS (its leader's: the first such level), filled
+//      with integer LDS atomics from the staged pairs - or, above SMOOTH_Q_LDS_MAX, from keys and weights derived again from
+//      global memory, the same integers.  Wave j mod 4 then finds the bin of level j by a wave scan over 4 bins per lane.  A
+//      level whose candidates are one distinct key (the leader's integer minimum and maximum agree) is finished at once; the
+//      loop ends when every level is.
+// Integer sums only: no floating-point atomics, the order of the additions is immaterial.  Every store is a plain vector store.
+constexpr int SMOOTH_Q_THREADS = 256;
+constexpr int SMOOTH_Q_BINS = 256, SMOOTH_Q_PASSES = 8;
+// the largest cloud that is staged: 16 bytes per particle, 128 KiB, beside the 16 KiB of histograms in the 160 KiB of a CU
+constexpr int64_t SMOOTH_Q_LDS_MAX = 8192;
+static_assert(QMAX == 8, "k_smooth_quantiles lays its per-level state out for 8 levels");
+constexpr size_t SMOOTH_Q_FIXED_LDS = (size_t)QMAX * SMOOTH_Q_BINS * 8 + 64 * 8;   // the histograms and the per-level state
+struct SmoothQArgs {
+    int64_t n;
+    int ntheta, d, component, np;
+    const double* x;    // [T][d][ntheta][n] the recorded clouds
+    const double* ws;   // [T][ntheta][n] the smoothed weights
+    double* out;        // [T][ntheta][np]
+    uint64_t p64[QMAX]; // the levels, 2^-64 fixed point (prob_to_u64)
+};
+__global__ void __launch_bounds__(SMOOTH_Q_THREADS) k_smooth_quantiles(SmoothQArgs a) {
+    // all of the kernel's LDS is dynamic (the raised limit is the whole 160 KiB: static LDS on top of it is refused):
+    // hist [QMAX][BINS] | W, kmin, kmax, prefix, below, target | K, nan, lead, fin | staged: key [n] | q [n]
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sq_lds[];
+    unsigned long long(*hist)[SMOOTH_Q_BINS] = (unsigned long long(*)[SMOOTH_Q_BINS])sq_lds;
+    unsigned long long* u = sq_lds + QMAX * SMOOTH_Q_BINS;
+    unsigned long long &s_W = u[0], *kmin = u + 8, *kmax = u + 16, *prefix = u + 24, *below = u + 32, *target = u + 40;
+    int* iv = (int*)(u + 48);
+    int &s_K = iv[0], &s_nan = iv[1], *lead = iv + 8, *fin = iv + 16;
+    unsigned long long* sq_stage = sq_lds + SMOOTH_Q_FIXED_LDS / 8;
+    const int t = blockIdx.x, th = blockIdx.y, tid = threadIdx.x;
+    const int64_t n = a.n;
+    const double* wt = a.ws + ((size_t)t * a.ntheta + th) * n;
+    const double* xt = a.x + (((size_t)t * a.d + a.component) * a.ntheta + th) * n;
+    double* out = a.out + ((size_t)t * a.ntheta + th) * a.np;
+    const bool staged = n <= SMOOTH_Q_LDS_MAX;
+    if (tid == 0) { s_K = SMOOTH_Q_NOBODY; s_nan = 0; s_W = 0; }
+    __syncthreads();
+    int K = SMOOTH_Q_NOBODY, bad = 0;
+    for (int64_t i = tid; i < n; i += SMOOTH_Q_THREADS) {
+        const double w = wt[i];
+        const int e = smooth_q_exponent(w);
+        bad |= w != w ? 1 : 0;
+        K = e > K ? e : K;
+    }
+    if (K != SMOOTH_Q_NOBODY) atomicMax(&s_K, K);
+    if (bad) s_nan = 1;   // (every writer stores the same value)
+    __syncthreads();
+    K = s_K;
+    if (s_nan || K == SMOOTH_Q_NOBODY) {   // (the same for every thread)
+        if (tid < a.np) out[tid] = bits2d(0x7ff8000000000000ULL);
+        return;
+    }
+    unsigned long long W = 0;
+    for (int64_t i = tid; i < n; i += SMOOTH_Q_THREADS) {
+        const uint64_t q = smooth_q_weight(wt[i], K);
+        W += q;
+        if (staged) {
+            sq_stage[i] = q ? order_key(xt[i]) : 0;
+            sq_stage[n + i] = q;
+        }
+    }
+    if (W) atomicAdd(&s_W, W);
+    __syncthreads();
+    if (tid < QMAX) {   // every level starts with the empty prefix: one histogram, level 0's
+        prefix[tid] = 0;
+        below[tid] = 0;
+        target[tid] = tid < a.np ? mulhi64(a.p64[tid], s_W) : 0;
+        fin[tid] = tid < a.np ? 0 : 1;
+        lead[tid] = tid < a.np ? 0 : -1;
+    }
+    __syncthreads();
+    for (int pass = 0; pass < SMOOTH_Q_PASSES; ++pass) {
+        const int shift = 56 - 8 * pass;
+        const uint64_t above = pass ? ~(uint64_t)0 << (shift + 8) : 0;   // the bits of the key that the prefix has fixed
+        unsigned own = 0;   // the levels that lead a histogram in this pass
+        uint64_t pre[QMAX];
+#pragma unroll
+        for (int j = 0; j < QMAX; ++j) {
+            own |= lead[j] == j ? 1u << j : 0u;
+            pre[j] = prefix[j];
+        }
+        if (!own) break;   // (every level is finished; the same for every thread)
+        for (int b = tid; b < QMAX * SMOOTH_Q_BINS; b += SMOOTH_Q_THREADS)
+            if ((own >> (b / SMOOTH_Q_BINS)) & 1u) hist[b / SMOOTH_Q_BINS][b % SMOOTH_Q_BINS] = 0;
+        if (tid < QMAX) { kmin[tid] = ~0ULL; kmax[tid] = 0; }
+        __syncthreads();
+        uint64_t lmin[QMAX], lmax[QMAX];
+#pragma unroll
+        for (int j = 0; j < QMAX; ++j) { lmin[j] = ~(uint64_t)0; lmax[j] = 0; }
+        for (int64_t i = tid; i < n; i += SMOOTH_Q_THREADS) {
+            const uint64_t q = staged ? (uint64_t)sq_stage[n + i] : smooth_q_weight(wt[i], K);
+            if (!q) continue;
+            const uint64_t key = staged ? (uint64_t)sq_stage[i] : order_key(xt[i]);
+            const int bin = (int)(key >> shift) & (SMOOTH_Q_BINS - 1);
+#pragma unroll
+            for (int j = 0; j < QMAX; ++j)
+                if (((own >> j) & 1u) && (key & above) == pre[j]) {
+                    atomicAdd(&hist[j][bin], (unsigned long long)q);
+                    lmin[j] = key < lmin[j] ? key : lmin[j];
+                    lmax[j] = key > lmax[j] ? key : lmax[j];
+                }
+        }
+#pragma unroll
+        for (int j = 0; j < QMAX; ++j)
+            if (lmin[j] <= lmax[j]) {   // (this thread met a candidate of leader j)
+                atomicMin(&kmin[j], (unsigned long long)lmin[j]);
+                atomicMax(&kmax[j], (unsigned long long)lmax[j]);
+            }
+        __syncthreads();
+        // the bin of every unfinished level: below <= T < below + (the weight of its candidates), so a bin is found
+        const int wave = tid >> 6, lane = tid & 63;
+        for (int j = wave; j < QMAX; j += SMOOTH_Q_THREADS / 64) {   // (the same for every lane of the wave)
+            const int L = lead[j];
+            if (L < 0) continue;
+            if (kmin[L] == kmax[L]) {   // one distinct candidate
+                if (lane == 0) { out[j] = key_value(kmin[L]); fin[j] = 1; }
+                continue;
+            }
+            const unsigned long long* h = &hist[L][4 * lane];
+            const unsigned long long h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3], s = h0 + h1 + h2 + h3;
+            unsigned long long incl = s;
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned long long v = __shfl_up(incl, o);
+                incl += lane >= o ? v : 0;
+            }
+            const unsigned long long b0 = below[j], T = target[j];
+            const unsigned long long over = __ballot(b0 + incl > T);
+            if (over && lane == __ffsll((long long)over) - 1) {
+                unsigned long long c = b0 + incl - s;
+                int b = 4 * lane;
+                if (c + h0 <= T) {
+                    c += h0; ++b;
+                    if (c + h1 <= T) {
+                        c += h1; ++b;
+                        if (c + h2 <= T) { c += h2; ++b; }
+                    }
+                }
+                const unsigned long long np_ = prefix[j] | ((unsigned long long)b << shift);
+                below[j] = c;
+                prefix[j] = np_;
+                if (pass == SMOOTH_Q_PASSES - 1) { out[j] = key_value(np_); fin[j] = 1; }   // (all 64 bits chosen)
+            }
+        }
+        __syncthreads();
+        int L = -1;   // the leader of level tid in the next pass: the first unfinished level with its prefix
+        if (tid < QMAX && !fin[tid])
+            for (int jj = tid; jj >= 0; --jj) L = (!fin[jj] && prefix[jj] == prefix[tid]) ? jj : L;
+        if (tid < QMAX) lead[tid] = L;
+        __syncthreads();
     }
 }
 

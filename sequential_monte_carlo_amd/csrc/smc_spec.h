@@ -1381,6 +1381,60 @@ SMC_HD double pair_r_term(double p, double xjc, double mc) {
 SMC_HD double pair_cross_term(double wi, double xia, double Xc) { return wi > 0.0 ? (wi * xia) * Xc : 0.0; }
 SMC_HD double pair_resid_term(double wi, double Rc) { return wi > 0.0 ? wi * Rc : 0.0; }
 
+// ---- the smoother: quantiles of the smoothed state -----------------------------------------------------------------
+// The quantile of ONE cloud: n values x_i (one state coordinate of one recorded step of one filter) with the smoothed weights
+// ws_i, non-negative doubles that nothing has normalised.  After the per-particle conversion below everything is INTEGER
+// arithmetic, so the result is a function of the two arrays alone: any launch geometry, any order of evaluation, host and
+// device the same bits.
+//   who takes part   particle i iff 0 < ws_i < +inf (smooth_q_takes_part; NaN compares false).  Its state may be anything, NaN
+//            included; the state of a particle that does not take part is never looked at.
+//   no quantile      no particle takes part, or some ws_i is NaN (a filter that collapsed at a recorded step: smc_smooth writes
+//            NaN everywhere): every level is NaN.
+//   weight   ws_i = f_i 2^(e_i), f_i in [0.5, 1) (smooth_q_parts: the bits of the double, a subnormal normalised by its leading
+//            zeros, so exact for every positive finite double); K = max e_i over the particles that take part;
+//            q_i = fix_weight_i(f_i, e_i - K, SMOOTH_Q_BITS) = rint(ws_i 2^(SMOOTH_Q_BITS - K)), ties to even (below e_i - K =
+//            -(SMOOTH_Q_BITS + 2) the 0 that fix_weight_i returns is what the rounding gives).  A particle that does not take
+//            part has q_i = 0.
+//   SMOOTH_Q_BITS = 40: the largest value for which W = sum q_i fits 63 bits at the largest cloud the smoother admits, 65535
+//            chunks of 128 = 8388480 < 2^23 particles, each q_i <= 2^40 (f < 1): W <= 8388480 2^40 < 2^63.  (f 2^40 < 2^50 is
+//            what fix_weight_i asks for.)  The particle with e_i = K has q_i >= 2^39, so W >= 2^39 > 0 whenever somebody takes
+//            part.  Each q_i is within half a unit of ws_i 2^(40 - K) and sum ws_i 2^(-K) >= 1/2, so every cumulative share
+//            of W differs from the share of the dense weights by at most n 2^(2 - SMOOTH_Q_BITS) (tests/test_smooth_quantiles_host.py
+//            derives and checks it): 2^-28 at 1024 particles.
+//   order    the IEEE total order of the bits: order_key / key_value (smc_kernels.h), as smc_host_quantile7 and the theta
+//            quantiles use it: -NaN < -inf < .. < -0.0 < +0.0 < .. < +inf < +NaN.  A NaN state that carries weight sorts by its
+//            sign bit.
+//   level p in [0, 1]: T = mulhi64(prob_to_u64(p), W) < W; the quantile is the smallest v among the x_i with
+//            sum{q_i : key(x_i) <= key(v)} > T (smc_get_quantiles' definition): p = 0 the smallest value that carries weight,
+//            p = 1 the largest, no interpolation.
+constexpr int SMOOTH_Q_BITS = 40;
+constexpr int SMOOTH_Q_NOBODY = -(1 << 30);   // K of a cloud in which nobody takes part
+SMC_HD bool smooth_q_takes_part(double ws) { return ws > 0.0 && ws < inf(); }
+// (f, e) of a positive finite ws = f 2^e, f in [0.5, 1): exact, subnormals included
+SMC_HD double smooth_q_parts(double ws, int& e) {
+    uint64_t b = d2bits(ws);
+    int E = (int)(b >> 52);                                // (the sign bit is 0)
+    if (E == 0) {                                          // a subnormal m 2^-1074, 0 < m < 2^52: its leading bit to bit 52
+        const int sh = __builtin_clzll(b) - 11;
+        b <<= sh;
+        E = 1 - sh;
+    }
+    e = E - 1022;
+    return bits2d((b & 0x000fffffffffffffULL) | 0x3fe0000000000000ULL);
+}
+// e_i of a particle, SMOOTH_Q_NOBODY when it does not take part: K is the maximum of these
+SMC_HD int smooth_q_exponent(double ws) {
+    int e = SMOOTH_Q_NOBODY;
+    if (smooth_q_takes_part(ws)) (void)smooth_q_parts(ws, e);
+    return e;
+}
+SMC_HD uint64_t smooth_q_weight(double ws, int K) {
+    if (!smooth_q_takes_part(ws)) return 0;
+    int e;
+    const double f = smooth_q_parts(ws, e);
+    return fix_weight_i(f, e - K, SMOOTH_Q_BITS);
+}
+
 // ---- backward simulation: joint smoothing paths (FFBSi; Godsill, Doucet and West 2004) --------------------------
 // Inputs: the recorded clouds (x_t, w_t), t = 0..T-1, of one filter (w the dense weights), its SmoothRow, a path seed and the
 // filter's Philox stream id.  Path p (0-based) is a function of these alone: not of the number of paths, of the other paths,

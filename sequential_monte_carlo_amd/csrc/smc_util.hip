@@ -789,6 +789,54 @@ extern "C" int smc_host_smooth_pairs(int model_id, const double* raw, int64_t T,
     return SMC_OK;
 }
 
+// ---- quantiles of the smoothed state on the host (smc_spec.h "quantiles of the smoothed state"): the twin of k_smooth_quantiles ----
+// One coordinate of one filter: x, ws [T][n] -> q [T][np].  The same integers by a sort where the device selects by radix.
+extern "C" int smc_host_smooth_quantiles(int64_t T, int64_t n, const double* x, const double* ws, const double* p, int np, double* q) {
+    if (!x || !ws || !p || !q) return fail(SMC_EINVAL, "smc_host_smooth_quantiles: NULL argument");
+    if (T < 1 || n < 1) return fail(SMC_EINVAL, "smc_host_smooth_quantiles: T and n must be positive");
+    if ((n + SMOOTH_CH - 1) / SMOOTH_CH > 65535) return fail(SMC_EINVAL, "smc_host_smooth_quantiles: more than 65535 chunks of particles");
+    if (np < 1 || np > QMAX) return fail(SMC_EINVAL, "smc_host_smooth_quantiles: 1 <= np <= 8");
+    for (int j = 0; j < np; ++j)
+        if (!(p[j] >= 0.0 && p[j] <= 1.0)) return fail(SMC_EINVAL, "smc_host_smooth_quantiles: levels must lie in [0, 1]");
+    std::vector<std::pair<uint64_t, uint64_t>> kv;   // (key, weight) of the particles that carry weight
+    for (int64_t t = 0; t < T; ++t) {
+        const double *xt = x + (size_t)t * n, *wt = ws + (size_t)t * n;
+        double* out = q + (size_t)t * np;
+        int K = SMOOTH_Q_NOBODY;
+        bool bad = false;
+        for (int64_t i = 0; i < n; ++i) {
+            const int e = smooth_q_exponent(wt[i]);
+            bad = bad || wt[i] != wt[i];
+            K = e > K ? e : K;
+        }
+        if (bad || K == SMOOTH_Q_NOBODY) {
+            for (int j = 0; j < np; ++j) out[j] = bits2d(0x7ff8000000000000ULL);
+            continue;
+        }
+        kv.clear();
+        for (int64_t i = 0; i < n; ++i) {
+            const uint64_t qi = smooth_q_weight(wt[i], K);
+            if (qi) kv.emplace_back(order_key(xt[i]), qi);
+        }
+        std::sort(kv.begin(), kv.end());
+        for (size_t a = 1; a < kv.size(); ++a) kv[a].second += kv[a - 1].second;   // inclusive sums: kv.back().second = W > 0
+        const uint64_t W = kv.back().second;
+        for (int j = 0; j < np; ++j) {
+            const uint64_t Tj = mulhi64(prob_to_u64(p[j]), W);
+            // the first entry with a sum above Tj (Tj < W: there is one); equal keys are adjacent and the last of them has the sum
+            // of all of them, so the entry's key is the smallest value with the weight at or below it above Tj
+            size_t a = 0, b = kv.size() - 1;
+            while (a < b) {
+                const size_t mid = (a + b) >> 1;
+                if (kv[mid].second > Tj) b = mid;
+                else a = mid + 1;
+            }
+            out[j] = key_value(kv[a].first);
+        }
+    }
+    return SMC_OK;
+}
+
 // ---- backward simulation on the host (smc_spec.h "backward simulation"): the specification as plain loops, one filter --------
 template <int MODEL>
 static void host_paths_t(const SmoothRow& k, int64_t T, int64_t n, const double* x, const double* w, int64_t M, uint64_t seed, uint32_t stream,

@@ -423,8 +423,26 @@ def _reference_out(xref, single):
     return r[:, 0] if single else r
 
 
+def _smooth_quantile_args(quantiles, component, model, rows):
+    """the levels of smoother(quantiles=...) as a float64 vector, checked without a device call: 1 to 8 levels in [0, 1], a
+    coordinate the state has, a family with a transition density"""
+    p = np.ascontiguousarray(quantiles, dtype=np.float64).ravel()
+    if p.size < 1 or p.size > 8:
+        raise ValueError("quantiles: between 1 and 8 levels in one call, not %d" % p.size)
+    if not np.all((p >= 0.0) & (p <= 1.0)):
+        raise ValueError("quantiles: every level must lie in [0, 1]")
+    mid = int(rows[0]) if rows is not None else params_matrix(model)[0]
+    if mid == _lib.MODEL_UCSV_RB:
+        raise _lib.SmcError("smoother(quantiles=...): MarginalUCSV has no smoother of this kind (its state rows have no transition "
+                            "density): rb_smoother is its smoother")
+    d = _lib.lib().smc_model_dim(int(mid))
+    if int(component) != component or not 0 <= int(component) < d:
+        raise ValueError("component must be one of the state's %d coordinates (0-based)" % d)
+    return p
+
+
 def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="multinomial", proposal=None, weights=False, rows=None,
-             paths=0, path_seed=None, path_counts=None, smooth=True, missing=False, reference=None, pairs=False):
+             paths=0, path_seed=None, path_counts=None, smooth=True, missing=False, reference=None, pairs=False, quantiles=None, component=0):
     """x, w, logZ, s = smoother(N, y, model): the particle filter of log_likelihood run step by step with its clouds recorded on
     the device, then the FFBS backward pass over them (forward filtering, backward smoothing).  x, w, logZ are the
     filter's, as log_likelihood returns them; s describes p(x_t | y_1:T):
@@ -445,6 +463,10 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
                                     the coordinate of x_t); resid2[t] = E[(x_{t+1} - m(x_t))^2 | y_1:T] with m the transition's
                                     centre, [T-1] or [T-1][d]; lag1_cov[t] = cross[t] - mean[t] (x) mean[t+1].  The batch axis
                                     follows T, as in s["mean"].  They are the E-step of em_mstep / particle_em.
+        s["quantiles"]              (quantiles=[p, ...], up to 8 levels in [0, 1]) [T][len(p)]: the weighted quantiles of state coordinate
+                                    `component` under the smoothed weights, selected on the device in the same backward pass
+                                    (DESIGN.md 2q): the 25 / 50 / 75 % band of p(x_t | y_1:T) without a copy of the weights.  The
+                                    definition of log_likelihood's quantiles=: no interpolation.  The batch axis follows T.
     The backward pass costs 2 N^2 (T - 1) transition densities per filter.  Any proposal, either resampler; MarginalUCSV has no
     smoother of this kind (its state rows have no transition density): rb_smoother is its smoother.
     rows=(model id, parameter rows [n_theta][n_raw]) with model=None: a batch given as rows (what the samplers hold).
@@ -455,6 +477,10 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
     One path of it (paths=1) is one sweep of particle Gibbs: ParticleGibbs keeps the handle between sweeps."""
     if pairs and not smooth:
         raise ValueError("pairs=True needs the backward pass of the marginals (smooth=True): the pair moments are formed inside it")
+    if quantiles is not None:
+        if not smooth:
+            raise ValueError("quantiles=... needs the backward pass of the marginals (smooth=True): they are selected under its weights")
+        quantiles = _smooth_quantile_args(quantiles, component, model, rows)
     if seed is None:
         seed = next(_seed_counter)
     f = _Filters(int(N), model, seed, seg, device, streams, False, resampler, proposal, rows=rows, missing=missing,
@@ -470,7 +496,11 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
         lm, es, logZ = _run_recorded(h, y)
         s = {}
         if smooth or weights:
-            ws, mean, var, *pm = h.smooth(weights=weights, moments=True, pairs=pairs)
+            ws, mean, var, *pm = h.smooth(weights=weights, moments=True, pairs=pairs,
+                                          quantiles=None if quantiles is None else (int(component), quantiles))
+            if quantiles is not None:
+                q = pm.pop()                                                   # [T][n_theta][np]
+                s["quantiles"] = q[:, 0] if f.single else q
             mean, var = np.moveaxis(mean, 1, -1), np.moveaxis(var, 1, -1)      # [T][n_theta][d]
             if mean.shape[-1] == 1:
                 mean, var = mean[..., 0], var[..., 0]

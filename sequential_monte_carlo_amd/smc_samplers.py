@@ -603,6 +603,45 @@ def smc2_step(smc, y, t, verbose=True, out=sys.stdout):
     return smc
 
 
+def _smoothed_blocks(smc, y, N, max_bytes, seed, **smoother_kw):
+    """the s of particles.smoother for the sampler's current parameter cloud, block of parameter particles after block (their
+    batch axes concatenate to [T][M]...): N particles per parameter particle (None: the sampler's N), blocks whose recorded
+    history stays under max_bytes, filter m on Philox stream m under `seed` (None: derived from the sampler's seed).  The ONE
+    block loop of smoothed_state and smoothed_quantiles: the same records, blocks and seeds for both."""
+    from .particles import smoother
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    N = smc.N if N is None else int(N)
+    mid, raw = _rows(smc._models(smc.theta))
+    d = _lib.lib().smc_model_dim(int(mid))
+    per_theta = y.size * N * (d + 2) * 8                  # recorded x and w, and the smoothed weights
+    blk = max(1, min(smc.M, int(max_bytes) // max(per_theta, 1)))
+    seed = ((smc.seed << 20) | 0xF5B00) if seed is None else int(seed)
+    for m0 in range(0, smc.M, blk):
+        m1 = min(smc.M, m0 + blk)
+        yield smoother(N, y, None, rows=(int(mid), raw[m0:m1]), seed=seed, device=getattr(smc.backend, "device", 0),
+                       streams=np.arange(m0, m1, dtype=np.uint32), **smoother_kw)[3]
+
+
+def smoothed_quantiles(smc, y, p, component=0, N=None, max_bytes=2 ** 31, seed=None):
+    """[T][len(p)]: per period, the omega-weighted average over the sampler's current parameter cloud of the per-filter weighted
+    quantiles of state coordinate `component` under the smoothed weights (particles.smoother(..., quantiles=p): selected on the
+    device in the backward pass) - the rule by which get_quantiles_ucsv (examples/inflation_example.jl:241-252) and
+    filtered_summaries integrate the filtered ones, here for p(x_t | y_1:T).  Up to 8 levels in [0, 1].  Filters of omega = 0 are
+    left out.  The records, blocks and seeds are smoothed_state's (N, max_bytes, seed as there), so the band belongs to its mean.
+    IBIS is out of scope: its smoothed law is a mixture of normals with an exact quantile (rts_quantile)."""
+    if isinstance(smc, IBIS):
+        raise TypeError("smoothed_quantiles: IBIS is out of scope: its smoothed law is a mixture of normals, whose quantile is exact "
+                        "(rts_quantile)")
+    from .particles import _smooth_quantile_args
+    mid, _ = _rows(smc._models(smc.theta))
+    p = _smooth_quantile_args(p, component, None, (int(mid), None))
+    q = np.concatenate([s["quantiles"] for s in _smoothed_blocks(smc, y, N, max_bytes, seed, quantiles=p, component=int(component))],
+                       axis=1)                                                       # [T][M][np]
+    om = np.asarray(smc.omega, dtype=np.float64)
+    keep = om > 0
+    return np.add.reduce(om[keep][None, :, None] * q[:, keep], axis=1)
+
+
 def smoothed_state(smc, y, N=None, max_bytes=2 ** 31, seed=None):
     """(mean [T], var [T]) of p(x_t | y_1:T, theta) integrated over the sampler's current parameter cloud ([T][d] for a state of d
     coordinates): fresh batched smoothers (particles.smoother: a particle filter of N particles per parameter particle, default
@@ -614,23 +653,10 @@ def smoothed_state(smc, y, N=None, max_bytes=2 ** 31, seed=None):
     IBIS is out of scope: its exact smoother is RTS, a different feature (rts_smoothed_state)."""
     if isinstance(smc, IBIS):
         raise TypeError("smoothed_state: IBIS is out of scope: its exact smoother is RTS, a different feature (rts_smoothed_state)")
-    from .particles import smoother
-    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
-    N = smc.N if N is None else int(N)
+    blocks = list(_smoothed_blocks(smc, y, N, max_bytes, seed))
     om = np.asarray(smc.omega, dtype=np.float64)
-    mid, raw = _rows(smc._models(smc.theta))
-    d = _lib.lib().smc_model_dim(int(mid))
-    per_theta = y.size * N * (d + 2) * 8                  # recorded x and w, and the smoothed weights
-    blk = max(1, min(smc.M, int(max_bytes) // max(per_theta, 1)))
-    seed = ((smc.seed << 20) | 0xF5B00) if seed is None else int(seed)
-    means, vars_ = [], []
-    for m0 in range(0, smc.M, blk):
-        m1 = min(smc.M, m0 + blk)
-        _, _, _, s = smoother(N, y, None, rows=(int(mid), raw[m0:m1]), seed=seed, device=getattr(smc.backend, "device", 0),
-                              streams=np.arange(m0, m1, dtype=np.uint32))
-        means.append(s["mean"])
-        vars_.append(s["var"])
-    mean_m, var_m = np.concatenate(means, axis=1), np.concatenate(vars_, axis=1)     # [T][M] or [T][M][d]
+    mean_m = np.concatenate([s["mean"] for s in blocks], axis=1)                     # [T][M] or [T][M][d]
+    var_m = np.concatenate([s["var"] for s in blocks], axis=1)
     keep = om > 0
     wk = om[keep].reshape((1, -1) + (1,) * (mean_m.ndim - 2))
     mean = np.add.reduce(wk * mean_m[:, keep], axis=1)
