@@ -862,6 +862,48 @@ int smc_host_smooth_quantiles(int64_t T, int64_t n, const double* x /*[T][n], on
                               int np, double* q /*[T][np]*/);
 int smc_smooth_quantiles_info(smc_handle h /*or NULL*/, int64_t* scratch_bytes, int32_t* q_bits, int64_t* lds_max);
 
+/* ---- predictive checks: PIT and one-step forecast moments (csrc/smc_spec.h "predictive checks") ----------------------
+ * logZ ranks models against each other; whether ONE model fits the series is read off the probability integral transform of its
+ * one-step-ahead predictive law, u_t = P(Y_t <= y_t | y_1:t-1): iid uniform under a correct model.  A bootstrap filter resamples at
+ * every step, so the cloud x_t a step leaves, taken whatever its weights, is a sample of p(x_t | y_1:t-1).  For one filter at one
+ * step, n particles in the order of smc_get_state, (ym_i, sd_i) the observation law at x_i and z_i = (y - ym_i) / sd_i as the step
+ * forms it:
+ *     pit = sum Phi(z_i) / n,   obs_mean = sum ym_i / n,   obs_var = sum sd_i^2 / n + sum (ym_i - obs_mean)^2 / n
+ * Phi = smc_host_normcdf; the sums run in chunks of 128, level by level (pred_sum).  A pure function of (cloud, y, parameter row):
+ * no weight is read, and nothing is special-cased - a NaN y gives a NaN pit beside the ordinary moments (the forecast of the
+ * unobserved y_t, also at a gap of an SMC_FLAG_NAN_MISSING handle), an infinite y gives 0 or 1, a NaN state or a zero sd does what
+ * IEEE arithmetic does, a cloud after a dead step gives what the formula gives.
+ *   smc_get_predictive    the rows of the CURRENT state for the observation y_t the last step assimilated: [n_theta] each, any NULL.
+ *                         State rules of smc_get_moments (SMC_ESTATE before smc_init).  Reads the handle and changes nothing: the
+ *                         steps that follow give the bits they would have given.
+ *   smc_predictive        the rows of every step of the record of an armed handle (smc_history_begin) in one launch: [T][n_theta]
+ *                         each, any NULL; row t is bit for bit what smc_get_predictive(h, y[t]) gave after step t.  SMC_ESTATE
+ *                         without a record, SMC_EINVAL when T != smc_history_len.
+ *   Both refuse, with SMC_EINVAL and the handle unchanged: a handle with a proposal (its cloud is drawn from the proposal),
+ *   SMC_FLAG_CONDITIONAL, and SMC_MODEL_UCSV_RB (its rows hold the updated m, P: the predictive pair is gone).  Scratch: a block of
+ *   its own, allocated at the first such call and freed by smc_destroy.
+ *   smc_host_predictive   the same specification for ONE cloud x [d][n] on the host (no GPU), the same bits: out = (pit, obs_mean,
+ *                         obs_var).  LG1D, SV1D, UCSV3D.
+ *   smc_host_normcdf / smc_device_normcdf   Phi in f64, the same bits on both sides: absolute error at most 1e-15 over the whole
+ *                         line (measured: csrc/smc_spec.h), 0 <= Phi <= 1, Phi(-inf) = +0, Phi(+inf) = 1, NaN gives NaN.
+ *   smc_predictive_info   small_max: clouds of at most this many particles are finished by one workgroup each, larger ones by one
+ *                         launch per level of the sums (the same bits; 4096, chosen by measurement: profiles/predictive_cost.log;
+ *                         SMC_PRED_SMALL_MAX in the environment moves it within [0, 128^2]); chunk = 128.
+ * The exact Kalman side (LinearModel rows (A, B, Q, R, x0, sigma0)): from the predicted pair (x-, S-) of each step,
+ *     ym = B x-,  yv = B^2 S- + R,  pit = Phi((y - ym) / sqrt(yv));
+ * with SMC_FLAG_NAN_MISSING a NaN y is a gap: the row is (NaN, ym, yv) and the filter takes the missing step.
+ *   smc_kalman_predictive_flags   [T][n_theta] each, any NULL, on `device`;   smc_host_kalman_predictive   one row on the host, the same bits. */
+int smc_get_predictive(smc_handle h, double y_t, double* pit, double* obs_mean, double* obs_var /*[n_theta] each, any NULL*/);
+int smc_predictive(smc_handle h, const double* y /*[T]*/, int64_t T, double* pit, double* obs_mean, double* obs_var /*[T][n_theta]*/);
+int smc_host_predictive(int model_id, const double* raw, const double* x /*[d][n]*/, int64_t n, double y, double* out /*[3]*/);
+double smc_host_normcdf(double z);
+int smc_device_normcdf(const double* z, int64_t n, double* out, int device);
+int smc_predictive_info(int64_t* small_max, int* chunk);
+int smc_kalman_predictive_flags(const double* raw /*[n_theta][6]*/, int64_t n_theta, const double* y, int64_t T, int predict_first,
+                                double* pit, double* ym, double* yv /*[T][n_theta], any NULL*/, int device, uint32_t flags);
+int smc_host_kalman_predictive(const double* row /*[6]*/, const double* y, int64_t T, int predict_first, uint32_t flags,
+                               double* pit, double* ym, double* yv /*[T]*/);
+
 /* ---- backward simulation: joint smoothing paths (FFBSi; Godsill, Doucet and West 2004) --------------------------------------
  * smc_smooth gives the marginals p(x_t | y_1:T).  Whatever depends on two or more times at once (the smoothed change of the
  * trend, the cycle as a path, lag covariances, the complete-data sums of a particle EM or Gibbs step) needs whole trajectories

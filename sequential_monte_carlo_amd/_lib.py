@@ -52,6 +52,8 @@ EXPORTS = [
     "smc_history_get_ancestors", "smc_history_put_ancestors", "smc_ancestor_sweep", "smc_host_ancestor_sweep",
     "smc_ibis_theta_quantiles", "smc_ibis_theta_histogram", "smc_host_theta_weights", "smc_host_theta_quantiles", "smc_host_theta_histogram",
     "smc_smooth_quantiles", "smc_host_smooth_quantiles", "smc_smooth_quantiles_info",
+    "smc_get_predictive", "smc_predictive", "smc_host_predictive", "smc_host_normcdf", "smc_device_normcdf", "smc_predictive_info",
+    "smc_kalman_predictive_flags", "smc_host_kalman_predictive",
 ]
 PROP_NONE, PROP_AFFINE, PROP_OPTIMAL, PROP_NPAR = 0, 1, 2, 4
 SUMM_WEIGHTED, SUMM_UNWEIGHTED = 0, 1
@@ -255,6 +257,15 @@ def lib():
     L.smc_smooth_quantiles.argtypes = L.smc_smooth_pairs.argtypes + [C.c_int, _dp, C.c_int, _dp]
     L.smc_host_smooth_quantiles.argtypes = [C.c_int64, C.c_int64, _dp, _dp, _dp, C.c_int, _dp]
     L.smc_smooth_quantiles_info.argtypes = [h, C.POINTER(C.c_int64), _i32p, C.POINTER(C.c_int64)]
+    L.smc_get_predictive.argtypes = [h, C.c_double, _dp, _dp, _dp]
+    L.smc_predictive.argtypes = [h, _dp, C.c_int64, _dp, _dp, _dp]
+    L.smc_host_predictive.argtypes = [C.c_int, _dp, _dp, C.c_int64, C.c_double, _dp]
+    L.smc_host_normcdf.restype = C.c_double
+    L.smc_host_normcdf.argtypes = [C.c_double]
+    L.smc_device_normcdf.argtypes = [_dp, C.c_int64, _dp, C.c_int]
+    L.smc_predictive_info.argtypes = [C.POINTER(C.c_int64), _ip]
+    L.smc_kalman_predictive_flags.argtypes = [_dp, C.c_int64, _dp, C.c_int64, C.c_int, _dp, _dp, _dp, C.c_int, C.c_uint32]
+    L.smc_host_kalman_predictive.argtypes = [_dp, _dp, C.c_int64, C.c_int, C.c_uint32, _dp, _dp, _dp]
     L.smc_sample_paths.argtypes = [h, C.c_int64, C.c_uint64, _i32p, _i32p, _dp]
     L.smc_host_sample_paths.argtypes = [C.c_int, _dp, C.c_int64, C.c_int64, _dp, _dp, C.c_int64, C.c_uint64, C.c_uint32, _i32p, _dp]
     L.smc_rb_sample_paths.argtypes = [h, _dp, C.c_int64, C.c_int64, C.c_uint64, _i32p, _i32p, _dp, _dp, _dp, _dp, _dp]
@@ -343,6 +354,58 @@ def host_kalman_steps(row, y, predict_first=False, missing=False):
     xf, Sf, lik = np.zeros(y.size), np.zeros(y.size), np.zeros(y.size)
     check(lib().smc_host_kalman_steps(_d(row), _d(y), y.size, int(bool(predict_first)), _kalman_flags(missing), _d(xf), _d(Sf), _d(lik)))
     return xf, Sf, lik
+
+
+def kalman_predictive(raw, y, predict_first=False, device=0, missing=False):
+    """(pit, ym, yv), each [T][n_theta]: the exact one-step predictive law of y_t under every LG1D row and its probability integral
+    transform (smc_kalman_predictive_flags; at a gap of a missing=True call the pit is NaN)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1, 6)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    out = np.zeros((3, y.size, raw.shape[0]))
+    check(lib().smc_kalman_predictive_flags(_d(raw), raw.shape[0], _d(y), y.size, int(bool(predict_first)), _d(out[0]), _d(out[1]), _d(out[2]),
+                                            device, _kalman_flags(missing)))
+    return out[0], out[1], out[2]
+
+
+def host_kalman_predictive(row, y, predict_first=False, missing=False):
+    """the same rows for ONE LG1D row on the host (smc_host_kalman_predictive; no GPU): (pit, ym, yv), each [T]"""
+    row = np.ascontiguousarray(row, dtype=np.float64).reshape(6)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    out = np.zeros((3, y.size))
+    check(lib().smc_host_kalman_predictive(_d(row), _d(y), y.size, int(bool(predict_first)), _kalman_flags(missing), _d(out[0]), _d(out[1]), _d(out[2])))
+    return out[0], out[1], out[2]
+
+
+def host_normcdf(z):
+    """sp_normcdf on the host (smc_host_normcdf), elementwise"""
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    f = lib().smc_host_normcdf
+    return np.array([f(float(v)) for v in z.ravel()]).reshape(z.shape)
+
+
+def device_normcdf(z, device=0):
+    """sp_normcdf on the device (smc_device_normcdf), elementwise: the same bits"""
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    out = np.zeros(z.size)
+    check(lib().smc_device_normcdf(_d(z.ravel()), z.size, _d(out), device))
+    return out.reshape(z.shape)
+
+
+def host_predictive(model_id, raw, x, y):
+    """(pit, obs_mean, obs_var) of ONE cloud x [d][n] for the observation y on the host (smc_host_predictive; no GPU)"""
+    raw = np.ascontiguousarray(raw, dtype=np.float64).ravel()
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    x = x.reshape(-1, x.shape[-1])
+    out = np.zeros(3)
+    check(lib().smc_host_predictive(int(model_id), _d(raw), _d(x), x.shape[1], float(y), _d(out)))
+    return out[0], out[1], out[2]
+
+
+def predictive_constants():
+    """(small_max, chunk) of the predictive checks (smc_predictive_info): the largest cloud one workgroup finishes, the chunk of pred_sum"""
+    sm, ch = C.c_int64(), C.c_int()
+    check(lib().smc_predictive_info(C.byref(sm), C.byref(ch)))
+    return sm.value, ch.value
 
 
 def kalman_smooth(raw, y, predict_first=False, device=0, missing=False):
@@ -981,6 +1044,21 @@ class Handle:
         v = np.zeros((self.d, self.n_theta))
         check(lib().smc_get_moments(self._h, _d(m), _d(v)))
         return m, v
+
+    def predictive(self, y_t):
+        """(pit, obs_mean, obs_var), each [n_theta]: the probability integral transform of y_t and the mean and variance of the
+        one-step predictive law of the observation, from the current cloud whatever its weights (smc_get_predictive; y_t is the
+        observation the last step assimilated).  Bootstrap handles of LG1D, SV1D, UCSV3D."""
+        out = np.zeros((3, self.n_theta))
+        check(lib().smc_get_predictive(self._h, float(y_t), _d(out[0]), _d(out[1]), _d(out[2])))
+        return out[0], out[1], out[2]
+
+    def predictive_record(self, y):
+        """the same rows for every step of the record (smc_predictive, one launch): (pit, obs_mean, obs_var), each [T][n_theta]"""
+        y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        out = np.zeros((3, y.size, self.n_theta))
+        check(lib().smc_predictive(self._h, _d(y), y.size, _d(out[0]), _d(out[1]), _d(out[2])))
+        return out[0], out[1], out[2]
 
     def quantiles(self, p, component=0):
         """quantiles of one state coordinate, [n_theta][len(p)], on the device (in the handle's summary mode: the inverse of the

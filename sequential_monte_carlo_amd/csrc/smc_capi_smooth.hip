@@ -142,6 +142,20 @@ extern "C" int smc_history_put_ancestors(smc_handle h, int64_t t, const int32_t*
     return SMC_OK;
 }
 
+// ---- predictive checks over the record (smc_spec.h "predictive checks") ----------------------------------------------------------
+// Row t is the row of the cloud recorded at step t for y[t]: smc_get_predictive's kernels over the dense record, in one launch.
+extern "C" int smc_predictive(smc_handle h, const double* y, int64_t T, double* pit, double* obs_mean, double* obs_var) {
+    if (!h || !y) return fail(SMC_EINVAL, "smc_predictive: NULL argument");
+    int rc = predictive_refuse(h, "smc_predictive");
+    if (rc) return rc;
+    if (!h->hist.armed || h->hist.len < 1) return fail(SMC_ESTATE, "smc_predictive: nothing is recorded (smc_history_begin, then smc_init / smc_step)");
+    if (T != h->hist.len)
+        return fail(SMC_EINVAL, "smc_predictive: T = " + std::to_string(T) + " observations for " + std::to_string(h->hist.len) + " recorded steps");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t n = h->v.n, nt = h->v.ntheta;
+    return predictive_run(h, "smc_predictive", h->hist.d_x, (int64_t)h->d * nt * n, nt * n, n, T, y, 0.0, pit, obs_mean, obs_var);
+}
+
 // ---- the backward pass ---------------------------------------------------------------------------------------------------
 namespace {
 // the rows the steps ran with, as the device holds them (the PMMH kernels write them there), and their constants as smooth_row

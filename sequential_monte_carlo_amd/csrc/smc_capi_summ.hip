@@ -1,8 +1,10 @@
 // smc_capi_summ.hip -- summaries of the particle clouds: quantiles and moments per step inside the multi-step calls
 // (smc_set_summaries / smc_get_summaries) and of the current state (smc_get_moments / smc_get_quantiles).
-// The only translation unit that includes smc_summ_kernels.h.
+// The only translation unit that includes smc_summ_kernels.h.  Predictive checks of the clouds (smc_get_predictive, and predictive_run
+// behind smc_predictive): the kernels of smc_pred_kernels.h over the handle's clouds.
 #include "smc_host.h"
 #include "smc_summ_kernels.h"
+#include "smc_pred_kernels.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -218,6 +220,132 @@ extern "C" int smc_get_moments(smc_handle h, double* mean, double* var) {
     HIPCHK(hipMemcpy(mean, d_mean, nout * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(var, d_var, nout * 8, hipMemcpyDeviceToHost));
     return SMC_OK;
+}
+
+// ---- predictive checks (smc_spec.h "predictive checks"; kernels and their order of summation: smc_pred_kernels.h) ----------------
+// The size at which the launches change: clouds of at most this many particles are finished by one workgroup each (k_predictive),
+// larger ones by tiles and one launch per level.  PRED_SMALL_MAX = 128^2 is the most the one-workgroup kernel can hold.  Measured
+// (profiles/predictive_cost.log, smc_get_predictive of 1 and of 64 clouds): one workgroup wins up to 2048 particles (13 against 18 us),
+// the two meet at 4096 (21 against 20 to 22 us), the launches per level win from 8192 on (36 to 38 against 24 to 33 us): the switch
+// is 4096.  SMC_PRED_SMALL_MAX in the environment moves it within [0, 128^2] (tests and measurements: the same bits either way).
+constexpr int64_t PRED_SWITCH = 4096;
+static int64_t pred_small_max() {
+    const char* e = getenv("SMC_PRED_SMALL_MAX");
+    if (!e || !*e) return PRED_SWITCH;
+    const long long v = atoll(e);
+    return v < 0 ? 0 : v > PRED_SMALL_MAX ? PRED_SMALL_MAX : (int64_t)v;
+}
+extern "C" int smc_predictive_info(int64_t* small_max, int* chunk) {
+    if (small_max) *small_max = pred_small_max();
+    if (chunk) *chunk = SMOOTH_CH;
+    return SMC_OK;
+}
+
+int predictive_refuse(const smc_filter_s* h, const char* who) {
+    const std::string w = std::string(who) + ": ";
+    if (h->v.prop_kind != 0)
+        return fail(SMC_EINVAL, w + "the handle has a proposal (smc_set_proposal): its cloud is drawn from the proposal and is not a sample of the "
+                                    "predictive law of the state");
+    if (conditional(h))
+        return fail(SMC_EINVAL, w + "the handle is conditional (SMC_FLAG_CONDITIONAL): its cloud holds the pinned reference and is not a predictive sample");
+    if (!has_density(h->model))
+        return fail(SMC_EINVAL, w + "SMC_MODEL_UCSV_RB keeps the UPDATED m and P in its rows: the predictive pair of the trend is gone when the step "
+                                    "ends; use a UCSV3D filter");
+    return SMC_OK;
+}
+
+int predictive_run(smc_handle h, const char* who, const double* x, int64_t st_t, int64_t st_c, int64_t st_f, int64_t T, const double* y, double y0,
+                   double* pit, double* obs_mean, double* obs_var) {
+    const std::string w = std::string(who) + ": ";
+    const int64_t n = h->v.n, nt = h->v.ntheta, rows = T * nt;
+    const int64_t nch = (n + SMOOTH_CH - 1) / SMOOTH_CH, ntiles = (n + PRED_THREADS - 1) / PRED_THREADS;
+    const bool small = n <= pred_small_max();
+    if (small ? (nt > 65535 || T > 0x7fffffff) : ((double)ntiles * (double)rows > 2147483647.0))
+        return fail(SMC_EINVAL, w + "too many clouds for one launch");
+    // the block: y | out [3][rows] | large clouds: the partials of level 0 [4][rows][nch] and of the level above [4][rows][ceil(nch / CH)]
+    const int64_t m1 = (nch + SMOOTH_CH - 1) / SMOOTH_CH;
+    OffsetPlan o;
+    const size_t o_y = o.take((size_t)T * 8), o_out = o.take(3 * (size_t)rows * 8);
+    const size_t o_a = small ? 0 : o.take(4 * (size_t)rows * (size_t)nch * 8), o_b = small ? 0 : o.take(4 * (size_t)rows * (size_t)m1 * 8);
+    if (h->pred.d_buf.bytes() < o.bytes) {
+        if (h->pred.d_buf) HIPCHK(hipStreamSynchronize(h->stream));   // (the old block first; the stream may still read it)
+        if (h->pred.d_buf.grow(o.bytes) != hipSuccess) return fail(SMC_ENOMEM, w + "hipMalloc of the block of the predictive checks");
+    }
+    char* buf = h->pred.d_buf.as<char>();
+    double *d_y = (double*)(buf + o_y), *d_out = (double*)(buf + o_out), *A = (double*)(buf + o_a), *B = (double*)(buf + o_b);
+    // one step (smc_get_predictive, once per step of a filter loop): the rows go straight into pinned host memory, as the one-launch
+    // summaries of the current state do - no copy behind the synchronisation
+    const bool pinned = T == 1;
+    if (pinned) {
+        HIPCHK(h->pred.h_out.grow(3 * (size_t)rows * 8));
+        d_out = h->pred.h_out.as<double>();
+    }
+    hipStream_t s = h->stream;
+    HIPCHK(hipEventRecord(h->ev0, s));   // (smc_last_elapsed_ms: the launches of this call)
+    if (y) HIPCHK(hipMemcpyAsync(d_y, y, (size_t)T * 8, hipMemcpyHostToDevice, s));
+    PredArgs a{};
+    a.x = x; a.st_t = st_t; a.st_c = st_c; a.st_f = st_f; a.n = n; a.ntheta = (int)nt; a.ntiles = ntiles;
+    a.params = h->d_params; a.y = y ? d_y : nullptr; a.y0 = y0; a.out = d_out;
+    HIPCHK(by_density_model(h->model, [&](auto Mt) {
+        constexpr int M = decltype(Mt)::value;
+        if (small) {
+            hipLaunchKernelGGL(k_predictive<M>, dim3((unsigned)T, (unsigned)nt), dim3(PRED_THREADS), 0, s, a);
+            return hipGetLastError();
+        }
+        // `planes` lines of sums, from the partials of level 0 at `from` down to one number a line; where they end up
+        auto levels = [&](double* from, double* other, int64_t planes, const double** done) {
+            int64_t m = nch;
+            while (m > 1) {
+                const int64_t mo = (m + SMOOTH_CH - 1) / SMOOTH_CH, lines = planes * rows;
+                hipLaunchKernelGGL(k_pred_level<SMOOTH_CH>, dim3((unsigned)((lines * mo + 255) / 256)), dim3(256), 0, s, (const double*)from, m, other, mo, lines);
+                const hipError_t e = hipGetLastError();
+                if (e != hipSuccess) return e;
+                double* tswap = from; from = other; other = tswap;
+                m = mo;
+            }
+            *done = from;
+            return hipSuccess;
+        };
+        hipError_t e;
+        const dim3 grid((unsigned)(ntiles * rows));
+        a.part = A;
+        hipLaunchKernelGGL((k_predictive_tiles<M, 0>), grid, dim3(PRED_THREADS), 0, s, a, rows);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = levels(A, B, 3, &a.sums)) != hipSuccess) return e;
+        // the centred pass: plane 3 of both buffers (the first-pass sums stay where they are)
+        double *A3 = A + 3 * rows * nch, *B3 = B + 3 * rows * m1;
+        a.part = A3;
+        hipLaunchKernelGGL((k_predictive_tiles<M, 1>), grid, dim3(PRED_THREADS), 0, s, a, rows);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = levels(A3, B3, 1, &a.sum_c)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_pred_finish<0>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, a, rows);
+        return hipGetLastError();
+    }));
+    int rc = finish_elapsed(h);
+    if (rc) return rc;
+    std::vector<double> res;
+    const double* r = d_out;
+    if (!pinned) {   // (one copy for the three planes)
+        res.resize(3 * (size_t)rows);
+        HIPCHK(hipMemcpy(res.data(), d_out, res.size() * 8, hipMemcpyDeviceToHost));
+        r = res.data();
+    }
+    if (pit) memcpy(pit, r, (size_t)rows * 8);
+    if (obs_mean) memcpy(obs_mean, r + rows, (size_t)rows * 8);
+    if (obs_var) memcpy(obs_var, r + 2 * rows, (size_t)rows * 8);
+    return SMC_OK;
+}
+
+// the row of the CURRENT cloud of every filter for the observation y_t the last step assimilated: read-only on the handle (no weight
+// is read, so nothing is emitted either: the steps that follow give the bits they would have given)
+extern "C" int smc_get_predictive(smc_handle h, double y_t, double* pit, double* obs_mean, double* obs_var) {
+    if (!h) return fail(SMC_EINVAL, "smc_get_predictive: NULL handle");
+    int rc = predictive_refuse(h, "smc_get_predictive");
+    if (rc) return rc;
+    if (!h->inited) return fail(SMC_ESTATE, "smc_get_predictive: filter not initialised");
+    HIPCHK(hipSetDevice(h->device));
+    const FilterView& v = h->v;
+    return predictive_run(h, "smc_get_predictive", v.x[h->cur], 0, (int64_t)v.ntheta * v.npad, v.npad, 1, nullptr, y_t, pit, obs_mean, obs_var);
 }
 
 extern "C" int smc_get_quantiles(smc_handle h, int component, const double* p, int np, double* out) {

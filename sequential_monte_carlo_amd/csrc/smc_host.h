@@ -198,6 +198,11 @@ struct smc_filter_s {
     struct {   // forecasts (smc_capi_forecast.hip): ONE block, grown on demand (old block first)
         DevBlock d_buf;                        // clouds [block][d + 3][ntheta][npad] | summary scratch | results of every horizon
     } fc;
+    struct {   // predictive checks (smc_get_predictive / smc_predictive; predictive_run, smc_capi_summ.hip): ONE block of their own,
+        DevBlock d_buf;                        // empty until the first such call (old block first): y [T] | pit, obs_mean, obs_var [3][T][ntheta] |
+                                               //   large clouds: the partials of the levels of pred_sum
+        PinBlock h_out;                        // smc_get_predictive: its rows [3][ntheta], written by the kernel that finishes them
+    } pred;
     struct {   // PMMH rejuvenation (smc_capi_pmmh.hip): this handle holds the proposal filters
         smc::PmmhSpec spec{};
         bool cfg = false;
@@ -285,6 +290,13 @@ int enqueue_step_summaries(smc_handle h, int64_t row);
 size_t cloud_summary_words(const smc_filter_s* h, int rows);
 int enqueue_cloud_summaries(smc_handle h, const double* cloud, int rows, uint64_t* scratch, int scratch_rows, int component, const double* p, int np,
                             bool mom, double* q_out, double* mean, double* var);
+// smc_capi_summ.hip: predictive checks (smc_spec.h "predictive checks").  predictive_refuse: the handles whose cloud is no predictive
+// sample (SMC_EINVAL with the reason; SMC_OK otherwise).  predictive_run: the rows of T clouds read through the strides (st_t, st_c,
+// st_f; smc_pred_kernels.h) with the observations y [T] on the host (nullptr: T = 1 and y0), on the handle's stream, waited for and
+// handed over as pit, obs_mean, obs_var [T][ntheta] (any NULL).  It reads the handle's parameter rows and touches nothing else.
+int predictive_refuse(const smc_filter_s* h, const char* who);
+int predictive_run(smc_handle h, const char* who, const double* x, int64_t st_t, int64_t st_c, int64_t st_f, int64_t T, const double* y, double y0,
+                   double* pit, double* obs_mean, double* obs_var);
 // smc_capi_slots.hip: the dense weights of the current state into w [ntheta][n], on the handle's stream (k_dense_weights)
 hipError_t enqueue_dense_weights(smc_filter_s* h, double* w);
 // ... and the block smc_get_state and smc_get_moments put them (and the moments behind them) in: h->d_wdense, allocated once

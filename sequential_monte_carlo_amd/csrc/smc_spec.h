@@ -1630,4 +1630,126 @@ SMC_HD uint64_t anc_uniform(uint64_t seed, uint32_t stream, uint32_t t) { return
 // one step of the trace: the particle of step t - 1 behind particle i of step t (kstar = k*_t, J = J_t, a_t the ancestors of step t)
 SMC_HD int32_t anc_trace(int32_t i, uint32_t kstar, int32_t J, const int32_t* a_t) { return (uint32_t)i == kstar ? J : a_t[i]; }
 
+// ---- predictive checks: PIT and one-step forecast moments ------------------------------------------------------------
+// A bootstrap filter resamples at every step, so the cloud x_t a step leaves, taken WITHOUT its weights, is a sample of
+// p(x_t | y_1:t-1); pushed through the observation law it is the predictive law of y_t.  The row of one cloud - one filter at one
+// step, n particles in the order of smc_get_state, the observation y, the filter's parameter row - is, with
+// (ym_i, sd_i) = model_obs_moments(x_i) and z_i = model_obs_z(x_i, y):
+//     pit      = pred_sum(Phi(z_i)) / n                                             P(Y_t <= y_t | y_1:t-1), uniform under the model
+//     obs_mean = pred_sum(ym_i) / n
+//     obs_var  = pred_sum(sd_i * sd_i) / n + pred_sum((ym_i - obs_mean)^2) / n      a centred second pass
+// Phi = sp_normcdf, the four divisions are divisions by (double)n.  A pure function of (cloud, y, row): no weight is read and there
+// is no rule for non-finite values, gaps or dead filters - a NaN y gives a NaN pit beside ordinary moments (the forecast of the
+// unobserved y_t), an infinite y gives 0 or 1, a NaN state or a zero sd does what IEEE arithmetic does with it.
+//
+// sp_normcdf(z): with a = |z|, the upper tail is Q(a) = exp(-a^2 / 2) H(s), t = 1 / (1 + a / 4), s = (t - tc) / th in [-1, 1] for
+// a in [0, 9]; H = Mills' ratio / sqrt(2 pi) is smooth there and is a polynomial of degree 20 in s (Chebyshev interpolation, monomial
+// basis: every coefficient is below 1, Horner's rule by fma; scripts/dbg/normcdf_coeffs.py derives them with mpmath - the
+// polynomial itself is within 2.5e-19 of Q before any rounding).  Beyond a = 9 the argument of H stays at 9: Q(9) = 1.13e-19 bounds
+// that.  Phi(z) = Q(a) for z <= 0 and 1 - Q(a) for z > 0.  One division, one sp_exp, 23 fma, the same on every input; the pieces
+// join at 0 and at +-9.  Phi(-inf) = +0 and Phi(+inf) = 1 (sp_exp(-inf) = 0), a NaN comes back as it is, 0 <= Phi <= 1 always
+// (H > 0 and Q <= 1/2 + 1 ulp).  The error of exp's argument, at most half an ulp of a^2 / 2, is a RELATIVE error of Q: the
+// absolute one, a^2 Q(a) 2^-54, stays below 1e-17.
+// Measured against mpmath at 50 digits (tests/test_predictive_host.py: 200001 points of [-40, 40], the joints +-4 ulp, zeros,
+// subnormals, infinities): the largest absolute error is SP_NORMCDF_MAX_ERR below; the contract is 1e-15.
+constexpr double SP_NORMCDF_MAX_ERR = 1.9e-16;   // measured 1.886e-16, at z = 0.326; the test reads this line and asserts its maximum against it
+constexpr double NORMCDF_AMAX = 9.0;
+SMC_HD double sp_normcdf(double z) {
+    const double a = fabs(z);
+    const double ac = a < NORMCDF_AMAX ? a : NORMCDF_AMAX;   // (a NaN takes 9 here and leaves as itself below)
+    const double t = 1.0 / fma(0.25, ac, 1.0);
+    const double s = fma(t, 0x1.71c71c71c71c7p+1, -0x1.e38e38e38e38ep+0);
+    double h = 0x1.3af85338f8637p-41;
+    h = SMC_FMAK(h, s, 0x1.131eff9b8a2b4p-39);
+    h = SMC_FMAK(h, s, -0x1.08eabef25d6c5p-36);
+    h = SMC_FMAK(h, s, -0x1.5e7f01a3559d1p-38);
+    h = SMC_FMAK(h, s, 0x1.de094d2cf7ec5p-33);
+    h = SMC_FMAK(h, s, -0x1.b47ca97ef9893p-32);
+    h = SMC_FMAK(h, s, -0x1.3025dd8fb5a73p-29);
+    h = SMC_FMAK(h, s, 0x1.5a6dd0975dde9p-27);
+    h = SMC_FMAK(h, s, 0x1.19ea251311c6dp-26);
+    h = SMC_FMAK(h, s, -0x1.89c33ebb25cc7p-23);
+    h = SMC_FMAK(h, s, -0x1.55802782421a1p-24);
+    h = SMC_FMAK(h, s, 0x1.b8f0cdb045c3dp-19);
+    h = SMC_FMAK(h, s, 0x1.5250a97f051dbp-20);
+    h = SMC_FMAK(h, s, -0x1.14bc83178dfaap-14);
+    h = SMC_FMAK(h, s, -0x1.16e937f7e563ep-13);
+    h = SMC_FMAK(h, s, 0x1.4a4a7780eb264p-10);
+    h = SMC_FMAK(h, s, 0x1.4a781132135a3p-7);
+    h = SMC_FMAK(h, s, 0x1.4038f25527432p-5);
+    h = SMC_FMAK(h, s, 0x1.9d73e8b76d46fp-4);
+    h = SMC_FMAK(h, s, 0x1.80a48d7396201p-3);
+    h = SMC_FMAK(h, s, 0x1.49bd3b6b47470p-3);
+    const double q = sp_exp(-0.5 * (a * a)) * h;
+    const double r = z > 0.0 ? 1.0 - q : q;
+    return z != z ? z : r;
+}
+
+// the standardised residual of y under the observation law at x, exactly as model_logobs forms it
+template <int MODEL>
+SMC_HD double model_obs_z(const Params& p, const double* x, double y) {
+    if constexpr (MODEL == MODEL_LG1D) return (y - p.raw[1] * x[0]) * p.der[3];
+    else if constexpr (MODEL == MODEL_SV1D) return y * sp_exp(-0.5 * x[0]);
+    else return (y - x[0]) * sp_exp(-0.5 * x[2]);
+}
+// the state rows the predictive row of a family reads: row 0, and for UCSV3D row 2 (the log-variance of the observation noise)
+template <int MODEL> struct pred_rows { static constexpr int count = MODEL == MODEL_UCSV3D ? 2 : 1, second = 2; };
+// the three terms of the first pass for one particle (x: the rows of pred_rows in their places, the others are not read)
+template <int MODEL>
+SMC_HD void pred_terms(const Params& p, const double* x, double y, double& cdf, double& ym, double& s2) {
+    double sd;
+    model_obs_moments<MODEL>(p, x, ym, sd);
+    s2 = sd * sd;
+    cdf = sp_normcdf(model_obs_z<MODEL>(p, x, y));
+}
+SMC_HD double pred_centred_term(double ym, double obs_mean) {
+    const double dm = ym - obs_mean;
+    return dm * dm;
+}
+// pred_sum: the smoother's order made recursive.  Level 0 cuts the index into chunks of SMOOTH_CH consecutive terms and sums each in
+// ascending order with plain adds from +0.0; level k sums SMOOTH_CH consecutive partials of level k - 1 in the same way, until one
+// number is left.  For n <= SMOOTH_CH^2 it is smooth_sum bit for bit; no serial run is longer than SMOOTH_CH, whatever n.
+// pred_level: one level, m_in numbers to ceil(m_in / SMOOTH_CH) (in place is fine: entry j is written after its chunk was read)
+inline int64_t pred_level(const double* in, int64_t m_in, double* out) {
+    const int64_t m_out = (m_in + SMOOTH_CH - 1) / SMOOTH_CH;
+    for (int64_t j = 0; j < m_out; ++j) {
+        double s = 0.0;
+        const int64_t c1 = (j + 1) * SMOOTH_CH < m_in ? (j + 1) * SMOOTH_CH : m_in;
+        for (int64_t i = j * SMOOTH_CH; i < c1; ++i) s += in[i];
+        out[j] = s;
+    }
+    return m_out;
+}
+// host only; part: scratch of ceil(n / SMOOTH_CH) doubles
+template <class F>
+inline double pred_sum(int64_t n, F term, double* part) {
+    int64_t m = (n + SMOOTH_CH - 1) / SMOOTH_CH;
+    for (int64_t j = 0; j < m; ++j) {
+        double s = 0.0;
+        const int64_t c1 = (j + 1) * SMOOTH_CH < n ? (j + 1) * SMOOTH_CH : n;
+        for (int64_t i = j * SMOOTH_CH; i < c1; ++i) s += term(i);
+        part[j] = s;
+    }
+    while (m > 1) m = pred_level(part, m, part);
+    return part[0];
+}
+// the row from its four sums
+SMC_HD double pred_mean_of(double sum, int64_t n) { return sum / (double)n; }
+SMC_HD double pred_var_of(double sum_s2, double sum_c, int64_t n) { return sum_s2 / (double)n + sum_c / (double)n; }
+
+// The exact Kalman row, beside kalman_step_gaps: the predictive law of y_t from the predicted pair (x-, S-) as kalman_step forms it
+// (at the first step of a filter with predict_first = 0 the pair is (x0, sigma0)), then the step itself.
+//     ym = B x-,   yv = (B B) S- + R  (the step's own innovation variance),   z = (y - ym) / sqrt(yv),   pit = sp_normcdf(z)
+// At a gap (MISS and a NaN y) the row is (NaN, ym, yv): z is NaN and sp_normcdf hands it back.  (x, S) are advanced in place by
+// kalman_step_gaps from the values they had: the filter's bits are those of a run that never asked.
+template <bool MISS>
+SMC_HD void kalman_predictive_step(double A, double B, double Q, double R, bool predict, double y, double& x, double& S, double& pit, double& ym,
+                                   double& yv) {
+    const double xm = predict ? A * x : x, Sm = predict ? (A * A) * S + Q : S;
+    ym = B * xm;
+    yv = (B * B) * Sm + R;
+    pit = sp_normcdf((y - ym) / sqrt(yv));
+    (void)kalman_step_gaps<MISS>(A, B, Q, R, predict, y, x, S);
+}
+
 }  // namespace smc

@@ -3,6 +3,7 @@
 // tests use.  Kernels in smc_util_kernels.h and below.
 #include "smc_host.h"
 #include "smc_util_kernels.h"
+#include "smc_pred_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -171,6 +172,97 @@ extern "C" int smc_kalman_log_likelihood_flags(const double* raw, int64_t n_thet
 extern "C" int smc_kalman_log_likelihood(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first,
                                          double* out, int device) {
     return smc_kalman_log_likelihood_flags(raw, n_theta, y, T, predict_first, out, device, 0);
+}
+
+// ---- predictive checks (smc_spec.h "predictive checks") without a handle -------------------------------------------------------
+// the exact Kalman rows of a series under every parameter row: pit, ym, yv [T][n_theta] (any NULL)
+extern "C" int smc_kalman_predictive_flags(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first, double* pit, double* ym,
+                                           double* yv, int device, uint32_t flags) {
+    if (flags & ~SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_kalman_predictive: flags is 0 or SMC_FLAG_NAN_MISSING");
+    if (!raw || !y || n_theta <= 0 || T <= 0) return fail(SMC_EINVAL, "smc_kalman_predictive: bad argument");
+    hipStream_t st = nullptr;
+    HIPCHK(util_stream(device, &st));
+    const size_t plane = (size_t)T * (size_t)n_theta;
+    DevBuf d_raw(0), d_y(1), d_out(2);
+    HIPCHK(d_raw.alloc((size_t)n_theta * 48));
+    HIPCHK(d_y.alloc((size_t)T * 8));
+    HIPCHK(d_out.alloc(3 * plane * 8));
+    HIPCHK(hipMemcpyAsync(d_raw.p, raw, (size_t)n_theta * 48, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_y.p, y, (size_t)T * 8, hipMemcpyHostToDevice, st));
+    double *o_pit = pit ? d_out.as<double>() : nullptr, *o_ym = ym ? d_out.as<double>() + plane : nullptr, *o_yv = yv ? d_out.as<double>() + 2 * plane : nullptr;
+    const dim3 grid((unsigned)((n_theta + KALMAN_THREADS - 1) / KALMAN_THREADS));
+    if (kalman_has_gap(flags, y, T))   // the MISS twin only for a flagged call whose series holds a NaN
+        hipLaunchKernelGGL((k_kalman_predictive<Lg1Row, true>), grid, dim3(KALMAN_THREADS), 0, st, d_raw.as<double>(), n_theta, d_y.as<double>(), T, predict_first,
+                           o_pit, o_ym, o_yv);
+    else
+        hipLaunchKernelGGL((k_kalman_predictive<Lg1Row, false>), grid, dim3(KALMAN_THREADS), 0, st, d_raw.as<double>(), n_theta, d_y.as<double>(), T, predict_first,
+                           o_pit, o_ym, o_yv);
+    HIPCHK(hipGetLastError());
+    if (pit) HIPCHK(hipMemcpyAsync(pit, o_pit, plane * 8, hipMemcpyDeviceToHost, st));
+    if (ym) HIPCHK(hipMemcpyAsync(ym, o_ym, plane * 8, hipMemcpyDeviceToHost, st));
+    if (yv) HIPCHK(hipMemcpyAsync(yv, o_yv, plane * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+// ... and their host twin for one row: pit, ym, yv [T] (any NULL)
+extern "C" int smc_host_kalman_predictive(const double* row, const double* y, int64_t T, int predict_first, uint32_t flags, double* pit, double* ym,
+                                          double* yv) {
+    if (flags & ~SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_host_kalman_predictive: flags is 0 or SMC_FLAG_NAN_MISSING");
+    if (!row || !y || T <= 0) return fail(SMC_EINVAL, "smc_host_kalman_predictive: bad argument");
+    const bool miss = kalman_has_gap(flags, y, T);
+    double x = row[4], S = row[5];
+    for (int64_t t = 0; t < T; ++t) {
+        double p, mu, v;
+        const bool predict = predict_first != 0 || t > 0;
+        if (miss) kalman_predictive_step<true>(row[0], row[1], row[2], row[3], predict, y[t], x, S, p, mu, v);
+        else kalman_predictive_step<false>(row[0], row[1], row[2], row[3], predict, y[t], x, S, p, mu, v);
+        if (pit) pit[t] = p;
+        if (ym) ym[t] = mu;
+        if (yv) yv[t] = v;
+    }
+    return SMC_OK;
+}
+extern "C" double smc_host_normcdf(double z) { return sp_normcdf(z); }
+extern "C" int smc_device_normcdf(const double* z, int64_t n, double* out, int device) {
+    if (!z || !out || n <= 0) return fail(SMC_EINVAL, "smc_device_normcdf: bad argument");
+    hipStream_t st = nullptr;
+    HIPCHK(util_stream(device, &st));
+    DevBuf dz(0), dout(1);
+    HIPCHK(dz.alloc((size_t)n * 8));
+    HIPCHK(dout.alloc((size_t)n * 8));
+    HIPCHK(hipMemcpyAsync(dz.p, z, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_normcdf<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dz.as<double>(), n, dout.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+// the row of ONE cloud x [d][n] (the order of smc_get_state) for the observation y: out = (pit, obs_mean, obs_var), the statement of
+// the specification in its own order (pred_sum over pred_terms, then the centred pass)
+extern "C" int smc_host_predictive(int model_id, const double* raw, const double* x, int64_t n, double y, double* out) {
+    if (!raw || !x || !out || n < 1) return fail(SMC_EINVAL, "smc_host_predictive: bad argument");
+    if (!has_density(model_id))
+        return fail(SMC_EINVAL, "smc_host_predictive: the families whose rows are a sample of the state: LG1D, SV1D, UCSV3D");
+    Params P;
+    const int nraw = model_nraw_rt(model_id);
+    for (int k = 0; k < NPARAM; ++k) P.raw[k] = k < nraw ? raw[k] : 0.0;
+    derive_params(model_id, P.raw, P.der);
+    std::vector<double> cdf((size_t)n), ymv((size_t)n), s2((size_t)n), part((size_t)((n + SMOOTH_CH - 1) / SMOOTH_CH));
+    (void)by_density_model(model_id, [&](auto Mt) {
+        constexpr int M = decltype(Mt)::value;
+        for (int64_t i = 0; i < n; ++i) {
+            double xi[3] = {x[i], 0.0, 0.0};
+            if constexpr (pred_rows<M>::count == 2) xi[pred_rows<M>::second] = x[(size_t)pred_rows<M>::second * n + i];
+            pred_terms<M>(P, xi, y, cdf[i], ymv[i], s2[i]);
+        }
+        return hipSuccess;
+    });
+    const double pit = pred_mean_of(pred_sum(n, [&](int64_t i) { return cdf[i]; }, part.data()), n);
+    const double mean = pred_mean_of(pred_sum(n, [&](int64_t i) { return ymv[i]; }, part.data()), n);
+    const double sum_s2 = pred_sum(n, [&](int64_t i) { return s2[i]; }, part.data());
+    const double sum_c = pred_sum(n, [&](int64_t i) { return pred_centred_term(ymv[i], mean); }, part.data());
+    out[0] = pit; out[1] = mean; out[2] = pred_var_of(sum_s2, sum_c, n);
+    return SMC_OK;
 }
 
 // ---- host-side helpers ---------------------------------------------------------------------------

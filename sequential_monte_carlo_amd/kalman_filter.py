@@ -2,6 +2,7 @@
 
     log_likelihood_kalman(y, model)   -> (x_T, Sigma_T, logZ)       kalman_filter.jl:55-70
     kalman_smoother(y, model)         -> (xs [T], Ps [T])           the exact RTS smoother over the same filter
+    kalman_predictive(y, model)       -> (pit, obs_mean, obs_var)   the one-step predictive law of y_t and its PIT
 and of kalman_filter.jl:3-27 for two-state models with a scalar observation (MultivariateLinearGaussian, hodrick_prescott;
 DESIGN.md 2n): (x_T [2], Sigma_T [2][2], logZ) and (xs [T][2], Ps [T][2][2]).
 
@@ -52,6 +53,19 @@ def log_likelihood_kalman(y, model, predict_first=False, device=0, missing=False
     if single:
         return float(out[0, 0]), float(out[0, 1]), float(out[0, 2])
     return out[:, 0], out[:, 1], out[:, 2]
+
+
+def kalman_predictive(y, model_or_list, missing=False, predict_first=False, device=0):
+    """(pit, obs_mean, obs_var): the exact one-step predictive law of every y_t under a LinearModel, N(B x-, B^2 S- + R) from the
+    predicted pair of the Kalman step, and its probability integral transform pit_t = Phi((y_t - obs_mean_t) / sqrt(obs_var_t)):
+    iid uniform under a correct model; pit_residuals(pit) are the standardised innovations.  [T] each; for a list
+    of LinearModels [T][n], one lane per parameter row (smc_kalman_predictive_flags).  missing=True: at a NaN y the pit is NaN
+    beside the forecast of the unobserved y_t.  What a particle filter's predictive=True estimates."""
+    single, models, two = _batch(model_or_list, "predictive check")
+    if two or not models:
+        raise TypeError("kalman_predictive: the scalar LinearModel only (two-state rows have no predictive check yet)")
+    pit, ym, yv = _lib.kalman_predictive(np.array([m.raw() for m in models]), y, predict_first, device, missing=missing)
+    return (pit[:, 0].copy(), ym[:, 0].copy(), yv[:, 0].copy()) if single else (pit, ym, yv)
 
 
 def kalman_smoother(y, model, predict_first=False, device=0, missing=False):

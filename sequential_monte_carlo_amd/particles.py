@@ -206,6 +206,15 @@ class Particles:
         _, _, a = self._f.h.state(want_w=False, want_anc=True)
         return a[0] if self._f.single else a
 
+    def predictive(self, y_t):
+        """(pit, obs_mean, obs_var) for the observation y_t the last step assimilated: pit = P(Y_t <= y_t | y_1:t-1), uniform under
+        a correct model, and the mean and variance of the one-step predictive law of y_t - computed on the device from the cloud
+        whatever its weights (a bootstrap step resamples first, so the cloud it leaves is a sample of p(x_t | y_1:t-1); DESIGN.md
+        2r).  Scalars, or [n_theta] for a list of models.  Bootstrap filters only."""
+        _predictive_check(self._f.model_id, self._f.proposal, "x.predictive")
+        pit, m, v = self._f.h.predictive(float(y_t))
+        return self._f.out(pit), self._f.out(m), self._f.out(v)
+
 
 class Weights:
     """w: the normalised weights of normalize() (particles.jl:11), resident on the GPU."""
@@ -219,6 +228,42 @@ class Weights:
 
     def __len__(self):
         return self._f.h.n_x
+
+
+def _predictive_check(model_id, proposal, who):
+    """predictive checks are defined for bootstrap filters whose rows are a sample of the state: refused without a
+    device call"""
+    if model_id == _lib.MODEL_UCSV_RB:
+        raise TypeError("%s: MarginalUCSV keeps the UPDATED Kalman pair (m, P) of the trend in its rows; the predictive pair of y_t, "
+                        "formed inside the step, is not kept - use UCSV for predictive checks" % who)
+    if proposal is not None:
+        raise ValueError("%s: a guided filter's cloud is drawn from the proposal and is not a sample of p(x_t | y_1:t-1); "
+                         "predictive checks need the bootstrap filter (proposal=None)" % who)
+
+
+def _predictive_out(f, rows):
+    """(pit, obs_mean, obs_var) [T][n_theta] each -> the dict entries, [T] for a single model"""
+    keys = ("pit", "obs_mean", "obs_var")
+    return {k: (r[:, 0] if f.single else r) for k, r in zip(keys, rows)}
+
+
+def pit_residuals(pit):
+    """Phi^-1(pit): the normalised forecast residuals, iid N(0, 1) under a correct model (their correlogram shows a wrong
+    persistence, their variance a wrong observation noise).  statistics.NormalDist().inv_cdf elementwise; 0 -> -inf, 1 -> +inf,
+    NaN (a gap) stays NaN."""
+    import statistics
+    inv = statistics.NormalDist().inv_cdf
+    p = np.asarray(pit, dtype=np.float64)
+
+    def one(u):
+        if u != u:
+            return np.nan
+        if u <= 0.0:
+            return -np.inf
+        if u >= 1.0:
+            return np.inf
+        return inv(u)
+    return np.array([one(float(u)) for u in p.ravel()]).reshape(p.shape)
 
 
 def bootstrap_filter(N, y, model, seed=None, seg=0, device=0, streams=None, ancestors=False, resampler="multinomial", missing=False):
@@ -288,7 +333,8 @@ def _summaries_out(f, T):
 
 
 def log_likelihood(N, y, model, seed=None, seg=0, device=0, streams=None, ancestors=False, trace=False,
-                   resampler="multinomial", quantiles=None, component=0, moments=False, weighted=True, proposal=None, missing=False):
+                   resampler="multinomial", quantiles=None, component=0, moments=False, weighted=True, proposal=None, missing=False,
+                   predictive=False):
     """x, w, logZ = log_likelihood(N, y, model)   particles.jl:132-147
     trace=True additionally returns the per-step (logmu_t, ess_t).  resampler="systematic": opt-in systematic
     resampling (same expectation, lower variance, one launch per step for big filters; not the reference's law).
@@ -299,11 +345,37 @@ def log_likelihood(N, y, model, seed=None, seg=0, device=0, streams=None, ancest
     weighted=True (the default) the weighted inverse CDF and the uncorrected weighted variance.
     proposal: the guided filter (particle_filter_ at every step after the first) instead of the bootstrap filter.
     missing=True (opt-in): NaN entries of y are periods without an observation: they add nothing to logZ, and the
-    per-step summaries there are those of the propagated cloud."""
+    per-step summaries there are those of the propagated cloud.
+    predictive=True: predictive checks - a dict s behind the usual results with s["pit"], s["obs_mean"],
+    s["obs_var"], each [T] (a batch axis follows T): the probability integral transform of every y_t under its one-step predictive
+    law, and that law's mean and variance (see Particles.predictive; pit_residuals(s["pit"]) are the normalised residuals).  The
+    filter then runs step by step, one launch more per step, and keeps no record.  Bootstrap filters only; not together with
+    quantiles= / moments=.  At a gap (missing=True) the pit is NaN and the moments are the forecast of the unobserved y_t."""
+    if predictive:
+        if quantiles is not None or moments:
+            raise ValueError("predictive=True runs step by step; the per-step summaries (quantiles=, moments=) belong to the whole-series call")
+        _predictive_check(params_matrix(model)[0], proposal, "log_likelihood(predictive=True)")
     if seed is None:
         seed = next(_seed_counter)
     f = _Filters(int(N), model, seed, seg, device, streams, ancestors, resampler, proposal, missing=missing)
     y = np.ascontiguousarray(y, dtype=np.float64)
+    if predictive:
+        y = y.ravel()
+        lm, es, rows = np.zeros((y.size, f.h.n_theta)), np.zeros((y.size, f.h.n_theta)), np.zeros((3, y.size, f.h.n_theta))
+        for t in range(y.size):
+            if t == 0:
+                lm[0] = f.h.init(float(y[0]))
+                es[0] = f.h.logZ()[1]
+            else:
+                lm[t], es[t] = f.h.step(float(y[t]))
+            rows[0, t], rows[1, t], rows[2, t] = f.h.predictive(float(y[t]))
+        logZ = f.h.logZ()[0]
+        extra = _predictive_out(f, rows)
+        if trace:
+            if f.single:
+                lm, es = lm[:, 0], es[:, 0]
+            return Particles(f), Weights(f), f.out(logZ), lm, es, extra
+        return Particles(f), Weights(f), f.out(logZ), extra
     summ = quantiles is not None or moments
     if summ:
         f.h.set_summaries(quantiles, component, moments)
@@ -442,7 +514,8 @@ def _smooth_quantile_args(quantiles, component, model, rows):
 
 
 def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="multinomial", proposal=None, weights=False, rows=None,
-             paths=0, path_seed=None, path_counts=None, smooth=True, missing=False, reference=None, pairs=False, quantiles=None, component=0):
+             paths=0, path_seed=None, path_counts=None, smooth=True, missing=False, reference=None, pairs=False, quantiles=None, component=0,
+             predictive=False):
     """x, w, logZ, s = smoother(N, y, model): the particle filter of log_likelihood run step by step with its clouds recorded on
     the device, then the FFBS backward pass over them (forward filtering, backward smoothing).  x, w, logZ are the
     filter's, as log_likelihood returns them; s describes p(x_t | y_1:T):
@@ -467,6 +540,9 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
                                     `component` under the smoothed weights, selected on the device in the same backward pass
                                     (DESIGN.md 2q): the 25 / 50 / 75 % band of p(x_t | y_1:T) without a copy of the weights.  The
                                     definition of log_likelihood's quantiles=: no interpolation.  The batch axis follows T.
+        s["pit"], s["obs_mean"], s["obs_var"]  (predictive=True) predictive checks of the FILTER over the recorded clouds, in one launch
+                                    (the keys of log_likelihood(predictive=True), the same bits).  Bootstrap filters
+                                    only: ValueError with a proposal or a reference.
     The backward pass costs 2 N^2 (T - 1) transition densities per filter.  Any proposal, either resampler; MarginalUCSV has no
     smoother of this kind (its state rows have no transition density): rb_smoother is its smoother.
     rows=(model id, parameter rows [n_theta][n_raw]) with model=None: a batch given as rows (what the samplers hold).
@@ -481,6 +557,10 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
         if not smooth:
             raise ValueError("quantiles=... needs the backward pass of the marginals (smooth=True): they are selected under its weights")
         quantiles = _smooth_quantile_args(quantiles, component, model, rows)
+    if predictive:
+        _predictive_check(int(rows[0]) if rows is not None else params_matrix(model)[0], proposal, "smoother(predictive=True)")
+        if reference is not None:
+            raise ValueError("smoother(predictive=True): a conditional filter's cloud holds the pinned reference and is not a predictive sample")
     if seed is None:
         seed = next(_seed_counter)
     f = _Filters(int(N), model, seed, seg, device, streams, False, resampler, proposal, rows=rows, missing=missing,
@@ -518,6 +598,8 @@ def smoother(N, y, model, seed=None, seg=0, device=0, streams=None, resampler="m
             idx, xp = h.sample_paths(int(paths), _path_seed(seed) if path_seed is None else int(path_seed), counts=path_counts)
             s["path_index"], s["paths"] = _paths_out(idx, xp, f.single)
         s["logmu"], s["ess"] = (lm[:, 0], es[:, 0]) if f.single else (lm, es)
+        if predictive:
+            s.update(_predictive_out(f, h.predictive_record(y)))
         if weights:
             xs = np.array([h.history_get(t)[0] for t in range(T)])        # [T][d][n_theta][N]
             xs = np.moveaxis(xs, 1, -1)                                    # [T][n_theta][N][d]
