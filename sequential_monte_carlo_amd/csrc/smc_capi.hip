@@ -413,8 +413,7 @@ extern "C" int smc_set_params(smc_handle h, const double* raw) {
     else HIPCHK(hipStreamSynchronize(h->stream));
     Params* P = h->h_params.as<Params>();
     for (int m = 0; m < h->v.ntheta; ++m) {
-        for (int k = 0; k < NPARAM; ++k) P[m].raw[k] = k < nraw ? raw[(size_t)m * nraw + k] : 0.0;
-        derive_params(h->model, P[m].raw, P[m].der);
+        params_from_raw(h->model, raw + (size_t)m * nraw, P[m]);
         if (h->v.prop_kind) fill_proposal(h, m);
     }
     HIPCHK(hipMemcpyAsync(h->d_params, P, (size_t)h->v.ntheta * sizeof(Params), hipMemcpyHostToDevice, h->stream));

@@ -2,7 +2,8 @@
 // the filter handle, and the few helpers that cross files.  Internal: not installed, not part of the ABI (include/smc_hip.h).
 // Which kernel variant a launch of a handle means: pick_variant, here.
 // The entry points on a handle: smc_capi.hip (core), smc_capi_series.hip, smc_capi_summ.hip, smc_capi_pmmh.hip,
-// smc_capi_slots.hip, smc_capi_smooth.hip, smc_capi_forecast.hip; without one: smc_util.hip.
+// smc_capi_slots.hip, smc_capi_smooth.hip, smc_capi_forecast.hip; without one: smc_util.hip, and the exact-Kalman row calls of
+// smc_kalman2.hip and smc_ibis.hip - all of them through DeviceCall, here.
 #pragma once
 #include "../../include/smc_hip.h"
 #include "smc_launch.h"
@@ -23,11 +24,15 @@ int fail(int code, const std::string& msg);
             return fail(SMC_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" +      \
                                       std::to_string(__LINE__) + ")");                                        \
     } while (0)
+// the refusal of a call whose own allocation failed with e
+inline int alloc_fail(const char* who, hipError_t e) {
+    return fail(e == hipErrorOutOfMemory ? SMC_ENOMEM : SMC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+}
 
 // ---- memory ----------------------------------------------------------------------------------------
 // Every device and pinned allocation of the library is a Block: it owns one pointer and its size in bytes, moves (the source is
 // left empty), does not copy, and frees in its destructor.  The only calls of hipMalloc / hipHostMalloc / hipFree / hipHostFree
-// outside the per-thread scratch of smc_util.hip and the SMC_ABLATE stamps.  A block never synchronises and never selects a
+// outside the one per-thread scratch of the calls without a handle (DeviceCall::use_scratch) and the SMC_ABLATE stamps.  A block never synchronises and never selects a
 // device: whoever replaces a block the stream may still read waits for the stream first, and whoever lets a handle go selects
 // its device first.  Two ways to grow, both no-ops (no runtime call) when the block already holds `need` bytes, both returning
 // HIP's error with the sticky error cleared; 0 bytes are allocated as 16.  Kernels only ever see views: plain pointers into blocks.
@@ -85,6 +90,38 @@ using PinBlock = Block<true>;    // hipHostMalloc(hipHostMallocDefault) / hipHos
 struct OffsetPlan {
     size_t bytes = 0;
     size_t take(size_t n) { const size_t o = bytes; bytes += (n + 255) & ~(size_t)255; return o; }
+};
+
+// The scope of an entry point that runs on the device WITHOUT a handle: after its own argument checks it opens one of these,
+// take()s the offsets of all its arrays, asks ONCE for the memory, and then copies, launches (plain hipLaunchKernelGGL on
+// `stream`) and waits.  Nothing is planned after the allocation, so no array of a call can move or alias another.
+//   begin       device checked against hipGetDeviceCount (SMC_EHIP "<who>: no HIP device", SMC_EINVAL "<who>: bad device"), then
+//               selected; stream = the calling thread's hipStreamNonBlocking stream of that device (a table of 16 per thread,
+//               created on first use; a device index >= 16 falls back to the null stream).  The streams are never destroyed,
+//               not at thread exit either.
+//   use_scratch the plan lies in the calling thread's ONE cached allocation: grown when the plan needs more or the device
+//               changed, freed at thread exit, NOT counted by smc_live_bytes - the one raw hipMalloc / hipFree outside Block
+//               (a hipMalloc / hipFree of a whole cloud's worth per call cost 30 ms per normalize at 2^20 entries, ten times the work)
+//   use_own     the plan lies in a block of this scope: counted while the call runs, freed when the scope dies
+//               (failure: SMC_ENOMEM / SMC_EHIP "<who>: <hip string>")
+// Defined in smc_util.hip.
+class DeviceCall {
+    const char* who_ = "";
+    OffsetPlan plan_;
+    DevBlock own_;
+    char* base_ = nullptr;
+    int device_ = -1;
+
+public:
+    hipStream_t stream = nullptr;
+    int begin(const char* who, int device);
+    size_t take(size_t bytes) { return plan_.take(bytes); }
+    int use_scratch();
+    int use_own();
+    template <class T> T* at(size_t off) const { return (T*)(base_ + off); }
+    hipError_t upload(size_t off, const void* host, size_t bytes) { return hipMemcpyAsync(base_ + off, host, bytes, hipMemcpyHostToDevice, stream); }
+    hipError_t download(void* host, size_t off, size_t bytes) { return hipMemcpyAsync(host, base_ + off, bytes, hipMemcpyDeviceToHost, stream); }
+    hipError_t finish() { return hipStreamSynchronize(stream); }
 };
 
 // ---- the filter handle ---------------------------------------------------------------------------
@@ -214,6 +251,12 @@ struct smc_filter_s {
     } pm;
 };
 
+// the parameter row of a known family from the caller's: raw [model_nraw_rt(model)] copied, the tail zero, der derived
+inline void params_from_raw(int model, const double* raw, smc::Params& P) {
+    const int nraw = smc::model_nraw_rt(model);
+    for (int k = 0; k < smc::NPARAM; ++k) P.raw[k] = k < nraw ? raw[k] : 0.0;
+    smc::derive_params(model, P.raw, P.der);
+}
 // a row of smc_set_proposal(AFFINE) is usable (smc_capi.hip, and the guided probes of smc_util.hip)
 inline bool affine_row_ok(const double* par) {
     for (int k = 0; k < smc::PROP_NPAR; ++k)

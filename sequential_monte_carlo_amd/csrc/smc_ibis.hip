@@ -794,19 +794,12 @@ extern "C" int smc_ibis_get(void* hp, double* theta, double* x, double* S, doubl
 // ---- the RTS smoother of the cloud and its backward-sampled paths (smc_spec.h "the RTS smoother of an IBIS cloud") -------------
 // Everything these calls need on the device is allocated by the call and freed before it returns: the handle is read only.
 namespace {
-// one device allocation for the life of a call: a local block, freed when the call returns
-int call_alloc(DevBlock& blk, const char* who, size_t bytes) {
-    const hipError_t e = blk.grow(bytes);
-    if (e == hipSuccess) return SMC_OK;
-    return fail(e == hipErrorOutOfMemory ? SMC_ENOMEM : SMC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
-}
 struct CallEvents {   // the bracket of a call's kernels on the handle's stream
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~CallEvents() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
     hipError_t create() { const hipError_t e = hipEventCreate(&e0); return e != hipSuccess ? e : hipEventCreate(&e1); }
     double ms() const { float f = 0.0f; return hipEventElapsedTime(&f, e0, e1) == hipSuccess ? (double)f : -1.0; }
 };
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 constexpr int64_t RTS_MAX_T = (int64_t)1 << 31;   // the step index is a 32-bit word of the Philox counter
 }  // namespace
 
@@ -819,12 +812,15 @@ extern "C" int smc_ibis_smooth(void* hp, const double* y, int64_t T, double* out
     if (h->win_k > 0) return fail(SMC_ESTATE, "smc_ibis_smooth: a window is pending (smc_ibis_commit first)");
     HIPCHK(hipSetDevice(h->device));
     const size_t M = (size_t)h->v.M, nchunk = grid_of(h->v.M), sT = (size_t)T;
-    const size_t b_y = up256(sT * 8), b_rec = up256(sT * M * 8), b_part = up256(sT * IBIS_SUM_NCOL * nchunk * 8), b_out = sT * IBIS_SUM_NOUT * 8;
-    DevBlock blk;
-    if (const int rc = call_alloc(blk, "smc_ibis_smooth", b_y + 2 * b_rec + b_part + b_out)) return rc;
+    const size_t b_out = sT * IBIS_SUM_NOUT * 8;
+    OffsetPlan plan;
+    const size_t o_y = plan.take(sT * 8), o_xf = plan.take(sT * M * 8), o_Sf = plan.take(sT * M * 8);
+    const size_t o_part = plan.take(sT * IBIS_SUM_NCOL * nchunk * 8), o_out = plan.take(b_out);
+    DevBlock blk;   // (a local block: freed when the call returns)
+    if (const hipError_t e = blk.grow(plan.bytes)) return alloc_fail("smc_ibis_smooth", e);
     char* const base = blk.as<char>();
-    double *d_y = (double*)base, *d_xf = (double*)(base + b_y), *d_Sf = (double*)(base + b_y + b_rec);
-    double *d_part = (double*)(base + b_y + 2 * b_rec), *d_out = (double*)(base + b_y + 2 * b_rec + b_part);
+    double *d_y = (double*)(base + o_y), *d_xf = (double*)(base + o_xf), *d_Sf = (double*)(base + o_Sf);
+    double *d_part = (double*)(base + o_part), *d_out = (double*)(base + o_out);
     const bool store = xs != nullptr || Ps != nullptr;
     CallEvents ev;
     HIPCHK(ev.create());
@@ -861,13 +857,14 @@ extern "C" int smc_ibis_sample_paths(void* hp, const double* y, int64_t T, int64
         if (which[p] < 0 || which[p] >= h->v.M) return fail(SMC_EINVAL, "smc_ibis_sample_paths: which entry outside [0, n_theta)");
     HIPCHK(hipSetDevice(h->device));
     const size_t sM = (size_t)Mp, sT = (size_t)T;
-    const size_t b_y = up256(sT * 8), b_w = up256(sM * 4), b_rec = up256(sT * sM * 8);
+    OffsetPlan plan;
+    const size_t o_y = plan.take(sT * 8), o_w = plan.take(sM * 4), o_paths = plan.take(sT * sM * 8), o_Sf = plan.take(sT * sM * 8);
     DevBlock blk;
-    if (const int rc = call_alloc(blk, "smc_ibis_sample_paths", b_y + b_w + 2 * b_rec)) return rc;
+    if (const hipError_t e = blk.grow(plan.bytes)) return alloc_fail("smc_ibis_sample_paths", e);
     char* const base = blk.as<char>();
-    double* d_y = (double*)base;
-    int32_t* d_w = (int32_t*)(base + b_y);
-    double *d_paths = (double*)(base + b_y + b_w), *d_Sf = (double*)(base + b_y + b_w + b_rec);
+    double* d_y = (double*)(base + o_y);
+    int32_t* d_w = (int32_t*)(base + o_w);
+    double *d_paths = (double*)(base + o_paths), *d_Sf = (double*)(base + o_Sf);
     HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, h->stream));
     CallEvents ev;
     HIPCHK(ev.create());
@@ -901,26 +898,21 @@ extern "C" int smc_kalman_smooth_flags(const double* raw, int64_t n_theta, const
     if (flags & ~SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_kalman_smooth: flags is 0 or SMC_FLAG_NAN_MISSING");
     if (!raw || !y || !xs || !Ps) return fail(SMC_EINVAL, "smc_kalman_smooth: bad argument");
     if (n_theta < 1 || n_theta > ((int64_t)1 << 30) || T < 1 || T > RTS_MAX_T) return fail(SMC_EINVAL, "smc_kalman_smooth: 1 <= n_theta <= 2^30, 1 <= T <= 2^31");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(SMC_EHIP, "smc_kalman_smooth: no HIP device");
-    if (device < 0 || device >= ndev) return fail(SMC_EINVAL, "smc_kalman_smooth: bad device");
-    HIPCHK(hipSetDevice(device));
-    const size_t M = (size_t)n_theta, sT = (size_t)T;
-    const size_t b_y = up256(sT * 8), b_raw = up256(M * IBIS_NRAW * 8), b_rec = up256(sT * M * 8);
-    DevBlock blk;
-    if (const int rc = call_alloc(blk, "smc_kalman_smooth", b_y + b_raw + 2 * b_rec)) return rc;
-    char* const base = blk.as<char>();
-    double *d_y = (double*)base, *d_raw = (double*)(base + b_y), *d_xf = (double*)(base + b_y + b_raw), *d_Sf = (double*)(base + b_y + b_raw + b_rec);
-    hipStream_t st = nullptr;   // the default stream: the call owns nothing that outlives it
-    HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_raw, raw, M * IBIS_NRAW * 8, hipMemcpyHostToDevice, st));
-    launch_rts_forward(st, kalman_has_gap(flags, y, T), d_raw, n_theta, d_y, T, predict_first ? 1 : 0, d_xf, d_Sf);
-    hipLaunchKernelGGL((k_ibis_rts_backward<false, true>), dim3(grid_of(n_theta)), dim3(IBIS_THREADS), 0, st, (const double*)d_raw,
+    DeviceCall c;   // (its memory is the call's own: counted while it runs, freed when it returns)
+    if (const int rc = c.begin("smc_kalman_smooth", device)) return rc;
+    const size_t b_y = (size_t)T * 8, b_raw = (size_t)n_theta * IBIS_NRAW * 8, b_rec = (size_t)T * (size_t)n_theta * 8;
+    const size_t o_y = c.take(b_y), o_raw = c.take(b_raw), o_xf = c.take(b_rec), o_Sf = c.take(b_rec);
+    if (const int rc = c.use_own()) return rc;
+    double *d_raw = c.at<double>(o_raw), *d_xf = c.at<double>(o_xf), *d_Sf = c.at<double>(o_Sf);
+    HIPCHK(c.upload(o_y, y, b_y));
+    HIPCHK(c.upload(o_raw, raw, b_raw));
+    launch_rts_forward(c.stream, kalman_has_gap(flags, y, T), d_raw, n_theta, c.at<double>(o_y), T, predict_first ? 1 : 0, d_xf, d_Sf);
+    hipLaunchKernelGGL((k_ibis_rts_backward<false, true>), dim3(grid_of(n_theta)), dim3(IBIS_THREADS), 0, c.stream, (const double*)d_raw,
                        (const double*)nullptr, n_theta, T, d_xf, d_Sf, (double*)nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(xs, d_xf, sT * M * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(Ps, d_Sf, sT * M * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(c.download(xs, o_xf, b_rec));
+    HIPCHK(c.download(Ps, o_Sf, b_rec));
+    HIPCHK(c.finish());
     return SMC_OK;
 }
 extern "C" int smc_kalman_smooth(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first, double* xs, double* Ps,

@@ -10,58 +10,46 @@ using namespace smc;
 
 namespace {
 constexpr int64_t K2_MAX_N = (int64_t)1 << 30, K2_MAX_T = (int64_t)1 << 31;
-size_t k2_up256(size_t b) { return (b + 255) & ~(size_t)255; }
 unsigned k2_grid(int64_t n) { return (unsigned)((n + KALMAN_THREADS - 1) / KALMAN_THREADS); }
-
-// the checks every device call of this file shares, and the call's one allocation (freed when the call returns)
-int k2_begin(const char* who, int64_t n, int64_t T, int device, DevBlock& blk, size_t bytes) {
-    if (n < 1 || n > K2_MAX_N || T < 1 || T > K2_MAX_T) return fail(SMC_EINVAL, std::string(who) + ": 1 <= n <= 2^30, 1 <= T <= 2^31");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(SMC_EHIP, std::string(who) + ": no HIP device");
-    if (device < 0 || device >= ndev) return fail(SMC_EINVAL, std::string(who) + ": bad device");
-    HIPCHK(hipSetDevice(device));
-    const hipError_t e = blk.grow(bytes);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SMC_ENOMEM : SMC_EHIP, std::string(who) + ": " + hipGetErrorString(e));
-    return SMC_OK;
-}
+// the sizes every device call of this file accepts
+bool k2_sizes_ok(int64_t n, int64_t T) { return n >= 1 && n <= K2_MAX_N && T >= 1 && T <= K2_MAX_T; }
 }  // namespace
 
+// Both device calls own their memory for the call (DeviceCall::use_own: counted while it runs, freed when it returns)
 extern "C" int smc_kalman2_log_likelihood(const double* raw, int64_t n, const double* y, int64_t T, int predict_first, double* out, int device) {
     if (!raw || !y || !out) return fail(SMC_EINVAL, "smc_kalman2_log_likelihood: bad argument");
-    const size_t sn = n > 0 ? (size_t)n : 0, sT = T > 0 ? (size_t)T : 0;
-    const size_t b_y = k2_up256(sT * 8), b_raw = k2_up256(sn * LG2_NRAW * 8), b_out = sn * 6 * 8;
-    DevBlock blk;
-    if (const int rc = k2_begin("smc_kalman2_log_likelihood", n, T, device, blk, b_y + b_raw + b_out)) return rc;
-    char* const base = blk.as<char>();
-    double *d_y = (double*)base, *d_raw = (double*)(base + b_y), *d_out = (double*)(base + b_y + b_raw);
-    hipStream_t st = nullptr;   // the default stream: the call owns nothing that outlives it
-    HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_raw, raw, sn * LG2_NRAW * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL((k_kalman_loglik<Lg2Row>), dim3(k2_grid(n)), dim3(KALMAN_THREADS), 0, st, (const double*)d_raw, n, (const double*)d_y, T,
-                       predict_first ? 1 : 0, d_out);
+    if (!k2_sizes_ok(n, T)) return fail(SMC_EINVAL, "smc_kalman2_log_likelihood: 1 <= n <= 2^30, 1 <= T <= 2^31");
+    DeviceCall c;
+    if (const int rc = c.begin("smc_kalman2_log_likelihood", device)) return rc;
+    const size_t b_y = (size_t)T * 8, b_raw = (size_t)n * LG2_NRAW * 8, b_out = (size_t)n * 6 * 8;
+    const size_t o_y = c.take(b_y), o_raw = c.take(b_raw), o_out = c.take(b_out);
+    if (const int rc = c.use_own()) return rc;
+    HIPCHK(c.upload(o_y, y, b_y));
+    HIPCHK(c.upload(o_raw, raw, b_raw));
+    hipLaunchKernelGGL((k_kalman_loglik<Lg2Row>), dim3(k2_grid(n)), dim3(KALMAN_THREADS), 0, c.stream, c.at<const double>(o_raw), n,
+                       c.at<const double>(o_y), T, predict_first ? 1 : 0, c.at<double>(o_out));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(c.download(out, o_out, b_out));
+    HIPCHK(c.finish());
     return SMC_OK;
 }
 
 extern "C" int smc_kalman2_smooth(const double* raw, int64_t n, const double* y, int64_t T, int predict_first, double* xs, double* Ps, int device) {
     if (!raw || !y || !xs || !Ps) return fail(SMC_EINVAL, "smc_kalman2_smooth: bad argument");
-    const size_t sn = n > 0 ? (size_t)n : 0, sT = T > 0 ? (size_t)T : 0;
-    const size_t b_y = k2_up256(sT * 8), b_raw = k2_up256(sn * LG2_NRAW * 8), b_xs = k2_up256(sT * sn * 2 * 8), b_Ps = sT * sn * 3 * 8;
-    DevBlock blk;
-    if (const int rc = k2_begin("smc_kalman2_smooth", n, T, device, blk, b_y + b_raw + b_xs + b_Ps)) return rc;
-    char* const base = blk.as<char>();
-    double *d_y = (double*)base, *d_raw = (double*)(base + b_y), *d_xs = (double*)(base + b_y + b_raw), *d_Ps = (double*)(base + b_y + b_raw + b_xs);
-    hipStream_t st = nullptr;
-    HIPCHK(hipMemcpyAsync(d_y, y, sT * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_raw, raw, sn * LG2_NRAW * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_kalman2_smooth, dim3(k2_grid(n)), dim3(KALMAN_THREADS), 0, st, (const double*)d_raw, n, (const double*)d_y, T,
-                       predict_first ? 1 : 0, d_xs, d_Ps);
+    if (!k2_sizes_ok(n, T)) return fail(SMC_EINVAL, "smc_kalman2_smooth: 1 <= n <= 2^30, 1 <= T <= 2^31");
+    DeviceCall c;
+    if (const int rc = c.begin("smc_kalman2_smooth", device)) return rc;
+    const size_t b_y = (size_t)T * 8, b_raw = (size_t)n * LG2_NRAW * 8, b_xs = (size_t)T * n * 2 * 8, b_Ps = (size_t)T * n * 3 * 8;
+    const size_t o_y = c.take(b_y), o_raw = c.take(b_raw), o_xs = c.take(b_xs), o_Ps = c.take(b_Ps);
+    if (const int rc = c.use_own()) return rc;
+    HIPCHK(c.upload(o_y, y, b_y));
+    HIPCHK(c.upload(o_raw, raw, b_raw));
+    hipLaunchKernelGGL(k_kalman2_smooth, dim3(k2_grid(n)), dim3(KALMAN_THREADS), 0, c.stream, c.at<const double>(o_raw), n, c.at<const double>(o_y), T,
+                       predict_first ? 1 : 0, c.at<double>(o_xs), c.at<double>(o_Ps));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(xs, d_xs, sT * sn * 2 * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(Ps, d_Ps, b_Ps, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(c.download(xs, o_xs, b_xs));
+    HIPCHK(c.download(Ps, o_Ps, b_Ps));
+    HIPCHK(c.finish());
     return SMC_OK;
 }
 

@@ -1,6 +1,6 @@
-// smc_util.hip -- the entry points that take no filter handle: stand-alone normalize / resample / Kalman (with their
-// thread-local scratch), simulation, and the host (smc_host_*) and device (smc_device_*) probes of the numerical spec that the
-// tests use.  Kernels in smc_util_kernels.h and below.
+// smc_util.hip -- the entry points that take no filter handle: the scope they all open (DeviceCall, smc_host.h: device, stream,
+// memory), stand-alone normalize / resample / Kalman, simulation, and the host (smc_host_*) and device (smc_device_*) probes of
+// the numerical spec that the tests use.  Kernels in smc_util_kernels.h and below.
 #include "smc_host.h"
 #include "smc_util_kernels.h"
 #include "smc_pred_kernels.h"
@@ -11,93 +11,81 @@
 
 using namespace smc;
 
+// ---- DeviceCall (smc_host.h): the scope of every call without a handle ---------------------------
+int DeviceCall::begin(const char* who, int device) {
+    static thread_local hipStream_t streams[16] = {};   // (never destroyed: see smc_host.h)
+    who_ = who;
+    device_ = device;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(SMC_EHIP, std::string(who) + ": no HIP device");
+    if (device < 0 || device >= ndev) return fail(SMC_EINVAL, std::string(who) + ": bad device");
+    HIPCHK(hipSetDevice(device));
+    if (device < 16 && !streams[device]) HIPCHK(hipStreamCreateWithFlags(&streams[device], hipStreamNonBlocking));
+    stream = device < 16 ? streams[device] : nullptr;
+    return SMC_OK;
+}
+int DeviceCall::use_scratch() {
+    static thread_local struct Scratch {
+        void* p = nullptr;
+        size_t cap = 0;
+        int device = -1;
+        ~Scratch() { if (p) (void)hipFree(p); }
+    } c;
+    const size_t need = plan_.bytes ? plan_.bytes : 16;
+    if (c.cap < need || c.device != device_) {
+        if (c.p) { (void)hipFree(c.p); c.p = nullptr; c.cap = 0; }
+        void* q = nullptr;
+        HIPCHK(hipMalloc(&q, need));
+        c.p = q; c.cap = need; c.device = device_;
+    }
+    base_ = (char*)c.p;
+    return SMC_OK;
+}
+int DeviceCall::use_own() {
+    const hipError_t e = own_.grow(plan_.bytes);
+    if (e != hipSuccess) return alloc_fail(who_, e);
+    base_ = own_.as<char>();
+    return SMC_OK;
+}
+
 // ---- stand-alone normalize / resample ------------------------------------------------------------
 static int fix_bits_for(int64_t n) {
     const int k = 61 - ceil_log2_i64(n);
     return k > FIX_BITS ? FIX_BITS : k;
 }
 
-// Scratch of the stand-alone entry points: device buffers kept per (host thread, slot) and grown on demand - hipMalloc / hipFree of a
-// whole cloud's worth on every call cost 30 ms per normalize at 2^20 entries, ten times the work - released when the thread
-// ends; and a private non-blocking stream per (host thread, device) so that these calls never serialise against the null stream.
-namespace {
-struct ScratchSlot {
-    void* p = nullptr;
-    size_t cap = 0;
-    int device = -1;
-    ~ScratchSlot() { if (p) (void)hipFree(p); }
-};
-struct DevBuf {   // a view of one cached slot: alloc() may be called once per call and slot
-    void* p = nullptr;
-    int slot;
-    explicit DevBuf(int s) : slot(s) {}
-    hipError_t alloc(size_t bytes) {
-        static thread_local ScratchSlot slots[8];
-        ScratchSlot& c = slots[slot];
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        bytes = bytes ? bytes : 16;
-        if (c.cap < bytes || c.device != dev) {
-            if (c.p) { (void)hipFree(c.p); c.p = nullptr; c.cap = 0; }
-            e = hipMalloc(&c.p, bytes);
-            if (e != hipSuccess) return e;
-            c.cap = bytes;
-            c.device = dev;
-        }
-        p = c.p;
-        return hipSuccess;
-    }
-    template <class T> T* as() const { return (T*)p; }
-};
-hipError_t util_stream(int device, hipStream_t* out) {
-    static thread_local hipStream_t streams[16] = {};
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return e;
-    if (device < 0 || device >= 16) { *out = nullptr; return hipSuccess; }
-    if (!streams[device]) {
-        e = hipStreamCreateWithFlags(&streams[device], hipStreamNonBlocking);
-        if (e != hipSuccess) return e;
-    }
-    *out = streams[device];
-    return hipSuccess;
-}
-}  // namespace
-
 extern "C" int smc_normalize(const double* logw, int64_t n, double* w, double* logmu, double* ess, int device) {
     if (!logw || !w || n <= 0) return fail(SMC_EINVAL, "smc_normalize: bad argument");
-    hipStream_t st = nullptr;
-    HIPCHK(util_stream(device, &st));
-    DevBuf d_in(0), d_w(1), d_o(2);
-    HIPCHK(d_in.alloc((size_t)n * 8));
-    HIPCHK(d_w.alloc((size_t)n * 8));
-    HIPCHK(d_o.alloc(16));
-    HIPCHK(hipMemcpyAsync(d_in.p, logw, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    DeviceCall c;
+    if (const int rc = c.begin("smc_normalize", device)) return rc;
+    const size_t b_n = (size_t)n * 8;
+    const size_t o_in = c.take(b_n), o_w = c.take(b_n), o_o = c.take(16), o_acc = c.take(5 * 8);   // (acc: the grid-wide branch only)
+    if (const int rc = c.use_scratch()) return rc;
+    const hipStream_t st = c.stream;
+    double *d_in = c.at<double>(o_in), *d_w = c.at<double>(o_w), *d_o = c.at<double>(o_o);
+    HIPCHK(c.upload(o_in, logw, b_n));
     if (n <= 16384) {
         // one workgroup: the outer reweight works on n_theta-vectors (a few thousand entries)
-        hipLaunchKernelGGL((k_normalize<1024>), dim3(1), dim3(1024), 0, st, d_in.as<double>(), n, fix_bits_for(n), d_w.as<double>(), d_o.as<double>());
+        hipLaunchKernelGGL((k_normalize<1024>), dim3(1), dim3(1024), 0, st, d_in, n, fix_bits_for(n), d_w, d_o);
         HIPCHK(hipGetLastError());
     } else {
         // a whole cloud's log-weights: three grid-wide passes, every cross-workgroup combination an integer one (same bits)
-        DevBuf d_acc(3);
-        HIPCHK(d_acc.alloc(5 * 8));
-        unsigned long long* acc = d_acc.as<unsigned long long>();
+        unsigned long long* acc = c.at<unsigned long long>(o_acc);
         int* kmax_i = reinterpret_cast<int*>(acc + 4);
         HIPCHK(hipMemsetAsync(acc, 0, 32, st));
         HIPCHK(hipMemsetD32Async(kmax_i, NORM_DEAD, 1, st));
         int64_t nb = (n + 4 * 256 - 1) / (4 * 256);
         nb = nb > 2048 ? 2048 : nb;
         const int K = fix_bits_for(n);
-        hipLaunchKernelGGL((k_normalize_max<256>), dim3((unsigned)nb), dim3(256), 0, st, d_in.as<double>(), n, kmax_i);
-        hipLaunchKernelGGL((k_normalize_sum<256>), dim3((unsigned)nb), dim3(256), 0, st, d_in.as<double>(), n, K, kmax_i, acc);
-        hipLaunchKernelGGL((k_normalize_write<256>), dim3((unsigned)nb), dim3(256), 0, st, d_in.as<double>(), n, K, kmax_i, acc,
-                           d_w.as<double>(), d_o.as<double>());
-        HIPCHK(hipGetLastError());   // (d_acc is a cached slot of this thread: it outlives the block)
+        hipLaunchKernelGGL((k_normalize_max<256>), dim3((unsigned)nb), dim3(256), 0, st, d_in, n, kmax_i);
+        hipLaunchKernelGGL((k_normalize_sum<256>), dim3((unsigned)nb), dim3(256), 0, st, d_in, n, K, kmax_i, acc);
+        hipLaunchKernelGGL((k_normalize_write<256>), dim3((unsigned)nb), dim3(256), 0, st, d_in, n, K, kmax_i, acc, d_w, d_o);
+        HIPCHK(hipGetLastError());
     }
     double o[2];
-    HIPCHK(hipMemcpyAsync(w, d_w.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(o, d_o.p, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(c.download(w, o_w, b_n));
+    HIPCHK(c.download(o, o_o, 16));
+    HIPCHK(c.finish());
     if (logmu) *logmu = o[0];
     if (ess) *ess = o[1];
     return SMC_OK;
@@ -108,41 +96,42 @@ extern "C" int smc_resample(const double* w, int64_t n, int64_t ndraw, uint64_t 
     if (!w || !a || n <= 0 || ndraw < 0) return fail(SMC_EINVAL, "smc_resample: bad argument");
     if (n > ((int64_t)1 << 31)) return fail(SMC_EINVAL, "smc_resample: n > 2^31");
     if (ndraw == 0) return SMC_OK;
-    hipStream_t st = nullptr;
-    HIPCHK(util_stream(device, &st));
-    DevBuf d_w(0), d_C(1), d_a(2), d_st(3);
-    HIPCHK(d_w.alloc((size_t)n * 8));
-    HIPCHK(d_C.alloc((size_t)n * 8));
-    HIPCHK(d_a.alloc((size_t)ndraw * 4));
-    HIPCHK(d_st.alloc(4));
-    HIPCHK(hipMemcpyAsync(d_w.p, w, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    // the chunks of the grid-wide branch (a whole cloud's weights): contiguous, a multiple of the workgroup
+    constexpr int TH = 256;
+    int nb = (int)((n + 4 * TH - 1) / (4 * TH));
+    nb = nb > 2048 ? 2048 : nb;
+    const int64_t chunk = ((n + nb - 1) / nb + TH - 1) / TH * TH;
+    nb = (int)((n + chunk - 1) / chunk);
+    DeviceCall c;
+    if (const int rc = c.begin("smc_resample", device)) return rc;
+    const size_t o_w = c.take((size_t)n * 8), o_C = c.take((size_t)n * 8), o_a = c.take((size_t)ndraw * 4), o_st = c.take(4);
+    const size_t o_bs = c.take(((size_t)nb + 1) * 8);   // (the chunk sums and the maximum: the grid-wide branch only)
+    if (const int rc = c.use_scratch()) return rc;
+    const hipStream_t st = c.stream;
+    double* d_w = c.at<double>(o_w);
+    uint64_t *d_C = c.at<uint64_t>(o_C), *d_bs = c.at<uint64_t>(o_bs);
+    int* d_st = c.at<int>(o_st);
+    HIPCHK(c.upload(o_w, w, (size_t)n * 8));
     if (n <= 65536) {
-        hipLaunchKernelGGL((k_resample_cdf<1024>), dim3(1), dim3(1024), 0, st, d_w.as<double>(), n, fix_bits_for(n), d_C.as<uint64_t>(), d_st.as<int>());
-    } else {   // a whole cloud's weights: the inclusive sums grid-wide (the same integers)
-        constexpr int TH = 256;
-        int nb = (int)((n + 4 * TH - 1) / (4 * TH));
-        nb = nb > 2048 ? 2048 : nb;
-        const int64_t chunk = ((n + nb - 1) / nb + TH - 1) / TH * TH;   // contiguous, a multiple of the workgroup
-        nb = (int)((n + chunk - 1) / chunk);
-        DevBuf d_bs(4);
-        HIPCHK(d_bs.alloc(((size_t)nb + 1) * 8));
-        unsigned long long* mbits = d_bs.as<unsigned long long>() + nb;
+        hipLaunchKernelGGL((k_resample_cdf<1024>), dim3(1), dim3(1024), 0, st, d_w, n, fix_bits_for(n), d_C, d_st);
+    } else {   // the inclusive sums grid-wide (the same integers)
+        unsigned long long* mbits = c.at<unsigned long long>(o_bs) + nb;
         HIPCHK(hipMemsetAsync(mbits, 0, 8, st));
-        hipLaunchKernelGGL((k_rs_max<TH>), dim3((unsigned)nb), dim3(TH), 0, st, d_w.as<double>(), n, mbits);
-        hipLaunchKernelGGL((k_rs_chunk_sums<TH>), dim3((unsigned)nb), dim3(TH), 0, st, d_w.as<double>(), n, fix_bits_for(n), mbits, chunk, d_bs.as<uint64_t>());
-        hipLaunchKernelGGL((k_rs_scan_chunks<1024>), dim3(1), dim3(1024), 0, st, mbits, nb, d_bs.as<uint64_t>(), d_st.as<int>());
-        hipLaunchKernelGGL((k_rs_write<TH>), dim3((unsigned)nb), dim3(TH), 0, st, d_w.as<double>(), n, fix_bits_for(n), mbits, chunk, d_bs.as<uint64_t>(), d_C.as<uint64_t>());
+        hipLaunchKernelGGL((k_rs_max<TH>), dim3((unsigned)nb), dim3(TH), 0, st, d_w, n, mbits);
+        hipLaunchKernelGGL((k_rs_chunk_sums<TH>), dim3((unsigned)nb), dim3(TH), 0, st, d_w, n, fix_bits_for(n), mbits, chunk, d_bs);
+        hipLaunchKernelGGL((k_rs_scan_chunks<1024>), dim3(1), dim3(1024), 0, st, mbits, nb, d_bs, d_st);
+        hipLaunchKernelGGL((k_rs_write<TH>), dim3((unsigned)nb), dim3(TH), 0, st, d_w, n, fix_bits_for(n), mbits, chunk, d_bs, d_C);
     }
     HIPCHK(hipGetLastError());
     int status = 0;
-    HIPCHK(hipMemcpyAsync(&status, d_st.p, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(c.download(&status, o_st, 4));
+    HIPCHK(c.finish());
     if (status != 0) return fail(SMC_EINVAL, "smc_resample: weights must be finite with a positive maximum");
-    hipLaunchKernelGGL(k_resample_draw, dim3((unsigned)((ndraw + 255) / 256)), dim3(256), 0, st, d_C.as<uint64_t>(), n, ndraw, seed,
-                       stream, t, d_a.as<int32_t>());
+    hipLaunchKernelGGL(k_resample_draw, dim3((unsigned)((ndraw + 255) / 256)), dim3(256), 0, st, d_C, n, ndraw, seed, stream, t,
+                       c.at<int32_t>(o_a));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(a, d_a.p, (size_t)ndraw * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(c.download(a, o_a, (size_t)ndraw * 4));
+    HIPCHK(c.finish());
     return SMC_OK;
 }
 
@@ -150,23 +139,22 @@ extern "C" int smc_kalman_log_likelihood_flags(const double* raw, int64_t n_thet
                                                double* out, int device, uint32_t flags) {
     if (flags & ~SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_kalman_log_likelihood: flags is 0 or SMC_FLAG_NAN_MISSING");
     if (!raw || !y || !out || n_theta <= 0 || T <= 0) return fail(SMC_EINVAL, "smc_kalman_log_likelihood: bad argument");
-    hipStream_t st = nullptr;
-    HIPCHK(util_stream(device, &st));
-    DevBuf d_raw(0), d_y(1), d_out(2);
-    HIPCHK(d_raw.alloc((size_t)n_theta * 48));
-    HIPCHK(d_y.alloc((size_t)T * 8));
-    HIPCHK(d_out.alloc((size_t)n_theta * 24));
-    HIPCHK(hipMemcpyAsync(d_raw.p, raw, (size_t)n_theta * 48, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_y.p, y, (size_t)T * 8, hipMemcpyHostToDevice, st));
+    DeviceCall c;
+    if (const int rc = c.begin("smc_kalman_log_likelihood", device)) return rc;
+    const size_t o_raw = c.take((size_t)n_theta * 48), o_y = c.take((size_t)T * 8), o_out = c.take((size_t)n_theta * 24);
+    if (const int rc = c.use_scratch()) return rc;
+    HIPCHK(c.upload(o_raw, raw, (size_t)n_theta * 48));
+    HIPCHK(c.upload(o_y, y, (size_t)T * 8));
+    const dim3 grid((unsigned)((n_theta + KALMAN_THREADS - 1) / KALMAN_THREADS));
     if (kalman_has_gap(flags, y, T))   // the MISS twin only for a flagged call whose series holds a NaN
-        hipLaunchKernelGGL((k_kalman_loglik<Lg1Row, true>), dim3((unsigned)((n_theta + KALMAN_THREADS - 1) / KALMAN_THREADS)), dim3(KALMAN_THREADS), 0, st,
-                           d_raw.as<double>(), n_theta, d_y.as<double>(), T, predict_first, d_out.as<double>());
+        hipLaunchKernelGGL((k_kalman_loglik<Lg1Row, true>), grid, dim3(KALMAN_THREADS), 0, c.stream, c.at<double>(o_raw), n_theta, c.at<double>(o_y), T,
+                           predict_first, c.at<double>(o_out));
     else
-        hipLaunchKernelGGL((k_kalman_loglik<Lg1Row, false>), dim3((unsigned)((n_theta + KALMAN_THREADS - 1) / KALMAN_THREADS)), dim3(KALMAN_THREADS), 0, st,
-                           d_raw.as<double>(), n_theta, d_y.as<double>(), T, predict_first, d_out.as<double>());
+        hipLaunchKernelGGL((k_kalman_loglik<Lg1Row, false>), grid, dim3(KALMAN_THREADS), 0, c.stream, c.at<double>(o_raw), n_theta, c.at<double>(o_y), T,
+                           predict_first, c.at<double>(o_out));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d_out.p, (size_t)n_theta * 24, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(c.download(out, o_out, (size_t)n_theta * 24));
+    HIPCHK(c.finish());
     return SMC_OK;
 }
 extern "C" int smc_kalman_log_likelihood(const double* raw, int64_t n_theta, const double* y, int64_t T, int predict_first,
@@ -180,28 +168,27 @@ extern "C" int smc_kalman_predictive_flags(const double* raw, int64_t n_theta, c
                                            double* yv, int device, uint32_t flags) {
     if (flags & ~SMC_FLAG_NAN_MISSING) return fail(SMC_EINVAL, "smc_kalman_predictive: flags is 0 or SMC_FLAG_NAN_MISSING");
     if (!raw || !y || n_theta <= 0 || T <= 0) return fail(SMC_EINVAL, "smc_kalman_predictive: bad argument");
-    hipStream_t st = nullptr;
-    HIPCHK(util_stream(device, &st));
-    const size_t plane = (size_t)T * (size_t)n_theta;
-    DevBuf d_raw(0), d_y(1), d_out(2);
-    HIPCHK(d_raw.alloc((size_t)n_theta * 48));
-    HIPCHK(d_y.alloc((size_t)T * 8));
-    HIPCHK(d_out.alloc(3 * plane * 8));
-    HIPCHK(hipMemcpyAsync(d_raw.p, raw, (size_t)n_theta * 48, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_y.p, y, (size_t)T * 8, hipMemcpyHostToDevice, st));
-    double *o_pit = pit ? d_out.as<double>() : nullptr, *o_ym = ym ? d_out.as<double>() + plane : nullptr, *o_yv = yv ? d_out.as<double>() + 2 * plane : nullptr;
+    DeviceCall c;
+    if (const int rc = c.begin("smc_kalman_predictive", device)) return rc;
+    const size_t plane = (size_t)T * (size_t)n_theta * 8;
+    const size_t o_raw = c.take((size_t)n_theta * 48), o_y = c.take((size_t)T * 8);
+    const size_t o_pit = c.take(plane), o_ym = c.take(plane), o_yv = c.take(plane);   // (the planes stay in the thread's scratch)
+    if (const int rc = c.use_scratch()) return rc;
+    HIPCHK(c.upload(o_raw, raw, (size_t)n_theta * 48));
+    HIPCHK(c.upload(o_y, y, (size_t)T * 8));
+    double *d_pit = pit ? c.at<double>(o_pit) : nullptr, *d_ym = ym ? c.at<double>(o_ym) : nullptr, *d_yv = yv ? c.at<double>(o_yv) : nullptr;
     const dim3 grid((unsigned)((n_theta + KALMAN_THREADS - 1) / KALMAN_THREADS));
     if (kalman_has_gap(flags, y, T))   // the MISS twin only for a flagged call whose series holds a NaN
-        hipLaunchKernelGGL((k_kalman_predictive<Lg1Row, true>), grid, dim3(KALMAN_THREADS), 0, st, d_raw.as<double>(), n_theta, d_y.as<double>(), T, predict_first,
-                           o_pit, o_ym, o_yv);
+        hipLaunchKernelGGL((k_kalman_predictive<Lg1Row, true>), grid, dim3(KALMAN_THREADS), 0, c.stream, c.at<double>(o_raw), n_theta, c.at<double>(o_y), T,
+                           predict_first, d_pit, d_ym, d_yv);
     else
-        hipLaunchKernelGGL((k_kalman_predictive<Lg1Row, false>), grid, dim3(KALMAN_THREADS), 0, st, d_raw.as<double>(), n_theta, d_y.as<double>(), T, predict_first,
-                           o_pit, o_ym, o_yv);
+        hipLaunchKernelGGL((k_kalman_predictive<Lg1Row, false>), grid, dim3(KALMAN_THREADS), 0, c.stream, c.at<double>(o_raw), n_theta, c.at<double>(o_y), T,
+                           predict_first, d_pit, d_ym, d_yv);
     HIPCHK(hipGetLastError());
-    if (pit) HIPCHK(hipMemcpyAsync(pit, o_pit, plane * 8, hipMemcpyDeviceToHost, st));
-    if (ym) HIPCHK(hipMemcpyAsync(ym, o_ym, plane * 8, hipMemcpyDeviceToHost, st));
-    if (yv) HIPCHK(hipMemcpyAsync(yv, o_yv, plane * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (pit) HIPCHK(c.download(pit, o_pit, plane));
+    if (ym) HIPCHK(c.download(ym, o_ym, plane));
+    if (yv) HIPCHK(c.download(yv, o_yv, plane));
+    HIPCHK(c.finish());
     return SMC_OK;
 }
 // ... and their host twin for one row: pit, ym, yv [T] (any NULL)
@@ -225,16 +212,15 @@ extern "C" int smc_host_kalman_predictive(const double* row, const double* y, in
 extern "C" double smc_host_normcdf(double z) { return sp_normcdf(z); }
 extern "C" int smc_device_normcdf(const double* z, int64_t n, double* out, int device) {
     if (!z || !out || n <= 0) return fail(SMC_EINVAL, "smc_device_normcdf: bad argument");
-    hipStream_t st = nullptr;
-    HIPCHK(util_stream(device, &st));
-    DevBuf dz(0), dout(1);
-    HIPCHK(dz.alloc((size_t)n * 8));
-    HIPCHK(dout.alloc((size_t)n * 8));
-    HIPCHK(hipMemcpyAsync(dz.p, z, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_normcdf<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dz.as<double>(), n, dout.as<double>());
+    DeviceCall c;
+    if (const int rc = c.begin("smc_device_normcdf", device)) return rc;
+    const size_t o_z = c.take((size_t)n * 8), o_out = c.take((size_t)n * 8);
+    if (const int rc = c.use_scratch()) return rc;
+    HIPCHK(c.upload(o_z, z, (size_t)n * 8));
+    hipLaunchKernelGGL(k_normcdf<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.stream, c.at<double>(o_z), n, c.at<double>(o_out));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(c.download(out, o_out, (size_t)n * 8));
+    HIPCHK(c.finish());
     return SMC_OK;
 }
 // the row of ONE cloud x [d][n] (the order of smc_get_state) for the observation y: out = (pit, obs_mean, obs_var), the statement of
@@ -244,9 +230,7 @@ extern "C" int smc_host_predictive(int model_id, const double* raw, const double
     if (!has_density(model_id))
         return fail(SMC_EINVAL, "smc_host_predictive: the families whose rows are a sample of the state: LG1D, SV1D, UCSV3D");
     Params P;
-    const int nraw = model_nraw_rt(model_id);
-    for (int k = 0; k < NPARAM; ++k) P.raw[k] = k < nraw ? raw[k] : 0.0;
-    derive_params(model_id, P.raw, P.der);
+    params_from_raw(model_id, raw, P);
     std::vector<double> cdf((size_t)n), ymv((size_t)n), s2((size_t)n), part((size_t)((n + SMOOTH_CH - 1) / SMOOTH_CH));
     (void)by_density_model(model_id, [&](auto Mt) {
         constexpr int M = decltype(Mt)::value;
@@ -310,11 +294,9 @@ static void simulate_t(const Params& p, int64_t T, uint64_t seed, double* x, dou
 
 extern "C" int smc_simulate_dim(int model_id) { return model_id == MODEL_UCSV_RB ? model_dim_rt(MODEL_UCSV3D) : model_dim_rt(model_id); }
 extern "C" int smc_simulate(int model_id, const double* raw, int64_t T, uint64_t seed, double* x, double* y) {
-    const int nraw = model_nraw_rt(model_id);
-    if (nraw < 0 || !raw || !y || T <= 0) return fail(SMC_EINVAL, "smc_simulate: bad argument");
+    if (model_nraw_rt(model_id) < 0 || !raw || !y || T <= 0) return fail(SMC_EINVAL, "smc_simulate: bad argument");
     Params p;
-    for (int k = 0; k < NPARAM; ++k) p.raw[k] = k < nraw ? raw[k] : 0.0;
-    derive_params(model_id, p.raw, p.der);
+    params_from_raw(model_id, raw, p);
     (void)by_model(model_id, [&](auto M) {
         // the data-generating model of the marginal family is UCSV: x is [3][T] (smc_simulate_dim)
         constexpr int SIM = decltype(M)::value == MODEL_UCSV_RB ? MODEL_UCSV3D : decltype(M)::value;
@@ -356,11 +338,10 @@ static void host_forecast_t(const Params& p, const double* x, int64_t n, int64_t
 }
 extern "C" int smc_host_forecast(int model_id, const double* raw, const double* x, int64_t n, int64_t H, uint64_t forecast_seed, uint32_t stream,
                                  double* xf, double* yf, double* ym, double* yv) {
-    const int nraw = model_nraw_rt(model_id);
-    if (nraw < 0 || !raw || !x || n < 1 || n > ((int64_t)1 << 31) || H < 1 || H > 0x7fffffff) return fail(SMC_EINVAL, "smc_host_forecast: bad argument");
+    if (model_nraw_rt(model_id) < 0 || !raw || !x || n < 1 || n > ((int64_t)1 << 31) || H < 1 || H > 0x7fffffff)
+        return fail(SMC_EINVAL, "smc_host_forecast: bad argument");
     Params p;
-    for (int k = 0; k < NPARAM; ++k) p.raw[k] = k < nraw ? raw[k] : 0.0;
-    derive_params(model_id, p.raw, p.der);
+    params_from_raw(model_id, raw, p);
     (void)by_model(model_id, [&](auto M) {
         host_forecast_t<decltype(M)::value>(p, x, n, H, forecast_seed, stream, xf, yf, ym, yv);
         return hipSuccess;
@@ -422,14 +403,14 @@ extern "C" int smc_sys_targets(uint64_t Dtot, uint32_t n, uint64_t u, uint64_t j
         for (int k = 0; k < nk; ++k) out[k] = sys_target(sb, (uint32_t)k);
         return SMC_OK;
     }
-    hipStream_t st = nullptr;
-    HIPCHK(util_stream(device, &st));
-    DevBuf d(0);
-    HIPCHK(d.alloc((size_t)nk * 8));
-    hipLaunchKernelGGL(k_sys_targets, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, Dtot, n, u, j0, nk, d.as<uint64_t>());
+    DeviceCall c;
+    if (const int rc = c.begin("smc_sys_targets", device)) return rc;
+    const size_t o_out = c.take((size_t)nk * 8);
+    if (const int rc = c.use_scratch()) return rc;
+    hipLaunchKernelGGL(k_sys_targets, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, c.stream, Dtot, n, u, j0, nk, c.at<uint64_t>(o_out));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d.p, (size_t)nk * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(c.download(out, o_out, (size_t)nk * 8));
+    HIPCHK(c.finish());
     return SMC_OK;
 }
 
@@ -442,16 +423,90 @@ extern "C" int smc_host_optimal_proposal(int model_id, const double* raw, double
 }
 // the parameter and proposal rows of one guided particle step from (raw, kind, par); false: refused
 static bool guided_params(int model_id, const double* raw, int kind, const double* par, Params& P, PropRow& R) {
-    const int nraw = model_nraw_rt(model_id);
-    if (nraw < 0 || !raw || kind == PROP_NONE || !proposal_supported(model_id, kind)) return false;
+    if (model_nraw_rt(model_id) < 0 || !raw || kind == PROP_NONE || !proposal_supported(model_id, kind)) return false;
     if ((kind == PROP_AFFINE) != (par != nullptr)) return false;
     if (kind == PROP_AFFINE && !affine_row_ok(par)) return false;
-    for (int k = 0; k < NPARAM; ++k) { P.raw[k] = k < nraw ? raw[k] : 0.0; R.p[k] = 0.0; }
-    derive_params(model_id, P.raw, P.der);
+    params_from_raw(model_id, raw, P);
+    R = PropRow{};
     if (kind == PROP_AFFINE)
         for (int k = 0; k < PROP_NPAR; ++k) R.p[k] = par[k];
     derive_proposal(model_id, kind, P.raw, P.der, R.p);
     return true;
+}
+// ... and of any particle step: kind == PROP_NONE is the bootstrap (or marginal) step, whose proposal row is zeros
+static bool filter_step_params(int model_id, const double* raw, int kind, const double* par, Params& P, PropRow& R) {
+    if (kind != PROP_NONE) return guided_params(model_id, raw, kind, par, P, R);
+    if (model_nraw_rt(model_id) < 0 || !raw || par) return false;
+    params_from_raw(model_id, raw, P);
+    R = PropRow{};
+    return true;
+}
+
+// The whole step of a filter (include/smc_hip.h "missing observations"): every family and proposal, the first step and the missing
+// step included - what k_init, k_step and k_resident do to one particle.  The ONE gather / step / scatter loop of the probes below:
+// for n particles on the host (host_steps) / on a device (k_filter_steps, device_steps); xp [d][n] (not read at the first step),
+// z [nz][n] -> x [d][n], logw [n]
+template <int MODEL>
+SMC_HD double filter_step_one(const Params& P, const PropRow& R, bool guided, bool first, bool miss, const double* xp, const double* z, double y,
+                              double* x) {
+    if (miss) {
+        model_missing_step<MODEL>(P, first, xp, z, x);
+        return 0.0;
+    }
+    if constexpr (model_marginal<MODEL>::value) {
+        return model_marginal_step<MODEL>(P, first, xp, z, y, x);
+    } else {
+        if (first) model_initial<MODEL>(P, z, x);
+        else if (guided) return model_guided<MODEL>(P, R, xp, z, y, x);
+        else model_transition<MODEL>(P, xp, z, x);
+        return model_logobs<MODEL>(P, x, y);
+    }
+}
+static void host_steps(int model_id, const Params& P, const PropRow& R, bool guided, bool first, bool miss, const double* xp, const double* z, double y,
+                       int64_t n, double* x, double* logw) {
+    (void)by_model(model_id, [&](auto M) {
+        constexpr int MODEL = decltype(M)::value, D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
+        for (int64_t i = 0; i < n; ++i) {
+            double a[D] = {}, zz[NZ], xn[D];
+            for (int c = 0; c < D && !first; ++c) a[c] = xp[(size_t)c * n + i];
+            for (int c = 0; c < NZ; ++c) zz[c] = z[(size_t)c * n + i];
+            logw[i] = filter_step_one<MODEL>(P, R, guided, first, miss, a, zz, y, xn);
+            for (int c = 0; c < D; ++c) x[(size_t)c * n + i] = xn[c];
+        }
+        return hipSuccess;
+    });
+}
+template <int MODEL>
+__global__ void k_filter_steps(Params P, PropRow R, int guided, int first, int miss, const double* xp, const double* z, double y, int64_t n, double* x,
+                               double* logw) {
+    constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double a[D] = {}, zz[NZ], xn[D];
+    for (int c = 0; c < D; ++c) a[c] = first ? 0.0 : xp[(size_t)c * n + i];
+    for (int c = 0; c < NZ; ++c) zz[c] = z[(size_t)c * n + i];
+    logw[i] = filter_step_one<MODEL>(P, R, guided != 0, first != 0, miss != 0, a, zz, y, xn);
+    for (int c = 0; c < D; ++c) x[(size_t)c * n + i] = xn[c];
+}
+static int device_steps(const char* who, int model_id, const Params& P, const PropRow& R, bool guided, bool first, bool miss, const double* xp,
+                        const double* z, double y, int64_t n, double* x, double* logw, int device) {
+    const size_t b_x = (size_t)model_dim_rt(model_id) * n * 8, b_z = (size_t)(model_id == MODEL_UCSV_RB ? 2 : model_dim_rt(model_id)) * n * 8;
+    DeviceCall c;
+    if (const int rc = c.begin(who, device)) return rc;
+    const size_t o_xp = c.take(b_x), o_z = c.take(b_z), o_x = c.take(b_x), o_lw = c.take((size_t)n * 8);
+    if (const int rc = c.use_scratch()) return rc;
+    if (!first) HIPCHK(c.upload(o_xp, xp, b_x));
+    HIPCHK(c.upload(o_z, z, b_z));
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    HIPCHK(by_model(model_id, [&](auto M) {
+        hipLaunchKernelGGL(k_filter_steps<decltype(M)::value>, grid, block, 0, c.stream, P, R, guided ? 1 : 0, first ? 1 : 0, miss ? 1 : 0,
+                           c.at<double>(o_xp), c.at<double>(o_z), y, n, c.at<double>(o_x), c.at<double>(o_lw));
+        return hipGetLastError();
+    }));
+    HIPCHK(c.download(x, o_x, b_x));
+    HIPCHK(c.download(logw, o_lw, (size_t)n * 8));
+    HIPCHK(c.finish());
+    return SMC_OK;
 }
 extern "C" int smc_host_guided_step(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z,
                                     double y, double* x, double* logw) {
@@ -472,28 +527,8 @@ extern "C" int smc_host_guided_steps(int model_id, const double* raw, int kind, 
     Params P;
     PropRow R;
     if (!guided_params(model_id, raw, kind, par, P, R)) return fail(SMC_EINVAL, "smc_host_guided_steps: bad model, kind or row");
-    (void)by_guided_model(model_id, [&](auto M) {
-        constexpr int D = model_dim<decltype(M)::value>::value;
-        for (int64_t i = 0; i < n; ++i) {
-            double a[D], zz[D], xn[D];
-            for (int c = 0; c < D; ++c) { a[c] = xp[(size_t)c * n + i]; zz[c] = z[(size_t)c * n + i]; }
-            logw[i] = model_guided<decltype(M)::value>(P, R, a, zz, y, xn);
-            for (int c = 0; c < D; ++c) x[(size_t)c * n + i] = xn[c];
-        }
-        return hipSuccess;
-    });
+    host_steps(model_id, P, R, true, false, false, xp, z, y, n, x, logw);
     return SMC_OK;
-}
-
-template <int MODEL>
-__global__ void k_guided_step(Params P, PropRow R, const double* xp, const double* z, double y, int64_t n, double* x, double* logw) {
-    constexpr int D = model_dim<MODEL>::value;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double a[D], zz[D], xn[D];
-    for (int c = 0; c < D; ++c) { a[c] = xp[(size_t)c * n + i]; zz[c] = z[(size_t)c * n + i]; }
-    logw[i] = model_guided<MODEL>(P, R, a, zz, y, xn);
-    for (int c = 0; c < D; ++c) x[(size_t)c * n + i] = xn[c];
 }
 extern "C" int smc_device_guided_step(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z,
                                       double y, int64_t n, double* x, double* logw, int device) {
@@ -501,26 +536,7 @@ extern "C" int smc_device_guided_step(int model_id, const double* raw, int kind,
     Params P;
     PropRow R;
     if (!guided_params(model_id, raw, kind, par, P, R)) return fail(SMC_EINVAL, "smc_device_guided_step: bad model, kind or row");
-    const int d = model_dim_rt(model_id);
-    hipStream_t st = nullptr;
-    HIPCHK(util_stream(device, &st));
-    const size_t bytes = (size_t)d * n * 8;
-    DevBuf dxp(0), dz(1), dx(2), dlw(3);
-    HIPCHK(dxp.alloc(bytes));
-    HIPCHK(dz.alloc(bytes));
-    HIPCHK(dx.alloc(bytes));
-    HIPCHK(dlw.alloc((size_t)n * 8));
-    HIPCHK(hipMemcpyAsync(dxp.p, xp, bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dz.p, z, bytes, hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    HIPCHK(by_guided_model(model_id, [&](auto M) {
-        hipLaunchKernelGGL(k_guided_step<decltype(M)::value>, grid, block, 0, st, P, R, dxp.as<double>(), dz.as<double>(), y, n, dx.as<double>(), dlw.as<double>());
-        return hipGetLastError();
-    }));
-    HIPCHK(hipMemcpyAsync(x, dx.p, bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(logw, dlw.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return SMC_OK;
+    return device_steps("smc_device_guided_step", model_id, P, R, true, false, false, xp, z, y, n, x, logw, device);
 }
 
 // what the blocks of smc_host.h hold right now, process-wide (include/smc_hip.h)
@@ -534,8 +550,7 @@ extern "C" int smc_live_bytes(int64_t* device_bytes, int64_t* pinned_bytes) {
 extern "C" int smc_host_rb_step(const double* raw, const double* sp, const double* z, double y, int first, double* s, double* logw) {
     if (!raw || !sp || !z || !s || !logw) return fail(SMC_EINVAL, "smc_host_rb_step: NULL argument");
     Params P;
-    for (int k = 0; k < NPARAM; ++k) P.raw[k] = k < model_nraw_rt(MODEL_UCSV_RB) ? raw[k] : 0.0;
-    derive_params(MODEL_UCSV_RB, P.raw, P.der);
+    params_from_raw(MODEL_UCSV_RB, raw, P);
     double a[4] = {sp[0], sp[1], sp[2], sp[3]}, o[4];
     *logw = model_marginal_step<MODEL_UCSV_RB>(P, first != 0, a, z, y, o);
     for (int c = 0; c < 4; ++c) s[c] = o[c];
@@ -546,94 +561,26 @@ extern "C" int smc_host_rb_steps(const double* raw, const double* sp, const doub
                                  double* logw) {
     if (!raw || !sp || !z || !s || !logw || n <= 0) return fail(SMC_EINVAL, "smc_host_rb_steps: bad argument");
     Params P;
-    for (int k = 0; k < NPARAM; ++k) P.raw[k] = k < model_nraw_rt(MODEL_UCSV_RB) ? raw[k] : 0.0;
-    derive_params(MODEL_UCSV_RB, P.raw, P.der);
-    for (int64_t i = 0; i < n; ++i) {
-        double a[4], zz[2], o[4];
-        for (int c = 0; c < 4; ++c) a[c] = sp[(size_t)c * n + i];
-        for (int c = 0; c < 2; ++c) zz[c] = z[(size_t)c * n + i];
-        logw[i] = model_marginal_step<MODEL_UCSV_RB>(P, first != 0, a, zz, y, o);
-        for (int c = 0; c < 4; ++c) s[(size_t)c * n + i] = o[c];
-    }
+    params_from_raw(MODEL_UCSV_RB, raw, P);
+    host_steps(MODEL_UCSV_RB, P, PropRow{}, false, first != 0, false, sp, z, y, n, s, logw);
     return SMC_OK;
-}
-__global__ void k_rb_step(Params P, int first, const double* sp, const double* z, double y, int64_t n, double* s, double* logw) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double a[4], zz[2], o[4];
-    for (int c = 0; c < 4; ++c) a[c] = sp[(size_t)c * n + i];
-    for (int c = 0; c < 2; ++c) zz[c] = z[(size_t)c * n + i];
-    logw[i] = model_marginal_step<MODEL_UCSV_RB>(P, first != 0, a, zz, y, o);
-    for (int c = 0; c < 4; ++c) s[(size_t)c * n + i] = o[c];
 }
 extern "C" int smc_device_rb_step(const double* raw, const double* sp, const double* z, double y, int first, int64_t n, double* s, double* logw,
                                   int device) {
     if (!raw || !sp || !z || !s || !logw || n <= 0) return fail(SMC_EINVAL, "smc_device_rb_step: bad argument");
     Params P;
-    for (int k = 0; k < NPARAM; ++k) P.raw[k] = k < model_nraw_rt(MODEL_UCSV_RB) ? raw[k] : 0.0;
-    derive_params(MODEL_UCSV_RB, P.raw, P.der);
-    hipStream_t st = nullptr;
-    HIPCHK(util_stream(device, &st));
-    DevBuf dsp(0), dz(1), ds(2), dlw(3);
-    HIPCHK(dsp.alloc((size_t)4 * n * 8));
-    HIPCHK(dz.alloc((size_t)2 * n * 8));
-    HIPCHK(ds.alloc((size_t)4 * n * 8));
-    HIPCHK(dlw.alloc((size_t)n * 8));
-    HIPCHK(hipMemcpyAsync(dsp.p, sp, (size_t)4 * n * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dz.p, z, (size_t)2 * n * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_rb_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, first, dsp.as<double>(), dz.as<double>(), y, n,
-                       ds.as<double>(), dlw.as<double>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s, ds.p, (size_t)4 * n * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(logw, dlw.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return SMC_OK;
+    params_from_raw(MODEL_UCSV_RB, raw, P);
+    return device_steps("smc_device_rb_step", MODEL_UCSV_RB, P, PropRow{}, false, first != 0, false, sp, z, y, n, s, logw, device);
 }
 
-// the whole step of a filter (include/smc_hip.h "missing observations"): every family and proposal, the first step and the missing
-// step included - what k_init, k_step and k_resident do to one particle, for n particles on the host / on a device
-template <int MODEL>
-SMC_HD double filter_step_one(const Params& P, const PropRow& R, bool guided, bool first, bool miss, const double* xp, const double* z, double y,
-                              double* x) {
-    if (miss) {
-        model_missing_step<MODEL>(P, first, xp, z, x);
-        return 0.0;
-    }
-    if constexpr (model_marginal<MODEL>::value) {
-        return model_marginal_step<MODEL>(P, first, xp, z, y, x);
-    } else {
-        if (first) model_initial<MODEL>(P, z, x);
-        else if (guided) return model_guided<MODEL>(P, R, xp, z, y, x);
-        else model_transition<MODEL>(P, xp, z, x);
-        return model_logobs<MODEL>(P, x, y);
-    }
-}
-static bool filter_step_params(int model_id, const double* raw, int kind, const double* par, Params& P, PropRow& R) {
-    if (kind != PROP_NONE) return guided_params(model_id, raw, kind, par, P, R);
-    const int nraw = model_nraw_rt(model_id);
-    if (nraw < 0 || !raw || par) return false;
-    for (int k = 0; k < NPARAM; ++k) { P.raw[k] = k < nraw ? raw[k] : 0.0; R.p[k] = 0.0; }
-    derive_params(model_id, P.raw, P.der);
-    return true;
-}
+// the whole step for n particles, every family and proposal (filter_step_one above)
 extern "C" int smc_host_filter_steps(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z, double y,
                                      int first, int nan_missing, int64_t n, double* x, double* logw) {
     if (!z || !x || !logw || n <= 0 || (!first && !xp)) return fail(SMC_EINVAL, "smc_host_filter_steps: bad argument");
     Params P;
     PropRow R;
     if (!filter_step_params(model_id, raw, kind, par, P, R)) return fail(SMC_EINVAL, "smc_host_filter_steps: bad model, kind or row");
-    const bool miss = nan_missing && y != y, guided = kind != PROP_NONE;
-    (void)by_model(model_id, [&](auto M) {
-        constexpr int MODEL = decltype(M)::value, D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
-        for (int64_t i = 0; i < n; ++i) {
-            double a[D] = {}, zz[NZ], xn[D];
-            for (int c = 0; c < D && !first; ++c) a[c] = xp[(size_t)c * n + i];
-            for (int c = 0; c < NZ; ++c) zz[c] = z[(size_t)c * n + i];
-            logw[i] = filter_step_one<MODEL>(P, R, guided, first != 0, miss, a, zz, y, xn);
-            for (int c = 0; c < D; ++c) x[(size_t)c * n + i] = xn[c];
-        }
-        return hipSuccess;
-    });
+    host_steps(model_id, P, R, kind != PROP_NONE, first != 0, nan_missing && y != y, xp, z, y, n, x, logw);
     return SMC_OK;
 }
 // the conditional particle filter (include/smc_hip.h): the retained slot and the log-weight of the reference row on the host
@@ -654,62 +601,29 @@ extern "C" int smc_host_logobs(int model_id, const double* raw, const double* x,
     });
     return SMC_OK;
 }
-template <int MODEL>
-__global__ void k_filter_steps(Params P, PropRow R, int guided, int first, int miss, const double* xp, const double* z, double y, int64_t n, double* x,
-                               double* logw) {
-    constexpr int D = model_dim<MODEL>::value, NZ = model_nz<MODEL>::value;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double a[D] = {}, zz[NZ], xn[D];
-    for (int c = 0; c < D; ++c) a[c] = first ? 0.0 : xp[(size_t)c * n + i];
-    for (int c = 0; c < NZ; ++c) zz[c] = z[(size_t)c * n + i];
-    logw[i] = filter_step_one<MODEL>(P, R, guided != 0, first != 0, miss != 0, a, zz, y, xn);
-    for (int c = 0; c < D; ++c) x[(size_t)c * n + i] = xn[c];
-}
 extern "C" int smc_device_filter_steps(int model_id, const double* raw, int kind, const double* par, const double* xp, const double* z, double y,
                                        int first, int nan_missing, int64_t n, double* x, double* logw, int device) {
     if (!z || !x || !logw || n <= 0 || (!first && !xp)) return fail(SMC_EINVAL, "smc_device_filter_steps: bad argument");
     Params P;
     PropRow R;
     if (!filter_step_params(model_id, raw, kind, par, P, R)) return fail(SMC_EINVAL, "smc_device_filter_steps: bad model, kind or row");
-    const int miss = (nan_missing && y != y) ? 1 : 0, guided = kind != PROP_NONE ? 1 : 0;
-    const size_t d = (size_t)model_dim_rt(model_id), nz = model_id == MODEL_UCSV_RB ? 2 : d;
-    hipStream_t st = nullptr;
-    HIPCHK(util_stream(device, &st));
-    DevBuf dxp(0), dz(1), dx(2), dlw(3);
-    HIPCHK(dxp.alloc(d * n * 8));
-    HIPCHK(dz.alloc(nz * n * 8));
-    HIPCHK(dx.alloc(d * n * 8));
-    HIPCHK(dlw.alloc((size_t)n * 8));
-    if (!first) HIPCHK(hipMemcpyAsync(dxp.p, xp, d * n * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dz.p, z, nz * n * 8, hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    HIPCHK(by_model(model_id, [&](auto M) {
-        hipLaunchKernelGGL(k_filter_steps<decltype(M)::value>, grid, block, 0, st, P, R, guided, first, miss, dxp.as<double>(), dz.as<double>(), y, n,
-                           dx.as<double>(), dlw.as<double>());
-        return hipGetLastError();
-    }));
-    HIPCHK(hipMemcpyAsync(x, dx.p, d * n * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(logw, dlw.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return SMC_OK;
+    return device_steps("smc_device_filter_steps", model_id, P, R, kind != PROP_NONE, first != 0, nan_missing && y != y, xp, z, y, n, x, logw, device);
 }
 
 extern "C" int smc_device_math(int which, const double* a, const double* b, int64_t n, double* out, int device) {
     if (!a || !out || n <= 0 || which < 0 || which > 5) return fail(SMC_EINVAL, "smc_device_math: bad argument");
     if (which >= 3 && !b) return fail(SMC_EINVAL, "smc_device_math: b required");
-    hipStream_t st = nullptr;
-    HIPCHK(util_stream(device, &st));
-    DevBuf da(0), db(1), dout(2);
-    HIPCHK(da.alloc((size_t)n * 8));
-    HIPCHK(db.alloc((size_t)n * 8));
-    HIPCHK(dout.alloc((size_t)n * 8));
-    HIPCHK(hipMemcpyAsync(da.p, a, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    if (b) HIPCHK(hipMemcpyAsync(db.p, b, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_device_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, which, da.as<double>(), db.as<double>(), n, dout.as<double>());
+    DeviceCall c;
+    if (const int rc = c.begin("smc_device_math", device)) return rc;
+    const size_t o_a = c.take((size_t)n * 8), o_b = c.take((size_t)n * 8), o_out = c.take((size_t)n * 8);
+    if (const int rc = c.use_scratch()) return rc;
+    HIPCHK(c.upload(o_a, a, (size_t)n * 8));
+    if (b) HIPCHK(c.upload(o_b, b, (size_t)n * 8));
+    hipLaunchKernelGGL(k_device_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.stream, which, c.at<double>(o_a), c.at<double>(o_b), n,
+                       c.at<double>(o_out));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(c.download(out, o_out, (size_t)n * 8));
+    HIPCHK(c.finish());
     return SMC_OK;
 }
 

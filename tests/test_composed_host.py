@@ -121,6 +121,47 @@ def test_batched_rb_twin_is_the_one_particle_twin(L, first):
         assert same(s[:, i], hs) and same([lw[i]], [hl]), (i, s[:, i], hs, lw[i], hl)
 
 
+def with_nonfinite(a):
+    """the first 257 columns of an edge input with particles 0, 1, 2 at +inf, -inf and NaN in the first row"""
+    a = a[:, :257].copy()
+    a[0, :3] = [np.inf, -np.inf, np.nan]
+    return a
+
+
+def step_sizes(n_all):
+    """the column sets of the step-probe comparisons: n = 1 (each non-finite particle and a finite one alone), 63, 257"""
+    return [slice(i, i + 1) for i in range(4)] + [slice(0, 63), slice(0, n_all)]
+
+
+@pytest.mark.parametrize("model,kind", [(1, CR.AFFINE), (1, CR.OPTIMAL), (3, CR.OPTIMAL)])
+def test_guided_steps_are_the_filter_steps(L, model, kind):
+    """smc_host_guided_steps == smc_host_filter_steps(kind, first=0, nan_missing=0) bit for bit, non-finite states and normals
+    included: one gather / step / scatter loop serves both exports"""
+    raw, par, xp, z, y = step_edge_inputs.guided(model, kind)
+    for xq, zq in ((with_nonfinite(xp), z[:, :257]), (xp[:, :257], with_nonfinite(z))):
+        for s in step_sizes(257):
+            gx, gl = L.host_guided_steps(model, raw, kind, par, xq[:, s], zq[:, s], y)
+            fx, fl = L.host_filter_steps(model, raw, kind, par, xq[:, s], zq[:, s], y, first=False, missing=False)
+            assert same(gx, fx) and same(gl, fl), (s, gx, fx, gl, fl)
+            if s.stop - s.start == 1:   # ... and the one-particle twin, whose loop is its own
+                hx, hl = L.host_guided_step(model, raw, kind, par, xq[:, s.start], zq[:, s.start], y)
+                assert same(gx[:, 0], hx) and same(gl, [hl]), (s, gx, hx, gl, hl)
+
+
+@pytest.mark.parametrize("first", [False, True])
+def test_rb_steps_are_the_filter_steps(L, first):
+    """smc_host_rb_steps == smc_host_filter_steps(MODEL_UCSV_RB, PROP_NONE, first) bit for bit, non-finite states and normals included"""
+    raw, sp, z, y = step_edge_inputs.rb(first)
+    for sq, zq in ((with_nonfinite(sp), z[:, :257]), (sp[:, :257], with_nonfinite(z))):
+        for s in step_sizes(257):
+            rs, rl = L.host_rb_steps(raw, sq[:, s], zq[:, s], y, first)
+            fs, fl = L.host_filter_steps(L.MODEL_UCSV_RB, raw, L.PROP_NONE, None, sq[:, s], zq[:, s], y, first=first, missing=False)
+            assert same(rs, fs) and same(rl, fl), (s, rs, fs, rl, fl)
+            if s.stop - s.start == 1:
+                hs, hl = L.host_rb_step(raw, sq[:, s.start], zq[:, s.start], y, first)
+                assert same(rs[:, 0], hs) and same(rl, [hl]), (s, rs, hs, rl, hl)
+
+
 @pytest.mark.parametrize("n,seg,systematic", [(1000, 0, False), (3000, 256, False), (5000, 1024, True)])
 def test_composed_identity_row_is_the_bootstrap_filter(L, ob, n, seg, systematic):
     """the composed LG1D filter with the AFFINE row (0, A, 0, Q) against ob.Filter's bootstrap run, two filters with their own rows
