@@ -222,7 +222,27 @@ int smc_step(smc_handle h, double y_t, double* logmu /*[n_theta]*/, double* ess 
  * returns (logmu, ess) of every step, [k][n_theta] each, but does NOT advance the filters - the caller looks at the
  * k outer ESS values and then keeps the first j steps with smc_step_commit(h, j) (j < k re-runs those j steps: the
  * random numbers are counter based, the bits are the same; j = 0 keeps nothing).  Bit-identical to k (or j) smc_step
- * calls.  Needs single-segment filters that fit the LDS-resident kernel (n_x <= 8192); k <= 64. */
+ * calls.  Needs single-segment filters that fit the LDS-resident kernel (n_x <= 8192); k <= 64.
+ * THE PENDING WINDOW.  Between a successful smc_step_window and the next smc_step_commit the window is pending: the (logmu, ess)
+ * it reported describe steps from the filters as they stand, under the rows, seed, stream ids and proposal in force.  ONE rule:
+ * a call that changes rows, seed, stream ids, proposal or the filters DROPS the window; a call that only reads, or that fails,
+ * KEEPS it.  smc_step_commit without a pending window is SMC_ESTATE ("no window pending"), with j outside [0, k] SMC_EINVAL (the
+ * window stays pending).  A second smc_step_window replaces the pending one.
+ *   drop  smc_set_params, smc_set_streams, smc_reseed, smc_set_proposal, smc_init, smc_step, smc_log_likelihood, smc_permute,
+ *         smc_copy_from (the destination; the source only reads), smc_unpack_slots, smc_comm_exchange_slots (it unpacks),
+ *         smc_pmmh_rejuvenate (the proposal handle and main), smc_step_commit itself, smc_time_step_kernel (it runs a series).
+ *   keep  smc_get_state, smc_get_weights_raw, smc_get_logZ, smc_get_moments, smc_get_quantiles, smc_get_predictive, smc_forecast,
+ *         smc_forecast_cloud, smc_pack_slots, smc_slot_bytes, smc_get_geometry, smc_get_launch_geometry, smc_get_flags,
+ *         smc_step_by_value, smc_last_elapsed_ms, smc_event_overhead_ms, smc_synchronize, smc_set_skip, smc_set_summaries,
+ *         smc_get_summaries, smc_set_summary_mode, smc_pmmh_configure (they change what later calls compute, not the filters).
+ *   n/a   the record and the smoothers (smc_history_*, smc_smooth*, smc_sample_paths, smc_rb_sample_paths, smc_predictive) and
+ *         the conditional calls (smc_set_reference, smc_reference_from_paths, smc_get_reference, smc_ancestor_sweep): an armed or
+ *         conditional handle refuses smc_step_window, so none of them meets a window opened on such a handle.  A window opened
+ *         BEFORE smc_history_begin stays pending on the armed handle (smc_history_begin keeps it); smc_step_commit is refused
+ *         (SMC_ESTATE) until smc_history_end, after which the window can still be committed, unless a recorded smc_init /
+ *         smc_step has dropped it meanwhile.  smc_destroy ends a window with the handle.
+ * REFUSED CALLS.  A call on a handle that returns SMC_EINVAL or SMC_ESTATE leaves the handle as it was: filters, logZ, time
+ * index, a pending window and the host's by-value copies of row 0 (smc_step_by_value) included. */
 int smc_step_window(smc_handle h, const double* y /*[k]*/, int k, double* logmu /*[k][n_theta]*/, double* ess /*[k][n_theta] or NULL*/);
 int smc_step_commit(smc_handle h, int j);
 /* log_likelihood(N, y, model) -> (x, w, logZ)               src/particles.jl:132-147
@@ -278,7 +298,11 @@ int smc_get_logZ(smc_handle h, double* logZ /*[n_theta]*/, double* ess /*[n_thet
 int smc_permute(smc_handle h, const int32_t* a /*[n_theta]*/);
 /* PMMH accept step of rejuvenate! (src/smc_samplers.jl:129-136): for every m with mask[m] != 0 the
  * filter state of slot m (x cloud, weights, logZ) is overwritten by slot m of `src` (the proposal
- * filters, same geometry).  Value copy on the device; streams and parameters are not copied. */
+ * filters, same geometry).  Value copy on the device; streams and parameters are not copied.
+ * A handle has ONE time index (the step number the next smc_step draws its random numbers under): after the call dst's is src's,
+ * for every filter of dst and whatever the mask - callers copy between handles that have seen the same observations.  A packed
+ * slot (smc_pack_slots) carries no time index: smc_unpack_slots leaves the receiver's as it is.
+ * dst == src, handles that differ in model, geometry or device: SMC_EINVAL; either one without weights: SMC_ESTATE. */
 int smc_copy_from(smc_handle dst, smc_handle src, const uint8_t* mask /*[n_theta]*/);
 
 /* Proposals outside the prior's support: the reference never filters them (src/smc_samplers.jl:116).  Filters m with

@@ -945,6 +945,8 @@ class Handle:
         self.proposal_kind = int(kind)
 
     def set_streams(self, streams):
+        """the stream ids of the filters (smc_set_streams, which drops a pending window).  Ids equal to the ones this object set
+        last are not handed to the library: such a call changes nothing, a pending window included."""
         s = np.ascontiguousarray(streams, dtype=np.uint32)
         assert s.size == self.n_theta
         if getattr(self, "_streams_set", None) is not None and np.array_equal(self._streams_set, s):

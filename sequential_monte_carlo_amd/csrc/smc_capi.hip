@@ -416,6 +416,7 @@ extern "C" int smc_set_params(smc_handle h, const double* raw) {
         params_from_raw(h->model, raw + (size_t)m * nraw, P[m]);
         if (h->v.prop_kind) fill_proposal(h, m);
     }
+    h->win.k = 0;   // an uncommitted window belongs to the previous rows (include/smc_hip.h "pending window")
     HIPCHK(hipMemcpyAsync(h->d_params, P, (size_t)h->v.ntheta * sizeof(Params), hipMemcpyHostToDevice, h->stream));
     h->hot.prm0 = P[0];
     h->hot.prm_ok = true;
@@ -466,6 +467,7 @@ extern "C" int smc_set_proposal(smc_handle h, int kind, const double* par) {
 extern "C" int smc_set_streams(smc_handle h, const uint32_t* s) {
     if (!h || !s) return fail(SMC_EINVAL, "smc_set_streams: NULL argument");
     HIPCHK(hipSetDevice(h->device));
+    h->win.k = 0;   // an uncommitted window belongs to the previous stream ids
     HIPCHK(hipMemcpyAsync(h->d_stream, s, (size_t)h->v.ntheta * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->hot.stream0 = s[0];
@@ -494,6 +496,7 @@ extern "C" int smc_get_launch_geometry(smc_handle h, int* threads, int* np, int*
 extern "C" int smc_reseed(smc_handle h, uint64_t seed) {
     if (!h) return fail(SMC_EINVAL, "smc_reseed: NULL handle");
     h->v.seed = seed;
+    h->win.k = 0;        // an uncommitted window belongs to the old seed
     h->brk_count = 0;    // cached break points belong to the old seed
     return SMC_OK;
 }

@@ -143,6 +143,7 @@ extern "C" int smc_time_step_kernel(smc_handle h, const double* y, int64_t T, in
     if (!h->have_params) return fail(SMC_ESTATE, "smc_time_step_kernel: smc_set_params has not been called");
     if (history_armed(h)) return history_refuse("smc_time_step_kernel");
     if (series_has_gap(h, y, T)) return fail(SMC_EINVAL, "smc_time_step_kernel: the series holds a NaN and the handle reads NaN as missing (SMC_FLAG_NAN_MISSING); it times the ordinary step");
+    h->win.k = 0;   // an uncommitted window is dropped: the call runs a series of its own over the filters and the window's observations
     HIPCHK(hipSetDevice(h->device));
     int rc = ensure_y(h, T);
     if (rc) return rc;

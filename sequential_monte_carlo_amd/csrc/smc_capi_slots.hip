@@ -54,9 +54,9 @@ extern "C" int smc_permute(smc_handle h, const int32_t* a) {
     if (!h || !a) return fail(SMC_EINVAL, "smc_permute: NULL argument");
     if (!h->inited) return fail(SMC_ESTATE, "smc_permute: filter not initialised");
     if (history_armed(h)) return history_refuse("smc_permute");
-    h->win.k = 0;
     for (int m = 0; m < h->v.ntheta; ++m)
         if (a[m] < 0 || a[m] >= h->v.ntheta) return fail(SMC_EINVAL, "smc_permute: index out of range");
+    h->win.k = 0;   // (behind every refusal: a refused call leaves the handle as it was)
     HIPCHK(hipSetDevice(h->device));
     int rc = emit_if_needed(h);
     if (rc) return rc;
@@ -85,10 +85,10 @@ extern "C" int smc_copy_from(smc_handle dst, smc_handle src, const uint8_t* mask
     if (dst == src) return fail(SMC_EINVAL, "smc_copy_from: dst and src are the same handle");
     if (!dst->inited || !src->inited) return fail(SMC_ESTATE, "smc_copy_from: filter not initialised");
     if (history_armed(dst)) return history_refuse("smc_copy_from");
-    dst->win.k = 0;
     const FilterView &a = dst->v, &b = src->v;
     if (dst->model != src->model || a.n != b.n || a.seg != b.seg || a.ntheta != b.ntheta || dst->device != src->device)
         return fail(SMC_EINVAL, "smc_copy_from: handles differ in model, geometry or device");
+    dst->win.k = 0;   // (behind every refusal)
     HIPCHK(hipSetDevice(dst->device));
     int rc = emit_if_needed(dst);
     if (rc) return rc;
@@ -114,11 +114,11 @@ static int pack_unpack(smc_handle h, const int32_t* idx, int64_t k, void* buf, b
     if (!h || k < 0 || (k > 0 && (!idx || !buf))) return fail(SMC_EINVAL, "smc_pack/unpack_slots: bad argument");
     if (!h->inited) return fail(SMC_ESTATE, "smc_pack/unpack_slots: filter not initialised");
     if (!pack && history_armed(h)) return history_refuse("smc_unpack_slots");
-    if (!pack) h->win.k = 0;
-    if (k == 0) return SMC_OK;
-    if (!pack) hot_invalidate(h);   // slots written on the device (the exchange of smc_comm.hip ends here too)
     for (int64_t i = 0; i < k; ++i)
         if (idx[i] < 0 || idx[i] >= h->v.ntheta) return fail(SMC_EINVAL, "smc_pack/unpack_slots: index out of range");
+    if (!pack) h->win.k = 0;   // (behind every refusal: a refused call leaves the pending window and the by-value copies alone)
+    if (k == 0) return SMC_OK;
+    if (!pack) hot_invalidate(h);   // slots written on the device (the exchange of smc_comm.hip ends here too)
     HIPCHK(hipSetDevice(h->device));
     int rc = emit_if_needed(h);
     if (rc) return rc;
